@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the GMR retargeting hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path (target preprocessing + two-stage IK, time loop on device) over one batch of
 synthetic human-motion streams -> Unitree G1 (29-DoF).  Inputs are resident in HBM when a timed region starts; every
@@ -9,7 +9,8 @@ timed region is K steps after W warm-up steps, bracketed by a barrier + device s
 
 N = 1 (default)  `value` = BASELINE.json configs[1]: the 10k-frame batch, S=100 streams x T=100 frames (SURVEY.md
                  section 8d "Config 2"), with the roofline object of its kernel and the CPU baseline timed on this
-                 box's host cores.  Beside it, `strong_1m`: the 1M-frame batch of the multi-GPU leg on this one GPU.
+                 box's host cores.  Beside it, `strong_1m`: the 1M-frame batch of the multi-GPU leg on this one GPU
+                 (an extra, kept short: min(K, 5) timed steps, reported as `strong_1m.steps`).
 N > 1            one rank per GPU.  Either launched by `python -m torch.distributed.run` (the launcher only provides
                  RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*), or plainly as `python bench.py --gpus N`: with WORLD_SIZE
                  unset the process becomes the LAUNCHER -- it never loads the library or touches a GPU, starts N fresh
@@ -25,6 +26,15 @@ N > 1            one rank per GPU.  Either launched by `python -m torch.distribu
                  batch alone on its GPU in the same run: `value_1gpu`, `efficiency` = value / (N * value_1gpu).
                  `weak_leg`: configs[1]'s S=100 x T=100 per rank (its makespan is the slowest of 100 N streams: the
                  value falls with N from that statistical tail alone, no communication involved).
+
+--dump-outputs DIR  after every timed region, rank 0 writes what the LAST timed step of each leg left in its output
+                 buffers -- what a caller of `retarget_streams` receives -- as float64 `DIR/<leg>_<name>.npy`, <leg> =
+                 `configs1` (rank 0's batch) and `strong` (the whole 1M-frame batch): `qpos` [n, T, nq], `solves` [n, T, 2]
+                 (solver iterations per stage) and `streams` [n], the stream ids of the rows.  The per-stream status is not
+                 written: a stream that fails ends the run before any file exists, so it could only ever hold zeros.  A leg
+                 is written whole when it fits half of 64 MB, else as a fixed, seeded sample of its streams.  The inputs
+                 depend on the arguments alone (stream i of a batch is generated from seed + i), so the files of two
+                 builds run with the same arguments compare row for row.
 
 Prints ONE JSON line (rank 0).
 """
@@ -144,6 +154,7 @@ BYTES_PER_FRAME = {"unitree_g1": 1360}
 F_ITER_DENSE = {"unitree_g1": 1.77e5}
 F_ERR = {"unitree_g1": 2.1e3}
 METRIC = "retargeted frames/sec (whole node) + max joint-angle err vs CPU ref, G1 29-DoF"
+DUMP_BYTES_PER_LEG = 32 << 20  # --dump-outputs: two legs, 64 MB in all
 
 
 def self_launch(n: int, argv) -> int:
@@ -167,6 +178,17 @@ def load_standin():
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     return mod
+
+
+def sampled_outputs(leg, q, ns):
+    """--dump-outputs: the float64 arrays of one leg, {file stem: array}.  Whole streams only: all of them if they fit
+    DUMP_BYTES_PER_LEG, else a sample drawn with a fixed seed (the same rows in every run and every build)."""
+    S = q.shape[0]
+    per_stream = 8 * (q[0].size + ns[0].size + 1)
+    n = min(S, DUMP_BYTES_PER_LEG // per_stream)
+    ids = np.sort(np.random.default_rng(0).choice(S, size=n, replace=False))
+    return {f"{leg}_qpos": q[ids].astype(np.float64), f"{leg}_solves": ns[ids].astype(np.float64),
+            f"{leg}_streams": ids.astype(np.float64)}
 
 
 class Shard:
@@ -368,6 +390,7 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra-legs", action="store_true", help="N = 1: skip the e2e / configs[2..4] legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the outputs of the last timed step of each leg as DIR/*.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -454,6 +477,7 @@ def main():
     q_hip, ns_hip, st_hip = shard.results()
     assert (st_hip == 0).all(), "IK kernel reported a failed stream"
     shard.free()
+    dump = sampled_outputs("configs1", q_hip, ns_hip) if args.dump_outputs and rank == 0 else {}
 
     # ---- leg B: the 1M-frame batch, sharded over the ranks (and whole on rank 0) --------------------------------------
     sres = None
@@ -474,8 +498,10 @@ def main():
         sres = sharding.strong_scaling_leg(comm, lens, make_step, k_strong, min(args.warmup, 1),
                                            single_step if world > 1 else None, device_sync=device_sync)
         last = keep.get("all") or keep["mine"]
-        _, ns_s, st_s = last.results()
+        q_s, ns_s, st_s = last.results()
         assert (st_s == 0).all(), "IK kernel reported a failed stream (1M-frame leg)"
+        if args.dump_outputs and rank == 0:     # rank 0's last timed step ran the whole batch, at every N
+            dump.update(sampled_outputs("strong", q_s, ns_s))
         sres["steps"] = k_strong
         sres["mean_solves_per_frame"] = float(ns_s.sum()) / (last.S * last.T)
 
@@ -641,6 +667,10 @@ def main():
             out["max_joint_err_rad"] = float(np.abs(q_hip[..., 7:] - q_cpu[..., 7:]).max())
             out["max_root_pos_err_m"] = float(np.abs(q_hip[..., :3] - q_cpu[..., :3]).max())
             out["frames_with_different_solve_count"] = int((ns_hip != ns_cpu).any(axis=-1).sum())
+        if args.dump_outputs:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, a in dump.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
         print(json.dumps(out), flush=True)
 
     comm.barrier()

@@ -8,6 +8,7 @@ import subprocess
 import sys
 import time
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -64,6 +65,44 @@ def test_single_rank_line_is_the_configs1_line():
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert out["n_gpus"] == 1 and out["scaling"] == "weak" and "configs[1]" in out["config"]["workload"]
     assert "strong_1m" in out and "world_size" not in out
+
+
+DUMP_FILES = sorted(f"{leg}_{name}.npy" for leg in ("configs1", "strong") for name in ("qpos", "solves", "streams"))
+
+
+@pytest.mark.timeout(300)
+def test_dump_outputs_rank0_writes_both_legs(tmp_path):
+    """--dump-outputs: rank 0 alone writes, float64, its configs[1] batch and the WHOLE 1M-frame-leg batch (here 64 x 4),
+    rows labelled with their stream ids; the JSON line stays the one line."""
+    d = tmp_path / "dump"
+    r = _run(["--gpus", "2", "--dump-outputs", str(d)] + SMALL, "tcp")
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert len([ln for ln in r.stdout.splitlines() if ln.startswith("{")]) == 1
+    assert sorted(os.listdir(d)) == DUMP_FILES
+    a = {f[:-4]: np.load(d / f, allow_pickle=False) for f in DUMP_FILES}
+    assert all(v.dtype == np.float64 for v in a.values())
+    for leg, S, T in (("configs1", 6, 5), ("strong", 64, 4)):
+        assert a[f"{leg}_qpos"].shape == (S, T, 36) and a[f"{leg}_solves"].shape == (S, T, 2)
+        assert np.array_equal(a[f"{leg}_streams"], np.arange(S))
+
+
+def test_dump_outputs_samples_a_large_leg_with_a_fixed_seed():
+    """A leg larger than its half of 64 MB is written as whole streams drawn with a fixed seed: the same rows every time."""
+    import bench
+    S, T, nq = 20000, 8, 36                                            # 46 MB of qpos
+    q = np.broadcast_to(np.arange(S, dtype=np.float64)[:, None, None], (S, T, nq))
+    ns = np.broadcast_to(np.arange(S, dtype=np.int32)[:, None, None], (S, T, 2))
+    a = bench.sampled_outputs("leg", q, ns)
+    b = bench.sampled_outputs("leg", q, ns)
+    assert sorted(a) == ["leg_qpos", "leg_solves", "leg_streams"]
+    assert all(v.dtype == np.float64 and np.array_equal(v, b[k]) for k, v in a.items())
+    ids = a["leg_streams"]
+    n = len(ids)
+    assert sum(v.nbytes for v in a.values()) <= 32 << 20 < (n + 1) * 8 * (T * (nq + 2) + 1)      # as many streams as fit
+    assert np.all(np.diff(ids) > 0) and 0 <= ids[0] and ids[-1] < S
+    assert not np.array_equal(ids, np.arange(n))                        # a sample of the batch, not its head
+    assert np.array_equal(a["leg_qpos"][:, 0, 0], ids) and np.array_equal(a["leg_solves"][:, 0, 0], ids)
+    assert a["leg_qpos"].shape == (n, T, nq) and a["leg_solves"].shape == (n, T, 2)
 
 
 @pytest.mark.timeout(120)

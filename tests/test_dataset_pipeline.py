@@ -134,12 +134,13 @@ def test_loading_retargeting_and_writing_overlap(tmp_path):
 
 def test_cli_launches_its_own_ranks_and_shards_the_folder(tmp_path):
     """`python -m ...dataset --gpus 2` without a launcher: two rank processes, the folder LPT-sharded, one summary line from
-    rank 0.  (No GPU here: the run stops at the communicator's device requirement -- what is checked is that the launcher
-    starts the ranks and reports the failure of a rank cleanly instead of hanging.)"""
+    rank 0.  (No GPU for the ranks, also where the host has one: HIP_VISIBLE_DEVICES hides it.  The run stops at the
+    communicator's device requirement -- what is checked is that the launcher starts the ranks and reports the failure of
+    a rank cleanly instead of hanging.)"""
     import subprocess
     import sys
     src = _tree(tmp_path, [5, 6, 7])
-    env = dict(os.environ, GMR_COMM_TIMEOUT="20", GMR_DATASET_TIMEOUT="120")
+    env = dict(os.environ, GMR_COMM_TIMEOUT="20", GMR_DATASET_TIMEOUT="120", HIP_VISIBLE_DEVICES="-1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

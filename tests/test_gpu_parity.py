@@ -608,6 +608,30 @@ def test_library_and_torch_share_one_hip_runtime():
 
 
 @pytest.mark.gpu
+def test_bench_dump_outputs_are_the_outputs_of_the_timed_path(oracle, g1, tmp_path):
+    """bench.py --dump-outputs: the files of a small run are the oracle's results on the batches its arguments name
+    (stream i of a batch is generated from seed + i; the 1M-frame leg's batch uses seed + 1 000 003), both legs."""
+    import subprocess
+    import sys
+    from general_motion_retargeting_amd import synth
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "GMR_BENCH_STANDIN")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--streams", "6",
+                        "--frames", "5", "--strong-streams", "64", "--strong-frames", "4", "--seed", "3", "--no-cpu-baseline",
+                        "--no-extra-legs", "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    for leg, S, T, seed in (("configs1", 6, 5, 3), ("strong", 64, 4, 3 + 1_000_003)):
+        human, q0 = synth.make_streams(g1.model, g1.tt, S, T, seed=seed)
+        q_o, ns_o, st_o = oracle.retarget_streams(g1.mb, g1.ts, q0, human)
+        q, ns, ids = (np.load(tmp_path / f"{leg}_{n}.npy", allow_pickle=False) for n in ("qpos", "solves", "streams"))
+        assert q.dtype == ns.dtype == ids.dtype == np.float64
+        assert np.array_equal(ids, np.arange(S)) and (st_o == 0).all()
+        assert np.array_equal(ns, ns_o), "solver-iteration counts differ"
+        joint, pos, rot = _compare(q, q_o)
+        assert joint <= TOL_RAD and pos <= TOL_POS and rot <= TOL_RAD, (leg, joint, pos, rot)
+
+
+@pytest.mark.gpu
 def test_robot_promoted_to_larger_size_class(hip, oracle, tmp_path):
     """LDS offsets are compile-time constants of a size class (csrc/gmr_ik_layout.h: NVP 28/32/36/48 with body /
     task / pair capacities).  A robot with few dofs but more bodies than its class holds (nv = 16 -> class 28,
