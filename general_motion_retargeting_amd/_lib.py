@@ -17,6 +17,7 @@ _lib = None
 
 FLAG_OFFSET_TO_GROUND = 1
 FLAG_EVAL_ONLY = 2
+POST_HEIGHT_ADJUST, POST_ROOT_ORIGIN_OFFSET = 1, 2
 STATUS_OK, STATUS_QP_FAILED, STATUS_QP_MAXITER = 0, -1, -2
 
 
@@ -70,6 +71,8 @@ _SIGS = {
     "gmr_fk_segment_min_z_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "gmr_fk_batch_segments": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                         C.c_void_p]),
+    "gmr_postprocess_clips_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gmr_smplx_create": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "gmr_smplx_destroy": (C.c_int, [C.c_void_p]),
     "gmr_smplx_rows": (C.c_int, [C.c_void_p]),
@@ -256,6 +259,11 @@ class Job(C.Structure):
     _fields_ = [("solver", C.c_void_p), ("S", C.c_int32), ("T", C.c_int32), ("q0", C.c_void_p), ("human", C.c_void_p),
                 ("len", C.c_void_p), ("q_out", C.c_void_p), ("nsolve", C.c_void_p), ("status", C.c_void_p),
                 ("tgt_out", C.c_void_p), ("err_out", C.c_void_p)]
+
+
+class PostSrc(C.Structure):
+    """``gmr_post_src_t``: one IK job's output as a source of :meth:`FkHandle.postprocess_clips_dev`."""
+    _fields_ = [("S", C.c_int32), ("T", C.c_int32), ("q_out", C.c_void_p), ("len", C.c_void_p)]
 
 
 def _addr(x):
@@ -503,6 +511,20 @@ class FkHandle:
     def fk_dev(self, B, d_root_pos, d_root_rot, d_dof, d_body_pos, d_body_rot=None, d_min_z=None, stream=None):
         check(lib().gmr_fk_batch_dev(self.handle, int(B), _d(d_root_pos), _d(d_root_rot), _d(d_dof), _d(d_body_pos),
                                      _d(d_body_rot), _d(d_min_z), _s(stream)))
+
+    def postprocess_clips_dev(self, sources, d_seg_start, C_clips, B, d_root_pos, d_root_rot, d_dof_pos, d_local_body_pos,
+                              d_lowest=None, height_adjust=True, root_origin_offset=True, ground_offset=0.0, stream=None):
+        """``gmr_postprocess_clips_dev``: the five pkl arrays of ``B`` frames in ``C_clips`` clips straight from IK outputs on the
+        device.  ``sources`` = list of ``(S, T, d_q_out, d_len or None)``, one per IK job, clips numbered in this order;
+        ``d_seg_start`` i32[C + 1] = exclusive prefix sum of the clip lengths.  Device pointers (DeviceBuffer or raw);
+        asynchronous on ``stream``."""
+        arr = (PostSrc * max(len(sources), 1))()
+        for i, (S, T, d_q, d_len) in enumerate(sources):
+            arr[i] = PostSrc(int(S), int(T), _addr(d_q), _addr(d_len))
+        flags = (POST_HEIGHT_ADJUST if height_adjust else 0) | (POST_ROOT_ORIGIN_OFFSET if root_origin_offset else 0)
+        check(lib().gmr_postprocess_clips_dev(self.handle, C.cast(arr, C.c_void_p), len(sources), self.ndof + 7, _d(d_seg_start),
+                                              int(C_clips), int(B), flags, float(ground_offset), _d(d_root_pos), _d(d_root_rot),
+                                              _d(d_dof_pos), _d(d_local_body_pos), _d(d_lowest), _s(stream)))
 
     def close(self):
         if self.handle:

@@ -8,6 +8,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <mutex>
 #include <new>
 #include <vector>
 
@@ -16,6 +17,7 @@
 #include "gmr_ik_layout.h"
 #include "gmr_ik_wide_layout.h"
 #include "gmr_internal.h"
+#include "gmr_post.h"
 
 static_assert(sizeof(gmr_model_t) % 8 == 0, "gmr_model_t must be 8-byte sized");
 static_assert(sizeof(gmr_taskset_t) % 8 == 0, "gmr_taskset_t must be 8-byte sized");
@@ -45,6 +47,11 @@ extern "C" hipError_t gmr_launch_fk_batch(const gmr::FkTree*, const gmr::FkTree*
                                           float*, float*, float*, float*, hipStream_t);
 extern "C" int gmr_fk_blocks(int B);
 extern "C" hipError_t gmr_launch_fk_segment_min(const float*, int, const int32_t*, int, float*, hipStream_t);
+extern "C" hipError_t gmr_launch_fk_qpos(const gmr::FkTree*, const gmr::FkTree*, int, const double* const*, int, float*, hipStream_t);
+extern "C" hipError_t gmr_launch_post_row_map(const gmr::PostSources*, const int32_t*, int, int, int, const double**, int32_t*,
+                                              int32_t*, hipStream_t);
+extern "C" hipError_t gmr_launch_post_gather(const double* const*, const int32_t*, const int32_t*, const float*, int, int, int, double,
+                                             double*, double*, double*, hipStream_t);
 
 // up to this many streams a launch uses the 4-wave (main + 3 helpers) shape; measured crossover on MI355X
 // (tools/shape_sweep.py, G1): S=256 1.04M vs 0.93M frames/s, S=384 1.24M vs 1.40M (NW=4 vs NW=1): the switch
@@ -98,6 +105,16 @@ struct gmr_fk {
   gmr::FkTree* d_tree = nullptr;
   float* d_min_part = nullptr;
   int min_part_cap = 0;
+  // gmr_postprocess_clips_dev: one grow-only scratch block per HIP stream that has called.  Work that still reads a block
+  // was enqueued on the block's own stream, so growing it waits for that stream alone and never frees memory another
+  // stream's kernels use; post_mu orders the host side (lookup, growth, the launches of one call).
+  struct PostWs {
+    hipStream_t stream;
+    char* d;
+    size_t bytes;
+  };
+  std::mutex post_mu;
+  std::vector<PostWs> post_ws;
 };
 
 extern "C" {
@@ -839,6 +856,8 @@ int gmr_fk_destroy(gmr_fk_t* k) {
   if (!k) return GMR_OK;
   (void)hipFree(k->d_tree);
   if (k->d_min_part) (void)hipFree(k->d_min_part);
+  for (auto& w : k->post_ws)
+    if (w.d) (void)hipFree(w.d);          // (hipFree waits for the device: nothing of this handle is in flight afterwards)
   delete k;
   return GMR_OK;
 }
@@ -944,6 +963,78 @@ int gmr_fk_batch_segments(gmr_fk_t* k, int B, const float* root_pos, const float
   }
   (void)hipFree(d);
   return rc;
+}
+
+// ---- the dataset drivers' post-processing on the device (gmr_post.hip) ------------------------------------------------
+int gmr_postprocess_clips_dev(gmr_fk_t* k, const gmr_post_src_t* src, int nsrc, int nq, const int32_t* d_seg_start, int C, int B,
+                              int flags, double ground_offset, double* d_root_pos, double* d_root_rot, double* d_dof_pos,
+                              float* d_local_body_pos, float* d_lowest, void* stream) {
+  if (!k) return fail(GMR_ERR_ARG, "null fk handle");
+  if (nsrc < 0 || nsrc > gmr::POST_MAX_SRC || (nsrc > 0 && !src)) return fail(GMR_ERR_ARG, "bad source list (at most %d sources)", gmr::POST_MAX_SRC);
+  if (nq != 7 + k->tree.ndof) return fail(GMR_ERR_ARG, "nq = %d, but this tree has %d dofs (nq = %d)", nq, k->tree.ndof, 7 + k->tree.ndof);
+  if (C < 0 || B < 0) return fail(GMR_ERR_ARG, "negative C / B");
+  if (flags & ~(GMR_POST_HEIGHT_ADJUST | GMR_POST_ROOT_ORIGIN_OFFSET)) return fail(GMR_ERR_ARG, "unknown flag bits 0x%x", flags);
+  gmr::PostSources ps;
+  memset(&ps, 0, sizeof ps);
+  ps.nsrc = nsrc;
+  long long clips = 0, rows = 0;
+  for (int i = 0; i < nsrc; i++) {
+    if (src[i].S < 0 || src[i].T < 0) return fail(GMR_ERR_ARG, "source %d: negative S/T", i);
+    if (src[i].S > 0 && (src[i].T < 1 || !src[i].q_out)) return fail(GMR_ERR_ARG, "source %d: S = %d streams need T >= 1 and q_out", i, src[i].S);
+    ps.clip0[i] = (int32_t)clips;
+    ps.T[i] = src[i].T;
+    ps.q_out[i] = src[i].q_out;
+    ps.len[i] = src[i].len;
+    clips += src[i].S;
+    rows += (long long)src[i].S * src[i].T;
+    if (clips > INT32_MAX) return fail(GMR_ERR_ARG, "too many clips");
+  }
+  for (int i = nsrc; i <= gmr::POST_MAX_SRC; i++) ps.clip0[i] = (int32_t)clips;
+  if (clips != C) return fail(GMR_ERR_ARG, "C = %d, but the sources hold %lld clips", C, clips);
+  if (B > rows) return fail(GMR_ERR_ARG, "B = %d rows, but the sources hold only %lld", B, rows);
+  if (C == 0) return GMR_OK;
+  if (!d_seg_start) return fail(GMR_ERR_ARG, "null seg_start");
+  if (B > 0 && (!d_root_pos || !d_root_rot || !d_local_body_pos || (k->tree.ndof > 0 && !d_dof_pos))) return fail(GMR_ERR_ARG, "null output buffer");
+  const bool height = flags & GMR_POST_HEIGHT_ADJUST;
+  if (B == 0 && !(height && d_lowest)) return GMR_OK;
+  // scratch: row_q [B] pointers, row_clip [B], seg_clamped [C + 1], lowest [C] (when the caller does not want it), and the
+  // world pass's body_pos [B][nbody][3]
+  auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+  const size_t o_rq = 0, o_rc = o_rq + up((size_t)B * 8), o_sc = o_rc + up((size_t)B * 4), o_lo = o_sc + up((size_t)(C + 1) * 4),
+               o_bp = o_lo + up((size_t)C * 4), total = o_bp + (height ? up((size_t)B * k->tree.nbody * 12) : 0);
+  hipStream_t st = (hipStream_t)stream;
+  std::lock_guard<std::mutex> lock(k->post_mu);
+  gmr_fk::PostWs* w = nullptr;
+  for (auto& e : k->post_ws)
+    if (e.stream == st) w = &e;
+  if (!w) {
+    k->post_ws.push_back(gmr_fk::PostWs{st, nullptr, 0});
+    w = &k->post_ws.back();
+  }
+  if (w->bytes < total) {
+    if (w->d) {
+      HIP_TRY(hipStreamSynchronize(st));      // earlier calls on this stream are the only users of the block
+      HIP_TRY(hipFree(w->d));
+      w->d = nullptr;
+      w->bytes = 0;
+    }
+    const size_t want = total + total / 4;
+    HIP_TRY(hipMalloc((void**)&w->d, want));
+    w->bytes = want;
+  }
+  char* d = w->d;
+  const double** row_q = (const double**)(d + o_rq);
+  int32_t* row_clip = (int32_t*)(d + o_rc);
+  int32_t* seg_clamped = (int32_t*)(d + o_sc);
+  float* lowest = d_lowest ? d_lowest : (float*)(d + o_lo);
+  HIP_TRY(gmr_launch_post_row_map(&ps, d_seg_start, C, B, nq, row_q, row_clip, seg_clamped, st));
+  if (height) {
+    HIP_TRY(gmr_launch_fk_qpos(k->d_tree, &k->tree, B, row_q, 1, (float*)(d + o_bp), st));
+    HIP_TRY(gmr_launch_fk_segment_min((const float*)(d + o_bp), k->tree.nbody, seg_clamped, C, lowest, st));
+  }
+  HIP_TRY(gmr_launch_fk_qpos(k->d_tree, &k->tree, B, row_q, 0, d_local_body_pos, st));
+  HIP_TRY(gmr_launch_post_gather(row_q, row_clip, seg_clamped, lowest, B, nq, flags, ground_offset, d_root_pos, d_root_rot, d_dof_pos, st));
+  return GMR_OK;
 }
 
 }  // extern "C"

@@ -204,11 +204,48 @@ __device__ __forceinline__ void fk_body(const FkBodyRec& cur, float ang, f4 prot
 
 constexpr int FK_BLOCK = 64;  // one wave per block
 
-template <bool STAGED>
-__global__ __launch_bounds__(FK_BLOCK) void fk_batch_kernel(const FkTree* __restrict__ tree, int B,
-                                                            const float* __restrict__ root_pos,
-                                                            const float* __restrict__ root_rot,
-                                                            const float* __restrict__ dof,
+// Where a lane's root pose and joint angles come from.  The kernels below are written once against this interface; only
+// the loads at their top differ between the instantiations, the per-body code, the LDS staging and the flush are shared.
+struct FkSrcF32 {      // gmr_fk_batch_dev: three float32 arrays indexed by frame
+  const float* __restrict__ root_pos;
+  const float* __restrict__ root_rot;
+  const float* __restrict__ dof;
+  struct Lane {
+    const float* rp;
+    const float* rr;
+    const float* d;
+    __device__ __forceinline__ float ang(int k) const { return d[k]; }
+    __device__ __forceinline__ void root(float& px, float& py, float& pz, f4& rot) const {
+      px = rp[0]; py = rp[1]; pz = rp[2];
+      rot = f4{rr[0], rr[1], rr[2], rr[3]};
+    }
+  };
+  __device__ __forceinline__ Lane lane(long long fc, int ndof) const { return Lane{root_pos + fc * 3, root_rot + fc * 4, dof + fc * ndof}; }
+};
+// gmr_postprocess_clips_dev: frame b is the float64 qpos row row_q[b] of an IK launch's output, read where it lies
+// (root position, root quaternion wxyz, joint angles), each value rounded to float32 as the dataset scripts' `.float()` does
+// (smplx_to_robot_dataset.py:106-121).  WORLD = false: the identity root of `local_body_pos` (:106-112).
+template <bool WORLD>
+struct FkSrcQpos {
+  const double* const* __restrict__ row_q;
+  struct Lane {
+    const double* q;
+    __device__ __forceinline__ float ang(int k) const { return (float)q[7 + k]; }
+    __device__ __forceinline__ void root(float& px, float& py, float& pz, f4& rot) const {
+      if (WORLD) {
+        px = (float)q[0]; py = (float)q[1]; pz = (float)q[2];
+        rot = f4{(float)q[4], (float)q[5], (float)q[6], (float)q[3]};
+      } else {
+        px = 0.0f; py = 0.0f; pz = 0.0f;
+        rot = f4{0.0f, 0.0f, 0.0f, 1.0f};
+      }
+    }
+  };
+  __device__ __forceinline__ Lane lane(long long fc, int) const { return Lane{row_q[fc]}; }
+};
+
+template <bool STAGED, class Src>
+__global__ __launch_bounds__(FK_BLOCK) void fk_batch_kernel(const FkTree* __restrict__ tree, int B, const Src src,
                                                             float* __restrict__ body_pos,
                                                             float* __restrict__ body_rot,
                                                             float* __restrict__ min_part) {
@@ -222,6 +259,7 @@ __global__ __launch_bounds__(FK_BLOCK) void fk_batch_kernel(const FkTree* __rest
   const long long f = (long long)blockIdx.x * FK_BLOCK + tid;
   const bool on = f < B;
   const long long fc = on ? f : 0;
+  const typename Src::Lane in = src.lane(fc, ndof);
   const int SW = STAGED ? 4 : 7;
   float* stk = fsm + tid;
   const int row = nb * 3;
@@ -238,14 +276,14 @@ __global__ __launch_bounds__(FK_BLOCK) void fk_batch_kernel(const FkTree* __rest
     // -> the vector L1 thrashes, 12x the L2 reads, 42 % of the wave's cycles waiting: profiles/r02_fk_*.)
     // Every lane reads ITS row, all loads issued back to back (independent: one trip to L2, each line fetched once
     // while its 29 users are in flight), and parks the values in its own staging row -- no cross-lane traffic.
-    const float* drow0 = dof + fc * ndof;
     float* orow = outb + tid * row;
 #pragma unroll 8
-    for (int d = 0; d < ndof; d++) orow[3 * tree->dof_body[d]] = drow0[d];
+    for (int d = 0; d < ndof; d++) orow[3 * tree->dof_body[d]] = in.ang(d);
   }
   {
-    float px = root_pos[fc * 3], py = root_pos[fc * 3 + 1], pz = root_pos[fc * 3 + 2];
-    f4 rot = {root_rot[fc * 4], root_rot[fc * 4 + 1], root_rot[fc * 4 + 2], root_rot[fc * 4 + 3]};
+    float px, py, pz;
+    f4 rot;
+    in.root(px, py, pz, rot);
     cpx = px; cpy = py; cpz = pz; crot = rot;
     if (tree->save_slot[0] >= 0 && SW > 0) {
       float* sl = stk + tree->save_slot[0] * SW * FK_BLOCK;
@@ -264,7 +302,6 @@ __global__ __launch_bounds__(FK_BLOCK) void fk_batch_kernel(const FkTree* __rest
       zmin = pz;
     }
   }
-  const float* drow = dof + fc * ndof;
   FkBodyRec nxt = tree->rec[nb > 1 ? 1 : 0];
   float ang_nxt = STAGED ? (outb + tid * row)[3] : 0.0f;     // parked joint angle of body 1 (garbage if it has no joint: unused)
   for (int j = 1; j < nb; j++) {
@@ -291,7 +328,7 @@ __global__ __launch_bounds__(FK_BLOCK) void fk_batch_kernel(const FkTree* __rest
     }
     float wx, wy, wz;
     f4 rot;
-    fk_body(cur, STAGED ? ang : ((cur.meta & 1u) ? drow[cur.dof_idx] : 0.0f), prot, wx, wy, wz, rot);
+    fk_body(cur, STAGED ? ang : ((cur.meta & 1u) ? in.ang(cur.dof_idx) : 0.0f), prot, wx, wy, wz, rot);
     float px = ppx + wx, py = ppy + wy, pz = ppz + wz;
     cpx = px; cpy = py; cpz = pz; crot = rot;
     if (dst >= 0 && SW > 0) {
@@ -364,10 +401,8 @@ __global__ __launch_bounds__(FK_BLOCK) void fk_batch_kernel(const FkTree* __rest
 // four it is 5 per SIMD walking ~12.  Parents that are not the body walked just before come from per-wavefront slots
 // (position and rotation): no wavefront reads what another one wrote before the final barrier.
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64 * FK_MAX_WAVES) void fk_split_kernel(const FkTree* __restrict__ tree, int B,
-                                                                     const float* __restrict__ root_pos,
-                                                                     const float* __restrict__ root_rot,
-                                                                     const float* __restrict__ dof,
+template <class Src>
+__global__ __launch_bounds__(64 * FK_MAX_WAVES) void fk_split_kernel(const FkTree* __restrict__ tree, int B, const Src src,
                                                                      float* __restrict__ body_pos,
                                                                      float* __restrict__ body_rot,
                                                                      float* __restrict__ min_part) {
@@ -388,7 +423,7 @@ __global__ __launch_bounds__(64 * FK_MAX_WAVES) void fk_split_kernel(const FkTre
   //  multiply-add, a quarter-rate instruction)
   const unsigned orow_i = (unsigned)(tree->nslot_split * 7 * 64) + (unsigned)(tid * row);
   const unsigned rrow_i = (unsigned)(tree->nslot_split * 7 * 64 + 64 * row) + (unsigned)(tid * rrow);
-  const float* drow = dof + fc * ndof;
+  const typename Src::Lane in = src.lane(fc, ndof);
   const int i0 = tree->wave_start[wave], i1 = tree->wave_start[wave + 1];
   float zmin = INFINITY;
   // Every joint angle this wavefront needs, read from the lane's dof row in ONE batch -- all loads issued back to back,
@@ -398,8 +433,9 @@ __global__ __launch_bounds__(64 * FK_MAX_WAVES) void fk_split_kernel(const FkTre
   // each -- the compiler could not batch them -- : a quarter of a block's lifetime was that serial chain.  Measured and
   // not kept: the block's 64 dof rows as ONE coalesced read by all wavefronts, scattered to the parking places, then a
   // barrier -- 0.230 against 0.207 ms: the per-lane loads are not what the block waits for, the extra barrier is felt.)
-  const float rpx = root_pos[fc * 3], rpy = root_pos[fc * 3 + 1], rpz = root_pos[fc * 3 + 2];
-  const f4 rrot = {root_rot[fc * 4], root_rot[fc * 4 + 1], root_rot[fc * 4 + 2], root_rot[fc * 4 + 3]};
+  float rpx, rpy, rpz;
+  f4 rrot;
+  in.root(rpx, rpy, rpz, rrot);
   {
     const uint32_t* pk = tree->wave_park[wave];
     for (int c = 0; c < 32; c += 16) {
@@ -409,7 +445,7 @@ __global__ __launch_bounds__(64 * FK_MAX_WAVES) void fk_split_kernel(const FkTre
       if (w[0] == 0xffffffffu) break;
       float a[16];
 #pragma unroll
-      for (int k = 0; k < 16; k++) a[k] = w[k] != 0xffffffffu ? drow[w[k] & 0xffffu] : 0.0f;
+      for (int k = 0; k < 16; k++) a[k] = w[k] != 0xffffffffu ? in.ang((int)(w[k] & 0xffffu)) : 0.0f;
 #pragma unroll
       for (int k = 0; k < 16; k++)
         if (w[k] != 0xffffffffu) *((w[k] >> 31) ? xtra + 64 * ((w[k] >> 16) & 0x7fffu) : orow + (w[k] >> 16)) = a[k];
@@ -566,25 +602,26 @@ extern "C" hipError_t gmr_launch_fk_segment_min(const float* d_body_pos, int nbo
 extern "C" int gmr_fk_blocks(int B) { return (B + gmr::FK_BLOCK - 1) / gmr::FK_BLOCK; }
 
 // > 64 KB of dynamic LDS needs an opt-in per kernel and per DEVICE: done once for every device this process uses
+template <class Src>
 static hipError_t fk_opt_in_large_lds() {
   static unsigned long long done_mask = 0;       // bit = device ordinal (benign if two threads race: the call is idempotent)
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
   if (e != hipSuccess) return e;
   if (dev < 64 && ((done_mask >> dev) & 1ull)) return hipSuccess;
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(gmr::fk_batch_kernel<true>),
+  e = hipFuncSetAttribute(reinterpret_cast<const void*>(gmr::fk_batch_kernel<true, Src>),
                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
   if (e == hipSuccess)
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(gmr::fk_split_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(gmr::fk_split_kernel<Src>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             160 * 1024 - 1024);
   if (e == hipSuccess && dev < 64) __atomic_fetch_or(&done_mask, 1ull << dev, __ATOMIC_RELAXED);
   return e;
 }
 
-extern "C" hipError_t gmr_launch_fk_batch(const gmr::FkTree* d_tree, const gmr::FkTree* h_tree, int B,
-                                          const float* d_root_pos, const float* d_root_rot, const float* d_dof,
-                                          float* d_body_pos, float* d_body_rot, float* d_min_part, float* d_min_z,
-                                          hipStream_t stream) {
+// the choice of kernel for a tree and a destination, the same for every source of frames
+template <class Src>
+static hipError_t fk_launch(const gmr::FkTree* d_tree, const gmr::FkTree* h_tree, int B, const Src src, float* d_body_pos,
+                            float* d_body_rot, float* d_min_part, float* d_min_z, hipStream_t stream) {
   if (B <= 0) return hipSuccess;
   const int nbody = h_tree->nbody, nslot = h_tree->nslot;
   const int blocks = gmr_fk_blocks(B);
@@ -597,7 +634,7 @@ extern "C" hipError_t gmr_launch_fk_batch(const gmr::FkTree* d_tree, const gmr::
   if (staged) {
     // staged variant: parent positions are re-read from the staging area; only rotations are parked
     smem = (size_t)nslot * 4 * gmr::FK_BLOCK * sizeof(float) + stage_bytes;
-    if (smem > 64 * 1024 && fk_opt_in_large_lds() != hipSuccess) {   // no opt-in on this device: the direct variant still works
+    if (smem > 64 * 1024 && fk_opt_in_large_lds<Src>() != hipSuccess) {   // no opt-in on this device: the direct variant still works
       (void)hipGetLastError();
       staged = false;
       smem = (size_t)nslot * 7 * gmr::FK_BLOCK * sizeof(float);
@@ -605,15 +642,15 @@ extern "C" hipError_t gmr_launch_fk_batch(const gmr::FkTree* d_tree, const gmr::
   }
   // several wavefronts per block when the tree splits (gmr_fk_create) and the slots of the split walk fit beside the staging area
   const size_t smem_split = (size_t)h_tree->nslot_split * 7 * 64 * sizeof(float) + stage_bytes + (size_t)h_tree->nextra * 64 * sizeof(float);
-  if (staged && h_tree->nwave > 1 && smem_split <= 160 * 1024 - 8192 && (smem_split <= 64 * 1024 || fk_opt_in_large_lds() == hipSuccess))
-    hipLaunchKernelGGL(gmr::fk_split_kernel, dim3(blocks), dim3(64 * h_tree->nwave), smem_split, stream, d_tree, B,
-                       d_root_pos, d_root_rot, d_dof, d_body_pos, d_body_rot, d_min_z ? d_min_part : nullptr);
+  if (staged && h_tree->nwave > 1 && smem_split <= 160 * 1024 - 8192 && (smem_split <= 64 * 1024 || fk_opt_in_large_lds<Src>() == hipSuccess))
+    hipLaunchKernelGGL(gmr::fk_split_kernel<Src>, dim3(blocks), dim3(64 * h_tree->nwave), smem_split, stream, d_tree, B, src,
+                       d_body_pos, d_body_rot, d_min_z ? d_min_part : nullptr);
   else if (staged)
-    hipLaunchKernelGGL(gmr::fk_batch_kernel<true>, dim3(blocks), dim3(gmr::FK_BLOCK), smem, stream, d_tree, B,
-                       d_root_pos, d_root_rot, d_dof, d_body_pos, d_body_rot, d_min_z ? d_min_part : nullptr);
+    hipLaunchKernelGGL((gmr::fk_batch_kernel<true, Src>), dim3(blocks), dim3(gmr::FK_BLOCK), smem, stream, d_tree, B, src,
+                       d_body_pos, d_body_rot, d_min_z ? d_min_part : nullptr);
   else
-    hipLaunchKernelGGL(gmr::fk_batch_kernel<false>, dim3(blocks), dim3(gmr::FK_BLOCK), smem, stream, d_tree, B,
-                       d_root_pos, d_root_rot, d_dof, d_body_pos, d_body_rot, d_min_z ? d_min_part : nullptr);
+    hipLaunchKernelGGL((gmr::fk_batch_kernel<false, Src>), dim3(blocks), dim3(gmr::FK_BLOCK), smem, stream, d_tree, B, src,
+                       d_body_pos, d_body_rot, d_min_z ? d_min_part : nullptr);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   if (d_min_z) {
@@ -621,4 +658,20 @@ extern "C" hipError_t gmr_launch_fk_batch(const gmr::FkTree* d_tree, const gmr::
     e = hipGetLastError();
   }
   return e;
+}
+
+extern "C" hipError_t gmr_launch_fk_batch(const gmr::FkTree* d_tree, const gmr::FkTree* h_tree, int B,
+                                          const float* d_root_pos, const float* d_root_rot, const float* d_dof,
+                                          float* d_body_pos, float* d_body_rot, float* d_min_part, float* d_min_z,
+                                          hipStream_t stream) {
+  return fk_launch(d_tree, h_tree, B, gmr::FkSrcF32{d_root_pos, d_root_rot, d_dof}, d_body_pos, d_body_rot, d_min_part, d_min_z,
+                   stream);
+}
+
+// positions of the B frames whose float64 qpos rows d_row_q[b] points at (gmr_post.hip), with their own root (world != 0)
+// or the identity root
+extern "C" hipError_t gmr_launch_fk_qpos(const gmr::FkTree* d_tree, const gmr::FkTree* h_tree, int B, const double* const* d_row_q,
+                                         int world, float* d_body_pos, hipStream_t stream) {
+  if (world) return fk_launch(d_tree, h_tree, B, gmr::FkSrcQpos<true>{d_row_q}, d_body_pos, nullptr, nullptr, nullptr, stream);
+  return fk_launch(d_tree, h_tree, B, gmr::FkSrcQpos<false>{d_row_q}, d_body_pos, nullptr, nullptr, nullptr, stream);
 }

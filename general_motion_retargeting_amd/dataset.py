@@ -10,6 +10,9 @@ The SMPL-X script has both adjustments on, the BVH script both off (``bvh_to_rob
 """
 from __future__ import annotations
 
+import os
+import threading
+import weakref
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -73,6 +76,181 @@ def postprocess_clips(qpos_list: Sequence[np.ndarray], km: KinematicsModel, fps:
     return out
 
 
+# ----------------------------------------------------------------------------------------------
+# The same post-processing ON THE DEVICE (``gmr_postprocess_clips_dev``): the IK launch's output never leaves the GPU, the
+# five pkl arrays of the whole batch come back in one asynchronous copy into page-locked memory, and the motion dicts are
+# VIEWS of that block.  ``GMR_DATASET_POST=host`` (or no GPU) keeps :func:`postprocess_clips`; the bytes are the same.
+# ----------------------------------------------------------------------------------------------
+def post_path() -> str:
+    """``"device"`` or ``"host"``: which post-processing the drivers take (environment switch ``GMR_DATASET_POST``)."""
+    from . import _lib
+    if os.environ.get("GMR_DATASET_POST", "device").strip().lower() == "host":
+        return "host"
+    try:
+        return "device" if _lib.lib().gmr_device_count() > 0 else "host"
+    except Exception:  # noqa: BLE001 -- no library, no device: the host path says so itself
+        return "host"
+
+
+class PinnedPool:
+    """Page-locked output blocks for batches whose results are handed out as views.  A block is taken for one batch; it
+    comes back when the LAST array viewing it has died (a finalizer on the buffer the arrays are views of), so a dict kept
+    by the caller or waiting for a writer thread never aliases memory a later batch writes.  A new block is locked only
+    when no free one is large enough.  ``alloc(nbytes)`` -> object with ``.ptr`` (``c_void_p``) and ``.nbytes``."""
+
+    def __init__(self, alloc=None, keep: int = 8):
+        self._alloc, self._keep = alloc, int(keep)
+        self._free: List = []
+        self._lock = threading.Lock()
+        self.blocks_allocated = 0
+
+    def take(self, nbytes: int):
+        """a ``ctypes`` char buffer of at least ``nbytes`` bytes; ``np.frombuffer`` views of it keep the block out of the pool"""
+        import ctypes as C
+        need = max(int(nbytes), 8)
+        with self._lock:
+            fit = [o for o in self._free if o.nbytes >= need]
+            owner = min(fit, key=lambda o: o.nbytes) if fit else None
+            if owner is not None:
+                self._free.remove(owner)
+        if owner is None:
+            if self._alloc is None:
+                from . import _lib
+                self._alloc = _lib._PinnedOwner
+            owner = self._alloc(need + need // 4)
+            self.blocks_allocated += 1
+        buf = (C.c_char * owner.nbytes).from_address(owner.ptr.value)
+        weakref.finalize(buf, self._give_back, owner).atexit = False      # (the finalizer holds the owner, not the buffer)
+        return buf
+
+    def _give_back(self, owner) -> None:
+        with self._lock:
+            if len(self._free) < self._keep:
+                self._free.append(owner)            # (beyond `keep` free blocks the owner dies here and unlocks its pages)
+
+    @property
+    def free_blocks(self) -> int:
+        with self._lock:
+            return len(self._free)
+
+
+class DevicePost:
+    """IK and post-processing of one batch without a host round trip in between: page-locked ``human`` -> H2D -> one group
+    launch -> ``gmr_postprocess_clips_dev`` over all jobs -> ONE D2H of the five arrays and the status words -> one stream
+    synchronisation.  Device buffers and the input staging are grow-only and reused from batch to batch; output blocks come
+    from a :class:`PinnedPool`."""
+
+    def __init__(self, pool: Optional[PinnedPool] = None):
+        self.pool = pool if pool is not None else PinnedPool()
+        self._stream = None
+        self._dev: Dict[str, object] = {}
+        self._pin: Dict[str, np.ndarray] = {}
+        self._events = None
+
+    def _d(self, name: str, nbytes: int):
+        from . import _lib
+        b = self._dev.get(name)
+        if b is None or b.nbytes < nbytes:
+            if b is not None:
+                b.free()                            # (every batch ends with a stream synchronisation: nothing is in flight)
+            b = self._dev[name] = _lib.DeviceBuffer(nbytes + nbytes // 4 + 256)
+        return b
+
+    def pinned(self, name: str, shape, dtype) -> np.ndarray:
+        from . import _lib
+        need = int(np.prod(shape)) * np.dtype(dtype).itemsize
+        blk = self._pin.get(name)
+        if blk is None or blk.nbytes < need:
+            self._pin.pop(name, None)
+            blk = self._pin[name] = _lib.pinned_empty((need + need // 2 + 8,), np.uint8)
+        return blk[:need].view(dtype).reshape(shape)
+
+    def run(self, jobs: Sequence[Dict], km: KinematicsModel, ik_flags: int = 0, height_adjust: bool = True,
+            root_origin_offset: bool = True, ground_offset: float = 0.0, timing: Optional[Dict[str, float]] = None):
+        """``jobs`` = ``[{"solver", "human": f64[S,T,nhuman,7] (page-locked for an asynchronous copy), "lens": i32[S],
+        "q0": f64[nq]}]``, all for the robot of ``km``.  Returns ``(root_pos, root_rot, dof_pos, local_body_pos, spans, status)``:
+        the four arrays are views of one pool block, ``spans[j][k] = (a, b)`` are the rows of clip k of job j, ``status[j]``
+        the IK status words of job j."""
+        import ctypes as C
+        from . import _lib
+        L = _lib.lib()
+        if self._stream is None:
+            self._stream = _lib.Stream()
+            self._events = [_lib.Event() for _ in range(5)]
+        st, ev = self._stream, self._events
+        fk = km.hip_handle
+        nb, ndof, nq = fk.nbody, fk.ndof, fk.ndof + 7
+        up = lambda x: (int(x) + 255) // 256 * 256            # noqa: E731
+        # the sources of one post-processing call are at most 8 jobs: more jobs -> more calls, each over its own dense range
+        # of rows that starts at a multiple of 4 (so that its local_body_pos starts 16-byte aligned)
+        chunks, spans, row = [], [], 0
+        for c0 in range(0, len(jobs), 8):
+            seg = [0]
+            for j in jobs[c0:c0 + 8]:
+                lens = np.asarray(j["lens"], dtype=np.int64)
+                starts = row + seg[-1] + np.concatenate([[0], np.cumsum(lens)])
+                spans.append([(int(a), int(b)) for a, b in zip(starts[:-1], starts[1:])])
+                seg.extend((seg[-1] + np.cumsum(lens)).tolist())
+            chunks.append((c0, row, np.asarray(seg, dtype=np.int32)))
+            row = (row + seg[-1] + 3) // 4 * 4
+        Bp, nclip = max(row, 1), sum(len(j["lens"]) for j in jobs)
+        o_rp = 0
+        o_rr = o_rp + up(Bp * 24)
+        o_dp = o_rr + up(Bp * 32)
+        o_lb = o_dp + up(Bp * ndof * 8)
+        o_st = o_lb + up(Bp * nb * 12)
+        total = o_st + up(nclip * 4)
+        d_out = self._d("out", total)
+        base = d_out.ptr.value
+        ev[0].record(st)
+        launch, sources, d_status, clip = [], [], [], 0
+        for i, j in enumerate(jobs):
+            sol, human = j["solver"], j["human"]
+            S, T = human.shape[:2]
+            assert human.dtype == np.float64 and human.flags.c_contiguous and human.shape[2:] == (sol.nhuman, 7)
+            q0 = self.pinned(f"q0_{i}", (S, sol.nq), np.float64)
+            q0[:] = j["q0"]
+            lens = self.pinned(f"len_{i}", (S,), np.int32)
+            lens[:] = j["lens"]
+            d_h, d_q0, d_len = self._d(f"human_{i}", human.nbytes), self._d(f"q0_{i}", q0.nbytes), self._d(f"len_{i}", lens.nbytes)
+            d_q, d_ns = self._d(f"q_out_{i}", S * T * sol.nq * 8), self._d(f"nsolve_{i}", S * T * 8)
+            for dst, src in ((d_h, human), (d_q0, q0), (d_len, lens)):
+                _lib.check(L.gmr_memcpy_h2d(dst.ptr, src.ctypes.data_as(C.c_void_p), src.nbytes, st.ptr))
+            d_status.append(C.c_void_p(base + o_st + 4 * clip))
+            launch.append((sol, S, T, d_q0, d_h, d_len, d_q, d_ns, d_status[-1]))
+            sources.append((S, T, d_q, d_len))
+            clip += S
+        ev[1].record(st)
+        _lib.retarget_group_dev(launch, ik_flags, st)
+        ev[2].record(st)
+        for n, (c0, r0, seg) in enumerate(chunks):
+            hseg = self.pinned(f"seg_{n}", seg.shape, np.int32)
+            hseg[:] = seg
+            d_seg = self._d(f"seg_{n}", seg.nbytes)
+            _lib.check(L.gmr_memcpy_h2d(d_seg.ptr, hseg.ctypes.data_as(C.c_void_p), seg.nbytes, st.ptr))
+            fk.postprocess_clips_dev(sources[c0:c0 + 8], d_seg, len(seg) - 1, int(seg[-1]), C.c_void_p(base + o_rp + r0 * 24),
+                                     C.c_void_p(base + o_rr + r0 * 32), C.c_void_p(base + o_dp + r0 * ndof * 8),
+                                     C.c_void_p(base + o_lb + r0 * nb * 12), None, height_adjust, root_origin_offset, ground_offset, st)
+        ev[3].record(st)
+        buf = self.pool.take(total)
+        # (the address, not ctypes.cast: a cast leaves the buffer referring to itself, and only the cycle collector would
+        #  hand the block back)
+        _lib.check(L.gmr_memcpy_d2h(C.c_void_p(C.addressof(buf)), d_out.ptr, total, st.ptr))
+        ev[4].record(st)
+        st.sync()
+        if timing is not None:
+            for k, a, b in (("h2d", 0, 1), ("ik", 1, 2), ("post", 2, 3), ("d2h", 3, 4)):
+                timing[k] = timing.get(k, 0.0) + ev[a].elapsed_ms(ev[b]) * 1e-3
+        view = lambda off, dtype, shape: np.frombuffer(buf, dtype=dtype, count=int(np.prod(shape)), offset=off).reshape(shape)   # noqa: E731
+        status_all = view(o_st, np.int32, (nclip,)).copy()
+        status, clip = [], 0
+        for j in jobs:
+            status.append(status_all[clip:clip + len(j["lens"])])
+            clip += len(j["lens"])
+        return (view(o_rp, np.float64, (Bp, 3)), view(o_rr, np.float64, (Bp, 4)), view(o_dp, np.float64, (Bp, ndof)),
+                view(o_lb, np.float32, (Bp, nb, 3)), spans, status)
+
+
 class ClipRetargeter:
     """Many clips of one (source, robot, height) per call, ONE IK launch each: the per-batch step of the dataset drivers.
     What does not depend on the batch is built once -- the solver, the ``KinematicsModel`` -- and the padded input /
@@ -85,6 +263,7 @@ class ClipRetargeter:
         self.height_adjust, self.root_origin_offset, self.offset_to_ground = height_adjust, root_origin_offset, offset_to_ground
         self._km: Optional[KinematicsModel] = None
         self._pin: Dict[str, np.ndarray] = {}
+        self._dev_post: Optional[DevicePost] = None
         self.timing: Dict[str, float] = {}
 
     def _buf(self, name: str, shape, dtype) -> np.ndarray:
@@ -141,6 +320,8 @@ class ClipRetargeter:
         t1 = time.perf_counter()
         sol = gmr.hip_solver
         lens = self._lens[:S].copy()
+        if post_path() == "device":
+            return self._finish_device(fps, lens)
         q0 = self._buf("q0", (S, sol.nq), np.float64)
         q0[:] = gmr.model.qpos0
         outs = [(self._buf("q_out", (S, T, sol.nq), np.float64), self._buf("nsolve", (S, T, 2), np.int32), np.zeros(S, np.int32))]
@@ -156,6 +337,28 @@ class ClipRetargeter:
         t3 = time.perf_counter()
         for k, v in (("ik", t2 - t1), ("post", t3 - t2)):
             self.timing[k] = self.timing.get(k, 0.0) + v
+        return out
+
+    def _finish_device(self, fps: Sequence[float], lens: np.ndarray) -> List[Dict]:
+        """:meth:`finish` with the post-processing on the device: ``q_out`` and ``nsolve`` never cross the bus.  ``timing`` gets
+        ``h2d`` / ``ik`` / ``post`` / ``d2h`` from device events of the one stream everything runs on (none of them overlaps
+        another) and ``dicts``, the host time to wrap the views."""
+        import time
+        S, gmr = self._n, self.gmr
+        if self._km is None:
+            self._km = KinematicsModel(gmr.xml_file)
+        if self._dev_post is None:
+            self._dev_post = DevicePost()
+        job = {"solver": gmr.hip_solver, "human": self._human[:S], "lens": lens, "q0": gmr.model.qpos0}
+        self._n = 0
+        rp, rr, dp, lbp, spans, (status,) = self._dev_post.run([job], self._km, gmr._flags(self.offset_to_ground), self.height_adjust,
+                                                               self.root_origin_offset, 0.0, self.timing)
+        if (status != 0).any():
+            raise RuntimeError(f"IK failed for clips {np.nonzero(status)[0].tolist()}")
+        t0 = time.perf_counter()
+        names = self._km.body_names
+        out = [motion_dict(fps[i], rp[a:b], rr[a:b], dp[a:b], lbp[a:b], names) for i, (a, b) in enumerate(spans[0])]
+        self.timing["dicts"] = self.timing.get("dicts", 0.0) + time.perf_counter() - t0
         return out
 
     def __call__(self, clips: Sequence, fps: Sequence[float]) -> List[Dict]:
@@ -631,28 +834,56 @@ def retarget_smplx_loaded(raws: Sequence[Dict], smplx_body_model_path: str, tgt_
             g = gmr_of[h] = GeneralMotionRetargeting("smplx", tgt_robot, actual_human_height=h)
         packed[i], fps_of[i] = smpl.smplx_frames_packed_fused(g, d, bm, tgt_fps=tgt_fps)      # body model + alignment, one call
         height[i] = h
+    device = post_path() == "device" and bool(raws)
+    dp = _smplx_device_post(next(iter(gmr_of.values())).xml_file) if device else None
     jobs, members = [], []
-    for h, g in gmr_of.items():
+    for n, (h, g) in enumerate(gmr_of.items()):
         idxs = [i for i in range(len(raws)) if height[i] == h]
         lens = np.array([packed[i].shape[0] for i in idxs], dtype=np.int32)
         T = max(int(lens.max()), 1)
-        human = np.zeros((len(idxs), T, len(g.human_body_names), 7))
+        shape = (len(idxs), T, len(g.human_body_names), 7)
+        human = dp[1].pinned(f"human_{n}", shape, np.float64) if device else np.empty(shape)
+        human[..., :3] = 0.0
         human[..., 3] = 1.0
+        human[..., 4:] = 0.0
         for k, i in enumerate(idxs):
             human[k, : lens[k]] = packed[i]
-        jobs.append({"solver": g.hip_solver, "human": human, "lens": lens})
+        jobs.append({"solver": g.hip_solver, "human": human, "lens": lens, "q0": g.model.qpos0})
         members.append((idxs, lens))
-    results = _lib.retarget_group(jobs) if jobs else []
+    if not raws:
+        return []
+    fps = [fps_of[i] for i in range(len(raws))]
+    if device:
+        km, post = dp
+        rp, rr, dof, lbp, spans, status = post.run(jobs, km, 0, height_adjust, root_origin_offset)
+        out: List[Optional[Dict]] = [None] * len(raws)
+        for (idxs, _), sp, stt in zip(members, spans, status):
+            if (stt != 0).any():
+                raise RuntimeError(f"IK failed for clips {[idxs[k] for k in np.nonzero(stt)[0]]}")
+            for i, (a, b) in zip(idxs, sp):
+                out[i] = motion_dict(fps[i], rp[a:b], rr[a:b], dof[a:b], lbp[a:b], km.body_names)
+        return out
+    results = _lib.retarget_group([{k: v for k, v in j.items() if k != "q0"} for j in jobs])
     qpos: List[Optional[np.ndarray]] = [None] * len(raws)
     for (idxs, lens), (q, _, status) in zip(members, results):
         if (status != 0).any():
             raise RuntimeError(f"IK failed for clips {[idxs[k] for k in np.nonzero(status)[0]]}")
         for k, i in enumerate(idxs):
             qpos[i] = q[k, : lens[k]]
-    if not raws:
-        return []
     km = KinematicsModel(next(iter(gmr_of.values())).xml_file)
-    return postprocess_clips(qpos, km, [fps_of[i] for i in range(len(raws))], height_adjust, root_origin_offset)
+    return postprocess_clips(qpos, km, fps, height_adjust, root_origin_offset)
+
+
+_SMPLX_DEVICE_POST: Dict[str, tuple] = {}
+
+
+def _smplx_device_post(xml_file: str):
+    """(KinematicsModel, DevicePost) of a robot, kept for the batches of a run: the FK handle owns the device scratch of the
+    post-processing, the DevicePost the device buffers and the page-locked staging."""
+    key = str(xml_file)
+    if key not in _SMPLX_DEVICE_POST:
+        _SMPLX_DEVICE_POST[key] = (KinematicsModel(xml_file), DevicePost())
+    return _SMPLX_DEVICE_POST[key]
 
 
 def run_smplx_dataset(src_folder: str, tgt_folder: str, robot: str, smplx_folder: str, override: bool = False,

@@ -186,6 +186,41 @@ int gmr_fk_segment_min_z_dev(gmr_fk_t* fk, const float* d_body_pos, const int32_
 int gmr_fk_batch_segments(gmr_fk_t* fk, int B, const float* root_pos, const float* root_rot, const float* dof, int nseg,
                           const int32_t* seg_start /* [nseg + 1] */, float* body_pos, float* seg_min_z /* [nseg] */);
 
+/* ---- H10: the dataset drivers' post-processing, on the device ------------------------------------------------------
+ * Replaces what `process_file` does between the retargeting loop and pickle.dump (scripts/smplx_to_robot_dataset.py:97-131;
+ * bvh_to_robot_dataset.py:111-139, which has both adjustments off) for ALL clips of a batch, reading the IK launch's output where
+ * it lies -- no round trip of q_out through the host, no float32 copies of it, no second upload:
+ *   root_pos = q[0:3], root_rot = q[4,5,6,3] (wxyz -> xyzw), dof_pos = q[7:]                         (:97-102)
+ *   local_body_pos = forward_kinematics(0, identity, float32(dof_pos))                               (:106-112)
+ *   GMR_POST_HEIGHT_ADJUST:      lowest[c] = min over the clip's frames and bodies of the z of
+ *                                forward_kinematics(float32(root_pos), float32(root_rot), float32(dof_pos));
+ *                                root_pos.z = root_pos.z - (double)lowest[c] + ground_offset          (:118-126)
+ *   GMR_POST_ROOT_ORIGIN_OFFSET: root_pos.xy -= root_pos.xy of the clip's first frame                (:128-131)
+ * Both FK passes are the walk of gmr_fk_batch_dev (the world pass is a walk of its own, not root + R * local: the chained
+ * products round differently, and `lowest` moves every root_pos.z of its clip), so the results are the bytes of
+ * gmr_fk_batch_segments on the host-converted arrays followed by the NumPy lines above. */
+#define GMR_POST_HEIGHT_ADJUST      1
+#define GMR_POST_ROOT_ORIGIN_OFFSET 2
+typedef struct gmr_post_src {      /* one IK job's output, as gmr_retarget_*_dev left it */
+  int32_t S, T;                    /* T >= 1 when S > 0 */
+  const double* q_out;             /* [S][T][nq]   */
+  const int32_t* len;              /* [S] or NULL (= all T) */
+} gmr_post_src_t;
+/* device pointers, asynchronous on `stream`.  The clips of src[0], then src[1], ... (nsrc <= 8) are numbered 0 .. C-1;
+ * seg_start i32 [C+1] ascending from 0 is the exclusive prefix sum of their lengths, B = seg_start[C] (the host passes B:
+ * the kernels clamp what they read from seg_start to it, and a frame index to the rows of its stream, so no read leaves
+ * the sources even for an inconsistent seg_start; rows at or beyond len[s] are never read).
+ * outputs: root_pos f64[B][3], root_rot f64[B][4] xyzw, dof_pos f64[B][ndof], local_body_pos f32[B][nbody][3] (16-byte
+ * aligned for the coalesced flush; any alignment works), lowest f32[C] (may be NULL; written only with
+ * GMR_POST_HEIGHT_ADJUST; +inf for an empty clip).
+ * The scratch memory of a call (16 B per row, and nbody * 12 B per row with GMR_POST_HEIGHT_ADJUST) belongs to the handle,
+ * one block per HIP stream that has called, grown on demand (the only time the call waits: for its own stream) and freed
+ * by gmr_fk_destroy: calls on different streams may be in flight together. */
+int gmr_postprocess_clips_dev(gmr_fk_t* fk, const gmr_post_src_t* src, int nsrc, int nq,
+                              const int32_t* d_seg_start, int C, int B, int flags, double ground_offset,
+                              double* d_root_pos, double* d_root_rot, double* d_dof_pos,
+                              float* d_local_body_pos, float* d_lowest, void* stream);
+
 /* ---- N1: SMPL-X frame extraction (the step in front of the loop) ---------- */
 /* A kinematic tree of J <= 64 joints (parents[j] < j, joint 0 the root) and the joints whose poses are
  * wanted: sel[nsel] (one output row each, in this order; nsel = 0 -> all J joints, row = joint).  For the
