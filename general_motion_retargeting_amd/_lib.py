@@ -86,6 +86,11 @@ _SIGS = {
     "gmr_smplx_compact_layout": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_int)]),
     "gmr_smplx_align_compact_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                               C.c_void_p]),
+    "gmr_bvh_create": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "gmr_bvh_destroy": (C.c_int, [C.c_void_p]),
+    "gmr_bvh_columns": (C.c_int, [C.c_void_p]),
+    "gmr_bvh_frames_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "gmr_bvh_frames": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "gmr_comm_create": (C.c_int, [C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),
     "gmr_comm_destroy": (C.c_int, [C.c_void_p]),
     "gmr_comm_rank": (C.c_int, [C.c_void_p]),
@@ -615,6 +620,55 @@ class SmplxHandle:
     def close(self):
         if self.handle:
             lib().gmr_smplx_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BvhHandle:
+    """BVH topology + row selection behind gmr_bvh_create (N2: raw channel rows -> packed human frames)."""
+
+    def __init__(self, parents, channels: int, order: str, sel_pos, sel_rot):
+        require_gpu()
+        self.parents = np.ascontiguousarray(parents, dtype=np.int32)
+        self.J = int(len(self.parents))
+        self.sel_pos = np.ascontiguousarray(sel_pos, dtype=np.int32)
+        self.sel_rot = np.ascontiguousarray(sel_rot, dtype=np.int32)
+        if self.sel_pos.shape != self.sel_rot.shape or self.sel_pos.ndim != 1:
+            raise ValueError("sel_pos and sel_rot are two lists of the same length")
+        self.rows = int(len(self.sel_pos))
+        h = C.c_void_p()
+        check(lib().gmr_bvh_create(self.J, _ptr(self.parents), int(channels), str(order).encode(), self.rows, _ptr(self.sel_pos),
+                                   _ptr(self.sel_rot), C.byref(h)))
+        self.handle = h
+        self.ncol = int(lib().gmr_bvh_columns(h))
+
+    def frames(self, rows, seg_start, offsets, T=None):
+        """``gmr_bvh_frames``: ``rows f64[B, ncol]`` of the clips ``seg_start i32[nclip + 1]`` with ``offsets f64[nclip, J, 3]``
+        -> ``human f64[nclip, T, rows, 7]`` (``T`` defaults to the longest clip; frames beyond a clip's length are zeros)."""
+        rows = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, self.ncol)
+        seg = np.ascontiguousarray(seg_start, dtype=np.int32)
+        nclip = len(seg) - 1
+        offsets = np.ascontiguousarray(offsets, dtype=np.float64)
+        if nclip < 0 or offsets.shape != (nclip, self.J, 3):
+            raise ValueError(f"offsets must be [{nclip}, {self.J}, 3]")
+        if T is None:
+            T = max(int(np.diff(seg).max()) if nclip else 0, 1)
+        out = np.zeros((nclip, int(T), self.rows, 7), dtype=np.float64)
+        check(lib().gmr_bvh_frames(self.handle, nclip, rows.shape[0], _ptr(rows), _ptr(seg), _ptr(offsets), int(T), _ptr(out)))
+        return out
+
+    def frames_dev(self, nclip, B, d_rows, d_seg_start, d_offsets, T, d_human, stream=None):
+        check(lib().gmr_bvh_frames_dev(self.handle, int(nclip), int(B), _d(d_rows), _d(d_seg_start), _d(d_offsets), int(T),
+                                       _d(d_human), _s(stream)))
+
+    def close(self):
+        if self.handle:
+            lib().gmr_bvh_destroy(self.handle)
             self.handle = None
 
     def __del__(self):

@@ -92,6 +92,15 @@ def post_path() -> str:
         return "host"
 
 
+def bvh_path() -> str:
+    """``"device"`` or ``"host"``: where the BVH drivers turn raw channel rows into packed frames.  ``"device"``
+    (``gmr_bvh_frames_dev`` in front of the IK launch, the loaders only parse text) needs a GPU and the device post-processing
+    (:func:`post_path`); ``GMR_DATASET_BVH=host`` keeps the NumPy functions of ``utils/lafan1.py`` in the loaders."""
+    if os.environ.get("GMR_DATASET_BVH", "device").strip().lower() == "host":
+        return "host"
+    return post_path()
+
+
 class PinnedPool:
     """Page-locked output blocks for batches whose results are handed out as views.  A block is taken for one batch; it
     comes back when the LAST array viewing it has died (a finalizer on the buffer the arrays are views of), so a dict kept
@@ -168,7 +177,11 @@ class DevicePost:
     def run(self, jobs: Sequence[Dict], km: KinematicsModel, ik_flags: int = 0, height_adjust: bool = True,
             root_origin_offset: bool = True, ground_offset: float = 0.0, timing: Optional[Dict[str, float]] = None):
         """``jobs`` = ``[{"solver", "human": f64[S,T,nhuman,7] (page-locked for an asynchronous copy), "lens": i32[S],
-        "q0": f64[nq]}]``, all for the robot of ``km``.  Returns ``(root_pos, root_rot, dof_pos, local_body_pos, spans, status)``:
+        "q0": f64[nq]}]``, all for the robot of ``km``.  A job of raw BVH clips carries, instead of ``"human"``, ``"T"`` and
+        ``"bvh"`` = ``[{"handle": _lib.BvhHandle, "rows": f64[B,ncol] (page-locked), "offsets": f64[n,J,3], "clips": [index in
+        lens, ...], "lens": [...]}]`` (one entry per topology) and optionally ``"packed"`` = ``[(index, f64[n,nhuman,7])]``: the
+        raw rows are uploaded ragged and ``gmr_bvh_frames_dev`` writes ``human`` on the device, on the same stream, in front
+        of the IK launch (inside the batch the clips are ordered by topology; the results come back in the job's order).  Returns ``(root_pos, root_rot, dof_pos, local_body_pos, spans, status)``:
         the four arrays are views of one pool block, ``spans[j][k] = (a, b)`` are the rows of clip k of job j, ``status[j]``
         the IK status words of job j."""
         import ctypes as C
@@ -176,18 +189,28 @@ class DevicePost:
         L = _lib.lib()
         if self._stream is None:
             self._stream = _lib.Stream()
-            self._events = [_lib.Event() for _ in range(5)]
+            self._events = [_lib.Event() for _ in range(6)]
         st, ev = self._stream, self._events
         fk = km.hip_handle
         nb, ndof, nq = fk.nbody, fk.ndof, fk.ndof + 7
         up = lambda x: (int(x) + 255) // 256 * 256            # noqa: E731
         # the sources of one post-processing call are at most 8 jobs: more jobs -> more calls, each over its own dense range
         # of rows that starts at a multiple of 4 (so that its local_body_pos starts 16-byte aligned)
+        # raw BVH jobs: the clips of one topology are consecutive streams of the batch (one gmr_bvh_frames_dev call each)
+        perms, dlens = [], []
+        for j in jobs:
+            lens = np.asarray(j["lens"], dtype=np.int64)
+            perm = None
+            if "bvh" in j:
+                perm = np.array([i for g in j["bvh"] for i in g["clips"]] + [i for i, _ in j.get("packed", ())], dtype=np.int64)
+                assert sorted(perm.tolist()) == list(range(len(lens)))
+                lens = lens[perm]
+            perms.append(perm)
+            dlens.append(lens)
         chunks, spans, row = [], [], 0
         for c0 in range(0, len(jobs), 8):
             seg = [0]
-            for j in jobs[c0:c0 + 8]:
-                lens = np.asarray(j["lens"], dtype=np.int64)
+            for lens in dlens[c0:c0 + 8]:
                 starts = row + seg[-1] + np.concatenate([[0], np.cumsum(lens)])
                 spans.append([(int(a), int(b)) for a, b in zip(starts[:-1], starts[1:])])
                 seg.extend((seg[-1] + np.cumsum(lens)).tolist())
@@ -203,24 +226,60 @@ class DevicePost:
         d_out = self._d("out", total)
         base = d_out.ptr.value
         ev[0].record(st)
-        launch, sources, d_status, clip = [], [], [], 0
+        launch, sources, d_status, clip, bvh_calls = [], [], [], 0, []
+        h2d = lambda dst, src: _lib.check(L.gmr_memcpy_h2d(dst, src.ctypes.data_as(C.c_void_p), src.nbytes, st.ptr))   # noqa: E731
         for i, j in enumerate(jobs):
-            sol, human = j["solver"], j["human"]
-            S, T = human.shape[:2]
-            assert human.dtype == np.float64 and human.flags.c_contiguous and human.shape[2:] == (sol.nhuman, 7)
+            sol = j["solver"]
+            if "bvh" in j:
+                S, T, copies = len(dlens[i]), max(int(j["T"]), 1), []
+                frame_bytes = sol.nhuman * 7 * 8
+                d_h = self._d(f"human_{i}", S * T * frame_bytes)       # (rows at or beyond a clip's length stay stale: never read)
+                pos = 0
+                for gi, g in enumerate(j["bvh"]):
+                    rows, n = g["rows"], len(g["clips"])
+                    assert rows.dtype == np.float64 and rows.flags.c_contiguous and rows.shape[1] == g["handle"].ncol
+                    seg = self.pinned(f"bvhseg_{i}_{gi}", (n + 1,), np.int32)
+                    seg[0] = 0
+                    seg[1:] = np.cumsum(g["lens"])
+                    assert int(seg[-1]) == rows.shape[0] and len(g["lens"]) == n
+                    off = self.pinned(f"bvhoff_{i}_{gi}", (n, g["handle"].J, 3), np.float64)
+                    off[:] = g["offsets"]
+                    d_rows, d_seg, d_off = (self._d(f"bvh{k}_{i}_{gi}", a.nbytes) for k, a in (("rows", rows), ("seg", seg), ("off", off)))
+                    copies += [(d_rows.ptr, rows), (d_seg.ptr, seg), (d_off.ptr, off)]
+                    bvh_calls.append((g["handle"], n, rows.shape[0], d_rows, d_seg, d_off, T, C.c_void_p(d_h.ptr.value + pos * T * frame_bytes)))
+                    pos += n
+                packed = j.get("packed", ())
+                if packed:      # clips the device path does not take, computed on the host: straight into their padded rows
+                    stage = self.pinned(f"bvhpacked_{i}", (sum(len(p) for _, p in packed), sol.nhuman, 7), np.float64)
+                    a = 0
+                    for _, p in packed:
+                        stage[a:a + len(p)] = p
+                        if len(p):
+                            copies.append((C.c_void_p(d_h.ptr.value + pos * T * frame_bytes), stage[a:a + len(p)]))
+                        a += len(p)
+                        pos += 1
+            else:
+                human = j["human"]
+                S, T = human.shape[:2]
+                assert human.dtype == np.float64 and human.flags.c_contiguous and human.shape[2:] == (sol.nhuman, 7)
+                d_h = self._d(f"human_{i}", human.nbytes)
+                copies = [(d_h.ptr, human)]
             q0 = self.pinned(f"q0_{i}", (S, sol.nq), np.float64)
             q0[:] = j["q0"]
             lens = self.pinned(f"len_{i}", (S,), np.int32)
-            lens[:] = j["lens"]
-            d_h, d_q0, d_len = self._d(f"human_{i}", human.nbytes), self._d(f"q0_{i}", q0.nbytes), self._d(f"len_{i}", lens.nbytes)
+            lens[:] = dlens[i]
+            d_q0, d_len = self._d(f"q0_{i}", q0.nbytes), self._d(f"len_{i}", lens.nbytes)
             d_q, d_ns = self._d(f"q_out_{i}", S * T * sol.nq * 8), self._d(f"nsolve_{i}", S * T * 8)
-            for dst, src in ((d_h, human), (d_q0, q0), (d_len, lens)):
-                _lib.check(L.gmr_memcpy_h2d(dst.ptr, src.ctypes.data_as(C.c_void_p), src.nbytes, st.ptr))
+            for dst, src in copies + [(d_q0.ptr, q0), (d_len.ptr, lens)]:
+                h2d(dst, src)
             d_status.append(C.c_void_p(base + o_st + 4 * clip))
             launch.append((sol, S, T, d_q0, d_h, d_len, d_q, d_ns, d_status[-1]))
             sources.append((S, T, d_q, d_len))
             clip += S
         ev[1].record(st)
+        for h, n, B, d_rows, d_seg, d_off, T, d_dst in bvh_calls:
+            h.frames_dev(n, B, d_rows, d_seg, d_off, T, d_dst, st)
+        ev[5].record(st)
         _lib.retarget_group_dev(launch, ik_flags, st)
         ev[2].record(st)
         for n, (c0, r0, seg) in enumerate(chunks):
@@ -239,14 +298,20 @@ class DevicePost:
         ev[4].record(st)
         st.sync()
         if timing is not None:
-            for k, a, b in (("h2d", 0, 1), ("ik", 1, 2), ("post", 2, 3), ("d2h", 3, 4)):
-                timing[k] = timing.get(k, 0.0) + ev[a].elapsed_ms(ev[b]) * 1e-3
+            for k, a, b in (("h2d", 0, 1), ("frames", 1, 5), ("ik", 5, 2), ("post", 2, 3), ("d2h", 3, 4)):
+                if k != "frames" or bvh_calls:
+                    timing[k] = timing.get(k, 0.0) + ev[a].elapsed_ms(ev[b]) * 1e-3
         view = lambda off, dtype, shape: np.frombuffer(buf, dtype=dtype, count=int(np.prod(shape)), offset=off).reshape(shape)   # noqa: E731
         status_all = view(o_st, np.int32, (nclip,)).copy()
         status, clip = [], 0
-        for j in jobs:
-            status.append(status_all[clip:clip + len(j["lens"])])
+        for i, j in enumerate(jobs):
+            stt = status_all[clip:clip + len(j["lens"])]
             clip += len(j["lens"])
+            if perms[i] is not None:          # back to the job's own clip order
+                inv = np.empty_like(perms[i])
+                inv[perms[i]] = np.arange(len(inv))
+                stt, spans[i] = stt[inv], [spans[i][p] for p in inv.tolist()]
+            status.append(stt)
         return (view(o_rp, np.float64, (Bp, 3)), view(o_rr, np.float64, (Bp, 4)), view(o_dp, np.float64, (Bp, ndof)),
                 view(o_lb, np.float32, (Bp, nb, 3)), spans, status)
 
@@ -256,6 +321,9 @@ class ClipRetargeter:
     What does not depend on the batch is built once -- the solver, the ``KinematicsModel`` -- and the padded input /
     output arrays live in page-locked memory that is reused from batch to batch (locking pages costs more than
     retargeting them), so the copies of a large batch run asynchronously, slice by slice, under its kernels."""
+
+    _seen_raw = False            # this object has staged raw BVH clips: its batches are raw batches from then on
+    _raw_index: Optional[Dict[tuple, int]] = None        # topology key -> number of its page-locked rows block
 
     def __init__(self, src_human: str, tgt_robot: str, actual_human_height: Optional[float] = None, height_adjust: bool = True,
                  root_origin_offset: bool = True, offset_to_ground: bool = False):
@@ -278,12 +346,16 @@ class ClipRetargeter:
 
     # ---- staged protocol (DatasetPipeline): clips are copied into the padded, page-locked batch AS THEY ARRIVE from the
     # loaders -- the time this thread would otherwise spend waiting for them -- instead of when the batch is launched
-    def reserve(self, frames_budget: int) -> None:
-        """Lock the pages of a batch of ``frames_budget`` padded frames now (e.g. while the loaders are starting up)."""
+    def reserve(self, frames_budget: int, row_doubles: int = 0) -> None:
+        """Lock the pages of a batch of ``frames_budget`` padded frames now (e.g. while the loaders are starting up);
+        ``row_doubles`` > 0: of ``frames_budget`` raw BVH rows of that many columns instead (the device path of :meth:`add`)."""
         sol = self.gmr.hip_solver
-        self._buf("human", (frames_budget, sol.nhuman, 7), np.float64)
-        self._buf("q_out", (frames_budget, sol.nq), np.float64)
-        self._buf("nsolve", (frames_budget, 2), np.int32)
+        if row_doubles > 0:
+            self._buf("rows_0", (frames_budget, row_doubles), np.float64)
+        else:
+            self._buf("human", (frames_budget, sol.nhuman, 7), np.float64)
+            self._buf("q_out", (frames_budget, sol.nq), np.float64)
+            self._buf("nsolve", (frames_budget, 2), np.int32)
         if self._km is None:
             self._km = KinematicsModel(self.gmr.xml_file)
             self._km.hip_handle
@@ -293,19 +365,70 @@ class ClipRetargeter:
         sol = self.gmr.hip_solver
         self._T = max(int(longest), 1)
         self._cap = max(1, min(int(max_clips), int(frames_budget) // self._T))
-        self._human = self._buf("human", (self._cap, self._T, sol.nhuman, 7), np.float64)
+        self._human = None                                # the padded batch: locked when the first packed clip arrives
         self._lens = np.zeros(self._cap, dtype=np.int32)
         self._n = 0
+        # a batch of raw BVH clips (device path): per topology the rows of its clips, concatenated in page-locked memory
+        self._raw_mode = self._seen_raw
+        self._bvh_device = bvh_path() == "device"         # (asked once per batch, not per clip)
+        self._raw: Dict[tuple, Dict] = {}
+        self._packed: List = []
+
+    def _add_raw(self, clip) -> bool:
+        """one raw BVH clip of a device-path batch: only its rows are copied"""
+        from .utils import lafan1
+        n = len(clip)
+        if self._n >= self._cap or n > self._T:
+            return False
+        key = lafan1.topology_key(clip)
+        if self._raw_index is None:
+            self._raw_index = {}
+        g = self._raw.get(key)
+        if g is None:
+            handle = lafan1.BVH_FRAMES.handle(clip, self.gmr.human_body_names)
+            g = self._raw[key] = {"handle": handle, "index": self._raw_index.setdefault(key, len(self._raw_index)), "buf": None,
+                                  "cap": 0, "used": 0, "clips": [], "lens": [], "offsets": []}
+        if g["used"] + n > g["cap"]:
+            # the first topology gets what the padded batch would have taken (cap x T rows); others grow as they fill
+            cap = max(g["used"] + n, 2 * g["cap"], self._cap * self._T if g["index"] == 0 and self._cap * self._T < (1 << 40) else 0)
+            keep = g["buf"][: g["used"]].copy() if g["used"] else None
+            g["buf"], g["cap"] = self._buf(f"rows_{g['index']}", (cap, g["handle"].ncol), np.float64), cap
+            if keep is not None:
+                g["buf"][: g["used"]] = keep
+        g["buf"][g["used"]: g["used"] + n] = clip.rows
+        g["used"] += n
+        g["clips"].append(self._n)
+        g["lens"].append(n)
+        g["offsets"].append(np.asarray(clip.offsets, dtype=np.float64))
+        self._lens[self._n] = n
+        self._n += 1
+        self._raw_mode = self._seen_raw = True
+        return True
 
     def add(self, clip) -> bool:
         """Copy one clip into the batch; False when it does not fit (batch full, or the clip is longer than the batch's
-        rows): the caller finishes this batch and begins another."""
+        rows): the caller finishes this batch and begins another.  A raw BVH clip (``lafan1.BvhRaw``) joins a batch whose
+        frames are computed on the device (:func:`bvh_path`): only its rows are copied.  On the host path, for a file the
+        device path does not take, or in a batch that already holds packed clips, its frames are computed here."""
         import time
+        from .utils import lafan1
         t0 = time.perf_counter()
+        if isinstance(clip, lafan1.BvhRaw):
+            if self._bvh_device and lafan1.device_takes(clip) and (self._raw_mode or self._n == 0):
+                ok = self._add_raw(clip)
+                self.timing["pack"] = self.timing.get("pack", 0.0) + time.perf_counter() - t0
+                return ok
+            clip = lafan1.packed_from_raw(clip, self.gmr.human_body_names)
         p = clip if isinstance(clip, np.ndarray) else self.gmr.pack_frames(clip)
         if self._n >= self._cap or p.shape[0] > self._T:
             return False
-        self._human[self._n, : p.shape[0]] = p          # (rows beyond a clip's length are never read by the kernel)
+        if self._raw_mode and self._bvh_device:
+            self._packed.append((self._n, np.asarray(p, dtype=np.float64)))      # uploaded into its padded rows by DevicePost
+        else:
+            self._raw_mode = False
+            if self._human is None:
+                self._human = self._buf("human", (self._cap, self._T, self.gmr.hip_solver.nhuman, 7), np.float64)
+            self._human[self._n, : p.shape[0]] = p      # (rows beyond a clip's length are never read by the kernel)
         self._lens[self._n] = p.shape[0]
         self._n += 1
         self.timing["pack"] = self.timing.get("pack", 0.0) + time.perf_counter() - t0
@@ -349,7 +472,12 @@ class ClipRetargeter:
             self._km = KinematicsModel(gmr.xml_file)
         if self._dev_post is None:
             self._dev_post = DevicePost()
-        job = {"solver": gmr.hip_solver, "human": self._human[:S], "lens": lens, "q0": gmr.model.qpos0}
+        if self._raw_mode:
+            job = {"solver": gmr.hip_solver, "lens": lens, "q0": gmr.model.qpos0, "T": self._T, "packed": self._packed,
+                   "bvh": [{"handle": g["handle"], "rows": g["buf"][: g["used"]], "offsets": np.stack(g["offsets"]), "clips": g["clips"],
+                            "lens": g["lens"]} for g in self._raw.values()]}
+        else:
+            job = {"solver": gmr.hip_solver, "human": self._human[:S], "lens": lens, "q0": gmr.model.qpos0}
         self._n = 0
         rp, rr, dp, lbp, spans, (status,) = self._dev_post.run([job], self._km, gmr._flags(self.offset_to_ground), self.height_adjust,
                                                                self.root_origin_offset, 0.0, self.timing)
@@ -362,10 +490,11 @@ class ClipRetargeter:
         return out
 
     def __call__(self, clips: Sequence, fps: Sequence[float]) -> List[Dict]:
-        packed = [c if isinstance(c, np.ndarray) else self.gmr.pack_frames(c) for c in clips]
+        from .utils.lafan1 import BvhRaw
+        packed = [c if isinstance(c, (np.ndarray, BvhRaw)) else self.gmr.pack_frames(c) for c in clips]
         if not packed:
             return []
-        self.begin(max(p.shape[0] for p in packed), len(packed), 1 << 62)
+        self.begin(max(len(p) for p in packed), len(packed), 1 << 62)
         for p in packed:
             assert self.add(p)
         return self.finish(fps)
@@ -408,10 +537,15 @@ def retarget_bvh_files(bvh_files: Sequence[str], tgt_robot: str, fps: float = 30
                        root_origin_offset: bool = False) -> List[Dict]:
     """``scripts/bvh_to_robot_dataset.py:60-152`` for a list of files: every BVH clip becomes one
     stream of ONE launch (LAFAN1: 77 ragged clips).  Both adjustments default to off like that script
-    (``HEIGHT_ADJUST = False``, :128); the loader's hard-coded height 1.75 is used (lafan1.py:39)."""
-    from .utils.lafan1 import load_lafan1_packed
+    (``HEIGHT_ADJUST = False``, :128); the loader's hard-coded height 1.75 is used (lafan1.py:39).
+    On the device path (:func:`bvh_path`) only the text is parsed here: the raw rows are uploaded and ``gmr_bvh_frames_dev``
+    writes the packed frames into the IK batch (files of several skeletons: one call per topology)."""
+    from .utils.lafan1 import load_lafan1_packed, read_bvh_raw
     gmr = GeneralMotionRetargeting("bvh", tgt_robot, actual_human_height=1.75)
-    clips = [load_lafan1_packed(f, gmr.human_body_names)[0] for f in bvh_files]
+    if bvh_path() == "device":
+        clips = [read_bvh_raw(f) for f in bvh_files]
+    else:
+        clips = [load_lafan1_packed(f, gmr.human_body_names)[0] for f in bvh_files]
     return retarget_clips("bvh", tgt_robot, clips, [fps] * len(clips), actual_human_height=1.75,
                           height_adjust=height_adjust, root_origin_offset=root_origin_offset)
 
@@ -755,10 +889,20 @@ def default_workers(world: int = 1) -> int:
 
 # ---- BVH ---------------------------------------------------------------------------------------------------------------
 def _load_bvh_clip(args):
-    """(file, body names) -> packed frames f64[T, nhuman, 7]; module-level: runs in spawned worker processes."""
-    from .utils.lafan1 import load_lafan1_packed
-    f, names = args
-    return load_lafan1_packed(f, names)[0]
+    """(file, body names[, raw]) -> packed frames f64[T, nhuman, 7], or with ``raw`` the parsed text alone
+    (``lafan1.BvhRaw``: less to compute here and less to pickle back; the frames are computed on the device) unless the
+    device path does not take the file; module-level: runs in spawned worker processes."""
+    from .utils import lafan1
+    f, names = args[0], args[1]
+    if len(args) > 2 and args[2]:
+        raw = lafan1.read_bvh_raw(f)
+        if lafan1.device_takes(raw):
+            lafan1.selection(raw.names, names)             # an unknown body is this file's error, as on the host path
+            lafan1._global_poses_names(raw.names)
+            lafan1.topology_key(raw)                       # (computed here, kept on the clip)
+            return raw
+        return lafan1.packed_from_raw(raw, names)
+    return lafan1.load_lafan1_packed(f, names)[0]
 
 
 def run_bvh_dataset(src_folder: str, tgt_folder: str, robot: str, override: bool = False, batch_files: int = 0,
@@ -779,12 +923,26 @@ def run_bvh_dataset(src_folder: str, tgt_folder: str, robot: str, override: bool
     if retarget is None:
         rt = ClipRetargeter("bvh", robot, 1.75, height_adjust=False, root_origin_offset=False)    # HEIGHT_ADJUST = False, :128
         retarget = _Staged(rt, 30)
+    raw = rt is not None and bvh_path() == "device"        # the loaders only parse; gmr_bvh_frames_dev computes the frames
     try:
-        pipe = DatasetPipeline((lambda f: _load_bvh_clip((f, names))) if (load is None and pool is None) else (load or _BvhLoad(names)),
+        pipe = DatasetPipeline((lambda f: _load_bvh_clip((f, names, raw))) if (load is None and pool is None) else (load or _BvhLoad(names, raw)),
                                retarget, len, BVH_KEYS, frames_budget, batch_files if batch_files > 0 else 16384, pool,
                                verbose=verbose, label="bvh")
+
+        def reserve():
+            row_doubles = 0
+            if raw:
+                try:                                       # columns of a motion row, from the first file's hierarchy
+                    from .utils import lafan1
+                    hdr = lafan1.read_bvh_raw(jobs[0][0], header_only=True)
+                    row_doubles = {3: 3 + 3 * len(hdr.parents), 6: 6 * len(hdr.parents)}.get(hdr.channels, 0)
+                except Exception:  # noqa: BLE001 -- a broken first file: the batch locks its pages when it knows
+                    return
+                if row_doubles == 0:
+                    return
+            rt.reserve(min(frames_budget, 420 * len(jobs)), row_doubles)
         # lock the pages of the first batch while the loader processes start up and parse the first files
-        warm = (lambda: rt.reserve(min(frames_budget, 420 * len(jobs)))) if (rt is not None and len(jobs) > 64) else None
+        warm = reserve if (rt is not None and len(jobs) > 64) else None
         done = pipe.run(jobs, warm)
     finally:
         if pool is not None:
@@ -801,11 +959,11 @@ def run_bvh_dataset(src_folder: str, tgt_folder: str, robot: str, override: bool
 class _BvhLoad:
     """Picklable ``load`` for the process pool."""
 
-    def __init__(self, names):
-        self.names = list(names)
+    def __init__(self, names, raw: bool = False):
+        self.names, self.raw = list(names), bool(raw)
 
     def __call__(self, f):
-        return _load_bvh_clip((f, self.names))
+        return _load_bvh_clip((f, self.names, self.raw))
 
 
 # ---- SMPL-X ---------------------------------------------------------------------------------------------------------------

@@ -14,7 +14,7 @@ per-frame dict ``{bone: (pos, quat_wxyz)}`` plus the two synthetic bodies ``Left
 from __future__ import annotations
 
 import re
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -59,8 +59,28 @@ class Bvh:
         self.quats = None
 
 
-def read_bvh(filename) -> Bvh:
-    """BVH text -> :class:`Bvh` (hierarchy walk and channel layouts of extract.py:43-166)."""
+class BvhRaw:
+    """The text half of :func:`read_bvh`, nothing computed: hierarchy (``names``, ``parents``, ``offsets f64[J, 3]``), the
+    channel layout (``channels``: 3, 6 or 9 per joint; ``order``: Euler order of the rotation channels), ``frametime`` and the
+    motion rows ``f64[T, ncol]`` as they stand in the file (degrees, centimetres).  ``len()`` is the number of frames."""
+
+    def __init__(self, names, parents, offsets, channels, order, frametime, rows, filename=None):
+        self.names: List[str] = list(names)
+        self.parents = parents
+        self.offsets = offsets
+        self.channels = channels
+        self.order = order
+        self.frametime = frametime
+        self.rows = rows
+        self.filename = filename
+
+    def __len__(self) -> int:
+        return int(self.rows.shape[0])
+
+
+def read_bvh_raw(filename, header_only: bool = False) -> BvhRaw:
+    """BVH text -> :class:`BvhRaw` (hierarchy walk and motion block of extract.py:43-153).  ``header_only`` stops at the
+    motion block (no rows)."""
     names: List[str] = []
     offsets: List[List[float]] = []
     parents: List[int] = []
@@ -121,7 +141,7 @@ def read_bvh(filename) -> Bvh:
         vals = line.strip().split(" ")
         if vals and vals != [""]:
             rows.append(np.array([float(v) for v in vals]))
-    if motion_at is not None:
+    if motion_at is not None and not header_only:
         # The motion block: one row of numbers per frame.  Parsed with one C call instead of a Python loop with five
         # regular-expression attempts per line (the loader's cost is what bounds the dataset driver: tools/dataset_probe.py);
         # the same correctly-rounded doubles as float().
@@ -135,6 +155,14 @@ def read_bvh(filename) -> Bvh:
     n = len(parents)
     off = np.array(offsets, dtype=np.float64).reshape(n, 3)
     data = np.stack(rows[:nframes]) if rows else np.zeros((0, 3 + 3 * n))
+    return BvhRaw(names, np.array(parents, dtype=int), off, channels, order, frametime, data, str(filename))
+
+
+def bvh_from_raw(raw: BvhRaw) -> Bvh:
+    """The numeric half of :func:`read_bvh`: channel layouts (extract.py:99-153), Euler angles -> local quaternions and the
+    sign de-flip along time (extract.py:155-166).  This is what ``gmr_bvh_frames`` does on the device."""
+    names, off, data, channels, order = raw.names, raw.offsets, raw.rows, raw.channels, raw.order
+    n = len(raw.parents)
     T = data.shape[0]
     positions = np.repeat(off[None], T, axis=0)
     eulers = np.zeros((T, n, 3))
@@ -152,9 +180,14 @@ def read_bvh(filename) -> Bvh:
         positions[:, 1:] += blk[..., 0:3] * blk[..., 6:9]
     else:
         raise Exception("Too many channels! %s" % channels)
-    bvh = Bvh(names, np.array(parents, dtype=int), off, positions, eulers, order, frametime)
+    bvh = Bvh(names, raw.parents, off, positions, eulers, order, raw.frametime)
     bvh.quats = remove_quat_discontinuities(euler_to_quat(np.radians(eulers), order))
     return bvh
+
+
+def read_bvh(filename) -> Bvh:
+    """BVH text -> :class:`Bvh` (hierarchy walk and channel layouts of extract.py:43-166)."""
+    return bvh_from_raw(read_bvh_raw(filename))
 
 
 def euler_to_quat(e, order="zyx"):
@@ -195,7 +228,10 @@ def quat_fk(lrot, lpos, parents):
 
 
 def _global_poses(bvh_file) -> Tuple[List[str], np.ndarray, np.ndarray]:
-    data = read_bvh(bvh_file)
+    return _global_poses_of(read_bvh(bvh_file))
+
+
+def _global_poses_of(data: Bvh) -> Tuple[List[str], np.ndarray, np.ndarray]:
     grot, gpos = quat_fk(data.quats, data.pos, data.parents)
     orient = _quat_mul(np.broadcast_to(_ROT_QUAT, grot.shape), grot)
     position = gpos @ _ROT.T / 100                                           # cm -> m
@@ -221,3 +257,95 @@ def load_lafan1_packed(bvh_file, body_names: Sequence[str]) -> Tuple[np.ndarray,
     names, position, orient = _global_poses(bvh_file)
     idx = [names.index(n) for n in body_names]          # ValueError for an unknown body
     return np.concatenate([position[:, idx], orient[:, idx]], axis=-1), 1.75
+
+
+def packed_from_raw(raw: BvhRaw, body_names: Sequence[str]) -> np.ndarray:
+    """:func:`load_lafan1_packed` from an already parsed file, on the host: ``human f64[T, len(body_names), 7]``."""
+    names, position, orient = _global_poses_of(bvh_from_raw(raw))
+    idx = [names.index(n) for n in body_names]          # ValueError for an unknown body
+    return np.concatenate([position[:, idx], orient[:, idx]], axis=-1)
+
+
+# ----------------------------------------------------------------------------------------------
+# The numeric half ON THE DEVICE (``gmr_bvh_frames``, csrc/gmr_bvh.hip): raw rows of many clips in, packed frames out.
+# ----------------------------------------------------------------------------------------------
+def topology_key(raw: BvhRaw) -> tuple:
+    """What the clips of one ``gmr_bvh_t`` handle share: joint names, parents, channel layout, Euler order.  (Offsets are
+    per-clip data: LAFAN1's five subjects have one topology and five sets of bone lengths.)  Kept on the clip: a loader
+    process computes it once and it travels with the parse."""
+    key = getattr(raw, "_key", None)
+    if key is None:
+        key = raw._key = (tuple(raw.names), tuple(int(p) for p in raw.parents), raw.channels, raw.order)
+    return key
+
+
+def device_takes(raw: BvhRaw) -> bool:
+    """Whether the device path takes this file: layout 3 or 6 with consistent rows, an Euler order that is a permutation of
+    xyz, a tree within the handle's limits.  Everything else (``channels == 9``, a malformed file) goes through the host
+    functions, which also raise the errors a broken file raises today."""
+    takes = getattr(raw, "_takes", None)
+    if takes is None:
+        n = len(raw.parents)
+        takes = raw.channels in (3, 6) and raw.order is not None and sorted(raw.order) == ["x", "y", "z"]
+        takes = takes and 1 <= n <= 256 and raw.rows.ndim == 2 and raw.rows.shape[1] == (3 + 3 * n if raw.channels == 3 else 6 * n)
+        takes = raw._takes = bool(takes and int(raw.parents[0]) < 0 and all(0 <= int(raw.parents[j]) < j for j in range(1, n)))
+    return takes
+
+
+def selection(names: Sequence[str], body_names: Sequence[str]) -> Tuple[List[int], List[int]]:
+    """``(sel_pos, sel_rot)`` of ``gmr_bvh_create`` for the bodies of an ik_config: a bone is (j, j), ``LeftFootMod`` /
+    ``RightFootMod`` the foot's position with the toe's orientation (lafan1.py:28-33).  ValueError for an unknown body."""
+    names = list(names)
+    mod = {"LeftFootMod": ("LeftFoot", "LeftToe"), "RightFootMod": ("RightFoot", "RightToe")}
+    sel_pos, sel_rot = [], []
+    for b in body_names:
+        p, r = mod.get(b, (b, b))
+        sel_pos.append(names.index(p))
+        sel_rot.append(names.index(r))
+    return sel_pos, sel_rot
+
+
+class BvhFrames:
+    """``(raw clips, body_names) -> packed frames`` on the device: one ``gmr_bvh_t`` handle per topology key, cached; a file
+    the device path does not take (:func:`device_takes`) is computed by the host functions."""
+
+    def __init__(self):
+        self._handles = {}
+
+    def handle(self, raw: BvhRaw, body_names: Sequence[str]):
+        from .. import _lib
+        key = (topology_key(raw), tuple(body_names))
+        h = self._handles.get(key)
+        if h is None:
+            sel_pos, sel_rot = selection(raw.names, body_names)
+            _global_poses_names(raw.names)                 # (the host path needs the four foot bones: the same error here)
+            h = self._handles[key] = _lib.BvhHandle(raw.parents, raw.channels, raw.order, sel_pos, sel_rot)
+        return h
+
+    def __call__(self, raws: Sequence[BvhRaw], body_names: Sequence[str]) -> List[np.ndarray]:
+        """one ``f64[T_i, len(body_names), 7]`` per clip; the clips of one topology share one call"""
+        out: List[Optional[np.ndarray]] = [None] * len(raws)
+        groups = {}
+        for i, raw in enumerate(raws):
+            if device_takes(raw):
+                groups.setdefault(topology_key(raw), []).append(i)
+            else:
+                out[i] = packed_from_raw(raw, body_names)
+        for idx in groups.values():
+            h = self.handle(raws[idx[0]], body_names)
+            lens = [len(raws[i]) for i in idx]
+            seg = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+            rows = np.concatenate([raws[i].rows for i in idx], axis=0)
+            offsets = np.stack([raws[i].offsets for i in idx])
+            human = h.frames(rows, seg, offsets)
+            for k, i in enumerate(idx):
+                out[i] = human[k, : lens[k]].copy()
+        return out
+
+
+def _global_poses_names(bones: Sequence[str]) -> None:
+    for b in ("LeftFoot", "LeftToe", "RightFoot", "RightToe"):
+        list(bones).index(b)
+
+
+BVH_FRAMES = BvhFrames()      # the handles of this process

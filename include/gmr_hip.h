@@ -262,6 +262,42 @@ int gmr_smplx_compact_layout(const gmr_smplx_t* h, int32_t* pose_joints, int* np
 int gmr_smplx_align_compact_dev(gmr_smplx_t* h, int N, const float* d_pose_c, const float* d_joints_c, int Nout,
                                 const double* d_target_time, double* d_out, void* stream);
 
+/* ---- N2: BVH frame extraction (LAFAN1; the step in front of the loop of the BVH dataset driver) -------------------- */
+/* The topology of a BVH skeleton and the rows wanted per frame.  J <= 256 joints in file order (parents[0] = -1,
+ * 0 <= parents[j] < j: a BVH hierarchy is written depth first, so every parent precedes its children); `channels` is the
+ * layout of a motion row as extract.py:99-166 parses it -- 3: root translation, then 3 rotations per joint (ncol = 3 + 3 J;
+ * LAFAN1), 6: 3 translations and 3 rotations per joint (ncol = 6 J); `order` the Euler order of the rotation channels, a
+ * permutation of "xyz" ("zyx" for LAFAN1).  Output row k of a frame takes its position from joint sel_pos[k] and its
+ * orientation from joint sel_rot[k] (nsel <= 64): a body of the ik_config is (j, j), `LeftFootMod` (lafan1.py:28-33: foot
+ * position, toe orientation) is (LeftFoot, LeftToe).  Only the ancestor closure of the selected joints (<= 64 joints) is
+ * walked.  Clips with another topology use another handle. */
+typedef struct gmr_bvh gmr_bvh_t;
+int gmr_bvh_create(int J, const int32_t* parents, int channels, const char* order /* "zyx" ... */,
+                   int nsel, const int32_t* sel_pos, const int32_t* sel_rot, gmr_bvh_t** out);
+int gmr_bvh_destroy(gmr_bvh_t* h);
+int gmr_bvh_columns(const gmr_bvh_t* h);   /* doubles per motion row (ncol) */
+/* Replaces, for nclip clips in one call, the numeric half of load_lafan1_file (general_motion_retargeting/utils/lafan1.py:8-41):
+ * read_bvh's euler_to_quat + remove_quat_discontinuities (lafan_vendor/extract.py:155-166, lafan_vendor/utils.py:137-162,
+ * 251-268), quat_fk (utils.py:88-103), the Y-up cm -> Z-up m change of axes and units (lafan1.py:20-27) and the packing of
+ * the selected bodies:
+ *   rows      f64 [B][ncol]          the motion rows of the clips, concatenated, as the text parses (degrees, centimetres)
+ *   seg_start i32 [nclip + 1]        rows of clip c = [seg_start[c], seg_start[c + 1]); ascending from 0 to B
+ *   offsets   f64 [nclip][J][3]      the OFFSET of every joint, per clip (LAFAN1's subjects differ in bone lengths)
+ *   human     f64 [nclip][T][nsel][7] position xyz, orientation wxyz: the padded layout of gmr_job_t.human
+ * Frames t >= the clip's length are not written by the device entry point (the IK kernels never read them); frames beyond
+ * T are dropped.  seg_start is not trusted: whatever it holds, no access leaves the buffers.  The de-flip along time
+ * (sign_t = prod_{u <= t} sign <q_{u-1}, q_u>, strict) is a prefix scan inside the call, exact across any clip length.
+ * Results are the NumPy path's bits except for the last place of sin / cos (<= 1e-12 on every output).
+ * The scratch of a call (12 B per row) belongs to the handle, one block per HIP stream that has called, grown on demand
+ * (the only time the call waits: for its own stream) and freed by gmr_bvh_destroy: no allocation in steady state, and calls
+ * on different streams may be in flight together. */
+int gmr_bvh_frames_dev(gmr_bvh_t* h, int nclip, int B, const double* d_rows, const int32_t* d_seg_start,
+                       const double* d_offsets, int T, double* d_human, void* stream);    /* asynchronous */
+/* host buffers; checks seg_start (ascending from 0 to B, no clip longer than T); frames t >= a clip's length come back as
+ * zeros.  One call per handle at a time. */
+int gmr_bvh_frames(gmr_bvh_t* h, int nclip, int B, const double* rows, const int32_t* seg_start,
+                   const double* offsets, int T, double* human);
+
 /* ---- multi-GPU: one rank per GPU, ONE broadcast, no per-step collective ------------ */
 /* The reference parallelises over files with mp.Pool on one CPU (scripts/smplx_to_robot_dataset.py:241-242); here
  * streams shard over the ranks of one node and the only data that crosses ranks is the packed robot model + task set.
