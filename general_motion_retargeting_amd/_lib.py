@@ -86,6 +86,12 @@ _SIGS = {
     "gmr_smplx_compact_layout": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_int)]),
     "gmr_smplx_align_compact_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                               C.c_void_p]),
+    "gmr_smplx_batch_takes": (C.c_int, [C.c_void_p]),
+    "gmr_smplx_target_times": (C.c_int, [C.c_int, C.c_int, C.c_void_p]),
+    "gmr_smplx_batch_frames_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gmr_smplx_batch_frames": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "gmr_bvh_create": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "gmr_bvh_destroy": (C.c_int, [C.c_void_p]),
     "gmr_bvh_columns": (C.c_int, [C.c_void_p]),
@@ -543,6 +549,13 @@ class FkHandle:
             pass
 
 
+def smplx_target_times(N: int, nout: int) -> np.ndarray:
+    """``np.linspace(0, N - 1, nout)`` as the batch kernels compute it (``gmr_smplx_target_times``; host code, no GPU needed)"""
+    out = np.empty(int(nout), dtype=np.float64)
+    check(lib().gmr_smplx_target_times(int(N), int(nout), _ptr(out)))
+    return out
+
+
 class SmplxHandle:
     """Kinematic tree + joint selection behind gmr_smplx_create (N1: SMPL-X frame extraction)."""
 
@@ -616,6 +629,41 @@ class SmplxHandle:
     def joints_dev(self, N, d_j_rest, d_full_pose, d_transl, d_joints, stream=None):
         check(lib().gmr_smplx_joints_dev(self.handle, int(N), _d(d_j_rest), _d(d_full_pose), _d(d_transl), _d(d_joints),
                                          _s(stream)))
+
+    @property
+    def batch_takes(self) -> bool:
+        """whether :meth:`batch_frames_dev` / :meth:`batch_frames` take this selection (its ancestor closure inside joints 0..21)"""
+        return bool(lib().gmr_smplx_batch_takes(self.handle))
+
+    def batch_frames_dev(self, nclip, B, d_root_orient, d_pose_body, d_trans, d_src_start, d_nout, d_align, d_j_rest, d_clip_out,
+                         stream=None):
+        """``gmr_smplx_batch_frames_dev``: the packed frames of ``nclip`` clips (``B`` source frames, concatenated) written at the
+        device addresses of the table ``d_clip_out`` -- asynchronous, nothing comes back to the host."""
+        check(lib().gmr_smplx_batch_frames_dev(self.handle, int(nclip), int(B), _d(d_root_orient), _d(d_pose_body), _d(d_trans),
+                                               _d(d_src_start), _d(d_nout), _d(d_align), _d(d_j_rest), _d(d_clip_out), _s(stream)))
+
+    def batch_frames(self, root_orient, pose_body, trans, src_start, nout, align, j_rest, T=None):
+        """``gmr_smplx_batch_frames``: ``root_orient f32[B,3]``, ``pose_body f32[B,63]``, ``trans f32[B,3]`` of the clips
+        ``src_start i32[nclip + 1]`` with ``nout i32[nclip]`` output frames each, ``align`` (per clip: fps alignment or frame by
+        frame) and ``j_rest f64[nclip,J,3]`` -> ``human f64[nclip, T, rows, 7]`` (``T`` defaults to the largest ``nout``;
+        frames at or beyond ``nout[c]`` are zeros).  The bits of one :meth:`frames` call per clip."""
+        seg = np.ascontiguousarray(src_start, dtype=np.int32)
+        nclip = len(seg) - 1
+        root_orient = np.ascontiguousarray(root_orient, dtype=np.float32).reshape(-1, 3)
+        B = root_orient.shape[0]
+        pose_body = np.ascontiguousarray(pose_body, dtype=np.float32).reshape(B, 63)
+        trans = np.ascontiguousarray(trans, dtype=np.float32).reshape(B, 3)
+        nout = np.ascontiguousarray(nout, dtype=np.int32)
+        align = np.ascontiguousarray(align, dtype=np.uint8)
+        j_rest = np.ascontiguousarray(j_rest, dtype=np.float64)
+        if nclip < 0 or nout.shape != (nclip,) or align.shape != (nclip,) or j_rest.shape != (nclip, self.J, 3):
+            raise ValueError(f"nout, align must be [{nclip}], j_rest [{nclip}, {self.J}, 3]")
+        if T is None:
+            T = max(int(nout.max()) if nclip else 0, 1)
+        out = np.zeros((nclip, int(T), self.rows, 7), dtype=np.float64)
+        check(lib().gmr_smplx_batch_frames(self.handle, nclip, B, _ptr(root_orient), _ptr(pose_body), _ptr(trans), _ptr(seg), _ptr(nout),
+                                           _ptr(align), _ptr(j_rest), int(T), _ptr(out)))
+        return out
 
     def close(self):
         if self.handle:

@@ -355,6 +355,245 @@ __global__ __launch_bounds__(SX_BLOCK) void smplx_joints_kernel(SmplxProg P, int
   }
 }
 
+// ---- a ragged batch of clips straight from the AMASS arrays (gmr_smplx_batch_frames_dev) ----------------------------------
+// Two launches over the B concatenated source frames, lane = frame, 64 frames per block:
+//   smplx_batch_joints_kernel  lane = SOURCE frame.  The block's 64 pose_body rows are ONE contiguous range (64 x 252 B), copied
+//       flat into an LDS tile (16-byte loads, every fetched line consumed at once) and read back by row (stride 63 words: no bank
+//       conflict); root_orient and trans are 12-byte rows, read directly.  The walk is smplx_joints_kernel's over the ancestor
+//       closure of the selection only (a joint's transform depends on its ancestors alone, so the closure's joints get the bits
+//       of the all-joints walk).  It leaves what the second kernel reads as FRAME-MINOR planes in the call's scratch: the poses
+//       of the closure pose_t f32[P.n][3][Bp] in walk order and the joints of the output rows joints_t f32[P.nrow][3][Bp] --
+//       the compact layout of smplx_align_kernel, whose measured history (above) is why frame-major rows are not read there:
+//       an output frame's two source frames are 1 .. 8 rows apart, so a wavefront's rows span up to 130 KB.
+//   smplx_batch_align_kernel   lane = OUTPUT frame o of its clip, indexed in the SOURCE frames' index space (nout <= N for every
+//       clip, so lane b of clip c is output frame o = b - src_start[c], idle when o >= nout[c]: no second prefix array, and at
+//       120 -> 30 fps whole wavefronts leave at once).  smplx_align_kernel's arithmetic, `align` a per-clip run-time flag, the
+//       target time computed here (sx_target_time), the frame stored at clip_out[c] + o * nrow * 7.
+// Frame -> clip: binary search of src_start (the prefix array the caller has anyway; a clip may be shorter than a wavefront or
+// longer than thousands of blocks, so whole blocks per clip would idle most lanes of short clips).  The tables are not trusted:
+// the search ends after log2(nclip) steps whatever they hold, the clip's range is clamped into [0, B], and a lane outside its
+// clip's clamped range returns, so every load stays inside the B-frame inputs and the scratch.  A store goes to frame o <
+// min(nout[c], N_c) of clip_out[c].
+#define SX_BODY_JOINTS 22            // root_orient + pose_body: joints 0 .. 21
+#define SX_BODY_POSE 63              // floats per pose_body row
+
+// np.linspace(0, N - 1, Nout)[o] (utils/smpl.py:127): arange(Nout) * ((N - 1) / (Nout - 1)), the last one set to N - 1
+__host__ __device__ inline double sx_target_time(int o, int N, int Nout) {
+  if (Nout <= 1) return 0.0;
+  if (o == Nout - 1) return (double)(N - 1);
+  return (double)o * ((double)(N - 1) / (double)(Nout - 1));
+}
+
+// the last clip whose start is <= b (empty clips in front of it are skipped); always in [0, nclip - 1]
+__device__ __forceinline__ int sx_clip_of(const int32_t* __restrict__ src_start, int nclip, int b) {
+  int lo = 0, hi = nclip - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (src_start[mid] <= b) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+__global__ __launch_bounds__(SX_BLOCK) void smplx_batch_joints_kernel(SmplxProg P, int nclip, int B, size_t Bp, int nslot_lds,
+                                                                      const float* __restrict__ root_orient,
+                                                                      const float* __restrict__ pose_body,
+                                                                      const float* __restrict__ trans,
+                                                                      const int32_t* __restrict__ src_start,
+                                                                      const double* __restrict__ j_rest,
+                                                                      float* __restrict__ pose_t, float* __restrict__ joints_t) {
+  extern __shared__ __align__(16) double stack[];     // parked transforms [nslot_lds][12][SX_BLOCK], then the tile f32[64][63]
+  float* tile = reinterpret_cast<float*>(stack + (size_t)nslot_lds * 12 * SX_BLOCK);
+  const int lane = threadIdx.x;
+  const int b0 = blockIdx.x * SX_BLOCK, b = b0 + lane;
+  {
+    const int n = min(SX_BLOCK, B - b0) * SX_BODY_POSE;
+    const float* rows_in = pose_body + (size_t)b0 * SX_BODY_POSE;
+    for (int i = lane * 4; i < n; i += SX_BLOCK * 4) {
+      if (i + 3 < n) {
+        const f4u t = *reinterpret_cast<const f4u*>(rows_in + i);
+        tile[i] = t.x; tile[i + 1] = t.y; tile[i + 2] = t.z; tile[i + 3] = t.w;
+      } else {
+        for (int k = 0; i + k < n; k++) tile[i + k] = rows_in[i + k];
+      }
+    }
+  }
+  __syncthreads();                                     // the only barrier: every lane of the block reaches it
+  if (b >= B) return;
+  const int c = sx_clip_of(src_start, nclip, b);
+  const double* jr = j_rest + (size_t)c * P.J * 3;
+  const float* pr = tile + lane * SX_BODY_POSE;        // joint j >= 1: pr[3 (j - 1) + c]
+  const float* ro = root_orient + (size_t)b * 3;
+  const double tx = trans[(size_t)b * 3], ty = trans[(size_t)b * 3 + 1], tz = trans[(size_t)b * 3 + 2];
+  double Rc[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, pc[3] = {0, 0, 0};        // the transform of the previous step
+  const int rslot = P.nslot - 1;                                         // the innermost parking slot lives in registers
+  double Rs[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, ps[3] = {0, 0, 0};
+  for (int k = 0; k < P.n; k++) {
+    const int j = P.joint[k], d = P.depth[k], pj = P.parent[k];
+    // full_pose of the host path: concatenate, then `+ pose_mean` (zero on the body joints; -0.0f + 0.0f = +0.0f)
+    float fx, fy, fz;
+    if (j == 0) { fx = ro[0] + 0.0f; fy = ro[1] + 0.0f; fz = ro[2] + 0.0f; }                // (uniform)
+    else { const float* q = pr + 3 * (j - 1); fx = q[0] + 0.0f; fy = q[1] + 0.0f; fz = q[2] + 0.0f; }
+    pose_t[(size_t)(3 * k) * Bp + b] = fx;
+    pose_t[(size_t)(3 * k + 1) * Bp + b] = fy;
+    pose_t[(size_t)(3 * k + 2) * Bp + b] = fz;
+    const double vx = fx, vy = fy, vz = fz;
+    double rel[3];
+    if (k == 0) { rel[0] = jr[3 * j]; rel[1] = jr[3 * j + 1]; rel[2] = jr[3 * j + 2]; }     // the root's rest position
+    else { rel[0] = jr[3 * j] - jr[3 * pj]; rel[1] = jr[3 * j + 1] - jr[3 * pj + 1]; rel[2] = jr[3 * j + 2] - jr[3 * pj + 2]; }
+    const double ax = vx + 1e-8, ay = vy + 1e-8, az = vz + 1e-8;
+    const double ang = sqrt(ax * ax + ay * ay + az * az);
+    const double x = vx / ang, y = vy / ang, z = vz / ang, s = sin(ang), c1 = 1.0 - cos(ang);
+    const double K[9] = {0, -z, y, z, 0, -x, -y, x, 0};
+    double Rl[9];
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+      for (int e = 0; e < 3; e++) {
+        double acc = 0;
+#pragma unroll
+        for (int m = 0; m < 3; m++) acc += K[a * 3 + m] * K[m * 3 + e];
+        Rl[a * 3 + e] = (a == e ? 1.0 : 0.0) + s * K[a * 3 + e] + c1 * acc;
+      }
+    double Rg[9], pg[3];
+    if (d == 0) {
+#pragma unroll
+      for (int i = 0; i < 9; i++) Rg[i] = Rl[i];
+      pg[0] = rel[0]; pg[1] = rel[1]; pg[2] = rel[2];
+    } else {
+      double Rp[9], pp[3];
+      const int ld = P.load[k];                       // (uniform)
+      if (ld == rslot) {
+#pragma unroll
+        for (int i = 0; i < 9; i++) Rp[i] = Rs[i];
+#pragma unroll
+        for (int i = 0; i < 3; i++) pp[i] = ps[i];
+      } else if (ld >= 0) {
+        const double* sp = stack + (size_t)ld * 12 * SX_BLOCK + lane;
+#pragma unroll
+        for (int i = 0; i < 9; i++) Rp[i] = sp[i * SX_BLOCK];
+#pragma unroll
+        for (int i = 0; i < 3; i++) pp[i] = sp[(9 + i) * SX_BLOCK];
+      } else {
+#pragma unroll
+        for (int i = 0; i < 9; i++) Rp[i] = Rc[i];
+#pragma unroll
+        for (int i = 0; i < 3; i++) pp[i] = pc[i];
+      }
+#pragma unroll
+      for (int a = 0; a < 3; a++) {
+#pragma unroll
+        for (int e = 0; e < 3; e++) {
+          double acc = 0;
+#pragma unroll
+          for (int m = 0; m < 3; m++) acc += Rp[a * 3 + m] * Rl[m * 3 + e];
+          Rg[a * 3 + e] = acc;
+        }
+        pg[a] = pp[a] + Rp[a * 3] * rel[0] + Rp[a * 3 + 1] * rel[1] + Rp[a * 3 + 2] * rel[2];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 9; i++) Rc[i] = Rg[i];
+#pragma unroll
+    for (int i = 0; i < 3; i++) pc[i] = pg[i];
+    const int sv = P.save[k];                         // (uniform)
+    if (sv == rslot) {
+#pragma unroll
+      for (int i = 0; i < 9; i++) Rs[i] = Rg[i];
+#pragma unroll
+      for (int i = 0; i < 3; i++) ps[i] = pg[i];
+    } else if (sv >= 0) {
+      double* so = stack + (size_t)sv * 12 * SX_BLOCK + lane;
+#pragma unroll
+      for (int i = 0; i < 9; i++) so[i * SX_BLOCK] = Rg[i];
+#pragma unroll
+      for (int i = 0; i < 3; i++) so[(9 + i) * SX_BLOCK] = pg[i];
+    }
+    const int r = P.row[k];
+    if (r >= 0) {
+      joints_t[(size_t)(3 * r) * Bp + b] = (float)(pg[0] + tx);
+      joints_t[(size_t)(3 * r + 1) * Bp + b] = (float)(pg[1] + ty);
+      joints_t[(size_t)(3 * r + 2) * Bp + b] = (float)(pg[2] + tz);
+    }
+  }
+}
+
+__global__ __launch_bounds__(SX_BLOCK) void smplx_batch_align_kernel(SmplxProg P, int nclip, int B, size_t Bp,
+                                                                     const int32_t* __restrict__ src_start,
+                                                                     const int32_t* __restrict__ nout,
+                                                                     const uint8_t* __restrict__ align,
+                                                                     const float* __restrict__ pose_t,
+                                                                     const float* __restrict__ joints_t,
+                                                                     double* const* __restrict__ clip_out) {
+  extern __shared__ __align__(16) double stack[];   // [max_depth][4][SX_BLOCK]
+  const int lane = threadIdx.x;
+  const int b = blockIdx.x * SX_BLOCK + lane;
+  if (b >= B) return;                                // no barriers in this kernel: columns are lane-private
+  const int c = sx_clip_of(src_start, nclip, b);
+  const int s0 = min(max(src_start[c], 0), B), s1 = min(max(src_start[c + 1], s0), B);
+  const int N = s1 - s0, o = b - s0, Nout = nout[c];
+  if (o < 0 || o >= N || o >= Nout) return;
+  const bool al = align[c] != 0;
+  if (al && N < 2) return;                           // (the host entry point refuses such a clip)
+  double* dst = clip_out[c];
+  if (!dst) return;
+  double t = 0.0, alpha = 0.0;
+  int idx1 = o, idx2 = o, lo = o, hi = o;
+  if (al) {
+    t = sx_target_time(o, N, Nout);
+    idx1 = (int)floor(t);
+    idx1 = min(max(idx1, 0), N - 1);
+    idx2 = min(idx1 + 1, N - 1);
+    alpha = t - (double)idx1;
+    int ss = (int)ceil(t);
+    ss = min(max(ss, 1), N - 1);
+    lo = ss - 1; hi = ss;
+  }
+  const size_t pstep = Bp, pj3 = 3 * Bp;
+  const float* p1 = pose_t + s0 + idx1;
+  const float* p2 = pose_t + s0 + idx2;
+  const float* jl = joints_t + s0 + lo;
+  const float* jh = joints_t + s0 + hi;
+  double* orow = dst + (size_t)o * P.nrow * 7;
+  for (int k = 0; k < P.n; k++) {
+    const int d = P.depth[k];
+    q4 ql;
+    const float* a1 = p1 + (size_t)k * pj3;
+    if (al) {
+      const float* a2 = p2 + (size_t)k * pj3;
+      q4 qa = sx_from_rotvec((double)a1[0], (double)a1[pstep], (double)a1[2 * pstep]);
+      q4 qb = sx_from_rotvec((double)a2[0], (double)a2[pstep], (double)a2[2 * pstep]);
+      ql = sx_slerp_local(qa, qb, alpha);
+    } else {
+      ql = sx_from_rotvec((double)a1[0], (double)a1[pstep], (double)a1[2 * pstep]);
+    }
+    q4 qg = ql;
+    if (d > 0) {
+      const double* s = stack + (size_t)(d - 1) * 4 * SX_BLOCK + lane;
+      qg = sx_compose(q4{s[0], s[SX_BLOCK], s[2 * SX_BLOCK], s[3 * SX_BLOCK]}, ql);
+    }
+    {
+      double* s = stack + (size_t)d * 4 * SX_BLOCK + lane;
+      s[0] = qg.x; s[SX_BLOCK] = qg.y; s[2 * SX_BLOCK] = qg.z; s[3 * SX_BLOCK] = qg.w;
+    }
+    const int r = P.row[k];
+    if (r >= 0) {
+      double* w = orow + r * 7;
+#pragma unroll
+      for (int e = 0; e < 3; e++) {
+        if (al) {
+          const float ylo = jl[(size_t)r * pj3 + e * pstep], yhi = jh[(size_t)r * pj3 + e * pstep];
+          const float df = yhi - ylo;                                  // float32 difference (interp1d on a float32 y)
+          const double slope = (double)df / (double)(hi - lo);
+          w[e] = slope * (t - (double)lo) + (double)ylo;
+        } else {
+          w[e] = (double)jl[(size_t)r * pj3 + e * pstep];
+        }
+      }
+      w[3] = qg.w; w[4] = qg.x; w[5] = qg.y; w[6] = qg.z;
+    }
+  }
+}
+
 // DFS program over the joints in `keep` (all when empty); rows from `row_of` (-1 = not written)
 static bool make_prog(int J, const int32_t* parents, const std::vector<char>& keep, const std::vector<int>& row_of,
                       int nrow, SmplxProg* P) {
@@ -410,6 +649,21 @@ struct gmr_smplx {
   std::mutex mu;                 // the host entry points of one handle run one at a time (they share d_jrest and ws)
   char* planes = nullptr;        // gmr_smplx_joints_dev: the transposed poses and joints of the launch in flight (one stream at
   size_t planes_bytes = 0;       //  a time per handle)
+  // gmr_smplx_batch_frames_dev: takes the handle only when the selection's ancestor closure lies inside the body joints;
+  // one grow-only scratch block per HIP stream that has called (the gmr_bvh pattern: growing a block waits for its own
+  // stream alone; batch_mu orders the host side)
+  bool batch_ok = false;
+  int batch_lds_joints = 0, batch_lds_align = 0, batch_nslot_lds = 1;
+  struct Ws {
+    hipStream_t stream;
+    char* d;
+    size_t bytes;
+  };
+  std::mutex batch_mu;
+  std::vector<Ws> batch_ws;
+  std::mutex batch_host_mu;      // gmr_smplx_batch_frames: device staging of the host buffers, grown on demand and kept
+  char* batch_host_ws = nullptr;
+  size_t batch_host_ws_bytes = 0;
 };
 
 static hipError_t smplx_workspace(gmr_smplx* h, size_t bytes, char** out) {
@@ -469,6 +723,18 @@ int gmr_smplx_create(int J, const int32_t* parents, int nsel, const int32_t* sel
     e = hipFuncSetAttribute((const void*)gmr::smplx_joints_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_joints);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gmr::smplx_joints_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_joints);
   }
+  // the batch entry points read root_orient + pose_body, the poses of joints 0 .. 21
+  h->batch_ok = nsel > 0;
+  for (int k = 0; k < h->sel.n; k++)
+    if (h->sel.joint[k] >= SX_BODY_JOINTS) h->batch_ok = false;
+  h->batch_nslot_lds = std::max(h->sel.nslot - 1, 1);
+  h->batch_lds_joints = h->batch_nslot_lds * 12 * SX_BLOCK * 8 + SX_BLOCK * SX_BODY_POSE * (int)sizeof(float);
+  h->batch_lds_align = h->sel.max_depth * 4 * SX_BLOCK * 8;
+  if (h->batch_lds_joints > 160 * 1024 - 1024) h->batch_ok = false;
+  if (e == hipSuccess && h->batch_ok && h->batch_lds_joints > 48 * 1024)
+    e = hipFuncSetAttribute((const void*)gmr::smplx_batch_joints_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, h->batch_lds_joints);
+  if (e == hipSuccess && h->batch_ok && h->batch_lds_align > 48 * 1024)
+    e = hipFuncSetAttribute((const void*)gmr::smplx_batch_align_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, h->batch_lds_align);
   if (e == hipSuccess) e = hipMalloc((void**)&h->d_jrest, (size_t)J * 3 * sizeof(double));
   if (e != hipSuccess) { delete h; return gmr_fail(GMR_ERR_HIP, "gmr_smplx_create: %s", hipGetErrorString(e)); }
   *out = h;
@@ -480,6 +746,9 @@ int gmr_smplx_destroy(gmr_smplx_t* h) {
   (void)hipFree(h->d_jrest);
   if (h->ws) (void)hipFree(h->ws);
   if (h->planes) (void)hipFree(h->planes);
+  for (auto& w : h->batch_ws)
+    if (w.d) (void)hipFree(w.d);          // (hipFree waits for the device: nothing of this handle is in flight afterwards)
+  if (h->batch_host_ws) (void)hipFree(h->batch_host_ws);
   delete h;
   return GMR_OK;
 }
@@ -667,6 +936,124 @@ int gmr_smplx_align(gmr_smplx_t* h, int N, int jstride, const float* full_pose, 
   if (rc == GMR_OK) rc = gmr_smplx_align_compact_dev(h, N, d_pose, d_j, Nout, target_time ? d_t : nullptr, d_o, nullptr);
   if (rc == GMR_OK && (e = hipMemcpy(out, d_o, nb_out, hipMemcpyDeviceToHost)) != hipSuccess)
     rc = gmr_fail(GMR_ERR_HIP, "gmr_smplx_align: %s", hipGetErrorString(e));
+  return rc;
+}
+
+// ---- ragged batches --------------------------------------------------------------------------------------------------------
+int gmr_smplx_batch_takes(const gmr_smplx_t* h) { return h && h->batch_ok ? 1 : 0; }
+
+int gmr_smplx_target_times(int N, int Nout, double* out) {
+  if (N < 1 || Nout < 0 || (Nout > 0 && !out)) return gmr_fail(GMR_ERR_ARG, "gmr_smplx_target_times: N >= 1, Nout >= 0");
+  for (int o = 0; o < Nout; o++) out[o] = gmr::sx_target_time(o, N, Nout);
+  return GMR_OK;
+}
+
+int gmr_smplx_batch_frames_dev(gmr_smplx_t* h, int nclip, int B, const float* d_root_orient, const float* d_pose_body,
+                               const float* d_trans, const int32_t* d_src_start, const int32_t* d_nout, const uint8_t* d_align,
+                               const double* d_j_rest, double* const* d_clip_out, void* stream) {
+  if (!h) return gmr_fail(GMR_ERR_ARG, "gmr_smplx_batch_frames_dev: null handle");
+  if (!h->batch_ok)
+    return gmr_fail(GMR_ERR_ARG, "gmr_smplx_batch_frames_dev: the selection reaches beyond the body joints 0 .. %d (root_orient + pose_body)",
+                    SX_BODY_JOINTS - 1);
+  if (nclip < 0 || B < 0) return gmr_fail(GMR_ERR_ARG, "gmr_smplx_batch_frames_dev: negative nclip / B");
+  if (nclip == 0 || B == 0) return GMR_OK;
+  if (!d_root_orient || !d_pose_body || !d_trans || !d_src_start || !d_nout || !d_align || !d_j_rest || !d_clip_out)
+    return gmr_fail(GMR_ERR_ARG, "gmr_smplx_batch_frames_dev: null buffer");
+  const gmr::SmplxProg& P = h->sel;
+  // scratch: pose_t f32[P.n][3][Bp], joints_t f32[P.nrow][3][Bp]
+  const size_t Bp = ((size_t)B + 63) / 64 * 64;
+  const size_t o_pose = 0, o_joints = o_pose + (size_t)P.n * 3 * Bp * sizeof(float), total = o_joints + (size_t)P.nrow * 3 * Bp * sizeof(float);
+  hipStream_t st = (hipStream_t)stream;
+  std::lock_guard<std::mutex> lock(h->batch_mu);
+  gmr_smplx::Ws* w = nullptr;
+  for (auto& e : h->batch_ws)
+    if (e.stream == st) w = &e;
+  if (!w) {
+    h->batch_ws.push_back(gmr_smplx::Ws{st, nullptr, 0});
+    w = &h->batch_ws.back();
+  }
+  if (w->bytes < total) {
+    if (w->d) {
+      hipError_t e = hipStreamSynchronize(st);       // earlier calls on this stream are the only users of the block
+      if (e == hipSuccess) e = hipFree(w->d);
+      if (e != hipSuccess) return gmr_fail(GMR_ERR_HIP, "gmr_smplx_batch_frames_dev: %s", hipGetErrorString(e));
+      w->d = nullptr;
+      w->bytes = 0;
+    }
+    const size_t want = total + total / 4;
+    hipError_t e = hipMalloc((void**)&w->d, want);
+    if (e != hipSuccess) return gmr_fail(GMR_ERR_HIP, "gmr_smplx_batch_frames_dev: %s", hipGetErrorString(e));
+    w->bytes = want;
+  }
+  float* pose_t = (float*)(w->d + o_pose);
+  float* joints_t = (float*)(w->d + o_joints);
+  const dim3 grid((unsigned)(Bp / SX_BLOCK)), block(SX_BLOCK);
+  hipLaunchKernelGGL(gmr::smplx_batch_joints_kernel, grid, block, h->batch_lds_joints, st, P, nclip, B, Bp, h->batch_nslot_lds,
+                     d_root_orient, d_pose_body, d_trans, d_src_start, d_j_rest, pose_t, joints_t);
+  hipLaunchKernelGGL(gmr::smplx_batch_align_kernel, grid, block, h->batch_lds_align, st, P, nclip, B, Bp, d_src_start, d_nout, d_align,
+                     pose_t, joints_t, d_clip_out);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return gmr_fail(GMR_ERR_HIP, "gmr_smplx_batch_frames_dev: %s", hipGetErrorString(e));
+  return GMR_OK;
+}
+
+int gmr_smplx_batch_frames(gmr_smplx_t* h, int nclip, int B, const float* root_orient, const float* pose_body, const float* trans,
+                           const int32_t* src_start, const int32_t* nout, const uint8_t* align, const double* j_rest, int T,
+                           double* human) {
+  if (!h) return gmr_fail(GMR_ERR_ARG, "gmr_smplx_batch_frames: null handle");
+  if (!h->batch_ok)
+    return gmr_fail(GMR_ERR_ARG, "gmr_smplx_batch_frames: the selection reaches beyond the body joints 0 .. %d (root_orient + pose_body)",
+                    SX_BODY_JOINTS - 1);
+  if (nclip < 0 || B < 0 || T < 0) return gmr_fail(GMR_ERR_ARG, "gmr_smplx_batch_frames: negative nclip / B / T");
+  if (nclip == 0) return B == 0 ? GMR_OK : gmr_fail(GMR_ERR_ARG, "gmr_smplx_batch_frames: B = %d frames but no clip", B);
+  if (!src_start || !nout || !align || !j_rest || !human || (B > 0 && (!root_orient || !pose_body || !trans)))
+    return gmr_fail(GMR_ERR_ARG, "gmr_smplx_batch_frames: null buffer");
+  if (src_start[0] != 0 || src_start[nclip] != B) return gmr_fail(GMR_ERR_ARG, "gmr_smplx_batch_frames: src_start runs from 0 to B = %d", B);
+  for (int c = 0; c < nclip; c++) {
+    const long long n = (long long)src_start[c + 1] - src_start[c];
+    if (n < 0) return gmr_fail(GMR_ERR_ARG, "gmr_smplx_batch_frames: src_start descends at clip %d", c);
+    if (align[c] && n < 2) return gmr_fail(GMR_ERR_ARG, "gmr_smplx_batch_frames: clip %d: fps alignment needs at least two source frames", c);
+    if (nout[c] < 0 || nout[c] > n || nout[c] > T)
+      return gmr_fail(GMR_ERR_ARG, "gmr_smplx_batch_frames: clip %d: nout = %d of %lld source frames, T = %d", c, nout[c], n, T);
+    if (!align[c] && nout[c] != n) return gmr_fail(GMR_ERR_ARG, "gmr_smplx_batch_frames: clip %d: without alignment nout must equal N", c);
+  }
+  const int nrow = h->sel.nrow, J = h->J;
+  auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+  const size_t nb_ro = (size_t)B * 3 * 4, nb_pb = (size_t)B * SX_BODY_POSE * 4, nb_seg = (size_t)(nclip + 1) * 4, nb_no = (size_t)nclip * 4,
+               nb_al = (size_t)nclip, nb_jr = (size_t)nclip * J * 3 * 8, nb_tab = (size_t)nclip * sizeof(double*),
+               nb_out = (size_t)nclip * T * nrow * 7 * 8;
+  if (nb_out == 0 || B == 0) { if (nb_out) memset(human, 0, nb_out); return GMR_OK; }
+  const size_t o_ro = 0, o_pb = o_ro + up(nb_ro), o_tr = o_pb + up(nb_pb), o_seg = o_tr + up(nb_ro), o_no = o_seg + up(nb_seg),
+               o_al = o_no + up(nb_no), o_jr = o_al + up(nb_al), o_tab = o_jr + up(nb_jr), o_out = o_tab + up(nb_tab), total = o_out + up(nb_out);
+  std::lock_guard<std::mutex> guard(h->batch_host_mu);
+  hipError_t e = hipSuccess;
+  if (h->batch_host_ws_bytes < total) {
+    if (h->batch_host_ws) (void)hipFree(h->batch_host_ws);
+    h->batch_host_ws = nullptr;
+    h->batch_host_ws_bytes = 0;
+    const size_t want = total + total / 4;
+    if ((e = hipMalloc((void**)&h->batch_host_ws, want)) != hipSuccess) return gmr_fail(GMR_ERR_HIP, "gmr_smplx_batch_frames: %s", hipGetErrorString(e));
+    h->batch_host_ws_bytes = want;
+  }
+  char* d = h->batch_host_ws;
+  std::vector<double*> tab(nclip);
+  for (int c = 0; c < nclip; c++) tab[c] = (double*)(d + o_out) + (size_t)c * T * nrow * 7;
+  // frames at or beyond nout[c] come back as zeros (the kernels do not write them)
+  if ((e = hipMemset(d + o_out, 0, nb_out)) != hipSuccess ||
+      (e = hipMemcpy(d + o_ro, root_orient, nb_ro, hipMemcpyHostToDevice)) != hipSuccess ||
+      (e = hipMemcpy(d + o_pb, pose_body, nb_pb, hipMemcpyHostToDevice)) != hipSuccess ||
+      (e = hipMemcpy(d + o_tr, trans, nb_ro, hipMemcpyHostToDevice)) != hipSuccess ||
+      (e = hipMemcpy(d + o_seg, src_start, nb_seg, hipMemcpyHostToDevice)) != hipSuccess ||
+      (e = hipMemcpy(d + o_no, nout, nb_no, hipMemcpyHostToDevice)) != hipSuccess ||
+      (e = hipMemcpy(d + o_al, align, nb_al, hipMemcpyHostToDevice)) != hipSuccess ||
+      (e = hipMemcpy(d + o_jr, j_rest, nb_jr, hipMemcpyHostToDevice)) != hipSuccess ||
+      (e = hipMemcpy(d + o_tab, tab.data(), nb_tab, hipMemcpyHostToDevice)) != hipSuccess)
+    return gmr_fail(GMR_ERR_HIP, "gmr_smplx_batch_frames: %s", hipGetErrorString(e));
+  int rc = gmr_smplx_batch_frames_dev(h, nclip, B, (const float*)(d + o_ro), (const float*)(d + o_pb), (const float*)(d + o_tr),
+                                      (const int32_t*)(d + o_seg), (const int32_t*)(d + o_no), (const uint8_t*)(d + o_al),
+                                      (const double*)(d + o_jr), (double* const*)(d + o_tab), nullptr);
+  if (rc == GMR_OK && (e = hipMemcpy(human, d + o_out, nb_out, hipMemcpyDeviceToHost)) != hipSuccess)
+    rc = gmr_fail(GMR_ERR_HIP, "gmr_smplx_batch_frames: %s", hipGetErrorString(e));
   return rc;
 }
 

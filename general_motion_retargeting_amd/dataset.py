@@ -101,6 +101,15 @@ def bvh_path() -> str:
     return post_path()
 
 
+def smplx_path() -> str:
+    """``"device"`` or ``"host"``: where the SMPL-X drivers compute the packed frames of a batch.  ``"device"`` (the raw arrays of
+    all clips uploaded ragged, ONE ``gmr_smplx_batch_frames_dev`` call in front of the IK launch) needs a GPU and the device
+    post-processing (:func:`post_path`); ``GMR_DATASET_SMPLX=host`` keeps one ``gmr_smplx_frames`` call per clip."""
+    if os.environ.get("GMR_DATASET_SMPLX", "device").strip().lower() == "host":
+        return "host"
+    return post_path()
+
+
 class PinnedPool:
     """Page-locked output blocks for batches whose results are handed out as views.  A block is taken for one batch; it
     comes back when the LAST array viewing it has died (a finalizer on the buffer the arrays are views of), so a dict kept
@@ -174,6 +183,48 @@ class DevicePost:
             blk = self._pin[name] = _lib.pinned_empty((need + need // 2 + 8,), np.uint8)
         return blk[:need].view(dtype).reshape(shape)
 
+    def _stage_smplx(self, jobs: Sequence[Dict]):
+        """The raw SMPL-X clips of all jobs that carry ``"smplx"``, per handle: one page-locked block (poses, translations, the
+        two tables, flags, rest joints and the per-clip destination addresses inside the jobs' ``human_{i}`` device buffers)
+        that goes up in ONE copy.  Returns ``([(handle, nclip, B, device block, offsets, staging)], {job index: human buffer})``."""
+        groups: Dict[int, tuple] = {}
+        d_human: Dict[int, object] = {}
+        for i, j in enumerate(jobs):
+            if "smplx" not in j:
+                continue
+            sx, sol = j["smplx"], j["solver"]
+            S, T = len(j["lens"]), max(int(j["T"]), 1)
+            assert len(sx["clips"]) == S and sx["handle"].rows == sol.nhuman and sx["handle"].batch_takes
+            d_human[i] = self._d(f"human_{i}", S * T * sol.nhuman * 56)
+            groups.setdefault(id(sx["handle"]), (sx["handle"], []))[1].extend((i, k, T, e) for k, e in enumerate(sx["clips"]))
+        up = lambda x: (int(x) + 255) // 256 * 256            # noqa: E731
+        calls = []
+        for gi, (h, members) in enumerate(groups.values()):
+            n, frame_bytes = len(members), h.rows * 56
+            B = sum(e["N"] for _, _, _, e in members)
+            fields = (("ro", np.float32, (B, 3)), ("pb", np.float32, (B, 63)), ("tr", np.float32, (B, 3)), ("seg", np.int32, (n + 1,)),
+                      ("nout", np.int32, (n,)), ("align", np.uint8, (n,)), ("jrest", np.float64, (n, h.J, 3)), ("tab", np.uint64, (n,)))
+            offs, total = {}, 0
+            for k, dt, shape in fields:
+                offs[k] = total
+                total += up(int(np.prod(shape)) * np.dtype(dt).itemsize)
+            stage = self.pinned(f"smplx_in_{gi}", (total,), np.uint8)
+            v = {k: stage[offs[k]: offs[k] + int(np.prod(shape)) * np.dtype(dt).itemsize].view(dt).reshape(shape) for k, dt, shape in fields}
+            a = 0
+            v["seg"][0] = 0
+            for m, (i, k, T, e) in enumerate(members):
+                N = e["N"]
+                assert 0 <= e["nout"] <= min(N, T) and int(jobs[i]["lens"][k]) == e["nout"] and (e["align"] or e["nout"] == N)
+                v["ro"][a:a + N] = e["root_orient"]
+                v["pb"][a:a + N] = e["pose_body"]
+                v["tr"][a:a + N] = e["trans"]
+                a += N
+                v["seg"][m + 1] = a
+                v["nout"][m], v["align"][m], v["jrest"][m] = e["nout"], e["align"], e["j_rest"]
+                v["tab"][m] = d_human[i].ptr.value + k * T * frame_bytes
+            calls.append((h, n, B, self._d(f"smplx_in_{gi}", total), offs, stage))
+        return calls, d_human
+
     def run(self, jobs: Sequence[Dict], km: KinematicsModel, ik_flags: int = 0, height_adjust: bool = True,
             root_origin_offset: bool = True, ground_offset: float = 0.0, timing: Optional[Dict[str, float]] = None):
         """``jobs`` = ``[{"solver", "human": f64[S,T,nhuman,7] (page-locked for an asynchronous copy), "lens": i32[S],
@@ -181,7 +232,10 @@ class DevicePost:
         ``"bvh"`` = ``[{"handle": _lib.BvhHandle, "rows": f64[B,ncol] (page-locked), "offsets": f64[n,J,3], "clips": [index in
         lens, ...], "lens": [...]}]`` (one entry per topology) and optionally ``"packed"`` = ``[(index, f64[n,nhuman,7])]``: the
         raw rows are uploaded ragged and ``gmr_bvh_frames_dev`` writes ``human`` on the device, on the same stream, in front
-        of the IK launch (inside the batch the clips are ordered by topology; the results come back in the job's order).  Returns ``(root_pos, root_rot, dof_pos, local_body_pos, spans, status)``:
+        of the IK launch (inside the batch the clips are ordered by topology; the results come back in the job's order).  A job
+        of raw SMPL-X clips carries ``"T"`` and ``"smplx"`` = ``{"handle": _lib.SmplxHandle, "clips": [utils.smpl.smplx_raw_clip
+        entry per clip of lens]}``: the arrays of ALL such jobs go up as one ragged block and one ``gmr_smplx_batch_frames_dev``
+        call per handle writes every job's ``human`` through a table of per-clip addresses.  Returns ``(root_pos, root_rot, dof_pos, local_body_pos, spans, status)``:
         the four arrays are views of one pool block, ``spans[j][k] = (a, b)`` are the rows of clip k of job j, ``status[j]``
         the IK status words of job j."""
         import ctypes as C
@@ -225,6 +279,7 @@ class DevicePost:
         total = o_st + up(nclip * 4)
         d_out = self._d("out", total)
         base = d_out.ptr.value
+        sx_calls, sx_human = self._stage_smplx(jobs)
         ev[0].record(st)
         launch, sources, d_status, clip, bvh_calls = [], [], [], 0, []
         h2d = lambda dst, src: _lib.check(L.gmr_memcpy_h2d(dst, src.ctypes.data_as(C.c_void_p), src.nbytes, st.ptr))   # noqa: E731
@@ -258,6 +313,9 @@ class DevicePost:
                             copies.append((C.c_void_p(d_h.ptr.value + pos * T * frame_bytes), stage[a:a + len(p)]))
                         a += len(p)
                         pos += 1
+            elif "smplx" in j:
+                S, T, copies = len(dlens[i]), max(int(j["T"]), 1), []
+                d_h = sx_human[i]                                      # (frames at or beyond a clip's nout stay stale: never read)
             else:
                 human = j["human"]
                 S, T = human.shape[:2]
@@ -276,9 +334,14 @@ class DevicePost:
             launch.append((sol, S, T, d_q0, d_h, d_len, d_q, d_ns, d_status[-1]))
             sources.append((S, T, d_q, d_len))
             clip += S
+        for _, _, _, d_in, _, stage in sx_calls:
+            h2d(d_in.ptr, stage)
         ev[1].record(st)
         for h, n, B, d_rows, d_seg, d_off, T, d_dst in bvh_calls:
             h.frames_dev(n, B, d_rows, d_seg, d_off, T, d_dst, st)
+        for h, n, B, d_in, offs, _ in sx_calls:
+            at = lambda k: C.c_void_p(d_in.ptr.value + offs[k])          # noqa: E731
+            h.batch_frames_dev(n, B, at("ro"), at("pb"), at("tr"), at("seg"), at("nout"), at("align"), at("jrest"), at("tab"), st)
         ev[5].record(st)
         _lib.retarget_group_dev(launch, ik_flags, st)
         ev[2].record(st)
@@ -299,7 +362,7 @@ class DevicePost:
         st.sync()
         if timing is not None:
             for k, a, b in (("h2d", 0, 1), ("frames", 1, 5), ("ik", 5, 2), ("post", 2, 3), ("d2h", 3, 4)):
-                if k != "frames" or bvh_calls:
+                if k != "frames" or bvh_calls or sx_calls:
                     timing[k] = timing.get(k, 0.0) + ev[a].elapsed_ms(ev[b]) * 1e-3
         view = lambda off, dtype, shape: np.frombuffer(buf, dtype=dtype, count=int(np.prod(shape)), offset=off).reshape(shape)   # noqa: E731
         status_all = view(o_st, np.int32, (nclip,)).copy()
@@ -975,30 +1038,47 @@ def _load_smplx_raw(f):
 
 
 def retarget_smplx_loaded(raws: Sequence[Dict], smplx_body_model_path: str, tgt_robot: str, tgt_fps: int = 30,
-                          height_adjust: bool = True, root_origin_offset: bool = True) -> List[Optional[Dict]]:
+                          height_adjust: bool = True, root_origin_offset: bool = True,
+                          timing: Optional[Dict[str, float]] = None) -> List[Optional[Dict]]:
     """``process_file`` (smplx_to_robot_dataset.py:39-146) for many already-read files: joints-only body model and fps
-    alignment on the device per clip, the clips grouped by human height (a file's height comes from its betas, :36-39)
-    into ONE group launch, two FK launches for the post-processing of all clips together."""
+    alignment on the device, the clips grouped by human height (a file's height comes from its betas, :36-39) into ONE group
+    launch, two FK launches for the post-processing of all clips together.  On the device path (:func:`smplx_path`, and every
+    body model of the batch one that ``utils.smpl.smplx_device_takes``) the files' arrays go up as they are and ONE
+    ``gmr_smplx_batch_frames_dev`` call writes the packed frames of all clips where the IK kernels read them; otherwise one
+    ``gmr_smplx_frames`` call per clip and a padded upload -- the same bits.  ``timing`` accumulates the seconds of the stages."""
+    import time
     from . import _lib
     from .utils import smpl
-    packed, fps_of, height = {}, {}, {}
+    t0 = time.perf_counter()
+    packed, fps_of, height, bms = {}, {}, {}, {}
     gmr_of: Dict[float, GeneralMotionRetargeting] = {}
     for i, d in enumerate(raws):
-        bm = smpl.body_model_for(smplx_body_model_path, str(d["gender"]))
+        bms[i] = smpl.body_model_for(smplx_body_model_path, str(d["gender"]))
         betas = np.asarray(d["betas"])
-        h = float(1.66 + 0.1 * (betas[0] if betas.ndim == 1 else betas[0, 0]))
-        g = gmr_of.get(h)
-        if g is None:
-            g = gmr_of[h] = GeneralMotionRetargeting("smplx", tgt_robot, actual_human_height=h)
-        packed[i], fps_of[i] = smpl.smplx_frames_packed_fused(g, d, bm, tgt_fps=tgt_fps)      # body model + alignment, one call
-        height[i] = h
+        h = height[i] = float(1.66 + 0.1 * (betas[0] if betas.ndim == 1 else betas[0, 0]))
+        if h not in gmr_of:
+            gmr_of[h] = GeneralMotionRetargeting("smplx", tgt_robot, actual_human_height=h)
     device = post_path() == "device" and bool(raws)
-    dp = _smplx_device_post(next(iter(gmr_of.values())).xml_file) if device else None
+    any_g = next(iter(gmr_of.values()), None)
+    raw = device and smplx_path() == "device" and all(smpl.smplx_device_takes(bm, any_g) for bm in {id(b): b for b in bms.values()}.values())
+    for i, d in enumerate(raws):
+        if raw:         # nothing per frame on the host: the arrays as float32, the frame counts, the subject's rest joints
+            packed[i] = smpl.smplx_raw_clip(d, bms[i], tgt_fps)
+            fps_of[i] = packed[i]["aligned_fps"]
+        else:
+            packed[i], fps_of[i] = smpl.smplx_frames_packed_fused(gmr_of[height[i]], d, bms[i], tgt_fps=tgt_fps)      # body model + alignment, one call
+    t1 = time.perf_counter()
+    dp = _smplx_device_post(any_g.xml_file) if device else None
     jobs, members = [], []
     for n, (h, g) in enumerate(gmr_of.items()):
         idxs = [i for i in range(len(raws)) if height[i] == h]
-        lens = np.array([packed[i].shape[0] for i in idxs], dtype=np.int32)
+        lens = np.array([packed[i]["nout"] if raw else packed[i].shape[0] for i in idxs], dtype=np.int32)
         T = max(int(lens.max()), 1)
+        members.append((idxs, lens))
+        if raw:
+            jobs.append({"solver": g.hip_solver, "T": T, "lens": lens, "q0": g.model.qpos0,
+                         "smplx": {"handle": smpl.smplx_batch_handle(bms[idxs[0]], g), "clips": [packed[i] for i in idxs]}})
+            continue
         shape = (len(idxs), T, len(g.human_body_names), 7)
         human = dp[1].pinned(f"human_{n}", shape, np.float64) if device else np.empty(shape)
         human[..., :3] = 0.0
@@ -1007,19 +1087,24 @@ def retarget_smplx_loaded(raws: Sequence[Dict], smplx_body_model_path: str, tgt_
         for k, i in enumerate(idxs):
             human[k, : lens[k]] = packed[i]
         jobs.append({"solver": g.hip_solver, "human": human, "lens": lens, "q0": g.model.qpos0})
-        members.append((idxs, lens))
+    if timing is not None:
+        timing["prepare"] = timing.get("prepare", 0.0) + t1 - t0
+        timing["pack"] = timing.get("pack", 0.0) + time.perf_counter() - t1
     if not raws:
         return []
     fps = [fps_of[i] for i in range(len(raws))]
     if device:
         km, post = dp
-        rp, rr, dof, lbp, spans, status = post.run(jobs, km, 0, height_adjust, root_origin_offset)
+        rp, rr, dof, lbp, spans, status = post.run(jobs, km, 0, height_adjust, root_origin_offset, timing=timing)
+        t2 = time.perf_counter()
         out: List[Optional[Dict]] = [None] * len(raws)
         for (idxs, _), sp, stt in zip(members, spans, status):
             if (stt != 0).any():
                 raise RuntimeError(f"IK failed for clips {[idxs[k] for k in np.nonzero(stt)[0]]}")
             for i, (a, b) in zip(idxs, sp):
                 out[i] = motion_dict(fps[i], rp[a:b], rr[a:b], dof[a:b], lbp[a:b], km.body_names)
+        if timing is not None:
+            timing["dicts"] = timing.get("dicts", 0.0) + time.perf_counter() - t2
         return out
     results = _lib.retarget_group([{k: v for k, v in j.items() if k != "q0"} for j in jobs])
     qpos: List[Optional[np.ndarray]] = [None] * len(raws)
@@ -1028,7 +1113,7 @@ def retarget_smplx_loaded(raws: Sequence[Dict], smplx_body_model_path: str, tgt_
             raise RuntimeError(f"IK failed for clips {[idxs[k] for k in np.nonzero(status)[0]]}")
         for k, i in enumerate(idxs):
             qpos[i] = q[k, : lens[k]]
-    km = KinematicsModel(next(iter(gmr_of.values())).xml_file)
+    km = KinematicsModel(any_g.xml_file)
     return postprocess_clips(qpos, km, fps, height_adjust, root_origin_offset)
 
 
@@ -1061,9 +1146,10 @@ def run_smplx_dataset(src_folder: str, tgt_folder: str, robot: str, smplx_folder
         jobs = _skip_existing(shard_jobs(list_smplx_jobs(src_folder, tgt_folder, True, hard)[1], rank, world), override, False)
     else:
         jobs = shard_jobs(jobs, rank, world)
+    timing: Dict[str, float] = {}
     if retarget is None:
         def retarget(raws, files):
-            return retarget_smplx_loaded(raws, smplx_folder, robot)
+            return retarget_smplx_loaded(raws, smplx_folder, robot, timing=timing)
     workers = default_workers(world) if loader_workers < 0 else loader_workers
     pool = _loader_pool("thread", workers if len(jobs) > 1 else 0)
     try:
@@ -1076,6 +1162,8 @@ def run_smplx_dataset(src_folder: str, tgt_folder: str, robot: str, smplx_folder
             pool.shutdown(wait=True, cancel_futures=True)
     if stats is not None:
         stats.update(pipe.stats)
+        if timing:
+            stats["seconds_gpu_parts"] = dict(timing)
     if verbose:
         print("Done. Saved to ", tgt_folder)
     return done
@@ -1151,7 +1239,9 @@ def main(argv=None) -> int:
                             frames_budget=a.frames_budget, loader_workers=a.num_cpus, rank=rank, world=world, stats=stats)
     else:
         from .params import ASSET_ROOT
-        assets = pathlib.Path(ASSET_ROOT)
+        if ASSET_ROOT is None and (a.smplx_folder is None or a.hard_motions is None):
+            raise SystemExit("no assets directory: give --smplx_folder and --hard_motions (or set GMR_ASSET_ROOT)")
+        assets = pathlib.Path(ASSET_ROOT) if ASSET_ROOT is not None else None      # (only the defaults need it)
         smplx_folder = a.smplx_folder or str(assets / "body_models")
         hard = a.hard_motions if a.hard_motions is not None else [str(assets / "hard_motions" / "0.txt"),
                                                                     str(assets / "hard_motions" / "1.txt")]

@@ -180,6 +180,16 @@ def _frame_counts(smplx_data, num_frames: int, tgt_fps) -> Tuple[Optional[np.nda
     return None, tgt_fps
 
 
+def _frame_plan(smplx_data, num_frames: int, tgt_fps) -> Tuple[bool, int, float]:
+    """``(align, nout, aligned_fps)`` of :func:`_frame_counts` without the target times themselves (the batch kernels compute
+    them): ``align`` is whether the reference interpolates at all (``tgt_fps < src_fps``), also when ``nout == num_frames``."""
+    src_fps = np.asarray(smplx_data["mocap_frame_rate"]).item()
+    if tgt_fps < src_fps:
+        new_num_frames = num_frames // int(src_fps / tgt_fps)
+        return True, new_num_frames, new_num_frames / num_frames * src_fps
+    return False, num_frames, tgt_fps
+
+
 def _poses(body_model, smplx_output):
     J = len(body_model.parents)
     full = _np(smplx_output.full_pose, np.float32)
@@ -249,3 +259,57 @@ def smplx_frames_packed_fused(retargeter, smplx_data, body_model, tgt_fps=30):
     frames = _handle(body_model.parents, sel).frames(body_model.rest_joints(_np(smplx_data["betas"])), full,
                                                      _np(smplx_data["trans"], np.float32).reshape(full.shape[0], 3), tt)
     return frames, aligned_fps
+
+
+# ---- ragged batches on the device (gmr_smplx_batch_frames_dev) ------------------------------------------------------------
+BODY_JOINTS = 22        # root_orient + pose_body: the joints an AMASS file poses (load_smplx_file passes nothing else)
+
+
+def _selection(body_model, retargeter) -> List[int]:
+    idx = {n: i for i, n in enumerate(_names(body_model))}
+    return [idx[n] for n in retargeter.human_body_names]
+
+
+def smplx_device_takes(body_model, retargeter) -> bool:
+    """Whether the batch entry point computes this (body model, retargeter) pair's frames: every body the retargeter reads and
+    every ancestor of it is one of the joints 0..21, and the body model adds no mean pose there (``pose_mean`` is the hands'),
+    so ``root_orient`` and ``pose_body`` are all the poses the frames depend on.  Host logic only."""
+    pm = getattr(body_model, "pose_mean", None)
+    parents = np.asarray(getattr(body_model, "parents", ()), dtype=np.int64)
+    if pm is None or len(parents) == 0 or len(parents) > 64:
+        return False
+    try:
+        sel = _selection(body_model, retargeter)
+    except KeyError:
+        return False
+    closure = set()
+    for j in sel:
+        while j >= 0 and j not in closure:
+            closure.add(j)
+            j = int(parents[j]) if j > 0 else -1
+    return bool(closure) and max(closure) < BODY_JOINTS and len(set(sel)) == len(sel) and not np.any(np.asarray(pm)[sorted(closure)])
+
+
+def smplx_batch_handle(body_model, retargeter) -> "_lib.SmplxHandle":
+    return _handle(body_model.parents, _selection(body_model, retargeter))
+
+
+def smplx_raw_clip(smplx_data, body_model, tgt_fps=30) -> Dict:
+    """One loaded AMASS file as an entry of a raw SMPL-X job (``DevicePost.run``, ``SmplxHandle.batch_frames``): the
+    ``float32`` arrays the reference hands to the body model (utils/smpl.py:27-31), C-contiguous, with ``N``, ``nout``,
+    ``align`` and ``aligned_fps`` as :func:`_frame_counts` gives them, the subject's rest joints and height.  Nothing is
+    computed per frame.  Raises what the per-clip path raises for a clip it rejects (no frame at all; fps alignment of a
+    one-frame clip), before anything is uploaded."""
+    ro = np.ascontiguousarray(_np(smplx_data["root_orient"], np.float32).reshape(-1, 3))
+    N = ro.shape[0]
+    pb = np.ascontiguousarray(_np(smplx_data["pose_body"], np.float32).reshape(N, 3 * (BODY_JOINTS - 1)))
+    tr = np.ascontiguousarray(_np(smplx_data["trans"], np.float32).reshape(N, 3))
+    if N < 1:
+        raise _lib.GmrHipError("libgmrhip error -1: smplx_raw_clip: a clip needs at least one frame")
+    align, nout, aligned_fps = _frame_plan(smplx_data, N, tgt_fps)
+    if align and N < 2:
+        raise _lib.GmrHipError("libgmrhip error -1: smplx_raw_clip: fps alignment needs at least two source frames")
+    betas = _np(smplx_data["betas"])
+    height = float(1.66 + 0.1 * (betas[0] if betas.ndim == 1 else betas[0, 0]))
+    return {"root_orient": ro, "pose_body": pb, "trans": tr, "N": N, "nout": int(nout), "align": bool(align),
+            "aligned_fps": aligned_fps, "j_rest": body_model.rest_joints(betas), "height": height}

@@ -262,6 +262,38 @@ int gmr_smplx_compact_layout(const gmr_smplx_t* h, int32_t* pose_joints, int* np
 int gmr_smplx_align_compact_dev(gmr_smplx_t* h, int N, const float* d_pose_c, const float* d_joints_c, int Nout,
                                 const double* d_target_time, double* d_out, void* stream);
 
+/* A ragged batch of clips straight from the arrays an AMASS file holds, written where the IK kernels read them: replaces, for
+ * nclip clips in one call, load_smplx_file's forward pass + get_smplx_data_offline_fast (utils/smpl.py:12-41, :109-197), i.e.
+ * one gmr_smplx_frames call per clip, with the SAME BITS on every frame.  B source frames in total, concatenated, float32 as the
+ * reference casts them (:27-31):
+ *   root_orient f32 [B][3]      pose_body f32 [B][63]      trans f32 [B][3]
+ *   src_start   i32 [nclip + 1]     source frames of clip c = [src_start[c], src_start[c + 1]); ascending from 0 to B
+ *   nout        i32 [nclip]         output frames of clip c: N // int(src_fps / tgt_fps) with alignment, else N (<= N always)
+ *   align       u8  [nclip]         1: fps alignment (tgt_fps < src_fps; also when nout == N, e.g. 50 -> 30 fps), 0: frame by frame
+ *   j_rest      f64 [nclip][J][3]   rest joints of the clip's subject (J_regressor on the shaped template)
+ *   clip_out    f64* [nclip]        where frame 0 of clip c goes (room for nout[c] frames of nsel x 7 doubles): a row of some
+ *                                   job's human f64[S][T][nsel][7]; the clips of one call may belong to different jobs
+ * Only joints 0 .. 21 have poses here (the hands, jaw and eyes are zero in load_smplx_file), so the handle's selection and its
+ * ancestors must lie inside them (gmr_smplx_batch_takes; every shipped smplx ik_config does) -- otherwise GMR_ERR_ARG before
+ * any launch.  The target times np.linspace(0, N - 1, nout) are computed on the device (gmr_smplx_target_times is the same
+ * inline on the host).  Frames t >= nout[c] are not written by the device entry point (the IK kernels never read them); a clip
+ * with nout == 0, or with alignment and fewer than two source frames, writes nothing.  The two tables are not trusted: whatever
+ * they hold, no load leaves the inputs and a store goes to frame o < min(nout[c], N_c) of clip_out[c].
+ * The scratch of a call (12 (npose + nsel) B per source frame: the poses of the closure and the joints of the rows as
+ * frame-minor planes) belongs to the handle, one block per HIP stream that has called, grown on demand (the only time the call
+ * waits: for its own stream) and freed by gmr_smplx_destroy: calls on different streams may be in flight together. */
+int gmr_smplx_batch_takes(const gmr_smplx_t* h);          /* 1: the batch entry points take this handle's selection */
+int gmr_smplx_target_times(int N, int Nout, double* out); /* out f64[Nout] = np.linspace(0, N - 1, Nout), bit for bit; host only */
+int gmr_smplx_batch_frames_dev(gmr_smplx_t* h, int nclip, int B, const float* d_root_orient, const float* d_pose_body,
+                               const float* d_trans, const int32_t* d_src_start, const int32_t* d_nout, const uint8_t* d_align,
+                               const double* d_j_rest, double* const* d_clip_out, void* stream);   /* asynchronous */
+/* host buffers; checks the tables (src_start ascending from 0 to B, 0 <= nout <= min(N, T), nout == N without alignment,
+ * alignment needs two source frames) before anything is launched; human f64[nclip][T][nsel][7], frames t >= nout[c] come back
+ * as zeros.  One call per handle at a time. */
+int gmr_smplx_batch_frames(gmr_smplx_t* h, int nclip, int B, const float* root_orient, const float* pose_body,
+                           const float* trans, const int32_t* src_start, const int32_t* nout, const uint8_t* align,
+                           const double* j_rest, int T, double* human);
+
 /* ---- N2: BVH frame extraction (LAFAN1; the step in front of the loop of the BVH dataset driver) -------------------- */
 /* The topology of a BVH skeleton and the rows wanted per frame.  J <= 256 joints in file order (parents[0] = -1,
  * 0 <= parents[j] < j: a BVH hierarchy is written depth first, so every parent precedes its children); `channels` is the
