@@ -69,6 +69,24 @@ def build(force: bool = False, verbose: bool = False) -> str:
     return _link([_object(s, [], force, verbose) for s in SOURCES], LIB)
 
 
+# The test-only probe of gmr_device_math.h (tests/hip/math_probe.hip): one shared object per flag set the shipped library
+# compiles that header under.  Libraries of their own -- nothing of the probe is linked into libgmrhip.so.
+PROBE_SRC = os.path.join(os.path.dirname(HERE), "tests", "hip", "math_probe.hip")
+PROBE_LIBS = {"flags": os.path.join(os.path.dirname(PROBE_SRC), "libgmr_math_probe.so"),
+              "wide": os.path.join(os.path.dirname(PROBE_SRC), "libgmr_math_probe_wide.so")}
+
+
+def build_probe(force: bool = False) -> dict:
+    """Both probe libraries, rebuilt when the probe source or the header is newer (the libraries are cached on those mtimes)."""
+    deps = [PROBE_SRC, os.path.join(CSRC, "gmr_device_math.h"), os.path.abspath(__file__)]
+    extra = {"flags": [], "wide": PER_SOURCE_FLAGS["gmr_ik_wide.hip"]}
+    for name, out in PROBE_LIBS.items():
+        if force or not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
+            subprocess.check_call([_hipcc()] + FLAGS + extra[name] + ["-shared", "-o", out + ".tmp", PROBE_SRC])
+            os.replace(out + ".tmp", out)
+    return dict(PROBE_LIBS)
+
+
 def build_variant(name: str, defines=(), verbose: bool = False) -> str:
     """libgmrhip_<name>.so with extra -D flags on every source (objects cached per flag set)."""
     out = os.path.join(HERE, f"libgmrhip_{name}.so")
