@@ -97,6 +97,10 @@ _SIGS = {
     "gmr_bvh_columns": (C.c_int, [C.c_void_p]),
     "gmr_bvh_frames_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "gmr_bvh_frames": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "gmr_chunk_plan": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gmr_chunk_gather_dev": (C.c_int, [C.c_int] * 6 + [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 8),
+    "gmr_chunk_stitch_dev": (C.c_int, [C.c_int] * 5 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 10),
+    "gmr_chunk_seams_dev": (C.c_int, [C.c_int] * 5 + [C.c_void_p] * 5 + [C.c_double] + [C.c_void_p] * 5),
     "gmr_comm_create": (C.c_int, [C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),
     "gmr_comm_destroy": (C.c_int, [C.c_void_p]),
     "gmr_comm_rank": (C.c_int, [C.c_void_p]),

@@ -164,6 +164,8 @@ class DevicePost:
         self._dev: Dict[str, object] = {}
         self._pin: Dict[str, np.ndarray] = {}
         self._events = None
+        self._chunker = None
+        self.chunk_reports: List = []             # per job of the last run: per-clip chunk reports (chunking.clip_report), or None
 
     def _d(self, name: str, nbytes: int):
         from . import _lib
@@ -226,8 +228,11 @@ class DevicePost:
         return calls, d_human
 
     def run(self, jobs: Sequence[Dict], km: KinematicsModel, ik_flags: int = 0, height_adjust: bool = True,
-            root_origin_offset: bool = True, ground_offset: float = 0.0, timing: Optional[Dict[str, float]] = None):
-        """``jobs`` = ``[{"solver", "human": f64[S,T,nhuman,7] (page-locked for an asynchronous copy), "lens": i32[S],
+            root_origin_offset: bool = True, ground_offset: float = 0.0, timing: Optional[Dict[str, float]] = None, chunk=None):
+        """``chunk`` (``None`` | ``chunking.ChunkSpec`` | ``"auto"``): jobs with a clip longer than the spec's ``frames`` run chunked
+        (:class:`chunking.ChunkRunner` in place of the one IK launch: NOT parity, ``chunk_reports`` says how far off); the
+        post-processing reads the stitched clip-major output unchanged.
+        ``jobs`` = ``[{"solver", "human": f64[S,T,nhuman,7] (page-locked for an asynchronous copy), "lens": i32[S],
         "q0": f64[nq]}]``, all for the robot of ``km``.  A job of raw BVH clips carries, instead of ``"human"``, ``"T"`` and
         ``"bvh"`` = ``[{"handle": _lib.BvhHandle, "rows": f64[B,ncol] (page-locked), "offsets": f64[n,J,3], "clips": [index in
         lens, ...], "lens": [...]}]`` (one entry per topology) and optionally ``"packed"`` = ``[(index, f64[n,nhuman,7])]``: the
@@ -343,7 +348,18 @@ class DevicePost:
             at = lambda k: C.c_void_p(d_in.ptr.value + offs[k])          # noqa: E731
             h.batch_frames_dev(n, B, at("ro"), at("pb"), at("tr"), at("seg"), at("nout"), at("align"), at("jrest"), at("tab"), st)
         ev[5].record(st)
-        _lib.retarget_group_dev(launch, ik_flags, st)
+        from . import chunking
+        total_frames = int(sum(int(l.sum()) for l in dlens))
+        specs = [chunking.resolve_any(chunk, l, total_frames) for l in dlens]
+        self.chunk_reports = [None] * len(jobs)
+        if any(sp is not None for sp in specs):
+            if self._chunker is None:
+                self._chunker = chunking.ChunkRunner()
+            reports = self._chunker.run(launch, dlens, specs, ik_flags, st)
+            for i, r in enumerate(reports):        # back to the job's own clip order
+                self.chunk_reports[i] = r if (r is None or perms[i] is None) else [r[k] for k in np.argsort(perms[i]).tolist()]
+        else:
+            _lib.retarget_group_dev(launch, ik_flags, st)
         ev[2].record(st)
         for n, (c0, r0, seg) in enumerate(chunks):
             hseg = self.pinned(f"seg_{n}", seg.shape, np.int32)
@@ -387,11 +403,20 @@ class ClipRetargeter:
 
     _seen_raw = False            # this object has staged raw BVH clips: its batches are raw batches from then on
     _raw_index: Optional[Dict[tuple, int]] = None        # topology key -> number of its page-locked rows block
+    chunk = None                 # chunked retargeting of long clips: off
+    chunk_report: Optional[List[Dict]] = None
 
     def __init__(self, src_human: str, tgt_robot: str, actual_human_height: Optional[float] = None, height_adjust: bool = True,
-                 root_origin_offset: bool = True, offset_to_ground: bool = False):
+                 root_origin_offset: bool = True, offset_to_ground: bool = False, chunk=None):
+        """``chunk``: ``None`` (default: one stream per clip, as ever), a ``chunking.ChunkSpec`` or ``"auto"``: clips longer than the
+        spec's ``frames`` are cut into chunks that run as independent streams (NOT parity with the sequential run; DESIGN.md
+        section 6g).  ``chunk_report`` then holds, per clip of the last batch, K, ``seam_max``, seams repaired / left bad, passes
+        and ``warm_solves``; ``chunk_summary`` the totals over all batches."""
         self.gmr = GeneralMotionRetargeting(src_human, tgt_robot, actual_human_height=actual_human_height)
         self.height_adjust, self.root_origin_offset, self.offset_to_ground = height_adjust, root_origin_offset, offset_to_ground
+        self.chunk = chunk
+        self.chunk_report: Optional[List[Dict]] = None
+        self.chunk_summary: Dict = {}
         self._km: Optional[KinematicsModel] = None
         self._pin: Dict[str, np.ndarray] = {}
         self._dev_post: Optional[DevicePost] = None
@@ -510,9 +535,16 @@ class ClipRetargeter:
             return self._finish_device(fps, lens)
         q0 = self._buf("q0", (S, sol.nq), np.float64)
         q0[:] = gmr.model.qpos0
-        outs = [(self._buf("q_out", (S, T, sol.nq), np.float64), self._buf("nsolve", (S, T, 2), np.int32), np.zeros(S, np.int32))]
-        (qpos, _, status), = _lib.retarget_group([{"solver": sol, "human": self._human[:S], "q0": q0, "lens": lens}],
-                                                 gmr._flags(self.offset_to_ground), 0, outs=outs)
+        from . import chunking
+        spec = chunking.resolve_any(self.chunk, lens)
+        self.chunk_report = None
+        if spec is not None:
+            qpos, _, status, self.chunk_report = chunking.retarget_chunked_host(sol, self._human[:S], q0, lens, gmr._flags(self.offset_to_ground), spec)
+            chunking.summarize(self.chunk_report, self.chunk_summary)
+        else:
+            outs = [(self._buf("q_out", (S, T, sol.nq), np.float64), self._buf("nsolve", (S, T, 2), np.int32), np.zeros(S, np.int32))]
+            (qpos, _, status), = _lib.retarget_group([{"solver": sol, "human": self._human[:S], "q0": q0, "lens": lens}],
+                                                     gmr._flags(self.offset_to_ground), 0, outs=outs)
         t2 = time.perf_counter()
         self._n = 0
         if (status != 0).any():
@@ -543,7 +575,11 @@ class ClipRetargeter:
             job = {"solver": gmr.hip_solver, "human": self._human[:S], "lens": lens, "q0": gmr.model.qpos0}
         self._n = 0
         rp, rr, dp, lbp, spans, (status,) = self._dev_post.run([job], self._km, gmr._flags(self.offset_to_ground), self.height_adjust,
-                                                               self.root_origin_offset, 0.0, self.timing)
+                                                               self.root_origin_offset, 0.0, self.timing, chunk=self.chunk)
+        self.chunk_report = self._dev_post.chunk_reports[0]
+        if self.chunk_report is not None:
+            from . import chunking
+            chunking.summarize(self.chunk_report, self.chunk_summary)
         if (status != 0).any():
             raise RuntimeError(f"IK failed for clips {np.nonzero(status)[0].tolist()}")
         t0 = time.perf_counter()
@@ -565,14 +601,19 @@ class ClipRetargeter:
 
 def retarget_clips(src_human: str, tgt_robot: str, clips: Sequence, fps: Sequence[float],
                    actual_human_height: Optional[float] = None, height_adjust: bool = True,
-                   root_origin_offset: bool = True, offset_to_ground: bool = False) -> List[Dict]:
-    """Retarget many clips of one (source, robot, height) in ONE IK launch.
+                   root_origin_offset: bool = True, offset_to_ground: bool = False, chunk=None, report: Optional[List] = None) -> List[Dict]:
+    """Retarget many clips of one (source, robot, height) in ONE IK launch.  ``chunk`` (``chunking.ChunkSpec`` or ``"auto"``; default
+    off) cuts long clips into independently running chunks -- NOT parity; the per-clip chunk reports are appended to ``report``.
 
     ``clips[i]`` is a list of ``human_data`` dicts or an array ``[T_i, nhuman, 7]`` (ragged lengths
     are fine: streams are padded and the kernel stops each stream at its own length).
     Returns one motion dict per clip, identical to processing the clips one by one.
     """
-    return ClipRetargeter(src_human, tgt_robot, actual_human_height, height_adjust, root_origin_offset, offset_to_ground)(clips, fps)
+    rt = ClipRetargeter(src_human, tgt_robot, actual_human_height, height_adjust, root_origin_offset, offset_to_ground, chunk=chunk)
+    out = rt(clips, fps)
+    if report is not None and rt.chunk_report is not None:
+        report.extend(rt.chunk_report)
+    return out
 
 
 def retarget_mixed(groups: Sequence[Dict], offset_to_ground: bool = False, slices: int = 0, pinned_outputs: bool = False):
@@ -597,7 +638,7 @@ def retarget_mixed(groups: Sequence[Dict], offset_to_ground: bool = False, slice
 
 
 def retarget_bvh_files(bvh_files: Sequence[str], tgt_robot: str, fps: float = 30.0, height_adjust: bool = False,
-                       root_origin_offset: bool = False) -> List[Dict]:
+                       root_origin_offset: bool = False, chunk=None, report: Optional[List] = None) -> List[Dict]:
     """``scripts/bvh_to_robot_dataset.py:60-152`` for a list of files: every BVH clip becomes one
     stream of ONE launch (LAFAN1: 77 ragged clips).  Both adjustments default to off like that script
     (``HEIGHT_ADJUST = False``, :128); the loader's hard-coded height 1.75 is used (lafan1.py:39).
@@ -610,12 +651,12 @@ def retarget_bvh_files(bvh_files: Sequence[str], tgt_robot: str, fps: float = 30
     else:
         clips = [load_lafan1_packed(f, gmr.human_body_names)[0] for f in bvh_files]
     return retarget_clips("bvh", tgt_robot, clips, [fps] * len(clips), actual_human_height=1.75,
-                          height_adjust=height_adjust, root_origin_offset=root_origin_offset)
+                          height_adjust=height_adjust, root_origin_offset=root_origin_offset, chunk=chunk, report=report)
 
 
 def retarget_smplx_files(smplx_files: Sequence[str], smplx_body_model_path: str, tgt_robot: str, tgt_fps: int = 30,
                          height_adjust: bool = True, root_origin_offset: bool = True,
-                         skip_errors: bool = True) -> List[Optional[Dict]]:
+                         skip_errors: bool = True, chunk=None, report: Optional[List] = None) -> List[Optional[Dict]]:
     """``scripts/smplx_to_robot_dataset.py:39-146`` (``process_file``) for a list of AMASS-style SMPL-X
     files, everything after the file read on the device: joints-only body model + fps alignment
     (utils/smpl.py) -> packed frames -> IK (one group launch for all heights) -> FK post-processing.
@@ -631,7 +672,8 @@ def retarget_smplx_files(smplx_files: Sequence[str], smplx_body_model_path: str,
                 raise
             print(f"Error loading {f}: {e}")
     out: List[Optional[Dict]] = [None] * len(smplx_files)
-    for i, md in zip(ok, retarget_smplx_loaded(raws, smplx_body_model_path, tgt_robot, tgt_fps, height_adjust, root_origin_offset)):
+    for i, md in zip(ok, retarget_smplx_loaded(raws, smplx_body_model_path, tgt_robot, tgt_fps, height_adjust, root_origin_offset,
+                                               chunk=chunk, report=report)):
         out[i] = md
     return out
 
@@ -970,8 +1012,8 @@ def _load_bvh_clip(args):
 
 def run_bvh_dataset(src_folder: str, tgt_folder: str, robot: str, override: bool = False, batch_files: int = 0,
                     retarget=None, verbose: bool = True, frames_budget: int = 1 << 19, loader_workers: int = -1,
-                    rank: int = 0, world: int = 1, load=None, stats: Optional[Dict] = None) -> int:
-    """``bvh_to_robot_dataset.py`` (:60-157) on the pipeline above.  ``batch_files`` > 0 additionally caps the clips of a
+                    rank: int = 0, world: int = 1, load=None, stats: Optional[Dict] = None, chunk=None) -> int:
+    """``bvh_to_robot_dataset.py`` (:60-157) on the pipeline above.  ``chunk``: see :class:`ClipRetargeter` (``stats["chunk"]`` gets the totals).  ``batch_files`` > 0 additionally caps the clips of a
     launch (0: only the frames budget does).  ``retarget(clips, files)`` and ``load(file)`` are injectable (tests)."""
     # the partition is computed on ALL source files (a rank that starts later must not see another partition because
     # some targets exist by then); skip-if-exists is applied to the rank's own shard
@@ -984,7 +1026,7 @@ def run_bvh_dataset(src_folder: str, tgt_folder: str, robot: str, override: bool
     names = gmr.human_body_names if gmr is not None else None
     rt = None
     if retarget is None:
-        rt = ClipRetargeter("bvh", robot, 1.75, height_adjust=False, root_origin_offset=False)    # HEIGHT_ADJUST = False, :128
+        rt = ClipRetargeter("bvh", robot, 1.75, height_adjust=False, root_origin_offset=False, chunk=chunk)    # HEIGHT_ADJUST = False, :128
         retarget = _Staged(rt, 30)
     raw = rt is not None and bvh_path() == "device"        # the loaders only parse; gmr_bvh_frames_dev computes the frames
     try:
@@ -1014,6 +1056,8 @@ def run_bvh_dataset(src_folder: str, tgt_folder: str, robot: str, override: bool
         stats.update(pipe.stats)
         if rt is not None:
             stats["seconds_gpu_parts"] = dict(rt.timing)
+            if rt.chunk_summary:
+                stats["chunk"] = dict(rt.chunk_summary)
     if verbose:
         print("Done. saved to ", tgt_folder)
     return done
@@ -1039,7 +1083,7 @@ def _load_smplx_raw(f):
 
 def retarget_smplx_loaded(raws: Sequence[Dict], smplx_body_model_path: str, tgt_robot: str, tgt_fps: int = 30,
                           height_adjust: bool = True, root_origin_offset: bool = True,
-                          timing: Optional[Dict[str, float]] = None) -> List[Optional[Dict]]:
+                          timing: Optional[Dict[str, float]] = None, chunk=None, report: Optional[List] = None) -> List[Optional[Dict]]:
     """``process_file`` (smplx_to_robot_dataset.py:39-146) for many already-read files: joints-only body model and fps
     alignment on the device, the clips grouped by human height (a file's height comes from its betas, :36-39) into ONE group
     launch, two FK launches for the post-processing of all clips together.  On the device path (:func:`smplx_path`, and every
@@ -1095,7 +1139,9 @@ def retarget_smplx_loaded(raws: Sequence[Dict], smplx_body_model_path: str, tgt_
     fps = [fps_of[i] for i in range(len(raws))]
     if device:
         km, post = dp
-        rp, rr, dof, lbp, spans, status = post.run(jobs, km, 0, height_adjust, root_origin_offset, timing=timing)
+        rp, rr, dof, lbp, spans, status = post.run(jobs, km, 0, height_adjust, root_origin_offset, timing=timing, chunk=chunk)
+        if report is not None:
+            report.extend(r for rs in post.chunk_reports if rs is not None for r in rs)
         t2 = time.perf_counter()
         out: List[Optional[Dict]] = [None] * len(raws)
         for (idxs, _), sp, stt in zip(members, spans, status):
@@ -1106,7 +1152,19 @@ def retarget_smplx_loaded(raws: Sequence[Dict], smplx_body_model_path: str, tgt_
         if timing is not None:
             timing["dicts"] = timing.get("dicts", 0.0) + time.perf_counter() - t2
         return out
-    results = _lib.retarget_group([{k: v for k, v in j.items() if k != "q0"} for j in jobs])
+    from . import chunking
+    total_frames = int(sum(int(l.sum()) for _, l in members))
+    specs = [chunking.resolve_any(chunk, l, total_frames) for _, l in members]
+    plain = [n for n, sp in enumerate(specs) if sp is None]
+    results: List = [None] * len(jobs)
+    for n, r in zip(plain, _lib.retarget_group([{k: v for k, v in jobs[n].items() if k != "q0"} for n in plain]) if plain else []):
+        results[n] = r
+    for n, sp in enumerate(specs):
+        if sp is not None:
+            q, ns, stt, rep = chunking.retarget_chunked_host(jobs[n]["solver"], jobs[n]["human"], jobs[n]["q0"], jobs[n]["lens"], 0, sp)
+            results[n] = (q, ns, stt)
+            if report is not None:
+                report.extend(rep)
     qpos: List[Optional[np.ndarray]] = [None] * len(raws)
     for (idxs, lens), (q, _, status) in zip(members, results):
         if (status != 0).any():
@@ -1132,7 +1190,7 @@ def _smplx_device_post(xml_file: str):
 def run_smplx_dataset(src_folder: str, tgt_folder: str, robot: str, smplx_folder: str, override: bool = False,
                       hard_motion_files: Sequence[str] = (), batch_files: int = 0, retarget=None, verbose: bool = True,
                       frames_budget: int = 1 << 19, loader_workers: int = -1, rank: int = 0, world: int = 1, load=None,
-                      stats: Optional[Dict] = None) -> int:
+                      stats: Optional[Dict] = None, chunk=None) -> int:
     """``smplx_to_robot_dataset.py:main`` (:171-242) on the pipeline above.  ``retarget(raws, files)`` defaults to
     :func:`retarget_smplx_loaded`, ``load(file)`` to the npz reader (tests inject stand-ins).  Returns the number of pkl
     files this rank wrote."""
@@ -1147,9 +1205,15 @@ def run_smplx_dataset(src_folder: str, tgt_folder: str, robot: str, smplx_folder
     else:
         jobs = shard_jobs(jobs, rank, world)
     timing: Dict[str, float] = {}
+    chunk_summary: Dict = {}
     if retarget is None:
         def retarget(raws, files):
-            return retarget_smplx_loaded(raws, smplx_folder, robot, timing=timing)
+            from . import chunking
+            rep: List = []
+            out = retarget_smplx_loaded(raws, smplx_folder, robot, timing=timing, chunk=chunk, report=rep)
+            if rep:
+                chunking.summarize(rep, chunk_summary)
+            return out
     workers = default_workers(world) if loader_workers < 0 else loader_workers
     pool = _loader_pool("thread", workers if len(jobs) > 1 else 0)
     try:
@@ -1164,6 +1228,8 @@ def run_smplx_dataset(src_folder: str, tgt_folder: str, robot: str, smplx_folder
         stats.update(pipe.stats)
         if timing:
             stats["seconds_gpu_parts"] = dict(timing)
+        if chunk_summary:
+            stats["chunk"] = dict(chunk_summary)
     if verbose:
         print("Done. Saved to ", tgt_folder)
     return done
@@ -1212,7 +1278,10 @@ def main(argv=None) -> int:
     ap.add_argument("--frames_budget", type=int, default=1 << 19, help="padded frames (clips x longest clip) of one IK launch")
     ap.add_argument("--gpus", type=int, default=1, help="ranks = GPUs of this node; the files are LPT-sharded over them")
     ap.add_argument("--quiet", action="store_true")
+    from . import chunking
+    chunking.add_cli_arguments(ap)
     a = ap.parse_args(argv)
+    chunk = chunking.spec_from_args(a)
     from . import launcher
     if a.gpus > 1 and not launcher.is_rank_process():
         # become the launcher: one rank process per GPU, nothing of the GPU is touched here
@@ -1236,7 +1305,7 @@ def main(argv=None) -> int:
     stats: Dict = {}
     if a.source == "bvh":
         n = run_bvh_dataset(a.src_folder, a.tgt_folder, a.robot, a.override, a.batch_files, verbose=not a.quiet,
-                            frames_budget=a.frames_budget, loader_workers=a.num_cpus, rank=rank, world=world, stats=stats)
+                            frames_budget=a.frames_budget, loader_workers=a.num_cpus, rank=rank, world=world, stats=stats, chunk=chunk)
     else:
         from .params import ASSET_ROOT
         if ASSET_ROOT is None and (a.smplx_folder is None or a.hard_motions is None):
@@ -1247,8 +1316,10 @@ def main(argv=None) -> int:
                                                                     str(assets / "hard_motions" / "1.txt")]
         n = run_smplx_dataset(a.src_folder, a.tgt_folder, a.robot, smplx_folder, a.override, hard, a.batch_files,
                               verbose=not a.quiet, frames_budget=a.frames_budget, loader_workers=a.num_cpus, rank=rank,
-                              world=world, stats=stats)
+                              world=world, stats=stats, chunk=chunk)
     dt = time.perf_counter() - t0
+    if chunk is not None:        # one line per rank: the mode is not parity, so what it did to the seams is always said
+        print(json.dumps({"chunk_summary": {"rank": rank, **stats.get("chunk", {"clips_split": 0})}}))
     frames = float(stats.get("frames", 0))
     if cm is not None:
         tot = cm.allgather(frames)

@@ -247,10 +247,12 @@ class GeneralMotionRetargeting:
         self.last_num_solves = ns[0].copy()
         return q[0].copy()
 
-    def retarget_clip(self, frames, offset_to_ground=False) -> np.ndarray:
+    def retarget_clip(self, frames, offset_to_ground=False, chunk=None) -> np.ndarray:
         """All frames of one clip in ONE launch (time loop on device); continues from the current
         configuration exactly like calling :meth:`retarget` per frame.  ``frames`` is a sequence of
-        ``human_data`` dicts or an array ``[T, nhuman, 7]``.  Returns ``qpos f64[T, nq]``."""
+        ``human_data`` dicts or an array ``[T, nhuman, 7]``.  Returns ``qpos f64[T, nq]``.
+        ``chunk`` (a ``chunking.ChunkSpec`` or ``"auto"``; default off): a clip longer than the spec's ``frames`` runs as
+        independent chunks with warm-up -- NOT parity with the per-frame loop; ``self.chunk_report`` says how far off."""
         key_order = None
         if isinstance(frames, np.ndarray):
             human = np.ascontiguousarray(frames, dtype=np.float64)
@@ -259,6 +261,19 @@ class GeneralMotionRetargeting:
             key_order = list(frames[-1].keys()) if len(frames) else None
         if human.shape[0] == 0:
             return np.zeros((0, self.model.nq))
+        from . import chunking
+        spec = chunking.resolve_any(chunk, [human.shape[0]])
+        self.chunk_report = None
+        if spec is not None:
+            q, ns, status, self.chunk_report = chunking.retarget_chunked_host(
+                self.hip_solver, human[None], self.configuration.data.qpos[None], None, self._flags(offset_to_ground), spec)
+            if status[0] != 0:
+                raise RuntimeError(f"IK failed (status {int(status[0])}): QP not solvable / non-finite input")
+            self._set_frame(human[-1], offset_to_ground, key_order)
+            self.configuration.data.qpos = q[0, -1].copy()
+            self._targets, self._errors, self._errors_q = None, None, None      # (evaluated on demand: tgt_out / err_out are not chunked)
+            self.last_num_solves = ns[0].copy()
+            return q[0]
         q, ns = self._run(human, offset_to_ground, key_order)
         self.last_num_solves = ns.copy()
         return q

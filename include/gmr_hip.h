@@ -221,6 +221,61 @@ int gmr_postprocess_clips_dev(gmr_fk_t* fk, const gmr_post_src_t* src, int nsrc,
                               double* d_root_pos, double* d_root_rot, double* d_dof_pos,
                               float* d_local_body_pos, float* d_lowest, void* stream);
 
+/* ---- chunked retargeting of long clips (opt-in, NOT parity) ---------------------------------
+ * Frames of a clip depend on each other (warm start), so a batch of few, long clips (LAFAN1: 77 clips of up to 9 855
+ * frames) leaves most of the device idle.  Here clip c of n frames is cut into K = max(1, ceil(n / L)) chunks that
+ * partition [0, n) in order and evenly -- chunk i owns [floor(i n / K), floor((i + 1) n / K)) -- and run as ordinary,
+ * independent streams of gmr_retarget_group_dev: chunk i >= 1 starts from the clip's q0 and first runs
+ * warm = min(W, first owned frame) warm-up frames whose results are dropped.  The frame in front of a chunk is thus
+ * computed twice; the difference (the seam residual) measures how far the chunk started from where the sequential run
+ * would have been, and a chunk whose seam is off can be run again from its predecessor's final state (repair), which
+ * makes its residual 0 until the predecessor itself changes.  Clips with n <= L are one chunk without warm-up: their
+ * results are the bits of the unchunked launch.
+ *
+ * Tables (host: from the plan; device: copies of them, NOT trusted -- every record is clamped into its clip's rows and a
+ * chunk's rows, a list entry outside [0, nchunk) names no chunk, so no access leaves the buffers whatever they hold):
+ *   chunk      i32 [nchunk][4]   clip, first source frame (warm-up included), warm, owned; chunks of a clip consecutive
+ *   clip_first i32 [nclip + 1]   first chunk of every clip; clip_first[nclip] = nchunk
+ *   Tc                           the longest chunk, warm + owned (>= 1)
+ * Plan: `chunk` == NULL sizes only (nchunk, Tc; clip_first is filled when given); otherwise `capacity` is the room in `chunk`.
+ * L >= 1; W >= 1 when any clip is split (GMR_ERR_ARG otherwise).  Host code, no GPU needed. */
+int gmr_chunk_plan(int nclip, const int32_t* len, int L, int W, int capacity, int32_t* chunk, int32_t* clip_first,
+                   int* nchunk, int* Tc);
+/* The three steps around the IK launch of a pass: device pointers, asynchronous on `stream`, no scratch memory, no
+ * synchronisation.  A pass works on SLOTS: slot i is chunk i (d_list == NULL: all nchunk chunks) or chunk d_list[i]
+ * (i < nlist), and is stream i of the pass's IK job  { S = slots, T = Tc, q0 = q0_c, human = human_c, len = len_c }.
+ *   GMR_CHUNK_PASS0   warm-up and owned frames, q0_c[i] = the clip's q0 row
+ *   GMR_CHUNK_REPAIR  owned frames only, q0_c[i] = q_seam[k] = clip-major q_out at the frame before the chunk
+ * gather:  human f64[S][T][nhuman][7] (clip-major, where the front ends and the host copies put it), q0 f64[S][nq],
+ *          q_out f64[S][T][nq] (repair only) -> human_c f64[slots][Tc][nhuman][7], len_c i32[slots], q0_c f64[slots][nq]
+ *          (a slot that names no chunk gets len 0).  A pure copy, 16 bytes per lane when a frame is a multiple of 16 bytes
+ *          and the buffers are 16-byte aligned (8 otherwise). */
+#define GMR_CHUNK_PASS0 0
+#define GMR_CHUNK_REPAIR 1
+int gmr_chunk_gather_dev(int S, int T, int nhuman, int nq, int nchunk, int Tc, const int32_t* d_chunk, const int32_t* d_list, int nlist,
+                         int mode, const double* d_human, const double* d_q0, const double* d_q_out, double* d_human_c,
+                         int32_t* d_len_c, double* d_q0_c, double* d_q_seam, void* stream);
+/* stitch:  the owned rows of q_out_c f64[slots][Tc][nq] / nsolve_c i32[slots][Tc][2] -> clip-major q_out f64[S][T][nq],
+ *          nsolve i32[S][T][2]: the layout gmr_post_src_t and every consumer of gmr_retarget_streams_dev read; rows of other
+ *          chunks are not touched.  chunk_status i32[nchunk] keeps every chunk's status word across passes, and
+ *          status i32[S] = the first non-OK status of the clip's chunks in order.  Pass 0 (no list) also writes
+ *          q_seam f64[nchunk][nq] = the chunk's last warm-up row (NaN without warm-up) and warm_solves i32[S] = the solves
+ *          of the clip's warm-up rows, which are the overhead of the mode and are NOT part of nsolve. */
+int gmr_chunk_stitch_dev(int S, int T, int nq, int nchunk, int Tc, const int32_t* d_chunk, const int32_t* d_clip_first,
+                         const int32_t* d_list, int nlist, int mode, const double* d_q_out_c, const int32_t* d_nsolve_c,
+                         const int32_t* d_status_c, double* d_q_out, int32_t* d_nsolve, int32_t* d_chunk_status, int32_t* d_status,
+                         double* d_q_seam, int32_t* d_warm_solves, void* stream);
+/* seams:   for every chunk that does not start its clip, q_seam[k] against q_out at the frame before the chunk:
+ *          resid f64[nchunk][3] = max |d joint angle| (rad), max |d root position| (m), angle between the root orientations
+ *          (rad; the same for q and -q, 2 atan2(|vector|, |scalar|) of the relative rotation); zeros for first chunks.
+ *          A seam is over the tolerance when a component is > tol or not finite.  bad_list i32[nchunk] receives those
+ *          chunks in ascending order (whatever the scheduling), nbad i32[1] their number -- the one word a pass loop reads
+ *          back; a seam behind a chunk that FAILED is not listed (a re-run cannot mend it; its clip fails through `status`).
+ *          seam_max f64[S][3] = the maxima of resid over the clip's chunks (NaN sticks). */
+int gmr_chunk_seams_dev(int S, int T, int nq, int nchunk, int Tc, const int32_t* d_chunk, const int32_t* d_clip_first,
+                        const double* d_q_out, const double* d_q_seam, const int32_t* d_chunk_status, double tol, double* d_resid,
+                        int32_t* d_bad_list, int32_t* d_nbad, double* d_seam_max, void* stream);
+
 /* ---- N1: SMPL-X frame extraction (the step in front of the loop) ---------- */
 /* A kinematic tree of J <= 64 joints (parents[j] < j, joint 0 the root) and the joints whose poses are
  * wanted: sel[nsel] (one output row each, in this order; nsel = 0 -> all J joints, row = joint).  For the
