@@ -101,6 +101,13 @@ _SIGS = {
     "gmr_chunk_gather_dev": (C.c_int, [C.c_int] * 6 + [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 8),
     "gmr_chunk_stitch_dev": (C.c_int, [C.c_int] * 5 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 10),
     "gmr_chunk_seams_dev": (C.c_int, [C.c_int] * 5 + [C.c_void_p] * 5 + [C.c_double] + [C.c_void_p] * 5),
+    "gmr_motion_lib_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "gmr_motion_lib_destroy": (C.c_int, [C.c_void_p]),
+    "gmr_motion_lib_fill_dev": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_void_p]),
+    "gmr_motion_lib_fill": (C.c_int, [C.c_void_p] * 5 + [C.c_int]),
+    "gmr_motion_lib_array": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "gmr_motion_sample_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 9),
+    "gmr_motion_sample": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8),
     "gmr_comm_create": (C.c_int, [C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),
     "gmr_comm_destroy": (C.c_int, [C.c_void_p]),
     "gmr_comm_rank": (C.c_int, [C.c_void_p]),

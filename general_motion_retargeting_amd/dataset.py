@@ -166,6 +166,7 @@ class DevicePost:
         self._events = None
         self._chunker = None
         self.chunk_reports: List = []             # per job of the last run: per-clip chunk reports (chunking.clip_report), or None
+        self.library = None                       # the motion library of the last run that asked for one (run(..., library=))
 
     def _d(self, name: str, nbytes: int):
         from . import _lib
@@ -228,8 +229,12 @@ class DevicePost:
         return calls, d_human
 
     def run(self, jobs: Sequence[Dict], km: KinematicsModel, ik_flags: int = 0, height_adjust: bool = True,
-            root_origin_offset: bool = True, ground_offset: float = 0.0, timing: Optional[Dict[str, float]] = None, chunk=None):
-        """``chunk`` (``None`` | ``chunking.ChunkSpec`` | ``"auto"``): jobs with a clip longer than the spec's ``frames`` run chunked
+            root_origin_offset: bool = True, ground_offset: float = 0.0, timing: Optional[Dict[str, float]] = None, chunk=None,
+            library: Optional[Dict] = None):
+        """``library`` (``None`` | ``{"fps": [per job: fps per clip], "ang_vel": "world" | "reference"}``): also fill a
+        ``motion_library.MotionLibrary`` from the post-processed block where it lies on the device (no second upload), on this
+        object's stream and before the block is reused; it is left in ``self.library``.  What is returned does not change.
+        ``chunk`` (``None`` | ``chunking.ChunkSpec`` | ``"auto"``): jobs with a clip longer than the spec's ``frames`` run chunked
         (:class:`chunking.ChunkRunner` in place of the one IK launch: NOT parity, ``chunk_reports`` says how far off); the
         post-processing reads the stitched clip-major output unchanged.
         ``jobs`` = ``[{"solver", "human": f64[S,T,nhuman,7] (page-locked for an asynchronous copy), "lens": i32[S],
@@ -370,6 +375,17 @@ class DevicePost:
                                      C.c_void_p(base + o_rr + r0 * 32), C.c_void_p(base + o_dp + r0 * ndof * 8),
                                      C.c_void_p(base + o_lb + r0 * nb * 12), None, height_adjust, root_origin_offset, ground_offset, st)
         ev[3].record(st)
+        self.library = None
+        if library is not None:
+            # the block is clip-contiguous from row 0 when one post-processing call covered it, in the jobs' own clip order
+            if len(chunks) != 1 or any(p is not None and not np.array_equal(p, np.arange(len(p))) for p in perms):
+                raise ValueError("a motion library takes the clips of at most 8 jobs in the order they were handed over")
+            from .motion_library import MotionLibrary
+            names = km.body_names
+            self.library = MotionLibrary.from_device(
+                chunks[0][2], np.concatenate([np.asarray(f, dtype=np.float64).reshape(-1) for f in library["fps"]]), ndof, nb,
+                C.c_void_p(base + o_rp), C.c_void_p(base + o_rr), C.c_void_p(base + o_dp), C.c_void_p(base + o_lb),
+                ang_vel=library.get("ang_vel", "world"), stream=st, link_body_lists=[names] * nclip)
         buf = self.pool.take(total)
         # (the address, not ctypes.cast: a cast leaves the buffer referring to itself, and only the cycle collector would
         #  hand the block back)
@@ -405,16 +421,23 @@ class ClipRetargeter:
     _raw_index: Optional[Dict[tuple, int]] = None        # topology key -> number of its page-locked rows block
     chunk = None                 # chunked retargeting of long clips: off
     chunk_report: Optional[List[Dict]] = None
+    _library_mode: Optional[str] = None       # hand the batch to a motion library: off
+    library = None
 
     def __init__(self, src_human: str, tgt_robot: str, actual_human_height: Optional[float] = None, height_adjust: bool = True,
-                 root_origin_offset: bool = True, offset_to_ground: bool = False, chunk=None):
-        """``chunk``: ``None`` (default: one stream per clip, as ever), a ``chunking.ChunkSpec`` or ``"auto"``: clips longer than the
+                 root_origin_offset: bool = True, offset_to_ground: bool = False, chunk=None, library=False):
+        """``library`` (``False`` | ``True`` | ``"world"`` | ``"reference"``): every batch also leaves a
+        ``motion_library.MotionLibrary`` of its clips in ``self.library`` -- on the device post-processing path filled from the
+        block the post-processing wrote, without a second upload (``True`` = ``"world"``).  The motion dicts do not change.
+        ``chunk``: ``None`` (default: one stream per clip, as ever), a ``chunking.ChunkSpec`` or ``"auto"``: clips longer than the
         spec's ``frames`` are cut into chunks that run as independent streams (NOT parity with the sequential run; DESIGN.md
         section 6g).  ``chunk_report`` then holds, per clip of the last batch, K, ``seam_max``, seams repaired / left bad, passes
         and ``warm_solves``; ``chunk_summary`` the totals over all batches."""
         self.gmr = GeneralMotionRetargeting(src_human, tgt_robot, actual_human_height=actual_human_height)
         self.height_adjust, self.root_origin_offset, self.offset_to_ground = height_adjust, root_origin_offset, offset_to_ground
         self.chunk = chunk
+        self._library_mode = None if not library else ("world" if library is True else str(library))
+        self.library = None
         self.chunk_report: Optional[List[Dict]] = None
         self.chunk_summary: Dict = {}
         self._km: Optional[KinematicsModel] = None
@@ -555,6 +578,9 @@ class ClipRetargeter:
         t3 = time.perf_counter()
         for k, v in (("ik", t2 - t1), ("post", t3 - t2)):
             self.timing[k] = self.timing.get(k, 0.0) + v
+        if self._library_mode is not None:      # (host post-processing: the arrays are on the host, so they go up once)
+            from .motion_library import MotionLibrary
+            self.library = MotionLibrary.from_motions(out, self._library_mode)
         return out
 
     def _finish_device(self, fps: Sequence[float], lens: np.ndarray) -> List[Dict]:
@@ -575,7 +601,10 @@ class ClipRetargeter:
             job = {"solver": gmr.hip_solver, "human": self._human[:S], "lens": lens, "q0": gmr.model.qpos0}
         self._n = 0
         rp, rr, dp, lbp, spans, (status,) = self._dev_post.run([job], self._km, gmr._flags(self.offset_to_ground), self.height_adjust,
-                                                               self.root_origin_offset, 0.0, self.timing, chunk=self.chunk)
+                                                               self.root_origin_offset, 0.0, self.timing, chunk=self.chunk,
+                                                               library=None if self._library_mode is None else
+                                                               {"fps": [list(fps)[:S]], "ang_vel": self._library_mode})
+        self.library = self._dev_post.library
         self.chunk_report = self._dev_post.chunk_reports[0]
         if self.chunk_report is not None:
             from . import chunking
@@ -601,19 +630,23 @@ class ClipRetargeter:
 
 def retarget_clips(src_human: str, tgt_robot: str, clips: Sequence, fps: Sequence[float],
                    actual_human_height: Optional[float] = None, height_adjust: bool = True,
-                   root_origin_offset: bool = True, offset_to_ground: bool = False, chunk=None, report: Optional[List] = None) -> List[Dict]:
-    """Retarget many clips of one (source, robot, height) in ONE IK launch.  ``chunk`` (``chunking.ChunkSpec`` or ``"auto"``; default
+                   root_origin_offset: bool = True, offset_to_ground: bool = False, chunk=None, report: Optional[List] = None,
+                   library=False):
+    """Retarget many clips of one (source, robot, height) in ONE IK launch.  ``library`` (``True`` | ``"world"`` | ``"reference"``;
+    default off): returns ``(motions, motion_library.MotionLibrary)``, the library filled on the device from the post-processed
+    batch; ``motions`` are the same bytes as without it.  ``chunk`` (``chunking.ChunkSpec`` or ``"auto"``; default
     off) cuts long clips into independently running chunks -- NOT parity; the per-clip chunk reports are appended to ``report``.
 
     ``clips[i]`` is a list of ``human_data`` dicts or an array ``[T_i, nhuman, 7]`` (ragged lengths
     are fine: streams are padded and the kernel stops each stream at its own length).
     Returns one motion dict per clip, identical to processing the clips one by one.
     """
-    rt = ClipRetargeter(src_human, tgt_robot, actual_human_height, height_adjust, root_origin_offset, offset_to_ground, chunk=chunk)
+    rt = ClipRetargeter(src_human, tgt_robot, actual_human_height, height_adjust, root_origin_offset, offset_to_ground, chunk=chunk,
+                        library=library)
     out = rt(clips, fps)
     if report is not None and rt.chunk_report is not None:
         report.extend(rt.chunk_report)
-    return out
+    return (out, rt.library) if library else out
 
 
 def retarget_mixed(groups: Sequence[Dict], offset_to_ground: bool = False, slices: int = 0, pinned_outputs: bool = False):

@@ -385,6 +385,61 @@ int gmr_bvh_frames_dev(gmr_bvh_t* h, int nclip, int B, const double* d_rows, con
 int gmr_bvh_frames(gmr_bvh_t* h, int nclip, int B, const double* rows, const int32_t* seg_start,
                    const double* offsets, int T, double* human);
 
+/* ---- N3: motion library (the training-side loader: derivatives, statistics, batched sampling) ---------------------- */
+/* What booster_gym/utils/motion_loader.py:100-247 does with the arrays of a motion pkl -- _compute_motion_stats,
+ * _compute_derivatives, get_motion_state -- for C clips (B frames in total, clip-contiguous) held in ONE block of device
+ * memory, with the per-frame and per-query Python loops replaced by three kernels.  Per clip c: T = seg_start[c + 1] -
+ * seg_start[c] frames at fps[c], dt = 1 / fps (double), duration = T / fps.
+ *   stored      float32 root_pos [B][3], root_rot [B][4] xyzw, dof_pos [B][ndof], local_body_pos [B][nbody][3] (optional)
+ *   derivatives root_vel, dof_vel: (x[i] - x[i - 1]) / (float)dt inside the clip, [0] = [1]; root_ang_vel [B][3]:
+ *               rotvec(r_i r_{i-1}^-1) / dt in float64 from the float32 quaternions, [0] = [1]; all zero for T == 1
+ *   stats       float32 [C][4][3 + ndof]: mean, unbiased std (NaN for T == 1), min, max of (root_pos | dof_pos) per column
+ * GMR_MOTION_ANGVEL_REFERENCE reproduces the reference's arithmetic, which reorders the quaternion to wxyz and then hands it
+ * to a scalar-LAST constructor (:131-135) -- the log of another rotation; the default is the physical world-frame angular
+ * velocity.  A library is immutable once its fill has completed, so sample calls on different streams may be in flight
+ * together; a sample must not be enqueued where it could run before the fill has finished. */
+typedef struct gmr_motion_lib gmr_motion_lib_t;
+#define GMR_MOTION_ANGVEL_WORLD     0   /* fill flags */
+#define GMR_MOTION_ANGVEL_REFERENCE 1
+#define GMR_MOTION_LOOP             1   /* sample flag: time modulo the clip's duration; without it, time clamped to duration - dt */
+/* array ids of gmr_motion_lib_array */
+#define GMR_MOTION_ROOT_POS       0
+#define GMR_MOTION_ROOT_ROT       1
+#define GMR_MOTION_DOF_POS        2
+#define GMR_MOTION_LOCAL_BODY_POS 3
+#define GMR_MOTION_ROOT_VEL       4
+#define GMR_MOTION_ROOT_ANG_VEL   5
+#define GMR_MOTION_DOF_VEL        6
+#define GMR_MOTION_STATS          7
+#define GMR_MOTION_SEG_START      8   /* i32 [C + 1] */
+#define GMR_MOTION_FPS            9   /* f64 [C]     */
+/* seg_start i32[C + 1] and fps f64[C] are HOST arrays, checked here (seg_start from 0, not descending, seg_start[C] == B; fps
+ * positive and finite; C, B >= 1) and uploaded: the kernels trust the library's own copy, never a caller's table. */
+int gmr_motion_lib_create(int C, int B, int ndof, int nbody, const int32_t* seg_start, const double* fps, gmr_motion_lib_t** out);
+int gmr_motion_lib_destroy(gmr_motion_lib_t* lib);
+/* The inputs as gmr_postprocess_clips_dev leaves them: root_pos f64[B][3], root_rot f64[B][4] xyzw, dof_pos f64[B][ndof],
+ * local_body_pos f32[B][nbody][3] (16-byte aligned) or NULL.  Two launches (fill, stats), asynchronous on `stream`; no load
+ * leaves rows [0, B) of the inputs. */
+int gmr_motion_lib_fill_dev(gmr_motion_lib_t* lib, const double* d_root_pos, const double* d_root_rot_xyzw,
+                            const double* d_dof_pos, const float* d_local_body_pos, int flags, void* stream);
+int gmr_motion_lib_fill(gmr_motion_lib_t* lib, const double* root_pos, const double* root_rot_xyzw, const double* dof_pos,
+                        const float* local_body_pos, int flags);   /* host buffers; synchronises */
+/* device address and size of one array of the library (local_body_pos: NULL / 0 when the fill had none) */
+int gmr_motion_lib_array(const gmr_motion_lib_t* lib, int which, void** d_ptr, size_t* bytes);
+/* N queries (clip i32[N], time f64[N]) in one launch.  t = time mod duration with GMR_MOTION_LOOP (Python's %), else
+ * min(time, duration - dt); x = t fps, lo = floor(x), hi = min(lo + 1, T - 1), blend = x - lo; lo == hi: the frame itself,
+ * otherwise (float)(1 - blend) a[lo] + (float)blend a[hi] (multiply and add rounded separately) and the reference's
+ * float32 slerp for root_rot (:205-233).  A frame index outside the clip (negative time without loop, t fps rounding up
+ * to T) is clamped to the nearest frame.  Outputs row-major [N][3] [N][4] [N][3] [N][3] [N][ndof] [N][ndof] [N][nbody][3];
+ * any of them may be NULL and is skipped.  A clip id outside [0, C), an empty clip or a non-finite time: that query's rows
+ * are NaN and status[i] = 1 (else 0); nothing of the library is read for it. */
+int gmr_motion_sample_dev(const gmr_motion_lib_t* lib, int N, const int32_t* d_clip, const double* d_time, int flags,
+                          float* d_root_pos, float* d_root_rot, float* d_root_vel, float* d_root_ang_vel, float* d_dof_pos,
+                          float* d_dof_vel, float* d_local_body_pos, int32_t* d_status, void* stream);
+int gmr_motion_sample(const gmr_motion_lib_t* lib, int N, const int32_t* clip, const double* time, int flags, float* root_pos,
+                      float* root_rot, float* root_vel, float* root_ang_vel, float* dof_pos, float* dof_vel,
+                      float* local_body_pos, int32_t* status);   /* host buffers; synchronises */
+
 /* ---- multi-GPU: one rank per GPU, ONE broadcast, no per-step collective ------------ */
 /* The reference parallelises over files with mp.Pool on one CPU (scripts/smplx_to_robot_dataset.py:241-242); here
  * streams shard over the ranks of one node and the only data that crosses ranks is the packed robot model + task set.
