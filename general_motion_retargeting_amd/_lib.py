@@ -276,6 +276,38 @@ def pinned_copy(a: np.ndarray) -> np.ndarray:
     return out
 
 
+def align256(nbytes) -> int:
+    """``nbytes`` rounded up to the 256-byte boundary every field of a packed device block starts on"""
+    return (int(nbytes) + 255) // 256 * 256
+
+
+class NamedBuffers:
+    """The grow-only buffers, by name, of an object that runs batch after batch: device blocks and page-locked host blocks.
+    A block that is too small is replaced, so the owner calls for one only when nothing enqueued still uses it (its batches
+    end with a stream synchronisation)."""
+
+    def __init__(self):
+        self._dev = {}
+        self._pin = {}
+
+    def device(self, name: str, nbytes: int) -> DeviceBuffer:
+        b = self._dev.get(name)
+        if b is None or b.nbytes < nbytes:
+            if b is not None:
+                b.free()
+            b = self._dev[name] = DeviceBuffer(nbytes + nbytes // 4 + 256)
+        return b
+
+    def pinned(self, name: str, shape, dtype) -> np.ndarray:
+        """a [shape] view of the page-locked block ``name`` (grown by half when too small)"""
+        need = int(np.prod(shape)) * np.dtype(dtype).itemsize
+        blk = self._pin.get(name)
+        if blk is None or blk.nbytes < need:
+            self._pin.pop(name, None)
+            blk = self._pin[name] = pinned_empty((need + need // 2 + 8,), np.uint8)
+        return blk[:need].view(dtype).reshape(shape)
+
+
 class Job(C.Structure):
     """``gmr_job_t``: one (solver, batch) of a group launch."""
     _fields_ = [("solver", C.c_void_p), ("S", C.c_int32), ("T", C.c_int32), ("q0", C.c_void_p), ("human", C.c_void_p),

@@ -198,27 +198,10 @@ class ChunkRunner:
     max K passes.  A repair pass is as long as one chunk whatever the number of bad chunks: passes cost, bad chunks do not."""
 
     def __init__(self):
-        self._dev: Dict[str, object] = {}
-        self._pin: Dict[str, np.ndarray] = {}
+        from . import _lib
+        self._bufs = _lib.NamedBuffers()
         self._events = None
         self.pass_ms: List[Dict[str, float]] = []      # per pass of the last run: gather / ik / stitch / seams (device events)
-
-    def _d(self, name: str, nbytes: int):
-        from . import _lib
-        b = self._dev.get(name)
-        if b is None or b.nbytes < nbytes:
-            if b is not None:
-                b.free()                     # (every pass ends with a stream synchronisation: nothing is in flight)
-            b = self._dev[name] = _lib.DeviceBuffer(nbytes + nbytes // 4 + 256)
-        return b
-
-    def _p(self, name: str, shape, dtype) -> np.ndarray:
-        from . import _lib
-        need = int(np.prod(shape)) * np.dtype(dtype).itemsize
-        blk = self._pin.get(name)
-        if blk is None or blk.nbytes < need:
-            blk = self._pin[name] = _lib.pinned_empty((need + need // 2 + 8,), np.uint8)
-        return blk[:need].view(dtype).reshape(shape)
 
     def run(self, launch: Sequence[tuple], lens: Sequence[np.ndarray], specs: Sequence[Optional[ChunkSpec]], flags: int, stream,
             timed: bool = False) -> List[Optional[List[Dict]]]:
@@ -249,10 +232,10 @@ class ChunkRunner:
                                  ("q0_c", n * nq * 8), ("q_out_c", n * Tc * nq * 8), ("nsolve_c", n * Tc * 8), ("status_c", n * 4),
                                  ("chunk_status", n * 4), ("q_seam", n * nq * 8), ("resid", n * 24), ("bad", n * 4), ("nbad", 4),
                                  ("seam_max", S * 24), ("warm", S * 4)):
-                j[name] = self._d(f"{name}_{i}", max(nbytes, 8))
+                j[name] = self._bufs.device(f"{name}_{i}", max(nbytes, 8))
             for name, shape, dt in (("h_nbad", (1,), np.int32), ("h_resid", (n, 3), np.float64), ("h_resid0", (n, 3), np.float64),
                                     ("h_warm", (S,), np.int32), ("h_cst", (n,), np.int32)):
-                j[name] = self._p(f"{name}_{i}", shape, dt)
+                j[name] = self._bufs.pinned(f"{name}_{i}", shape, dt)
             h2d(j["chunk"], p.chunk)
             h2d(j["first"], p.clip_first)
             jobs.append(j)

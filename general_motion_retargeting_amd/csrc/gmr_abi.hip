@@ -8,7 +8,6 @@
 #include <string.h>
 
 #include <algorithm>
-#include <mutex>
 #include <new>
 #include <vector>
 
@@ -18,6 +17,7 @@
 #include "gmr_ik_wide_layout.h"
 #include "gmr_internal.h"
 #include "gmr_post.h"
+#include "gmr_workspace.h"
 
 static_assert(sizeof(gmr_model_t) % 8 == 0, "gmr_model_t must be 8-byte sized");
 static_assert(sizeof(gmr_taskset_t) % 8 == 0, "gmr_taskset_t must be 8-byte sized");
@@ -68,53 +68,35 @@ int gmr_fail(int code, const char* fmt, ...) {
   va_end(ap);
   return code;
 }
-namespace {
 #define fail gmr_fail
-#define HIP_TRY(call)                                                                         \
-  do {                                                                                        \
-    hipError_t _e = (call);                                                                   \
-    if (_e != hipSuccess) return fail(GMR_ERR_HIP, "%s: %s", #call, hipGetErrorString(_e));   \
-  } while (0)
-}  // namespace
 
 struct gmr_solver {
   gmr_model_t model;
   gmr_taskset_t ts;
   gmr::IkLayout layout;          // one wave per stream (many streams)
   gmr::IkLayout layout4;         // main wave + 3 helpers per stream (few streams: latency shape)
-  uint4* d_image4 = nullptr;
+  gmr::DeviceBlock image4;
   int force_waves = 0;           // 0 = choose by stream count, 1 or 4 = forced (gmr_solver_set_waves)
   gmr::IkParams params;
-  uint4* d_image = nullptr;      // host-built LDS image of the constants (gmr_ik_layout.h)
+  gmr::DeviceBlock image;        // host-built LDS image of the constants (gmr_ik_layout.h)
   gmr::WideLayout wide;          // throughput shape (gmr_ik_wide.hip): ok = 0 when the robot does not fit it
-  char* d_wide = nullptr;        // its global image of the constants
+  gmr::DeviceBlock wide_image;   // its global image of the constants
   void* wide_pool = nullptr;     // queue workspaces of its queued dispatch mode (one per HIP stream)
-  char* ws = nullptr;            // grow-only device workspace of the host-buffer entry point
-  size_t ws_bytes = 0;
+  gmr::DeviceBlock ws;           // grow-only device workspace of the host-buffer entry point
   char* pin = nullptr;           // pinned host staging for small calls (one H2D + one D2H per call)
   static constexpr size_t kPinBytes = 1u << 20;
   // the sliced host pipeline (gmr_retarget_group): HIP streams and one device workspace per slice in flight
   static constexpr int kPipe = 4;
   hipStream_t pipe_stream[kPipe] = {nullptr, nullptr, nullptr, nullptr};
-  char* pipe_ws[kPipe] = {nullptr, nullptr, nullptr, nullptr};
-  size_t pipe_bytes[kPipe] = {0, 0, 0, 0};
+  gmr::DeviceBlock pipe_ws[kPipe];
 };
 
 struct gmr_fk {
   gmr::FkTree tree;
-  gmr::FkTree* d_tree = nullptr;
-  float* d_min_part = nullptr;
-  int min_part_cap = 0;
-  // gmr_postprocess_clips_dev: one grow-only scratch block per HIP stream that has called.  Work that still reads a block
-  // was enqueued on the block's own stream, so growing it waits for that stream alone and never frees memory another
-  // stream's kernels use; post_mu orders the host side (lookup, growth, the launches of one call).
-  struct PostWs {
-    hipStream_t stream;
-    char* d;
-    size_t bytes;
-  };
-  std::mutex post_mu;
-  std::vector<PostWs> post_ws;
+  gmr::DeviceBlock d_tree;       // the tree as the kernels read it
+  const gmr::FkTree* dev() const { return (const gmr::FkTree*)d_tree.data(); }
+  gmr::DeviceBlock min_part;     // gmr_fk_batch_dev: one float per block of the min_z reduction
+  gmr::StreamWorkspace post_ws;  // gmr_postprocess_clips_dev
 };
 
 extern "C" {
@@ -137,66 +119,66 @@ int gmr_device_count(void) {
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
   return n;
 }
-int gmr_set_device(int device) { HIP_TRY(hipSetDevice(device)); return GMR_OK; }
+int gmr_set_device(int device) { GMR_HIP_TRY(hipSetDevice(device)); return GMR_OK; }
 size_t gmr_sizeof_model(void) { return sizeof(gmr_model_t); }
 size_t gmr_sizeof_taskset(void) { return sizeof(gmr_taskset_t); }
 
 int gmr_malloc(void** ptr, size_t bytes) {
   if (!ptr) return fail(GMR_ERR_ARG, "gmr_malloc: null out pointer");
-  HIP_TRY(hipMalloc(ptr, bytes ? bytes : 8));
+  GMR_HIP_TRY(hipMalloc(ptr, bytes ? bytes : 8));
   return GMR_OK;
 }
-int gmr_free(void* ptr) { if (ptr) HIP_TRY(hipFree(ptr)); return GMR_OK; }
+int gmr_free(void* ptr) { if (ptr) GMR_HIP_TRY(hipFree(ptr)); return GMR_OK; }
 int gmr_host_alloc(void** ptr, size_t bytes) {
   if (!ptr) return fail(GMR_ERR_ARG, "gmr_host_alloc: null out pointer");
-  HIP_TRY(hipHostMalloc(ptr, bytes ? bytes : 8, hipHostMallocDefault));
+  GMR_HIP_TRY(hipHostMalloc(ptr, bytes ? bytes : 8, hipHostMallocDefault));
   return GMR_OK;
 }
-int gmr_host_free(void* ptr) { if (ptr) HIP_TRY(hipHostFree(ptr)); return GMR_OK; }
+int gmr_host_free(void* ptr) { if (ptr) GMR_HIP_TRY(hipHostFree(ptr)); return GMR_OK; }
 int gmr_host_register(void* ptr, size_t bytes) {
   if (!ptr) return fail(GMR_ERR_ARG, "gmr_host_register: null pointer");
-  HIP_TRY(hipHostRegister(ptr, bytes, hipHostRegisterDefault));
+  GMR_HIP_TRY(hipHostRegister(ptr, bytes, hipHostRegisterDefault));
   return GMR_OK;
 }
-int gmr_host_unregister(void* ptr) { if (ptr) HIP_TRY(hipHostUnregister(ptr)); return GMR_OK; }
+int gmr_host_unregister(void* ptr) { if (ptr) GMR_HIP_TRY(hipHostUnregister(ptr)); return GMR_OK; }
 int gmr_memset(void* ptr, int value, size_t bytes, void* stream) {
-  HIP_TRY(hipMemsetAsync(ptr, value, bytes, (hipStream_t)stream));
+  GMR_HIP_TRY(hipMemsetAsync(ptr, value, bytes, (hipStream_t)stream));
   return GMR_OK;
 }
 int gmr_memcpy_h2d(void* dst, const void* src, size_t bytes, void* stream) {
-  HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
+  GMR_HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
   return GMR_OK;
 }
 int gmr_memcpy_d2h(void* dst, const void* src, size_t bytes, void* stream) {
-  HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  GMR_HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, (hipStream_t)stream));
   return GMR_OK;
 }
 int gmr_stream_create(void** stream) {
   hipStream_t s;
-  HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  GMR_HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
   *stream = (void*)s;
   return GMR_OK;
 }
-int gmr_stream_destroy(void* stream) { HIP_TRY(hipStreamDestroy((hipStream_t)stream)); return GMR_OK; }
+int gmr_stream_destroy(void* stream) { GMR_HIP_TRY(hipStreamDestroy((hipStream_t)stream)); return GMR_OK; }
 int gmr_stream_sync(void* stream) {
-  if (stream) HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-  else HIP_TRY(hipDeviceSynchronize());
+  if (stream) GMR_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  else GMR_HIP_TRY(hipDeviceSynchronize());
   return GMR_OK;
 }
 int gmr_event_create(void** event) {
   hipEvent_t e;
-  HIP_TRY(hipEventCreate(&e));
+  GMR_HIP_TRY(hipEventCreate(&e));
   *event = (void*)e;
   return GMR_OK;
 }
-int gmr_event_destroy(void* event) { HIP_TRY(hipEventDestroy((hipEvent_t)event)); return GMR_OK; }
+int gmr_event_destroy(void* event) { GMR_HIP_TRY(hipEventDestroy((hipEvent_t)event)); return GMR_OK; }
 int gmr_event_record(void* event, void* stream) {
-  HIP_TRY(hipEventRecord((hipEvent_t)event, (hipStream_t)stream));
+  GMR_HIP_TRY(hipEventRecord((hipEvent_t)event, (hipStream_t)stream));
   return GMR_OK;
 }
 int gmr_event_elapsed_ms(void* start, void* stop, float* ms) {
-  HIP_TRY(hipEventSynchronize((hipEvent_t)stop));
-  HIP_TRY(hipEventElapsedTime(ms, (hipEvent_t)start, (hipEvent_t)stop));
+  GMR_HIP_TRY(hipEventSynchronize((hipEvent_t)stop));
+  GMR_HIP_TRY(hipEventElapsedTime(ms, (hipEvent_t)start, (hipEvent_t)stop));
   return GMR_OK;
 }
 
@@ -269,9 +251,9 @@ int gmr_solver_create(const gmr_model_t* model, const gmr_taskset_t* taskset, gm
     lay = gmr::make_ik_layout(s->model, s->ts, sch, nw);
     if (lay.smem_bytes > 160 * 1024 - 1024) { delete s; return fail(GMR_ERR_ARG, "robot too large for LDS"); }
     std::vector<char> img = gmr::make_ik_image(s->model, s->ts, sch, lay);
-    uint4** dst = v == 0 ? &s->d_image : &s->d_image4;
-    if ((e = hipMalloc((void**)dst, img.size())) != hipSuccess) break;
-    if ((e = hipMemcpy(*dst, img.data(), img.size(), hipMemcpyHostToDevice)) != hipSuccess) break;
+    gmr::DeviceBlock& dst = v == 0 ? s->image : s->image4;
+    if ((e = dst.reserve(img.size())) != hipSuccess) break;
+    if ((e = hipMemcpy(dst.data(), img.data(), img.size(), hipMemcpyHostToDevice)) != hipSuccess) break;
     e = gmr_ik_set_max_smem(lay.nvp, nw, lay.tree_small, lay.smem_bytes);
   }
   s->wide = gmr::WideLayout{};
@@ -279,15 +261,12 @@ int gmr_solver_create(const gmr_model_t* model, const gmr_taskset_t* taskset, gm
     std::vector<char> img;
     s->wide = gmr::make_wide_layout(s->model, s->ts, &img);
     if (s->wide.ok) {
-      if ((e = hipMalloc((void**)&s->d_wide, img.size())) == hipSuccess)
-        e = hipMemcpy(s->d_wide, img.data(), img.size(), hipMemcpyHostToDevice);
+      if ((e = s->wide_image.reserve(img.size())) == hipSuccess)
+        e = hipMemcpy(s->wide_image.data(), img.data(), img.size(), hipMemcpyHostToDevice);
       if (e == hipSuccess) s->wide_pool = gmr_ik_wide_pool_create();
     }
   }
   if (e != hipSuccess) {
-    if (s->d_image) (void)hipFree(s->d_image);
-    if (s->d_image4) (void)hipFree(s->d_image4);
-    if (s->d_wide) (void)hipFree(s->d_wide);
     gmr_ik_wide_pool_destroy(s->wide_pool);
     delete s;
     return fail(GMR_ERR_HIP, "gmr_solver_create: %s", hipGetErrorString(e));
@@ -298,16 +277,10 @@ int gmr_solver_create(const gmr_model_t* model, const gmr_taskset_t* taskset, gm
 
 int gmr_solver_destroy(gmr_solver_t* s) {
   if (!s) return GMR_OK;
-  (void)hipFree(s->d_image);
-  (void)hipFree(s->d_image4);
-  if (s->d_wide) (void)hipFree(s->d_wide);
   gmr_ik_wide_pool_destroy(s->wide_pool);
-  if (s->ws) (void)hipFree(s->ws);
   if (s->pin) (void)hipHostFree(s->pin);
-  for (int i = 0; i < gmr_solver::kPipe; i++) {
+  for (int i = 0; i < gmr_solver::kPipe; i++)
     if (s->pipe_stream[i]) { (void)hipStreamSynchronize(s->pipe_stream[i]); (void)hipStreamDestroy(s->pipe_stream[i]); }
-    if (s->pipe_ws[i]) (void)hipFree(s->pipe_ws[i]);
-  }
   delete s;
   return GMR_OK;
 }
@@ -348,10 +321,10 @@ int gmr_retarget_streams_dev(gmr_solver_t* s, int S, int T, const double* d_q0, 
   // latency); many streams: 1 wave per stream (more streams resident, more frames per second)
   const bool wide = s->layout4.tree_ok && (s->force_waves ? s->force_waves == 4 : S <= GMR_HELPER_MAX_STREAMS);
   if (!wide && s->wide.ok)     // throughput shape: two resident wavefronts per SIMD (gmr_ik_wide.hip)
-    HIP_TRY(gmr_launch_ik_wide(s->d_wide, &s->wide, &s->params, S, T, d_q0, d_human, d_len, flags, d_q_out, d_nsolve,
+    GMR_HIP_TRY(gmr_launch_ik_wide(s->wide_image.data(), &s->wide, &s->params, S, T, d_q0, d_human, d_len, flags, d_q_out, d_nsolve,
                                d_status, d_tgt_out, d_err_out, (hipStream_t)stream, nullptr, s->wide_pool));
   else
-    HIP_TRY(gmr_launch_ik_streams(wide ? s->d_image4 : s->d_image, wide ? &s->layout4 : &s->layout, &s->params, S, T,
+    GMR_HIP_TRY(gmr_launch_ik_streams((const uint4*)(wide ? s->image4 : s->image).data(), wide ? &s->layout4 : &s->layout, &s->params, S, T,
                                   d_q0, d_human, d_len, flags, d_q_out, d_nsolve, d_status, d_tgt_out, d_err_out,
                                   (hipStream_t)stream, nullptr));
   return GMR_OK;
@@ -394,7 +367,7 @@ int gmr_retarget_group_dev(const gmr_job_t* jobs, int njobs, int flags, void* st
     gmr_solver* s = J.solver;
     if (njobs > 1 && job_takes_wide_shape(s, total)) {
       if (nw == 0) pool = s->wide_pool;
-      wd[nw++] = gmr_wide_job_desc{s->d_wide, &s->wide, &s->params, J.S, J.T, J.q0, J.human, J.len, J.q_out, J.nsolve, J.status,
+      wd[nw++] = gmr_wide_job_desc{s->wide_image.data(), &s->wide, &s->params, J.S, J.T, J.q0, J.human, J.len, J.q_out, J.nsolve, J.status,
                                    J.tgt_out, J.err_out};
       if (nw == 8) { int rc = flush(); if (rc) return rc; }
     } else {
@@ -438,7 +411,7 @@ int gmr_retarget_group_window_dev(const gmr_job_t* jobs, int njobs, int flags, i
     if (J.S == 0 || J.T == 0) continue;
     gmr_solver* s = J.solver;
     if (nw == 0) pool = s->wide_pool;
-    wd[nw++] = gmr_wide_job_desc{s->d_wide, &s->wide, &s->params, J.S, J.T, J.q0, J.human, J.len, J.q_out, J.nsolve, J.status,
+    wd[nw++] = gmr_wide_job_desc{s->wide_image.data(), &s->wide, &s->params, J.S, J.T, J.q0, J.human, J.len, J.q_out, J.nsolve, J.status,
                                  J.tgt_out, J.err_out};
   }
   if (nw == 0) return GMR_OK;
@@ -453,38 +426,49 @@ int gmr_retarget_group_window_dev(const gmr_job_t* jobs, int njobs, int flags, i
 // window w - 1 likewise.  (Cutting such a batch by streams loses: launches narrower than the resident width are bound by
 // their longest stream.)  Three HIP streams, one device workspace holding the whole batch; results are bit-identical to
 // one launch -- the per-stream state travels from window to window in device memory.
+// The arrays of S streams of job J in a workspace of the host-buffer entry points, in the order the zero-fill relies on:
+// [qo, end) is what the kernel writes (q_out, nsolve, status, then tgt_out and err_out when the caller wants them).
+struct JobOff { size_t q0, h, len, qo, ns, st, tg, er, end; };
+static JobOff carve_job(gmr::Carve& c, const gmr_job_t& J, size_t S) {
+  const size_t nq = J.solver->model.nq, nh = J.solver->ts.nhuman, T = (size_t)J.T;
+  JobOff o;
+  o.q0 = c.take(S * nq * 8);
+  o.h = c.take(S * T * nh * 56);
+  o.len = c.take(S * 4);
+  o.qo = c.take(S * T * nq * 8);
+  o.ns = c.take(S * T * 8);
+  o.st = c.take(S * 4);
+  o.tg = c.take(J.tgt_out ? S * T * nh * 56 : 0);
+  o.er = c.take(J.err_out ? S * T * 16 : 0);
+  o.end = c.total();
+  return o;
+}
+// job J with its buffers at those offsets of the device block d (an array the caller did not give stays null)
+static gmr_job_t job_at(const gmr_job_t& J, char* d, const JobOff& o) {
+  gmr_job_t D = J;
+  D.q0 = (const double*)(d + o.q0); D.human = (const double*)(d + o.h); D.len = J.len ? (const int32_t*)(d + o.len) : nullptr;
+  D.q_out = (double*)(d + o.qo); D.nsolve = (int32_t*)(d + o.ns); D.status = (int32_t*)(d + o.st);
+  D.tgt_out = J.tgt_out ? (double*)(d + o.tg) : nullptr; D.err_out = J.err_out ? (double*)(d + o.er) : nullptr;
+  return D;
+}
+
 static int retarget_group_windows(const gmr_job_t* jobs, int njobs, int flags, gmr_solver* owner, int W) {
-  auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-  struct Off { size_t q0, h, len, qo, ns, st, tg, er; };
-  std::vector<Off> off((size_t)njobs);
-  size_t need = 0;
+  std::vector<JobOff> off((size_t)njobs);
+  gmr::Carve need;
   int maxT = 0;
   for (int j = 0; j < njobs; j++) {
     const gmr_job_t& J = jobs[j];
     if (J.S == 0 || J.T == 0) continue;
-    const size_t nq = J.solver->model.nq, nh = J.solver->ts.nhuman, S = (size_t)J.S, T = (size_t)J.T;
-    Off& o = off[j];
-    o.q0 = need; need += up(S * nq * 8);
-    o.h = need; need += up(S * T * nh * 56);
-    o.len = need; need += up(S * 4);
-    o.qo = need; need += up(S * T * nq * 8);
-    o.ns = need; need += up(S * T * 8);
-    o.st = need; need += up(S * 4);
-    o.tg = need; need += J.tgt_out ? up(S * T * nh * 56) : 0;
-    o.er = need; need += J.err_out ? up(S * T * 16) : 0;
+    off[j] = carve_job(need, J, (size_t)J.S);
     maxT = std::max(maxT, J.T);
   }
   for (int i = 0; i < 3; i++)
-    if (!owner->pipe_stream[i]) HIP_TRY(hipStreamCreateWithFlags(&owner->pipe_stream[i], hipStreamNonBlocking));
+    if (!owner->pipe_stream[i]) GMR_HIP_TRY(hipStreamCreateWithFlags(&owner->pipe_stream[i], hipStreamNonBlocking));
   hipStream_t s_in = owner->pipe_stream[0], s_k = owner->pipe_stream[1], s_out = owner->pipe_stream[2];
-  if (need > owner->pipe_bytes[0]) {
-    for (int i = 0; i < 3; i++) HIP_TRY(hipStreamSynchronize(owner->pipe_stream[i]));
-    if (owner->pipe_ws[0]) (void)hipFree(owner->pipe_ws[0]);
-    owner->pipe_ws[0] = nullptr; owner->pipe_bytes[0] = 0;
-    HIP_TRY(hipMalloc((void**)&owner->pipe_ws[0], need));
-    owner->pipe_bytes[0] = need;
-  }
-  char* d = owner->pipe_ws[0];
+  if (need.total() > owner->pipe_ws[0].size())
+    for (int i = 0; i < 3; i++) GMR_HIP_TRY(hipStreamSynchronize(owner->pipe_stream[i]));
+  GMR_HIP_TRY(owner->pipe_ws[0].reserve(need.total()));       // exact: this block holds a whole batch
+  char* d = owner->pipe_ws[0].data();
   W = std::max(2, std::min(W, maxT / 2));
   int wl = (maxT + W - 1) / W;
   wl = (wl + 3) / 4 * 4;                              // whole queue items (4 frames) per window
@@ -500,21 +484,17 @@ static int retarget_group_windows(const gmr_job_t* jobs, int njobs, int flags, g
   auto new_event = [&](hipEvent_t* out) { e = hipEventCreateWithFlags(out, hipEventDisableTiming); if (e == hipSuccess) ev.push_back(*out); return e; };
   for (int j = 0; j < njobs && rc == GMR_OK; j++) {
     const gmr_job_t& J = jobs[j];
-    gmr_job_t& D = dj[j];
-    D = J;
+    dj[j] = J;
     if (J.S == 0 || J.T == 0) continue;
-    const Off& o = off[j];
-    const size_t nq = J.solver->model.nq, nh = J.solver->ts.nhuman, S = (size_t)J.S, T = (size_t)J.T;
+    const JobOff& o = off[j];
+    const size_t nq = J.solver->model.nq, S = (size_t)J.S;
     if ((e = hipMemcpyAsync(d + o.q0, J.q0, S * nq * 8, hipMemcpyHostToDevice, s_in)) != hipSuccess ||
         (J.len && (e = hipMemcpyAsync(d + o.len, J.len, S * 4, hipMemcpyHostToDevice, s_in)) != hipSuccess))
       rc = fail(GMR_ERR_HIP, "H2D copy: %s", hipGetErrorString(e));
-    if (rc == GMR_OK && (J.len || J.tgt_out || J.err_out)) {      // rows the kernel does not write come back as zeros
-      const size_t end = J.err_out ? o.er + up(S * T * 16) : (J.tgt_out ? o.tg + up(S * T * nh * 56) : o.st + up(S * 4));
-      if ((e = hipMemsetAsync(d + o.qo, 0, end - o.qo, s_k)) != hipSuccess) rc = fail(GMR_ERR_HIP, "memset: %s", hipGetErrorString(e));
-    }
-    D.q0 = (const double*)(d + o.q0); D.human = (const double*)(d + o.h); D.len = J.len ? (const int32_t*)(d + o.len) : nullptr;
-    D.q_out = (double*)(d + o.qo); D.nsolve = (int32_t*)(d + o.ns); D.status = (int32_t*)(d + o.st);
-    D.tgt_out = J.tgt_out ? (double*)(d + o.tg) : nullptr; D.err_out = J.err_out ? (double*)(d + o.er) : nullptr;
+    // rows the kernel does not write come back as zeros
+    if (rc == GMR_OK && (J.len || J.tgt_out || J.err_out) && (e = hipMemsetAsync(d + o.qo, 0, o.end - o.qo, s_k)) != hipSuccess)
+      rc = fail(GMR_ERR_HIP, "memset: %s", hipGetErrorString(e));
+    dj[j] = job_at(J, d, o);
   }
   for (int tb = 0; tb < maxT && rc == GMR_OK; tb += wl) {
     const int te = std::min(tb + wl, maxT);
@@ -537,7 +517,7 @@ static int retarget_group_windows(const gmr_job_t* jobs, int njobs, int flags, g
     for (int j = 0; j < njobs && rc == GMR_OK; j++) {
       const gmr_job_t& J = jobs[j];
       if (J.S == 0 || J.T == 0 || tb >= J.T) continue;
-      const Off& o = off[j];
+      const JobOff& o = off[j];
       const size_t nq = J.solver->model.nq, nh = J.solver->ts.nhuman, T = (size_t)J.T, S = (size_t)J.S, n = (size_t)(std::min(te, (int)J.T) - tb);
       auto back = [&](void* host, size_t dev_off, size_t row) {
         return hipMemcpy2DAsync((char*)host + (size_t)tb * row, T * row, d + dev_off + (size_t)tb * row, T * row, n * row, S, hipMemcpyDeviceToHost, s_out);
@@ -594,71 +574,53 @@ int gmr_retarget_group(const gmr_job_t* jobs, int njobs, int flags, int slices) 
     if (want && maxT >= 4 && group_is_windowable(jobs, njobs) && !getenv("GMR_NO_WINDOWS"))
       return retarget_group_windows(jobs, njobs, flags, owner, slices < 0 ? -slices : (int)std::min<size_t>(8, in_bytes >> 26));
   }
-  auto up = [](size_t x) { return (x + 255) / 256 * 256; };
   int rc = GMR_OK;
   hipError_t e = hipSuccess;
   const int nslot = std::min(n, (int)gmr_solver::kPipe);
   for (int i = 0; i < nslot; i++)
-    if (!owner->pipe_stream[i]) HIP_TRY(hipStreamCreateWithFlags(&owner->pipe_stream[i], hipStreamNonBlocking));
+    if (!owner->pipe_stream[i]) GMR_HIP_TRY(hipStreamCreateWithFlags(&owner->pipe_stream[i], hipStreamNonBlocking));
   std::vector<gmr_job_t> dj((size_t)njobs);
   for (int k = 0; k < n && rc == GMR_OK; k++) {
     const int slot = k % gmr_solver::kPipe;
     hipStream_t st = owner->pipe_stream[slot];
     // layout of this slice in the slot's workspace
-    size_t need = 0;
-    struct Off { size_t q0, h, len, qo, ns, st, tg, er; int s0, S; };
-    std::vector<Off> off((size_t)njobs);
+    gmr::Carve need;
+    struct Slice { JobOff o; int s0, S; };
+    std::vector<Slice> off((size_t)njobs);
     for (int j = 0; j < njobs; j++) {
       const gmr_job_t& J = jobs[j];
-      Off& o = off[j];
-      o.s0 = (int)((long long)J.S * k / n);
-      o.S = (int)((long long)J.S * (k + 1) / n) - o.s0;
-      if (J.S == 0 || J.T == 0) { o.S = 0; continue; }
-      const size_t nq = J.solver->model.nq, nh = J.solver->ts.nhuman, S = (size_t)o.S, T = (size_t)J.T;
-      o.q0 = need; need += up(S * nq * 8);
-      o.h = need; need += up(S * T * nh * 56);
-      o.len = need; need += up(S * 4);
-      o.qo = need; need += up(S * T * nq * 8);
-      o.ns = need; need += up(S * T * 8);
-      o.st = need; need += up(S * 4);
-      o.tg = need; need += J.tgt_out ? up(S * T * nh * 56) : 0;
-      o.er = need; need += J.err_out ? up(S * T * 16) : 0;
+      Slice& sl = off[j];
+      sl.s0 = (int)((long long)J.S * k / n);
+      sl.S = (int)((long long)J.S * (k + 1) / n) - sl.s0;
+      if (J.S == 0 || J.T == 0) { sl.S = 0; continue; }
+      sl.o = carve_job(need, J, (size_t)sl.S);
     }
-    if (need > owner->pipe_bytes[slot]) {
-      HIP_TRY(hipStreamSynchronize(st));
-      if (owner->pipe_ws[slot]) (void)hipFree(owner->pipe_ws[slot]);
-      owner->pipe_ws[slot] = nullptr; owner->pipe_bytes[slot] = 0;
-      HIP_TRY(hipMalloc((void**)&owner->pipe_ws[slot], need));
-      owner->pipe_bytes[slot] = need;
-    }
-    char* d = owner->pipe_ws[slot];
+    if (need.total() > owner->pipe_ws[slot].size()) GMR_HIP_TRY(hipStreamSynchronize(st));
+    GMR_HIP_TRY(owner->pipe_ws[slot].reserve(need.total()));
+    char* d = owner->pipe_ws[slot].data();
     for (int j = 0; j < njobs && rc == GMR_OK; j++) {
       const gmr_job_t& J = jobs[j];
-      const Off& o = off[j];
+      const JobOff& o = off[j].o;
       gmr_job_t& D = dj[j];
       D = J;
-      D.S = o.S;
-      if (o.S == 0) continue;
-      const size_t nq = J.solver->model.nq, nh = J.solver->ts.nhuman, S = (size_t)o.S, T = (size_t)J.T, s0 = (size_t)o.s0;
+      D.S = off[j].S;
+      if (D.S == 0) continue;
+      const size_t nq = J.solver->model.nq, nh = J.solver->ts.nhuman, S = (size_t)D.S, T = (size_t)J.T, s0 = (size_t)off[j].s0;
       if ((e = hipMemcpyAsync(d + o.q0, J.q0 + s0 * nq, S * nq * 8, hipMemcpyHostToDevice, st)) != hipSuccess ||
           (e = hipMemcpyAsync(d + o.h, J.human + s0 * T * nh * 7, S * T * nh * 56, hipMemcpyHostToDevice, st)) != hipSuccess ||
           (J.len && (e = hipMemcpyAsync(d + o.len, J.len + s0, S * 4, hipMemcpyHostToDevice, st)) != hipSuccess))
         rc = fail(GMR_ERR_HIP, "H2D copy: %s", hipGetErrorString(e));
       // rows the kernel does not write come back as zeros (see gmr_hip.h)
-      if (rc == GMR_OK && (J.len || J.tgt_out || J.err_out)) {
-        const size_t end = J.err_out ? o.er + up(S * T * 16) : (J.tgt_out ? o.tg + up(S * T * nh * 56) : o.st + up(S * 4));
-        if ((e = hipMemsetAsync(d + o.qo, 0, end - o.qo, st)) != hipSuccess) rc = fail(GMR_ERR_HIP, "memset: %s", hipGetErrorString(e));
-      }
-      D.q0 = (const double*)(d + o.q0); D.human = (const double*)(d + o.h); D.len = J.len ? (const int32_t*)(d + o.len) : nullptr;
-      D.q_out = (double*)(d + o.qo); D.nsolve = (int32_t*)(d + o.ns); D.status = (int32_t*)(d + o.st);
-      D.tgt_out = J.tgt_out ? (double*)(d + o.tg) : nullptr; D.err_out = J.err_out ? (double*)(d + o.er) : nullptr;
+      if (rc == GMR_OK && (J.len || J.tgt_out || J.err_out) && (e = hipMemsetAsync(d + o.qo, 0, o.end - o.qo, st)) != hipSuccess)
+        rc = fail(GMR_ERR_HIP, "memset: %s", hipGetErrorString(e));
+      D = job_at(D, d, o);
     }
     if (rc == GMR_OK) rc = gmr_retarget_group_dev(dj.data(), njobs, flags, st);
     for (int j = 0; j < njobs && rc == GMR_OK; j++) {
       const gmr_job_t& J = jobs[j];
-      const Off& o = off[j];
-      if (o.S == 0) continue;
-      const size_t nq = J.solver->model.nq, nh = J.solver->ts.nhuman, S = (size_t)o.S, T = (size_t)J.T, s0 = (size_t)o.s0;
+      const JobOff& o = off[j].o;
+      if (off[j].S == 0) continue;
+      const size_t nq = J.solver->model.nq, nh = J.solver->ts.nhuman, S = (size_t)off[j].S, T = (size_t)J.T, s0 = (size_t)off[j].s0;
       if ((e = hipMemcpyAsync(J.q_out + s0 * T * nq, d + o.qo, S * T * nq * 8, hipMemcpyDeviceToHost, st)) != hipSuccess ||
           (e = hipMemcpyAsync(J.nsolve + s0 * T * 2, d + o.ns, S * T * 8, hipMemcpyDeviceToHost, st)) != hipSuccess ||
           (e = hipMemcpyAsync(J.status + s0, d + o.st, S * 4, hipMemcpyDeviceToHost, st)) != hipSuccess ||
@@ -679,10 +641,10 @@ int gmr_retarget_streams_prof(gmr_solver_t* s, int S, int T, const double* d_q0,
                               double* d_q_out, int32_t* d_nsolve, int32_t* d_status, unsigned long long* d_prof) {
   const bool wide = s->layout4.tree_ok && (s->force_waves ? s->force_waves == 4 : S <= GMR_HELPER_MAX_STREAMS);
   if (!wide && s->wide.ok)
-    HIP_TRY(gmr_launch_ik_wide(s->d_wide, &s->wide, &s->params, S, T, d_q0, d_human, nullptr, flags, d_q_out, d_nsolve,
+    GMR_HIP_TRY(gmr_launch_ik_wide(s->wide_image.data(), &s->wide, &s->params, S, T, d_q0, d_human, nullptr, flags, d_q_out, d_nsolve,
                                d_status, nullptr, nullptr, nullptr, d_prof, nullptr));
   else
-    HIP_TRY(gmr_launch_ik_streams(wide ? s->d_image4 : s->d_image, wide ? &s->layout4 : &s->layout, &s->params, S, T,
+    GMR_HIP_TRY(gmr_launch_ik_streams((const uint4*)(wide ? s->image4 : s->image).data(), wide ? &s->layout4 : &s->layout, &s->params, S, T,
                                   d_q0, d_human, nullptr, flags, d_q_out, d_nsolve, d_status, nullptr, nullptr, nullptr, d_prof));
   return GMR_OK;
 }
@@ -694,72 +656,62 @@ int gmr_retarget_streams(gmr_solver_t* s, int S, int T, const double* q0, const 
   if (S < 0 || T < 0) return fail(GMR_ERR_ARG, "negative S/T");
   if (S == 0 || T == 0) return GMR_OK;
   if (!q0 || !human || !q_out || !nsolve || !status) return fail(GMR_ERR_ARG, "null host buffer");
+  const gmr_job_t job{s, S, T, q0, human, len, q_out, nsolve, status, tgt_out, err_out};
   const size_t nq = s->model.nq, nh = s->ts.nhuman;
   const size_t b_q0 = (size_t)S * nq * 8, b_h = (size_t)S * T * nh * 7 * 8, b_qo = (size_t)S * T * nq * 8;
   const size_t b_ns = (size_t)S * T * 2 * 4, b_st = (size_t)S * 4, b_len = (size_t)S * 4;
   const size_t b_tg = tgt_out ? b_h : 0, b_er = err_out ? (size_t)S * T * 2 * 8 : 0;
-  if (b_h >= ((size_t)32 << 20)) {       // large batches: sliced, copies overlapped with the kernels (gmr_retarget_group)
-    const gmr_job_t job{s, S, T, q0, human, len, q_out, nsolve, status, tgt_out, err_out};
-    return gmr_retarget_group(&job, 1, flags, 0);
-  }
-  auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-  size_t o_q0 = 0, o_h = o_q0 + up(b_q0), o_len = o_h + up(b_h), o_qo = o_len + up(b_len), o_ns = o_qo + up(b_qo),
-         o_st = o_ns + up(b_ns), o_tg = o_st + up(b_st), o_er = o_tg + up(b_tg), total = o_er + up(b_er);
+  // large batches: sliced, copies overlapped with the kernels (gmr_retarget_group)
+  if (b_h >= ((size_t)32 << 20)) return gmr_retarget_group(&job, 1, flags, 0);
+  gmr::Carve layout;
+  const JobOff o = carve_job(layout, job, (size_t)S);
   // grow-only workspace kept on the handle: a per-frame caller (retarget() once per frame) pays no
   // hipMalloc/hipFree per call.  Like the reference object, a handle is not re-entrant on this path.
-  if (total > s->ws_bytes) {
-    if (s->ws) (void)hipFree(s->ws);
-    s->ws = nullptr;
-    s->ws_bytes = 0;
-    size_t want = total < (1u << 20) ? (1u << 20) : total;
-    HIP_TRY(hipMalloc((void**)&s->ws, want));
-    s->ws_bytes = want;
-  }
-  char* d = s->ws;
+  GMR_HIP_TRY(s->ws.reserve(o.end, 0, 1u << 20));
+  char* d = s->ws.data();
   int rc = GMR_OK;
   hipError_t e;
   // buffers are laid out [q0 | human | len | q_out | nsolve | status | tgt_out | err_out]; small calls (the per-frame
   // API) go through pinned staging so that a call is 1 H2D + 1 launch + 1 D2H + 1 sync
-  const size_t in_bytes = o_qo, out_bytes = total - o_qo;
-  const bool small = total <= gmr_solver::kPinBytes;
-  if (small && !s->pin) HIP_TRY(hipHostMalloc((void**)&s->pin, gmr_solver::kPinBytes, hipHostMallocDefault));
+  const size_t in_bytes = o.qo, out_bytes = o.end - o.qo;
+  const bool small = o.end <= gmr_solver::kPinBytes;
+  if (small && !s->pin) GMR_HIP_TRY(hipHostMalloc((void**)&s->pin, gmr_solver::kPinBytes, hipHostMallocDefault));
   if (small) {
-    memcpy(s->pin + o_q0, q0, b_q0);
-    memcpy(s->pin + o_h, human, b_h);
-    if (len) memcpy(s->pin + o_len, len, b_len);
+    memcpy(s->pin + o.q0, q0, b_q0);
+    memcpy(s->pin + o.h, human, b_h);
+    if (len) memcpy(s->pin + o.len, len, b_len);
     if ((e = hipMemcpyAsync(d, s->pin, in_bytes, hipMemcpyHostToDevice, nullptr)) != hipSuccess)
       rc = fail(GMR_ERR_HIP, "H2D copy: %s", hipGetErrorString(e));
-  } else if ((e = hipMemcpyAsync(d + o_q0, q0, b_q0, hipMemcpyHostToDevice, nullptr)) != hipSuccess ||
-             (e = hipMemcpyAsync(d + o_h, human, b_h, hipMemcpyHostToDevice, nullptr)) != hipSuccess ||
-             (len && (e = hipMemcpyAsync(d + o_len, len, b_len, hipMemcpyHostToDevice, nullptr)) != hipSuccess)) {
+  } else if ((e = hipMemcpyAsync(d + o.q0, q0, b_q0, hipMemcpyHostToDevice, nullptr)) != hipSuccess ||
+             (e = hipMemcpyAsync(d + o.h, human, b_h, hipMemcpyHostToDevice, nullptr)) != hipSuccess ||
+             (len && (e = hipMemcpyAsync(d + o.len, len, b_len, hipMemcpyHostToDevice, nullptr)) != hipSuccess)) {
     rc = fail(GMR_ERR_HIP, "H2D copy: %s", hipGetErrorString(e));
   }
   // frames at or beyond len[s] are not touched by the kernel, nor are the tgt_out / err_out rows of the frames after a
   // stream's status turned non-OK (err_out: including the failing frame): hand them back as zeros, never as what an
   // earlier call left in the grow-only workspace
-  if (rc == GMR_OK && (len || tgt_out || err_out) && (e = hipMemsetAsync(d + o_qo, 0, out_bytes, nullptr)) != hipSuccess)
+  if (rc == GMR_OK && (len || tgt_out || err_out) && (e = hipMemsetAsync(d + o.qo, 0, out_bytes, nullptr)) != hipSuccess)
     rc = fail(GMR_ERR_HIP, "memset: %s", hipGetErrorString(e));
+  const gmr_job_t D = job_at(job, d, o);
   if (rc == GMR_OK)
-    rc = gmr_retarget_streams_dev(s, S, T, (double*)(d + o_q0), (double*)(d + o_h), len ? (int32_t*)(d + o_len) : nullptr,
-                                  flags, (double*)(d + o_qo), (int32_t*)(d + o_ns), (int32_t*)(d + o_st),
-                                  tgt_out ? (double*)(d + o_tg) : nullptr, err_out ? (double*)(d + o_er) : nullptr, nullptr);
+    rc = gmr_retarget_streams_dev(s, S, T, D.q0, D.human, D.len, flags, D.q_out, D.nsolve, D.status, D.tgt_out, D.err_out, nullptr);
   if (rc == GMR_OK && small) {
-    if ((e = hipMemcpyAsync(s->pin + o_qo, d + o_qo, out_bytes, hipMemcpyDeviceToHost, nullptr)) != hipSuccess ||
+    if ((e = hipMemcpyAsync(s->pin + o.qo, d + o.qo, out_bytes, hipMemcpyDeviceToHost, nullptr)) != hipSuccess ||
         (e = hipStreamSynchronize(nullptr)) != hipSuccess)
       rc = fail(GMR_ERR_HIP, "kernel / D2H copy: %s", hipGetErrorString(e));
     else {
-      memcpy(q_out, s->pin + o_qo, b_qo);
-      memcpy(nsolve, s->pin + o_ns, b_ns);
-      memcpy(status, s->pin + o_st, b_st);
-      if (tgt_out) memcpy(tgt_out, s->pin + o_tg, b_tg);
-      if (err_out) memcpy(err_out, s->pin + o_er, b_er);
+      memcpy(q_out, s->pin + o.qo, b_qo);
+      memcpy(nsolve, s->pin + o.ns, b_ns);
+      memcpy(status, s->pin + o.st, b_st);
+      if (tgt_out) memcpy(tgt_out, s->pin + o.tg, b_tg);
+      if (err_out) memcpy(err_out, s->pin + o.er, b_er);
     }
   } else if (rc == GMR_OK) {
-    if ((e = hipMemcpyAsync(q_out, d + o_qo, b_qo, hipMemcpyDeviceToHost, nullptr)) != hipSuccess ||
-        (e = hipMemcpyAsync(nsolve, d + o_ns, b_ns, hipMemcpyDeviceToHost, nullptr)) != hipSuccess ||
-        (e = hipMemcpyAsync(status, d + o_st, b_st, hipMemcpyDeviceToHost, nullptr)) != hipSuccess ||
-        (tgt_out && (e = hipMemcpyAsync(tgt_out, d + o_tg, b_tg, hipMemcpyDeviceToHost, nullptr)) != hipSuccess) ||
-        (err_out && (e = hipMemcpyAsync(err_out, d + o_er, b_er, hipMemcpyDeviceToHost, nullptr)) != hipSuccess) ||
+    if ((e = hipMemcpyAsync(q_out, d + o.qo, b_qo, hipMemcpyDeviceToHost, nullptr)) != hipSuccess ||
+        (e = hipMemcpyAsync(nsolve, d + o.ns, b_ns, hipMemcpyDeviceToHost, nullptr)) != hipSuccess ||
+        (e = hipMemcpyAsync(status, d + o.st, b_st, hipMemcpyDeviceToHost, nullptr)) != hipSuccess ||
+        (tgt_out && (e = hipMemcpyAsync(tgt_out, d + o.tg, b_tg, hipMemcpyDeviceToHost, nullptr)) != hipSuccess) ||
+        (err_out && (e = hipMemcpyAsync(err_out, d + o.er, b_er, hipMemcpyDeviceToHost, nullptr)) != hipSuccess) ||
         (e = hipStreamSynchronize(nullptr)) != hipSuccess)
       rc = fail(GMR_ERR_HIP, "kernel / D2H copy: %s", hipGetErrorString(e));
   }
@@ -842,9 +794,8 @@ int gmr_fk_create(int nbody, const int32_t* parent, const float* local_t, const 
     if (why) { delete k; return fail(GMR_ERR_ARG, "split walk: %s", why); }
   }
   hipError_t e;
-  if ((e = hipMalloc((void**)&k->d_tree, sizeof(gmr::FkTree))) != hipSuccess ||
-      (e = hipMemcpy(k->d_tree, &k->tree, sizeof(gmr::FkTree), hipMemcpyHostToDevice)) != hipSuccess) {
-    if (k->d_tree) (void)hipFree(k->d_tree);
+  if ((e = k->d_tree.reserve(sizeof(gmr::FkTree))) != hipSuccess ||
+      (e = hipMemcpy(k->d_tree.data(), &k->tree, sizeof(gmr::FkTree), hipMemcpyHostToDevice)) != hipSuccess) {
     delete k;
     return fail(GMR_ERR_HIP, "gmr_fk_create: %s", hipGetErrorString(e));
   }
@@ -853,12 +804,7 @@ int gmr_fk_create(int nbody, const int32_t* parent, const float* local_t, const 
 }
 
 int gmr_fk_destroy(gmr_fk_t* k) {
-  if (!k) return GMR_OK;
-  (void)hipFree(k->d_tree);
-  if (k->d_min_part) (void)hipFree(k->d_min_part);
-  for (auto& w : k->post_ws)
-    if (w.d) (void)hipFree(w.d);          // (hipFree waits for the device: nothing of this handle is in flight afterwards)
-  delete k;
+  delete k;                                // (freeing its blocks waits for the device: nothing of the handle is in flight afterwards)
   return GMR_OK;
 }
 
@@ -868,17 +814,11 @@ int gmr_fk_batch_dev(gmr_fk_t* k, int B, const float* d_root_pos, const float* d
   if (B < 0) return fail(GMR_ERR_ARG, "negative B");
   if (B == 0) return GMR_OK;
   if (!d_root_pos || !d_root_rot || !d_body_pos || (k->tree.ndof > 0 && !d_dof)) return fail(GMR_ERR_ARG, "null device buffer");
-  if (d_min_z) {
-    int blocks = gmr_fk_blocks(B);
-    if (blocks > k->min_part_cap) {  // grows only; not graph-capturable on the first call of a size
-      if (k->d_min_part) (void)hipFree(k->d_min_part);
-      k->d_min_part = nullptr;
-      HIP_TRY(hipMalloc((void**)&k->d_min_part, (size_t)blocks * sizeof(float)));
-      k->min_part_cap = blocks;
-    }
-  }
-  HIP_TRY(gmr_launch_fk_batch(k->d_tree, &k->tree, B, d_root_pos, d_root_rot, d_dof, d_body_pos,
-                              d_body_rot, k->d_min_part, d_min_z, (hipStream_t)stream));
+  // grows only; not graph-capturable on the first call of a size.  Earlier launches on any stream may still read the old
+  // block: freeing it waits for the device.
+  if (d_min_z) GMR_HIP_TRY(k->min_part.reserve((size_t)gmr_fk_blocks(B) * sizeof(float)));
+  GMR_HIP_TRY(gmr_launch_fk_batch(k->dev(), &k->tree, B, d_root_pos, d_root_rot, d_dof, d_body_pos,
+                              d_body_rot, (float*)k->min_part.data(), d_min_z, (hipStream_t)stream));
   return GMR_OK;
 }
 
@@ -889,13 +829,13 @@ int gmr_fk_batch(gmr_fk_t* k, int B, const float* root_pos, const float* root_ro
   if (B == 0) return GMR_OK;
   if (!root_pos || !root_rot || !body_pos) return fail(GMR_ERR_ARG, "null host buffer");
   const size_t nb = k->tree.nbody, nd = k->tree.ndof;
-  auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-  size_t b_rp = (size_t)B * 12, b_rr = (size_t)B * 16, b_d = (size_t)B * nd * 4, b_bp = (size_t)B * nb * 12,
-         b_br = (size_t)B * nb * 16;
-  size_t o_rp = 0, o_rr = o_rp + up(b_rp), o_d = o_rr + up(b_rr), o_bp = o_d + up(b_d), o_br = o_bp + up(b_bp),
-         o_mz = o_br + up(b_br), total = o_mz + 256;
-  char* d = nullptr;
-  HIP_TRY(hipMalloc((void**)&d, total));
+  const size_t b_rp = (size_t)B * 12, b_rr = (size_t)B * 16, b_d = (size_t)B * nd * 4, b_bp = (size_t)B * nb * 12,
+               b_br = (size_t)B * nb * 16;
+  gmr::Carve c;
+  const size_t o_rp = c.take(b_rp), o_rr = c.take(b_rr), o_d = c.take(b_d), o_bp = c.take(b_bp), o_br = c.take(b_br), o_mz = c.take(4);
+  gmr::DeviceBlock blk;                  // scratch of this call
+  GMR_HIP_TRY(blk.reserve(c.total()));
+  char* d = blk.data();
   int rc = GMR_OK;
   hipError_t e;
   if ((e = hipMemcpy(d + o_rp, root_pos, b_rp, hipMemcpyHostToDevice)) != hipSuccess ||
@@ -912,7 +852,6 @@ int gmr_fk_batch(gmr_fk_t* k, int B, const float* root_pos, const float* root_ro
         (min_z && (e = hipMemcpy(min_z, d + o_mz, 4, hipMemcpyDeviceToHost)) != hipSuccess))
       rc = fail(GMR_ERR_HIP, "kernel / D2H copy: %s", hipGetErrorString(e));
   }
-  (void)hipFree(d);
   return rc;
 }
 
@@ -922,7 +861,7 @@ int gmr_fk_segment_min_z_dev(gmr_fk_t* k, const float* d_body_pos, const int32_t
   if (nseg < 0) return fail(GMR_ERR_ARG, "negative nseg");
   if (nseg == 0) return GMR_OK;
   if (!d_body_pos || !d_seg_start || !d_seg_min) return fail(GMR_ERR_ARG, "null device buffer");
-  HIP_TRY(gmr_launch_fk_segment_min(d_body_pos, k->tree.nbody, d_seg_start, nseg, d_seg_min, (hipStream_t)stream));
+  GMR_HIP_TRY(gmr_launch_fk_segment_min(d_body_pos, k->tree.nbody, d_seg_start, nseg, d_seg_min, (hipStream_t)stream));
   return GMR_OK;
 }
 
@@ -937,13 +876,13 @@ int gmr_fk_batch_segments(gmr_fk_t* k, int B, const float* root_pos, const float
   for (int g = 0; g < nseg; g++)
     if (seg_start[g] < 0 || seg_start[g] > seg_start[g + 1] || seg_start[g + 1] > B) return fail(GMR_ERR_ARG, "seg_start must ascend within [0, B]");
   const size_t nb = k->tree.nbody, nd = k->tree.ndof;
-  auto up = [](size_t x) { return (x + 255) / 256 * 256; };
   const size_t b_rp = (size_t)B * 12, b_rr = (size_t)B * 16, b_d = (size_t)B * nd * 4, b_bp = (size_t)B * nb * 12,
                b_ss = (size_t)(nseg + 1) * 4, b_sm = (size_t)nseg * 4;
-  const size_t o_rp = 0, o_rr = o_rp + up(b_rp), o_d = o_rr + up(b_rr), o_bp = o_d + up(b_d), o_ss = o_bp + up(b_bp),
-               o_sm = o_ss + up(b_ss), total = o_sm + up(b_sm) + 256;
-  char* d = nullptr;
-  HIP_TRY(hipMalloc((void**)&d, total));
+  gmr::Carve c;
+  const size_t o_rp = c.take(b_rp), o_rr = c.take(b_rr), o_d = c.take(b_d), o_bp = c.take(b_bp), o_ss = c.take(b_ss), o_sm = c.take(b_sm);
+  gmr::DeviceBlock blk;                  // scratch of this call
+  GMR_HIP_TRY(blk.reserve(c.total() + 256));
+  char* d = blk.data();
   int rc = GMR_OK;
   hipError_t e;
   if ((e = hipMemcpy(d + o_rp, root_pos, b_rp, hipMemcpyHostToDevice)) != hipSuccess ||
@@ -961,7 +900,6 @@ int gmr_fk_batch_segments(gmr_fk_t* k, int B, const float* root_pos, const float
         (nseg && (e = hipMemcpy(seg_min_z, d + o_sm, b_sm, hipMemcpyDeviceToHost)) != hipSuccess))
       rc = fail(GMR_ERR_HIP, "kernel / D2H copy: %s", hipGetErrorString(e));
   }
-  (void)hipFree(d);
   return rc;
 }
 
@@ -999,41 +937,24 @@ int gmr_postprocess_clips_dev(gmr_fk_t* k, const gmr_post_src_t* src, int nsrc, 
   if (B == 0 && !(height && d_lowest)) return GMR_OK;
   // scratch: row_q [B] pointers, row_clip [B], seg_clamped [C + 1], lowest [C] (when the caller does not want it), and the
   // world pass's body_pos [B][nbody][3]
-  auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-  const size_t o_rq = 0, o_rc = o_rq + up((size_t)B * 8), o_sc = o_rc + up((size_t)B * 4), o_lo = o_sc + up((size_t)(C + 1) * 4),
-               o_bp = o_lo + up((size_t)C * 4), total = o_bp + (height ? up((size_t)B * k->tree.nbody * 12) : 0);
+  gmr::Carve c;
+  const size_t o_rq = c.take((size_t)B * 8), o_rc = c.take((size_t)B * 4), o_sc = c.take((size_t)(C + 1) * 4), o_lo = c.take((size_t)C * 4),
+               o_bp = c.take(height ? (size_t)B * k->tree.nbody * 12 : 0);
   hipStream_t st = (hipStream_t)stream;
-  std::lock_guard<std::mutex> lock(k->post_mu);
-  gmr_fk::PostWs* w = nullptr;
-  for (auto& e : k->post_ws)
-    if (e.stream == st) w = &e;
-  if (!w) {
-    k->post_ws.push_back(gmr_fk::PostWs{st, nullptr, 0});
-    w = &k->post_ws.back();
-  }
-  if (w->bytes < total) {
-    if (w->d) {
-      HIP_TRY(hipStreamSynchronize(st));      // earlier calls on this stream are the only users of the block
-      HIP_TRY(hipFree(w->d));
-      w->d = nullptr;
-      w->bytes = 0;
-    }
-    const size_t want = total + total / 4;
-    HIP_TRY(hipMalloc((void**)&w->d, want));
-    w->bytes = want;
-  }
-  char* d = w->d;
+  const auto ws = k->post_ws.acquire(st, c.total());           // (held until the last launch below is enqueued)
+  GMR_NAMED_HIP_TRY("gmr_postprocess_clips_dev: scratch", ws.error());
+  char* d = ws.base();
   const double** row_q = (const double**)(d + o_rq);
   int32_t* row_clip = (int32_t*)(d + o_rc);
   int32_t* seg_clamped = (int32_t*)(d + o_sc);
   float* lowest = d_lowest ? d_lowest : (float*)(d + o_lo);
-  HIP_TRY(gmr_launch_post_row_map(&ps, d_seg_start, C, B, nq, row_q, row_clip, seg_clamped, st));
+  GMR_HIP_TRY(gmr_launch_post_row_map(&ps, d_seg_start, C, B, nq, row_q, row_clip, seg_clamped, st));
   if (height) {
-    HIP_TRY(gmr_launch_fk_qpos(k->d_tree, &k->tree, B, row_q, 1, (float*)(d + o_bp), st));
-    HIP_TRY(gmr_launch_fk_segment_min((const float*)(d + o_bp), k->tree.nbody, seg_clamped, C, lowest, st));
+    GMR_HIP_TRY(gmr_launch_fk_qpos(k->dev(), &k->tree, B, row_q, 1, (float*)(d + o_bp), st));
+    GMR_HIP_TRY(gmr_launch_fk_segment_min((const float*)(d + o_bp), k->tree.nbody, seg_clamped, C, lowest, st));
   }
-  HIP_TRY(gmr_launch_fk_qpos(k->d_tree, &k->tree, B, row_q, 0, d_local_body_pos, st));
-  HIP_TRY(gmr_launch_post_gather(row_q, row_clip, seg_clamped, lowest, B, nq, flags, ground_offset, d_root_pos, d_root_rot, d_dof_pos, st));
+  GMR_HIP_TRY(gmr_launch_fk_qpos(k->dev(), &k->tree, B, row_q, 0, d_local_body_pos, st));
+  GMR_HIP_TRY(gmr_launch_post_gather(row_q, row_clip, seg_clamped, lowest, B, nq, flags, ground_offset, d_root_pos, d_root_rot, d_dof_pos, st));
   return GMR_OK;
 }
 

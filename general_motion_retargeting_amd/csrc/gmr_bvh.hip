@@ -24,12 +24,12 @@
 #include <string.h>
 
 #include <algorithm>
-#include <mutex>
 #include <new>
 #include <vector>
 
 #include "../../include/gmr_hip.h"
 #include "gmr_internal.h"
+#include "gmr_workspace.h"
 
 // float64 arithmetic here mirrors NumPy's (one rounding per operation)
 #pragma clang fp contract(off)
@@ -257,19 +257,10 @@ __global__ __launch_bounds__(BVH_BLOCK) void bvh_frames_kernel(const BvhProg P, 
 struct gmr_bvh {
   gmr::BvhProg prog;
   size_t lds_bytes = 0;
-  // gmr_bvh_frames_dev: one grow-only scratch block per HIP stream that has called (like gmr_fk's post-processing scratch:
-  // growing a block waits for its own stream alone; mu orders the host side)
-  struct Ws {
-    hipStream_t stream;
-    char* d;
-    size_t bytes;
-  };
-  std::mutex mu;
-  std::vector<Ws> ws;
+  gmr::StreamWorkspace ws;       // gmr_bvh_frames_dev
   // gmr_bvh_frames: device staging of the host buffers, grown on demand and kept
   std::mutex host_mu;
-  char* host_ws = nullptr;
-  size_t host_ws_bytes = 0;
+  gmr::DeviceBlock host_ws;
 };
 
 extern "C" {
@@ -365,11 +356,7 @@ int gmr_bvh_create(int J, const int32_t* parents, int channels, const char* orde
 }
 
 int gmr_bvh_destroy(gmr_bvh_t* h) {
-  if (!h) return GMR_OK;
-  for (auto& w : h->ws)
-    if (w.d) (void)hipFree(w.d);          // (hipFree waits for the device: nothing of this handle is in flight afterwards)
-  if (h->host_ws) (void)hipFree(h->host_ws);
-  delete h;
+  delete h;                                // (freeing its blocks waits for the device: nothing of the handle is in flight afterwards)
   return GMR_OK;
 }
 
@@ -384,32 +371,13 @@ int gmr_bvh_frames_dev(gmr_bvh_t* h, int nclip, int B, const double* d_rows, con
   if (!d_rows || !d_seg_start || !d_offsets || !d_human) return gmr_fail(GMR_ERR_ARG, "gmr_bvh_frames_dev: null buffer");
   const int nblk = (B + BVH_SCAN_ROWS - 1) / BVH_SCAN_ROWS;
   // scratch: row_pref [B] u64, blk_tail [nblk] u64, carry [nblk] u64, row_clip [B] i32, seg_clamped [nclip + 1] i32
-  auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-  const size_t o_rp = 0, o_bt = o_rp + up((size_t)B * 8), o_ca = o_bt + up((size_t)nblk * 8), o_rc = o_ca + up((size_t)nblk * 8),
-               o_sc = o_rc + up((size_t)B * 4), total = o_sc + up((size_t)(nclip + 1) * 4);
+  gmr::Carve c;
+  const size_t o_rp = c.take((size_t)B * 8), o_bt = c.take((size_t)nblk * 8), o_ca = c.take((size_t)nblk * 8), o_rc = c.take((size_t)B * 4),
+               o_sc = c.take((size_t)(nclip + 1) * 4);
   hipStream_t st = (hipStream_t)stream;
-  std::lock_guard<std::mutex> lock(h->mu);
-  gmr_bvh::Ws* w = nullptr;
-  for (auto& e : h->ws)
-    if (e.stream == st) w = &e;
-  if (!w) {
-    h->ws.push_back(gmr_bvh::Ws{st, nullptr, 0});
-    w = &h->ws.back();
-  }
-  if (w->bytes < total) {
-    if (w->d) {
-      hipError_t e = hipStreamSynchronize(st);       // earlier calls on this stream are the only users of the block
-      if (e == hipSuccess) e = hipFree(w->d);
-      if (e != hipSuccess) return gmr_fail(GMR_ERR_HIP, "gmr_bvh_frames_dev: %s", hipGetErrorString(e));
-      w->d = nullptr;
-      w->bytes = 0;
-    }
-    const size_t want = total + total / 4;
-    hipError_t e = hipMalloc((void**)&w->d, want);
-    if (e != hipSuccess) return gmr_fail(GMR_ERR_HIP, "gmr_bvh_frames_dev: %s", hipGetErrorString(e));
-    w->bytes = want;
-  }
-  char* d = w->d;
+  const auto ws = h->ws.acquire(st, c.total());                // (held until the last launch below is enqueued)
+  GMR_NAMED_HIP_TRY("gmr_bvh_frames_dev", ws.error());
+  char* d = ws.base();
   unsigned long long* row_pref = (unsigned long long*)(d + o_rp);
   unsigned long long* blk_tail = (unsigned long long*)(d + o_bt);
   unsigned long long* carry = (unsigned long long*)(d + o_ca);
@@ -422,8 +390,7 @@ int gmr_bvh_frames_dev(gmr_bvh_t* h, int nclip, int B, const double* d_rows, con
     hipLaunchKernelGGL(gmr::bvh_carry_kernel, dim3((nclip + 255) / 256), dim3(256), 0, st, seg_clamped, nclip, nblk, blk_tail, carry);
   hipLaunchKernelGGL(gmr::bvh_frames_kernel, dim3((B + BVH_BLOCK - 1) / BVH_BLOCK), dim3(BVH_BLOCK), h->lds_bytes, st, h->prog, d_rows,
                      seg_clamped, d_offsets, nclip, B, T, row_pref, row_clip, carry, d_human);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return gmr_fail(GMR_ERR_HIP, "gmr_bvh_frames_dev: %s", hipGetErrorString(e));
+  GMR_NAMED_HIP_TRY("gmr_bvh_frames_dev", hipGetLastError());
   return GMR_OK;
 }
 
@@ -439,22 +406,15 @@ int gmr_bvh_frames(gmr_bvh_t* h, int nclip, int B, const double* rows, const int
     if (n < 0 || n > T) return gmr_fail(GMR_ERR_ARG, "gmr_bvh_frames: clip %d has %lld frames (0 .. T = %d)", c, n, T);
   }
   const gmr::BvhProg& P = h->prog;
-  auto up = [](size_t x) { return (x + 255) / 256 * 256; };
   const size_t nb_rows = (size_t)B * P.ncol * 8, nb_seg = (size_t)(nclip + 1) * 4, nb_off = (size_t)nclip * P.J * 3 * 8,
                nb_out = (size_t)nclip * T * P.nrow * 7 * 8;
-  const size_t o_rows = 0, o_seg = o_rows + up(nb_rows), o_off = o_seg + up(nb_seg), o_out = o_off + up(nb_off), total = o_out + up(nb_out);
+  gmr::Carve c;
+  const size_t o_rows = c.take(nb_rows), o_seg = c.take(nb_seg), o_off = c.take(nb_off), o_out = c.take(nb_out);
   if (nb_out == 0) return GMR_OK;
   std::lock_guard<std::mutex> guard(h->host_mu);
+  GMR_NAMED_HIP_TRY("gmr_bvh_frames", h->host_ws.reserve(c.total(), 4));
+  char* d = h->host_ws.data();
   hipError_t e = hipSuccess;
-  if (h->host_ws_bytes < total) {
-    if (h->host_ws) (void)hipFree(h->host_ws);
-    h->host_ws = nullptr;
-    h->host_ws_bytes = 0;
-    const size_t want = total + total / 4;
-    if ((e = hipMalloc((void**)&h->host_ws, want)) != hipSuccess) return gmr_fail(GMR_ERR_HIP, "gmr_bvh_frames: %s", hipGetErrorString(e));
-    h->host_ws_bytes = want;
-  }
-  char* d = h->host_ws;
   // rows at or beyond a clip's length come back as zeros (the kernels do not write them)
   if ((e = hipMemset(d + o_out, 0, nb_out)) != hipSuccess ||
       (nb_rows && (e = hipMemcpy(d + o_rows, rows, nb_rows, hipMemcpyHostToDevice)) != hipSuccess) ||

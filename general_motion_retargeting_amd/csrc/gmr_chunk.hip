@@ -287,12 +287,6 @@ __global__ __launch_bounds__(1024) void chunk_scan_kernel(int S, int T, int nchu
 }  // namespace gmr
 
 namespace {
-#define HIP_TRY(call)                                                                            \
-  do {                                                                                           \
-    hipError_t _e = (call);                                                                      \
-    if (_e != hipSuccess) return gmr_fail(GMR_ERR_HIP, "%s: %s", #call, hipGetErrorString(_e)); \
-  } while (0)
-
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 inline bool aligned8(const void* p) { return ((uintptr_t)p & 7) == 0; }
 
@@ -363,7 +357,7 @@ int gmr_chunk_gather_dev(int S, int T, int nhuman, int nq, int nchunk, int Tc, c
   else
     hipLaunchKernelGGL(gmr::chunk_gather_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, S, T, fd, nq, nchunk, Tc, d_chunk, d_list, mode,
                        d_human, d_q0, d_q_out, d_human_c, d_len_c, d_q0_c, d_q_seam);
-  HIP_TRY(hipGetLastError());
+  GMR_HIP_TRY(hipGetLastError());
   return GMR_OK;
 }
 
@@ -393,11 +387,11 @@ int gmr_chunk_stitch_dev(int S, int T, int nq, int nchunk, int Tc, const int32_t
     else
       hipLaunchKernelGGL(gmr::chunk_stitch_kernel<1>, grid, dim3(256), 0, st, S, T, nq, nchunk, Tc, (int)tiles_q, d_chunk, d_list, mode,
                          d_q_out_c, d_nsolve_c, d_status_c, d_q_out, d_nsolve, d_chunk_status, d_q_seam);
-    HIP_TRY(hipGetLastError());
+    GMR_HIP_TRY(hipGetLastError());
   }
   hipLaunchKernelGGL(gmr::chunk_finalize_kernel, dim3((S + 3) / 4), dim3(256), 0, st, S, T, nchunk, Tc, d_chunk, d_clip_first, d_chunk_status,
                      mode == GMR_CHUNK_PASS0 ? d_nsolve_c : (const int32_t*)nullptr, d_status, d_warm_solves);
-  HIP_TRY(hipGetLastError());
+  GMR_HIP_TRY(hipGetLastError());
   return GMR_OK;
 }
 
@@ -409,17 +403,17 @@ int gmr_chunk_seams_dev(int S, int T, int nq, int nchunk, int Tc, const int32_t*
   if (!d_nbad) return gmr_fail(GMR_ERR_ARG, "gmr_chunk_seams_dev: null count");
   hipStream_t st = (hipStream_t)stream;
   if (S == 0 || nchunk == 0) {
-    HIP_TRY(hipMemsetAsync(d_nbad, 0, 4, st));
+    GMR_HIP_TRY(hipMemsetAsync(d_nbad, 0, 4, st));
     return GMR_OK;
   }
   if (!d_chunk || !d_clip_first || !d_q_out || !d_q_seam || !d_chunk_status || !d_resid || !d_bad_list || !d_seam_max)
     return gmr_fail(GMR_ERR_ARG, "gmr_chunk_seams_dev: null buffer");
   hipLaunchKernelGGL(gmr::chunk_resid_kernel, dim3((nchunk + 255) / 256), dim3(256), 0, st, S, T, nq, nchunk, Tc, d_chunk, d_clip_first,
                      d_q_out, d_q_seam, d_resid);
-  HIP_TRY(hipGetLastError());
+  GMR_HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(gmr::chunk_scan_kernel, dim3(1 + (S + 1023) / 1024), dim3(1024), 0, st, S, T, nchunk, Tc, d_chunk, d_clip_first,
                      d_chunk_status, d_resid, tol, d_bad_list, d_nbad, d_seam_max);
-  HIP_TRY(hipGetLastError());
+  GMR_HIP_TRY(hipGetLastError());
   return GMR_OK;
 }
 

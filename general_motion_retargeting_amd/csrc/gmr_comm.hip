@@ -30,6 +30,7 @@
 
 #include "../../include/gmr_hip.h"
 #include "gmr_internal.h"
+#include "gmr_workspace.h"
 
 namespace {
 
@@ -107,11 +108,6 @@ int recv_all(int fd, void* buf, size_t n) {
     ncclResult_t _r = (call);                                                                                \
     if (_r != ncclSuccess) return gmr_fail(GMR_ERR_COMM, "%s: %s", #call, g_rccl.GetErrorString(_r));        \
   } while (0)
-#define HIPC_TRY(call)                                                                                       \
-  do {                                                                                                       \
-    hipError_t _e = (call);                                                                                  \
-    if (_e != hipSuccess) return gmr_fail(GMR_ERR_HIP, "%s: %s", #call, hipGetErrorString(_e));              \
-  } while (0)
 
 }  // namespace
 
@@ -122,8 +118,7 @@ struct gmr_comm {
   int rank = 0, world = 1;
   int backend = BACKEND_RCCL;
   hipStream_t stream = nullptr;
-  void* d_scratch = nullptr;     // small device staging for the host-buffer conveniences
-  size_t scratch_bytes = 0;
+  gmr::DeviceBlock scratch;      // small device staging for the host-buffer conveniences (grown to the exact size asked)
   // control star: rank 0 holds one socket per peer (index = rank), a peer holds its socket to rank 0
   int* fds = nullptr;
   int fd0 = -1;
@@ -400,7 +395,7 @@ int gmr_comm_create(int rank, int world, const char* master_addr, int port, gmr_
     if (!ok) { c->comm = nullptr; snprintf(why, sizeof why, "ncclCommInitRank: %s", g_rccl.GetErrorString(r)); }
     if (ok) {
       hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-      if (e == hipSuccess) { c->scratch_bytes = 1 << 16; e = hipMalloc(&c->d_scratch, c->scratch_bytes); }
+      if (e == hipSuccess) e = c->scratch.reserve(1 << 16);
       if (e != hipSuccess) { ok = false; snprintf(why, sizeof why, "gmr_comm_create: %s", hipGetErrorString(e)); }
     }
     rc = star_agree(c, ok, why, &v);
@@ -427,7 +422,6 @@ int gmr_comm_create(int rank, int world, const char* master_addr, int port, gmr_
   char msg[256];
   if (rc == GMR_OK) snprintf(msg, sizeof msg, "RCCL bring-up failed on rank %d: %.200s", v.rank, v.msg);
   else snprintf(msg, sizeof msg, "%.250s", gmr_last_error());
-  if (c->d_scratch) (void)hipFree(c->d_scratch);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   star_close(c);
   delete c;
@@ -438,7 +432,6 @@ int gmr_comm_destroy(gmr_comm_t* c) {
   if (!c) return GMR_OK;
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->comm) (void)g_rccl.CommDestroy(c->comm);
-  if (c->d_scratch) (void)hipFree(c->d_scratch);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   star_close(c);
   delete c;
@@ -457,15 +450,6 @@ int gmr_comm_broadcast_dev(gmr_comm_t* c, void* d_buf, size_t bytes, int root, v
   return GMR_OK;
 }
 
-static int need_scratch(gmr_comm* c, size_t bytes) {
-  if (bytes <= c->scratch_bytes) return GMR_OK;
-  if (c->d_scratch) (void)hipFree(c->d_scratch);
-  c->d_scratch = nullptr; c->scratch_bytes = 0;
-  HIPC_TRY(hipMalloc(&c->d_scratch, bytes));
-  c->scratch_bytes = bytes;
-  return GMR_OK;
-}
-
 // gmr_broadcast_model of SURVEY.md section 8(b): host bytes (the packed gmr_model_t + gmr_taskset_t, 24 KB) of rank
 // `root` to the same host buffer on every rank: H2D, RCCL broadcast over xGMI, D2H, synchronised.
 int gmr_comm_broadcast(gmr_comm_t* c, void* buf, size_t bytes, int root) {
@@ -480,12 +464,12 @@ int gmr_comm_broadcast(gmr_comm_t* c, void* buf, size_t bytes, int root) {
     }
     return star_scatter_same(c, buf, bytes);
   }
-  int rc = need_scratch(c, bytes);
-  if (rc) return rc;
-  if (c->rank == root) HIPC_TRY(hipMemcpyAsync(c->d_scratch, buf, bytes, hipMemcpyHostToDevice, c->stream));
-  NCCL_TRY(g_rccl.Broadcast(c->d_scratch, c->d_scratch, bytes, ncclUint8, root, c->comm, c->stream));
-  HIPC_TRY(hipMemcpyAsync(buf, c->d_scratch, bytes, hipMemcpyDeviceToHost, c->stream));
-  HIPC_TRY(hipStreamSynchronize(c->stream));
+  GMR_HIP_TRY(c->scratch.reserve(bytes));
+  char* d = c->scratch.data();
+  if (c->rank == root) GMR_HIP_TRY(hipMemcpyAsync(d, buf, bytes, hipMemcpyHostToDevice, c->stream));
+  NCCL_TRY(g_rccl.Broadcast(d, d, bytes, ncclUint8, root, c->comm, c->stream));
+  GMR_HIP_TRY(hipMemcpyAsync(buf, d, bytes, hipMemcpyDeviceToHost, c->stream));
+  GMR_HIP_TRY(hipStreamSynchronize(c->stream));
   return GMR_OK;
 }
 
@@ -494,12 +478,12 @@ static int allreduce_f64(gmr_comm* c, double* inout, int n, ncclRedOp_t op) {
   if (!c || !inout || n < 0) return gmr_fail(GMR_ERR_ARG, "null comm / buffer");
   if (n == 0) return GMR_OK;
   if (c->backend == BACKEND_TCP) return tcp_allreduce(c, inout, n, op == ncclMax ? 0 : 1);
-  int rc = need_scratch(c, (size_t)n * 8);
-  if (rc) return rc;
-  HIPC_TRY(hipMemcpyAsync(c->d_scratch, inout, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-  NCCL_TRY(g_rccl.AllReduce(c->d_scratch, c->d_scratch, (size_t)n, ncclFloat64, op, c->comm, c->stream));
-  HIPC_TRY(hipMemcpyAsync(inout, c->d_scratch, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPC_TRY(hipStreamSynchronize(c->stream));
+  GMR_HIP_TRY(c->scratch.reserve((size_t)n * 8));
+  char* d = c->scratch.data();
+  GMR_HIP_TRY(hipMemcpyAsync(d, inout, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+  NCCL_TRY(g_rccl.AllReduce(d, d, (size_t)n, ncclFloat64, op, c->comm, c->stream));
+  GMR_HIP_TRY(hipMemcpyAsync(inout, d, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+  GMR_HIP_TRY(hipStreamSynchronize(c->stream));
   return GMR_OK;
 }
 int gmr_comm_allreduce_max(gmr_comm_t* c, double* inout, int n) { return allreduce_f64(c, inout, n, ncclMax); }
@@ -516,20 +500,19 @@ int gmr_comm_allgather(gmr_comm_t* c, const double* in, double* out, int n) {
     if (rc) return rc;
     return star_scatter_same(c, out, one * (size_t)c->world);
   }
-  int rc = need_scratch(c, one * (size_t)(c->world + 1));
-  if (rc) return rc;
-  char* d = (char*)c->d_scratch;
-  HIPC_TRY(hipMemcpyAsync(d, in, one, hipMemcpyHostToDevice, c->stream));
+  GMR_HIP_TRY(c->scratch.reserve(one * (size_t)(c->world + 1)));
+  char* d = c->scratch.data();
+  GMR_HIP_TRY(hipMemcpyAsync(d, in, one, hipMemcpyHostToDevice, c->stream));
   NCCL_TRY(g_rccl.AllGather(d, d + one, (size_t)n, ncclFloat64, c->comm, c->stream));
-  HIPC_TRY(hipMemcpyAsync(out, d + one, one * (size_t)c->world, hipMemcpyDeviceToHost, c->stream));
-  HIPC_TRY(hipStreamSynchronize(c->stream));
+  GMR_HIP_TRY(hipMemcpyAsync(out, d + one, one * (size_t)c->world, hipMemcpyDeviceToHost, c->stream));
+  GMR_HIP_TRY(hipStreamSynchronize(c->stream));
   return GMR_OK;
 }
 
 // all ranks have reached this point and their device work is complete
 int gmr_comm_barrier(gmr_comm_t* c) {
   if (!c) return gmr_fail(GMR_ERR_ARG, "null comm");
-  if (c->has_device) HIPC_TRY(hipDeviceSynchronize());
+  if (c->has_device) GMR_HIP_TRY(hipDeviceSynchronize());
   double one = 1.0;
   int rc = allreduce_f64(c, &one, 1, ncclSum);
   if (rc) return rc;

@@ -18,11 +18,11 @@
 
 #include <cmath>
 #include <new>
-#include <vector>
 
 #include "../../include/gmr_hip.h"
 #include "gmr_device_math.h"
 #include "gmr_internal.h"
+#include "gmr_workspace.h"
 
 // float32 arithmetic here mirrors NumPy's / torch's (one rounding per operation: a multiply and an add stay two)
 #pragma clang fp contract(off)
@@ -322,33 +322,13 @@ __global__ __launch_bounds__(256) void motion_sample_kernel(const MotionArrays A
 
 // ---- C-ABI (include/gmr_hip.h, "motion library") ---------------------------------------------------------------------------
 
-#define HIP_TRY(call)                                                                             \
-  do {                                                                                            \
-    hipError_t _e = (call);                                                                       \
-    if (_e != hipSuccess) return gmr_fail(GMR_ERR_HIP, "%s: %s", #call, hipGetErrorString(_e));   \
-  } while (0)
-
 struct gmr_motion_lib {
   gmr::MotionArrays A;
-  char* d_block = nullptr;       // every array of the library: one allocation
+  gmr::DeviceBlock block;        // every array of the library: one allocation
   size_t off[GMR_MOTION_FPS + 1], bytes[GMR_MOTION_FPS + 1];
   int filled = 0;                // 1 once a fill has been enqueued
   int has_body = 0;              // the fill was given local_body_pos
 };
-
-namespace {
-
-struct DevTmp {                  // device scratch of one host-pointer call
-  std::vector<void*> p;
-  ~DevTmp() { for (void* q : p) (void)hipFree(q); }
-  hipError_t take(void** out, size_t bytes) {
-    hipError_t e = hipMalloc(out, bytes ? bytes : 8);
-    if (e == hipSuccess) p.push_back(*out);
-    return e;
-  }
-};
-
-}  // namespace
 
 extern "C" {
 
@@ -370,21 +350,20 @@ int gmr_motion_lib_create(int C, int B, int ndof, int nbody, const int32_t* seg_
   const size_t b = (size_t)B, ncol = 3 + (size_t)ndof;
   const size_t want[GMR_MOTION_FPS + 1] = {b * 12, b * 16, b * ndof * 4, b * nbody * 12, b * 12, b * 12, b * ndof * 4,
                                            (size_t)C * gmr::MOTION_STAT_ROWS * ncol * 4, ((size_t)C + 1) * 4, (size_t)C * 8};
-  size_t total = 0;
+  gmr::Carve c;
   for (int k = 0; k <= GMR_MOTION_FPS; k++) {
-    lib->off[k] = total;
+    lib->off[k] = c.take(want[k]);
     lib->bytes[k] = want[k];
-    total += (want[k] + 255) / 256 * 256;
   }
-  hipError_t e = hipMalloc((void**)&lib->d_block, total);
-  if (e == hipSuccess) e = hipMemcpy(lib->d_block + lib->off[GMR_MOTION_SEG_START], seg_start, want[GMR_MOTION_SEG_START], hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(lib->d_block + lib->off[GMR_MOTION_FPS], fps, want[GMR_MOTION_FPS], hipMemcpyHostToDevice);
+  hipError_t e = lib->block.reserve(c.total());
+  char* d_block = lib->block.data();
+  if (e == hipSuccess) e = hipMemcpy(d_block + lib->off[GMR_MOTION_SEG_START], seg_start, want[GMR_MOTION_SEG_START], hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_block + lib->off[GMR_MOTION_FPS], fps, want[GMR_MOTION_FPS], hipMemcpyHostToDevice);
   if (e != hipSuccess) {
-    if (lib->d_block) (void)hipFree(lib->d_block);
     delete lib;
     return gmr_fail(GMR_ERR_HIP, "gmr_motion_lib_create: %s", hipGetErrorString(e));
   }
-  auto at = [&](int k) { return (float*)(lib->d_block + lib->off[k]); };
+  auto at = [&](int k) { return (float*)(d_block + lib->off[k]); };
   lib->A = gmr::MotionArrays{C, B, ndof, nbody, (const int32_t*)at(GMR_MOTION_SEG_START), (const double*)at(GMR_MOTION_FPS),
                              at(GMR_MOTION_ROOT_POS), at(GMR_MOTION_ROOT_ROT), at(GMR_MOTION_DOF_POS), at(GMR_MOTION_LOCAL_BODY_POS),
                              at(GMR_MOTION_ROOT_VEL), at(GMR_MOTION_ROOT_ANG_VEL), at(GMR_MOTION_DOF_VEL), at(GMR_MOTION_STATS)};
@@ -393,8 +372,6 @@ int gmr_motion_lib_create(int C, int B, int ndof, int nbody, const int32_t* seg_
 }
 
 int gmr_motion_lib_destroy(gmr_motion_lib_t* lib) {
-  if (!lib) return GMR_OK;
-  if (lib->d_block) HIP_TRY(hipFree(lib->d_block));
   delete lib;
   return GMR_OK;
 }
@@ -410,9 +387,9 @@ int gmr_motion_lib_fill_dev(gmr_motion_lib_t* lib, const double* d_root_pos, con
   lib->has_body = d_local_body_pos && lib->A.nbody > 0;
   hipLaunchKernelGGL(gmr::motion_fill_kernel, dim3((B + gmr::MOTION_ROWS - 1) / gmr::MOTION_ROWS), dim3(256), 0, st, lib->A, d_root_pos,
                      d_root_rot_xyzw, d_dof_pos, d_local_body_pos, (flags & GMR_MOTION_ANGVEL_REFERENCE) ? 1 : 0);
-  HIP_TRY(hipGetLastError());
+  GMR_HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(gmr::motion_stats_kernel, dim3(lib->A.C), dim3(256), 0, st, lib->A);
-  HIP_TRY(hipGetLastError());
+  GMR_HIP_TRY(hipGetLastError());
   lib->filled = 1;
   return GMR_OK;
 }
@@ -425,16 +402,19 @@ int gmr_motion_lib_fill(gmr_motion_lib_t* lib, const double* root_pos, const dou
   const size_t n[4] = {B * 24, B * 32, B * lib->A.ndof * 8, local_body_pos ? B * lib->A.nbody * 12 : 0};
   const void* h[4] = {root_pos, root_rot_xyzw, dof_pos, local_body_pos};
   void* d[4] = {nullptr, nullptr, nullptr, nullptr};
-  DevTmp tmp;
+  gmr::Carve c;
+  size_t off[4];
+  for (int k = 0; k < 4; k++) off[k] = c.take(n[k]);
+  gmr::DeviceBlock blk;          // device scratch of this call
+  GMR_HIP_TRY(blk.reserve(c.total()));
   for (int k = 0; k < 4; k++) {
-    if (!n[k]) continue;
-    HIP_TRY(tmp.take(&d[k], n[k]));
-    HIP_TRY(hipMemcpy(d[k], h[k], n[k], hipMemcpyHostToDevice));
+    if (!n[k] && k != 2) continue;                     // (an absent local_body_pos stays null; dof_pos of no dofs is never read)
+    d[k] = blk.data() + off[k];
+    if (n[k]) GMR_HIP_TRY(hipMemcpy(d[k], h[k], n[k], hipMemcpyHostToDevice));
   }
-  if (lib->A.ndof == 0) HIP_TRY(tmp.take(&d[2], 8));
   const int rc = gmr_motion_lib_fill_dev(lib, (const double*)d[0], (const double*)d[1], (const double*)d[2], (const float*)d[3], flags, nullptr);
   if (rc != GMR_OK) return rc;
-  HIP_TRY(hipDeviceSynchronize());
+  GMR_HIP_TRY(hipDeviceSynchronize());
   return GMR_OK;
 }
 
@@ -446,7 +426,7 @@ int gmr_motion_lib_array(const gmr_motion_lib_t* lib, int which, void** d_ptr, s
     if (bytes) *bytes = 0;
     return GMR_OK;
   }
-  if (d_ptr) *d_ptr = lib->d_block + lib->off[which];
+  if (d_ptr) *d_ptr = lib->block.data() + lib->off[which];
   if (bytes) *bytes = lib->bytes[which];
   return GMR_OK;
 }
@@ -465,7 +445,7 @@ int gmr_motion_sample_dev(const gmr_motion_lib_t* lib, int N, const int32_t* d_c
   const int per_block = 256 / gmr::MOTION_GROUP;
   hipLaunchKernelGGL(gmr::motion_sample_kernel, dim3((N + per_block - 1) / per_block), dim3(256), 0, (hipStream_t)stream, lib->A, N, d_clip,
                      d_time, (flags & GMR_MOTION_LOOP) ? 1 : 0, O);
-  HIP_TRY(hipGetLastError());
+  GMR_HIP_TRY(hipGetLastError());
   return GMR_OK;
 }
 
@@ -480,20 +460,23 @@ int gmr_motion_sample(const gmr_motion_lib_t* lib, int N, const int32_t* clip, c
   void* h[8] = {root_pos, root_rot, root_vel, root_ang_vel, dof_pos, dof_vel, local_body_pos, status};
   const size_t nb[8] = {n * 12, n * 16, n * 12, n * 12, n * ndof * 4, n * ndof * 4, n * nb3 * 4, n * 4};
   void* d[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  void *d_clip = nullptr, *d_time = nullptr;
-  DevTmp tmp;
-  HIP_TRY(tmp.take(&d_clip, n * 4));
-  HIP_TRY(tmp.take(&d_time, n * 8));
-  HIP_TRY(hipMemcpy(d_clip, clip, n * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_time, time, n * 8, hipMemcpyHostToDevice));
+  gmr::Carve c;
+  const size_t o_clip = c.take(n * 4), o_time = c.take(n * 8);
+  size_t off[8];
+  for (int k = 0; k < 8; k++) off[k] = c.take(h[k] ? nb[k] : 0);
+  gmr::DeviceBlock blk;          // device scratch of this call
+  GMR_HIP_TRY(blk.reserve(c.total()));
+  void *d_clip = blk.data() + o_clip, *d_time = blk.data() + o_time;
+  GMR_HIP_TRY(hipMemcpy(d_clip, clip, n * 4, hipMemcpyHostToDevice));
+  GMR_HIP_TRY(hipMemcpy(d_time, time, n * 8, hipMemcpyHostToDevice));
   for (int k = 0; k < 8; k++)
-    if (h[k]) HIP_TRY(tmp.take(&d[k], nb[k]));
+    if (h[k]) d[k] = blk.data() + off[k];
   const int rc = gmr_motion_sample_dev(lib, N, (const int32_t*)d_clip, (const double*)d_time, flags, (float*)d[0], (float*)d[1], (float*)d[2],
                                        (float*)d[3], (float*)d[4], (float*)d[5], (float*)d[6], (int32_t*)d[7], nullptr);
   if (rc != GMR_OK) return rc;
-  HIP_TRY(hipDeviceSynchronize());
+  GMR_HIP_TRY(hipDeviceSynchronize());
   for (int k = 0; k < 8; k++)
-    if (h[k] && nb[k]) HIP_TRY(hipMemcpy(h[k], d[k], nb[k], hipMemcpyDeviceToHost));
+    if (h[k] && nb[k]) GMR_HIP_TRY(hipMemcpy(h[k], d[k], nb[k], hipMemcpyDeviceToHost));
   return GMR_OK;
 }
 

@@ -20,12 +20,12 @@
 #include <string.h>
 
 #include <algorithm>
-#include <mutex>
 #include <new>
 #include <vector>
 
 #include "../../include/gmr_hip.h"
 #include "gmr_internal.h"
+#include "gmr_workspace.h"
 
 #define SX_MAX_JOINTS 64
 #define SX_BLOCK 64
@@ -643,41 +643,18 @@ static bool make_prog(int J, const int32_t* parents, const std::vector<char>& ke
 struct gmr_smplx {
   int J = 0, nsel = 0;
   gmr::SmplxProg all, sel;       // every joint (rows = joint index) / ancestor closure of the selection
-  double* d_jrest = nullptr;     // staging of the host entry points
-  char* ws = nullptr;            // their device workspace, grown on demand and kept (a hipMalloc / hipFree pair per clip costs
-  size_t ws_bytes = 0;           //  more than the kernels of a short clip)
-  std::mutex mu;                 // the host entry points of one handle run one at a time (they share d_jrest and ws)
-  char* planes = nullptr;        // gmr_smplx_joints_dev: the transposed poses and joints of the launch in flight (one stream at
-  size_t planes_bytes = 0;       //  a time per handle)
-  // gmr_smplx_batch_frames_dev: takes the handle only when the selection's ancestor closure lies inside the body joints;
-  // one grow-only scratch block per HIP stream that has called (the gmr_bvh pattern: growing a block waits for its own
-  // stream alone; batch_mu orders the host side)
+  gmr::DeviceBlock jrest;        // staging of the host entry points: j_rest f64[J][3]
+  gmr::DeviceBlock ws;           // their device workspace, grown on demand and kept (a hipMalloc / hipFree pair per clip costs
+                                 //  more than the kernels of a short clip)
+  std::mutex mu;                 // the host entry points of one handle run one at a time (they share jrest and ws)
+  gmr::StreamWorkspace planes;   // gmr_smplx_joints_dev: the transposed poses and joints of a launch
+  // gmr_smplx_batch_frames_dev takes the handle only when the selection's ancestor closure lies inside the body joints
   bool batch_ok = false;
   int batch_lds_joints = 0, batch_lds_align = 0, batch_nslot_lds = 1;
-  struct Ws {
-    hipStream_t stream;
-    char* d;
-    size_t bytes;
-  };
-  std::mutex batch_mu;
-  std::vector<Ws> batch_ws;
+  gmr::StreamWorkspace batch_ws;
   std::mutex batch_host_mu;      // gmr_smplx_batch_frames: device staging of the host buffers, grown on demand and kept
-  char* batch_host_ws = nullptr;
-  size_t batch_host_ws_bytes = 0;
+  gmr::DeviceBlock batch_host_ws;
 };
-
-static hipError_t smplx_workspace(gmr_smplx* h, size_t bytes, char** out) {
-  if (bytes > h->ws_bytes) {
-    if (h->ws) (void)hipFree(h->ws);
-    h->ws = nullptr; h->ws_bytes = 0;
-    const size_t want = bytes + bytes / 4;
-    hipError_t e = hipMalloc((void**)&h->ws, want);
-    if (e != hipSuccess) return e;
-    h->ws_bytes = want;
-  }
-  *out = h->ws;
-  return hipSuccess;
-}
 
 extern "C" {
 
@@ -735,21 +712,14 @@ int gmr_smplx_create(int J, const int32_t* parents, int nsel, const int32_t* sel
     e = hipFuncSetAttribute((const void*)gmr::smplx_batch_joints_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, h->batch_lds_joints);
   if (e == hipSuccess && h->batch_ok && h->batch_lds_align > 48 * 1024)
     e = hipFuncSetAttribute((const void*)gmr::smplx_batch_align_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, h->batch_lds_align);
-  if (e == hipSuccess) e = hipMalloc((void**)&h->d_jrest, (size_t)J * 3 * sizeof(double));
+  if (e == hipSuccess) e = h->jrest.reserve((size_t)J * 3 * sizeof(double));
   if (e != hipSuccess) { delete h; return gmr_fail(GMR_ERR_HIP, "gmr_smplx_create: %s", hipGetErrorString(e)); }
   *out = h;
   return GMR_OK;
 }
 
 int gmr_smplx_destroy(gmr_smplx_t* h) {
-  if (!h) return GMR_OK;
-  (void)hipFree(h->d_jrest);
-  if (h->ws) (void)hipFree(h->ws);
-  if (h->planes) (void)hipFree(h->planes);
-  for (auto& w : h->batch_ws)
-    if (w.d) (void)hipFree(w.d);          // (hipFree waits for the device: nothing of this handle is in flight afterwards)
-  if (h->batch_host_ws) (void)hipFree(h->batch_host_ws);
-  delete h;
+  delete h;                                // (freeing its blocks waits for the device: nothing of the handle is in flight afterwards)
   return GMR_OK;
 }
 
@@ -767,17 +737,12 @@ int gmr_smplx_joints_dev(gmr_smplx_t* h, int N, const double* d_j_rest, const fl
     hipLaunchKernelGGL(gmr::smplx_joints_kernel<false>, grid, block, lds, st, h->all, N, d_j_rest, d_full_pose, d_transl, d_joints);
   } else {
     const int C = h->J * 3;
-    const size_t plane = ((size_t)N * C * sizeof(float) + 255) / 256 * 256;
-    if (2 * plane > h->planes_bytes) {
-      hipError_t e = hipStreamSynchronize(st);                        // (the launch in flight may still use the old block)
-      if (e != hipSuccess) return gmr_fail(GMR_ERR_HIP, "gmr_smplx_joints_dev: %s", hipGetErrorString(e));
-      if (h->planes) (void)hipFree(h->planes);
-      h->planes = nullptr; h->planes_bytes = 0;
-      if ((e = hipMalloc((void**)&h->planes, 2 * plane + plane / 2)) != hipSuccess) return gmr_fail(GMR_ERR_HIP, "gmr_smplx_joints_dev: %s", hipGetErrorString(e));
-      h->planes_bytes = 2 * plane + plane / 2;
-    }
-    float* pose_t = reinterpret_cast<float*>(h->planes);
-    float* joints_t = reinterpret_cast<float*>(h->planes + h->planes_bytes / 2 / 256 * 256);
+    gmr::Carve c;
+    const size_t o_pose = c.take((size_t)N * C * sizeof(float)), o_joints = c.take((size_t)N * C * sizeof(float));
+    const auto ws = h->planes.acquire(st, c.total());                 // (held until the last launch below is enqueued)
+    GMR_NAMED_HIP_TRY("gmr_smplx_joints_dev", ws.error());
+    float* pose_t = reinterpret_cast<float*>(ws.base() + o_pose);
+    float* joints_t = reinterpret_cast<float*>(ws.base() + o_joints);
     hipLaunchKernelGGL(gmr::rows_planes_kernel<true>, dim3((N + 63) / 64), dim3(256), 64 * (C + 1) * sizeof(float), st, d_full_pose, N, C, pose_t);
     hipLaunchKernelGGL(gmr::smplx_joints_kernel<true>, grid, block, lds, st, h->all, N, d_j_rest, pose_t, d_transl, joints_t);
     hipLaunchKernelGGL(gmr::rows_planes_kernel<false>, dim3((N + 63) / 64), dim3(256), 64 * (C + 1) * sizeof(float), st, joints_t, N, C, d_joints);
@@ -838,18 +803,18 @@ int gmr_smplx_joints(gmr_smplx_t* h, int N, const double* j_rest, const float* f
   if (N == 0) return GMR_OK;
   const size_t nb_pose = (size_t)N * h->J * 3 * sizeof(float), nb_tr = (size_t)N * 3 * sizeof(float);
   std::lock_guard<std::mutex> guard(h->mu);
-  char* ws = nullptr;
-  hipError_t e = smplx_workspace(h, 2 * nb_pose + nb_tr + 64, &ws);
-  if (e != hipSuccess) return gmr_fail(GMR_ERR_HIP, "gmr_smplx_joints: %s", hipGetErrorString(e));
+  GMR_NAMED_HIP_TRY("gmr_smplx_joints", h->ws.reserve(2 * nb_pose + nb_tr + 64, 4));
+  char* ws = h->ws.data();
+  hipError_t e = hipSuccess;
   float* d_pose = (float*)ws;
   float* d_j = (float*)(ws + nb_pose);
   float* d_tr = (float*)(ws + 2 * nb_pose);
   int rc = GMR_OK;
-  if ((e = hipMemcpy(h->d_jrest, j_rest, (size_t)h->J * 3 * sizeof(double), hipMemcpyHostToDevice)) != hipSuccess ||
+  if ((e = hipMemcpy(h->jrest.data(), j_rest, (size_t)h->J * 3 * sizeof(double), hipMemcpyHostToDevice)) != hipSuccess ||
       (e = hipMemcpy(d_pose, full_pose, nb_pose, hipMemcpyHostToDevice)) != hipSuccess ||
       (e = hipMemcpy(d_tr, transl, nb_tr, hipMemcpyHostToDevice)) != hipSuccess)
     rc = gmr_fail(GMR_ERR_HIP, "gmr_smplx_joints: %s", hipGetErrorString(e));
-  if (rc == GMR_OK) rc = gmr_smplx_joints_dev(h, N, h->d_jrest, d_pose, d_tr, d_j, nullptr);
+  if (rc == GMR_OK) rc = gmr_smplx_joints_dev(h, N, (const double*)h->jrest.data(), d_pose, d_tr, d_j, nullptr);
   if (rc == GMR_OK && (e = hipMemcpy(joints, d_j, nb_pose, hipMemcpyDeviceToHost)) != hipSuccess)
     rc = gmr_fail(GMR_ERR_HIP, "gmr_smplx_joints: %s", hipGetErrorString(e));
   return rc;
@@ -865,27 +830,28 @@ int gmr_smplx_frames(gmr_smplx_t* h, int N, const double* j_rest, const float* f
   if (target_time && N < 2) return gmr_fail(GMR_ERR_ARG, "gmr_smplx_frames: fps alignment needs at least two source frames");
   if (Nout == 0) return GMR_OK;
   const int C = h->J * 3;
-  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-  const size_t nb_pose = up((size_t)N * C * sizeof(float)), nb_tr = up((size_t)N * 3 * sizeof(float));
-  const size_t nb_t = up((size_t)Nout * sizeof(double)), nb_out = up((size_t)Nout * h->sel.nrow * 7 * sizeof(double));
+  const size_t nb_pose = (size_t)N * C * sizeof(float);
+  gmr::Carve c;
+  const size_t o_pose = c.take(nb_pose), o_pose_t = c.take(nb_pose), o_joints_t = c.take(nb_pose), o_tr = c.take((size_t)N * 3 * sizeof(float)),
+               o_t = c.take((size_t)Nout * sizeof(double)), o_out = c.take((size_t)Nout * h->sel.nrow * 7 * sizeof(double));
   std::lock_guard<std::mutex> guard(h->mu);
-  char* ws = nullptr;
-  hipError_t e = smplx_workspace(h, 3 * nb_pose + nb_tr + nb_t + nb_out, &ws);
-  if (e != hipSuccess) return gmr_fail(GMR_ERR_HIP, "gmr_smplx_frames: %s", hipGetErrorString(e));
-  float* d_pose = (float*)ws;
-  float* pose_t = (float*)(ws + nb_pose);
-  float* joints_t = (float*)(ws + 2 * nb_pose);
-  float* d_tr = (float*)(ws + 3 * nb_pose);
-  double* d_t = (double*)(ws + 3 * nb_pose + nb_tr);
-  double* d_o = (double*)(ws + 3 * nb_pose + nb_tr + nb_t);
-  if ((e = hipMemcpy(h->d_jrest, j_rest, (size_t)h->J * 3 * sizeof(double), hipMemcpyHostToDevice)) != hipSuccess ||
+  GMR_NAMED_HIP_TRY("gmr_smplx_frames", h->ws.reserve(c.total(), 4));
+  char* ws = h->ws.data();
+  hipError_t e = hipSuccess;
+  float* d_pose = (float*)(ws + o_pose);
+  float* pose_t = (float*)(ws + o_pose_t);
+  float* joints_t = (float*)(ws + o_joints_t);
+  float* d_tr = (float*)(ws + o_tr);
+  double* d_t = (double*)(ws + o_t);
+  double* d_o = (double*)(ws + o_out);
+  if ((e = hipMemcpy(h->jrest.data(), j_rest, (size_t)h->J * 3 * sizeof(double), hipMemcpyHostToDevice)) != hipSuccess ||
       (e = hipMemcpy(d_pose, full_pose, (size_t)N * C * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess ||
       (e = hipMemcpy(d_tr, transl, (size_t)N * 3 * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess ||
       (target_time && (e = hipMemcpy(d_t, target_time, (size_t)Nout * sizeof(double), hipMemcpyHostToDevice)) != hipSuccess))
     return gmr_fail(GMR_ERR_HIP, "gmr_smplx_frames: %s", hipGetErrorString(e));
   hipLaunchKernelGGL(gmr::rows_planes_kernel<true>, dim3((N + 63) / 64), dim3(256), 64 * (C + 1) * sizeof(float), nullptr, d_pose, N, C, pose_t);
   hipLaunchKernelGGL(gmr::smplx_joints_kernel<true>, dim3((N + SX_BLOCK - 1) / SX_BLOCK), dim3(SX_BLOCK),
-                     std::max(h->all.nslot - 1, 1) * 12 * SX_BLOCK * 8, nullptr, h->all, N, h->d_jrest, pose_t, d_tr, joints_t);
+                     std::max(h->all.nslot - 1, 1) * 12 * SX_BLOCK * 8, nullptr, h->all, N, (const double*)h->jrest.data(), pose_t, d_tr, joints_t);
   if ((e = hipGetLastError()) != hipSuccess) return gmr_fail(GMR_ERR_HIP, "gmr_smplx_frames: %s", hipGetErrorString(e));
   int rc = smplx_align_launch(h, true, N, -1, pose_t, joints_t, Nout, target_time ? d_t : nullptr, d_o, nullptr);
   if (rc == GMR_OK && (e = hipMemcpy(out, d_o, (size_t)Nout * h->sel.nrow * 7 * sizeof(double), hipMemcpyDeviceToHost)) != hipSuccess)
@@ -919,15 +885,16 @@ int gmr_smplx_align(gmr_smplx_t* h, int N, int jstride, const float* full_pose, 
   }
   const size_t nb_pose = pc.size() * sizeof(float), nb_j = jc.size() * sizeof(float);
   const size_t nb_t = (size_t)Nout * sizeof(double), nb_out = (size_t)Nout * h->sel.nrow * 7 * sizeof(double);
-  auto up = [](size_t v) { return (v + 63) / 64 * 64; };
+  gmr::Carve c;
+  const size_t o_pose = c.take(nb_pose), o_j = c.take(nb_j), o_t = c.take(nb_t), o_out = c.take(nb_out);
   std::lock_guard<std::mutex> guard(h->mu);
-  char* ws = nullptr;
-  hipError_t e = smplx_workspace(h, up(nb_pose) + up(nb_j) + up(nb_t) + up(nb_out), &ws);
-  if (e != hipSuccess) return gmr_fail(GMR_ERR_HIP, "gmr_smplx_align: %s", hipGetErrorString(e));
-  float* d_pose = (float*)ws;
-  float* d_j = (float*)(ws + up(nb_pose));
-  double* d_t = (double*)(ws + up(nb_pose) + up(nb_j));
-  double* d_o = (double*)(ws + up(nb_pose) + up(nb_j) + up(nb_t));
+  GMR_NAMED_HIP_TRY("gmr_smplx_align", h->ws.reserve(c.total(), 4));
+  char* ws = h->ws.data();
+  hipError_t e = hipSuccess;
+  float* d_pose = (float*)(ws + o_pose);
+  float* d_j = (float*)(ws + o_j);
+  double* d_t = (double*)(ws + o_t);
+  double* d_o = (double*)(ws + o_out);
   int rc = GMR_OK;
   if ((e = hipMemcpy(d_pose, pc.data(), nb_pose, hipMemcpyHostToDevice)) != hipSuccess ||
       (e = hipMemcpy(d_j, jc.data(), nb_j, hipMemcpyHostToDevice)) != hipSuccess ||
@@ -964,36 +931,16 @@ int gmr_smplx_batch_frames_dev(gmr_smplx_t* h, int nclip, int B, const float* d_
   const size_t Bp = ((size_t)B + 63) / 64 * 64;
   const size_t o_pose = 0, o_joints = o_pose + (size_t)P.n * 3 * Bp * sizeof(float), total = o_joints + (size_t)P.nrow * 3 * Bp * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
-  std::lock_guard<std::mutex> lock(h->batch_mu);
-  gmr_smplx::Ws* w = nullptr;
-  for (auto& e : h->batch_ws)
-    if (e.stream == st) w = &e;
-  if (!w) {
-    h->batch_ws.push_back(gmr_smplx::Ws{st, nullptr, 0});
-    w = &h->batch_ws.back();
-  }
-  if (w->bytes < total) {
-    if (w->d) {
-      hipError_t e = hipStreamSynchronize(st);       // earlier calls on this stream are the only users of the block
-      if (e == hipSuccess) e = hipFree(w->d);
-      if (e != hipSuccess) return gmr_fail(GMR_ERR_HIP, "gmr_smplx_batch_frames_dev: %s", hipGetErrorString(e));
-      w->d = nullptr;
-      w->bytes = 0;
-    }
-    const size_t want = total + total / 4;
-    hipError_t e = hipMalloc((void**)&w->d, want);
-    if (e != hipSuccess) return gmr_fail(GMR_ERR_HIP, "gmr_smplx_batch_frames_dev: %s", hipGetErrorString(e));
-    w->bytes = want;
-  }
-  float* pose_t = (float*)(w->d + o_pose);
-  float* joints_t = (float*)(w->d + o_joints);
+  const auto ws = h->batch_ws.acquire(st, total);              // (held until the last launch below is enqueued)
+  GMR_NAMED_HIP_TRY("gmr_smplx_batch_frames_dev", ws.error());
+  float* pose_t = (float*)(ws.base() + o_pose);
+  float* joints_t = (float*)(ws.base() + o_joints);
   const dim3 grid((unsigned)(Bp / SX_BLOCK)), block(SX_BLOCK);
   hipLaunchKernelGGL(gmr::smplx_batch_joints_kernel, grid, block, h->batch_lds_joints, st, P, nclip, B, Bp, h->batch_nslot_lds,
                      d_root_orient, d_pose_body, d_trans, d_src_start, d_j_rest, pose_t, joints_t);
   hipLaunchKernelGGL(gmr::smplx_batch_align_kernel, grid, block, h->batch_lds_align, st, P, nclip, B, Bp, d_src_start, d_nout, d_align,
                      pose_t, joints_t, d_clip_out);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return gmr_fail(GMR_ERR_HIP, "gmr_smplx_batch_frames_dev: %s", hipGetErrorString(e));
+  GMR_NAMED_HIP_TRY("gmr_smplx_batch_frames_dev", hipGetLastError());
   return GMR_OK;
 }
 
@@ -1018,24 +965,17 @@ int gmr_smplx_batch_frames(gmr_smplx_t* h, int nclip, int B, const float* root_o
     if (!align[c] && nout[c] != n) return gmr_fail(GMR_ERR_ARG, "gmr_smplx_batch_frames: clip %d: without alignment nout must equal N", c);
   }
   const int nrow = h->sel.nrow, J = h->J;
-  auto up = [](size_t x) { return (x + 255) / 256 * 256; };
   const size_t nb_ro = (size_t)B * 3 * 4, nb_pb = (size_t)B * SX_BODY_POSE * 4, nb_seg = (size_t)(nclip + 1) * 4, nb_no = (size_t)nclip * 4,
                nb_al = (size_t)nclip, nb_jr = (size_t)nclip * J * 3 * 8, nb_tab = (size_t)nclip * sizeof(double*),
                nb_out = (size_t)nclip * T * nrow * 7 * 8;
   if (nb_out == 0 || B == 0) { if (nb_out) memset(human, 0, nb_out); return GMR_OK; }
-  const size_t o_ro = 0, o_pb = o_ro + up(nb_ro), o_tr = o_pb + up(nb_pb), o_seg = o_tr + up(nb_ro), o_no = o_seg + up(nb_seg),
-               o_al = o_no + up(nb_no), o_jr = o_al + up(nb_al), o_tab = o_jr + up(nb_jr), o_out = o_tab + up(nb_tab), total = o_out + up(nb_out);
+  gmr::Carve c;
+  const size_t o_ro = c.take(nb_ro), o_pb = c.take(nb_pb), o_tr = c.take(nb_ro), o_seg = c.take(nb_seg), o_no = c.take(nb_no),
+               o_al = c.take(nb_al), o_jr = c.take(nb_jr), o_tab = c.take(nb_tab), o_out = c.take(nb_out);
   std::lock_guard<std::mutex> guard(h->batch_host_mu);
+  GMR_NAMED_HIP_TRY("gmr_smplx_batch_frames", h->batch_host_ws.reserve(c.total(), 4));
+  char* d = h->batch_host_ws.data();
   hipError_t e = hipSuccess;
-  if (h->batch_host_ws_bytes < total) {
-    if (h->batch_host_ws) (void)hipFree(h->batch_host_ws);
-    h->batch_host_ws = nullptr;
-    h->batch_host_ws_bytes = 0;
-    const size_t want = total + total / 4;
-    if ((e = hipMalloc((void**)&h->batch_host_ws, want)) != hipSuccess) return gmr_fail(GMR_ERR_HIP, "gmr_smplx_batch_frames: %s", hipGetErrorString(e));
-    h->batch_host_ws_bytes = want;
-  }
-  char* d = h->batch_host_ws;
   std::vector<double*> tab(nclip);
   for (int c = 0; c < nclip; c++) tab[c] = (double*)(d + o_out) + (size_t)c * T * nrow * 7;
   // frames at or beyond nout[c] come back as zeros (the kernels do not write them)

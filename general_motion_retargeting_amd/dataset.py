@@ -17,6 +17,7 @@ from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
+from . import _lib
 from .data_loader import motion_dict
 from .kinematics_model import KinematicsModel
 from .motion_retarget import GeneralMotionRetargeting
@@ -161,30 +162,17 @@ class DevicePost:
     def __init__(self, pool: Optional[PinnedPool] = None):
         self.pool = pool if pool is not None else PinnedPool()
         self._stream = None
-        self._dev: Dict[str, object] = {}
-        self._pin: Dict[str, np.ndarray] = {}
+        self._bufs = _lib.NamedBuffers()          # device blocks and input staging
         self._events = None
         self._chunker = None
         self.chunk_reports: List = []             # per job of the last run: per-clip chunk reports (chunking.clip_report), or None
         self.library = None                       # the motion library of the last run that asked for one (run(..., library=))
 
     def _d(self, name: str, nbytes: int):
-        from . import _lib
-        b = self._dev.get(name)
-        if b is None or b.nbytes < nbytes:
-            if b is not None:
-                b.free()                            # (every batch ends with a stream synchronisation: nothing is in flight)
-            b = self._dev[name] = _lib.DeviceBuffer(nbytes + nbytes // 4 + 256)
-        return b
+        return self._bufs.device(name, nbytes)
 
     def pinned(self, name: str, shape, dtype) -> np.ndarray:
-        from . import _lib
-        need = int(np.prod(shape)) * np.dtype(dtype).itemsize
-        blk = self._pin.get(name)
-        if blk is None or blk.nbytes < need:
-            self._pin.pop(name, None)
-            blk = self._pin[name] = _lib.pinned_empty((need + need // 2 + 8,), np.uint8)
-        return blk[:need].view(dtype).reshape(shape)
+        return self._bufs.pinned(name, shape, dtype)
 
     def _stage_smplx(self, jobs: Sequence[Dict]):
         """The raw SMPL-X clips of all jobs that carry ``"smplx"``, per handle: one page-locked block (poses, translations, the
@@ -200,7 +188,6 @@ class DevicePost:
             assert len(sx["clips"]) == S and sx["handle"].rows == sol.nhuman and sx["handle"].batch_takes
             d_human[i] = self._d(f"human_{i}", S * T * sol.nhuman * 56)
             groups.setdefault(id(sx["handle"]), (sx["handle"], []))[1].extend((i, k, T, e) for k, e in enumerate(sx["clips"]))
-        up = lambda x: (int(x) + 255) // 256 * 256            # noqa: E731
         calls = []
         for gi, (h, members) in enumerate(groups.values()):
             n, frame_bytes = len(members), h.rows * 56
@@ -210,7 +197,7 @@ class DevicePost:
             offs, total = {}, 0
             for k, dt, shape in fields:
                 offs[k] = total
-                total += up(int(np.prod(shape)) * np.dtype(dt).itemsize)
+                total += _lib.align256(int(np.prod(shape)) * np.dtype(dt).itemsize)
             stage = self.pinned(f"smplx_in_{gi}", (total,), np.uint8)
             v = {k: stage[offs[k]: offs[k] + int(np.prod(shape)) * np.dtype(dt).itemsize].view(dt).reshape(shape) for k, dt, shape in fields}
             a = 0
@@ -257,7 +244,6 @@ class DevicePost:
         st, ev = self._stream, self._events
         fk = km.hip_handle
         nb, ndof, nq = fk.nbody, fk.ndof, fk.ndof + 7
-        up = lambda x: (int(x) + 255) // 256 * 256            # noqa: E731
         # the sources of one post-processing call are at most 8 jobs: more jobs -> more calls, each over its own dense range
         # of rows that starts at a multiple of 4 (so that its local_body_pos starts 16-byte aligned)
         # raw BVH jobs: the clips of one topology are consecutive streams of the batch (one gmr_bvh_frames_dev call each)
@@ -282,11 +268,11 @@ class DevicePost:
             row = (row + seg[-1] + 3) // 4 * 4
         Bp, nclip = max(row, 1), sum(len(j["lens"]) for j in jobs)
         o_rp = 0
-        o_rr = o_rp + up(Bp * 24)
-        o_dp = o_rr + up(Bp * 32)
-        o_lb = o_dp + up(Bp * ndof * 8)
-        o_st = o_lb + up(Bp * nb * 12)
-        total = o_st + up(nclip * 4)
+        o_rr = o_rp + _lib.align256(Bp * 24)
+        o_dp = o_rr + _lib.align256(Bp * 32)
+        o_lb = o_dp + _lib.align256(Bp * ndof * 8)
+        o_st = o_lb + _lib.align256(Bp * nb * 12)
+        total = o_st + _lib.align256(nclip * 4)
         d_out = self._d("out", total)
         base = d_out.ptr.value
         sx_calls, sx_human = self._stage_smplx(jobs)
@@ -441,19 +427,13 @@ class ClipRetargeter:
         self.chunk_report: Optional[List[Dict]] = None
         self.chunk_summary: Dict = {}
         self._km: Optional[KinematicsModel] = None
-        self._pin: Dict[str, np.ndarray] = {}
+        self._pin = _lib.NamedBuffers()
         self._dev_post: Optional[DevicePost] = None
         self.timing: Dict[str, float] = {}
 
     def _buf(self, name: str, shape, dtype) -> np.ndarray:
         """a [shape] view of this object's page-locked block ``name`` (grown by half when too small)"""
-        from . import _lib
-        need = int(np.prod(shape)) * np.dtype(dtype).itemsize
-        blk = self._pin.get(name)
-        if blk is None or blk.nbytes < need:
-            self._pin.pop(name, None)
-            blk = self._pin[name] = _lib.pinned_empty((need + need // 2,), np.uint8)
-        return blk[:need].view(dtype).reshape(shape)
+        return self._pin.pinned(name, shape, dtype)
 
     # ---- staged protocol (DatasetPipeline): clips are copied into the padded, page-locked batch AS THEY ARRIVE from the
     # loaders -- the time this thread would otherwise spend waiting for them -- instead of when the batch is launched

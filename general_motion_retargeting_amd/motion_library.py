@@ -164,7 +164,7 @@ class MotionLibrary:
         offs, total = [], 0
         for a in parts:
             offs.append(total)
-            total += (a.nbytes + 255) // 256 * 256
+            total += _lib.align256(a.nbytes)
         host = np.zeros(max(total, 8), dtype=np.uint8)
         for a, o in zip(parts, offs):
             host[o:o + a.nbytes] = a.reshape(-1).view(np.uint8)

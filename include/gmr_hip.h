@@ -5,11 +5,15 @@
  * reference-side stub.
  *
  * Conventions: every function returns 0 on success and a negative code on error
- * (gmr_last_error() returns a thread-local message); handles are immutable after creation, so
- * batch calls on different HIP streams are re-entrant.  "dev" entry points take device pointers
- * and a hipStream_t (as void*; NULL = the default stream) and never synchronise; the entry points
- * without the suffix take host pointers, copy, launch and synchronise; they stage through a per-handle
- * device workspace, so at most one host-pointer call per handle at a time (like the reference object,
+ * (gmr_last_error() returns a thread-local message); what a handle describes is immutable after
+ * creation, so batch calls on different HIP streams are re-entrant.  "dev" entry points take device
+ * pointers and a hipStream_t (as void*; NULL = the default stream).  Those that need scratch memory
+ * (gmr_postprocess_clips_dev, gmr_smplx_joints_dev, gmr_smplx_batch_frames_dev, gmr_bvh_frames_dev)
+ * keep it on the handle, one grow-only block per HIP stream that has called, freed when the handle is
+ * destroyed: calls on different streams may be in flight together, and the only time such a call
+ * waits is when its block has to grow -- for its own stream alone.  The entry points without the
+ * suffix take host pointers, copy, launch and synchronise; they stage through ONE device workspace
+ * per handle, so at most one host-pointer call per handle at a time (like the reference object,
  * which is not thread-safe either: SURVEY.md section 8b).
  *
  * Row IDs (H1..H10) refer to SURVEY.md section 8(a).
@@ -288,7 +292,9 @@ int gmr_smplx_rows(const gmr_smplx_t* h);   /* rows per output frame (nsel, or J
 /* Replaces the joints of `body_model(betas, global_orient, body_pose, transl, ...)` as called at
  * general_motion_retargeting/utils/smpl.py:12-34, without the mesh: joints f32[N][J][3] from the rest
  * joints j_rest f64[J][3] (J_regressor applied to the shaped template, once per clip), the axis-angle
- * poses full_pose f32[N][J][3] and transl f32[N][3].  (The body model is third-party: parity unpinned.) */
+ * poses full_pose f32[N][J][3] and transl f32[N][3].  (The body model is third-party: parity unpinned.)
+ * The device entry point is asynchronous; its scratch (the poses and joints as frame-minor planes, 24 J B per frame) is a
+ * block per HIP stream like that of the other dev entry points: one handle may be used on several streams at once. */
 int gmr_smplx_joints_dev(gmr_smplx_t* h, int N, const double* d_j_rest, const float* d_full_pose,
                          const float* d_transl, float* d_joints, void* stream);
 int gmr_smplx_joints(gmr_smplx_t* h, int N, const double* j_rest, const float* full_pose, const float* transl,

@@ -1,6 +1,7 @@
 """The C++ host logic behind the IK kernel (static H-assembly schedule, limb/trunk decomposition, LDS
 layout + image) checked on the CPU for every (source, robot) pair: tests/cpp/layout_check.cpp is plain
-C++ (g++), includes the product header csrc/gmr_ik_layout.h and reads the packed structs from a file."""
+C++ (g++), includes the product header csrc/gmr_ik_layout.h and reads the packed structs from a file.
+tests/cpp/workspace_check.cpp does the same for csrc/gmr_workspace.h, how the host side owns device memory."""
 import os
 import subprocess
 
@@ -92,6 +93,16 @@ def test_fk_tree_partition_for_the_split_walk(split_checker):
         assert out.returncode == 0 and out.stdout.strip().endswith("ok"), (name, out.stdout, out.stderr)
         if name == "unitree_g1":        # four wavefronts walk at most 13 of the 38 bodies each
             assert "maxw=4 nw=4 longest=13" in out.stdout, out.stdout
+
+
+def test_device_workspace_contract(tmp_path):
+    """csrc/gmr_workspace.h against a recording fake of the HIP runtime: the layout rounding, grow-only blocks with their
+    headroom and floor, and the per-stream workspace's order of operations (synchronise the block's own stream, free,
+    allocate), its isolation between streams, its recovery from a failed allocation and its lock."""
+    exe = str(tmp_path / "workspace_check")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-pthread", "-o", exe, os.path.join(ROOT, "tests", "cpp", "workspace_check.cpp")])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and out.stdout.strip() == "ok", (out.stdout, out.stderr)
 
 
 def test_layout_code_is_clean_under_sanitizers(tmp_path):
