@@ -108,6 +108,9 @@ _SIGS = {
     "gmr_motion_lib_array": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     "gmr_motion_sample_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 9),
     "gmr_motion_sample": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8),
+    "gmr_motion_body_state_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                            C.c_void_p, C.c_void_p]),
+    "gmr_motion_body_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "gmr_comm_create": (C.c_int, [C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),
     "gmr_comm_destroy": (C.c_int, [C.c_void_p]),
     "gmr_comm_rank": (C.c_int, [C.c_void_p]),
@@ -515,6 +518,16 @@ class Solver:
             self.close()
         except Exception:
             pass
+
+
+BODY_STATE_FIELDS = ("root_pos", "root_rot", "root_vel", "root_ang_vel", "dof_pos", "dof_vel", "body_pos", "body_rot", "body_vel",
+                     "body_ang_vel", "status")
+FK_MAX_BODIES = 64
+
+
+class BodyStateOut(C.Structure):
+    """``gmr_body_state_out_t``: the outputs of ``gmr_motion_body_state[_dev]``, each an address or NULL"""
+    _fields_ = [(k, C.c_void_p) for k in BODY_STATE_FIELDS]
 
 
 class FkHandle:

@@ -13,6 +13,7 @@
 
 #include "../../include/gmr_hip.h"
 #include "gmr_fk_tree.h"
+#include "gmr_handles.h"      // struct gmr_fk
 #include "gmr_ik_layout.h"
 #include "gmr_ik_wide_layout.h"
 #include "gmr_internal.h"
@@ -89,14 +90,6 @@ struct gmr_solver {
   static constexpr int kPipe = 4;
   hipStream_t pipe_stream[kPipe] = {nullptr, nullptr, nullptr, nullptr};
   gmr::DeviceBlock pipe_ws[kPipe];
-};
-
-struct gmr_fk {
-  gmr::FkTree tree;
-  gmr::DeviceBlock d_tree;       // the tree as the kernels read it
-  const gmr::FkTree* dev() const { return (const gmr::FkTree*)d_tree.data(); }
-  gmr::DeviceBlock min_part;     // gmr_fk_batch_dev: one float per block of the min_z reduction
-  gmr::StreamWorkspace post_ws;  // gmr_postprocess_clips_dev
 };
 
 extern "C" {

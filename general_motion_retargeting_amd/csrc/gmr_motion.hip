@@ -21,7 +21,9 @@
 
 #include "../../include/gmr_hip.h"
 #include "gmr_device_math.h"
+#include "gmr_handles.h"
 #include "gmr_internal.h"
+#include "gmr_motion_sample.h"
 #include "gmr_workspace.h"
 
 // float32 arithmetic here mirrors NumPy's / torch's (one rounding per operation: a multiply and an add stay two)
@@ -30,15 +32,7 @@
 namespace gmr {
 
 constexpr int MOTION_ROWS = 64;      // rows per block of the fill kernel
-constexpr int MOTION_GROUP = 16;     // lanes per query of the sample kernel
 constexpr int MOTION_STAT_ROWS = 4;  // mean, std, min, max
-
-struct MotionArrays {
-  int C, B, ndof, nbody;
-  const int32_t* seg_start;   // [C + 1], validated on the host when the library was created
-  const double* fps;          // [C]
-  float *root_pos, *root_rot, *dof_pos, *local_body_pos, *root_vel, *root_ang_vel, *dof_vel, *stats;
-};
 
 // the clip of row b: the LAST c with seg_start[c] <= b (an empty clip shares its start with the clip after it)
 __device__ __forceinline__ int clip_of_row(const int32_t* __restrict__ seg_start, int C, int b) {
@@ -211,12 +205,6 @@ struct MotionSampleOut {
   int32_t* status;
 };
 
-// a[lo] (same) or (float)(1 - blend) a[lo] + (float)blend a[hi] as a separate multiply and add (:196-200)
-__device__ __forceinline__ float lerp1(const float* __restrict__ a, size_t lo, size_t hi, bool same, float w0, float w1) {
-  const float x = a[lo];
-  return same ? x : w0 * x + w1 * a[hi];
-}
-
 // 16 lanes per query: they stride over the columns of the two source rows, so the row reads and the output writes of a
 // query are contiguous.  The scalars of a query (frame pair, blend, slerp weights) are computed by all 16 lanes alike -- in
 // a SIMD that is the same instruction stream as computing them once and sharing them.
@@ -228,10 +216,8 @@ __global__ __launch_bounds__(256) void motion_sample_kernel(const MotionArrays A
   const int c = clip[q];
   const double tm = time[q];
   const int ndof = A.ndof, nb3 = A.nbody * 3;
-  int T = 0, first = 0;
-  const bool clip_ok = c >= 0 && c < A.C;
-  if (clip_ok) { first = A.seg_start[c]; T = A.seg_start[c + 1] - first; }
-  const bool ok = clip_ok && T >= 1 && isfinite(tm);
+  const MotionQuery Q = motion_query(A, c, tm, loop);      // (gmr_motion_sample.h)
+  const bool ok = Q.ok;
   if (O.status && l == 0) O.status[q] = ok ? 0 : 1;
   if (!ok) {
     // neutralised: NaN rows, nothing of the library is read
@@ -250,27 +236,9 @@ __global__ __launch_bounds__(256) void motion_sample_kernel(const MotionArrays A
       for (int k = l; k < nb3; k += MOTION_GROUP) O.local_body_pos[(size_t)q * nb3 + k] = nan;
     return;
   }
-  // :165-175 in float64
-  const double fps = A.fps[c];
-  const double dt = 1.0 / fps, duration = (double)T / fps;
-  double t;
-  if (loop) {
-    t = fmod(tm, duration);             // Python's %: the sign of the divisor
-    if (t < 0.0) t += duration;
-  } else {
-    t = fmin(tm, duration - dt);
-  }
-  const double x = t * fps, fl = floor(x);
-  int lo;
-  double blend;
-  // where the reference would index out of range (a negative time without loop; t * fps rounding up to T): the nearest frame
-  if (!(fl >= 0.0)) { lo = 0; blend = 0.0; }
-  else if (fl > (double)(T - 1)) { lo = T - 1; blend = 0.0; }
-  else { lo = (int)fl; blend = x - fl; }
-  const int hi = min(lo + 1, T - 1);
-  const bool same = lo == hi;
-  const size_t rl = (size_t)(first + lo), rh = (size_t)(first + hi);
-  const float w0 = (float)(1.0 - blend), w1 = (float)blend;
+  const bool same = Q.same;
+  const size_t rl = Q.rl, rh = Q.rh;
+  const float w0 = Q.w0, w1 = Q.w1;
   if (l < 3) {
     if (O.root_pos) O.root_pos[(size_t)q * 3 + l] = lerp1(A.root_pos, rl * 3 + l, rh * 3 + l, same, w0, w1);
     if (O.root_vel) O.root_vel[(size_t)q * 3 + l] = lerp1(A.root_vel, rl * 3 + l, rh * 3 + l, same, w0, w1);
@@ -283,52 +251,12 @@ __global__ __launch_bounds__(256) void motion_sample_kernel(const MotionArrays A
   if (O.local_body_pos)
     for (int k = l; k < nb3; k += MOTION_GROUP)
       O.local_body_pos[(size_t)q * nb3 + k] = lerp1(A.local_body_pos, rl * nb3 + k, rh * nb3 + k, same, w0, w1);
-  if (O.root_rot && l < 4) {
-    const float* q1 = A.root_rot + rl * 4;      // xyzw
-    float r;
-    if (same) {
-      r = q1[l];
-    } else {
-      // :205-233 in float32; the component order of the dot is wxyz, as the reference sums it
-      const float* q2 = A.root_rot + rh * 4;
-      float dot = q1[3] * q2[3];
-      dot = dot + q1[0] * q2[0];
-      dot = dot + q1[1] * q2[1];
-      dot = dot + q1[2] * q2[2];
-      const float sgn = dot < 0.0f ? -1.0f : 1.0f;
-      dot = fminf(fmaxf(sgn * dot, -1.0f), 1.0f);
-      const float a = q1[l], b = sgn * q2[l];
-      if (dot > 0.9995f) {
-        float v[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) v[k] = w0 * q1[k] + w1 * (sgn * q2[k]);
-        float n2 = v[3] * v[3];
-        n2 = n2 + v[0] * v[0];
-        n2 = n2 + v[1] * v[1];
-        n2 = n2 + v[2] * v[2];
-        r = __fdiv_rn(w0 * a + w1 * b, __fsqrt_rn(n2));
-      } else {
-        const float th0 = acosf(dot), sn0 = sinf(th0);
-        const float th = th0 * w1, sn = sinf(th);
-        const float s0 = cosf(th) - __fdiv_rn(dot * sn, sn0), s1 = __fdiv_rn(sn, sn0);
-        r = s0 * a + s1 * b;
-      }
-    }
-    O.root_rot[(size_t)q * 4 + l] = r;
-  }
+  if (O.root_rot && l < 4) O.root_rot[(size_t)q * 4 + l] = slerp1(A.root_rot, rl, rh, l, same, w0, w1);
 }
 
 }  // namespace gmr
 
 // ---- C-ABI (include/gmr_hip.h, "motion library") ---------------------------------------------------------------------------
-
-struct gmr_motion_lib {
-  gmr::MotionArrays A;
-  gmr::DeviceBlock block;        // every array of the library: one allocation
-  size_t off[GMR_MOTION_FPS + 1], bytes[GMR_MOTION_FPS + 1];
-  int filled = 0;                // 1 once a fill has been enqueued
-  int has_body = 0;              // the fill was given local_body_pos
-};
 
 extern "C" {
 
@@ -385,6 +313,7 @@ int gmr_motion_lib_fill_dev(gmr_motion_lib_t* lib, const double* d_root_pos, con
   hipStream_t st = (hipStream_t)stream;
   const int B = lib->A.B;
   lib->has_body = d_local_body_pos && lib->A.nbody > 0;
+  lib->reference_angvel = (flags & GMR_MOTION_ANGVEL_REFERENCE) ? 1 : 0;
   hipLaunchKernelGGL(gmr::motion_fill_kernel, dim3((B + gmr::MOTION_ROWS - 1) / gmr::MOTION_ROWS), dim3(256), 0, st, lib->A, d_root_pos,
                      d_root_rot_xyzw, d_dof_pos, d_local_body_pos, (flags & GMR_MOTION_ANGVEL_REFERENCE) ? 1 : 0);
   GMR_HIP_TRY(hipGetLastError());

@@ -372,6 +372,7 @@ class DevicePost:
                 chunks[0][2], np.concatenate([np.asarray(f, dtype=np.float64).reshape(-1) for f in library["fps"]]), ndof, nb,
                 C.c_void_p(base + o_rp), C.c_void_p(base + o_rr), C.c_void_p(base + o_dp), C.c_void_p(base + o_lb),
                 ang_vel=library.get("ang_vel", "world"), stream=st, link_body_lists=[names] * nclip)
+            self.library._kinematics = km         # the robot of these clips: body_state() needs no kinematics argument
         buf = self.pool.take(total)
         # (the address, not ctypes.cast: a cast leaves the buffer referring to itself, and only the cycle collector would
         #  hand the block back)
@@ -561,6 +562,7 @@ class ClipRetargeter:
         if self._library_mode is not None:      # (host post-processing: the arrays are on the host, so they go up once)
             from .motion_library import MotionLibrary
             self.library = MotionLibrary.from_motions(out, self._library_mode)
+            self.library._kinematics = self._km
         return out
 
     def _finish_device(self, fps: Sequence[float], lens: np.ndarray) -> List[Dict]:

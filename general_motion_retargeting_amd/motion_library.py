@@ -6,7 +6,8 @@ finite-difference velocities, the angular velocity through one pair of scipy ``R
 derivatives and statistics are computed by two kernels when the library is filled, and :meth:`MotionLibrary.sample` answers
 N ``(clip, time)`` queries in one launch.
 
-* :class:`MotionLibrary` -- the batched interface (``from_motions``, ``from_files``, ``sample``, ``sample_dev``, ``clip``), and
+* :class:`MotionLibrary` -- the batched interface (``from_motions``, ``from_files``, ``sample``, ``sample_dev``, ``body_state``,
+  ``body_state_dev``, ``clip``), and
   with a directory as its argument the reference's class of the same name (``sample_motion``, ``get_motion_names``);
 * :class:`MotionLoader` -- the reference's per-file class (attribute and method names kept, NumPy instead of torch), a one-clip
   library underneath.
@@ -35,6 +36,8 @@ ARRAY_IDS = {"root_pos": 0, "root_rot": 1, "dof_pos": 2, "local_body_pos": 3, "r
              "stats": 7, "seg_start": 8, "fps": 9}
 STAT_ROWS = ("mean", "std", "min", "max")
 SAMPLE_FIELDS = ("root_pos", "root_rot", "root_vel", "root_ang_vel", "dof_pos", "dof_vel", "local_body_pos")
+STATE_FIELDS = SAMPLE_FIELDS[:6]                                        # what body_state shares with sample
+BODY_FIELDS = {"body_pos": 3, "body_rot": 4, "body_vel": 3, "body_ang_vel": 3}      # floats per body
 
 
 def _dev_ptr(x, what: str, dtype: str, count: int):
@@ -189,6 +192,7 @@ class MotionLibrary:
         self.motion_names = list(names) if names is not None else [f"clip{k}" for k in range(self.num_clips)]
         self.link_body_lists = list(link_body_lists) if link_body_lists is not None else [[] for _ in range(self.num_clips)]
         self.has_local_body_pos = False
+        self._kinematics = self._fk = None          # attach_kinematics(): the robot body_state() walks
         self._host: Dict[str, np.ndarray] = {}
         self._views: Dict[int, ClipView] = {}
         self._loaders: Dict[str, "MotionLoader"] = {}
@@ -296,6 +300,101 @@ class MotionLibrary:
         ptrs = [_dev_ptr(given[k], k, "float32", N * count[k]) for k in SAMPLE_FIELDS]
         _lib.check(_lib.lib().gmr_motion_sample_dev(self.handle, N, _dev_ptr(d_clip, "clip", "int32", N), _dev_ptr(d_time, "time", "float64", N),
                                                     LOOP if loop else 0, *ptrs, _dev_ptr(status, "status", "int32", N), _lib._s(stream)))
+
+    # ---- per-body state --------------------------------------------------------------------------------
+    def attach_kinematics(self, kinematics) -> "MotionLibrary":
+        """The robot of this library, a ``KinematicsModel`` or an ``_lib.FkHandle``: :meth:`body_state` walks its tree when it is
+        not handed one.  A library handed over by the dataset driver has it attached."""
+        ndof = kinematics.num_dof if hasattr(kinematics, "body_names") else kinematics.ndof
+        if int(ndof) != self.ndof:
+            raise ValueError(f"the kinematics has {int(ndof)} dofs, the library {self.ndof}")
+        self._kinematics = kinematics
+        return self
+
+    def _resolve_kinematics(self, kinematics):
+        """``(fk handle, body names or None)`` of ``kinematics`` or of the attached one; the checks that need no device"""
+        if self.ang_vel != "world":
+            raise ValueError(f'body_state needs a library built with ang_vel="world": the root_ang_vel of ang_vel="{self.ang_vel}" is '
+                             "not a physical angular velocity (DESIGN.md section 6h) and cannot be carried through the tree")
+        km = self._kinematics if kinematics is None else kinematics
+        if km is None:
+            raise ValueError("body_state needs the robot: pass kinematics= (a KinematicsModel or an _lib.FkHandle) or call "
+                             "attach_kinematics() once")
+        names = getattr(km, "body_names", None)
+        ndof = km.num_dof if names is not None else km.ndof
+        if int(ndof) != self.ndof:
+            raise ValueError(f"the kinematics has {int(ndof)} dofs, the library {self.ndof}")
+        return km, (list(names) if names is not None else None)
+
+    @staticmethod
+    def _body_selection(bodies, names, nbody: int):
+        """``bodies`` (``None`` | indices | names) -> ``(i32 array or None, nsel)``"""
+        from . import _lib
+        if bodies is None:
+            return None, nbody
+        sel = []
+        for b in bodies:
+            if isinstance(b, str):
+                if names is None or b not in names:
+                    raise KeyError(f"unknown body {b!r}")
+                sel.append(names.index(b))
+            else:
+                sel.append(int(b))
+        if not 1 <= len(sel) <= _lib.FK_MAX_BODIES:
+            raise ValueError(f"a selection holds 1 to {_lib.FK_MAX_BODIES} bodies, got {len(sel)}")
+        for b in sel:
+            if not 0 <= b < nbody:
+                raise ValueError(f"body {b} outside [0, {nbody})")
+        if len(set(sel)) != len(sel):
+            raise ValueError("a selection names every body once")
+        return np.array(sel, dtype=np.int32), len(sel)
+
+    def _body_state_setup(self, kinematics, bodies):
+        km, names = self._resolve_kinematics(kinematics)
+        nbody = len(names) if names is not None else km.nbody
+        sel, nsel = self._body_selection(bodies, names, nbody)
+        fk = km.hip_handle if names is not None else km
+        return fk, sel, nsel
+
+    def body_state(self, clip_ids, times, kinematics=None, loop: bool = True, bodies=None, state: bool = True) -> Dict[str, np.ndarray]:
+        """N queries in one launch -> world-frame ``body_pos [N,nsel,3]``, ``body_rot [N,nsel,4]`` xyzw, ``body_vel``,
+        ``body_ang_vel [N,nsel,3]`` of every body (``bodies=None``) or of the bodies named by index or by name, in that order, plus
+        ``status``; with ``state`` also the six arrays of :meth:`sample` (same bits).  The pose is the float32 FK of the sampled
+        state, the velocities are the library's ``root_vel / root_ang_vel / dof_vel`` carried through the tree."""
+        from . import _lib
+        fk, sel, nsel = self._body_state_setup(kinematics, bodies)
+        times = np.ascontiguousarray(times, dtype=np.float64).reshape(-1)
+        clip_ids = np.ascontiguousarray(np.broadcast_to(np.asarray(clip_ids), times.shape), dtype=np.int32)
+        N = len(times)
+        widths = {"root_pos": (3,), "root_rot": (4,), "root_vel": (3,), "root_ang_vel": (3,), "dof_pos": (self.ndof,), "dof_vel": (self.ndof,)}
+        out = {k: np.empty((N,) + widths[k], dtype=np.float32) for k in STATE_FIELDS} if state else {}
+        for k, w in BODY_FIELDS.items():
+            out[k] = np.empty((N, nsel, w), dtype=np.float32)
+        out["status"] = np.zeros(N, dtype=np.int32)
+        table = _lib.BodyStateOut(**{k: out[k].ctypes.data for k in out})
+        _lib.check(_lib.lib().gmr_motion_body_state(self.handle, fk.handle, N, _lib._ptr(clip_ids), _lib._ptr(times), LOOP if loop else 0,
+                                                    _lib._ptr(sel), nsel, C.byref(table)))
+        return out
+
+    def body_state_dev(self, N: int, d_clip, d_time, kinematics=None, loop: bool = True, bodies=None, stream=None, **outputs) -> None:
+        """The same on device memory, asynchronous on ``stream``: ``outputs`` names whichever of ``root_pos, root_rot, root_vel,
+        root_ang_vel, dof_pos, dof_vel, body_pos, body_rot, body_vel, body_ang_vel, status`` are wanted, each a ``_lib.DeviceBuffer``, a
+        raw address or an object with ``data_ptr()``, checked as :meth:`sample_dev` checks them."""
+        from . import _lib
+        fk, sel, nsel = self._body_state_setup(kinematics, bodies)
+        N = int(N)
+        count = {"root_pos": 3, "root_rot": 4, "root_vel": 3, "root_ang_vel": 3, "dof_pos": self.ndof, "dof_vel": self.ndof, "status": 1}
+        count.update({k: nsel * w for k, w in BODY_FIELDS.items()})
+        unknown = sorted(set(outputs) - set(count))
+        if unknown:
+            raise TypeError(f"body_state_dev: unknown outputs {unknown}")
+        table = _lib.BodyStateOut()
+        for k, x in outputs.items():
+            p = _dev_ptr(x, k, "int32" if k == "status" else "float32", N * count[k])
+            setattr(table, k, None if p is None else p.value)
+        _lib.check(_lib.lib().gmr_motion_body_state_dev(self.handle, fk.handle, N, _dev_ptr(d_clip, "clip", "int32", N),
+                                                        _dev_ptr(d_time, "time", "float64", N), LOOP if loop else 0, _lib._ptr(sel), nsel,
+                                                        C.byref(table), _lib._s(stream)))
 
     # ---- the reference's MotionLibrary surface (motion_loader.py:300-312) ----------------------------------------------------
     def sample_motion(self, motion_name: Optional[str] = None) -> "MotionLoader":

@@ -446,6 +446,32 @@ int gmr_motion_sample(const gmr_motion_lib_t* lib, int N, const int32_t* clip, c
                       float* root_rot, float* root_vel, float* root_ang_vel, float* dof_pos, float* dof_vel,
                       float* local_body_pos, int32_t* status);   /* host buffers; synchronises */
 
+/* Per-body state per query: one launch samples N (clip, time) queries as gmr_motion_sample_dev does and walks the FK tree
+ * of `fk` on the sampled state.  All outputs float32, world frame, rows in the order of the selection:
+ *   body_pos [N][nsel][3], body_rot [N][nsel][4] xyzw   the float32 FK of (root_pos, root_rot, dof_pos) as gmr_fk_batch_dev
+ *                                                      computes it (the same per-body code: bit-equal)
+ *   body_vel [N][nsel][3]      velocity of the body frame's origin:  v_0 = root_vel,      v_b = v_p + w_p x (p_b - p_p)
+ *   body_ang_vel [N][nsel][3]  angular velocity of the body:         w_0 = root_ang_vel,  w_b = w_p + (R_b a_b) dof_vel[dof of b]
+ *                              (p: the parent, a_b: the normalised hinge axis, R_b: the body's world rotation; w_b = w_p for a
+ *                              body without a hinge)
+ * and the six arrays of the sampler, bit-equal to gmr_motion_sample_dev's.  The velocities are the library's own (backward
+ * differences, lerped) carried through the tree, not a derivative of the interpolated pose.  Any output pointer may be NULL
+ * and is skipped.  body_sel: HOST array i32[nsel] of distinct bodies in [0, nbody), 1 <= nsel <= 64, in any order, or NULL
+ * for all bodies in tree order (nsel is then ignored); it is validated here and travels as a kernel argument.  A bad query
+ * (as in the sampler): every requested row of it NaN, status[i] = 1, nothing of the library read.  GMR_ERR_ARG when the
+ * library was filled with GMR_MOTION_ANGVEL_REFERENCE (that root_ang_vel is not a physical angular velocity: propagating it
+ * through the tree would be meaningless) and when fk's ndof is not the library's.  Asynchronous on `stream`; no device
+ * scratch, nothing of either handle is written: calls on different streams may be in flight together. */
+typedef struct {            /* device pointers (gmr_motion_body_state: host pointers), each may be NULL */
+  float *root_pos, *root_rot, *root_vel, *root_ang_vel, *dof_pos, *dof_vel;   /* = gmr_motion_sample_dev, same bits */
+  float *body_pos, *body_rot, *body_vel, *body_ang_vel;                        /* [N][nsel][3|4|3|3], world frame    */
+  int32_t* status;                                                            /* [N]                                */
+} gmr_body_state_out_t;
+int gmr_motion_body_state_dev(const gmr_motion_lib_t* lib, gmr_fk_t* fk, int N, const int32_t* d_clip, const double* d_time,
+                              int flags, const int32_t* body_sel, int nsel, const gmr_body_state_out_t* out, void* stream);
+int gmr_motion_body_state(const gmr_motion_lib_t* lib, gmr_fk_t* fk, int N, const int32_t* clip, const double* time, int flags,
+                          const int32_t* body_sel, int nsel, const gmr_body_state_out_t* out);   /* host buffers; synchronises */
+
 /* ---- multi-GPU: one rank per GPU, ONE broadcast, no per-step collective ------------ */
 /* The reference parallelises over files with mp.Pool on one CPU (scripts/smplx_to_robot_dataset.py:241-242); here
  * streams shard over the ranks of one node and the only data that crosses ranks is the packed robot model + task set.
