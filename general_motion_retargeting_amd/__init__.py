@@ -10,6 +10,7 @@ from .motion_retarget import GeneralMotionRetargeting, TargetNotSet
 from .data_loader import load_robot_motion, save_robot_motion
 from .kinematics_model import KinematicsModel
 from .motion_library import MotionLibrary, MotionLoader
+from .motion_tracker import MotionTracker
 from . import dataset, sharding, synth
 
 
@@ -20,4 +21,4 @@ class RobotMotionViewer:  # pragma: no cover - out of scope (GUI), kept so impor
 
 __all__ = ["IK_CONFIG_ROOT", "ASSET_ROOT", "ROBOT_XML_DICT", "IK_CONFIG_DICT", "ROBOT_BASE_DICT",
            "VIEWER_CAM_DISTANCE_DICT", "GeneralMotionRetargeting", "TargetNotSet", "KinematicsModel",
-           "RobotMotionViewer", "load_robot_motion", "save_robot_motion", "MotionLibrary", "MotionLoader"]
+           "RobotMotionViewer", "load_robot_motion", "save_robot_motion", "MotionLibrary", "MotionLoader", "MotionTracker"]

@@ -111,6 +111,18 @@ _SIGS = {
     "gmr_motion_body_state_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                             C.c_void_p, C.c_void_p]),
     "gmr_motion_body_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "gmr_motion_tracker_create": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_uint64, C.POINTER(C.c_void_p)]),
+    "gmr_motion_tracker_destroy": (C.c_int, [C.c_void_p]),
+    "gmr_motion_tracker_set_dof_map": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gmr_motion_tracker_set_terms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gmr_motion_tracker_assign_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gmr_motion_tracker_assign": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "gmr_motion_tracker_reset_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_void_p]),
+    "gmr_motion_tracker_reset": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_int)]),
+    "gmr_motion_tracker_step_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gmr_motion_tracker_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gmr_motion_tracker_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
     "gmr_comm_create": (C.c_int, [C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),
     "gmr_comm_destroy": (C.c_int, [C.c_void_p]),
     "gmr_comm_rank": (C.c_int, [C.c_void_p]),
@@ -528,6 +540,23 @@ FK_MAX_BODIES = 64
 class BodyStateOut(C.Structure):
     """``gmr_body_state_out_t``: the outputs of ``gmr_motion_body_state[_dev]``, each an address or NULL"""
     _fields_ = [(k, C.c_void_p) for k in BODY_STATE_FIELDS]
+
+
+TRACKER_OUT_FIELDS = ("ref_root_pos", "ref_root_rot", "ref_root_vel", "ref_root_ang_vel", "ref_dof_pos", "ref_dof_vel", "err", "term", "total",
+                      "status", "finished")
+TRACKER_SIM_FIELDS = ("base_pos", "base_quat", "base_lin_vel", "base_ang_vel", "dof_pos", "dof_vel")
+TRACKER_MAX_DOF = 64
+TRACKER_TERMS = 6
+
+
+class TrackerOut(C.Structure):
+    """``gmr_tracker_out_t``: the outputs of ``gmr_motion_tracker_step[_dev]``, each an address or NULL"""
+    _fields_ = [(k, C.c_void_p) for k in TRACKER_OUT_FIELDS]
+
+
+class TrackerSim(C.Structure):
+    """``gmr_tracker_sim_t``: the simulator state of ``gmr_motion_tracker_step[_dev]``, each an address or NULL"""
+    _fields_ = [(k, C.c_void_p) for k in TRACKER_SIM_FIELDS]
 
 
 class FkHandle:

@@ -1,5 +1,6 @@
 // gmr_handles.h -- the handles of the C-ABI that more than one translation unit of libgmrhip.so looks into (not part of the
-// C-ABI): the FK tree (created in gmr_abi.hip) and the motion library (gmr_motion.hip), both read by gmr_body_state.hip.
+// C-ABI): the FK tree (created in gmr_abi.hip) and the motion library (gmr_motion.hip), both read by gmr_body_state.hip, and
+// the motion tracker (gmr_tracker.hip), which is bound to a library.
 #pragma once
 #include <stdint.h>
 
@@ -32,4 +33,35 @@ struct gmr_motion_lib {
   int filled = 0;                // 1 once a fill has been enqueued
   int has_body = 0;              // the fill was given local_body_pos
   int reference_angvel = 0;      // the fill was asked for GMR_MOTION_ANGVEL_REFERENCE: root_ang_vel is not a physical angular velocity
+};
+
+namespace gmr {
+constexpr int TRACKER_MAX_DOF = 64;   // robot dofs of a tracker
+constexpr int TRACKER_TERMS = 6;      // root pos, root rot, root vel, root ang vel, dof pos, dof vel
+// what every workgroup of a step reads alike; travels as a kernel argument, so replacing it never touches a launch in flight
+struct TrackerTables {
+  int32_t R;                          // robot dofs
+  int8_t map[TRACKER_MAX_DOF];        // robot dof j <- column map[j] of the library, -1: dof_default[j] / velocity 0
+  float dof_default[TRACKER_MAX_DOF], dof_weight[TRACKER_MAX_DOF];
+  float scale[TRACKER_TERMS], weight[TRACKER_TERMS];
+};
+// the tracker's own device memory (one block)
+struct TrackerState {
+  int32_t* clip;       // [N]
+  float *time, *length;   // [N] the clock and (float)(T / fps) of the assigned clip (0 for a clip id outside [0, C))
+  uint32_t* draws;     // [N] Philox draws made for the environment so far
+  uint32_t* ignored;   // [1] environment ids outside [0, N) met by reset / assign since creation
+  const double* cdf;   // [C] with clip weights: cdf[k] = (w_0 + .. + w_{k-1}) / sum, else null
+};
+}  // namespace gmr
+
+struct gmr_motion_tracker {
+  const gmr_motion_lib* lib;     // not owned: the library outlives its trackers
+  int N, loop;
+  float dtf;                     // (float)dt: the clock is float32
+  uint32_t key[2];               // the seed, low word first
+  gmr::TrackerTables tab;
+  gmr::TrackerState S;
+  gmr::DeviceBlock block;
+  std::mutex mu;                 // the tables, and the whole of every synchronous entry point
 };

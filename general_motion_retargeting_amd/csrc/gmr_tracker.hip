@@ -1,0 +1,526 @@
+// gmr_tracker.hip -- the motion tracker: what an imitation environment does with the motion library every step (reference
+// booster_gym/envs/t1_imitation.py:103-235, 249-309), for N environments and on the device.
+//
+//   tracker_step_kernel     ONE launch per environment step, the sampler's shape (16 lanes per environment, 16 environments per
+//                           workgroup): the query of gmr_motion_sample.h at the environment's own (clip, clock), the reference
+//                           rows with the dofs in robot order, the six tracking errors and terms against the simulator's
+//                           state, the float32 clock advance and, without loop, the redraw of a finished clip
+//   tracker_reset_kernel    _reset_idx (:215-235): one lane per listed environment, one Philox draw each
+//   tracker_assign_kernel   (clip, time) set explicitly, one lane per listed environment
+//
+// The kernels write the tracker's own state and nothing else of either handle: a tracker is single-stream (include/gmr_hip.h).
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include <cmath>
+#include <mutex>
+#include <new>
+
+#include "../../include/gmr_hip.h"
+#include "gmr_handles.h"
+#include "gmr_internal.h"
+#include "gmr_motion_sample.h"
+#include "gmr_philox.h"
+#include "gmr_workspace.h"
+
+// one rounding per operation, as in the sampler whose bits the reference rows reproduce
+#pragma clang fp contract(off)
+
+namespace gmr {
+
+struct TrackerSim {
+  const float *base_pos, *base_quat, *base_lin_vel, *base_ang_vel, *dof_pos, *dof_vel;
+};
+struct TrackerOut {
+  float *ref_root_pos, *ref_root_rot, *ref_root_vel, *ref_root_ang_vel, *ref_dof_pos, *ref_dof_vel, *err, *term, *total;
+  int32_t *status, *finished;
+};
+
+// (float)(T / fps) of clip c; 0 for a clip id outside [0, C)
+__device__ __forceinline__ float clip_length(const MotionArrays& A, int c) {
+  if (c < 0 || c >= A.C) return 0.0f;
+  return (float)((double)(A.seg_start[c + 1] - A.seg_start[c]) / A.fps[c]);
+}
+
+// One draw for environment e: counter (e, draws[e], 0, 0), after which draws[e] is one more.  With want_clip, *clip is set
+// from word 0; the return value is u of word 1.
+__device__ __forceinline__ float tracker_draw(const MotionArrays& A, const TrackerState& S, uint32_t key0, uint32_t key1, int e,
+                                              bool want_clip, int* clip) {
+  const uint32_t ctr[4] = {(uint32_t)e, S.draws[e], 0u, 0u}, key[2] = {key0, key1};
+  uint32_t w[4];
+  philox4x32(ctr, key, w);
+  S.draws[e] = ctr[1] + 1u;
+  if (want_clip) {
+    if (S.cdf) {
+      // the largest k with cdf[k] <= x (cdf[0] = 0 <= x always)
+      const double x = (double)w[0] * 2.3283064365386963e-10;
+      int lo = 0, hi = A.C - 1;
+      while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (S.cdf[mid] <= x) lo = mid; else hi = mid - 1;
+      }
+      *clip = lo;
+    } else {
+      *clip = philox_below(w[0], A.C);
+    }
+  }
+  return philox_unit(w[1]);
+}
+
+// the sum over the 16 lanes of an environment, in every one of them
+__device__ __forceinline__ float group_sum(float x) {
+#pragma unroll
+  for (int m = 1; m < MOTION_GROUP; m <<= 1) x = x + __shfl_xor(x, m, MOTION_GROUP);
+  return x;
+}
+
+// Lanes l < 3 (l < 4) of an environment hold component l of the root rows, as in the sampler; all 16 stride over the robot
+// dofs.  Each lane squares what it holds, the six sums of an environment are butterflies over its 16-lane row, and lane 0
+// writes the terms, the flags and the new clock.  The dof tables are the same for every environment: they come in as a kernel
+// argument and are staged in LDS once per workgroup.
+__global__ __launch_bounds__(256) void tracker_step_kernel(const MotionArrays A, const TrackerState S, const TrackerTables Tb, int N, int loop,
+                                                           float dtf, uint32_t key0, uint32_t key1, const TrackerSim X, const TrackerOut O) {
+  __shared__ int s_map[TRACKER_MAX_DOF];
+  __shared__ float s_def[TRACKER_MAX_DOF], s_w[TRACKER_MAX_DOF];
+  if (threadIdx.x < TRACKER_MAX_DOF) {
+    s_map[threadIdx.x] = Tb.map[threadIdx.x];
+    s_def[threadIdx.x] = Tb.dof_default[threadIdx.x];
+    s_w[threadIdx.x] = Tb.dof_weight[threadIdx.x];
+  }
+  __syncthreads();
+  const int e = (blockIdx.x * 256 + threadIdx.x) / MOTION_GROUP;
+  const int l = threadIdx.x & (MOTION_GROUP - 1);
+  if (e >= N) return;
+  const int R = Tb.R, ndof = A.ndof;
+  const int c = S.clip[e];
+  const float tf = S.time[e];
+  const MotionQuery Q = motion_query(A, c, (double)tf, loop);      // (gmr_motion_sample.h)
+  const bool terms = O.err || O.term || O.total;
+  if (!Q.ok) {
+    // neutralised: NaN rows, nothing of the library is read, the clock stays
+    const float nan = NAN;
+    if (l < 3) {
+      if (O.ref_root_pos) O.ref_root_pos[(size_t)e * 3 + l] = nan;
+      if (O.ref_root_vel) O.ref_root_vel[(size_t)e * 3 + l] = nan;
+      if (O.ref_root_ang_vel) O.ref_root_ang_vel[(size_t)e * 3 + l] = nan;
+    }
+    if (l < 4 && O.ref_root_rot) O.ref_root_rot[(size_t)e * 4 + l] = nan;
+    for (int j = l; j < R; j += MOTION_GROUP) {
+      if (O.ref_dof_pos) O.ref_dof_pos[(size_t)e * R + j] = nan;
+      if (O.ref_dof_vel) O.ref_dof_vel[(size_t)e * R + j] = nan;
+    }
+    if (l < TRACKER_TERMS) {
+      if (O.err) O.err[(size_t)e * TRACKER_TERMS + l] = nan;
+      if (O.term) O.term[(size_t)e * TRACKER_TERMS + l] = nan;
+    }
+    if (l == 0) {
+      if (O.total) O.total[e] = nan;
+      if (O.status) O.status[e] = 1;
+      if (O.finished) O.finished[e] = 0;
+    }
+    return;
+  }
+  const bool same = Q.same;
+  const size_t rl = Q.rl, rh = Q.rh;
+  const float w0 = Q.w0, w1 = Q.w1;
+  float acc[TRACKER_TERMS] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};      // this lane's share of the six sums
+  if (l < 3) {
+    const float p = lerp1(A.root_pos, rl * 3 + l, rh * 3 + l, same, w0, w1);
+    const float v = lerp1(A.root_vel, rl * 3 + l, rh * 3 + l, same, w0, w1);
+    const float w = lerp1(A.root_ang_vel, rl * 3 + l, rh * 3 + l, same, w0, w1);
+    if (O.ref_root_pos) O.ref_root_pos[(size_t)e * 3 + l] = p;
+    if (O.ref_root_vel) O.ref_root_vel[(size_t)e * 3 + l] = v;
+    if (O.ref_root_ang_vel) O.ref_root_ang_vel[(size_t)e * 3 + l] = w;
+    if (terms) {
+      if (X.base_pos) { const float d = X.base_pos[(size_t)e * 3 + l] - p; acc[0] = d * d; }
+      if (X.base_lin_vel) { const float d = X.base_lin_vel[(size_t)e * 3 + l] - v; acc[2] = d * d; }
+      if (X.base_ang_vel) { const float d = X.base_ang_vel[(size_t)e * 3 + l] - w; acc[3] = d * d; }
+    }
+  }
+  if (l < 4 && (O.ref_root_rot || (terms && X.base_quat))) {
+    const float q = slerp1(A.root_rot, rl, rh, l, same, w0, w1);
+    if (O.ref_root_rot) O.ref_root_rot[(size_t)e * 4 + l] = q;
+    if (terms && X.base_quat) acc[1] = X.base_quat[(size_t)e * 4 + l] * q;      // <q, q_ref> = the w of conj(q) * q_ref
+  }
+  for (int j = l; j < R; j += MOTION_GROUP) {
+    const int m = s_map[j];
+    float p = s_def[j], v = 0.0f;
+    if (m >= 0) {
+      p = lerp1(A.dof_pos, rl * ndof + m, rh * ndof + m, same, w0, w1);
+      v = lerp1(A.dof_vel, rl * ndof + m, rh * ndof + m, same, w0, w1);
+    }
+    if (O.ref_dof_pos) O.ref_dof_pos[(size_t)e * R + j] = p;
+    if (O.ref_dof_vel) O.ref_dof_vel[(size_t)e * R + j] = v;
+    if (terms) {
+      if (X.dof_pos) { const float d = s_w[j] * (X.dof_pos[(size_t)e * R + j] - p); acc[4] = acc[4] + d * d; }
+      if (X.dof_vel) { const float d = s_w[j] * (X.dof_vel[(size_t)e * R + j] - v); acc[5] = acc[5] + d * d; }
+    }
+  }
+  if (terms) {
+#pragma unroll
+    for (int k = 0; k < TRACKER_TERMS; k++) acc[k] = group_sum(acc[k]);
+    if (l == 0) {
+      const bool given[TRACKER_TERMS] = {X.base_pos != nullptr, X.base_quat != nullptr, X.base_lin_vel != nullptr,
+                                         X.base_ang_vel != nullptr, X.dof_pos != nullptr, X.dof_vel != nullptr};
+      float total = 0.0f;
+#pragma unroll
+      for (int k = 0; k < TRACKER_TERMS; k++) {
+        float err = 0.0f, term = 0.0f;
+        if (given[k]) {
+          if (k == 1) {
+            float a = fabsf(acc[1]);
+            a = a > 1.0f ? 1.0f : a;                 // (a NaN stays one, as torch.clamp leaves it)
+            err = 2.0f * acosf(a);
+          } else {
+            err = __fsqrt_rn(acc[k]);
+          }
+          term = expf(-__fdiv_rn(err, Tb.scale[k]));
+          if (Tb.weight[k] != 0.0f) total = total + Tb.weight[k] * term;
+        }
+        if (O.err) O.err[(size_t)e * TRACKER_TERMS + k] = err;
+        if (O.term) O.term[(size_t)e * TRACKER_TERMS + k] = term;
+      }
+      if (O.total) O.total[e] = total;
+    }
+  }
+  if (l == 0) {
+    float tn = tf + dtf;                                             // :198, a float32 tensor += dt
+    int finished = 0;
+    if (!loop && tn >= S.length[e]) {                                // :201-213
+      int nc = c;
+      (void)tracker_draw(A, S, key0, key1, e, true, &nc);
+      S.clip[e] = nc;
+      S.length[e] = clip_length(A, nc);
+      tn = 0.0f;
+      finished = 1;
+    }
+    S.time[e] = tn;
+    if (O.status) O.status[e] = 0;
+    if (O.finished) O.finished[e] = finished;
+  }
+}
+
+// the environment of lane i of a reset / assign: ids[i], or i itself without a list; -1 (and counted) outside [0, N)
+__device__ __forceinline__ int tracker_env(const TrackerState& S, const int32_t* __restrict__ ids, int i, int N) {
+  const int e = ids ? ids[i] : i;
+  if (e >= 0 && e < N) return e;
+  atomicAdd(S.ignored, 1u);
+  return -1;
+}
+
+__global__ __launch_bounds__(256) void tracker_reset_kernel(const MotionArrays A, const TrackerState S, int N, int n,
+                                                            const int32_t* __restrict__ ids, int resample, float lo, float hi, uint32_t key0,
+                                                            uint32_t key1) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int e = tracker_env(S, ids, i, N);
+  if (e < 0) return;
+  int c = 0;
+  const float u = tracker_draw(A, S, key0, key1, e, resample != 0, &c);
+  if (resample) {
+    S.clip[e] = c;
+    S.length[e] = clip_length(A, c);
+  }
+  S.time[e] = lo + (hi - lo) * u;          // :232-234
+}
+
+// clip == null: clip 0 at time 0 (how a tracker starts)
+__global__ __launch_bounds__(256) void tracker_assign_kernel(const MotionArrays A, const TrackerState S, int N, int n,
+                                                             const int32_t* __restrict__ ids, const int32_t* __restrict__ clip,
+                                                             const float* __restrict__ time) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int e = tracker_env(S, ids, i, N);
+  if (e < 0) return;
+  const int c = clip ? clip[i] : 0;
+  S.clip[e] = c;
+  S.time[e] = clip ? time[i] : 0.0f;
+  S.length[e] = clip_length(A, c);
+}
+
+// the dof tables of a tracker from the caller's host arrays, validated; the terms of T are left as they are
+static int tracker_tables(const gmr_motion_lib* lib, int R, const int32_t* dof_map, const float* dof_default, const float* dof_weight,
+                          TrackerTables* T) {
+  const int ndof = lib->A.ndof;
+  if (R < 1 || R > TRACKER_MAX_DOF) return gmr_fail(GMR_ERR_ARG, "R = %d robot dofs outside [1, %d]", R, TRACKER_MAX_DOF);
+  if (!dof_map && R != ndof) return gmr_fail(GMR_ERR_ARG, "the identity map needs R = ndof (R = %d, ndof = %d)", R, ndof);
+  for (int j = 0; j < R; j++) {
+    const int m = dof_map ? dof_map[j] : j;
+    if (m < -1 || m >= ndof || m > INT8_MAX) return gmr_fail(GMR_ERR_ARG, "dof_map[%d] = %d outside [-1, %d)", j, m, ndof <= INT8_MAX ? ndof : INT8_MAX + 1);
+    if (dof_default && !std::isfinite(dof_default[j])) return gmr_fail(GMR_ERR_ARG, "dof_default[%d] is not finite", j);
+    if (dof_weight && !std::isfinite(dof_weight[j])) return gmr_fail(GMR_ERR_ARG, "dof_weight[%d] is not finite", j);
+  }
+  for (int j = 0; j < TRACKER_MAX_DOF; j++) {
+    const bool on = j < R;
+    T->map[j] = (int8_t)(on ? (dof_map ? dof_map[j] : j) : -1);
+    T->dof_default[j] = on && dof_default ? dof_default[j] : 0.0f;
+    T->dof_weight[j] = on ? (dof_weight ? dof_weight[j] : 1.0f) : 0.0f;
+  }
+  T->R = R;
+  return GMR_OK;
+}
+
+static dim3 one_lane_each(int n) { return dim3((unsigned)((n + 255) / 256)); }
+
+// what the two step entry points share once the tables are in hand
+static int tracker_step_launch(gmr_motion_tracker* t, const TrackerTables& T, const gmr_tracker_sim_t* sim, const gmr_tracker_out_t* out,
+                               hipStream_t stream) {
+  if (!sim && (out->err || out->term || out->total)) return gmr_fail(GMR_ERR_ARG, "err / term / total need the simulator's state");
+  const TrackerSim X = sim ? TrackerSim{sim->base_pos, sim->base_quat, sim->base_lin_vel, sim->base_ang_vel, sim->dof_pos, sim->dof_vel}
+                           : TrackerSim{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  const TrackerOut O{out->ref_root_pos, out->ref_root_rot, out->ref_root_vel, out->ref_root_ang_vel, out->ref_dof_pos, out->ref_dof_vel,
+                     out->err, out->term, out->total, out->status, out->finished};
+  const int per_block = 256 / MOTION_GROUP;
+  hipLaunchKernelGGL(tracker_step_kernel, dim3((unsigned)((t->N + per_block - 1) / per_block)), dim3(256), 0, stream, t->lib->A, t->S, T, t->N,
+                     t->loop, t->dtf, t->key[0], t->key[1], X, O);
+  GMR_HIP_TRY(hipGetLastError());
+  return GMR_OK;
+}
+
+// the ids outside [0, N) counted so far (synchronous)
+static int tracker_ignored(const gmr_motion_tracker* t, uint32_t* value) {
+  GMR_HIP_TRY(hipMemcpy(value, t->S.ignored, 4, hipMemcpyDeviceToHost));
+  return GMR_OK;
+}
+
+}  // namespace gmr
+
+// ---- C-ABI (include/gmr_hip.h, "motion tracker") ----------------------------------------------------------------------------
+
+extern "C" {
+
+int gmr_motion_tracker_create(const gmr_motion_lib_t* lib, int N, double dt, int flags, int R, const int32_t* dof_map,
+                              const float* dof_default, const float* dof_weight, const double* clip_weights, uint64_t seed,
+                              gmr_motion_tracker_t** out) {
+  if (!out) return gmr_fail(GMR_ERR_ARG, "gmr_motion_tracker_create: null out pointer");
+  *out = nullptr;
+  if (!lib) return gmr_fail(GMR_ERR_ARG, "null motion library");
+  if (!lib->filled) return gmr_fail(GMR_ERR_ARG, "the motion library has not been filled");
+  if (flags & ~GMR_MOTION_LOOP) return gmr_fail(GMR_ERR_ARG, "unknown tracker flag bits 0x%x", flags);
+  if (N < 1 || N > (1 << 26)) return gmr_fail(GMR_ERR_ARG, "N = %d environments out of range", N);
+  if (!std::isfinite(dt) || !std::isfinite((float)dt)) return gmr_fail(GMR_ERR_ARG, "dt = %g is not finite", dt);
+  const int C = lib->A.C;
+  double sum = 0.0;
+  if (clip_weights) {
+    for (int c = 0; c < C; c++) {
+      if (!(clip_weights[c] >= 0.0) || !std::isfinite(clip_weights[c]))
+        return gmr_fail(GMR_ERR_ARG, "clip_weights[%d] = %g, must be finite and not negative", c, clip_weights[c]);
+      sum += clip_weights[c];
+    }
+    if (!(sum > 0.0) || !std::isfinite(sum)) return gmr_fail(GMR_ERR_ARG, "the clip weights sum to %g", sum);
+  }
+  gmr_motion_tracker* t = new (std::nothrow) gmr_motion_tracker;
+  if (!t) return gmr_fail(GMR_ERR_ARG, "out of host memory");
+  const int rc = gmr::tracker_tables(lib, R, dof_map, dof_default, dof_weight, &t->tab);
+  if (rc != GMR_OK) {
+    delete t;
+    return rc;
+  }
+  const float scale[gmr::TRACKER_TERMS] = {0.5f, 0.5f, 2.0f, 1.0f, 1.0f, 0.1f};      // T1Imitation.yaml:327-332
+  for (int k = 0; k < gmr::TRACKER_TERMS; k++) { t->tab.scale[k] = scale[k]; t->tab.weight[k] = 1.0f; }
+  t->lib = lib; t->N = N; t->loop = (flags & GMR_MOTION_LOOP) ? 1 : 0;
+  t->dtf = (float)dt;
+  t->key[0] = (uint32_t)seed; t->key[1] = (uint32_t)(seed >> 32);
+  const size_t n = (size_t)N;
+  gmr::Carve cv;
+  const size_t o_clip = cv.take(n * 4), o_time = cv.take(n * 4), o_len = cv.take(n * 4), o_draws = cv.take(n * 4), o_ign = cv.take(4),
+               o_cdf = cv.take(clip_weights ? (size_t)C * 8 : 0);
+  hipError_t e = t->block.reserve(cv.total() + 256);
+  char* d = t->block.data();
+  if (e == hipSuccess) e = hipMemset(d, 0, cv.total());
+  if (e == hipSuccess && clip_weights) {
+    double* cdf = new (std::nothrow) double[C];
+    if (!cdf) {
+      delete t;
+      return gmr_fail(GMR_ERR_ARG, "out of host memory");
+    }
+    double before = 0.0;
+    for (int c = 0; c < C; c++) { cdf[c] = before / sum; before += clip_weights[c]; }
+    e = hipMemcpy(d + o_cdf, cdf, (size_t)C * 8, hipMemcpyHostToDevice);
+    delete[] cdf;
+  }
+  if (e == hipSuccess) {
+    t->S = gmr::TrackerState{(int32_t*)(d + o_clip), (float*)(d + o_time), (float*)(d + o_len), (uint32_t*)(d + o_draws), (uint32_t*)(d + o_ign),
+                             clip_weights ? (const double*)(d + o_cdf) : nullptr};
+    // every environment on clip 0 at time 0; the length of clip 0 is the library's to say
+    hipLaunchKernelGGL(gmr::tracker_assign_kernel, gmr::one_lane_each(N), dim3(256), 0, nullptr, lib->A, t->S, N, N, nullptr, nullptr, nullptr);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    delete t;
+    return gmr_fail(GMR_ERR_HIP, "gmr_motion_tracker_create: %s", hipGetErrorString(e));
+  }
+  *out = t;
+  return GMR_OK;
+}
+
+int gmr_motion_tracker_destroy(gmr_motion_tracker_t* t) {
+  delete t;
+  return GMR_OK;
+}
+
+int gmr_motion_tracker_set_dof_map(gmr_motion_tracker_t* t, int R, const int32_t* dof_map, const float* dof_default, const float* dof_weight) {
+  if (!t) return gmr_fail(GMR_ERR_ARG, "null motion tracker");
+  std::lock_guard<std::mutex> g(t->mu);
+  gmr::TrackerTables T = t->tab;
+  const int rc = gmr::tracker_tables(t->lib, R, dof_map, dof_default, dof_weight, &T);
+  if (rc == GMR_OK) t->tab = T;
+  return rc;
+}
+
+int gmr_motion_tracker_set_terms(gmr_motion_tracker_t* t, const float* scale, const float* weight) {
+  if (!t) return gmr_fail(GMR_ERR_ARG, "null motion tracker");
+  for (int k = 0; k < gmr::TRACKER_TERMS; k++) {
+    if (scale && (!(scale[k] > 0.0f) || !std::isfinite(scale[k])))
+      return gmr_fail(GMR_ERR_ARG, "scale[%d] = %g, must be positive and finite", k, (double)scale[k]);
+    if (weight && !std::isfinite(weight[k])) return gmr_fail(GMR_ERR_ARG, "weight[%d] is not finite", k);
+  }
+  std::lock_guard<std::mutex> g(t->mu);
+  for (int k = 0; k < gmr::TRACKER_TERMS; k++) {
+    if (scale) t->tab.scale[k] = scale[k];
+    if (weight) t->tab.weight[k] = weight[k];
+  }
+  return GMR_OK;
+}
+
+int gmr_motion_tracker_assign_dev(gmr_motion_tracker_t* t, int n, const int32_t* d_env_ids, const int32_t* d_clip, const float* d_time,
+                                  void* stream) {
+  if (!t) return gmr_fail(GMR_ERR_ARG, "null motion tracker");
+  if (n < 0 || n > (1 << 26)) return gmr_fail(GMR_ERR_ARG, "n = %d out of range", n);
+  if (!d_env_ids && n != t->N) return gmr_fail(GMR_ERR_ARG, "without env_ids every environment is assigned: n = %d, N = %d", n, t->N);
+  if (n == 0) return GMR_OK;
+  if (!d_clip || !d_time) return gmr_fail(GMR_ERR_ARG, "null clip / time");
+  hipLaunchKernelGGL(gmr::tracker_assign_kernel, gmr::one_lane_each(n), dim3(256), 0, (hipStream_t)stream, t->lib->A, t->S, t->N, n, d_env_ids,
+                     d_clip, d_time);
+  GMR_HIP_TRY(hipGetLastError());
+  return GMR_OK;
+}
+
+int gmr_motion_tracker_reset_dev(gmr_motion_tracker_t* t, int n, const int32_t* d_env_ids, int resample, float lo, float hi, void* stream) {
+  if (!t) return gmr_fail(GMR_ERR_ARG, "null motion tracker");
+  if (!d_env_ids) n = t->N;
+  if (n < 0 || n > (1 << 26)) return gmr_fail(GMR_ERR_ARG, "n = %d out of range", n);
+  if (!std::isfinite(lo) || !std::isfinite(hi)) return gmr_fail(GMR_ERR_ARG, "time_offset_range (%g, %g) is not finite", (double)lo, (double)hi);
+  if (n == 0) return GMR_OK;
+  hipLaunchKernelGGL(gmr::tracker_reset_kernel, gmr::one_lane_each(n), dim3(256), 0, (hipStream_t)stream, t->lib->A, t->S, t->N, n, d_env_ids,
+                     resample ? 1 : 0, lo, hi, t->key[0], t->key[1]);
+  GMR_HIP_TRY(hipGetLastError());
+  return GMR_OK;
+}
+
+int gmr_motion_tracker_step_dev(gmr_motion_tracker_t* t, const gmr_tracker_sim_t* sim, const gmr_tracker_out_t* out, void* stream) {
+  if (!t) return gmr_fail(GMR_ERR_ARG, "null motion tracker");
+  if (!out) return gmr_fail(GMR_ERR_ARG, "null output table");
+  gmr::TrackerTables T;
+  {
+    std::lock_guard<std::mutex> g(t->mu);
+    T = t->tab;
+  }
+  return gmr::tracker_step_launch(t, T, sim, out, (hipStream_t)stream);
+}
+
+int gmr_motion_tracker_assign(gmr_motion_tracker_t* t, int n, const int32_t* env_ids, const int32_t* clip, const float* time, int* ignored) {
+  if (!t) return gmr_fail(GMR_ERR_ARG, "null motion tracker");
+  if (ignored) *ignored = 0;
+  if (n < 0 || n > (1 << 26)) return gmr_fail(GMR_ERR_ARG, "n = %d out of range", n);
+  if (!env_ids && n != t->N) return gmr_fail(GMR_ERR_ARG, "without env_ids every environment is assigned: n = %d, N = %d", n, t->N);
+  if (n == 0) return GMR_OK;
+  if (!clip || !time) return gmr_fail(GMR_ERR_ARG, "null clip / time");
+  std::lock_guard<std::mutex> g(t->mu);
+  const size_t nb = (size_t)n * 4;
+  gmr::Carve cv;
+  const size_t o_ids = cv.take(env_ids ? nb : 0), o_clip = cv.take(nb), o_time = cv.take(nb);
+  gmr::DeviceBlock blk;          // device scratch of this call
+  GMR_HIP_TRY(blk.reserve(cv.total()));
+  char* d = blk.data();
+  if (env_ids) GMR_HIP_TRY(hipMemcpy(d + o_ids, env_ids, nb, hipMemcpyHostToDevice));
+  GMR_HIP_TRY(hipMemcpy(d + o_clip, clip, nb, hipMemcpyHostToDevice));
+  GMR_HIP_TRY(hipMemcpy(d + o_time, time, nb, hipMemcpyHostToDevice));
+  uint32_t before = 0, after = 0;
+  int rc = gmr::tracker_ignored(t, &before);
+  if (rc == GMR_OK)
+    rc = gmr_motion_tracker_assign_dev(t, n, env_ids ? (const int32_t*)(d + o_ids) : nullptr, (const int32_t*)(d + o_clip),
+                                       (const float*)(d + o_time), nullptr);
+  if (rc != GMR_OK) return rc;
+  GMR_HIP_TRY(hipDeviceSynchronize());
+  if ((rc = gmr::tracker_ignored(t, &after)) != GMR_OK) return rc;
+  if (ignored) *ignored = (int)(after - before);
+  return GMR_OK;
+}
+
+int gmr_motion_tracker_reset(gmr_motion_tracker_t* t, int n, const int32_t* env_ids, int resample, float lo, float hi, int* ignored) {
+  if (!t) return gmr_fail(GMR_ERR_ARG, "null motion tracker");
+  if (ignored) *ignored = 0;
+  if (n < 0 || n > (1 << 26)) return gmr_fail(GMR_ERR_ARG, "n = %d out of range", n);
+  if (env_ids && n == 0) return GMR_OK;
+  std::lock_guard<std::mutex> g(t->mu);
+  gmr::DeviceBlock blk;          // device scratch of this call
+  if (env_ids) {
+    GMR_HIP_TRY(blk.reserve((size_t)n * 4));
+    GMR_HIP_TRY(hipMemcpy(blk.data(), env_ids, (size_t)n * 4, hipMemcpyHostToDevice));
+  }
+  uint32_t before = 0, after = 0;
+  int rc = gmr::tracker_ignored(t, &before);
+  if (rc == GMR_OK) rc = gmr_motion_tracker_reset_dev(t, n, env_ids ? (const int32_t*)blk.data() : nullptr, resample, lo, hi, nullptr);
+  if (rc != GMR_OK) return rc;
+  GMR_HIP_TRY(hipDeviceSynchronize());
+  if ((rc = gmr::tracker_ignored(t, &after)) != GMR_OK) return rc;
+  if (ignored) *ignored = (int)(after - before);
+  return GMR_OK;
+}
+
+int gmr_motion_tracker_step(gmr_motion_tracker_t* t, const gmr_tracker_sim_t* sim, const gmr_tracker_out_t* out) {
+  if (!t) return gmr_fail(GMR_ERR_ARG, "null motion tracker");
+  if (!out) return gmr_fail(GMR_ERR_ARG, "null output table");
+  std::lock_guard<std::mutex> g(t->mu);
+  const size_t n = (size_t)t->N, r = (size_t)t->tab.R;
+  const void* hs[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  if (sim) {
+    hs[0] = sim->base_pos; hs[1] = sim->base_quat; hs[2] = sim->base_lin_vel;
+    hs[3] = sim->base_ang_vel; hs[4] = sim->dof_pos; hs[5] = sim->dof_vel;
+  }
+  const size_t ns[6] = {n * 12, n * 16, n * 12, n * 12, n * r * 4, n * r * 4};
+  void* ho[11] = {out->ref_root_pos, out->ref_root_rot, out->ref_root_vel, out->ref_root_ang_vel, out->ref_dof_pos, out->ref_dof_vel,
+                  out->err, out->term, out->total, out->status, out->finished};
+  const size_t no[11] = {n * 12, n * 16, n * 12, n * 12, n * r * 4, n * r * 4, n * 24, n * 24, n * 4, n * 4, n * 4};
+  gmr::Carve cv;
+  size_t os[6], oo[11];
+  for (int k = 0; k < 6; k++) os[k] = cv.take(hs[k] ? ns[k] : 0);
+  for (int k = 0; k < 11; k++) oo[k] = cv.take(ho[k] ? no[k] : 0);
+  gmr::DeviceBlock blk;          // device scratch of this call
+  GMR_HIP_TRY(blk.reserve(cv.total() + 256));
+  char* d = blk.data();
+  const float* ds[6];
+  void* dv[11];
+  for (int k = 0; k < 6; k++) {
+    ds[k] = hs[k] ? (const float*)(d + os[k]) : nullptr;
+    if (hs[k]) GMR_HIP_TRY(hipMemcpy(d + os[k], hs[k], ns[k], hipMemcpyHostToDevice));
+  }
+  for (int k = 0; k < 11; k++) dv[k] = ho[k] ? d + oo[k] : nullptr;
+  const gmr_tracker_sim_t dsim{ds[0], ds[1], ds[2], ds[3], ds[4], ds[5]};
+  const gmr_tracker_out_t dout{(float*)dv[0], (float*)dv[1], (float*)dv[2], (float*)dv[3], (float*)dv[4], (float*)dv[5],
+                               (float*)dv[6], (float*)dv[7], (float*)dv[8], (int32_t*)dv[9], (int32_t*)dv[10]};
+  const int rc = gmr::tracker_step_launch(t, t->tab, sim ? &dsim : nullptr, &dout, nullptr);
+  if (rc != GMR_OK) return rc;
+  GMR_HIP_TRY(hipDeviceSynchronize());
+  for (int k = 0; k < 11; k++)
+    if (ho[k]) GMR_HIP_TRY(hipMemcpy(ho[k], dv[k], no[k], hipMemcpyDeviceToHost));
+  return GMR_OK;
+}
+
+int gmr_motion_tracker_state(gmr_motion_tracker_t* t, int32_t* clip, float* time, float* length, uint32_t* draws, uint32_t* ignored) {
+  if (!t) return gmr_fail(GMR_ERR_ARG, "null motion tracker");
+  std::lock_guard<std::mutex> g(t->mu);
+  GMR_HIP_TRY(hipDeviceSynchronize());
+  const size_t nb = (size_t)t->N * 4;
+  if (clip) GMR_HIP_TRY(hipMemcpy(clip, t->S.clip, nb, hipMemcpyDeviceToHost));
+  if (time) GMR_HIP_TRY(hipMemcpy(time, t->S.time, nb, hipMemcpyDeviceToHost));
+  if (length) GMR_HIP_TRY(hipMemcpy(length, t->S.length, nb, hipMemcpyDeviceToHost));
+  if (draws) GMR_HIP_TRY(hipMemcpy(draws, t->S.draws, nb, hipMemcpyDeviceToHost));
+  if (ignored) return gmr::tracker_ignored(t, ignored);
+  return GMR_OK;
+}
+
+}  // extern "C"

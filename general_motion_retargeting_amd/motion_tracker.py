@@ -1,0 +1,248 @@
+"""Motion tracker: the reference source of an imitation environment, on the device.
+
+What the reference's ``booster_gym/envs/t1_imitation.py`` does per environment and per step in Python -- ``_update_reference_motion``
+(:103-200: one ``get_motion_state`` per environment, the map of the motion's dofs onto the robot's, the clock advance),
+``_reset_finished_motions`` / ``_reset_idx`` (:201-235) and the six ``_reward_imitation_*`` terms (:249-309) -- for N environments
+bound to one :class:`MotionLibrary`: every environment's clip and float32 clock live on the device, and :meth:`MotionTracker.step`
+is ONE kernel launch (``csrc/gmr_tracker.hip``).  Random draws are counter-based (Philox4x32-10 keyed by the seed, counter =
+environment and draw number), so a run is reproducible whatever the number of environments around it.
+
+No GPU framework is imported here: :meth:`MotionTracker.step` takes and returns NumPy arrays, :meth:`MotionTracker.step_dev` reads
+and writes device memory the caller names -- ``_lib.DeviceBuffer``, a raw address, or anything with ``data_ptr()``.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, Optional, Sequence
+
+import numpy as np
+
+from .motion_library import LOOP, MotionLibrary, _dev_ptr
+
+TERMS = ("root_pos", "root_rot", "root_vel", "root_ang_vel", "dof_pos", "dof_vel")
+DEFAULT_SCALES = (0.5, 0.5, 2.0, 1.0, 1.0, 0.1)           # T1Imitation.yaml:327-332
+MAX_DOF = 64
+
+
+def _dof_tables(ndof: int, dof_map, dof_default, dof_weight):
+    """``(R, map i32[R] or None, default f32[R] or None, weight f32[R] or None)``, checked as the library checks them"""
+    m = None if dof_map is None else np.ascontiguousarray(dof_map, dtype=np.int32).reshape(-1)
+    R = ndof if m is None else len(m)
+    if not 1 <= R <= MAX_DOF:
+        raise ValueError(f"a tracker serves 1 to {MAX_DOF} robot dofs, got {R}")
+    if m is not None and ((m < -1) | (m >= ndof)).any():
+        raise ValueError(f"dof_map entries lie in [-1, {ndof}): {m.tolist()}")
+    out = [R, m]
+    for name, a in (("dof_default", dof_default), ("dof_weight", dof_weight)):
+        if a is not None:
+            a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+            if len(a) != R:
+                raise ValueError(f"{name} has {len(a)} entries, the robot {R} dofs")
+            if not np.isfinite(a).all():
+                raise ValueError(f"{name} is not finite")
+        out.append(a)
+    return tuple(out)
+
+
+def _clip_weights(num_clips: int, clip_weights):
+    if clip_weights is None:
+        return None
+    w = np.ascontiguousarray(clip_weights, dtype=np.float64).reshape(-1)
+    if len(w) != num_clips:
+        raise ValueError(f"clip_weights has {len(w)} entries, the library {num_clips} clips")
+    if not np.isfinite(w).all() or (w < 0).any() or not w.sum() > 0:
+        raise ValueError("clip_weights must be finite, not negative and not all zero")
+    return w
+
+
+def _terms(scales, weights):
+    out = []
+    for name, a, positive in (("scales", scales, True), ("weights", weights, False)):
+        if a is not None:
+            if isinstance(a, dict):
+                unknown = sorted(set(a) - set(TERMS))
+                if unknown:
+                    raise KeyError(f"{name}: unknown terms {unknown} (known: {list(TERMS)})")
+                base = DEFAULT_SCALES if positive else (1.0,) * len(TERMS)
+                a = [a.get(k, b) for k, b in zip(TERMS, base)]
+            a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+            if len(a) != len(TERMS):
+                raise ValueError(f"{name} has {len(a)} entries, there are {len(TERMS)} terms: {list(TERMS)}")
+            if not np.isfinite(a).all() or (positive and not (a > 0).all()):
+                raise ValueError(f"{name} must be finite" + (" and positive" if positive else ""))
+        out.append(a)
+    return out
+
+
+class MotionTracker:
+    """``num_envs`` environments on one library.  ``dof_map[j]`` is the library column robot dof ``j`` follows, or -1 for
+    ``dof_default[j]`` at velocity zero (identity by default); ``dof_weight`` weighs the dofs inside the two dof terms (ones: the
+    reference's formula); ``scales`` / ``weights`` are six numbers or a dict over :data:`TERMS`; ``clip_weights`` bias the random
+    choice of a clip.  A new tracker has every environment on clip 0 at time 0: call :meth:`reset` or :meth:`assign`.
+
+    A tracker is single-stream: its ``*_dev`` calls go to one stream, or the caller orders them."""
+
+    def __init__(self, library: MotionLibrary, num_envs: int, dt: float, dof_map=None, dof_default=None, dof_weight=None, loop: bool = True,
+                 scales=None, weights=None, clip_weights=None, seed: int = 0):
+        from . import _lib
+        self.library, self.num_envs, self.dt, self.loop, self.seed = library, int(num_envs), float(dt), bool(loop), int(seed)
+        if self.num_envs < 1:
+            raise ValueError(f"num_envs = {num_envs}")
+        if not 0 <= self.seed < 2 ** 64:
+            raise ValueError("seed is a 64-bit unsigned number")
+        R, m, d, w = _dof_tables(library.ndof, dof_map, dof_default, dof_weight)
+        cw = _clip_weights(library.num_clips, clip_weights)
+        sc, wt = _terms(scales, weights)
+        self.handle = None
+        _lib.require_gpu()
+        h = C.c_void_p()
+        _lib.check(_lib.lib().gmr_motion_tracker_create(library.handle, self.num_envs, self.dt, LOOP if loop else 0, R, _lib._ptr(m), _lib._ptr(d),
+                                                        _lib._ptr(w), _lib._ptr(cw), self.seed, C.byref(h)))
+        self.handle, self.nrobot_dof = h, R
+        if sc is not None or wt is not None:
+            self.set_terms(sc, wt)
+
+    # ---- tables ---------------------------------------------------------------------------------------------------------
+    def set_dof_map(self, dof_map=None, dof_default=None, dof_weight=None) -> None:
+        """Replaces the three dof tables (a curriculum changes them between stages); steps already enqueued keep theirs."""
+        from . import _lib
+        R, m, d, w = _dof_tables(self.library.ndof, dof_map, dof_default, dof_weight)
+        _lib.check(_lib.lib().gmr_motion_tracker_set_dof_map(self.handle, R, _lib._ptr(m), _lib._ptr(d), _lib._ptr(w)))
+        self.nrobot_dof = R
+
+    def set_terms(self, scales=None, weights=None) -> None:
+        """``term = exp(-err / scale)``, ``total = sum of weight * term`` over the terms whose weight is not zero; what is ``None``
+        is kept."""
+        from . import _lib
+        sc, wt = _terms(scales, weights)
+        _lib.check(_lib.lib().gmr_motion_tracker_set_terms(self.handle, _lib._ptr(sc), _lib._ptr(wt)))
+
+    # ---- clip assignment and clocks ---------------------------------------------------------------------------------------
+    def reset(self, env_ids=None, resample: bool = True, time_offset_range: Sequence[float] = (0.0, 0.0)) -> int:
+        """``_reset_idx`` (:215-235) for ``env_ids`` (all by default): a new clip when ``resample``, and the clock at a uniformly
+        random point of ``time_offset_range``.  Returns how many ids lay outside ``[0, num_envs)`` (they are ignored)."""
+        from . import _lib
+        lo, hi = (float(x) for x in time_offset_range)
+        ids, n = None, 0
+        if env_ids is not None:
+            ids = np.unique(np.asarray(env_ids, dtype=np.int32).reshape(-1))        # every environment once
+            n = len(ids)
+            if n == 0:
+                return 0
+        ignored = C.c_int()
+        _lib.check(_lib.lib().gmr_motion_tracker_reset(self.handle, n, _lib._ptr(ids), 1 if resample else 0, lo, hi, C.byref(ignored)))
+        return int(ignored.value)
+
+    def assign(self, clip_ids, times, env_ids=None) -> int:
+        """Sets ``(clip, time)`` of ``env_ids`` (all, in order, by default) explicitly; returns the number of ignored ids."""
+        from . import _lib
+        n = self.num_envs if env_ids is None else int(np.size(env_ids))
+        ids = None if env_ids is None else np.ascontiguousarray(env_ids, dtype=np.int32).reshape(-1)
+        clip = np.ascontiguousarray(np.broadcast_to(np.asarray(clip_ids, dtype=np.int32), (n,)))
+        time = np.ascontiguousarray(np.broadcast_to(np.asarray(times, dtype=np.float32), (n,)))
+        ignored = C.c_int()
+        _lib.check(_lib.lib().gmr_motion_tracker_assign(self.handle, n, _lib._ptr(ids), _lib._ptr(clip), _lib._ptr(time), C.byref(ignored)))
+        return int(ignored.value)
+
+    def reset_dev(self, n: int = 0, d_env_ids=None, resample: bool = True, time_offset_range: Sequence[float] = (0.0, 0.0), stream=None) -> None:
+        """:meth:`reset` with the ids (``i32[n]``, every environment once) on the device, asynchronous on ``stream``"""
+        from . import _lib
+        lo, hi = (float(x) for x in time_offset_range)
+        _lib.check(_lib.lib().gmr_motion_tracker_reset_dev(self.handle, int(n), _dev_ptr(d_env_ids, "env_ids", "int32", int(n)),
+                                                           1 if resample else 0, lo, hi, _lib._s(stream)))
+
+    def assign_dev(self, n: int, d_clip, d_time, d_env_ids=None, stream=None) -> None:
+        """:meth:`assign` on device memory (``clip i32[n]``, ``time f32[n]``, ``env_ids i32[n]`` or None with n = num_envs)"""
+        from . import _lib
+        n = int(n)
+        _lib.check(_lib.lib().gmr_motion_tracker_assign_dev(self.handle, n, _dev_ptr(d_env_ids, "env_ids", "int32", n),
+                                                            _dev_ptr(d_clip, "clip", "int32", n), _dev_ptr(d_time, "time", "float32", n),
+                                                            _lib._s(stream)))
+
+    def state(self) -> Dict[str, np.ndarray]:
+        """``clip i32[N]``, ``time f32[N]``, ``length f32[N]``, ``draws u32[N]`` and ``ignored``, the ids outside ``[0, N)`` met so far"""
+        from . import _lib
+        N = self.num_envs
+        out = {"clip": np.empty(N, np.int32), "time": np.empty(N, np.float32), "length": np.empty(N, np.float32), "draws": np.empty(N, np.uint32)}
+        ign = C.c_uint32()
+        _lib.check(_lib.lib().gmr_motion_tracker_state(self.handle, *[_lib._ptr(out[k]) for k in ("clip", "time", "length", "draws")], C.byref(ign)))
+        out["ignored"] = int(ign.value)
+        return out
+
+    # ---- the step ---------------------------------------------------------------------------------------------------------
+    def _counts(self):
+        R = self.nrobot_dof
+        out = {"ref_root_pos": 3, "ref_root_rot": 4, "ref_root_vel": 3, "ref_root_ang_vel": 3, "ref_dof_pos": R, "ref_dof_vel": R, "err": 6,
+               "term": 6, "total": 1, "status": 1, "finished": 1}
+        sim = {"base_pos": 3, "base_quat": 4, "base_lin_vel": 3, "base_ang_vel": 3, "dof_pos": R, "dof_vel": R}
+        return out, sim
+
+    def step(self, sim: Optional[Dict[str, np.ndarray]] = None) -> Dict[str, np.ndarray]:
+        """One environment step, host arrays in and out.  Returns ``ref_root_pos [N,3]``, ``ref_root_rot [N,4]`` xyzw, ``ref_root_vel``,
+        ``ref_root_ang_vel``, ``ref_dof_pos [N,R]``, ``ref_dof_vel`` (robot dof order), ``status`` and ``finished`` (``i32[N]``); with
+        ``sim`` -- any of ``base_pos, base_quat, base_lin_vel, base_ang_vel, dof_pos, dof_vel`` (quaternions xyzw) -- also ``err [N,6]``,
+        ``term [N,6]`` and ``total [N]`` in the order of :data:`TERMS`."""
+        from . import _lib
+        N = self.num_envs
+        counts, sim_counts = self._counts()
+        out = {}
+        for k, w in counts.items():
+            if k in ("err", "term", "total") and sim is None:
+                continue
+            dtype = np.int32 if k in ("status", "finished") else np.float32
+            out[k] = np.empty((N,) if k in ("total", "status", "finished") else (N, w), dtype=dtype)
+        table = _lib.TrackerOut(**{k: a.ctypes.data for k, a in out.items()})
+        keep, st = [], None
+        if sim is not None:
+            unknown = sorted(set(sim) - set(sim_counts))
+            if unknown:
+                raise TypeError(f"step: unknown simulator arrays {unknown}")
+            st = _lib.TrackerSim()
+            for k, a in sim.items():
+                if a is None:
+                    continue
+                a = np.ascontiguousarray(a, dtype=np.float32)
+                if a.shape != (N, sim_counts[k]):
+                    raise ValueError(f"{k}: shape {a.shape}, {(N, sim_counts[k])} needed")
+                keep.append(a)
+                setattr(st, k, a.ctypes.data)
+        _lib.check(_lib.lib().gmr_motion_tracker_step(self.handle, None if st is None else C.byref(st), C.byref(table)))
+        return out
+
+    def step_dev(self, sim: Optional[Dict[str, object]] = None, stream=None, **outputs) -> None:
+        """The same on device memory, asynchronous on ``stream``: ``sim`` maps names to device arrays, ``outputs`` names whichever of the
+        arrays of :meth:`step` are wanted; each is a ``_lib.DeviceBuffer``, a raw address or an object with ``data_ptr()``, checked as
+        ``MotionLibrary.sample_dev`` checks them."""
+        from . import _lib
+        N = self.num_envs
+        counts, sim_counts = self._counts()
+        unknown = sorted(set(outputs) - set(counts))
+        if unknown:
+            raise TypeError(f"step_dev: unknown outputs {unknown}")
+        table = _lib.TrackerOut()
+        for k, x in outputs.items():
+            p = _dev_ptr(x, k, "int32" if k in ("status", "finished") else "float32", N * counts[k])
+            setattr(table, k, None if p is None else p.value)
+        st = None
+        if sim is not None:
+            unknown = sorted(set(sim) - set(sim_counts))
+            if unknown:
+                raise TypeError(f"step_dev: unknown simulator arrays {unknown}")
+            st = _lib.TrackerSim()
+            for k, x in sim.items():
+                p = _dev_ptr(x, k, "float32", N * sim_counts[k])
+                setattr(st, k, None if p is None else p.value)
+        _lib.check(_lib.lib().gmr_motion_tracker_step_dev(self.handle, None if st is None else C.byref(st), C.byref(table), _lib._s(stream)))
+
+    def close(self) -> None:
+        h = getattr(self, "handle", None)
+        if h:
+            from . import _lib
+            _lib.lib().gmr_motion_tracker_destroy(h)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -472,6 +472,85 @@ int gmr_motion_body_state_dev(const gmr_motion_lib_t* lib, gmr_fk_t* fk, int N, 
 int gmr_motion_body_state(const gmr_motion_lib_t* lib, gmr_fk_t* fk, int N, const int32_t* clip, const double* time, int flags,
                           const int32_t* body_sel, int nsel, const gmr_body_state_out_t* out);   /* host buffers; synchronises */
 
+/* ---- N4: motion tracker (the reference source of an imitation environment: clocks, reference rows, tracking terms) -- */
+/* What booster_gym/envs/t1_imitation.py does per environment and per step in Python -- _update_reference_motion (:103-200),
+ * _reset_finished_motions / _reset_idx (:201-235) and the six _reward_imitation_* terms (:249-309) -- for N environments
+ * bound to one motion library, ONE kernel launch per step.  Per environment e the tracker holds, on the
+ * device: clip i32, time f32 (the reference's motion_times is a float32 tensor), length f32 = (float)(T / fps) of that clip
+ * and draws u32, the random draws made for e so far.  A new tracker has every environment on clip 0 at time 0.
+ * A step, per environment and in the order of :103-207:
+ *   1. the library is sampled at (clip, (double)time), GMR_MOTION_LOOP or clamp as given at creation: the same code as
+ *      gmr_motion_sample_dev, the same bits
+ *   2. ref_root_pos [N][3], ref_root_rot [N][4] xyzw, ref_root_vel, ref_root_ang_vel [N][3] as sampled; ref_dof_pos / ref_dof_vel
+ *      [N][R] in ROBOT dof order: robot dof j takes column dof_map[j] of the library, or, for dof_map[j] = -1, dof_default[j]
+ *      and velocity 0 (:139-161: head zero, stage-1 legs at their default pose)
+ *   3. with simulator state: err [N][6] = |base_pos - ref|, 2 acos(min(|<base_quat, ref_root_rot>|, 1)) (the w of
+ *      conj(q) * q_ref, :256-270), |base_lin_vel - ref|, |base_ang_vel - ref|, |w (dof_pos - ref)|, |w (dof_vel - ref)| in
+ *      float32 (w: dof_weight, ones = the reference's formula); term [N][6] = exp(-err / scale); total [N] = the sum of
+ *      weight_k term_k over the terms whose weight is not zero and whose simulator array was given (:341-345).  err and
+ *      term of an array that was not given are 0.
+ *   4. time = time + (float)dt, in float32
+ *   5. without GMR_MOTION_LOOP: time >= length redraws the clip, sets time = 0 and finished[e] = 1 (else 0)
+ *   6. a clip id outside [0, C), an empty clip or a non-finite time: every requested row of e is NaN, status[e] = 1 (else 0),
+ *      finished[e] = 0, nothing of the library is read and the clock does not move
+ * A random draw is one Philox4x32-10 call with key = seed (low word first) and counter = (e, draws[e], 0, 0), after which
+ * draws[e] += 1: the result depends on neither the launch shape nor the order of calls on other environments.  Word 0
+ * chooses the clip -- (word0 * C) >> 32, or with clip_weights the largest k with cdf[k] <= word0 2^-32, cdf[k] = (w_0 + ..
+ * + w_{k-1}) / sum in float64 (a clip of weight zero is never drawn) -- and word 1 gives u = (word1 >> 8) 2^-24 in [0, 1).
+ * A tracker is SINGLE-STREAM: its kernels read and write its own state, so every *_dev call on one tracker goes to one stream
+ * (or the caller orders the streams); a step must not run before the library's fill has finished.  The plain entry points
+ * take host buffers, run on the default stream, synchronise the device and hold the tracker's mutex throughout.  The
+ * library must outlive the tracker. */
+typedef struct gmr_motion_tracker gmr_motion_tracker_t;
+#define GMR_TRACKER_MAX_DOF 64
+typedef struct {            /* outputs of a step: device pointers (gmr_motion_tracker_step: host pointers), each may be NULL */
+  float *ref_root_pos, *ref_root_rot, *ref_root_vel, *ref_root_ang_vel;   /* [N][3|4|3|3]                       */
+  float *ref_dof_pos, *ref_dof_vel;                                       /* [N][R], robot dof order            */
+  float *err, *term;                                                      /* [N][6]; need the simulator state   */
+  float *total;                                                           /* [N];    needs the simulator state  */
+  int32_t *status, *finished;                                             /* [N]                                */
+} gmr_tracker_out_t;
+typedef struct {            /* simulator state of a step: device pointers (host for the plain call), each may be NULL */
+  const float *base_pos, *base_quat /* xyzw */, *base_lin_vel, *base_ang_vel;   /* [N][3|4|3|3] */
+  const float *dof_pos, *dof_vel;                                               /* [N][R]       */
+} gmr_tracker_sim_t;
+/* HOST arrays, validated here: dof_map i32[R] with entries in [-1, ndof) or NULL for the identity (R = the library's ndof),
+ * dof_default f32[R] or NULL (zeros), dof_weight f32[R] finite or NULL (ones), clip_weights f64[C] finite, not negative and
+ * not all zero, or NULL (uniform).  1 <= R <= GMR_TRACKER_MAX_DOF, 1 <= N <= 2^26, dt finite; flags: GMR_MOTION_LOOP.
+ * The terms start with the scales of T1Imitation.yaml:327-332 (0.5, 0.5, 2.0, 1.0, 1.0, 0.1) and weights of one. */
+int gmr_motion_tracker_create(const gmr_motion_lib_t* lib, int N, double dt, int flags, int R, const int32_t* dof_map,
+                              const float* dof_default, const float* dof_weight, const double* clip_weights, uint64_t seed,
+                              gmr_motion_tracker_t** out);
+int gmr_motion_tracker_destroy(gmr_motion_tracker_t* t);
+/* Replaces the dof tables (a curriculum changes them between stages, :145-158); R may change with them.  The tables travel with
+ * every launch, so steps already enqueued keep the ones they were launched with. */
+int gmr_motion_tracker_set_dof_map(gmr_motion_tracker_t* t, int R, const int32_t* dof_map, const float* dof_default,
+                                   const float* dof_weight);
+/* scale f32[6] positive and finite, weight f32[6] finite (0 skips the term); either may be NULL and is then kept (:249-309) */
+int gmr_motion_tracker_set_terms(gmr_motion_tracker_t* t, const float* scale, const float* weight);
+/* (clip, time) of the n listed environments, or of all N in order with env_ids = NULL (n = N); ids outside [0, N) are ignored
+ * and counted, an id listed twice takes one of its two rows.  A clip id outside [0, C) is stored as it is (step 6). */
+int gmr_motion_tracker_assign_dev(gmr_motion_tracker_t* t, int n, const int32_t* d_env_ids, const int32_t* d_clip,
+                                  const float* d_time, void* stream);            /* asynchronous */
+int gmr_motion_tracker_assign(gmr_motion_tracker_t* t, int n, const int32_t* env_ids, const int32_t* clip, const float* time,
+                              int* ignored /* ids of this call outside [0, N), or NULL */);
+/* _reset_idx (:215-235) for the n listed environments, or for all with env_ids = NULL: one draw each; with `resample` its
+ * word 0 redraws the clip, and in either case time = lo + (hi - lo) u in float32 (time_offset_range).  Ids outside [0, N)
+ * are ignored and counted.  An id listed twice in one call gives that environment one of the two possible outcomes (one or
+ * two draws) and touches no other: list every environment once. */
+int gmr_motion_tracker_reset_dev(gmr_motion_tracker_t* t, int n, const int32_t* d_env_ids, int resample, float lo, float hi,
+                                 void* stream);                                  /* asynchronous */
+int gmr_motion_tracker_reset(gmr_motion_tracker_t* t, int n, const int32_t* env_ids, int resample, float lo, float hi,
+                             int* ignored /* ids of this call outside [0, N), or NULL */);
+/* One environment step (:103-207, :249-309) in one launch; sim may be NULL (then err, term and total must be). */
+int gmr_motion_tracker_step_dev(gmr_motion_tracker_t* t, const gmr_tracker_sim_t* sim, const gmr_tracker_out_t* out,
+                                void* stream);                                   /* asynchronous */
+int gmr_motion_tracker_step(gmr_motion_tracker_t* t, const gmr_tracker_sim_t* sim, const gmr_tracker_out_t* out);
+/* the state on the host: clip i32[N], time f32[N], length f32[N], draws u32[N] (each may be NULL) and the ids ignored since
+ * creation; synchronises */
+int gmr_motion_tracker_state(gmr_motion_tracker_t* t, int32_t* clip, float* time, float* length, uint32_t* draws,
+                             uint32_t* ignored);
+
 /* ---- multi-GPU: one rank per GPU, ONE broadcast, no per-step collective ------------ */
 /* The reference parallelises over files with mp.Pool on one CPU (scripts/smplx_to_robot_dataset.py:241-242); here
  * streams shard over the ranks of one node and the only data that crosses ranks is the packed robot model + task set.
