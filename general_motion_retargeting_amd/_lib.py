@@ -123,6 +123,10 @@ _SIGS = {
     "gmr_motion_tracker_step_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gmr_motion_tracker_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "gmr_motion_tracker_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
+    "gmr_motion_tracker_set_links": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+    "gmr_motion_tracker_set_link_terms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float]),
+    "gmr_motion_tracker_step_links_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "gmr_motion_tracker_step_links": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "gmr_comm_create": (C.c_int, [C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),
     "gmr_comm_destroy": (C.c_int, [C.c_void_p]),
     "gmr_comm_rank": (C.c_int, [C.c_void_p]),
@@ -557,6 +561,23 @@ class TrackerOut(C.Structure):
 class TrackerSim(C.Structure):
     """``gmr_tracker_sim_t``: the simulator state of ``gmr_motion_tracker_step[_dev]``, each an address or NULL"""
     _fields_ = [(k, C.c_void_p) for k in TRACKER_SIM_FIELDS]
+
+
+TRACKER_LINKS_OUT_FIELDS = ("ref_body_pos", "ref_body_rot", "ref_body_vel", "ref_body_ang_vel", "link_err", "link_term", "max_dist", "fail")
+TRACKER_LINKS_SIM_FIELDS = ("body_pos", "body_rot", "body_vel", "body_ang_vel")
+TRACKER_LINK_TERMS = 4
+TRACKER_FRAME_WORLD, TRACKER_FRAME_HEADING = 0, 1
+TRACKER_NO_ADVANCE = 1
+
+
+class TrackerLinksOut(C.Structure):
+    """``gmr_tracker_links_out_t``: the link outputs of ``gmr_motion_tracker_step_links[_dev]``, each an address or NULL"""
+    _fields_ = [(k, C.c_void_p) for k in TRACKER_LINKS_OUT_FIELDS]
+
+
+class TrackerLinksSim(C.Structure):
+    """``gmr_tracker_links_sim_t``: the simulator's rigid-body state, four addresses (or NULL) and the two strides in floats"""
+    _fields_ = [(k, C.c_void_p) for k in TRACKER_LINKS_SIM_FIELDS] + [("env_stride", C.c_int64), ("body_stride", C.c_int64)]
 
 
 class FkHandle:

@@ -1,11 +1,12 @@
 // gmr_handles.h -- the handles of the C-ABI that more than one translation unit of libgmrhip.so looks into (not part of the
 // C-ABI): the FK tree (created in gmr_abi.hip) and the motion library (gmr_motion.hip), both read by gmr_body_state.hip, and
-// the motion tracker (gmr_tracker.hip), which is bound to a library.
+// the motion tracker (gmr_tracker.hip), which is bound to a library and, with links attached (gmr_tracker_links.hip), to an FK tree.
 #pragma once
 #include <stdint.h>
 
 #include "../../include/gmr_hip.h"
 #include "gmr_fk_tree.h"
+#include "gmr_link_plan.h"
 #include "gmr_workspace.h"
 
 struct gmr_fk {
@@ -61,6 +62,8 @@ struct gmr_motion_tracker {
   float dtf;                     // (float)dt: the clock is float32
   uint32_t key[2];               // the seed, low word first
   gmr::TrackerTables tab;
+  gmr::LinkPlan links;           // links.nsel = 0 until gmr_motion_tracker_set_links attaches a selection
+  const gmr_fk* fk = nullptr;    // not owned: the tree of the attached links outlives the tracker
   gmr::TrackerState S;
   gmr::DeviceBlock block;
   std::mutex mu;                 // the tables, and the whole of every synchronous entry point

@@ -22,58 +22,13 @@
 #include "gmr_internal.h"
 #include "gmr_motion_sample.h"
 #include "gmr_philox.h"
+#include "gmr_tracker_dev.h"
 #include "gmr_workspace.h"
 
 // one rounding per operation, as in the sampler whose bits the reference rows reproduce
 #pragma clang fp contract(off)
 
 namespace gmr {
-
-struct TrackerSim {
-  const float *base_pos, *base_quat, *base_lin_vel, *base_ang_vel, *dof_pos, *dof_vel;
-};
-struct TrackerOut {
-  float *ref_root_pos, *ref_root_rot, *ref_root_vel, *ref_root_ang_vel, *ref_dof_pos, *ref_dof_vel, *err, *term, *total;
-  int32_t *status, *finished;
-};
-
-// (float)(T / fps) of clip c; 0 for a clip id outside [0, C)
-__device__ __forceinline__ float clip_length(const MotionArrays& A, int c) {
-  if (c < 0 || c >= A.C) return 0.0f;
-  return (float)((double)(A.seg_start[c + 1] - A.seg_start[c]) / A.fps[c]);
-}
-
-// One draw for environment e: counter (e, draws[e], 0, 0), after which draws[e] is one more.  With want_clip, *clip is set
-// from word 0; the return value is u of word 1.
-__device__ __forceinline__ float tracker_draw(const MotionArrays& A, const TrackerState& S, uint32_t key0, uint32_t key1, int e,
-                                              bool want_clip, int* clip) {
-  const uint32_t ctr[4] = {(uint32_t)e, S.draws[e], 0u, 0u}, key[2] = {key0, key1};
-  uint32_t w[4];
-  philox4x32(ctr, key, w);
-  S.draws[e] = ctr[1] + 1u;
-  if (want_clip) {
-    if (S.cdf) {
-      // the largest k with cdf[k] <= x (cdf[0] = 0 <= x always)
-      const double x = (double)w[0] * 2.3283064365386963e-10;
-      int lo = 0, hi = A.C - 1;
-      while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (S.cdf[mid] <= x) lo = mid; else hi = mid - 1;
-      }
-      *clip = lo;
-    } else {
-      *clip = philox_below(w[0], A.C);
-    }
-  }
-  return philox_unit(w[1]);
-}
-
-// the sum over the 16 lanes of an environment, in every one of them
-__device__ __forceinline__ float group_sum(float x) {
-#pragma unroll
-  for (int m = 1; m < MOTION_GROUP; m <<= 1) x = x + __shfl_xor(x, m, MOTION_GROUP);
-  return x;
-}
 
 // Lanes l < 3 (l < 4) of an environment hold component l of the root rows, as in the sampler; all 16 stride over the robot
 // dofs.  Each lane squares what it holds, the six sums of an environment are butterflies over its 16-lane row, and lane 0

@@ -22,6 +22,10 @@ from .motion_library import LOOP, MotionLibrary, _dev_ptr
 TERMS = ("root_pos", "root_rot", "root_vel", "root_ang_vel", "dof_pos", "dof_vel")
 DEFAULT_SCALES = (0.5, 0.5, 2.0, 1.0, 1.0, 0.1)           # T1Imitation.yaml:327-332
 MAX_DOF = 64
+LINK_TERMS = ("link_pos", "link_rot", "link_vel", "link_ang_vel")
+DEFAULT_LINK_SCALES = (0.3, 0.8, 2.0, 4.0)               # m, rad, m/s, rad/s: a choice of this library, the reference has no link terms
+FRAMES = {"world": 0, "heading": 1}
+LINK_SIM = {"body_pos": (0, 3), "body_rot": (3, 4), "body_vel": (7, 3), "body_ang_vel": (10, 3)}      # offset and width in a packed row of 13
 
 
 def _dof_tables(ndof: int, dof_map, dof_default, dof_weight):
@@ -55,19 +59,19 @@ def _clip_weights(num_clips: int, clip_weights):
     return w
 
 
-def _terms(scales, weights):
+def _terms(scales, weights, names=TERMS, default_scales=DEFAULT_SCALES):
     out = []
     for name, a, positive in (("scales", scales, True), ("weights", weights, False)):
         if a is not None:
             if isinstance(a, dict):
-                unknown = sorted(set(a) - set(TERMS))
+                unknown = sorted(set(a) - set(names))
                 if unknown:
-                    raise KeyError(f"{name}: unknown terms {unknown} (known: {list(TERMS)})")
-                base = DEFAULT_SCALES if positive else (1.0,) * len(TERMS)
-                a = [a.get(k, b) for k, b in zip(TERMS, base)]
+                    raise KeyError(f"{name}: unknown terms {unknown} (known: {list(names)})")
+                base = default_scales if positive else (1.0,) * len(names)
+                a = [a.get(k, b) for k, b in zip(names, base)]
             a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
-            if len(a) != len(TERMS):
-                raise ValueError(f"{name} has {len(a)} entries, there are {len(TERMS)} terms: {list(TERMS)}")
+            if len(a) != len(names):
+                raise ValueError(f"{name} has {len(a)} entries, there are {len(names)} terms: {list(names)}")
             if not np.isfinite(a).all() or (positive and not (a > 0).all()):
                 raise ValueError(f"{name} must be finite" + (" and positive" if positive else ""))
         out.append(a)
@@ -99,6 +103,7 @@ class MotionTracker:
         _lib.check(_lib.lib().gmr_motion_tracker_create(library.handle, self.num_envs, self.dt, LOOP if loop else 0, R, _lib._ptr(m), _lib._ptr(d),
                                                         _lib._ptr(w), _lib._ptr(cw), self.seed, C.byref(h)))
         self.handle, self.nrobot_dof = h, R
+        self._links = None            # (fk, nsel, sim_body, frame) once set_links has attached a selection
         if sc is not None or wt is not None:
             self.set_terms(sc, wt)
 
@@ -233,6 +238,207 @@ class MotionTracker:
                 p = _dev_ptr(x, k, "float32", N * sim_counts[k])
                 setattr(st, k, None if p is None else p.value)
         _lib.check(_lib.lib().gmr_motion_tracker_step_dev(self.handle, None if st is None else C.byref(st), C.byref(table), _lib._s(stream)))
+
+    # ---- links ---------------------------------------------------------------------------------------
+    def _link_setup(self, kinematics, bodies, sim_bodies, link_weight, frame):
+        """the checks of :meth:`set_links`, all of them before a device is touched: ``(kinematics, has names, sel i32[nsel], sim_body
+        i32[nsel], weight f32[nsel] or None, frame)``"""
+        if frame not in FRAMES:
+            raise ValueError(f"frame is one of {sorted(FRAMES)}, got {frame!r}")
+        km, names = self.library._resolve_kinematics(kinematics)
+        nbody = len(names) if names is not None else km.nbody
+        sel, nsel = self.library._body_selection(bodies, names, nbody)
+        if sel is None:
+            if not 1 <= nbody <= 64:
+                raise ValueError(f"a selection holds 1 to 64 bodies, the robot has {nbody}")
+            sel = np.arange(nbody, dtype=np.int32)
+        sb = np.arange(nsel, dtype=np.int32) if sim_bodies is None else np.ascontiguousarray(sim_bodies, dtype=np.int32).reshape(-1)
+        if len(sb) != nsel:
+            raise ValueError(f"sim_bodies has {len(sb)} entries, the selection {nsel}")
+        if ((sb < 0) | (sb >= 1 << 16)).any():
+            raise ValueError(f"sim_bodies entries lie in [0, 65536): {sb.tolist()}")
+        w = None
+        if link_weight is not None:
+            w = np.ascontiguousarray(link_weight, dtype=np.float32).reshape(-1)
+            if len(w) != nsel:
+                raise ValueError(f"link_weight has {len(w)} entries, the selection {nsel}")
+            if not np.isfinite(w).all() or (w < 0).any() or not w.sum() > 0:
+                raise ValueError("link_weight must be finite, not negative and not all zero")
+        return km, names is not None, sel, sb, w, frame
+
+    def set_links(self, kinematics=None, bodies=None, sim_bodies=None, link_weight=None, frame: str = "world") -> None:
+        """Attaches link targets: the robot (``kinematics``, or the library's attached one) and ``bodies`` by name or index, in any
+        order (``None``: all).  ``sim_bodies[s]`` is the simulator's body index of selection row ``s`` (identity by default),
+        ``link_weight`` weighs the links inside the four link terms, ``frame`` is ``"world"`` or ``"heading"`` (each side relative to
+        its own root with the root's yaw removed).  ``bodies=[]`` detaches.  Link targets follow the motion in the library's dof
+        order: the ``dof_map`` does not enter."""
+        from . import _lib
+        if bodies is not None and len(bodies) == 0:
+            _lib.check(_lib.lib().gmr_motion_tracker_set_links(self.handle, None, None, 0, None, None, 0))
+            self._links = None
+            return
+        km, named, sel, sb, w, frame = self._link_setup(kinematics, bodies, sim_bodies, link_weight, frame)
+        fk = km.hip_handle if named else km          # (a KinematicsModel makes its device handle here, after every check)
+        _lib.check(_lib.lib().gmr_motion_tracker_set_links(self.handle, fk.handle, _lib._ptr(sel), len(sel), _lib._ptr(sb), _lib._ptr(w), FRAMES[frame]))
+        self._links = (fk, len(sel), sb, frame)
+
+    def set_link_terms(self, scales=None, weights=None, fail_dist: float = float("inf")) -> None:
+        """``link_term = exp(-link_err / scale)`` over :data:`LINK_TERMS` (defaults :data:`DEFAULT_LINK_SCALES`, weights one; ``None``
+        keeps what is set); ``fail = not (max_dist <= fail_dist)`` and ``fail_dist`` is set by every call."""
+        from . import _lib
+        sc, wt = _terms(scales, weights, LINK_TERMS, DEFAULT_LINK_SCALES)
+        fail_dist = float(fail_dist)
+        if not fail_dist > 0:
+            raise ValueError(f"fail_dist = {fail_dist}, must be positive (or inf)")
+        _lib.check(_lib.lib().gmr_motion_tracker_set_link_terms(self.handle, _lib._ptr(sc), _lib._ptr(wt), fail_dist))
+
+    def _link_counts(self):
+        nsel = self._links[1] if self._links else 0
+        return {"ref_body_pos": nsel * 3, "ref_body_rot": nsel * 4, "ref_body_vel": nsel * 3, "ref_body_ang_vel": nsel * 3, "link_err": 4,
+                "link_term": 4, "max_dist": 1, "fail": 1}
+
+    def _check_links(self, sim, links, device: bool):
+        """the checks of a link step that need no device -> ``("packed", array) | ("separate", {name: array}) | None``"""
+        if links is None:
+            return None
+        if self._links is None:
+            raise ValueError("the tracker has no links attached: call set_links() first")
+        _, nsel, sb, frame = self._links
+        unknown = sorted(set(links) - set(LINK_SIM) - {"body_state"})
+        if unknown:
+            raise TypeError(f"step_links: unknown link arrays {unknown}")
+        if frame == "heading" and (sim is None or sim.get("base_pos") is None or sim.get("base_quat") is None):
+            raise ValueError('frame="heading" needs base_pos and base_quat of the simulator\'s root in sim')
+        if "body_state" in links:
+            if len(links) != 1:
+                raise TypeError("links is either {'body_state': [N, nb, 13]} or the four separate arrays")
+            return "packed", links["body_state"]
+        given = {k: v for k, v in links.items() if v is not None}
+        if not given:
+            raise ValueError(f"links names none of {sorted(LINK_SIM)}: pass links=None for a step without the simulator's links")
+        return "separate", given
+
+    def step_links(self, sim: Optional[Dict[str, np.ndarray]] = None, links: Optional[Dict[str, np.ndarray]] = None,
+                   advance: bool = True) -> Dict[str, np.ndarray]:
+        """:meth:`step` plus, in the same launch, ``ref_body_pos [N,nsel,3]``, ``ref_body_rot [N,nsel,4]``, ``ref_body_vel``,
+        ``ref_body_ang_vel`` of the attached links at the environments' own clocks and -- with ``links``, the simulator's rigid-body
+        state as ``{"body_state": [N, nb, 13]}`` (pos, quat xyzw, vel, ang vel) or as ``body_pos / body_rot / body_vel / body_ang_vel
+        [N, nsel, k]`` -- ``link_err [N,4]``, ``link_term [N,4]``, ``max_dist [N]`` and ``fail i32[N]``; ``total`` then includes the link
+        terms.  ``advance=False`` leaves clocks and clips as they are (reference-state initialisation after :meth:`reset`)."""
+        from . import _lib
+        N = self.num_envs
+        kind = self._check_links(sim, links, False)
+        counts, sim_counts = self._counts()
+        out = {}
+        for k, w in counts.items():
+            if k in ("err", "term") and sim is None or k == "total" and sim is None and kind is None:
+                continue
+            dtype = np.int32 if k in ("status", "finished") else np.float32
+            out[k] = np.empty((N,) if k in ("total", "status", "finished") else (N, w), dtype=dtype)
+        table = _lib.TrackerOut(**{k: a.ctypes.data for k, a in out.items()})
+        lout = {}
+        if self._links is not None:
+            nsel = self._links[1]
+            for k, w in (("ref_body_pos", 3), ("ref_body_rot", 4), ("ref_body_vel", 3), ("ref_body_ang_vel", 3)):
+                lout[k] = np.empty((N, nsel, w), dtype=np.float32)
+            if kind is not None:
+                lout.update(link_err=np.empty((N, 4), np.float32), link_term=np.empty((N, 4), np.float32), max_dist=np.empty(N, np.float32),
+                            fail=np.empty(N, np.int32))
+        ltable = _lib.TrackerLinksOut(**{k: a.ctypes.data for k, a in lout.items()})
+        keep, st, ls = [], None, None
+        if sim is not None:
+            unknown = sorted(set(sim) - set(sim_counts))
+            if unknown:
+                raise TypeError(f"step_links: unknown simulator arrays {unknown}")
+            st = _lib.TrackerSim()
+            for k, a in sim.items():
+                if a is None:
+                    continue
+                a = np.ascontiguousarray(a, dtype=np.float32)
+                if a.shape != (N, sim_counts[k]):
+                    raise ValueError(f"{k}: shape {a.shape}, {(N, sim_counts[k])} needed")
+                keep.append(a)
+                setattr(st, k, a.ctypes.data)
+        if kind is not None:
+            nsel, sb = self._links[1], self._links[2]
+            ls = _lib.TrackerLinksSim()
+            if kind[0] == "packed":
+                a = np.ascontiguousarray(kind[1], dtype=np.float32)
+                if a.ndim != 3 or a.shape[0] != N or a.shape[2] != 13:
+                    raise ValueError(f"body_state: shape {a.shape}, ({N}, nb, 13) needed")
+                if int(sb.max()) >= a.shape[1]:
+                    raise ValueError(f"sim_bodies reaches body {int(sb.max())}, body_state has {a.shape[1]}")
+                keep.append(a)
+                for k, (off, _) in LINK_SIM.items():
+                    setattr(ls, k, a.ctypes.data + 4 * off)
+                ls.env_stride, ls.body_stride = 13 * a.shape[1], 13
+            else:
+                if not np.array_equal(sb, np.arange(nsel)):
+                    raise ValueError("separate link arrays are [N, nsel, k] in selection order: they need the identity sim_bodies")
+                for k, a in kind[1].items():
+                    a = np.ascontiguousarray(a, dtype=np.float32)
+                    if a.shape != (N, nsel, LINK_SIM[k][1]):
+                        raise ValueError(f"{k}: shape {a.shape}, {(N, nsel, LINK_SIM[k][1])} needed")
+                    keep.append(a)
+                    setattr(ls, k, a.ctypes.data)
+        _lib.check(_lib.lib().gmr_motion_tracker_step_links(self.handle, None if st is None else C.byref(st), None if ls is None else C.byref(ls),
+                                                            C.byref(table), C.byref(ltable), 0 if advance else _lib.TRACKER_NO_ADVANCE))
+        out.update(lout)
+        return out
+
+    def step_links_dev(self, sim: Optional[Dict[str, object]] = None, links: Optional[Dict[str, object]] = None, advance: bool = True,
+                       stream=None, **outputs) -> None:
+        """:meth:`step_links` on device memory, asynchronous on ``stream``.  ``links`` is ``{"body_state": array, "num_bodies": nb}``
+        for a packed ``[N, nb, 13]`` tensor or the four separate ``[N, nsel, k]`` arrays; ``outputs`` names whichever arrays of
+        :meth:`step_links` are wanted."""
+        from . import _lib
+        N = self.num_envs
+        links = None if links is None else dict(links)
+        nb = None if links is None else links.pop("num_bodies", None)
+        kind = self._check_links(sim, links, True)
+        counts, sim_counts = self._counts()
+        lcounts = self._link_counts()
+        unknown = sorted(set(outputs) - set(counts) - set(lcounts))
+        if unknown:
+            raise TypeError(f"step_links_dev: unknown outputs {unknown}")
+        table, ltable = _lib.TrackerOut(), _lib.TrackerLinksOut()
+        for k, x in outputs.items():
+            p = _dev_ptr(x, k, "int32" if k in ("status", "finished", "fail") else "float32", N * (counts[k] if k in counts else lcounts[k]))
+            setattr(table if k in counts else ltable, k, None if p is None else p.value)
+        st, ls = None, None
+        if sim is not None:
+            unknown = sorted(set(sim) - set(sim_counts))
+            if unknown:
+                raise TypeError(f"step_links_dev: unknown simulator arrays {unknown}")
+            st = _lib.TrackerSim()
+            for k, x in sim.items():
+                p = _dev_ptr(x, k, "float32", N * sim_counts[k])
+                setattr(st, k, None if p is None else p.value)
+        if kind is not None:
+            nsel, sb = self._links[1], self._links[2]
+            ls = _lib.TrackerLinksSim()
+            if kind[0] == "packed":
+                if nb is None:
+                    shape = getattr(kind[1], "shape", None)
+                    if shape is None or len(shape) != 3:
+                        raise ValueError("a packed body_state on the device needs num_bodies (or a [N, nb, 13] shape)")
+                    nb = int(shape[1])
+                nb = int(nb)
+                if int(sb.max()) >= nb:
+                    raise ValueError(f"sim_bodies reaches body {int(sb.max())}, body_state has {nb}")
+                p = _dev_ptr(kind[1], "body_state", "float32", N * nb * 13)
+                for k, (off, _) in LINK_SIM.items():
+                    setattr(ls, k, p.value + 4 * off)
+                ls.env_stride, ls.body_stride = 13 * nb, 13
+            else:
+                if not np.array_equal(sb, np.arange(nsel)):
+                    raise ValueError("separate link arrays are [N, nsel, k] in selection order: they need the identity sim_bodies")
+                for k, x in kind[1].items():
+                    p = _dev_ptr(x, k, "float32", N * nsel * LINK_SIM[k][1])
+                    setattr(ls, k, None if p is None else p.value)
+        _lib.check(_lib.lib().gmr_motion_tracker_step_links_dev(self.handle, None if st is None else C.byref(st), None if ls is None else C.byref(ls),
+                                                                C.byref(table), C.byref(ltable), 0 if advance else _lib.TRACKER_NO_ADVANCE,
+                                                                _lib._s(stream)))
 
     def close(self) -> None:
         h = getattr(self, "handle", None)

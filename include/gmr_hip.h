@@ -551,6 +551,74 @@ int gmr_motion_tracker_step(gmr_motion_tracker_t* t, const gmr_tracker_sim_t* si
 int gmr_motion_tracker_state(gmr_motion_tracker_t* t, int32_t* clip, float* time, float* length, uint32_t* draws,
                              uint32_t* ignored);
 
+/* ---- N5: tracker links (per-link targets and whole-body tracking terms of a motion tracker) ---- */
+/* A tracker may have LINKS attached: an FK handle of the robot and a selection of 1 <= nsel <= 64 distinct bodies in any order.
+ * The library must have been filled in GMR_MOTION_ANGVEL_WORLD mode and the handle's ndof must be the library's: the rules, and
+ * the errors, of gmr_motion_body_state_dev.  A LINK STEP does everything gmr_motion_tracker_step_dev does -- the same bits in the
+ * same outputs, the same clock / redraw / finished / status -- and, in the same launch, per environment e:
+ *   1. ref_body_pos [N][nsel][3], ref_body_rot [N][nsel][4] xyzw, ref_body_vel, ref_body_ang_vel [N][nsel][3]: the float32 FK and
+ *      velocity propagation of gmr_motion_body_state_dev applied to the library's own sampled state at (clip, (double)time), rows
+ *      in selection order.  In GMR_TRACKER_FRAME_WORLD they are bit-equal to what gmr_motion_body_state_dev returns for that
+ *      (clip, (double)time) and selection.  The dof_map does NOT enter: link targets come from the motion as retargeted, in the
+ *      library's dof order -- also while a curriculum stage parks the legs at their defaults in ref_dof_pos.
+ *   2. with simulator link state, in float32, w_b >= 0 the link weights and W = sum w_b > 0:
+ *        d_b = |p_b - ref p_b|                          theta_b = 2 acos(min(|<q_b, ref q_b>|, 1))
+ *        link_err [N][4] = sqrt(sum_b w_b x_b^2 / W) for x_b = d_b, theta_b, |v_b - ref v_b|, |om_b - ref om_b|
+ *        link_term [N][4] = exp(-link_err / link_scale)
+ *        max_dist [N] = the largest d_b over the links with w_b > 0 (NaN if any such d_b is NaN)
+ *        fail [N] = !(max_dist <= fail_dist): with fail_dist = +inf only a non-finite distance fails
+ *        total [N] (of gmr_tracker_out_t) = the six weighted terms + sum_k link_weight_k link_term_k
+ *      A link of weight zero is not read.  As for the six terms: a term whose weight is zero or whose array was not given stays
+ *      out of the total; err and term of an array that was not given are 0 (max_dist 0 and fail 0 without body_pos).
+ *   3. GMR_TRACKER_FRAME_HEADING: each side is expressed relative to its OWN root with the root's yaw removed, before
+ *      differencing and before ref_body_* is written:
+ *        p' = Rz(-psi)(p - p_root)   q' = conj(q_psi) q   v' = Rz(-psi) v   om' = Rz(-psi) om
+ *        q_psi = normalize(0, 0, q_root.z, q_root.w), the identity when z = w = 0
+ *      The reference side takes the sampled root, the simulator side base_pos / base_quat of gmr_tracker_sim_t, which are then
+ *      mandatory.  The link terms do not see drift in x, y and yaw; they do see a tilted or sunken robot.
+ *   4. a bad assignment (step 6 of the tracker): every requested link row is NaN, fail = 0, status = 1, the clock stays.
+ * GMR_TRACKER_NO_ADVANCE computes every output at the current clocks and leaves the tracker's state as it is (no clock advance,
+ * no redraw, finished = 0): after gmr_motion_tracker_reset_dev that is reference-state initialisation.
+ * The link scales start at (0.3 m, 0.8 rad, 2.0 m/s, 4.0 rad/s) with weights of one and fail_dist = +inf: a choice of this
+ * library, the reference has no link terms.  The plan of the walk, the weights and the term constants travel with every launch,
+ * so launches already enqueued keep theirs.  The FK handle must outlive the tracker; the tracker stays single-stream. */
+#define GMR_TRACKER_FRAME_WORLD 0
+#define GMR_TRACKER_FRAME_HEADING 1
+#define GMR_TRACKER_NO_ADVANCE 1
+#define GMR_TRACKER_LINK_TERMS 4
+typedef struct {            /* link outputs of a step: device pointers (gmr_motion_tracker_step_links: host), each may be NULL */
+  float *ref_body_pos, *ref_body_rot, *ref_body_vel, *ref_body_ang_vel;   /* [N][nsel][3|4|3|3]                  */
+  float *link_err, *link_term;                                            /* [N][4]; need the simulator's links  */
+  float *max_dist;                                                        /* [N];    needs the simulator's links */
+  int32_t *fail;                                                          /* [N];    needs the simulator's links */
+} gmr_tracker_links_out_t;
+/* The simulator's rigid-body state: selection row s of environment e is read at base[e * env_stride + sim_body[s] * body_stride],
+ * strides in floats.  A packed [N][nb][13] tensor (pos 3, quat xyzw 4, vel 3, ang vel 3) is the four pointers at offsets
+ * 0 / 3 / 7 / 10 with strides 13 nb and 13.  env_stride = body_stride = 0 stands for four separate contiguous arrays
+ * [N][nsel][3|4|3|3] with their natural strides (nsel k and k).  Both layouts give the same bits. */
+typedef struct {
+  const float *body_pos, *body_rot /* xyzw */, *body_vel, *body_ang_vel;   /* each may be NULL */
+  int64_t env_stride, body_stride;
+} gmr_tracker_links_sim_t;
+/* HOST arrays, validated here: body_sel i32[nsel] distinct bodies of the tree, or NULL for all of them in order (nsel = nbody);
+ * sim_body i32[nsel] in [0, 2^16) or NULL for the identity; link_weight f32[nsel] finite, not negative and not all zero, or NULL
+ * (ones); frame GMR_TRACKER_FRAME_*.  nsel = 0 detaches the links (the other arguments are ignored). */
+int gmr_motion_tracker_set_links(gmr_motion_tracker_t* t, gmr_fk_t* fk, const int32_t* body_sel, int nsel, const int32_t* sim_body,
+                                 const float* link_weight, int frame);
+/* scale f32[4] positive and finite, weight f32[4] finite (0 skips the term), either may be NULL and is then kept; fail_dist > 0
+ * (+inf allowed) is set by every call */
+int gmr_motion_tracker_set_link_terms(gmr_motion_tracker_t* t, const float* scale, const float* weight, float fail_dist);
+/* One link step in one launch.  sim, links_sim, out and links_out may each be NULL; err / term need sim, total needs sim or
+ * links_sim, link_err / link_term / max_dist / fail need links_sim.  Without attached links every pointer of links_out must be
+ * NULL and links_sim is not looked at: a plain step with flags.  flags: GMR_TRACKER_NO_ADVANCE. */
+int gmr_motion_tracker_step_links_dev(gmr_motion_tracker_t* t, const gmr_tracker_sim_t* sim, const gmr_tracker_links_sim_t* links_sim,
+                                      const gmr_tracker_out_t* out, const gmr_tracker_links_out_t* links_out, int flags,
+                                      void* stream);                             /* asynchronous */
+/* host buffers; synchronises and holds the tracker's mutex.  Each given array of links_sim is copied from its first float to the
+ * last one the strides reach (arrays that interleave in one tensor are copied once). */
+int gmr_motion_tracker_step_links(gmr_motion_tracker_t* t, const gmr_tracker_sim_t* sim, const gmr_tracker_links_sim_t* links_sim,
+                                  const gmr_tracker_out_t* out, const gmr_tracker_links_out_t* links_out, int flags);
+
 /* ---- multi-GPU: one rank per GPU, ONE broadcast, no per-step collective ------------ */
 /* The reference parallelises over files with mp.Pool on one CPU (scripts/smplx_to_robot_dataset.py:241-242); here
  * streams shard over the ranks of one node and the only data that crosses ranks is the packed robot model + task set.
