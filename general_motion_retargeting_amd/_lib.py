@@ -127,6 +127,9 @@ _SIGS = {
     "gmr_motion_tracker_set_link_terms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float]),
     "gmr_motion_tracker_step_links_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "gmr_motion_tracker_step_links": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "gmr_motion_tracker_set_preview": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "gmr_motion_tracker_preview_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gmr_motion_tracker_preview": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gmr_comm_create": (C.c_int, [C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),
     "gmr_comm_destroy": (C.c_int, [C.c_void_p]),
     "gmr_comm_rank": (C.c_int, [C.c_void_p]),
@@ -568,6 +571,12 @@ TRACKER_LINKS_SIM_FIELDS = ("body_pos", "body_rot", "body_vel", "body_ang_vel")
 TRACKER_LINK_TERMS = 4
 TRACKER_FRAME_WORLD, TRACKER_FRAME_HEADING = 0, 1
 TRACKER_NO_ADVANCE = 1
+
+
+# gmr_motion_tracker_set_preview: the block bits in row order, the frames and the limits (include/gmr_hip.h, "tracker preview")
+PREVIEW_BLOCKS = {"root_pos": 1, "root_quat": 2, "root_rot6": 4, "root_vel": 8, "root_ang_vel": 16, "dof_pos": 32, "dof_vel": 64, "body_pos": 128}
+PREVIEW_FRAME_RAW, PREVIEW_FRAME_REFERENCE, PREVIEW_FRAME_SIM = 0, 1, 2
+PREVIEW_MAX_OFFSETS, PREVIEW_MAX_BODIES = 16, 32
 
 
 class TrackerLinksOut(C.Structure):

@@ -1,6 +1,7 @@
 // gmr_handles.h -- the handles of the C-ABI that more than one translation unit of libgmrhip.so looks into (not part of the
 // C-ABI): the FK tree (created in gmr_abi.hip) and the motion library (gmr_motion.hip), both read by gmr_body_state.hip, and
-// the motion tracker (gmr_tracker.hip), which is bound to a library and, with links attached (gmr_tracker_links.hip), to an FK tree.
+// the motion tracker (gmr_tracker.hip), which is bound to a library and, with links attached (gmr_tracker_links.hip), to an FK tree;
+// gmr_tracker_preview.hip reads its state and tables.
 #pragma once
 #include <stdint.h>
 
@@ -54,6 +55,15 @@ struct TrackerState {
   uint32_t* ignored;   // [1] environment ids outside [0, N) met by reset / assign since creation
   const double* cdf;   // [C] with clip weights: cdf[k] = (w_0 + .. + w_{k-1}) / sum, else null
 };
+constexpr int PREVIEW_MAX_OFFSETS = 16;   // clock offsets of a preview
+constexpr int PREVIEW_MAX_BODIES = 32;    // library bodies of its body block
+// the preview of a tracker: validated on the host, travels as a kernel argument like TrackerTables
+struct PreviewPlan {
+  int32_t K = 0;                            // offsets; 0: no preview configured
+  int32_t blocks = 0, frame = 0, nsel = 0;  // GMR_PREVIEW_* block bits, GMR_PREVIEW_FRAME_*, bodies of the body block
+  float offset[PREVIEW_MAX_OFFSETS] = {};   // seconds, finite
+  int16_t body[PREVIEW_MAX_BODIES] = {};    // rows of the library's local_body_pos, distinct
+};
 }  // namespace gmr
 
 struct gmr_motion_tracker {
@@ -64,6 +74,7 @@ struct gmr_motion_tracker {
   gmr::TrackerTables tab;
   gmr::LinkPlan links;           // links.nsel = 0 until gmr_motion_tracker_set_links attaches a selection
   const gmr_fk* fk = nullptr;    // not owned: the tree of the attached links outlives the tracker
+  gmr::PreviewPlan preview;      // preview.K = 0 until gmr_motion_tracker_set_preview configures one
   gmr::TrackerState S;
   gmr::DeviceBlock block;
   std::mutex mu;                 // the tables, and the whole of every synchronous entry point

@@ -5,7 +5,9 @@ What the reference's ``booster_gym/envs/t1_imitation.py`` does per environment a
 ``_reset_finished_motions`` / ``_reset_idx`` (:201-235) and the six ``_reward_imitation_*`` terms (:249-309) -- for N environments
 bound to one :class:`MotionLibrary`: every environment's clip and float32 clock live on the device, and :meth:`MotionTracker.step`
 is ONE kernel launch (``csrc/gmr_tracker.hip``).  Random draws are counter-based (Philox4x32-10 keyed by the seed, counter =
-environment and draw number), so a run is reproducible whatever the number of environments around it.
+environment and draw number), so a run is reproducible whatever the number of environments around it.  :meth:`MotionTracker.preview` is
+the observation half: the reference at every environment's clock plus a few offsets, packed as observation rows in
+one launch (``csrc/gmr_tracker_preview.hip``) that moves no clock.
 
 No GPU framework is imported here: :meth:`MotionTracker.step` takes and returns NumPy arrays, :meth:`MotionTracker.step_dev` reads
 and writes device memory the caller names -- ``_lib.DeviceBuffer``, a raw address, or anything with ``data_ptr()``.
@@ -25,6 +27,10 @@ MAX_DOF = 64
 LINK_TERMS = ("link_pos", "link_rot", "link_vel", "link_ang_vel")
 DEFAULT_LINK_SCALES = (0.3, 0.8, 2.0, 4.0)               # m, rad, m/s, rad/s: a choice of this library, the reference has no link terms
 FRAMES = {"world": 0, "heading": 1}
+PREVIEW_BLOCKS = ("root_pos", "root_quat", "root_rot6", "root_vel", "root_ang_vel", "dof_pos", "dof_vel", "body_pos")      # row order
+PREVIEW_SAMPLER_BLOCKS = ("root_pos", "root_quat", "root_vel", "root_ang_vel", "dof_pos", "dof_vel")
+PREVIEW_FRAMES = {"raw": 0, "reference": 1, "sim": 2}
+PREVIEW_MAX_OFFSETS, PREVIEW_MAX_BODIES = 16, 32
 LINK_SIM = {"body_pos": (0, 3), "body_rot": (3, 4), "body_vel": (7, 3), "body_ang_vel": (10, 3)}      # offset and width in a packed row of 13
 
 
@@ -104,6 +110,7 @@ class MotionTracker:
                                                         _lib._ptr(w), _lib._ptr(cw), self.seed, C.byref(h)))
         self.handle, self.nrobot_dof = h, R
         self._links = None            # (fk, nsel, sim_body, frame) once set_links has attached a selection
+        self._preview = None          # (K, blocks in row order, frame, nsel) once set_preview has configured one
         if sc is not None or wt is not None:
             self.set_terms(sc, wt)
 
@@ -439,6 +446,146 @@ class MotionTracker:
         _lib.check(_lib.lib().gmr_motion_tracker_step_links_dev(self.handle, None if st is None else C.byref(st), None if ls is None else C.byref(ls),
                                                                 C.byref(table), C.byref(ltable), 0 if advance else _lib.TRACKER_NO_ADVANCE,
                                                                 _lib._s(stream)))
+
+    # ---- preview ------------------------------------------------------------------------------------
+    def _preview_setup(self, offsets, blocks, frame, bodies):
+        """the checks of :meth:`set_preview`, all of them before a device is touched: ``(offsets f32[K], blocks in row order, block
+        bits, sel i32[nsel] or None)``"""
+        from . import _lib
+        off = np.ascontiguousarray(offsets, dtype=np.float32).reshape(-1)
+        if not 1 <= len(off) <= PREVIEW_MAX_OFFSETS:
+            raise ValueError(f"a preview holds 1 to {PREVIEW_MAX_OFFSETS} offsets, got {len(off)}")
+        if not np.isfinite(off).all():
+            raise ValueError(f"offsets must be finite: {off.tolist()}")
+        if isinstance(blocks, str):
+            blocks = (blocks,)
+        unknown = sorted(set(blocks) - set(PREVIEW_BLOCKS))
+        if unknown:
+            raise ValueError(f"unknown preview blocks {unknown} (known: {list(PREVIEW_BLOCKS)})")
+        names = tuple(b for b in PREVIEW_BLOCKS if b in blocks)
+        if not names:
+            raise ValueError("a preview needs at least one block")
+        if frame not in PREVIEW_FRAMES:
+            raise ValueError(f"frame is one of {sorted(PREVIEW_FRAMES)}, got {frame!r}")
+        lib = self.library
+        if frame != "raw" and "root_ang_vel" in names and lib.ang_vel != "world":
+            raise ValueError(f'root_ang_vel in frame "{frame}" needs a library built with ang_vel="world": the root_ang_vel of '
+                             f'ang_vel="{lib.ang_vel}" is not a physical angular velocity and cannot be rotated')
+        sel = None
+        if "body_pos" in names:
+            if not lib.has_local_body_pos:
+                raise ValueError("the body_pos block needs a library that holds local_body_pos")
+            if bodies is None or len(bodies) == 0:
+                raise ValueError("the body_pos block needs bodies=: rows of the library's local_body_pos, by index or by name")
+            ids = []
+            for b in bodies:
+                if isinstance(b, str):
+                    lists = lib.link_body_lists
+                    if not lists or not lists[0] or any(list(x) != list(lists[0]) for x in lists):
+                        raise ValueError("bodies by name need every clip of the library to carry the same non-empty link_body_list")
+                    if b not in lists[0]:
+                        raise KeyError(f"unknown body {b!r}")
+                    ids.append(list(lists[0]).index(b))
+                else:
+                    ids.append(int(b))
+            if not 1 <= len(ids) <= PREVIEW_MAX_BODIES:
+                raise ValueError(f"the body_pos block holds 1 to {PREVIEW_MAX_BODIES} bodies, got {len(ids)}")
+            for b in ids:
+                if not 0 <= b < lib.nbody:
+                    raise ValueError(f"body {b} outside [0, {lib.nbody})")
+            if len(set(ids)) != len(ids):
+                raise ValueError("a selection names every body once")
+            sel = np.array(ids, dtype=np.int32)
+        elif bodies is not None and len(bodies):
+            raise ValueError("bodies= is given but body_pos is not among the blocks")
+        return off, names, sum(_lib.PREVIEW_BLOCKS[b] for b in names), sel
+
+    @property
+    def preview_layout(self) -> Optional[Dict[str, object]]:
+        """``{block: slice into the last axis of obs, ..., "row_width": D}`` of the configured preview under the current dof tables,
+        or ``None``"""
+        if self._preview is None:
+            return None
+        _, names, _, nsel = self._preview
+        width = {"root_pos": 3, "root_quat": 4, "root_rot6": 6, "root_vel": 3, "root_ang_vel": 3, "dof_pos": self.nrobot_dof,
+                 "dof_vel": self.nrobot_dof, "body_pos": 3 * nsel}
+        out, at = {}, 0
+        for b in names:
+            out[b] = slice(at, at + width[b])
+            at += width[b]
+        out["row_width"] = at
+        return out
+
+    def set_preview(self, offsets, blocks=PREVIEW_SAMPLER_BLOCKS, frame: str = "raw", bodies=None) -> Optional[Dict[str, object]]:
+        """Configures the preview: ``offsets`` (1 to 16, seconds, any sign and order) added to every environment's clock, ``blocks`` out
+        of :data:`PREVIEW_BLOCKS` (packed in that order whatever order they are named in), ``frame`` -- ``"raw"`` as sampled,
+        ``"reference"`` relative to the reference root at the environment's current clock with its yaw removed, ``"sim"`` relative to the
+        simulator's ``base_pos / base_quat`` -- and, for ``body_pos``, ``bodies``: rows of the library's ``local_body_pos`` by index, or
+        by name when every clip carries the same ``link_body_list``.  Returns :attr:`preview_layout`.  ``offsets=[]`` removes the
+        configuration.  Previews already enqueued keep the configuration they were launched with."""
+        from . import _lib
+        if offsets is None or np.size(offsets) == 0:
+            _lib.check(_lib.lib().gmr_motion_tracker_set_preview(self.handle, 0, None, 0, 0, None, 0, None))
+            self._preview = None
+            return None
+        off, names, bits, sel = self._preview_setup(offsets, blocks, frame, bodies)
+        D = C.c_int()
+        _lib.check(_lib.lib().gmr_motion_tracker_set_preview(self.handle, len(off), _lib._ptr(off), bits, PREVIEW_FRAMES[frame], _lib._ptr(sel),
+                                                             0 if sel is None else len(sel), C.byref(D)))
+        self._preview = (len(off), names, frame, 0 if sel is None else len(sel))
+        assert self.preview_layout["row_width"] == D.value, (self.preview_layout, D.value)
+        return self.preview_layout
+
+    def _check_preview(self, sim, what):
+        """the checks of a preview that need no device -> ``(K, D, frame)``"""
+        if self._preview is None:
+            raise ValueError("the tracker has no preview configured: call set_preview() first")
+        K, _, frame, _ = self._preview
+        if sim is not None:
+            unknown = sorted(set(sim) - set(self._counts()[1]))
+            if unknown:
+                raise TypeError(f"{what}: unknown simulator arrays {unknown}")
+        if frame == "sim" and (sim is None or sim.get("base_pos") is None or sim.get("base_quat") is None):
+            raise ValueError('frame="sim" needs base_pos and base_quat of the simulator\'s root in sim')
+        return K, self.preview_layout["row_width"], frame
+
+    def preview(self, sim: Optional[Dict[str, np.ndarray]] = None) -> Dict[str, np.ndarray]:
+        """The reference at every environment's clock plus each offset, host arrays out: ``obs [N,K,D]`` (see :attr:`preview_layout`),
+        ``valid i32[N,K]`` -- 1 where the query lies inside the clip, neither wrapped nor clamped -- and ``status i32[N]``, 1 for a bad
+        assignment (its rows are NaN).  One launch; clocks, clips and draw counters stay as they are.  ``sim`` is read in
+        ``frame="sim"`` only: ``base_pos [N,3]``, ``base_quat [N,4]`` xyzw."""
+        from . import _lib
+        N = self.num_envs
+        K, D, frame = self._check_preview(sim, "preview")
+        st, keep = None, []
+        if frame == "sim":
+            st = _lib.TrackerSim()
+            for k, w in (("base_pos", 3), ("base_quat", 4)):
+                a = np.ascontiguousarray(sim[k], dtype=np.float32)
+                if a.shape != (N, w):
+                    raise ValueError(f"{k}: shape {a.shape}, {(N, w)} needed")
+                keep.append(a)
+                setattr(st, k, a.ctypes.data)
+        out = {"obs": np.empty((N, K, D), np.float32), "valid": np.empty((N, K), np.int32), "status": np.empty(N, np.int32)}
+        _lib.check(_lib.lib().gmr_motion_tracker_preview(self.handle, None if st is None else C.byref(st), _lib._ptr(out["obs"]),
+                                                         _lib._ptr(out["valid"]), _lib._ptr(out["status"])))
+        return out
+
+    def preview_dev(self, sim: Optional[Dict[str, object]] = None, stream=None, obs=None, valid=None, status=None) -> None:
+        """:meth:`preview` on device memory, asynchronous on ``stream`` (the tracker's stream, or one the caller orders behind it):
+        whichever of ``obs f32[N*K*D]``, ``valid i32[N*K]``, ``status i32[N]`` are wanted, each a ``_lib.DeviceBuffer``, a raw address or
+        an object with ``data_ptr()``."""
+        from . import _lib
+        N = self.num_envs
+        K, D, frame = self._check_preview(sim, "preview_dev")
+        st = None
+        if frame == "sim":
+            st = _lib.TrackerSim()
+            for k, w in (("base_pos", 3), ("base_quat", 4)):
+                setattr(st, k, _dev_ptr(sim[k], k, "float32", N * w).value)
+        _lib.check(_lib.lib().gmr_motion_tracker_preview_dev(self.handle, None if st is None else C.byref(st),
+                                                             _dev_ptr(obs, "obs", "float32", N * K * D), _dev_ptr(valid, "valid", "int32", N * K),
+                                                             _dev_ptr(status, "status", "int32", N), _lib._s(stream)))
 
     def close(self) -> None:
         h = getattr(self, "handle", None)

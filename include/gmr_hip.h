@@ -619,6 +619,67 @@ int gmr_motion_tracker_step_links_dev(gmr_motion_tracker_t* t, const gmr_tracker
 int gmr_motion_tracker_step_links(gmr_motion_tracker_t* t, const gmr_tracker_sim_t* sim, const gmr_tracker_links_sim_t* links_sim,
                                   const gmr_tracker_out_t* out, const gmr_tracker_links_out_t* links_out, int flags);
 
+/* ---- N6: tracker preview (future reference frames as observation rows of a motion tracker) ---- */
+/* The observation half of an imitation environment (the stub `include_reference_in_obs` of t1_imitation.py:236-245): a tracker
+ * may have a PREVIEW configured -- 1 <= K <= 16 clock offsets in seconds (finite, any sign, any order; typically 0, dt, 2 dt ..),
+ * a set of blocks, a frame and, for the body block, 1 <= nsel <= 32 distinct rows of the library's local_body_pos.  A preview
+ * call is ONE launch that reads the tracker's state and WRITES NOTHING of the tracker (no clock, no draw counter) and nothing of
+ * the library: observations are taken after the resets that follow a step, at the clocks the next step will sample.
+ * Per environment e and offset k: tq = (double)time[e] + (double)offset[k]; the library is sampled at (clip[e], tq) with the
+ * tracker's loop flag by the code of gmr_motion_sample_dev (the same bits), so with offset 0 a preview shows the reference rows
+ * the next step will emit.  obs f32 [N][K][D]: the selected blocks in this order, a block that is not selected takes no room,
+ * D = the sum of the widths (R: the robot dofs of the tables the launch travels with):
+ *   block          width    GMR_PREVIEW_FRAME_RAW             GMR_PREVIEW_FRAME_REFERENCE / _SIM
+ *   ROOT_POS       3        sampled root_pos                  Rz(-psi_a) (p - p_a)
+ *   ROOT_QUAT      4        sampled root_rot xyzw             q_rel = conj(q_psi_a) q, xyzw
+ *   ROOT_ROT6      6        columns 0 and 1 of R(q)           columns 0 and 1 of R(q_rel)
+ *   ROOT_VEL       3        sampled root_vel                  Rz(-psi_a) v
+ *   ROOT_ANG_VEL   3        sampled root_ang_vel              Rz(-psi_a) w
+ *   DOF_POS        R        robot dof order through dof_map, dof_default[j] where the map is -1 (as in a step); every frame
+ *   DOF_VEL        R        through dof_map, 0 where the map is -1; every frame
+ *   BODY_POS       3 nsel   sampled local_body_pos rows       Rz(-psi_a) (p + R(q) l_b - p_a)
+ * (p, q, v, w, l_b): the sampled root position, quaternion, velocity, angular velocity and local body position at tq.
+ * q_psi = normalize(0, 0, q.z, q.w), the identity where z = w = 0; Rz(-psi) from it as c = w'^2 - z'^2, s = 2 z' w',
+ * (x, y, z) -> (c x + s y, c y - s x, z): the heading frame of the tracker links.  R(q), q xyzw NOT renormalised:
+ * col0 = (1 - 2(y^2 + z^2), 2(xy + zw), 2(xz - yw)), col1 = (2(xy - zw), 1 - 2(x^2 + z^2), 2(yz + xw)), written col0 then col1;
+ * R(q) l = l + w t + u x t, t = 2 (u x l), u = (x, y, z).  All of it float32 with one rounding per operation.
+ * The anchor (p_a, q_a): FRAME_REFERENCE -- the reference root at the environment's current clock (the query at offset 0, whether
+ * or not 0 is among the offsets); FRAME_SIM -- base_pos[e], base_quat[e] of gmr_tracker_sim_t, the only two members read and
+ * then mandatory.
+ *   valid i32 [N][K]  1 iff 0 <= tq <= duration - 1 / fps of the clip in float64 (inside the clip: neither wrapped by the loop
+ *                     nor clamped), else 0.  The values of a wrapped or clamped frame are written all the same.
+ *   status i32 [N]    step 6 of the tracker: a clip id outside [0, C), an empty clip or a non-finite clock -- every obs float of
+ *                     e NaN, its valid 0, status 1 (else 0), nothing of the library read.
+ * obs, valid and status may each be NULL.  The configuration is host state that travels with each launch as a kernel argument:
+ * replacing it needs no copy and no synchronisation, launches already enqueued keep theirs; gmr_motion_tracker_set_dof_map may
+ * change R and with it D.  The tracker stays single-stream: a preview reads what a step or reset writes. */
+#define GMR_PREVIEW_ROOT_POS 1
+#define GMR_PREVIEW_ROOT_QUAT 2
+#define GMR_PREVIEW_ROOT_ROT6 4
+#define GMR_PREVIEW_ROOT_VEL 8
+#define GMR_PREVIEW_ROOT_ANG_VEL 16
+#define GMR_PREVIEW_DOF_POS 32
+#define GMR_PREVIEW_DOF_VEL 64
+#define GMR_PREVIEW_BODY_POS 128
+#define GMR_PREVIEW_FRAME_RAW 0
+#define GMR_PREVIEW_FRAME_REFERENCE 1
+#define GMR_PREVIEW_FRAME_SIM 2
+#define GMR_PREVIEW_MAX_OFFSETS 16
+#define GMR_PREVIEW_MAX_BODIES 32
+/* HOST arrays, validated here: offsets f32[K], body_sel i32[nsel] rows of local_body_pos (looked at only with BODY_POS, and
+ * then mandatory).  K = 0 removes the configuration (the other arguments are ignored).  GMR_ERR_ARG: K or nsel out of range, a
+ * non-finite offset, unknown block bits, no block, an unknown frame, BODY_POS without a selection or on a library filled without
+ * local_body_pos, a body outside [0, nbody) or listed twice, a selection without BODY_POS, ROOT_ANG_VEL in an anchored frame on
+ * a library filled with GMR_MOTION_ANGVEL_REFERENCE (that row is not a vector to rotate).  *row_width (may be NULL) = D under
+ * the current dof tables. */
+int gmr_motion_tracker_set_preview(gmr_motion_tracker_t* t, int K, const float* offsets, int blocks, int frame, const int32_t* body_sel,
+                                   int nsel, int* row_width);
+/* One preview in one launch; GMR_ERR_ARG without a configured preview and in FRAME_SIM without base_pos / base_quat. */
+int gmr_motion_tracker_preview_dev(gmr_motion_tracker_t* t, const gmr_tracker_sim_t* sim, float* d_obs, int32_t* d_valid,
+                                   int32_t* d_status, void* stream);             /* asynchronous */
+/* host buffers; default stream, synchronises and holds the tracker's mutex */
+int gmr_motion_tracker_preview(gmr_motion_tracker_t* t, const gmr_tracker_sim_t* sim, float* obs, int32_t* valid, int32_t* status);
+
 /* ---- multi-GPU: one rank per GPU, ONE broadcast, no per-step collective ------------ */
 /* The reference parallelises over files with mp.Pool on one CPU (scripts/smplx_to_robot_dataset.py:241-242); here
  * streams shard over the ranks of one node and the only data that crosses ranks is the packed robot model + task set.
