@@ -1,9 +1,12 @@
 // gmr_handles.h -- the handles of the C-ABI that more than one translation unit of libgmrhip.so looks into (not part of the
 // C-ABI): the FK tree (created in gmr_abi.hip) and the motion library (gmr_motion.hip), both read by gmr_body_state.hip, and
 // the motion tracker (gmr_tracker.hip), which is bound to a library and, with links attached (gmr_tracker_links.hip), to an FK tree;
-// gmr_tracker_preview.hip reads its state and tables.
+// gmr_tracker_preview.hip reads its state and tables, gmr_tracker_adaptive.hip owns its bins (adaptive sampling, masked resets).
 #pragma once
 #include <stdint.h>
+
+#include <mutex>
+#include <vector>
 
 #include "../../include/gmr_hip.h"
 #include "gmr_fk_tree.h"
@@ -47,6 +50,15 @@ struct TrackerTables {
   float dof_default[TRACKER_MAX_DOF], dof_weight[TRACKER_MAX_DOF];
   float scale[TRACKER_TERMS], weight[TRACKER_TERMS];
 };
+// What a draw from the bins of adaptive sampling reads.  The step kernels reach it through ONE pointer of TrackerState, so that a plain
+// step carries eight more bytes of kernel arguments than before and nothing else; the adaptive kernels take it by value.
+struct AdaptiveBins {
+  int32_t nbins;                 // Bt
+  const double* cdf;             // [Bt] cdf[b] = p[0] + .. + p[b-1], written by tracker_adapt_cdf_kernel
+  const int32_t* start;          // [C + 1] first bin of every clip
+  const int32_t* clip;           // [Bt] the clip of a bin
+  const int32_t* frames;         // [C] F_c, frames per bin (at most max(T_c, 1))
+};
 // the tracker's own device memory (one block)
 struct TrackerState {
   int32_t* clip;       // [N]
@@ -54,6 +66,26 @@ struct TrackerState {
   uint32_t* draws;     // [N] Philox draws made for the environment so far
   uint32_t* ignored;   // [1] environment ids outside [0, N) met by reset / assign since creation
   const double* cdf;   // [C] with clip weights: cdf[k] = (w_0 + .. + w_{k-1}) / sum, else null
+  const AdaptiveBins* bins;   // adaptive sampling: the table a draw from the bins reads, ON THE DEVICE; null on a plain tracker
+};
+constexpr int ADAPT_MAX_K = 16;       // look-ahead of adaptive sampling, in bins
+constexpr int ADAPT_CHUNK = 64;       // bins one lane sums in order (tracker_adapt_cdf_kernel)
+constexpr int ADAPT_TILE = 4096;      // bins per workgroup of tracker_adapt_score_kernel: one partial sum each
+constexpr int ADAPT_MAX_BINS = 1 << 22;
+// the parameters of an Adapt; travel as a kernel argument like TrackerTables, so replacing them never touches a launch in flight
+struct AdaptivePlan {
+  int32_t Bt = 0;                // bins; 0: adaptive sampling is off
+  int32_t K = 1;                 // look-ahead, 1 .. ADAPT_MAX_K
+  double alpha = 0.0, uniform = 1.0;
+  double g[ADAPT_MAX_K] = {};    // g[u] = gamma^u by repeated multiplication
+};
+// what only the adaptive kernels touch (device pointers into the tracker's adaptive block)
+struct AdaptiveArrays {
+  const double* base;            // [Bt] Wn_c frames(b) / T_c
+  uint32_t* fail_now;            // [Bt] failures recorded since the last Adapt
+  double *ema, *prob;            // [Bt]
+  double* cdf;                   // [Bt] (AdaptiveBins::cdf, writable)
+  double *part, *tot;            // [ceil(Bt / ADAPT_TILE)], [ceil(Bt / ADAPT_CHUNK)] scratch of an Adapt
 };
 constexpr int PREVIEW_MAX_OFFSETS = 16;   // clock offsets of a preview
 constexpr int PREVIEW_MAX_BODIES = 32;    // library bodies of its body block
@@ -77,5 +109,11 @@ struct gmr_motion_tracker {
   gmr::PreviewPlan preview;      // preview.K = 0 until gmr_motion_tracker_set_preview configures one
   gmr::TrackerState S;
   gmr::DeviceBlock block;
+  gmr::AdaptivePlan adaptive;    // adaptive.Bt = 0 until gmr_motion_tracker_set_adaptive configures the bins
+  gmr::AdaptiveBins bin_tab = {}; // the host's copy of *S.bins
+  gmr::AdaptiveArrays bins = {};
+  gmr::DeviceBlock bin_block;    // every array of adaptive sampling: one allocation, made by set_adaptive
+  double bin_seconds = 0.0;      // what the bins were built with
+  std::vector<double> clip_w;    // the clip weights as given at creation (empty: uniform)
   std::mutex mu;                 // the tables, and the whole of every synchronous entry point
 };

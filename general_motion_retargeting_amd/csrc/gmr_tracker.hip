@@ -144,24 +144,15 @@ __global__ __launch_bounds__(256) void tracker_step_kernel(const MotionArrays A,
     int finished = 0;
     if (!loop && tn >= S.length[e]) {                                // :201-213
       int nc = c;
-      (void)tracker_draw(A, S, key0, key1, e, true, &nc);
+      tn = tracker_redraw(A, S, key0, key1, e, &nc);
       S.clip[e] = nc;
       S.length[e] = clip_length(A, nc);
-      tn = 0.0f;
       finished = 1;
     }
     S.time[e] = tn;
     if (O.status) O.status[e] = 0;
     if (O.finished) O.finished[e] = finished;
   }
-}
-
-// the environment of lane i of a reset / assign: ids[i], or i itself without a list; -1 (and counted) outside [0, N)
-__device__ __forceinline__ int tracker_env(const TrackerState& S, const int32_t* __restrict__ ids, int i, int N) {
-  const int e = ids ? ids[i] : i;
-  if (e >= 0 && e < N) return e;
-  atomicAdd(S.ignored, 1u);
-  return -1;
 }
 
 __global__ __launch_bounds__(256) void tracker_reset_kernel(const MotionArrays A, const TrackerState S, int N, int n,
@@ -219,15 +210,15 @@ static int tracker_tables(const gmr_motion_lib* lib, int R, const int32_t* dof_m
 static dim3 one_lane_each(int n) { return dim3((unsigned)((n + 255) / 256)); }
 
 // what the two step entry points share once the tables are in hand
-static int tracker_step_launch(gmr_motion_tracker* t, const TrackerTables& T, const gmr_tracker_sim_t* sim, const gmr_tracker_out_t* out,
-                               hipStream_t stream) {
+static int tracker_step_launch(gmr_motion_tracker* t, const TrackerState& S, const TrackerTables& T, const gmr_tracker_sim_t* sim,
+                               const gmr_tracker_out_t* out, hipStream_t stream) {
   if (!sim && (out->err || out->term || out->total)) return gmr_fail(GMR_ERR_ARG, "err / term / total need the simulator's state");
   const TrackerSim X = sim ? TrackerSim{sim->base_pos, sim->base_quat, sim->base_lin_vel, sim->base_ang_vel, sim->dof_pos, sim->dof_vel}
                            : TrackerSim{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   const TrackerOut O{out->ref_root_pos, out->ref_root_rot, out->ref_root_vel, out->ref_root_ang_vel, out->ref_dof_pos, out->ref_dof_vel,
                      out->err, out->term, out->total, out->status, out->finished};
   const int per_block = 256 / MOTION_GROUP;
-  hipLaunchKernelGGL(tracker_step_kernel, dim3((unsigned)((t->N + per_block - 1) / per_block)), dim3(256), 0, stream, t->lib->A, t->S, T, t->N,
+  hipLaunchKernelGGL(tracker_step_kernel, dim3((unsigned)((t->N + per_block - 1) / per_block)), dim3(256), 0, stream, t->lib->A, S, T, t->N,
                      t->loop, t->dtf, t->key[0], t->key[1], X, O);
   GMR_HIP_TRY(hipGetLastError());
   return GMR_OK;
@@ -275,6 +266,7 @@ int gmr_motion_tracker_create(const gmr_motion_lib_t* lib, int N, double dt, int
   const float scale[gmr::TRACKER_TERMS] = {0.5f, 0.5f, 2.0f, 1.0f, 1.0f, 0.1f};      // T1Imitation.yaml:327-332
   for (int k = 0; k < gmr::TRACKER_TERMS; k++) { t->tab.scale[k] = scale[k]; t->tab.weight[k] = 1.0f; }
   t->lib = lib; t->N = N; t->loop = (flags & GMR_MOTION_LOOP) ? 1 : 0;
+  if (clip_weights) t->clip_w.assign(clip_weights, clip_weights + C);
   t->dtf = (float)dt;
   t->key[0] = (uint32_t)seed; t->key[1] = (uint32_t)(seed >> 32);
   const size_t n = (size_t)N;
@@ -369,11 +361,12 @@ int gmr_motion_tracker_step_dev(gmr_motion_tracker_t* t, const gmr_tracker_sim_t
   if (!t) return gmr_fail(GMR_ERR_ARG, "null motion tracker");
   if (!out) return gmr_fail(GMR_ERR_ARG, "null output table");
   gmr::TrackerTables T;
+  gmr::TrackerState S;
   {
     std::lock_guard<std::mutex> g(t->mu);
-    T = t->tab;
+    T = t->tab; S = t->S;
   }
-  return gmr::tracker_step_launch(t, T, sim, out, (hipStream_t)stream);
+  return gmr::tracker_step_launch(t, S, T, sim, out, (hipStream_t)stream);
 }
 
 int gmr_motion_tracker_assign(gmr_motion_tracker_t* t, int n, const int32_t* env_ids, const int32_t* clip, const float* time, int* ignored) {
@@ -457,7 +450,7 @@ int gmr_motion_tracker_step(gmr_motion_tracker_t* t, const gmr_tracker_sim_t* si
   const gmr_tracker_sim_t dsim{ds[0], ds[1], ds[2], ds[3], ds[4], ds[5]};
   const gmr_tracker_out_t dout{(float*)dv[0], (float*)dv[1], (float*)dv[2], (float*)dv[3], (float*)dv[4], (float*)dv[5],
                                (float*)dv[6], (float*)dv[7], (float*)dv[8], (int32_t*)dv[9], (int32_t*)dv[10]};
-  const int rc = gmr::tracker_step_launch(t, t->tab, sim ? &dsim : nullptr, &dout, nullptr);
+  const int rc = gmr::tracker_step_launch(t, t->S, t->tab, sim ? &dsim : nullptr, &dout, nullptr);
   if (rc != GMR_OK) return rc;
   GMR_HIP_TRY(hipDeviceSynchronize());
   for (int k = 0; k < 11; k++)

@@ -1,6 +1,7 @@
-// gmr_tracker_dev.h -- what the step kernels of the motion tracker share on the device: tracker_step_kernel (gmr_tracker.hip)
-// and tracker_links_kernel (gmr_tracker_links.hip).  One definition of the pointer tables, the clip length, the Philox draw and
-// the 16-lane sum, so that a link step leaves the same clocks, draws and term bits as a plain step.  Device code only.
+// gmr_tracker_dev.h -- what the kernels of the motion tracker share on the device: tracker_step_kernel (gmr_tracker.hip),
+// tracker_links_kernel (gmr_tracker_links.hip) and the masked reset (gmr_tracker_adaptive.hip).  One definition of the pointer tables,
+// the clip length, the Philox draws (by clip weight, and from the bins of adaptive sampling), the redraw of a finished clip and the
+// 16-lane sum, so that a link step leaves the same clocks, draws and term bits as a plain step.  Device code only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -52,6 +53,45 @@ __device__ __forceinline__ float tracker_draw(const MotionArrays& A, const Track
     }
   }
   return philox_unit(w[1]);
+}
+
+// One draw for environment e from the bins of adaptive sampling: the counter and key of tracker_draw,
+// word 0 picks the bin -- the largest b with cdf[b] <= word0 2^-32 --, word 1 the start inside it.  Returns the start time.
+__device__ __forceinline__ float tracker_draw_bin(const MotionArrays& A, const TrackerState& S, uint32_t key0, uint32_t key1, int e, int* clip) {
+  const uint32_t ctr[4] = {(uint32_t)e, S.draws[e], 0u, 0u}, key[2] = {key0, key1};
+  uint32_t w[4];
+  philox4x32(ctr, key, w);
+  S.draws[e] = ctr[1] + 1u;
+  const AdaptiveBins Bn = *S.bins;
+  const double x = (double)w[0] * 2.3283064365386963e-10;
+  int lo = 0, hi = Bn.nbins - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (Bn.cdf[mid] <= x) lo = mid; else hi = mid - 1;
+  }
+  const int c = Bn.clip[lo];
+  const long long F = Bn.frames[c], T = A.seg_start[c + 1] - A.seg_start[c];
+  const long long f0 = (long long)(lo - Bn.start[c]) * F;
+  const long long f1 = f0 + F < T ? f0 + F : T;                     // bin k covers frames [k F, min((k + 1) F, T))
+  const double u = (double)philox_unit(w[1]);
+  *clip = c;
+  return (float)(((double)f0 + u * (double)(f1 - f0)) / A.fps[c]);
+}
+
+// What a step does with a finished clip (loop off), for both step kernels: the new clip of environment e and its start time.  A
+// plain tracker draws the clip and starts at 0 (:201-213); an adaptive one takes clip and start from the bins, and records nothing.
+__device__ __forceinline__ float tracker_redraw(const MotionArrays& A, const TrackerState& S, uint32_t key0, uint32_t key1, int e, int* clip) {
+  if (S.bins) return tracker_draw_bin(A, S, key0, key1, e, clip);
+  (void)tracker_draw(A, S, key0, key1, e, true, clip);
+  return 0.0f;
+}
+
+// the environment of lane i of a reset / assign: ids[i], or i itself without a list; -1 (and counted) outside [0, N)
+__device__ __forceinline__ int tracker_env(const TrackerState& S, const int32_t* __restrict__ ids, int i, int N) {
+  const int e = ids ? ids[i] : i;
+  if (e >= 0 && e < N) return e;
+  atomicAdd(S.ignored, 1u);
+  return -1;
 }
 
 // the sum over the 16 lanes of an environment, in every one of them

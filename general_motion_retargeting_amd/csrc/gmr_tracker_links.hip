@@ -403,10 +403,9 @@ __global__ __launch_bounds__(64 * FK_MAX_WAVES) void tracker_links_kernel(const 
     float tn = S.time[e] + dtf;
     if (!loop && tn >= S.length[e]) {
       int nc = c;
-      (void)tracker_draw(A, S, key0, key1, (int)e, true, &nc);
+      tn = tracker_redraw(A, S, key0, key1, (int)e, &nc);
       S.clip[e] = nc;
       S.length[e] = clip_length(A, nc);
-      tn = 0.0f;
       finished = 1;
     }
     S.time[e] = tn;
@@ -416,7 +415,7 @@ __global__ __launch_bounds__(64 * FK_MAX_WAVES) void tracker_links_kernel(const 
 }
 
 // what the two step entry points share once the plan is in hand; every argument check of a link step
-static int links_step_launch(gmr_motion_tracker* t, const TrackerTables& T, const LinkPlan& P, const gmr_fk* fk, const gmr_tracker_sim_t* sim,
+static int links_step_launch(gmr_motion_tracker* t, const TrackerState& S, const TrackerTables& T, const LinkPlan& P, const gmr_fk* fk, const gmr_tracker_sim_t* sim,
                              const gmr_tracker_links_sim_t* lsim, const gmr_tracker_out_t* out, const gmr_tracker_links_out_t* lout, int flags,
                              hipStream_t stream) {
   if (flags & ~GMR_TRACKER_NO_ADVANCE) return gmr_fail(GMR_ERR_ARG, "unknown link step flag bits 0x%x", flags);
@@ -465,10 +464,10 @@ static int links_step_launch(gmr_motion_tracker* t, const TrackerTables& T, cons
   const FkTree* tree = fk ? fk->dev() : nullptr;
   const int advance = (flags & GMR_TRACKER_NO_ADVANCE) ? 0 : 1;
   if (want_ref)
-    hipLaunchKernelGGL(tracker_links_kernel<true>, grid, block, smem, stream, t->lib->A, tree, t->S, T, Pw, t->N, t->loop, advance, t->dtf,
+    hipLaunchKernelGGL(tracker_links_kernel<true>, grid, block, smem, stream, t->lib->A, tree, S, T, Pw, t->N, t->loop, advance, t->dtf,
                        t->key[0], t->key[1], X, Y, O, L);
   else
-    hipLaunchKernelGGL(tracker_links_kernel<false>, grid, block, smem, stream, t->lib->A, tree, t->S, T, Pw, t->N, t->loop, advance, t->dtf,
+    hipLaunchKernelGGL(tracker_links_kernel<false>, grid, block, smem, stream, t->lib->A, tree, S, T, Pw, t->N, t->loop, advance, t->dtf,
                        t->key[0], t->key[1], X, Y, O, L);
   GMR_HIP_TRY(hipGetLastError());
   return GMR_OK;
@@ -551,12 +550,13 @@ int gmr_motion_tracker_step_links_dev(gmr_motion_tracker_t* t, const gmr_tracker
   if (!t) return gmr_fail(GMR_ERR_ARG, "null motion tracker");
   gmr::TrackerTables T;
   gmr::LinkPlan P;
+  gmr::TrackerState S;
   const gmr_fk* fk;
   {
     std::lock_guard<std::mutex> g(t->mu);
-    T = t->tab; P = t->links; fk = t->fk;
+    T = t->tab; P = t->links; fk = t->fk; S = t->S;
   }
-  return gmr::links_step_launch(t, T, P, fk, sim, links_sim, out, links_out, flags, (hipStream_t)stream);
+  return gmr::links_step_launch(t, S, T, P, fk, sim, links_sim, out, links_out, flags, (hipStream_t)stream);
 }
 
 int gmr_motion_tracker_step_links(gmr_motion_tracker_t* t, const gmr_tracker_sim_t* sim, const gmr_tracker_links_sim_t* links_sim,
@@ -632,7 +632,7 @@ int gmr_motion_tracker_step_links(gmr_motion_tracker_t* t, const gmr_tracker_sim
                                (float*)dv[6], (float*)dv[7], (float*)dv[8], (int32_t*)dv[9], (int32_t*)dv[10]};
   const gmr_tracker_links_out_t dlout{(float*)dv[11], (float*)dv[12], (float*)dv[13], (float*)dv[14], (float*)dv[15], (float*)dv[16],
                                       (float*)dv[17], (int32_t*)dv[18]};
-  const int rc = gmr::links_step_launch(t, t->tab, P, t->fk, sim ? &dsim : nullptr, links_sim ? &dlsim : nullptr, &dout, &dlout, flags, nullptr);
+  const int rc = gmr::links_step_launch(t, t->S, t->tab, P, t->fk, sim ? &dsim : nullptr, links_sim ? &dlsim : nullptr, &dout, &dlout, flags, nullptr);
   if (rc != GMR_OK) return rc;
   GMR_HIP_TRY(hipDeviceSynchronize());
   for (int k = 0; k < 19; k++)

@@ -7,7 +7,9 @@ bound to one :class:`MotionLibrary`: every environment's clip and float32 clock 
 is ONE kernel launch (``csrc/gmr_tracker.hip``).  Random draws are counter-based (Philox4x32-10 keyed by the seed, counter =
 environment and draw number), so a run is reproducible whatever the number of environments around it.  :meth:`MotionTracker.preview` is
 the observation half: the reference at every environment's clock plus a few offsets, packed as observation rows in
-one launch (``csrc/gmr_tracker_preview.hip``) that moves no clock.
+one launch (``csrc/gmr_tracker_preview.hip``) that moves no clock.  :meth:`MotionTracker.reset_done` resets from done / failed masks in one
+launch and :meth:`MotionTracker.set_adaptive` draws episode starts where episodes recently failed (DESIGN.md section 6n,
+``csrc/gmr_tracker_adaptive.hip``).
 
 No GPU framework is imported here: :meth:`MotionTracker.step` takes and returns NumPy arrays, :meth:`MotionTracker.step_dev` reads
 and writes device memory the caller names -- ``_lib.DeviceBuffer``, a raw address, or anything with ``data_ptr()``.
@@ -31,6 +33,9 @@ PREVIEW_BLOCKS = ("root_pos", "root_quat", "root_rot6", "root_vel", "root_ang_ve
 PREVIEW_SAMPLER_BLOCKS = ("root_pos", "root_quat", "root_vel", "root_ang_vel", "dof_pos", "dof_vel")
 PREVIEW_FRAMES = {"raw": 0, "reference": 1, "sim": 2}
 PREVIEW_MAX_OFFSETS, PREVIEW_MAX_BODIES = 16, 32
+ADAPTIVE_MAX_BINS, ADAPTIVE_MAX_LOOKAHEAD = 1 << 22, 16
+# failure-driven start sampling: a choice of this library, the reference starts every motion at time 0
+DEFAULT_ADAPTIVE = {"bin_seconds": 1.0, "alpha": 0.1, "uniform": 0.3, "lookahead": 4, "gamma": 0.8}
 LINK_SIM = {"body_pos": (0, 3), "body_rot": (3, 4), "body_vel": (7, 3), "body_ang_vel": (10, 3)}      # offset and width in a packed row of 13
 
 
@@ -63,6 +68,30 @@ def _clip_weights(num_clips: int, clip_weights):
     if not np.isfinite(w).all() or (w < 0).any() or not w.sum() > 0:
         raise ValueError("clip_weights must be finite, not negative and not all zero")
     return w
+
+
+def _adaptive_bins(seg_start, fps, bin_seconds: float):
+    """``(bin_start i32[C + 1], frames i64[C])`` of the library under ``bin_seconds``: ``F_c = max(1, round-half-away(bin_seconds fps_c))``
+    frames per bin and ``ceil(T_c / F_c)`` bins per clip, as ``gmr_motion_tracker_set_adaptive`` builds them"""
+    seg = np.asarray(seg_start, dtype=np.int64)
+    T = np.diff(seg)
+    f = np.minimum(float(bin_seconds) * np.asarray(fps, dtype=np.float64), 2147483647.0)
+    whole = np.floor(f)
+    F = np.maximum((whole + (f - whole >= 0.5)).astype(np.int64), 1)
+    nb = -(-T // F)
+    return np.concatenate([[0], np.cumsum(nb)]), F
+
+
+def _mask(a, what: str, n: int):
+    """a done / failed mask of ``n`` entries as ``i32[n]`` (bool or integer in), or None"""
+    if a is None:
+        return None
+    a = np.asarray(a)
+    if a.dtype != np.bool_ and not np.issubdtype(a.dtype, np.integer):
+        raise TypeError(f"{what}: a mask is bool or integer, got {a.dtype}")
+    if a.shape != (n,):
+        raise ValueError(f"{what}: shape {a.shape}, {(n,)} needed")
+    return np.ascontiguousarray(a != 0, dtype=np.int32)
 
 
 def _terms(scales, weights, names=TERMS, default_scales=DEFAULT_SCALES):
@@ -111,6 +140,7 @@ class MotionTracker:
         self.handle, self.nrobot_dof = h, R
         self._links = None            # (fk, nsel, sim_body, frame) once set_links has attached a selection
         self._preview = None          # (K, blocks in row order, frame, nsel) once set_preview has configured one
+        self._adaptive = None         # (bin_seconds, bin_start i64[C + 1]) once set_adaptive has built the bins
         if sc is not None or wt is not None:
             self.set_terms(sc, wt)
 
@@ -157,7 +187,9 @@ class MotionTracker:
         return int(ignored.value)
 
     def reset_dev(self, n: int = 0, d_env_ids=None, resample: bool = True, time_offset_range: Sequence[float] = (0.0, 0.0), stream=None) -> None:
-        """:meth:`reset` with the ids (``i32[n]``, every environment once) on the device, asynchronous on ``stream``"""
+        """:meth:`reset` with the ids (``i32[n]``, every environment once) on the device, asynchronous on ``stream``.  A list that names
+        an environment twice gives that environment one of two outcomes (one draw or two) and touches no other; the masked form,
+        :meth:`reset_done_dev`, takes the flags themselves and cannot have that problem."""
         from . import _lib
         lo, hi = (float(x) for x in time_offset_range)
         _lib.check(_lib.lib().gmr_motion_tracker_reset_dev(self.handle, int(n), _dev_ptr(d_env_ids, "env_ids", "int32", int(n)),
@@ -172,13 +204,135 @@ class MotionTracker:
                                                             _lib._s(stream)))
 
     def state(self) -> Dict[str, np.ndarray]:
-        """``clip i32[N]``, ``time f32[N]``, ``length f32[N]``, ``draws u32[N]`` and ``ignored``, the ids outside ``[0, N)`` met so far"""
+        """``clip i32[N]``, ``time f32[N]``, ``length f32[N]``, ``draws u32[N]``, ``ignored``, the ids outside ``[0, N)`` met so far, and
+        ``adaptive``: whether :meth:`set_adaptive` has bins in place"""
         from . import _lib
         N = self.num_envs
         out = {"clip": np.empty(N, np.int32), "time": np.empty(N, np.float32), "length": np.empty(N, np.float32), "draws": np.empty(N, np.uint32)}
         ign = C.c_uint32()
         _lib.check(_lib.lib().gmr_motion_tracker_state(self.handle, *[_lib._ptr(out[k]) for k in ("clip", "time", "length", "draws")], C.byref(ign)))
         out["ignored"] = int(ign.value)
+        out["adaptive"] = getattr(self, "_adaptive", None) is not None
+        return out
+
+    # ---- adaptive sampling and masked resets (DESIGN.md section 6n) ---------------------------------------------------------
+    def _adaptive_setup(self, bin_seconds, alpha, uniform, lookahead, gamma):
+        """the checks of :meth:`set_adaptive`, all of them before a device is touched -> ``(bin_seconds, alpha, uniform, K, gamma,
+        bin_start)``"""
+        bin_seconds, alpha, uniform, gamma = float(bin_seconds), float(alpha), float(uniform), float(gamma)
+        if not np.isfinite(bin_seconds) or not bin_seconds > 0:
+            raise ValueError(f"bin_seconds = {bin_seconds}, must be positive and finite (None turns adaptive sampling off)")
+        if not 0.0 <= alpha <= 1.0:
+            raise ValueError(f"alpha = {alpha} outside [0, 1]")
+        if not 0.0 <= uniform <= 1.0:
+            raise ValueError(f"uniform = {uniform} outside [0, 1]")
+        if int(lookahead) != lookahead or not 1 <= int(lookahead) <= ADAPTIVE_MAX_LOOKAHEAD:
+            raise ValueError(f"lookahead = {lookahead} outside 1 to {ADAPTIVE_MAX_LOOKAHEAD} bins")
+        if not 0.0 < gamma <= 1.0:
+            raise ValueError(f"gamma = {gamma} outside (0, 1]")
+        bin_start, _ = _adaptive_bins(self.library.seg_start, self.library._fps, bin_seconds)
+        if not 1 <= int(bin_start[-1]) <= ADAPTIVE_MAX_BINS:
+            raise ValueError(f"bin_seconds = {bin_seconds} cuts the library into {int(bin_start[-1])} bins, 1 to {ADAPTIVE_MAX_BINS} are served")
+        return bin_seconds, alpha, uniform, int(lookahead), gamma, bin_start
+
+    def set_adaptive(self, bin_seconds: Optional[float] = DEFAULT_ADAPTIVE["bin_seconds"], alpha: float = DEFAULT_ADAPTIVE["alpha"],
+                     uniform: float = DEFAULT_ADAPTIVE["uniform"], lookahead: int = DEFAULT_ADAPTIVE["lookahead"],
+                     gamma: float = DEFAULT_ADAPTIVE["gamma"]) -> None:
+        """Failure-driven start sampling.  Every clip is cut into bins of ``bin_seconds``; :meth:`reset_done` counts the failures per
+        bin, :meth:`adapt` folds the counts into a history (``ema = (1 - alpha) ema + alpha count``) and turns it into start
+        probabilities: a failure raises its own bin and, discounted by ``gamma`` per bin, the ``lookahead - 1`` bins in front of it
+        inside its clip, and ``uniform`` is the share that stays "clip by weight, start uniform over the clip".  A fresh configuration
+        draws from that base distribution.  The same ``bin_seconds`` again replaces the four parameters and keeps the history;
+        ``bin_seconds=None`` (or ``<= 0``) turns adaptive sampling off.  From then on :meth:`reset_done` and the redraw of a finished clip
+        (``loop=False``) take clip and start time from the bins; :meth:`reset` and :meth:`assign` do not change.  The defaults
+        (:data:`DEFAULT_ADAPTIVE`) are a choice of this library."""
+        from . import _lib
+        if bin_seconds is None or (np.isfinite(float(bin_seconds)) and float(bin_seconds) <= 0):
+            _lib.check(_lib.lib().gmr_motion_tracker_set_adaptive(self.handle, 0.0, 0.0, 1.0, 1, 1.0))
+            self._adaptive = None
+            return
+        bin_seconds, alpha, uniform, K, gamma, bin_start = self._adaptive_setup(bin_seconds, alpha, uniform, lookahead, gamma)
+        _lib.check(_lib.lib().gmr_motion_tracker_set_adaptive(self.handle, bin_seconds, alpha, uniform, K, gamma))
+        self._adaptive = (bin_seconds, bin_start)
+
+    def _need_adaptive(self, what: str):
+        if getattr(self, "_adaptive", None) is None:
+            raise ValueError(f"{what}: adaptive sampling is not configured, call set_adaptive() first")
+        return self._adaptive
+
+    def adapt(self) -> None:
+        """One Adapt (typically once per rollout): the failure counts enter the history and are cleared, the start probabilities and
+        their CDF are rebuilt.  Synchronous."""
+        from . import _lib
+        self._need_adaptive("adapt")
+        _lib.check(_lib.lib().gmr_motion_tracker_adapt(self.handle))
+
+    def adapt_dev(self, stream=None) -> None:
+        """:meth:`adapt`, asynchronous on ``stream`` (three launches)"""
+        from . import _lib
+        self._need_adaptive("adapt_dev")
+        _lib.check(_lib.lib().gmr_motion_tracker_adapt_dev(self.handle, _lib._s(stream)))
+
+    def _check_reset_done(self, what: str, resample: bool, time_offset_range):
+        lo, hi = (float(x) for x in time_offset_range)
+        if not (np.isfinite(lo) and np.isfinite(hi)):
+            raise ValueError(f"{what}: time_offset_range {(lo, hi)} is not finite")
+        if getattr(self, "_adaptive", None) is not None and (not resample or lo != 0.0 or hi != 0.0):
+            raise ValueError(f"{what}: an adaptive tracker draws clip and start time from its bins, so resample=True and "
+                             f"time_offset_range=(0, 0) are the only choice (got {resample}, {(lo, hi)}); reset() serves a range")
+        return lo, hi
+
+    def reset_done(self, done=None, failed=None, env_ids=None, resample: bool = True, time_offset_range: Sequence[float] = (0.0, 0.0)) -> int:
+        """The masked reset, host arrays in.  Without ``env_ids``: environment ``e`` is reset iff ``done[e]`` (``[N]``, bool or integer;
+        ``None``: every one).  With ``env_ids`` (every environment at most once): the listed ones, ``done`` / ``failed`` indexed by list
+        position.  On a plain tracker a done environment gets what :meth:`reset` gives it, bit for bit, and one that is not done consumes
+        no draw.  On an adaptive tracker the bin of every done environment with ``failed`` set is counted first -- at the clock it has
+        now -- and clip and start time come from the bins.  Returns how many ids of done entries lay outside ``[0, num_envs)``."""
+        from . import _lib
+        lo, hi = self._check_reset_done("reset_done", resample, time_offset_range)
+        ids, n = None, self.num_envs
+        if env_ids is not None:
+            ids = np.ascontiguousarray(env_ids, dtype=np.int32).reshape(-1)
+            n = len(ids)
+            if len(np.unique(ids)) != n:
+                raise ValueError("reset_done: env_ids names an environment twice")
+        d, f = _mask(done, "done", n), _mask(failed, "failed", n)
+        if n == 0:
+            return 0
+        ignored = C.c_int()
+        _lib.check(_lib.lib().gmr_motion_tracker_reset_done(self.handle, n, _lib._ptr(ids), _lib._ptr(d), _lib._ptr(f), 1 if resample else 0, lo, hi,
+                                                            C.byref(ignored)))
+        return int(ignored.value)
+
+    def reset_done_dev(self, done=None, failed=None, env_ids=None, n: Optional[int] = None, resample: bool = True,
+                       time_offset_range: Sequence[float] = (0.0, 0.0), stream=None) -> None:
+        """:meth:`reset_done` on device memory, asynchronous on ``stream``: ONE launch, no allocation, no synchronisation, no
+        read-back.  ``done`` / ``failed`` are ``i32`` masks as a step leaves them (``finished``, ``fail``) or as the simulator keeps them;
+        with ``env_ids`` (``i32[n]``) they are indexed by list position and ``n`` is mandatory."""
+        from . import _lib
+        lo, hi = self._check_reset_done("reset_done_dev", resample, time_offset_range)
+        if env_ids is None:
+            if n is not None and int(n) != self.num_envs:
+                raise ValueError(f"reset_done_dev: without env_ids the masks cover every environment: n = {n}, num_envs = {self.num_envs}")
+            n = self.num_envs
+        elif n is None or int(n) < 0:
+            raise ValueError("reset_done_dev: env_ids on the device needs n, the length of the list")
+        n = int(n)
+        p_ids, p_done, p_failed = (_dev_ptr(x, k, "int32", n) for k, x in (("env_ids", env_ids), ("done", done), ("failed", failed)))
+        _lib.check(_lib.lib().gmr_motion_tracker_reset_done_dev(self.handle, n, p_ids, p_done, p_failed, 1 if resample else 0, lo, hi,
+                                                                _lib._s(stream)))
+
+    def adaptive_state(self) -> Dict[str, np.ndarray]:
+        """``bin_start i32[C + 1]``, ``fail_now u32[Bt]`` (failures since the last Adapt), ``ema``, ``prob``, ``cdf`` (``f64[Bt]``) and
+        ``clip_prob f64[C]``, the sum of ``prob`` over the bins of every clip.  Synchronous."""
+        from . import _lib
+        _, bin_start = self._need_adaptive("adaptive_state")
+        Bt, Cn = int(bin_start[-1]), len(bin_start) - 1
+        out = {"bin_start": np.empty(Cn + 1, np.int32), "fail_now": np.empty(Bt, np.uint32), "ema": np.empty(Bt, np.float64),
+               "prob": np.empty(Bt, np.float64), "cdf": np.empty(Bt, np.float64)}
+        _lib.check(_lib.lib().gmr_motion_tracker_adaptive_state(self.handle, *[_lib._ptr(out[k]) for k in ("bin_start", "fail_now", "ema", "prob", "cdf")]))
+        assert np.array_equal(out["bin_start"], bin_start), "the library's bins differ from the ones computed here"
+        out["clip_prob"] = np.bincount(np.repeat(np.arange(Cn), np.diff(bin_start)), weights=out["prob"], minlength=Cn)
         return out
 
     # ---- the step ---------------------------------------------------------------------------------------------------------

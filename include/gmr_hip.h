@@ -537,7 +537,8 @@ int gmr_motion_tracker_assign(gmr_motion_tracker_t* t, int n, const int32_t* env
 /* _reset_idx (:215-235) for the n listed environments, or for all with env_ids = NULL: one draw each; with `resample` its
  * word 0 redraws the clip, and in either case time = lo + (hi - lo) u in float32 (time_offset_range).  Ids outside [0, N)
  * are ignored and counted.  An id listed twice in one call gives that environment one of the two possible outcomes (one or
- * two draws) and touches no other: list every environment once. */
+ * two draws) and touches no other: list every environment once.  gmr_motion_tracker_reset_done_dev (N7) takes the done flags
+ * themselves instead of a list and cannot have that problem. */
 int gmr_motion_tracker_reset_dev(gmr_motion_tracker_t* t, int n, const int32_t* d_env_ids, int resample, float lo, float hi,
                                  void* stream);                                  /* asynchronous */
 int gmr_motion_tracker_reset(gmr_motion_tracker_t* t, int n, const int32_t* env_ids, int resample, float lo, float hi,
@@ -679,6 +680,56 @@ int gmr_motion_tracker_preview_dev(gmr_motion_tracker_t* t, const gmr_tracker_si
                                    int32_t* d_status, void* stream);             /* asynchronous */
 /* host buffers; default stream, synchronises and holds the tracker's mutex */
 int gmr_motion_tracker_preview(gmr_motion_tracker_t* t, const gmr_tracker_sim_t* sim, float* obs, int32_t* valid, int32_t* status);
+
+/* ---- N7: tracker adaptive sampling (failure-driven episode starts and masked resets of a motion tracker) ---- */
+/* Opt-in, a capability of this library (the reference resets in a Python loop and starts every finished motion at time 0).  The
+ * statement of record is tests/adaptive_mirror.py; this is the same in words.
+ * BINS, in frames.  Clip c has T_c frames at fps_c.  F_c = max(1, llround(bin_seconds fps_c)) frames per bin, nb_c = ceil(T_c / F_c)
+ * bins (none for T_c = 0); bin k covers frames [k F_c, min((k + 1) F_c, T_c)).  bin_start i32[C + 1] is the prefix sum of nb_c,
+ * Bt = bin_start[C], 1 <= Bt <= 2^22.  The bin of an environment is bin_start[clip] + min(lo / F_c, nb_c - 1) in integers, lo being
+ * the lower frame of the sampler's query at (clip, (double)time, loop), counted from the clip's first frame; a bad assignment (step 6
+ * of the tracker) has no bin.
+ * BASE.  base[b] = Wn_c frames(b) / T_c in float64 on the host; Wn_c = w_c / (the sum of w over the clips that have frames, added in
+ * clip order), w = the tracker's clip_weights or ones.  base sums to 1; a clip of weight zero has base 0.
+ * RECORDING.  fail_now u32[Bt]: a masked reset adds 1 (an integer atomic) to the bin of every done environment whose failed flag is
+ * not zero, at the clock it has when the reset runs.
+ * ADAPT, all float64, one rounding per operation, in this order:
+ *   1. ema[b] = (1 - alpha) ema[b] + alpha (double)fail_now[b]; fail_now[b] = 0
+ *   2. s[b] = sum over u = 0 .. K-1, ascending, of g[u] ema[min(b + u, last bin of b's clip)], g[u] = gamma^u by repeated
+ *      multiplication on the host; s[b] = 0 for a clip of weight zero.  A failure in bin b raises the K - 1 bins in front of it,
+ *      inside its clip: an episode has to start before the point where it falls.
+ *   3. S = sum of s (order: DESIGN.md 6n); p[b] = base[b] if S == 0, else ((1 - uniform) s[b]) / S + uniform base[b]
+ *   4. cdf[b] = p[0] + .. + p[b-1] (order: DESIGN.md 6n): cdf[0] = 0, cdf never decreases, a bin of p = 0 has cdf[b + 1] == cdf[b]
+ * DRAW from the bins: the Philox call of the tracker (counter (e, draws[e], 0, 0), draws[e] += 1); b = the largest bin with
+ * cdf[b] <= word0 2^-32; clip = the clip of b, k = b - bin_start[clip]; u from word 1;
+ * time = (float)(((double)(k F_c) + (double)u (double)frames(b)) / fps_c); length as everywhere.
+ * A step of an adaptive tracker redraws a finished clip (GMR_MOTION_LOOP off) with this draw -- clip and start time from the bins,
+ * nothing recorded -- instead of "clip by weight, time 0".  gmr_motion_tracker_reset[_dev] and assign[_dev] are unchanged: on an
+ * adaptive tracker they still draw from the clip weights and the offset range and do not read the bins. */
+/* bin_seconds > 0 builds the bins (synchronous: reads the library's seg_start / fps back, allocates once, runs one Adapt, so a fresh
+ * configuration draws from base); called again with the same bin_seconds it only replaces alpha, uniform, K and gamma -- a host
+ * assignment, no Adapt, ema is kept, Adapts already enqueued keep the parameters they were launched with.  bin_seconds <= 0 turns
+ * adaptive sampling off (synchronises; the tracker draws as a plain one again).  GMR_ERR_ARG: alpha or uniform outside [0, 1],
+ * K outside [1, 16], gamma outside (0, 1], Bt outside [1, 2^22], every clip with frames of weight zero. */
+int gmr_motion_tracker_set_adaptive(gmr_motion_tracker_t* t, double bin_seconds, double alpha, double uniform, int K, double gamma);
+/* One Adapt, three launches; GMR_ERR_ARG on a plain tracker.  Typically once per rollout. */
+int gmr_motion_tracker_adapt_dev(gmr_motion_tracker_t* t, void* stream);          /* asynchronous */
+int gmr_motion_tracker_adapt(gmr_motion_tracker_t* t);                            /* default stream, synchronises */
+/* The MASKED RESET, one launch, no allocation, no synchronisation, no read-back.  d_done / d_failed are i32 masks on the device.
+ *   with d_env_ids   i32[n]: entry i is environment d_env_ids[i]; d_done[i] / d_failed[i] belong to entry i
+ *   without          n = N: environment e is reset iff d_done[e] != 0
+ * d_done = NULL resets every entry; d_failed = NULL records nothing.  An entry that is not done is not looked at (no draw, and its id
+ * is not read); ids of done entries outside [0, N) are ignored and counted.  Every environment at most once in a list.
+ *   plain tracker     the draw, clip and time = lo + (hi - lo) u of gmr_motion_tracker_reset_dev, the same bits; d_failed is ignored
+ *   adaptive tracker  record (failed), then the draw from the bins; needs resample = 1 and lo = hi = 0, else GMR_ERR_ARG */
+int gmr_motion_tracker_reset_done_dev(gmr_motion_tracker_t* t, int n, const int32_t* d_env_ids, const int32_t* d_done,
+                                      const int32_t* d_failed, int resample, float lo, float hi, void* stream);   /* asynchronous */
+int gmr_motion_tracker_reset_done(gmr_motion_tracker_t* t, int n, const int32_t* env_ids, const int32_t* done, const int32_t* failed,
+                                  int resample, float lo, float hi, int* ignored /* ids of this call outside [0, N), or NULL */);
+/* the adaptive state on the host: bin_start i32[C + 1], fail_now u32[Bt], ema / prob / cdf f64[Bt], each may be NULL (ask for bin_start
+ * first: Bt = bin_start[C]); synchronises; GMR_ERR_ARG on a plain tracker */
+int gmr_motion_tracker_adaptive_state(gmr_motion_tracker_t* t, int32_t* bin_start, uint32_t* fail_now, double* ema, double* prob,
+                                      double* cdf);
 
 /* ---- multi-GPU: one rank per GPU, ONE broadcast, no per-step collective ------------ */
 /* The reference parallelises over files with mp.Pool on one CPU (scripts/smplx_to_robot_dataset.py:241-242); here
