@@ -968,12 +968,10 @@ __global__ __launch_bounds__(64 * NW, GMR_IK_MIN_WAVES) void ik_streams_kernel(c
           PROF_COUNT(pr, PH_NSOLVE);
           int rc;
           if (NW > 1) {   // the 4-wavefront shape is only launched for robots that decompose (gmr_abi.hip)
-            PROF_COUNT(pr, PH_NFACT);
             // helpers joined after barrier B3
             rc = QP == QP_TREE_SMALL ? solve_qp_tree<7, 9, false, true>(L, sm, sw, si, 0, lane, tree_state, pr, rows_s)
                                      : solve_qp_tree<8, 10, false, false>(L, sm, sw, si, 0, lane, tree_state, pr, rows_l);
           } else if (QP == QP_TREE_SMALL) {   // one wavefront, the four limbs in its four 16-lane rows
-            PROF_COUNT(pr, PH_NFACT);
             rc = solve_qp_tree<7, 9, true, true>(L, sm, sw, si, 0, lane, tree_state, pr, rows_r);
           } else {
             rc = solve_qp_regs<NVP, NW>(L, sm, lane, qp_state, pr);

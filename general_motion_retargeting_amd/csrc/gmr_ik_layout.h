@@ -34,7 +34,7 @@ struct IkOffsets {
   // offsets in doubles
   int body_pos, body_quat, axis, range_lo, range_hi, scale, pos_off, quat_off;
   int wpos[2], wrot[2];
-  int q, xa, xb, xaxis, raw, tgt, e, eaux, we, M, Jw, cpart, H, Kt, c, x, lo, hi, scal, tr_spart, tr_rpart;
+  int q, xa, xb, xaxis, raw, tgt, e, eaux, we, M, Jw, cpart, H, Kt, c, x, lo, hi, scal, tr_spart, tr_rpart, tr_gpart;
   int params;                    // damping, lm_damping, tol, limit_gain, ground_offset, dt (read where used: not in SGPRs)
   int hsc;                       // (sin, cos) of every hinge's half angle, written where q changes, read by the FK
   int n_double;
@@ -88,7 +88,8 @@ constexpr IkOffsets ik_offsets(int nvp, int nw) {
   if (o & 1) o++;
   L.H = o; o += nvp * L.ldh + 2;
   L.c = o; o += nvp; L.x = o; o += nvp; L.lo = o; o += nvp; L.hi = o; o += nvp; L.scal = o; o += 2;
-  if (nw == 4) { L.tr_spart = o; o += 4 * 10 * 10; L.tr_rpart = o; o += 4 * 10; }
+  // (tr_gpart: the four limbs' shares of the multipliers of fixed trunk variables, gmr_ik_tree.h step 6)
+  if (nw == 4) { L.tr_spart = o; o += 4 * 10 * 10; L.tr_rpart = o; o += 4 * 10; L.tr_gpart = o; o += 4 * 10; }
   if (o & 1) o++;                                  // every region starts 16-byte aligned
   L.n_double = o;
   int i = 0;

@@ -15,7 +15,7 @@
 // factors and solves the trunk Schur complement redundantly (no exchange of x_T), and the limbs
 // back-substitute in parallel.  Bounds are handled by the same block principal pivoting as the dense solver
 // (gmr_ik.hip) on wave-uniform bound masks kept identically in all wavefronts: two to three workgroup
-// barriers per pivoting round (Schur parts; x when a bound is active; violation sets).
+// barriers per pivoting round (Schur parts; the limbs' shares of a fixed trunk row's multiplier; violation sets).
 //
 // Used by the latency shape (NW = 4) when the robot decomposes into <= 4 limbs of <= 8 dofs and a
 // trunk of <= 10 (all 8 shipped robots do); other robots always run the 1-wavefront kernel (dense solver).
@@ -32,9 +32,13 @@ constexpr int TR_LD = TR_MAX_NL + TR_MAX_NT + 1; // row stride of the LDS transp
 struct TreeState { unsigned long long lower, upper; };
 
 // All four wavefronts call this together.  Returns GMR_STATUS_* (the same value in every wavefront);
-// the solution is left in sm[L.o.x].  Three workgroup barriers per pivoting round (two when no bound is
-// active): the trunk system is summed, factorised and solved redundantly by every wavefront, so
-// the only exchanges are the limbs' Schur contributions, the solution x and the violation sets.
+// the solution is left in sm[L.o.x].  Two workgroup barriers per pivoting round (three when a TRUNK variable
+// sits on a bound): the trunk system is summed, factorised and solved redundantly by every wavefront, so
+// the only exchanges are the limbs' Schur contributions, the violation sets and -- for the multiplier of a fixed
+// trunk variable -- each limb's share of that row of H x.  Row i of H is structurally zero outside its own limb and
+// the trunk: exactly the columns of the local matrix of the wavefront that owns the row, which holds their x in
+// lanes 0 .. TR_NV-1 after the back substitution.  The multiplier of a fixed LIMB variable is therefore formed from
+// registers alone (TR_NV row broadcasts and FMAs); nobody reads sm[L.o.x] inside a round.
 // TR_NL / TR_NT: rows actually eliminated (limbs <= TR_NL dofs, trunk <= TR_NT): the pivots are unrolled, so a
 // robot with 7-dof limbs and a 9-dof trunk (every shipped one) runs the <7, 9> instance: 16 instead of 18 pivots.
 //
@@ -88,6 +92,7 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
   const double* his = sm + L.o.hi;
   double* Spart = sm + L.o.tr_spart;                           // [4][TR_NT][TR_NT]
   double* rpart = sm + L.o.tr_rpart;                           // [4][TR_NT]
+  double* gpart = sm + L.o.tr_gpart;                           // [4][TR_NT] (4-wavefront form only)
   double* Lscr = sm + L.o.Kt + wave * (ROWS ? 16 : TR_MAX_NL + TR_MAX_NT) * TR_LD;   // this wavefront's / row's transpose scratch
   // violation sets of a round, double-buffered: {to_lower, to_upper, release, flags} x 2
   unsigned long long* vset = reinterpret_cast<unsigned long long*>(sw + L.o.w_tr_mask);
@@ -107,6 +112,7 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
 
   int pcount = 3, ninf_best = 65;
   for (int it = 0; it < 100; it++) {
+    PROF_COUNT(pr, PH_NFACT);                                 // pivoting rounds (one factorisation each)
     PROF_BEGIN(pr);
     const unsigned long long fixedm = bs.lower | bs.upper;
     const bool self_fixed = !row || ((fixedm >> dof) & 1ull);
@@ -305,13 +311,46 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
       if (fresh_lane(lane0) < TR_NL) x = bb * mydinv;
     }
     // ---- (6) violated bounds (free set) / multipliers (fixed set): g = H x + c ---------------------
-    if (fixedm != 0ull) {                                     // multipliers need the whole x
-      if (own) xs[dof] = x;
+    double pl = 0.0, pt = 0.0;                                // this row of H x: the limb's columns, the trunk's columns
+    bool trunk_fixed = false;                                 // workgroup-uniform
+    if (fixedm != 0ull) {
       if (dual_tol < 0.0) {                                   // (wave-uniform; most solves never fix a variable)
         const int li = fresh_lane(lane_in);
         dual_tol = 1e-13 * (1.0 + rows3_max(li < n ? fabs((sm + L.o.c)[li]) : 0.0));
       }
-      TR_SYNC();                                                                             // B2
+      if (ROWS) {                                             // one wavefront: every owner lane reads the whole x
+        if (own) xs[dof] = x;
+        TR_SYNC();                                                                           // B2
+      } else {
+        // all loads first (the unmasked row of H over the local matrix' columns), then the products with the
+        // wavefront's own x: two chains per part.  (A padding column's x is an exact zero: any finite H will do.)
+        double hl[TR_NL], ht[TR_NT];
+#pragma unroll
+        for (int m = 0; m < TR_NL; m++) hl[m] = Hrow[cdof[m] >= 0 ? cdof[m] : 0];
+#pragma unroll
+        for (int u = 0; u < TR_NT; u++) ht[u] = Hrow[cdof[TR_NL + u] >= 0 ? cdof[TR_NL + u] : 0];
+        double pl1 = 0.0, pt1 = 0.0;
+#pragma unroll
+        for (int m = 0; m < TR_NL; m++) {
+          const double xm = TR_BCAST(x, m);
+          if (m & 1) pl1 = fma(hl[m], xm, pl1); else pl = fma(hl[m], xm, pl);
+        }
+#pragma unroll
+        for (int u = 0; u < TR_NT; u++) {
+          const double xu = TR_BCAST(x, TR_NL + u);
+          if (u & 1) pt1 = fma(ht[u], xu, pt1); else pt = fma(ht[u], xu, pt);
+        }
+        pl += pl1; pt += pt1;
+        // A fixed trunk row (owned by wavefront 0) needs the limb parts of all four wavefronts.  gpart is written
+        // here, after B1 of this round, and read after B2; B3 separates that read from the next round's writes.
+        // (every wavefront holds the same trunk rows in the same lanes: the vote is workgroup-uniform)
+        TR_ROW()
+        trunk_fixed = __any(is_trunk && row && self_fixed);
+        if (trunk_fixed) {
+          if (is_trunk) gpart[wave * TR_MAX_NT + t] = pl;
+          TR_SYNC();                                                                         // B2
+        }
+      }
     }
     PROF_END(pr, PH_MULT);
     PROF_BEGIN(pr);
@@ -321,21 +360,30 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
         if (x < lo - ptol_lo) newst = 1;
         else if (x > hi + ptol_hi) newst = 2;
       } else {
-        double g0 = ci, g1 = 0.0;
-        // (eight products per trip with all their loads in flight: the stream that sets the batch's time sits on joint
-        //  limits in nearly every frame, so this row product is on the headline's critical path)
-        double g2 = 0.0, g3 = 0.0;
-        int j = 0;
-        for (; j + 7 < n; j += 8) {
-          const double h0 = Hrow[j], h1 = Hrow[j + 1], h2 = Hrow[j + 2], h3 = Hrow[j + 3], h4 = Hrow[j + 4], h5 = Hrow[j + 5],
-                       h6 = Hrow[j + 6], h7 = Hrow[j + 7];
-          const double x0 = xs[j], x1 = xs[j + 1], x2 = xs[j + 2], x3 = xs[j + 3], x4 = xs[j + 4], x5 = xs[j + 5],
-                       x6 = xs[j + 6], x7 = xs[j + 7];
-          g0 = fma(h0, x0, g0); g1 = fma(h1, x1, g1); g2 = fma(h2, x2, g2); g3 = fma(h3, x3, g3);
-          g0 = fma(h4, x4, g0); g1 = fma(h5, x5, g1); g2 = fma(h6, x6, g2); g3 = fma(h7, x7, g3);
+        double g;
+        if (ROWS) {
+          double g0 = ci, g1 = 0.0;
+          // (eight products per trip with all their loads in flight)
+          double g2 = 0.0, g3 = 0.0;
+          int j = 0;
+          for (; j + 7 < n; j += 8) {
+            const double h0 = Hrow[j], h1 = Hrow[j + 1], h2 = Hrow[j + 2], h3 = Hrow[j + 3], h4 = Hrow[j + 4], h5 = Hrow[j + 5],
+                         h6 = Hrow[j + 6], h7 = Hrow[j + 7];
+            const double x0 = xs[j], x1 = xs[j + 1], x2 = xs[j + 2], x3 = xs[j + 3], x4 = xs[j + 4], x5 = xs[j + 5],
+                         x6 = xs[j + 6], x7 = xs[j + 7];
+            g0 = fma(h0, x0, g0); g1 = fma(h1, x1, g1); g2 = fma(h2, x2, g2); g3 = fma(h3, x3, g3);
+            g0 = fma(h4, x4, g0); g1 = fma(h5, x5, g1); g2 = fma(h6, x6, g2); g3 = fma(h7, x7, g3);
+          }
+          for (; j < n; j++) g0 = fma(Hrow[j], xs[j], g0);
+          g = (g0 + g1) + (g2 + g3);
+        } else {
+          const int lane = fresh_lane(lane0);
+          g = ci + (pl + pt);                                 // limb row: its own wavefront holds every column
+          if (lane >= TR_NL) {                                // trunk row (wavefront 0): the four limbs' parts
+            const double* gp = gpart + (lane - TR_NL);
+            g = (ci + pt) + ((gp[0] + gp[TR_MAX_NT]) + (gp[2 * TR_MAX_NT] + gp[3 * TR_MAX_NT]));
+          }
         }
-        for (; j < n; j++) g0 = fma(Hrow[j], xs[j], g0);
-        const double g = (g0 + g1) + (g2 + g3);
         const bool at_lower = (bs.lower >> dof) & 1ull;
         if (at_lower ? g < -dual_tol : g > dual_tol) newst = 3;
       }
@@ -343,10 +391,11 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
     // each violating owner lane sets its dof's bit in the round's set (LDS atomic OR: order-independent)
     if (newst != 0) atomicOr(&vcur[newst - 1], 1ull << dof);
     if (fresh_lane(lane0) == 0 && tbad) atomicOr(&vcur[3], 1ull);
-    // With no variable fixed nobody reads xs in this round (no multipliers): a lane without a violation stores its
-    // result now, and if the round turns out to be the last one, B3 has already published it -- one barrier less per
-    // solve on the common path.  (A violating lane's round is not the last; its store would be overwritten anyway.)
-    const bool early = fixedm == 0ull;                        // wave- and workgroup-uniform
+    // Nobody reads xs inside a round of the 4-wavefront form (one wavefront: unless a variable is fixed): a lane
+    // without a violation stores its result now, and if the round turns out to be the last one, B3 has already
+    // published it -- no trailing store and barrier.  (A violating lane's round is not the last; its store would be
+    // overwritten anyway.)
+    const bool early = !ROWS || fixedm == 0ull;               // wave- and workgroup-uniform
     if (early && own && newst == 0) xs[dof] = fmin(fmax(x, lo), hi);
     TR_SYNC();                                                                               // B3
     PROF_END(pr, PH_IO);

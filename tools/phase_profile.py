@@ -3,6 +3,9 @@
 Not part of the product or of the bench; read SHARES, not absolute time (stamps forbid overlap).
 
     python tools/phase_profile.py [S] [T]
+
+GMR_PROF_LIBRARY=/path/to/libgmrhip_prof.so profiles that build instead (A/B of two trees' profile builds).
+The tree QP counts its pivoting rounds (one factorisation each) in NFACT: "rounds/solve".
 """
 import ctypes as C
 import os
@@ -24,7 +27,7 @@ def main():
     S = int(sys.argv[1]) if len(sys.argv) > 1 else 100
     T = int(sys.argv[2]) if len(sys.argv) > 2 else 100
     pkg = os.path.join(ROOT, "general_motion_retargeting_amd")
-    so = os.path.join(pkg, "libgmrhip_prof.so")
+    so = os.environ.get("GMR_PROF_LIBRARY") or os.path.join(pkg, "libgmrhip_prof.so")
     if not os.path.exists(so) or os.environ.get("REBUILD"):
         from general_motion_retargeting_amd import build
         build.build_variant("prof", ["-DGMR_IK_PROFILE"])
@@ -52,13 +55,13 @@ def main():
     tot = pr[:, :14].sum(axis=1).mean()
     nsolve = pr[:, 15].mean()
     nfact = pr[:, 14].mean()
-    print(f"S={S} T={T}  solves/stream={nsolve:.0f}  factorizations/solve={nfact / nsolve:.2f}  "
+    print(f"S={S} T={T}  solves/stream={nsolve:.0f}  rounds/solve={nfact / nsolve:.3f}  "
           f"stamped cycles/solve={tot / nsolve:.0f} (100 MHz ticks if s_memtime is the constant clock)")
     clk = pr[:, 16].mean() / pr[:, 17].mean() * 100.0
     print(f"  kernel ticks/stream={pr[:, 16].mean():.3e}  realtime(100MHz)={pr[:, 17].mean():.3e}  => in-kernel clock {clk:.0f} MHz; "
           f"stream wall {pr[:, 17].mean() / 100.0:.0f} us")
     rt = pr[:, 17] / 100.0
-    print("  per-stream wall us: min %.0f median %.0f max %.0f ; fact/solve per stream: min %.2f max %.2f" % (
+    print("  per-stream wall us: min %.0f median %.0f max %.0f ; rounds/solve per stream: min %.3f max %.3f" % (
         rt.min(), np.median(rt), rt.max(), (pr[:, 14] / pr[:, 15]).min(), (pr[:, 14] / pr[:, 15]).max()))
     for i, n in enumerate(PH[:14]):
         print(f"  {n:7s} {pr[:, i].mean() / tot * 100:6.2f} %   {pr[:, i].mean() / nsolve:10.0f} /solve")
@@ -67,7 +70,8 @@ def main():
         med = int(np.argsort(pr[:, 17])[S // 2])
         for name, i in (("slowest", k), ("median", med)):
             ns_i, tot_i = pr[i, 15], pr[i, :14].sum()
-            print(f"  {name} stream {i}: wall {pr[i, 17] / 100.0:.0f} us, {ns_i:.0f} solves, {tot_i / ns_i:.0f} stamped cycles/solve: " +
+            print(f"  {name} stream {i}: wall {pr[i, 17] / 100.0:.0f} us, {ns_i:.0f} solves, {pr[i, 14] / ns_i:.3f} rounds/solve, "
+                  f"{tot_i / ns_i:.0f} stamped cycles/solve: " +
                   " ".join(f"{n}={pr[i, j] / ns_i:.0f}" for j, n in enumerate(PH[:14])))
     if hp.sum() > 0:
         print("  helper wavefront 1 (cycles/solve): idle at B1 %.0f, Jacobian share %.0f, wait B2 %.0f, H share %.0f, wait B3 %.0f, tree-QP %.0f" % (
