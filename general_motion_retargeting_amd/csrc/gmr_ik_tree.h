@@ -39,6 +39,18 @@ struct TreeState { unsigned long long lower, upper; };
 // the trunk: exactly the columns of the local matrix of the wavefront that owns the row, which holds their x in
 // lanes 0 .. TR_NV-1 after the back substitution.  The multiplier of a fixed LIMB variable is therefore formed from
 // registers alone (TR_NV row broadcasts and FMAs); nobody reads sm[L.o.x] inside a round.
+// The same structure forms the RIGHT-HAND SIDE of a round with fixed variables, -c_i - sum over fixed j of H_ij x_j:
+// column m of the local matrix is the dof of lane m, so the bound value of column m is a broadcast of lane m's `xfix`
+// (an exact zero for a free or padding lane), and the sum runs over the TR_NV columns in a fixed order that does not
+// depend on the bound set: the limb columns' products in two FMA chains by column parity (even + odd), the trunk
+// columns' likewise.  A free limb row subtracts both sums from -c_i.  A free trunk row keeps the trunk columns' sum in
+// its own right-hand side and starts its forward-substituted share `b` from minus the sum over THIS wavefront's limb
+// columns; the share reaches the trunk system through `rpart`, which every wavefront adds as (w0 + w1) + (w2 + w3), and
+// elimination leaves it alone (a fixed limb column's pivot has l = 0 in every other row).  No loop over the set bits of
+// the bound masks, no read of lo / hi.
+// The unmasked row of H over the local matrix' columns (clamped address for a padding column: finite, multiplied by
+// zeros or masked) is read ONCE per solve into registers -- H does not change between the rounds of a solve -- and
+// serves the row build, these products, the trunk rows and the multipliers.
 // TR_NL / TR_NT: rows actually eliminated (limbs <= TR_NL dofs, trunk <= TR_NT): the pivots are unrolled, so a
 // robot with 7-dof limbs and a 9-dof trunk (every shipped one) runs the <7, 9> instance: 16 instead of 18 pivots.
 //
@@ -110,6 +122,11 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
   // column dofs of the local matrix (wave-uniform): limb columns then trunk columns
   const int* cdof = rows.cdof;
 
+  // row `dof` of H over the local matrix' columns, unmasked (a padding column reads column 0: finite, never used unmasked)
+  double h[TR_NV];
+#pragma unroll
+  for (int m = 0; m < TR_NV; m++) h[m] = Hrow[cdof[m] >= 0 ? cdof[m] : 0];
+
   int pcount = 3, ninf_best = 65;
   for (int it = 0; it < 100; it++) {
     PROF_COUNT(pr, PH_NFACT);                                 // pivoting rounds (one factorisation each)
@@ -130,32 +147,33 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
       const bool cfixed = cd < 0 || ((fixedm >> cd) & 1ull);
       // limb row a keeps columns m <= a; trunk rows keep all limb columns (B_l)
       const bool keep = row && !self_fixed && !cfixed && (is_trunk || (is_limb && m <= a));
-      double h = (row && cd >= 0) ? Hrow[cd] : 0.0;
-      double v = keep ? h : 0.0;
+      double v = keep ? h[m] : 0.0;
       if (is_limb && m == a && (self_fixed || cfixed)) v = 1.0;   // fixed / padding limb row: identity
       r[m] = v;
     }
-    // -c_i - sum over fixed j of H_ij x_j (the bound value of j from the uniform sets)
+    // -c_i - sum over fixed j of H_ij x_j: lane m's xfix is the bound value of column m (0.0 when free or padding), so
+    // every product of a column that is not fixed is an exact zero.  Fixed order, two chains per part (header comment).
     rhs0 = row ? (self_fixed ? xfix : -ci) : 0.0;
-    if (row && !self_fixed) {
-      // (same terms in the same order, one iteration ahead with the loads: the LDS round trips of the fixed variables
-      //  overlap instead of adding up -- the stream that sets the batch's time has five of them in every solve)
-      unsigned long long mm = fixedm;
-      if (mm) {
-        int j = __ffsll((long long)mm) - 1;
-        mm &= mm - 1;
-        double h = Hrow[j], bv = (((bs.lower >> j) & 1ull) ? los : his)[j];
-        while (mm) {
-          const int jn = __ffsll((long long)mm) - 1;
-          mm &= mm - 1;
-          const double hn = Hrow[jn], bn = (((bs.lower >> jn) & 1ull) ? los : his)[jn];
-          rhs0 -= h * bv;
-          h = hn; bv = bn;
-        }
-        rhs0 -= h * bv;
+    double bshare = 0.0;                                      // free trunk row: its limb columns' part, sent through rpart
+    if (fixedm != 0ull) {                                     // (wave-uniform; most solves never fix a variable)
+      double sl0 = 0.0, sl1 = 0.0, st0 = 0.0, st1 = 0.0;
+#pragma unroll
+      for (int m = 0; m < TR_NL; m++) {
+        const double xf = TR_BCAST(xfix, m);
+        if (m & 1) sl1 = fma(h[m], xf, sl1); else sl0 = fma(h[m], xf, sl0);
+      }
+#pragma unroll
+      for (int u = 0; u < TR_NT; u++) {
+        const double xf = TR_BCAST(xfix, TR_NL + u);
+        if (u & 1) st1 = fma(h[TR_NL + u], xf, st1); else st0 = fma(h[TR_NL + u], xf, st0);
+      }
+      const double sl = sl0 + sl1, st = st0 + st1;
+      if (row && !self_fixed) {
+        rhs0 = is_limb ? (rhs0 - st) - sl : rhs0 - st;
+        bshare = -sl;
       }
     }
-    b = is_limb ? rhs0 : 0.0;
+    b = is_limb ? rhs0 : (is_trunk ? bshare : 0.0);
     }
     PROF_END(pr, PH_KBUILD);
     PROF_BEGIN(pr);
@@ -209,6 +227,20 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
     }
     PROF_END(pr, PH_SUBST);
     PROF_BEGIN(pr);
+    // Operands of the limb back substitution (5): column a of L_l without its diagonal and of Y_l, from this wavefront's
+    // own scratch (complete since B1; the trunk's transpose below uses other columns of it).  Requested here, used after
+    // the trunk solve, so that their LDS latency hides under the trunk factorisation.  (clamped address outside the limb)
+    double ltl[TR_NL], yl[TR_NT];
+    {
+      TR_ROW()
+      const int ac = is_limb ? a : 0;
+#pragma unroll
+      for (int m = 0; m < TR_NL; m++) ltl[m] = Lscr[m * TR_LD + ac];
+#pragma unroll
+      for (int u = 0; u < TR_NT; u++) yl[u] = Lscr[(TR_NL + u) * TR_LD + ac];
+#pragma unroll
+      for (int m = 0; m < TR_NL; m++) ltl[m] = (is_limb && m != a) ? ltl[m] : 0.0;
+    }
     // ---- (4) every wavefront: trunk Schur complement, factor, solve (redundant, no exchange) -------
     double bt = 0.0;
     bool tbad = false;
@@ -223,8 +255,7 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
         double hv[TR_NT], sp[TR_NT];
 #pragma unroll
         for (int u = 0; u < TR_NT; u++) {
-          const int cd = cdof[TR_NL + u];
-          hv[u] = Hrow[cd >= 0 ? cd : 0];
+          hv[u] = h[TR_NL + u];
           const double* q0 = Spart + tt * TR_MAX_NT + u;
           sp[u] = (q0[0] + q0[TR_MAX_NT * TR_MAX_NT]) + (q0[2 * TR_MAX_NT * TR_MAX_NT] + q0[3 * TR_MAX_NT * TR_MAX_NT]);
         }
@@ -291,22 +322,19 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
     // ---- (5) limbs: y_l - Y_l^T x_T, then back substitution with L_l^T ----------------------------
     double x = bt;                                                                     // trunk lanes
     {
-      double lt[TR_NL];
       double bb = b;                                                                   // y_l (limb lanes)
       {
         TR_ROW()
 #pragma unroll
-        for (int m = 0; m < TR_NL; m++) lt[m] = (is_limb && m != a) ? Lscr[m * TR_LD + a] : 0.0;   // column a of L_l, off-diagonal
-#pragma unroll
         for (int u = 0; u < TR_NT; u++) {
           const double xt = TR_BCAST(bt, TR_NL + u);
-          if (is_limb) bb = fma(-Lscr[(TR_NL + u) * TR_LD + a], xt, bb);               // Y_l[u][a]
+          if (is_limb) bb = fma(-yl[u], xt, bb);                                       // Y_l[u][a]
         }
       }
 #pragma unroll
       for (int p = TR_NL - 1; p >= 0; p--) {
         const double xp = TR_BCAST(bb * mydinv, p);
-        bb = fma(-lt[p], xp, bb);                            // (rows >= p have lt[p] = 0: row p is final at its step)
+        bb = fma(-ltl[p], xp, bb);                           // (rows >= p have ltl[p] = 0: row p is final at its step)
       }
       if (fresh_lane(lane0) < TR_NL) x = bb * mydinv;
     }
@@ -322,23 +350,18 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
         if (own) xs[dof] = x;
         TR_SYNC();                                                                           // B2
       } else {
-        // all loads first (the unmasked row of H over the local matrix' columns), then the products with the
-        // wavefront's own x: two chains per part.  (A padding column's x is an exact zero: any finite H will do.)
-        double hl[TR_NL], ht[TR_NT];
-#pragma unroll
-        for (int m = 0; m < TR_NL; m++) hl[m] = Hrow[cdof[m] >= 0 ? cdof[m] : 0];
-#pragma unroll
-        for (int u = 0; u < TR_NT; u++) ht[u] = Hrow[cdof[TR_NL + u] >= 0 ? cdof[TR_NL + u] : 0];
+        // the products of the row of H (h, read once per solve) with the wavefront's own x: two chains per part.
+        // (A padding column's x is an exact zero: any finite H will do.)
         double pl1 = 0.0, pt1 = 0.0;
 #pragma unroll
         for (int m = 0; m < TR_NL; m++) {
           const double xm = TR_BCAST(x, m);
-          if (m & 1) pl1 = fma(hl[m], xm, pl1); else pl = fma(hl[m], xm, pl);
+          if (m & 1) pl1 = fma(h[m], xm, pl1); else pl = fma(h[m], xm, pl);
         }
 #pragma unroll
         for (int u = 0; u < TR_NT; u++) {
           const double xu = TR_BCAST(x, TR_NL + u);
-          if (u & 1) pt1 = fma(ht[u], xu, pt1); else pt = fma(ht[u], xu, pt);
+          if (u & 1) pt1 = fma(h[TR_NL + u], xu, pt1); else pt = fma(h[TR_NL + u], xu, pt);
         }
         pl += pl1; pt += pt1;
         // A fixed trunk row (owned by wavefront 0) needs the limb parts of all four wavefronts.  gpart is written
