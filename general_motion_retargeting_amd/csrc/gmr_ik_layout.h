@@ -73,10 +73,11 @@ constexpr IkOffsets ik_offsets(int nvp, int nw) {
   L.Jw = o; o += ik_max(6 * (cp.p + 1), 7 * cp.nb + 1);   // row cap.p stays zero: what items without a term read
   L.cpart = o; o += cp.p + 1;                      // slot cap.p stays zero: the share of an absent (task, dof) pair
   L.xb = L.Jw;                                     // FK runs between solves, when the assembly scratch is dead
-  // The transpose scratch of the QP solvers (dense: nvp x (nvp+1); tree: 4 x 18 x 19) is only live inside a
-  // solve, when the assembly scratch [e, eaux, we, M, Jw, cpart] is dead: alias it there.
-  // nw == 1: the one-wavefront tree solver (four limbs in the four 16-lane rows) parks 4 x 16 x 19 transposes
-  // and exchanges its Schur parts (4 x 10 x 10 + 4 x 10) in the same dead region.
+  // The transpose scratch of the dense QP solver (nvp x (nvp+1)) is only live inside a
+  // solve, when the assembly scratch [e, eaux, we, M, Jw, cpart] is dead: alias it there.  (The tree solver no longer
+  // transposes through LDS; the sizes it used to need, 4 x 18 x 19 and 4 x 16 x 19, still fix the offsets below.)
+  // nw == 1: the one-wavefront tree solver (four limbs in the four 16-lane rows) exchanges its Schur parts
+  // (4 x 10 x 10 + 4 x 10) in the same dead region, behind the 4 x 16 x 19 doubles.
   {
     const int rows_scr = 4 * 16 * 19;
     const int need = nw == 4 ? ik_max(nvp * (nvp + 1), 4 * 18 * 19) : ik_max(nvp * (nvp + 1), rows_scr + 440);

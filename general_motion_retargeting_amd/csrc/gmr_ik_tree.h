@@ -13,8 +13,12 @@
 // dense solver, but on an 18-column local matrix: 108 instead of 630 (pivot, column) updates and 8
 // instead of 36 pivots on the critical path, the four limbs side by side.  Every wavefront then sums,
 // factors and solves the trunk Schur complement redundantly (no exchange of x_T), and the limbs
-// back-substitute in parallel.  Bounds are handled by the same block principal pivoting as the dense solver
-// (gmr_ik.hip) on wave-uniform bound masks kept identically in all wavefronts: two to three workgroup
+// back-substitute in parallel.  The rows are FULL symmetric rows: the right-looking elimination updates every
+// column of every lane and leaves a finished row alone, so at its pivot lane p holds row p of the unscaled upper
+// factor, and one multiply by its own 1 / sqrt(d_p) gives column p of the lower factor -- the operand of the back
+// substitutions -- bit for bit what the lanes below hold (H is bitwise symmetric; a fused update multiplies the same
+// two numbers in either lane).  No factor is transposed through LDS.
+// Bounds are handled by the same block principal pivoting as the dense solver (gmr_ik.hip) on wave-uniform bound masks kept identically in all wavefronts: two to three workgroup
 // barriers per pivoting round (Schur parts; the limbs' shares of a fixed trunk row's multiplier; violation sets).
 //
 // Used by the latency shape (NW = 4) when the robot decomposes into <= 4 limbs of <= 8 dofs and a
@@ -23,9 +27,8 @@
 
 namespace gmr {
 
-constexpr int TR_MAX_NL = 8;                     // capacity: limb rows per wavefront (LDS tables, scratch strides)
+constexpr int TR_MAX_NL = 8;                     // capacity: limb rows per wavefront (LDS tables)
 constexpr int TR_MAX_NT = 10;                    // capacity: trunk rows
-constexpr int TR_LD = TR_MAX_NL + TR_MAX_NT + 1; // row stride of the LDS transpose scratch
 
 // Bound sets of the QP, identical in every wavefront (wave-uniform registers, carried from solve to
 // solve for the warm start): bit d of `lower` / `upper` = dof d sits on its lower / upper bound.
@@ -105,7 +108,6 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
   double* Spart = sm + L.o.tr_spart;                           // [4][TR_NT][TR_NT]
   double* rpart = sm + L.o.tr_rpart;                           // [4][TR_NT]
   double* gpart = sm + L.o.tr_gpart;                           // [4][TR_NT] (4-wavefront form only)
-  double* Lscr = sm + L.o.Kt + wave * (ROWS ? 16 : TR_MAX_NL + TR_MAX_NT) * TR_LD;   // this wavefront's / row's transpose scratch
   // violation sets of a round, double-buffered: {to_lower, to_upper, release, flags} x 2
   unsigned long long* vset = reinterpret_cast<unsigned long long*>(sw + L.o.w_tr_mask);
 
@@ -134,6 +136,10 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
     const unsigned long long fixedm = bs.lower | bs.upper;
     const bool self_fixed = !row || ((fixedm >> dof) & 1ull);
     const double xfix = !row ? 0.0 : (((bs.lower >> dof) & 1ull) ? lo : (((bs.upper >> dof) & 1ull) ? hi : 0.0));
+    // Column m of the local matrix is the dof of lane m: "column m is fixed or padding" is lane m's self_fixed.  One
+    // ballot per round holds all TR_NV of them at constant bit positions (ROWS: in the 16-bit slice of the lane's row).
+    const unsigned long long fixed_lanes = __ballot(self_fixed);
+    const unsigned colmask = (ROWS ? (unsigned)(fixed_lanes >> (16 * wave)) : (unsigned)fixed_lanes) & ((1u << TR_NV) - 1u);
     // ---- (1) local rows and right-hand side -----------------------------------------------------
     double r[TR_NV];
 #pragma unroll
@@ -143,13 +149,19 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
     TR_ROW()
 #pragma unroll
     for (int m = 0; m < TR_NL; m++) {
-      const int cd = cdof[m];                                 // wave-uniform
-      const bool cfixed = cd < 0 || ((fixedm >> cd) & 1ull);
-      // limb row a keeps columns m <= a; trunk rows keep all limb columns (B_l)
-      const bool keep = row && !self_fixed && !cfixed && (is_trunk || (is_limb && m <= a));
+      const bool cfixed = (colmask >> m) & 1u;                // wave-uniform (ROWS: uniform in the 16-lane row)
+      // every free row keeps all its free limb columns: D_l as full symmetric rows (limb rows), B_l (trunk rows)
+      const bool keep = row && !self_fixed && !cfixed;
       double v = keep ? h[m] : 0.0;
       if (is_limb && m == a && (self_fixed || cfixed)) v = 1.0;   // fixed / padding limb row: identity
       r[m] = v;
+    }
+    // limb row a also keeps its trunk columns, B_l^T: column a of Y_l grows there.  (A trunk row's trunk columns start
+    // from zero and collect its Schur part.)
+#pragma unroll
+    for (int u = 0; u < TR_NT; u++) {
+      const bool cfixed = (colmask >> (TR_NL + u)) & 1u;      // wave-uniform
+      r[TR_NL + u] = (is_limb && row && !self_fixed && !cfixed) ? h[TR_NL + u] : 0.0;
     }
     // -c_i - sum over fixed j of H_ij x_j: lane m's xfix is the bound value of column m (0.0 when free or padding), so
     // every product of a column that is not fixed is an exact zero.  Fixed order, two chains per part (header comment).
@@ -190,8 +202,7 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
       bad = bad || !(dp > 0.0);
       const double rs = r[p] * dinv;                         // (row p holds the pivot itself: d_p / sqrt(d_p))
       double l = lane > p ? rs : 0.0;                        // column p of L_l (rows > p) and of Y_l
-      r[p] = lane == p ? rs : l;
-      if (lane == p) mydinv = dinv;
+      if (lane == p) mydinv = dinv;                          // (rows <= p keep r[p]: l = 0 leaves a finished row alone)
       double dinv_next = 1.0;
       if (p + 1 < TR_NL) {
         r[p + 1] = fma(-l, TR_BCAST(l, p + 1), r[p + 1]);
@@ -205,9 +216,22 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
       dinv = dinv_next;
     }
     if (fresh_lane(lane0) < TR_NL) b *= mydinv;              // y_p = b_p / sqrt(d_p): the value every later row was given
+    // Operands of the limb back substitution (5): column a of L_l without its diagonal and of Y_l.  The local matrix is
+    // symmetric, so when pivot a came, limb lane a held row a of the unscaled upper factor in r[k], k > a -- entry (a, k)
+    // started equal to entry (k, a) of lane k and received the same fused updates at pivots 0 .. a-1 -- and nothing
+    // touched it since.  Scaled by the lane's own 1 / sqrt(d_a) it is column a of the lower factor, bit for bit what
+    // lane k holds in its column a: no transpose through LDS.
+    double ltl[TR_NL], yl[TR_NT];
+    {
+      TR_ROW()
+#pragma unroll
+      for (int m = 0; m < TR_NL; m++) ltl[m] = (is_limb && m > a) ? r[m] * mydinv : 0.0;
+#pragma unroll
+      for (int u = 0; u < TR_NT; u++) yl[u] = r[TR_NL + u] * mydinv;   // (used by limb lanes only)
+    }
     PROF_END(pr, PH_CHOL);
     PROF_BEGIN(pr);
-    // ---- (3) publish the Schur contribution; park L_l / Y_l for the transposed reads --------------
+    // ---- (3) publish the Schur contribution --------------------------------------------------------
     unsigned long long* vcur = vset + 4 * (it & 1);
     {
     TR_ROW()
@@ -216,10 +240,6 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
       for (int u = 0; u < TR_NT; u++) Spart[(wave * TR_MAX_NT + t) * TR_MAX_NT + u] = r[TR_NL + u];
       rpart[wave * TR_MAX_NT + t] = b;
     }
-    if (lane < TR_NV) {
-#pragma unroll
-      for (int m = 0; m < TR_NL; m++) Lscr[lane * TR_LD + m] = r[m];
-    }
     if (lane == 0 && bad) atomicOr(&vcur[3], 1ull);
     TR_SYNC();                                                                               // B1
     // the other slot was last read before this barrier: clear it for the next round
@@ -227,20 +247,6 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
     }
     PROF_END(pr, PH_SUBST);
     PROF_BEGIN(pr);
-    // Operands of the limb back substitution (5): column a of L_l without its diagonal and of Y_l, from this wavefront's
-    // own scratch (complete since B1; the trunk's transpose below uses other columns of it).  Requested here, used after
-    // the trunk solve, so that their LDS latency hides under the trunk factorisation.  (clamped address outside the limb)
-    double ltl[TR_NL], yl[TR_NT];
-    {
-      TR_ROW()
-      const int ac = is_limb ? a : 0;
-#pragma unroll
-      for (int m = 0; m < TR_NL; m++) ltl[m] = Lscr[m * TR_LD + ac];
-#pragma unroll
-      for (int u = 0; u < TR_NT; u++) yl[u] = Lscr[(TR_NL + u) * TR_LD + ac];
-#pragma unroll
-      for (int m = 0; m < TR_NL; m++) ltl[m] = (is_limb && m != a) ? ltl[m] : 0.0;
-    }
     // ---- (4) every wavefront: trunk Schur complement, factor, solve (redundant, no exchange) -------
     double bt = 0.0;
     bool tbad = false;
@@ -263,9 +269,8 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
         const bool live = is_trunk && row && !self_fixed;
 #pragma unroll
         for (int u = 0; u < TR_NT; u++) {
-          const int cd = cdof[TR_NL + u];
-          const bool cfixed = cd < 0 || ((fixedm >> cd) & 1ull);           // wave-uniform
-          double v = (live && !cfixed && u <= t) ? hv[u] + sp[u] : 0.0;
+          const bool cfixed = (colmask >> (TR_NL + u)) & 1u;               // wave-uniform
+          double v = (live && !cfixed) ? hv[u] + sp[u] : 0.0;       // full symmetric rows, as in (1)
           if (is_trunk && u == t && !(live && !cfixed)) v = 1.0;
           s[u] = v;
         }
@@ -280,8 +285,7 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
         tbad = tbad || !(dq > 0.0);
         const double ss = s[q] * dinv;
         double l = t > q ? ss : 0.0;
-        s[q] = t == q ? ss : l;
-        if (t == q) tdinv = dinv;
+        if (t == q) tdinv = dinv;                            // (rows <= q keep s[q], as in (2))
         double dinv_next = 1.0;
         if (q + 1 < TR_NT) {
           s[q + 1] = fma(-l, TR_BCAST(l, TR_NL + q + 1), s[q + 1]);
@@ -294,20 +298,14 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
         for (int k = q + 2; k < TR_NT; k++) s[k] = fma(-l, TR_BCAST(l, TR_NL + k), s[k]);
         dinv = dinv_next;
       }
-      // back substitution: L^T through this wavefront's scratch (columns 8..17 of rows 8..17 are free)
-      double* Tscr = Lscr + TR_NL;
+      // back substitution: row t of L^T without its diagonal is trunk lane t's own unscaled upper row times its
+      // 1 / sqrt(d_t), as in (2) (the rows below are zero, rows outside the trunk get zeros): row q is final when its
+      // step comes, so no step needs a select
       double lt[TR_NT];
       {
         TR_ROW()
-        if (is_trunk) {
 #pragma unroll
-          for (int u = 0; u < TR_NT; u++) Tscr[lane * TR_LD + u] = s[u];
-        }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-#pragma unroll
-        // row t of L^T without its diagonal (the rows below are zero, rows outside the trunk get zeros): row q is final
-        // when its step comes, so no step needs a select
-        for (int q = 0; q < TR_NT; q++) lt[q] = (is_trunk && t != q) ? Tscr[(TR_NL + q) * TR_LD + t] : 0.0;
+        for (int q = 0; q < TR_NT; q++) lt[q] = (is_trunk && q > t) ? s[q] * tdinv : 0.0;
       }
       bt *= tdinv;                                           // y (rows kept their unscaled right-hand side)
 #pragma unroll
