@@ -138,6 +138,12 @@ _SIGS = {
     "gmr_motion_tracker_reset_done": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float,
                                                 C.POINTER(C.c_int)]),
     "gmr_motion_tracker_adaptive_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gmr_motion_tracker_enable_anchors": (C.c_int, [C.c_void_p, C.c_int]),
+    "gmr_motion_tracker_set_anchor_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gmr_motion_tracker_set_anchor": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "gmr_motion_tracker_anchor_to_root_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "gmr_motion_tracker_anchor_to_root": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "gmr_motion_tracker_anchor_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "gmr_comm_create": (C.c_int, [C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),
     "gmr_comm_destroy": (C.c_int, [C.c_void_p]),
     "gmr_comm_rank": (C.c_int, [C.c_void_p]),
@@ -579,6 +585,7 @@ TRACKER_LINKS_SIM_FIELDS = ("body_pos", "body_rot", "body_vel", "body_ang_vel")
 TRACKER_LINK_TERMS = 4
 TRACKER_FRAME_WORLD, TRACKER_FRAME_HEADING = 0, 1
 TRACKER_NO_ADVANCE = 1
+ANCHOR_YAW, ANCHOR_Z = 1, 2          # gmr_motion_tracker_anchor_to_root[_dev] flags (include/gmr_hip.h, "tracker anchors")
 
 
 # gmr_motion_tracker_set_preview: the block bits in row order, the frames and the limits (include/gmr_hip.h, "tracker preview")

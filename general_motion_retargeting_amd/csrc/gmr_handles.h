@@ -1,7 +1,8 @@
 // gmr_handles.h -- the handles of the C-ABI that more than one translation unit of libgmrhip.so looks into (not part of the
 // C-ABI): the FK tree (created in gmr_abi.hip) and the motion library (gmr_motion.hip), both read by gmr_body_state.hip, and
 // the motion tracker (gmr_tracker.hip), which is bound to a library and, with links attached (gmr_tracker_links.hip), to an FK tree;
-// gmr_tracker_preview.hip reads its state and tables, gmr_tracker_adaptive.hip owns its bins (adaptive sampling, masked resets).
+// gmr_tracker_preview.hip reads its state and tables, gmr_tracker_adaptive.hip owns its bins (adaptive sampling, masked resets),
+// gmr_tracker_anchor.hip its anchors.
 #pragma once
 #include <stdint.h>
 
@@ -67,6 +68,8 @@ struct TrackerState {
   uint32_t* ignored;   // [1] environment ids outside [0, N) met by reset / assign since creation
   const double* cdf;   // [C] with clip weights: cdf[k] = (w_0 + .. + w_{k-1}) / sum, else null
   const AdaptiveBins* bins;   // adaptive sampling: the table a draw from the bins reads, ON THE DEVICE; null on a plain tracker
+  float* anchor_pos;   // [N][3] tracker anchors: the translation of every environment; null until they are enabled
+  float* anchor_yaw;   // [N][2] (z, w) of the unit quaternion (0, 0, z, w) of its yaw; null exactly when anchor_pos is
 };
 constexpr int ADAPT_MAX_K = 16;       // look-ahead of adaptive sampling, in bins
 constexpr int ADAPT_CHUNK = 64;       // bins one lane sums in order (tracker_adapt_cdf_kernel)
@@ -114,6 +117,7 @@ struct gmr_motion_tracker {
   gmr::AdaptiveArrays bins = {};
   gmr::DeviceBlock bin_block;    // every array of adaptive sampling: one allocation, made by set_adaptive
   double bin_seconds = 0.0;      // what the bins were built with
+  gmr::DeviceBlock anchor_block; // S.anchor_pos / S.anchor_yaw: one allocation, made by gmr_motion_tracker_enable_anchors
   std::vector<double> clip_w;    // the clip weights as given at creation (empty: uniform)
   std::mutex mu;                 // the tables, and the whole of every synchronous entry point
 };

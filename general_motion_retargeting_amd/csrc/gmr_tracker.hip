@@ -4,7 +4,8 @@
 //   tracker_step_kernel     ONE launch per environment step, the sampler's shape (16 lanes per environment, 16 environments per
 //                           workgroup): the query of gmr_motion_sample.h at the environment's own (clip, clock), the reference
 //                           rows with the dofs in robot order, the six tracking errors and terms against the simulator's
-//                           state, the float32 clock advance and, without loop, the redraw of a finished clip
+//                           state, the float32 clock advance and, without loop, the redraw of a finished clip; with anchors
+//                           enabled (gmr_tracker_anchor.hip) the four root rows are moved by the environment's anchor first
 //   tracker_reset_kernel    _reset_idx (:215-235): one lane per listed environment, one Philox draw each
 //   tracker_assign_kernel   (clip, time) set explicitly, one lane per listed environment
 //
@@ -80,10 +81,23 @@ __global__ __launch_bounds__(256) void tracker_step_kernel(const MotionArrays A,
   const size_t rl = Q.rl, rh = Q.rh;
   const float w0 = Q.w0, w1 = Q.w1;
   float acc[TRACKER_TERMS] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};      // this lane's share of the six sums
+  // the anchor of the environment: one branch, the same in every lane of the launch
+  const bool anchored = S.anchor_pos != nullptr;
+  Anchor An;
+  float at = 0.0f;                                                     // component l of its translation
+  if (anchored) {
+    anchor_turn(S, (size_t)e, An);
+    if (l < 3) at = S.anchor_pos[(size_t)e * 3 + l];
+  }
   if (l < 3) {
-    const float p = lerp1(A.root_pos, rl * 3 + l, rh * 3 + l, same, w0, w1);
-    const float v = lerp1(A.root_vel, rl * 3 + l, rh * 3 + l, same, w0, w1);
-    const float w = lerp1(A.root_ang_vel, rl * 3 + l, rh * 3 + l, same, w0, w1);
+    float p = lerp1(A.root_pos, rl * 3 + l, rh * 3 + l, same, w0, w1);
+    float v = lerp1(A.root_vel, rl * 3 + l, rh * 3 + l, same, w0, w1);
+    float w = lerp1(A.root_ang_vel, rl * 3 + l, rh * 3 + l, same, w0, w1);
+    if (anchored) {      // lanes 0 and 1 swap x and y; the root terms below compare against the anchored rows
+      p = anchor_point_lane(An, l, p, at);
+      v = anchor_vector_lane(An, l, v);
+      w = anchor_vector_lane(An, l, w);
+    }
     if (O.ref_root_pos) O.ref_root_pos[(size_t)e * 3 + l] = p;
     if (O.ref_root_vel) O.ref_root_vel[(size_t)e * 3 + l] = v;
     if (O.ref_root_ang_vel) O.ref_root_ang_vel[(size_t)e * 3 + l] = w;
@@ -94,7 +108,8 @@ __global__ __launch_bounds__(256) void tracker_step_kernel(const MotionArrays A,
     }
   }
   if (l < 4 && (O.ref_root_rot || (terms && X.base_quat))) {
-    const float q = slerp1(A.root_rot, rl, rh, l, same, w0, w1);
+    float q = slerp1(A.root_rot, rl, rh, l, same, w0, w1);
+    if (anchored) q = anchor_quat_lane(An, l, q);
     if (O.ref_root_rot) O.ref_root_rot[(size_t)e * 4 + l] = q;
     if (terms && X.base_quat) acc[1] = X.base_quat[(size_t)e * 4 + l] * q;      // <q, q_ref> = the w of conj(q) * q_ref
   }

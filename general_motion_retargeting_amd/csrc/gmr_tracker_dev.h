@@ -101,4 +101,67 @@ __device__ __forceinline__ float group_sum(float x) {
   return x;
 }
 
+// ---- tracker anchors (include/gmr_hip.h N8; the statement of record is tests/anchor_mirror.py) ----------------
+
+// the yaw of a rotation as the unit quaternion (0, 0, z, w): normalize(0, 0, q.z, q.w), the identity when both are zero
+__device__ __forceinline__ void yaw_of(float qz, float qw, float& z, float& w) {
+  const float n2 = qz * qz + qw * qw;
+  z = 0.0f; w = 1.0f;
+  if (n2 != 0.0f) {                // (a NaN goes through the division and stays one)
+    const float n = __fsqrt_rn(n2);
+    z = __fdiv_rn(qz, n); w = __fdiv_rn(qw, n);
+  }
+}
+
+// yaw_of with a correctly rounded square root (sqrtf; __fsqrt_rn above is the hardware's, good to one ulp): what anchor_to_root
+// uses, so that tests/anchor_mirror.py reproduces the anchor's bits in NumPy.  The heading frame keeps yaw_of and with it its bits.
+__device__ __forceinline__ void yaw_of_exact(float qz, float qw, float& z, float& w) {
+  const float n2 = qz * qz + qw * qw;
+  z = 0.0f; w = 1.0f;
+  if (n2 != 0.0f) {
+    const float n = sqrtf(n2);
+    z = qz / n; w = qw / n;
+  }
+}
+
+// The anchor of one environment: yaw (z, w) with c = w w - z z, s = 2 z w, then the translation.  tx, ty, tz are filled by
+// anchor_load (lane = environment); a lane that holds ONE component of a row keeps its own translation component beside it.
+struct Anchor {
+  float z, w, c, s, tx, ty, tz;
+};
+__device__ __forceinline__ void anchor_turn(const TrackerState& S, size_t e, Anchor& a) {
+  a.z = S.anchor_yaw[e * 2]; a.w = S.anchor_yaw[e * 2 + 1];
+  a.c = a.w * a.w - a.z * a.z; a.s = 2.0f * a.z * a.w;
+}
+__device__ __forceinline__ Anchor anchor_load(const TrackerState& S, size_t e) {
+  Anchor a;
+  anchor_turn(S, e, a);
+  a.tx = S.anchor_pos[e * 3]; a.ty = S.anchor_pos[e * 3 + 1]; a.tz = S.anchor_pos[e * 3 + 2];
+  return a;
+}
+// lane = environment: a vector (x and y turn, z stays), a position (the vector, then the translation), a quaternion xyzw
+__device__ __forceinline__ void anchor_vector(const Anchor& a, float& x, float& y) {
+  const float nx = a.c * x - a.s * y, ny = a.s * x + a.c * y;
+  x = nx; y = ny;
+}
+__device__ __forceinline__ void anchor_point(const Anchor& a, float& x, float& y, float& z) {
+  anchor_vector(a, x, y);
+  x = x + a.tx; y = y + a.ty; z = z + a.tz;
+}
+__device__ __forceinline__ void anchor_quat(const Anchor& a, float& qx, float& qy, float& qz, float& qw) {
+  const float nx = a.w * qx - a.z * qy, ny = a.w * qy + a.z * qx, nz = a.w * qz + a.z * qw, nw = a.w * qw - a.z * qz;
+  qx = nx; qy = ny; qz = nz; qw = nw;
+}
+// lane = component: lane l of a 16-lane row holds component l (x, y, z; w of a quaternion in lane 3).  Lanes 0 and 1 (2 and 3) swap
+// inside the row; the lanes of a row are all here or all gone.  Lanes that hold no component return something nobody reads.
+__device__ __forceinline__ float anchor_vector_lane(const Anchor& a, int l, float v) {
+  const float o = __shfl(v, l ^ 1, MOTION_GROUP);
+  return l == 0 ? a.c * v - a.s * o : (l == 1 ? a.s * o + a.c * v : v);
+}
+__device__ __forceinline__ float anchor_point_lane(const Anchor& a, int l, float v, float t) { return anchor_vector_lane(a, l, v) + t; }
+__device__ __forceinline__ float anchor_quat_lane(const Anchor& a, int l, float q) {
+  const float o = __shfl(q, l ^ 1, MOTION_GROUP);
+  return (l == 0 || l == 3) ? a.w * q - a.z * o : a.w * q + a.z * o;
+}
+
 }  // namespace gmr

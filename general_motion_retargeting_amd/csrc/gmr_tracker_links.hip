@@ -5,12 +5,14 @@
 //   tracker_links_kernel   64 environments per workgroup of W wavefronts, W = the wavefronts of the link plan (1 .. 4)
 //     phase 1  all W x 64 lanes, 16 lanes per environment: the plain step's work with the plain step's lane layout -- the query,
 //              the root rows, the mapped dof rows, the six sums, err / term -- and, for the walk, the library-order
-//              dof_pos | dof_vel row of the environment (odd stride) and its 13 root floats parked in LDS
+//              dof_pos | dof_vel row of the environment (odd stride) and its 13 root floats parked in LDS; with anchors enabled
+//              (gmr_tracker_anchor.hip) the four root rows and their terms are the anchored ones, what is parked is not
 //     phase 2  lane = environment: wavefront w walks ITS list of the plan (LinkPlan, gmr_link_plan.h) -- the trunk ancestors its
 //              subtrees hang from, recomputed by every wavefront that needs them, then the subtrees: the partition of
 //              fk_split_tree restricted to the ancestor closure of the selection -- with fk_body of gmr_fk_walk.h for the pose
 //              and the two velocity lines of body_state_kernel.  For a selected body it writes the reference row (REFS), loads
-//              the simulator's row through sim_body and the strides, applies the frame and keeps five partials in registers:
+//              the simulator's row through sim_body and the strides, applies the frame (and, in the world frame, the anchor) and
+//              keeps five partials in registers:
 //              four weighted sums of squares and the largest squared distance
 //     phase 3  the W x 5 partials of an environment meet in LDS; wavefront 0 finishes sqrt / exp, total and fail, then advances
 //              the clock and redraws a finished clip exactly as lane 0 of the plain kernel does (not with NO_ADVANCE)
@@ -51,15 +53,7 @@ struct LinkOut {
   int32_t* fail;
 };
 
-// the yaw of a root rotation as the unit quaternion (0, 0, z, w): normalize(0, 0, q.z, q.w), the identity when both are zero
-__device__ __forceinline__ void yaw_of(float qz, float qw, float& z, float& w) {
-  const float n2 = qz * qz + qw * qw;
-  z = 0.0f; w = 1.0f;
-  if (n2 != 0.0f) {                // (a NaN goes through the division and stays one)
-    const float n = __fsqrt_rn(n2);
-    z = __fdiv_rn(qz, n); w = __fdiv_rn(qw, n);
-  }
-}
+// (yaw_of: gmr_tracker_dev.h)
 // Rz(-psi) (x, y) for the yaw (z, w): cos psi = w w - z z, sin psi = 2 z w
 __device__ __forceinline__ void unyaw(float z, float w, float& x, float& y) {
   const float c = w * w - z * z, s = 2.0f * z * w;
@@ -103,6 +97,7 @@ __global__ __launch_bounds__(64 * FK_MAX_WAVES) void tracker_links_kernel(const 
   __syncthreads();
   const long long q0 = (long long)blockIdx.x * TL_BLOCK;
   const bool terms = O.err || O.term || O.total;
+  const bool anchored = S.anchor_pos != nullptr;      // tracker anchors: the same in every lane of the launch
 
   // ---- phase 1: 16 lanes per environment, the plain step ----
   {
@@ -142,13 +137,24 @@ __global__ __launch_bounds__(64 * FK_MAX_WAVES) void tracker_links_kernel(const 
       const size_t rl = Q.rl, rh = Q.rh;
       const float w0 = Q.w0, w1 = Q.w1;
       float acc[TRACKER_TERMS] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+      Anchor An;
+      float at = 0.0f;
+      if (anchored) {      // (the plain step's lines; the walk is parked the root as the library has it)
+        anchor_turn(S, (size_t)e, An);
+        if (l < 3) at = S.anchor_pos[(size_t)e * 3 + l];
+      }
       if (l < 3) {
-        const float p = lerp1(A.root_pos, rl * 3 + l, rh * 3 + l, same, w0, w1);
-        const float v = lerp1(A.root_vel, rl * 3 + l, rh * 3 + l, same, w0, w1);
-        const float w = lerp1(A.root_ang_vel, rl * 3 + l, rh * 3 + l, same, w0, w1);
+        float p = lerp1(A.root_pos, rl * 3 + l, rh * 3 + l, same, w0, w1);
+        float v = lerp1(A.root_vel, rl * 3 + l, rh * 3 + l, same, w0, w1);
+        float w = lerp1(A.root_ang_vel, rl * 3 + l, rh * 3 + l, same, w0, w1);
         s_root[l * TL_BLOCK + qi] = p;
         s_root[(7 + l) * TL_BLOCK + qi] = v;
         s_root[(10 + l) * TL_BLOCK + qi] = w;
+        if (anchored) {
+          p = anchor_point_lane(An, l, p, at);
+          v = anchor_vector_lane(An, l, v);
+          w = anchor_vector_lane(An, l, w);
+        }
         if (O.ref_root_pos) O.ref_root_pos[(size_t)e * 3 + l] = p;
         if (O.ref_root_vel) O.ref_root_vel[(size_t)e * 3 + l] = v;
         if (O.ref_root_ang_vel) O.ref_root_ang_vel[(size_t)e * 3 + l] = w;
@@ -159,8 +165,9 @@ __global__ __launch_bounds__(64 * FK_MAX_WAVES) void tracker_links_kernel(const 
         }
       }
       if (l < 4) {
-        const float q = slerp1(A.root_rot, rl, rh, l, same, w0, w1);
+        float q = slerp1(A.root_rot, rl, rh, l, same, w0, w1);
         s_root[(3 + l) * TL_BLOCK + qi] = q;
+        if (anchored) q = anchor_quat_lane(An, l, q);
         if (O.ref_root_rot) O.ref_root_rot[(size_t)e * 4 + l] = q;
         if (terms && X.base_quat) acc[1] = X.base_quat[(size_t)e * 4 + l] * q;
       }
@@ -240,6 +247,9 @@ __global__ __launch_bounds__(64 * FK_MAX_WAVES) void tracker_links_kernel(const 
         yaw_of(X.base_quat[(size_t)e * 4 + 2], X.base_quat[(size_t)e * 4 + 3], syz, syw);
       }
     }
+    // the world frame moves with the environment's anchor; the heading frame removes every common x / y / yaw, the anchor's too
+    // (its five floats are loaded where a selected body is finished, not carried through the walk: the walk has no registers to spare)
+    const bool move = anchored && !heading && in;
     FkBodyRec nxt = tree->rec[P.step[i0] & 255u];
     for (int i = i0; i < i1; i++) {
       const uint32_t sc = P.step[i];
@@ -299,6 +309,13 @@ __global__ __launch_bounds__(64 * FK_MAX_WAVES) void tracker_links_kernel(const 
         q = unyaw_q(ryz, ryw, q);
         unyaw(ryz, ryw, vx, vy);
         unyaw(ryz, ryw, ox, oy);
+      }
+      if (move) {      // the finished world row, after the walk and before it is written and differenced
+        const Anchor An = anchor_load(S, (size_t)e);
+        anchor_point(An, px, py, pz);
+        anchor_quat(An, q.x, q.y, q.z, q.w);
+        anchor_vector(An, vx, vy);
+        anchor_vector(An, ox, oy);
       }
       if (REFS && in) {
         const float nan = NAN;

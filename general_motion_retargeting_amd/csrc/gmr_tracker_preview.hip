@@ -3,7 +3,8 @@
 //
 //   tracker_preview_kernel   the sampler's shape: 16 lanes per (environment, offset) query, 16 queries per workgroup, the K queries
 //                            of an environment adjacent.  Lanes l < 3 (l < 4) hold component l of the sampled root rows as in the
-//                            step; a 16-lane group is one DPP row, so the components meet by row-local shuffles.  The row of a
+//                            step (moved by the environment's anchor in the raw and the sim frame when anchors are enabled,
+//                            gmr_tracker_anchor.hip); a 16-lane group is one DPP row, so the components meet by row-local shuffles.  The row of a
 //                            query is assembled in LDS and the 16 rows of a workgroup -- one contiguous span of 16 D floats that
 //                            starts at a multiple of 64 D bytes -- leave with 16-byte stores.
 //
@@ -20,6 +21,7 @@
 #include "gmr_handles.h"
 #include "gmr_internal.h"
 #include "gmr_motion_sample.h"
+#include "gmr_tracker_dev.h"
 #include "gmr_workspace.h"
 
 // one rounding per operation, as in the sampler whose bits the raw rows reproduce
@@ -132,6 +134,18 @@ __global__ __launch_bounds__(256) void tracker_preview_kernel(const MotionArrays
           if (want_w) wc = lerp1(A.root_ang_vel, rl * 3 + l, rh * 3 + l, same, w0, w1);
         }
         if (l < 4 && want_q) qc = slerp1(A.root_rot, rl, rh, l, same, w0, w1);
+        // Tracker anchors: the raw and the sim frame see the reference where the environment's anchor puts it.
+        // The reference frame is blind to it, and so is the root-local body block of the raw frame.  The K queries of an
+        // environment are adjacent groups: they read the same 20 bytes.
+        if (S.anchor_pos != nullptr && P.frame != GMR_PREVIEW_FRAME_REFERENCE) {
+          Anchor An;
+          anchor_turn(S, (size_t)e, An);
+          const float at = l < 3 ? S.anchor_pos[(size_t)e * 3 + l] : 0.0f;
+          if (want_p) pc = anchor_point_lane(An, l, pc, at);
+          if (want_v) vc = anchor_vector_lane(An, l, vc);
+          if (want_w) wc = anchor_vector_lane(An, l, wc);
+          if (want_q) qc = anchor_quat_lane(An, l, qc);
+        }
         // the anchor: its position in lanes 0 .. 2, z and w of its rotation in lanes 2 and 3
         float cy = 1.0f, sy = 0.0f, yz = 0.0f, yw = 1.0f, pax = 0.0f, pay = 0.0f, paz = 0.0f;
         if (anchored) {

@@ -9,7 +9,9 @@ environment and draw number), so a run is reproducible whatever the number of en
 the observation half: the reference at every environment's clock plus a few offsets, packed as observation rows in
 one launch (``csrc/gmr_tracker_preview.hip``) that moves no clock.  :meth:`MotionTracker.reset_done` resets from done / failed masks in one
 launch and :meth:`MotionTracker.set_adaptive` draws episode starts where episodes recently failed (DESIGN.md section 6n,
-``csrc/gmr_tracker_adaptive.hip``).
+``csrc/gmr_tracker_adaptive.hip``).  :meth:`MotionTracker.set_anchor` and :meth:`MotionTracker.anchor_to_root` place the reference of every
+environment in the simulator's world: a yaw and a translation per environment that every world-frame output goes through (DESIGN.md
+section 6o, ``csrc/gmr_tracker_anchor.hip``).
 
 No GPU framework is imported here: :meth:`MotionTracker.step` takes and returns NumPy arrays, :meth:`MotionTracker.step_dev` reads
 and writes device memory the caller names -- ``_lib.DeviceBuffer``, a raw address, or anything with ``data_ptr()``.
@@ -141,6 +143,7 @@ class MotionTracker:
         self._links = None            # (fk, nsel, sim_body, frame) once set_links has attached a selection
         self._preview = None          # (K, blocks in row order, frame, nsel) once set_preview has configured one
         self._adaptive = None         # (bin_seconds, bin_start i64[C + 1]) once set_adaptive has built the bins
+        self._anchors = False         # whether the per-environment anchors are enabled
         if sc is not None or wt is not None:
             self.set_terms(sc, wt)
 
@@ -333,6 +336,135 @@ class MotionTracker:
         _lib.check(_lib.lib().gmr_motion_tracker_adaptive_state(self.handle, *[_lib._ptr(out[k]) for k in ("bin_start", "fail_now", "ema", "prob", "cdf")]))
         assert np.array_equal(out["bin_start"], bin_start), "the library's bins differ from the ones computed here"
         out["clip_prob"] = np.bincount(np.repeat(np.arange(Cn), np.diff(bin_start)), weights=out["prob"], minlength=Cn)
+        return out
+
+    # ---- anchors -------------------------------------------------------------------------------------
+    def _anchor_yaw_allowed(self, what: str) -> None:
+        if self.library.ang_vel != "world":
+            raise ValueError(f'{what}: a yaw anchor needs a library built with ang_vel="world": the root_ang_vel of '
+                             f'ang_vel="{self.library.ang_vel}" is not a physical angular velocity and cannot be rotated')
+
+    def _need_anchors(self, what: str) -> None:
+        if not getattr(self, "_anchors", False):
+            raise ValueError(f"{what}: anchors are not enabled on this tracker, call enable_anchors() first")
+
+    def enable_anchors(self, on: bool = True) -> None:
+        """Per-environment anchors: a yaw about the vertical, then a translation, applied to every world-frame quantity the tracker emits
+        or compares -- the four root rows and root terms of :meth:`step` / :meth:`step_links`, the ``frame="world"`` link rows and terms,
+        the root blocks of a ``"raw"`` preview and the reference of a ``"sim"`` one.  ``frame="heading"`` links and a ``"reference"``
+        preview do not see them.  Enabling allocates the two arrays once and fills them with the identity (synchronous; a tracker that
+        has them keeps them as they are); ``on=False`` frees them and the tracker runs the plain code path again."""
+        from . import _lib
+        _lib.check(_lib.lib().gmr_motion_tracker_enable_anchors(self.handle, 1 if on else 0))
+        self._anchors = bool(on)
+
+    def _anchor_setup(self, what, pos, yaw, env_ids, n=None):
+        """the checks of :meth:`set_anchor`, all of them before a device is touched -> ``(n, ids i32[n] or None, pos f32[n,3] or None, yaw
+        f32[n] or None)``"""
+        ids = None
+        if env_ids is None:
+            n = self.num_envs
+        else:
+            ids = np.ascontiguousarray(env_ids, dtype=np.int32).reshape(-1)
+            n = len(ids)
+        if pos is not None:
+            pos = np.ascontiguousarray(pos, dtype=np.float32)
+            if pos.shape != (n, 3):
+                raise ValueError(f"{what}: pos has shape {pos.shape}, {(n, 3)} needed")
+            if not np.isfinite(pos).all():
+                raise ValueError(f"{what}: pos is not finite")
+        if yaw is not None:
+            self._anchor_yaw_allowed(what)
+            yaw = np.ascontiguousarray(yaw, dtype=np.float32)
+            if yaw.shape != (n,):
+                raise ValueError(f"{what}: yaw has shape {yaw.shape}, {(n,)} needed")
+            if not np.isfinite(yaw).all():
+                raise ValueError(f"{what}: yaw is not finite")
+        return n, ids, pos, yaw
+
+    def set_anchor(self, pos=None, yaw=None, env_ids=None) -> int:
+        """Sets the anchors of ``env_ids`` (all, in order, by default): ``pos [n,3]`` metres and / or ``yaw [n]`` radians; what is ``None``
+        is kept.  Enables anchors when they are not.  Returns how many ids lay outside ``[0, num_envs)`` (they are ignored)."""
+        from . import _lib
+        n, ids, pos, yaw = self._anchor_setup("set_anchor", pos, yaw, env_ids)
+        ignored = C.c_int()
+        _lib.check(_lib.lib().gmr_motion_tracker_set_anchor(self.handle, n, _lib._ptr(ids), _lib._ptr(pos), _lib._ptr(yaw), C.byref(ignored)))
+        self._anchors = True
+        return int(ignored.value)
+
+    def set_anchor_dev(self, pos=None, yaw=None, env_ids=None, n: Optional[int] = None, stream=None) -> None:
+        """:meth:`set_anchor` on device memory (``pos f32[n*3]``, ``yaw f32[n]`` radians, ``env_ids i32[n]`` with ``n``, or None for all),
+        asynchronous on ``stream``: one launch.  Anchors must be enabled."""
+        from . import _lib
+        self._need_anchors("set_anchor_dev")
+        if yaw is not None:
+            self._anchor_yaw_allowed("set_anchor_dev")
+        n = self._list_length("set_anchor_dev", env_ids, n)
+        p_ids, p_pos, p_yaw = _dev_ptr(env_ids, "env_ids", "int32", n), _dev_ptr(pos, "pos", "float32", n * 3), _dev_ptr(yaw, "yaw", "float32", n)
+        _lib.check(_lib.lib().gmr_motion_tracker_set_anchor_dev(self.handle, n, p_ids, p_pos, p_yaw, _lib._s(stream)))
+
+    def _list_length(self, what: str, env_ids, n) -> int:
+        if env_ids is None:
+            if n is not None and int(n) != self.num_envs:
+                raise ValueError(f"{what}: without env_ids every environment is served: n = {n}, num_envs = {self.num_envs}")
+            return self.num_envs
+        if n is None or int(n) < 0:
+            raise ValueError(f"{what}: env_ids on the device needs n, the length of the list")
+        return int(n)
+
+    def anchor_to_root(self, root_pos, root_quat, mask=None, env_ids=None, yaw: bool = True, z: bool = False) -> int:
+        """Anchors the reference to where the robot is: for every environment whose ``mask`` is set (``None``: all), the anchor that
+        carries the reference root at the environment's own ``(clip, time)`` onto ``root_pos [n,3]`` / ``root_quat [n,4]`` xyzw in x, y and
+        -- with ``yaw`` -- heading, and -- with ``z`` -- height; what is not asked for is kept.  Without ``env_ids`` the three arrays
+        cover every environment; with it (every environment at most once) they are indexed by list position, as the masks of
+        :meth:`reset_done` are.  A bad assignment or a root that is not finite leaves that environment's anchor as it was.  Enables
+        anchors when they are not.  Returns how many ids of masked entries lay outside ``[0, num_envs)``."""
+        from . import _lib
+        if yaw:
+            self._anchor_yaw_allowed("anchor_to_root")
+        ids, n = None, self.num_envs
+        if env_ids is not None:
+            ids = np.ascontiguousarray(env_ids, dtype=np.int32).reshape(-1)
+            n = len(ids)
+            if len(np.unique(ids)) != n:
+                raise ValueError("anchor_to_root: env_ids names an environment twice")
+        rp, rq = np.ascontiguousarray(root_pos, dtype=np.float32), np.ascontiguousarray(root_quat, dtype=np.float32)
+        if rp.shape != (n, 3):
+            raise ValueError(f"anchor_to_root: root_pos has shape {rp.shape}, {(n, 3)} needed")
+        if rq.shape != (n, 4):
+            raise ValueError(f"anchor_to_root: root_quat has shape {rq.shape}, {(n, 4)} needed")
+        m = _mask(mask, "mask", n)
+        ignored = C.c_int()
+        _lib.check(_lib.lib().gmr_motion_tracker_anchor_to_root(self.handle, n, _lib._ptr(ids), _lib._ptr(m), _lib._ptr(rp), _lib._ptr(rq),
+                                                                (_lib.ANCHOR_YAW if yaw else 0) | (_lib.ANCHOR_Z if z else 0), C.byref(ignored)))
+        self._anchors = True
+        return int(ignored.value)
+
+    def anchor_to_root_dev(self, root_pos, root_quat, mask=None, env_ids=None, n: Optional[int] = None, yaw: bool = True, z: bool = False,
+                           stream=None) -> None:
+        """:meth:`anchor_to_root` on device memory, asynchronous on ``stream``: ONE launch, no allocation, no synchronisation, no
+        read-back.  ``mask`` is an ``i32`` mask as a step leaves it (``finished``) or as :meth:`reset_done_dev` takes it; ``root_pos
+        f32[n*3]``, ``root_quat f32[n*4]``; with ``env_ids`` (``i32[n]``) ``n`` is mandatory.  Anchors must be enabled."""
+        from . import _lib
+        self._need_anchors("anchor_to_root_dev")
+        if yaw:
+            self._anchor_yaw_allowed("anchor_to_root_dev")
+        n = self._list_length("anchor_to_root_dev", env_ids, n)
+        if root_pos is None or root_quat is None:
+            raise ValueError("anchor_to_root_dev: root_pos and root_quat are needed")
+        p_ids, p_mask = _dev_ptr(env_ids, "env_ids", "int32", n), _dev_ptr(mask, "mask", "int32", n)
+        p_pos, p_quat = _dev_ptr(root_pos, "root_pos", "float32", n * 3), _dev_ptr(root_quat, "root_quat", "float32", n * 4)
+        _lib.check(_lib.lib().gmr_motion_tracker_anchor_to_root_dev(self.handle, n, p_ids, p_mask, p_pos, p_quat,
+                                                                    (_lib.ANCHOR_YAW if yaw else 0) | (_lib.ANCHOR_Z if z else 0), _lib._s(stream)))
+
+    def anchor_state(self) -> Optional[Dict[str, np.ndarray]]:
+        """``pos f32[N,3]`` and ``yaw_zw f32[N,2]``, the ``(z, w)`` of the yaw's unit quaternion, or ``None`` when anchors are off.
+        Synchronous."""
+        from . import _lib
+        if not getattr(self, "_anchors", False):
+            return None
+        out = {"pos": np.empty((self.num_envs, 3), np.float32), "yaw_zw": np.empty((self.num_envs, 2), np.float32)}
+        _lib.check(_lib.lib().gmr_motion_tracker_anchor_state(self.handle, _lib._ptr(out["pos"]), _lib._ptr(out["yaw_zw"])))
         return out
 
     # ---- the step ---------------------------------------------------------------------------------------------------------

@@ -731,6 +731,65 @@ int gmr_motion_tracker_reset_done(gmr_motion_tracker_t* t, int n, const int32_t*
 int gmr_motion_tracker_adaptive_state(gmr_motion_tracker_t* t, int32_t* bin_start, uint32_t* fail_now, double* ema, double* prob,
                                       double* cdf);
 
+/* ---- N8: tracker anchors (a per-environment rigid move of the reference about the vertical) ---- */
+/* Opt-in, a capability of this library.  A simulator spreads its N environments over a grid of origins and a robot faces wherever it
+ * faces after a reset; the clips of a library all live in the coordinates of their files.  An anchor is what lies between the two: per
+ * environment a yaw psi_e about z, then a translation t_e, kept on the device beside the clocks and applied to every world-frame
+ * quantity the tracker emits or compares.  The statement of record is tests/anchor_mirror.py; this is the same in words.
+ * STATE per environment: anchor_pos f32[3] = t, anchor_yaw f32[2] = (z, w) of the unit quaternion (0, 0, z, w).  Identity: (0, 0, 0),
+ * (0, 1).
+ * ARITHMETIC, float32, one rounding per operation, in exactly this order:
+ *   c = w w - z z, s = 2 z w
+ *   position    x' = (c x - s y) + tx, y' = (s x + c y) + ty, z' = z + tz
+ *   vector      x' = c x - s y, y' = s x + c y, z untouched (linear and angular velocity)
+ *   quaternion  xyzw, not renormalised: (w qx - z qy, w qy + z qx, w qz + z qw, w qw - z qz)
+ * WHERE.
+ *   1. gmr_motion_tracker_step[_dev] / step_links[_dev]: ref_root_pos and ref_root_rot are anchored, ref_root_vel and ref_root_ang_vel
+ *      rotated; the four root terms compare against those rows.  Dof rows and dof terms are untouched.
+ *   2. step_links, GMR_TRACKER_FRAME_WORLD: the finished world row of every selected body -- after the walk, before it is written and
+ *      differenced -- so ref_body_* and the link terms, max_dist and fail are the anchored ones.  GMR_TRACKER_FRAME_HEADING removes
+ *      every common x / y / yaw: its link rows and link terms are bit-identical to an unanchored tracker's.
+ *   3. preview: GMR_PREVIEW_FRAME_RAW anchors the root blocks (root_pos, root_quat, root_vel, root_ang_vel; root_rot6 is the matrix
+ *      of the anchored quaternion), the root-local body block keeps its bits; GMR_PREVIEW_FRAME_SIM expresses the ANCHORED reference
+ *      (root and bodies) relative to the simulator's root; GMR_PREVIEW_FRAME_REFERENCE keeps its bits.
+ * A tracker on which anchors were never enabled (or are disabled again) runs the code it ran before they existed: the two arrays are
+ * null and the test is one branch, uniform over the launch.  A redraw (GMR_MOTION_LOOP off) and a loop wrap leave the anchor as it is.
+ * A yaw is refused (GMR_ERR_ARG) on a library filled with GMR_MOTION_ANGVEL_REFERENCE, whose root_ang_vel cannot be rotated; a
+ * translation is fine there.  The angle of set_anchor becomes (sin(psi / 2), cos(psi / 2)) in float32 by a routine of this library
+ * made of +, -, * and floor only (gmr_tracker_anchor.hip, anchor_half_angle; tests/anchor_mirror.py half_angle), on the host for the
+ * synchronous entry point and in the kernel for _dev: the same bits both ways. */
+#define GMR_ANCHOR_YAW 1   /* anchor_to_root: take the yaw from the given root (else it is kept) */
+#define GMR_ANCHOR_Z   2   /* anchor_to_root: take t_z too (else it is kept) */
+/* on != 0: allocates the two arrays and fills them with the identity (synchronous; the only allocation of the feature; nothing happens
+ * when they are there already).  on == 0: synchronises, frees them, the tracker is a plain one again. */
+int gmr_motion_tracker_enable_anchors(gmr_motion_tracker_t* t, int on);
+/* Sets the anchors of the n listed environments (d_env_ids NULL: all of them, in order, n = N): pos f32[n][3] and / or yaw f32[n] in
+ * radians, a NULL part is kept.  Ids outside [0, N) are dropped and counted as gmr_motion_tracker_reset counts them.  One launch.
+ * _dev: GMR_ERR_ARG unless anchors are enabled; values are not looked at.  The synchronous twin enables anchors first, refuses
+ * non-finite input before anything is touched and reports the ids of this call that were dropped. */
+int gmr_motion_tracker_set_anchor_dev(gmr_motion_tracker_t* t, int n, const int32_t* d_env_ids, const float* d_pos, const float* d_yaw,
+                                      void* stream);                                                       /* asynchronous */
+int gmr_motion_tracker_set_anchor(gmr_motion_tracker_t* t, int n, const int32_t* env_ids, const float* pos, const float* yaw,
+                                  int* ignored /* or NULL */);
+/* Anchors the reference to where the robot is.  ONE launch, no allocation, no synchronisation, no read-back.  Entry i is environment
+ * d_env_ids[i] (without a list: environment i, n = N); d_mask i32[n] (NULL: every entry), d_root_pos f32[n][3] and d_root_quat
+ * f32[n][4] xyzw belong to entry i, as the masks of gmr_motion_tracker_reset_done_dev do.  For every entry whose mask is not zero:
+ *   (p_r, q_r) = the reference root at (clip, (double)time) under the tracker's loop mode, the sampler's bits
+ *   (z_r, w_r) = yaw(q_r), (z_s, w_s) = yaw(q_s): normalize(0, 0, q.z, q.w), the identity for z = w = 0; here with a correctly
+ *     rounded float32 square root and division (the heading frame of N5 / N6 takes the hardware's square root, good to one ulp)
+ *   GMR_ANCHOR_YAW: (z, w) = yaw(z_s w_r - w_s z_r, w_s w_r + z_s z_r); else (z, w) stays
+ *   t_x = p_s.x - (c p_r.x - s p_r.y), t_y = p_s.y - (s p_r.x + c p_r.y) with c, s of the new (z, w)
+ *   GMR_ANCHOR_Z: t_z = p_s.z - p_r.z; else t_z stays
+ * A bad assignment (step 6 of the tracker) or a root that is not finite leaves that environment's anchor as it was.  Ids of masked
+ * entries outside [0, N) are dropped and counted.  Every environment at most once in a list.  _dev: GMR_ERR_ARG unless anchors are
+ * enabled; the synchronous twin enables them first. */
+int gmr_motion_tracker_anchor_to_root_dev(gmr_motion_tracker_t* t, int n, const int32_t* d_env_ids, const int32_t* d_mask,
+                                          const float* d_root_pos, const float* d_root_quat, int flags, void* stream);   /* asynchronous */
+int gmr_motion_tracker_anchor_to_root(gmr_motion_tracker_t* t, int n, const int32_t* env_ids, const int32_t* mask, const float* root_pos,
+                                      const float* root_quat, int flags, int* ignored /* or NULL */);
+/* the anchors on the host: pos f32[N][3], yaw_zw f32[N][2], each may be NULL; synchronises; GMR_ERR_ARG unless anchors are enabled */
+int gmr_motion_tracker_anchor_state(gmr_motion_tracker_t* t, float* pos, float* yaw_zw);
+
 /* ---- multi-GPU: one rank per GPU, ONE broadcast, no per-step collective ------------ */
 /* The reference parallelises over files with mp.Pool on one CPU (scripts/smplx_to_robot_dataset.py:241-242); here
  * streams shard over the ranks of one node and the only data that crosses ranks is the packed robot model + task set.

@@ -8,6 +8,10 @@ composition it replaces, in one run.
             the composition: ``sample_dev`` into torch tensors, the clock converted to float64, the scatter into robot order and the
             six formulas of t1_imitation.py:249-309 as torch operations, the clock advance
 
+  --anchors per N, on the same tracker: the step with simulator state and a link step (six links of the G1, world
+            frame, packed rigid-body tensor, ``total / fail / finished / link_err``) plain, then both again with anchors enabled and set
+            to random moves, and ``anchor_to_root_dev`` alone with a mask of one in fifty and of all
+
 Each figure is the mean of ``--reps`` repetitions between two device events on one stream, after a warm-up (the composition: a host
 clock around a device synchronise, since torch enqueues on its own stream).  Bytes come from the shapes (state, two source rows,
 simulator rows, every output row once); the share is bytes/s over the 8 TB/s HBM peak.  Prints one JSON document; --out writes it to
@@ -69,6 +73,36 @@ def torch_composition(torch, lib, N, R, dmap, default, scales, reps):
     return (clock.perf_counter() - t0) / reps
 
 
+def anchored_legs(hip, st, t, rng, N, sim, out, reps):
+    """the plain step and link step of tracker ``t``, the same two with anchors set, and ``anchor_to_root_dev`` alone -> microseconds"""
+    from general_motion_retargeting_amd import KinematicsModel, ROBOT_XML_DICT
+    km = KinematicsModel(ROBOT_XML_DICT["unitree_g1"])
+    sel = [29, 3, 15, 0, 36, 8]
+    nb = len(km.body_names)
+    t.set_links(km, bodies=sel, sim_bodies=sel, frame="world")
+    links = {"body_state": hip.DeviceBuffer.from_host(rng.normal(size=(N, nb, 13)).astype(np.float32)), "num_bodies": nb}
+    lout = {k: hip.DeviceBuffer(N * c * 4) for k, c in (("total", 1), ("fail", 1), ("finished", 1), ("link_err", 4))}
+    legs = {"step": lambda: t.step_dev(sim, stream=st, **out), "step_links": lambda: t.step_links_dev(sim, links, stream=st, **lout)}
+    r = {}
+    for name, fn in legs.items():
+        r[name + "_plain_us"] = timed(hip, st, fn, reps) * 1e6
+    t.enable_anchors()
+    t.set_anchor_dev(hip.DeviceBuffer.from_host(rng.uniform(-10, 10, (N, 3)).astype(np.float32)),
+                     hip.DeviceBuffer.from_host(rng.uniform(-np.pi, np.pi, N).astype(np.float32)), stream=st)
+    for name, fn in legs.items():
+        r[name + "_anchored_us"] = timed(hip, st, fn, reps) * 1e6
+        r[name + "_anchored_over_plain"] = r[name + "_anchored_us"] / r[name + "_plain_us"]
+    q = rng.normal(size=(N, 4))
+    root_pos = hip.DeviceBuffer.from_host(rng.uniform(-5, 5, (N, 3)).astype(np.float32))
+    root_quat = hip.DeviceBuffer.from_host((q / np.linalg.norm(q, axis=1, keepdims=True)).astype(np.float32))
+    for name, mask in (("one_in_fifty", (rng.uniform(size=N) < 0.02).astype(np.int32)), ("all", None)):
+        d_mask = None if mask is None else hip.DeviceBuffer.from_host(mask)
+        r[f"anchor_to_root_dev_{name}_us"] = timed(hip, st, lambda: t.anchor_to_root_dev(root_pos, root_quat, mask=d_mask, yaw=True, z=True, stream=st), reps) * 1e6
+    t.enable_anchors(False)
+    t.set_links(bodies=[])
+    return r
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--clips", type=int, default=4096)
@@ -76,6 +110,7 @@ def main(argv=None):
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--sizes", type=int, nargs="+", default=[4096, 65536, 1048576])
     ap.add_argument("--no-torch", action="store_true", help="skip the composition even when torch is importable")
+    ap.add_argument("--anchors", action="store_true", help="add the anchored legs of DESIGN.md section 6o")
     ap.add_argument("--out")
     args = ap.parse_args(argv)
     from general_motion_retargeting_amd import MotionTracker, _lib as hip
@@ -132,6 +167,8 @@ def main(argv=None):
             sec = torch_composition(torch, lib, N, R, dmap, default, scales, args.reps)
             r["composition_sample_dev_plus_torch"] = {"us": sec * 1e6, "note": "host clock around a device synchronise"}
             r["composition_over_step"] = sec * 1e6 / r["step_with_simulator_state"]["us"]
+        if args.anchors:
+            r["anchors"] = anchored_legs(hip, st, t, rng, N, sim, out, args.reps)
         doc["N"][str(N)] = r
         t.close()
     txt = json.dumps(doc, indent=1)
