@@ -76,15 +76,29 @@ PROBE_LIBS = {"flags": os.path.join(os.path.dirname(PROBE_SRC), "libgmr_math_pro
               "wide": os.path.join(os.path.dirname(PROBE_SRC), "libgmr_math_probe_wide.so")}
 
 
+def _build_probe_libs(src: str, libs: dict, force: bool) -> dict:
+    deps = [src, os.path.join(CSRC, "gmr_device_math.h"), os.path.abspath(__file__)]
+    extra = {"flags": [], "wide": PER_SOURCE_FLAGS["gmr_ik_wide.hip"]}
+    for name, out in libs.items():
+        if force or not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
+            subprocess.check_call([_hipcc()] + FLAGS + extra[name] + ["-shared", "-o", out + ".tmp", src])
+            os.replace(out + ".tmp", out)
+    return dict(libs)
+
+
 def build_probe(force: bool = False) -> dict:
     """Both probe libraries, rebuilt when the probe source or the header is newer (the libraries are cached on those mtimes)."""
-    deps = [PROBE_SRC, os.path.join(CSRC, "gmr_device_math.h"), os.path.abspath(__file__)]
-    extra = {"flags": [], "wide": PER_SOURCE_FLAGS["gmr_ik_wide.hip"]}
-    for name, out in PROBE_LIBS.items():
-        if force or not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-            subprocess.check_call([_hipcc()] + FLAGS + extra[name] + ["-shared", "-o", out + ".tmp", PROBE_SRC])
-            os.replace(out + ".tmp", out)
-    return dict(PROBE_LIBS)
+    return _build_probe_libs(PROBE_SRC, PROBE_LIBS, force)
+
+
+# The probe of se3_jlinv_coef5 / se3_jlinv_apply5 (tests/hip/jlinv_apply_probe.hip, tests/test_jlinv_apply.py): the same two flag sets.
+JLINV_PROBE_SRC = os.path.join(os.path.dirname(PROBE_SRC), "jlinv_apply_probe.hip")
+JLINV_PROBE_LIBS = {"flags": os.path.join(os.path.dirname(PROBE_SRC), "libgmr_jlinv_apply_probe.so"),
+                    "wide": os.path.join(os.path.dirname(PROBE_SRC), "libgmr_jlinv_apply_probe_wide.so")}
+
+
+def build_jlinv_probe(force: bool = False) -> dict:
+    return _build_probe_libs(JLINV_PROBE_SRC, JLINV_PROBE_LIBS, force)
 
 
 def build_variant(name: str, defines=(), verbose: bool = False) -> str:

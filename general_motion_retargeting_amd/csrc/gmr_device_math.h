@@ -374,6 +374,73 @@ __device__ __forceinline__ void se3_jlinv_col5(const double e[6], const double a
   Bc[0] = -(hy.x + awy * w.x + da * y.x); Bc[1] = -(hy.y + awy * w.y + da * y.y); Bc[2] = -(hy.z + awy * w.z + da * y.z);
 }
 
+// The same blocks APPLIED to a vector, for one lane per (task, dof) pair: the latency kernel never needs M = -Jl^-1(e)
+// itself, only M [jl; ja] per pair.  se3_jlinv_coef5 is the prelude of se3_jlinv_col5 and nothing else (the same t2
+// switches, the same expressions in the same order), once per task: coef = {a, da, c1, kw, dq, sq.x, sq.y, sq.z}.  In the
+// identity zone it returns {0, 1, 0, 0, 0, 0, 0, 0}; a == 0 marks that zone for se3_jlinv_apply5 (a >= 1/12 elsewhere).
+__device__ __forceinline__ void se3_jlinv_coef5(const double e[6], const double aux[5], double coef[8]) {
+  const d3 rho = {e[0], e[1], e[2]}, w = {e[3], e[4], e[5]};
+  const double t2 = dot(w, w);
+  coef[0] = 0.0; coef[1] = 1.0;
+#pragma unroll
+  for (int i = 2; i < 8; i++) coef[i] = 0.0;
+  if (t2 < 1e-10) return;
+  const double a = aux[0];
+  double c1, c2, c3;
+  if (t2 < 1e-2) {
+    c1 = 1.0 / 6.0 - t2 / 120.0 + t2 * t2 / 5040.0 - t2 * t2 * t2 / 362880.0;
+    c2 = -1.0 / 24.0 + t2 / 720.0 - t2 * t2 / 40320.0 + t2 * t2 * t2 / 3628800.0;
+    c3 = -1.0 / 120.0 + t2 / 5040.0 - t2 * t2 / 362880.0 + t2 * t2 * t2 / 39916800.0;
+  } else {
+    const double t = aux[3], it = aux[4], sn = aux[1], cs = aux[2];
+    const double it2 = it * it;
+    c1 = (t - sn) * it2 * it;
+    c2 = (1.0 - 0.5 * t2 - cs) * it2 * it2;
+    c3 = (t - sn - t2 * t / 6.0) * it2 * it2 * it;
+  }
+  const double c4 = -0.5 * (c2 - 3.0 * c3);
+  const double s = dot(w, rho);
+  const d3 n = cross(w, rho), m = cross(w, n);
+  const double k1 = (c1 + c2) * s;
+  coef[0] = a;
+  coef[1] = 1.0 - a * t2;
+  coef[2] = c1;
+  coef[3] = -2.0 * c4 * s;
+  coef[4] = -2.0 * c1 * s + 2.0 * c4 * s * t2;
+  coef[5] = 0.5 * rho.x - k1 * w.x - c2 * m.x;
+  coef[6] = 0.5 * rho.y - k1 * w.y - c2 * m.y;
+  coef[7] = 0.5 * rho.z - k1 * w.z - c2 * m.z;
+}
+
+// A x = hw x x + (a (w . x)) w + da x
+__device__ __forceinline__ d3 jlinv_op_a(d3 w, d3 hw, double a, double da, d3 x) {
+  const double aw = a * dot(w, x);
+  const d3 hx = cross(hw, x);
+  return d3{hx.x + aw * w.x + da * x.x, hx.y + aw * w.y + da * x.y, hx.z + aw * w.z + da * x.z};
+}
+// Q v = sq x v + (c1 (w . v)) rho + (c1 (rho . v) + kw (w . v)) w + dq v
+__device__ __forceinline__ d3 jlinv_op_q(d3 w, d3 rho, d3 sq, double c1, double kw, double dq, d3 v) {
+  const double wv = dot(w, v), rv = dot(rho, v);
+  const double kr = c1 * wv, kq = c1 * rv + kw * wv;
+  const d3 sx = cross(sq, v);
+  return d3{sx.x + kr * rho.x + kq * w.x + dq * v.x, sx.y + kr * rho.y + kq * w.y + dq * v.y, sx.z + kr * rho.z + kq * w.z + dq * v.z};
+}
+
+// [top; bot] = M [jl; ja], M = -Jl^-1(e) = [[-A, -B], [0, -A]], B = -A Q A: three applications of A and one of Q, no 3 x 3
+// matrix anywhere.  In the identity zone hw is zero too, so that A = I and Q = 0 exactly (up to the sign of zeros).
+__device__ __forceinline__ void se3_jlinv_apply5(const double e[6], const double coef[8], d3 jl, d3 ja, d3& top, d3& bot) {
+  const d3 rho = {e[0], e[1], e[2]}, w = {e[3], e[4], e[5]};
+  const double a = coef[0], da = coef[1], c1 = coef[2], kw = coef[3], dq = coef[4];
+  const d3 sq = {coef[5], coef[6], coef[7]};
+  const double h = a != 0.0 ? -0.5 : 0.0;
+  const d3 hw = {h * w.x, h * w.y, h * w.z};
+  const d3 v1 = jlinv_op_a(w, hw, a, da, ja);
+  const d3 z = jlinv_op_a(w, hw, a, da, jlinv_op_q(w, rho, sq, c1, kw, dq, v1));
+  const d3 u = jlinv_op_a(w, hw, a, da, jl);
+  top = d3{z.x - u.x, z.y - u.y, z.z - u.z};
+  bot = d3{-v1.x, -v1.y, -v1.z};
+}
+
 // The lane id as a value the optimiser cannot see through.  Every predicate on the lane id (lane < nb, lane == pivot, ...)
 // is invariant for the whole kernel, so LLVM computes each ONCE at kernel entry and keeps its 64-bit mask in an SGPR
 // pair; a fully inlined frame loop has more than a hundred of them, they spill to VGPR lanes (v_writelane) and every

@@ -9,7 +9,7 @@
 //   LDS constants  joint-local transforms (body pos/quat, hinge axes), limits, task tables, solve parameters
 //                  (NW = 4: also the static H-assembly schedule; NW = 1 streams it from global memory)
 //   LDS state      q, FK ping-pong (pos, quat per body), world hinge axes, targets, residuals e_k,
-//                  -Jl^-1(e_k), weighted per-(task,dof) Jacobian columns, H, c, bounds
+//                  -Jl^-1(e_k) (NW = 4: its eight coefficients), weighted per-(task,dof) Jacobian columns, H, c, bounds
 //   registers      the working copy of H during the factorisation: lane i holds row i
 //
 // Per frame only nhuman*7 doubles are read from HBM (coalesced, contiguous) and nq doubles are
@@ -20,8 +20,10 @@
 //   FK          lane = body; log2(depth) rounds of pointer jumping over the kinematic tree
 //               (transform composition is associative), ping-pong buffers in LDS
 //   residuals   lane = task: e_k = log(T_wb^-1 T_wt); DPP row reduction for |e|
-//   Jl^-1       lane = task
-//   Jacobian    lane = (task, ancestor dof) pair: weighted column W_k (-Jl^-1) J_body[:, d]
+//   Jl^-1       NW = 1: lane = 16 j + task, column j of M_k = -Jl^-1(e_k).  NW = 4: lane = task, only the eight
+//               coefficients of the operator form (se3_jlinv_coef5); no matrix is formed
+//   Jacobian    lane = (task, ancestor dof) pair: weighted column W_k (-Jl^-1) J_body[:, d].  NW = 1: M_k times the
+//               column.  NW = 4: the operators applied to the column (se3_jlinv_apply5: cross and dot products)
 //   H           lane = owner of a set of H entries (static LPT schedule, gmr_ik_layout.h): the
 //               Jacobian of a task is non-zero only on its root->frame path, so H is assembled
 //               block-sparse (6k instead of 103k multiply-adds for G1), one store per entry
@@ -33,7 +35,7 @@
 //               once, Murty's single exchange as the finite-termination fallback), warm-started from the
 //               previous solve's active set.
 //   NW = 4      the helpers (i) turn each new FK state into the body Jacobians while the main wavefront
-//               evaluates residuals and Jl^-1, (ii) share the weighted Jacobian columns, (iii) assemble H while
+//               evaluates residuals and the Jl^-1 coefficients, (ii) share the weighted Jacobian columns, (iii) assemble H while
 //               the main wavefront gathers c and the bounds, (iv) eliminate one limb each in the QP.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -149,6 +151,10 @@ __device__ __forceinline__ void fk_wave(const LT& L, double* sm, const FkLane& F
     const int src = F.src[r];
     const d3 pa = {bpermute_d(src, pos.x), bpermute_d(src, pos.y), bpermute_d(src, pos.z)};
     const d4 qa = {bpermute_d(src, quat.w), bpermute_d(src, quat.x), bpermute_d(src, quat.y), bpermute_d(src, quat.z)};
+    // All 14 permutes are consumed inside the branch below, which the compiler skips on an empty mask: at the join it had to
+    // assume them still in flight and put a (no-op) wait in front of each of the next round's permutes.  One explicit wait
+    // here, on both paths, replaces those 14: s_waitcnt lgkmcnt(0), vmcnt and expcnt left alone (gfx9 encoding).
+    if (NW > 1) __builtin_amdgcn_s_waitcnt(0xc07f);
     if (lane < nb && dep >= (1 << r)) {
       pos = pa + qrot(qa, pos);
       quat = qmul(qa, quat);
@@ -207,8 +213,10 @@ struct StageTabs {
   const short* pair_index; const uint2* items;      // 64-bit schedule items (gmr_ik_layout.h)
 };
 
-// (a) lane = 16 j + task: column j of M_k = -Jl^-1(e_k) (blocks -A, -B; three lanes per task), weighted residual;
-// returns the LM term mu
+// (a) NW == 1: lane = 16 j + task: column j of M_k = -Jl^-1(e_k) (blocks -A, -B; three lanes per task), weighted residual.
+// NW > 1: lane = task: only the eight coefficients of the operator form (se3_jlinv_coef5), stored where M_k would start
+// (sm[L.o.M + 18 k ..]); every pair lane applies the operators to its own column (pairs_from_jbody), so no matrix is
+// formed on the wavefront everybody waits for.  Returns the LM term mu.
 template <int NW, class LT>
 __device__ __forceinline__ double jlog_phase(const LT& L, double* sm, int stage, double lm_damping, int lane,
                                              Prof& pr) {
@@ -219,7 +227,29 @@ __device__ __forceinline__ double jlog_phase(const LT& L, double* sm, int stage,
   const double* wrot = sm + L.o.wrot[stage];
   double mu = 0.0;
   const int k = lane & 15, j = lane >> 4;
-  if (k < K && j < 3) {
+  if (NW > 1) {
+    if (lane < K) {
+      const double* e = sm + L.o.e + 6 * lane;
+      double ee[6];
+#pragma unroll
+      for (int r = 0; r < 6; r++) ee[r] = e[r];
+      const double* ax = sm + L.o.eaux + 5 * lane;
+      const double aux[5] = {ax[0], ax[1], ax[2], ax[3], ax[4]};
+      double coef[8];
+      se3_jlinv_coef5(ee, aux, coef);
+      double* co = sm + L.o.M + 18 * lane;
+#pragma unroll
+      for (int r = 0; r < 8; r++) co[r] = coef[r];
+      const double wp = wpos[lane], wr = wrot[lane];
+      double* we = sm + L.o.we + 6 * lane;
+#pragma unroll
+      for (int r = 0; r < 6; r++) {
+        double v = (r < 3 ? wp : wr) * ee[r];
+        we[r] = v;
+        mu += v * v;
+      }
+    }
+  } else if (k < K && j < 3) {
     const double* e = sm + L.o.e + 6 * k;
     double ee[6];
 #pragma unroll
@@ -336,7 +366,9 @@ __device__ __forceinline__ void jbody_phase(const LT& L, double* sm, int stage, 
   }
 }
 
-// (b2) all wavefronts, after Jl^-1: Jw[p] = W_k (-Jl^-1(e_k)) Jb[p] in place, and the column's share of c
+// (b2) all wavefronts, after the coefficient phase: Jw[p] = W_k (-Jl^-1(e_k)) Jb[p] in place, -Jl^-1(e_k) applied in operator
+// form from the task's e and its eight coefficients (14 doubles read instead of the 18 of a matrix), and the column's share of c.
+// Every pair is treated alike: a task without a position cost multiplies `top` by its zero weight.
 template <class LT>
 __device__ __forceinline__ void pairs_from_jbody(const LT& L, double* sm, int stage, const StageTabs& tb, int vlane, int nvl,
                                                  const uint32_t* zero_off, int k_first) {
@@ -350,19 +382,24 @@ __device__ __forceinline__ void pairs_from_jbody(const LT& L, double* sm, int st
     const int k = p == vlane ? k_first : ((unsigned short)tb.pair_task[p] & 15u);
     double* o = Jw + 6 * p;
     const d3 jl = {o[0], o[1], o[2]}, ja = {o[3], o[4], o[5]};
-    const double* M = sm + L.o.M + 18 * k;
+    const double* e = sm + L.o.e + 6 * k;
+    const double* co = sm + L.o.M + 18 * k;            // the task's coefficients (jlog_phase), not a matrix
     const double* we = sm + L.o.we + 6 * k;
     const double wp = wpos[k], wr = wrot[k];
+    double ee[6], coef[8];
+#pragma unroll
+    for (int r = 0; r < 6; r++) ee[r] = e[r];
+#pragma unroll
+    for (int r = 0; r < 8; r++) coef[r] = co[r];
+    d3 tv, bv;
+    se3_jlinv_apply5(ee, coef, jl, ja, tv, bv);
+    const double top[3] = {tv.x * wp, tv.y * wp, tv.z * wp}, bot[3] = {bv.x * wr, bv.y * wr, bv.z * wr};
     double cp = 0.0;
 #pragma unroll
     for (int r = 0; r < 3; r++) {
-      double top = M[3 * r] * jl.x + M[3 * r + 1] * jl.y + M[3 * r + 2] * jl.z + M[9 + 3 * r] * ja.x +
-                   M[9 + 3 * r + 1] * ja.y + M[9 + 3 * r + 2] * ja.z;
-      double bot = M[3 * r] * ja.x + M[3 * r + 1] * ja.y + M[3 * r + 2] * ja.z;
-      top *= wp; bot *= wr;
-      o[r] = top;
-      o[3 + r] = bot;
-      cp += top * we[r] + bot * we[3 + r];
+      o[r] = top[r];
+      o[3 + r] = bot[r];
+      cp += top[r] * we[r] + bot[r] * we[3 + r];
     }
     cpart[p] = cp;
   }
