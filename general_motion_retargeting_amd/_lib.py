@@ -144,6 +144,14 @@ _SIGS = {
     "gmr_motion_tracker_anchor_to_root_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "gmr_motion_tracker_anchor_to_root": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "gmr_motion_tracker_anchor_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gmr_motion_tracker_set_control": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int]),
+    "gmr_motion_tracker_targets_dev": (C.c_int, [C.c_void_p] * 7),
+    "gmr_motion_tracker_targets": (C.c_int, [C.c_void_p] * 6),
+    "gmr_motion_tracker_hold_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gmr_motion_tracker_hold": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "gmr_motion_tracker_torques_dev": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 8),
+    "gmr_motion_tracker_torques": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 7),
+    "gmr_motion_tracker_control_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "gmr_comm_create": (C.c_int, [C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),
     "gmr_comm_destroy": (C.c_int, [C.c_void_p]),
     "gmr_comm_rank": (C.c_int, [C.c_void_p]),
@@ -586,6 +594,16 @@ TRACKER_LINK_TERMS = 4
 TRACKER_FRAME_WORLD, TRACKER_FRAME_HEADING = 0, 1
 TRACKER_NO_ADVANCE = 1
 ANCHOR_YAW, ANCHOR_Z = 1, 2          # gmr_motion_tracker_anchor_to_root[_dev] flags (include/gmr_hip.h, "tracker anchors")
+
+
+CONTROL_MAX_DECIMATION = 64           # gmr_motion_tracker_set_control (include/gmr_hip.h, "tracker control")
+TRACKER_ACTUATOR_FIELDS = ("stiffness", "damping", "friction", "torque_limit")
+
+
+class TrackerActuator(C.Structure):
+    """``gmr_tracker_actuator_t``: the actuators of ``gmr_motion_tracker_torques[_dev]``, four addresses (``friction`` and ``torque_limit``
+    may be NULL) and whether the first three are ``[N][R]`` (1) or ``[R]`` (0)"""
+    _fields_ = [(k, C.c_void_p) for k in TRACKER_ACTUATOR_FIELDS] + [("per_env", C.c_int32)]
 
 
 # gmr_motion_tracker_set_preview: the block bits in row order, the frames and the limits (include/gmr_hip.h, "tracker preview")

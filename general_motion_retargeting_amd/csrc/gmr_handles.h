@@ -2,7 +2,7 @@
 // C-ABI): the FK tree (created in gmr_abi.hip) and the motion library (gmr_motion.hip), both read by gmr_body_state.hip, and
 // the motion tracker (gmr_tracker.hip), which is bound to a library and, with links attached (gmr_tracker_links.hip), to an FK tree;
 // gmr_tracker_preview.hip reads its state and tables, gmr_tracker_adaptive.hip owns its bins (adaptive sampling, masked resets),
-// gmr_tracker_anchor.hip its anchors.
+// gmr_tracker_anchor.hip its anchors, gmr_tracker_control.hip its control tables and the two arrays of the actuator model.
 #pragma once
 #include <stdint.h>
 
@@ -99,6 +99,15 @@ struct PreviewPlan {
   float offset[PREVIEW_MAX_OFFSETS] = {};   // seconds, finite
   int16_t body[PREVIEW_MAX_BODIES] = {};    // rows of the library's local_body_pos, distinct
 };
+// the control configuration of a tracker: validated on the host, travels as a kernel argument like TrackerTables
+struct ControlTables {
+  int32_t R = 0;                            // the robot dofs it was set for; 0: control was never set
+  int32_t M = 0;                            // decimation: physics substeps per environment step, 1 .. CONTROL_MAX_DECIMATION
+  float action_scale = 0.0f, clip = 0.0f;   // k, c (c may be inf)
+  float startup = 0.0f, gain_startup = 0.0f, gain_run = 0.0f;   // D seconds, g0, g1
+  float default_pos[TRACKER_MAX_DOF] = {};  // the robot's default pose, where the start-up easing begins (NOT TrackerTables::dof_default)
+};
+constexpr int CONTROL_MAX_DECIMATION = 64;
 }  // namespace gmr
 
 struct gmr_motion_tracker {
@@ -118,6 +127,10 @@ struct gmr_motion_tracker {
   gmr::DeviceBlock bin_block;    // every array of adaptive sampling: one allocation, made by set_adaptive
   double bin_seconds = 0.0;      // what the bins were built with
   gmr::DeviceBlock anchor_block; // S.anchor_pos / S.anchor_yaw: one allocation, made by gmr_motion_tracker_enable_anchors
+  gmr::ControlTables control;    // control.R = 0 until gmr_motion_tracker_set_control configures it
+  float* held = nullptr;         // [N][R] the targets the actuators hold (the reference's last_dof_targets); null until control is set
+  float* torque_acc = nullptr;   // [N][R] the running sum of the torques of an environment step
+  gmr::DeviceBlock control_block; // held and torque_acc: one allocation, made by gmr_motion_tracker_set_control
   std::vector<double> clip_w;    // the clip weights as given at creation (empty: uniform)
   std::mutex mu;                 // the tables, and the whole of every synchronous entry point
 };

@@ -11,7 +11,9 @@ one launch (``csrc/gmr_tracker_preview.hip``) that moves no clock.  :meth:`Motio
 launch and :meth:`MotionTracker.set_adaptive` draws episode starts where episodes recently failed (DESIGN.md section 6n,
 ``csrc/gmr_tracker_adaptive.hip``).  :meth:`MotionTracker.set_anchor` and :meth:`MotionTracker.anchor_to_root` place the reference of every
 environment in the simulator's world: a yaw and a translation per environment that every world-frame output goes through (DESIGN.md
-section 6o, ``csrc/gmr_tracker_anchor.hip``).
+section 6o, ``csrc/gmr_tracker_anchor.hip``).  :meth:`MotionTracker.targets` and :meth:`MotionTracker.torques` are the control half of the step
+(``csrc/gmr_tracker_control.hip``): the PD targets -- the reference's joint row eased in from the default pose, plus
+the clipped action -- in one launch, and the actuator model in one launch per physics substep.
 
 No GPU framework is imported here: :meth:`MotionTracker.step` takes and returns NumPy arrays, :meth:`MotionTracker.step_dev` reads
 and writes device memory the caller names -- ``_lib.DeviceBuffer``, a raw address, or anything with ``data_ptr()``.
@@ -38,6 +40,9 @@ PREVIEW_MAX_OFFSETS, PREVIEW_MAX_BODIES = 16, 32
 ADAPTIVE_MAX_BINS, ADAPTIVE_MAX_LOOKAHEAD = 1 << 22, 16
 # failure-driven start sampling: a choice of this library, the reference starts every motion at time 0
 DEFAULT_ADAPTIVE = {"bin_seconds": 1.0, "alpha": 0.1, "uniform": 0.3, "lookahead": 4, "gamma": 0.8}
+CONTROL_MAX_DECIMATION = 64
+# t1_imitation.py:388, :414: two seconds of start-up, the action gain during it and afterwards
+DEFAULT_CONTROL = {"startup_seconds": 2.0, "gain_startup": 0.1, "gain_run": 0.2}
 LINK_SIM = {"body_pos": (0, 3), "body_rot": (3, 4), "body_vel": (7, 3), "body_ang_vel": (10, 3)}      # offset and width in a packed row of 13
 
 
@@ -144,6 +149,7 @@ class MotionTracker:
         self._preview = None          # (K, blocks in row order, frame, nsel) once set_preview has configured one
         self._adaptive = None         # (bin_seconds, bin_start i64[C + 1]) once set_adaptive has built the bins
         self._anchors = False         # whether the per-environment anchors are enabled
+        self._control = None          # (R, decimation) once set_control has configured the control half
         if sc is not None or wt is not None:
             self.set_terms(sc, wt)
 
@@ -465,6 +471,213 @@ class MotionTracker:
             return None
         out = {"pos": np.empty((self.num_envs, 3), np.float32), "yaw_zw": np.empty((self.num_envs, 2), np.float32)}
         _lib.check(_lib.lib().gmr_motion_tracker_anchor_state(self.handle, _lib._ptr(out["pos"]), _lib._ptr(out["yaw_zw"])))
+        return out
+
+    # ---- control -------------------------------------------------------------------------------------
+    def _control_setup(self, default_dof_pos, action_scale, clip_actions, startup_seconds, gain_startup, gain_run, decimation):
+        """the checks of :meth:`set_control`, all of them before a device is touched -> ``(default f32[R], k, c, D, g0, g1, M)``"""
+        R = self.nrobot_dof
+        d = np.ascontiguousarray(default_dof_pos, dtype=np.float32).reshape(-1)
+        if len(d) != R:
+            raise ValueError(f"default_dof_pos has {len(d)} entries, the robot {R} dofs")
+        if not np.isfinite(d).all():
+            raise ValueError("default_dof_pos is not finite")
+        k, c, D, g0, g1 = (float(np.float32(x)) for x in (action_scale, clip_actions, startup_seconds, gain_startup, gain_run))
+        if not (np.isfinite(k) and np.isfinite(g0) and np.isfinite(g1)):
+            raise ValueError(f"action_scale = {k}, gain_startup = {g0} and gain_run = {g1} must be finite")
+        if not c > 0:
+            raise ValueError(f"clip_actions = {c}, must be positive (inf: no clipping)")
+        if not (np.isfinite(D) and D >= 0):
+            raise ValueError(f"startup_seconds = {D}, must be finite and not negative (0: no start-up phase)")
+        if int(decimation) != decimation or not 1 <= int(decimation) <= CONTROL_MAX_DECIMATION:
+            raise ValueError(f"decimation = {decimation} outside 1 to {CONTROL_MAX_DECIMATION} substeps")
+        return d, k, c, D, g0, g1, int(decimation)
+
+    def set_control(self, default_dof_pos, action_scale: float, clip_actions: float, startup_seconds: float = DEFAULT_CONTROL["startup_seconds"],
+                    gain_startup: float = DEFAULT_CONTROL["gain_startup"], gain_run: float = DEFAULT_CONTROL["gain_run"], *, decimation: int) -> None:
+        """Configures the control half: ``default_dof_pos [R]``, the robot's default joint angles from which :meth:`targets` eases in (a
+        table of its own, not the ``dof_default`` of the dof map), ``action_scale`` and ``clip_actions`` (``inf``: no clipping) of the
+        policy action, the ``startup_seconds`` of the easing (0: none) with the action gain during it and afterwards, and ``decimation``,
+        the physics substeps per step.  Allocates ``held`` and ``torque_acc`` (``[N, R]``, zeros).  Synchronous; call it again after
+        :meth:`set_dof_map` has changed the number of robot dofs."""
+        from . import _lib
+        d, k, c, D, g0, g1, M = self._control_setup(default_dof_pos, action_scale, clip_actions, startup_seconds, gain_startup, gain_run, decimation)
+        _lib.check(_lib.lib().gmr_motion_tracker_set_control(self.handle, _lib._ptr(d), k, c, D, g0, g1, M))
+        self._control = (self.nrobot_dof, M)
+
+    def _need_control(self, what: str):
+        ctl = getattr(self, "_control", None)
+        if ctl is None:
+            raise ValueError(f"{what}: control is not set on this tracker, call set_control() first")
+        if ctl[0] != self.nrobot_dof:
+            raise ValueError(f"{what}: control was set for {ctl[0]} robot dofs, the dof map now has {self.nrobot_dof}: call set_control() again")
+        return ctl
+
+    def _rows(self, a, what: str, n: Optional[int] = None):
+        """``a`` as ``f32[n, R]`` (n = num_envs by default), its shape checked"""
+        n = self.num_envs if n is None else n
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.shape != (n, self.nrobot_dof):
+            raise ValueError(f"{what}: shape {a.shape}, {(n, self.nrobot_dof)} needed")
+        return a
+
+    def _per_env_ints(self, a, what: str):
+        if a is None:
+            return None
+        a = np.asarray(a)
+        if not np.issubdtype(a.dtype, np.integer):
+            raise TypeError(f"{what}: integers needed, got {a.dtype}")
+        if a.shape != (self.num_envs,):
+            raise ValueError(f"{what}: shape {a.shape}, {(self.num_envs,)} needed")
+        return np.ascontiguousarray(a, dtype=np.int32)
+
+    def targets(self, actions=None, episode_steps=None) -> Dict[str, np.ndarray]:
+        """The PD targets of the next physics step, host arrays in and out: ``dof_targets [N,R]`` -- the reference's joint row at every
+        environment's present clock (what a following :meth:`step` returns as ``ref_dof_pos``, bit for bit), eased in from the default
+        pose with a cosine S-curve while ``episode_steps [N] * dt`` (the simulator's episode length counter; ``None``: no start-up) is
+        below ``startup_seconds``, plus ``action_scale * clip(actions) * gain`` --, ``status i32[N]`` (1: a bad assignment, its row is
+        NaN) and, with ``actions [N,R]``, ``actions_clipped``.  One launch; clocks, clips and draw counters stay as they are."""
+        from . import _lib
+        self._need_control("targets")
+        N, R = self.num_envs, self.nrobot_dof
+        a = None if actions is None else self._rows(actions, "actions")
+        st = self._per_env_ints(episode_steps, "episode_steps")
+        out = {"dof_targets": np.empty((N, R), np.float32), "status": np.empty(N, np.int32)}
+        if a is not None:
+            out["actions_clipped"] = np.empty((N, R), np.float32)
+        _lib.check(_lib.lib().gmr_motion_tracker_targets(self.handle, _lib._ptr(a), _lib._ptr(st), _lib._ptr(out["dof_targets"]),
+                                                         _lib._ptr(out.get("actions_clipped")), _lib._ptr(out["status"])))
+        return out
+
+    def targets_dev(self, actions=None, episode_steps=None, dof_targets=None, actions_clipped=None, status=None, stream=None) -> None:
+        """:meth:`targets` on device memory, asynchronous on ``stream``: ``actions f32[N*R]`` and ``episode_steps i32[N]`` (each may be
+        ``None``) in, whichever of ``dof_targets f32[N*R]``, ``actions_clipped f32[N*R]``, ``status i32[N]`` are wanted out."""
+        from . import _lib
+        self._need_control("targets_dev")
+        N, R = self.num_envs, self.nrobot_dof
+        if actions_clipped is not None and actions is None:
+            raise ValueError("targets_dev: actions_clipped needs actions")
+        ptrs = (_dev_ptr(actions, "actions", "float32", N * R), _dev_ptr(episode_steps, "episode_steps", "int32", N),
+                _dev_ptr(dof_targets, "dof_targets", "float32", N * R), _dev_ptr(actions_clipped, "actions_clipped", "float32", N * R),
+                _dev_ptr(status, "status", "int32", N))
+        _lib.check(_lib.lib().gmr_motion_tracker_targets_dev(self.handle, *ptrs, _lib._s(stream)))
+
+    def hold(self, dof_pos, mask=None, env_ids=None) -> int:
+        """After a reset: the actuators of every environment whose ``mask`` is set (``None``: all) hold ``dof_pos [n,R]`` and its running
+        torque sum is cleared.  Without ``env_ids`` the arrays cover every environment; with it (every environment at most once) they are
+        indexed by list position, as the masks of :meth:`reset_done` are.  Returns how many ids of masked entries lay outside
+        ``[0, num_envs)``."""
+        from . import _lib
+        self._need_control("hold")
+        ids, n = None, self.num_envs
+        if env_ids is not None:
+            ids = np.ascontiguousarray(env_ids, dtype=np.int32).reshape(-1)
+            n = len(ids)
+            if len(np.unique(ids)) != n:
+                raise ValueError("hold: env_ids names an environment twice")
+        q = self._rows(dof_pos, "dof_pos", n)
+        m = _mask(mask, "mask", n)
+        if n == 0:
+            return 0
+        ignored = C.c_int()
+        _lib.check(_lib.lib().gmr_motion_tracker_hold(self.handle, n, _lib._ptr(ids), _lib._ptr(m), _lib._ptr(q), C.byref(ignored)))
+        return int(ignored.value)
+
+    def hold_dev(self, dof_pos, mask=None, env_ids=None, n: Optional[int] = None, stream=None) -> None:
+        """:meth:`hold` on device memory, asynchronous on ``stream``: ONE launch.  ``dof_pos f32[n*R]``, ``mask i32[n]`` as a step leaves
+        it (``finished``) or as :meth:`reset_done_dev` takes it; with ``env_ids`` (``i32[n]``) ``n`` is mandatory."""
+        from . import _lib
+        self._need_control("hold_dev")
+        n = self._list_length("hold_dev", env_ids, n)
+        if dof_pos is None:
+            raise ValueError("hold_dev: dof_pos is needed")
+        ptrs = (_dev_ptr(env_ids, "env_ids", "int32", n), _dev_ptr(mask, "mask", "int32", n), _dev_ptr(dof_pos, "dof_pos", "float32", n * self.nrobot_dof))
+        _lib.check(_lib.lib().gmr_motion_tracker_hold_dev(self.handle, n, *ptrs, _lib._s(stream)))
+
+    def _check_substep(self, what: str, substep) -> int:
+        _, M = self._need_control(what)
+        if int(substep) != substep or not 0 <= int(substep) < M:
+            raise ValueError(f"{what}: substep = {substep} outside [0, {M})")
+        return int(substep)
+
+    def _actuator(self, what: str, stiffness, damping, friction, torque_limit, per_env):
+        """the actuator arrays of :meth:`torques` as float32, their shapes checked -> ``(per_env, kp, kd, fr or None, lim or None)``"""
+        N, R = self.num_envs, self.nrobot_dof
+        kp = np.ascontiguousarray(stiffness, dtype=np.float32)
+        if per_env is None:
+            per_env = kp.ndim == 2
+        shape = (N, R) if per_env else (R,)
+        out = [bool(per_env)]
+        for name, a in (("stiffness", kp), ("damping", damping), ("friction", friction)):
+            if a is None:
+                if name != "friction":
+                    raise ValueError(f"{what}: {name} is needed")
+                out.append(None)
+                continue
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.shape != shape:
+                raise ValueError(f"{what}: {name} has shape {a.shape}, {shape} needed (per_env = {bool(per_env)}: the three share one shape)")
+            out.append(a)
+        lim = None
+        if torque_limit is not None:
+            lim = np.ascontiguousarray(torque_limit, dtype=np.float32)
+            if lim.shape != (R,):
+                raise ValueError(f"{what}: torque_limit has shape {lim.shape}, {(R,)} needed")
+        return tuple(out) + (lim,)
+
+    def torques(self, substep: int, dof_targets, dof_pos, dof_vel, stiffness, damping, friction=None, torque_limit=None, delay_steps=None,
+                per_env: Optional[bool] = None) -> Dict[str, np.ndarray]:
+        """The actuator model of physics substep ``substep`` (0 to ``decimation - 1``), host arrays in and out: an environment whose
+        ``delay_steps [N]`` (``None``: 0) equals the substep takes ``dof_targets [N,R]`` into ``held``; ``tau = stiffness * (held -
+        dof_pos) - damping * dof_vel``, less ``min(friction, |tau|) * sign(tau)``, clipped to ``torque_limit [R]``.  ``stiffness``,
+        ``damping`` and ``friction`` are all ``[N,R]`` (``per_env``) or all ``[R]``; ``per_env=None`` reads it off ``stiffness``.  Returns
+        ``dof_torques [N,R]`` and, after the last substep, ``mean_torques``, the mean over the step's substeps.  One launch."""
+        from . import _lib
+        i = self._check_substep("torques", substep)
+        N, R = self.num_envs, self.nrobot_dof
+        tg, q, qd = self._rows(dof_targets, "dof_targets"), self._rows(dof_pos, "dof_pos"), self._rows(dof_vel, "dof_vel")
+        pe, kp, kd, fr, lim = self._actuator("torques", stiffness, damping, friction, torque_limit, per_env)
+        ds = self._per_env_ints(delay_steps, "delay_steps")
+        act = _lib.TrackerActuator(*[None if a is None else a.ctypes.data for a in (kp, kd, fr, lim)], 1 if pe else 0)
+        out = {"dof_torques": np.empty((N, R), np.float32)}
+        if i == self._control[1] - 1:
+            out["mean_torques"] = np.empty((N, R), np.float32)
+        _lib.check(_lib.lib().gmr_motion_tracker_torques(self.handle, i, _lib._ptr(tg), _lib._ptr(q), _lib._ptr(qd), C.byref(act), _lib._ptr(ds),
+                                                         _lib._ptr(out["dof_torques"]), _lib._ptr(out.get("mean_torques"))))
+        return out
+
+    def torques_dev(self, substep: int, dof_targets, dof_pos, dof_vel, stiffness, damping, dof_torques, friction=None, torque_limit=None,
+                    delay_steps=None, mean_torques=None, per_env: bool = True, stream=None) -> None:
+        """:meth:`torques` on device memory, asynchronous on ``stream``: ONE launch.  Every array is a ``_lib.DeviceBuffer``, a raw address
+        or an object with ``data_ptr()``; ``per_env`` says whether ``stiffness``, ``damping`` and ``friction`` hold ``N*R`` or ``R``
+        floats.  ``mean_torques`` is written by the last substep only."""
+        from . import _lib
+        i = self._check_substep("torques_dev", substep)
+        N, R = self.num_envs, self.nrobot_dof
+        for name, x in (("dof_targets", dof_targets), ("dof_pos", dof_pos), ("dof_vel", dof_vel), ("stiffness", stiffness), ("damping", damping),
+                        ("dof_torques", dof_torques)):
+            if x is None:
+                raise ValueError(f"torques_dev: {name} is needed")
+        g = N * R if per_env else R
+        act = _lib.TrackerActuator()
+        for name, x, count in (("stiffness", stiffness, g), ("damping", damping, g), ("friction", friction, g), ("torque_limit", torque_limit, R)):
+            p = _dev_ptr(x, name, "float32", count)
+            setattr(act, name, None if p is None else p.value)
+        act.per_env = 1 if per_env else 0
+        rows = [_dev_ptr(x, name, "float32", N * R) for name, x in (("dof_targets", dof_targets), ("dof_pos", dof_pos), ("dof_vel", dof_vel))]
+        p_delay, p_tau = _dev_ptr(delay_steps, "delay_steps", "int32", N), _dev_ptr(dof_torques, "dof_torques", "float32", N * R)
+        p_mean = _dev_ptr(mean_torques, "mean_torques", "float32", N * R)
+        _lib.check(_lib.lib().gmr_motion_tracker_torques_dev(self.handle, i, *rows, C.byref(act), p_delay, p_tau, p_mean, _lib._s(stream)))
+
+    def control_state(self) -> Optional[Dict[str, np.ndarray]]:
+        """``held f32[N,R]``, the targets the actuators hold, and ``torque_acc f32[N,R]``, the running torque sum of the current step, or
+        ``None`` when control is not set.  Synchronous."""
+        from . import _lib
+        if getattr(self, "_control", None) is None:
+            return None
+        self._need_control("control_state")
+        out = {"held": np.empty((self.num_envs, self.nrobot_dof), np.float32), "torque_acc": np.empty((self.num_envs, self.nrobot_dof), np.float32)}
+        _lib.check(_lib.lib().gmr_motion_tracker_control_state(self.handle, _lib._ptr(out["held"]), _lib._ptr(out["torque_acc"])))
         return out
 
     # ---- the step ---------------------------------------------------------------------------------------------------------

@@ -790,6 +790,71 @@ int gmr_motion_tracker_anchor_to_root(gmr_motion_tracker_t* t, int n, const int3
 /* the anchors on the host: pos f32[N][3], yaw_zw f32[N][2], each may be NULL; synchronises; GMR_ERR_ARG unless anchors are enabled */
 int gmr_motion_tracker_anchor_state(gmr_motion_tracker_t* t, float* pos, float* yaw_zw);
 
+/* ---- N9: tracker control (joint targets and the actuator model of a motion tracker) ---- */
+/* The control half of an imitation step: the PD targets of booster_gym/envs/t1_imitation.py:386-415 -- the reference's joint row at the
+ * environment's clock, eased in from the default pose over the first seconds of an episode, plus the clipped policy action as a
+ * residual -- in ONE launch, and the actuator model that runs `decimation` times per step between physics substeps (:449-462,
+ * t1.py:443-456) -- actuator delay, PD law, Coulomb friction, torque clip, running mean -- in ONE launch per substep.  The statement
+ * of record is tests/control_mirror.py; this is the same in words.  Everything is float32 with one rounding per operation.
+ * CONFIGURATION (a host assignment that travels with every launch): default_pos f32[R] d, action_scale k, clip_actions c,
+ * startup_seconds D, gain_startup g0, gain_run g1, decimation M.  STATE (device, owned by the tracker, zero after set_control):
+ * held f32[N][R], the targets the actuators hold (last_dof_targets), and torque_acc f32[N][R], the running sum of a step's torques.
+ * TARGETS, for environment e and robot dof j:
+ *   r       = what gmr_motion_tracker_step_dev would write to ref_dof_pos[e][j] at the environment's present (clip, clock): the same
+ *             code, the same bits; the clock does not move, no draw is made, no tracker state is written
+ *   te      = (float)episode_steps[e] * (float)dt; startup = te < D; p = min(max(te / D, 0), 1);
+ *   s       = 0.5 * (1 - cosf(p * 3.14159f))   (the reference's literal, :403); without episode_steps: startup = false
+ *   base    = startup ? d_j * (1 - s) + r * s : r
+ *   a       = min(max(action, -c), c), a NaN stays one (t1.py:439); target = base + (k * a) * (startup ? g0 : g1); without actions
+ *             target = base
+ *   a bad assignment (step 6 of the tracker): status[e] = 1 (else 0), the target row is NaN, nothing of the library is read;
+ *   actions_clipped is written all the same
+ * TORQUES of substep i, per element: if (delay_steps ? delay_steps[e] : 0) == i then held = dof_targets (a delay outside [0, M)
+ * never matches); tau = kp * (held - q) - kd * qd; with friction f = min(fr, |tau|) (a NaN propagates), tau = tau - f * sgn(tau),
+ * sgn = +1, -1 or +0; with a limit tau = min(max(tau, -lim), lim); dof_torques = tau; torque_acc = (i == 0 ? 0 : torque_acc) + tau;
+ * for i == M - 1 mean_torques = torque_acc / (float)M.
+ * The tracker stays SINGLE-STREAM: targets reads its state, hold and torques write held / torque_acc.  Every call below is
+ * GMR_ERR_ARG, before a device is touched, on a tracker whose control was never set, or whose dof map has changed R since. */
+#define GMR_CONTROL_MAX_DECIMATION 64
+typedef struct {            /* the actuators of a torques call: device pointers (gmr_motion_tracker_torques: host pointers) of the user */
+  const float *stiffness, *damping;   /* kp, kd: [N][R] with per_env = 1, [R] with per_env = 0                         */
+  const float *friction;              /* fr, shaped as the gains; NULL: no friction                                   */
+  const float *torque_limit;          /* lim [R]; NULL: no clip                                                       */
+  int32_t per_env;
+} gmr_tracker_actuator_t;
+/* HOST array default_dof_pos f32[R] finite (t1.py:264-272; R is the tracker's), action_scale and the gains finite, clip_actions > 0
+ * (inf: no clipping), startup_seconds >= 0 and finite (0: no start-up phase; the reference's 2.0 at :388, gains 0.1 / 0.2 at :414),
+ * 1 <= decimation <= GMR_CONTROL_MAX_DECIMATION.  Allocates held and torque_acc and fills them with zeros (the reference's
+ * last_dof_targets and torques start as zeros); synchronises the device.  Launches in flight keep the configuration they carry. */
+int gmr_motion_tracker_set_control(gmr_motion_tracker_t* t, const float* default_dof_pos, float action_scale, float clip_actions,
+                                   float startup_seconds, float gain_startup, float gain_run, int decimation);
+/* The joint targets (t1_imitation.py:386-415 with the clip of t1.py:439), ONE launch: actions f32[N][R] or NULL, episode_steps
+ * i32[N] or NULL (the simulator's episode_length_buf; it stays the environment's); outputs dof_targets f32[N][R], actions_clipped
+ * f32[N][R] (needs actions), status i32[N], each may be NULL. */
+int gmr_motion_tracker_targets_dev(gmr_motion_tracker_t* t, const float* d_actions, const int32_t* d_episode_steps, float* d_dof_targets,
+                                   float* d_actions_clipped, int32_t* d_status, void* stream);      /* asynchronous */
+int gmr_motion_tracker_targets(gmr_motion_tracker_t* t, const float* actions, const int32_t* episode_steps, float* dof_targets,
+                               float* actions_clipped, int32_t* status);
+/* last_dof_targets[env_ids] = dof_pos[env_ids] after a reset (t1.py:309), ONE launch: entry i -- environment env_ids[i], or i with
+ * env_ids = NULL (n = N), the convention of reset_done and anchor_to_root -- whose mask i32[n] is not zero (NULL: every entry) gets
+ * held[e][:] = dof_pos[i][:] and torque_acc[e][:] = 0.  Ids of such entries outside [0, N) are dropped and counted.  Every
+ * environment at most once in a list. */
+int gmr_motion_tracker_hold_dev(gmr_motion_tracker_t* t, int n, const int32_t* d_env_ids, const int32_t* d_mask, const float* d_dof_pos,
+                                void* stream);                                                      /* asynchronous */
+int gmr_motion_tracker_hold(gmr_motion_tracker_t* t, int n, const int32_t* env_ids, const int32_t* mask, const float* dof_pos,
+                            int* ignored /* ids of this call outside [0, N), or NULL */);
+/* The actuator model of physics substep i (t1_imitation.py:449-462, t1.py:443-456), ONE launch: dof_targets, dof_pos, dof_vel
+ * f32[N][R], delay_steps i32[N] or NULL (no delay); writes dof_torques f32[N][R] and, when given and i = M - 1, mean_torques
+ * f32[N][R].  0 <= substep < M, else GMR_ERR_ARG and no launch. */
+int gmr_motion_tracker_torques_dev(gmr_motion_tracker_t* t, int substep, const float* d_dof_targets, const float* d_dof_pos,
+                                   const float* d_dof_vel, const gmr_tracker_actuator_t* act, const int32_t* d_delay_steps,
+                                   float* d_dof_torques, float* d_mean_torques, void* stream);      /* asynchronous */
+int gmr_motion_tracker_torques(gmr_motion_tracker_t* t, int substep, const float* dof_targets, const float* dof_pos, const float* dof_vel,
+                               const gmr_tracker_actuator_t* act, const int32_t* delay_steps, float* dof_torques, float* mean_torques);
+/* held and torque_acc on the host (last_dof_targets, t1.py:309; the sum behind torques, t1.py:449-456): f32[N][R] each, either may
+ * be NULL; synchronises */
+int gmr_motion_tracker_control_state(gmr_motion_tracker_t* t, float* held, float* torque_acc);
+
 /* ---- multi-GPU: one rank per GPU, ONE broadcast, no per-step collective ------------ */
 /* The reference parallelises over files with mp.Pool on one CPU (scripts/smplx_to_robot_dataset.py:241-242); here
  * streams shard over the ranks of one node and the only data that crosses ranks is the packed robot model + task set.
