@@ -101,6 +101,21 @@ def build_jlinv_probe(force: bool = False) -> dict:
     return _build_probe_libs(JLINV_PROBE_SRC, JLINV_PROBE_LIBS, force)
 
 
+# The probe of the split evaluation (tests/hip/split_eval_probe.hip, tests/test_split_eval.py): the split forms of se3_log_rel5 /
+# se3_jlinv_coef5 and the latency kernel's two walks, under the library's own flags.
+SPLIT_PROBE_SRC = os.path.join(os.path.dirname(PROBE_SRC), "split_eval_probe.hip")
+SPLIT_PROBE_LIB = os.path.join(os.path.dirname(PROBE_SRC), "libgmr_split_eval_probe.so")
+
+
+def build_split_probe(force: bool = False) -> str:
+    deps = [SPLIT_PROBE_SRC, os.path.abspath(__file__)] + [os.path.join(CSRC, h) for h in ["gmr_ik.hip"] + HEADERS]
+    out = SPLIT_PROBE_LIB
+    if force or not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
+        subprocess.check_call([_hipcc()] + FLAGS + ["-shared", "-o", out + ".tmp", SPLIT_PROBE_SRC])
+        os.replace(out + ".tmp", out)
+    return out
+
+
 def build_variant(name: str, defines=(), verbose: bool = False) -> str:
     """libgmrhip_<name>.so with extra -D flags on every source (objects cached per flag set)."""
     out = os.path.join(HERE, f"libgmrhip_{name}.so")

@@ -412,6 +412,58 @@ __device__ __forceinline__ void se3_jlinv_coef5(const double e[6], const double 
   coef[7] = 0.5 * rho.z - k1 * w.z - c2 * m.z;
 }
 
+// ---- split forms: what depends on the body ROTATIONS alone, and the rest ------------------------------------------
+// The latency kernel evaluates the rotation half while another wavefront is still walking the positions of the tree.
+// se3_log_rel5 cut in two: the same expressions in the same order (same switches), so the results are the original's
+// bit for bit (tests/test_split_eval.py).
+
+// rotation half of se3_log_rel5: w = log(conj(qb) qt) and the whole of aux
+__device__ __forceinline__ void se3_log_rel5_rot(d4 qb, d4 qt, double w3[3], double aux[5]) {
+  const d4 q = qmul(qconj(qb), qt);
+  const double n2 = q.x * q.x + q.y * q.y + q.z * q.z;
+  const double cw = fabs(q.w);
+  double f, sh = 0.0, ch = 1.0, inv_sh = 0.0, half = 0.0;
+  if (n2 < 1e-10) {
+    f = 2.0 / q.w - 2.0 / 3.0 * n2 / (q.w * q.w * q.w);
+  } else {
+    const double inv_n = fast_rsqrt(n2);
+    sh = n2 * inv_n; ch = cw; inv_sh = inv_n;
+    half = atan2_q1(sh, ch);
+    bool neg = q.w < 0.0;
+    if (cw < 1e-10) {
+      half = 1.57079632679489661923; sh = 1.0; ch = 6.123233995736766e-17; inv_sh = 1.0;
+      neg = !(q.w > 0.0);
+    }
+    f = 2.0 * half * inv_n;
+    if (neg) f = -f;
+  }
+  const d3 w = {f * q.x, f * q.y, f * q.z};
+  const double t2 = dot(w, w);
+  double a;
+  if (t2 < 1e-2) {
+    aux[1] = 0.0; aux[2] = 1.0; aux[3] = 0.0; aux[4] = 0.0;
+    a = 1.0 / 12.0 + t2 * (1.0 / 720.0 + t2 * (1.0 / 30240.0 + t2 * (1.0 / 1209600.0 + t2 / 47900160.0)));
+  } else {
+    const double t = 2.0 * half, inv_t = fast_rcp(t);
+    aux[1] = 2.0 * sh * ch;
+    aux[2] = 1.0 - 2.0 * sh * sh;
+    aux[3] = t; aux[4] = inv_t;
+    a = (sh - half * ch) * inv_sh * (inv_t * inv_t);
+  }
+  aux[0] = a;
+  w3[0] = w.x; w3[1] = w.y; w3[2] = w.z;
+}
+
+// position half of se3_log_rel5: V^-1(w) p_bt from w and a = aux[0] of the rotation half
+__device__ __forceinline__ void se3_log_rel5_pos(d3 pb, d4 qb, d3 pt, const double w3[3], double a, double v3[3]) {
+  const d3 pbt = qrot_inv(qb, pt - pb);
+  const d3 w = {w3[0], w3[1], w3[2]};
+  const d3 wp = cross(w, pbt);
+  const d3 wwp = cross(w, wp);
+  const d3 v = pbt - 0.5 * wp + a * wwp;
+  v3[0] = v.x; v3[1] = v.y; v3[2] = v.z;
+}
+
 // A x = hw x x + (a (w . x)) w + da x
 __device__ __forceinline__ d3 jlinv_op_a(d3 w, d3 hw, double a, double da, d3 x) {
   const double aw = a * dot(w, x);

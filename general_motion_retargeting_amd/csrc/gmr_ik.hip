@@ -34,9 +34,11 @@
 //               Box constraints: block principal pivoting (all violated bounds / multipliers are exchanged at
 //               once, Murty's single exchange as the finite-termination fallback), warm-started from the
 //               previous solve's active set.
-//   NW = 4      the helpers (i) turn each new FK state into the body Jacobians while the main wavefront
-//               evaluates residuals and the Jl^-1 coefficients, (ii) share the weighted Jacobian columns, (iii) assemble H while
-//               the main wavefront gathers c and the bounds, (iv) eliminate one limb each in the QP.
+//   NW = 4      after a solve helper 1 walks the tree (positions and rotations) while the main wavefront walks the rotations
+//               alone and takes the residuals' logarithms; the helpers (i) turn each new FK state into the body Jacobians while
+//               the main wavefront evaluates (the position half of) the residuals and the Jl^-1 coefficients, (ii) share the
+//               weighted Jacobian columns, (iii) assemble H while the main wavefront gathers c and the bounds, (iv) eliminate
+//               one limb each in the QP.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -63,7 +65,9 @@ __device__ __forceinline__ void wsync() {
 #define GMR_IK_MIN_WAVES 1
 #endif
 enum { QP_DENSE = 0, QP_TREE_SMALL = 1, QP_TREE = 2 };   // solver carried by a kernel instance
-enum { CMD_BUILD = 1, CMD_EXIT = 2, CMD_JBODY = 3 };   // BUILD: assemble the QP, then solve it together; JBODY: body Jacobians
+// BUILD: assemble the QP, then solve it together; JBODY: body Jacobians; FK: helper 1 walks the tree (positions and
+// rotations), all meet at a second barrier, then body Jacobians
+enum { CMD_BUILD = 1, CMD_EXIT = 2, CMD_JBODY = 3, CMD_FK = 4 };
 
 // value of lane `src` (wave-uniform index) as a scalar operand
 __device__ __forceinline__ double readlane_d(double v, int src) {
@@ -116,7 +120,9 @@ __device__ __forceinline__ FkLane fk_lane(const LT& L, const double* sm, const s
   return F;
 }
 
-template <int NW, class LT>
+// NORM: normalise the base quaternion and store it back to q (false: integrate_wave<NW, true> has done so, and nobody
+// may write q: the main wavefront's rotation walk reads it at the same time)
+template <int NW, bool NORM = true, class LT>
 __device__ __forceinline__ void fk_wave(const LT& L, double* sm, const FkLane& F, int lane, Prof& pr) {
   lane = fresh_lane(lane);
   PROF_BEGIN(pr);
@@ -128,8 +134,11 @@ __device__ __forceinline__ void fk_wave(const LT& L, double* sm, const FkLane& F
   // round 0 input: transform of every body relative to its parent (body 0: world pose)
   if (lane < nb) {
     if (lane == 0) {
-      quat = qnormalize(d4{q[3], q[4], q[5], q[6]});
-      q[3] = quat.w; q[4] = quat.x; q[5] = quat.y; q[6] = quat.z;
+      quat = d4{q[3], q[4], q[5], q[6]};
+      if (NORM) {
+        quat = qnormalize(quat);
+        q[3] = quat.w; q[4] = quat.x; q[5] = quat.y; q[6] = quat.z;
+      }
       pos = d3{q[0], q[1], q[2]};
     } else {
       quat = F.bq;
@@ -204,6 +213,100 @@ __device__ __forceinline__ double errors_wave(const LT& L, double* sm, const sho
   return sqrt(ss);
 }
 
+// ---------------------------------------------------------------------------------------------
+// 4-wavefront shape, evaluation after a solve, split over two wavefronts.  The body rotations do not depend on any
+// position (quat = qmul(qa, quat) in fk_wave), and neither does the rotation half of a residual.  So while helper 1 walks
+// the whole tree (fk_wave<NW, false>), the main wavefront walks the rotations alone and takes the logarithms
+// (rot_half_wave); after one barrier it adds the position half from the helper's xa (pos_half_wave).  The two sides are
+// about as long; the Jl^-1 coefficients stay behind the barrier, whole.  Same expressions, same order as
+// fk_wave + errors_wave: the same bits.
+// ---------------------------------------------------------------------------------------------
+struct RotHalf { d4 qb; double w[3], a; };     // a task lane's rotation half, handed to its position half in registers
+
+// the walk of fk_wave<NW, false> on the rotations alone: body `lane`'s world quaternion, the bits of its xa[3..6]
+template <class LT>
+__device__ __forceinline__ d4 qwalk_wave(const LT& L, const double* sm, const FkLane& F, int lane) {
+  const int nb = L.nb;
+  const double* q = sm + L.o.q;
+  d4 quat = {1, 0, 0, 0};
+  const int dep = F.dep;
+  if (lane < nb) {
+    if (lane == 0) {
+      quat = d4{q[3], q[4], q[5], q[6]};      // normalised by integrate_wave<NW, true>
+    } else {
+      quat = F.bq;
+      if (F.hinge >= 0) {
+        const double* sc = sm + L.o.hsc + 2 * F.hinge;
+        const double s = sc[0], c = sc[1];
+        quat = qmul(quat, d4{c, F.ax.x * s, F.ax.y * s, F.ax.z * s});
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < IK_MAX_HOPS; r++) {     // the rounds of fk_wave on the rotations alone: 4 permuted doubles instead of 7
+    if (r >= L.nhop) break;
+    const int src = F.src[r];
+    const d4 qa = {bpermute_d(src, quat.w), bpermute_d(src, quat.x), bpermute_d(src, quat.y), bpermute_d(src, quat.z)};
+    __builtin_amdgcn_s_waitcnt(0xc07f);        // one wait per round (see fk_wave)
+    if (lane < nb && dep >= (1 << r)) quat = qmul(qa, quat);
+  }
+  if (lane < nb) quat = qnormalize(quat);
+  return quat;
+}
+
+template <class LT>
+__device__ __forceinline__ RotHalf rot_half_wave(const LT& L, double* sm, const FkLane& F, int tq, int th, int K, int lane, Prof& pr) {
+  // tq: byte address (ds_bpermute) of the lane of this task's body; th: offset of its target in tgt.  Both 0 for lane >= K.
+  lane = fresh_lane(lane);
+  PROF_BEGIN(pr);
+  const d4 quat = qwalk_wave(L, sm, F, lane);
+  RotHalf R;
+  R.qb = d4{bpermute_d(tq, quat.w), bpermute_d(tq, quat.x), bpermute_d(tq, quat.y), bpermute_d(tq, quat.z)};
+  R.w[0] = R.w[1] = R.w[2] = 0.0; R.a = 0.0;
+  PROF_END(pr, PH_QWALK);
+  PROF_BEGIN(pr);
+  if (lane < K) {
+    const double* tg = sm + L.o.tgt + th;
+    double aux[5];
+    se3_log_rel5_rot(R.qb, d4{tg[3], tg[4], tg[5], tg[6]}, R.w, aux);
+    R.a = aux[0];
+    double* eo = sm + L.o.e + 6 * lane;
+#pragma unroll
+    for (int r = 0; r < 3; r++) eo[3 + r] = R.w[r];
+    double* ao = sm + L.o.eaux + 5 * lane;
+#pragma unroll
+    for (int r = 0; r < 5; r++) ao[r] = aux[r];
+  }
+  PROF_END(pr, PH_ROT);
+  return R;
+}
+
+// after the barrier behind helper 1's walk: e[0..2] and the residual norm E (in every lane)
+template <class LT>
+__device__ __forceinline__ double pos_half_wave(const LT& L, double* sm, const RotHalf& R, int tq, int th, int K, int lane, Prof& pr) {
+  lane = fresh_lane(lane);
+  PROF_BEGIN(pr);
+  double ss = 0.0;
+  if (lane < K) {
+    const double* x = sm + L.o.xa + 7 * (tq >> 2);
+    const double* tg = sm + L.o.tgt + th;
+    double v[3];
+    se3_log_rel5_pos(d3{x[0], x[1], x[2]}, R.qb, d3{tg[0], tg[1], tg[2]}, R.w, R.a, v);
+    double* eo = sm + L.o.e + 6 * lane;
+#pragma unroll
+    for (int r = 0; r < 3; r++) { eo[r] = v[r]; ss += v[r] * v[r]; }
+#pragma unroll
+    for (int r = 0; r < 3; r++) ss += R.w[r] * R.w[r];
+  }
+  ss = row0_sum(ss);
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+  PROF_END(pr, PH_POS);
+  return sqrt(ss);
+}
+
+#ifdef GMR_IK_WALKS_ONLY    // tests/hip/split_eval_probe.hip compiles the file up to here: the walks, not the kernel
+}  // namespace gmr
+#else
 // ---------------------------------------------------------------------------------------------
 // QP assembly (mink compute_qp_objective + ConfigurationLimit; App. A.4-A.6), in four phases so
 // that helper waves can share the two wide ones (Jacobian columns, H entries)
@@ -590,6 +693,8 @@ __device__ __forceinline__ void helper_loop(const LT& L, double* sm, const uint3
   int pk[2];                              // task of this lane's (task, dof) pair in either table
 #pragma unroll
   for (int st = 0; st < 2; st++) pk[st] = (unsigned short)(si + L.o.i_pair_task[st])[min(wave * 64 + lane, L.o.cap.p - 1)] & 15u;
+  // helper 1 walks the tree after every solve (CMD_FK): its body lane's constants, read once per launch
+  const FkLane fkc = fk_lane(L, sm, si + L.o.i_hop, si + L.o.i_depth, si + L.o.i_body_hinge, lane);
   for (int epoch = 0;; epoch++) {         // command n sits in mailbox slot n & 1 (see the main wavefront)
     PROF_BEGIN(hp);
     __syncthreads();                      // B1 (or the EXIT barrier)
@@ -600,6 +705,16 @@ __device__ __forceinline__ void helper_loop(const LT& L, double* sm, const uint3
     StageTabs tb = {si + L.o.i_task_body[stage], si + L.o.i_task_human[stage], si + L.o.i_pair_task[stage],
                     si + L.o.i_pair_dof[stage], si + L.o.i_pair_index[stage],
                     reinterpret_cast<const uint2*>(sw + L.w_items[stage])};
+    if (cmd == CMD_FK) {                  // the main wavefront walks the rotations and evaluates what needs them alone
+      if (wave == 1) fk_wave<NW, false>(L, sm, fkc, lane, hp);
+      PROF_BEGIN(hp);
+      __syncthreads();                    // K2: xa and xaxis are final, and so are the main wavefront's rotation halves
+      PROF_END(hp, PH_ERR);               // wait at K2
+      PROF_BEGIN(hp);
+      jbody_phase(L, sm, stage, tb, (wave - 1) * 64 + lane, 64 * (NW - 1));
+      PROF_END(hp, PH_PAIRS);
+      continue;
+    }
     if (cmd == CMD_JBODY) {               // the main wavefront is evaluating the residuals meanwhile
       PROF_BEGIN(hp);
       jbody_phase(L, sm, stage, tb, (wave - 1) * 64 + lane, 64 * (NW - 1));
@@ -790,7 +905,9 @@ __device__ __forceinline__ void hinge_sincos(const LT& L, double* sm, int lane) 
 
 // mj_integratePos with v = dq/dt (App. A.7): lane 0 the free joint, lane 6+h hinge h
 // ---------------------------------------------------------------------------------------------
-template <int NW, class LT>
+// NORM: also the normalisation of the base quaternion that otherwise opens fk_wave (the same operations on the same
+// values, before the store instead of after a reload)
+template <int NW, bool NORM = false, class LT>
 __device__ __forceinline__ void integrate_wave(const LT& L, double* sm, double dt, int lane, Prof& pr) {
   lane = fresh_lane(lane);
   PROF_BEGIN(pr);
@@ -817,6 +934,7 @@ __device__ __forceinline__ void integrate_wave(const LT& L, double* sm, double d
   if (base) {
     d4 quat = qnormalize(d4{q[3], q[4], q[5], q[6]});
     if (rotate) quat = qmul(quat, d4{c, dq[3] * inv * s, dq[4] * inv * s, dq[5] * inv * s});
+    if (NORM) quat = qnormalize(quat);
     q[3] = quat.w; q[4] = quat.x; q[5] = quat.y; q[6] = quat.z;
   } else if (hinge) {
     double* sc = sm + L.o.hsc + 2 * (lane - 6);
@@ -935,6 +1053,13 @@ __global__ __launch_bounds__(64 * NW, GMR_IK_MIN_WAVES) void ik_streams_kernel(c
   int pk_main[2];                         // task of this lane's (task, dof) pair in either table (column phase)
 #pragma unroll
   for (int st = 0; st < 2; st++) pk_main[st] = (unsigned short)(si + L.o.i_pair_task[st])[lane] & 15u;
+  int tq_main[2], th_main[2];             // this task lane's body lane (ds_bpermute address) and target offset, per table
+#pragma unroll
+  for (int st = 0; st < 2; st++) {
+    const bool on = NW > 1 && lane < L.K[st];
+    tq_main[st] = on ? 4 * (si + L.o.i_task_body[st])[lane] : 0;
+    th_main[st] = on ? 7 * (si + L.o.i_task_human[st])[lane] : 0;
+  }
   fk_wave<NW>(L, sm, fkc, lane, pr);
 
   const int Ts = len ? min(len[s], T) : T;
@@ -1014,14 +1139,22 @@ __global__ __launch_bounds__(64 * NW, GMR_IK_MIN_WAVES) void ik_streams_kernel(c
             rc = solve_qp_regs<NVP, NW>(L, sm, lane, qp_state, pr);
           }
           if (rc != GMR_STATUS_OK) { stat = rc; break; }
-          integrate_wave<NW>(L, sm, prm[5], lane, pr);
-          fk_wave<NW>(L, sm, fkc, lane, pr);
+          double next;
           if (NW > 1) {
-            if (lane == 0) { int* c = ctl + 2 * (epoch & 1); c[0] = CMD_JBODY; c[1] = stage; }
+            integrate_wave<NW, true>(L, sm, prm[5], lane, pr);     // q is final: nobody writes it until the next solve
+            if (lane == 0) { int* c = ctl + 2 * (epoch & 1); c[0] = CMD_FK; c[1] = stage; }
             epoch++;
-            __syncthreads();
+            __syncthreads();                    // K1: helper 1 walks positions and rotations
+            const RotHalf rh = rot_half_wave(L, sm, fkc, tq_main[stage], th_main[stage], K, lane, pr);
+            PROF_BEGIN(pr);
+            __syncthreads();                    // K2: xa is final; the helpers go on to the body Jacobians
+            PROF_END(pr, PH_K2);
+            next = pos_half_wave(L, sm, rh, tq_main[stage], th_main[stage], K, lane, pr);
+          } else {
+            integrate_wave<NW>(L, sm, prm[5], lane, pr);
+            fk_wave<NW>(L, sm, fkc, lane, pr);
+            next = errors_wave<NW>(L, sm, tb.task_body, tb.task_human, K, lane, pr);
           }
-          double next = errors_wave<NW>(L, sm, tb.task_body, tb.task_human, K, lane, pr);
           last_E = next;
           nsol++;
           if (nsol > 1) num_iter++;
@@ -1122,3 +1255,4 @@ extern "C" hipError_t gmr_ik_set_max_smem(int nvp, int nw, int tree_small, int b
   }
   return hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
+#endif  // GMR_IK_WALKS_ONLY

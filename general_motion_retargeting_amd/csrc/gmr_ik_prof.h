@@ -6,7 +6,12 @@
 namespace gmr {
 
 enum { PH_PRE, PH_FK, PH_ERR, PH_JLOG, PH_PAIRS, PH_CVEC, PH_HACC, PH_KBUILD, PH_CHOL, PH_SUBST, PH_RATIO,
-       PH_MULT, PH_INTEG, PH_IO, PH_NFACT, PH_NSOLVE, PH_TICKS, PH_REALTIME, PH_COUNT };
+       PH_MULT, PH_INTEG, PH_IO,
+       // latency kernel, split evaluation after a solve (main wavefront): rotation walk, rotation halves of residuals and
+       // series, wait at the barrier behind helper 1's walk, position halves
+       PH_QWALK, PH_ROT, PH_K2, PH_POS,
+       PH_NFACT, PH_NSOLVE, PH_TICKS, PH_REALTIME, PH_COUNT };
+enum { PH_NTIME = PH_NFACT };   // the stamped phases come first, then the counters
 #ifdef GMR_IK_PROFILE
 struct Prof {
   unsigned long long acc[PH_COUNT];

@@ -19,8 +19,15 @@ from general_motion_retargeting_amd import _lib, params, synth  # noqa: E402
 from general_motion_retargeting_amd.ik_config import build_task_tables, pack_model, pack_taskset  # noqa: E402
 from general_motion_retargeting_amd.models import load_ik_config, load_robot  # noqa: E402
 
+# csrc/gmr_ik_prof.h.  QWALK, ROT, K2, POS: the latency kernel's split evaluation after a solve (main wavefront): rotation
+# walk, rotation halves of residuals and series, wait at the barrier behind helper 1's walk, position halves.
 PH = ["PRE", "FK", "ERR", "JLOG", "PAIRS", "CVEC", "HACC", "KBUILD", "CHOL", "SUBST", "RATIO", "MULT", "INTEG", "IO",
-      "NFACT", "NSOLVE", "TICKS", "REALTIME"]
+      "QWALK", "ROT", "K2", "POS", "NFACT", "NSOLVE", "TICKS", "REALTIME"]
+# a library from before the split has no QWALK .. POS (GMR_PROF_LEGACY=1: A/B against such a build)
+if os.environ.get("GMR_PROF_LEGACY"):
+    PH = [n for n in PH if n not in ("QWALK", "ROT", "K2", "POS")]
+NT = PH.index("NFACT")          # the stamped phases come first, then the counters
+NFACT, NSOLVE, TICKS, REALTIME = (PH.index(n) for n in ("NFACT", "NSOLVE", "TICKS", "REALTIME"))
 
 
 def main():
@@ -52,31 +59,37 @@ def main():
     _lib.check(L.gmr_stream_sync(None))
     both = d_pr.to_host((2, S, len(PH)), np.uint64).astype(np.float64)
     pr, hp = both[0], both[1]
-    tot = pr[:, :14].sum(axis=1).mean()
-    nsolve = pr[:, 15].mean()
-    nfact = pr[:, 14].mean()
+    tot = pr[:, :NT].sum(axis=1).mean()
+    nsolve = pr[:, NSOLVE].mean()
+    nfact = pr[:, NFACT].mean()
     print(f"S={S} T={T}  solves/stream={nsolve:.0f}  rounds/solve={nfact / nsolve:.3f}  "
           f"stamped cycles/solve={tot / nsolve:.0f} (100 MHz ticks if s_memtime is the constant clock)")
-    clk = pr[:, 16].mean() / pr[:, 17].mean() * 100.0
-    print(f"  kernel ticks/stream={pr[:, 16].mean():.3e}  realtime(100MHz)={pr[:, 17].mean():.3e}  => in-kernel clock {clk:.0f} MHz; "
-          f"stream wall {pr[:, 17].mean() / 100.0:.0f} us")
-    rt = pr[:, 17] / 100.0
+    clk = pr[:, TICKS].mean() / pr[:, REALTIME].mean() * 100.0
+    print(f"  kernel ticks/stream={pr[:, TICKS].mean():.3e}  realtime(100MHz)={pr[:, REALTIME].mean():.3e}  => in-kernel clock {clk:.0f} MHz; "
+          f"stream wall {pr[:, REALTIME].mean() / 100.0:.0f} us")
+    rt = pr[:, REALTIME] / 100.0
     print("  per-stream wall us: min %.0f median %.0f max %.0f ; rounds/solve per stream: min %.3f max %.3f" % (
-        rt.min(), np.median(rt), rt.max(), (pr[:, 14] / pr[:, 15]).min(), (pr[:, 14] / pr[:, 15]).max()))
-    for i, n in enumerate(PH[:14]):
+        rt.min(), np.median(rt), rt.max(), (pr[:, NFACT] / pr[:, NSOLVE]).min(), (pr[:, NFACT] / pr[:, NSOLVE]).max()))
+    for i, n in enumerate(PH[:NT]):
         print(f"  {n:7s} {pr[:, i].mean() / tot * 100:6.2f} %   {pr[:, i].mean() / nsolve:10.0f} /solve")
     if S <= 512:     # latency shape: the batch's time is its slowest stream's -- the same breakdown for that stream alone
-        k = int(np.argmax(pr[:, 17]))
-        med = int(np.argsort(pr[:, 17])[S // 2])
+        k = int(np.argmax(pr[:, REALTIME]))
+        med = int(np.argsort(pr[:, REALTIME])[S // 2])
         for name, i in (("slowest", k), ("median", med)):
-            ns_i, tot_i = pr[i, 15], pr[i, :14].sum()
-            print(f"  {name} stream {i}: wall {pr[i, 17] / 100.0:.0f} us, {ns_i:.0f} solves, {pr[i, 14] / ns_i:.3f} rounds/solve, "
+            ns_i, tot_i = pr[i, NSOLVE], pr[i, :NT].sum()
+            print(f"  {name} stream {i}: wall {pr[i, REALTIME] / 100.0:.0f} us, {ns_i:.0f} solves, {pr[i, NFACT] / ns_i:.3f} rounds/solve, "
                   f"{tot_i / ns_i:.0f} stamped cycles/solve: " +
-                  " ".join(f"{n}={pr[i, j] / ns_i:.0f}" for j, n in enumerate(PH[:14])))
+                  " ".join(f"{n}={pr[i, j] / ns_i:.0f}" for j, n in enumerate(PH[:NT])))
     if hp.sum() > 0:
-        print("  helper wavefront 1 (cycles/solve): idle at B1 %.0f, Jacobian share %.0f, wait B2 %.0f, H share %.0f, wait B3 %.0f, tree-QP %.0f" % (
-            hp[:, 0].mean() / nsolve, hp[:, 4].mean() / nsolve, hp[:, 5].mean() / nsolve, hp[:, 6].mean() / nsolve,
-            hp[:, 3].mean() / nsolve, hp[:, 7:14].sum(axis=1).mean() / nsolve))
+        print("  helper wavefront 1 (cycles/solve): idle at B1 %.0f, FK walk %.0f, wait K2 %.0f, Jacobian share %.0f, wait B2 %.0f, "
+              "H share %.0f, wait B3 %.0f, tree-QP %.0f" % (
+            hp[:, 0].mean() / nsolve, hp[:, 1].mean() / nsolve, hp[:, 2].mean() / nsolve, hp[:, 4].mean() / nsolve,
+            hp[:, 5].mean() / nsolve, hp[:, 6].mean() / nsolve, hp[:, 3].mean() / nsolve, hp[:, 7:14].sum(axis=1).mean() / nsolve))
+        if S <= 512:
+            for name, i in (("slowest", k), ("median", med)):
+                ns_i = pr[i, NSOLVE]
+                print(f"  helper wavefront 1 of the {name} stream {i} (cycles/solve): idle at B1 {hp[i, 0] / ns_i:.0f}, "
+                      f"FK walk {hp[i, 1] / ns_i:.0f}, wait K2 {hp[i, 2] / ns_i:.0f}")
 
 
 if __name__ == "__main__":
