@@ -152,6 +152,12 @@ _SIGS = {
     "gmr_motion_tracker_torques_dev": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 8),
     "gmr_motion_tracker_torques": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 7),
     "gmr_motion_tracker_control_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gmr_motion_tracker_set_proprio": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gmr_motion_tracker_proprio_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "gmr_motion_tracker_proprio": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "gmr_motion_tracker_proprio_reset_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gmr_motion_tracker_proprio_reset": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "gmr_motion_tracker_proprio_state": (C.c_int, [C.c_void_p] * 7),
     "gmr_comm_create": (C.c_int, [C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),
     "gmr_comm_destroy": (C.c_int, [C.c_void_p]),
     "gmr_comm_rank": (C.c_int, [C.c_void_p]),
@@ -604,6 +610,43 @@ class TrackerActuator(C.Structure):
     """``gmr_tracker_actuator_t``: the actuators of ``gmr_motion_tracker_torques[_dev]``, four addresses (``friction`` and ``torque_limit``
     may be NULL) and whether the first three are ``[N][R]`` (1) or ``[R]`` (0)"""
     _fields_ = [(k, C.c_void_p) for k in TRACKER_ACTUATOR_FIELDS] + [("per_env", C.c_int32)]
+
+
+# gmr_motion_tracker_set_proprio / _proprio[_dev] (include/gmr_hip.h, "tracker proprioception")
+PROPRIO_TERMS = ("lin_vel_z", "ang_vel_xy", "orientation", "torques", "dof_vel", "dof_acc", "root_acc", "action_rate", "dof_pos_limits",
+                 "dof_vel_limits", "torque_limits", "torque_tiredness", "power", "base_height")
+PROPRIO_MAX_EXTRA = 16
+PROPRIO_NOISE_BLOCKS = ("gravity", "ang_vel", "dof_pos", "dof_vel", "lin_vel", "height")
+NOISE_DISTRIBUTIONS = {"none": 0, "gaussian": 1, "uniform": 2}
+NOISE_OPERATIONS = {"additive": 0, "scaling": 1}
+PROPRIO_CONFIG_TABLES = ("default_dof_pos", "dof_pos_limits", "dof_vel_limits", "torque_limits", "scales")
+PROPRIO_IN_FIELDS = ("root_states", "dof_pos", "dof_vel", "actions", "mean_torques", "extra", "ground", "episode_steps")
+PROPRIO_OUT_FIELDS = ("base_lin_vel", "base_ang_vel", "projected_gravity", "filtered_lin_vel", "filtered_ang_vel", "obs", "priv", "term", "total",
+                      "done")
+
+
+class ProprioNoise(C.Structure):
+    """``gmr_proprio_noise_t``: one spec of ``apply_randomization``"""
+    _fields_ = [("distribution", C.c_int32), ("operation", C.c_int32), ("a", C.c_double), ("b", C.c_double)]
+
+
+class ProprioConfig(C.Structure):
+    """``gmr_proprio_config_t``: the configuration of ``gmr_motion_tracker_set_proprio``, host addresses and values"""
+    _fields_ = ([(k, C.c_void_p) for k in PROPRIO_CONFIG_TABLES] + [("extra_cols", C.c_int32), ("max_episode_steps", C.c_int32)]
+                + [(k, C.c_double) for k in ("filter_weight", "soft_dof_pos_limit", "soft_dof_vel_limit", "soft_torque_limit")]
+                + [(k, C.c_float) for k in ("scale_gravity", "scale_lin_vel", "scale_ang_vel", "scale_dof_pos", "scale_dof_vel",
+                                            "base_height_target", "terminate_vel", "terminate_height")]
+                + [("noise", ProprioNoise * len(PROPRIO_NOISE_BLOCKS))])
+
+
+class ProprioIn(C.Structure):
+    """``gmr_proprio_in_t``: the inputs of ``gmr_motion_tracker_proprio[_dev]``, each an address or NULL"""
+    _fields_ = [(k, C.c_void_p) for k in PROPRIO_IN_FIELDS]
+
+
+class ProprioOut(C.Structure):
+    """``gmr_proprio_out_t``: the outputs of ``gmr_motion_tracker_proprio[_dev]``, each an address or NULL"""
+    _fields_ = [(k, C.c_void_p) for k in PROPRIO_OUT_FIELDS]
 
 
 # gmr_motion_tracker_set_preview: the block bits in row order, the frames and the limits (include/gmr_hip.h, "tracker preview")

@@ -2,7 +2,8 @@
 // C-ABI): the FK tree (created in gmr_abi.hip) and the motion library (gmr_motion.hip), both read by gmr_body_state.hip, and
 // the motion tracker (gmr_tracker.hip), which is bound to a library and, with links attached (gmr_tracker_links.hip), to an FK tree;
 // gmr_tracker_preview.hip reads its state and tables, gmr_tracker_adaptive.hip owns its bins (adaptive sampling, masked resets),
-// gmr_tracker_anchor.hip its anchors, gmr_tracker_control.hip its control tables and the two arrays of the actuator model.
+// gmr_tracker_anchor.hip its anchors, gmr_tracker_control.hip its control tables and the two arrays of the actuator model,
+// gmr_tracker_proprio.hip its proprioception tables and the six arrays behind them.
 #pragma once
 #include <stdint.h>
 
@@ -108,6 +109,37 @@ struct ControlTables {
   float default_pos[TRACKER_MAX_DOF] = {};  // the robot's default pose, where the start-up easing begins (NOT TrackerTables::dof_default)
 };
 constexpr int CONTROL_MAX_DECIMATION = 64;
+constexpr int PROPRIO_TERMS = 14;         // lin_vel_z .. base_height, the order of include/gmr_hip.h N10
+constexpr int PROPRIO_MAX_EXTRA = 16;     // pass-through columns of the observation row
+constexpr int PROPRIO_NOISE_BLOCKS = 6;   // gravity, ang_vel, dof_pos, dof_vel, lin_vel, height
+// one noise spec as the kernel applies it: n = a + m * (z or u), then x + n or x * n
+struct ProprioNoise {
+  int32_t dist = 0, op = 0;                 // GMR_NOISE_NONE / _GAUSSIAN / _UNIFORM, GMR_NOISE_ADDITIVE / _SCALING
+  float a = 0.0f, m = 0.0f;                 // gaussian: (float)mu, (float)sigma; uniform: (float)lower, (float)(upper - lower), the span formed in double
+};
+// the proprioception configuration of a tracker: validated on the host, travels as a kernel argument like TrackerTables
+struct ProprioTables {
+  int32_t R = 0;                            // the robot dofs it was set for; 0: proprio was never set
+  int32_t C = 0;                            // pass-through columns, 0 .. PROPRIO_MAX_EXTRA
+  int32_t max_steps = 0;                    // the time-out: episode_steps > max_steps
+  int32_t any_noise = 0;                    // some spec is not GMR_NOISE_NONE
+  float fw = 0.0f, fw1 = 0.0f;              // (float)filter_weight, (float)(1.0 - filter_weight)
+  float s_g = 0.0f, s_v = 0.0f, s_w = 0.0f, s_q = 0.0f, s_qd = 0.0f;      // the normalisation scales
+  float height_target = 0.0f, term_vel = 0.0f, term_height = 0.0f;
+  ProprioNoise noise[PROPRIO_NOISE_BLOCKS];
+  float scale[PROPRIO_TERMS] = {};          // the weights of the total; zero: the term stays out
+  float default_pos[TRACKER_MAX_DOF] = {};  // (a table of its own: not ControlTables::default_pos)
+  float lower[TRACKER_MAX_DOF] = {}, upper[TRACKER_MAX_DOF] = {};      // the soft position limits, formed on the host in the order of t1.py:665-670
+  float vel_soft[TRACKER_MAX_DOF] = {};     // dof_vel_limits * (float)soft_dof_vel_limit
+  float tq_lim[TRACKER_MAX_DOF] = {}, tq_soft[TRACKER_MAX_DOF] = {};   // torque_limits and torque_limits * (float)soft_torque_limit
+};
+// the proprioception state of a tracker (device pointers into its proprio block; zero after set_proprio)
+struct ProprioState {
+  float *filtered_lin_vel = nullptr, *filtered_ang_vel = nullptr;      // [N][3]
+  float* last_root_vel = nullptr;                                      // [N][6]
+  float *last_actions = nullptr, *last_dof_vel = nullptr;              // [N][R]
+  uint32_t* noise_tick = nullptr;                                      // [N] launches that applied noise to the environment
+};
 }  // namespace gmr
 
 struct gmr_motion_tracker {
@@ -131,6 +163,9 @@ struct gmr_motion_tracker {
   float* held = nullptr;         // [N][R] the targets the actuators hold (the reference's last_dof_targets); null until control is set
   float* torque_acc = nullptr;   // [N][R] the running sum of the torques of an environment step
   gmr::DeviceBlock control_block; // held and torque_acc: one allocation, made by gmr_motion_tracker_set_control
+  gmr::ProprioTables proprio;    // proprio.R = 0 until gmr_motion_tracker_set_proprio configures it
+  gmr::ProprioState proprio_state;
+  gmr::DeviceBlock proprio_block; // the six arrays of proprio_state: one allocation, made by gmr_motion_tracker_set_proprio
   std::vector<double> clip_w;    // the clip weights as given at creation (empty: uniform)
   std::mutex mu;                 // the tables, and the whole of every synchronous entry point
 };

@@ -29,6 +29,9 @@ GMR_PHILOX_FN void philox4x32(const uint32_t c[4], const uint32_t k[2], uint32_t
 // word 1 of a draw -> u in [0, 1): 24 bits, exact in float32
 GMR_PHILOX_FN float philox_unit(uint32_t w) { return (float)(w >> 8) * 5.9604644775390625e-8f; }
 
+// a word -> u in (0, 1]: 24 bits, exact in float32; what a logarithm may take
+GMR_PHILOX_FN float philox_unit_open(uint32_t w) { return (float)((w >> 8) + 1u) * 5.9604644775390625e-8f; }
+
 // word 0 of a draw -> one of C equally likely clips
 GMR_PHILOX_FN int philox_below(uint32_t w, int C) { return (int)(((uint64_t)w * (uint64_t)C) >> 32); }
 

@@ -13,7 +13,9 @@ launch and :meth:`MotionTracker.set_adaptive` draws episode starts where episode
 environment in the simulator's world: a yaw and a translation per environment that every world-frame output goes through (DESIGN.md
 section 6o, ``csrc/gmr_tracker_anchor.hip``).  :meth:`MotionTracker.targets` and :meth:`MotionTracker.torques` are the control half of the step
 (``csrc/gmr_tracker_control.hip``): the PD targets -- the reference's joint row eased in from the default pose, plus
-the clipped action -- in one launch, and the actuator model in one launch per physics substep.
+the clipped action -- in one launch, and the actuator model in one launch per physics substep.  :meth:`MotionTracker.proprio` is what
+follows the physics (``csrc/gmr_tracker_proprio.hip``): the body-frame base state, the proprioceptive observation row
+with sensor noise, the regularisation penalties, the state-based termination and the roll-over of the ``last_*`` arrays, in one launch.
 
 No GPU framework is imported here: :meth:`MotionTracker.step` takes and returns NumPy arrays, :meth:`MotionTracker.step_dev` reads
 and writes device memory the caller names -- ``_lib.DeviceBuffer``, a raw address, or anything with ``data_ptr()``.
@@ -43,6 +45,15 @@ DEFAULT_ADAPTIVE = {"bin_seconds": 1.0, "alpha": 0.1, "uniform": 0.3, "lookahead
 CONTROL_MAX_DECIMATION = 64
 # t1_imitation.py:388, :414: two seconds of start-up, the action gain during it and afterwards
 DEFAULT_CONTROL = {"startup_seconds": 2.0, "gain_startup": 0.1, "gain_run": 0.2}
+# the penalties of :meth:`MotionTracker.proprio` in column order (t1.py:622-625, :631-694) and the blocks that take sensor noise
+PROPRIO_TERMS = ("lin_vel_z", "ang_vel_xy", "orientation", "torques", "dof_vel", "dof_acc", "root_acc", "action_rate", "dof_pos_limits",
+                 "dof_vel_limits", "torque_limits", "torque_tiredness", "power", "base_height")
+PROPRIO_NOISE_BLOCKS = ("gravity", "ang_vel", "dof_pos", "dof_vel", "lin_vel", "height")
+PROPRIO_NORMALIZATION = ("gravity", "lin_vel", "ang_vel", "dof_pos", "dof_vel")
+PROPRIO_MAX_EXTRA = 16
+PROPRIO_STATE = ("filtered_lin_vel", "filtered_ang_vel", "last_root_vel", "last_actions", "last_dof_vel", "noise_tick")
+NOISE_DISTRIBUTIONS = {"none": 0, "gaussian": 1, "uniform": 2}
+NOISE_OPERATIONS = {"additive": 0, "scaling": 1}
 LINK_SIM = {"body_pos": (0, 3), "body_rot": (3, 4), "body_vel": (7, 3), "body_ang_vel": (10, 3)}      # offset and width in a packed row of 13
 
 
@@ -150,6 +161,7 @@ class MotionTracker:
         self._adaptive = None         # (bin_seconds, bin_start i64[C + 1]) once set_adaptive has built the bins
         self._anchors = False         # whether the per-environment anchors are enabled
         self._control = None          # (R, decimation) once set_control has configured the control half
+        self._proprio = None          # (R, extra_cols) once set_proprio has configured the proprioception half
         if sc is not None or wt is not None:
             self.set_terms(sc, wt)
 
@@ -680,6 +692,262 @@ class MotionTracker:
         _lib.check(_lib.lib().gmr_motion_tracker_control_state(self.handle, _lib._ptr(out["held"]), _lib._ptr(out["torque_acc"])))
         return out
 
+    # ---- proprioception ------------------------------------------------------------------------------
+    def _proprio_setup(self, default_dof_pos, dof_pos_limits, dof_vel_limits, torque_limits, extra_cols, filter_weight, normalization, noise,
+                       soft_dof_pos_limit, soft_dof_vel_limit, soft_torque_limit, base_height_target, terminate_vel, terminate_height,
+                       max_episode_steps, scales):
+        """the checks of :meth:`set_proprio`, all of them before a device is touched -> a dict of the checked values"""
+        R = self.nrobot_dof
+        tables = {}
+        for name, a, shape in (("default_dof_pos", default_dof_pos, (R,)), ("dof_pos_limits", dof_pos_limits, (R, 2)),
+                               ("dof_vel_limits", dof_vel_limits, (R,)), ("torque_limits", torque_limits, (R,))):
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.shape != shape:
+                raise ValueError(f"{name} has shape {a.shape}, {shape} needed (the robot has {R} dofs)")
+            if not np.isfinite(a).all():
+                raise ValueError(f"{name} is not finite")
+            tables[name] = a
+        if int(extra_cols) != extra_cols or not 0 <= int(extra_cols) <= PROPRIO_MAX_EXTRA:
+            raise ValueError(f"extra_cols = {extra_cols} outside 0 to {PROPRIO_MAX_EXTRA} pass-through columns")
+        if int(max_episode_steps) != max_episode_steps or not 0 <= int(max_episode_steps) < 2 ** 31:
+            raise ValueError(f"max_episode_steps = {max_episode_steps}, a whole number of steps that is not negative is needed")
+        fw, sp, sv, st = (float(x) for x in (filter_weight, soft_dof_pos_limit, soft_dof_vel_limit, soft_torque_limit))
+        if not all(np.isfinite(x) for x in (fw, sp, sv, st)):
+            raise ValueError(f"filter_weight = {fw} and the soft factors {(sp, sv, st)} must be finite")
+        norm = dict.fromkeys(PROPRIO_NORMALIZATION, 1.0)
+        if normalization is not None:
+            unknown = sorted(set(normalization) - set(norm))
+            if unknown:
+                raise KeyError(f"normalization: unknown scales {unknown} (known: {list(PROPRIO_NORMALIZATION)})")
+            norm.update(normalization)
+        norm = {k: float(np.float32(v)) for k, v in norm.items()}
+        scalars = {k: float(np.float32(v)) for k, v in (("base_height_target", base_height_target), ("terminate_vel", terminate_vel),
+                                                        ("terminate_height", terminate_height))}
+        for k, v in {**norm, **scalars}.items():
+            if not np.isfinite(v):
+                raise ValueError(f"{k} = {v} must be finite")
+        specs = []
+        noise = {} if noise is None else dict(noise)
+        unknown = sorted(set(noise) - set(PROPRIO_NOISE_BLOCKS))
+        if unknown:
+            raise KeyError(f"noise: unknown blocks {unknown} (known: {list(PROPRIO_NOISE_BLOCKS)})")
+        for k in PROPRIO_NOISE_BLOCKS:
+            spec = noise.get(k)
+            if spec is None or spec.get("distribution", "none") == "none":
+                specs.append((0, 0, 0.0, 0.0))
+                continue
+            dist, op = spec.get("distribution"), spec.get("operation")
+            if dist not in NOISE_DISTRIBUTIONS:
+                raise ValueError(f"noise[{k!r}]: distribution is one of {sorted(NOISE_DISTRIBUTIONS)}, got {dist!r}")
+            if op not in NOISE_OPERATIONS:
+                raise ValueError(f"noise[{k!r}]: operation is one of {sorted(NOISE_OPERATIONS)}, got {op!r}")
+            rng = spec.get("range")
+            if rng is None or len(rng) != 2:
+                raise ValueError(f"noise[{k!r}]: range is a pair, got {rng!r}")
+            a, b = float(rng[0]), float(rng[1])
+            with np.errstate(over="ignore"):
+                fits = all(np.isfinite(np.float32(x)) for x in (a, b, b - a))
+            if not fits:
+                raise ValueError(f"noise[{k!r}]: range {(a, b)} is not finite in float32")
+            if dist == "gaussian" and b < 0:
+                raise ValueError(f"noise[{k!r}]: a gaussian's deviation {b} is negative")
+            specs.append((NOISE_DISTRIBUTIONS[dist], NOISE_OPERATIONS[op], a, b))
+        if scales is None:
+            sc = np.zeros(len(PROPRIO_TERMS), np.float32)
+        else:
+            if isinstance(scales, dict):
+                unknown = sorted(set(scales) - set(PROPRIO_TERMS))
+                if unknown:
+                    raise KeyError(f"scales: unknown terms {unknown} (known: {list(PROPRIO_TERMS)})")
+                scales = [scales.get(k, 0.0) for k in PROPRIO_TERMS]
+            sc = np.ascontiguousarray(scales, dtype=np.float32).reshape(-1)
+            if len(sc) != len(PROPRIO_TERMS):
+                raise ValueError(f"scales has {len(sc)} entries, there are {len(PROPRIO_TERMS)} terms: {list(PROPRIO_TERMS)}")
+            if not np.isfinite(sc).all():
+                raise ValueError("scales must be finite")
+        # the soft position limits as the library forms them (t1.py:665-670), to refuse upper < lower here
+        lim = tables["dof_pos_limits"]
+        half = np.float32(0.5 * (1.0 - sp))
+        span = lim[:, 1] - lim[:, 0]
+        lower, upper = lim[:, 0] + half * span, lim[:, 1] - half * span
+        soft = (lower, upper, tables["dof_vel_limits"] * np.float32(sv), tables["torque_limits"] * np.float32(st))
+        if not all(np.isfinite(x).all() for x in soft):
+            raise ValueError("the soft limits are not finite in float32")
+        if (upper < lower).any():
+            raise ValueError(f"dof_pos_limits: upper < lower at dofs {np.nonzero(upper < lower)[0].tolist()}")
+        return {**tables, "scales": sc, "extra_cols": int(extra_cols), "max_episode_steps": int(max_episode_steps), "filter_weight": fw,
+                "soft": (sp, sv, st), "norm": norm, **scalars, "noise": specs}
+
+    def set_proprio(self, default_dof_pos, dof_pos_limits, dof_vel_limits, torque_limits, *, base_height_target: float, terminate_vel: float,
+                    terminate_height: float, max_episode_steps: int, extra_cols: int = 0, filter_weight: float = 1.0, normalization=None,
+                    noise=None, soft_dof_pos_limit: float = 1.0, soft_dof_vel_limit: float = 1.0, soft_torque_limit: float = 1.0,
+                    scales=None) -> None:
+        """Configures the proprioception half: ``default_dof_pos [R]`` (a table of its own, independent of :meth:`set_control`),
+        ``dof_pos_limits [R,2]``, ``dof_vel_limits [R]`` and ``torque_limits [R]`` with their three soft factors, ``extra_cols`` pass-through
+        columns (0 to 16) of the observation row, the ``filter_weight`` of the low-pass filtered velocities, ``normalization`` -- a dict
+        over ``gravity, lin_vel, ang_vel, dof_pos, dof_vel`` (1 by default) --, ``noise`` -- a dict over :data:`PROPRIO_NOISE_BLOCKS` of
+        ``{"distribution": "gaussian" | "uniform" | "none", "operation": "additive" | "scaling", "range": (a, b)}`` as the reference's
+        configuration writes them --, ``base_height_target``, the thresholds ``terminate_vel`` and ``terminate_height``,
+        ``max_episode_steps`` (``ceil(episode_length_s / dt)``) and ``scales``, fourteen numbers or a dict over :data:`PROPRIO_TERMS` that
+        weigh ``total`` (zero, the default: the term stays out).  Allocates the six state arrays (zeros).  Synchronous; call it again
+        after :meth:`set_dof_map` has changed the number of robot dofs."""
+        from . import _lib
+        c = self._proprio_setup(default_dof_pos, dof_pos_limits, dof_vel_limits, torque_limits, extra_cols, filter_weight, normalization, noise,
+                                soft_dof_pos_limit, soft_dof_vel_limit, soft_torque_limit, base_height_target, terminate_vel, terminate_height,
+                                max_episode_steps, scales)
+        cfg = _lib.ProprioConfig()
+        for k in _lib.PROPRIO_CONFIG_TABLES:
+            setattr(cfg, k, c[k].ctypes.data)
+        cfg.extra_cols, cfg.max_episode_steps, cfg.filter_weight = c["extra_cols"], c["max_episode_steps"], c["filter_weight"]
+        cfg.soft_dof_pos_limit, cfg.soft_dof_vel_limit, cfg.soft_torque_limit = c["soft"]
+        for k in PROPRIO_NORMALIZATION:
+            setattr(cfg, "scale_" + k, c["norm"][k])
+        cfg.base_height_target, cfg.terminate_vel, cfg.terminate_height = c["base_height_target"], c["terminate_vel"], c["terminate_height"]
+        for i, (dist, op, a, b) in enumerate(c["noise"]):
+            cfg.noise[i].distribution, cfg.noise[i].operation, cfg.noise[i].a, cfg.noise[i].b = dist, op, a, b
+        _lib.check(_lib.lib().gmr_motion_tracker_set_proprio(self.handle, C.byref(cfg)))
+        self._proprio = (self.nrobot_dof, c["extra_cols"])
+
+    def _need_proprio(self, what: str):
+        p = getattr(self, "_proprio", None)
+        if p is None:
+            raise ValueError(f"{what}: proprio is not set on this tracker, call set_proprio() first")
+        if p[0] != self.nrobot_dof:
+            raise ValueError(f"{what}: proprio was set for {p[0]} robot dofs, the dof map now has {self.nrobot_dof}: call set_proprio() again")
+        return p
+
+    def proprio_layout(self) -> Dict[str, object]:
+        """The column ranges ``(first, end)`` of ``obs`` -- ``gravity, ang_vel, extra, dof_pos, dof_vel, actions`` --, its ``width``, the
+        ranges of ``priv`` (``lin_vel, height``) and ``terms``, the names of the columns of ``term``"""
+        R, Cx = self._need_proprio("proprio_layout")
+        edges = np.cumsum([0, 3, 3, Cx, R, R, R])
+        names = ("gravity", "ang_vel", "extra", "dof_pos", "dof_vel", "actions")
+        return {"obs": {k: (int(edges[i]), int(edges[i + 1])) for i, k in enumerate(names)}, "width": int(edges[-1]),
+                "priv": {"lin_vel": (0, 3), "height": (3, 4)}, "terms": PROPRIO_TERMS}
+
+    def _proprio_counts(self):
+        R, Cx = self._proprio
+        ins = {"root_states": 13, "dof_pos": R, "dof_vel": R, "actions": R, "mean_torques": R, "extra": Cx, "ground": 1, "episode_steps": 1}
+        outs = {"base_lin_vel": 3, "base_ang_vel": 3, "projected_gravity": 3, "filtered_lin_vel": 3, "filtered_ang_vel": 3, "obs": 6 + Cx + 3 * R,
+                "priv": 4, "term": len(PROPRIO_TERMS), "total": 1, "done": 1}
+        return ins, outs
+
+    def _check_extra(self, what: str, extra) -> None:
+        if (extra is not None) != (self._proprio[1] > 0):
+            raise ValueError(f"{what}: extra is needed exactly when extra_cols > 0 (extra_cols = {self._proprio[1]}, extra "
+                             f"{'given' if extra is not None else 'missing'})")
+
+    def proprio(self, root_states, dof_pos, dof_vel, actions=None, mean_torques=None, extra=None, ground=None, episode_steps=None,
+                noise: bool = True) -> Dict[str, np.ndarray]:
+        """What follows the physics of a step, host arrays in and out: from ``root_states [N,13]`` (position, xyzw quaternion, world linear
+        and angular velocity, the simulator's tensor as it lies), ``dof_pos``, ``dof_vel`` ``[N,R]`` and, each optional, the clipped
+        ``actions [N,R]`` of :meth:`targets`, the ``mean_torques [N,R]`` of :meth:`torques`, ``extra [N,extra_cols]``, ``ground [N]``
+        (terrain height under the base; ``None``: 0) and ``episode_steps i32[N]`` -- ``base_lin_vel``, ``base_ang_vel``,
+        ``projected_gravity``, ``filtered_lin_vel``, ``filtered_ang_vel`` ``[N,3]``, ``obs [N,W]`` (see :meth:`proprio_layout`), ``priv
+        [N,4]``, ``term [N,14]`` in the order of :data:`PROPRIO_TERMS`, ``total [N]`` and ``done i32[N]`` (bit 0: velocity, bit 1: height,
+        bit 2: time-out).  A term without its input is 0 and stays out of ``total``.  Then ``last_actions`` (with actions),
+        ``last_dof_vel`` and ``last_root_vel`` roll over, and with ``noise`` and a noise spec every environment's tick moves by one.
+        One launch; clocks, clips and draw counters stay as they are."""
+        from . import _lib
+        self._need_proprio("proprio")
+        self._check_extra("proprio", extra)
+        N = self.num_envs
+        ins, outs = self._proprio_counts()
+        given = {"root_states": root_states, "dof_pos": dof_pos, "dof_vel": dof_vel, "actions": actions, "mean_torques": mean_torques, "extra": extra,
+                 "ground": ground}
+        st, keep = _lib.ProprioIn(), []
+        for k, a in given.items():
+            if a is None:
+                if k in ("root_states", "dof_pos", "dof_vel"):
+                    raise ValueError(f"proprio: {k} is needed")
+                continue
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            shape = (N,) if k == "ground" else (N, ins[k])
+            if a.shape != shape:
+                raise ValueError(f"{k}: shape {a.shape}, {shape} needed")
+            keep.append(a)
+            setattr(st, k, a.ctypes.data)
+        steps = self._per_env_ints(episode_steps, "episode_steps")
+        if steps is not None:
+            st.episode_steps = steps.ctypes.data
+        out = {k: np.empty((N,) if k in ("total", "done") else (N, w), dtype=np.int32 if k == "done" else np.float32) for k, w in outs.items()}
+        table = _lib.ProprioOut(**{k: a.ctypes.data for k, a in out.items()})
+        _lib.check(_lib.lib().gmr_motion_tracker_proprio(self.handle, C.byref(st), 1 if noise else 0, C.byref(table)))
+        return out
+
+    def proprio_dev(self, root_states, dof_pos, dof_vel, actions=None, mean_torques=None, extra=None, ground=None, episode_steps=None,
+                    noise: bool = True, stream=None, **outputs) -> None:
+        """:meth:`proprio` on device memory, asynchronous on ``stream``: ONE launch.  ``outputs`` names whichever of the arrays of
+        :meth:`proprio` are wanted; every array is a ``_lib.DeviceBuffer``, a raw address or an object with ``data_ptr()``."""
+        from . import _lib
+        self._need_proprio("proprio_dev")
+        self._check_extra("proprio_dev", extra)
+        N = self.num_envs
+        ins, outs = self._proprio_counts()
+        unknown = sorted(set(outputs) - set(outs))
+        if unknown:
+            raise TypeError(f"proprio_dev: unknown outputs {unknown}")
+        given = {"root_states": root_states, "dof_pos": dof_pos, "dof_vel": dof_vel, "actions": actions, "mean_torques": mean_torques, "extra": extra,
+                 "ground": ground, "episode_steps": episode_steps}
+        st, table = _lib.ProprioIn(), _lib.ProprioOut()
+        for k, x in given.items():
+            if x is None and k in ("root_states", "dof_pos", "dof_vel"):
+                raise ValueError(f"proprio_dev: {k} is needed")
+            p = _dev_ptr(x, k, "int32" if k == "episode_steps" else "float32", N * ins[k])
+            setattr(st, k, None if p is None else p.value)
+        for k, x in outputs.items():
+            p = _dev_ptr(x, k, "int32" if k == "done" else "float32", N * outs[k])
+            setattr(table, k, None if p is None else p.value)
+        _lib.check(_lib.lib().gmr_motion_tracker_proprio_dev(self.handle, C.byref(st), 1 if noise else 0, C.byref(table), _lib._s(stream)))
+
+    def proprio_reset(self, root_states, mask=None, env_ids=None) -> int:
+        """After a reset: every environment whose ``mask`` is set (``None``: all) gets filtered velocities of zero and ``last_root_vel =
+        root_states[i, 7:13]`` (``root_states [n,13]``); ``last_actions`` and ``last_dof_vel`` stay, as in the reference.  Without
+        ``env_ids`` the arrays cover every environment; with it (every environment at most once) they are indexed by list position, as
+        the arrays of :meth:`hold` are.  Returns how many ids of masked entries lay outside ``[0, num_envs)``."""
+        from . import _lib
+        self._need_proprio("proprio_reset")
+        ids, n = None, self.num_envs
+        if env_ids is not None:
+            ids = np.ascontiguousarray(env_ids, dtype=np.int32).reshape(-1)
+            n = len(ids)
+            if len(np.unique(ids)) != n:
+                raise ValueError("proprio_reset: env_ids names an environment twice")
+        rs = np.ascontiguousarray(root_states, dtype=np.float32)
+        if rs.shape != (n, 13):
+            raise ValueError(f"root_states: shape {rs.shape}, {(n, 13)} needed")
+        m = _mask(mask, "mask", n)
+        if n == 0:
+            return 0
+        ignored = C.c_int()
+        _lib.check(_lib.lib().gmr_motion_tracker_proprio_reset(self.handle, n, _lib._ptr(ids), _lib._ptr(m), _lib._ptr(rs), C.byref(ignored)))
+        return int(ignored.value)
+
+    def proprio_reset_dev(self, root_states, mask=None, env_ids=None, n: Optional[int] = None, stream=None) -> None:
+        """:meth:`proprio_reset` on device memory, asynchronous on ``stream``: ONE launch.  ``root_states f32[n*13]``, ``mask i32[n]`` as a
+        step leaves it (``done``) or as :meth:`reset_done_dev` takes it; with ``env_ids`` (``i32[n]``) ``n`` is mandatory."""
+        from . import _lib
+        self._need_proprio("proprio_reset_dev")
+        n = self._list_length("proprio_reset_dev", env_ids, n)
+        if root_states is None:
+            raise ValueError("proprio_reset_dev: root_states is needed")
+        ptrs = (_dev_ptr(env_ids, "env_ids", "int32", n), _dev_ptr(mask, "mask", "int32", n), _dev_ptr(root_states, "root_states", "float32", n * 13))
+        _lib.check(_lib.lib().gmr_motion_tracker_proprio_reset_dev(self.handle, n, *ptrs, _lib._s(stream)))
+
+    def proprio_state(self) -> Optional[Dict[str, np.ndarray]]:
+        """``filtered_lin_vel``, ``filtered_ang_vel`` ``f32[N,3]``, ``last_root_vel f32[N,6]``, ``last_actions``, ``last_dof_vel``
+        ``f32[N,R]`` and ``noise_tick u32[N]``, or ``None`` when proprio is not set.  Synchronous."""
+        from . import _lib
+        if getattr(self, "_proprio", None) is None:
+            return None
+        self._need_proprio("proprio_state")
+        N, R = self.num_envs, self.nrobot_dof
+        out = {"filtered_lin_vel": np.empty((N, 3), np.float32), "filtered_ang_vel": np.empty((N, 3), np.float32),
+               "last_root_vel": np.empty((N, 6), np.float32), "last_actions": np.empty((N, R), np.float32),
+               "last_dof_vel": np.empty((N, R), np.float32), "noise_tick": np.empty(N, np.uint32)}
+        _lib.check(_lib.lib().gmr_motion_tracker_proprio_state(self.handle, *[_lib._ptr(out[k]) for k in PROPRIO_STATE]))
+        return out
+
     # ---- the step ---------------------------------------------------------------------------------------------------------
     def _counts(self):
         R = self.nrobot_dof
@@ -1092,6 +1360,7 @@ class MotionTracker:
             from . import _lib
             _lib.lib().gmr_motion_tracker_destroy(h)
             self.handle = None
+            self._proprio = None          # the state arrays went with the handle
 
     def __del__(self):
         try:

@@ -855,6 +855,107 @@ int gmr_motion_tracker_torques(gmr_motion_tracker_t* t, int substep, const float
  * be NULL; synchronises */
 int gmr_motion_tracker_control_state(gmr_motion_tracker_t* t, float* held, float* torque_acc);
 
+/* ---- N10: tracker proprioception (observation rows, penalty terms and termination of a motion tracker) ---- */
+/* What booster_gym/envs/t1.py::step does between "physics is done" and "the policy gets its next input", ONE launch per step: the
+ * body-frame base state and the two filtered velocities (t1.py:463-473), the proprioceptive observation row and the privileged block
+ * with sensor noise (:574-603, utils/utils.py:5-30), the fourteen regularisation penalties (:622-625, :631-694), the state-based
+ * termination (:554-557) and the roll-over of last_actions / last_dof_vel / last_root_vel (:492-494).  The statement of record is
+ * tests/proprio_mirror.py; this is the same in words.  Everything is float32 with one rounding per operation.
+ * STATE (device, owned by the tracker, zero after set_proprio): filtered_lin_vel, filtered_ang_vel f32[N][3], last_root_vel f32[N][6],
+ * last_actions, last_dof_vel f32[N][R], noise_tick u32[N].
+ * THE STEP, for environment e (p, q = (qv, w), v, om: position, xyzw quaternion, world linear and angular velocity of root_states[e];
+ * h = p.z - (ground ? ground[e] : 0)):
+ *   rot(u)  = u * (2 * (w * w) - 1) - cross(qv, u) * w * 2 + qv * ((qv.x * u.x + qv.y * u.y) + qv.z * u.z) * 2   (quat_rotate_inverse,
+ *             general_motion_retargeting/torch_utils.py:78-87, in this grouping; q is used as given, not normalised)
+ *   base_lin_vel = rot(v), base_ang_vel = rot(om), projected_gravity = rot((0, 0, -1))
+ *   filtered = base * (float)fw + filtered * (float)(1.0 - fw), written to the state and to the outputs
+ *   obs[e]  = [noisy(projected_gravity) * s_g | noisy(base_ang_vel) * s_w | extra[e] | noisy(dof_pos - default) * s_q |
+ *              noisy(dof_vel) * s_qd | actions (zeros without)], W = 6 + C + 3 R columns
+ *   priv[e] = [noisy(base_lin_vel) * s_v | noisy(h)]
+ *   term[e] = lin_vel_z: filtered_lin_vel.z^2; ang_vel_xy: base_ang_vel.x^2 + .y^2; orientation: projected_gravity.x^2 + .y^2;
+ *             torques: sum tau^2; dof_vel: sum qd^2; dof_acc: sum ((last_dof_vel - qd) / (float)dt)^2; root_acc: sum over the six of
+ *             ((last_root_vel - (v, om)) / (float)dt)^2 in rising order; action_rate: sum (last_actions - a)^2; dof_pos_limits: the
+ *             count of q < lower or q > upper; dof_vel_limits: sum min(max(|qd| - vel_limit * soft, 0), 1); torque_limits: sum
+ *             max(|tau| - torque_limit * soft, 0); torque_tiredness: sum min((tau / torque_limit)^2, 1); power: sum max(tau * qd, 0);
+ *             base_height: (h - target)^2.  A min / max keeps a NaN.  A sum over the dofs: lane l of the environment's 16 adds the
+ *             columns l, l + 16, .. in rising order, then x = x + x[lane ^ m] for m = 1, 2, 4, 8 (tracker_step_kernel's order).  A term
+ *             without its input (tau: mean_torques, a: actions) is 0.
+ *   total[e] = sum of scale_k * term_k in rising k over the terms with scale_k != 0 whose input is there
+ *   done[e] = 1 * (sum over the six of (v, om)^2 in rising order > terminate_vel) | 2 * (h < terminate_height) |
+ *             4 * (episode_steps[e] > max_episode_steps); a NaN compares false
+ *   then last_actions = actions (kept without actions), last_dof_vel = dof_vel, last_root_vel = (v, om), noise_tick[e] += 1 if noise
+ *   was applied.  No clock moves, no draw counter of the tracker moves, nothing of the library is read.
+ * NOISE of element i of environment e (i: the obs column, or W + k for priv column k), when the launch's noise flag is set and the
+ * block of the element has a spec: (w0, w1, w2, w3) = philox4x32(counter (e, noise_tick[e], i >> 1, 1), the tracker's key); an even i
+ * takes (wa, wb) = (w0, w1), an odd i (w2, w3).  uniform: n = a + (float)(b - a) * philox_unit(wa).  gaussian: u1 = (float)((wa >> 8) +
+ * 1) * 2^-24, u2 = philox_unit(wb), z = sqrtf(-2 * logf(u1)) * cosf(6.2831855f * u2), n = a + b * z.  additive: x + n, scaling: x * n
+ * (utils/utils.py:9-25).  Word 3 = 1 of the counter keeps these draws apart from the (e, draws, 0, 0) of the tracker's resets.
+ * The tracker stays SINGLE-STREAM.  Every call below is GMR_ERR_ARG, before a device is touched, on a tracker whose proprio was never
+ * set, or whose dof map has changed R since. */
+#define GMR_PROPRIO_TERMS 14
+#define GMR_PROPRIO_MAX_EXTRA 16
+#define GMR_PROPRIO_NOISE_BLOCKS 6     /* gravity, ang_vel, dof_pos, dof_vel, lin_vel, height */
+#define GMR_NOISE_NONE 0
+#define GMR_NOISE_GAUSSIAN 1
+#define GMR_NOISE_UNIFORM 2
+#define GMR_NOISE_ADDITIVE 0
+#define GMR_NOISE_SCALING 1
+typedef struct {            /* apply_randomization (utils/utils.py:5-30): range (a, b) is (mean, deviation) or (lower, upper) */
+  int32_t distribution, operation;
+  double a, b;
+} gmr_proprio_noise_t;
+typedef struct {            /* the configuration of set_proprio: HOST pointers and values */
+  const float *default_dof_pos;       /* [R] (t1.py:264-272)                                                          */
+  const float *dof_pos_limits;        /* [R][2] lower, upper (t1.py:665-670)                                          */
+  const float *dof_vel_limits;        /* [R] (t1.py:677)                                                              */
+  const float *torque_limits;         /* [R] (t1.py:684, :690)                                                        */
+  const float *scales;                /* [GMR_PROPRIO_TERMS] the weights of the total                                 */
+  int32_t extra_cols, max_episode_steps;
+  double filter_weight;
+  double soft_dof_pos_limit, soft_dof_vel_limit, soft_torque_limit;
+  float scale_gravity, scale_lin_vel, scale_ang_vel, scale_dof_pos, scale_dof_vel;
+  float base_height_target, terminate_vel, terminate_height;
+  gmr_proprio_noise_t noise[GMR_PROPRIO_NOISE_BLOCKS];
+} gmr_proprio_config_t;
+typedef struct {            /* the inputs of a proprio call: device pointers (gmr_motion_tracker_proprio: host pointers) of the user */
+  const float *root_states;           /* [N][13] position, xyzw quaternion, world linear and angular velocity         */
+  const float *dof_pos, *dof_vel;     /* [N][R]                                                                       */
+  const float *actions;               /* [N][R] the clipped actions, or NULL                                          */
+  const float *mean_torques;          /* [N][R] or NULL                                                               */
+  const float *extra;                 /* [N][C]; there if and only if C > 0                                           */
+  const float *ground;                /* [N] terrain height under the base, or NULL: 0                                */
+  const int32_t *episode_steps;       /* [N] or NULL: no time-out                                                     */
+} gmr_proprio_in_t;
+typedef struct {            /* the outputs of a proprio call, each an address or NULL */
+  float *base_lin_vel, *base_ang_vel, *projected_gravity, *filtered_lin_vel, *filtered_ang_vel;   /* [N][3] */
+  float *obs;                         /* [N][6 + C + 3 R]                                                             */
+  float *priv;                        /* [N][4]                                                                       */
+  float *term;                        /* [N][GMR_PROPRIO_TERMS]                                                       */
+  float *total;                       /* [N]                                                                          */
+  int32_t *done;                      /* [N]                                                                          */
+} gmr_proprio_out_t;
+/* The configuration (t1.py:264-272 for the pose, :468-472 the filter, :582-597 scales and noise, :665-690 the limits, :554-556 the
+ * thresholds): every value finite, 0 <= extra_cols <= GMR_PROPRIO_MAX_EXTRA, b >= 0 for a gaussian, upper >= lower after the soft
+ * factor, max_episode_steps >= 0 (the caller's ceil(episode_length_s / dt)).  The host forms lower = lim0 + (float)(0.5 * (1 - soft))
+ * * (lim1 - lim0) and upper = lim1 - the same in float32.  Allocates the six state arrays and fills them with zeros; synchronises the
+ * device.  Launches in flight keep the configuration they carry. */
+int gmr_motion_tracker_set_proprio(gmr_motion_tracker_t* t, const gmr_proprio_config_t* cfg);
+/* The step (t1.py:463-473, :554-557, :574-603, :622-694, :492-494), ONE launch; noise: 0 or 1 */
+int gmr_motion_tracker_proprio_dev(gmr_motion_tracker_t* t, const gmr_proprio_in_t* in, int noise, const gmr_proprio_out_t* out,
+                                   void* stream);                                                   /* asynchronous */
+int gmr_motion_tracker_proprio(gmr_motion_tracker_t* t, const gmr_proprio_in_t* in, int noise, const gmr_proprio_out_t* out);
+/* After a reset (t1.py:310-313), ONE launch: entry i -- environment env_ids[i], or i with env_ids = NULL (n = N), the convention of
+ * hold and anchor_to_root -- whose mask i32[n] is not zero (NULL: every entry) gets filtered_lin_vel = filtered_ang_vel = 0 and
+ * last_root_vel[e] = root_states[i][7:13] (root_states f32[n][13]); last_actions and last_dof_vel stay, as in the reference.  Ids of
+ * such entries outside [0, N) are dropped and counted.  Every environment at most once in a list. */
+int gmr_motion_tracker_proprio_reset_dev(gmr_motion_tracker_t* t, int n, const int32_t* d_env_ids, const int32_t* d_mask,
+                                         const float* d_root_states, void* stream);                 /* asynchronous */
+int gmr_motion_tracker_proprio_reset(gmr_motion_tracker_t* t, int n, const int32_t* env_ids, const int32_t* mask, const float* root_states,
+                                     int* ignored /* ids of this call outside [0, N), or NULL */);
+/* the six state arrays on the host (filtered velocities t1.py:468-473, the three last_* of :492-494), each may be NULL; synchronises */
+int gmr_motion_tracker_proprio_state(gmr_motion_tracker_t* t, float* filtered_lin_vel, float* filtered_ang_vel, float* last_root_vel,
+                                     float* last_actions, float* last_dof_vel, uint32_t* noise_tick);
+
 /* ---- multi-GPU: one rank per GPU, ONE broadcast, no per-step collective ------------ */
 /* The reference parallelises over files with mp.Pool on one CPU (scripts/smplx_to_robot_dataset.py:241-242); here
  * streams shard over the ranks of one node and the only data that crosses ranks is the packed robot model + task set.
