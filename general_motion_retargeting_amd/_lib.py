@@ -158,6 +158,13 @@ _SIGS = {
     "gmr_motion_tracker_proprio_reset_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gmr_motion_tracker_proprio_reset": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
     "gmr_motion_tracker_proprio_state": (C.c_int, [C.c_void_p] * 7),
+    "gmr_motion_tracker_set_terrain": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int]),
+    "gmr_motion_tracker_terrain_heights_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gmr_motion_tracker_terrain_heights": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "gmr_motion_tracker_set_feet": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gmr_motion_tracker_feet_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gmr_motion_tracker_feet": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gmr_motion_tracker_feet_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "gmr_comm_create": (C.c_int, [C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),
     "gmr_comm_destroy": (C.c_int, [C.c_void_p]),
     "gmr_comm_rank": (C.c_int, [C.c_void_p]),
@@ -647,6 +654,32 @@ class ProprioIn(C.Structure):
 class ProprioOut(C.Structure):
     """``gmr_proprio_out_t``: the outputs of ``gmr_motion_tracker_proprio[_dev]``, each an address or NULL"""
     _fields_ = [(k, C.c_void_p) for k in PROPRIO_OUT_FIELDS]
+
+
+# gmr_motion_tracker_set_terrain / _terrain_heights[_dev] / _set_feet / _feet[_dev] (include/gmr_hip.h, "tracker feet")
+FEET_TERMS = ("collision", "feet_slip", "feet_vel_z", "feet_roll", "feet_yaw_diff", "feet_yaw_mean", "feet_distance", "feet_swing")
+FEET_MAX_EDGES, FEET_MAX_BODIES = 8, 64
+FEET_DONE_CONTACT = 8
+FEET_CONFIG_TABLES = ("edge_pos", "termination_body", "penalized_body", "scales")
+FEET_IN_FIELDS = ("contact_forces", "root_states", "episode_steps", "gait_frequency")
+FEET_OUT_FIELDS = ("feet_pos", "feet_roll", "feet_yaw", "feet_contact", "ground", "gait", "term", "total", "done")
+
+
+class FeetConfig(C.Structure):
+    """``gmr_feet_config_t``: the configuration of ``gmr_motion_tracker_set_feet``, host addresses and values"""
+    _fields_ = ([(k, C.c_void_p) for k in FEET_CONFIG_TABLES] + [("feet_body", C.c_int32 * 2)]
+                + [(k, C.c_int32) for k in ("num_edges", "nb", "num_termination", "num_penalized")]
+                + [(k, C.c_double) for k in ("force_threshold", "contact_clearance", "feet_distance_ref", "swing_period")])
+
+
+class FeetIn(C.Structure):
+    """``gmr_feet_in_t``: the inputs of ``gmr_motion_tracker_feet[_dev]`` beside the bodies, each an address or NULL"""
+    _fields_ = [(k, C.c_void_p) for k in FEET_IN_FIELDS]
+
+
+class FeetOut(C.Structure):
+    """``gmr_feet_out_t``: the outputs of ``gmr_motion_tracker_feet[_dev]``, each an address or NULL"""
+    _fields_ = [(k, C.c_void_p) for k in FEET_OUT_FIELDS]
 
 
 # gmr_motion_tracker_set_preview: the block bits in row order, the frames and the limits (include/gmr_hip.h, "tracker preview")

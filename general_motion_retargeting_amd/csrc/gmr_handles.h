@@ -3,7 +3,8 @@
 // the motion tracker (gmr_tracker.hip), which is bound to a library and, with links attached (gmr_tracker_links.hip), to an FK tree;
 // gmr_tracker_preview.hip reads its state and tables, gmr_tracker_adaptive.hip owns its bins (adaptive sampling, masked resets),
 // gmr_tracker_anchor.hip its anchors, gmr_tracker_control.hip its control tables and the two arrays of the actuator model,
-// gmr_tracker_proprio.hip its proprioception tables and the six arrays behind them.
+// gmr_tracker_proprio.hip its proprioception tables and the six arrays behind them, gmr_tracker_feet.hip its terrain, its feet tables and
+// the two arrays behind them.
 #pragma once
 #include <stdint.h>
 
@@ -140,6 +141,34 @@ struct ProprioState {
   float *last_actions = nullptr, *last_dof_vel = nullptr;              // [N][R]
   uint32_t* noise_tick = nullptr;                                      // [N] launches that applied noise to the environment
 };
+constexpr int FEET_TERMS = 8;             // collision, feet_slip .. feet_swing, the order of include/gmr_hip.h N11
+constexpr int FEET_MAX_EDGES = 8;         // edge points of one foot
+constexpr int FEET_MAX_BODIES = 64;       // entries of the termination / penalised body lists
+// the terrain of a tracker: travels as a kernel argument; field = null is the plane of height 0
+struct TerrainTables {
+  const int16_t* field = nullptr;           // [nx][ny] on the device, the first index is x (terrain.py:113)
+  int32_t nx = 0, ny = 0;
+  float border = 0.0f, hs = 1.0f;           // (float)border_pixels, (float)horizontal_scale
+  double vs = 1.0;                          // vertical_scale
+};
+// the feet configuration of a tracker: validated on the host, travels as a kernel argument like ControlTables
+struct FeetTables {
+  int32_t E = 0;                            // edge points per foot, 1 .. FEET_MAX_EDGES; 0: feet were never set
+  int32_t nb = 0;                           // bodies of the contact-force tensor
+  int32_t feet_body[2] = {};                // left, right
+  int32_t n_term = 0, n_pen = 0;
+  float threshold = 0.0f, clearance = 0.0f; // (float)force_threshold, (float)contact_clearance
+  float distance_ref = 0.0f;                // (float)feet_distance_ref
+  float half_swing = 0.0f;                  // (float)(0.5 * swing_period)
+  float scale[FEET_TERMS] = {};             // the weights of the total; zero: the term stays out
+  float edge[FEET_MAX_EDGES * 3] = {};      // edge_pos [E][3] in the foot's frame
+  int32_t term_body[FEET_MAX_BODIES] = {}, pen_body[FEET_MAX_BODIES] = {};
+};
+// the feet state of a tracker (device pointers into its feet block; zero after set_feet)
+struct FeetState {
+  float* last_feet_pos = nullptr;           // [N][2][3]
+  float* gait_process = nullptr;            // [N]
+};
 }  // namespace gmr
 
 struct gmr_motion_tracker {
@@ -166,6 +195,11 @@ struct gmr_motion_tracker {
   gmr::ProprioTables proprio;    // proprio.R = 0 until gmr_motion_tracker_set_proprio configures it
   gmr::ProprioState proprio_state;
   gmr::DeviceBlock proprio_block; // the six arrays of proprio_state: one allocation, made by gmr_motion_tracker_set_proprio
+  gmr::TerrainTables terrain;    // the plane until gmr_motion_tracker_set_terrain uploads a field
+  gmr::DeviceBlock terrain_block; // the int16 field
+  gmr::FeetTables feet;          // feet.E = 0 until gmr_motion_tracker_set_feet configures them
+  gmr::FeetState feet_state;
+  gmr::DeviceBlock feet_block;   // last_feet_pos and gait_process: one allocation, made by gmr_motion_tracker_set_feet
   std::vector<double> clip_w;    // the clip weights as given at creation (empty: uniform)
   std::mutex mu;                 // the tables, and the whole of every synchronous entry point
 };

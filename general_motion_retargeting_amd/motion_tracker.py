@@ -16,6 +16,9 @@ section 6o, ``csrc/gmr_tracker_anchor.hip``).  :meth:`MotionTracker.targets` and
 the clipped action -- in one launch, and the actuator model in one launch per physics substep.  :meth:`MotionTracker.proprio` is what
 follows the physics (``csrc/gmr_tracker_proprio.hip``): the body-frame base state, the proprioceptive observation row
 with sensor noise, the regularisation penalties, the state-based termination and the roll-over of the ``last_*`` arrays, in one launch.
+:meth:`MotionTracker.set_terrain`, :meth:`MotionTracker.terrain_heights` and :meth:`MotionTracker.feet` close the step (DESIGN.md section 6r,
+``csrc/gmr_tracker_feet.hip``): the bilinear terrain height the reference interpolates on the host, the feet pose and edge contacts, the gait
+clock, the contact-force termination, ``collision`` and the seven ``feet_*`` terms, in one launch.
 
 No GPU framework is imported here: :meth:`MotionTracker.step` takes and returns NumPy arrays, :meth:`MotionTracker.step_dev` reads
 and writes device memory the caller names -- ``_lib.DeviceBuffer``, a raw address, or anything with ``data_ptr()``.
@@ -54,6 +57,12 @@ PROPRIO_MAX_EXTRA = 16
 PROPRIO_STATE = ("filtered_lin_vel", "filtered_ang_vel", "last_root_vel", "last_actions", "last_dof_vel", "noise_tick")
 NOISE_DISTRIBUTIONS = {"none": 0, "gaussian": 1, "uniform": 2}
 NOISE_OPERATIONS = {"additive": 0, "scaling": 1}
+# the terms of :meth:`MotionTracker.feet` in column order (t1.py:627-629, :696-730)
+FEET_TERMS = ("collision", "feet_slip", "feet_vel_z", "feet_roll", "feet_yaw_diff", "feet_yaw_mean", "feet_distance", "feet_swing")
+FEET_MAX_EDGES, FEET_MAX_BODIES = 8, 64
+FEET_DONE_CONTACT = 8                    # the bit of ``done`` of :meth:`MotionTracker.feet`: OR-able with the bits 0 to 2 of :meth:`MotionTracker.proprio`
+FEET_STATE = ("last_feet_pos", "gait_process")
+DEFAULT_FEET = {"force_threshold": 1.0, "contact_clearance": 0.01}          # t1.py:553, :629 and :545
 LINK_SIM = {"body_pos": (0, 3), "body_rot": (3, 4), "body_vel": (7, 3), "body_ang_vel": (10, 3)}      # offset and width in a packed row of 13
 
 
@@ -162,6 +171,7 @@ class MotionTracker:
         self._anchors = False         # whether the per-environment anchors are enabled
         self._control = None          # (R, decimation) once set_control has configured the control half
         self._proprio = None          # (R, extra_cols) once set_proprio has configured the proprioception half
+        self._feet = None             # (num_bodies, num_edges) once set_feet has configured the feet
         if sc is not None or wt is not None:
             self.set_terms(sc, wt)
 
@@ -946,6 +956,252 @@ class MotionTracker:
                "last_root_vel": np.empty((N, 6), np.float32), "last_actions": np.empty((N, R), np.float32),
                "last_dof_vel": np.empty((N, R), np.float32), "noise_tick": np.empty(N, np.uint32)}
         _lib.check(_lib.lib().gmr_motion_tracker_proprio_state(self.handle, *[_lib._ptr(out[k]) for k in PROPRIO_STATE]))
+        return out
+
+    # ---- terrain and feet ---------------------------------------------------------------------------
+    @staticmethod
+    def _terrain_setup(height_field, horizontal_scale, vertical_scale, border_pixels):
+        """the checks of :meth:`set_terrain`, all of them before a device is touched -> ``(field i16[nx,ny] or None, hs, vs, border)``"""
+        hs, vs = float(horizontal_scale), float(vertical_scale)
+        with np.errstate(over="ignore"):
+            if not (np.isfinite(hs) and hs > 0 and np.isfinite(np.float32(hs)) and np.float32(hs) > 0):
+                raise ValueError(f"horizontal_scale = {horizontal_scale} must be positive and finite (in float32 too)")
+        if not (np.isfinite(vs) and vs > 0):
+            raise ValueError(f"vertical_scale = {vertical_scale} must be positive and finite")
+        if int(border_pixels) != border_pixels or not 0 <= int(border_pixels) <= 2 ** 24:
+            raise ValueError(f"border_pixels = {border_pixels}, a whole number of pixels from 0 to 2^24 is needed")
+        field = None
+        if height_field is not None:
+            if not isinstance(height_field, np.ndarray) or height_field.dtype != np.int16:
+                raise TypeError(f"height_field is an int16 array, got {getattr(height_field, 'dtype', type(height_field).__name__)}")
+            if height_field.ndim != 2:
+                raise ValueError(f"height_field has {height_field.ndim} dimensions, [nx, ny] needed")
+            if min(height_field.shape) < 2 or max(height_field.shape) > 2 ** 24:
+                raise ValueError(f"height_field has shape {height_field.shape}, 2 to 2^24 pixels per side are needed")
+            field = np.ascontiguousarray(height_field)
+        return field, hs, vs, int(border_pixels)
+
+    def set_terrain(self, height_field=None, horizontal_scale: float = 1.0, vertical_scale: float = 1.0, border_pixels: int = 0) -> None:
+        """The terrain the heights are taken from: ``height_field int16 [nx, ny]`` (the first index is x, the reference's
+        ``height_field_raw``) with its ``horizontal_scale``, ``vertical_scale`` and ``border_pixels``, or ``None`` for the plane of height
+        0 (the state of a new tracker).  Synchronous: launches in flight keep the field they were given."""
+        from . import _lib
+        field, hs, vs, b = self._terrain_setup(height_field, horizontal_scale, vertical_scale, border_pixels)
+        nx, ny = (0, 0) if field is None else field.shape
+        _lib.check(_lib.lib().gmr_motion_tracker_set_terrain(self.handle, _lib._ptr(field), nx, ny, hs, vs, b))
+
+    def terrain_heights(self, points):
+        """``Terrain.terrain_heights`` of the reference without its host round trip: ``points [M, k]``, k >= 2 (x and y lead) ->
+        ``(heights f32[M], outside)``, the reference's bits inside the field.  A point whose cell leaves the field is clamped to it and
+        counted in ``outside``; a coordinate that is not finite gives NaN and is counted too.  One launch."""
+        from . import _lib
+        p = np.ascontiguousarray(points, dtype=np.float32)
+        if p.ndim != 2 or p.shape[1] < 2:
+            raise ValueError(f"points: shape {p.shape}, (M, k) with k >= 2 needed")
+        h = np.empty(len(p), np.float32)
+        outside = C.c_int32()
+        _lib.check(_lib.lib().gmr_motion_tracker_terrain_heights(self.handle, len(p), _lib._ptr(p), p.shape[1], _lib._ptr(h), C.byref(outside)))
+        return h, int(outside.value)
+
+    def terrain_heights_dev(self, points, n: int, heights, outside=None, stride: int = 3, stream=None) -> None:
+        """:meth:`terrain_heights` on device memory, asynchronous on ``stream``: ONE launch.  Point ``i`` is ``points[i * stride]`` and
+        the float behind it (``stride`` >= 2 floats: 3 for packed positions, 13 for root states); ``heights f32[n]``; the points outside
+        the field are ADDED to ``outside i32[1]``, which the caller has zeroed."""
+        from . import _lib
+        n, stride = int(n), int(stride)
+        if n < 0:
+            raise ValueError(f"terrain_heights_dev: n = {n}")
+        if stride < 2:
+            raise ValueError(f"terrain_heights_dev: stride = {stride} floats, a point has at least x and y")
+        if points is None or heights is None:
+            raise ValueError("terrain_heights_dev: points and heights are needed")
+        ptrs = (_dev_ptr(points, "points", "float32", max((n - 1) * stride + 2, 0)), _dev_ptr(heights, "heights", "float32", n),
+                _dev_ptr(outside, "outside", "int32", 1))
+        _lib.check(_lib.lib().gmr_motion_tracker_terrain_heights_dev(self.handle, n, ptrs[0], stride, ptrs[1], ptrs[2], _lib._s(stream)))
+
+    @staticmethod
+    def _feet_setup(feet_bodies, edge_pos, num_bodies, termination_bodies, penalized_bodies, force_threshold, contact_clearance, feet_distance_ref,
+                    swing_period, scales):
+        """the checks of :meth:`set_feet`, all of them before a device is touched -> a dict of the checked values"""
+        if int(num_bodies) != num_bodies or not 1 <= int(num_bodies) <= 2 ** 16:
+            raise ValueError(f"num_bodies = {num_bodies} outside 1 to 2^16")
+        nb = int(num_bodies)
+        edges = np.ascontiguousarray(edge_pos, dtype=np.float32)
+        if edges.ndim != 2 or edges.shape[1] != 3 or not 1 <= len(edges) <= FEET_MAX_EDGES:
+            raise ValueError(f"edge_pos has shape {edges.shape}, (E, 3) with 1 <= E <= {FEET_MAX_EDGES} needed")
+        if not np.isfinite(edges).all():
+            raise ValueError("edge_pos is not finite")
+        lists = {}
+        for name, a, count in (("feet_bodies", feet_bodies, (2, 2)), ("termination_bodies", termination_bodies, (0, FEET_MAX_BODIES)),
+                               ("penalized_bodies", penalized_bodies, (0, FEET_MAX_BODIES))):
+            a = np.asarray([] if a is None else a)
+            if a.size and not np.issubdtype(a.dtype, np.integer):
+                raise TypeError(f"{name} holds body indices (integers), got {a.dtype}")
+            a = np.ascontiguousarray(a, dtype=np.int64).reshape(-1)
+            if not count[0] <= len(a) <= count[1]:
+                raise ValueError(f"{name} has {len(a)} entries, {count[0]} to {count[1]} needed" if count[0] != count[1] else
+                                 f"{name} has {len(a)} entries, the left and the right foot are needed")
+            if ((a < 0) | (a >= nb)).any():
+                raise ValueError(f"{name} entries lie in [0, {nb}): {a.tolist()}")
+            if name != "feet_bodies" and len(np.unique(a)) != len(a):
+                raise ValueError(f"{name} names a body twice: {a.tolist()}")
+            lists[name] = a.astype(np.int32)
+        scalars = {}
+        for k, v in (("force_threshold", force_threshold), ("contact_clearance", contact_clearance), ("feet_distance_ref", feet_distance_ref),
+                     ("swing_period", swing_period)):
+            v = float(v)
+            with np.errstate(over="ignore"):
+                if not (np.isfinite(v) and np.isfinite(np.float32(v))):
+                    raise ValueError(f"{k} = {v} must be finite in float32")
+            scalars[k] = v
+        if scales is None:
+            sc = np.zeros(len(FEET_TERMS), np.float32)
+        else:
+            if isinstance(scales, dict):
+                unknown = sorted(set(scales) - set(FEET_TERMS))
+                if unknown:
+                    raise KeyError(f"scales: unknown terms {unknown} (known: {list(FEET_TERMS)})")
+                scales = [scales.get(k, 0.0) for k in FEET_TERMS]
+            sc = np.ascontiguousarray(scales, dtype=np.float32).reshape(-1)
+            if len(sc) != len(FEET_TERMS):
+                raise ValueError(f"scales has {len(sc)} entries, there are {len(FEET_TERMS)} terms: {list(FEET_TERMS)}")
+            if not np.isfinite(sc).all():
+                raise ValueError("scales must be finite")
+        return {"edge_pos": edges, "num_bodies": nb, **lists, **scalars, "scales": sc}
+
+    def set_feet(self, feet_bodies, edge_pos, num_bodies: int, *, feet_distance_ref: float, swing_period: float, termination_bodies=(),
+                 penalized_bodies=(), force_threshold: float = DEFAULT_FEET["force_threshold"],
+                 contact_clearance: float = DEFAULT_FEET["contact_clearance"], scales=None) -> None:
+        """Configures the feet: ``feet_bodies`` (left, right) among the ``num_bodies`` rigid bodies of the simulator's tensors,
+        ``edge_pos [E,3]`` (1 to 8 points in the foot's frame, the reference's ``feet_edge_pos``), the bodies whose contact force ends an
+        episode and those it is penalised on (0 to 64 each, distinct), the force threshold and the contact clearance (the reference's 1.0
+        and 0.01), ``feet_distance_ref``, ``swing_period`` and ``scales``, eight numbers or a dict over :data:`FEET_TERMS` that weigh
+        ``total`` (zero, the default: the term stays out).  Allocates ``last_feet_pos`` and ``gait_process`` (zeros).  Synchronous."""
+        from . import _lib
+        c = self._feet_setup(feet_bodies, edge_pos, num_bodies, termination_bodies, penalized_bodies, force_threshold, contact_clearance,
+                             feet_distance_ref, swing_period, scales)
+        cfg = _lib.FeetConfig()
+        cfg.edge_pos, cfg.scales = c["edge_pos"].ctypes.data, c["scales"].ctypes.data
+        cfg.termination_body = c["termination_bodies"].ctypes.data if len(c["termination_bodies"]) else None
+        cfg.penalized_body = c["penalized_bodies"].ctypes.data if len(c["penalized_bodies"]) else None
+        cfg.feet_body[0], cfg.feet_body[1] = int(c["feet_bodies"][0]), int(c["feet_bodies"][1])
+        cfg.num_edges, cfg.nb = len(c["edge_pos"]), c["num_bodies"]
+        cfg.num_termination, cfg.num_penalized = len(c["termination_bodies"]), len(c["penalized_bodies"])
+        for k in ("force_threshold", "contact_clearance", "feet_distance_ref", "swing_period"):
+            setattr(cfg, k, c[k])
+        _lib.check(_lib.lib().gmr_motion_tracker_set_feet(self.handle, C.byref(cfg)))
+        self._feet = (c["num_bodies"], len(c["edge_pos"]))
+
+    def _need_feet(self, what: str):
+        f = getattr(self, "_feet", None)
+        if f is None:
+            raise ValueError(f"{what}: the feet are not set on this tracker, call set_feet() first")
+        return f
+
+    def _feet_counts(self):
+        nb = self._feet[0]
+        ins = {"contact_forces": nb * 3, "root_states": 13, "episode_steps": 1, "gait_frequency": 1}
+        outs = {"feet_pos": 6, "feet_roll": 2, "feet_yaw": 2, "feet_contact": 2, "ground": 1, "gait": 2, "term": len(FEET_TERMS), "total": 1, "done": 1}
+        return ins, outs
+
+    @staticmethod
+    def _feet_bodies(what: str, bodies):
+        """``bodies`` of a feet call -> ``("packed", array) | ("separate", pos, rot)``"""
+        if not isinstance(bodies, dict):
+            raise TypeError(f"{what}: bodies is {{'body_state': [N, nb, 13]}} or {{'body_pos': [N, nb, 3], 'body_rot': [N, nb, 4]}}")
+        if set(bodies) == {"body_state"} and bodies["body_state"] is not None:
+            return ("packed", bodies["body_state"])
+        if set(bodies) == {"body_pos", "body_rot"} and bodies["body_pos"] is not None and bodies["body_rot"] is not None:
+            return ("separate", bodies["body_pos"], bodies["body_rot"])
+        raise TypeError(f"{what}: bodies is either {{'body_state': ..}} or {{'body_pos': .., 'body_rot': ..}}, got {sorted(bodies)}")
+
+    def feet(self, bodies, root_states, contact_forces=None, episode_steps=None, gait_frequency=None) -> Dict[str, np.ndarray]:
+        """The feet half of a step, host arrays in and out: from ``bodies`` -- the simulator's rigid bodies as ``{"body_state": [N, nb,
+        13]}`` (pos, quat xyzw, vel, ang vel) or ``{"body_pos": [N, nb, 3], "body_rot": [N, nb, 4]}`` --, ``root_states [N,13]`` and, each
+        optional, ``contact_forces [N, nb, 3]``, ``episode_steps i32[N]`` and ``gait_frequency [N]`` -- ``feet_pos [N,2,3]``,
+        ``feet_roll``, ``feet_yaw`` ``[N,2]``, ``feet_contact i32[N,2]``, ``ground [N]`` (the terrain height under the root: the
+        ``ground`` of :meth:`proprio`), ``gait [N,2]`` (the cos and sin columns of the observation row), ``term [N,8]`` in the order of
+        :data:`FEET_TERMS`, ``total [N]`` and ``done i32[N]`` (:data:`FEET_DONE_CONTACT` where a termination body is in contact).
+        Without ``contact_forces`` ``collision`` is 0 and stays out of ``total``, and ``done`` is 0.  Then ``last_feet_pos`` rolls over
+        and the gait clock has moved.  One launch; clocks, clips and draw counters stay as they are."""
+        from . import _lib
+        nb, _ = self._need_feet("feet")
+        N = self.num_envs
+        kind = self._feet_bodies("feet", bodies)
+        ls, keep = _lib.TrackerLinksSim(), []
+        if kind[0] == "packed":
+            a = np.ascontiguousarray(kind[1], dtype=np.float32)
+            if a.shape != (N, nb, 13):
+                raise ValueError(f"body_state: shape {a.shape}, {(N, nb, 13)} needed")
+            keep.append(a)
+            ls.body_pos, ls.body_rot, ls.env_stride, ls.body_stride = a.ctypes.data, a.ctypes.data + 12, 13 * nb, 13
+        else:
+            for k, a, w in (("body_pos", kind[1], 3), ("body_rot", kind[2], 4)):
+                a = np.ascontiguousarray(a, dtype=np.float32)
+                if a.shape != (N, nb, w):
+                    raise ValueError(f"{k}: shape {a.shape}, {(N, nb, w)} needed")
+                keep.append(a)
+                setattr(ls, k, a.ctypes.data)
+        st = _lib.FeetIn()
+        if root_states is None:
+            raise ValueError("feet: root_states is needed")
+        for k, a, shape in (("root_states", root_states, (N, 13)), ("contact_forces", contact_forces, (N, nb, 3)), ("gait_frequency", gait_frequency, (N,))):
+            if a is None:
+                continue
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.shape != shape:
+                raise ValueError(f"{k}: shape {a.shape}, {shape} needed")
+            keep.append(a)
+            setattr(st, k, a.ctypes.data)
+        steps = self._per_env_ints(episode_steps, "episode_steps")
+        if steps is not None:
+            st.episode_steps = steps.ctypes.data
+        _, outs = self._feet_counts()
+        shapes = {"feet_pos": (N, 2, 3), "ground": (N,), "total": (N,), "done": (N,)}
+        out = {k: np.empty(shapes.get(k, (N, w)), dtype=np.int32 if k in ("done", "feet_contact") else np.float32) for k, w in outs.items()}
+        table = _lib.FeetOut(**{k: a.ctypes.data for k, a in out.items()})
+        _lib.check(_lib.lib().gmr_motion_tracker_feet(self.handle, C.byref(ls), C.byref(st), C.byref(table)))
+        return out
+
+    def feet_dev(self, bodies, root_states, contact_forces=None, episode_steps=None, gait_frequency=None, stream=None, **outputs) -> None:
+        """:meth:`feet` on device memory, asynchronous on ``stream``: ONE launch.  ``bodies`` is ``{"body_state": array}`` for the packed
+        ``[N, nb, 13]`` tensor or ``{"body_pos": array, "body_rot": array}``; ``outputs`` names whichever of the arrays of :meth:`feet`
+        are wanted (``ground`` goes into :meth:`proprio_dev` as it lies, ``gait`` into its ``extra`` columns); every array is a
+        ``_lib.DeviceBuffer``, a raw address or an object with ``data_ptr()``."""
+        from . import _lib
+        nb, _ = self._need_feet("feet_dev")
+        N = self.num_envs
+        kind = self._feet_bodies("feet_dev", bodies)
+        ins, outs = self._feet_counts()
+        unknown = sorted(set(outputs) - set(outs))
+        if unknown:
+            raise TypeError(f"feet_dev: unknown outputs {unknown}")
+        ls = _lib.TrackerLinksSim()
+        if kind[0] == "packed":
+            p = _dev_ptr(kind[1], "body_state", "float32", N * nb * 13)
+            ls.body_pos, ls.body_rot, ls.env_stride, ls.body_stride = p.value, p.value + 12, 13 * nb, 13
+        else:
+            ls.body_pos = _dev_ptr(kind[1], "body_pos", "float32", N * nb * 3).value
+            ls.body_rot = _dev_ptr(kind[2], "body_rot", "float32", N * nb * 4).value
+        if root_states is None:
+            raise ValueError("feet_dev: root_states is needed")
+        st, table = _lib.FeetIn(), _lib.FeetOut()
+        for k, x in (("root_states", root_states), ("contact_forces", contact_forces), ("episode_steps", episode_steps), ("gait_frequency", gait_frequency)):
+            p = _dev_ptr(x, k, "int32" if k == "episode_steps" else "float32", N * ins[k])
+            setattr(st, k, None if p is None else p.value)
+        for k, x in outputs.items():
+            p = _dev_ptr(x, k, "int32" if k in ("done", "feet_contact") else "float32", N * outs[k])
+            setattr(table, k, None if p is None else p.value)
+        _lib.check(_lib.lib().gmr_motion_tracker_feet_dev(self.handle, C.byref(ls), C.byref(st), C.byref(table), _lib._s(stream)))
+
+    def feet_state(self) -> Optional[Dict[str, np.ndarray]]:
+        """``last_feet_pos f32[N,2,3]`` and ``gait_process f32[N]``, or ``None`` when the feet are not set.  Synchronous."""
+        from . import _lib
+        if getattr(self, "_feet", None) is None:
+            return None
+        N = self.num_envs
+        out = {"last_feet_pos": np.empty((N, 2, 3), np.float32), "gait_process": np.empty(N, np.float32)}
+        _lib.check(_lib.lib().gmr_motion_tracker_feet_state(self.handle, *[_lib._ptr(out[k]) for k in FEET_STATE]))
         return out
 
     # ---- the step ---------------------------------------------------------------------------------------------------------

@@ -956,6 +956,110 @@ int gmr_motion_tracker_proprio_reset(gmr_motion_tracker_t* t, int n, const int32
 int gmr_motion_tracker_proprio_state(gmr_motion_tracker_t* t, float* filtered_lin_vel, float* filtered_ang_vel, float* last_root_vel,
                                      float* last_actions, float* last_dof_vel, uint32_t* noise_tick);
 
+/* ---- N11: tracker feet (terrain heights, feet pose and contacts, the gait clock, contact-force termination, collision and the feet_*
+ * terms of a motion tracker) ---- */
+/* What booster_gym/envs/t1.py::step still did in small launches and host round trips: Terrain.terrain_heights
+ * (booster_gym/utils/terrain.py:101-121, which copies the positions to the host, interpolates in NumPy and uploads the result, several
+ * times per step), _refresh_feet_state (t1.py:529-549), the gait clock (:478, :585-586), the contact-force termination (:553),
+ * collision (:627-629), the seven feet_* terms (:696-730) and the roll-over of last_feet_pos (:495), ONE launch per step.  The statement
+ * of record is tests/feet_mirror.py; this is the same in words.
+ * TERRAIN.  A field int16 [nx][ny], the first index is x (terrain.py:113), with horizontal_scale hs, vertical_scale vs and border_pixels
+ * b; without a field the terrain is the plane: height 0, nothing loaded, nothing counted.  height(px, py), in the reference's NumPy
+ * type promotion:
+ *   x = (float)b + px / (float)hs, y likewise, in float32; x1 = floor(x), x2 = x1 + 1, y1, y2 likewise
+ *   the four weights (x2 - x), (x - x1), (y2 - y), (y - y1) in float64 (exact)
+ *   s = (((x2 - x) * (y2 - y)) * h[x1][y1] + ((x - x1) * (y2 - y)) * h[x2][y1]) + ((x2 - x) * (y - y1)) * h[x1][y2]
+ *       + ((x - x1) * (y - y1)) * h[x2][y2] in float64, the sum from the left; height = (float)(s * vs): ONE rounding to float32
+ * The reference wraps a negative index silently and raises past the edge; here each of the four indices is clamped to the field, the
+ * weights stay as computed, and the point is counted in `outside`.  A coordinate x or y that is not finite gives NaN and is counted too.
+ * FEET.  CONFIGURATION (a host struct that travels with every launch): gmr_feet_config_t.  STATE (device, owned by the tracker, zero after
+ * set_feet): last_feet_pos f32[N][2][3], gait_process f32[N].  Everything below is float32 with one rounding per operation; T = 6.2831855f,
+ * P = 3.1415927f; rem(a, T) = fmodf(a, T), plus T when that is negative (torch's remainder); wrap(a) = rem(a + P, T) - P.
+ * THE STEP, for environment e (pos_f, q_f = (x, y, z, w): position and xyzw quaternion of body feet_body[f], f = 0 left, 1 right):
+ *   feet_pos     = pos_f (:530)
+ *   roll_f       = wrap(rem(atan2f(2 * (w * x + y * z), ((w * w - x * x) - y * y) + z * z), T))            (:532-533)
+ *   yaw_f        = wrap(rem(atan2f(2 * (w * z + x * y), ((w * w + x * x) - y * y) - z * z), T))            (:534)
+ *                  the roll and yaw of isaacgym's get_euler_xyz as restated here; not pinned to isaacgym, which no test machine has
+ *   rot(q, v)    = (v * (2 * (w * w) - 1) + cross(qv, v) * w * 2) + qv * ((qv.x * v.x + qv.y * v.y) + qv.z * v.z) * 2   (quat_rotate,
+ *                  general_motion_retargeting/torch_utils.py:66-75, a + b + c in this grouping; q as given, not normalised)
+ *   edge_fk      = pos_f + rot(q_f, edge_pos[k]); contact_f = any over k of (edge_fk.z - height(edge_fk) < (float)clearance)   (:535-549)
+ *   ground       = height(root position) (:555, :597, :624): what gmr_proprio_in_t takes as `ground`
+ *   gait_process = fmodf(gait_process + (float)dt * gf, 1), gf = gait_frequency[e] or 0 (:478)
+ *   gait         = (cosf(T * gait_process) * on, sinf(T * gait_process) * on), on = gf > 1e-8f ? 1 : 0 (:585-586)
+ *   |F_b|        = sqrtf((F.x * F.x + F.y * F.y) + F.z * F.z) of contact_forces[e][b]
+ *   d_f          = (last_feet_pos_f - pos_f) / (float)dt per component
+ *   base_yaw     = rem(atan2f(..), T) of the root quaternion, the yaw formula above without the wrap (:717, :720)
+ *   term[e]      = collision: the count of penalized bodies with |F_b| > (float)threshold (:629);
+ *                  feet_slip: (s_0 * contact_0 + s_1 * contact_1) * gate, s_f = (d_f.x^2 + d_f.y^2) + d_f.z^2, gate = episode_steps[e] > 1
+ *                  ? 1 : 0, 1 without episode_steps (:698-704); feet_vel_z: d_0.z^2 + d_1.z^2 (:707); feet_roll: roll_0^2 + roll_1^2
+ *                  (:710); feet_yaw_diff: wrap(yaw_1 - yaw_0)^2 (:713); feet_yaw_mean: wrap(base_yaw - m)^2, m = (yaw_0 + yaw_1) / 2 +
+ *                  (|yaw_1 - yaw_0| > P ? P : 0) (:716-717); feet_distance: min(max((float)feet_distance_ref - |cosf(base_yaw) * (pos_1.y -
+ *                  pos_0.y) - sinf(base_yaw) * (pos_1.x - pos_0.x)|, 0), 0.1f), a NaN stays one (:721-725); feet_swing: (left and not
+ *                  contact_0) + (right and not contact_1), left = |gait_process - 0.25f| < (float)(0.5 * swing_period) and gf > 1e-8f,
+ *                  right with 0.75f (:728-730).  Without contact_forces collision is 0 and stays out of the total.
+ *   total[e]     = sum of scale_k * term_k in rising k over the terms with scale_k != 0 whose input is there
+ *   done[e]      = 8 if any termination body has |F_b| > (float)threshold, else 0 (:553; a NaN compares false): bit 3, so that the word
+ *                  can be OR-ed with the bits 0 to 2 of gmr_proprio_out_t.done
+ *   then last_feet_pos = feet_pos (:495).  Nothing is reset on an episode reset, as in the reference.  No clock moves, no draw is made.
+ * Commands, curriculum, kicks and pushes act on the simulator and stay the caller's.  The tracker stays SINGLE-STREAM. */
+#define GMR_FEET_TERMS 8
+#define GMR_FEET_MAX_EDGES 8
+#define GMR_FEET_MAX_BODIES 64
+#define GMR_FEET_DONE_CONTACT 8
+typedef struct {            /* the configuration of set_feet: HOST pointers and values */
+  const float *edge_pos;              /* [num_edges][3] in the foot's frame (t1.py:536)                               */
+  const int32_t *termination_body;    /* [num_termination] distinct, in [0, nb) (t1.py:553)                           */
+  const int32_t *penalized_body;      /* [num_penalized] distinct, in [0, nb) (t1.py:629)                             */
+  const float *scales;                /* [GMR_FEET_TERMS] the weights of the total                                    */
+  int32_t feet_body[2];               /* left, right (t1.py:713-730 hard-codes two feet)                              */
+  int32_t num_edges, nb, num_termination, num_penalized;
+  double force_threshold, contact_clearance;   /* 1.0 (t1.py:553, :629) and 0.01 (:545) in the reference              */
+  double feet_distance_ref, swing_period;
+} gmr_feet_config_t;
+typedef struct {            /* the inputs of a feet call beside the bodies: device pointers (gmr_motion_tracker_feet: host pointers) */
+  const float *contact_forces;        /* [N][nb][3] or NULL: no collision term, done = 0                              */
+  const float *root_states;           /* [N][13] position, xyzw quaternion, world linear and angular velocity         */
+  const int32_t *episode_steps;       /* [N] or NULL: feet_slip is not gated                                          */
+  const float *gait_frequency;        /* [N] or NULL: 0                                                               */
+} gmr_feet_in_t;
+typedef struct {            /* the outputs of a feet call, each an address or NULL */
+  float *feet_pos;                    /* [N][2][3]                                                                    */
+  float *feet_roll, *feet_yaw;        /* [N][2]                                                                       */
+  int32_t *feet_contact;              /* [N][2]                                                                       */
+  float *ground;                      /* [N] terrain height under the root                                            */
+  float *gait;                        /* [N][2] the cos and sin columns of t1.py:585-586                              */
+  float *term;                        /* [N][GMR_FEET_TERMS]                                                          */
+  float *total;                       /* [N]                                                                          */
+  int32_t *done;                      /* [N] 0 or GMR_FEET_DONE_CONTACT                                               */
+} gmr_feet_out_t;
+/* The terrain (terrain.py:30-45, :105-118): height_field int16 [nx][ny] on the HOST, copied to the device, or NULL for the plane (nx and
+ * ny are then not looked at).  GMR_ERR_ARG: a scale that is not finite or not positive (horizontal_scale also as a float32), a negative
+ * border, nx or ny below 2.  Synchronises the device: launches already in flight keep the field they were given. */
+int gmr_motion_tracker_set_terrain(gmr_motion_tracker_t* t, const int16_t* height_field, int nx, int ny, double horizontal_scale,
+                                   double vertical_scale, int border_pixels);
+/* Terrain.terrain_heights (terrain.py:101-121; also what _reset_root_states needs, t1.py:331), ONE launch: point i is (points[i * stride],
+ * points[i * stride + 1]), stride >= 2 in floats; heights f32[M].  _dev ADDS the number of points outside the field to *d_outside (one
+ * int32 the caller has zeroed; may be NULL); the synchronous twin sets *outside (may be NULL) to the count of its call. */
+int gmr_motion_tracker_terrain_heights_dev(gmr_motion_tracker_t* t, int64_t M, const float* d_points, int64_t stride, float* d_heights,
+                                           int32_t* d_outside, void* stream);                      /* asynchronous */
+int gmr_motion_tracker_terrain_heights(gmr_motion_tracker_t* t, int64_t M, const float* points, int64_t stride, float* heights,
+                                       int32_t* outside);
+/* The feet configuration (t1.py:529-549, :553, :627-629, :696-730): 1 <= num_edges <= GMR_FEET_MAX_EDGES finite edge points, feet_body and
+ * the two lists (0 to GMR_FEET_MAX_BODIES entries each, distinct) in [0, nb), the four scalars finite in float32, scales finite.
+ * Allocates last_feet_pos and gait_process and fills them with zeros; synchronises the device.  Launches in flight keep the configuration
+ * they carry. */
+int gmr_motion_tracker_set_feet(gmr_motion_tracker_t* t, const gmr_feet_config_t* cfg);
+/* The step (t1.py:474-478, :495, :529-549, :553, :627-629, :696-730), ONE launch.  bodies: body_pos and body_rot of the simulator's rigid
+ * bodies in the convention of gmr_tracker_links_sim_t -- body b of environment e at base[e * env_stride + b * body_stride], strides in
+ * floats, or both 0 for two contiguous arrays [N][nb][3] and [N][nb][4]; body_vel and body_ang_vel are not read.  GMR_ERR_ARG, before a
+ * device is touched, on a tracker whose feet were never set. */
+int gmr_motion_tracker_feet_dev(gmr_motion_tracker_t* t, const gmr_tracker_links_sim_t* bodies, const gmr_feet_in_t* in,
+                                const gmr_feet_out_t* out, void* stream);                           /* asynchronous */
+int gmr_motion_tracker_feet(gmr_motion_tracker_t* t, const gmr_tracker_links_sim_t* bodies, const gmr_feet_in_t* in,
+                            const gmr_feet_out_t* out);
+/* the two state arrays on the host (last_feet_pos t1.py:495, gait_process :478), either may be NULL; synchronises */
+int gmr_motion_tracker_feet_state(gmr_motion_tracker_t* t, float* last_feet_pos, float* gait_process);
+
 /* ---- multi-GPU: one rank per GPU, ONE broadcast, no per-step collective ------------ */
 /* The reference parallelises over files with mp.Pool on one CPU (scripts/smplx_to_robot_dataset.py:241-242); here
  * streams shard over the ranks of one node and the only data that crosses ranks is the packed robot model + task set.
