@@ -682,7 +682,8 @@ def test_robot_promoted_to_larger_size_class(hip, oracle, tmp_path):
 def test_many_joints_on_their_limits(hip, oracle, src, robot):
     """Targets far from reachable (0.3 m / 40 deg noise, skeleton stretched) put many joints on their limits at
     once: block principal pivoting, multiplier checks and the warm start of the bound sets are exercised in both
-    QP code paths (tree solver over four wavefronts; tree solver in the DPP rows of one wavefront)."""
+    QP code paths (tree solver over four wavefronts; with set_waves(1) the throughput kernel of gmr_ik_wide.hip, which
+    every shipped configuration fits -- the one-wavefront instances of gmr_ik.hip run in test_ik_variants.py)."""
     from general_motion_retargeting_amd import synth
     su = get_setup(src, robot, 1.7)
     human, q0 = synth.make_streams(su.model, su.tt, 24, 12, seed=911, pos_noise=0.30, rot_noise_deg=40.0)
