@@ -332,30 +332,19 @@ int gmr_motion_body_state(const gmr_motion_lib_t* lib, gmr_fk_t* fk, int N, cons
   if (N > 0 && (!clip || !time)) return gmr_fail(GMR_ERR_ARG, "null clip / time");
   const size_t n = (size_t)N, ndof = (size_t)lib->A.ndof;
   const size_t ns = body_sel ? (size_t)(nsel > 0 ? nsel : 0) : (size_t)fk->tree.nbody;
-  void* h[11] = {out->root_pos, out->root_rot, out->root_vel, out->root_ang_vel, out->dof_pos, out->dof_vel,
-                 out->body_pos, out->body_rot, out->body_vel, out->body_ang_vel, out->status};
-  const size_t nb[11] = {n * 12, n * 16, n * 12, n * 12, n * ndof * 4, n * ndof * 4, n * ns * 12, n * ns * 16, n * ns * 12, n * ns * 12, n * 4};
-  void* d[11] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  gmr::Carve c;
-  const size_t o_clip = c.take(n * 4), o_time = c.take(n * 8);
-  size_t off[11];
-  for (int k = 0; k < 11; k++) off[k] = c.take(h[k] ? nb[k] : 0);
-  gmr::DeviceBlock blk;          // device scratch of this call
-  GMR_HIP_TRY(blk.reserve(c.total() + 256));
-  void *d_clip = blk.data() + o_clip, *d_time = blk.data() + o_time;
-  if (N > 0) {
-    GMR_HIP_TRY(hipMemcpy(d_clip, clip, n * 4, hipMemcpyHostToDevice));
-    GMR_HIP_TRY(hipMemcpy(d_time, time, n * 8, hipMemcpyHostToDevice));
-  }
-  for (int k = 0; k < 11; k++)
-    if (h[k]) d[k] = blk.data() + off[k];
-  const gmr_body_state_out_t dev{(float*)d[0], (float*)d[1], (float*)d[2], (float*)d[3], (float*)d[4], (float*)d[5],
-                                 (float*)d[6], (float*)d[7], (float*)d[8], (float*)d[9], (int32_t*)d[10]};
-  const int rc = gmr_motion_body_state_dev(lib, fk, N, (const int32_t*)d_clip, (const double*)d_time, flags, body_sel, nsel, &dev, nullptr);
+  gmr::HostStage st;
+  const int32_t* d_clip;
+  const double* d_time;
+  gmr_body_state_out_t dev = {};
+  st.in(d_clip, clip, n * 4); st.in(d_time, time, n * 8);
+  st.out(dev.root_pos, out->root_pos, n * 12); st.out(dev.root_rot, out->root_rot, n * 16); st.out(dev.root_vel, out->root_vel, n * 12);
+  st.out(dev.root_ang_vel, out->root_ang_vel, n * 12); st.out(dev.dof_pos, out->dof_pos, n * ndof * 4);
+  st.out(dev.dof_vel, out->dof_vel, n * ndof * 4); st.out(dev.body_pos, out->body_pos, n * ns * 12); st.out(dev.body_rot, out->body_rot, n * ns * 16);
+  st.out(dev.body_vel, out->body_vel, n * ns * 12); st.out(dev.body_ang_vel, out->body_ang_vel, n * ns * 12); st.out(dev.status, out->status, n * 4);
+  GMR_STAGE_TRY(st, upload);
+  const int rc = gmr_motion_body_state_dev(lib, fk, N, d_clip, d_time, flags, body_sel, nsel, &dev, nullptr);
   if (rc != GMR_OK) return rc;
-  GMR_HIP_TRY(hipDeviceSynchronize());
-  for (int k = 0; k < 11; k++)
-    if (h[k] && nb[k]) GMR_HIP_TRY(hipMemcpy(h[k], d[k], nb[k], hipMemcpyDeviceToHost));
+  GMR_STAGE_TRY(st, download);
   return GMR_OK;
 }
 

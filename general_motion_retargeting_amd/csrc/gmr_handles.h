@@ -13,6 +13,7 @@
 
 #include "../../include/gmr_hip.h"
 #include "gmr_fk_tree.h"
+#include "gmr_internal.h"
 #include "gmr_link_plan.h"
 #include "gmr_workspace.h"
 
@@ -203,3 +204,23 @@ struct gmr_motion_tracker {
   std::vector<double> clip_w;    // the clip weights as given at creation (empty: uniform)
   std::mutex mu;                 // the tables, and the whole of every synchronous entry point
 };
+
+namespace gmr {
+// the ids outside [0, N) counted so far (synchronous): an entry point that reports them reads it before its launch and after its wait
+inline int tracker_ignored(const gmr_motion_tracker* t, uint32_t* value) {
+  GMR_HIP_TRY(hipMemcpy(value, t->S.ignored, 4, hipMemcpyDeviceToHost));
+  return GMR_OK;
+}
+// the simulator state and the outputs of a step (n environments, r robot dofs) as a synchronous step or link step stages them:
+// h holds the caller's host pointers, d gets the device pointers
+inline void stage_tracker_sim(HostStage& st, gmr_tracker_sim_t& d, const gmr_tracker_sim_t& h, size_t n, size_t r) {
+  st.in(d.base_pos, h.base_pos, n * 12); st.in(d.base_quat, h.base_quat, n * 16); st.in(d.base_lin_vel, h.base_lin_vel, n * 12);
+  st.in(d.base_ang_vel, h.base_ang_vel, n * 12); st.in(d.dof_pos, h.dof_pos, n * r * 4); st.in(d.dof_vel, h.dof_vel, n * r * 4);
+}
+inline void stage_tracker_out(HostStage& st, gmr_tracker_out_t& d, const gmr_tracker_out_t& h, size_t n, size_t r) {
+  st.out(d.ref_root_pos, h.ref_root_pos, n * 12); st.out(d.ref_root_rot, h.ref_root_rot, n * 16); st.out(d.ref_root_vel, h.ref_root_vel, n * 12);
+  st.out(d.ref_root_ang_vel, h.ref_root_ang_vel, n * 12); st.out(d.ref_dof_pos, h.ref_dof_pos, n * r * 4);
+  st.out(d.ref_dof_vel, h.ref_dof_vel, n * r * 4); st.out(d.err, h.err, n * 24); st.out(d.term, h.term, n * 24); st.out(d.total, h.total, n * 4);
+  st.out(d.status, h.status, n * 4); st.out(d.finished, h.finished, n * 4);
+}
+}  // namespace gmr

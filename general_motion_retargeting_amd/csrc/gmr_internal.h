@@ -10,4 +10,6 @@ __attribute__((visibility("hidden"))) int gmr_fail(int code, const char* fmt, ..
     if (_e != hipSuccess) return gmr_fail(GMR_ERR_HIP, "%s: %s", what, hipGetErrorString(_e));      \
   } while (0)
 #define GMR_HIP_TRY(call) GMR_NAMED_HIP_TRY(#call, call)
+// the same for st.upload() / st.download() of a gmr::HostStage: the message names the operation inside that failed
+#define GMR_STAGE_TRY(st, step) GMR_NAMED_HIP_TRY((st).failed(), (st).step())
 #endif

@@ -328,22 +328,16 @@ int gmr_motion_lib_fill(gmr_motion_lib_t* lib, const double* root_pos, const dou
   if (!lib) return gmr_fail(GMR_ERR_ARG, "null motion library");
   if (!root_pos || !root_rot_xyzw || (lib->A.ndof > 0 && !dof_pos)) return gmr_fail(GMR_ERR_ARG, "null input array");
   const size_t B = (size_t)lib->A.B;
-  const size_t n[4] = {B * 24, B * 32, B * lib->A.ndof * 8, local_body_pos ? B * lib->A.nbody * 12 : 0};
-  const void* h[4] = {root_pos, root_rot_xyzw, dof_pos, local_body_pos};
-  void* d[4] = {nullptr, nullptr, nullptr, nullptr};
-  gmr::Carve c;
-  size_t off[4];
-  for (int k = 0; k < 4; k++) off[k] = c.take(n[k]);
-  gmr::DeviceBlock blk;          // device scratch of this call
-  GMR_HIP_TRY(blk.reserve(c.total()));
-  for (int k = 0; k < 4; k++) {
-    if (!n[k] && k != 2) continue;                     // (an absent local_body_pos stays null; dof_pos of no dofs is never read)
-    d[k] = blk.data() + off[k];
-    if (n[k]) GMR_HIP_TRY(hipMemcpy(d[k], h[k], n[k], hipMemcpyHostToDevice));
-  }
-  const int rc = gmr_motion_lib_fill_dev(lib, (const double*)d[0], (const double*)d[1], (const double*)d[2], (const float*)d[3], flags, nullptr);
+  gmr::HostStage st;
+  const double *d_root_pos, *d_root_rot, *d_dof_pos;
+  const float* d_body;
+  st.in(d_root_pos, root_pos, B * 24); st.in(d_root_rot, root_rot_xyzw, B * 32);
+  st.in(d_dof_pos, dof_pos, B * lib->A.ndof * 8);      // (of no dofs: an address that is never read)
+  st.in(d_body, local_body_pos, B * lib->A.nbody * 12);
+  GMR_STAGE_TRY(st, upload);
+  const int rc = gmr_motion_lib_fill_dev(lib, d_root_pos, d_root_rot, d_dof_pos, d_body, flags, nullptr);
   if (rc != GMR_OK) return rc;
-  GMR_HIP_TRY(hipDeviceSynchronize());
+  GMR_STAGE_TRY(st, download);
   return GMR_OK;
 }
 
@@ -386,26 +380,20 @@ int gmr_motion_sample(const gmr_motion_lib_t* lib, int N, const int32_t* clip, c
   if (N == 0) return GMR_OK;
   if (!clip || !time) return gmr_fail(GMR_ERR_ARG, "null clip / time");
   const size_t n = (size_t)N, ndof = (size_t)lib->A.ndof, nb3 = (size_t)lib->A.nbody * 3;
-  void* h[8] = {root_pos, root_rot, root_vel, root_ang_vel, dof_pos, dof_vel, local_body_pos, status};
-  const size_t nb[8] = {n * 12, n * 16, n * 12, n * 12, n * ndof * 4, n * ndof * 4, n * nb3 * 4, n * 4};
-  void* d[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  gmr::Carve c;
-  const size_t o_clip = c.take(n * 4), o_time = c.take(n * 8);
-  size_t off[8];
-  for (int k = 0; k < 8; k++) off[k] = c.take(h[k] ? nb[k] : 0);
-  gmr::DeviceBlock blk;          // device scratch of this call
-  GMR_HIP_TRY(blk.reserve(c.total()));
-  void *d_clip = blk.data() + o_clip, *d_time = blk.data() + o_time;
-  GMR_HIP_TRY(hipMemcpy(d_clip, clip, n * 4, hipMemcpyHostToDevice));
-  GMR_HIP_TRY(hipMemcpy(d_time, time, n * 8, hipMemcpyHostToDevice));
-  for (int k = 0; k < 8; k++)
-    if (h[k]) d[k] = blk.data() + off[k];
-  const int rc = gmr_motion_sample_dev(lib, N, (const int32_t*)d_clip, (const double*)d_time, flags, (float*)d[0], (float*)d[1], (float*)d[2],
-                                       (float*)d[3], (float*)d[4], (float*)d[5], (float*)d[6], (int32_t*)d[7], nullptr);
+  gmr::HostStage st;
+  const int32_t* d_clip;
+  const double* d_time;
+  float *d_root_pos, *d_root_rot, *d_root_vel, *d_root_ang_vel, *d_dof_pos, *d_dof_vel, *d_body;
+  int32_t* d_status;
+  st.in(d_clip, clip, n * 4); st.in(d_time, time, n * 8);
+  st.out(d_root_pos, root_pos, n * 12); st.out(d_root_rot, root_rot, n * 16); st.out(d_root_vel, root_vel, n * 12);
+  st.out(d_root_ang_vel, root_ang_vel, n * 12); st.out(d_dof_pos, dof_pos, n * ndof * 4); st.out(d_dof_vel, dof_vel, n * ndof * 4);
+  st.out(d_body, local_body_pos, n * nb3 * 4); st.out(d_status, status, n * 4);
+  GMR_STAGE_TRY(st, upload);
+  const int rc = gmr_motion_sample_dev(lib, N, d_clip, d_time, flags, d_root_pos, d_root_rot, d_root_vel, d_root_ang_vel, d_dof_pos, d_dof_vel,
+                                       d_body, d_status, nullptr);
   if (rc != GMR_OK) return rc;
-  GMR_HIP_TRY(hipDeviceSynchronize());
-  for (int k = 0; k < 8; k++)
-    if (h[k] && nb[k]) GMR_HIP_TRY(hipMemcpy(h[k], d[k], nb[k], hipMemcpyDeviceToHost));
+  GMR_STAGE_TRY(st, download);
   return GMR_OK;
 }
 

@@ -239,12 +239,6 @@ static int tracker_step_launch(gmr_motion_tracker* t, const TrackerState& S, con
   return GMR_OK;
 }
 
-// the ids outside [0, N) counted so far (synchronous)
-static int tracker_ignored(const gmr_motion_tracker* t, uint32_t* value) {
-  GMR_HIP_TRY(hipMemcpy(value, t->S.ignored, 4, hipMemcpyDeviceToHost));
-  return GMR_OK;
-}
-
 }  // namespace gmr
 
 // ---- C-ABI (include/gmr_hip.h, "motion tracker") ----------------------------------------------------------------------------
@@ -393,21 +387,16 @@ int gmr_motion_tracker_assign(gmr_motion_tracker_t* t, int n, const int32_t* env
   if (!clip || !time) return gmr_fail(GMR_ERR_ARG, "null clip / time");
   std::lock_guard<std::mutex> g(t->mu);
   const size_t nb = (size_t)n * 4;
-  gmr::Carve cv;
-  const size_t o_ids = cv.take(env_ids ? nb : 0), o_clip = cv.take(nb), o_time = cv.take(nb);
-  gmr::DeviceBlock blk;          // device scratch of this call
-  GMR_HIP_TRY(blk.reserve(cv.total()));
-  char* d = blk.data();
-  if (env_ids) GMR_HIP_TRY(hipMemcpy(d + o_ids, env_ids, nb, hipMemcpyHostToDevice));
-  GMR_HIP_TRY(hipMemcpy(d + o_clip, clip, nb, hipMemcpyHostToDevice));
-  GMR_HIP_TRY(hipMemcpy(d + o_time, time, nb, hipMemcpyHostToDevice));
+  gmr::HostStage st;
+  const int32_t *d_ids, *d_clip;
+  const float* d_time;
+  st.in(d_ids, env_ids, nb); st.in(d_clip, clip, nb); st.in(d_time, time, nb);
+  GMR_STAGE_TRY(st, upload);
   uint32_t before = 0, after = 0;
   int rc = gmr::tracker_ignored(t, &before);
-  if (rc == GMR_OK)
-    rc = gmr_motion_tracker_assign_dev(t, n, env_ids ? (const int32_t*)(d + o_ids) : nullptr, (const int32_t*)(d + o_clip),
-                                       (const float*)(d + o_time), nullptr);
+  if (rc == GMR_OK) rc = gmr_motion_tracker_assign_dev(t, n, d_ids, d_clip, d_time, nullptr);
   if (rc != GMR_OK) return rc;
-  GMR_HIP_TRY(hipDeviceSynchronize());
+  GMR_STAGE_TRY(st, download);
   if ((rc = gmr::tracker_ignored(t, &after)) != GMR_OK) return rc;
   if (ignored) *ignored = (int)(after - before);
   return GMR_OK;
@@ -419,16 +408,15 @@ int gmr_motion_tracker_reset(gmr_motion_tracker_t* t, int n, const int32_t* env_
   if (n < 0 || n > (1 << 26)) return gmr_fail(GMR_ERR_ARG, "n = %d out of range", n);
   if (env_ids && n == 0) return GMR_OK;
   std::lock_guard<std::mutex> g(t->mu);
-  gmr::DeviceBlock blk;          // device scratch of this call
-  if (env_ids) {
-    GMR_HIP_TRY(blk.reserve((size_t)n * 4));
-    GMR_HIP_TRY(hipMemcpy(blk.data(), env_ids, (size_t)n * 4, hipMemcpyHostToDevice));
-  }
+  gmr::HostStage st;
+  const int32_t* d_ids;
+  st.in(d_ids, env_ids, (size_t)n * 4);
+  GMR_STAGE_TRY(st, upload);
   uint32_t before = 0, after = 0;
   int rc = gmr::tracker_ignored(t, &before);
-  if (rc == GMR_OK) rc = gmr_motion_tracker_reset_dev(t, n, env_ids ? (const int32_t*)blk.data() : nullptr, resample, lo, hi, nullptr);
+  if (rc == GMR_OK) rc = gmr_motion_tracker_reset_dev(t, n, d_ids, resample, lo, hi, nullptr);
   if (rc != GMR_OK) return rc;
-  GMR_HIP_TRY(hipDeviceSynchronize());
+  GMR_STAGE_TRY(st, download);
   if ((rc = gmr::tracker_ignored(t, &after)) != GMR_OK) return rc;
   if (ignored) *ignored = (int)(after - before);
   return GMR_OK;
@@ -439,37 +427,15 @@ int gmr_motion_tracker_step(gmr_motion_tracker_t* t, const gmr_tracker_sim_t* si
   if (!out) return gmr_fail(GMR_ERR_ARG, "null output table");
   std::lock_guard<std::mutex> g(t->mu);
   const size_t n = (size_t)t->N, r = (size_t)t->tab.R;
-  const void* hs[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  if (sim) {
-    hs[0] = sim->base_pos; hs[1] = sim->base_quat; hs[2] = sim->base_lin_vel;
-    hs[3] = sim->base_ang_vel; hs[4] = sim->dof_pos; hs[5] = sim->dof_vel;
-  }
-  const size_t ns[6] = {n * 12, n * 16, n * 12, n * 12, n * r * 4, n * r * 4};
-  void* ho[11] = {out->ref_root_pos, out->ref_root_rot, out->ref_root_vel, out->ref_root_ang_vel, out->ref_dof_pos, out->ref_dof_vel,
-                  out->err, out->term, out->total, out->status, out->finished};
-  const size_t no[11] = {n * 12, n * 16, n * 12, n * 12, n * r * 4, n * r * 4, n * 24, n * 24, n * 4, n * 4, n * 4};
-  gmr::Carve cv;
-  size_t os[6], oo[11];
-  for (int k = 0; k < 6; k++) os[k] = cv.take(hs[k] ? ns[k] : 0);
-  for (int k = 0; k < 11; k++) oo[k] = cv.take(ho[k] ? no[k] : 0);
-  gmr::DeviceBlock blk;          // device scratch of this call
-  GMR_HIP_TRY(blk.reserve(cv.total() + 256));
-  char* d = blk.data();
-  const float* ds[6];
-  void* dv[11];
-  for (int k = 0; k < 6; k++) {
-    ds[k] = hs[k] ? (const float*)(d + os[k]) : nullptr;
-    if (hs[k]) GMR_HIP_TRY(hipMemcpy(d + os[k], hs[k], ns[k], hipMemcpyHostToDevice));
-  }
-  for (int k = 0; k < 11; k++) dv[k] = ho[k] ? d + oo[k] : nullptr;
-  const gmr_tracker_sim_t dsim{ds[0], ds[1], ds[2], ds[3], ds[4], ds[5]};
-  const gmr_tracker_out_t dout{(float*)dv[0], (float*)dv[1], (float*)dv[2], (float*)dv[3], (float*)dv[4], (float*)dv[5],
-                               (float*)dv[6], (float*)dv[7], (float*)dv[8], (int32_t*)dv[9], (int32_t*)dv[10]};
+  gmr::HostStage st;
+  gmr_tracker_sim_t dsim = {};
+  gmr_tracker_out_t dout = {};
+  if (sim) gmr::stage_tracker_sim(st, dsim, *sim, n, r);
+  gmr::stage_tracker_out(st, dout, *out, n, r);
+  GMR_STAGE_TRY(st, upload);
   const int rc = gmr::tracker_step_launch(t, t->S, t->tab, sim ? &dsim : nullptr, &dout, nullptr);
   if (rc != GMR_OK) return rc;
-  GMR_HIP_TRY(hipDeviceSynchronize());
-  for (int k = 0; k < 11; k++)
-    if (ho[k]) GMR_HIP_TRY(hipMemcpy(ho[k], dv[k], no[k], hipMemcpyDeviceToHost));
+  GMR_STAGE_TRY(st, download);
   return GMR_OK;
 }
 

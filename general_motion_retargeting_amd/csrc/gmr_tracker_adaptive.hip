@@ -370,23 +370,17 @@ int gmr_motion_tracker_reset_done(gmr_motion_tracker_t* t, int n, const int32_t*
   if (ignored) *ignored = 0;
   if (n < 0 || n > (1 << 26)) return gmr_fail(GMR_ERR_ARG, "n = %d out of range", n);
   std::lock_guard<std::mutex> g(t->mu);
-  gmr::DeviceBlock blk;          // device scratch of this call
   const size_t nb = (size_t)n * 4;
-  gmr::Carve cv;
-  const size_t o_ids = cv.take(env_ids ? nb : 0), o_done = cv.take(done ? nb : 0), o_failed = cv.take(failed ? nb : 0);
-  GMR_HIP_TRY(blk.reserve(cv.total() + 256));
-  char* d = blk.data();
-  if (env_ids && nb) GMR_HIP_TRY(hipMemcpy(d + o_ids, env_ids, nb, hipMemcpyHostToDevice));
-  if (done && nb) GMR_HIP_TRY(hipMemcpy(d + o_done, done, nb, hipMemcpyHostToDevice));
-  if (failed && nb) GMR_HIP_TRY(hipMemcpy(d + o_failed, failed, nb, hipMemcpyHostToDevice));
+  gmr::HostStage st;
+  const int32_t *d_ids, *d_done, *d_failed;
+  st.in(d_ids, env_ids, nb); st.in(d_done, done, nb); st.in(d_failed, failed, nb);
+  GMR_STAGE_TRY(st, upload);
   uint32_t before = 0, after = 0;
-  GMR_HIP_TRY(hipMemcpy(&before, t->S.ignored, 4, hipMemcpyDeviceToHost));
-  const int rc = gmr::reset_done_launch(t, t->S, t->bins.fail_now, n, env_ids ? (const int32_t*)(d + o_ids) : nullptr,
-                                        done ? (const int32_t*)(d + o_done) : nullptr, failed ? (const int32_t*)(d + o_failed) : nullptr, resample,
-                                        lo, hi, nullptr);
+  int rc = gmr::tracker_ignored(t, &before);
+  if (rc == GMR_OK) rc = gmr::reset_done_launch(t, t->S, t->bins.fail_now, n, d_ids, d_done, d_failed, resample, lo, hi, nullptr);
   if (rc != GMR_OK) return rc;
-  GMR_HIP_TRY(hipDeviceSynchronize());
-  GMR_HIP_TRY(hipMemcpy(&after, t->S.ignored, 4, hipMemcpyDeviceToHost));
+  GMR_STAGE_TRY(st, download);
+  if ((rc = gmr::tracker_ignored(t, &after)) != GMR_OK) return rc;
   if (ignored) *ignored = (int)(after - before);
   return GMR_OK;
 }

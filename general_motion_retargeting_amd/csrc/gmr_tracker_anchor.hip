@@ -221,21 +221,17 @@ int gmr_motion_tracker_set_anchor(gmr_motion_tracker_t* t, int n, const int32_t*
     for (size_t i = 0; i < (size_t)n; i++) gmr::anchor_half_angle(yaw[i], &zw[i * 2], &zw[i * 2 + 1]);
   }
   const size_t nn = (size_t)n;
-  gmr::Carve cv;
-  const size_t o_ids = cv.take(env_ids ? nn * 4 : 0), o_pos = cv.take(pos ? nn * 12 : 0), o_yaw = cv.take(yaw ? nn * 8 : 0);
-  gmr::DeviceBlock blk;          // device scratch of this call
-  GMR_HIP_TRY(blk.reserve(cv.total() + 256));
-  char* d = blk.data();
-  if (env_ids) GMR_HIP_TRY(hipMemcpy(d + o_ids, env_ids, nn * 4, hipMemcpyHostToDevice));
-  if (pos) GMR_HIP_TRY(hipMemcpy(d + o_pos, pos, nn * 12, hipMemcpyHostToDevice));
-  if (yaw) GMR_HIP_TRY(hipMemcpy(d + o_yaw, zw.data(), nn * 8, hipMemcpyHostToDevice));
+  gmr::HostStage st;
+  const int32_t* d_ids;
+  const float *d_pos, *d_yaw;
+  st.in(d_ids, env_ids, nn * 4); st.in(d_pos, pos, nn * 12); st.in(d_yaw, yaw ? zw.data() : nullptr, nn * 8);
+  GMR_STAGE_TRY(st, upload);
   uint32_t before = 0, after = 0;
-  GMR_HIP_TRY(hipMemcpy(&before, t->S.ignored, 4, hipMemcpyDeviceToHost));
-  rc = gmr::anchor_set_launch(t, t->S, n, env_ids ? (const int32_t*)(d + o_ids) : nullptr, pos ? (const float*)(d + o_pos) : nullptr,
-                              yaw ? (const float*)(d + o_yaw) : nullptr, 1, nullptr);
+  if ((rc = gmr::tracker_ignored(t, &before)) != GMR_OK) return rc;
+  rc = gmr::anchor_set_launch(t, t->S, n, d_ids, d_pos, d_yaw, 1, nullptr);
   if (rc != GMR_OK) return rc;
-  GMR_HIP_TRY(hipDeviceSynchronize());
-  GMR_HIP_TRY(hipMemcpy(&after, t->S.ignored, 4, hipMemcpyDeviceToHost));
+  GMR_STAGE_TRY(st, download);
+  if ((rc = gmr::tracker_ignored(t, &after)) != GMR_OK) return rc;
   if (ignored) *ignored = (int)(after - before);
   return GMR_OK;
 }
@@ -268,22 +264,17 @@ int gmr_motion_tracker_anchor_to_root(gmr_motion_tracker_t* t, int n, const int3
   if (rc != GMR_OK) return rc;
   if (n == 0) return GMR_OK;
   const size_t nn = (size_t)n;
-  gmr::Carve cv;
-  const size_t o_ids = cv.take(env_ids ? nn * 4 : 0), o_mask = cv.take(mask ? nn * 4 : 0), o_pos = cv.take(nn * 12), o_quat = cv.take(nn * 16);
-  gmr::DeviceBlock blk;          // device scratch of this call
-  GMR_HIP_TRY(blk.reserve(cv.total() + 256));
-  char* d = blk.data();
-  if (env_ids) GMR_HIP_TRY(hipMemcpy(d + o_ids, env_ids, nn * 4, hipMemcpyHostToDevice));
-  if (mask) GMR_HIP_TRY(hipMemcpy(d + o_mask, mask, nn * 4, hipMemcpyHostToDevice));
-  GMR_HIP_TRY(hipMemcpy(d + o_pos, root_pos, nn * 12, hipMemcpyHostToDevice));
-  GMR_HIP_TRY(hipMemcpy(d + o_quat, root_quat, nn * 16, hipMemcpyHostToDevice));
+  gmr::HostStage st;
+  const int32_t *d_ids, *d_mask;
+  const float *d_pos, *d_quat;
+  st.in(d_ids, env_ids, nn * 4); st.in(d_mask, mask, nn * 4); st.in(d_pos, root_pos, nn * 12); st.in(d_quat, root_quat, nn * 16);
+  GMR_STAGE_TRY(st, upload);
   uint32_t before = 0, after = 0;
-  GMR_HIP_TRY(hipMemcpy(&before, t->S.ignored, 4, hipMemcpyDeviceToHost));
-  rc = gmr::anchor_root_launch(t, t->S, n, env_ids ? (const int32_t*)(d + o_ids) : nullptr, mask ? (const int32_t*)(d + o_mask) : nullptr,
-                               (const float*)(d + o_pos), (const float*)(d + o_quat), flags, nullptr);
+  if ((rc = gmr::tracker_ignored(t, &before)) != GMR_OK) return rc;
+  rc = gmr::anchor_root_launch(t, t->S, n, d_ids, d_mask, d_pos, d_quat, flags, nullptr);
   if (rc != GMR_OK) return rc;
-  GMR_HIP_TRY(hipDeviceSynchronize());
-  GMR_HIP_TRY(hipMemcpy(&after, t->S.ignored, 4, hipMemcpyDeviceToHost));
+  GMR_STAGE_TRY(st, download);
+  if ((rc = gmr::tracker_ignored(t, &after)) != GMR_OK) return rc;
   if (ignored) *ignored = (int)(after - before);
   return GMR_OK;
 }

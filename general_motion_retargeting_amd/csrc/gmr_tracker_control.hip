@@ -366,22 +366,17 @@ int gmr_motion_tracker_targets(gmr_motion_tracker_t* t, const float* actions, co
   if (rc != GMR_OK) return rc;
   if (actions_clipped && !actions) return gmr_fail(GMR_ERR_ARG, "actions_clipped needs actions");
   const size_t n = (size_t)t->N, nr = n * (size_t)V.ctl.R * 4;
-  gmr::Carve cv;
-  const size_t o_act = cv.take(actions ? nr : 0), o_steps = cv.take(episode_steps ? n * 4 : 0), o_tg = cv.take(dof_targets ? nr : 0),
-               o_clip = cv.take(actions_clipped ? nr : 0), o_st = cv.take(status ? n * 4 : 0);
-  gmr::DeviceBlock blk;          // device scratch of this call
-  GMR_HIP_TRY(blk.reserve(cv.total() + 256));
-  char* d = blk.data();
-  if (actions) GMR_HIP_TRY(hipMemcpy(d + o_act, actions, nr, hipMemcpyHostToDevice));
-  if (episode_steps) GMR_HIP_TRY(hipMemcpy(d + o_steps, episode_steps, n * 4, hipMemcpyHostToDevice));
-  rc = gmr::targets_launch(t, V, actions ? (const float*)(d + o_act) : nullptr, episode_steps ? (const int32_t*)(d + o_steps) : nullptr,
-                           dof_targets ? (float*)(d + o_tg) : nullptr, actions_clipped ? (float*)(d + o_clip) : nullptr,
-                           status ? (int32_t*)(d + o_st) : nullptr, nullptr);
+  gmr::HostStage st;
+  const float* d_actions;
+  const int32_t* d_steps;
+  float *d_targets, *d_clipped;
+  int32_t* d_status;
+  st.in(d_actions, actions, nr); st.in(d_steps, episode_steps, n * 4);
+  st.out(d_targets, dof_targets, nr); st.out(d_clipped, actions_clipped, nr); st.out(d_status, status, n * 4);
+  GMR_STAGE_TRY(st, upload);
+  rc = gmr::targets_launch(t, V, d_actions, d_steps, d_targets, d_clipped, d_status, nullptr);
   if (rc != GMR_OK) return rc;
-  GMR_HIP_TRY(hipDeviceSynchronize());
-  if (dof_targets) GMR_HIP_TRY(hipMemcpy(dof_targets, d + o_tg, nr, hipMemcpyDeviceToHost));
-  if (actions_clipped) GMR_HIP_TRY(hipMemcpy(actions_clipped, d + o_clip, nr, hipMemcpyDeviceToHost));
-  if (status) GMR_HIP_TRY(hipMemcpy(status, d + o_st, n * 4, hipMemcpyDeviceToHost));
+  GMR_STAGE_TRY(st, download);
   return GMR_OK;
 }
 
@@ -408,21 +403,17 @@ int gmr_motion_tracker_hold(gmr_motion_tracker_t* t, int n, const int32_t* env_i
   if (n == 0) return GMR_OK;
   if (!dof_pos) return gmr_fail(GMR_ERR_ARG, "null dof_pos");
   const size_t nn = (size_t)n, nr = nn * (size_t)V.ctl.R * 4;
-  gmr::Carve cv;
-  const size_t o_ids = cv.take(env_ids ? nn * 4 : 0), o_mask = cv.take(mask ? nn * 4 : 0), o_pos = cv.take(nr);
-  gmr::DeviceBlock blk;          // device scratch of this call
-  GMR_HIP_TRY(blk.reserve(cv.total() + 256));
-  char* d = blk.data();
-  if (env_ids) GMR_HIP_TRY(hipMemcpy(d + o_ids, env_ids, nn * 4, hipMemcpyHostToDevice));
-  if (mask) GMR_HIP_TRY(hipMemcpy(d + o_mask, mask, nn * 4, hipMemcpyHostToDevice));
-  GMR_HIP_TRY(hipMemcpy(d + o_pos, dof_pos, nr, hipMemcpyHostToDevice));
+  gmr::HostStage st;
+  const int32_t *d_ids, *d_mask;
+  const float* d_pos;
+  st.in(d_ids, env_ids, nn * 4); st.in(d_mask, mask, nn * 4); st.in(d_pos, dof_pos, nr);
+  GMR_STAGE_TRY(st, upload);
   uint32_t before = 0, after = 0;
-  GMR_HIP_TRY(hipMemcpy(&before, t->S.ignored, 4, hipMemcpyDeviceToHost));
-  rc = gmr::hold_launch(t, V, n, env_ids ? (const int32_t*)(d + o_ids) : nullptr, mask ? (const int32_t*)(d + o_mask) : nullptr,
-                        (const float*)(d + o_pos), nullptr);
+  if ((rc = gmr::tracker_ignored(t, &before)) != GMR_OK) return rc;
+  rc = gmr::hold_launch(t, V, n, d_ids, d_mask, d_pos, nullptr);
   if (rc != GMR_OK) return rc;
-  GMR_HIP_TRY(hipDeviceSynchronize());
-  GMR_HIP_TRY(hipMemcpy(&after, t->S.ignored, 4, hipMemcpyDeviceToHost));
+  GMR_STAGE_TRY(st, download);
+  if ((rc = gmr::tracker_ignored(t, &after)) != GMR_OK) return rc;
   if (ignored) *ignored = (int)(after - before);
   return GMR_OK;
 }
@@ -449,27 +440,20 @@ int gmr_motion_tracker_torques(gmr_motion_tracker_t* t, int substep, const float
   if (rc != GMR_OK) return rc;
   const size_t n = (size_t)t->N, r = (size_t)V.ctl.R, nr = n * r * 4;
   const size_t gain = act->per_env ? nr : r * 4;
-  const void* hs[8] = {dof_targets, dof_pos, dof_vel, act->stiffness, act->damping, act->friction, act->torque_limit, delay_steps};
-  const size_t ns[8] = {nr, nr, nr, gain, gain, gain, r * 4, n * 4};
-  gmr::Carve cv;
-  size_t os[8];
-  for (int k = 0; k < 8; k++) os[k] = cv.take(hs[k] ? ns[k] : 0);
-  const size_t o_tau = cv.take(nr), o_mean = cv.take(mean_torques ? nr : 0);
-  gmr::DeviceBlock blk;          // device scratch of this call
-  GMR_HIP_TRY(blk.reserve(cv.total() + 256));
-  char* d = blk.data();
-  const void* ds[8];
-  for (int k = 0; k < 8; k++) {
-    ds[k] = hs[k] ? d + os[k] : nullptr;
-    if (hs[k]) GMR_HIP_TRY(hipMemcpy(d + os[k], hs[k], ns[k], hipMemcpyHostToDevice));
-  }
-  const gmr_tracker_actuator_t dact{(const float*)ds[3], (const float*)ds[4], (const float*)ds[5], (const float*)ds[6], act->per_env};
-  rc = gmr::torques_launch(t, V, substep, (const float*)ds[0], (const float*)ds[1], (const float*)ds[2], &dact, (const int32_t*)ds[7],
-                           (float*)(d + o_tau), mean_torques ? (float*)(d + o_mean) : nullptr, nullptr);
+  gmr::HostStage st;
+  const float *d_targets, *d_pos, *d_vel;
+  gmr_tracker_actuator_t dact = *act;
+  const int32_t* d_delay;
+  float *d_tau, *d_mean;
+  st.in(d_targets, dof_targets, nr); st.in(d_pos, dof_pos, nr); st.in(d_vel, dof_vel, nr); st.in(dact.stiffness, act->stiffness, gain);
+  st.in(dact.damping, act->damping, gain); st.in(dact.friction, act->friction, gain); st.in(dact.torque_limit, act->torque_limit, r * 4);
+  st.in(d_delay, delay_steps, n * 4);
+  st.out(d_tau, dof_torques, nr);
+  st.out(d_mean, mean_torques, nr, substep == V.ctl.M - 1);      // (the mean of an environment step: there after its last substep)
+  GMR_STAGE_TRY(st, upload);
+  rc = gmr::torques_launch(t, V, substep, d_targets, d_pos, d_vel, &dact, d_delay, d_tau, d_mean, nullptr);
   if (rc != GMR_OK) return rc;
-  GMR_HIP_TRY(hipDeviceSynchronize());
-  GMR_HIP_TRY(hipMemcpy(dof_torques, d + o_tau, nr, hipMemcpyDeviceToHost));
-  if (mean_torques && substep == V.ctl.M - 1) GMR_HIP_TRY(hipMemcpy(mean_torques, d + o_mean, nr, hipMemcpyDeviceToHost));
+  GMR_STAGE_TRY(st, download);
   return GMR_OK;
 }
 

@@ -361,18 +361,18 @@ int gmr_motion_tracker_terrain_heights(gmr_motion_tracker_t* t, int64_t M, const
   if (rc != GMR_OK) return rc;
   if (M == 0) return GMR_OK;
   const size_t m = (size_t)M, nin = ((m - 1) * (size_t)stride + 2) * 4;
-  gmr::Carve cv;
-  const size_t o_in = cv.take(nin), o_h = cv.take(m * 4), o_c = cv.take(4);
-  gmr::DeviceBlock blk;          // device scratch of this call
-  GMR_HIP_TRY(blk.reserve(cv.total() + 256));
-  char* d = blk.data();
-  GMR_HIP_TRY(hipMemcpy(d + o_in, points, nin, hipMemcpyHostToDevice));
-  GMR_HIP_TRY(hipMemset(d + o_c, 0, 4));
-  rc = gmr::heights_launch(t->terrain, (long long)M, (const float*)(d + o_in), (long long)stride, (float*)(d + o_h), (int32_t*)(d + o_c), nullptr);
+  gmr::HostStage st;
+  const float* d_points;
+  float* d_heights;
+  int32_t *d_count, count = 0;
+  st.in(d_points, points, nin);
+  st.out(d_heights, heights, m * 4); st.out(d_count, &count, 4, outside != nullptr);
+  GMR_STAGE_TRY(st, upload);
+  GMR_HIP_TRY(hipMemset(d_count, 0, 4));
+  rc = gmr::heights_launch(t->terrain, (long long)M, d_points, (long long)stride, d_heights, d_count, nullptr);
   if (rc != GMR_OK) return rc;
-  GMR_HIP_TRY(hipDeviceSynchronize());
-  GMR_HIP_TRY(hipMemcpy(heights, d + o_h, m * 4, hipMemcpyDeviceToHost));
-  if (outside) GMR_HIP_TRY(hipMemcpy(outside, d + o_c, 4, hipMemcpyDeviceToHost));
+  GMR_STAGE_TRY(st, download);
+  if (outside) *outside = count;
   return GMR_OK;
 }
 
@@ -449,45 +449,22 @@ int gmr_motion_tracker_feet(gmr_motion_tracker_t* t, const gmr_tracker_links_sim
   int rc = gmr::feet_check(V.tab, bodies, in, out, es, bs);
   if (rc != GMR_OK) return rc;
   const size_t n = (size_t)t->N, nb = (size_t)V.tab.nb;
-  // inputs: the two body arrays (their extent from the strides; one copy of their hull when they interleave in one tensor), then the rest
-  const void* hs[6] = {bodies->body_pos, bodies->body_rot, in->contact_forces, in->root_states, in->episode_steps, in->gait_frequency};
-  const size_t ns[6] = {4 * ((n - 1) * (size_t)es[0] + (nb - 1) * (size_t)bs[0] + 3), 4 * ((n - 1) * (size_t)es[1] + (nb - 1) * (size_t)bs[1] + 4),
-                        n * nb * 12, n * 52, n * 4, n * 4};
-  const char* lo = (const char*)hs[0] < (const char*)hs[1] ? (const char*)hs[0] : (const char*)hs[1];
-  const char* e0 = (const char*)hs[0] + ns[0];
-  const char* e1 = (const char*)hs[1] + ns[1];
-  const char* hi = e0 > e1 ? e0 : e1;
-  const bool hull = (size_t)(hi - lo) <= ns[0] + ns[1];
-  void* ho[9] = {out->feet_pos, out->feet_roll, out->feet_yaw, out->feet_contact, out->ground, out->gait, out->term, out->total, out->done};
-  const size_t no[9] = {n * 24, n * 8, n * 8, n * 8, n * 4, n * 8, n * GMR_FEET_TERMS * 4, n * 4, n * 4};
-  gmr::Carve cv;
-  size_t os[6], oo[9];
-  const size_t o_hull = cv.take(hull ? (size_t)(hi - lo) : 0);
-  for (int k = 0; k < 6; k++) os[k] = (k < 2 && hull) ? 0 : cv.take(hs[k] ? ns[k] : 0);
-  for (int k = 0; k < 9; k++) oo[k] = cv.take(ho[k] ? no[k] : 0);
-  gmr::DeviceBlock blk;          // device scratch of this call
-  GMR_HIP_TRY(blk.reserve(cv.total() + 256));
-  char* d = blk.data();
-  const void* ds[6];
-  for (int k = 0; k < 6; k++) {
-    ds[k] = nullptr;
-    if (!hs[k]) continue;
-    if (k < 2 && hull) { ds[k] = d + o_hull + ((const char*)hs[k] - lo); continue; }
-    ds[k] = d + os[k];
-    GMR_HIP_TRY(hipMemcpy(d + os[k], hs[k], ns[k], hipMemcpyHostToDevice));
-  }
-  if (hull) GMR_HIP_TRY(hipMemcpy(d + o_hull, lo, (size_t)(hi - lo), hipMemcpyHostToDevice));
-  void* dd[9];
-  for (int k = 0; k < 9; k++) dd[k] = ho[k] ? d + oo[k] : nullptr;
-  const gmr_tracker_links_sim_t dbodies{(const float*)ds[0], (const float*)ds[1], nullptr, nullptr, bodies->env_stride, bodies->body_stride};
-  const gmr_feet_in_t din{(const float*)ds[2], (const float*)ds[3], (const int32_t*)ds[4], (const float*)ds[5]};
-  const gmr_feet_out_t dout{(float*)dd[0], (float*)dd[1], (float*)dd[2], (int32_t*)dd[3], (float*)dd[4], (float*)dd[5], (float*)dd[6],
-                            (float*)dd[7], (int32_t*)dd[8]};
+  gmr::HostStage st;
+  gmr_tracker_links_sim_t dbodies{nullptr, nullptr, nullptr, nullptr, bodies->env_stride, bodies->body_stride};
+  gmr_feet_in_t din = {};
+  gmr_feet_out_t dout = {};
+  // the two body arrays (their extent from the strides) may interleave in one tensor
+  st.in_shared(dbodies.body_pos, bodies->body_pos, 4 * ((n - 1) * (size_t)es[0] + (nb - 1) * (size_t)bs[0] + 3));
+  st.in_shared(dbodies.body_rot, bodies->body_rot, 4 * ((n - 1) * (size_t)es[1] + (nb - 1) * (size_t)bs[1] + 4));
+  st.in(din.contact_forces, in->contact_forces, n * nb * 12); st.in(din.root_states, in->root_states, n * 52);
+  st.in(din.episode_steps, in->episode_steps, n * 4); st.in(din.gait_frequency, in->gait_frequency, n * 4);
+  st.out(dout.feet_pos, out->feet_pos, n * 24); st.out(dout.feet_roll, out->feet_roll, n * 8); st.out(dout.feet_yaw, out->feet_yaw, n * 8);
+  st.out(dout.feet_contact, out->feet_contact, n * 8); st.out(dout.ground, out->ground, n * 4); st.out(dout.gait, out->gait, n * 8);
+  st.out(dout.term, out->term, n * GMR_FEET_TERMS * 4); st.out(dout.total, out->total, n * 4); st.out(dout.done, out->done, n * 4);
+  GMR_STAGE_TRY(st, upload);
   rc = gmr::feet_launch(t, V, &dbodies, &din, &dout, nullptr);
   if (rc != GMR_OK) return rc;
-  GMR_HIP_TRY(hipDeviceSynchronize());
-  for (int k = 0; k < 9; k++)
-    if (ho[k]) GMR_HIP_TRY(hipMemcpy(ho[k], dd[k], no[k], hipMemcpyDeviceToHost));
+  GMR_STAGE_TRY(st, download);
   return GMR_OK;
 }
 

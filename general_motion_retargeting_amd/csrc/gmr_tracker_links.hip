@@ -587,73 +587,33 @@ int gmr_motion_tracker_step_links(gmr_motion_tracker_t* t, const gmr_tracker_sim
   if (!out) out = &none_out;
   if (!links_out) links_out = &none_lout;
   if (P.nsel == 0) links_sim = nullptr;
-  // inputs: the six arrays of the simulator's root and dofs, then the link arrays (their extent from the strides)
-  const void* hs[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  size_t nin[10] = {n * 12, n * 16, n * 12, n * 12, n * r * 4, n * r * 4, 0, 0, 0, 0};
-  if (sim) {
-    hs[0] = sim->base_pos; hs[1] = sim->base_quat; hs[2] = sim->base_lin_vel;
-    hs[3] = sim->base_ang_vel; hs[4] = sim->dof_pos; hs[5] = sim->dof_vel;
-  }
+  gmr::HostStage st;
+  gmr_tracker_sim_t dsim = {};
+  gmr_tracker_links_sim_t dlsim = {};
+  gmr_tracker_out_t dout = {};
+  gmr_tracker_links_out_t dlout = {};
+  if (sim) gmr::stage_tracker_sim(st, dsim, *sim, n, r);
   if (links_sim) {
+    // the link arrays (their extent from the strides) may interleave in one tensor
     const long long es = links_sim->env_stride, bs = links_sim->body_stride;
     if ((es == 0) != (bs == 0) || es < 0 || bs < 0)
       return gmr_fail(GMR_ERR_ARG, "env_stride = %lld, body_stride = %lld: both positive, or both 0 for four contiguous arrays", es, bs);
     int maxb = 0;
     for (int k = 0; k < P.nsel; k++) maxb = P.sim_body[k] > maxb ? P.sim_body[k] : maxb;
-    const int width[4] = {3, 4, 3, 3};
-    hs[6] = links_sim->body_pos; hs[7] = links_sim->body_rot; hs[8] = links_sim->body_vel; hs[9] = links_sim->body_ang_vel;
-    for (int k = 0; k < 4; k++)
-      nin[6 + k] = 4 * (es ? (n - 1) * (size_t)es + (size_t)maxb * (size_t)bs + width[k] : n * ns * width[k]);
+    auto extent = [&](size_t width) { return 4 * (es ? (n - 1) * (size_t)es + (size_t)maxb * (size_t)bs + width : n * ns * width); };
+    st.in_shared(dlsim.body_pos, links_sim->body_pos, extent(3)); st.in_shared(dlsim.body_rot, links_sim->body_rot, extent(4));
+    st.in_shared(dlsim.body_vel, links_sim->body_vel, extent(3)); st.in_shared(dlsim.body_ang_vel, links_sim->body_ang_vel, extent(3));
+    dlsim.env_stride = es; dlsim.body_stride = bs;
   }
-  // arrays that interleave in one tensor: one copy of their hull
-  const char *lo = nullptr, *hi = nullptr;
-  size_t sum = 0;
-  for (int k = 6; k < 10; k++) {
-    if (!hs[k]) continue;
-    const char* p = (const char*)hs[k];
-    if (!lo || p < lo) lo = p;
-    if (!hi || p + nin[k] > hi) hi = p + nin[k];
-    sum += nin[k];
-  }
-  const bool hull = lo && (size_t)(hi - lo) <= sum;
-  void* ho[19] = {out->ref_root_pos, out->ref_root_rot, out->ref_root_vel, out->ref_root_ang_vel, out->ref_dof_pos, out->ref_dof_vel,
-                  out->err, out->term, out->total, out->status, out->finished,
-                  links_out->ref_body_pos, links_out->ref_body_rot, links_out->ref_body_vel, links_out->ref_body_ang_vel,
-                  links_out->link_err, links_out->link_term, links_out->max_dist, links_out->fail};
-  const size_t no[19] = {n * 12, n * 16, n * 12, n * 12, n * r * 4, n * r * 4, n * 24, n * 24, n * 4, n * 4, n * 4,
-                         n * ns * 12, n * ns * 16, n * ns * 12, n * ns * 12, n * 16, n * 16, n * 4, n * 4};
-  gmr::Carve cv;
-  size_t os[10], oo[19];
-  for (int k = 0; k < 6; k++) os[k] = cv.take(hs[k] ? nin[k] : 0);
-  const size_t o_hull = cv.take(hull ? (size_t)(hi - lo) : 0);
-  for (int k = 6; k < 10; k++) os[k] = hull ? 0 : cv.take(hs[k] ? nin[k] : 0);
-  for (int k = 0; k < 19; k++) oo[k] = cv.take(ho[k] ? no[k] : 0);
-  gmr::DeviceBlock blk;          // device scratch of this call
-  GMR_HIP_TRY(blk.reserve(cv.total() + 256));
-  char* d = blk.data();
-  const float* ds[10];
-  for (int k = 0; k < 10; k++) {
-    ds[k] = nullptr;
-    if (!hs[k]) continue;
-    if (k >= 6 && hull) { ds[k] = (const float*)(d + o_hull + ((const char*)hs[k] - lo)); continue; }
-    ds[k] = (const float*)(d + os[k]);
-    GMR_HIP_TRY(hipMemcpy(d + os[k], hs[k], nin[k], hipMemcpyHostToDevice));
-  }
-  if (hull) GMR_HIP_TRY(hipMemcpy(d + o_hull, lo, (size_t)(hi - lo), hipMemcpyHostToDevice));
-  void* dv[19];
-  for (int k = 0; k < 19; k++) dv[k] = ho[k] ? d + oo[k] : nullptr;
-  const gmr_tracker_sim_t dsim{ds[0], ds[1], ds[2], ds[3], ds[4], ds[5]};
-  gmr_tracker_links_sim_t dlsim{ds[6], ds[7], ds[8], ds[9], 0, 0};
-  if (links_sim) { dlsim.env_stride = links_sim->env_stride; dlsim.body_stride = links_sim->body_stride; }
-  const gmr_tracker_out_t dout{(float*)dv[0], (float*)dv[1], (float*)dv[2], (float*)dv[3], (float*)dv[4], (float*)dv[5],
-                               (float*)dv[6], (float*)dv[7], (float*)dv[8], (int32_t*)dv[9], (int32_t*)dv[10]};
-  const gmr_tracker_links_out_t dlout{(float*)dv[11], (float*)dv[12], (float*)dv[13], (float*)dv[14], (float*)dv[15], (float*)dv[16],
-                                      (float*)dv[17], (int32_t*)dv[18]};
+  gmr::stage_tracker_out(st, dout, *out, n, r);
+  st.out(dlout.ref_body_pos, links_out->ref_body_pos, n * ns * 12); st.out(dlout.ref_body_rot, links_out->ref_body_rot, n * ns * 16);
+  st.out(dlout.ref_body_vel, links_out->ref_body_vel, n * ns * 12); st.out(dlout.ref_body_ang_vel, links_out->ref_body_ang_vel, n * ns * 12);
+  st.out(dlout.link_err, links_out->link_err, n * 16); st.out(dlout.link_term, links_out->link_term, n * 16);
+  st.out(dlout.max_dist, links_out->max_dist, n * 4); st.out(dlout.fail, links_out->fail, n * 4);
+  GMR_STAGE_TRY(st, upload);
   const int rc = gmr::links_step_launch(t, t->S, t->tab, P, t->fk, sim ? &dsim : nullptr, links_sim ? &dlsim : nullptr, &dout, &dlout, flags, nullptr);
   if (rc != GMR_OK) return rc;
-  GMR_HIP_TRY(hipDeviceSynchronize());
-  for (int k = 0; k < 19; k++)
-    if (ho[k] && no[k]) GMR_HIP_TRY(hipMemcpy(ho[k], dv[k], no[k], hipMemcpyDeviceToHost));
+  GMR_STAGE_TRY(st, download);
   return GMR_OK;
 }
 

@@ -366,25 +366,18 @@ int gmr_motion_tracker_preview(gmr_motion_tracker_t* t, const gmr_tracker_sim_t*
   if (from_sim && (!sim || !sim->base_pos || !sim->base_quat))
     return gmr_fail(GMR_ERR_ARG, "the sim frame needs base_pos and base_quat of the simulator's root");
   const size_t n = (size_t)t->N, nk = n * (size_t)P.K, d = (size_t)gmr::preview_width(P.blocks, t->tab.R, P.nsel);
-  gmr::Carve cv;
-  const size_t o_pos = cv.take(from_sim ? n * 12 : 0), o_quat = cv.take(from_sim ? n * 16 : 0), o_obs = cv.take(obs ? nk * d * 4 : 0),
-               o_valid = cv.take(valid ? nk * 4 : 0), o_status = cv.take(status ? n * 4 : 0);
-  gmr::DeviceBlock blk;          // device scratch of this call
-  GMR_HIP_TRY(blk.reserve(cv.total() + 256));
-  char* b = blk.data();
+  gmr::HostStage st;
   gmr_tracker_sim_t dsim = {};
+  float* d_obs;
+  int32_t *d_valid, *d_status;
   if (from_sim) {
-    GMR_HIP_TRY(hipMemcpy(b + o_pos, sim->base_pos, n * 12, hipMemcpyHostToDevice));
-    GMR_HIP_TRY(hipMemcpy(b + o_quat, sim->base_quat, n * 16, hipMemcpyHostToDevice));
-    dsim.base_pos = (const float*)(b + o_pos); dsim.base_quat = (const float*)(b + o_quat);
+    st.in(dsim.base_pos, sim->base_pos, n * 12); st.in(dsim.base_quat, sim->base_quat, n * 16);
   }
-  const int rc = gmr::preview_launch(t, t->tab, P, from_sim ? &dsim : nullptr, obs ? (float*)(b + o_obs) : nullptr,
-                                     valid ? (int32_t*)(b + o_valid) : nullptr, status ? (int32_t*)(b + o_status) : nullptr, nullptr);
+  st.out(d_obs, obs, nk * d * 4); st.out(d_valid, valid, nk * 4); st.out(d_status, status, n * 4);
+  GMR_STAGE_TRY(st, upload);
+  const int rc = gmr::preview_launch(t, t->tab, P, from_sim ? &dsim : nullptr, d_obs, d_valid, d_status, nullptr);
   if (rc != GMR_OK) return rc;
-  GMR_HIP_TRY(hipDeviceSynchronize());
-  if (obs) GMR_HIP_TRY(hipMemcpy(obs, b + o_obs, nk * d * 4, hipMemcpyDeviceToHost));
-  if (valid) GMR_HIP_TRY(hipMemcpy(valid, b + o_valid, nk * 4, hipMemcpyDeviceToHost));
-  if (status) GMR_HIP_TRY(hipMemcpy(status, b + o_status, n * 4, hipMemcpyDeviceToHost));
+  GMR_STAGE_TRY(st, download);
   return GMR_OK;
 }
 

@@ -412,34 +412,20 @@ int gmr_motion_tracker_proprio(gmr_motion_tracker_t* t, const gmr_proprio_in_t* 
   int rc = gmr::proprio_check(t, V.tab, in, noise, out);
   if (rc != GMR_OK) return rc;
   const size_t n = (size_t)t->N, r = (size_t)V.tab.R, nr = n * r * 4, w = 6 + (size_t)V.tab.C + 3 * r;
-  const void* hs[8] = {in->root_states, in->dof_pos, in->dof_vel, in->actions, in->mean_torques, in->extra, in->ground, in->episode_steps};
-  const size_t ns[8] = {n * 52, nr, nr, nr, nr, n * (size_t)V.tab.C * 4, n * 4, n * 4};
-  void* ho[10] = {out->base_lin_vel, out->base_ang_vel, out->projected_gravity, out->filtered_lin_vel, out->filtered_ang_vel,
-                  out->obs, out->priv, out->term, out->total, out->done};
-  const size_t no[10] = {n * 12, n * 12, n * 12, n * 12, n * 12, n * w * 4, n * 16, n * GMR_PROPRIO_TERMS * 4, n * 4, n * 4};
-  gmr::Carve cv;
-  size_t os[8], oo[10];
-  for (int k = 0; k < 8; k++) os[k] = cv.take(hs[k] ? ns[k] : 0);
-  for (int k = 0; k < 10; k++) oo[k] = cv.take(ho[k] ? no[k] : 0);
-  gmr::DeviceBlock blk;          // device scratch of this call
-  GMR_HIP_TRY(blk.reserve(cv.total() + 256));
-  char* d = blk.data();
-  const void* ds[8];
-  void* dd[10];
-  for (int k = 0; k < 8; k++) {
-    ds[k] = hs[k] ? d + os[k] : nullptr;
-    if (hs[k]) GMR_HIP_TRY(hipMemcpy(d + os[k], hs[k], ns[k], hipMemcpyHostToDevice));
-  }
-  for (int k = 0; k < 10; k++) dd[k] = ho[k] ? d + oo[k] : nullptr;
-  const gmr_proprio_in_t din{(const float*)ds[0], (const float*)ds[1], (const float*)ds[2], (const float*)ds[3], (const float*)ds[4],
-                             (const float*)ds[5], (const float*)ds[6], (const int32_t*)ds[7]};
-  const gmr_proprio_out_t dout{(float*)dd[0], (float*)dd[1], (float*)dd[2], (float*)dd[3], (float*)dd[4], (float*)dd[5], (float*)dd[6],
-                               (float*)dd[7], (float*)dd[8], (int32_t*)dd[9]};
+  gmr::HostStage st;
+  gmr_proprio_in_t din = {};
+  gmr_proprio_out_t dout = {};
+  st.in(din.root_states, in->root_states, n * 52); st.in(din.dof_pos, in->dof_pos, nr); st.in(din.dof_vel, in->dof_vel, nr);
+  st.in(din.actions, in->actions, nr); st.in(din.mean_torques, in->mean_torques, nr); st.in(din.extra, in->extra, n * (size_t)V.tab.C * 4);
+  st.in(din.ground, in->ground, n * 4); st.in(din.episode_steps, in->episode_steps, n * 4);
+  st.out(dout.base_lin_vel, out->base_lin_vel, n * 12); st.out(dout.base_ang_vel, out->base_ang_vel, n * 12);
+  st.out(dout.projected_gravity, out->projected_gravity, n * 12); st.out(dout.filtered_lin_vel, out->filtered_lin_vel, n * 12);
+  st.out(dout.filtered_ang_vel, out->filtered_ang_vel, n * 12); st.out(dout.obs, out->obs, n * w * 4); st.out(dout.priv, out->priv, n * 16);
+  st.out(dout.term, out->term, n * GMR_PROPRIO_TERMS * 4); st.out(dout.total, out->total, n * 4); st.out(dout.done, out->done, n * 4);
+  GMR_STAGE_TRY(st, upload);
   rc = gmr::proprio_launch(t, V, &din, noise, &dout, nullptr);
   if (rc != GMR_OK) return rc;
-  GMR_HIP_TRY(hipDeviceSynchronize());
-  for (int k = 0; k < 10; k++)
-    if (ho[k]) GMR_HIP_TRY(hipMemcpy(ho[k], dd[k], no[k], hipMemcpyDeviceToHost));
+  GMR_STAGE_TRY(st, download);
   return GMR_OK;
 }
 
@@ -464,21 +450,17 @@ int gmr_motion_tracker_proprio_reset(gmr_motion_tracker_t* t, int n, const int32
   if (rc != GMR_OK) return rc;
   if (n == 0) return GMR_OK;
   const size_t nn = (size_t)n;
-  gmr::Carve cv;
-  const size_t o_ids = cv.take(env_ids ? nn * 4 : 0), o_mask = cv.take(mask ? nn * 4 : 0), o_root = cv.take(nn * 52);
-  gmr::DeviceBlock blk;          // device scratch of this call
-  GMR_HIP_TRY(blk.reserve(cv.total() + 256));
-  char* d = blk.data();
-  if (env_ids) GMR_HIP_TRY(hipMemcpy(d + o_ids, env_ids, nn * 4, hipMemcpyHostToDevice));
-  if (mask) GMR_HIP_TRY(hipMemcpy(d + o_mask, mask, nn * 4, hipMemcpyHostToDevice));
-  GMR_HIP_TRY(hipMemcpy(d + o_root, root_states, nn * 52, hipMemcpyHostToDevice));
+  gmr::HostStage st;
+  const int32_t *d_ids, *d_mask;
+  const float* d_root;
+  st.in(d_ids, env_ids, nn * 4); st.in(d_mask, mask, nn * 4); st.in(d_root, root_states, nn * 52);
+  GMR_STAGE_TRY(st, upload);
   uint32_t before = 0, after = 0;
-  GMR_HIP_TRY(hipMemcpy(&before, t->S.ignored, 4, hipMemcpyDeviceToHost));
-  rc = gmr::proprio_reset_launch(t, V, n, env_ids ? (const int32_t*)(d + o_ids) : nullptr, mask ? (const int32_t*)(d + o_mask) : nullptr,
-                                 (const float*)(d + o_root), nullptr);
+  if ((rc = gmr::tracker_ignored(t, &before)) != GMR_OK) return rc;
+  rc = gmr::proprio_reset_launch(t, V, n, d_ids, d_mask, d_root, nullptr);
   if (rc != GMR_OK) return rc;
-  GMR_HIP_TRY(hipDeviceSynchronize());
-  GMR_HIP_TRY(hipMemcpy(&after, t->S.ignored, 4, hipMemcpyDeviceToHost));
+  GMR_STAGE_TRY(st, download);
+  if ((rc = gmr::tracker_ignored(t, &after)) != GMR_OK) return rc;
   if (ignored) *ignored = (int)(after - before);
   return GMR_OK;
 }

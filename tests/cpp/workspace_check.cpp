@@ -1,15 +1,24 @@
-// The host side's device-memory helpers (csrc/gmr_workspace.h: Carve, DeviceBlock, StreamWorkspace) driven on the CPU
+// The host side's device-memory helpers (csrc/gmr_workspace.h: Carve, DeviceBlock, StreamWorkspace, HostStage) driven on the CPU
 // with a backend that records what the library would ask of the HIP runtime (plain C++, no HIP):
 //   * Carve: offsets are multiples of 256, ascending, non-overlapping; total() covers the last field; empty fields are legal;
 //   * DeviceBlock: grow-only, the requested headroom and floor, freed exactly once;
 //   * StreamWorkspace: a call that fits asks nothing of the runtime; growth is synchronise(own stream), free, allocate
 //     (bytes + bytes / 4) and touches no other stream; a failed allocation leaves the entry empty and the next call
-//     retries; the lease excludes other threads until it is released.
+//     retries; the lease excludes other threads until it is released;
+//   * HostStage: one allocation per call and one copy per present non-empty input; null stays null, empty gets an address and no
+//     copy; fields at multiples of 256 that do not overlap; download is synchronise, then the copies of the outputs that are
+//     neither skipped nor empty; the bytes a "kernel" (a host loop over the device pointers) wrote come back; arrays that
+//     interleave in one tensor travel as one copy of their hull, arrays apart as one copy each; a failed allocation copies
+//     nothing and writes no host output; the block is freed exactly once.  The fake's memory is malloc'd and its copies are
+//     memcpy, so real bytes make the round trip.
 // Prints "ok"; exit code 0 = all good.
+#include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <set>
 #include <string>
 #include <thread>
@@ -20,8 +29,8 @@
 #define CHECK(c, ...) do { if (!(c)) { std::fprintf(stderr, "CHECK failed (line %d): %s : ", __LINE__, #c); std::fprintf(stderr, __VA_ARGS__); std::fprintf(stderr, "\n"); return 1; } } while (0)
 
 struct Op {
-  char what;                 // 'a'lloc, 'f'ree, 's'ync
-  void* p;                   // the block (alloc / free) or the stream (sync)
+  char what;                 // 'a'lloc, 'f'ree, 's'ync of a stream, 'S'ync of the device, 'u'pload (host to device), 'd'ownload
+  void* p;                   // the block (alloc / free), the stream (sync) or the device address (copies)
   size_t bytes;
   bool operator==(const Op& o) const { return what == o.what && p == o.p && bytes == o.bytes; }
 };
@@ -48,6 +57,10 @@ struct Fake {
     return 0;
   }
   static int sync(void* s) { log.push_back({'s', s, 0}); return 0; }
+  static int sync_device() { log.push_back({'S', nullptr, 0}); return 0; }
+  static int to_device(void* d, const void* h, size_t bytes) { std::memcpy(d, h, bytes); log.push_back({'u', d, bytes}); return 0; }
+  static int to_host(void* h, const void* d, size_t bytes) { std::memcpy(h, d, bytes); log.push_back({'d', const_cast<void*>(d), bytes}); return 0; }
+  static size_t count(char what) { size_t n = 0; for (const Op& o : log) n += o.what == what; return n; }
 };
 std::vector<Op> Fake::log;
 std::set<void*> Fake::live;
@@ -56,6 +69,7 @@ int Fake::double_frees = 0;
 
 using Block = gmr::DeviceBlockT<Fake>;
 using Workspace = gmr::StreamWorkspaceT<Fake>;
+using Stage = gmr::HostStageT<Fake>;
 
 static int check_carve() {
   gmr::Carve c;
@@ -138,8 +152,141 @@ static int check_workspace() {
   return 0;
 }
 
+static int check_stage() {
+  // every kind of array in one call: present, null and empty inputs; present, null, skipped and empty outputs
+  std::vector<unsigned char> a(100), d(300), o1(64, 0), o3(32, 0x11), o5(257, 0);
+  for (size_t i = 0; i < a.size(); i++) a[i] = (unsigned char)(i * 7 + 1);
+  for (size_t i = 0; i < d.size(); i++) d[i] = (unsigned char)(i * 13 + 5);
+  char empty_in = 0, empty_out = 0x22;       // only their addresses are used
+  Fake::log.clear();
+  {
+    Stage st;
+    const unsigned char *d_a, *d_b, *d_c, *d_d;
+    unsigned char *d_o1, *d_o2, *d_o3, *d_o4, *d_o5;
+    st.in(d_a, a.data(), a.size());
+    st.in(d_b, nullptr, 999);
+    st.in(d_c, &empty_in, 0);
+    st.in(d_d, d.data(), d.size());
+    st.out(d_o1, o1.data(), o1.size());
+    st.out(d_o2, nullptr, 999);
+    st.out(d_o3, o3.data(), o3.size(), false);
+    st.out(d_o5, o5.data(), o5.size());
+    st.out(d_o4, &empty_out, 0);             // (a trailing empty field)
+    CHECK(Fake::log.empty(), "declaring asks nothing of the runtime");
+    CHECK(st.upload() == 0, "upload");
+    CHECK(Fake::log.size() == 3 && Fake::log[0].what == 'a' && Fake::count('u') == 2, "one allocation, then one copy per present non-empty input (%zu ops)", Fake::log.size());
+    CHECK(d_b == nullptr && d_o2 == nullptr, "null in gives null out");
+    CHECK(d_c != nullptr && d_o4 != nullptr, "non-null with 0 bytes gives an address");
+    const char* base = (const char*)Fake::log[0].p;
+    const size_t cap = Fake::log[0].bytes;
+    CHECK(cap > 0, "the allocation is never empty");
+    const struct { const void* p; size_t bytes; } f[] = {{d_a, a.size()}, {d_c, 0}, {d_d, d.size()}, {d_o1, o1.size()}, {d_o3, o3.size()}, {d_o5, o5.size()}, {d_o4, 0}};
+    size_t prev_end = 0;
+    for (const auto& x : f) {
+      const size_t at = (size_t)((const char*)x.p - base);
+      CHECK(at % 256 == 0 && at >= prev_end && at + x.bytes <= cap && at < cap, "a field of %zu bytes at %zu (the one before ends at %zu, the block at %zu)", x.bytes, at, prev_end, cap);
+      prev_end = at + x.bytes;
+    }
+    CHECK(Fake::log[1] == (Op{'u', (void*)d_a, a.size()}) && Fake::log[2] == (Op{'u', (void*)d_d, d.size()}), "the copies are of the inputs, at their size");
+    CHECK(!std::memcmp(d_a, a.data(), a.size()) && !std::memcmp(d_d, d.data(), d.size()), "the device sees the inputs");
+    // the "kernel"
+    for (size_t i = 0; i < o1.size(); i++) d_o1[i] = d_a[i] ^ 0x5a;
+    for (size_t i = 0; i < o3.size(); i++) d_o3[i] = 0xee;
+    for (size_t i = 0; i < o5.size(); i++) d_o5[i] = (unsigned char)(d_d[i] + 1);
+    CHECK(o1[0] == 0 && o5[0] == 0, "nothing reaches the host before download");
+    Fake::log.clear();
+    CHECK(st.download() == 0, "download");
+    CHECK(Fake::log.size() == 3 && Fake::log[0] == (Op{'S', nullptr, 0}) && Fake::log[1] == (Op{'d', d_o1, o1.size()}) && Fake::log[2] == (Op{'d', d_o5, o5.size()}),
+          "download is synchronise, then one copy per output that is neither skipped nor empty (%zu ops)", Fake::log.size());
+    for (size_t i = 0; i < o1.size(); i++) CHECK(o1[i] == (unsigned char)(a[i] ^ 0x5a), "o1[%zu]", i);
+    for (size_t i = 0; i < o5.size(); i++) CHECK(o5[i] == (unsigned char)(d[i] + 1), "o5[%zu]", i);
+    for (size_t i = 0; i < o3.size(); i++) CHECK(o3[i] == 0x11, "a skipped output was written at %zu", i);
+    CHECK(empty_out == 0x22, "an empty output was written");
+    Fake::log.clear();
+  }
+  CHECK(Fake::log.size() == 1 && Fake::log[0].what == 'f' && Fake::live.empty() && Fake::double_frees == 0, "the block is freed exactly once");
+  {
+    Stage st;
+    CHECK(st.upload() == 0 && st.download() == 0 && Fake::count('a') == 0, "a call without arrays allocates nothing");
+  }
+
+  // arrays that interleave in one tensor: [n][7] (pos 3, quat 4) and [n][13] (pos 3, quat 4, vel 3, ang vel 3, the vel left out)
+  const size_t n = 5;
+  std::vector<float> t7(n * 7), t13(n * 13);
+  for (size_t i = 0; i < t7.size(); i++) t7[i] = (float)i;
+  for (size_t i = 0; i < t13.size(); i++) t13[i] = 1000.0f + (float)i;
+  Fake::log.clear();
+  {
+    Stage st;
+    const float *d_pos, *d_rot;
+    st.in_shared(d_pos, t7.data(), ((n - 1) * 7 + 3) * 4);
+    st.in_shared(d_rot, t7.data() + 3, ((n - 1) * 7 + 4) * 4);
+    CHECK(st.upload() == 0, "upload");
+    CHECK(Fake::count('a') == 1 && Fake::count('u') == 1 && Fake::log[1] == (Op{'u', (void*)d_pos, n * 7 * 4}), "two interleaved arrays: one copy of hi - lo bytes");
+    CHECK(d_rot == d_pos + 3, "each at its own offset in the hull");
+    for (size_t e = 0; e < n; e++) CHECK(d_pos[e * 7 + 2] == t7[e * 7 + 2] && d_rot[e * 7 + 3] == t7[e * 7 + 6], "row %zu", e);
+  }
+  Fake::log.clear();
+  {
+    Stage st;
+    const float *d_pos, *d_rot, *d_vel, *d_ang, *d_other;
+    const float other[2] = {7.0f, 8.0f};
+    st.in(d_other, other, sizeof other);                // (a plain input beside the group)
+    st.in_shared(d_rot, t13.data() + 3, ((n - 1) * 13 + 4) * 4);      // (in any order)
+    st.in_shared(d_pos, t13.data(), ((n - 1) * 13 + 3) * 4);
+    st.in_shared(d_vel, nullptr, ((n - 1) * 13 + 3) * 4);
+    st.in_shared(d_ang, t13.data() + 10, ((n - 1) * 13 + 3) * 4);
+    CHECK(st.upload() == 0, "upload");
+    CHECK(Fake::count('a') == 1 && Fake::count('u') == 2, "four interleaved arrays and one plain: two copies, got %zu", Fake::count('u'));
+    bool hull_copied = false;
+    for (const Op& o : Fake::log) hull_copied |= o == (Op{'u', (void*)d_pos, n * 13 * 4});
+    CHECK(hull_copied, "one of them the hull, of hi - lo bytes");
+    CHECK(d_vel == nullptr, "a null member is left out");
+    CHECK(d_rot == d_pos + 3 && d_ang == d_pos + 10 && ((const char*)d_pos - (const char*)Fake::log[0].p) % 256 == 0, "each at its own offset in the hull");
+    for (size_t e = 0; e < n; e++)
+      CHECK(d_pos[e * 13] == t13[e * 13] && d_rot[e * 13 + 3] == t13[e * 13 + 6] && d_ang[e * 13 + 2] == t13[e * 13 + 12], "row %zu", e);
+    CHECK(d_other[0] == 7.0f && d_other[1] == 8.0f, "the plain input");
+  }
+  // arrays of one group in separate allocations: one copy each
+  Fake::log.clear();
+  {
+    std::vector<float> p(n * 3, 1.0f), q(n * 4, 2.0f);
+    const uintptr_t lo = std::min((uintptr_t)p.data(), (uintptr_t)q.data()), hi = std::max((uintptr_t)(p.data() + p.size()), (uintptr_t)(q.data() + q.size()));
+    CHECK(hi - lo > (p.size() + q.size()) * 4, "the two arrays of this case must lie apart");
+    Stage st;
+    const float *d_p, *d_q;
+    st.in_shared(d_p, p.data(), p.size() * 4);
+    st.in_shared(d_q, q.data(), q.size() * 4);
+    CHECK(st.upload() == 0, "upload");
+    CHECK(Fake::count('a') == 1 && Fake::count('u') == 2 && Fake::log[1] == (Op{'u', (void*)d_p, p.size() * 4}) && Fake::log[2] == (Op{'u', (void*)d_q, q.size() * 4}),
+          "arrays apart: one copy each");
+    const size_t at_p = (size_t)((const char*)d_p - (const char*)Fake::log[0].p), at_q = (size_t)((const char*)d_q - (const char*)Fake::log[0].p);
+    CHECK(at_p % 256 == 0 && at_q % 256 == 0 && at_q >= at_p + p.size() * 4, "as fields of their own");
+    CHECK(d_p[n * 3 - 1] == 1.0f && d_q[n * 4 - 1] == 2.0f, "their data");
+  }
+  CHECK(Fake::live.empty() && Fake::double_frees == 0, "every block freed exactly once");
+
+  // a failed allocation: the error comes back, nothing is copied, no host output is written
+  Fake::log.clear();
+  {
+    std::vector<unsigned char> in(40, 3), out(40, 0x44);
+    Stage st;
+    const unsigned char* d_in;
+    unsigned char* d_out;
+    st.in(d_in, in.data(), in.size());
+    st.out(d_out, out.data(), out.size());
+    Fake::fail_allocs = 1;
+    CHECK(st.upload() == 2, "a failed allocation is reported");
+    CHECK(st.failed()[0] != 0, "and the failing operation named");
+    CHECK(Fake::log.size() == 1 && Fake::log[0].what == 'a', "with no copy (%zu ops)", Fake::log.size());
+    for (unsigned char c : out) CHECK(c == 0x44, "a host output was written after a failed upload");
+  }
+  CHECK(Fake::live.empty() && Fake::double_frees == 0 && Fake::count('f') == 0, "nothing to free after a failed allocation");
+  return 0;
+}
+
 int main() {
-  if (check_carve() || check_block() || check_workspace()) return 1;
+  if (check_carve() || check_block() || check_workspace() || check_stage()) return 1;
   std::printf("ok\n");
   return 0;
 }

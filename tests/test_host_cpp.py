@@ -1,7 +1,8 @@
 """The C++ host logic behind the IK kernel (static H-assembly schedule, limb/trunk decomposition, LDS
 layout + image) checked on the CPU for every (source, robot) pair: tests/cpp/layout_check.cpp is plain
 C++ (g++), includes the product header csrc/gmr_ik_layout.h and reads the packed structs from a file.
-tests/cpp/workspace_check.cpp does the same for csrc/gmr_workspace.h, how the host side owns device memory."""
+tests/cpp/workspace_check.cpp does the same for csrc/gmr_workspace.h, how the host side owns device memory
+and stages the arrays of a synchronous call."""
 import os
 import subprocess
 
@@ -11,6 +12,7 @@ import pytest
 from conftest import ALL_CONFIGS, ROOT, get_setup
 
 SRC = os.path.join(ROOT, "tests", "cpp", "layout_check.cpp")
+WORKSPACE_SRC = os.path.join(ROOT, "tests", "cpp", "workspace_check.cpp")
 
 
 @pytest.fixture(scope="module")
@@ -98,11 +100,27 @@ def test_fk_tree_partition_for_the_split_walk(split_checker):
 def test_device_workspace_contract(tmp_path):
     """csrc/gmr_workspace.h against a recording fake of the HIP runtime: the layout rounding, grow-only blocks with their
     headroom and floor, and the per-stream workspace's order of operations (synchronise the block's own stream, free,
-    allocate), its isolation between streams, its recovery from a failed allocation and its lock."""
+    allocate), its isolation between streams, its recovery from a failed allocation and its lock; and the staging of a
+    synchronous call (HostStage): one allocation and one copy per present non-empty input, null and empty arrays, fields
+    at multiples of 256 that do not overlap, synchronise before the first copy back, skipped and empty outputs left
+    alone, the round trip of the bytes a host-loop "kernel" wrote, one copy of the hull for arrays that interleave and
+    one each for arrays apart, a failed allocation that copies and writes nothing, and no leak or double free."""
     exe = str(tmp_path / "workspace_check")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-pthread", "-o", exe, os.path.join(ROOT, "tests", "cpp", "workspace_check.cpp")])
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-pthread", "-o", exe, WORKSPACE_SRC])
     out = subprocess.run([exe], capture_output=True, text=True)
     assert out.returncode == 0 and out.stdout.strip() == "ok", (out.stdout, out.stderr)
+
+
+def test_device_workspace_code_is_clean_under_sanitizers(tmp_path):
+    """The same stand-alone program under AddressSanitizer + UBSan: the offsets and byte counts of a synchronous call's
+    staging are host arithmetic, and a wrong one would become an out-of-bounds device copy."""
+    exe = str(tmp_path / "workspace_check_asan")
+    cc = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-pthread", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                         "-o", exe, WORKSPACE_SRC], capture_output=True, text=True)
+    if cc.returncode != 0:
+        pytest.skip("sanitizer runtime not available: " + cc.stderr[-200:])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and out.stdout.strip() == "ok" and "runtime error" not in out.stderr and "ERROR" not in out.stderr, (out.stdout, out.stderr[-2000:])
 
 
 def test_layout_code_is_clean_under_sanitizers(tmp_path):

@@ -115,6 +115,32 @@ def test_fill_of_a_long_clip_and_without_local_body_pos(hip):
         lib.sample_dev(1, hip.DeviceBuffer(4), hip.DeviceBuffer(8), local_body_pos=hip.DeviceBuffer(64))
 
 
+def test_the_synchronous_fill_with_and_without_local_body_pos(hip):
+    """``gmr_motion_lib_fill`` takes host arrays (the package itself fills from device memory): with local_body_pos and with the
+    mandatory arrays alone, the arrays both libraries hold are the same bits, and those of a library filled on the device.  2 clips of
+    4 and 5 frames, 2 dofs, 3 bodies."""
+    from general_motion_retargeting_amd.motion_library import ANGVEL, MotionLibrary
+    rng = np.random.default_rng(19)
+    motions = make_motions(rng, [4, 5], 2, 3)
+    seg = np.concatenate([[0], np.cumsum([len(m["root_pos"]) for m in motions])]).astype(np.int32)
+    rp, rr, dp = (np.ascontiguousarray(np.concatenate([m[k] for m in motions]), dtype=np.float64) for k in ("root_pos", "root_rot", "dof_pos"))
+    body = np.ascontiguousarray(np.concatenate([m["local_body_pos"] for m in motions]), dtype=F)
+
+    def filled(lbp):
+        lib = MotionLibrary.__new__(MotionLibrary)
+        lib.device = lib.motion_dir = None
+        lib._create(seg, [m["fps"] for m in motions], 2, 3, "world")
+        hip.check(hip.lib().gmr_motion_lib_fill(lib.handle, hip._ptr(rp), hip._ptr(rr), hip._ptr(dp), hip._ptr(lbp), ANGVEL["world"]))
+        lib.has_local_body_pos = lbp is not None
+        return lib
+
+    full, bare, ref = filled(body), filled(None), device_library(hip, motions)
+    for k in LIB_ARRAYS:
+        assert np.array_equal(_bits(full.array(k)), _bits(bare.array(k))) and np.array_equal(_bits(full.array(k)), _bits(ref.array(k))), k
+    assert np.array_equal(_bits(full.array("local_body_pos")), _bits(ref.array("local_body_pos"))) and full.array("dof_vel").any()
+    assert bare.device_array("local_body_pos") == (None, 0)
+
+
 def test_world_mode_on_constant_rates(hip):
     for axis in ((0, 0, 1), (0, 1, 0), (1, 0, 0)):
         m = constant_rate_clip(axis, 1.7)

@@ -13,7 +13,8 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import feet_mirror as fm  # noqa: E402
-from test_motion_tracker import STATE  # noqa: E402
+from test_motion_library import device_library, make_motions  # noqa: E402
+from test_motion_tracker import STATE, tracker  # noqa: E402
 from test_tracker_control import G, SENTINEL, hip, same, world  # noqa: E402,F401
 from test_tracker_feet_host import ANGLE_UNIT, EPS, clamped_height, golden, golden_terrain, rough_field, term_bounds  # noqa: E402
 from test_tracker_proprio import STATE6  # noqa: E402
@@ -420,3 +421,60 @@ def test_the_device_call_on_a_stream_of_its_own_gives_the_synchronous_bytes(hip,
     sa, sb = ta.state(), tb.state()
     for k in STATE:
         same(sa[k], sb[k], k)
+
+
+# ---- 9. the synchronous calls with every optional array and with the mandatory ones alone ------------------------------------------------
+def small_twins(hip, rng, n, nb):
+    """two trackers alike on a library of 2 clips of 4 and 5 frames with 2 dofs, terrain and feet set (bodies 0 and 2 of nb) -> them, the field"""
+    lib = device_library(hip, make_motions(rng, [4, 5], 2, 0))
+    field = field_of(rng)
+    twins = [tracker(lib, n, DT) for _ in range(2)]
+    for t in twins:
+        t.set_terrain(field, HS, VS, BORDER)
+        t.set_feet((0, 2), edges_of(4), nb, termination_bodies=(1,), penalized_bodies=(0, 2), feet_distance_ref=0.2, swing_period=0.2, scales=SCALES)
+    return twins, field
+
+
+def test_synchronous_feet_with_every_optional_input_and_with_none(hip):
+    """``feet`` on host arrays: the packed tensor (one copy of the hull of its two views) with every optional input against a twin given
+    two separate body arrays and root_states alone, two steps each.  What does not read the absent inputs -- the feet's positions,
+    angles and contacts, the ground, the terms from feet_vel_z to feet_distance, last_feet_pos -- is the same bits; collision, done
+    and the gait columns of the twin are zero.  5 environments (no multiple of the 16-lane group), 3 bodies."""
+    rng = np.random.default_rng(92)
+    n, nb = 5, 3
+    (ta, tb), field = small_twins(hip, rng, n, nb)
+    ter = fm.terrain(field, HS, VS, BORDER)
+    for s in range(2):
+        state = rng.normal(0, 1, (n, nb, 13)).astype(F)
+        state[:, :, 3:7] /= np.linalg.norm(state[:, :, 3:7], axis=-1, keepdims=True)
+        state[:, :, 0], state[:, :, 1] = rng.uniform(0.05, X_HI - 0.2, (n, nb)), rng.uniform(0.05, Y_HI - 0.2, (n, nb))
+        under, _ = fm.heights(ter, state[:, :, :2].reshape(-1, 2))
+        state[:, :, 2] = under.reshape(n, nb) + rng.uniform(-0.03, 0.2, (n, nb)).astype(F)
+        root = np.concatenate([state[:, 1, :7], rng.normal(0, 1, (n, 6)).astype(F)], axis=1)
+        every = ta.feet({"body_state": state}, root, rng.normal(0, 2.0, (n, nb, 3)).astype(F), rng.integers(0, 4, n).astype(np.int32),
+                        rng.uniform(1.0, 2.5, n).astype(F))
+        alone = tb.feet({"body_pos": state[:, :, 0:3], "body_rot": state[:, :, 3:7]}, root)
+        for k in ("feet_pos", "feet_roll", "feet_yaw", "feet_contact", "ground"):
+            same(every[k], alone[k], (s, k))
+        same(every["term"][:, 2:7], alone["term"][:, 2:7], (s, "term"))
+        same(ta.feet_state()["last_feet_pos"], tb.feet_state()["last_feet_pos"], (s, "last_feet_pos"))
+        assert not alone["done"].any() and not alone["gait"].any() and not alone["term"][:, 0].any()
+        assert every["gait"].any() and every["term"][:, 0].any() and (every["term"][:, 2:6] != 0).any(axis=0).all() and every["ground"].any()
+        assert np.array_equal(every["feet_pos"], state[:, (0, 2), 0:3])
+    assert tb.feet_state()["gait_process"].tolist() == [0.0] * n and ta.feet_state()["gait_process"].all()
+
+
+def test_synchronous_terrain_heights_with_and_without_the_counter(hip):
+    """``terrain_heights`` on host arrays with its one optional array, the counter of the points outside, and without: the same heights"""
+    rng = np.random.default_rng(93)
+    n = 5
+    (t, _), field = small_twins(hip, rng, n, 3)
+    pts = rng.uniform(-0.6, 2.3, (n, 2)).astype(F)
+    pts[0] = (-50.0, 0.3)
+    h, outside = t.terrain_heights(pts)
+    alone = np.full(n, SENTINEL, F)
+    hip.check(hip.lib().gmr_motion_tracker_terrain_heights(t.handle, n, hip._ptr(pts), 2, hip._ptr(alone), None))
+    want, count = fm.heights(fm.terrain(field, HS, VS, BORDER), pts)
+    same(h, alone, "heights")
+    same(h, want, "the mirror")
+    assert outside == count >= 1
