@@ -165,6 +165,13 @@ _SIGS = {
     "gmr_motion_tracker_feet_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gmr_motion_tracker_feet": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gmr_motion_tracker_feet_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gmr_motion_tracker_set_commands": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "gmr_motion_tracker_commands_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gmr_motion_tracker_commands": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gmr_motion_tracker_command_state": (C.c_int, [C.c_void_p] * 9),
+    "gmr_motion_tracker_set_disturbances": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gmr_motion_tracker_disturb_dev": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "gmr_motion_tracker_disturb": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     "gmr_comm_create": (C.c_int, [C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),
     "gmr_comm_destroy": (C.c_int, [C.c_void_p]),
     "gmr_comm_rank": (C.c_int, [C.c_void_p]),
@@ -680,6 +687,49 @@ class FeetIn(C.Structure):
 class FeetOut(C.Structure):
     """``gmr_feet_out_t``: the outputs of ``gmr_motion_tracker_feet[_dev]``, each an address or NULL"""
     _fields_ = [(k, C.c_void_p) for k in FEET_OUT_FIELDS]
+
+
+# gmr_motion_tracker_set_commands / _commands[_dev] / _set_disturbances / _disturb[_dev] (include/gmr_hip.h, "tracker commands")
+CMD_TERMS = ("survival", "tracking_lin_vel_x", "tracking_lin_vel_y", "tracking_ang_vel")
+CMD_MAX_LEVELS, CMD_CHUNK = 20, 8
+CMD_BOUNDARY, CMD_RESAMPLED, CMD_SUCCESS = 1, 2, 4
+CMD_INDEX_ORDERS = {"grid": 0, "reference": 1}
+DISTURB_KICK, DISTURB_PUSH_START, DISTURB_PUSH_STOP = 1, 2, 4
+DISTURB_SPECS = ("kick_lin_vel", "kick_ang_vel", "push_force", "push_torque")
+CMD_IN_FIELDS = ("episode_steps", "done", "lin_vel", "ang_vel")
+CMD_OUT_FIELDS = ("term", "total", "commands", "gait_frequency", "flags", "cmd_obs")
+DISTURB_IO_FIELDS = ("root_states", "push_force", "push_torque")
+
+
+class CommandsConfig(C.Structure):
+    """``gmr_commands_config_t``: the configuration of ``gmr_motion_tracker_set_commands``, values only"""
+    _fields_ = ([(k, C.c_double * 2) for k in ("lin_vel_x", "lin_vel_y", "ang_vel_yaw", "gait_frequency")]
+                + [(k, C.c_double) for k in ("still_proportion", "tracking_sigma", "update_rate")]
+                + [("toler", C.c_double * 3), ("resolution", C.c_double * 3), ("scales", C.c_float * len(CMD_TERMS)), ("obs_scale", C.c_float * 3),
+                   ("resample_steps", C.c_int32 * 2)]
+                + [(k, C.c_int32) for k in ("curriculum", "lin_vel_levels", "ang_vel_levels", "min_success_steps", "index_order")])
+
+
+class CommandsIn(C.Structure):
+    """``gmr_commands_in_t``: the inputs of ``gmr_motion_tracker_commands[_dev]``, each an address or NULL"""
+    _fields_ = [(k, C.c_void_p) for k in CMD_IN_FIELDS]
+
+
+class CommandsOut(C.Structure):
+    """``gmr_commands_out_t``: the outputs of ``gmr_motion_tracker_commands[_dev]``, each an address or NULL, and the row stride of ``cmd_obs``"""
+    _fields_ = [(k, C.c_void_p) for k in CMD_OUT_FIELDS] + [("cmd_obs_stride", C.c_int64)]
+
+
+class DisturbConfig(C.Structure):
+    """``gmr_disturb_config_t``: the configuration of ``gmr_motion_tracker_set_disturbances``"""
+    _fields_ = ([(k, ProprioNoise) for k in DISTURB_SPECS] + [(k, C.c_int32) for k in ("kick_every", "push_every", "push_duration")]
+                + [("scale_push_force", C.c_float), ("scale_push_torque", C.c_float)])
+
+
+class DisturbIo(C.Structure):
+    """``gmr_disturb_io_t``: what ``gmr_motion_tracker_disturb[_dev]`` writes, each an address or NULL, and the two row strides"""
+    _fields_ = ([(k, C.c_void_p) for k in DISTURB_IO_FIELDS] + [("push_force_stride", C.c_int64), ("push_torque_stride", C.c_int64),
+                                                                ("push_obs", C.c_void_p)])
 
 
 # gmr_motion_tracker_set_preview: the block bits in row order, the frames and the limits (include/gmr_hip.h, "tracker preview")

@@ -4,7 +4,7 @@
 // gmr_tracker_preview.hip reads its state and tables, gmr_tracker_adaptive.hip owns its bins (adaptive sampling, masked resets),
 // gmr_tracker_anchor.hip its anchors, gmr_tracker_control.hip its control tables and the two arrays of the actuator model,
 // gmr_tracker_proprio.hip its proprioception tables and the six arrays behind them, gmr_tracker_feet.hip its terrain, its feet tables and
-// the two arrays behind them.
+// the two arrays behind them, gmr_tracker_commands.hip its command and disturbance tables and the arrays of the velocity commands.
 #pragma once
 #include <stdint.h>
 
@@ -170,6 +170,42 @@ struct FeetState {
   float* last_feet_pos = nullptr;           // [N][2][3]
   float* gait_process = nullptr;            // [N]
 };
+constexpr int CMD_TERMS = 4;              // survival, tracking_lin_vel_x, tracking_lin_vel_y, tracking_ang_vel, the order of include/gmr_hip.h N12
+constexpr int CMD_MAX_LEVELS = 20;        // curriculum levels per axis: a grid of at most 41 x 41 cells
+constexpr int CMD_CHUNK = 8;              // grid cells one lane sums in order (tracker_commands_grid_kernel)
+// the command configuration of a tracker: validated on the host, travels as a kernel argument like ControlTables
+struct CommandTables {
+  int32_t on = 0;                           // 0: commands were never set
+  int32_t curriculum = 0, L = 0, A = 0;     // the grid is [2 L + 1][2 A + 1], the first index is the linear level
+  int32_t G = 0;                            // its cells
+  int32_t order = 0;                        // GMR_CMD_ORDER_GRID / _REFERENCE
+  int32_t min_success = 0;                  // success needs episode_steps > min_success
+  int32_t rs_lo = 1, rs_span = 1;           // cmd_resample_time grows by rs_lo + a draw below rs_span
+  float lo[4] = {}, span[4] = {};           // lin_vel_x, lin_vel_y, ang_vel_yaw, gait_frequency: (float)lower, (float)(upper - lower), the span formed in double
+  float still = 0.0f, sigma = 1.0f;         // (float)still_proportion, (float)tracking_sigma
+  float scale[CMD_TERMS] = {};              // the weights of the total; zero: the term stays out
+  float obs_scale[3] = {};
+  float rate = 0.0f, tol[3] = {}, res[3] = {};
+};
+// the command state of a tracker (device pointers into its command block; see include/gmr_hip.h N12 for the initial values)
+struct CommandState {
+  float* commands = nullptr;                // [N][3]
+  float* gait_frequency = nullptr;          // [N]
+  int32_t* resample_time = nullptr;         // [N]
+  uint32_t* draws = nullptr;                // [N]
+  int32_t* carry = nullptr;                 // [N] the flag bits the first launch of a curriculum call hands to its third
+  int32_t* level = nullptr;                 // [N][2], curriculum only, like the three below
+  float* prob = nullptr;                    // [G]
+  uint32_t* hits = nullptr;                 // [G]
+  double* cum = nullptr;                    // [G + 1]
+};
+// the kicks and pushes of a tracker: travel as a kernel argument; no device state
+struct DisturbTables {
+  int32_t on = 0;                           // 0: disturbances were never set
+  int32_t kick_every = 1, push_every = 1, push_duration = 0;
+  ProprioNoise spec[4];                     // kick_lin_vel, kick_ang_vel, push_force, push_torque
+  float s_force = 1.0f, s_torque = 1.0f;    // the two privileged-observation scales
+};
 }  // namespace gmr
 
 struct gmr_motion_tracker {
@@ -201,6 +237,10 @@ struct gmr_motion_tracker {
   gmr::FeetTables feet;          // feet.E = 0 until gmr_motion_tracker_set_feet configures them
   gmr::FeetState feet_state;
   gmr::DeviceBlock feet_block;   // last_feet_pos and gait_process: one allocation, made by gmr_motion_tracker_set_feet
+  gmr::CommandTables commands;   // commands.on = 0 until gmr_motion_tracker_set_commands configures them
+  gmr::CommandState command_state;
+  gmr::DeviceBlock command_block; // the arrays of command_state: one allocation, made by gmr_motion_tracker_set_commands
+  gmr::DisturbTables disturb;    // disturb.on = 0 until gmr_motion_tracker_set_disturbances configures them
   std::vector<double> clip_w;    // the clip weights as given at creation (empty: uniform)
   std::mutex mu;                 // the tables, and the whole of every synchronous entry point
 };

@@ -18,7 +18,9 @@ follows the physics (``csrc/gmr_tracker_proprio.hip``): th
 with sensor noise, the regularisation penalties, the state-based termination and the roll-over of the ``last_*`` arrays, in one launch.
 :meth:`MotionTracker.set_terrain`, :meth:`MotionTracker.terrain_heights` and :meth:`MotionTracker.feet` close the step (DESIGN.md section 6r,
 ``csrc/gmr_tracker_feet.hip``): the bilinear terrain height the reference interpolates on the host, the feet pose and edge contacts, the gait
-clock, the contact-force termination, ``collision`` and the seven ``feet_*`` terms, in one launch.
+clock, the contact-force termination, ``collision`` and the seven ``feet_*`` terms, in one launch.  :meth:`MotionTracker.commands` and
+:meth:`MotionTracker.disturb` take what was left of the step (``csrc/gmr_tracker_commands.hip``): the velocity commands
+with their resampling and curriculum, the command-tracking terms, and the kicks and pushes.
 
 No GPU framework is imported here: :meth:`MotionTracker.step` takes and returns NumPy arrays, :meth:`MotionTracker.step_dev` reads
 and writes device memory the caller names -- ``_lib.DeviceBuffer``, a raw address, or anything with ``data_ptr()``.
@@ -63,6 +65,14 @@ FEET_MAX_EDGES, FEET_MAX_BODIES = 8, 64
 FEET_DONE_CONTACT = 8                    # the bit of ``done`` of :meth:`MotionTracker.feet`: OR-able with the bits 0 to 2 of :meth:`MotionTracker.proprio`
 FEET_STATE = ("last_feet_pos", "gait_process")
 DEFAULT_FEET = {"force_threshold": 1.0, "contact_clearance": 0.01}          # t1.py:553, :629 and :545
+# the terms of :meth:`MotionTracker.commands` in column order (t1.py:606-620), the bits of its ``flags`` and of :meth:`MotionTracker.disturb`
+CMD_TERMS = ("survival", "tracking_lin_vel_x", "tracking_lin_vel_y", "tracking_ang_vel")
+CMD_MAX_LEVELS = 20
+CMD_BOUNDARY, CMD_RESAMPLED, CMD_SUCCESS = 1, 2, 4
+CMD_INDEX_ORDERS = {"grid": 0, "reference": 1}
+COMMAND_STATE = ("commands", "gait_frequency", "cmd_resample_time", "cmd_draws", "env_level", "curriculum_prob", "hits", "cum")
+DISTURB_KICK, DISTURB_PUSH_START, DISTURB_PUSH_STOP = 1, 2, 4
+DISTURB_SPECS = ("kick_lin_vel", "kick_ang_vel", "push_force", "push_torque")
 LINK_SIM = {"body_pos": (0, 3), "body_rot": (3, 4), "body_vel": (7, 3), "body_ang_vel": (10, 3)}      # offset and width in a packed row of 13
 
 
@@ -172,6 +182,8 @@ class MotionTracker:
         self._control = None          # (R, decimation) once set_control has configured the control half
         self._proprio = None          # (R, extra_cols) once set_proprio has configured the proprioception half
         self._feet = None             # (num_bodies, num_edges) once set_feet has configured the feet
+        self._commands = None         # ((L, A) or None,) once set_commands has configured the velocity commands
+        self._disturb = None          # (kick_every, push_every, push_duration) once set_disturbances has configured kicks and pushes
         if sc is not None or wt is not None:
             self.set_terms(sc, wt)
 
@@ -1203,6 +1215,343 @@ class MotionTracker:
         out = {"last_feet_pos": np.empty((N, 2, 3), np.float32), "gait_process": np.empty(N, np.float32)}
         _lib.check(_lib.lib().gmr_motion_tracker_feet_state(self.handle, *[_lib._ptr(out[k]) for k in FEET_STATE]))
         return out
+
+    # ---- commands, curriculum, kicks and pushes ----------------------------------------------------------
+    @staticmethod
+    def _commands_setup(lin_vel_x, lin_vel_y, ang_vel_yaw, gait_frequency, resample_steps, still_proportion, tracking_sigma, scales, obs_scales,
+                        curriculum):
+        """the checks of :meth:`set_commands`, all of them before the library is loaded -> a dict of the checked values"""
+        def fits(x):
+            with np.errstate(over="ignore"):
+                return bool(np.isfinite(x) and np.isfinite(np.float32(x)))
+        c = {}
+        for name, r in (("lin_vel_x", lin_vel_x), ("lin_vel_y", lin_vel_y), ("ang_vel_yaw", ang_vel_yaw), ("gait_frequency", gait_frequency)):
+            if r is None or len(r) != 2:
+                raise ValueError(f"{name}: a range is a pair (lower, upper), got {r!r}")
+            lo, hi = float(r[0]), float(r[1])
+            if not (fits(lo) and fits(hi) and fits(hi - lo)):
+                raise ValueError(f"{name}: range {(lo, hi)} is not finite in float32")
+            if hi < lo:
+                raise ValueError(f"{name}: upper = {hi} < lower = {lo}")
+            c[name] = (lo, hi)
+        if resample_steps is None or len(resample_steps) != 2 or any(int(x) != x for x in resample_steps):
+            raise ValueError(f"resample_steps: a pair of whole step counts, got {resample_steps!r}")
+        lo, hi = (int(x) for x in resample_steps)
+        if not 1 <= lo < hi < 2 ** 31:
+            raise ValueError(f"resample_steps = {(lo, hi)}: hi > lo >= 1 needed (the caller's int(resampling_time_s / dt) pair)")
+        c["resample_steps"] = (lo, hi)
+        p = float(still_proportion)
+        if not 0.0 <= p <= 1.0:
+            raise ValueError(f"still_proportion = {still_proportion} outside [0, 1]")
+        sg = float(tracking_sigma)
+        if not (fits(sg) and np.float32(sg) > 0):
+            raise ValueError(f"tracking_sigma = {tracking_sigma} must be positive and finite (in float32 too)")
+        c["still_proportion"], c["tracking_sigma"] = p, sg
+        if scales is None:
+            sc = np.zeros(len(CMD_TERMS), np.float32)
+        else:
+            if isinstance(scales, dict):
+                unknown = sorted(set(scales) - set(CMD_TERMS))
+                if unknown:
+                    raise KeyError(f"scales: unknown terms {unknown} (known: {list(CMD_TERMS)})")
+                scales = [scales.get(k, 0.0) for k in CMD_TERMS]
+            with np.errstate(over="ignore"):
+                sc = np.ascontiguousarray(scales, dtype=np.float32).reshape(-1)
+            if len(sc) != len(CMD_TERMS):
+                raise ValueError(f"scales has {len(sc)} entries, there are {len(CMD_TERMS)} terms: {list(CMD_TERMS)}")
+            if not np.isfinite(sc).all():
+                raise ValueError("scales must be finite")
+        with np.errstate(over="ignore"):
+            ob = np.ascontiguousarray((1.0, 1.0, 1.0) if obs_scales is None else obs_scales, dtype=np.float32).reshape(-1)
+        if len(ob) != 3 or not np.isfinite(ob).all():
+            raise ValueError(f"obs_scales: three finite numbers (lin_vel, lin_vel, ang_vel), got {obs_scales!r}")
+        c["scales"], c["obs_scales"], c["curriculum"] = sc, ob, None
+        if curriculum is not None:
+            need = ("lin_vel_levels", "ang_vel_levels", "update_rate", "tolerances", "resolutions", "min_success_steps")
+            unknown, missing = sorted(set(curriculum) - set(need) - {"index_order"}), [k for k in need if k not in curriculum]
+            if unknown or missing:
+                raise KeyError(f"curriculum: unknown keys {unknown}, missing keys {missing}")
+            L, A = curriculum["lin_vel_levels"], curriculum["ang_vel_levels"]
+            if int(L) != L or int(A) != A or not (0 <= L <= CMD_MAX_LEVELS and 0 <= A <= CMD_MAX_LEVELS):
+                raise ValueError(f"curriculum: lin_vel_levels = {L}, ang_vel_levels = {A} are whole numbers in [0, {CMD_MAX_LEVELS}]")
+            order = curriculum.get("index_order", "grid")
+            if order not in CMD_INDEX_ORDERS:
+                raise ValueError(f"curriculum: index_order is one of {sorted(CMD_INDEX_ORDERS)}, got {order!r}")
+            if order == "reference" and int(L) != int(A):
+                raise ValueError(f"curriculum: index_order 'reference' transposes the grid and needs lin_vel_levels == ang_vel_levels, got {(L, A)}")
+            rate = float(curriculum["update_rate"])
+            if not (fits(rate) and rate >= 0):
+                raise ValueError(f"curriculum: update_rate = {rate} must be finite and not negative")
+            tol, res = (tuple(float(x) for x in curriculum[k]) for k in ("tolerances", "resolutions"))
+            if len(tol) != 3 or len(res) != 3 or not all(fits(x) for x in tol + res):
+                raise ValueError(f"curriculum: tolerances {tol} and resolutions {res} are three numbers each, finite in float32")
+            ms = curriculum["min_success_steps"]
+            if int(ms) != ms or not 0 <= ms < 2 ** 31:
+                raise ValueError(f"curriculum: min_success_steps = {ms}, a whole number of steps that is not negative is needed")
+            c["curriculum"] = {"L": int(L), "A": int(A), "order": order, "rate": rate, "tol": tol, "res": res, "min_success_steps": int(ms)}
+        return c
+
+    @staticmethod
+    def min_success_steps(episode_length_s: float, dt: float, episode_length_toler: float) -> int:
+        """``floor(ceil(episode_length_s / dt) * (1 - toler))``: for a whole ``steps``, ``steps > that`` is the reference's comparison at
+        t1.py:394-396"""
+        return int(np.floor(np.ceil(episode_length_s / dt) * (1 - episode_length_toler)))
+
+    def set_commands(self, lin_vel_x, lin_vel_y, ang_vel_yaw, gait_frequency, resample_steps, *, still_proportion: float = 0.0,
+                     tracking_sigma: float = 0.25, scales=None, obs_scales=None, curriculum=None, keep_state: bool = False) -> None:
+        """Configures the velocity commands: the three command ranges and the gait-frequency range ``(lower, upper)``, ``resample_steps
+        (lo, hi)`` -- the caller's ``int(resampling_time_s / dt)`` pair --, ``still_proportion``, ``tracking_sigma``, ``scales`` -- four
+        numbers or a dict over :data:`CMD_TERMS` that weigh ``total`` (zero, the default: the term stays out) --, ``obs_scales`` (``lin_vel,
+        lin_vel, ang_vel`` of the normalisation) and, optionally, ``curriculum``: a dict of ``lin_vel_levels``, ``ang_vel_levels`` (0 to
+        20), ``update_rate``, ``tolerances`` and ``resolutions`` (x, y, yaw), ``min_success_steps`` (:meth:`min_success_steps`) and
+        ``index_order`` -- ``"grid"`` (default) or ``"reference"``, the reference's transposed split of a drawn cell, only for equal level
+        counts.  Allocates the state (zeros; the centre cell of ``curriculum_prob`` is 1).  With ``keep_state`` only the configuration is
+        replaced -- calls already enqueued keep theirs --, and the curriculum's presence and level counts must stay.  Synchronous."""
+        from . import _lib
+        c = self._commands_setup(lin_vel_x, lin_vel_y, ang_vel_yaw, gait_frequency, resample_steps, still_proportion, tracking_sigma, scales,
+                                 obs_scales, curriculum)
+        cur = c["curriculum"]
+        shape = None if cur is None else (cur["L"], cur["A"])
+        if keep_state:
+            old = getattr(self, "_commands", None)
+            if old is None:
+                raise ValueError("set_commands: keep_state needs commands that were set before")
+            if old != (shape,):
+                raise ValueError(f"set_commands: keep_state keeps the curriculum and its levels as they are, {old[0]} is set, {shape} given")
+        cfg = _lib.CommandsConfig()
+        for k in ("lin_vel_x", "lin_vel_y", "ang_vel_yaw", "gait_frequency"):
+            getattr(cfg, k)[:] = c[k]
+        cfg.resample_steps[:] = c["resample_steps"]
+        cfg.still_proportion, cfg.tracking_sigma = c["still_proportion"], c["tracking_sigma"]
+        cfg.scales[:] = c["scales"].tolist()
+        cfg.obs_scale[:] = c["obs_scales"].tolist()
+        if cur is not None:
+            cfg.curriculum, cfg.lin_vel_levels, cfg.ang_vel_levels, cfg.update_rate = 1, cur["L"], cur["A"], cur["rate"]
+            cfg.toler[:], cfg.resolution[:] = cur["tol"], cur["res"]
+            cfg.min_success_steps, cfg.index_order = cur["min_success_steps"], _lib.CMD_INDEX_ORDERS[cur["order"]]
+        _lib.check(_lib.lib().gmr_motion_tracker_set_commands(self.handle, C.byref(cfg), 1 if keep_state else 0))
+        self._commands = (shape,)
+
+    def _need_commands(self, what: str):
+        c = getattr(self, "_commands", None)
+        if c is None:
+            raise ValueError(f"{what}: commands are not set on this tracker, call set_commands() first")
+        return c[0]
+
+    def commands(self, episode_steps, done=None, lin_vel=None, ang_vel=None, cmd_obs=None) -> Dict[str, np.ndarray]:
+        """The command half of a step, host arrays in and out: from ``episode_steps i32[N]`` (after the caller's increment, before any
+        reset), the ``done`` mask (``None``: nobody resets) and the filtered velocities ``lin_vel``, ``ang_vel`` ``[N,3]`` of
+        :meth:`proprio` (optional without a curriculum) -- ``term [N,4]`` in the order of :data:`CMD_TERMS` and ``total [N]`` for the
+        commands of the episode that ends, then the curriculum's bookkeeping, the reset of the resample time of a done environment and the
+        resample where the step count meets it; ``commands [N,3]``, ``gait_frequency [N]`` (what :meth:`feet` takes next step) and ``flags
+        i32[N]`` (:data:`CMD_BOUNDARY`: OR it into the time-outs, :data:`CMD_RESAMPLED`, :data:`CMD_SUCCESS`).  ``cmd_obs`` is a host array
+        ``[N,W]``, ``W >= 3``, or a pair ``(array, column)``: its three columns from ``column`` on get ``commands * obs_scales``, in place.
+        One launch, three with a curriculum; clocks, clips and draw counters of the tracker stay as they are."""
+        from . import _lib
+        shape = self._need_commands("commands")
+        N = self.num_envs
+        steps = self._per_env_ints(episode_steps, "episode_steps")
+        if steps is None:
+            raise ValueError("commands: episode_steps is needed")
+        st, keep = _lib.CommandsIn(episode_steps=steps.ctypes.data), [steps]
+        m = _mask(done, "done", N)
+        if m is not None:
+            st.done = m.ctypes.data
+        if shape is not None and (lin_vel is None or ang_vel is None):
+            raise ValueError("commands: the curriculum needs lin_vel and ang_vel (the filtered velocities)")
+        for k, a in (("lin_vel", lin_vel), ("ang_vel", ang_vel)):
+            if a is None:
+                continue
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.shape != (N, 3):
+                raise ValueError(f"{k}: shape {a.shape}, {(N, 3)} needed")
+            keep.append(a)
+            setattr(st, k, a.ctypes.data)
+        out = {"term": np.empty((N, len(CMD_TERMS)), np.float32), "total": np.empty(N, np.float32), "commands": np.empty((N, 3), np.float32),
+               "gait_frequency": np.empty(N, np.float32), "flags": np.empty(N, np.int32)}
+        table = _lib.CommandsOut(**{k: a.ctypes.data for k, a in out.items()})
+        if cmd_obs is not None:
+            rows, col = cmd_obs if isinstance(cmd_obs, tuple) else (cmd_obs, 0)
+            if not (isinstance(rows, np.ndarray) and rows.dtype == np.float32 and rows.flags.c_contiguous and rows.flags.writeable and rows.ndim == 2
+                    and rows.shape[0] == N):
+                raise ValueError(f"cmd_obs: a writeable C-contiguous float32 array [N = {N}, W] is needed")
+            if int(col) != col or not 0 <= col <= rows.shape[1] - 3:
+                raise ValueError(f"cmd_obs: column {col} leaves no three columns in rows of {rows.shape[1]}")
+            table.cmd_obs, table.cmd_obs_stride = rows.ctypes.data + 4 * int(col), rows.shape[1]
+        _lib.check(_lib.lib().gmr_motion_tracker_commands(self.handle, C.byref(st), C.byref(table)))
+        return out
+
+    def commands_dev(self, episode_steps, done=None, lin_vel=None, ang_vel=None, cmd_obs=None, cmd_obs_stride: int = 3, stream=None,
+                     **outputs) -> None:
+        """:meth:`commands` on device memory, asynchronous on ``stream``: ONE launch, THREE with a curriculum, no host synchronisation.
+        ``outputs`` names whichever of ``term, total, commands, gait_frequency, flags`` are wanted; ``cmd_obs`` is the address of the
+        first command column of environment 0 (``obs + 6`` floats of the row of :meth:`proprio_dev`) and ``cmd_obs_stride`` the row's
+        width in floats.  Every array is a ``_lib.DeviceBuffer``, a raw address or an object with ``data_ptr()``."""
+        from . import _lib
+        shape = self._need_commands("commands_dev")
+        N = self.num_envs
+        outs = {"term": len(CMD_TERMS), "total": 1, "commands": 3, "gait_frequency": 1, "flags": 1}
+        unknown = sorted(set(outputs) - set(outs))
+        if unknown:
+            raise TypeError(f"commands_dev: unknown outputs {unknown}")
+        if episode_steps is None:
+            raise ValueError("commands_dev: episode_steps is needed")
+        if shape is not None and (lin_vel is None or ang_vel is None):
+            raise ValueError("commands_dev: the curriculum needs lin_vel and ang_vel (the filtered velocities)")
+        st, table = _lib.CommandsIn(), _lib.CommandsOut()
+        for k, x, dt, w in (("episode_steps", episode_steps, "int32", 1), ("done", done, "int32", 1), ("lin_vel", lin_vel, "float32", 3),
+                            ("ang_vel", ang_vel, "float32", 3)):
+            p = _dev_ptr(x, k, dt, N * w)
+            setattr(st, k, None if p is None else p.value)
+        for k, x in outputs.items():
+            p = _dev_ptr(x, k, "int32" if k == "flags" else "float32", N * outs[k])
+            setattr(table, k, None if p is None else p.value)
+        if cmd_obs is not None:
+            if int(cmd_obs_stride) != cmd_obs_stride or cmd_obs_stride < 3:
+                raise ValueError(f"commands_dev: cmd_obs_stride = {cmd_obs_stride}, at least 3 floats needed")
+            table.cmd_obs = _dev_ptr(cmd_obs, "cmd_obs", "float32", (N - 1) * int(cmd_obs_stride) + 3).value
+            table.cmd_obs_stride = int(cmd_obs_stride)
+        _lib.check(_lib.lib().gmr_motion_tracker_commands_dev(self.handle, C.byref(st), C.byref(table), _lib._s(stream)))
+
+    def command_state(self) -> Optional[Dict[str, object]]:
+        """``commands f32[N,3]``, ``gait_frequency f32[N]``, ``cmd_resample_time i32[N]``, ``cmd_draws u32[N]`` and, with a curriculum,
+        ``env_level i32[N,2]``, ``curriculum_prob f32[2L+1,2A+1]``, ``hits u32[G]``, ``cum f64[G+1]`` and -- formed here from ``env_level``
+        -- ``mean_lin_vel_level``, ``mean_ang_vel_level``, ``max_lin_vel_level``, ``max_ang_vel_level`` (t1.py:421-424); ``None`` when the
+        commands are not set.  Synchronous."""
+        from . import _lib
+        if getattr(self, "_commands", None) is None:
+            return None
+        shape = self._need_commands("command_state")
+        N = self.num_envs
+        out = {"commands": np.empty((N, 3), np.float32), "gait_frequency": np.empty(N, np.float32), "cmd_resample_time": np.empty(N, np.int32),
+               "cmd_draws": np.empty(N, np.uint32)}
+        if shape is not None:
+            nx, ny = 2 * shape[0] + 1, 2 * shape[1] + 1
+            out.update({"env_level": np.empty((N, 2), np.int32), "curriculum_prob": np.empty((nx, ny), np.float32), "hits": np.empty(nx * ny, np.uint32),
+                        "cum": np.empty(nx * ny + 1, np.float64)})
+        ptrs = [_lib._ptr(out.get(k)) for k in COMMAND_STATE]
+        _lib.check(_lib.lib().gmr_motion_tracker_command_state(self.handle, *ptrs))
+        if shape is not None:
+            mag = np.abs(out["env_level"])
+            out["mean_lin_vel_level"], out["mean_ang_vel_level"] = (float(np.mean(mag[:, k].astype(np.float32))) for k in (0, 1))
+            out["max_lin_vel_level"], out["max_ang_vel_level"] = int(mag[:, 0].max()), int(mag[:, 1].max())
+        return out
+
+    @staticmethod
+    def disturb_actions(common_step: int, kick_every: int, push_every: int, push_duration: int) -> int:
+        """What ``common_step`` does (t1.py:501, :508, :517): :data:`DISTURB_KICK` | :data:`DISTURB_PUSH_START` | :data:`DISTURB_PUSH_STOP`;
+        a stop is the ``elif`` of a start.  The library decides by the same rule."""
+        act = DISTURB_KICK if common_step % kick_every == 0 else 0
+        if common_step % push_every == 0:
+            act |= DISTURB_PUSH_START
+        elif common_step % push_every == push_duration:
+            act |= DISTURB_PUSH_STOP
+        return act
+
+    @staticmethod
+    def _disturb_setup(kick_lin_vel, kick_ang_vel, push_force, push_torque, kick_every, push_every, push_duration, scale_push_force,
+                       scale_push_torque):
+        """the checks of :meth:`set_disturbances`, all of them before the library is loaded -> a dict of the checked values"""
+        specs = []
+        for k, spec in zip(DISTURB_SPECS, (kick_lin_vel, kick_ang_vel, push_force, push_torque)):
+            if spec is None or spec.get("distribution", "none") == "none":
+                specs.append((0, 0, 0.0, 0.0))
+                continue
+            dist, op = spec.get("distribution"), spec.get("operation")
+            if dist not in NOISE_DISTRIBUTIONS:
+                raise ValueError(f"{k}: distribution is one of {sorted(NOISE_DISTRIBUTIONS)}, got {dist!r}")
+            if op not in NOISE_OPERATIONS:
+                raise ValueError(f"{k}: operation is one of {sorted(NOISE_OPERATIONS)}, got {op!r}")
+            rng = spec.get("range")
+            if rng is None or len(rng) != 2:
+                raise ValueError(f"{k}: range is a pair, got {rng!r}")
+            a, b = float(rng[0]), float(rng[1])
+            with np.errstate(over="ignore"):
+                fits = all(np.isfinite(np.float32(x)) for x in (a, b, b - a))
+            if not fits:
+                raise ValueError(f"{k}: range {(a, b)} is not finite in float32")
+            if dist == "gaussian" and b < 0:
+                raise ValueError(f"{k}: a gaussian's deviation {b} is negative")
+            specs.append((NOISE_DISTRIBUTIONS[dist], NOISE_OPERATIONS[op], a, b))
+        for k, v, least in (("kick_every", kick_every, 1), ("push_every", push_every, 1), ("push_duration", push_duration, 0)):
+            if int(v) != v or not least <= v < 2 ** 31:
+                raise ValueError(f"{k} = {v}: a whole number of steps, at least {least}, is needed (the caller's ceil(seconds / dt))")
+        with np.errstate(over="ignore"):
+            sf, st = float(np.float32(scale_push_force)), float(np.float32(scale_push_torque))
+        if not (np.isfinite(sf) and np.isfinite(st)):
+            raise ValueError(f"scale_push_force = {scale_push_force} and scale_push_torque = {scale_push_torque} must be finite")
+        return {"specs": specs, "periods": (int(kick_every), int(push_every), int(push_duration)), "scales": (sf, st)}
+
+    def set_disturbances(self, kick_every: int, push_every: int, push_duration: int, *, kick_lin_vel=None, kick_ang_vel=None, push_force=None,
+                         push_torque=None, scale_push_force: float = 1.0, scale_push_torque: float = 1.0) -> None:
+        """Configures kicks and pushes: the three periods in steps (``ceil(seconds / dt)``), four specs in the form of the ``noise`` of
+        :meth:`set_proprio` (``None``: the block is left alone) and the two privileged-observation scales.  Keeps no device state."""
+        from . import _lib
+        c = self._disturb_setup(kick_lin_vel, kick_ang_vel, push_force, push_torque, kick_every, push_every, push_duration, scale_push_force,
+                                scale_push_torque)
+        cfg = _lib.DisturbConfig()
+        for k, (dist, op, a, b) in zip(DISTURB_SPECS, c["specs"]):
+            s = getattr(cfg, k)
+            s.distribution, s.operation, s.a, s.b = dist, op, a, b
+        cfg.kick_every, cfg.push_every, cfg.push_duration = c["periods"]
+        cfg.scale_push_force, cfg.scale_push_torque = c["scales"]
+        _lib.check(_lib.lib().gmr_motion_tracker_set_disturbances(self.handle, C.byref(cfg)))
+        self._disturb = c["periods"]
+
+    def _need_disturb(self, what: str, common_step):
+        if getattr(self, "_disturb", None) is None:
+            raise ValueError(f"{what}: disturbances are not set on this tracker, call set_disturbances() first")
+        if int(common_step) != common_step or not 0 <= common_step < 2 ** 32:
+            raise ValueError(f"{what}: common_step = {common_step}, a step count in [0, 2^32) is needed")
+        return int(common_step)
+
+    def disturb(self, common_step: int, root_states) -> Dict[str, object]:
+        """Kicks and pushes at ``common_step``, host arrays: ``actions`` (the bits of :meth:`disturb_actions`), ``root_states [N,13]`` (a
+        copy, columns 7 to 12 kicked on a kick step) and, on a step that starts or stops a push, ``push_force``, ``push_torque`` ``[N,3]``
+        and ``push_obs [N,6]`` (zeros at a stop; ``None`` on other steps).  One launch, none on an idle step."""
+        from . import _lib
+        step = self._need_disturb("disturb", common_step)
+        N = self.num_envs
+        rs = np.array(root_states, dtype=np.float32, order="C")
+        if rs.shape != (N, 13):
+            raise ValueError(f"root_states: shape {rs.shape}, {(N, 13)} needed")
+        out = {"push_force": np.zeros((N, 3), np.float32), "push_torque": np.zeros((N, 3), np.float32), "push_obs": np.zeros((N, 6), np.float32)}
+        io = _lib.DisturbIo(root_states=rs.ctypes.data, push_force=out["push_force"].ctypes.data, push_torque=out["push_torque"].ctypes.data,
+                            push_force_stride=3, push_torque_stride=3, push_obs=out["push_obs"].ctypes.data)
+        act = _lib.lib().gmr_motion_tracker_disturb(self.handle, step, C.byref(io))
+        if act < 0:
+            _lib.check(act)
+        if not act & (DISTURB_PUSH_START | DISTURB_PUSH_STOP):
+            out = dict.fromkeys(out)
+        return {"actions": int(act), "root_states": rs, **out}
+
+    def disturb_dev(self, common_step: int, root_states=None, push_force=None, push_torque=None, push_obs=None, push_force_stride: int = 3,
+                    push_torque_stride: int = 3, stream=None) -> int:
+        """:meth:`disturb` on device memory, asynchronous on ``stream``: ONE launch, none on an idle step.  ``root_states f32[N*13]`` is
+        kicked in place; ``push_force`` / ``push_torque`` are the addresses of the base body's row of environment 0 (``forces + base_body *
+        3`` floats) with the environment's row stride in floats (``num_bodies * 3``), so the push lands in the simulator's ``[N, nb, 3]``
+        tensors; ``push_obs f32[N*6]``.  Returns the bits of :meth:`disturb_actions`: with :data:`DISTURB_KICK` hand ``root_states`` back
+        to the simulator."""
+        from . import _lib
+        step = self._need_disturb("disturb_dev", common_step)
+        N = self.num_envs
+        io = _lib.DisturbIo()
+        for k, x, count in (("root_states", root_states, N * 13), ("push_obs", push_obs, N * 6)):
+            p = _dev_ptr(x, k, "float32", count)
+            setattr(io, k, None if p is None else p.value)
+        for k, x, stride in (("push_force", push_force, push_force_stride), ("push_torque", push_torque, push_torque_stride)):
+            if x is None:
+                continue
+            if int(stride) != stride or stride < 3:
+                raise ValueError(f"disturb_dev: {k}_stride = {stride}, at least 3 floats needed")
+            setattr(io, k, _dev_ptr(x, k, "float32", (N - 1) * int(stride) + 3).value)
+            setattr(io, k + "_stride", int(stride))
+        if self.disturb_actions(step, *self._disturb) & DISTURB_KICK and root_states is None:
+            raise ValueError("disturb_dev: a kick step needs root_states")
+        act = _lib.lib().gmr_motion_tracker_disturb_dev(self.handle, step, C.byref(io), _lib._s(stream))
+        if act < 0:
+            _lib.check(act)
+        return int(act)
 
     # ---- the step ---------------------------------------------------------------------------------------------------------
     def _counts(self):

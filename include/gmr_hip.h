@@ -1060,6 +1060,139 @@ int gmr_motion_tracker_feet(gmr_motion_tracker_t* t, const gmr_tracker_links_sim
 /* the two state arrays on the host (last_feet_pos t1.py:495, gait_process :478), either may be NULL; synchronises */
 int gmr_motion_tracker_feet_state(gmr_motion_tracker_t* t, float* last_feet_pos, float* gait_process);
 
+/* ---- N12: tracker commands (velocity commands and their resampling, the command curriculum, kicks and pushes of a motion tracker,
+ * DESIGN.md section 6s) ---- */
+/* What booster_gym/envs/t1.py::step still left to the caller after N10 and N11: _resample_commands / _resample_curriculum_commands
+ * (t1.py:362-389, :415-435), _update_curriculum (:391-413, a Python loop over the reset environments with one device read each), the
+ * three command-tracking rewards and survival (:606-620), the command columns of the observation row (:584), _kick_robots and _push_robots
+ * (:499-527) with the push columns of the privileged block (:598-599).  The statement of record is tests/commands_mirror.py; this is the
+ * same in words.  Everything is float32 with one rounding per operation; a Python number is rounded to float32 where torch rounds it; the
+ * span (upper - lower) of a uniform is formed in double and rounded once.
+ * A. COMMANDS.  CONFIGURATION (a host struct that travels with every launch): gmr_commands_config_t.  STATE (device, owned by the tracker,
+ * one block made by set_commands): commands f32[N][3], gait_frequency f32[N], cmd_resample_time i32[N], cmd_draws u32[N], all zero; with a
+ * curriculum also env_level i32[N][2] (zero), curriculum_prob f32[2L+1][2A+1] (zero, the centre cell 1, t1.py:245-251; the first index is
+ * the linear level), hits u32[G] and cum f64[G + 1] (zero), G = (2L+1)(2A+1).
+ * THE CALL, for environment e (steps = episode_steps[e] after the caller's increment and before any reset; d = done && done[e] != 0;
+ * f = lin_vel[e], g = ang_vel[e]: the filtered velocities gmr_proprio_out_t writes; c = commands[e] of the episode that is ending):
+ *   1. term[e]  = (1, expf(-((c0 - f0) * (c0 - f0)) / (float)sigma), the same with c1, f1, the same with c2, g2) (:606-620); a term whose
+ *                 velocity is absent is 0.  total[e] = sum of scale_k * term_k in rising k over the terms with scale_k != 0 whose input
+ *                 is there.
+ *   2. flags bit 0 (GMR_CMD_BOUNDARY) = steps == cmd_resample_time[e], before any reset: what the caller ORs into time_outs (:558).
+ *   3. with a curriculum and d (:391-413): success = steps > min_success_steps && |f0 - c0| < (float)tol_x && |f1 - c1| < (float)tol_y &&
+ *      |g2 - c2| < (float)tol_yaw; with x = env_level[e][0] + L, y = env_level[e][1] + A a success adds 1 to hits of the cells (x, y),
+ *      (x -+ 1, y), (x, y -+ 1) that lie inside the grid (unsigned integer atomics: arrival order cannot matter).  flags bit 2
+ *      (GMR_CMD_SUCCESS) = success.
+ *   4. with d: cmd_resample_time[e] = 0 and steps = 0 from here on (:314).
+ *   5. with a curriculum, once every environment has done 3: prob[g] = min(prob[g] + (float)rate * (float)hits[g], 1), hits[g] = 0.  THE
+ *      REFERENCE adds rate once per success and clamps at the end: the two differ by float32 rounding unless the sums are exact (they are
+ *      for a rate that is a power of two).  Then cum: lane k sums the GMR_CMD_CHUNK = 8 cells 8k .. 8k + 7 of the flattened grid in rising
+ *      order in double, s_0 = 0, s_{i+1} = s_i + (double)prob[8k + i]; base_0 = 0, base_{k+1} = base_k + s_8 of chunk k, chained in rising
+ *      k; cum[8k + i] = base_k + s_i and cum[G] = base + s of the last chunk's end.  cum is non-decreasing and a cell with prob = 0 has
+ *      cum[g + 1] == cum[g] by construction.
+ *   6. where steps == cmd_resample_time[e] (:362-389): (w0..w3) = philox4x32(counter (e, cmd_draws[e], 0, 2), key), (v0..v3) = the same
+ *      with word 2 = 1; u_k = philox_unit(w_k), u4 = philox_unit(v0); cmd_draws[e] += 1.  Word 3 = 2 keeps these draws apart from the
+ *      resets (0) and the sensor noise (1).
+ *      without a curriculum: c_k = (float)(hi_k - lo_k) * u_k + (float)lo_k, k = 0, 1, 2 (isaacgym's torch_rand_float as restated here;
+ *      not pinned to isaacgym, which no test machine has).
+ *      with one: the cell is the largest g with cum[g] <= (double)v2 * 2^-32 * cum[G]; GMR_CMD_ORDER_REFERENCE splits it as the reference
+ *      does (:417-418), lin = g % ny - L, ang = g / ny - A with ny = 2A + 1 -- the transpose of how _update_curriculum indexes the grid,
+ *      kept as a mode and refused unless L == A --, GMR_CMD_ORDER_GRID is the consistent lin = g / ny - L, ang = g % ny - A;
+ *      env_level[e] = (lin, ang); c0 = ((float)lin + (u0 + -0.5f)) * (float)res_x, c1 = ((float)|lin| * (2.0f * u1 + -1.0f)) *
+ *      (float)res_y, c2 = ((float)ang + (u2 + -0.5f)) * (float)res_yaw (:425-435).
+ *      gait_frequency[e] = (float)(hi - lo) * u3 + (float)lo.  u4 < (float)still_proportion zeroes the three commands and the gait
+ *      frequency.  THE REFERENCE picks exactly int(p n) of the n resampling environments with randperm, a global selection; here every
+ *      environment decides alone: the expected count is the same, the variance binomial.  cmd_resample_time[e] += lo + philox_below(v1,
+ *      hi - lo) of resample_steps.  flags bit 1 (GMR_CMD_RESAMPLED).
+ *   7. the outputs, each an address or NULL, written for every environment: commands, gait_frequency (what gmr_feet_in_t takes next
+ *      step), flags, and cmd_obs[e * cmd_obs_stride + k] = commands[e][k] * obs_scale[k] (point it at obs + 6 with the row's width as
+ *      stride: the row gmr_proprio_out_t.obs got earlier in the step then carries the commands after the resample, as :584 does).
+ * Without a curriculum ONE launch, one lane per environment; with one THREE launches enqueued by the one call (1-4; one workgroup for 5;
+ * 6-7), no host synchronisation between them.  No clock moves and no draw counter of the tracker moves.
+ * B. KICKS AND PUSHES.  No device state.  The host decides from common_step what the step does -- kick: common_step % kick_every == 0;
+ * push start: common_step % push_every == 0; push stop: common_step % push_every == push_duration and not a push start (the elif of
+ * :517) -- and launches nothing on an idle step.  On a step that acts, ONE launch: element i (kick 0..5 = root_states[e][7 + i], push
+ * 6..11 = force then torque) of environment e takes philox4x32(counter (e, common_step, i >> 1, 3), key), words (0, 1) for an even i,
+ * (2, 3) for an odd one, and the recipe of N10 (uniform, gaussian, additive, scaling).  A kick replaces root_states[e][7:13] in place
+ * (:502-503); an element whose block has no spec is left alone and costs no Philox call.  A push start applies the randomisation to zero
+ * (:509-516; a block without a spec gives zero) and writes push_force[e * stride + k], push_torque likewise, and push_obs[e] = (force *
+ * scale_force, torque * scale_torque) (:598-599); a push stop zeroes the same three.  THE REFERENCE reads the observation columns from
+ * body 0 while it pushes base_indice; here push_obs is always the applied push.
+ * The tracker stays SINGLE-STREAM. */
+#define GMR_CMD_TERMS 4                /* survival, tracking_lin_vel_x, tracking_lin_vel_y, tracking_ang_vel */
+#define GMR_CMD_MAX_LEVELS 20
+#define GMR_CMD_CHUNK 8
+#define GMR_CMD_BOUNDARY 1
+#define GMR_CMD_RESAMPLED 2
+#define GMR_CMD_SUCCESS 4
+#define GMR_CMD_ORDER_GRID 0
+#define GMR_CMD_ORDER_REFERENCE 1
+#define GMR_DISTURB_KICK 1
+#define GMR_DISTURB_PUSH_START 2
+#define GMR_DISTURB_PUSH_STOP 4
+typedef struct {            /* the configuration of set_commands: values */
+  double lin_vel_x[2], lin_vel_y[2], ang_vel_yaw[2], gait_frequency[2];   /* (lower, upper) (t1.py:369-380)               */
+  double still_proportion;            /* in [0, 1] (:381)                                                             */
+  double tracking_sigma;              /* > 0 (:612)                                                                   */
+  double update_rate;                 /* (:404), like everything below looked at with a curriculum only               */
+  double toler[3];                    /* lin_vel_x_toler, lin_vel_y_toler, ang_vel_yaw_toler (:397-399)               */
+  double resolution[3];               /* lin_vel_x_resolution, lin_vel_y_resolution, ang_vel_resolution (:427-435)    */
+  float scales[GMR_CMD_TERMS];        /* the weights of the total                                                     */
+  float obs_scale[3];                 /* lin_vel, lin_vel, ang_vel of the normalisation (:584)                        */
+  int32_t resample_steps[2];          /* int(resampling_time_s / dt): hi > lo >= 1 (:385-386)                         */
+  int32_t curriculum;                 /* 0 or 1                                                                       */
+  int32_t lin_vel_levels, ang_vel_levels;   /* L, A in [0, GMR_CMD_MAX_LEVELS]                                        */
+  int32_t min_success_steps;          /* floor(ceil(episode_length_s / dt) * (1 - episode_length_toler)) (:394-396)   */
+  int32_t index_order;                /* GMR_CMD_ORDER_*                                                              */
+} gmr_commands_config_t;
+typedef struct {            /* the inputs of a commands call: device pointers (gmr_motion_tracker_commands: host pointers) */
+  const int32_t *episode_steps;       /* [N]                                                                          */
+  const int32_t *done;                /* [N] or NULL: nobody resets                                                   */
+  const float *lin_vel, *ang_vel;     /* [N][3] the filtered velocities, or NULL (GMR_ERR_ARG with a curriculum)      */
+} gmr_commands_in_t;
+typedef struct {            /* the outputs of a commands call, each an address or NULL */
+  float *term;                        /* [N][GMR_CMD_TERMS]                                                           */
+  float *total;                       /* [N]                                                                          */
+  float *commands;                    /* [N][3]                                                                       */
+  float *gait_frequency;              /* [N]                                                                          */
+  int32_t *flags;                     /* [N] GMR_CMD_BOUNDARY | GMR_CMD_RESAMPLED | GMR_CMD_SUCCESS                   */
+  float *cmd_obs;                     /* row e at cmd_obs + e * cmd_obs_stride, three floats                          */
+  int64_t cmd_obs_stride;             /* in floats, >= 3 when cmd_obs is given                                        */
+} gmr_commands_out_t;
+typedef struct {            /* the configuration of set_disturbances */
+  gmr_proprio_noise_t kick_lin_vel, kick_ang_vel, push_force, push_torque;   /* (t1.py:502-503, :509-516)             */
+  int32_t kick_every, push_every;     /* ceil(kick_interval_s / dt), ceil(push_interval_s / dt): >= 1 (:501, :508)    */
+  int32_t push_duration;              /* ceil(push_duration_s / dt): >= 0 (:517)                                      */
+  float scale_push_force, scale_push_torque;   /* (:598-599)                                                          */
+} gmr_disturb_config_t;
+typedef struct {            /* what a disturb call writes: device pointers (gmr_motion_tracker_disturb: host pointers) */
+  float *root_states;                 /* [N][13], columns 7..12 replaced by a kick; needed on a kick step             */
+  float *push_force, *push_torque;    /* row e at base + e * stride, three floats; each may be NULL                   */
+  int64_t push_force_stride, push_torque_stride;   /* in floats, >= 3 where the address is given                     */
+  float *push_obs;                    /* [N][6] or NULL                                                               */
+} gmr_disturb_io_t;
+/* The command configuration (t1.py:362-435, :606-620): every value finite (in float32 too), upper >= lower, still_proportion in [0, 1],
+ * resample_steps hi > lo >= 1, tracking_sigma > 0 as a float32; with a curriculum L, A in [0, GMR_CMD_MAX_LEVELS], update_rate >= 0, the
+ * tolerances and resolutions finite, min_success_steps >= 0, GMR_CMD_ORDER_REFERENCE only with L == A.  keep_state = 0 allocates the state
+ * and gives it its initial values (synchronises the device); keep_state = 1 replaces the configuration alone and is GMR_ERR_ARG when
+ * commands were never set or curriculum, L or A differ.  Launches in flight keep the configuration they carry. */
+int gmr_motion_tracker_set_commands(gmr_motion_tracker_t* t, const gmr_commands_config_t* cfg, int keep_state);
+/* The call (t1.py:362-435, :558, :584, :606-620): ONE launch, THREE with a curriculum */
+int gmr_motion_tracker_commands_dev(gmr_motion_tracker_t* t, const gmr_commands_in_t* in, const gmr_commands_out_t* out,
+                                    void* stream);                                                  /* asynchronous */
+int gmr_motion_tracker_commands(gmr_motion_tracker_t* t, const gmr_commands_in_t* in, const gmr_commands_out_t* out);
+/* the state arrays on the host (t1.py:240-251), each may be NULL; the last four are GMR_ERR_ARG to ask for without a curriculum;
+ * synchronises.  mean and max of |env_level| (:421-424) are the caller's to form from env_level. */
+int gmr_motion_tracker_command_state(gmr_motion_tracker_t* t, float* commands, float* gait_frequency, int32_t* cmd_resample_time,
+                                     uint32_t* cmd_draws, int32_t* env_level, float* curriculum_prob, uint32_t* hits, double* cum);
+/* The kicks and pushes (t1.py:499-527): each spec as in N10 (b >= 0 for a gaussian), kick_every and push_every >= 1, push_duration >= 0,
+ * the two scales finite.  Touches no device. */
+int gmr_motion_tracker_set_disturbances(gmr_motion_tracker_t* t, const gmr_disturb_config_t* cfg);
+/* _kick_robots and _push_robots (t1.py:499-527, :598-599) at common_step, ONE launch or none.  Returns GMR_DISTURB_KICK |
+ * GMR_DISTURB_PUSH_START | GMR_DISTURB_PUSH_STOP, what the step did (0: idle, nothing launched, nothing written), or a negative GMR_ERR_*;
+ * with the kick bit the caller hands root_states back to the simulator. */
+int gmr_motion_tracker_disturb_dev(gmr_motion_tracker_t* t, uint32_t common_step, const gmr_disturb_io_t* io, void* stream);   /* asynchronous */
+int gmr_motion_tracker_disturb(gmr_motion_tracker_t* t, uint32_t common_step, const gmr_disturb_io_t* io);
+
 /* ---- multi-GPU: one rank per GPU, ONE broadcast, no per-step collective ------------ */
 /* The reference parallelises over files with mp.Pool on one CPU (scripts/smplx_to_robot_dataset.py:241-242); here
  * streams shard over the ranks of one node and the only data that crosses ranks is the packed robot model + task set.
