@@ -116,6 +116,16 @@ def build_split_probe(force: bool = False) -> str:
     return out
 
 
+# The probe of the folded row broadcasts and of div_const (tests/hip/rowfma_probe.hip, tests/test_row_bcast_fma.py), under the
+# library's own flags.
+ROWFMA_PROBE_SRC = os.path.join(os.path.dirname(PROBE_SRC), "rowfma_probe.hip")
+ROWFMA_PROBE_LIB = os.path.join(os.path.dirname(PROBE_SRC), "libgmr_rowfma_probe.so")
+
+
+def build_rowfma_probe(force: bool = False) -> str:
+    return _build_probe_libs(ROWFMA_PROBE_SRC, {"flags": ROWFMA_PROBE_LIB}, force)["flags"]
+
+
 def build_variant(name: str, defines=(), verbose: bool = False) -> str:
     """libgmrhip_<name>.so with extra -D flags on every source (objects cached per flag set)."""
     out = os.path.join(HERE, f"libgmrhip_{name}.so")

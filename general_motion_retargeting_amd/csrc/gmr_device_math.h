@@ -58,6 +58,27 @@ __device__ __forceinline__ d4 axis_angle(d3 axis, double angle) {
   return {c, axis.x * s, axis.y * s, axis.z * s};
 }
 
+// x / c for a LITERAL c, bit for bit what the division gives, in three instructions instead of the ~14 of the IEEE
+// sequence (v_div_scale x 2, v_rcp, Newton steps, v_div_fmas, v_div_fixup): rc = 1 / c is folded at compile time,
+// q = x rc is within an ulp of the quotient, r = x - q c is exact (one fused operation) and q + r rc rounds to the
+// quotient.  tests/test_div_const.py checks every literal the series below divide by (6, 120, 720, 5040, 40320,
+// 362880, 3628800, 39916800, 47900160) with exact rationals, random numerators and numerators next to the rounding
+// midpoints of the quotient; no literal has shown a counterexample, none keeps a true division.
+// Domain: a finite x with |x| >= 1e-290, or x == 0 (+-0 keep their sign).  Below that the quotient may differ in a
+// subnormal bit, which no caller's sum can see (every quotient is added to a term of order 1e-8 or more).  A
+// non-finite x yields NaN where the division gave +-inf (inf - inf in r); both end a stream.
+// GMR_NO_DIV_CONST restores the division (A/B builds).
+__device__ __forceinline__ double div_const(double x, double c) {
+#ifdef GMR_NO_DIV_CONST
+  return x / c;
+#else
+  const double rc = 1.0 / c;
+  const double q = x * rc;
+  const double r = __builtin_fma(-q, c, x);
+  return __builtin_fma(r, rc, q);
+#endif
+}
+
 // SO3 log of a unit quaternion (|w| <= pi), mink/jaxlie branch structure (App. A.5)
 __device__ __forceinline__ d3 so3_log(d4 q) {
   double n2 = q.x * q.x + q.y * q.y + q.z * q.z;
@@ -75,7 +96,7 @@ __device__ __forceinline__ d3 so3_log(d4 q) {
 // coefficient a of K^2 in  I - K/2 + a K^2  (V^-1 of SE3.log and Jl^-1 of SO3 share it)
 __device__ __forceinline__ double vinv_coef(double t2) {
   if (t2 < 1e-2)
-    return 1.0 / 12.0 + t2 * (1.0 / 720.0 + t2 * (1.0 / 30240.0 + t2 * (1.0 / 1209600.0 + t2 / 47900160.0)));
+    return 1.0 / 12.0 + t2 * (1.0 / 720.0 + t2 * (1.0 / 30240.0 + t2 * (1.0 / 1209600.0 + div_const(t2, 47900160.0))));
   double t = sqrt(t2), h = 0.5 * t, s, c;
   sincos(h, &s, &c);
   return (1.0 - h * c / s) / t2;
@@ -86,7 +107,7 @@ __device__ __forceinline__ double vinv_coef(double t2) {
 __device__ __forceinline__ double vinv_coef_sc(double t2, double& sin_t, double& cos_t) {
   if (t2 < 1e-2) {
     sin_t = 0.0; cos_t = 1.0;
-    return 1.0 / 12.0 + t2 * (1.0 / 720.0 + t2 * (1.0 / 30240.0 + t2 * (1.0 / 1209600.0 + t2 / 47900160.0)));
+    return 1.0 / 12.0 + t2 * (1.0 / 720.0 + t2 * (1.0 / 30240.0 + t2 * (1.0 / 1209600.0 + div_const(t2, 47900160.0))));
   }
   double t = sqrt(t2), h = 0.5 * t, s, c;
   sincos(h, &s, &c);
@@ -149,15 +170,15 @@ __device__ __forceinline__ void se3_jlinv_aux(const double e[6], const double au
   const double a = aux[0];
   double c1, c2, c3;
   if (t2 < 1e-2) {
-    c1 = 1.0 / 6.0 - t2 / 120.0 + t2 * t2 / 5040.0 - t2 * t2 * t2 / 362880.0;
-    c2 = -1.0 / 24.0 + t2 / 720.0 - t2 * t2 / 40320.0 + t2 * t2 * t2 / 3628800.0;
-    c3 = -1.0 / 120.0 + t2 / 5040.0 - t2 * t2 / 362880.0 + t2 * t2 * t2 / 39916800.0;
+    c1 = 1.0 / 6.0 - div_const(t2, 120.0) + div_const(t2 * t2, 5040.0) - div_const(t2 * t2 * t2, 362880.0);
+    c2 = -1.0 / 24.0 + div_const(t2, 720.0) - div_const(t2 * t2, 40320.0) + div_const(t2 * t2 * t2, 3628800.0);
+    c3 = -1.0 / 120.0 + div_const(t2, 5040.0) - div_const(t2 * t2, 362880.0) + div_const(t2 * t2 * t2, 39916800.0);
   } else {
     double t = sqrt(t2), sn = aux[1], cs = aux[2];
     double it2 = 1.0 / t2, it = 1.0 / t;
     c1 = (t - sn) * it2 * it;
     c2 = (1.0 - 0.5 * t2 - cs) * it2 * it2;
-    c3 = (t - sn - t2 * t / 6.0) * it2 * it2 * it;
+    c3 = (t - sn - div_const(t2 * t, 6.0)) * it2 * it2 * it;
   }
   const double c4 = -0.5 * (c2 - 3.0 * c3);
   const double s = dot(w, rho);
@@ -266,7 +287,7 @@ __device__ __forceinline__ void se3_log_rel5(d3 pb, d4 qb, d3 pt, d4 qt, double 
   double a;
   if (t2 < 1e-2) {
     aux[1] = 0.0; aux[2] = 1.0; aux[3] = 0.0; aux[4] = 0.0;
-    a = 1.0 / 12.0 + t2 * (1.0 / 720.0 + t2 * (1.0 / 30240.0 + t2 * (1.0 / 1209600.0 + t2 / 47900160.0)));
+    a = 1.0 / 12.0 + t2 * (1.0 / 720.0 + t2 * (1.0 / 30240.0 + t2 * (1.0 / 1209600.0 + div_const(t2, 47900160.0))));
   } else {                      // t >= 0.1: the main branch above was taken
     const double t = 2.0 * half, inv_t = fast_rcp(t);
     aux[1] = 2.0 * sh * ch;
@@ -293,15 +314,15 @@ __device__ __forceinline__ void se3_jlinv_aux5(const double e[6], const double a
   const double a = aux[0];
   double c1, c2, c3;
   if (t2 < 1e-2) {
-    c1 = 1.0 / 6.0 - t2 / 120.0 + t2 * t2 / 5040.0 - t2 * t2 * t2 / 362880.0;
-    c2 = -1.0 / 24.0 + t2 / 720.0 - t2 * t2 / 40320.0 + t2 * t2 * t2 / 3628800.0;
-    c3 = -1.0 / 120.0 + t2 / 5040.0 - t2 * t2 / 362880.0 + t2 * t2 * t2 / 39916800.0;
+    c1 = 1.0 / 6.0 - div_const(t2, 120.0) + div_const(t2 * t2, 5040.0) - div_const(t2 * t2 * t2, 362880.0);
+    c2 = -1.0 / 24.0 + div_const(t2, 720.0) - div_const(t2 * t2, 40320.0) + div_const(t2 * t2 * t2, 3628800.0);
+    c3 = -1.0 / 120.0 + div_const(t2, 5040.0) - div_const(t2 * t2, 362880.0) + div_const(t2 * t2 * t2, 39916800.0);
   } else {
     const double t = aux[3], it = aux[4], sn = aux[1], cs = aux[2];
     const double it2 = it * it;
     c1 = (t - sn) * it2 * it;
     c2 = (1.0 - 0.5 * t2 - cs) * it2 * it2;
-    c3 = (t - sn - t2 * t / 6.0) * it2 * it2 * it;
+    c3 = (t - sn - div_const(t2 * t, 6.0)) * it2 * it2 * it;
   }
   const double c4 = -0.5 * (c2 - 3.0 * c3);
   const double s = dot(w, rho);
@@ -340,15 +361,15 @@ __device__ __forceinline__ void se3_jlinv_col5(const double e[6], const double a
   const double a = aux[0];
   double c1, c2, c3;
   if (t2 < 1e-2) {
-    c1 = 1.0 / 6.0 - t2 / 120.0 + t2 * t2 / 5040.0 - t2 * t2 * t2 / 362880.0;
-    c2 = -1.0 / 24.0 + t2 / 720.0 - t2 * t2 / 40320.0 + t2 * t2 * t2 / 3628800.0;
-    c3 = -1.0 / 120.0 + t2 / 5040.0 - t2 * t2 / 362880.0 + t2 * t2 * t2 / 39916800.0;
+    c1 = 1.0 / 6.0 - div_const(t2, 120.0) + div_const(t2 * t2, 5040.0) - div_const(t2 * t2 * t2, 362880.0);
+    c2 = -1.0 / 24.0 + div_const(t2, 720.0) - div_const(t2 * t2, 40320.0) + div_const(t2 * t2 * t2, 3628800.0);
+    c3 = -1.0 / 120.0 + div_const(t2, 5040.0) - div_const(t2 * t2, 362880.0) + div_const(t2 * t2 * t2, 39916800.0);
   } else {
     const double t = aux[3], it = aux[4], sn = aux[1], cs = aux[2];
     const double it2 = it * it;
     c1 = (t - sn) * it2 * it;
     c2 = (1.0 - 0.5 * t2 - cs) * it2 * it2;
-    c3 = (t - sn - t2 * t / 6.0) * it2 * it2 * it;
+    c3 = (t - sn - div_const(t2 * t, 6.0)) * it2 * it2 * it;
   }
   const double c4 = -0.5 * (c2 - 3.0 * c3);
   const double s = dot(w, rho);
@@ -388,15 +409,15 @@ __device__ __forceinline__ void se3_jlinv_coef5(const double e[6], const double 
   const double a = aux[0];
   double c1, c2, c3;
   if (t2 < 1e-2) {
-    c1 = 1.0 / 6.0 - t2 / 120.0 + t2 * t2 / 5040.0 - t2 * t2 * t2 / 362880.0;
-    c2 = -1.0 / 24.0 + t2 / 720.0 - t2 * t2 / 40320.0 + t2 * t2 * t2 / 3628800.0;
-    c3 = -1.0 / 120.0 + t2 / 5040.0 - t2 * t2 / 362880.0 + t2 * t2 * t2 / 39916800.0;
+    c1 = 1.0 / 6.0 - div_const(t2, 120.0) + div_const(t2 * t2, 5040.0) - div_const(t2 * t2 * t2, 362880.0);
+    c2 = -1.0 / 24.0 + div_const(t2, 720.0) - div_const(t2 * t2, 40320.0) + div_const(t2 * t2 * t2, 3628800.0);
+    c3 = -1.0 / 120.0 + div_const(t2, 5040.0) - div_const(t2 * t2, 362880.0) + div_const(t2 * t2 * t2, 39916800.0);
   } else {
     const double t = aux[3], it = aux[4], sn = aux[1], cs = aux[2];
     const double it2 = it * it;
     c1 = (t - sn) * it2 * it;
     c2 = (1.0 - 0.5 * t2 - cs) * it2 * it2;
-    c3 = (t - sn - t2 * t / 6.0) * it2 * it2 * it;
+    c3 = (t - sn - div_const(t2 * t, 6.0)) * it2 * it2 * it;
   }
   const double c4 = -0.5 * (c2 - 3.0 * c3);
   const double s = dot(w, rho);
@@ -442,7 +463,7 @@ __device__ __forceinline__ void se3_log_rel5_rot(d4 qb, d4 qt, double w3[3], dou
   double a;
   if (t2 < 1e-2) {
     aux[1] = 0.0; aux[2] = 1.0; aux[3] = 0.0; aux[4] = 0.0;
-    a = 1.0 / 12.0 + t2 * (1.0 / 720.0 + t2 * (1.0 / 30240.0 + t2 * (1.0 / 1209600.0 + t2 / 47900160.0)));
+    a = 1.0 / 12.0 + t2 * (1.0 / 720.0 + t2 * (1.0 / 30240.0 + t2 * (1.0 / 1209600.0 + div_const(t2, 47900160.0))));
   } else {
     const double t = 2.0 * half, inv_t = fast_rcp(t);
     aux[1] = 2.0 * sh * ch;
@@ -563,6 +584,192 @@ __device__ __forceinline__ double row_bcast_d(double v, int k) {
   return __builtin_bit_cast(double, y);
 }
 #undef GMR_ROW_BCAST_CASE
+
+// ---- row broadcasts folded into the multiply-add that consumes them ------------------------------------------------
+// acc +- bcast_row(v, K) * m as ONE instruction: gfx90a+ has v_fmac_f64 as a VOP2 instruction with a DPP form, and
+// row_newbcast is the one control it executes on 64-bit operands.  The compiler never folds the v_mov_b64_dpp of
+// row_bcast_d into its consumer (checked on the assembly, every spelling of the source), so the instruction is written
+// out.  fmac is the fused multiply-add of the same three numbers: no bit of any result changes.
+// Inline assembly hides the DPP hazards from the compiler, so every statement carries them itself:
+//   * a DPP source written by the instruction before needs 2 wait states: every statement STARTS with s_nop 1;
+//   * a result that is read through DPP next (the next pivot's diagonal) is broadcast INSIDE the statement, behind
+//     another s_nop 1 (row_bcast_fnma_bcast); no other result of these statements is the source of a DPP read before
+//     an ordinary instruction has rewritten it (gmr_ik_tree.h: products, stores and selects follow);
+//   * no statement writes EXEC, and the callers run with all lanes enabled (a disabled source lane would leave the
+//     accumulator as it is, which is also what the zero of bound_ctrl:1 gives).
+// To pay the s_nop once per pivot and not once per update, the multi-update forms put a whole run into one statement.
+// GMR_NO_ROW_FMA restores row_bcast_d + fma (A/B builds).
+#define GMR_RF_CTRL " row_mask:0xf bank_mask:0xf\n\t"
+template <int K, bool NEG>
+__device__ __forceinline__ double row_bcast_fma(double acc, double v, double m) {   // acc +- bcast(v, K) m
+  static_assert(K >= 0 && K < 16, "row_newbcast takes a lane of the 16-lane row");
+#ifdef GMR_NO_ROW_FMA
+  return fma(NEG ? -row_bcast_d(v, K) : row_bcast_d(v, K), m, acc);
+#else
+  if (NEG) asm("s_nop 1\n\tv_fmac_f64_dpp %0, %1, -%2 row_newbcast:%3" GMR_RF_CTRL : "+v"(acc) : "v"(v), "v"(m), "n"(K));
+  else asm("s_nop 1\n\tv_fmac_f64_dpp %0, %1, %2 row_newbcast:%3" GMR_RF_CTRL : "+v"(acc) : "v"(v), "v"(m), "n"(K));
+  return acc;
+#endif
+}
+// acc -= bcast(l, K) l, and the new acc of lane K handed to the whole row: the first column update of a pivot and the
+// next pivot's diagonal
+template <int K>
+__device__ __forceinline__ double row_bcast_fnma_bcast(double& acc, double l) {
+  static_assert(K >= 0 && K < 16, "row_newbcast takes a lane of the 16-lane row");
+#ifdef GMR_NO_ROW_FMA
+  acc = fma(-l, row_bcast_d(l, K), acc);
+  return row_bcast_d(acc, K);
+#else
+  double d;
+  asm("s_nop 1\n\tv_fmac_f64_dpp %0, %2, -%2 row_newbcast:%3" GMR_RF_CTRL
+      "s_nop 1\n\tv_mov_b64_dpp %1, %0 row_newbcast:%3 row_mask:0xf bank_mask:0xf bound_ctrl:1"
+      : "+v"(acc), "=v"(d) : "v"(l), "n"(K));
+  return d;
+#endif
+}
+// r[i] -= bcast(l, K0 + i) l for i < N: all column updates of one pivot behind one s_nop (they read the same l, none
+// reads another's result)
+#define GMR_RF_COL(i) "v_fmac_f64_dpp %[a" #i "], %[l], -%[l] row_newbcast:%[k]+" #i GMR_RF_CTRL
+#define GMR_RF_ACC(i) [a##i] "+v"(r[i])
+#define GMR_RF_COLS(N, TEXT, ...) if constexpr (N_ == N) asm("s_nop 1\n\t" TEXT : __VA_ARGS__ : [l] "v"(l), [k] "n"(K0));
+template <int K0, int N_>
+__device__ __forceinline__ void row_bcast_fnma_cols(double* r, double l) {
+  static_assert(N_ >= 0 && N_ <= 14 && K0 >= 0 && K0 + N_ <= 16, "at most 14 columns of one 16-lane row");
+#ifdef GMR_NO_ROW_FMA
+#pragma unroll
+  for (int i = 0; i < N_; i++) r[i] = fma(-l, row_bcast_d(l, K0 + i), r[i]);
+#else
+#define GMR_RF_T1 GMR_RF_COL(0)
+#define GMR_RF_T2 GMR_RF_T1 GMR_RF_COL(1)
+#define GMR_RF_T3 GMR_RF_T2 GMR_RF_COL(2)
+#define GMR_RF_T4 GMR_RF_T3 GMR_RF_COL(3)
+#define GMR_RF_T5 GMR_RF_T4 GMR_RF_COL(4)
+#define GMR_RF_T6 GMR_RF_T5 GMR_RF_COL(5)
+#define GMR_RF_T7 GMR_RF_T6 GMR_RF_COL(6)
+#define GMR_RF_T8 GMR_RF_T7 GMR_RF_COL(7)
+#define GMR_RF_T9 GMR_RF_T8 GMR_RF_COL(8)
+#define GMR_RF_T10 GMR_RF_T9 GMR_RF_COL(9)
+#define GMR_RF_T11 GMR_RF_T10 GMR_RF_COL(10)
+#define GMR_RF_T12 GMR_RF_T11 GMR_RF_COL(11)
+#define GMR_RF_T13 GMR_RF_T12 GMR_RF_COL(12)
+#define GMR_RF_T14 GMR_RF_T13 GMR_RF_COL(13)
+#define GMR_RF_A1 GMR_RF_ACC(0)
+#define GMR_RF_A2 GMR_RF_A1, GMR_RF_ACC(1)
+#define GMR_RF_A3 GMR_RF_A2, GMR_RF_ACC(2)
+#define GMR_RF_A4 GMR_RF_A3, GMR_RF_ACC(3)
+#define GMR_RF_A5 GMR_RF_A4, GMR_RF_ACC(4)
+#define GMR_RF_A6 GMR_RF_A5, GMR_RF_ACC(5)
+#define GMR_RF_A7 GMR_RF_A6, GMR_RF_ACC(6)
+#define GMR_RF_A8 GMR_RF_A7, GMR_RF_ACC(7)
+#define GMR_RF_A9 GMR_RF_A8, GMR_RF_ACC(8)
+#define GMR_RF_A10 GMR_RF_A9, GMR_RF_ACC(9)
+#define GMR_RF_A11 GMR_RF_A10, GMR_RF_ACC(10)
+#define GMR_RF_A12 GMR_RF_A11, GMR_RF_ACC(11)
+#define GMR_RF_A13 GMR_RF_A12, GMR_RF_ACC(12)
+#define GMR_RF_A14 GMR_RF_A13, GMR_RF_ACC(13)
+  GMR_RF_COLS(1, GMR_RF_T1, GMR_RF_A1) GMR_RF_COLS(2, GMR_RF_T2, GMR_RF_A2) GMR_RF_COLS(3, GMR_RF_T3, GMR_RF_A3)
+  GMR_RF_COLS(4, GMR_RF_T4, GMR_RF_A4) GMR_RF_COLS(5, GMR_RF_T5, GMR_RF_A5) GMR_RF_COLS(6, GMR_RF_T6, GMR_RF_A6)
+  GMR_RF_COLS(7, GMR_RF_T7, GMR_RF_A7) GMR_RF_COLS(8, GMR_RF_T8, GMR_RF_A8) GMR_RF_COLS(9, GMR_RF_T9, GMR_RF_A9)
+  GMR_RF_COLS(10, GMR_RF_T10, GMR_RF_A10) GMR_RF_COLS(11, GMR_RF_T11, GMR_RF_A11) GMR_RF_COLS(12, GMR_RF_T12, GMR_RF_A12)
+  GMR_RF_COLS(13, GMR_RF_T13, GMR_RF_A13) GMR_RF_COLS(14, GMR_RF_T14, GMR_RF_A14)
+#endif
+}
+// acc +- sum over i < N of bcast(v, K0 + S i) m[S i]: one dependent chain behind one s_nop (the products of a row of
+// H, of Y_l^T, with a vector that lives in the lanes of the row)
+#define GMR_RF_DOT(SG, i) "v_fmac_f64_dpp %[acc], %[v], " SG "%[m" #i "] row_newbcast:%[k]+%[s]*" #i GMR_RF_CTRL
+#define GMR_RF_M(i) [m##i] "v"(m[S * i])
+#define GMR_RF_DOTS(N, ...)                                                                                         \
+  if constexpr (N_ == N) {                                                                                          \
+    if (NEG) asm("s_nop 1\n\t" GMR_RF_D##N("-") : [acc] "+v"(acc) : [v] "v"(v), [k] "n"(K0), [s] "n"(S), __VA_ARGS__);  \
+    else asm("s_nop 1\n\t" GMR_RF_D##N("") : [acc] "+v"(acc) : [v] "v"(v), [k] "n"(K0), [s] "n"(S), __VA_ARGS__);       \
+  }
+template <int K0, int S, int N_, bool NEG>
+__device__ __forceinline__ double row_bcast_fma_dot(double acc, double v, const double* m) {
+  static_assert(N_ >= 1 && N_ <= 10 && S >= 1 && K0 >= 0 && K0 + S * (N_ - 1) < 16, "at most 10 lanes of one 16-lane row");
+#ifdef GMR_NO_ROW_FMA
+#pragma unroll
+  for (int i = 0; i < N_; i++) acc = fma(NEG ? -row_bcast_d(v, K0 + S * i) : row_bcast_d(v, K0 + S * i), m[S * i], acc);
+#else
+#define GMR_RF_D1(SG) GMR_RF_DOT(SG, 0)
+#define GMR_RF_D2(SG) GMR_RF_D1(SG) GMR_RF_DOT(SG, 1)
+#define GMR_RF_D3(SG) GMR_RF_D2(SG) GMR_RF_DOT(SG, 2)
+#define GMR_RF_D4(SG) GMR_RF_D3(SG) GMR_RF_DOT(SG, 3)
+#define GMR_RF_D5(SG) GMR_RF_D4(SG) GMR_RF_DOT(SG, 4)
+#define GMR_RF_D6(SG) GMR_RF_D5(SG) GMR_RF_DOT(SG, 5)
+#define GMR_RF_D7(SG) GMR_RF_D6(SG) GMR_RF_DOT(SG, 6)
+#define GMR_RF_D8(SG) GMR_RF_D7(SG) GMR_RF_DOT(SG, 7)
+#define GMR_RF_D9(SG) GMR_RF_D8(SG) GMR_RF_DOT(SG, 8)
+#define GMR_RF_D10(SG) GMR_RF_D9(SG) GMR_RF_DOT(SG, 9)
+#define GMR_RF_M1 GMR_RF_M(0)
+#define GMR_RF_M2 GMR_RF_M1, GMR_RF_M(1)
+#define GMR_RF_M3 GMR_RF_M2, GMR_RF_M(2)
+#define GMR_RF_M4 GMR_RF_M3, GMR_RF_M(3)
+#define GMR_RF_M5 GMR_RF_M4, GMR_RF_M(4)
+#define GMR_RF_M6 GMR_RF_M5, GMR_RF_M(5)
+#define GMR_RF_M7 GMR_RF_M6, GMR_RF_M(6)
+#define GMR_RF_M8 GMR_RF_M7, GMR_RF_M(7)
+#define GMR_RF_M9 GMR_RF_M8, GMR_RF_M(8)
+#define GMR_RF_M10 GMR_RF_M9, GMR_RF_M(9)
+  GMR_RF_DOTS(1, GMR_RF_M1) GMR_RF_DOTS(2, GMR_RF_M2) GMR_RF_DOTS(3, GMR_RF_M3) GMR_RF_DOTS(4, GMR_RF_M4) GMR_RF_DOTS(5, GMR_RF_M5)
+  GMR_RF_DOTS(6, GMR_RF_M6) GMR_RF_DOTS(7, GMR_RF_M7) GMR_RF_DOTS(8, GMR_RF_M8) GMR_RF_DOTS(9, GMR_RF_M9) GMR_RF_DOTS(10, GMR_RF_M10)
+#endif
+  return acc;
+}
+#undef GMR_RF_M
+#undef GMR_RF_A1
+#undef GMR_RF_A2
+#undef GMR_RF_A3
+#undef GMR_RF_A4
+#undef GMR_RF_A5
+#undef GMR_RF_A6
+#undef GMR_RF_A7
+#undef GMR_RF_A8
+#undef GMR_RF_A9
+#undef GMR_RF_D1
+#undef GMR_RF_D2
+#undef GMR_RF_D3
+#undef GMR_RF_D4
+#undef GMR_RF_D5
+#undef GMR_RF_D6
+#undef GMR_RF_D7
+#undef GMR_RF_D8
+#undef GMR_RF_D9
+#undef GMR_RF_M1
+#undef GMR_RF_M2
+#undef GMR_RF_M3
+#undef GMR_RF_M4
+#undef GMR_RF_M5
+#undef GMR_RF_M6
+#undef GMR_RF_M7
+#undef GMR_RF_M8
+#undef GMR_RF_M9
+#undef GMR_RF_T1
+#undef GMR_RF_T2
+#undef GMR_RF_T3
+#undef GMR_RF_T4
+#undef GMR_RF_T5
+#undef GMR_RF_T6
+#undef GMR_RF_T7
+#undef GMR_RF_T8
+#undef GMR_RF_T9
+#undef GMR_RF_A10
+#undef GMR_RF_A11
+#undef GMR_RF_A12
+#undef GMR_RF_A13
+#undef GMR_RF_A14
+#undef GMR_RF_ACC
+#undef GMR_RF_COL
+#undef GMR_RF_D10
+#undef GMR_RF_DOT
+#undef GMR_RF_M10
+#undef GMR_RF_T10
+#undef GMR_RF_T11
+#undef GMR_RF_T12
+#undef GMR_RF_T13
+#undef GMR_RF_T14
+#undef GMR_RF_COLS
+#undef GMR_RF_CTRL
+#undef GMR_RF_DOTS
 // sum of lanes 0..15 (lanes 16..63 must hold 0 or are ignored), the same value in every lane
 __device__ __forceinline__ double row0_sum(double v) {
   v += dpp_row_shr(v, 0.0, 1);

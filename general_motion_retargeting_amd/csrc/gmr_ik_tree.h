@@ -24,6 +24,7 @@
 // Used by the latency shape (NW = 4) when the robot decomposes into <= 4 limbs of <= 8 dofs and a
 // trunk of <= 10 (all 8 shipped robots do); other robots always run the 1-wavefront kernel (dense solver).
 #pragma once
+#include <type_traits>
 
 namespace gmr {
 
@@ -81,6 +82,16 @@ __device__ __forceinline__ TreeRows<TR_NL + TR_NT> tree_rows(const LT& L, const 
   return R;
 }
 
+// f(integral_constant<int, I>) for I = I0 .. I1 - 1: the pivots as compile-time constants (the folded row broadcasts
+// of gmr_device_math.h take their lane as an immediate)
+template <int I0, int I1, class F>
+__device__ __forceinline__ void tr_static_for(F&& f) {
+  if constexpr (I0 < I1) {
+    f(std::integral_constant<int, I0>{});
+    tr_static_for<I0 + 1, I1>(f);
+  }
+}
+
 template <int TR_NL, int TR_NT, bool ROWS, bool DPPB, class LT>
 __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* sw, const short* si, int wave_in,
                                              int lane_in, TreeState& bs, Prof& pr, const TreeRows<TR_NL + TR_NT>& rows) {
@@ -99,6 +110,9 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
   const int lane = lane0;
   static_assert(!DPPB || TR_NV <= 16, "DPP row broadcasts need the local matrix in one 16-lane row");
 #define TR_BCAST(v, k) ((ROWS || DPPB) ? row_bcast_d((v), (k)) : readlane_d((v), (k)))
+  // DPP broadcasts that feed a multiply-add are folded into it (row_bcast_fma and its multi-update forms: the same
+  // fused operation on the same three numbers); the v_readlane path of the <8, 10> instance keeps fma(.., TR_BCAST(..), ..)
+  constexpr bool FOLD = ROWS || DPPB;
 #define TR_SYNC() do { if (ROWS) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); else __syncthreads(); } while (0)
   const int n = L.nv, ldh = L.o.ldh;
   const double* H = sm + L.o.H;
@@ -169,15 +183,22 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
     double bshare = 0.0;                                      // free trunk row: its limb columns' part, sent through rpart
     if (fixedm != 0ull) {                                     // (wave-uniform; most solves never fix a variable)
       double sl0 = 0.0, sl1 = 0.0, st0 = 0.0, st1 = 0.0;
+      if constexpr (FOLD) {
+        sl0 = row_bcast_fma_dot<0, 2, (TR_NL + 1) / 2, false>(sl0, xfix, h);
+        sl1 = row_bcast_fma_dot<1, 2, TR_NL / 2, false>(sl1, xfix, h + 1);
+        st0 = row_bcast_fma_dot<TR_NL, 2, (TR_NT + 1) / 2, false>(st0, xfix, h + TR_NL);
+        st1 = row_bcast_fma_dot<TR_NL + 1, 2, TR_NT / 2, false>(st1, xfix, h + TR_NL + 1);
+      } else {
 #pragma unroll
-      for (int m = 0; m < TR_NL; m++) {
-        const double xf = TR_BCAST(xfix, m);
-        if (m & 1) sl1 = fma(h[m], xf, sl1); else sl0 = fma(h[m], xf, sl0);
-      }
+        for (int m = 0; m < TR_NL; m++) {
+          const double xf = TR_BCAST(xfix, m);
+          if (m & 1) sl1 = fma(h[m], xf, sl1); else sl0 = fma(h[m], xf, sl0);
+        }
 #pragma unroll
-      for (int u = 0; u < TR_NT; u++) {
-        const double xf = TR_BCAST(xfix, TR_NL + u);
-        if (u & 1) st1 = fma(h[TR_NL + u], xf, st1); else st0 = fma(h[TR_NL + u], xf, st0);
+        for (int u = 0; u < TR_NT; u++) {
+          const double xf = TR_BCAST(xfix, TR_NL + u);
+          if (u & 1) st1 = fma(h[TR_NL + u], xf, st1); else st0 = fma(h[TR_NL + u], xf, st0);
+        }
       }
       const double sl = sl0 + sl1, st = st0 + st1;
       if (row && !self_fixed) {
@@ -196,25 +217,34 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
     bool bad = false;
     double dp = TR_BCAST(r[0], 0);
     double dinv = fast_rsqrt(dp);
-#pragma unroll
-    for (int p = 0; p < TR_NL; p++) {
+    tr_static_for<0, TR_NL>([&](auto P) __attribute__((always_inline)) {
+      constexpr int p = decltype(P)::value;
       const int lane = fresh_lane(lane0);                    // (lane > p), (lane == p): computed here, dead after this pivot
       bad = bad || !(dp > 0.0);
       const double rs = r[p] * dinv;                         // (row p holds the pivot itself: d_p / sqrt(d_p))
       double l = lane > p ? rs : 0.0;                        // column p of L_l (rows > p) and of Y_l
       if (lane == p) mydinv = dinv;                          // (rows <= p keep r[p]: l = 0 leaves a finished row alone)
       double dinv_next = 1.0;
-      if (p + 1 < TR_NL) {
-        r[p + 1] = fma(-l, TR_BCAST(l, p + 1), r[p + 1]);
-        dp = TR_BCAST(r[p + 1], p + 1);
+      if constexpr (p + 1 < TR_NL) {
+        if constexpr (FOLD) {
+          dp = row_bcast_fnma_bcast<p + 1>(r[p + 1], l);
+        } else {
+          r[p + 1] = fma(-l, TR_BCAST(l, p + 1), r[p + 1]);
+          dp = TR_BCAST(r[p + 1], p + 1);
+        }
         dinv_next = fast_rsqrt(dp);
       }
       const double yp = TR_BCAST(b, p) * dinv;               // row p keeps its unscaled b (l = 0 there): scaled after the loop
       b = fma(-l, yp, b);
+      constexpr int k0 = p + 1 < TR_NL ? p + 2 : p + 1;
+      if constexpr (FOLD) {
+        row_bcast_fnma_cols<k0, TR_NV - k0>(r + k0, l);
+      } else {
 #pragma unroll
-      for (int k = (p + 1 < TR_NL ? p + 2 : p + 1); k < TR_NV; k++) r[k] = fma(-l, TR_BCAST(l, k), r[k]);
+        for (int k = k0; k < TR_NV; k++) r[k] = fma(-l, TR_BCAST(l, k), r[k]);
+      }
       dinv = dinv_next;
-    }
+    });
     if (fresh_lane(lane0) < TR_NL) b *= mydinv;              // y_p = b_p / sqrt(d_p): the value every later row was given
     // Operands of the limb back substitution (5): column a of L_l without its diagonal and of Y_l.  The local matrix is
     // symmetric, so when pivot a came, limb lane a held row a of the unscaled upper factor in r[k], k > a -- entry (a, k)
@@ -279,25 +309,33 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
       double tdinv = 1.0;
       double dq = TR_BCAST(s[0], TR_NL);
       double dinv = fast_rsqrt(dq);
-#pragma unroll
-      for (int q = 0; q < TR_NT; q++) {
+      tr_static_for<0, TR_NT>([&](auto Q) __attribute__((always_inline)) {
+        constexpr int q = decltype(Q)::value;
         const int t = fresh_lane(lane0) - TR_NL;             // (t > q), (t == q): computed here, dead after this pivot
         tbad = tbad || !(dq > 0.0);
         const double ss = s[q] * dinv;
         double l = t > q ? ss : 0.0;
         if (t == q) tdinv = dinv;                            // (rows <= q keep s[q], as in (2))
         double dinv_next = 1.0;
-        if (q + 1 < TR_NT) {
-          s[q + 1] = fma(-l, TR_BCAST(l, TR_NL + q + 1), s[q + 1]);
-          dq = TR_BCAST(s[q + 1], TR_NL + q + 1);
+        if constexpr (q + 1 < TR_NT) {
+          if constexpr (FOLD) {
+            dq = row_bcast_fnma_bcast<TR_NL + q + 1>(s[q + 1], l);
+          } else {
+            s[q + 1] = fma(-l, TR_BCAST(l, TR_NL + q + 1), s[q + 1]);
+            dq = TR_BCAST(s[q + 1], TR_NL + q + 1);
+          }
           dinv_next = fast_rsqrt(dq);
         }
         const double yq = TR_BCAST(bt, TR_NL + q) * dinv;
         bt = fma(-l, yq, bt);
+        if constexpr (FOLD && q + 2 < TR_NT) {
+          row_bcast_fnma_cols<TR_NL + q + 2, TR_NT - q - 2>(s + q + 2, l);
+        } else {
 #pragma unroll
-        for (int k = q + 2; k < TR_NT; k++) s[k] = fma(-l, TR_BCAST(l, TR_NL + k), s[k]);
+          for (int k = q + 2; k < TR_NT; k++) s[k] = fma(-l, TR_BCAST(l, TR_NL + k), s[k]);
+        }
         dinv = dinv_next;
-      }
+      });
       // back substitution: row t of L^T without its diagonal is trunk lane t's own unscaled upper row times its
       // 1 / sqrt(d_t), as in (2) (the rows below are zero, rows outside the trunk get zeros): row q is final when its
       // step comes, so no step needs a select
@@ -308,10 +346,17 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
         for (int q = 0; q < TR_NT; q++) lt[q] = (is_trunk && q > t) ? s[q] * tdinv : 0.0;
       }
       bt *= tdinv;                                           // y (rows kept their unscaled right-hand side)
+      if constexpr (FOLD) {
+        tr_static_for<0, TR_NT>([&](auto I) __attribute__((always_inline)) {
+          constexpr int q = TR_NT - 1 - decltype(I)::value;
+          bt = row_bcast_fma<TR_NL + q, true>(bt, bt * tdinv, lt[q]);
+        });
+      } else {
 #pragma unroll
-      for (int q = TR_NT - 1; q >= 0; q--) {
-        const double xq = TR_BCAST(bt * tdinv, TR_NL + q);
-        bt = fma(-lt[q], xq, bt);
+        for (int q = TR_NT - 1; q >= 0; q--) {
+          const double xq = TR_BCAST(bt * tdinv, TR_NL + q);
+          bt = fma(-lt[q], xq, bt);
+        }
       }
       bt *= tdinv;                                           // x
     }
@@ -321,18 +366,27 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
     double x = bt;                                                                     // trunk lanes
     {
       double bb = b;                                                                   // y_l (limb lanes)
-      {
-        TR_ROW()
+      if constexpr (FOLD) {
+        // unconditional: a trunk lane's bb is dead (its x is bt, and the back substitution reads limb lanes only)
+        bb = row_bcast_fma_dot<TR_NL, 1, TR_NT, true>(bb, bt, yl);                     // Y_l[u][a]
+        tr_static_for<0, TR_NL>([&](auto I) __attribute__((always_inline)) {
+          constexpr int p = TR_NL - 1 - decltype(I)::value;
+          bb = row_bcast_fma<p, true>(bb, bb * mydinv, ltl[p]);   // (rows >= p have ltl[p] = 0: row p is final at its step)
+        });
+      } else {
+        {
+          TR_ROW()
 #pragma unroll
-        for (int u = 0; u < TR_NT; u++) {
-          const double xt = TR_BCAST(bt, TR_NL + u);
-          if (is_limb) bb = fma(-yl[u], xt, bb);                                       // Y_l[u][a]
+          for (int u = 0; u < TR_NT; u++) {
+            const double xt = TR_BCAST(bt, TR_NL + u);
+            if (is_limb) bb = fma(-yl[u], xt, bb);                                     // Y_l[u][a]
+          }
         }
-      }
 #pragma unroll
-      for (int p = TR_NL - 1; p >= 0; p--) {
-        const double xp = TR_BCAST(bb * mydinv, p);
-        bb = fma(-ltl[p], xp, bb);                           // (rows >= p have ltl[p] = 0: row p is final at its step)
+        for (int p = TR_NL - 1; p >= 0; p--) {
+          const double xp = TR_BCAST(bb * mydinv, p);
+          bb = fma(-ltl[p], xp, bb);                         // (rows >= p have ltl[p] = 0: row p is final at its step)
+        }
       }
       if (fresh_lane(lane0) < TR_NL) x = bb * mydinv;
     }
@@ -351,15 +405,22 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
         // the products of the row of H (h, read once per solve) with the wavefront's own x: two chains per part.
         // (A padding column's x is an exact zero: any finite H will do.)
         double pl1 = 0.0, pt1 = 0.0;
+        if constexpr (FOLD) {
+          pl = row_bcast_fma_dot<0, 2, (TR_NL + 1) / 2, false>(pl, x, h);
+          pl1 = row_bcast_fma_dot<1, 2, TR_NL / 2, false>(pl1, x, h + 1);
+          pt = row_bcast_fma_dot<TR_NL, 2, (TR_NT + 1) / 2, false>(pt, x, h + TR_NL);
+          pt1 = row_bcast_fma_dot<TR_NL + 1, 2, TR_NT / 2, false>(pt1, x, h + TR_NL + 1);
+        } else {
 #pragma unroll
-        for (int m = 0; m < TR_NL; m++) {
-          const double xm = TR_BCAST(x, m);
-          if (m & 1) pl1 = fma(h[m], xm, pl1); else pl = fma(h[m], xm, pl);
-        }
+          for (int m = 0; m < TR_NL; m++) {
+            const double xm = TR_BCAST(x, m);
+            if (m & 1) pl1 = fma(h[m], xm, pl1); else pl = fma(h[m], xm, pl);
+          }
 #pragma unroll
-        for (int u = 0; u < TR_NT; u++) {
-          const double xu = TR_BCAST(x, TR_NL + u);
-          if (u & 1) pt1 = fma(h[TR_NL + u], xu, pt1); else pt = fma(h[TR_NL + u], xu, pt);
+          for (int u = 0; u < TR_NT; u++) {
+            const double xu = TR_BCAST(x, TR_NL + u);
+            if (u & 1) pt1 = fma(h[TR_NL + u], xu, pt1); else pt = fma(h[TR_NL + u], xu, pt);
+          }
         }
         pl += pl1; pt += pt1;
         // A fixed trunk row (owned by wavefront 0) needs the limb parts of all four wavefronts.  gpart is written
