@@ -172,6 +172,16 @@ _SIGS = {
     "gmr_motion_tracker_set_disturbances": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gmr_motion_tracker_disturb_dev": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "gmr_motion_tracker_disturb": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "gmr_motion_tracker_set_reset_states": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gmr_motion_tracker_reset_states_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "gmr_motion_tracker_reset_states": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "gmr_motion_tracker_reset_state": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gmr_motion_tracker_set_rewards": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gmr_motion_tracker_rewards_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gmr_motion_tracker_rewards": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gmr_motion_tracker_reward_stats_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "gmr_motion_tracker_reward_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "gmr_motion_tracker_reward_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "gmr_comm_create": (C.c_int, [C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),
     "gmr_comm_destroy": (C.c_int, [C.c_void_p]),
     "gmr_comm_rank": (C.c_int, [C.c_void_p]),
@@ -730,6 +740,46 @@ class DisturbIo(C.Structure):
     """``gmr_disturb_io_t``: what ``gmr_motion_tracker_disturb[_dev]`` writes, each an address or NULL, and the two row strides"""
     _fields_ = ([(k, C.c_void_p) for k in DISTURB_IO_FIELDS] + [("push_force_stride", C.c_int64), ("push_torque_stride", C.c_int64),
                                                                 ("push_obs", C.c_void_p)])
+
+
+# gmr_motion_tracker_set_reset_states / _reset_states[_dev] / _set_rewards / _rewards[_dev] / _reward_stats[_dev] (include/gmr_hip.h,
+# "tracker episode")
+RESET_SPECS = ("init_dof_pos", "init_base_pos_xy", "init_base_lin_vel_xy")
+RESET_IO_FIELDS = ("root_states", "dof_pos", "dof_vel", "delay_steps", "episode_steps", "init_root_states", "init_dof_pos", "init_dof_vel")
+REWARD_MAX_EXTRA, REWARD_MAX_COLS = 16, 52
+REWARD_BLOCKS = {"terms": 1, "links": 2, "proprio": 4, "feet": 8, "commands": 16}      # column order
+REWARD_LOCOMOTION, REWARD_IMITATION = 1, 2
+REWARD_DONE_TIME_OUT = 4
+REWARD_IN_FIELDS = ("term", "link_term", "proprio_term", "feet_term", "cmd_term", "extra", "done", "flags")
+REWARD_OUT_FIELDS = ("reward", "scaled", "group_total", "reset", "time_outs")
+
+
+class ResetConfig(C.Structure):
+    """``gmr_reset_config_t``: the configuration of ``gmr_motion_tracker_set_reset_states``, values and two host addresses"""
+    _fields_ = ([("base_init_state", C.c_float * 13), ("default_dof_pos", C.c_void_p), ("env_origins", C.c_void_p)]
+                + [(k, ProprioNoise) for k in RESET_SPECS] + [("yaw_range", C.c_double * 2)]
+                + [(k, C.c_int32) for k in ("yaw", "decimation", "use_terrain")])
+
+
+class ResetIo(C.Structure):
+    """``gmr_reset_io_t``: the arrays of ``gmr_motion_tracker_reset_states[_dev]``, each an address or NULL"""
+    _fields_ = [(k, C.c_void_p) for k in RESET_IO_FIELDS]
+
+
+class RewardConfig(C.Structure):
+    """``gmr_reward_config_t``: the configuration of ``gmr_motion_tracker_set_rewards``, values only"""
+    _fields_ = ([("group_weight", C.c_float * 2), ("extra_weights", C.c_float * REWARD_MAX_EXTRA), ("only_positive", C.c_int32 * 2)]
+                + [(k, C.c_int32) for k in ("blocks", "extra_cols", "stats")] + [("groups", C.c_uint8 * REWARD_MAX_COLS)])
+
+
+class RewardIn(C.Structure):
+    """``gmr_reward_in_t``: the inputs of ``gmr_motion_tracker_rewards[_dev]``, each an address or NULL"""
+    _fields_ = [(k, C.c_void_p) for k in REWARD_IN_FIELDS]
+
+
+class RewardOut(C.Structure):
+    """``gmr_reward_out_t``: the outputs of ``gmr_motion_tracker_rewards[_dev]``, each an address or NULL"""
+    _fields_ = [(k, C.c_void_p) for k in REWARD_OUT_FIELDS]
 
 
 # gmr_motion_tracker_set_preview: the block bits in row order, the frames and the limits (include/gmr_hip.h, "tracker preview")

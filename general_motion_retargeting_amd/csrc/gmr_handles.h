@@ -4,7 +4,8 @@
 // gmr_tracker_preview.hip reads its state and tables, gmr_tracker_adaptive.hip owns its bins (adaptive sampling, masked resets),
 // gmr_tracker_anchor.hip its anchors, gmr_tracker_control.hip its control tables and the two arrays of the actuator model,
 // gmr_tracker_proprio.hip its proprioception tables and the six arrays behind them, gmr_tracker_feet.hip its terrain, its feet tables and
-// the two arrays behind them, gmr_tracker_commands.hip its command and disturbance tables and the arrays of the velocity commands.
+// the two arrays behind them, gmr_tracker_commands.hip its command and disturbance tables and the arrays of the velocity commands,
+// gmr_tracker_episode.hip its reset-state and reward tables, the reset counters and the arrays of the episode statistics.
 #pragma once
 #include <stdint.h>
 
@@ -206,6 +207,48 @@ struct DisturbTables {
   ProprioNoise spec[4];                     // kick_lin_vel, kick_ang_vel, push_force, push_torque
   float s_force = 1.0f, s_torque = 1.0f;    // the two privileged-observation scales
 };
+constexpr int RESET_SPECS = 3;            // init_dof_pos, init_base_pos_xy, init_base_lin_vel_xy
+// the reset-state configuration of a tracker: validated on the host, travels as a kernel argument like ControlTables
+struct ResetTables {
+  int32_t R = 0;                            // the robot dofs it was set for; 0: reset states were never set
+  int32_t yaw = 0;                          // the yaw is drawn
+  int32_t decimation = 0;                   // delay_steps is drawn below it; 0: no draw
+  int32_t use_terrain = 0;
+  float yaw_lo = 0.0f, yaw_span = 0.0f;     // (float)lo, (float)(hi - lo), the span formed in double
+  const float* origins = nullptr;           // [N][2] on the device, or null
+  ProprioNoise spec[RESET_SPECS];
+  float base[13] = {};                      // base_init_state
+  float default_pos[TRACKER_MAX_DOF] = {};  // (a table of its own, like ControlTables::default_pos)
+};
+constexpr int REWARD_BLOCKS = 5;          // TERMS, LINK_TERMS, PROPRIO_TERMS, FEET_TERMS, CMD_TERMS: the column order of include/gmr_hip.h N13
+constexpr int REWARD_MAX_EXTRA = 16;      // caller columns behind them
+constexpr int REWARD_MAX_COLS = 52;       // 6 + 4 + 14 + 8 + 4 + 16
+// the reward configuration of a tracker: validated on the host, travels as a kernel argument like ControlTables.  The
+// handle keeps the weights of the caller's columns alone: those of the blocks' columns are copied from the blocks' tables into the copy
+// a call carries, when an entry point enqueues it.
+struct RewardTables {
+  int32_t on = 0;                           // 0: rewards were never set
+  int32_t mask = 0;                         // GMR_REWARD_BLOCK_*: the blocks the columns were laid out for
+  int32_t C = 0, E = 0;                     // columns, the caller's among them
+  int32_t stats = 0;                        // the episode statistics are kept
+  int32_t pos[2] = {};                      // only_positive of the two groups
+  float gw[2] = {};                         // group_weight
+  float w[REWARD_MAX_COLS] = {};            // the weight of a column; zero: the column stays out
+  uint8_t group[REWARD_MAX_COLS] = {};      // GMR_REWARD_LOCOMOTION | GMR_REWARD_IMITATION
+  uint8_t block[REWARD_MAX_COLS] = {}, off[REWARD_MAX_COLS] = {};      // column c is term off[c] of input array block[c] (REWARD_BLOCKS: extra)
+  int32_t width[REWARD_BLOCKS + 1] = {};    // the row length of every input array
+};
+// the episode statistics of a tracker (device pointers into its reward block, all zero after set_rewards; null without statistics)
+struct RewardState {
+  int32_t* ep_steps = nullptr;              // [N]
+  float* ep_sum = nullptr;                  // [N][C + 1], column 0 is the reward
+  uint32_t* fin_count = nullptr;            // [1] episodes finished since the last clear
+  unsigned long long* fin_steps = nullptr;  // [1] their steps
+  double* fin_sum = nullptr;                // [C + 1] their sums
+  uint32_t* started = nullptr;              // [1] a reward call has been made
+  double* part = nullptr;                   // [ceil(N / 16)][C + 1] the partials of one call
+  uint32_t* wg_any = nullptr;               // [ceil(N / 16)] the workgroup finished an episode in this call
+};
 }  // namespace gmr
 
 struct gmr_motion_tracker {
@@ -241,6 +284,12 @@ struct gmr_motion_tracker {
   gmr::CommandState command_state;
   gmr::DeviceBlock command_block; // the arrays of command_state: one allocation, made by gmr_motion_tracker_set_commands
   gmr::DisturbTables disturb;    // disturb.on = 0 until gmr_motion_tracker_set_disturbances configures them
+  gmr::ResetTables resets;       // resets.R = 0 until gmr_motion_tracker_set_reset_states configures them
+  uint32_t* reset_draws = nullptr; // [N] resets drawn for the environment so far
+  gmr::DeviceBlock reset_block;  // reset_draws and the copy of env_origins: one allocation, made by gmr_motion_tracker_set_reset_states
+  gmr::RewardTables rewards;     // rewards.on = 0 until gmr_motion_tracker_set_rewards configures them
+  gmr::RewardState reward_state;
+  gmr::DeviceBlock reward_block; // the arrays of reward_state: one allocation, made by gmr_motion_tracker_set_rewards with statistics
   std::vector<double> clip_w;    // the clip weights as given at creation (empty: uniform)
   std::mutex mu;                 // the tables, and the whole of every synchronous entry point
 };

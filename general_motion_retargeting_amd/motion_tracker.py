@@ -73,6 +73,10 @@ CMD_INDEX_ORDERS = {"grid": 0, "reference": 1}
 COMMAND_STATE = ("commands", "gait_frequency", "cmd_resample_time", "cmd_draws", "env_level", "curriculum_prob", "hits", "cum")
 DISTURB_KICK, DISTURB_PUSH_START, DISTURB_PUSH_STOP = 1, 2, 4
 DISTURB_SPECS = ("kick_lin_vel", "kick_ang_vel", "push_force", "push_torque")
+RESET_SPECS = ("init_dof_pos", "init_base_pos_xy", "init_base_lin_vel_xy")
+REWARD_MAX_EXTRA = 16
+REWARD_BLOCKS = {"terms": 1, "links": 2, "proprio": 4, "feet": 8, "commands": 16}      # the bits of gmr_reward_config_t.blocks, in column order
+REWARD_LOCOMOTION, REWARD_IMITATION = 1, 2         # the bits of a column's ``groups`` entry of :meth:`MotionTracker.set_rewards`
 LINK_SIM = {"body_pos": (0, 3), "body_rot": (3, 4), "body_vel": (7, 3), "body_ang_vel": (10, 3)}      # offset and width in a packed row of 13
 
 
@@ -183,6 +187,8 @@ class MotionTracker:
         self._proprio = None          # (R, extra_cols) once set_proprio has configured the proprioception half
         self._feet = None             # (num_bodies, num_edges) once set_feet has configured the feet
         self._commands = None         # ((L, A) or None,) once set_commands has configured the velocity commands
+        self._resets = None           # (R, decimation) once set_reset_states has configured the reset states
+        self._rewards = None          # the checked configuration once set_rewards has laid the reward columns out
         self._disturb = None          # (kick_every, push_every, push_duration) once set_disturbances has configured kicks and pushes
         if sc is not None or wt is not None:
             self.set_terms(sc, wt)
@@ -1552,6 +1558,380 @@ class MotionTracker:
         if act < 0:
             _lib.check(act)
         return int(act)
+
+    # ---- reset states, the reward total and the episode statistics ----------------------------------------
+    @staticmethod
+    def _noise_spec(name: str, spec):
+        """one spec in the form of the ``noise`` of :meth:`set_proprio` -> ``(distribution, operation, a, b)``, checked"""
+        if spec is None or spec.get("distribution", "none") == "none":
+            return (0, 0, 0.0, 0.0)
+        dist, op = spec.get("distribution"), spec.get("operation")
+        if dist not in NOISE_DISTRIBUTIONS:
+            raise ValueError(f"{name}: distribution is one of {sorted(NOISE_DISTRIBUTIONS)}, got {dist!r}")
+        if op not in NOISE_OPERATIONS:
+            raise ValueError(f"{name}: operation is one of {sorted(NOISE_OPERATIONS)}, got {op!r}")
+        rng = spec.get("range")
+        if rng is None or len(rng) != 2:
+            raise ValueError(f"{name}: range is a pair, got {rng!r}")
+        a, b = float(rng[0]), float(rng[1])
+        with np.errstate(over="ignore", invalid="ignore"):
+            fits = all(np.isfinite(np.float32(x)) for x in (a, b, b - a))
+        if not fits:
+            raise ValueError(f"{name}: range {(a, b)} is not finite in float32")
+        if dist == "gaussian" and b < 0:
+            raise ValueError(f"{name}: a gaussian's deviation {b} is negative")
+        return (NOISE_DISTRIBUTIONS[dist], NOISE_OPERATIONS[op], a, b)
+
+    def _reset_setup(self, base_init_state, default_dof_pos, env_origins, init_dof_pos, init_base_pos_xy, init_base_lin_vel_xy, yaw_range,
+                     decimation, use_terrain):
+        """the checks of :meth:`set_reset_states`, all of them before the library is loaded -> a dict of the checked values"""
+        N, R = self.num_envs, self.nrobot_dof
+        with np.errstate(over="ignore"):
+            base = np.ascontiguousarray(base_init_state, dtype=np.float32).reshape(-1)
+            q0 = np.ascontiguousarray(default_dof_pos, dtype=np.float32).reshape(-1)
+        if len(base) != 13 or not np.isfinite(base).all():
+            raise ValueError(f"base_init_state: 13 finite numbers (pos, quat xyzw, lin vel, ang vel), got {len(base)}")
+        if len(q0) != R or not np.isfinite(q0).all():
+            raise ValueError(f"default_dof_pos: {R} finite numbers needed, one per robot dof, got {len(q0)}")
+        org = None
+        if env_origins is not None:
+            with np.errstate(over="ignore"):
+                org = np.ascontiguousarray(env_origins, dtype=np.float32)
+            if org.ndim == 2 and org.shape == (N, 3):
+                org = np.ascontiguousarray(org[:, :2])
+            if org.shape != (N, 2) or not np.isfinite(org).all():
+                raise ValueError(f"env_origins: finite numbers of shape {(N, 2)} (or {(N, 3)}) needed, got {org.shape}")
+        specs = [self._noise_spec(k, s) for k, s in zip(RESET_SPECS, (init_dof_pos, init_base_pos_xy, init_base_lin_vel_xy))]
+        yaw = None
+        if yaw_range is not None:
+            if len(yaw_range) != 2:
+                raise ValueError(f"yaw_range: a pair (lower, upper) or None, got {yaw_range!r}")
+            lo, hi = float(yaw_range[0]), float(yaw_range[1])
+            with np.errstate(over="ignore", invalid="ignore"):
+                fits = all(np.isfinite(np.float32(x)) for x in (lo, hi, hi - lo))
+            if not fits:
+                raise ValueError(f"yaw_range {(lo, hi)} is not finite in float32")
+            if hi < lo:
+                raise ValueError(f"yaw_range: upper = {hi} < lower = {lo}")
+            yaw = (lo, hi)
+        if int(decimation) != decimation or not 0 <= decimation <= CONTROL_MAX_DECIMATION:
+            raise ValueError(f"decimation = {decimation}: a whole number in [0, {CONTROL_MAX_DECIMATION}] is needed (0: no delay draw)")
+        return {"base": base, "default_dof_pos": q0, "env_origins": org, "specs": specs, "yaw": yaw, "decimation": int(decimation),
+                "use_terrain": bool(use_terrain)}
+
+    def set_reset_states(self, base_init_state, default_dof_pos, *, env_origins=None, init_dof_pos=None, init_base_pos_xy=None,
+                         init_base_lin_vel_xy=None, yaw_range=(0.0, 2.0 * np.pi), decimation: int = 0, use_terrain: bool = True) -> None:
+        """Configures the reset states (t1.py:316-340): ``base_init_state [13]`` (pos, quat xyzw, lin vel, ang vel), ``default_dof_pos
+        [R]``, optionally ``env_origins [N,2]`` (copied to the device), three specs in the form of the ``noise`` of :meth:`set_proprio`
+        (``None``: no draw for that block), ``yaw_range (lower, upper)`` (``None``: no yaw draw, the row's quaternion stays), ``decimation``
+        -- ``delay_steps`` is drawn below it, 0: no draw -- and ``use_terrain`` (the height of :meth:`set_terrain` under the drawn point is
+        added to ``z``).  Allocates ``reset_draws`` (zeros).  Synchronous."""
+        from . import _lib
+        c = self._reset_setup(base_init_state, default_dof_pos, env_origins, init_dof_pos, init_base_pos_xy, init_base_lin_vel_xy, yaw_range,
+                              decimation, use_terrain)
+        cfg = _lib.ResetConfig()
+        cfg.base_init_state[:] = c["base"].tolist()
+        cfg.default_dof_pos = c["default_dof_pos"].ctypes.data
+        if c["env_origins"] is not None:
+            cfg.env_origins = c["env_origins"].ctypes.data
+        for k, (dist, op, a, b) in zip(RESET_SPECS, c["specs"]):
+            s = getattr(cfg, k)
+            s.distribution, s.operation, s.a, s.b = dist, op, a, b
+        if c["yaw"] is not None:
+            cfg.yaw, cfg.yaw_range[0], cfg.yaw_range[1] = 1, c["yaw"][0], c["yaw"][1]
+        cfg.decimation, cfg.use_terrain = c["decimation"], int(c["use_terrain"])
+        _lib.check(_lib.lib().gmr_motion_tracker_set_reset_states(self.handle, C.byref(cfg)))
+        self._resets = (self.nrobot_dof, c["decimation"])
+
+    def _need_resets(self, what: str):
+        r = getattr(self, "_resets", None)
+        if r is None:
+            raise ValueError(f"{what}: reset states are not set on this tracker, call set_reset_states() first")
+        if r[0] != self.nrobot_dof:
+            raise ValueError(f"{what}: reset states were set for {r[0]} robot dofs, the dof map now has {self.nrobot_dof}: call "
+                             "set_reset_states() again")
+        return r
+
+    def reset_states(self, root_states, dof_pos, dof_vel, mask=None, env_ids=None, delay_steps=None, episode_steps=None, init_root_states=None,
+                     init_dof_pos=None, init_dof_vel=None, chain: bool = False) -> Dict[str, object]:
+        """``_reset_dofs``, ``_reset_root_states`` and the ``delay_steps`` draw (t1.py:316-340) for every entry whose ``mask`` is set
+        (``None``: all), host arrays: copies of ``root_states [N,13]``, ``dof_pos``, ``dof_vel`` ``[N,R]`` and, when given, ``delay_steps``
+        and ``episode_steps`` ``i32[N]`` with the rows of the served environments rewritten, and ``ignored``: how many ids of served
+        entries lay outside ``[0, num_envs)``.  Without ``env_ids`` the mask and the ``init_*`` rows cover every environment; with it
+        (every environment at most once) they are indexed by list position, as the masks of :meth:`reset_done` are.  ``init_root_states
+        [n,13]``, ``init_dof_pos``, ``init_dof_vel`` ``[n,R]`` take the place of ``base_init_state``, ``default_dof_pos`` and the zero
+        velocity of that entry -- the rows of ``step_links(advance=False)`` can be fed in.  With ``chain`` the same launch also does what
+        :meth:`hold` and :meth:`proprio_reset` would do afterwards, for the halves that are configured.  One launch."""
+        from . import _lib
+        self._need_resets("reset_states")
+        N, R = self.num_envs, self.nrobot_dof
+        ids, n = None, N
+        if env_ids is not None:
+            ids = np.ascontiguousarray(env_ids, dtype=np.int32).reshape(-1)
+            n = len(ids)
+            if len(np.unique(ids)) != n:
+                raise ValueError("reset_states: env_ids names an environment twice")
+        rs = np.array(root_states, dtype=np.float32, order="C")
+        if rs.shape != (N, 13):
+            raise ValueError(f"root_states: shape {rs.shape}, {(N, 13)} needed")
+        out = {"root_states": rs, "dof_pos": self._rows(dof_pos, "dof_pos").copy(), "dof_vel": self._rows(dof_vel, "dof_vel").copy()}
+        for k, a in (("delay_steps", delay_steps), ("episode_steps", episode_steps)):
+            if a is not None:
+                out[k] = self._per_env_ints(a, k).copy()
+        io = _lib.ResetIo(**{k: a.ctypes.data for k, a in out.items()})
+        keep = []
+        for k, a, w in (("init_root_states", init_root_states, 13), ("init_dof_pos", init_dof_pos, R), ("init_dof_vel", init_dof_vel, R)):
+            if a is None:
+                continue
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.shape != (n, w):
+                raise ValueError(f"{k}: shape {a.shape}, {(n, w)} needed")
+            keep.append(a)
+            setattr(io, k, a.ctypes.data)
+        m = _mask(mask, "mask", n)
+        ignored = C.c_int()
+        if n > 0:
+            _lib.check(_lib.lib().gmr_motion_tracker_reset_states(self.handle, n, _lib._ptr(ids), _lib._ptr(m), C.byref(io), 1 if chain else 0,
+                                                                  C.byref(ignored)))
+        out["ignored"] = int(ignored.value)
+        return out
+
+    def reset_states_dev(self, root_states, dof_pos, dof_vel, mask=None, env_ids=None, n: Optional[int] = None, delay_steps=None,
+                         episode_steps=None, init_root_states=None, init_dof_pos=None, init_dof_vel=None, chain: bool = False, stream=None) -> None:
+        """:meth:`reset_states` on device memory, asynchronous on ``stream``: ONE launch, no ``nonzero``, no compaction, no read-back.
+        ``root_states f32[N*13]``, ``dof_pos`` / ``dof_vel f32[N*R]``, ``delay_steps`` / ``episode_steps i32[N]`` are the simulator's own
+        arrays, written in place in the rows of served entries; ``mask i32[n]`` as a step leaves it (``reset`` of :meth:`rewards_dev`); the
+        ``init_*`` rows by list position; with ``env_ids`` (``i32[n]``) ``n`` is mandatory."""
+        from . import _lib
+        self._need_resets("reset_states_dev")
+        N, R = self.num_envs, self.nrobot_dof
+        n = self._list_length("reset_states_dev", env_ids, n)
+        if root_states is None or dof_pos is None or dof_vel is None:
+            raise ValueError("reset_states_dev: root_states, dof_pos and dof_vel are needed")
+        io = _lib.ResetIo()
+        for k, x, dt, count in (("root_states", root_states, "float32", N * 13), ("dof_pos", dof_pos, "float32", N * R),
+                                ("dof_vel", dof_vel, "float32", N * R), ("delay_steps", delay_steps, "int32", N),
+                                ("episode_steps", episode_steps, "int32", N), ("init_root_states", init_root_states, "float32", n * 13),
+                                ("init_dof_pos", init_dof_pos, "float32", n * R), ("init_dof_vel", init_dof_vel, "float32", n * R)):
+            p = _dev_ptr(x, k, dt, count)
+            setattr(io, k, None if p is None else p.value)
+        p_ids, p_mask = _dev_ptr(env_ids, "env_ids", "int32", n), _dev_ptr(mask, "mask", "int32", n)
+        _lib.check(_lib.lib().gmr_motion_tracker_reset_states_dev(self.handle, n, p_ids, p_mask, C.byref(io), 1 if chain else 0, _lib._s(stream)))
+
+    def reset_state(self) -> Optional[Dict[str, np.ndarray]]:
+        """``reset_draws u32[N]``: the resets drawn for every environment so far; ``None`` when the reset states are not set.  Synchronous."""
+        from . import _lib
+        if getattr(self, "_resets", None) is None:
+            return None
+        out = {"reset_draws": np.empty(self.num_envs, np.uint32)}
+        _lib.check(_lib.lib().gmr_motion_tracker_reset_state(self.handle, _lib._ptr(out["reset_draws"])))
+        return out
+
+    def _reward_blocks(self):
+        """the blocks configured on this tracker, in column order -> [(block, names)]"""
+        blocks = [("terms", TERMS)]
+        if getattr(self, "_links", None) is not None:
+            blocks.append(("links", LINK_TERMS))
+        if getattr(self, "_proprio", None) is not None:
+            blocks.append(("proprio", PROPRIO_TERMS))
+        if getattr(self, "_feet", None) is not None:
+            blocks.append(("feet", FEET_TERMS))
+        if getattr(self, "_commands", None) is not None:
+            blocks.append(("commands", CMD_TERMS))
+        return blocks
+
+    def _rewards_setup(self, extra_names, extra_weights, groups, group_weight, only_positive, stats):
+        """the checks of :meth:`set_rewards`, all of them before the library is loaded -> a dict of the checked values"""
+        blocks = self._reward_blocks()
+        names = [k for _, ks in blocks for k in ks]
+        default = [REWARD_IMITATION if b in ("terms", "links") else REWARD_LOCOMOTION for b, ks in blocks for _ in ks]
+        extra_names = [] if extra_names is None else [str(k) for k in extra_names]
+        E = len(extra_names)
+        if E > REWARD_MAX_EXTRA:
+            raise ValueError(f"extra_names: {E} caller columns, at most {REWARD_MAX_EXTRA}")
+        if len(set(extra_names)) != E or set(extra_names) & set(names) or set(extra_names) & {"reward", "steps", "episodes"}:
+            raise ValueError(f"extra_names {extra_names} must differ from one another, from the blocks' terms and from reward / steps / episodes")
+        with np.errstate(over="ignore"):
+            ew = np.ascontiguousarray([] if extra_weights is None else extra_weights, dtype=np.float32).reshape(-1)
+        if extra_weights is None:
+            ew = np.ones(E, np.float32)
+        if len(ew) != E or not np.isfinite(ew).all():
+            raise ValueError(f"extra_weights: {E} finite numbers needed, one per caller column, got {len(ew)}")
+        names += extra_names
+        default += [REWARD_LOCOMOTION] * E
+        if groups is None:
+            g = default
+        elif isinstance(groups, dict):
+            unknown = sorted(set(groups) - set(names))
+            if unknown:
+                raise KeyError(f"groups: unknown columns {unknown} (known: {names})")
+            g = [groups.get(k, d) for k, d in zip(names, default)]
+        else:
+            g = list(groups)
+            if len(g) != len(names):
+                raise ValueError(f"groups has {len(g)} entries, there are {len(names)} columns: {names}")
+        if any(int(x) != x or not 0 <= x <= (REWARD_LOCOMOTION | REWARD_IMITATION) for x in g):
+            raise ValueError(f"groups: each entry is a mask of REWARD_LOCOMOTION = 1 and REWARD_IMITATION = 2, got {g}")
+        with np.errstate(over="ignore"):
+            gw = np.ascontiguousarray(group_weight, dtype=np.float32).reshape(-1)
+        if len(gw) != 2 or not np.isfinite(gw).all():
+            raise ValueError(f"group_weight: two finite numbers (locomotion, imitation), got {group_weight!r}")
+        if only_positive is None or len(only_positive) != 2:
+            raise ValueError(f"only_positive: a pair of flags (locomotion, imitation), got {only_positive!r}")
+        return {"blocks": blocks, "names": names, "E": E, "extra_weights": ew, "groups": [int(x) for x in g], "group_weight": gw,
+                "only_positive": (bool(only_positive[0]), bool(only_positive[1])), "stats": bool(stats)}
+
+    def set_rewards(self, *, extra_names=None, extra_weights=None, groups=None, group_weight=(1.0, 1.0), only_positive=(False, False),
+                    stats: bool = False) -> Dict[str, object]:
+        """Configures the reward (t1.py:560-572, t1_imitation.py:323-352).  The columns are the term rows of the blocks configured on the
+        tracker NOW, in fixed order -- :data:`TERMS`, :data:`LINK_TERMS`, :data:`PROPRIO_TERMS`, :data:`FEET_TERMS`, :data:`CMD_TERMS` --,
+        then one caller column per name of ``extra_names`` (at most 16) weighed by ``extra_weights`` (default 1); call it again after a
+        block is configured.  The weight of a block's column is the one the block is configured with, read when a call is enqueued.
+        ``groups``: per column (a list, or a dict by name over the defaults) a mask of :data:`REWARD_LOCOMOTION` and
+        :data:`REWARD_IMITATION`; by default the tracking terms feed the imitation group and everything else locomotion; 3 counts a column
+        in both, which is the reference's double count.  ``group_weight (locomotion, imitation)``, ``only_positive`` a pair of flags.
+        ``stats``: keep the Recorder's episode statistics (allocates and zeroes their state).  Returns :meth:`reward_layout`.  Synchronous."""
+        from . import _lib
+        c = self._rewards_setup(extra_names, extra_weights, groups, group_weight, only_positive, stats)
+        cfg = _lib.RewardConfig()
+        cfg.group_weight[:] = c["group_weight"].tolist()
+        for k, w in enumerate(c["extra_weights"].tolist()):
+            cfg.extra_weights[k] = w
+        cfg.only_positive[:] = [int(x) for x in c["only_positive"]]
+        cfg.blocks = sum(REWARD_BLOCKS[b] for b, _ in c["blocks"])
+        cfg.extra_cols, cfg.stats = c["E"], int(c["stats"])
+        for k, g in enumerate(c["groups"]):
+            cfg.groups[k] = g
+        _lib.check(_lib.lib().gmr_motion_tracker_set_rewards(self.handle, C.byref(cfg)))
+        self._rewards = c
+        return self.reward_layout()
+
+    def _need_rewards(self, what: str, stats: bool = False):
+        c = getattr(self, "_rewards", None)
+        if c is None:
+            raise ValueError(f"{what}: rewards are not set on this tracker, call set_rewards() first")
+        if [b for b, _ in c["blocks"]] != [b for b, _ in self._reward_blocks()]:
+            raise ValueError(f"{what}: the blocks configured on the tracker changed since set_rewards(): call it again")
+        if stats and not c["stats"]:
+            raise ValueError(f"{what}: the episode statistics are off, call set_rewards(stats=True)")
+        return c
+
+    def reward_layout(self) -> Optional[Dict[str, object]]:
+        """``names``: the columns in order; ``blocks``: ``{block: (first column, count)}`` (``extra`` among them); ``groups``; ``num_cols``;
+        ``None`` when the rewards are not set"""
+        c = getattr(self, "_rewards", None)
+        if c is None:
+            return None
+        blocks, at = {}, 0
+        for b, ks in c["blocks"]:
+            blocks[b] = (at, len(ks))
+            at += len(ks)
+        blocks["extra"] = (at, c["E"])
+        return {"names": tuple(c["names"]), "blocks": blocks, "groups": tuple(c["groups"]), "num_cols": len(c["names"])}
+
+    _REWARD_INPUTS = (("term", "terms", len(TERMS)), ("link_term", "links", len(LINK_TERMS)), ("proprio_term", "proprio", len(PROPRIO_TERMS)),
+                      ("feet_term", "feet", len(FEET_TERMS)), ("cmd_term", "commands", len(CMD_TERMS)))
+
+    def rewards(self, term=None, link_term=None, proprio_term=None, feet_term=None, cmd_term=None, extra=None, done=None,
+                flags=None) -> Dict[str, np.ndarray]:
+        """The reward of a step, host arrays in and out: from the ``term`` arrays as the blocks' calls left them (``None`` keeps that
+        block's columns out), the caller's ``extra [N,E]``, the ``done`` word (the OR of the done words of :meth:`proprio` and
+        :meth:`feet`) and the ``flags`` of :meth:`commands` -- ``reward [N]``, ``scaled [N,C]`` (weight times term, what the reference puts
+        into ``extras["rew_terms"]``), ``group_total [N,2]``, ``reset i32[N] = done != 0`` and ``time_outs i32[N] = ((done & 4) | (flags &
+        CMD_BOUNDARY)) != 0``.  With ``stats`` the episode sums move on.  One launch, two with the statistics."""
+        from . import _lib
+        c = self._need_rewards("rewards")
+        N, Cn = self.num_envs, len(c["names"])
+        have = {b for b, _ in c["blocks"]}
+        given = dict(term=term, link_term=link_term, proprio_term=proprio_term, feet_term=feet_term, cmd_term=cmd_term)
+        st, keep = _lib.RewardIn(), []
+        for k, b, w in self._REWARD_INPUTS + (("extra", "extra", c["E"]),):
+            a = extra if k == "extra" else given[k]
+            if a is None:
+                continue
+            if b != "extra" and b not in have:
+                raise ValueError(f"rewards: {k} given, but the block {b!r} is not configured on this tracker")
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.shape != (N, w):
+                raise ValueError(f"{k}: shape {a.shape}, {(N, w)} needed")
+            keep.append(a)
+            setattr(st, k, a.ctypes.data)
+        for k, a in (("done", done), ("flags", flags)):
+            a = self._per_env_ints(a, k)
+            if a is not None:
+                keep.append(a)
+                setattr(st, k, a.ctypes.data)
+        out = {"reward": np.empty(N, np.float32), "scaled": np.empty((N, Cn), np.float32), "group_total": np.empty((N, 2), np.float32),
+               "reset": np.empty(N, np.int32), "time_outs": np.empty(N, np.int32)}
+        table = _lib.RewardOut(**{k: a.ctypes.data for k, a in out.items()})
+        _lib.check(_lib.lib().gmr_motion_tracker_rewards(self.handle, C.byref(st), C.byref(table)))
+        return out
+
+    def rewards_dev(self, term=None, link_term=None, proprio_term=None, feet_term=None, cmd_term=None, extra=None, done=None, flags=None,
+                    stream=None, **outputs) -> None:
+        """:meth:`rewards` on device memory, asynchronous on ``stream``: ONE launch, TWO with the statistics, no host synchronisation.
+        ``outputs`` names whichever of ``reward, scaled, group_total, reset, time_outs`` are wanted.  Every array is a
+        ``_lib.DeviceBuffer``, a raw address or an object with ``data_ptr()``."""
+        from . import _lib
+        c = self._need_rewards("rewards_dev")
+        N, Cn = self.num_envs, len(c["names"])
+        outs = {"reward": 1, "scaled": Cn, "group_total": 2, "reset": 1, "time_outs": 1}
+        unknown = sorted(set(outputs) - set(outs))
+        if unknown:
+            raise TypeError(f"rewards_dev: unknown outputs {unknown}")
+        have = {b for b, _ in c["blocks"]}
+        given = dict(term=term, link_term=link_term, proprio_term=proprio_term, feet_term=feet_term, cmd_term=cmd_term)
+        st, table = _lib.RewardIn(), _lib.RewardOut()
+        for k, b, w in self._REWARD_INPUTS:
+            if given[k] is not None and b not in have:
+                raise ValueError(f"rewards_dev: {k} given, but the block {b!r} is not configured on this tracker")
+            p = _dev_ptr(given[k], k, "float32", N * w)
+            setattr(st, k, None if p is None else p.value)
+        for k, x, dt, w in (("extra", extra, "float32", c["E"]), ("done", done, "int32", 1), ("flags", flags, "int32", 1)):
+            p = _dev_ptr(x, k, dt, N * w)
+            setattr(st, k, None if p is None else p.value)
+        for k, x in outputs.items():
+            p = _dev_ptr(x, k, "int32" if k in ("reset", "time_outs") else "float32", N * outs[k])
+            setattr(table, k, None if p is None else p.value)
+        _lib.check(_lib.lib().gmr_motion_tracker_rewards_dev(self.handle, C.byref(st), C.byref(table), _lib._s(stream)))
+
+    def reward_stats_dev(self, out=None, clear: bool = True, stream=None) -> None:
+        """Copies the three accumulators of the episode statistics into ``out`` -- ``u64[C + 3]`` on the device: episodes, steps, then the
+        ``C + 1`` sums as float64, the reward first -- and, with ``clear``, zeroes them, in one launch; asynchronous on ``stream``."""
+        from . import _lib
+        c = self._need_rewards("reward_stats_dev", stats=True)
+        p = _dev_ptr(out, "out", "uint64", len(c["names"]) + 3)
+        _lib.check(_lib.lib().gmr_motion_tracker_reward_stats_dev(self.handle, p, 1 if clear else 0, _lib._s(stream)))
+
+    def reward_stats(self, clear: bool = True, raw: bool = False) -> Dict[str, object]:
+        """What the reference's ``Recorder`` writes (recorder.py:55-62): ``episodes`` finished since the last clear, ``steps`` their mean
+        length, ``reward`` and every column by name the mean of the episode sums; 0.0 when no episode finished, as ``_mean`` gives.  The
+        division is made here, on the host.  With ``raw`` the accumulators themselves: ``episodes``, ``steps`` (their sum) and ``sums
+        f64[C + 1]``.  With ``clear`` the accumulators are zeroed in the same launch.  Synchronous."""
+        from . import _lib
+        c = self._need_rewards("reward_stats", stats=True)
+        K = len(c["names"]) + 1
+        buf = np.zeros(K + 2, np.uint64)
+        _lib.check(_lib.lib().gmr_motion_tracker_reward_stats(self.handle, _lib._ptr(buf), 1 if clear else 0))
+        episodes, steps, sums = int(buf[0]), int(buf[1]), buf[2:].view(np.float64).copy()
+        if raw:
+            return {"episodes": episodes, "steps": steps, "sums": sums}
+        out = {"episodes": episodes, "steps": steps / episodes if episodes else 0.0}
+        for k, name in enumerate(["reward"] + list(c["names"])):
+            out[name] = float(sums[k]) / episodes if episodes else 0.0
+        return out
+
+    def reward_state(self) -> Optional[Dict[str, np.ndarray]]:
+        """``ep_steps i32[N]`` and ``ep_sum f32[N,C+1]`` (column 0 is the reward) of the open episodes; ``None`` without statistics.
+        Synchronous."""
+        from . import _lib
+        c = getattr(self, "_rewards", None)
+        if c is None or not c["stats"]:
+            return None
+        N, K = self.num_envs, len(c["names"]) + 1
+        out = {"ep_steps": np.empty(N, np.int32), "ep_sum": np.empty((N, K), np.float32)}
+        _lib.check(_lib.lib().gmr_motion_tracker_reward_state(self.handle, _lib._ptr(out["ep_steps"]), _lib._ptr(out["ep_sum"])))
+        return out
 
     # ---- the step ---------------------------------------------------------------------------------------------------------
     def _counts(self):

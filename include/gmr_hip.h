@@ -1193,6 +1193,158 @@ int gmr_motion_tracker_set_disturbances(gmr_motion_tracker_t* t, const gmr_distu
 int gmr_motion_tracker_disturb_dev(gmr_motion_tracker_t* t, uint32_t common_step, const gmr_disturb_io_t* io, void* stream);   /* asynchronous */
 int gmr_motion_tracker_disturb(gmr_motion_tracker_t* t, uint32_t common_step, const gmr_disturb_io_t* io);
 
+/* ---- N13: tracker episode (reset states, the reward total and the episode statistics of a motion tracker) ---- */
+/* What booster_gym/envs/t1.py::step still left to the caller after N12: _reset_dofs, _reset_root_states and the delay_steps draw
+ * (t1.py:316-340), the sum over the blocks' weighted terms with its clip (t1.py:560-572), the two-group reward of
+ * t1_imitation.py:323-352, the reset and time-out words (t1.py:556-558) and the per-episode sums of utils/recorder.py:36-53, a Python loop
+ * with one device read per finished environment and reward term.  The statement of record is tests/episode_mirror.py; this is the same
+ * in words.  Everything is float32 with one rounding per operation unless it says double; a Python number is rounded to float32 where
+ * torch rounds it; the span (upper - lower) of a uniform is formed in double and rounded once.
+ * A. RESET STATES.  CONFIGURATION: gmr_reset_config_t -- base_init_state, default_dof_pos f32[R], env_origins f32[N][2] or NULL, copied to
+ * the device by the set_ call, three specs of the kind of N10, the yaw range, decimation, use_terrain.  STATE: reset_draws u32[N], zero.
+ * THE CALL takes the masked list of N9's hold: entry i is environment env_ids[i] (i without env_ids, then n = N), served when mask is NULL
+ * or mask[i] != 0; ids of served entries outside [0, N) are dropped and counted; every environment at most once in a list (the host twin
+ * refuses a repeated id, the device call cannot look).  No nonzero, no compaction.  It writes the simulator's own arrays in place, rows
+ * of served entries only -- root_states [N][13], dof_pos and dof_vel [N][R], optionally delay_steps and episode_steps i32[N] -- in the
+ * reference's order (t1.py:319-340, :311, :316), n = reset_draws[e]:
+ *   1. dof_pos[e][j] = randomise(default_dof_pos[j]) by init_dof_pos, dof_vel[e][j] = 0.
+ *   2. the root row = base_init_state; x, y += env_origins[e]; x, y = randomise(x, y) by init_base_pos_xy.
+ *   3. with use_terrain: z += the tracker's terrain height at (x, y), bit-equal to what terrain_heights returns there (N11); the plane adds
+ *      (float)0.
+ *   4. with a yaw range: yaw = (float)lo + (float)(hi - lo) * u, half = 0.5f * yaw, the quaternion (0, 0, sinf(half), cosf(half)):
+ *      isaacgym's quat_from_euler_xyz at zero roll and pitch as restated here; not pinned to isaacgym, which no test machine has.  Without
+ *      one the row's quaternion stays.
+ *   5. vx, vy = randomise(0) by init_base_lin_vel_xy (0 without a spec); the other velocities are the row's.
+ *   6. delay_steps[e] = philox_below(word, decimation) (decimation > 0 and the array given).
+ *   7. episode_steps[e] = 0 (the array given).
+ *   8. reset_draws[e] = n + 1.
+ * init_root_states [n][13], init_dof_pos [n][R], init_dof_vel [n][R], each or NULL, are indexed by LIST POSITION and replace
+ * base_init_state, default_dof_pos and the zero velocity of that entry (the rows step_links returns without advancing can be fed in:
+ * reference-state initialisation); a given root row keeps its quaternion unless a yaw range is set, and its vx, vy take the place of the
+ * zero of 5.
+ * DRAWS: environment e has R + 6 elements -- dofs 0..R-1, x, y, yaw, vx, vy, delay; element i takes philox4x32(counter (e, n, i >> 1, 4),
+ * key), words (0, 1) for an even i, (2, 3) for an odd one, and the recipe of N10 (uniform from the first word, gaussian from both,
+ * additive, scaling); the yaw is philox_unit and the delay philox_below of the first word.  Word 3 = 4 is a counter domain of its own
+ * next to 0 (clips), 1 (sensor noise), 2 (commands), 3 (kicks).  A block without a spec makes no Philox call.  THE REFERENCE draws ONE
+ * dof-noise row per call for all reset environments (default_dof_pos is [1, R], t1.py:320); here every environment draws its own: a draw
+ * depends on (seed, environment, its reset count, element) alone.
+ * chain = 1: the same launch also does what hold (N9; held = the new dof_pos, torque_acc = 0) and proprio_reset (N10; filtered velocities
+ * 0, last_root_vel = the new root_states[e][7:13]) would do afterwards (t1.py:309-313), each for the half that is configured.
+ * ONE launch, 16 lanes per list entry: the lanes stride over the dofs, lane 0 does the root.
+ * B. THE REWARD.  COLUMNS: the term rows of the blocks configured on the tracker when set_rewards is called, in the fixed order TERMS (6,
+ * N4), LINK_TERMS (4, N5; with links attached), PROPRIO_TERMS (14, N10; with set_proprio), FEET_TERMS (8, N11; with set_feet), CMD_TERMS
+ * (4, N12; with set_commands), then extra_cols <= GMR_REWARD_MAX_EXTRA columns of the caller's; C <= GMR_REWARD_MAX_COLS in all.
+ * gmr_reward_config_t.blocks names the configured blocks and is GMR_ERR_ARG when the tracker disagrees; a call is GMR_ERR_ARG when a block
+ * was configured or links were detached since.  WEIGHTS: the weight of a block's column is the one that block is configured with (the
+ * weights of N4 and N5, the scales of N10 to N12), copied from the handle when the call is enqueued; a caller column takes
+ * extra_weights.  groups[c] is GMR_REWARD_LOCOMOTION | GMR_REWARD_IMITATION, the groups column c feeds: one, both -- how the reference's
+ * double count of the imitation terms (t1_imitation.py:323-352: they enter the clipped locomotion sum and then the imitation sum) is
+ * expressed -- or none.
+ * THE CALL, for environment e, the inputs as the blocks' calls left them (an array that is NULL keeps its columns out; the array of a
+ * block that is not configured is never read):
+ *   1. scaled[e][c] = w_c * term_c; a column with w_c == 0 or an absent array is +0 and out.
+ *   2. S_g = the sum of scaled[e][c] over the columns of group g that are in, from +0 in rising c.
+ *   3. with only_positive[g]: S_g < 0 ? 0 : S_g (a NaN stays, as torch.clip keeps it; t1.py:571-572).  group_total[e] = (S_0, S_1).
+ *   4. reward[e] = group_weight[0] * S_0 + group_weight[1] * S_1, each product rounded, then the sum (t1_imitation.py:349-350).
+ *   5. reset[e] = done[e] != 0 and time_outs[e] = ((done[e] & GMR_REWARD_DONE_TIME_OUT) | (flags[e] & GMR_CMD_BOUNDARY)) != 0
+ *      (t1.py:556-558): done is the caller's OR of the done words of N10 and N11, flags the word of N12, both read as they lie; NULL is 0.
+ * ONE launch, 16 lanes per environment, lane l holds the columns l, l + 16, ..; every lane of the sixteen gathers the row through the
+ * group's permutes and adds it in the plain rising order of 2.  No clock, draw counter or state of another block is touched.
+ * C. THE EPISODE STATISTICS (gmr_reward_config_t.stats = 1).  STATE (device, owned by the tracker, one block made by set_rewards, zero):
+ * ep_steps i32[N], ep_sum f32[N][C + 1] (column 0 is the reward, column 1 + c is scaled column c), fin_count u32, fin_steps u64, fin_sum
+ * f64[C + 1], a started flag.  PER REWARD CALL (recorder.py:36-53), in the same launch:
+ *   6. ep_steps[e] += 1, except in the very first call after set_rewards: the reference starts from zeros there (:37-40), so its first
+ *      episode counts one step fewer; kept.
+ *   7. ep_sum[e][k] += value (a float32 add).
+ *   8. where reset[e]: fin_count += 1 and fin_steps += ep_steps[e] (unsigned integer atomics), the row ep_sum[e] goes into fin_sum, then
+ *      ep_steps[e] = 0 and ep_sum[e] = 0.
+ * fin_sum does not depend on arrival order: workgroup w holds the environments 16 w .. 16 w + 15; its partial of column k is
+ * p = +0, p = p + (double)ep_sum[e][k] over its reset environments in rising e; a SECOND small launch of one workgroup then chains
+ * fin_sum[k] = fin_sum[k] + p_w over the workgroups that have a reset environment, in rising w.  No floating-point atomics.
+ * READING OUT: reward_stats copies out[0] = fin_count (as u64), out[1] = fin_steps, out[2 + k] = fin_sum[k] as f64, and with clear = 1
+ * zeroes the three, in one launch; ep_steps, ep_sum and the started flag stay.  The means are the caller's divisions.
+ * The tracker stays SINGLE-STREAM. */
+#define GMR_REWARD_MAX_EXTRA 16
+#define GMR_REWARD_MAX_COLS 52
+#define GMR_REWARD_BLOCK_TERMS 1
+#define GMR_REWARD_BLOCK_LINKS 2
+#define GMR_REWARD_BLOCK_PROPRIO 4
+#define GMR_REWARD_BLOCK_FEET 8
+#define GMR_REWARD_BLOCK_COMMANDS 16
+#define GMR_REWARD_LOCOMOTION 1
+#define GMR_REWARD_IMITATION 2
+#define GMR_REWARD_DONE_TIME_OUT 4     /* bit 2 of gmr_proprio_out_t.done */
+typedef struct {            /* the configuration of set_reset_states: values and two host addresses */
+  float base_init_state[13];          /* pos, quat xyzw, lin vel, ang vel (t1.py:328)                                 */
+  const float *default_dof_pos;       /* [R] (t1.py:320)                                                              */
+  const float *env_origins;           /* [N][2] or NULL (t1.py:329)                                                   */
+  gmr_proprio_noise_t init_dof_pos, init_base_pos_xy, init_base_lin_vel_xy;   /* (t1.py:320, :330, :337-340)          */
+  double yaw_range[2];                /* (lower, upper), looked at with yaw = 1; the reference: (0, 2 pi) (t1.py:335) */
+  int32_t yaw;                        /* 0 or 1: draw the yaw                                                         */
+  int32_t decimation;                 /* in [0, GMR_CONTROL_MAX_DECIMATION]; 0: no delay draw (t1.py:316)             */
+  int32_t use_terrain;                /* 0 or 1 (t1.py:331)                                                           */
+} gmr_reset_config_t;
+typedef struct {            /* the arrays of a reset_states call: device pointers (gmr_motion_tracker_reset_states: host pointers) */
+  float *root_states;                 /* [N][13], rows of served entries written                                      */
+  float *dof_pos, *dof_vel;           /* [N][R]                                                                       */
+  int32_t *delay_steps;               /* [N] or NULL                                                                  */
+  int32_t *episode_steps;             /* [N] or NULL                                                                  */
+  const float *init_root_states;      /* [n][13] by list position, or NULL                                            */
+  const float *init_dof_pos, *init_dof_vel;   /* [n][R] by list position, or NULL                                     */
+} gmr_reset_io_t;
+typedef struct {            /* the configuration of set_rewards: values */
+  float group_weight[2];              /* locomotion_weight, imitation_weight (t1_imitation.py:349-350)                */
+  float extra_weights[GMR_REWARD_MAX_EXTRA];   /* of the caller's columns                                            */
+  int32_t only_positive[2];           /* 0 or 1 per group (t1.py:571)                                                 */
+  int32_t blocks;                     /* GMR_REWARD_BLOCK_*: the blocks configured on the tracker                     */
+  int32_t extra_cols;                 /* E in [0, GMR_REWARD_MAX_EXTRA]                                               */
+  int32_t stats;                      /* 0 or 1: keep the episode statistics                                          */
+  uint8_t groups[GMR_REWARD_MAX_COLS];   /* per column GMR_REWARD_LOCOMOTION | GMR_REWARD_IMITATION                  */
+} gmr_reward_config_t;
+typedef struct {            /* the inputs of a rewards call: device pointers (gmr_motion_tracker_rewards: host pointers), each or NULL */
+  const float *term;                  /* [N][6]  gmr_tracker_out_t.term                                               */
+  const float *link_term;             /* [N][4]  gmr_tracker_links_out_t.link_term                                    */
+  const float *proprio_term;          /* [N][14] gmr_proprio_out_t.term                                               */
+  const float *feet_term;             /* [N][8]  gmr_feet_out_t.term                                                  */
+  const float *cmd_term;              /* [N][4]  gmr_commands_out_t.term                                              */
+  const float *extra;                 /* [N][E]                                                                       */
+  const int32_t *done;                /* [N] the OR of the done words; NULL: nobody resets                            */
+  const int32_t *flags;               /* [N] gmr_commands_out_t.flags; NULL: no boundary                              */
+} gmr_reward_in_t;
+typedef struct {            /* the outputs of a rewards call, each an address or NULL */
+  float *reward;                      /* [N]                                                                          */
+  float *scaled;                      /* [N][C] what the reference puts into extras["rew_terms"] (t1.py:570)          */
+  float *group_total;                 /* [N][2]                                                                       */
+  int32_t *reset;                     /* [N] 0 or 1                                                                   */
+  int32_t *time_outs;                 /* [N] 0 or 1                                                                   */
+} gmr_reward_out_t;
+/* The reset-state configuration (t1.py:316-340): every number finite (in float32 too), each spec as in N10 (b >= 0 for a gaussian),
+ * upper >= lower, decimation in [0, GMR_CONTROL_MAX_DECIMATION].  Allocates reset_draws (zero) and the device copy of env_origins;
+ * synchronises the device.  Launches in flight keep the configuration they carry. */
+int gmr_motion_tracker_set_reset_states(gmr_motion_tracker_t* t, const gmr_reset_config_t* cfg);
+/* _reset_dofs, _reset_root_states and the delay draw (t1.py:316-340), chained also t1.py:309-313: ONE launch */
+int gmr_motion_tracker_reset_states_dev(gmr_motion_tracker_t* t, int n, const int32_t* d_env_ids, const int32_t* d_mask,
+                                        const gmr_reset_io_t* io, int chain, void* stream);         /* asynchronous */
+int gmr_motion_tracker_reset_states(gmr_motion_tracker_t* t, int n, const int32_t* env_ids, const int32_t* mask, const gmr_reset_io_t* io,
+                                    int chain, int* ignored);
+/* reset_draws u32[N] on the host (the count behind the draws of t1.py:316-340); synchronises */
+int gmr_motion_tracker_reset_state(gmr_motion_tracker_t* t, uint32_t* reset_draws);
+/* The reward configuration (t1.py:560-572, t1_imitation.py:323-352): the weights finite, extra_cols in [0, GMR_REWARD_MAX_EXTRA], the
+ * flags 0 or 1, blocks what the tracker has configured, groups[c] <= 3 for c < C.  With stats = 1 allocates the state and zeroes it;
+ * synchronises the device either way.  Launches in flight keep the configuration they carry. */
+int gmr_motion_tracker_set_rewards(gmr_motion_tracker_t* t, const gmr_reward_config_t* cfg);
+/* The call (t1.py:556-572, t1_imitation.py:323-352, recorder.py:36-53): ONE launch, TWO with the statistics */
+int gmr_motion_tracker_rewards_dev(gmr_motion_tracker_t* t, const gmr_reward_in_t* in, const gmr_reward_out_t* out,
+                                   void* stream);                                                   /* asynchronous */
+int gmr_motion_tracker_rewards(gmr_motion_tracker_t* t, const gmr_reward_in_t* in, const gmr_reward_out_t* out);
+/* The read-out of the statistics (recorder.py:55-62, what t1.py:556-558 hands the Recorder through the runner): out u64[C + 3] -- episodes,
+ * steps, then C + 1 doubles -- or NULL; clear = 1 zeroes the accumulators in the same launch.  GMR_ERR_ARG without statistics. */
+int gmr_motion_tracker_reward_stats_dev(gmr_motion_tracker_t* t, uint64_t* out, int clear, void* stream);   /* asynchronous */
+int gmr_motion_tracker_reward_stats(gmr_motion_tracker_t* t, uint64_t* out, int clear);
+/* the running sums of the open episodes on the host (recorder.py:36-53: episode_steps and episode_statistics), either may be NULL;
+ * synchronises.  GMR_ERR_ARG without statistics. */
+int gmr_motion_tracker_reward_state(gmr_motion_tracker_t* t, int32_t* ep_steps, float* ep_sum);
+
 /* ---- multi-GPU: one rank per GPU, ONE broadcast, no per-step collective ------------ */
 /* The reference parallelises over files with mp.Pool on one CPU (scripts/smplx_to_robot_dataset.py:241-242); here
  * streams shard over the ranks of one node and the only data that crosses ranks is the packed robot model + task set.
