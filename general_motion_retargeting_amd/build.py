@@ -126,6 +126,16 @@ def build_rowfma_probe(force: bool = False) -> str:
     return _build_probe_libs(ROWFMA_PROBE_SRC, {"flags": ROWFMA_PROBE_LIB}, force)["flags"]
 
 
+# The probe of the hazard-complete solver statements (tests/hip/filled_probe.hip, tests/test_filled_waits.py), under the
+# library's own flags.
+FILLED_PROBE_SRC = os.path.join(os.path.dirname(PROBE_SRC), "filled_probe.hip")
+FILLED_PROBE_LIB = os.path.join(os.path.dirname(PROBE_SRC), "libgmr_filled_probe.so")
+
+
+def build_filled_probe(force: bool = False) -> str:
+    return _build_probe_libs(FILLED_PROBE_SRC, {"flags": FILLED_PROBE_LIB}, force)["flags"]
+
+
 def build_variant(name: str, defines=(), verbose: bool = False) -> str:
     """libgmrhip_<name>.so with extra -D flags on every source (objects cached per flag set)."""
     out = os.path.join(HERE, f"libgmrhip_{name}.so")

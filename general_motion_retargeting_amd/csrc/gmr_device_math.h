@@ -599,6 +599,23 @@ __device__ __forceinline__ double row_bcast_d(double v, int k) {
 //     accumulator as it is, which is also what the zero of bound_ctrl:1 gives).
 // To pay the s_nop once per pivot and not once per update, the multi-update forms put a whole run into one statement.
 // GMR_NO_ROW_FMA restores row_bcast_d + fma (A/B builds).
+// HAZARD-COMPLETE forms (row_bcast_fnma_pivot, row_backsub_fill, row_dot_backsub): a whole pivot, a whole back
+// substitution in one statement, whose DPP sources get their wait states from useful instructions of the same statement
+// wherever the algorithm has independent ones.  The rules they rely on, beside the three above:
+//   * a wait state is any instruction issued between the write and the DPP read, so two independent VALU instructions
+//     serve as well as s_nop 1 (and s_nop 0 beside one of them);
+//   * consecutive DPP reads of a register that was written three or more instructions ago need nothing (a pivot's column
+//     updates all read l; a dot product's steps all read v);
+//   * an ordinary (non-DPP) read of a result needs no wait state: the multiply of a substitution step follows the
+//     v_fmac_f64_dpp of the step before directly;
+//   * the assembler checks every operand, but nobody checks the distances: they are counted in the comments below.
+// Behind EVERY asm statement the compiler itself puts one wait state (s_nop 0) when the next instruction reads a register
+// the statement wrote.  Its hazard recogniser cannot look into the text, so it assumes the worst case of the rule that a
+// VALU write with a destination select (SDWA, op_sel, the 8-bit conversions) must be one wait state ahead of a VALU read of
+// that register.  None of these statements has such a write; the pad cannot be switched off, it can only be avoided by
+// not ending a statement where a result is consumed at once -- which is why a whole substitution is ONE statement (it
+// was one s_nop 0 per step) and a pivot is one statement instead of two.  The new statements still draw it once each.
+// GMR_NO_FILLED_WAITS restores the per-step statements (A/B builds).
 #define GMR_RF_CTRL " row_mask:0xf bank_mask:0xf\n\t"
 template <int K, bool NEG>
 __device__ __forceinline__ double row_bcast_fma(double acc, double v, double m) {   // acc +- bcast(v, K) m
@@ -674,6 +691,37 @@ __device__ __forceinline__ void row_bcast_fnma_cols(double* r, double l) {
   GMR_RF_COLS(13, GMR_RF_T13, GMR_RF_A13) GMR_RF_COLS(14, GMR_RF_T14, GMR_RF_A14)
 #endif
 }
+// One pivot whose next diagonal lies in the same row: r[i] -= bcast(l, K + i) l for i < N (r[0] the next pivot's
+// diagonal, lane K), and the new r[0] of lane K handed to the whole row.  = row_bcast_fnma_bcast<K>(r[0], l) followed by
+// row_bcast_fnma_cols<K + 1, N - 1>(r + 1, l), the same fused operations on the same numbers.  One leading s_nop 1 (l comes
+// out of a select just before); the broadcast of r[0] stands BEHIND the other column updates, which are its wait states
+// (N >= 3: two or more instructions between the write of r[0] and its DPP read; N = 2: one and s_nop 0; N = 1: s_nop 1).
+#define GMR_RF_PIVOT(N, PAD, TEXT, ...)                                                                                  \
+  if constexpr (N_ == N)                                                                                                 \
+    asm("s_nop 1\n\t" TEXT PAD "v_mov_b64_dpp %[d], %[a0] row_newbcast:%[k] row_mask:0xf bank_mask:0xf bound_ctrl:1"     \
+        : [d] "=&v"(d), __VA_ARGS__ : [l] "v"(l), [k] "n"(K));
+template <int K, int N_>
+__device__ __forceinline__ double row_bcast_fnma_pivot(double* r, double l) {
+  static_assert(N_ >= 1 && N_ <= 15 && K >= 0 && K + N_ <= 16, "at most 15 columns of one 16-lane row");
+  double d;
+#ifdef GMR_NO_ROW_FMA
+  d = row_bcast_fnma_bcast<K>(r[0], l);
+  if constexpr (N_ > 1) row_bcast_fnma_cols<K + 1, N_ - 1>(r + 1, l);
+#else
+#define GMR_RF_T15 GMR_RF_T14 GMR_RF_COL(14)
+#define GMR_RF_A15 GMR_RF_A14, GMR_RF_ACC(14)
+  GMR_RF_PIVOT(1, "s_nop 1\n\t", GMR_RF_T1, GMR_RF_A1) GMR_RF_PIVOT(2, "s_nop 0\n\t", GMR_RF_T2, GMR_RF_A2)
+  GMR_RF_PIVOT(3, "", GMR_RF_T3, GMR_RF_A3) GMR_RF_PIVOT(4, "", GMR_RF_T4, GMR_RF_A4) GMR_RF_PIVOT(5, "", GMR_RF_T5, GMR_RF_A5)
+  GMR_RF_PIVOT(6, "", GMR_RF_T6, GMR_RF_A6) GMR_RF_PIVOT(7, "", GMR_RF_T7, GMR_RF_A7) GMR_RF_PIVOT(8, "", GMR_RF_T8, GMR_RF_A8)
+  GMR_RF_PIVOT(9, "", GMR_RF_T9, GMR_RF_A9) GMR_RF_PIVOT(10, "", GMR_RF_T10, GMR_RF_A10) GMR_RF_PIVOT(11, "", GMR_RF_T11, GMR_RF_A11)
+  GMR_RF_PIVOT(12, "", GMR_RF_T12, GMR_RF_A12) GMR_RF_PIVOT(13, "", GMR_RF_T13, GMR_RF_A13) GMR_RF_PIVOT(14, "", GMR_RF_T14, GMR_RF_A14)
+  GMR_RF_PIVOT(15, "", GMR_RF_T15, GMR_RF_A15)
+#undef GMR_RF_T15
+#undef GMR_RF_A15
+#endif
+  return d;
+}
+#undef GMR_RF_PIVOT
 // acc +- sum over i < N of bcast(v, K0 + S i) m[S i]: one dependent chain behind one s_nop (the products of a row of
 // H, of Y_l^T, with a vector that lives in the lanes of the row)
 #define GMR_RF_DOT(SG, i) "v_fmac_f64_dpp %[acc], %[v], " SG "%[m" #i "] row_newbcast:%[k]+%[s]*" #i GMR_RF_CTRL
@@ -715,6 +763,72 @@ __device__ __forceinline__ double row_bcast_fma_dot(double acc, double v, const 
 #endif
   return acc;
 }
+// ---- whole back substitutions of the <7, 9> shape -------------------------------------------------------------------
+// A step is  t = acc * dinv;  acc -= bcast(t, K0 + i) m[i]  (i = N - 1 .. 0: row i is final when its step comes, and its
+// x_i = y_i / sqrt(d_i) goes to the rows above).  t is written by the instruction before its DPP read: two wait states.
+// row_backsub_fill<K0> (N = 9, the trunk): the wait states of steps 8 .. 1 are the SIXTEEN products f[j] * fs that the NEXT
+// substitution needs as operands (two per step; they read nothing the steps write), step 0 has s_nop 1.  The same multiplies
+// on the same operands as f[j] *= fs in front of the chain (in place: no register beside t is added).
+#define GMR_RF_BS_MUL "v_mul_f64 %[t], %[acc], %[dv]\n\t"
+#define GMR_RF_BS_FMA(i) "v_fmac_f64_dpp %[acc], %[t], -%[m" #i "] row_newbcast:%[k]+" #i GMR_RF_CTRL
+#define GMR_RF_BS_FILL(j) "v_mul_f64 %[f" #j "], %[f" #j "], %[fs]\n\t"
+#define GMR_RF_BS_STEP(i, j0, j1) GMR_RF_BS_MUL GMR_RF_BS_FILL(j0) GMR_RF_BS_FILL(j1) GMR_RF_BS_FMA(i)
+#define GMR_RF_BS_PLAIN(i) GMR_RF_BS_MUL "s_nop 1\n\t" GMR_RF_BS_FMA(i)
+#define GMR_RF_BS_M(i) [m##i] "v"(m[i])
+#define GMR_RF_BS_F(j) [f##j] "+v"(f[j])
+template <int K0>
+__device__ __forceinline__ double row_backsub_fill(double acc, double dinv, const double* m, double* f, double fs) {
+  static_assert(K0 >= 0 && K0 + 9 <= 16, "nine lanes of one 16-lane row");
+#ifdef GMR_NO_ROW_FMA
+#pragma unroll
+  for (int j = 0; j < 16; j++) f[j] *= fs;
+#pragma unroll
+  for (int i = 8; i >= 0; i--) acc = fma(-row_bcast_d(acc * dinv, K0 + i), m[i], acc);
+#else
+  double t;
+  asm(GMR_RF_BS_STEP(8, 0, 1) GMR_RF_BS_STEP(7, 2, 3) GMR_RF_BS_STEP(6, 4, 5) GMR_RF_BS_STEP(5, 6, 7) GMR_RF_BS_STEP(4, 8, 9)
+      GMR_RF_BS_STEP(3, 10, 11) GMR_RF_BS_STEP(2, 12, 13) GMR_RF_BS_STEP(1, 14, 15) GMR_RF_BS_PLAIN(0)
+      : [acc] "+v"(acc), [t] "=&v"(t), GMR_RF_BS_F(0), GMR_RF_BS_F(1), GMR_RF_BS_F(2), GMR_RF_BS_F(3), GMR_RF_BS_F(4), GMR_RF_BS_F(5),
+        GMR_RF_BS_F(6), GMR_RF_BS_F(7), GMR_RF_BS_F(8), GMR_RF_BS_F(9), GMR_RF_BS_F(10), GMR_RF_BS_F(11), GMR_RF_BS_F(12), GMR_RF_BS_F(13),
+        GMR_RF_BS_F(14), GMR_RF_BS_F(15)
+      : [dv] "v"(dinv), [fs] "v"(fs), [k] "n"(K0), GMR_RF_BS_M(0), GMR_RF_BS_M(1), GMR_RF_BS_M(2), GMR_RF_BS_M(3), GMR_RF_BS_M(4),
+        GMR_RF_BS_M(5), GMR_RF_BS_M(6), GMR_RF_BS_M(7), GMR_RF_BS_M(8));
+#endif
+  return acc;
+}
+// row_dot_backsub<KD, K0> (the limb): acc -= sum over u < 9 of bcast(v, KD + u) y[u] (one chain behind one s_nop 1, as
+// row_bcast_fma_dot<KD, 1, 9, true>), then the seven steps of the substitution over lanes K0 .. K0 + 6.  Nothing independent
+// is left at this point of a round: every step carries its s_nop 1.
+#define GMR_RF_BS_DOT(u) "v_fmac_f64_dpp %[acc], %[v], -%[y" #u "] row_newbcast:%[kd]+" #u GMR_RF_CTRL
+#define GMR_RF_BS_Y(u) [y##u] "v"(y[u])
+template <int KD, int K0>
+__device__ __forceinline__ double row_dot_backsub(double acc, double v, const double* y, double dinv, const double* m) {
+  static_assert(KD >= 0 && KD + 9 <= 16 && K0 >= 0 && K0 + 7 <= 16, "lanes of one 16-lane row");
+#ifdef GMR_NO_ROW_FMA
+  acc = row_bcast_fma_dot<KD, 1, 9, true>(acc, v, y);
+#pragma unroll
+  for (int i = 6; i >= 0; i--) acc = fma(-row_bcast_d(acc * dinv, K0 + i), m[i], acc);
+#else
+  double t;
+  asm("s_nop 1\n\t" GMR_RF_BS_DOT(0) GMR_RF_BS_DOT(1) GMR_RF_BS_DOT(2) GMR_RF_BS_DOT(3) GMR_RF_BS_DOT(4) GMR_RF_BS_DOT(5)
+      GMR_RF_BS_DOT(6) GMR_RF_BS_DOT(7) GMR_RF_BS_DOT(8)
+      GMR_RF_BS_PLAIN(6) GMR_RF_BS_PLAIN(5) GMR_RF_BS_PLAIN(4) GMR_RF_BS_PLAIN(3) GMR_RF_BS_PLAIN(2) GMR_RF_BS_PLAIN(1) GMR_RF_BS_PLAIN(0)
+      : [acc] "+v"(acc), [t] "=&v"(t)
+      : [v] "v"(v), [dv] "v"(dinv), [kd] "n"(KD), [k] "n"(K0), GMR_RF_BS_Y(0), GMR_RF_BS_Y(1), GMR_RF_BS_Y(2), GMR_RF_BS_Y(3),
+        GMR_RF_BS_Y(4), GMR_RF_BS_Y(5), GMR_RF_BS_Y(6), GMR_RF_BS_Y(7), GMR_RF_BS_Y(8), GMR_RF_BS_M(0), GMR_RF_BS_M(1), GMR_RF_BS_M(2),
+        GMR_RF_BS_M(3), GMR_RF_BS_M(4), GMR_RF_BS_M(5), GMR_RF_BS_M(6));
+#endif
+  return acc;
+}
+#undef GMR_RF_BS_MUL
+#undef GMR_RF_BS_FMA
+#undef GMR_RF_BS_FILL
+#undef GMR_RF_BS_STEP
+#undef GMR_RF_BS_PLAIN
+#undef GMR_RF_BS_M
+#undef GMR_RF_BS_F
+#undef GMR_RF_BS_DOT
+#undef GMR_RF_BS_Y
 #undef GMR_RF_M
 #undef GMR_RF_A1
 #undef GMR_RF_A2

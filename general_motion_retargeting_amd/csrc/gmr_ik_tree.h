@@ -113,6 +113,13 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
   // DPP broadcasts that feed a multiply-add are folded into it (row_bcast_fma and its multi-update forms: the same
   // fused operation on the same three numbers); the v_readlane path of the <8, 10> instance keeps fma(.., TR_BCAST(..), ..)
   constexpr bool FOLD = ROWS || DPPB;
+  // ... and a pivot, a back substitution is ONE statement that covers its own DPP wait states (row_bcast_fnma_pivot,
+  // row_backsub_fill, row_dot_backsub: the same operations on the same operands in the same order per row; the <7, 9> shape)
+#ifdef GMR_NO_FILLED_WAITS
+  constexpr bool FILLED = false;
+#else
+  constexpr bool FILLED = FOLD && TR_NL == 7 && TR_NT == 9;
+#endif
 #define TR_SYNC() do { if (ROWS) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); else __syncthreads(); } while (0)
   const int n = L.nv, ldh = L.o.ldh;
   const double* H = sm + L.o.H;
@@ -226,7 +233,9 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
       if (lane == p) mydinv = dinv;                          // (rows <= p keep r[p]: l = 0 leaves a finished row alone)
       double dinv_next = 1.0;
       if constexpr (p + 1 < TR_NL) {
-        if constexpr (FOLD) {
+        if constexpr (FILLED) {                              // all columns of the pivot, the new diagonal broadcast behind them
+          dp = row_bcast_fnma_pivot<p + 1, TR_NV - p - 1>(r + p + 1, l);
+        } else if constexpr (FOLD) {
           dp = row_bcast_fnma_bcast<p + 1>(r[p + 1], l);
         } else {
           r[p + 1] = fma(-l, TR_BCAST(l, p + 1), r[p + 1]);
@@ -237,7 +246,8 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
       const double yp = TR_BCAST(b, p) * dinv;               // row p keeps its unscaled b (l = 0 there): scaled after the loop
       b = fma(-l, yp, b);
       constexpr int k0 = p + 1 < TR_NL ? p + 2 : p + 1;
-      if constexpr (FOLD) {
+      if constexpr (FILLED && p + 1 < TR_NL) {
+      } else if constexpr (FOLD) {
         row_bcast_fnma_cols<k0, TR_NV - k0>(r + k0, l);
       } else {
 #pragma unroll
@@ -251,8 +261,9 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
     // started equal to entry (k, a) of lane k and received the same fused updates at pivots 0 .. a-1 -- and nothing
     // touched it since.  Scaled by the lane's own 1 / sqrt(d_a) it is column a of the lower factor, bit for bit what
     // lane k holds in its column a: no transpose through LDS.
+    // FILLED: the sixteen products are the wait states of the trunk back substitution (4), the selects follow it.
     double ltl[TR_NL], yl[TR_NT];
-    {
+    if constexpr (!FILLED) {
       TR_ROW()
 #pragma unroll
       for (int m = 0; m < TR_NL; m++) ltl[m] = (is_limb && m > a) ? r[m] * mydinv : 0.0;
@@ -318,7 +329,9 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
         if (t == q) tdinv = dinv;                            // (rows <= q keep s[q], as in (2))
         double dinv_next = 1.0;
         if constexpr (q + 1 < TR_NT) {
-          if constexpr (FOLD) {
+          if constexpr (FILLED) {
+            dq = row_bcast_fnma_pivot<TR_NL + q + 1, TR_NT - q - 1>(s + q + 1, l);
+          } else if constexpr (FOLD) {
             dq = row_bcast_fnma_bcast<TR_NL + q + 1>(s[q + 1], l);
           } else {
             s[q + 1] = fma(-l, TR_BCAST(l, TR_NL + q + 1), s[q + 1]);
@@ -328,7 +341,8 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
         }
         const double yq = TR_BCAST(bt, TR_NL + q) * dinv;
         bt = fma(-l, yq, bt);
-        if constexpr (FOLD && q + 2 < TR_NT) {
+        if constexpr (FILLED) {
+        } else if constexpr (FOLD && q + 2 < TR_NT) {
           row_bcast_fnma_cols<TR_NL + q + 2, TR_NT - q - 2>(s + q + 2, l);
         } else {
 #pragma unroll
@@ -346,7 +360,21 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
         for (int q = 0; q < TR_NT; q++) lt[q] = (is_trunk && q > t) ? s[q] * tdinv : 0.0;
       }
       bt *= tdinv;                                           // y (rows kept their unscaled right-hand side)
-      if constexpr (FOLD) {
+      if constexpr (FILLED) {
+        // one statement; its wait states are r[k] *= mydinv, the operands of (5): Y_l (trunk columns) and, behind their
+        // selects, L_l^T (limb columns)
+        if constexpr (TR_NL == 7 && TR_NT == 9) {            // (the statement is written out for this shape)
+          double f[TR_NV];
+#pragma unroll
+          for (int j = 0; j < TR_NV; j++) f[j] = r[(TR_NL + j) % TR_NV];
+          bt = row_backsub_fill<TR_NL>(bt, tdinv, lt, f, mydinv);
+          TR_ROW()
+#pragma unroll
+          for (int u = 0; u < TR_NT; u++) yl[u] = f[u];      // (used by limb lanes only)
+#pragma unroll
+          for (int m = 0; m < TR_NL; m++) ltl[m] = (is_limb && m > a) ? f[TR_NT + m] : 0.0;
+        }
+      } else if constexpr (FOLD) {
         tr_static_for<0, TR_NT>([&](auto I) __attribute__((always_inline)) {
           constexpr int q = TR_NT - 1 - decltype(I)::value;
           bt = row_bcast_fma<TR_NL + q, true>(bt, bt * tdinv, lt[q]);
@@ -366,7 +394,9 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
     double x = bt;                                                                     // trunk lanes
     {
       double bb = b;                                                                   // y_l (limb lanes)
-      if constexpr (FOLD) {
+      if constexpr (FILLED) {
+        if constexpr (TR_NL == 7 && TR_NT == 9) bb = row_dot_backsub<TR_NL, 0>(bb, bt, yl, mydinv, ltl);
+      } else if constexpr (FOLD) {
         // unconditional: a trunk lane's bb is dead (its x is bt, and the back substitution reads limb lanes only)
         bb = row_bcast_fma_dot<TR_NL, 1, TR_NT, true>(bb, bt, yl);                     // Y_l[u][a]
         tr_static_for<0, TR_NL>([&](auto I) __attribute__((always_inline)) {
