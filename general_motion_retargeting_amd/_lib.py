@@ -182,6 +182,11 @@ _SIGS = {
     "gmr_motion_tracker_reward_stats_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "gmr_motion_tracker_reward_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "gmr_motion_tracker_reward_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gmr_motion_tracker_set_rollout": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double]),
+    "gmr_motion_tracker_record_dev": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 8),
+    "gmr_motion_tracker_record": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 7),
+    "gmr_motion_tracker_advantages_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "gmr_motion_tracker_advantages": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "gmr_comm_create": (C.c_int, [C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),
     "gmr_comm_destroy": (C.c_int, [C.c_void_p]),
     "gmr_comm_rank": (C.c_int, [C.c_void_p]),
@@ -780,6 +785,22 @@ class RewardIn(C.Structure):
 class RewardOut(C.Structure):
     """``gmr_reward_out_t``: the outputs of ``gmr_motion_tracker_rewards[_dev]``, each an address or NULL"""
     _fields_ = [(k, C.c_void_p) for k in REWARD_OUT_FIELDS]
+
+
+# gmr_motion_tracker_set_rollout / _record[_dev] / _advantages[_dev] (include/gmr_hip.h, "tracker rollout")
+ROLLOUT_ENVS, ROLLOUT_FOLD = 64, 64
+ROLLOUT_IO_FIELDS = ("obs", "priv", "actions", "rewards", "dones", "time_outs")
+ROLLOUT_OUT_FIELDS = ("advantages", "returns", "normalized", "stats")
+
+
+class RolloutIo(C.Structure):
+    """``gmr_rollout_io_t``: the caller's rollout arrays, each an address or NULL"""
+    _fields_ = [(k, C.c_void_p) for k in ROLLOUT_IO_FIELDS]
+
+
+class RolloutOut(C.Structure):
+    """``gmr_rollout_out_t``: the outputs of ``gmr_motion_tracker_advantages[_dev]``, each an address or NULL"""
+    _fields_ = [(k, C.c_void_p) for k in ROLLOUT_OUT_FIELDS]
 
 
 # gmr_motion_tracker_set_preview: the block bits in row order, the frames and the limits (include/gmr_hip.h, "tracker preview")

@@ -5,7 +5,8 @@
 // gmr_tracker_anchor.hip its anchors, gmr_tracker_control.hip its control tables and the two arrays of the actuator model,
 // gmr_tracker_proprio.hip its proprioception tables and the six arrays behind them, gmr_tracker_feet.hip its terrain, its feet tables and
 // the two arrays behind them, gmr_tracker_commands.hip its command and disturbance tables and the arrays of the velocity commands,
-// gmr_tracker_episode.hip its reset-state and reward tables, the reset counters and the arrays of the episode statistics.
+// gmr_tracker_episode.hip its reset-state and reward tables, the reset counters and the arrays of the episode statistics,
+// gmr_tracker_rollout.hip its rollout configuration and the partial sums of an advantages call.
 #pragma once
 #include <stdint.h>
 
@@ -249,6 +250,15 @@ struct RewardState {
   double* part = nullptr;                   // [ceil(N / 16)][C + 1] the partials of one call
   uint32_t* wg_any = nullptr;               // [ceil(N / 16)] the workgroup finished an episode in this call
 };
+// the rollout configuration of a tracker and its scratch: device pointers into the rollout block
+struct RolloutTables {
+  int32_t H = 0;                            // the horizon; 0: the rollout was never set
+  int32_t O = 0, P = 0, A = 0;              // columns of obs, priv and actions
+  double gamma = 0.0, lam = 0.0;            // as given
+  float g = 0.0f, gl = 0.0f;                // (float)gamma, (float)(gamma * lam)
+  double* part = nullptr;                   // [ceil(N / GMR_ROLLOUT_ENVS)][2] the partial sums of one call
+  double* sums = nullptr;                   // [4] S1, S2, mean, std of one call beyond GMR_ROLLOUT_FOLD groups
+};
 }  // namespace gmr
 
 struct gmr_motion_tracker {
@@ -290,6 +300,8 @@ struct gmr_motion_tracker {
   gmr::RewardTables rewards;     // rewards.on = 0 until gmr_motion_tracker_set_rewards configures them
   gmr::RewardState reward_state;
   gmr::DeviceBlock reward_block; // the arrays of reward_state: one allocation, made by gmr_motion_tracker_set_rewards with statistics
+  gmr::RolloutTables rollout;    // rollout.H = 0 until gmr_motion_tracker_set_rollout configures it
+  gmr::DeviceBlock rollout_block; // the partial sums of an advantages call: one allocation, made by gmr_motion_tracker_set_rollout
   std::vector<double> clip_w;    // the clip weights as given at creation (empty: uniform)
   std::mutex mu;                 // the tables, and the whole of every synchronous entry point
 };

@@ -189,6 +189,7 @@ class MotionTracker:
         self._commands = None         # ((L, A) or None,) once set_commands has configured the velocity commands
         self._resets = None           # (R, decimation) once set_reset_states has configured the reset states
         self._rewards = None          # the checked configuration once set_rewards has laid the reward columns out
+        self._rollout = None          # the checked configuration once set_rollout has configured the rollout
         self._disturb = None          # (kick_every, push_every, push_duration) once set_disturbances has configured kicks and pushes
         if sc is not None or wt is not None:
             self.set_terms(sc, wt)
@@ -1932,6 +1933,182 @@ class MotionTracker:
         out = {"ep_steps": np.empty(N, np.int32), "ep_sum": np.empty((N, K), np.float32)}
         _lib.check(_lib.lib().gmr_motion_tracker_reward_state(self.handle, _lib._ptr(out["ep_steps"]), _lib._ptr(out["ep_sum"])))
         return out
+
+    # ---- rollout storage, GAE, returns and advantages ---------------------------------------------------------
+    @staticmethod
+    def _rollout_setup(horizon, obs_cols, priv_cols, act_cols, gamma, lam):
+        """the checks of :meth:`set_rollout`, all of them before the library is loaded -> a dict of the checked values"""
+        for k, v, least in (("horizon", horizon, 1), ("obs_cols", obs_cols, 1), ("priv_cols", priv_cols, 0), ("act_cols", act_cols, 1)):
+            if isinstance(v, bool) or int(v) != v or v < least or v >= 2 ** 31:
+                raise ValueError(f"set_rollout: {k} = {v!r}: a whole number of at least {least} is needed")
+        for k, v in (("gamma", gamma), ("lam", lam)):
+            v = float(v)
+            if not np.isfinite(v) or not 0.0 <= v <= 1.0:
+                raise ValueError(f"set_rollout: {k} = {v}: a finite number in [0, 1] is needed")
+        return {"horizon": int(horizon), "obs_cols": int(obs_cols), "priv_cols": int(priv_cols), "act_cols": int(act_cols), "gamma": float(gamma),
+                "lam": float(lam)}
+
+    def set_rollout(self, horizon: int, obs_cols: int, priv_cols: int, act_cols: int, gamma: float, lam: float) -> Dict[str, object]:
+        """Configures the rollout (runner.py:36-42, :141-142): ``horizon`` slots of ``num_envs`` rows with ``obs_cols``, ``priv_cols`` (0:
+        no privileged observations) and ``act_cols`` columns, and the two discounts of the advantages, each in ``[0, 1]``.  The arrays stay
+        the caller's; the tracker allocates the scratch of the partial sums.  Returns :meth:`rollout_state`.  Synchronous."""
+        from . import _lib
+        c = self._rollout_setup(horizon, obs_cols, priv_cols, act_cols, gamma, lam)
+        _lib.check(_lib.lib().gmr_motion_tracker_set_rollout(self.handle, c["horizon"], c["obs_cols"], c["priv_cols"], c["act_cols"], c["gamma"],
+                                                             c["lam"]))
+        self._rollout = c
+        return self.rollout_state()
+
+    def rollout_state(self) -> Optional[Dict[str, object]]:
+        """The rollout configuration -- ``horizon, obs_cols, priv_cols, act_cols, gamma, lam``, ``num_envs`` and ``shapes``, the shape of
+        each of the caller's six arrays (``priv``: ``None`` without privileged observations) --; ``None`` when the rollout was never set"""
+        c = getattr(self, "_rollout", None)
+        if c is None:
+            return None
+        H, N = c["horizon"], self.num_envs
+        shapes = {"obs": (H, N, c["obs_cols"]), "priv": (H, N, c["priv_cols"]) if c["priv_cols"] else None, "actions": (H, N, c["act_cols"]),
+                  "rewards": (H, N), "dones": (H, N), "time_outs": (H, N)}
+        return dict(c, num_envs=N, shapes=shapes)
+
+    def _need_rollout(self, what: str):
+        c = getattr(self, "_rollout", None)
+        if c is None:
+            raise ValueError(f"{what}: the rollout is not set on this tracker, call set_rollout() first")
+        return c
+
+    _ROLLOUT_DTYPES = {"obs": "float32", "priv": "float32", "actions": "float32", "rewards": "float32", "dones": "uint8", "time_outs": "uint8"}
+
+    def _rollout_io(self, what: str, io, need, device: bool):
+        """the caller's rollout arrays ``io`` (a dict) as a ``gmr_rollout_io_t``: the arrays named in ``need`` must be there -> (table, keep)"""
+        from . import _lib
+        c = self._need_rollout(what)
+        shapes = self.rollout_state()["shapes"]
+        unknown = sorted(set(io) - set(shapes))
+        if unknown:
+            raise ValueError(f"{what}: unknown rollout arrays {unknown} (known: {sorted(shapes)})")
+        table, keep = _lib.RolloutIo(), []
+        for k in _lib.ROLLOUT_IO_FIELDS:
+            a = io.get(k)
+            if a is None:
+                if k in need:
+                    raise ValueError(f"{what}: the rollout array {k!r} is needed")
+                continue
+            if shapes[k] is None:
+                raise ValueError(f"{what}: {k} given, but the rollout was set with priv_cols = 0")
+            dt = self._ROLLOUT_DTYPES[k]
+            if device:
+                p = _dev_ptr(a, k, dt, int(np.prod(shapes[k])))
+                setattr(table, k, p.value)
+                continue
+            if not isinstance(a, np.ndarray) or a.dtype not in ((np.dtype(dt),) if dt == "float32" else (np.dtype(np.uint8), np.dtype(np.bool_))) \
+                    or not a.flags.c_contiguous or not a.flags.writeable:
+                raise TypeError(f"{what}: {k} is written in place: a writeable C-contiguous {dt} array is needed")
+            if a.shape != shapes[k]:
+                raise ValueError(f"{what}: {k}: shape {a.shape}, {shapes[k]} needed")
+            keep.append(a)
+            setattr(table, k, a.ctypes.data)
+        return c, table, keep
+
+    def _record_inputs(self, what: str, c, obs, priv, actions, reward, done, time_outs):
+        if priv is not None and c["priv_cols"] == 0:
+            raise ValueError(f"{what}: priv given, but the rollout was set with priv_cols = 0")
+        return (("obs", obs, "float32", c["obs_cols"], "obs"), ("priv", priv, "float32", c["priv_cols"], "priv"),
+                ("actions", actions, "float32", c["act_cols"], "actions"), ("reward", reward, "float32", 0, "rewards"),
+                ("done", done, "int32", 0, "dones"), ("time_outs", time_outs, "int32", 0, "time_outs"))
+
+    def _check_slot(self, what: str, c, n):
+        if isinstance(n, bool) or int(n) != n or not 0 <= n < c["horizon"]:
+            raise ValueError(f"{what}: slot n = {n!r} outside [0, {c['horizon']})")
+        return int(n)
+
+    def record(self, n: int, io, obs=None, priv=None, actions=None, reward=None, done=None, time_outs=None) -> None:
+        """What the runner's six ``update_data`` calls of a step do (runner.py:107-108, :115-118), host arrays: slot ``n`` of the arrays of
+        ``io`` -- a dict of NumPy arrays in the shapes of :meth:`rollout_state`, written in place -- receives ``obs [N,O]``, ``priv [N,P]``,
+        ``actions [N,A]``, ``reward [N]`` and the ``done`` and ``time_outs`` words (integers or booleans, stored as 0 / 1 bytes).  An input that
+        is ``None`` leaves its slot as it is.  One launch."""
+        from . import _lib
+        c = self._need_rollout("record")
+        n = self._check_slot("record", c, n)
+        inputs = self._record_inputs("record", c, obs, priv, actions, reward, done, time_outs)
+        _, table, keep = self._rollout_io("record", io, {slot for _, a, _, _, slot in inputs if a is not None}, device=False)
+        N, args = self.num_envs, []
+        for k, a, dt, w, _ in inputs:
+            if a is None:
+                args.append(None)
+                continue
+            if dt == "int32":
+                a = np.asarray(a)
+                a = self._per_env_ints(a.astype(np.int32) if a.dtype == np.bool_ else a, k)
+            else:
+                a = np.ascontiguousarray(a, dtype=np.float32)
+                if a.shape != ((N, w) if w else (N,)):
+                    raise ValueError(f"record: {k}: shape {a.shape}, {(N, w) if w else (N,)} needed")
+            keep.append(a)
+            args.append(_lib._ptr(a))
+        _lib.check(_lib.lib().gmr_motion_tracker_record(self.handle, n, C.byref(table), *args))
+
+    def record_dev(self, n: int, io, obs=None, priv=None, actions=None, reward=None, done=None, time_outs=None, stream=None) -> None:
+        """:meth:`record` on device memory, asynchronous on ``stream``: ONE launch.  ``io`` is a dict of device arrays (``obs f32[H*N*O]``,
+        ``priv``, ``actions``, ``rewards f32[H*N]``, ``dones`` / ``time_outs u8[H*N]``); ``done`` and ``time_outs`` are the ``i32[N]`` words
+        :meth:`rewards_dev` writes (``reset``, ``time_outs``).  Every array is a ``_lib.DeviceBuffer``, a raw address or an object with
+        ``data_ptr()``."""
+        from . import _lib
+        c = self._need_rollout("record_dev")
+        n = self._check_slot("record_dev", c, n)
+        inputs = self._record_inputs("record_dev", c, obs, priv, actions, reward, done, time_outs)
+        _, table, _ = self._rollout_io("record_dev", io, {slot for _, a, _, _, slot in inputs if a is not None}, device=True)
+        args = [_dev_ptr(a, k, dt, self.num_envs * max(w, 1)) for k, a, dt, w, _ in inputs]
+        _lib.check(_lib.lib().gmr_motion_tracker_record_dev(self.handle, n, C.byref(table), *args, _lib._s(stream)))
+
+    def advantages(self, io, values, last_values, normalize: bool = True) -> Dict[str, object]:
+        """What a mini-epoch does before the loss (runner.py:135-145, utils.py:33-44), host arrays: the rewards of timed-out steps become
+        the critic's ``values [H,N]`` -- written into ``io["rewards"]`` in place, as the reference mutates its buffer --, then
+        ``advantages`` (``discount_values`` with ``last_values [N]``), ``returns = values + advantages`` and, with ``normalize``,
+        ``normalized`` and ``stats`` -- ``S1, S2, mean, std`` as float64 -- of all ``H N`` advantages (the unbiased deviation: ``H N >= 2``).
+        ``io`` needs ``rewards``, ``dones`` and ``time_outs``."""
+        from . import _lib
+        c = self._need_rollout("advantages")
+        H, N = c["horizon"], self.num_envs
+        if normalize and H * N < 2:
+            raise ValueError(f"advantages: normalize with H * N = {H * N}: the unbiased deviation needs two advantages")
+        _, table, keep = self._rollout_io("advantages", {k: io.get(k) for k in ("rewards", "dones", "time_outs")}, {"rewards", "dones", "time_outs"},
+                                          device=False)
+        v, lv = np.ascontiguousarray(values, dtype=np.float32), np.ascontiguousarray(last_values, dtype=np.float32)
+        if v.shape != (H, N) or lv.shape != (N,):
+            raise ValueError(f"advantages: values {v.shape} and last_values {lv.shape}, {(H, N)} and {(N,)} needed")
+        out = {"advantages": np.empty((H, N), np.float32), "returns": np.empty((H, N), np.float32)}
+        if normalize:
+            out.update(normalized=np.empty((H, N), np.float32), stats=np.empty(4, np.float64))
+        res = _lib.RolloutOut(**{k: a.ctypes.data for k, a in out.items()})
+        _lib.check(_lib.lib().gmr_motion_tracker_advantages(self.handle, C.byref(table), _lib._ptr(v), _lib._ptr(lv), C.byref(res),
+                                                            1 if normalize else 0))
+        return out
+
+    def advantages_dev(self, io, values, last_values, out, normalize: bool = True, stream=None) -> None:
+        """:meth:`advantages` on device memory, asynchronous on ``stream``: the scan, then with ``normalize`` the normalisation (beyond
+        ``64 * 64`` environments a chain of one workgroup between them); no host synchronisation.  ``io`` names ``rewards``, ``dones``,
+        ``time_outs``; ``out`` names whichever of ``advantages``, ``returns``, ``normalized`` (``f32[H*N]``) and ``stats`` (``f64[4]``) are
+        wanted; no output may overlap another one, ``values``, ``last_values`` or an array of ``io`` (nothing checks it).  A torch loop
+        hands ``values.detach()`` and its buffers as they are: anything with ``data_ptr()`` is taken."""
+        from . import _lib
+        c = self._need_rollout("advantages_dev")
+        H, N = c["horizon"], self.num_envs
+        if normalize and H * N < 2:
+            raise ValueError(f"advantages_dev: normalize with H * N = {H * N}: the unbiased deviation needs two advantages")
+        unknown = sorted(set(out) - set(_lib.ROLLOUT_OUT_FIELDS))
+        if unknown:
+            raise TypeError(f"advantages_dev: unknown outputs {unknown}")
+        _, table, _ = self._rollout_io("advantages_dev", {k: io.get(k) for k in ("rewards", "dones", "time_outs")},
+                                       {"rewards", "dones", "time_outs"}, device=True)
+        if values is None or last_values is None:
+            raise ValueError("advantages_dev: values and last_values are needed")
+        res = _lib.RolloutOut()
+        for k, x in out.items():
+            p = _dev_ptr(x, k, "float64" if k == "stats" else "float32", 4 if k == "stats" else H * N)
+            setattr(res, k, None if p is None else p.value)
+        _lib.check(_lib.lib().gmr_motion_tracker_advantages_dev(self.handle, C.byref(table), _dev_ptr(values, "values", "float32", H * N),
+                                                                _dev_ptr(last_values, "last_values", "float32", N), C.byref(res),
+                                                                1 if normalize else 0, _lib._s(stream)))
 
     # ---- the step ---------------------------------------------------------------------------------------------------------
     def _counts(self):

@@ -1345,6 +1345,70 @@ int gmr_motion_tracker_reward_stats(gmr_motion_tracker_t* t, uint64_t* out, int 
  * synchronises.  GMR_ERR_ARG without statistics. */
 int gmr_motion_tracker_reward_state(gmr_motion_tracker_t* t, int32_t* ep_steps, float* ep_sum);
 
+/* ---- N14: tracker rollout (rollout storage, GAE, returns and normalised advantages of a motion tracker) ---- */
+/* What booster_gym/utils/runner.py still does with the outputs of a step after N13: the six indexed assignments into its ExperienceBuffer
+ * per step (runner.py:107-108, :115-118, utils/buffer.py:15-16) and, per mini-epoch, the bootstrap of the timed-out rewards, discount_values
+ * -- a Python loop over the horizon, utils/utils.py:33-44 --, the returns, the mean, the deviation and the normalisation
+ * (runner.py:135-145).  The statement of record is tests/rollout_mirror.py; this is the same in words.
+ * STORAGE: the caller's, as everywhere in the tracker; H = horizon, N environments, O, P, A columns: obs f32[H][N][O], priv f32[H][N][P]
+ * (NULL when P = 0), actions f32[H][N][A], rewards f32[H][N], dones and time_outs u8[H][N].  The tracker owns the configuration and the
+ * scratch of the partial sums alone.
+ * RECORD, slot n in [0, H): slot n of each array receives the N rows handed in; done and time_outs are the int32 words N13 emits and
+ * are stored as bytes, nonzero as 1.  An input that is NULL leaves its slot as it is -- obs before the step and the rest after it, as the
+ * reference orders them, are two calls.  Nothing outside slot n is written.  ONE launch.
+ * ADVANTAGES, from values f32[H][N] and last_values f32[N], float32 with one rounding per operation, e an environment, t a slot:
+ *   1. where time_outs[t][e]: rewards[t][e] = values[t][e], written into the caller's array as the reference mutates its buffer
+ *      (runner.py:135); a second call with other values overwrites it again.  (The launch stores every reward back, the others with the
+ *      bits they had.)
+ *   2. nn = 1 - (dones[t][e] | time_outs[t][e]) (runner.py:138, utils.py:37).
+ *   3. g = (float)gamma, gl = (float)(gamma * lam), the product formed in double (what Python hands torch, utils.py:42-43).
+ *   4. for t = H - 1 .. 0: nv = t == H - 1 ? last_values[e] : values[t + 1][e]; delta = (rewards[t][e] + (g * nn) * nv) - values[t][e];
+ *      advantages[t][e] = last = delta + (gl * nn) * last, from last = +0 (utils.py:36-43).
+ *   5. returns[t][e] = values[t][e] + advantages[t][e] (runner.py:144).
+ *   6. with normalize: S1 = the sum of (double)adv and S2 = the sum of (double)adv * (double)adv (each product exact), both in this
+ *      order: per environment from +0 in the scan's falling t; the environments of a group -- GMR_ROLLOUT_ENVS consecutive ones, an
+ *      absent one counting +0 -- by the balanced tree x[i] = x[i] + x[i + s] for s = 1, 2, 4, .. (i a multiple of 2 s); the groups from
+ *      +0 in rising order.  M = H N; mean = S1 / M; std = sqrt((S2 - S1 * S1 / M) / (M - 1)), torch's unbiased std, in double;
+ *      normalized[t][e] = (adv - (float)mean) / ((float)std + 1e-8f) (runner.py:145).  M < 2 with normalize is GMR_ERR_ARG (the
+ *      reference: NaN).  stats = (S1, S2, mean, std).  Without normalize, normalized and stats stay as they are.
+ * Every output is an address or NULL.  NO OVERLAP: advantages, returns, normalized and stats must not overlap one another, values,
+ * last_values, rewards, dones or time_outs -- rows are requested ahead of the stores, so an output laid over an input changes results
+ * and nothing checks it; the slots of a record call must not overlap its inputs either.
+ * One lane per environment walks t downward, sixteen rows requested ahead of the sixteen it works on.
+ * No floating-point atomics.  TWO launches while there are at most GMR_ROLLOUT_FOLD groups -- every workgroup of the normalisation adds
+ * the partials itself, in the same order --, THREE beyond (a chain of one workgroup between them); ONE without normalize.
+ * The tracker stays SINGLE-STREAM; no call waits for the host. */
+#define GMR_ROLLOUT_ENVS 64
+#define GMR_ROLLOUT_FOLD 64
+typedef struct {            /* the caller's rollout arrays: device pointers (the synchronous twins: host pointers) */
+  float *obs;                         /* [H][N][O]                                                                    */
+  float *priv;                        /* [H][N][P], NULL when P = 0                                                   */
+  float *actions;                     /* [H][N][A]                                                                    */
+  float *rewards;                     /* [H][N]                                                                       */
+  uint8_t *dones, *time_outs;         /* [H][N] 0 or 1                                                                */
+} gmr_rollout_io_t;
+typedef struct {            /* the outputs of an advantages call, each an address or NULL */
+  float *advantages;                  /* [H][N]                                                                       */
+  float *returns;                     /* [H][N]                                                                       */
+  float *normalized;                  /* [H][N], written with normalize                                               */
+  double *stats;                      /* [4] S1, S2, mean, std, written with normalize                                */
+} gmr_rollout_out_t;
+/* The rollout configuration (runner.py:36-42, the horizon and the two discounts of runner.py:141-142): horizon >= 1, obs_cols >= 1,
+ * act_cols >= 1, priv_cols >= 0, gamma and lam finite and in [0, 1].  Allocates the scratch of the partial sums; synchronises the device. */
+int gmr_motion_tracker_set_rollout(gmr_motion_tracker_t* t, int horizon, int obs_cols, int priv_cols, int act_cols, double gamma, double lam);
+/* The six assignments of a step (runner.py:107-108, :115-118): ONE launch.  n outside [0, H) is GMR_ERR_ARG. */
+int gmr_motion_tracker_record_dev(gmr_motion_tracker_t* t, int n, const gmr_rollout_io_t* io, const float* d_obs, const float* d_priv,
+                                  const float* d_actions, const float* d_reward, const int32_t* d_done, const int32_t* d_time_outs,
+                                  void* stream);                                                    /* asynchronous */
+int gmr_motion_tracker_record(gmr_motion_tracker_t* t, int n, const gmr_rollout_io_t* io, const float* obs, const float* priv,
+                              const float* actions, const float* reward, const int32_t* done, const int32_t* time_outs);
+/* The bootstrap, discount_values, the returns and the normalisation of a mini-epoch (runner.py:135-145, utils.py:33-44): at most THREE
+ * launches.  io names rewards, dones and time_outs; normalize is 0 or 1. */
+int gmr_motion_tracker_advantages_dev(gmr_motion_tracker_t* t, const gmr_rollout_io_t* io, const float* d_values, const float* d_last_values,
+                                      const gmr_rollout_out_t* out, int normalize, void* stream);  /* asynchronous */
+int gmr_motion_tracker_advantages(gmr_motion_tracker_t* t, const gmr_rollout_io_t* io, const float* values, const float* last_values,
+                                  const gmr_rollout_out_t* out, int normalize);
+
 /* ---- multi-GPU: one rank per GPU, ONE broadcast, no per-step collective ------------ */
 /* The reference parallelises over files with mp.Pool on one CPU (scripts/smplx_to_robot_dataset.py:241-242); here
  * streams shard over the ranks of one node and the only data that crosses ranks is the packed robot model + task set.
