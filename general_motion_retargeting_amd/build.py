@@ -142,6 +142,17 @@ def build_variant(name: str, defines=(), verbose: bool = False) -> str:
     return _link([_object(s, list(defines), False, verbose) for s in SOURCES], out)
 
 
+def build_ik_variant(name: str, defines=(), sources=("gmr_ik.hip",), force: bool = False) -> str:
+    """libgmrhip_<name>.so with extra -D flags on `sources` ONLY, linked with the default objects of every other source:
+    a switch of the latency kernel (-DGMR_QP_CARRIED_START) costs one compilation, not twenty-two.  A profile build
+    (-DGMR_IK_PROFILE) names gmr_abi.hip as well: its entry point lives there.  Cached on the mtimes of sources and headers."""
+    out = os.path.join(HERE, f"libgmrhip_{name}.so")
+    deps = [os.path.join(CSRC, s) for s in SOURCES + HEADERS] + [os.path.abspath(__file__)]
+    if not force and os.path.exists(out) and all(os.path.getmtime(d) <= os.path.getmtime(out) for d in deps):
+        return out
+    return _link([_object(s, list(defines) if s in sources else [], False, False) for s in SOURCES], out)
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 2 and sys.argv[1] == "--variant":
         print(build_variant(sys.argv[2], sys.argv[3:], verbose=False))

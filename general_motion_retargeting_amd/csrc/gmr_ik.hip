@@ -650,7 +650,7 @@ template <int NW, class LT>
 __device__ __forceinline__ void build_qp_main(const LT& L, double* sm, int stage, const StageTabs& tb,
                                               const short* hinge_body, const short* limited, int* ctl, int& epoch,
                                               double damping, double lm_damping, double limit_gain, int lane,
-                                              int pk_main, Prof& pr) {   // pk_main: task of this lane's pair in this table
+                                              int pk_main, bool first, Prof& pr) {   // pk_main: task of this lane's pair in this table
   double mu = jlog_phase<NW>(L, sm, stage, lm_damping, lane, pr);
   const double diag = damping + mu;
   if (NW == 1) {
@@ -667,7 +667,8 @@ __device__ __forceinline__ void build_qp_main(const LT& L, double* sm, int stage
     PROF_END(pr, PH_HACC);
   } else {
     PROF_BEGIN(pr);
-    if (lane == 0) { int* c = ctl + 2 * (epoch & 1); c[0] = CMD_BUILD; c[1] = stage; (sm + L.o.scal)[0] = diag; }
+    // (bit 1 of the stage word: this is the stage's first solve in its frame -- the helpers switch bound sets with us)
+    if (lane == 0) { int* c = ctl + 2 * (epoch & 1); c[0] = CMD_BUILD; c[1] = stage | (first ? 2 : 0); (sm + L.o.scal)[0] = diag; }
     epoch++;
     __syncthreads();                      // B1: helpers see the command; M / we and the body Jacobians are final
     pairs_from_jbody(L, sm, stage, tb, lane, 64 * NW, nullptr, pk_main);      // (the main wavefront's lanes zero nothing)
@@ -682,12 +683,36 @@ __device__ __forceinline__ void build_qp_main(const LT& L, double* sm, int stage
   }
 }
 
+// Per-stage start of the QP's bound sets.  A frame's first solve of stage s starts from the set that the first solve of
+// stage s ENDED with in the previous frame of this launch, not from the set the other stage's last solve left behind
+// (on coherent motion that set is the closer one: fewer pivoting rounds, the same solution -- a round computes x from
+// (H, c, set) alone).  Every other solve carries on from its predecessor.  A launch starts with nothing remembered.
+// S: TreeState (wave-uniform) or the dense solver's per-lane state.  -DGMR_QP_CARRIED_START: always carry on.
+template <class S>
+struct StageStart {
+#ifndef GMR_QP_CARRIED_START
+  S set0{}, set1{};
+  int have = 0;                           // bit s: stage s has a remembered set
+  __device__ __forceinline__ void restore(int stage, S& cur) const {
+    if ((have >> stage) & 1) cur = stage ? set1 : set0;
+  }
+  __device__ __forceinline__ void remember(int stage, const S& cur) {
+    if (stage) set1 = cur; else set0 = cur;
+    have |= 1 << stage;
+  }
+#else
+  __device__ __forceinline__ void restore(int, S&) const {}
+  __device__ __forceinline__ void remember(int, const S&) {}
+#endif
+};
+
 // helper waves (NW > 1): serve assembly requests until the main wave says EXIT
 template <int NW, int QP, class LT>
 __device__ __forceinline__ void helper_loop(const LT& L, double* sm, const uint32_t* sw, const short* si,
                                             const short* hinge_body, const int* ctl, int wave, int lane,
                                             Prof& hp) {
   TreeState bs = {0ull, 0ull};            // bound sets of the QP (identical in every wavefront)
+  StageStart<TreeState> start;            // ... and the per-stage start, switched at the same solves as the main wavefront's
   const TreeRows<16> rows_s = tree_rows<7, 9, false>(L, si, wave, lane);
   const TreeRows<18> rows_l = tree_rows<8, 10, false>(L, si, wave, lane);
   int pk[2];                              // task of this lane's (task, dof) pair in either table
@@ -695,13 +720,22 @@ __device__ __forceinline__ void helper_loop(const LT& L, double* sm, const uint3
   for (int st = 0; st < 2; st++) pk[st] = (unsigned short)(si + L.o.i_pair_task[st])[min(wave * 64 + lane, L.o.cap.p - 1)] & 15u;
   // helper 1 walks the tree after every solve (CMD_FK): its body lane's constants, read once per launch
   const FkLane fkc = fk_lane(L, sm, si + L.o.i_hop, si + L.o.i_depth, si + L.o.i_body_hinge, lane);
+#ifdef GMR_IK_PROFILE
+  bool after_jbody = false;               // the previous command ended in jbody_phase (CMD_FK, CMD_JBODY)
+#endif
   for (int epoch = 0;; epoch++) {         // command n sits in mailbox slot n & 1 (see the main wavefront)
     PROF_BEGIN(hp);
     __syncthreads();                      // B1 (or the EXIT barrier)
-    PROF_END(hp, PH_PRE);                 // (helper stamps reuse the slots: PRE = idle at B1)
+#ifdef GMR_IK_PROFILE                     // (helper stamps reuse the slots: PRE = idle at B1 behind a QP or at the launch's
+    PROF_END(hp, after_jbody ? PH_INTEG : PH_PRE);   //  start, INTEG = idle at B1 behind jbody_phase)
+#endif
     const int cmd = ctl[2 * (epoch & 1)];
     if (cmd == CMD_EXIT) return;
-    const int stage = ctl[2 * (epoch & 1) + 1];
+#ifdef GMR_IK_PROFILE
+    after_jbody = cmd == CMD_FK || cmd == CMD_JBODY;
+#endif
+    const int word = ctl[2 * (epoch & 1) + 1];      // CMD_BUILD: bit 1 marks the stage's first solve of a frame
+    const int stage = word & 1;
     StageTabs tb = {si + L.o.i_task_body[stage], si + L.o.i_task_human[stage], si + L.o.i_pair_task[stage],
                     si + L.o.i_pair_dof[stage], si + L.o.i_pair_index[stage],
                     reinterpret_cast<const uint2*>(sw + L.w_items[stage])};
@@ -739,9 +773,12 @@ __device__ __forceinline__ void helper_loop(const LT& L, double* sm, const uint3
     PROF_BEGIN(hp);
     __syncthreads();                      // B3
     PROF_END(hp, PH_JLOG);                // wait at B3
+    const bool stage_first = (word & 2) != 0;
+    if (stage_first) start.restore(stage, bs);
     // NW > 1 is only launched for robots that decompose
     if (QP == QP_TREE_SMALL) (void)solve_qp_tree<7, 9, false, true>(L, sm, const_cast<uint32_t*>(sw), si, wave, lane, bs, hp, rows_s);
     else (void)solve_qp_tree<8, 10, false, false>(L, sm, const_cast<uint32_t*>(sw), si, wave, lane, bs, hp, rows_l);
+    if (stage_first) start.remember(stage, bs);
   }
 }
 
@@ -1068,6 +1105,8 @@ __global__ __launch_bounds__(64 * NW, GMR_IK_MIN_WAVES) void ik_streams_kernel(c
   int stat = GMR_STATUS_OK;
   int qp_state = 0;     // this lane's bound state of the previous solve (QP warm start)
   TreeState tree_state = {0ull, 0ull};
+  StageStart<int> qp_start;               // the stage's start of either (StageStart above; the helpers keep their own)
+  StageStart<TreeState> tree_start;
   // (only the instance's own solver's table is live: the others are dead code per template instance)
   const TreeRows<16> rows_s = (NW > 1 && QP == QP_TREE_SMALL) ? tree_rows<7, 9, false>(L, si, 0, lane) : TreeRows<16>{};
   const TreeRows<18> rows_l = (NW > 1 && QP != QP_TREE_SMALL) ? tree_rows<8, 10, false>(L, si, 0, lane) : TreeRows<18>{};
@@ -1126,8 +1165,11 @@ __global__ __launch_bounds__(64 * NW, GMR_IK_MIN_WAVES) void ik_streams_kernel(c
                                                                  : errors_wave<NW>(L, sm, tb.task_body, tb.task_human, K, lane, pr);
         int nsol = 0, num_iter = 0;
         for (;;) {
-          build_qp_main<NW>(L, sm, stage, tb, hinge_body, limited, ctl, epoch, prm[0], prm[1], prm[3], lane, pk_main[stage], pr);
+          const bool first = nsol == 0;
+          build_qp_main<NW>(L, sm, stage, tb, hinge_body, limited, ctl, epoch, prm[0], prm[1], prm[3], lane, pk_main[stage], first, pr);
           PROF_COUNT(pr, PH_NSOLVE);
+          constexpr bool DENSE = NW == 1 && QP != QP_TREE_SMALL;
+          if (first) { if (DENSE) qp_start.restore(stage, qp_state); else tree_start.restore(stage, tree_state); }
           int rc;
           if (NW > 1) {   // the 4-wavefront shape is only launched for robots that decompose (gmr_abi.hip)
             // helpers joined after barrier B3
@@ -1139,6 +1181,7 @@ __global__ __launch_bounds__(64 * NW, GMR_IK_MIN_WAVES) void ik_streams_kernel(c
             rc = solve_qp_regs<NVP, NW>(L, sm, lane, qp_state, pr);
           }
           if (rc != GMR_STATUS_OK) { stat = rc; break; }
+          if (first) { if (DENSE) qp_start.remember(stage, qp_state); else tree_start.remember(stage, tree_state); }
           double next;
           if (NW > 1) {
             integrate_wave<NW, true>(L, sm, prm[5], lane, pr);     // q is final: nobody writes it until the next solve

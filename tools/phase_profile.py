@@ -85,6 +85,13 @@ def main():
               "H share %.0f, wait B3 %.0f, tree-QP %.0f" % (
             hp[:, 0].mean() / nsolve, hp[:, 1].mean() / nsolve, hp[:, 2].mean() / nsolve, hp[:, 4].mean() / nsolve,
             hp[:, 5].mean() / nsolve, hp[:, 6].mean() / nsolve, hp[:, 3].mean() / nsolve, hp[:, 7:14].sum(axis=1).mean() / nsolve))
+        if "INTEG" in PH and hp[:, PH.index("INTEG")].sum() > 0:   # the helpers never integrate: the slot holds the other half of B1
+            ij = PH.index("INTEG")
+            print("  helper wavefront 1: 'idle at B1' above is the wait behind a QP only (%.0f); the wait behind jbody_phase is %.0f cycles/solve"
+                  % (hp[:, 0].mean() / nsolve, hp[:, ij].mean() / nsolve)
+                  + ("; slowest stream %.0f behind jbody_phase / %.0f behind the QP, median stream %.0f / %.0f"
+                     % (hp[k, ij] / pr[k, NSOLVE], hp[k, 0] / pr[k, NSOLVE], hp[med, ij] / pr[med, NSOLVE], hp[med, 0] / pr[med, NSOLVE])
+                     if S <= 512 else ""))
         if S <= 512:
             for name, i in (("slowest", k), ("median", med)):
                 ns_i = pr[i, NSOLVE]
