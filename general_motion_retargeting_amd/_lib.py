@@ -187,6 +187,12 @@ _SIGS = {
     "gmr_motion_tracker_record": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 7),
     "gmr_motion_tracker_advantages_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "gmr_motion_tracker_advantages": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "gmr_motion_tracker_set_loss": (C.c_int, [C.c_void_p] + [C.c_double] * 8),
+    "gmr_motion_tracker_loss_state": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gmr_motion_tracker_log_prob_dev": (C.c_int, [C.c_void_p] * 6),
+    "gmr_motion_tracker_log_prob": (C.c_int, [C.c_void_p] * 5),
+    "gmr_motion_tracker_loss_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "gmr_motion_tracker_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "gmr_comm_create": (C.c_int, [C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),
     "gmr_comm_destroy": (C.c_int, [C.c_void_p]),
     "gmr_comm_rank": (C.c_int, [C.c_void_p]),
@@ -801,6 +807,24 @@ class RolloutIo(C.Structure):
 class RolloutOut(C.Structure):
     """``gmr_rollout_out_t``: the outputs of ``gmr_motion_tracker_advantages[_dev]``, each an address or NULL"""
     _fields_ = [(k, C.c_void_p) for k in ROLLOUT_OUT_FIELDS]
+
+
+# gmr_motion_tracker_set_loss / _loss_state / _log_prob[_dev] / _loss[_dev] (include/gmr_hip.h, "tracker loss")
+LOSS_ROWS, LOSS_FOLD, LOSS_MAX_ACT = 64, 64, 32
+LOSS_IN_FIELDS = ("loc", "logstd", "actions", "old_log_prob", "values", "returns", "advantages", "old_loc", "old_logstd")
+LOSS_OUT_FIELDS = ("grad_loc", "grad_logstd", "grad_values", "log_prob", "terms")
+LOSS_TERMS = ("value_loss", "actor_loss", "bound_loss", "entropy", "loss", "kl_mean", "learning_rate", "clip_fraction")
+LOSS_STATE = ("bound_coef", "entropy_coef", "desired_kl", "learning_rate", "e_clip", "lr_min", "lr_max", "lr_factor")
+
+
+class LossIn(C.Structure):
+    """``gmr_loss_in_t``: the inputs of ``gmr_motion_tracker_loss[_dev]``, each an address (``old_loc``, ``old_logstd``: or NULL)"""
+    _fields_ = [(k, C.c_void_p) for k in LOSS_IN_FIELDS]
+
+
+class LossOut(C.Structure):
+    """``gmr_loss_out_t``: the outputs of ``gmr_motion_tracker_loss[_dev]``, each an address or NULL"""
+    _fields_ = [(k, C.c_void_p) for k in LOSS_OUT_FIELDS]
 
 
 # gmr_motion_tracker_set_preview: the block bits in row order, the frames and the limits (include/gmr_hip.h, "tracker preview")

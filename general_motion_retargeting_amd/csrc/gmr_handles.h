@@ -6,7 +6,8 @@
 // gmr_tracker_proprio.hip its proprioception tables and the six arrays behind them, gmr_tracker_feet.hip its terrain, its feet tables and
 // the two arrays behind them, gmr_tracker_commands.hip its command and disturbance tables and the arrays of the velocity commands,
 // gmr_tracker_episode.hip its reset-state and reward tables, the reset counters and the arrays of the episode statistics,
-// gmr_tracker_rollout.hip its rollout configuration and the partial sums of an advantages call.
+// gmr_tracker_rollout.hip its rollout configuration and the partial sums of an advantages call, gmr_tracker_loss.hip its loss configuration,
+// the partial sums of a loss call and the learning rate.
 #pragma once
 #include <stdint.h>
 
@@ -259,6 +260,15 @@ struct RolloutTables {
   double* part = nullptr;                   // [ceil(N / GMR_ROLLOUT_ENVS)][2] the partial sums of one call
   double* sums = nullptr;                   // [4] S1, S2, mean, std of one call beyond GMR_ROLLOUT_FOLD groups
 };
+// the loss configuration of a tracker and its scratch: device pointers into the loss block
+struct LossTables {
+  int32_t on = 0;                           // 0: the loss was never set
+  int32_t A = 0;                            // columns, the rollout's act_cols when the loss was set
+  int64_t M = 0;                            // rows, the rollout's H * N when the loss was set
+  double bound_coef = 0.0, entropy_coef = 0.0, desired_kl = 0.0, e_clip = 0.0, lr_min = 0.0, lr_max = 0.0, lr_factor = 0.0;   // as given
+  double* part = nullptr;                   // [A + 6][ceil(M / GMR_LOSS_ROWS)] the partial sums of one call
+  double* lr = nullptr;                     // [1] the learning rate
+};
 }  // namespace gmr
 
 struct gmr_motion_tracker {
@@ -302,6 +312,8 @@ struct gmr_motion_tracker {
   gmr::DeviceBlock reward_block; // the arrays of reward_state: one allocation, made by gmr_motion_tracker_set_rewards with statistics
   gmr::RolloutTables rollout;    // rollout.H = 0 until gmr_motion_tracker_set_rollout configures it
   gmr::DeviceBlock rollout_block; // the partial sums of an advantages call: one allocation, made by gmr_motion_tracker_set_rollout
+  gmr::LossTables loss;          // loss.on = 0 until gmr_motion_tracker_set_loss configures it
+  gmr::DeviceBlock loss_block;   // the partial sums of a loss call and the learning rate: one allocation, made by gmr_motion_tracker_set_loss
   std::vector<double> clip_w;    // the clip weights as given at creation (empty: uniform)
   std::mutex mu;                 // the tables, and the whole of every synchronous entry point
 };

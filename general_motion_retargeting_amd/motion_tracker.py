@@ -190,6 +190,7 @@ class MotionTracker:
         self._resets = None           # (R, decimation) once set_reset_states has configured the reset states
         self._rewards = None          # the checked configuration once set_rewards has laid the reward columns out
         self._rollout = None          # the checked configuration once set_rollout has configured the rollout
+        self._loss = None             # the checked configuration, with its rows and columns, once set_loss has configured the loss head
         self._disturb = None          # (kick_every, push_every, push_duration) once set_disturbances has configured kicks and pushes
         if sc is not None or wt is not None:
             self.set_terms(sc, wt)
@@ -2109,6 +2110,160 @@ class MotionTracker:
         _lib.check(_lib.lib().gmr_motion_tracker_advantages_dev(self.handle, C.byref(table), _dev_ptr(values, "values", "float32", H * N),
                                                                 _dev_ptr(last_values, "last_values", "float32", N), C.byref(res),
                                                                 1 if normalize else 0, _lib._s(stream)))
+
+    # ---- the PPO loss head, its gradients and the KL step -------------------------------------------------------
+    def _loss_setup(self, bound_coef, entropy_coef, desired_kl, learning_rate, e_clip, lr_min, lr_max, lr_factor):
+        """the checks of :meth:`set_loss`, all of them before the library is loaded -> a dict of the checked values, rows and columns"""
+        from . import _lib
+        r = self._need_rollout("set_loss")
+        if r["act_cols"] > _lib.LOSS_MAX_ACT:
+            raise ValueError(f"set_loss: act_cols = {r['act_cols']}, at most {_lib.LOSS_MAX_ACT}")
+        c = {k: float(v) for k, v in (("bound_coef", bound_coef), ("entropy_coef", entropy_coef), ("desired_kl", desired_kl),
+                                      ("learning_rate", learning_rate), ("e_clip", e_clip), ("lr_min", lr_min), ("lr_max", lr_max),
+                                      ("lr_factor", lr_factor))}
+        for k, v in c.items():
+            if not np.isfinite(v):
+                raise ValueError(f"set_loss: {k} = {v}: a finite number is needed")
+        for k in ("desired_kl", "learning_rate", "lr_min"):
+            if c[k] <= 0.0:
+                raise ValueError(f"set_loss: {k} = {c[k]}: a number above 0 is needed")
+        if not 0.0 < c["e_clip"] < 1.0:
+            raise ValueError(f"set_loss: e_clip = {c['e_clip']}: a number in (0, 1) is needed")
+        if c["lr_min"] > c["lr_max"]:
+            raise ValueError(f"set_loss: lr_min = {c['lr_min']} above lr_max = {c['lr_max']}")
+        if c["lr_factor"] < 1.0:
+            raise ValueError(f"set_loss: lr_factor = {c['lr_factor']}: at least 1 is needed")
+        return dict(c, rows=r["horizon"] * self.num_envs, cols=r["act_cols"])
+
+    def set_loss(self, bound_coef: float, entropy_coef: float, desired_kl: float, learning_rate: float, e_clip: float = 0.2, lr_min: float = 1e-5,
+                 lr_max: float = 1e-2, lr_factor: float = 1.5) -> Dict[str, object]:
+        """Configures the loss head (runner.py:156-161, :175-178, utils.py:47): the two coefficients, the clip of the surrogate, the rule of
+        the learning rate and the rate it starts from, which the tracker keeps as one double on the device.  Needs :meth:`set_rollout`
+        first -- the rows ``M = horizon * num_envs`` and the columns ``A = act_cols`` are its --, and again after a new ``set_rollout``.
+        Returns :meth:`loss_state`.  Synchronous."""
+        from . import _lib
+        c = self._loss_setup(bound_coef, entropy_coef, desired_kl, learning_rate, e_clip, lr_min, lr_max, lr_factor)
+        _lib.check(_lib.lib().gmr_motion_tracker_set_loss(self.handle, *(c[k] for k in _lib.LOSS_STATE)))
+        self._loss = c
+        return self.loss_state()
+
+    def _need_loss(self, what: str):
+        c = getattr(self, "_loss", None)
+        if self._need_rollout(what) is None or c is None:
+            raise ValueError(f"{what}: the loss is not set on this tracker, call set_loss() first")
+        r = self._rollout
+        if (c["rows"], c["cols"]) != (r["horizon"] * self.num_envs, r["act_cols"]):
+            raise ValueError(f"{what}: the rollout was set again after the loss, call set_loss() again")
+        return c
+
+    def loss_state(self) -> Optional[Dict[str, object]]:
+        """The loss configuration as given, ``rows`` and ``cols``, and ``learning_rate`` as the last ``update_lr`` call left it on the
+        device; ``None`` when the loss was never set.  Synchronises."""
+        from . import _lib
+        c = getattr(self, "_loss", None)
+        if c is None:
+            return None
+        out = np.empty(len(_lib.LOSS_STATE), np.float64)
+        _lib.check(_lib.lib().gmr_motion_tracker_loss_state(self.handle, _lib._ptr(out)))
+        return dict(c, **{k: float(v) for k, v in zip(_lib.LOSS_STATE, out)})
+
+    def _loss_shapes(self, c):
+        M, A = c["rows"], c["cols"]
+        return {"loc": (M, A), "logstd": (A,), "actions": (M, A), "old_log_prob": (M,), "values": (M,), "returns": (M,), "advantages": (M,),
+                "old_loc": (M, A), "old_logstd": (A,), "grad_loc": (M, A), "grad_logstd": (A,), "grad_values": (M,), "log_prob": (M,), "terms": (8,)}
+
+    def _loss_in(self, what: str, c, inputs, update_lr, device: bool):
+        """the inputs of a loss call (a dict) as a ``gmr_loss_in_t`` -> (table, keep)"""
+        from . import _lib
+        unknown = sorted(set(inputs) - set(_lib.LOSS_IN_FIELDS))
+        if unknown:
+            raise TypeError(f"{what}: unknown inputs {unknown} (known: {list(_lib.LOSS_IN_FIELDS)})")
+        old = [inputs.get(k) is not None for k in ("old_loc", "old_logstd")]
+        if old[0] != old[1]:
+            raise ValueError(f"{what}: old_loc and old_logstd are given together, or neither")
+        if update_lr and not old[0]:
+            raise ValueError(f"{what}: update_lr without old_loc and old_logstd: there is no KL to drive the learning rate")
+        shapes, table, keep = self._loss_shapes(c), _lib.LossIn(), []
+        for k in _lib.LOSS_IN_FIELDS:
+            a = inputs.get(k)
+            if a is None:
+                if k not in ("old_loc", "old_logstd"):
+                    raise ValueError(f"{what}: the input {k!r} is needed")
+                continue
+            if device:
+                setattr(table, k, _dev_ptr(a, k, "float32", int(np.prod(shapes[k]))).value)
+                continue
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.size != int(np.prod(shapes[k])) or a.shape not in (shapes[k], self._loss_rollout_shape(shapes[k])):
+                raise ValueError(f"{what}: {k}: shape {a.shape}, {shapes[k]} needed")
+            keep.append(a)
+            setattr(table, k, a.ctypes.data)
+        return table, keep
+
+    def _loss_rollout_shape(self, shape):
+        """``[M, ...]`` as the rollout lays it out: ``[H, N, ...]``"""
+        H, N = self._rollout["horizon"], self.num_envs
+        return (H, N) + tuple(shape[1:]) if shape[0] == H * N else shape
+
+    def log_prob(self, loc, logstd, actions) -> np.ndarray:
+        """``old_actions_log_prob`` (runner.py:123-125), host arrays: ``loc`` and ``actions`` ``[M, A]`` (or ``[H, N, A]``), ``logstd [A]``
+        -> ``f32[M]``, the log-probability of every row's action under ``Normal(loc, exp(logstd))``, summed over the columns."""
+        from . import _lib
+        c = self._need_loss("log_prob")
+        shapes, args = self._loss_shapes(c), []
+        for k, a in (("loc", loc), ("logstd", logstd), ("actions", actions)):
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.size != int(np.prod(shapes[k])) or a.shape not in (shapes[k], self._loss_rollout_shape(shapes[k])):
+                raise ValueError(f"log_prob: {k}: shape {a.shape}, {shapes[k]} needed")
+            args.append(a)
+        out = np.empty(c["rows"], np.float32)
+        _lib.check(_lib.lib().gmr_motion_tracker_log_prob(self.handle, *(_lib._ptr(a) for a in args), _lib._ptr(out)))
+        return out
+
+    def log_prob_dev(self, loc, logstd, actions, out, stream=None) -> None:
+        """:meth:`log_prob` on device memory, asynchronous on ``stream``: ONE launch.  ``loc`` and ``actions`` ``f32[M*A]``, ``logstd
+        f32[A]``, ``out f32[M]``; each a ``_lib.DeviceBuffer``, a raw address or an object with ``data_ptr()``."""
+        from . import _lib
+        c = self._need_loss("log_prob_dev")
+        M, A = c["rows"], c["cols"]
+        args = [_dev_ptr(a, k, "float32", n) for k, a, n in (("loc", loc, M * A), ("logstd", logstd, A), ("actions", actions, M * A), ("out", out, M))]
+        if any(a is None for a in args):
+            raise ValueError("log_prob_dev: loc, logstd, actions and out are needed")
+        _lib.check(_lib.lib().gmr_motion_tracker_log_prob_dev(self.handle, *args, _lib._s(stream)))
+
+    def loss(self, inputs, update_lr: bool = False) -> Dict[str, object]:
+        """The loss head of a mini-epoch (runner.py:146-180 without the networks and the optimiser), host arrays.  ``inputs`` is a dict of
+        ``loc [M, A]``, ``logstd [A]``, ``actions [M, A]``, ``old_log_prob``, ``values``, ``returns``, ``advantages`` (the normalised ones)
+        ``[M]`` and, for the KL, ``old_loc [M, A]`` with ``old_logstd [A]``.  Returns ``grad_loc [M, A]``, ``grad_logstd [A]``, ``grad_values
+        [M]`` -- the gradient of the loss with respect to the networks' outputs --, ``log_prob [M]`` and ``terms`` ``f64[8]``: value_loss,
+        actor_loss, bound_loss, entropy, loss, kl_mean, the learning rate after this call, clip_fraction.  With ``update_lr`` the KL steps
+        the learning rate the tracker keeps."""
+        from . import _lib
+        c = self._need_loss("loss")
+        table, keep = self._loss_in("loss", c, inputs, update_lr, device=False)
+        shapes = self._loss_shapes(c)
+        out = {k: np.empty(shapes[k], np.float64 if k == "terms" else np.float32) for k in _lib.LOSS_OUT_FIELDS}
+        res = _lib.LossOut(**{k: a.ctypes.data for k, a in out.items()})
+        _lib.check(_lib.lib().gmr_motion_tracker_loss(self.handle, C.byref(table), C.byref(res), 1 if update_lr else 0))
+        return out
+
+    def loss_dev(self, inputs, out, update_lr: bool = False, stream=None) -> None:
+        """:meth:`loss` on device memory, asynchronous on ``stream``: the pass over the rows and, when ``terms``, ``grad_logstd`` or
+        ``update_lr`` are wanted, the fold -- at most TWO launches, no host synchronisation.  ``out`` names whichever of ``grad_loc``
+        (``f32[M*A]``), ``grad_logstd`` (``f32[A]``), ``grad_values``, ``log_prob`` (``f32[M]``) and ``terms`` (``f64[8]``) are wanted; no
+        output may overlap another one or an input (nothing checks it).  A torch loop hands ``loc.detach()``, ``model.logstd.detach()``
+        and ``values.detach()`` as they are: anything with ``data_ptr()`` is taken."""
+        from . import _lib
+        c = self._need_loss("loss_dev")
+        unknown = sorted(set(out) - set(_lib.LOSS_OUT_FIELDS))
+        if unknown:
+            raise TypeError(f"loss_dev: unknown outputs {unknown}")
+        table, _ = self._loss_in("loss_dev", c, inputs, update_lr, device=True)
+        shapes, res = self._loss_shapes(c), _lib.LossOut()
+        for k, x in out.items():
+            p = _dev_ptr(x, k, "float64" if k == "terms" else "float32", int(np.prod(shapes[k])))
+            setattr(res, k, None if p is None else p.value)
+        _lib.check(_lib.lib().gmr_motion_tracker_loss_dev(self.handle, C.byref(table), C.byref(res), 1 if update_lr else 0, _lib._s(stream)))
 
     # ---- the step ---------------------------------------------------------------------------------------------------------
     def _counts(self):

@@ -1409,6 +1409,80 @@ int gmr_motion_tracker_advantages_dev(gmr_motion_tracker_t* t, const gmr_rollout
 int gmr_motion_tracker_advantages(gmr_motion_tracker_t* t, const gmr_rollout_io_t* io, const float* values, const float* last_values,
                                   const gmr_rollout_out_t* out, int normalize);
 
+/* ---- N15: tracker loss (the PPO loss head of a motion tracker, its gradients and the KL step) ---- */
+/* What booster_gym/utils/runner.py still does between the outputs of its two networks and its optimiser after N14: old_actions_log_prob
+ * (runner.py:123-125), the value, surrogate, bound and entropy terms and their sum (runner.py:146-161, utils/utils.py:47-52), the backward
+ * pass of that sum down to loc, logstd and values (what runner.py:163 delivers at the outputs of the networks), the KL between the old
+ * and the new policy (runner.py:168-174) and the learning-rate rule (runner.py:175-178).  The statement of record is tests/ppo_mirror.py;
+ * this is the same in words.  M = H N rows and A = act_cols columns, both from gmr_motion_tracker_set_rollout.
+ * Float32 with one rounding per operation, the sums over rows float64.  Per column a: scale = expf(logstd[a]), var = scale * scale,
+ * log_scale = logf(scale) (the reference takes the log of the exp) -- these exp and log, and the log of the KL, with ONE rounding: formed
+ * in double and rounded once --; C = (float)log(sqrt(2 pi)), E0 = (float)(0.5 + 0.5 log(2 pi)),
+ * lo = (float)(1 - e_clip), hi = (float)(1 + e_clip).
+ * LOG_PROB: d = actions - loc; per element ((-(d * d)) / (2 * var) - log_scale) - C; the row value lp is the sum over rising a from the
+ * first element.
+ * LOSS, per row: ratio = expf(lp - old_log_prob); s = (-adv) * ratio; sc = (-adv) * min(max(ratio, lo), hi); surr = max(s, sc); the weight
+ * w is what torch's backward of max and clamp amounts to: 1 where lo <= ratio <= hi (sc is s bit for bit there: a tie with both halves
+ * alive); outside, 1 where s > sc, 0.5 where s == sc, 0 where s < sc; glp = (w * s) / (float)M.
+ *   grad_values = (2 * (values - returns)) / (float)M
+ *   grad_loc    = glp * (d / var) + cb * (2 * max(loc - 1, 0) + 2 * min(loc + 1, 0)), cb = (float)(bound_coef / (M A))
+ *   grad_logstd[a] = (float)(S_a + entropy_coef), S_a the sum over the rows of (double)glp * (double)((d * d) / var - 1)
+ *   terms = value_loss = sum((values - returns)^2) / M, actor_loss = sum(surr) / M, bound_loss = sum(max(loc - 1, 0)^2) / (M A) +
+ *           sum(min(loc + 1, 0)^2) / (M A) (the squares float32, added within a row from +0 over rising a), entropy = the sum from +0 over
+ *           rising a of (double)(E0 + log_scale[a]), loss = ((value_loss + actor_loss) + bound_coef * bound_loss) + entropy_coef * entropy,
+ *           kl_mean (0 without the old policy), the learning rate after this call, clip_fraction = the share of rows with w = 0
+ *   KL, per element (logf(scale / old_scale) + (0.5 * (old_var + (loc - old_loc)^2)) / var) - 0.5, the row value the float32 sum over
+ *           rising a from the first element, kl_mean = sum / M
+ *   LEARNING RATE, with update_lr, in double: kl_mean > 2 desired_kl: lr = max(lr_min, lr / lr_factor); else kl_mean < desired_kl / 2:
+ *           lr = min(lr_max, lr * lr_factor).  The comparison is made in double; the reference compares a float32 kl_mean, so the two can
+ *           differ only when kl_mean lies within float32 rounding of a threshold.  The rate stays on the device for the next call.
+ * EVERY SUM OVER ROWS is float64 in one association, a function of M alone (ppo_mirror.sums): the rows of a group -- GMR_LOSS_ROWS
+ * consecutive ones, an absent one counting +0 -- by the balanced tree x[i] = x[i] + x[i + s] for s = 1, 2, 4, .. (i a multiple of 2 s);
+ * the groups of a block -- GMR_LOSS_FOLD consecutive ones, an absent one counting +0 -- by the same tree; the blocks from +0 in rising
+ * order.  No floating-point atomics.  Inputs are taken as finite.
+ * NO OVERLAP: no output may overlap another one or an input; nothing checks it.
+ * ONE launch for the log-probability; at most TWO for the loss (the fold writes grad_logstd and terms and steps the rate; there is no
+ * third).  Everything is enqueued on the caller's stream; no call waits for the host.  The tracker stays SINGLE-STREAM. */
+#define GMR_LOSS_ROWS 64
+#define GMR_LOSS_FOLD 64
+#define GMR_LOSS_MAX_ACT 32
+typedef struct {            /* the inputs of a loss call: device pointers (the synchronous twin: host pointers) */
+  const float *loc;                   /* [M][A] the actor's output                                                    */
+  const float *logstd;                /* [A]                                                                          */
+  const float *actions;               /* [M][A] the rollout array                                                     */
+  const float *old_log_prob;          /* [M]                                                                          */
+  const float *values;                /* [M] the critic's output                                                      */
+  const float *returns;               /* [M]                                                                          */
+  const float *advantages;            /* [M] the normalised ones                                                      */
+  const float *old_loc;               /* [M][A], or NULL together with old_logstd: no KL                              */
+  const float *old_logstd;            /* [A]                                                                          */
+} gmr_loss_in_t;
+typedef struct {            /* the outputs of a loss call, each an address or NULL */
+  float *grad_loc;                    /* [M][A]                                                                       */
+  float *grad_logstd;                 /* [A]                                                                          */
+  float *grad_values;                 /* [M]                                                                          */
+  float *log_prob;                    /* [M]                                                                          */
+  double *terms;                      /* [8] value_loss, actor_loss, bound_loss, entropy, loss, kl_mean, lr, clip_fraction */
+} gmr_loss_out_t;
+/* The coefficients of runner.py:156-161, the clip of utils.py:47, the rule of runner.py:175-178 and its starting rate: bound_coef and
+ * entropy_coef finite, desired_kl and learning_rate finite and above 0, e_clip in (0, 1), 0 < lr_min <= lr_max, lr_factor >= 1.  Needs
+ * gmr_motion_tracker_set_rollout first (and again after the rollout is set again); act_cols above GMR_LOSS_MAX_ACT is GMR_ERR_ARG.
+ * Allocates the partial sums and the learning rate, one double on the device; synchronises the device. */
+int gmr_motion_tracker_set_loss(gmr_motion_tracker_t* t, double bound_coef, double entropy_coef, double desired_kl, double learning_rate,
+                                double e_clip, double lr_min, double lr_max, double lr_factor);
+/* out f64[8]: bound_coef, entropy_coef, desired_kl, the learning rate as the last update_lr of runner.py:175-178 left it, e_clip, lr_min,
+ * lr_max, lr_factor; synchronises the device. */
+int gmr_motion_tracker_loss_state(gmr_motion_tracker_t* t, double* out);
+/* old_actions_log_prob (runner.py:123-125): out f32[M].  ONE launch. */
+int gmr_motion_tracker_log_prob_dev(gmr_motion_tracker_t* t, const float* d_loc, const float* d_logstd, const float* d_actions, float* d_out,
+                                    void* stream);                                                  /* asynchronous */
+int gmr_motion_tracker_log_prob(gmr_motion_tracker_t* t, const float* loc, const float* logstd, const float* actions, float* out);
+/* The loss head (runner.py:146-180 without the networks and the optimiser): at most TWO launches.  update_lr is 0 or 1; 1 without
+ * old_loc and old_logstd is GMR_ERR_ARG. */
+int gmr_motion_tracker_loss_dev(gmr_motion_tracker_t* t, const gmr_loss_in_t* in, const gmr_loss_out_t* out, int update_lr,
+                                void* stream);                                                      /* asynchronous */
+int gmr_motion_tracker_loss(gmr_motion_tracker_t* t, const gmr_loss_in_t* in, const gmr_loss_out_t* out, int update_lr);
+
 /* ---- multi-GPU: one rank per GPU, ONE broadcast, no per-step collective ------------ */
 /* The reference parallelises over files with mp.Pool on one CPU (scripts/smplx_to_robot_dataset.py:241-242); here
  * streams shard over the ranks of one node and the only data that crosses ranks is the packed robot model + task set.
