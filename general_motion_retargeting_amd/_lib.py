@@ -4,6 +4,7 @@ from __future__ import annotations
 
 import ctypes as C
 import importlib.util
+import math
 import os
 import sys
 
@@ -602,39 +603,183 @@ class Solver:
             pass
 
 
-BODY_STATE_FIELDS = ("root_pos", "root_rot", "root_vel", "root_ang_vel", "dof_pos", "dof_vel", "body_pos", "body_rot", "body_vel",
-                     "body_ang_vel", "status")
+# ---- array tables --------------------------------------------------------------------------------------------------------------------
+# Every struct of array addresses has ONE table beside it.  A row ``(name, dtype, shape)`` is an array: its full shape, each axis a number
+# or the name of a dimension the caller resolves -- "N" environments (or queries), "n" listed entries, "R" robot dofs, "extra_cols" and
+# "obs_cols" of the proprioception, "nb" simulator bodies, "nsel" selected bodies, "C" reward columns, "E" caller columns, "H" / "O" / "P" /
+# "A" of the rollout, "M" = H N rows of the loss.  A row ``(name, ctype)`` is a plain value among the addresses.  The struct's ``_fields_``
+# and the ``*_FIELDS`` tuple are derived; :func:`resolve` / :func:`resolved` turn a table into shapes and :func:`host_inputs`, :func:`host_outputs` and
+# :func:`device_struct` fill the struct from them.  A new block adds its tables here and nothing else.
+def _fields(table):
+    return [(row[0], C.c_void_p if len(row) == 3 else row[1]) for row in table]
+
+
+def _arrays(table):
+    return tuple(row[0] for row in table if len(row) == 3)
+
+
+def resolve(table, **dims):
+    """``{name: (dtype, shape, element count)}`` of the arrays of ``table`` under ``dims``"""
+    out = {}
+    for row in table:
+        if len(row) == 3:
+            shape = tuple(dims[s] if isinstance(s, str) else s for s in row[2])
+            out[row[0]] = (row[1], shape, math.prod(shape))
+    return out
+
+
+_RESOLVED = {}
+
+
+def resolved(table, **dims):
+    """:func:`resolve`, done once per table and set of dimensions (always named in the same order): what a call in a training loop pays is
+    a dictionary look-up"""
+    key = (id(table), *dims.values())
+    rows = _RESOLVED.get(key)
+    if rows is None:
+        rows = _RESOLVED[key] = resolve(table, **dims)
+    return rows
+
+
+def widths(table, **dims):
+    """``{name: elements per environment}`` of the arrays of ``table``"""
+    return {k: count for k, (_, _, count) in resolve(table, N=1, n=1, **dims).items()}
+
+
+def _unknown(what, noun, given, rows):
+    unknown = sorted(set(given) - set(rows))
+    if unknown:
+        raise TypeError(f"{what}: unknown {noun} {unknown}")
+
+
+def host_inputs(struct, rows, arrays, what="", required=(), unknown=None, prefix=""):
+    """The caller's host ``arrays`` (``{name: array or None}``) as a ``struct`` of addresses -> ``(struct, arrays to keep alive)``.  Each
+    array is made contiguous in the dtype of its row of ``rows`` (:func:`resolve`) and its shape is checked; an ``int32`` row takes
+    integers only; the absence of a name in ``required`` is refused, and with ``unknown`` (a noun) so is a name outside ``rows``."""
+    if unknown:
+        _unknown(what, unknown, arrays, rows)
+    st, keep = struct() if isinstance(struct, type) else struct, []          # (an instance: go on filling it)
+    for k, a in arrays.items():
+        if a is None:
+            if k in required:
+                raise ValueError(f"{what}: {k} is needed")
+            continue
+        dtype, shape, _ = rows[k]
+        if dtype == "int32":
+            a = np.asarray(a)
+            if not np.issubdtype(a.dtype, np.integer):
+                raise TypeError(f"{prefix}{k}: integers needed, got {a.dtype}")
+        a = np.ascontiguousarray(a, dtype=dtype)
+        if a.shape != shape:
+            raise ValueError(f"{prefix}{k}: shape {a.shape}, {shape} needed")
+        keep.append(a)
+        setattr(st, k, a.ctypes.data)
+    return st, keep
+
+
+def host_outputs(struct, rows, skip=()):
+    """Freshly allocated arrays for the rows of ``rows`` that are not in ``skip`` -> ``(struct of their addresses, {name: array})``"""
+    out = {k: np.empty(shape, dtype) for k, (dtype, shape, _) in rows.items() if k not in skip}
+    return struct(**{k: a.ctypes.data for k, a in out.items()}), out
+
+
+def device_struct(struct, rows, arrays, what="", required=(), unknown="outputs"):
+    """:func:`host_inputs` for device memory: every value of ``arrays`` a :class:`DeviceBuffer`, a raw address or an object with
+    ``data_ptr()``, taken through :func:`_dev_ptr` with the element count of its row.  A name outside ``rows`` is refused."""
+    if not rows.keys() >= arrays.keys():
+        _unknown(what, unknown, arrays, rows)
+    st = struct()
+    for k, x in arrays.items():
+        if x is None:
+            if k in required:
+                raise ValueError(f"{what}: {k} is needed")
+            continue
+        dtype, _, count = rows[k]
+        setattr(st, k, _dev_ptr(x, k, dtype, count).value)
+    return st
+
+
+def _dev_ptr(x, what: str, dtype: str, count: int):
+    """Device address of an array of a ``*_dev`` call: None, a :class:`DeviceBuffer`, a raw address (``int`` / ``c_void_p``) or an
+    object with ``data_ptr()``, whose dtype, contiguity and size are checked when it tells them."""
+    if x is None:
+        return None
+    if isinstance(x, DeviceBuffer):
+        need = count * np.dtype(dtype).itemsize
+        if x.nbytes < need:
+            raise ValueError(f"{what}: buffer of {x.nbytes} bytes, {need} needed")
+        return x.ptr
+    if isinstance(x, C.c_void_p):
+        return x
+    if isinstance(x, (int, np.integer)):
+        return C.c_void_p(int(x))
+    if hasattr(x, "data_ptr"):
+        if isinstance(x, np.ndarray) or getattr(getattr(x, "device", None), "type", "cuda") == "cpu":
+            raise ValueError(f"{what}: host memory handed to a device entry point")
+        if hasattr(x, "dtype") and str(x.dtype).split(".")[-1] != dtype:
+            raise ValueError(f"{what}: dtype {x.dtype}, {dtype} needed")
+        if hasattr(x, "is_contiguous") and not x.is_contiguous():
+            raise ValueError(f"{what}: not contiguous")
+        if hasattr(x, "numel") and x.numel() < count:
+            raise ValueError(f"{what}: {x.numel()} elements, {count} needed")
+        return C.c_void_p(int(x.data_ptr()))
+    raise TypeError(f"{what}: cannot take a device address from {type(x).__name__}")
+
+
+_F, _I = "float32", "int32"
 FK_MAX_BODIES = 64
+BODY_STATE = (("root_pos", _F, ("N", 3)), ("root_rot", _F, ("N", 4)), ("root_vel", _F, ("N", 3)), ("root_ang_vel", _F, ("N", 3)),
+              ("dof_pos", _F, ("N", "R")), ("dof_vel", _F, ("N", "R")), ("body_pos", _F, ("N", "nsel", 3)), ("body_rot", _F, ("N", "nsel", 4)),
+              ("body_vel", _F, ("N", "nsel", 3)), ("body_ang_vel", _F, ("N", "nsel", 3)), ("status", _I, ("N",)))
+BODY_STATE_FIELDS = _arrays(BODY_STATE)
 
 
 class BodyStateOut(C.Structure):
     """``gmr_body_state_out_t``: the outputs of ``gmr_motion_body_state[_dev]``, each an address or NULL"""
-    _fields_ = [(k, C.c_void_p) for k in BODY_STATE_FIELDS]
+    _fields_ = _fields(BODY_STATE)
 
 
-TRACKER_OUT_FIELDS = ("ref_root_pos", "ref_root_rot", "ref_root_vel", "ref_root_ang_vel", "ref_dof_pos", "ref_dof_vel", "err", "term", "total",
-                      "status", "finished")
-TRACKER_SIM_FIELDS = ("base_pos", "base_quat", "base_lin_vel", "base_ang_vel", "dof_pos", "dof_vel")
 TRACKER_MAX_DOF = 64
 TRACKER_TERMS = 6
+TRACKER_OUT = (("ref_root_pos", _F, ("N", 3)), ("ref_root_rot", _F, ("N", 4)), ("ref_root_vel", _F, ("N", 3)), ("ref_root_ang_vel", _F, ("N", 3)),
+               ("ref_dof_pos", _F, ("N", "R")), ("ref_dof_vel", _F, ("N", "R")), ("err", _F, ("N", 6)), ("term", _F, ("N", 6)), ("total", _F, ("N",)),
+               ("status", _I, ("N",)), ("finished", _I, ("N",)))
+TRACKER_SIM = (("base_pos", _F, ("N", 3)), ("base_quat", _F, ("N", 4)), ("base_lin_vel", _F, ("N", 3)), ("base_ang_vel", _F, ("N", 3)),
+               ("dof_pos", _F, ("N", "R")), ("dof_vel", _F, ("N", "R")))
+TRACKER_OUT_FIELDS, TRACKER_SIM_FIELDS = _arrays(TRACKER_OUT), _arrays(TRACKER_SIM)
 
 
 class TrackerOut(C.Structure):
     """``gmr_tracker_out_t``: the outputs of ``gmr_motion_tracker_step[_dev]``, each an address or NULL"""
-    _fields_ = [(k, C.c_void_p) for k in TRACKER_OUT_FIELDS]
+    _fields_ = _fields(TRACKER_OUT)
 
 
 class TrackerSim(C.Structure):
     """``gmr_tracker_sim_t``: the simulator state of ``gmr_motion_tracker_step[_dev]``, each an address or NULL"""
-    _fields_ = [(k, C.c_void_p) for k in TRACKER_SIM_FIELDS]
+    _fields_ = _fields(TRACKER_SIM)
 
 
-TRACKER_LINKS_OUT_FIELDS = ("ref_body_pos", "ref_body_rot", "ref_body_vel", "ref_body_ang_vel", "link_err", "link_term", "max_dist", "fail")
-TRACKER_LINKS_SIM_FIELDS = ("body_pos", "body_rot", "body_vel", "body_ang_vel")
 TRACKER_LINK_TERMS = 4
 TRACKER_FRAME_WORLD, TRACKER_FRAME_HEADING = 0, 1
 TRACKER_NO_ADVANCE = 1
 ANCHOR_YAW, ANCHOR_Z = 1, 2          # gmr_motion_tracker_anchor_to_root[_dev] flags (include/gmr_hip.h, "tracker anchors")
+TRACKER_LINKS_OUT = (("ref_body_pos", _F, ("N", "nsel", 3)), ("ref_body_rot", _F, ("N", "nsel", 4)), ("ref_body_vel", _F, ("N", "nsel", 3)),
+                     ("ref_body_ang_vel", _F, ("N", "nsel", 3)), ("link_err", _F, ("N", 4)), ("link_term", _F, ("N", 4)), ("max_dist", _F, ("N",)),
+                     ("fail", _I, ("N",)))
+# the separate arrays hold the selected bodies ("nsel"; for the feet: every body of the simulator); a packed tensor goes in by offsets and strides
+TRACKER_LINKS_SIM = (("body_pos", _F, ("N", "nsel", 3)), ("body_rot", _F, ("N", "nsel", 4)), ("body_vel", _F, ("N", "nsel", 3)),
+                     ("body_ang_vel", _F, ("N", "nsel", 3)), ("env_stride", C.c_int64), ("body_stride", C.c_int64))
+TRACKER_LINKS_OUT_FIELDS, TRACKER_LINKS_SIM_FIELDS = _arrays(TRACKER_LINKS_OUT), _arrays(TRACKER_LINKS_SIM)
+
+
+class TrackerLinksOut(C.Structure):
+    """``gmr_tracker_links_out_t``: the link outputs of ``gmr_motion_tracker_step_links[_dev]``, each an address or NULL"""
+    _fields_ = _fields(TRACKER_LINKS_OUT)
+
+
+class TrackerLinksSim(C.Structure):
+    """``gmr_tracker_links_sim_t``: the simulator's rigid-body state, four addresses (or NULL) and the two strides in floats"""
+    _fields_ = _fields(TRACKER_LINKS_SIM)
 
 
 CONTROL_MAX_DECIMATION = 64           # gmr_motion_tracker_set_control (include/gmr_hip.h, "tracker control")
@@ -647,7 +792,8 @@ class TrackerActuator(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in TRACKER_ACTUATOR_FIELDS] + [("per_env", C.c_int32)]
 
 
-# gmr_motion_tracker_set_proprio / _proprio[_dev] (include/gmr_hip.h, "tracker proprioception")
+# gmr_motion_tracker_set_proprio / _proprio[_dev] (include/gmr_hip.h, "tracker proprioception"): the penalties in column order (t1.py:622-625,
+# :631-694) and the blocks that take sensor noise
 PROPRIO_TERMS = ("lin_vel_z", "ang_vel_xy", "orientation", "torques", "dof_vel", "dof_acc", "root_acc", "action_rate", "dof_pos_limits",
                  "dof_vel_limits", "torque_limits", "torque_tiredness", "power", "base_height")
 PROPRIO_MAX_EXTRA = 16
@@ -655,9 +801,12 @@ PROPRIO_NOISE_BLOCKS = ("gravity", "ang_vel", "dof_pos", "dof_vel", "lin_vel", "
 NOISE_DISTRIBUTIONS = {"none": 0, "gaussian": 1, "uniform": 2}
 NOISE_OPERATIONS = {"additive": 0, "scaling": 1}
 PROPRIO_CONFIG_TABLES = ("default_dof_pos", "dof_pos_limits", "dof_vel_limits", "torque_limits", "scales")
-PROPRIO_IN_FIELDS = ("root_states", "dof_pos", "dof_vel", "actions", "mean_torques", "extra", "ground", "episode_steps")
-PROPRIO_OUT_FIELDS = ("base_lin_vel", "base_ang_vel", "projected_gravity", "filtered_lin_vel", "filtered_ang_vel", "obs", "priv", "term", "total",
-                      "done")
+PROPRIO_IN = (("root_states", _F, ("N", 13)), ("dof_pos", _F, ("N", "R")), ("dof_vel", _F, ("N", "R")), ("actions", _F, ("N", "R")),
+              ("mean_torques", _F, ("N", "R")), ("extra", _F, ("N", "extra_cols")), ("ground", _F, ("N",)), ("episode_steps", _I, ("N",)))
+PROPRIO_OUT = (("base_lin_vel", _F, ("N", 3)), ("base_ang_vel", _F, ("N", 3)), ("projected_gravity", _F, ("N", 3)), ("filtered_lin_vel", _F, ("N", 3)),
+               ("filtered_ang_vel", _F, ("N", 3)), ("obs", _F, ("N", "obs_cols")), ("priv", _F, ("N", 4)), ("term", _F, ("N", len(PROPRIO_TERMS))),
+               ("total", _F, ("N",)), ("done", _I, ("N",)))
+PROPRIO_IN_FIELDS, PROPRIO_OUT_FIELDS = _arrays(PROPRIO_IN), _arrays(PROPRIO_OUT)
 
 
 class ProprioNoise(C.Structure):
@@ -676,21 +825,24 @@ class ProprioConfig(C.Structure):
 
 class ProprioIn(C.Structure):
     """``gmr_proprio_in_t``: the inputs of ``gmr_motion_tracker_proprio[_dev]``, each an address or NULL"""
-    _fields_ = [(k, C.c_void_p) for k in PROPRIO_IN_FIELDS]
+    _fields_ = _fields(PROPRIO_IN)
 
 
 class ProprioOut(C.Structure):
     """``gmr_proprio_out_t``: the outputs of ``gmr_motion_tracker_proprio[_dev]``, each an address or NULL"""
-    _fields_ = [(k, C.c_void_p) for k in PROPRIO_OUT_FIELDS]
+    _fields_ = _fields(PROPRIO_OUT)
 
 
-# gmr_motion_tracker_set_terrain / _terrain_heights[_dev] / _set_feet / _feet[_dev] (include/gmr_hip.h, "tracker feet")
+# gmr_motion_tracker_set_terrain / _terrain_heights[_dev] / _set_feet / _feet[_dev] (include/gmr_hip.h, "tracker feet"): the terms in column
+# order (t1.py:627-629, :696-730); FEET_DONE_CONTACT is the bit of ``done``, OR-able with the bits 0 to 2 of the proprioception's
 FEET_TERMS = ("collision", "feet_slip", "feet_vel_z", "feet_roll", "feet_yaw_diff", "feet_yaw_mean", "feet_distance", "feet_swing")
 FEET_MAX_EDGES, FEET_MAX_BODIES = 8, 64
 FEET_DONE_CONTACT = 8
 FEET_CONFIG_TABLES = ("edge_pos", "termination_body", "penalized_body", "scales")
-FEET_IN_FIELDS = ("contact_forces", "root_states", "episode_steps", "gait_frequency")
-FEET_OUT_FIELDS = ("feet_pos", "feet_roll", "feet_yaw", "feet_contact", "ground", "gait", "term", "total", "done")
+FEET_IN = (("contact_forces", _F, ("N", "nb", 3)), ("root_states", _F, ("N", 13)), ("episode_steps", _I, ("N",)), ("gait_frequency", _F, ("N",)))
+FEET_OUT = (("feet_pos", _F, ("N", 2, 3)), ("feet_roll", _F, ("N", 2)), ("feet_yaw", _F, ("N", 2)), ("feet_contact", _I, ("N", 2)), ("ground", _F, ("N",)),
+            ("gait", _F, ("N", 2)), ("term", _F, ("N", len(FEET_TERMS))), ("total", _F, ("N",)), ("done", _I, ("N",)))
+FEET_IN_FIELDS, FEET_OUT_FIELDS = _arrays(FEET_IN), _arrays(FEET_OUT)
 
 
 class FeetConfig(C.Structure):
@@ -702,24 +854,29 @@ class FeetConfig(C.Structure):
 
 class FeetIn(C.Structure):
     """``gmr_feet_in_t``: the inputs of ``gmr_motion_tracker_feet[_dev]`` beside the bodies, each an address or NULL"""
-    _fields_ = [(k, C.c_void_p) for k in FEET_IN_FIELDS]
+    _fields_ = _fields(FEET_IN)
 
 
 class FeetOut(C.Structure):
     """``gmr_feet_out_t``: the outputs of ``gmr_motion_tracker_feet[_dev]``, each an address or NULL"""
-    _fields_ = [(k, C.c_void_p) for k in FEET_OUT_FIELDS]
+    _fields_ = _fields(FEET_OUT)
 
 
-# gmr_motion_tracker_set_commands / _commands[_dev] / _set_disturbances / _disturb[_dev] (include/gmr_hip.h, "tracker commands")
+# gmr_motion_tracker_set_commands / _commands[_dev] / _set_disturbances / _disturb[_dev] (include/gmr_hip.h, "tracker commands"): the terms in
+# column order (t1.py:606-620), the bits of ``flags`` and of the disturbances
 CMD_TERMS = ("survival", "tracking_lin_vel_x", "tracking_lin_vel_y", "tracking_ang_vel")
 CMD_MAX_LEVELS, CMD_CHUNK = 20, 8
 CMD_BOUNDARY, CMD_RESAMPLED, CMD_SUCCESS = 1, 2, 4
 CMD_INDEX_ORDERS = {"grid": 0, "reference": 1}
 DISTURB_KICK, DISTURB_PUSH_START, DISTURB_PUSH_STOP = 1, 2, 4
 DISTURB_SPECS = ("kick_lin_vel", "kick_ang_vel", "push_force", "push_torque")
-CMD_IN_FIELDS = ("episode_steps", "done", "lin_vel", "ang_vel")
-CMD_OUT_FIELDS = ("term", "total", "commands", "gait_frequency", "flags", "cmd_obs")
-DISTURB_IO_FIELDS = ("root_states", "push_force", "push_torque")
+CMD_IN = (("episode_steps", _I, ("N",)), ("done", _I, ("N",)), ("lin_vel", _F, ("N", 3)), ("ang_vel", _F, ("N", 3)))
+# cmd_obs is three columns inside the caller's rows of cmd_obs_stride floats; the two pushes of the disturbances lie in rows of their strides
+CMD_OUT = (("term", _F, ("N", len(CMD_TERMS))), ("total", _F, ("N",)), ("commands", _F, ("N", 3)), ("gait_frequency", _F, ("N",)), ("flags", _I, ("N",)),
+           ("cmd_obs", _F, ("N", 3)), ("cmd_obs_stride", C.c_int64))
+DISTURB_IO = (("root_states", _F, ("N", 13)), ("push_force", _F, ("N", 3)), ("push_torque", _F, ("N", 3)), ("push_force_stride", C.c_int64),
+              ("push_torque_stride", C.c_int64), ("push_obs", _F, ("N", 6)))
+CMD_IN_FIELDS, CMD_OUT_FIELDS, DISTURB_IO_FIELDS = _arrays(CMD_IN), _arrays(CMD_OUT), _arrays(DISTURB_IO)
 
 
 class CommandsConfig(C.Structure):
@@ -733,12 +890,12 @@ class CommandsConfig(C.Structure):
 
 class CommandsIn(C.Structure):
     """``gmr_commands_in_t``: the inputs of ``gmr_motion_tracker_commands[_dev]``, each an address or NULL"""
-    _fields_ = [(k, C.c_void_p) for k in CMD_IN_FIELDS]
+    _fields_ = _fields(CMD_IN)
 
 
 class CommandsOut(C.Structure):
     """``gmr_commands_out_t``: the outputs of ``gmr_motion_tracker_commands[_dev]``, each an address or NULL, and the row stride of ``cmd_obs``"""
-    _fields_ = [(k, C.c_void_p) for k in CMD_OUT_FIELDS] + [("cmd_obs_stride", C.c_int64)]
+    _fields_ = _fields(CMD_OUT)
 
 
 class DisturbConfig(C.Structure):
@@ -749,20 +906,23 @@ class DisturbConfig(C.Structure):
 
 class DisturbIo(C.Structure):
     """``gmr_disturb_io_t``: what ``gmr_motion_tracker_disturb[_dev]`` writes, each an address or NULL, and the two row strides"""
-    _fields_ = ([(k, C.c_void_p) for k in DISTURB_IO_FIELDS] + [("push_force_stride", C.c_int64), ("push_torque_stride", C.c_int64),
-                                                                ("push_obs", C.c_void_p)])
+    _fields_ = _fields(DISTURB_IO)
 
 
 # gmr_motion_tracker_set_reset_states / _reset_states[_dev] / _set_rewards / _rewards[_dev] / _reward_stats[_dev] (include/gmr_hip.h,
 # "tracker episode")
 RESET_SPECS = ("init_dof_pos", "init_base_pos_xy", "init_base_lin_vel_xy")
-RESET_IO_FIELDS = ("root_states", "dof_pos", "dof_vel", "delay_steps", "episode_steps", "init_root_states", "init_dof_pos", "init_dof_vel")
 REWARD_MAX_EXTRA, REWARD_MAX_COLS = 16, 52
-REWARD_BLOCKS = {"terms": 1, "links": 2, "proprio": 4, "feet": 8, "commands": 16}      # column order
-REWARD_LOCOMOTION, REWARD_IMITATION = 1, 2
+REWARD_BLOCKS = {"terms": 1, "links": 2, "proprio": 4, "feet": 8, "commands": 16}      # the bits of gmr_reward_config_t.blocks, in column order
+REWARD_LOCOMOTION, REWARD_IMITATION = 1, 2                                             # the bits of a column's ``groups`` entry
 REWARD_DONE_TIME_OUT = 4
-REWARD_IN_FIELDS = ("term", "link_term", "proprio_term", "feet_term", "cmd_term", "extra", "done", "flags")
-REWARD_OUT_FIELDS = ("reward", "scaled", "group_total", "reset", "time_outs")
+RESET_IO = (("root_states", _F, ("N", 13)), ("dof_pos", _F, ("N", "R")), ("dof_vel", _F, ("N", "R")), ("delay_steps", _I, ("N",)),
+            ("episode_steps", _I, ("N",)), ("init_root_states", _F, ("n", 13)), ("init_dof_pos", _F, ("n", "R")), ("init_dof_vel", _F, ("n", "R")))
+REWARD_IN = (("term", _F, ("N", TRACKER_TERMS)), ("link_term", _F, ("N", TRACKER_LINK_TERMS)), ("proprio_term", _F, ("N", len(PROPRIO_TERMS))),
+             ("feet_term", _F, ("N", len(FEET_TERMS))), ("cmd_term", _F, ("N", len(CMD_TERMS))), ("extra", _F, ("N", "E")), ("done", _I, ("N",)),
+             ("flags", _I, ("N",)))
+REWARD_OUT = (("reward", _F, ("N",)), ("scaled", _F, ("N", "C")), ("group_total", _F, ("N", 2)), ("reset", _I, ("N",)), ("time_outs", _I, ("N",)))
+RESET_IO_FIELDS, REWARD_IN_FIELDS, REWARD_OUT_FIELDS = _arrays(RESET_IO), _arrays(REWARD_IN), _arrays(REWARD_OUT)
 
 
 class ResetConfig(C.Structure):
@@ -774,7 +934,7 @@ class ResetConfig(C.Structure):
 
 class ResetIo(C.Structure):
     """``gmr_reset_io_t``: the arrays of ``gmr_motion_tracker_reset_states[_dev]``, each an address or NULL"""
-    _fields_ = [(k, C.c_void_p) for k in RESET_IO_FIELDS]
+    _fields_ = _fields(RESET_IO)
 
 
 class RewardConfig(C.Structure):
@@ -785,62 +945,57 @@ class RewardConfig(C.Structure):
 
 class RewardIn(C.Structure):
     """``gmr_reward_in_t``: the inputs of ``gmr_motion_tracker_rewards[_dev]``, each an address or NULL"""
-    _fields_ = [(k, C.c_void_p) for k in REWARD_IN_FIELDS]
+    _fields_ = _fields(REWARD_IN)
 
 
 class RewardOut(C.Structure):
     """``gmr_reward_out_t``: the outputs of ``gmr_motion_tracker_rewards[_dev]``, each an address or NULL"""
-    _fields_ = [(k, C.c_void_p) for k in REWARD_OUT_FIELDS]
+    _fields_ = _fields(REWARD_OUT)
 
 
 # gmr_motion_tracker_set_rollout / _record[_dev] / _advantages[_dev] (include/gmr_hip.h, "tracker rollout")
 ROLLOUT_ENVS, ROLLOUT_FOLD = 64, 64
-ROLLOUT_IO_FIELDS = ("obs", "priv", "actions", "rewards", "dones", "time_outs")
-ROLLOUT_OUT_FIELDS = ("advantages", "returns", "normalized", "stats")
+ROLLOUT_IO = (("obs", _F, ("H", "N", "O")), ("priv", _F, ("H", "N", "P")), ("actions", _F, ("H", "N", "A")), ("rewards", _F, ("H", "N")),
+              ("dones", "uint8", ("H", "N")), ("time_outs", "uint8", ("H", "N")))
+ROLLOUT_OUT = (("advantages", _F, ("H", "N")), ("returns", _F, ("H", "N")), ("normalized", _F, ("H", "N")), ("stats", "float64", (4,)))
+ROLLOUT_IO_FIELDS, ROLLOUT_OUT_FIELDS = _arrays(ROLLOUT_IO), _arrays(ROLLOUT_OUT)
 
 
 class RolloutIo(C.Structure):
     """``gmr_rollout_io_t``: the caller's rollout arrays, each an address or NULL"""
-    _fields_ = [(k, C.c_void_p) for k in ROLLOUT_IO_FIELDS]
+    _fields_ = _fields(ROLLOUT_IO)
 
 
 class RolloutOut(C.Structure):
     """``gmr_rollout_out_t``: the outputs of ``gmr_motion_tracker_advantages[_dev]``, each an address or NULL"""
-    _fields_ = [(k, C.c_void_p) for k in ROLLOUT_OUT_FIELDS]
+    _fields_ = _fields(ROLLOUT_OUT)
 
 
 # gmr_motion_tracker_set_loss / _loss_state / _log_prob[_dev] / _loss[_dev] (include/gmr_hip.h, "tracker loss")
 LOSS_ROWS, LOSS_FOLD, LOSS_MAX_ACT = 64, 64, 32
-LOSS_IN_FIELDS = ("loc", "logstd", "actions", "old_log_prob", "values", "returns", "advantages", "old_loc", "old_logstd")
-LOSS_OUT_FIELDS = ("grad_loc", "grad_logstd", "grad_values", "log_prob", "terms")
 LOSS_TERMS = ("value_loss", "actor_loss", "bound_loss", "entropy", "loss", "kl_mean", "learning_rate", "clip_fraction")
 LOSS_STATE = ("bound_coef", "entropy_coef", "desired_kl", "learning_rate", "e_clip", "lr_min", "lr_max", "lr_factor")
+LOSS_IN = (("loc", _F, ("M", "A")), ("logstd", _F, ("A",)), ("actions", _F, ("M", "A")), ("old_log_prob", _F, ("M",)), ("values", _F, ("M",)),
+           ("returns", _F, ("M",)), ("advantages", _F, ("M",)), ("old_loc", _F, ("M", "A")), ("old_logstd", _F, ("A",)))
+LOSS_OUT = (("grad_loc", _F, ("M", "A")), ("grad_logstd", _F, ("A",)), ("grad_values", _F, ("M",)), ("log_prob", _F, ("M",)),
+            ("terms", "float64", (len(LOSS_TERMS),)))
+LOSS_IN_FIELDS, LOSS_OUT_FIELDS = _arrays(LOSS_IN), _arrays(LOSS_OUT)
 
 
 class LossIn(C.Structure):
     """``gmr_loss_in_t``: the inputs of ``gmr_motion_tracker_loss[_dev]``, each an address (``old_loc``, ``old_logstd``: or NULL)"""
-    _fields_ = [(k, C.c_void_p) for k in LOSS_IN_FIELDS]
+    _fields_ = _fields(LOSS_IN)
 
 
 class LossOut(C.Structure):
     """``gmr_loss_out_t``: the outputs of ``gmr_motion_tracker_loss[_dev]``, each an address or NULL"""
-    _fields_ = [(k, C.c_void_p) for k in LOSS_OUT_FIELDS]
+    _fields_ = _fields(LOSS_OUT)
 
 
 # gmr_motion_tracker_set_preview: the block bits in row order, the frames and the limits (include/gmr_hip.h, "tracker preview")
 PREVIEW_BLOCKS = {"root_pos": 1, "root_quat": 2, "root_rot6": 4, "root_vel": 8, "root_ang_vel": 16, "dof_pos": 32, "dof_vel": 64, "body_pos": 128}
 PREVIEW_FRAME_RAW, PREVIEW_FRAME_REFERENCE, PREVIEW_FRAME_SIM = 0, 1, 2
 PREVIEW_MAX_OFFSETS, PREVIEW_MAX_BODIES = 16, 32
-
-
-class TrackerLinksOut(C.Structure):
-    """``gmr_tracker_links_out_t``: the link outputs of ``gmr_motion_tracker_step_links[_dev]``, each an address or NULL"""
-    _fields_ = [(k, C.c_void_p) for k in TRACKER_LINKS_OUT_FIELDS]
-
-
-class TrackerLinksSim(C.Structure):
-    """``gmr_tracker_links_sim_t``: the simulator's rigid-body state, four addresses (or NULL) and the two strides in floats"""
-    _fields_ = [(k, C.c_void_p) for k in TRACKER_LINKS_SIM_FIELDS] + [("env_stride", C.c_int64), ("body_stride", C.c_int64)]
 
 
 class FkHandle:

@@ -28,6 +28,8 @@ from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
+from . import _lib
+from ._lib import _dev_ptr  # noqa: F401  (the tracker and callers take it from here)
 from .data_loader import motion_arrays
 
 ANGVEL = {"world": 0, "reference": 1}
@@ -38,34 +40,6 @@ STAT_ROWS = ("mean", "std", "min", "max")
 SAMPLE_FIELDS = ("root_pos", "root_rot", "root_vel", "root_ang_vel", "dof_pos", "dof_vel", "local_body_pos")
 STATE_FIELDS = SAMPLE_FIELDS[:6]                                        # what body_state shares with sample
 BODY_FIELDS = {"body_pos": 3, "body_rot": 4, "body_vel": 3, "body_ang_vel": 3}      # floats per body
-
-
-def _dev_ptr(x, what: str, dtype: str, count: int):
-    """Device address of an output / input of ``sample_dev``: None, a ``_lib.DeviceBuffer``, a raw address (``int`` /
-    ``c_void_p``) or an object with ``data_ptr()``, whose dtype, contiguity and size are checked when it tells them."""
-    from . import _lib
-    if x is None:
-        return None
-    need = count * np.dtype(dtype).itemsize
-    if isinstance(x, _lib.DeviceBuffer):
-        if x.nbytes < need:
-            raise ValueError(f"{what}: buffer of {x.nbytes} bytes, {need} needed")
-        return x.ptr
-    if isinstance(x, C.c_void_p):
-        return x
-    if isinstance(x, (int, np.integer)):
-        return C.c_void_p(int(x))
-    if hasattr(x, "data_ptr"):
-        if isinstance(x, np.ndarray) or getattr(getattr(x, "device", None), "type", "cuda") == "cpu":
-            raise ValueError(f"{what}: host memory handed to a device entry point")
-        if hasattr(x, "dtype") and str(x.dtype).split(".")[-1] != dtype:
-            raise ValueError(f"{what}: dtype {x.dtype}, {dtype} needed")
-        if hasattr(x, "is_contiguous") and not x.is_contiguous():
-            raise ValueError(f"{what}: not contiguous")
-        if hasattr(x, "numel") and x.numel() < count:
-            raise ValueError(f"{what}: {x.numel()} elements, {count} needed")
-        return C.c_void_p(int(x.data_ptr()))
-    raise TypeError(f"{what}: cannot take a device address from {type(x).__name__}")
 
 
 class ClipView:
@@ -159,7 +133,6 @@ class MotionLibrary:
         return seg, fps, cat("root_pos"), cat("root_rot"), cat("dof_pos"), lbp, [list(a["link_body_list"]) for a in arrs]
 
     def _build(self, motions, ang_vel, names):
-        from . import _lib
         seg, fps, rp, rr, dp, lbp, links = self.host_inputs(motions)
         self._create(seg, fps, dp.shape[1], 0 if lbp is None else lbp.shape[1], ang_vel, names, links)
         # ONE upload: the four arrays in one host block (every part starts 256-byte aligned)
@@ -178,7 +151,6 @@ class MotionLibrary:
         d.free()
 
     def _create(self, seg_start, fps, ndof, nbody, ang_vel, names=None, link_body_lists=None):
-        from . import _lib
         if ang_vel not in ANGVEL:
             raise ValueError(f"ang_vel must be one of {sorted(ANGVEL)}, got {ang_vel!r}")
         _lib.require_gpu()
@@ -214,7 +186,6 @@ class MotionLibrary:
         return self
 
     def fill_dev(self, d_root_pos, d_root_rot, d_dof_pos, d_local_body_pos=None, stream=None) -> None:
-        from . import _lib
         B = self.num_frames
         _lib.check(_lib.lib().gmr_motion_lib_fill_dev(self.handle, _dev_ptr(d_root_pos, "root_pos", "float64", B * 3),
                                                       _dev_ptr(d_root_rot, "root_rot", "float64", B * 4),
@@ -236,14 +207,12 @@ class MotionLibrary:
 
     def device_array(self, name: str):
         """``(address, bytes)`` of one array of the library on the device"""
-        from . import _lib
         p, n = C.c_void_p(), C.c_size_t()
         _lib.check(_lib.lib().gmr_motion_lib_array(self.handle, ARRAY_IDS[name], C.byref(p), C.byref(n)))
         return p.value, int(n.value)
 
     def array(self, name: str) -> np.ndarray:
         """One array of the library on the host (downloaded on first use; synchronises the device)."""
-        from . import _lib
         a = self._host.get(name)
         if a is None:
             if name == "local_body_pos" and not self.has_local_body_pos:
@@ -272,7 +241,6 @@ class MotionLibrary:
         """N queries in one launch, host arrays in and out: ``root_pos [N,3]``, ``root_rot [N,4]`` xyzw, ``root_vel``,
         ``root_ang_vel``, ``dof_pos [N,ndof]``, ``dof_vel`` (and ``local_body_pos [N,nbody,3]`` when asked for), plus ``status
         i32[N]``: 1 where the clip id is out of range or the time not finite -- those rows are NaN."""
-        from . import _lib
         times = np.ascontiguousarray(times, dtype=np.float64).reshape(-1)
         clip_ids = np.ascontiguousarray(np.broadcast_to(np.asarray(clip_ids), times.shape), dtype=np.int32)
         N = len(times)
@@ -291,7 +259,6 @@ class MotionLibrary:
         """The same on device memory, asynchronous on ``stream``: ``d_clip i32[N]``, ``d_time f64[N]`` and whichever outputs are
         wanted (float32, row-major; ``status`` int32).  Each may be a ``_lib.DeviceBuffer``, a raw address or an object with
         ``data_ptr()``; what such an object says about its dtype, contiguity and size is checked."""
-        from . import _lib
         N = int(N)
         given = dict(root_pos=root_pos, root_rot=root_rot, root_vel=root_vel, root_ang_vel=root_ang_vel, dof_pos=dof_pos,
                      dof_vel=dof_vel, local_body_pos=local_body_pos)
@@ -329,7 +296,6 @@ class MotionLibrary:
     @staticmethod
     def _body_selection(bodies, names, nbody: int):
         """``bodies`` (``None`` | indices | names) -> ``(i32 array or None, nsel)``"""
-        from . import _lib
         if bodies is None:
             return None, nbody
         sel = []
@@ -361,7 +327,6 @@ class MotionLibrary:
         ``body_ang_vel [N,nsel,3]`` of every body (``bodies=None``) or of the bodies named by index or by name, in that order, plus
         ``status``; with ``state`` also the six arrays of :meth:`sample` (same bits).  The pose is the float32 FK of the sampled
         state, the velocities are the library's ``root_vel / root_ang_vel / dof_vel`` carried through the tree."""
-        from . import _lib
         fk, sel, nsel = self._body_state_setup(kinematics, bodies)
         times = np.ascontiguousarray(times, dtype=np.float64).reshape(-1)
         clip_ids = np.ascontiguousarray(np.broadcast_to(np.asarray(clip_ids), times.shape), dtype=np.int32)
@@ -380,18 +345,10 @@ class MotionLibrary:
         """The same on device memory, asynchronous on ``stream``: ``outputs`` names whichever of ``root_pos, root_rot, root_vel,
         root_ang_vel, dof_pos, dof_vel, body_pos, body_rot, body_vel, body_ang_vel, status`` are wanted, each a ``_lib.DeviceBuffer``, a
         raw address or an object with ``data_ptr()``, checked as :meth:`sample_dev` checks them."""
-        from . import _lib
         fk, sel, nsel = self._body_state_setup(kinematics, bodies)
         N = int(N)
-        count = {"root_pos": 3, "root_rot": 4, "root_vel": 3, "root_ang_vel": 3, "dof_pos": self.ndof, "dof_vel": self.ndof, "status": 1}
-        count.update({k: nsel * w for k, w in BODY_FIELDS.items()})
-        unknown = sorted(set(outputs) - set(count))
-        if unknown:
-            raise TypeError(f"body_state_dev: unknown outputs {unknown}")
-        table = _lib.BodyStateOut()
-        for k, x in outputs.items():
-            p = _dev_ptr(x, k, "int32" if k == "status" else "float32", N * count[k])
-            setattr(table, k, None if p is None else p.value)
+        rows = _lib.resolve(_lib.BODY_STATE, N=N, R=self.ndof, nsel=nsel)
+        table = _lib.device_struct(_lib.BodyStateOut, rows, outputs, "body_state_dev")
         _lib.check(_lib.lib().gmr_motion_body_state_dev(self.handle, fk.handle, N, _dev_ptr(d_clip, "clip", "int32", N),
                                                         _dev_ptr(d_time, "time", "float64", N), LOOP if loop else 0, _lib._ptr(sel), nsel,
                                                         C.byref(table), _lib._s(stream)))
@@ -413,7 +370,6 @@ class MotionLibrary:
     def close(self) -> None:
         h = getattr(self, "handle", None)
         if h:
-            from . import _lib
             _lib.lib().gmr_motion_lib_destroy(h)
             self.handle = None
 

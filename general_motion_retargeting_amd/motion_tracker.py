@@ -32,51 +32,33 @@ from typing import Dict, Optional, Sequence
 
 import numpy as np
 
-from .motion_library import LOOP, MotionLibrary, _dev_ptr
+from . import _lib
+from ._lib import (CMD_BOUNDARY, CMD_INDEX_ORDERS, CMD_MAX_LEVELS, CMD_RESAMPLED, CMD_SUCCESS, CMD_TERMS, CONTROL_MAX_DECIMATION, DISTURB_KICK,  # noqa: F401
+                   DISTURB_PUSH_START, DISTURB_PUSH_STOP, DISTURB_SPECS, FEET_DONE_CONTACT, FEET_MAX_BODIES, FEET_MAX_EDGES, FEET_TERMS,
+                   NOISE_DISTRIBUTIONS, NOISE_OPERATIONS, PREVIEW_MAX_BODIES, PREVIEW_MAX_OFFSETS, PROPRIO_MAX_EXTRA, PROPRIO_NOISE_BLOCKS,
+                   PROPRIO_TERMS, RESET_SPECS, REWARD_BLOCKS, REWARD_IMITATION, REWARD_LOCOMOTION, REWARD_MAX_EXTRA, _dev_ptr)
+from .motion_library import LOOP, MotionLibrary
 
+# what the library's ABI fixes -- term names in column order, limits, flag bits -- is defined once, in _lib.py, and bound here under the same name
 TERMS = ("root_pos", "root_rot", "root_vel", "root_ang_vel", "dof_pos", "dof_vel")
 DEFAULT_SCALES = (0.5, 0.5, 2.0, 1.0, 1.0, 0.1)           # T1Imitation.yaml:327-332
-MAX_DOF = 64
+MAX_DOF = _lib.TRACKER_MAX_DOF
 LINK_TERMS = ("link_pos", "link_rot", "link_vel", "link_ang_vel")
 DEFAULT_LINK_SCALES = (0.3, 0.8, 2.0, 4.0)               # m, rad, m/s, rad/s: a choice of this library, the reference has no link terms
 FRAMES = {"world": 0, "heading": 1}
-PREVIEW_BLOCKS = ("root_pos", "root_quat", "root_rot6", "root_vel", "root_ang_vel", "dof_pos", "dof_vel", "body_pos")      # row order
+PREVIEW_BLOCKS = tuple(_lib.PREVIEW_BLOCKS)               # row order
 PREVIEW_SAMPLER_BLOCKS = ("root_pos", "root_quat", "root_vel", "root_ang_vel", "dof_pos", "dof_vel")
 PREVIEW_FRAMES = {"raw": 0, "reference": 1, "sim": 2}
-PREVIEW_MAX_OFFSETS, PREVIEW_MAX_BODIES = 16, 32
 ADAPTIVE_MAX_BINS, ADAPTIVE_MAX_LOOKAHEAD = 1 << 22, 16
 # failure-driven start sampling: a choice of this library, the reference starts every motion at time 0
 DEFAULT_ADAPTIVE = {"bin_seconds": 1.0, "alpha": 0.1, "uniform": 0.3, "lookahead": 4, "gamma": 0.8}
-CONTROL_MAX_DECIMATION = 64
 # t1_imitation.py:388, :414: two seconds of start-up, the action gain during it and afterwards
 DEFAULT_CONTROL = {"startup_seconds": 2.0, "gain_startup": 0.1, "gain_run": 0.2}
-# the penalties of :meth:`MotionTracker.proprio` in column order (t1.py:622-625, :631-694) and the blocks that take sensor noise
-PROPRIO_TERMS = ("lin_vel_z", "ang_vel_xy", "orientation", "torques", "dof_vel", "dof_acc", "root_acc", "action_rate", "dof_pos_limits",
-                 "dof_vel_limits", "torque_limits", "torque_tiredness", "power", "base_height")
-PROPRIO_NOISE_BLOCKS = ("gravity", "ang_vel", "dof_pos", "dof_vel", "lin_vel", "height")
 PROPRIO_NORMALIZATION = ("gravity", "lin_vel", "ang_vel", "dof_pos", "dof_vel")
-PROPRIO_MAX_EXTRA = 16
 PROPRIO_STATE = ("filtered_lin_vel", "filtered_ang_vel", "last_root_vel", "last_actions", "last_dof_vel", "noise_tick")
-NOISE_DISTRIBUTIONS = {"none": 0, "gaussian": 1, "uniform": 2}
-NOISE_OPERATIONS = {"additive": 0, "scaling": 1}
-# the terms of :meth:`MotionTracker.feet` in column order (t1.py:627-629, :696-730)
-FEET_TERMS = ("collision", "feet_slip", "feet_vel_z", "feet_roll", "feet_yaw_diff", "feet_yaw_mean", "feet_distance", "feet_swing")
-FEET_MAX_EDGES, FEET_MAX_BODIES = 8, 64
-FEET_DONE_CONTACT = 8                    # the bit of ``done`` of :meth:`MotionTracker.feet`: OR-able with the bits 0 to 2 of :meth:`MotionTracker.proprio`
 FEET_STATE = ("last_feet_pos", "gait_process")
 DEFAULT_FEET = {"force_threshold": 1.0, "contact_clearance": 0.01}          # t1.py:553, :629 and :545
-# the terms of :meth:`MotionTracker.commands` in column order (t1.py:606-620), the bits of its ``flags`` and of :meth:`MotionTracker.disturb`
-CMD_TERMS = ("survival", "tracking_lin_vel_x", "tracking_lin_vel_y", "tracking_ang_vel")
-CMD_MAX_LEVELS = 20
-CMD_BOUNDARY, CMD_RESAMPLED, CMD_SUCCESS = 1, 2, 4
-CMD_INDEX_ORDERS = {"grid": 0, "reference": 1}
 COMMAND_STATE = ("commands", "gait_frequency", "cmd_resample_time", "cmd_draws", "env_level", "curriculum_prob", "hits", "cum")
-DISTURB_KICK, DISTURB_PUSH_START, DISTURB_PUSH_STOP = 1, 2, 4
-DISTURB_SPECS = ("kick_lin_vel", "kick_ang_vel", "push_force", "push_torque")
-RESET_SPECS = ("init_dof_pos", "init_base_pos_xy", "init_base_lin_vel_xy")
-REWARD_MAX_EXTRA = 16
-REWARD_BLOCKS = {"terms": 1, "links": 2, "proprio": 4, "feet": 8, "commands": 16}      # the bits of gmr_reward_config_t.blocks, in column order
-REWARD_LOCOMOTION, REWARD_IMITATION = 1, 2         # the bits of a column's ``groups`` entry of :meth:`MotionTracker.set_rewards`
 LINK_SIM = {"body_pos": (0, 3), "body_rot": (3, 4), "body_vel": (7, 3), "body_ang_vel": (10, 3)}      # offset and width in a packed row of 13
 
 
@@ -164,8 +146,8 @@ class MotionTracker:
 
     def __init__(self, library: MotionLibrary, num_envs: int, dt: float, dof_map=None, dof_default=None, dof_weight=None, loop: bool = True,
                  scales=None, weights=None, clip_weights=None, seed: int = 0):
-        from . import _lib
-        self.library, self.num_envs, self.dt, self.loop, self.seed = library, int(num_envs), float(dt), bool(loop), int(seed)
+        self._init_state(library, num_envs)
+        self.dt, self.loop, self.seed = float(dt), bool(loop), int(seed)
         if self.num_envs < 1:
             raise ValueError(f"num_envs = {num_envs}")
         if not 0 <= self.seed < 2 ** 64:
@@ -173,32 +155,83 @@ class MotionTracker:
         R, m, d, w = _dof_tables(library.ndof, dof_map, dof_default, dof_weight)
         cw = _clip_weights(library.num_clips, clip_weights)
         sc, wt = _terms(scales, weights)
-        self.handle = None
         _lib.require_gpu()
         h = C.c_void_p()
         _lib.check(_lib.lib().gmr_motion_tracker_create(library.handle, self.num_envs, self.dt, LOOP if loop else 0, R, _lib._ptr(m), _lib._ptr(d),
                                                         _lib._ptr(w), _lib._ptr(cw), self.seed, C.byref(h)))
         self.handle, self.nrobot_dof = h, R
-        self._links = None            # (fk, nsel, sim_body, frame) once set_links has attached a selection
-        self._preview = None          # (K, blocks in row order, frame, nsel) once set_preview has configured one
-        self._adaptive = None         # (bin_seconds, bin_start i64[C + 1]) once set_adaptive has built the bins
-        self._anchors = False         # whether the per-environment anchors are enabled
-        self._control = None          # (R, decimation) once set_control has configured the control half
-        self._proprio = None          # (R, extra_cols) once set_proprio has configured the proprioception half
-        self._feet = None             # (num_bodies, num_edges) once set_feet has configured the feet
-        self._commands = None         # ((L, A) or None,) once set_commands has configured the velocity commands
-        self._resets = None           # (R, decimation) once set_reset_states has configured the reset states
-        self._rewards = None          # the checked configuration once set_rewards has laid the reward columns out
-        self._rollout = None          # the checked configuration once set_rollout has configured the rollout
-        self._loss = None             # the checked configuration, with its rows and columns, once set_loss has configured the loss head
-        self._disturb = None          # (kick_every, push_every, push_duration) once set_disturbances has configured kicks and pushes
         if sc is not None or wt is not None:
             self.set_terms(sc, wt)
+
+    # The private state of a tracker on which nothing is configured yet, stated once: a ``set_*`` call replaces an entry on the instance.
+    _links = None            # (fk, nsel, sim_body, frame) once set_links has attached a selection
+    _preview = None          # (K, blocks in row order, frame, nsel) once set_preview has configured one
+    _adaptive = None         # (bin_seconds, bin_start i64[C + 1]) once set_adaptive has built the bins
+    _anchors = False         # whether the per-environment anchors are enabled
+    _control = None          # (R, decimation) once set_control has configured the control half
+    _proprio = None          # (R, extra_cols) once set_proprio has configured the proprioception half
+    _feet = None             # (num_bodies, num_edges) once set_feet has configured the feet
+    _commands = None         # ((L, A) or None,) once set_commands has configured the velocity commands
+    _resets = None           # (R, decimation) once set_reset_states has configured the reset states
+    _rewards = None          # the checked configuration once set_rewards has laid the reward columns out
+    _rollout = None          # the checked configuration once set_rollout has configured the rollout
+    _loss = None             # the checked configuration, with its rows and columns, once set_loss has configured the loss head
+    _disturb = None          # (kick_every, push_every, push_duration) once set_disturbances has configured kicks and pushes
+
+    def _init_state(self, library, num_envs, nrobot_dof=None) -> None:
+        """What a tracker holds before a handle exists, beside the class's "nothing configured" entries above: needs no device"""
+        self.library, self.num_envs, self.nrobot_dof, self.handle = library, int(num_envs), nrobot_dof, None
+
+    def _rows_of(self, table, **dims):
+        """the arrays of a table of ``_lib.py`` as ``{name: (dtype, shape, count)}`` under ``N = num_envs`` and ``dims``"""
+        return _lib.resolved(table, N=self.num_envs, **dims)
+
+    def _subset(self, what: str, env_ids, mask=None, n=None, device: bool = False, once: bool = True, all_envs: str = "every environment is served"):
+        """``env_ids`` / ``mask`` / ``n`` of a call that serves a listed subset -> ``(n, ids, mask)``: host arrays ``i32[n]`` or ``None``
+        (``once``: a list that names an environment twice is refused), or -- ``device`` -- device addresses, where a list needs ``n``"""
+        if device:
+            if env_ids is None:
+                if n is not None and int(n) != self.num_envs:
+                    raise ValueError(f"{what}: without env_ids {all_envs}: n = {n}, num_envs = {self.num_envs}")
+                n = self.num_envs
+            elif n is None or int(n) < 0:
+                raise ValueError(f"{what}: env_ids on the device needs n, the length of the list")
+            n = int(n)
+            return n, _dev_ptr(env_ids, "env_ids", "int32", n), _dev_ptr(mask, "mask", "int32", n)
+        ids, n = None, self.num_envs
+        if env_ids is not None:
+            ids = np.ascontiguousarray(env_ids, dtype=np.int32).reshape(-1)
+            n = len(ids)
+            if once and len(np.unique(ids)) != n:
+                raise ValueError(f"{what}: env_ids names an environment twice")
+        return n, ids, _mask(mask, "mask", n)
+
+    def _bodies(self, bodies, names, width: int, nb=None, reach=None, device: bool = False):
+        """The simulator's rigid bodies as a ``gmr_tracker_links_sim_t`` -> ``(struct, arrays to keep alive)``.  ``bodies`` is
+        ``{"body_state": the packed [N, nb, 13] tensor}`` -- the fields ``names`` become offsets into it, with its two strides; ``nb=None``
+        reads the count off a host array; ``reach``, the largest body index that will be read, must lie inside -- or ``{name: [N, width, k]}``,
+        the separate arrays."""
+        N = self.num_envs
+        if "body_state" not in bodies:
+            rows = self._rows_of(_lib.TRACKER_LINKS_SIM, nsel=width)
+            return (_lib.device_struct(_lib.TrackerLinksSim, rows, bodies), []) if device else _lib.host_inputs(_lib.TrackerLinksSim, rows, bodies)
+        a = bodies["body_state"]
+        if not device:
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.ndim != 3 or a.shape[0] != N or a.shape[2] != 13 or nb not in (None, a.shape[1]):
+                raise ValueError(f"body_state: shape {a.shape}, ({N}, {'nb' if nb is None else nb}, 13) needed")
+            nb = a.shape[1]
+        if reach is not None and reach >= nb:
+            raise ValueError(f"sim_bodies reaches body {reach}, body_state has {nb}")
+        base = _dev_ptr(a, "body_state", "float32", N * nb * 13).value if device else a.ctypes.data
+        ls = _lib.TrackerLinksSim(env_stride=13 * nb, body_stride=13)
+        for k in names:
+            setattr(ls, k, base + 4 * LINK_SIM[k][0])
+        return ls, [a]
 
     # ---- tables ---------------------------------------------------------------------------------------------------------
     def set_dof_map(self, dof_map=None, dof_default=None, dof_weight=None) -> None:
         """Replaces the three dof tables (a curriculum changes them between stages); steps already enqueued keep theirs."""
-        from . import _lib
         R, m, d, w = _dof_tables(self.library.ndof, dof_map, dof_default, dof_weight)
         _lib.check(_lib.lib().gmr_motion_tracker_set_dof_map(self.handle, R, _lib._ptr(m), _lib._ptr(d), _lib._ptr(w)))
         self.nrobot_dof = R
@@ -206,7 +239,6 @@ class MotionTracker:
     def set_terms(self, scales=None, weights=None) -> None:
         """``term = exp(-err / scale)``, ``total = sum of weight * term`` over the terms whose weight is not zero; what is ``None``
         is kept."""
-        from . import _lib
         sc, wt = _terms(scales, weights)
         _lib.check(_lib.lib().gmr_motion_tracker_set_terms(self.handle, _lib._ptr(sc), _lib._ptr(wt)))
 
@@ -214,7 +246,6 @@ class MotionTracker:
     def reset(self, env_ids=None, resample: bool = True, time_offset_range: Sequence[float] = (0.0, 0.0)) -> int:
         """``_reset_idx`` (:215-235) for ``env_ids`` (all by default): a new clip when ``resample``, and the clock at a uniformly
         random point of ``time_offset_range``.  Returns how many ids lay outside ``[0, num_envs)`` (they are ignored)."""
-        from . import _lib
         lo, hi = (float(x) for x in time_offset_range)
         ids, n = None, 0
         if env_ids is not None:
@@ -228,7 +259,6 @@ class MotionTracker:
 
     def assign(self, clip_ids, times, env_ids=None) -> int:
         """Sets ``(clip, time)`` of ``env_ids`` (all, in order, by default) explicitly; returns the number of ignored ids."""
-        from . import _lib
         n = self.num_envs if env_ids is None else int(np.size(env_ids))
         ids = None if env_ids is None else np.ascontiguousarray(env_ids, dtype=np.int32).reshape(-1)
         clip = np.ascontiguousarray(np.broadcast_to(np.asarray(clip_ids, dtype=np.int32), (n,)))
@@ -241,14 +271,12 @@ class MotionTracker:
         """:meth:`reset` with the ids (``i32[n]``, every environment once) on the device, asynchronous on ``stream``.  A list that names
         an environment twice gives that environment one of two outcomes (one draw or two) and touches no other; the masked form,
         :meth:`reset_done_dev`, takes the flags themselves and cannot have that problem."""
-        from . import _lib
         lo, hi = (float(x) for x in time_offset_range)
         _lib.check(_lib.lib().gmr_motion_tracker_reset_dev(self.handle, int(n), _dev_ptr(d_env_ids, "env_ids", "int32", int(n)),
                                                            1 if resample else 0, lo, hi, _lib._s(stream)))
 
     def assign_dev(self, n: int, d_clip, d_time, d_env_ids=None, stream=None) -> None:
         """:meth:`assign` on device memory (``clip i32[n]``, ``time f32[n]``, ``env_ids i32[n]`` or None with n = num_envs)"""
-        from . import _lib
         n = int(n)
         _lib.check(_lib.lib().gmr_motion_tracker_assign_dev(self.handle, n, _dev_ptr(d_env_ids, "env_ids", "int32", n),
                                                             _dev_ptr(d_clip, "clip", "int32", n), _dev_ptr(d_time, "time", "float32", n),
@@ -257,13 +285,12 @@ class MotionTracker:
     def state(self) -> Dict[str, np.ndarray]:
         """``clip i32[N]``, ``time f32[N]``, ``length f32[N]``, ``draws u32[N]``, ``ignored``, the ids outside ``[0, N)`` met so far, and
         ``adaptive``: whether :meth:`set_adaptive` has bins in place"""
-        from . import _lib
         N = self.num_envs
         out = {"clip": np.empty(N, np.int32), "time": np.empty(N, np.float32), "length": np.empty(N, np.float32), "draws": np.empty(N, np.uint32)}
         ign = C.c_uint32()
         _lib.check(_lib.lib().gmr_motion_tracker_state(self.handle, *[_lib._ptr(out[k]) for k in ("clip", "time", "length", "draws")], C.byref(ign)))
         out["ignored"] = int(ign.value)
-        out["adaptive"] = getattr(self, "_adaptive", None) is not None
+        out["adaptive"] = self._adaptive is not None
         return out
 
     # ---- adaptive sampling and masked resets (DESIGN.md section 6n) ---------------------------------------------------------
@@ -297,7 +324,6 @@ class MotionTracker:
         ``bin_seconds=None`` (or ``<= 0``) turns adaptive sampling off.  From then on :meth:`reset_done` and the redraw of a finished clip
         (``loop=False``) take clip and start time from the bins; :meth:`reset` and :meth:`assign` do not change.  The defaults
         (:data:`DEFAULT_ADAPTIVE`) are a choice of this library."""
-        from . import _lib
         if bin_seconds is None or (np.isfinite(float(bin_seconds)) and float(bin_seconds) <= 0):
             _lib.check(_lib.lib().gmr_motion_tracker_set_adaptive(self.handle, 0.0, 0.0, 1.0, 1, 1.0))
             self._adaptive = None
@@ -307,20 +333,18 @@ class MotionTracker:
         self._adaptive = (bin_seconds, bin_start)
 
     def _need_adaptive(self, what: str):
-        if getattr(self, "_adaptive", None) is None:
+        if self._adaptive is None:
             raise ValueError(f"{what}: adaptive sampling is not configured, call set_adaptive() first")
         return self._adaptive
 
     def adapt(self) -> None:
         """One Adapt (typically once per rollout): the failure counts enter the history and are cleared, the start probabilities and
         their CDF are rebuilt.  Synchronous."""
-        from . import _lib
         self._need_adaptive("adapt")
         _lib.check(_lib.lib().gmr_motion_tracker_adapt(self.handle))
 
     def adapt_dev(self, stream=None) -> None:
         """:meth:`adapt`, asynchronous on ``stream`` (three launches)"""
-        from . import _lib
         self._need_adaptive("adapt_dev")
         _lib.check(_lib.lib().gmr_motion_tracker_adapt_dev(self.handle, _lib._s(stream)))
 
@@ -328,7 +352,7 @@ class MotionTracker:
         lo, hi = (float(x) for x in time_offset_range)
         if not (np.isfinite(lo) and np.isfinite(hi)):
             raise ValueError(f"{what}: time_offset_range {(lo, hi)} is not finite")
-        if getattr(self, "_adaptive", None) is not None and (not resample or lo != 0.0 or hi != 0.0):
+        if self._adaptive is not None and (not resample or lo != 0.0 or hi != 0.0):
             raise ValueError(f"{what}: an adaptive tracker draws clip and start time from its bins, so resample=True and "
                              f"time_offset_range=(0, 0) are the only choice (got {resample}, {(lo, hi)}); reset() serves a range")
         return lo, hi
@@ -339,14 +363,8 @@ class MotionTracker:
         position.  On a plain tracker a done environment gets what :meth:`reset` gives it, bit for bit, and one that is not done consumes
         no draw.  On an adaptive tracker the bin of every done environment with ``failed`` set is counted first -- at the clock it has
         now -- and clip and start time come from the bins.  Returns how many ids of done entries lay outside ``[0, num_envs)``."""
-        from . import _lib
         lo, hi = self._check_reset_done("reset_done", resample, time_offset_range)
-        ids, n = None, self.num_envs
-        if env_ids is not None:
-            ids = np.ascontiguousarray(env_ids, dtype=np.int32).reshape(-1)
-            n = len(ids)
-            if len(np.unique(ids)) != n:
-                raise ValueError("reset_done: env_ids names an environment twice")
+        n, ids, _ = self._subset("reset_done", env_ids)
         d, f = _mask(done, "done", n), _mask(failed, "failed", n)
         if n == 0:
             return 0
@@ -360,23 +378,15 @@ class MotionTracker:
         """:meth:`reset_done` on device memory, asynchronous on ``stream``: ONE launch, no allocation, no synchronisation, no
         read-back.  ``done`` / ``failed`` are ``i32`` masks as a step leaves them (``finished``, ``fail``) or as the simulator keeps them;
         with ``env_ids`` (``i32[n]``) they are indexed by list position and ``n`` is mandatory."""
-        from . import _lib
         lo, hi = self._check_reset_done("reset_done_dev", resample, time_offset_range)
-        if env_ids is None:
-            if n is not None and int(n) != self.num_envs:
-                raise ValueError(f"reset_done_dev: without env_ids the masks cover every environment: n = {n}, num_envs = {self.num_envs}")
-            n = self.num_envs
-        elif n is None or int(n) < 0:
-            raise ValueError("reset_done_dev: env_ids on the device needs n, the length of the list")
-        n = int(n)
-        p_ids, p_done, p_failed = (_dev_ptr(x, k, "int32", n) for k, x in (("env_ids", env_ids), ("done", done), ("failed", failed)))
+        n, p_ids, _ = self._subset("reset_done_dev", env_ids, n=n, device=True, all_envs="the masks cover every environment")
+        p_done, p_failed = _dev_ptr(done, "done", "int32", n), _dev_ptr(failed, "failed", "int32", n)
         _lib.check(_lib.lib().gmr_motion_tracker_reset_done_dev(self.handle, n, p_ids, p_done, p_failed, 1 if resample else 0, lo, hi,
                                                                 _lib._s(stream)))
 
     def adaptive_state(self) -> Dict[str, np.ndarray]:
         """``bin_start i32[C + 1]``, ``fail_now u32[Bt]`` (failures since the last Adapt), ``ema``, ``prob``, ``cdf`` (``f64[Bt]``) and
         ``clip_prob f64[C]``, the sum of ``prob`` over the bins of every clip.  Synchronous."""
-        from . import _lib
         _, bin_start = self._need_adaptive("adaptive_state")
         Bt, Cn = int(bin_start[-1]), len(bin_start) - 1
         out = {"bin_start": np.empty(Cn + 1, np.int32), "fail_now": np.empty(Bt, np.uint32), "ema": np.empty(Bt, np.float64),
@@ -393,7 +403,7 @@ class MotionTracker:
                              f'ang_vel="{self.library.ang_vel}" is not a physical angular velocity and cannot be rotated')
 
     def _need_anchors(self, what: str) -> None:
-        if not getattr(self, "_anchors", False):
+        if not self._anchors:
             raise ValueError(f"{what}: anchors are not enabled on this tracker, call enable_anchors() first")
 
     def enable_anchors(self, on: bool = True) -> None:
@@ -402,19 +412,13 @@ class MotionTracker:
         the root blocks of a ``"raw"`` preview and the reference of a ``"sim"`` one.  ``frame="heading"`` links and a ``"reference"``
         preview do not see them.  Enabling allocates the two arrays once and fills them with the identity (synchronous; a tracker that
         has them keeps them as they are); ``on=False`` frees them and the tracker runs the plain code path again."""
-        from . import _lib
         _lib.check(_lib.lib().gmr_motion_tracker_enable_anchors(self.handle, 1 if on else 0))
         self._anchors = bool(on)
 
     def _anchor_setup(self, what, pos, yaw, env_ids, n=None):
         """the checks of :meth:`set_anchor`, all of them before a device is touched -> ``(n, ids i32[n] or None, pos f32[n,3] or None, yaw
         f32[n] or None)``"""
-        ids = None
-        if env_ids is None:
-            n = self.num_envs
-        else:
-            ids = np.ascontiguousarray(env_ids, dtype=np.int32).reshape(-1)
-            n = len(ids)
+        n, ids, _ = self._subset(what, env_ids, once=False)
         if pos is not None:
             pos = np.ascontiguousarray(pos, dtype=np.float32)
             if pos.shape != (n, 3):
@@ -433,7 +437,6 @@ class MotionTracker:
     def set_anchor(self, pos=None, yaw=None, env_ids=None) -> int:
         """Sets the anchors of ``env_ids`` (all, in order, by default): ``pos [n,3]`` metres and / or ``yaw [n]`` radians; what is ``None``
         is kept.  Enables anchors when they are not.  Returns how many ids lay outside ``[0, num_envs)`` (they are ignored)."""
-        from . import _lib
         n, ids, pos, yaw = self._anchor_setup("set_anchor", pos, yaw, env_ids)
         ignored = C.c_int()
         _lib.check(_lib.lib().gmr_motion_tracker_set_anchor(self.handle, n, _lib._ptr(ids), _lib._ptr(pos), _lib._ptr(yaw), C.byref(ignored)))
@@ -443,22 +446,12 @@ class MotionTracker:
     def set_anchor_dev(self, pos=None, yaw=None, env_ids=None, n: Optional[int] = None, stream=None) -> None:
         """:meth:`set_anchor` on device memory (``pos f32[n*3]``, ``yaw f32[n]`` radians, ``env_ids i32[n]`` with ``n``, or None for all),
         asynchronous on ``stream``: one launch.  Anchors must be enabled."""
-        from . import _lib
         self._need_anchors("set_anchor_dev")
         if yaw is not None:
             self._anchor_yaw_allowed("set_anchor_dev")
-        n = self._list_length("set_anchor_dev", env_ids, n)
-        p_ids, p_pos, p_yaw = _dev_ptr(env_ids, "env_ids", "int32", n), _dev_ptr(pos, "pos", "float32", n * 3), _dev_ptr(yaw, "yaw", "float32", n)
+        n, p_ids, _ = self._subset("set_anchor_dev", env_ids, n=n, device=True)
+        p_pos, p_yaw = _dev_ptr(pos, "pos", "float32", n * 3), _dev_ptr(yaw, "yaw", "float32", n)
         _lib.check(_lib.lib().gmr_motion_tracker_set_anchor_dev(self.handle, n, p_ids, p_pos, p_yaw, _lib._s(stream)))
-
-    def _list_length(self, what: str, env_ids, n) -> int:
-        if env_ids is None:
-            if n is not None and int(n) != self.num_envs:
-                raise ValueError(f"{what}: without env_ids every environment is served: n = {n}, num_envs = {self.num_envs}")
-            return self.num_envs
-        if n is None or int(n) < 0:
-            raise ValueError(f"{what}: env_ids on the device needs n, the length of the list")
-        return int(n)
 
     def anchor_to_root(self, root_pos, root_quat, mask=None, env_ids=None, yaw: bool = True, z: bool = False) -> int:
         """Anchors the reference to where the robot is: for every environment whose ``mask`` is set (``None``: all), the anchor that
@@ -467,21 +460,14 @@ class MotionTracker:
         cover every environment; with it (every environment at most once) they are indexed by list position, as the masks of
         :meth:`reset_done` are.  A bad assignment or a root that is not finite leaves that environment's anchor as it was.  Enables
         anchors when they are not.  Returns how many ids of masked entries lay outside ``[0, num_envs)``."""
-        from . import _lib
         if yaw:
             self._anchor_yaw_allowed("anchor_to_root")
-        ids, n = None, self.num_envs
-        if env_ids is not None:
-            ids = np.ascontiguousarray(env_ids, dtype=np.int32).reshape(-1)
-            n = len(ids)
-            if len(np.unique(ids)) != n:
-                raise ValueError("anchor_to_root: env_ids names an environment twice")
+        n, ids, m = self._subset("anchor_to_root", env_ids, mask)
         rp, rq = np.ascontiguousarray(root_pos, dtype=np.float32), np.ascontiguousarray(root_quat, dtype=np.float32)
         if rp.shape != (n, 3):
             raise ValueError(f"anchor_to_root: root_pos has shape {rp.shape}, {(n, 3)} needed")
         if rq.shape != (n, 4):
             raise ValueError(f"anchor_to_root: root_quat has shape {rq.shape}, {(n, 4)} needed")
-        m = _mask(mask, "mask", n)
         ignored = C.c_int()
         _lib.check(_lib.lib().gmr_motion_tracker_anchor_to_root(self.handle, n, _lib._ptr(ids), _lib._ptr(m), _lib._ptr(rp), _lib._ptr(rq),
                                                                 (_lib.ANCHOR_YAW if yaw else 0) | (_lib.ANCHOR_Z if z else 0), C.byref(ignored)))
@@ -493,14 +479,12 @@ class MotionTracker:
         """:meth:`anchor_to_root` on device memory, asynchronous on ``stream``: ONE launch, no allocation, no synchronisation, no
         read-back.  ``mask`` is an ``i32`` mask as a step leaves it (``finished``) or as :meth:`reset_done_dev` takes it; ``root_pos
         f32[n*3]``, ``root_quat f32[n*4]``; with ``env_ids`` (``i32[n]``) ``n`` is mandatory.  Anchors must be enabled."""
-        from . import _lib
         self._need_anchors("anchor_to_root_dev")
         if yaw:
             self._anchor_yaw_allowed("anchor_to_root_dev")
-        n = self._list_length("anchor_to_root_dev", env_ids, n)
+        n, p_ids, p_mask = self._subset("anchor_to_root_dev", env_ids, mask, n, device=True)
         if root_pos is None or root_quat is None:
             raise ValueError("anchor_to_root_dev: root_pos and root_quat are needed")
-        p_ids, p_mask = _dev_ptr(env_ids, "env_ids", "int32", n), _dev_ptr(mask, "mask", "int32", n)
         p_pos, p_quat = _dev_ptr(root_pos, "root_pos", "float32", n * 3), _dev_ptr(root_quat, "root_quat", "float32", n * 4)
         _lib.check(_lib.lib().gmr_motion_tracker_anchor_to_root_dev(self.handle, n, p_ids, p_mask, p_pos, p_quat,
                                                                     (_lib.ANCHOR_YAW if yaw else 0) | (_lib.ANCHOR_Z if z else 0), _lib._s(stream)))
@@ -508,8 +492,7 @@ class MotionTracker:
     def anchor_state(self) -> Optional[Dict[str, np.ndarray]]:
         """``pos f32[N,3]`` and ``yaw_zw f32[N,2]``, the ``(z, w)`` of the yaw's unit quaternion, or ``None`` when anchors are off.
         Synchronous."""
-        from . import _lib
-        if not getattr(self, "_anchors", False):
+        if not self._anchors:
             return None
         out = {"pos": np.empty((self.num_envs, 3), np.float32), "yaw_zw": np.empty((self.num_envs, 2), np.float32)}
         _lib.check(_lib.lib().gmr_motion_tracker_anchor_state(self.handle, _lib._ptr(out["pos"]), _lib._ptr(out["yaw_zw"])))
@@ -542,13 +525,12 @@ class MotionTracker:
         policy action, the ``startup_seconds`` of the easing (0: none) with the action gain during it and afterwards, and ``decimation``,
         the physics substeps per step.  Allocates ``held`` and ``torque_acc`` (``[N, R]``, zeros).  Synchronous; call it again after
         :meth:`set_dof_map` has changed the number of robot dofs."""
-        from . import _lib
         d, k, c, D, g0, g1, M = self._control_setup(default_dof_pos, action_scale, clip_actions, startup_seconds, gain_startup, gain_run, decimation)
         _lib.check(_lib.lib().gmr_motion_tracker_set_control(self.handle, _lib._ptr(d), k, c, D, g0, g1, M))
         self._control = (self.nrobot_dof, M)
 
     def _need_control(self, what: str):
-        ctl = getattr(self, "_control", None)
+        ctl = self._control
         if ctl is None:
             raise ValueError(f"{what}: control is not set on this tracker, call set_control() first")
         if ctl[0] != self.nrobot_dof:
@@ -579,7 +561,6 @@ class MotionTracker:
         pose with a cosine S-curve while ``episode_steps [N] * dt`` (the simulator's episode length counter; ``None``: no start-up) is
         below ``startup_seconds``, plus ``action_scale * clip(actions) * gain`` --, ``status i32[N]`` (1: a bad assignment, its row is
         NaN) and, with ``actions [N,R]``, ``actions_clipped``.  One launch; clocks, clips and draw counters stay as they are."""
-        from . import _lib
         self._need_control("targets")
         N, R = self.num_envs, self.nrobot_dof
         a = None if actions is None else self._rows(actions, "actions")
@@ -594,7 +575,6 @@ class MotionTracker:
     def targets_dev(self, actions=None, episode_steps=None, dof_targets=None, actions_clipped=None, status=None, stream=None) -> None:
         """:meth:`targets` on device memory, asynchronous on ``stream``: ``actions f32[N*R]`` and ``episode_steps i32[N]`` (each may be
         ``None``) in, whichever of ``dof_targets f32[N*R]``, ``actions_clipped f32[N*R]``, ``status i32[N]`` are wanted out."""
-        from . import _lib
         self._need_control("targets_dev")
         N, R = self.num_envs, self.nrobot_dof
         if actions_clipped is not None and actions is None:
@@ -609,16 +589,9 @@ class MotionTracker:
         torque sum is cleared.  Without ``env_ids`` the arrays cover every environment; with it (every environment at most once) they are
         indexed by list position, as the masks of :meth:`reset_done` are.  Returns how many ids of masked entries lay outside
         ``[0, num_envs)``."""
-        from . import _lib
         self._need_control("hold")
-        ids, n = None, self.num_envs
-        if env_ids is not None:
-            ids = np.ascontiguousarray(env_ids, dtype=np.int32).reshape(-1)
-            n = len(ids)
-            if len(np.unique(ids)) != n:
-                raise ValueError("hold: env_ids names an environment twice")
+        n, ids, m = self._subset("hold", env_ids, mask)
         q = self._rows(dof_pos, "dof_pos", n)
-        m = _mask(mask, "mask", n)
         if n == 0:
             return 0
         ignored = C.c_int()
@@ -628,13 +601,12 @@ class MotionTracker:
     def hold_dev(self, dof_pos, mask=None, env_ids=None, n: Optional[int] = None, stream=None) -> None:
         """:meth:`hold` on device memory, asynchronous on ``stream``: ONE launch.  ``dof_pos f32[n*R]``, ``mask i32[n]`` as a step leaves
         it (``finished``) or as :meth:`reset_done_dev` takes it; with ``env_ids`` (``i32[n]``) ``n`` is mandatory."""
-        from . import _lib
         self._need_control("hold_dev")
-        n = self._list_length("hold_dev", env_ids, n)
+        n, p_ids, p_mask = self._subset("hold_dev", env_ids, mask, n, device=True)
         if dof_pos is None:
             raise ValueError("hold_dev: dof_pos is needed")
-        ptrs = (_dev_ptr(env_ids, "env_ids", "int32", n), _dev_ptr(mask, "mask", "int32", n), _dev_ptr(dof_pos, "dof_pos", "float32", n * self.nrobot_dof))
-        _lib.check(_lib.lib().gmr_motion_tracker_hold_dev(self.handle, n, *ptrs, _lib._s(stream)))
+        p_pos = _dev_ptr(dof_pos, "dof_pos", "float32", n * self.nrobot_dof)
+        _lib.check(_lib.lib().gmr_motion_tracker_hold_dev(self.handle, n, p_ids, p_mask, p_pos, _lib._s(stream)))
 
     def _check_substep(self, what: str, substep) -> int:
         _, M = self._need_control(what)
@@ -674,7 +646,6 @@ class MotionTracker:
         dof_pos) - damping * dof_vel``, less ``min(friction, |tau|) * sign(tau)``, clipped to ``torque_limit [R]``.  ``stiffness``,
         ``damping`` and ``friction`` are all ``[N,R]`` (``per_env``) or all ``[R]``; ``per_env=None`` reads it off ``stiffness``.  Returns
         ``dof_torques [N,R]`` and, after the last substep, ``mean_torques``, the mean over the step's substeps.  One launch."""
-        from . import _lib
         i = self._check_substep("torques", substep)
         N, R = self.num_envs, self.nrobot_dof
         tg, q, qd = self._rows(dof_targets, "dof_targets"), self._rows(dof_pos, "dof_pos"), self._rows(dof_vel, "dof_vel")
@@ -693,7 +664,6 @@ class MotionTracker:
         """:meth:`torques` on device memory, asynchronous on ``stream``: ONE launch.  Every array is a ``_lib.DeviceBuffer``, a raw address
         or an object with ``data_ptr()``; ``per_env`` says whether ``stiffness``, ``damping`` and ``friction`` hold ``N*R`` or ``R``
         floats.  ``mean_torques`` is written by the last substep only."""
-        from . import _lib
         i = self._check_substep("torques_dev", substep)
         N, R = self.num_envs, self.nrobot_dof
         for name, x in (("dof_targets", dof_targets), ("dof_pos", dof_pos), ("dof_vel", dof_vel), ("stiffness", stiffness), ("damping", damping),
@@ -714,8 +684,7 @@ class MotionTracker:
     def control_state(self) -> Optional[Dict[str, np.ndarray]]:
         """``held f32[N,R]``, the targets the actuators hold, and ``torque_acc f32[N,R]``, the running torque sum of the current step, or
         ``None`` when control is not set.  Synchronous."""
-        from . import _lib
-        if getattr(self, "_control", None) is None:
+        if self._control is None:
             return None
         self._need_control("control_state")
         out = {"held": np.empty((self.num_envs, self.nrobot_dof), np.float32), "torque_acc": np.empty((self.num_envs, self.nrobot_dof), np.float32)}
@@ -821,7 +790,6 @@ class MotionTracker:
         ``max_episode_steps`` (``ceil(episode_length_s / dt)``) and ``scales``, fourteen numbers or a dict over :data:`PROPRIO_TERMS` that
         weigh ``total`` (zero, the default: the term stays out).  Allocates the six state arrays (zeros).  Synchronous; call it again
         after :meth:`set_dof_map` has changed the number of robot dofs."""
-        from . import _lib
         c = self._proprio_setup(default_dof_pos, dof_pos_limits, dof_vel_limits, torque_limits, extra_cols, filter_weight, normalization, noise,
                                 soft_dof_pos_limit, soft_dof_vel_limit, soft_torque_limit, base_height_target, terminate_vel, terminate_height,
                                 max_episode_steps, scales)
@@ -839,7 +807,7 @@ class MotionTracker:
         self._proprio = (self.nrobot_dof, c["extra_cols"])
 
     def _need_proprio(self, what: str):
-        p = getattr(self, "_proprio", None)
+        p = self._proprio
         if p is None:
             raise ValueError(f"{what}: proprio is not set on this tracker, call set_proprio() first")
         if p[0] != self.nrobot_dof:
@@ -857,10 +825,11 @@ class MotionTracker:
 
     def _proprio_counts(self):
         R, Cx = self._proprio
-        ins = {"root_states": 13, "dof_pos": R, "dof_vel": R, "actions": R, "mean_torques": R, "extra": Cx, "ground": 1, "episode_steps": 1}
-        outs = {"base_lin_vel": 3, "base_ang_vel": 3, "projected_gravity": 3, "filtered_lin_vel": 3, "filtered_ang_vel": 3, "obs": 6 + Cx + 3 * R,
-                "priv": 4, "term": len(PROPRIO_TERMS), "total": 1, "done": 1}
-        return ins, outs
+        return _lib.widths(_lib.PROPRIO_IN, R=R, extra_cols=Cx), _lib.widths(_lib.PROPRIO_OUT, obs_cols=6 + Cx + 3 * R)
+
+    def _proprio_rows(self):
+        R, Cx = self._proprio
+        return self._rows_of(_lib.PROPRIO_IN, R=R, extra_cols=Cx), self._rows_of(_lib.PROPRIO_OUT, obs_cols=6 + Cx + 3 * R)
 
     def _check_extra(self, what: str, extra) -> None:
         if (extra is not None) != (self._proprio[1] > 0):
@@ -878,30 +847,13 @@ class MotionTracker:
         bit 2: time-out).  A term without its input is 0 and stays out of ``total``.  Then ``last_actions`` (with actions),
         ``last_dof_vel`` and ``last_root_vel`` roll over, and with ``noise`` and a noise spec every environment's tick moves by one.
         One launch; clocks, clips and draw counters stay as they are."""
-        from . import _lib
         self._need_proprio("proprio")
         self._check_extra("proprio", extra)
-        N = self.num_envs
-        ins, outs = self._proprio_counts()
+        ins, outs = self._proprio_rows()
         given = {"root_states": root_states, "dof_pos": dof_pos, "dof_vel": dof_vel, "actions": actions, "mean_torques": mean_torques, "extra": extra,
-                 "ground": ground}
-        st, keep = _lib.ProprioIn(), []
-        for k, a in given.items():
-            if a is None:
-                if k in ("root_states", "dof_pos", "dof_vel"):
-                    raise ValueError(f"proprio: {k} is needed")
-                continue
-            a = np.ascontiguousarray(a, dtype=np.float32)
-            shape = (N,) if k == "ground" else (N, ins[k])
-            if a.shape != shape:
-                raise ValueError(f"{k}: shape {a.shape}, {shape} needed")
-            keep.append(a)
-            setattr(st, k, a.ctypes.data)
-        steps = self._per_env_ints(episode_steps, "episode_steps")
-        if steps is not None:
-            st.episode_steps = steps.ctypes.data
-        out = {k: np.empty((N,) if k in ("total", "done") else (N, w), dtype=np.int32 if k == "done" else np.float32) for k, w in outs.items()}
-        table = _lib.ProprioOut(**{k: a.ctypes.data for k, a in out.items()})
+                 "ground": ground, "episode_steps": episode_steps}
+        st, keep = _lib.host_inputs(_lib.ProprioIn, ins, given, "proprio", required=("root_states", "dof_pos", "dof_vel"))
+        table, out = _lib.host_outputs(_lib.ProprioOut, outs)
         _lib.check(_lib.lib().gmr_motion_tracker_proprio(self.handle, C.byref(st), 1 if noise else 0, C.byref(table)))
         return out
 
@@ -909,25 +861,13 @@ class MotionTracker:
                     noise: bool = True, stream=None, **outputs) -> None:
         """:meth:`proprio` on device memory, asynchronous on ``stream``: ONE launch.  ``outputs`` names whichever of the arrays of
         :meth:`proprio` are wanted; every array is a ``_lib.DeviceBuffer``, a raw address or an object with ``data_ptr()``."""
-        from . import _lib
         self._need_proprio("proprio_dev")
         self._check_extra("proprio_dev", extra)
-        N = self.num_envs
-        ins, outs = self._proprio_counts()
-        unknown = sorted(set(outputs) - set(outs))
-        if unknown:
-            raise TypeError(f"proprio_dev: unknown outputs {unknown}")
+        ins, outs = self._proprio_rows()
+        table = _lib.device_struct(_lib.ProprioOut, outs, outputs, "proprio_dev")
         given = {"root_states": root_states, "dof_pos": dof_pos, "dof_vel": dof_vel, "actions": actions, "mean_torques": mean_torques, "extra": extra,
                  "ground": ground, "episode_steps": episode_steps}
-        st, table = _lib.ProprioIn(), _lib.ProprioOut()
-        for k, x in given.items():
-            if x is None and k in ("root_states", "dof_pos", "dof_vel"):
-                raise ValueError(f"proprio_dev: {k} is needed")
-            p = _dev_ptr(x, k, "int32" if k == "episode_steps" else "float32", N * ins[k])
-            setattr(st, k, None if p is None else p.value)
-        for k, x in outputs.items():
-            p = _dev_ptr(x, k, "int32" if k == "done" else "float32", N * outs[k])
-            setattr(table, k, None if p is None else p.value)
+        st = _lib.device_struct(_lib.ProprioIn, ins, given, "proprio_dev", required=("root_states", "dof_pos", "dof_vel"))
         _lib.check(_lib.lib().gmr_motion_tracker_proprio_dev(self.handle, C.byref(st), 1 if noise else 0, C.byref(table), _lib._s(stream)))
 
     def proprio_reset(self, root_states, mask=None, env_ids=None) -> int:
@@ -935,18 +875,11 @@ class MotionTracker:
         root_states[i, 7:13]`` (``root_states [n,13]``); ``last_actions`` and ``last_dof_vel`` stay, as in the reference.  Without
         ``env_ids`` the arrays cover every environment; with it (every environment at most once) they are indexed by list position, as
         the arrays of :meth:`hold` are.  Returns how many ids of masked entries lay outside ``[0, num_envs)``."""
-        from . import _lib
         self._need_proprio("proprio_reset")
-        ids, n = None, self.num_envs
-        if env_ids is not None:
-            ids = np.ascontiguousarray(env_ids, dtype=np.int32).reshape(-1)
-            n = len(ids)
-            if len(np.unique(ids)) != n:
-                raise ValueError("proprio_reset: env_ids names an environment twice")
+        n, ids, m = self._subset("proprio_reset", env_ids, mask)
         rs = np.ascontiguousarray(root_states, dtype=np.float32)
         if rs.shape != (n, 13):
             raise ValueError(f"root_states: shape {rs.shape}, {(n, 13)} needed")
-        m = _mask(mask, "mask", n)
         if n == 0:
             return 0
         ignored = C.c_int()
@@ -956,19 +889,17 @@ class MotionTracker:
     def proprio_reset_dev(self, root_states, mask=None, env_ids=None, n: Optional[int] = None, stream=None) -> None:
         """:meth:`proprio_reset` on device memory, asynchronous on ``stream``: ONE launch.  ``root_states f32[n*13]``, ``mask i32[n]`` as a
         step leaves it (``done``) or as :meth:`reset_done_dev` takes it; with ``env_ids`` (``i32[n]``) ``n`` is mandatory."""
-        from . import _lib
         self._need_proprio("proprio_reset_dev")
-        n = self._list_length("proprio_reset_dev", env_ids, n)
+        n, p_ids, p_mask = self._subset("proprio_reset_dev", env_ids, mask, n, device=True)
         if root_states is None:
             raise ValueError("proprio_reset_dev: root_states is needed")
-        ptrs = (_dev_ptr(env_ids, "env_ids", "int32", n), _dev_ptr(mask, "mask", "int32", n), _dev_ptr(root_states, "root_states", "float32", n * 13))
-        _lib.check(_lib.lib().gmr_motion_tracker_proprio_reset_dev(self.handle, n, *ptrs, _lib._s(stream)))
+        p_roots = _dev_ptr(root_states, "root_states", "float32", n * 13)
+        _lib.check(_lib.lib().gmr_motion_tracker_proprio_reset_dev(self.handle, n, p_ids, p_mask, p_roots, _lib._s(stream)))
 
     def proprio_state(self) -> Optional[Dict[str, np.ndarray]]:
         """``filtered_lin_vel``, ``filtered_ang_vel`` ``f32[N,3]``, ``last_root_vel f32[N,6]``, ``last_actions``, ``last_dof_vel``
         ``f32[N,R]`` and ``noise_tick u32[N]``, or ``None`` when proprio is not set.  Synchronous."""
-        from . import _lib
-        if getattr(self, "_proprio", None) is None:
+        if self._proprio is None:
             return None
         self._need_proprio("proprio_state")
         N, R = self.num_envs, self.nrobot_dof
@@ -1005,7 +936,6 @@ class MotionTracker:
         """The terrain the heights are taken from: ``height_field int16 [nx, ny]`` (the first index is x, the reference's
         ``height_field_raw``) with its ``horizontal_scale``, ``vertical_scale`` and ``border_pixels``, or ``None`` for the plane of height
         0 (the state of a new tracker).  Synchronous: launches in flight keep the field they were given."""
-        from . import _lib
         field, hs, vs, b = self._terrain_setup(height_field, horizontal_scale, vertical_scale, border_pixels)
         nx, ny = (0, 0) if field is None else field.shape
         _lib.check(_lib.lib().gmr_motion_tracker_set_terrain(self.handle, _lib._ptr(field), nx, ny, hs, vs, b))
@@ -1014,7 +944,6 @@ class MotionTracker:
         """``Terrain.terrain_heights`` of the reference without its host round trip: ``points [M, k]``, k >= 2 (x and y lead) ->
         ``(heights f32[M], outside)``, the reference's bits inside the field.  A point whose cell leaves the field is clamped to it and
         counted in ``outside``; a coordinate that is not finite gives NaN and is counted too.  One launch."""
-        from . import _lib
         p = np.ascontiguousarray(points, dtype=np.float32)
         if p.ndim != 2 or p.shape[1] < 2:
             raise ValueError(f"points: shape {p.shape}, (M, k) with k >= 2 needed")
@@ -1027,7 +956,6 @@ class MotionTracker:
         """:meth:`terrain_heights` on device memory, asynchronous on ``stream``: ONE launch.  Point ``i`` is ``points[i * stride]`` and
         the float behind it (``stride`` >= 2 floats: 3 for packed positions, 13 for root states); ``heights f32[n]``; the points outside
         the field are ADDED to ``outside i32[1]``, which the caller has zeroed."""
-        from . import _lib
         n, stride = int(n), int(stride)
         if n < 0:
             raise ValueError(f"terrain_heights_dev: n = {n}")
@@ -1097,7 +1025,6 @@ class MotionTracker:
         episode and those it is penalised on (0 to 64 each, distinct), the force threshold and the contact clearance (the reference's 1.0
         and 0.01), ``feet_distance_ref``, ``swing_period`` and ``scales``, eight numbers or a dict over :data:`FEET_TERMS` that weigh
         ``total`` (zero, the default: the term stays out).  Allocates ``last_feet_pos`` and ``gait_process`` (zeros).  Synchronous."""
-        from . import _lib
         c = self._feet_setup(feet_bodies, edge_pos, num_bodies, termination_bodies, penalized_bodies, force_threshold, contact_clearance,
                              feet_distance_ref, swing_period, scales)
         cfg = _lib.FeetConfig()
@@ -1113,27 +1040,22 @@ class MotionTracker:
         self._feet = (c["num_bodies"], len(c["edge_pos"]))
 
     def _need_feet(self, what: str):
-        f = getattr(self, "_feet", None)
+        f = self._feet
         if f is None:
             raise ValueError(f"{what}: the feet are not set on this tracker, call set_feet() first")
         return f
 
     def _feet_counts(self):
-        nb = self._feet[0]
-        ins = {"contact_forces": nb * 3, "root_states": 13, "episode_steps": 1, "gait_frequency": 1}
-        outs = {"feet_pos": 6, "feet_roll": 2, "feet_yaw": 2, "feet_contact": 2, "ground": 1, "gait": 2, "term": len(FEET_TERMS), "total": 1, "done": 1}
-        return ins, outs
+        return _lib.widths(_lib.FEET_IN, nb=self._feet[0]), _lib.widths(_lib.FEET_OUT)
 
     @staticmethod
     def _feet_bodies(what: str, bodies):
-        """``bodies`` of a feet call -> ``("packed", array) | ("separate", pos, rot)``"""
+        """``bodies`` of a feet call, checked: the packed tensor alone, or ``body_pos`` with ``body_rot``"""
         if not isinstance(bodies, dict):
             raise TypeError(f"{what}: bodies is {{'body_state': [N, nb, 13]}} or {{'body_pos': [N, nb, 3], 'body_rot': [N, nb, 4]}}")
-        if set(bodies) == {"body_state"} and bodies["body_state"] is not None:
-            return ("packed", bodies["body_state"])
-        if set(bodies) == {"body_pos", "body_rot"} and bodies["body_pos"] is not None and bodies["body_rot"] is not None:
-            return ("separate", bodies["body_pos"], bodies["body_rot"])
-        raise TypeError(f"{what}: bodies is either {{'body_state': ..}} or {{'body_pos': .., 'body_rot': ..}}, got {sorted(bodies)}")
+        if set(bodies) not in ({"body_state"}, {"body_pos", "body_rot"}) or any(a is None for a in bodies.values()):
+            raise TypeError(f"{what}: bodies is either {{'body_state': ..}} or {{'body_pos': .., 'body_rot': ..}}, got {sorted(bodies)}")
+        return bodies
 
     def feet(self, bodies, root_states, contact_forces=None, episode_steps=None, gait_frequency=None) -> Dict[str, np.ndarray]:
         """The feet half of a step, host arrays in and out: from ``bodies`` -- the simulator's rigid bodies as ``{"body_state": [N, nb,
@@ -1144,42 +1066,11 @@ class MotionTracker:
         :data:`FEET_TERMS`, ``total [N]`` and ``done i32[N]`` (:data:`FEET_DONE_CONTACT` where a termination body is in contact).
         Without ``contact_forces`` ``collision`` is 0 and stays out of ``total``, and ``done`` is 0.  Then ``last_feet_pos`` rolls over
         and the gait clock has moved.  One launch; clocks, clips and draw counters stay as they are."""
-        from . import _lib
         nb, _ = self._need_feet("feet")
-        N = self.num_envs
-        kind = self._feet_bodies("feet", bodies)
-        ls, keep = _lib.TrackerLinksSim(), []
-        if kind[0] == "packed":
-            a = np.ascontiguousarray(kind[1], dtype=np.float32)
-            if a.shape != (N, nb, 13):
-                raise ValueError(f"body_state: shape {a.shape}, {(N, nb, 13)} needed")
-            keep.append(a)
-            ls.body_pos, ls.body_rot, ls.env_stride, ls.body_stride = a.ctypes.data, a.ctypes.data + 12, 13 * nb, 13
-        else:
-            for k, a, w in (("body_pos", kind[1], 3), ("body_rot", kind[2], 4)):
-                a = np.ascontiguousarray(a, dtype=np.float32)
-                if a.shape != (N, nb, w):
-                    raise ValueError(f"{k}: shape {a.shape}, {(N, nb, w)} needed")
-                keep.append(a)
-                setattr(ls, k, a.ctypes.data)
-        st = _lib.FeetIn()
-        if root_states is None:
-            raise ValueError("feet: root_states is needed")
-        for k, a, shape in (("root_states", root_states, (N, 13)), ("contact_forces", contact_forces, (N, nb, 3)), ("gait_frequency", gait_frequency, (N,))):
-            if a is None:
-                continue
-            a = np.ascontiguousarray(a, dtype=np.float32)
-            if a.shape != shape:
-                raise ValueError(f"{k}: shape {a.shape}, {shape} needed")
-            keep.append(a)
-            setattr(st, k, a.ctypes.data)
-        steps = self._per_env_ints(episode_steps, "episode_steps")
-        if steps is not None:
-            st.episode_steps = steps.ctypes.data
-        _, outs = self._feet_counts()
-        shapes = {"feet_pos": (N, 2, 3), "ground": (N,), "total": (N,), "done": (N,)}
-        out = {k: np.empty(shapes.get(k, (N, w)), dtype=np.int32 if k in ("done", "feet_contact") else np.float32) for k, w in outs.items()}
-        table = _lib.FeetOut(**{k: a.ctypes.data for k, a in out.items()})
+        ls, keep = self._bodies(self._feet_bodies("feet", bodies), ("body_pos", "body_rot"), nb, nb)
+        given = {"root_states": root_states, "contact_forces": contact_forces, "gait_frequency": gait_frequency, "episode_steps": episode_steps}
+        st, held = _lib.host_inputs(_lib.FeetIn, self._rows_of(_lib.FEET_IN, nb=nb), given, "feet", required=("root_states",))
+        table, out = _lib.host_outputs(_lib.FeetOut, self._rows_of(_lib.FEET_OUT))
         _lib.check(_lib.lib().gmr_motion_tracker_feet(self.handle, C.byref(ls), C.byref(st), C.byref(table)))
         return out
 
@@ -1188,36 +1079,17 @@ class MotionTracker:
         ``[N, nb, 13]`` tensor or ``{"body_pos": array, "body_rot": array}``; ``outputs`` names whichever of the arrays of :meth:`feet`
         are wanted (``ground`` goes into :meth:`proprio_dev` as it lies, ``gait`` into its ``extra`` columns); every array is a
         ``_lib.DeviceBuffer``, a raw address or an object with ``data_ptr()``."""
-        from . import _lib
         nb, _ = self._need_feet("feet_dev")
-        N = self.num_envs
-        kind = self._feet_bodies("feet_dev", bodies)
-        ins, outs = self._feet_counts()
-        unknown = sorted(set(outputs) - set(outs))
-        if unknown:
-            raise TypeError(f"feet_dev: unknown outputs {unknown}")
-        ls = _lib.TrackerLinksSim()
-        if kind[0] == "packed":
-            p = _dev_ptr(kind[1], "body_state", "float32", N * nb * 13)
-            ls.body_pos, ls.body_rot, ls.env_stride, ls.body_stride = p.value, p.value + 12, 13 * nb, 13
-        else:
-            ls.body_pos = _dev_ptr(kind[1], "body_pos", "float32", N * nb * 3).value
-            ls.body_rot = _dev_ptr(kind[2], "body_rot", "float32", N * nb * 4).value
-        if root_states is None:
-            raise ValueError("feet_dev: root_states is needed")
-        st, table = _lib.FeetIn(), _lib.FeetOut()
-        for k, x in (("root_states", root_states), ("contact_forces", contact_forces), ("episode_steps", episode_steps), ("gait_frequency", gait_frequency)):
-            p = _dev_ptr(x, k, "int32" if k == "episode_steps" else "float32", N * ins[k])
-            setattr(st, k, None if p is None else p.value)
-        for k, x in outputs.items():
-            p = _dev_ptr(x, k, "int32" if k in ("done", "feet_contact") else "float32", N * outs[k])
-            setattr(table, k, None if p is None else p.value)
+        bodies = self._feet_bodies("feet_dev", bodies)
+        table = _lib.device_struct(_lib.FeetOut, self._rows_of(_lib.FEET_OUT), outputs, "feet_dev")
+        ls, _ = self._bodies(bodies, ("body_pos", "body_rot"), nb, nb, device=True)
+        given = {"root_states": root_states, "contact_forces": contact_forces, "episode_steps": episode_steps, "gait_frequency": gait_frequency}
+        st = _lib.device_struct(_lib.FeetIn, self._rows_of(_lib.FEET_IN, nb=nb), given, "feet_dev", required=("root_states",))
         _lib.check(_lib.lib().gmr_motion_tracker_feet_dev(self.handle, C.byref(ls), C.byref(st), C.byref(table), _lib._s(stream)))
 
     def feet_state(self) -> Optional[Dict[str, np.ndarray]]:
         """``last_feet_pos f32[N,2,3]`` and ``gait_process f32[N]``, or ``None`` when the feet are not set.  Synchronous."""
-        from . import _lib
-        if getattr(self, "_feet", None) is None:
+        if self._feet is None:
             return None
         N = self.num_envs
         out = {"last_feet_pos": np.empty((N, 2, 3), np.float32), "gait_process": np.empty(N, np.float32)}
@@ -1315,13 +1187,12 @@ class MotionTracker:
         ``index_order`` -- ``"grid"`` (default) or ``"reference"``, the reference's transposed split of a drawn cell, only for equal level
         counts.  Allocates the state (zeros; the centre cell of ``curriculum_prob`` is 1).  With ``keep_state`` only the configuration is
         replaced -- calls already enqueued keep theirs --, and the curriculum's presence and level counts must stay.  Synchronous."""
-        from . import _lib
         c = self._commands_setup(lin_vel_x, lin_vel_y, ang_vel_yaw, gait_frequency, resample_steps, still_proportion, tracking_sigma, scales,
                                  obs_scales, curriculum)
         cur = c["curriculum"]
         shape = None if cur is None else (cur["L"], cur["A"])
         if keep_state:
-            old = getattr(self, "_commands", None)
+            old = self._commands
             if old is None:
                 raise ValueError("set_commands: keep_state needs commands that were set before")
             if old != (shape,):
@@ -1341,7 +1212,7 @@ class MotionTracker:
         self._commands = (shape,)
 
     def _need_commands(self, what: str):
-        c = getattr(self, "_commands", None)
+        c = self._commands
         if c is None:
             raise ValueError(f"{what}: commands are not set on this tracker, call set_commands() first")
         return c[0]
@@ -1355,29 +1226,19 @@ class MotionTracker:
         i32[N]`` (:data:`CMD_BOUNDARY`: OR it into the time-outs, :data:`CMD_RESAMPLED`, :data:`CMD_SUCCESS`).  ``cmd_obs`` is a host array
         ``[N,W]``, ``W >= 3``, or a pair ``(array, column)``: its three columns from ``column`` on get ``commands * obs_scales``, in place.
         One launch, three with a curriculum; clocks, clips and draw counters of the tracker stay as they are."""
-        from . import _lib
         shape = self._need_commands("commands")
         N = self.num_envs
-        steps = self._per_env_ints(episode_steps, "episode_steps")
-        if steps is None:
+        if episode_steps is None:
             raise ValueError("commands: episode_steps is needed")
-        st, keep = _lib.CommandsIn(episode_steps=steps.ctypes.data), [steps]
-        m = _mask(done, "done", N)
+        ins = self._rows_of(_lib.CMD_IN)
+        st, keep = _lib.host_inputs(_lib.CommandsIn, ins, {"episode_steps": episode_steps})
+        m = _mask(done, "done", N)              # a mask may be bool: it goes in as 0 / 1
         if m is not None:
             st.done = m.ctypes.data
         if shape is not None and (lin_vel is None or ang_vel is None):
             raise ValueError("commands: the curriculum needs lin_vel and ang_vel (the filtered velocities)")
-        for k, a in (("lin_vel", lin_vel), ("ang_vel", ang_vel)):
-            if a is None:
-                continue
-            a = np.ascontiguousarray(a, dtype=np.float32)
-            if a.shape != (N, 3):
-                raise ValueError(f"{k}: shape {a.shape}, {(N, 3)} needed")
-            keep.append(a)
-            setattr(st, k, a.ctypes.data)
-        out = {"term": np.empty((N, len(CMD_TERMS)), np.float32), "total": np.empty(N, np.float32), "commands": np.empty((N, 3), np.float32),
-               "gait_frequency": np.empty(N, np.float32), "flags": np.empty(N, np.int32)}
-        table = _lib.CommandsOut(**{k: a.ctypes.data for k, a in out.items()})
+        st, held = _lib.host_inputs(st, ins, {"lin_vel": lin_vel, "ang_vel": ang_vel})
+        table, out = _lib.host_outputs(_lib.CommandsOut, self._rows_of(_lib.CMD_OUT), skip=("cmd_obs",))
         if cmd_obs is not None:
             rows, col = cmd_obs if isinstance(cmd_obs, tuple) else (cmd_obs, 0)
             if not (isinstance(rows, np.ndarray) and rows.dtype == np.float32 and rows.flags.c_contiguous and rows.flags.writeable and rows.ndim == 2
@@ -1395,25 +1256,15 @@ class MotionTracker:
         ``outputs`` names whichever of ``term, total, commands, gait_frequency, flags`` are wanted; ``cmd_obs`` is the address of the
         first command column of environment 0 (``obs + 6`` floats of the row of :meth:`proprio_dev`) and ``cmd_obs_stride`` the row's
         width in floats.  Every array is a ``_lib.DeviceBuffer``, a raw address or an object with ``data_ptr()``."""
-        from . import _lib
         shape = self._need_commands("commands_dev")
         N = self.num_envs
-        outs = {"term": len(CMD_TERMS), "total": 1, "commands": 3, "gait_frequency": 1, "flags": 1}
-        unknown = sorted(set(outputs) - set(outs))
-        if unknown:
-            raise TypeError(f"commands_dev: unknown outputs {unknown}")
+        table = _lib.device_struct(_lib.CommandsOut, self._rows_of(_lib.CMD_OUT), outputs, "commands_dev")
         if episode_steps is None:
             raise ValueError("commands_dev: episode_steps is needed")
         if shape is not None and (lin_vel is None or ang_vel is None):
             raise ValueError("commands_dev: the curriculum needs lin_vel and ang_vel (the filtered velocities)")
-        st, table = _lib.CommandsIn(), _lib.CommandsOut()
-        for k, x, dt, w in (("episode_steps", episode_steps, "int32", 1), ("done", done, "int32", 1), ("lin_vel", lin_vel, "float32", 3),
-                            ("ang_vel", ang_vel, "float32", 3)):
-            p = _dev_ptr(x, k, dt, N * w)
-            setattr(st, k, None if p is None else p.value)
-        for k, x in outputs.items():
-            p = _dev_ptr(x, k, "int32" if k == "flags" else "float32", N * outs[k])
-            setattr(table, k, None if p is None else p.value)
+        given = {"episode_steps": episode_steps, "done": done, "lin_vel": lin_vel, "ang_vel": ang_vel}
+        st = _lib.device_struct(_lib.CommandsIn, self._rows_of(_lib.CMD_IN), given)
         if cmd_obs is not None:
             if int(cmd_obs_stride) != cmd_obs_stride or cmd_obs_stride < 3:
                 raise ValueError(f"commands_dev: cmd_obs_stride = {cmd_obs_stride}, at least 3 floats needed")
@@ -1426,8 +1277,7 @@ class MotionTracker:
         ``env_level i32[N,2]``, ``curriculum_prob f32[2L+1,2A+1]``, ``hits u32[G]``, ``cum f64[G+1]`` and -- formed here from ``env_level``
         -- ``mean_lin_vel_level``, ``mean_ang_vel_level``, ``max_lin_vel_level``, ``max_ang_vel_level`` (t1.py:421-424); ``None`` when the
         commands are not set.  Synchronous."""
-        from . import _lib
-        if getattr(self, "_commands", None) is None:
+        if self._commands is None:
             return None
         shape = self._need_commands("command_state")
         N = self.num_envs
@@ -1494,7 +1344,6 @@ class MotionTracker:
                          push_torque=None, scale_push_force: float = 1.0, scale_push_torque: float = 1.0) -> None:
         """Configures kicks and pushes: the three periods in steps (``ceil(seconds / dt)``), four specs in the form of the ``noise`` of
         :meth:`set_proprio` (``None``: the block is left alone) and the two privileged-observation scales.  Keeps no device state."""
-        from . import _lib
         c = self._disturb_setup(kick_lin_vel, kick_ang_vel, push_force, push_torque, kick_every, push_every, push_duration, scale_push_force,
                                 scale_push_torque)
         cfg = _lib.DisturbConfig()
@@ -1507,7 +1356,7 @@ class MotionTracker:
         self._disturb = c["periods"]
 
     def _need_disturb(self, what: str, common_step):
-        if getattr(self, "_disturb", None) is None:
+        if self._disturb is None:
             raise ValueError(f"{what}: disturbances are not set on this tracker, call set_disturbances() first")
         if int(common_step) != common_step or not 0 <= common_step < 2 ** 32:
             raise ValueError(f"{what}: common_step = {common_step}, a step count in [0, 2^32) is needed")
@@ -1517,15 +1366,13 @@ class MotionTracker:
         """Kicks and pushes at ``common_step``, host arrays: ``actions`` (the bits of :meth:`disturb_actions`), ``root_states [N,13]`` (a
         copy, columns 7 to 12 kicked on a kick step) and, on a step that starts or stops a push, ``push_force``, ``push_torque`` ``[N,3]``
         and ``push_obs [N,6]`` (zeros at a stop; ``None`` on other steps).  One launch, none on an idle step."""
-        from . import _lib
         step = self._need_disturb("disturb", common_step)
-        N = self.num_envs
+        rows = self._rows_of(_lib.DISTURB_IO)
         rs = np.array(root_states, dtype=np.float32, order="C")
-        if rs.shape != (N, 13):
-            raise ValueError(f"root_states: shape {rs.shape}, {(N, 13)} needed")
-        out = {"push_force": np.zeros((N, 3), np.float32), "push_torque": np.zeros((N, 3), np.float32), "push_obs": np.zeros((N, 6), np.float32)}
-        io = _lib.DisturbIo(root_states=rs.ctypes.data, push_force=out["push_force"].ctypes.data, push_torque=out["push_torque"].ctypes.data,
-                            push_force_stride=3, push_torque_stride=3, push_obs=out["push_obs"].ctypes.data)
+        if rs.shape != rows["root_states"][1]:
+            raise ValueError(f"root_states: shape {rs.shape}, {rows['root_states'][1]} needed")
+        out = {k: np.zeros(rows[k][1], np.float32) for k in ("push_force", "push_torque", "push_obs")}
+        io = _lib.DisturbIo(root_states=rs.ctypes.data, push_force_stride=3, push_torque_stride=3, **{k: a.ctypes.data for k, a in out.items()})
         act = _lib.lib().gmr_motion_tracker_disturb(self.handle, step, C.byref(io))
         if act < 0:
             _lib.check(act)
@@ -1540,13 +1387,9 @@ class MotionTracker:
         3`` floats) with the environment's row stride in floats (``num_bodies * 3``), so the push lands in the simulator's ``[N, nb, 3]``
         tensors; ``push_obs f32[N*6]``.  Returns the bits of :meth:`disturb_actions`: with :data:`DISTURB_KICK` hand ``root_states`` back
         to the simulator."""
-        from . import _lib
         step = self._need_disturb("disturb_dev", common_step)
         N = self.num_envs
-        io = _lib.DisturbIo()
-        for k, x, count in (("root_states", root_states, N * 13), ("push_obs", push_obs, N * 6)):
-            p = _dev_ptr(x, k, "float32", count)
-            setattr(io, k, None if p is None else p.value)
+        io = _lib.device_struct(_lib.DisturbIo, self._rows_of(_lib.DISTURB_IO), {"root_states": root_states, "push_obs": push_obs})
         for k, x, stride in (("push_force", push_force, push_force_stride), ("push_torque", push_torque, push_torque_stride)):
             if x is None:
                 continue
@@ -1628,7 +1471,6 @@ class MotionTracker:
         (``None``: no draw for that block), ``yaw_range (lower, upper)`` (``None``: no yaw draw, the row's quaternion stays), ``decimation``
         -- ``delay_steps`` is drawn below it, 0: no draw -- and ``use_terrain`` (the height of :meth:`set_terrain` under the drawn point is
         added to ``z``).  Allocates ``reset_draws`` (zeros).  Synchronous."""
-        from . import _lib
         c = self._reset_setup(base_init_state, default_dof_pos, env_origins, init_dof_pos, init_base_pos_xy, init_base_lin_vel_xy, yaw_range,
                               decimation, use_terrain)
         cfg = _lib.ResetConfig()
@@ -1646,7 +1488,7 @@ class MotionTracker:
         self._resets = (self.nrobot_dof, c["decimation"])
 
     def _need_resets(self, what: str):
-        r = getattr(self, "_resets", None)
+        r = self._resets
         if r is None:
             raise ValueError(f"{what}: reset states are not set on this tracker, call set_reset_states() first")
         if r[0] != self.nrobot_dof:
@@ -1664,33 +1506,18 @@ class MotionTracker:
         [n,13]``, ``init_dof_pos``, ``init_dof_vel`` ``[n,R]`` take the place of ``base_init_state``, ``default_dof_pos`` and the zero
         velocity of that entry -- the rows of ``step_links(advance=False)`` can be fed in.  With ``chain`` the same launch also does what
         :meth:`hold` and :meth:`proprio_reset` would do afterwards, for the halves that are configured.  One launch."""
-        from . import _lib
         self._need_resets("reset_states")
-        N, R = self.num_envs, self.nrobot_dof
-        ids, n = None, N
-        if env_ids is not None:
-            ids = np.ascontiguousarray(env_ids, dtype=np.int32).reshape(-1)
-            n = len(ids)
-            if len(np.unique(ids)) != n:
-                raise ValueError("reset_states: env_ids names an environment twice")
+        n, ids, m = self._subset("reset_states", env_ids, mask)
+        rows = _lib.resolve(_lib.RESET_IO, N=self.num_envs, n=n, R=self.nrobot_dof)
         rs = np.array(root_states, dtype=np.float32, order="C")
-        if rs.shape != (N, 13):
-            raise ValueError(f"root_states: shape {rs.shape}, {(N, 13)} needed")
+        if rs.shape != rows["root_states"][1]:
+            raise ValueError(f"root_states: shape {rs.shape}, {rows['root_states'][1]} needed")
         out = {"root_states": rs, "dof_pos": self._rows(dof_pos, "dof_pos").copy(), "dof_vel": self._rows(dof_vel, "dof_vel").copy()}
         for k, a in (("delay_steps", delay_steps), ("episode_steps", episode_steps)):
             if a is not None:
                 out[k] = self._per_env_ints(a, k).copy()
-        io = _lib.ResetIo(**{k: a.ctypes.data for k, a in out.items()})
-        keep = []
-        for k, a, w in (("init_root_states", init_root_states, 13), ("init_dof_pos", init_dof_pos, R), ("init_dof_vel", init_dof_vel, R)):
-            if a is None:
-                continue
-            a = np.ascontiguousarray(a, dtype=np.float32)
-            if a.shape != (n, w):
-                raise ValueError(f"{k}: shape {a.shape}, {(n, w)} needed")
-            keep.append(a)
-            setattr(io, k, a.ctypes.data)
-        m = _mask(mask, "mask", n)
+        io = _lib.ResetIo(**{k: a.ctypes.data for k, a in out.items()})               # copies: the caller's arrays stay as they are
+        io, keep = _lib.host_inputs(io, rows, {"init_root_states": init_root_states, "init_dof_pos": init_dof_pos, "init_dof_vel": init_dof_vel})
         ignored = C.c_int()
         if n > 0:
             _lib.check(_lib.lib().gmr_motion_tracker_reset_states(self.handle, n, _lib._ptr(ids), _lib._ptr(m), C.byref(io), 1 if chain else 0,
@@ -1704,26 +1531,18 @@ class MotionTracker:
         ``root_states f32[N*13]``, ``dof_pos`` / ``dof_vel f32[N*R]``, ``delay_steps`` / ``episode_steps i32[N]`` are the simulator's own
         arrays, written in place in the rows of served entries; ``mask i32[n]`` as a step leaves it (``reset`` of :meth:`rewards_dev`); the
         ``init_*`` rows by list position; with ``env_ids`` (``i32[n]``) ``n`` is mandatory."""
-        from . import _lib
         self._need_resets("reset_states_dev")
-        N, R = self.num_envs, self.nrobot_dof
-        n = self._list_length("reset_states_dev", env_ids, n)
+        n, p_ids, p_mask = self._subset("reset_states_dev", env_ids, mask, n, device=True)
         if root_states is None or dof_pos is None or dof_vel is None:
             raise ValueError("reset_states_dev: root_states, dof_pos and dof_vel are needed")
-        io = _lib.ResetIo()
-        for k, x, dt, count in (("root_states", root_states, "float32", N * 13), ("dof_pos", dof_pos, "float32", N * R),
-                                ("dof_vel", dof_vel, "float32", N * R), ("delay_steps", delay_steps, "int32", N),
-                                ("episode_steps", episode_steps, "int32", N), ("init_root_states", init_root_states, "float32", n * 13),
-                                ("init_dof_pos", init_dof_pos, "float32", n * R), ("init_dof_vel", init_dof_vel, "float32", n * R)):
-            p = _dev_ptr(x, k, dt, count)
-            setattr(io, k, None if p is None else p.value)
-        p_ids, p_mask = _dev_ptr(env_ids, "env_ids", "int32", n), _dev_ptr(mask, "mask", "int32", n)
+        given = {"root_states": root_states, "dof_pos": dof_pos, "dof_vel": dof_vel, "delay_steps": delay_steps, "episode_steps": episode_steps,
+                 "init_root_states": init_root_states, "init_dof_pos": init_dof_pos, "init_dof_vel": init_dof_vel}
+        io = _lib.device_struct(_lib.ResetIo, _lib.resolve(_lib.RESET_IO, N=self.num_envs, n=n, R=self.nrobot_dof), given)
         _lib.check(_lib.lib().gmr_motion_tracker_reset_states_dev(self.handle, n, p_ids, p_mask, C.byref(io), 1 if chain else 0, _lib._s(stream)))
 
     def reset_state(self) -> Optional[Dict[str, np.ndarray]]:
         """``reset_draws u32[N]``: the resets drawn for every environment so far; ``None`` when the reset states are not set.  Synchronous."""
-        from . import _lib
-        if getattr(self, "_resets", None) is None:
+        if self._resets is None:
             return None
         out = {"reset_draws": np.empty(self.num_envs, np.uint32)}
         _lib.check(_lib.lib().gmr_motion_tracker_reset_state(self.handle, _lib._ptr(out["reset_draws"])))
@@ -1732,13 +1551,13 @@ class MotionTracker:
     def _reward_blocks(self):
         """the blocks configured on this tracker, in column order -> [(block, names)]"""
         blocks = [("terms", TERMS)]
-        if getattr(self, "_links", None) is not None:
+        if self._links is not None:
             blocks.append(("links", LINK_TERMS))
-        if getattr(self, "_proprio", None) is not None:
+        if self._proprio is not None:
             blocks.append(("proprio", PROPRIO_TERMS))
-        if getattr(self, "_feet", None) is not None:
+        if self._feet is not None:
             blocks.append(("feet", FEET_TERMS))
-        if getattr(self, "_commands", None) is not None:
+        if self._commands is not None:
             blocks.append(("commands", CMD_TERMS))
         return blocks
 
@@ -1793,7 +1612,6 @@ class MotionTracker:
         :data:`REWARD_IMITATION`; by default the tracking terms feed the imitation group and everything else locomotion; 3 counts a column
         in both, which is the reference's double count.  ``group_weight (locomotion, imitation)``, ``only_positive`` a pair of flags.
         ``stats``: keep the Recorder's episode statistics (allocates and zeroes their state).  Returns :meth:`reward_layout`.  Synchronous."""
-        from . import _lib
         c = self._rewards_setup(extra_names, extra_weights, groups, group_weight, only_positive, stats)
         cfg = _lib.RewardConfig()
         cfg.group_weight[:] = c["group_weight"].tolist()
@@ -1809,7 +1627,7 @@ class MotionTracker:
         return self.reward_layout()
 
     def _need_rewards(self, what: str, stats: bool = False):
-        c = getattr(self, "_rewards", None)
+        c = self._rewards
         if c is None:
             raise ValueError(f"{what}: rewards are not set on this tracker, call set_rewards() first")
         if [b for b, _ in c["blocks"]] != [b for b, _ in self._reward_blocks()]:
@@ -1821,7 +1639,7 @@ class MotionTracker:
     def reward_layout(self) -> Optional[Dict[str, object]]:
         """``names``: the columns in order; ``blocks``: ``{block: (first column, count)}`` (``extra`` among them); ``groups``; ``num_cols``;
         ``None`` when the rewards are not set"""
-        c = getattr(self, "_rewards", None)
+        c = self._rewards
         if c is None:
             return None
         blocks, at = {}, 0
@@ -1831,8 +1649,16 @@ class MotionTracker:
         blocks["extra"] = (at, c["E"])
         return {"names": tuple(c["names"]), "blocks": blocks, "groups": tuple(c["groups"]), "num_cols": len(c["names"])}
 
-    _REWARD_INPUTS = (("term", "terms", len(TERMS)), ("link_term", "links", len(LINK_TERMS)), ("proprio_term", "proprio", len(PROPRIO_TERMS)),
-                      ("feet_term", "feet", len(FEET_TERMS)), ("cmd_term", "commands", len(CMD_TERMS)))
+    _REWARD_INPUTS = {"term": "terms", "link_term": "links", "proprio_term": "proprio", "feet_term": "feet", "cmd_term": "commands"}    # input: its block
+
+    def _reward_io(self, what: str, given):
+        """the checks of a reward call that need no device -> the rows of its two tables"""
+        c = self._need_rewards(what)
+        have = {b for b, _ in c["blocks"]}
+        for k, b in self._REWARD_INPUTS.items():
+            if given[k] is not None and b not in have:
+                raise ValueError(f"{what}: {k} given, but the block {b!r} is not configured on this tracker")
+        return self._rows_of(_lib.REWARD_IN, E=c["E"]), self._rows_of(_lib.REWARD_OUT, C=len(c["names"]))
 
     def rewards(self, term=None, link_term=None, proprio_term=None, feet_term=None, cmd_term=None, extra=None, done=None,
                 flags=None) -> Dict[str, np.ndarray]:
@@ -1841,31 +1667,10 @@ class MotionTracker:
         :meth:`feet`) and the ``flags`` of :meth:`commands` -- ``reward [N]``, ``scaled [N,C]`` (weight times term, what the reference puts
         into ``extras["rew_terms"]``), ``group_total [N,2]``, ``reset i32[N] = done != 0`` and ``time_outs i32[N] = ((done & 4) | (flags &
         CMD_BOUNDARY)) != 0``.  With ``stats`` the episode sums move on.  One launch, two with the statistics."""
-        from . import _lib
-        c = self._need_rewards("rewards")
-        N, Cn = self.num_envs, len(c["names"])
-        have = {b for b, _ in c["blocks"]}
-        given = dict(term=term, link_term=link_term, proprio_term=proprio_term, feet_term=feet_term, cmd_term=cmd_term)
-        st, keep = _lib.RewardIn(), []
-        for k, b, w in self._REWARD_INPUTS + (("extra", "extra", c["E"]),):
-            a = extra if k == "extra" else given[k]
-            if a is None:
-                continue
-            if b != "extra" and b not in have:
-                raise ValueError(f"rewards: {k} given, but the block {b!r} is not configured on this tracker")
-            a = np.ascontiguousarray(a, dtype=np.float32)
-            if a.shape != (N, w):
-                raise ValueError(f"{k}: shape {a.shape}, {(N, w)} needed")
-            keep.append(a)
-            setattr(st, k, a.ctypes.data)
-        for k, a in (("done", done), ("flags", flags)):
-            a = self._per_env_ints(a, k)
-            if a is not None:
-                keep.append(a)
-                setattr(st, k, a.ctypes.data)
-        out = {"reward": np.empty(N, np.float32), "scaled": np.empty((N, Cn), np.float32), "group_total": np.empty((N, 2), np.float32),
-               "reset": np.empty(N, np.int32), "time_outs": np.empty(N, np.int32)}
-        table = _lib.RewardOut(**{k: a.ctypes.data for k, a in out.items()})
+        given = dict(term=term, link_term=link_term, proprio_term=proprio_term, feet_term=feet_term, cmd_term=cmd_term, extra=extra, done=done, flags=flags)
+        ins, outs = self._reward_io("rewards", given)
+        st, keep = _lib.host_inputs(_lib.RewardIn, ins, given)
+        table, out = _lib.host_outputs(_lib.RewardOut, outs)
         _lib.check(_lib.lib().gmr_motion_tracker_rewards(self.handle, C.byref(st), C.byref(table)))
         return out
 
@@ -1874,33 +1679,15 @@ class MotionTracker:
         """:meth:`rewards` on device memory, asynchronous on ``stream``: ONE launch, TWO with the statistics, no host synchronisation.
         ``outputs`` names whichever of ``reward, scaled, group_total, reset, time_outs`` are wanted.  Every array is a
         ``_lib.DeviceBuffer``, a raw address or an object with ``data_ptr()``."""
-        from . import _lib
-        c = self._need_rewards("rewards_dev")
-        N, Cn = self.num_envs, len(c["names"])
-        outs = {"reward": 1, "scaled": Cn, "group_total": 2, "reset": 1, "time_outs": 1}
-        unknown = sorted(set(outputs) - set(outs))
-        if unknown:
-            raise TypeError(f"rewards_dev: unknown outputs {unknown}")
-        have = {b for b, _ in c["blocks"]}
-        given = dict(term=term, link_term=link_term, proprio_term=proprio_term, feet_term=feet_term, cmd_term=cmd_term)
-        st, table = _lib.RewardIn(), _lib.RewardOut()
-        for k, b, w in self._REWARD_INPUTS:
-            if given[k] is not None and b not in have:
-                raise ValueError(f"rewards_dev: {k} given, but the block {b!r} is not configured on this tracker")
-            p = _dev_ptr(given[k], k, "float32", N * w)
-            setattr(st, k, None if p is None else p.value)
-        for k, x, dt, w in (("extra", extra, "float32", c["E"]), ("done", done, "int32", 1), ("flags", flags, "int32", 1)):
-            p = _dev_ptr(x, k, dt, N * w)
-            setattr(st, k, None if p is None else p.value)
-        for k, x in outputs.items():
-            p = _dev_ptr(x, k, "int32" if k in ("reset", "time_outs") else "float32", N * outs[k])
-            setattr(table, k, None if p is None else p.value)
+        given = dict(term=term, link_term=link_term, proprio_term=proprio_term, feet_term=feet_term, cmd_term=cmd_term, extra=extra, done=done, flags=flags)
+        ins, outs = self._reward_io("rewards_dev", given)
+        table = _lib.device_struct(_lib.RewardOut, outs, outputs, "rewards_dev")
+        st = _lib.device_struct(_lib.RewardIn, ins, given)
         _lib.check(_lib.lib().gmr_motion_tracker_rewards_dev(self.handle, C.byref(st), C.byref(table), _lib._s(stream)))
 
     def reward_stats_dev(self, out=None, clear: bool = True, stream=None) -> None:
         """Copies the three accumulators of the episode statistics into ``out`` -- ``u64[C + 3]`` on the device: episodes, steps, then the
         ``C + 1`` sums as float64, the reward first -- and, with ``clear``, zeroes them, in one launch; asynchronous on ``stream``."""
-        from . import _lib
         c = self._need_rewards("reward_stats_dev", stats=True)
         p = _dev_ptr(out, "out", "uint64", len(c["names"]) + 3)
         _lib.check(_lib.lib().gmr_motion_tracker_reward_stats_dev(self.handle, p, 1 if clear else 0, _lib._s(stream)))
@@ -1910,7 +1697,6 @@ class MotionTracker:
         length, ``reward`` and every column by name the mean of the episode sums; 0.0 when no episode finished, as ``_mean`` gives.  The
         division is made here, on the host.  With ``raw`` the accumulators themselves: ``episodes``, ``steps`` (their sum) and ``sums
         f64[C + 1]``.  With ``clear`` the accumulators are zeroed in the same launch.  Synchronous."""
-        from . import _lib
         c = self._need_rewards("reward_stats", stats=True)
         K = len(c["names"]) + 1
         buf = np.zeros(K + 2, np.uint64)
@@ -1926,8 +1712,7 @@ class MotionTracker:
     def reward_state(self) -> Optional[Dict[str, np.ndarray]]:
         """``ep_steps i32[N]`` and ``ep_sum f32[N,C+1]`` (column 0 is the reward) of the open episodes; ``None`` without statistics.
         Synchronous."""
-        from . import _lib
-        c = getattr(self, "_rewards", None)
+        c = self._rewards
         if c is None or not c["stats"]:
             return None
         N, K = self.num_envs, len(c["names"]) + 1
@@ -1953,7 +1738,6 @@ class MotionTracker:
         """Configures the rollout (runner.py:36-42, :141-142): ``horizon`` slots of ``num_envs`` rows with ``obs_cols``, ``priv_cols`` (0:
         no privileged observations) and ``act_cols`` columns, and the two discounts of the advantages, each in ``[0, 1]``.  The arrays stay
         the caller's; the tracker allocates the scratch of the partial sums.  Returns :meth:`rollout_state`.  Synchronous."""
-        from . import _lib
         c = self._rollout_setup(horizon, obs_cols, priv_cols, act_cols, gamma, lam)
         _lib.check(_lib.lib().gmr_motion_tracker_set_rollout(self.handle, c["horizon"], c["obs_cols"], c["priv_cols"], c["act_cols"], c["gamma"],
                                                              c["lam"]))
@@ -1963,7 +1747,7 @@ class MotionTracker:
     def rollout_state(self) -> Optional[Dict[str, object]]:
         """The rollout configuration -- ``horizon, obs_cols, priv_cols, act_cols, gamma, lam``, ``num_envs`` and ``shapes``, the shape of
         each of the caller's six arrays (``priv``: ``None`` without privileged observations) --; ``None`` when the rollout was never set"""
-        c = getattr(self, "_rollout", None)
+        c = self._rollout
         if c is None:
             return None
         H, N = c["horizon"], self.num_envs
@@ -1972,40 +1756,36 @@ class MotionTracker:
         return dict(c, num_envs=N, shapes=shapes)
 
     def _need_rollout(self, what: str):
-        c = getattr(self, "_rollout", None)
+        c = self._rollout
         if c is None:
             raise ValueError(f"{what}: the rollout is not set on this tracker, call set_rollout() first")
         return c
 
-    _ROLLOUT_DTYPES = {"obs": "float32", "priv": "float32", "actions": "float32", "rewards": "float32", "dones": "uint8", "time_outs": "uint8"}
-
     def _rollout_io(self, what: str, io, need, device: bool):
         """the caller's rollout arrays ``io`` (a dict) as a ``gmr_rollout_io_t``: the arrays named in ``need`` must be there -> (table, keep)"""
-        from . import _lib
         c = self._need_rollout(what)
-        shapes = self.rollout_state()["shapes"]
-        unknown = sorted(set(io) - set(shapes))
+        rows = self._rows_of(_lib.ROLLOUT_IO, H=c["horizon"], O=c["obs_cols"], P=c["priv_cols"], A=c["act_cols"])
+        unknown = sorted(set(io) - set(rows))
         if unknown:
-            raise ValueError(f"{what}: unknown rollout arrays {unknown} (known: {sorted(shapes)})")
-        table, keep = _lib.RolloutIo(), []
-        for k in _lib.ROLLOUT_IO_FIELDS:
-            a = io.get(k)
-            if a is None:
-                if k in need:
-                    raise ValueError(f"{what}: the rollout array {k!r} is needed")
-                continue
-            if shapes[k] is None:
+            raise ValueError(f"{what}: unknown rollout arrays {unknown} (known: {sorted(rows)})")
+        given = {k: io.get(k) for k in rows}
+        for k, a in given.items():
+            if a is None and k in need:
+                raise ValueError(f"{what}: the rollout array {k!r} is needed")
+            if a is not None and k == "priv" and c["priv_cols"] == 0:
                 raise ValueError(f"{what}: {k} given, but the rollout was set with priv_cols = 0")
-            dt = self._ROLLOUT_DTYPES[k]
-            if device:
-                p = _dev_ptr(a, k, dt, int(np.prod(shapes[k])))
-                setattr(table, k, p.value)
+        if device:
+            return c, _lib.device_struct(_lib.RolloutIo, rows, given), []
+        table, keep = _lib.RolloutIo(), []
+        for k, a in given.items():          # written in place: nothing is converted, so no host_inputs here
+            if a is None:
                 continue
+            dt, shape, _ = rows[k]
             if not isinstance(a, np.ndarray) or a.dtype not in ((np.dtype(dt),) if dt == "float32" else (np.dtype(np.uint8), np.dtype(np.bool_))) \
                     or not a.flags.c_contiguous or not a.flags.writeable:
                 raise TypeError(f"{what}: {k} is written in place: a writeable C-contiguous {dt} array is needed")
-            if a.shape != shapes[k]:
-                raise ValueError(f"{what}: {k}: shape {a.shape}, {shapes[k]} needed")
+            if a.shape != shape:
+                raise ValueError(f"{what}: {k}: shape {a.shape}, {shape} needed")
             keep.append(a)
             setattr(table, k, a.ctypes.data)
         return c, table, keep
@@ -2027,7 +1807,6 @@ class MotionTracker:
         ``io`` -- a dict of NumPy arrays in the shapes of :meth:`rollout_state`, written in place -- receives ``obs [N,O]``, ``priv [N,P]``,
         ``actions [N,A]``, ``reward [N]`` and the ``done`` and ``time_outs`` words (integers or booleans, stored as 0 / 1 bytes).  An input that
         is ``None`` leaves its slot as it is.  One launch."""
-        from . import _lib
         c = self._need_rollout("record")
         n = self._check_slot("record", c, n)
         inputs = self._record_inputs("record", c, obs, priv, actions, reward, done, time_outs)
@@ -2053,7 +1832,6 @@ class MotionTracker:
         ``priv``, ``actions``, ``rewards f32[H*N]``, ``dones`` / ``time_outs u8[H*N]``); ``done`` and ``time_outs`` are the ``i32[N]`` words
         :meth:`rewards_dev` writes (``reset``, ``time_outs``).  Every array is a ``_lib.DeviceBuffer``, a raw address or an object with
         ``data_ptr()``."""
-        from . import _lib
         c = self._need_rollout("record_dev")
         n = self._check_slot("record_dev", c, n)
         inputs = self._record_inputs("record_dev", c, obs, priv, actions, reward, done, time_outs)
@@ -2067,7 +1845,6 @@ class MotionTracker:
         ``advantages`` (``discount_values`` with ``last_values [N]``), ``returns = values + advantages`` and, with ``normalize``,
         ``normalized`` and ``stats`` -- ``S1, S2, mean, std`` as float64 -- of all ``H N`` advantages (the unbiased deviation: ``H N >= 2``).
         ``io`` needs ``rewards``, ``dones`` and ``time_outs``."""
-        from . import _lib
         c = self._need_rollout("advantages")
         H, N = c["horizon"], self.num_envs
         if normalize and H * N < 2:
@@ -2077,10 +1854,7 @@ class MotionTracker:
         v, lv = np.ascontiguousarray(values, dtype=np.float32), np.ascontiguousarray(last_values, dtype=np.float32)
         if v.shape != (H, N) or lv.shape != (N,):
             raise ValueError(f"advantages: values {v.shape} and last_values {lv.shape}, {(H, N)} and {(N,)} needed")
-        out = {"advantages": np.empty((H, N), np.float32), "returns": np.empty((H, N), np.float32)}
-        if normalize:
-            out.update(normalized=np.empty((H, N), np.float32), stats=np.empty(4, np.float64))
-        res = _lib.RolloutOut(**{k: a.ctypes.data for k, a in out.items()})
+        res, out = _lib.host_outputs(_lib.RolloutOut, self._rows_of(_lib.ROLLOUT_OUT, H=H), skip=() if normalize else ("normalized", "stats"))
         _lib.check(_lib.lib().gmr_motion_tracker_advantages(self.handle, C.byref(table), _lib._ptr(v), _lib._ptr(lv), C.byref(res),
                                                             1 if normalize else 0))
         return out
@@ -2091,22 +1865,15 @@ class MotionTracker:
         ``time_outs``; ``out`` names whichever of ``advantages``, ``returns``, ``normalized`` (``f32[H*N]``) and ``stats`` (``f64[4]``) are
         wanted; no output may overlap another one, ``values``, ``last_values`` or an array of ``io`` (nothing checks it).  A torch loop
         hands ``values.detach()`` and its buffers as they are: anything with ``data_ptr()`` is taken."""
-        from . import _lib
         c = self._need_rollout("advantages_dev")
         H, N = c["horizon"], self.num_envs
         if normalize and H * N < 2:
             raise ValueError(f"advantages_dev: normalize with H * N = {H * N}: the unbiased deviation needs two advantages")
-        unknown = sorted(set(out) - set(_lib.ROLLOUT_OUT_FIELDS))
-        if unknown:
-            raise TypeError(f"advantages_dev: unknown outputs {unknown}")
+        res = _lib.device_struct(_lib.RolloutOut, self._rows_of(_lib.ROLLOUT_OUT, H=H), out, "advantages_dev")
         _, table, _ = self._rollout_io("advantages_dev", {k: io.get(k) for k in ("rewards", "dones", "time_outs")},
                                        {"rewards", "dones", "time_outs"}, device=True)
         if values is None or last_values is None:
             raise ValueError("advantages_dev: values and last_values are needed")
-        res = _lib.RolloutOut()
-        for k, x in out.items():
-            p = _dev_ptr(x, k, "float64" if k == "stats" else "float32", 4 if k == "stats" else H * N)
-            setattr(res, k, None if p is None else p.value)
         _lib.check(_lib.lib().gmr_motion_tracker_advantages_dev(self.handle, C.byref(table), _dev_ptr(values, "values", "float32", H * N),
                                                                 _dev_ptr(last_values, "last_values", "float32", N), C.byref(res),
                                                                 1 if normalize else 0, _lib._s(stream)))
@@ -2114,7 +1881,6 @@ class MotionTracker:
     # ---- the PPO loss head, its gradients and the KL step -------------------------------------------------------
     def _loss_setup(self, bound_coef, entropy_coef, desired_kl, learning_rate, e_clip, lr_min, lr_max, lr_factor):
         """the checks of :meth:`set_loss`, all of them before the library is loaded -> a dict of the checked values, rows and columns"""
-        from . import _lib
         r = self._need_rollout("set_loss")
         if r["act_cols"] > _lib.LOSS_MAX_ACT:
             raise ValueError(f"set_loss: act_cols = {r['act_cols']}, at most {_lib.LOSS_MAX_ACT}")
@@ -2141,14 +1907,13 @@ class MotionTracker:
         the learning rate and the rate it starts from, which the tracker keeps as one double on the device.  Needs :meth:`set_rollout`
         first -- the rows ``M = horizon * num_envs`` and the columns ``A = act_cols`` are its --, and again after a new ``set_rollout``.
         Returns :meth:`loss_state`.  Synchronous."""
-        from . import _lib
         c = self._loss_setup(bound_coef, entropy_coef, desired_kl, learning_rate, e_clip, lr_min, lr_max, lr_factor)
         _lib.check(_lib.lib().gmr_motion_tracker_set_loss(self.handle, *(c[k] for k in _lib.LOSS_STATE)))
         self._loss = c
         return self.loss_state()
 
     def _need_loss(self, what: str):
-        c = getattr(self, "_loss", None)
+        c = self._loss
         if self._need_rollout(what) is None or c is None:
             raise ValueError(f"{what}: the loss is not set on this tracker, call set_loss() first")
         r = self._rollout
@@ -2159,63 +1924,56 @@ class MotionTracker:
     def loss_state(self) -> Optional[Dict[str, object]]:
         """The loss configuration as given, ``rows`` and ``cols``, and ``learning_rate`` as the last ``update_lr`` call left it on the
         device; ``None`` when the loss was never set.  Synchronises."""
-        from . import _lib
-        c = getattr(self, "_loss", None)
+        c = self._loss
         if c is None:
             return None
         out = np.empty(len(_lib.LOSS_STATE), np.float64)
         _lib.check(_lib.lib().gmr_motion_tracker_loss_state(self.handle, _lib._ptr(out)))
         return dict(c, **{k: float(v) for k, v in zip(_lib.LOSS_STATE, out)})
 
-    def _loss_shapes(self, c):
-        M, A = c["rows"], c["cols"]
-        return {"loc": (M, A), "logstd": (A,), "actions": (M, A), "old_log_prob": (M,), "values": (M,), "returns": (M,), "advantages": (M,),
-                "old_loc": (M, A), "old_logstd": (A,), "grad_loc": (M, A), "grad_logstd": (A,), "grad_values": (M,), "log_prob": (M,), "terms": (8,)}
+    def _loss_rows(self, c):
+        return self._rows_of(_lib.LOSS_IN, M=c["rows"], A=c["cols"]), self._rows_of(_lib.LOSS_OUT, M=c["rows"], A=c["cols"])
+
+    def _loss_array(self, what: str, rows, k: str, a):
+        """a host input of the loss as float32: ``[M, ...]`` or, as the rollout lays it out, ``[H, N, ...]``"""
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        _, shape, count = rows[k]
+        H, N = self._rollout["horizon"], self.num_envs
+        if a.size != count or a.shape not in (shape, (H, N) + shape[1:] if shape[0] == H * N else shape):
+            raise ValueError(f"{what}: {k}: shape {a.shape}, {shape} needed")
+        return a
 
     def _loss_in(self, what: str, c, inputs, update_lr, device: bool):
         """the inputs of a loss call (a dict) as a ``gmr_loss_in_t`` -> (table, keep)"""
-        from . import _lib
-        unknown = sorted(set(inputs) - set(_lib.LOSS_IN_FIELDS))
+        rows, _ = self._loss_rows(c)
+        unknown = sorted(set(inputs) - set(rows))
         if unknown:
-            raise TypeError(f"{what}: unknown inputs {unknown} (known: {list(_lib.LOSS_IN_FIELDS)})")
+            raise TypeError(f"{what}: unknown inputs {unknown} (known: {list(rows)})")
         old = [inputs.get(k) is not None for k in ("old_loc", "old_logstd")]
         if old[0] != old[1]:
             raise ValueError(f"{what}: old_loc and old_logstd are given together, or neither")
         if update_lr and not old[0]:
             raise ValueError(f"{what}: update_lr without old_loc and old_logstd: there is no KL to drive the learning rate")
-        shapes, table, keep = self._loss_shapes(c), _lib.LossIn(), []
-        for k in _lib.LOSS_IN_FIELDS:
+        table, keep = _lib.LossIn(), []
+        for k in rows:
             a = inputs.get(k)
             if a is None:
                 if k not in ("old_loc", "old_logstd"):
                     raise ValueError(f"{what}: the input {k!r} is needed")
                 continue
             if device:
-                setattr(table, k, _dev_ptr(a, k, "float32", int(np.prod(shapes[k]))).value)
+                setattr(table, k, _dev_ptr(a, k, "float32", rows[k][2]).value)
                 continue
-            a = np.ascontiguousarray(a, dtype=np.float32)
-            if a.size != int(np.prod(shapes[k])) or a.shape not in (shapes[k], self._loss_rollout_shape(shapes[k])):
-                raise ValueError(f"{what}: {k}: shape {a.shape}, {shapes[k]} needed")
-            keep.append(a)
-            setattr(table, k, a.ctypes.data)
+            keep.append(self._loss_array(what, rows, k, a))
+            setattr(table, k, keep[-1].ctypes.data)
         return table, keep
-
-    def _loss_rollout_shape(self, shape):
-        """``[M, ...]`` as the rollout lays it out: ``[H, N, ...]``"""
-        H, N = self._rollout["horizon"], self.num_envs
-        return (H, N) + tuple(shape[1:]) if shape[0] == H * N else shape
 
     def log_prob(self, loc, logstd, actions) -> np.ndarray:
         """``old_actions_log_prob`` (runner.py:123-125), host arrays: ``loc`` and ``actions`` ``[M, A]`` (or ``[H, N, A]``), ``logstd [A]``
         -> ``f32[M]``, the log-probability of every row's action under ``Normal(loc, exp(logstd))``, summed over the columns."""
-        from . import _lib
         c = self._need_loss("log_prob")
-        shapes, args = self._loss_shapes(c), []
-        for k, a in (("loc", loc), ("logstd", logstd), ("actions", actions)):
-            a = np.ascontiguousarray(a, dtype=np.float32)
-            if a.size != int(np.prod(shapes[k])) or a.shape not in (shapes[k], self._loss_rollout_shape(shapes[k])):
-                raise ValueError(f"log_prob: {k}: shape {a.shape}, {shapes[k]} needed")
-            args.append(a)
+        rows, _ = self._loss_rows(c)
+        args = [self._loss_array("log_prob", rows, k, a) for k, a in (("loc", loc), ("logstd", logstd), ("actions", actions))]
         out = np.empty(c["rows"], np.float32)
         _lib.check(_lib.lib().gmr_motion_tracker_log_prob(self.handle, *(_lib._ptr(a) for a in args), _lib._ptr(out)))
         return out
@@ -2223,7 +1981,6 @@ class MotionTracker:
     def log_prob_dev(self, loc, logstd, actions, out, stream=None) -> None:
         """:meth:`log_prob` on device memory, asynchronous on ``stream``: ONE launch.  ``loc`` and ``actions`` ``f32[M*A]``, ``logstd
         f32[A]``, ``out f32[M]``; each a ``_lib.DeviceBuffer``, a raw address or an object with ``data_ptr()``."""
-        from . import _lib
         c = self._need_loss("log_prob_dev")
         M, A = c["rows"], c["cols"]
         args = [_dev_ptr(a, k, "float32", n) for k, a, n in (("loc", loc, M * A), ("logstd", logstd, A), ("actions", actions, M * A), ("out", out, M))]
@@ -2238,12 +1995,9 @@ class MotionTracker:
         [M]`` -- the gradient of the loss with respect to the networks' outputs --, ``log_prob [M]`` and ``terms`` ``f64[8]``: value_loss,
         actor_loss, bound_loss, entropy, loss, kl_mean, the learning rate after this call, clip_fraction.  With ``update_lr`` the KL steps
         the learning rate the tracker keeps."""
-        from . import _lib
         c = self._need_loss("loss")
         table, keep = self._loss_in("loss", c, inputs, update_lr, device=False)
-        shapes = self._loss_shapes(c)
-        out = {k: np.empty(shapes[k], np.float64 if k == "terms" else np.float32) for k in _lib.LOSS_OUT_FIELDS}
-        res = _lib.LossOut(**{k: a.ctypes.data for k, a in out.items()})
+        res, out = _lib.host_outputs(_lib.LossOut, self._loss_rows(c)[1])
         _lib.check(_lib.lib().gmr_motion_tracker_loss(self.handle, C.byref(table), C.byref(res), 1 if update_lr else 0))
         return out
 
@@ -2253,55 +2007,26 @@ class MotionTracker:
         (``f32[M*A]``), ``grad_logstd`` (``f32[A]``), ``grad_values``, ``log_prob`` (``f32[M]``) and ``terms`` (``f64[8]``) are wanted; no
         output may overlap another one or an input (nothing checks it).  A torch loop hands ``loc.detach()``, ``model.logstd.detach()``
         and ``values.detach()`` as they are: anything with ``data_ptr()`` is taken."""
-        from . import _lib
         c = self._need_loss("loss_dev")
-        unknown = sorted(set(out) - set(_lib.LOSS_OUT_FIELDS))
-        if unknown:
-            raise TypeError(f"loss_dev: unknown outputs {unknown}")
+        res = _lib.device_struct(_lib.LossOut, self._loss_rows(c)[1], out, "loss_dev")
         table, _ = self._loss_in("loss_dev", c, inputs, update_lr, device=True)
-        shapes, res = self._loss_shapes(c), _lib.LossOut()
-        for k, x in out.items():
-            p = _dev_ptr(x, k, "float64" if k == "terms" else "float32", int(np.prod(shapes[k])))
-            setattr(res, k, None if p is None else p.value)
         _lib.check(_lib.lib().gmr_motion_tracker_loss_dev(self.handle, C.byref(table), C.byref(res), 1 if update_lr else 0, _lib._s(stream)))
 
     # ---- the step ---------------------------------------------------------------------------------------------------------
     def _counts(self):
-        R = self.nrobot_dof
-        out = {"ref_root_pos": 3, "ref_root_rot": 4, "ref_root_vel": 3, "ref_root_ang_vel": 3, "ref_dof_pos": R, "ref_dof_vel": R, "err": 6,
-               "term": 6, "total": 1, "status": 1, "finished": 1}
-        sim = {"base_pos": 3, "base_quat": 4, "base_lin_vel": 3, "base_ang_vel": 3, "dof_pos": R, "dof_vel": R}
-        return out, sim
+        return _lib.widths(_lib.TRACKER_OUT, R=self.nrobot_dof), _lib.widths(_lib.TRACKER_SIM, R=self.nrobot_dof)
+
+    def _step_rows(self):
+        return self._rows_of(_lib.TRACKER_OUT, R=self.nrobot_dof), self._rows_of(_lib.TRACKER_SIM, R=self.nrobot_dof)
 
     def step(self, sim: Optional[Dict[str, np.ndarray]] = None) -> Dict[str, np.ndarray]:
         """One environment step, host arrays in and out.  Returns ``ref_root_pos [N,3]``, ``ref_root_rot [N,4]`` xyzw, ``ref_root_vel``,
         ``ref_root_ang_vel``, ``ref_dof_pos [N,R]``, ``ref_dof_vel`` (robot dof order), ``status`` and ``finished`` (``i32[N]``); with
         ``sim`` -- any of ``base_pos, base_quat, base_lin_vel, base_ang_vel, dof_pos, dof_vel`` (quaternions xyzw) -- also ``err [N,6]``,
         ``term [N,6]`` and ``total [N]`` in the order of :data:`TERMS`."""
-        from . import _lib
-        N = self.num_envs
-        counts, sim_counts = self._counts()
-        out = {}
-        for k, w in counts.items():
-            if k in ("err", "term", "total") and sim is None:
-                continue
-            dtype = np.int32 if k in ("status", "finished") else np.float32
-            out[k] = np.empty((N,) if k in ("total", "status", "finished") else (N, w), dtype=dtype)
-        table = _lib.TrackerOut(**{k: a.ctypes.data for k, a in out.items()})
-        keep, st = [], None
-        if sim is not None:
-            unknown = sorted(set(sim) - set(sim_counts))
-            if unknown:
-                raise TypeError(f"step: unknown simulator arrays {unknown}")
-            st = _lib.TrackerSim()
-            for k, a in sim.items():
-                if a is None:
-                    continue
-                a = np.ascontiguousarray(a, dtype=np.float32)
-                if a.shape != (N, sim_counts[k]):
-                    raise ValueError(f"{k}: shape {a.shape}, {(N, sim_counts[k])} needed")
-                keep.append(a)
-                setattr(st, k, a.ctypes.data)
+        outs, sims = self._step_rows()
+        table, out = _lib.host_outputs(_lib.TrackerOut, outs, skip=("err", "term", "total") if sim is None else ())
+        st, keep = (None, None) if sim is None else _lib.host_inputs(_lib.TrackerSim, sims, sim, "step", unknown="simulator arrays")
         _lib.check(_lib.lib().gmr_motion_tracker_step(self.handle, None if st is None else C.byref(st), C.byref(table)))
         return out
 
@@ -2309,25 +2034,9 @@ class MotionTracker:
         """The same on device memory, asynchronous on ``stream``: ``sim`` maps names to device arrays, ``outputs`` names whichever of the
         arrays of :meth:`step` are wanted; each is a ``_lib.DeviceBuffer``, a raw address or an object with ``data_ptr()``, checked as
         ``MotionLibrary.sample_dev`` checks them."""
-        from . import _lib
-        N = self.num_envs
-        counts, sim_counts = self._counts()
-        unknown = sorted(set(outputs) - set(counts))
-        if unknown:
-            raise TypeError(f"step_dev: unknown outputs {unknown}")
-        table = _lib.TrackerOut()
-        for k, x in outputs.items():
-            p = _dev_ptr(x, k, "int32" if k in ("status", "finished") else "float32", N * counts[k])
-            setattr(table, k, None if p is None else p.value)
-        st = None
-        if sim is not None:
-            unknown = sorted(set(sim) - set(sim_counts))
-            if unknown:
-                raise TypeError(f"step_dev: unknown simulator arrays {unknown}")
-            st = _lib.TrackerSim()
-            for k, x in sim.items():
-                p = _dev_ptr(x, k, "float32", N * sim_counts[k])
-                setattr(st, k, None if p is None else p.value)
+        outs, sims = self._step_rows()
+        table = _lib.device_struct(_lib.TrackerOut, outs, outputs, "step_dev")
+        st = None if sim is None else _lib.device_struct(_lib.TrackerSim, sims, sim, "step_dev", unknown="simulator arrays")
         _lib.check(_lib.lib().gmr_motion_tracker_step_dev(self.handle, None if st is None else C.byref(st), C.byref(table), _lib._s(stream)))
 
     # ---- links (DESIGN.md section 6l) ---------------------------------------------------------------------------------------
@@ -2363,7 +2072,6 @@ class MotionTracker:
         ``link_weight`` weighs the links inside the four link terms, ``frame`` is ``"world"`` or ``"heading"`` (each side relative to
         its own root with the root's yaw removed).  ``bodies=[]`` detaches.  Link targets follow the motion in the library's dof
         order: the ``dof_map`` does not enter."""
-        from . import _lib
         if bodies is not None and len(bodies) == 0:
             _lib.check(_lib.lib().gmr_motion_tracker_set_links(self.handle, None, None, 0, None, None, 0))
             self._links = None
@@ -2376,7 +2084,6 @@ class MotionTracker:
     def set_link_terms(self, scales=None, weights=None, fail_dist: float = float("inf")) -> None:
         """``link_term = exp(-link_err / scale)`` over :data:`LINK_TERMS` (defaults :data:`DEFAULT_LINK_SCALES`, weights one; ``None``
         keeps what is set); ``fail = not (max_dist <= fail_dist)`` and ``fail_dist`` is set by every call."""
-        from . import _lib
         sc, wt = _terms(scales, weights, LINK_TERMS, DEFAULT_LINK_SCALES)
         fail_dist = float(fail_dist)
         if not fail_dist > 0:
@@ -2384,9 +2091,7 @@ class MotionTracker:
         _lib.check(_lib.lib().gmr_motion_tracker_set_link_terms(self.handle, _lib._ptr(sc), _lib._ptr(wt), fail_dist))
 
     def _link_counts(self):
-        nsel = self._links[1] if self._links else 0
-        return {"ref_body_pos": nsel * 3, "ref_body_rot": nsel * 4, "ref_body_vel": nsel * 3, "ref_body_ang_vel": nsel * 3, "link_err": 4,
-                "link_term": 4, "max_dist": 1, "fail": 1}
+        return _lib.widths(_lib.TRACKER_LINKS_OUT, nsel=self._links[1] if self._links else 0)
 
     def _check_links(self, sim, links, device: bool):
         """the checks of a link step that need no device -> ``("packed", array) | ("separate", {name: array}) | None``"""
@@ -2416,117 +2121,54 @@ class MotionTracker:
         state as ``{"body_state": [N, nb, 13]}`` (pos, quat xyzw, vel, ang vel) or as ``body_pos / body_rot / body_vel / body_ang_vel
         [N, nsel, k]`` -- ``link_err [N,4]``, ``link_term [N,4]``, ``max_dist [N]`` and ``fail i32[N]``; ``total`` then includes the link
         terms.  ``advance=False`` leaves clocks and clips as they are (reference-state initialisation after :meth:`reset`)."""
-        from . import _lib
-        N = self.num_envs
         kind = self._check_links(sim, links, False)
-        counts, sim_counts = self._counts()
-        out = {}
-        for k, w in counts.items():
-            if k in ("err", "term") and sim is None or k == "total" and sim is None and kind is None:
-                continue
-            dtype = np.int32 if k in ("status", "finished") else np.float32
-            out[k] = np.empty((N,) if k in ("total", "status", "finished") else (N, w), dtype=dtype)
-        table = _lib.TrackerOut(**{k: a.ctypes.data for k, a in out.items()})
-        lout = {}
+        outs, sims = self._step_rows()
+        skip = ("err", "term") if sim is None else ()
+        table, out = _lib.host_outputs(_lib.TrackerOut, outs, skip=skip + ("total",) if sim is None and kind is None else skip)
+        ltable, lout = _lib.TrackerLinksOut(), {}
         if self._links is not None:
-            nsel = self._links[1]
-            for k, w in (("ref_body_pos", 3), ("ref_body_rot", 4), ("ref_body_vel", 3), ("ref_body_ang_vel", 3)):
-                lout[k] = np.empty((N, nsel, w), dtype=np.float32)
-            if kind is not None:
-                lout.update(link_err=np.empty((N, 4), np.float32), link_term=np.empty((N, 4), np.float32), max_dist=np.empty(N, np.float32),
-                            fail=np.empty(N, np.int32))
-        ltable = _lib.TrackerLinksOut(**{k: a.ctypes.data for k, a in lout.items()})
-        keep, st, ls = [], None, None
-        if sim is not None:
-            unknown = sorted(set(sim) - set(sim_counts))
-            if unknown:
-                raise TypeError(f"step_links: unknown simulator arrays {unknown}")
-            st = _lib.TrackerSim()
-            for k, a in sim.items():
-                if a is None:
-                    continue
-                a = np.ascontiguousarray(a, dtype=np.float32)
-                if a.shape != (N, sim_counts[k]):
-                    raise ValueError(f"{k}: shape {a.shape}, {(N, sim_counts[k])} needed")
-                keep.append(a)
-                setattr(st, k, a.ctypes.data)
-        if kind is not None:
-            nsel, sb = self._links[1], self._links[2]
-            ls = _lib.TrackerLinksSim()
-            if kind[0] == "packed":
-                a = np.ascontiguousarray(kind[1], dtype=np.float32)
-                if a.ndim != 3 or a.shape[0] != N or a.shape[2] != 13:
-                    raise ValueError(f"body_state: shape {a.shape}, ({N}, nb, 13) needed")
-                if int(sb.max()) >= a.shape[1]:
-                    raise ValueError(f"sim_bodies reaches body {int(sb.max())}, body_state has {a.shape[1]}")
-                keep.append(a)
-                for k, (off, _) in LINK_SIM.items():
-                    setattr(ls, k, a.ctypes.data + 4 * off)
-                ls.env_stride, ls.body_stride = 13 * a.shape[1], 13
-            else:
-                if not np.array_equal(sb, np.arange(nsel)):
-                    raise ValueError("separate link arrays are [N, nsel, k] in selection order: they need the identity sim_bodies")
-                for k, a in kind[1].items():
-                    a = np.ascontiguousarray(a, dtype=np.float32)
-                    if a.shape != (N, nsel, LINK_SIM[k][1]):
-                        raise ValueError(f"{k}: shape {a.shape}, {(N, nsel, LINK_SIM[k][1])} needed")
-                    keep.append(a)
-                    setattr(ls, k, a.ctypes.data)
+            louts = self._rows_of(_lib.TRACKER_LINKS_OUT, nsel=self._links[1])
+            ltable, lout = _lib.host_outputs(_lib.TrackerLinksOut, louts, skip=() if kind is not None else ("link_err", "link_term", "max_dist", "fail"))
+        st, keep = (None, None) if sim is None else _lib.host_inputs(_lib.TrackerSim, sims, sim, "step_links", unknown="simulator arrays")
+        ls, held = (None, None) if kind is None else self._links_sim(kind, None, False)
         _lib.check(_lib.lib().gmr_motion_tracker_step_links(self.handle, None if st is None else C.byref(st), None if ls is None else C.byref(ls),
                                                             C.byref(table), C.byref(ltable), 0 if advance else _lib.TRACKER_NO_ADVANCE))
         out.update(lout)
         return out
+
+    def _links_sim(self, kind, nb, device: bool):
+        """the simulator's links of a link step, as :meth:`_check_links` sorted them, through :meth:`_bodies`"""
+        nsel, sb = self._links[1], self._links[2]
+        if kind[0] == "packed":
+            return self._bodies({"body_state": kind[1]}, LINK_SIM, nsel, nb, int(sb.max()), device)
+        if not np.array_equal(sb, np.arange(nsel)):
+            raise ValueError("separate link arrays are [N, nsel, k] in selection order: they need the identity sim_bodies")
+        return self._bodies(kind[1], LINK_SIM, nsel, device=device)
 
     def step_links_dev(self, sim: Optional[Dict[str, object]] = None, links: Optional[Dict[str, object]] = None, advance: bool = True,
                        stream=None, **outputs) -> None:
         """:meth:`step_links` on device memory, asynchronous on ``stream``.  ``links`` is ``{"body_state": array, "num_bodies": nb}``
         for a packed ``[N, nb, 13]`` tensor or the four separate ``[N, nsel, k]`` arrays; ``outputs`` names whichever arrays of
         :meth:`step_links` are wanted."""
-        from . import _lib
-        N = self.num_envs
         links = None if links is None else dict(links)
         nb = None if links is None else links.pop("num_bodies", None)
         kind = self._check_links(sim, links, True)
-        counts, sim_counts = self._counts()
-        lcounts = self._link_counts()
-        unknown = sorted(set(outputs) - set(counts) - set(lcounts))
+        outs, sims = self._step_rows()
+        louts = self._rows_of(_lib.TRACKER_LINKS_OUT, nsel=self._links[1] if self._links else 0)
+        unknown = sorted(set(outputs) - set(outs) - set(louts))
         if unknown:
             raise TypeError(f"step_links_dev: unknown outputs {unknown}")
-        table, ltable = _lib.TrackerOut(), _lib.TrackerLinksOut()
-        for k, x in outputs.items():
-            p = _dev_ptr(x, k, "int32" if k in ("status", "finished", "fail") else "float32", N * (counts[k] if k in counts else lcounts[k]))
-            setattr(table if k in counts else ltable, k, None if p is None else p.value)
-        st, ls = None, None
-        if sim is not None:
-            unknown = sorted(set(sim) - set(sim_counts))
-            if unknown:
-                raise TypeError(f"step_links_dev: unknown simulator arrays {unknown}")
-            st = _lib.TrackerSim()
-            for k, x in sim.items():
-                p = _dev_ptr(x, k, "float32", N * sim_counts[k])
-                setattr(st, k, None if p is None else p.value)
+        table = _lib.device_struct(_lib.TrackerOut, outs, {k: x for k, x in outputs.items() if k in outs})
+        ltable = _lib.device_struct(_lib.TrackerLinksOut, louts, {k: x for k, x in outputs.items() if k in louts})
+        st = None if sim is None else _lib.device_struct(_lib.TrackerSim, sims, sim, "step_links_dev", unknown="simulator arrays")
+        ls = None
         if kind is not None:
-            nsel, sb = self._links[1], self._links[2]
-            ls = _lib.TrackerLinksSim()
-            if kind[0] == "packed":
-                if nb is None:
-                    shape = getattr(kind[1], "shape", None)
-                    if shape is None or len(shape) != 3:
-                        raise ValueError("a packed body_state on the device needs num_bodies (or a [N, nb, 13] shape)")
-                    nb = int(shape[1])
-                nb = int(nb)
-                if int(sb.max()) >= nb:
-                    raise ValueError(f"sim_bodies reaches body {int(sb.max())}, body_state has {nb}")
-                p = _dev_ptr(kind[1], "body_state", "float32", N * nb * 13)
-                for k, (off, _) in LINK_SIM.items():
-                    setattr(ls, k, p.value + 4 * off)
-                ls.env_stride, ls.body_stride = 13 * nb, 13
-            else:
-                if not np.array_equal(sb, np.arange(nsel)):
-                    raise ValueError("separate link arrays are [N, nsel, k] in selection order: they need the identity sim_bodies")
-                for k, x in kind[1].items():
-                    p = _dev_ptr(x, k, "float32", N * nsel * LINK_SIM[k][1])
-                    setattr(ls, k, None if p is None else p.value)
+            if kind[0] == "packed" and nb is None:
+                shape = getattr(kind[1], "shape", None)
+                if shape is None or len(shape) != 3:
+                    raise ValueError("a packed body_state on the device needs num_bodies (or a [N, nb, 13] shape)")
+                nb = shape[1]
+            ls, _ = self._links_sim(kind, None if nb is None else int(nb), True)
         _lib.check(_lib.lib().gmr_motion_tracker_step_links_dev(self.handle, None if st is None else C.byref(st), None if ls is None else C.byref(ls),
                                                                 C.byref(table), C.byref(ltable), 0 if advance else _lib.TRACKER_NO_ADVANCE,
                                                                 _lib._s(stream)))
@@ -2535,7 +2177,6 @@ class MotionTracker:
     def _preview_setup(self, offsets, blocks, frame, bodies):
         """the checks of :meth:`set_preview`, all of them before a device is touched: ``(offsets f32[K], blocks in row order, block
         bits, sel i32[nsel] or None)``"""
-        from . import _lib
         off = np.ascontiguousarray(offsets, dtype=np.float32).reshape(-1)
         if not 1 <= len(off) <= PREVIEW_MAX_OFFSETS:
             raise ValueError(f"a preview holds 1 to {PREVIEW_MAX_OFFSETS} offsets, got {len(off)}")
@@ -2607,7 +2248,6 @@ class MotionTracker:
         simulator's ``base_pos / base_quat`` -- and, for ``body_pos``, ``bodies``: rows of the library's ``local_body_pos`` by index, or
         by name when every clip carries the same ``link_body_list``.  Returns :attr:`preview_layout`.  ``offsets=[]`` removes the
         configuration.  Previews already enqueued keep the configuration they were launched with."""
-        from . import _lib
         if offsets is None or np.size(offsets) == 0:
             _lib.check(_lib.lib().gmr_motion_tracker_set_preview(self.handle, 0, None, 0, 0, None, 0, None))
             self._preview = None
@@ -2638,18 +2278,11 @@ class MotionTracker:
         ``valid i32[N,K]`` -- 1 where the query lies inside the clip, neither wrapped nor clamped -- and ``status i32[N]``, 1 for a bad
         assignment (its rows are NaN).  One launch; clocks, clips and draw counters stay as they are.  ``sim`` is read in
         ``frame="sim"`` only: ``base_pos [N,3]``, ``base_quat [N,4]`` xyzw."""
-        from . import _lib
         N = self.num_envs
         K, D, frame = self._check_preview(sim, "preview")
-        st, keep = None, []
+        st, keep = None, None
         if frame == "sim":
-            st = _lib.TrackerSim()
-            for k, w in (("base_pos", 3), ("base_quat", 4)):
-                a = np.ascontiguousarray(sim[k], dtype=np.float32)
-                if a.shape != (N, w):
-                    raise ValueError(f"{k}: shape {a.shape}, {(N, w)} needed")
-                keep.append(a)
-                setattr(st, k, a.ctypes.data)
+            st, keep = _lib.host_inputs(_lib.TrackerSim, self._step_rows()[1], {k: sim[k] for k in ("base_pos", "base_quat")})
         out = {"obs": np.empty((N, K, D), np.float32), "valid": np.empty((N, K), np.int32), "status": np.empty(N, np.int32)}
         _lib.check(_lib.lib().gmr_motion_tracker_preview(self.handle, None if st is None else C.byref(st), _lib._ptr(out["obs"]),
                                                          _lib._ptr(out["valid"]), _lib._ptr(out["status"])))
@@ -2659,14 +2292,11 @@ class MotionTracker:
         """:meth:`preview` on device memory, asynchronous on ``stream`` (the tracker's stream, or one the caller orders behind it):
         whichever of ``obs f32[N*K*D]``, ``valid i32[N*K]``, ``status i32[N]`` are wanted, each a ``_lib.DeviceBuffer``, a raw address or
         an object with ``data_ptr()``."""
-        from . import _lib
         N = self.num_envs
         K, D, frame = self._check_preview(sim, "preview_dev")
         st = None
         if frame == "sim":
-            st = _lib.TrackerSim()
-            for k, w in (("base_pos", 3), ("base_quat", 4)):
-                setattr(st, k, _dev_ptr(sim[k], k, "float32", N * w).value)
+            st = _lib.device_struct(_lib.TrackerSim, self._step_rows()[1], {k: sim[k] for k in ("base_pos", "base_quat")})
         _lib.check(_lib.lib().gmr_motion_tracker_preview_dev(self.handle, None if st is None else C.byref(st),
                                                              _dev_ptr(obs, "obs", "float32", N * K * D), _dev_ptr(valid, "valid", "int32", N * K),
                                                              _dev_ptr(status, "status", "int32", N), _lib._s(stream)))
@@ -2674,7 +2304,6 @@ class MotionTracker:
     def close(self) -> None:
         h = getattr(self, "handle", None)
         if h:
-            from . import _lib
             _lib.lib().gmr_motion_tracker_destroy(h)
             self.handle = None
             self._proprio = None          # the state arrays went with the handle

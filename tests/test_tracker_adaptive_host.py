@@ -268,7 +268,7 @@ def offline_tracker(lens=(30, 0, 200), fps=(30.0, 50.0, 120.0), N=8):
     lib.seg_start = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
     lib._fps = np.asarray(fps, dtype=np.float64)
     lib.num_clips = len(fps)
-    t.library, t.num_envs, t.nrobot_dof, t.handle, t._links, t._preview, t._adaptive = lib, N, 5, None, None, None, None
+    t._init_state(lib, N, 5)
     return t
 
 

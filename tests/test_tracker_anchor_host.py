@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_header as abi  # noqa: E402
 import anchor_mirror as am  # noqa: E402
 from test_motion_body_state_host import _OfflineLibrary  # noqa: E402
 from test_motion_library import _bits  # noqa: E402
@@ -19,14 +20,6 @@ ANCHOR_SYMBOLS = ("gmr_motion_tracker_enable_anchors", "gmr_motion_tracker_set_a
                   "gmr_motion_tracker_anchor_to_root_dev", "gmr_motion_tracker_anchor_to_root", "gmr_motion_tracker_anchor_state")
 F = np.float32
 U = 2.0 ** -24          # the unit roundoff of float32
-
-
-def _ctype_of(decl: str):
-    """the ctypes type _lib.py must give a C parameter declaration of the header"""
-    decl = decl.strip()
-    if "*" in decl:
-        return C.POINTER(C.c_int) if re.match(r"int\s*\*", decl) else C.c_void_p
-    return {"int": C.c_int, "float": C.c_float, "double": C.c_double}[decl.split()[0]]
 
 
 def test_the_library_exports_the_anchor_entry_points_with_the_headers_signatures():
@@ -40,9 +33,9 @@ def test_the_library_exports_the_anchor_entry_points_with_the_headers_signatures
         assert sym in _lib.EXPORTED_SYMBOLS
         m = re.search(r"\bint " + sym + r"\(([^;]*)\);", hdr)
         assert m, sym
-        params = [p for p in re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S).split(",")]
+        params = abi.parameters(hdr, sym)
         res, args = _lib._SIGS[sym]
-        assert res is C.c_int and args == [_ctype_of(p) for p in params], (sym, params, args)
+        assert res is C.c_int and args == params, (sym, params, args)
     for name, value in (("GMR_ANCHOR_YAW", _lib.ANCHOR_YAW), ("GMR_ANCHOR_Z", _lib.ANCHOR_Z)):
         assert int(re.search(r"#define " + name + r"\s+(\d+)", hdr).group(1)) == value == getattr(am, name[4:])
     for name in ("enable_anchors", "set_anchor", "set_anchor_dev", "anchor_to_root", "anchor_to_root_dev", "anchor_state"):
@@ -62,8 +55,7 @@ def test_the_sources_of_the_other_kernels_do_not_see_the_changed_headers():
 def offline_tracker(N=8, ang_vel="world"):
     from general_motion_retargeting_amd import MotionTracker
     t = MotionTracker.__new__(MotionTracker)
-    t.library, t.num_envs, t.nrobot_dof, t.handle = _OfflineLibrary(5, ang_vel), N, 5, None
-    t._links, t._preview, t._adaptive, t._anchors = None, None, None, False
+    t._init_state(_OfflineLibrary(5, ang_vel), N, 5)
     return t
 
 

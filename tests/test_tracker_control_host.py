@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_header as abi  # noqa: E402
 import control_mirror as cm  # noqa: E402
 from test_motion_body_state_host import _OfflineLibrary  # noqa: E402
 
@@ -17,14 +18,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CONTROL_SYMBOLS = ("gmr_motion_tracker_set_control", "gmr_motion_tracker_targets_dev", "gmr_motion_tracker_targets", "gmr_motion_tracker_hold_dev",
                    "gmr_motion_tracker_hold", "gmr_motion_tracker_torques_dev", "gmr_motion_tracker_torques", "gmr_motion_tracker_control_state")
 F = np.float32
-
-
-def _ctype_of(decl: str):
-    """the ctypes type _lib.py must give a C parameter declaration of the header"""
-    decl = decl.strip()
-    if "*" in decl:
-        return C.POINTER(C.c_int) if re.match(r"int\s*\*", decl) else C.c_void_p
-    return {"int": C.c_int, "float": C.c_float, "double": C.c_double}[decl.split()[0]]
 
 
 def test_the_library_exports_the_control_entry_points_with_the_headers_signatures():
@@ -38,9 +31,9 @@ def test_the_library_exports_the_control_entry_points_with_the_headers_signature
         assert sym in _lib.EXPORTED_SYMBOLS
         m = re.search(r"\bint " + sym + r"\(([^;]*)\);", hdr)
         assert m, sym
-        params = [p for p in re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S).split(",")]
+        params = abi.parameters(hdr, sym)
         res, args = _lib._SIGS[sym]
-        assert res is C.c_int and args == [_ctype_of(p) for p in params], (sym, params, args)
+        assert res is C.c_int and args == params, (sym, params, args)
         # the comment in front of the prototype (a _dev call and its twin share one) cites the reference lines it replaces
         section = hdr[hdr.index("N9: tracker control"):m.start()]
         comment = [c for c in re.findall(r"/\*.*?\*/", section, flags=re.S) if "\n" in c][-1]
@@ -64,8 +57,7 @@ def test_the_library_exports_the_control_entry_points_with_the_headers_signature
 def offline_tracker(N=8, R=5):
     from general_motion_retargeting_amd import MotionTracker
     t = MotionTracker.__new__(MotionTracker)
-    t.library, t.num_envs, t.nrobot_dof, t.handle = _OfflineLibrary(R, "world"), N, R, None
-    t._links, t._preview, t._adaptive, t._anchors, t._control = None, None, None, False, None
+    t._init_state(_OfflineLibrary(R, "world"), N, R)
     return t
 
 

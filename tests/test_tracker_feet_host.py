@@ -13,6 +13,7 @@ import pytest
 from conftest import GOLDEN, ROOT
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_header as abi  # noqa: E402
 import feet_mirror as fm  # noqa: E402
 from test_tracker_proprio_host import offline_tracker  # noqa: E402
 
@@ -58,14 +59,6 @@ def term_bounds(term, feet_roll, feet_pos, scale, d_angle, d_base_yaw, d_trig, f
     return b, total
 
 
-def _ctype_of(decl: str):
-    """the ctypes type _lib.py must give a C parameter declaration of the header"""
-    decl = decl.strip()
-    if "*" in decl:
-        return C.c_void_p
-    return {"int": C.c_int, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double}[decl.split()[0]]
-
-
 def test_the_library_exports_the_feet_entry_points_with_the_headers_signatures():
     from general_motion_retargeting_amd import _lib
     from general_motion_retargeting_amd import motion_tracker as mt
@@ -77,31 +70,22 @@ def test_the_library_exports_the_feet_entry_points_with_the_headers_signatures()
         assert sym in _lib.EXPORTED_SYMBOLS
         m = re.search(r"\bint " + sym + r"\(([^;]*)\);", hdr)
         assert m, sym
-        params = [p for p in re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S).split(",")]
+        params = abi.parameters(hdr, sym)
         res, args = _lib._SIGS[sym]
-        assert res is C.c_int and args == [_ctype_of(p) for p in params], (sym, params, args)
+        assert res is C.c_int and args == params, (sym, params, args)
         # the comment in front of the prototype (a _dev call and its twin share one) cites the reference lines it replaces
         section = hdr[hdr.index("N11: tracker feet"):m.start()]
         comment = [c for c in re.findall(r"/\*.*?\*/", section, flags=re.S) if "\n" in c][-1]
         assert re.search(r"(t1|terrain)\.py:\d+", comment), sym
 
-    def fields(name):
-        body = re.search(r"typedef struct \{([^}]*)\} " + name, hdr).group(1)
-        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-        out = []
-        for decl in body.split(";"):
-            decl = decl.strip()
-            if decl:
-                out += [re.sub(r"\[.*\]", "", x).strip(" *") for x in re.sub(r"^(const\s+)?\w+\s+", "", decl).split(",")]
-        return out
     for name, struct in (("gmr_feet_config_t", _lib.FeetConfig), ("gmr_feet_in_t", _lib.FeetIn), ("gmr_feet_out_t", _lib.FeetOut)):
-        assert fields(name) == [f for f, _ in struct._fields_], name
+        assert abi.fields(hdr, name) == [f for f, _ in struct._fields_], name
     P = C.sizeof(C.c_void_p)
     assert C.sizeof(_lib.FeetIn) == 4 * P and C.sizeof(_lib.FeetOut) == 9 * P
     assert _lib.FeetConfig.feet_body.offset == 4 * P and _lib.FeetConfig.force_threshold.offset == 4 * P + 24 and C.sizeof(_lib.FeetConfig) == 4 * P + 56
     for define, value in (("GMR_FEET_TERMS", len(_lib.FEET_TERMS)), ("GMR_FEET_MAX_EDGES", _lib.FEET_MAX_EDGES), ("GMR_FEET_MAX_BODIES", _lib.FEET_MAX_BODIES),
                           ("GMR_FEET_DONE_CONTACT", _lib.FEET_DONE_CONTACT)):
-        assert re.search(rf"#define {define} {value}\b", hdr), define
+        assert abi.define(hdr, define) == value, define
     assert mt.FEET_TERMS == _lib.FEET_TERMS == fm.TERMS and mt.FEET_DONE_CONTACT == _lib.FEET_DONE_CONTACT == fm.DONE_CONTACT == 8
     assert (mt.FEET_MAX_EDGES, mt.FEET_MAX_BODIES) == (_lib.FEET_MAX_EDGES, _lib.FEET_MAX_BODIES)
     for name in ("set_terrain", "terrain_heights", "terrain_heights_dev", "set_feet", "feet", "feet_dev", "feet_state"):

@@ -166,7 +166,7 @@ def test_heading_frame_is_blind_to_drift_in_x_y_and_yaw_but_not_to_a_roll():
 def offline_tracker(ndof, ang_vel="world"):
     from general_motion_retargeting_amd import MotionTracker
     t = MotionTracker.__new__(MotionTracker)
-    t.library, t.num_envs, t.nrobot_dof, t.handle, t._links = _OfflineLibrary(ndof, ang_vel), 8, ndof, None, None
+    t._init_state(_OfflineLibrary(ndof, ang_vel), 8, ndof)
     return t
 
 

@@ -176,7 +176,7 @@ def offline_tracker(ndof=29, ang_vel="world", nbody=12, has_body=True, link_body
     lib = _OfflineLibrary(ndof, ang_vel)
     lib.nbody, lib.has_local_body_pos, lib.num_clips = nbody, has_body, 3
     lib.link_body_lists = link_body_lists if link_body_lists is not None else [[] for _ in range(3)]
-    t.library, t.num_envs, t.nrobot_dof, t.handle, t._links, t._preview = lib, 8, ndof, None, None, None
+    t._init_state(lib, 8, ndof)
     return t
 
 

@@ -13,6 +13,7 @@ import pytest
 from conftest import GOLDEN, ROOT
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_header as abi  # noqa: E402
 import proprio_mirror as pm  # noqa: E402
 import tracker_mirror as tm  # noqa: E402
 from test_motion_body_state_host import _OfflineLibrary  # noqa: E402
@@ -22,14 +23,6 @@ PROPRIO_SYMBOLS = ("gmr_motion_tracker_set_proprio", "gmr_motion_tracker_proprio
                    "gmr_motion_tracker_proprio_reset", "gmr_motion_tracker_proprio_state")
 F = np.float32
 EPS = 2.0 ** -24
-
-
-def _ctype_of(decl: str):
-    """the ctypes type _lib.py must give a C parameter declaration of the header"""
-    decl = decl.strip()
-    if "*" in decl:
-        return C.POINTER(C.c_int) if re.match(r"int\s*\*", decl) else C.c_void_p
-    return {"int": C.c_int, "float": C.c_float, "double": C.c_double}[decl.split()[0]]
 
 
 def test_the_library_exports_the_proprio_entry_points_with_the_headers_signatures():
@@ -43,26 +36,17 @@ def test_the_library_exports_the_proprio_entry_points_with_the_headers_signature
         assert sym in _lib.EXPORTED_SYMBOLS
         m = re.search(r"\bint " + sym + r"\(([^;]*)\);", hdr)
         assert m, sym
-        params = [p for p in re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S).split(",")]
+        params = abi.parameters(hdr, sym)
         res, args = _lib._SIGS[sym]
-        assert res is C.c_int and args == [_ctype_of(p) for p in params], (sym, params, args)
+        assert res is C.c_int and args == params, (sym, params, args)
         # the comment in front of the prototype (a _dev call and its twin share one) cites the reference lines it replaces
         section = hdr[hdr.index("N10: tracker proprioception"):m.start()]
         comment = [c for c in re.findall(r"/\*.*?\*/", section, flags=re.S) if "\n" in c][-1]
         assert re.search(r"t1\.py:\d+", comment), sym
     # the structs: the same fields in the same order
-    def fields(name):
-        body = re.search(r"typedef struct \{([^}]*)\} " + name, hdr).group(1)
-        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-        out = []
-        for decl in body.split(";"):
-            decl = decl.strip()
-            if decl:
-                out += [re.sub(r"\[.*\]", "", x).strip(" *") for x in re.sub(r"^(const\s+)?\w+\s+", "", decl).split(",")]
-        return out
     for name, struct in (("gmr_proprio_noise_t", _lib.ProprioNoise), ("gmr_proprio_config_t", _lib.ProprioConfig), ("gmr_proprio_in_t", _lib.ProprioIn),
                          ("gmr_proprio_out_t", _lib.ProprioOut)):
-        assert fields(name) == [f for f, _ in struct._fields_], name
+        assert abi.fields(hdr, name) == [f for f, _ in struct._fields_], name
     P = C.sizeof(C.c_void_p)
     assert C.sizeof(_lib.ProprioNoise) == 24 and C.sizeof(_lib.ProprioIn) == 8 * P and C.sizeof(_lib.ProprioOut) == 10 * P
     assert _lib.ProprioConfig.filter_weight.offset == 5 * P + 8 and _lib.ProprioConfig.noise.offset == 5 * P + 8 + 32 + 32
@@ -71,7 +55,7 @@ def test_the_library_exports_the_proprio_entry_points_with_the_headers_signature
                           ("GMR_PROPRIO_NOISE_BLOCKS", len(_lib.PROPRIO_NOISE_BLOCKS)), ("GMR_NOISE_NONE", _lib.NOISE_DISTRIBUTIONS["none"]),
                           ("GMR_NOISE_GAUSSIAN", _lib.NOISE_DISTRIBUTIONS["gaussian"]), ("GMR_NOISE_UNIFORM", _lib.NOISE_DISTRIBUTIONS["uniform"]),
                           ("GMR_NOISE_ADDITIVE", _lib.NOISE_OPERATIONS["additive"]), ("GMR_NOISE_SCALING", _lib.NOISE_OPERATIONS["scaling"])):
-        assert re.search(rf"#define {define} {value}\b", hdr), define
+        assert abi.define(hdr, define) == value, define
     assert mt.PROPRIO_TERMS == _lib.PROPRIO_TERMS == pm.TERMS and mt.PROPRIO_NOISE_BLOCKS == _lib.PROPRIO_NOISE_BLOCKS == pm.NOISE_BLOCKS
     assert mt.PROPRIO_MAX_EXTRA == _lib.PROPRIO_MAX_EXTRA and mt.NOISE_DISTRIBUTIONS == _lib.NOISE_DISTRIBUTIONS
     for name in ("set_proprio", "proprio", "proprio_dev", "proprio_reset", "proprio_reset_dev", "proprio_state", "proprio_layout"):
@@ -84,8 +68,7 @@ def test_the_library_exports_the_proprio_entry_points_with_the_headers_signature
 def offline_tracker(N=8, R=5):
     from general_motion_retargeting_amd import MotionTracker
     t = MotionTracker.__new__(MotionTracker)
-    t.library, t.num_envs, t.nrobot_dof, t.handle = _OfflineLibrary(R, "world"), N, R, None
-    t._links, t._preview, t._adaptive, t._anchors, t._control, t._proprio = None, None, None, False, None, None
+    t._init_state(_OfflineLibrary(R, "world"), N, R)
     return t
 
 
