@@ -19,6 +19,8 @@ pytestmark = pytest.mark.gpu
 F = np.float32
 REFS = ("ref_root_pos", "ref_root_rot", "ref_root_vel", "ref_root_ang_vel", "ref_dof_pos", "ref_dof_vel")
 STATE = ("clip", "time", "length", "draws")
+ROOT_ROT_BOUND = 1e-6                    # ref_root_rot against the mirror (sin / cos / acos of the device's and NumPy's float32 libraries)
+TERM_BOUND = 2e-6                        # x max(1, |w|): err / term / total against the float64 formulas
 
 
 @pytest.fixture(scope="module")
@@ -44,7 +46,7 @@ def mirror_library(lib, motions, ang_vel="world"):
 def assert_refs_equal(got, want, rows=slice(None)):
     for k in REFS:
         if k == "ref_root_rot":          # (sin / cos / acos of the device's and NumPy's float32 libraries)
-            close(got[k][rows], want[k][rows], abs_=1e-6)
+            close(got[k][rows], want[k][rows], abs_=ROOT_ROT_BOUND)
         else:
             assert np.array_equal(_bits(got[k][rows]), _bits(want[k][rows])), k
 
@@ -72,7 +74,7 @@ def close_terms(out, sim, m):
     for k in ("err", "term", "total"):
         w = np.asarray(want[k], dtype=np.float64)
         assert out[k].dtype == F and out[k].shape == w.shape
-        tol = 2e-6 * np.maximum(1.0, np.abs(w))
+        tol = TERM_BOUND * np.maximum(1.0, np.abs(w))
         bad = ~(np.abs(out[k] - w) <= tol) & ~(np.isnan(out[k]) & np.isnan(w))
         assert not bad.any(), (k, np.abs(out[k] - w)[bad].max())
 

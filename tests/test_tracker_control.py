@@ -27,6 +27,7 @@ DT = 0.02
 D = 2.0
 G = 64                                   # guard floats behind every device output
 SENTINEL = F(-77.25)
+START_UP_BOUND = 2e-6                    # x max(1, |x|): start-up targets against the float64 formula (the tracker's bound)
 
 
 @pytest.fixture(scope="module")
@@ -153,7 +154,7 @@ def test_startup_targets_against_the_float64_formula_on_the_devices_reference_ro
     want = base + (d64(cfg["k"]) * clipped.astype(d64)) * d64(cfg["g0"])
     dev = np.abs(got["dof_targets"].astype(d64) - want)[startup] / np.maximum(1.0, np.abs(want[startup]))
     print(f"start-up targets: largest deviation from float64 {dev.max():.3e} of max(1, |x|) (bound 2e-6)")
-    assert dev.max() <= 2e-6
+    assert dev.max() <= START_UP_BOUND
     # at step 0 the target is the default pose plus the action term, whatever the reference says
     zero = got["dof_targets"][3]
     assert np.array_equal(zero, (cfg["default_pos"] * F(1.0) + ref[3] * F(0.0) + (cfg["k"] * clipped[3]) * cfg["g0"]).astype(F))

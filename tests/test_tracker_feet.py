@@ -40,6 +40,7 @@ SCALES = {"collision": -1.0, "feet_slip": -0.1, "feet_vel_z": -0.05, "feet_roll"
 # in float64.  Angles (feet_roll, feet_yaw) in units of 2^-24 max(1, 3 pi): largest met 1.698.  The gait columns in units of 2^-24: 1.0.
 ANGLE_BOUND = 4 * 1.698
 GAIT_BOUND = 4 * 1.0
+CLEARANCE_MARGIN, ANGLE_MARGIN = 2e-5, 2e-3          # how far inputs stay from the contact threshold and from the angles' seams
 
 
 def field_of(rng):
@@ -79,7 +80,7 @@ def inputs(rng, mirror, n=N):
         x = draw(rng, mirror, n)
         trial = copy.deepcopy(mirror)
         mirror_step(trial, x)
-        if trial.margins["clearance"] > 2e-5 and trial.margins["angle"] > 2e-3:
+        if trial.margins["clearance"] > CLEARANCE_MARGIN and trial.margins["angle"] > ANGLE_MARGIN:
             return x
     raise AssertionError("no draw away from the discontinuities")
 

@@ -41,6 +41,7 @@ MEASURED = {"log_prob": 10.290834920480847, "ratio": 24.347130525329316, "grad_l
             "bound_loss": 0.07604557275772095, "entropy": 0.23118088059273517, "loss": 0.13946516132496709, "kl_mean": 0.6246731316205114,
             "clip_fraction": 0.0}
 BOUND = {k: 4.0 * v for k, v in MEASURED.items()}
+KL_MARGIN = 1e-3                                                      # the KL stays this far, relatively, from both thresholds of the rule
 MARGIN = 16.0 * BOUND["ratio"]                                        # no row's ratio within this many units of lo or hi
 
 
@@ -113,7 +114,7 @@ def check_inputs(shape):
     assert near > MARGIN, (shape, near, MARGIN)
     assert (m32["w"] == m64["w"]).all() and units(m32["ratio"], m64["ratio"]) <= MEASURED["ratio"]
     kl = m64["terms"][5]
-    assert min(abs(kl / (2 * cfg["desired_kl"]) - 1), abs(kl / (cfg["desired_kl"] / 2) - 1)) > 1e-3      # the rule's branch is not in doubt
+    assert min(abs(kl / (2 * cfg["desired_kl"]) - 1), abs(kl / (cfg["desired_kl"] / 2) - 1)) > KL_MARGIN      # the rule's branch is not in doubt
     return x, cfg, m32, m64
 
 
