@@ -242,7 +242,13 @@ int gmr_solver_create(const gmr_model_t* model, const gmr_taskset_t* taskset, gm
     gmr::IkSchedule sch = gmr::make_ik_schedule(s->model, s->ts, v == 0 ? 64 : 64 * (nw - 1));
     gmr::IkLayout& lay = v == 0 ? s->layout : s->layout4;
     lay = gmr::make_ik_layout(s->model, s->ts, sch, nw);
-    if (lay.smem_bytes > 160 * 1024 - 1024) { delete s; return fail(GMR_ERR_ARG, "robot too large for LDS"); }
+    // a robot that does not decompose is never launched with helpers (gmr_retarget_streams_dev): its 4-wavefront layout,
+    // whose schedule lives in LDS and grows with the task set, is neither checked nor uploaded.  layout4 keeps tree_ok = 0.
+    if (nw == 4 && !lay.tree_ok) continue;
+    if (lay.smem_bytes > 160 * 1024 - 1024) {
+      delete s;
+      return fail(GMR_ERR_ARG, "robot too large for LDS: the %d-wavefront layout needs %d bytes of %d", nw, lay.smem_bytes, 160 * 1024 - 1024);
+    }
     std::vector<char> img = gmr::make_ik_image(s->model, s->ts, sch, lay);
     gmr::DeviceBlock& dst = v == 0 ? s->image : s->image4;
     if ((e = dst.reserve(img.size())) != hipSuccess) break;
@@ -301,7 +307,7 @@ int gmr_solver_set_dispatch(gmr_solver_t* s, int frames_per_item) {
   return GMR_OK;
 }
 
-int gmr_retarget_lds_bytes(const gmr_solver_t* s) { return s ? s->layout4.smem_bytes : 0; }
+int gmr_retarget_lds_bytes(const gmr_solver_t* s) { return !s ? 0 : s->layout4.tree_ok ? s->layout4.smem_bytes : s->layout.smem_bytes; }
 
 int gmr_retarget_streams_dev(gmr_solver_t* s, int S, int T, const double* d_q0, const double* d_human,
                              const int32_t* d_len, int flags, double* d_q_out, int32_t* d_nsolve,

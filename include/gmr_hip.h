@@ -162,7 +162,8 @@ int gmr_host_free(void* ptr);
 int gmr_host_register(void* ptr, size_t bytes);
 int gmr_host_unregister(void* ptr);
 
-/* LDS bytes per stream of the IK kernel for this solver (occupancy reporting). */
+/* LDS bytes per stream of the IK kernel for this solver (occupancy reporting): of the 4-wavefront layout when the robot
+ * decomposes into trunk and limbs, else of the one-wavefront layout, the only one such a robot is launched with. */
 int gmr_retarget_lds_bytes(const gmr_solver_t* solver);
 
 /* ---- H8-H9: post-hoc batched FK (float32) ------------------------------------------------- */

@@ -31,6 +31,17 @@
 #define GMR_MAX_TASKS  16  /* frame tasks per stage (Hi: 15)                            */
 #define GMR_MAX_HUMAN  16  /* human bodies consumed per frame (G1: 14)                  */
 #define GMR_MAX_PAIRS  384 /* (task, ancestor dof) pairs per stage (G1: 157)            */
+/*
+ * What a (robot, task set) inside these limits is still bounded by: the LDS of the layout it is launched with
+ * (162 816 B per workgroup, csrc/gmr_ik_layout.h).
+ *   - A robot that does NOT decompose into a trunk of <= 10 dofs and <= 4 limbs of <= 8 (make_ik_tree) only ever runs the
+ *     one-wavefront kernel, whose layout holds no schedule and is 66 112 B whatever the task set: for it the limits above
+ *     are the real ones, K = 16 with P = 384 included (tests/ik_capacity.py, `at_abi_caps`).
+ *   - A robot that decomposes also gets the 4-wavefront layout, whose H schedule lives in LDS and grows with the terms of H.
+ *     Its tasks list at most 6 + 4 + 8 = 18 dofs, so P <= 288; over the task placements of
+ *     tests/test_ik_capacity_host.py the largest such layout is 119 104 B.  gmr_solver_create refuses
+ *     ("robot too large for LDS") a layout above the limit; none inside these limits is known to reach it.
+ */
 
 #ifdef __cplusplus
 extern "C" {

@@ -3,7 +3,10 @@
 // size class, whether the task set fits the throughput kernel (gmr_ik_wide_layout.h), the stage switches of
 // make_ik_params and the tasks / (task, dof) pairs per stage.
 //   tree_ok=1 tree_small=1 tree_class=36 tree_wide_fits=1 tree_use0=1 tree_use1=3 K=14,14 P=124,154 trunk=0,1,...
-//   limb0=... limb1=... limb2=... limb3=...
+//   limb0=... limb1=... limb2=... limb3=... tree_nbody=38 tree_nhinge=29 tree_nhuman=14 tree_maxd=12 tree_nhop=4
+//   tree_smem1=40624 tree_smem4=62896
+// (bodies, hinges, human bodies, bodies on the longest root -> leaf path, FK rounds, LDS bytes of the one- and the
+// 4-wavefront layout; the latter is stated for a robot that does not decompose too, although it is never launched)
 #include <cstdio>
 
 #include "../../general_motion_retargeting_amd/csrc/gmr_ik_layout.h"
@@ -28,6 +31,10 @@ int main(int argc, char** argv) {
     std::printf(" limb%d=", l);
     for (int a = 0, k = 0; a < 8; a++) if (tr.limb[l][a] >= 0) std::printf(k++ ? ",%d" : "%d", tr.limb[l][a]);
   }
+  // sizes: bodies, hinges, human bodies, bodies on the longest path, FK rounds, LDS bytes of the two launch shapes
+  const gmr::IkLayout L1 = gmr::make_ik_layout(m, ts, gmr::make_ik_schedule(m, ts, 64), 1);
+  std::printf(" tree_nbody=%d tree_nhinge=%d tree_nhuman=%d tree_maxd=%d tree_nhop=%d tree_smem1=%d tree_smem4=%d", L.nb, L.nh, L.nhum,
+              L.maxd, L.nhop, L1.smem_bytes, L.smem_bytes);
   std::printf("\n");
   return 0;
 }
