@@ -723,6 +723,8 @@ int gmr_fk_create(int nbody, const int32_t* parent, const float* local_t, const 
   if (!out || !parent || !local_t || !local_r || !dof_idx || !axis) return fail(GMR_ERR_ARG, "null argument");
   if (nbody < 1 || nbody > gmr::FK_MAX_BODIES) return fail(GMR_ERR_ARG, "nbody out of range");
   if (ndof < 0) return fail(GMR_ERR_ARG, "ndof negative");
+  // (every dof drives one body: dof_body[] below has FK_MAX_BODIES entries)
+  if (ndof > gmr::FK_MAX_BODIES) return fail(GMR_ERR_ARG, "ndof = %d out of range [0, %d]", ndof, gmr::FK_MAX_BODIES);
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(GMR_ERR_NO_DEVICE, "no HIP device visible");
   gmr_fk* k = new (std::nothrow) gmr_fk;
@@ -741,12 +743,14 @@ int gmr_fk_create(int nbody, const int32_t* parent, const float* local_t, const 
   }
   if (maxd > gmr::FK_MAX_DEPTH) { delete k; return fail(GMR_ERR_ARG, "tree too deep"); }
   t.maxd = maxd;
-  // LDS slots: bodies with >= 2 children are parked; a later child reloads its parent from the slot
+  // LDS slots: a body with a child that does not follow it immediately is parked; that child reloads its parent from the
+  // slot.  In depth-first body order (what the reference's parser yields) these are the bodies with >= 2 children; any other
+  // order with parent[b] < b is accepted too, and there an only child may come later than right behind its parent.
   {
-    int nchild[gmr::FK_MAX_BODIES] = {0};
-    for (int b = 1; b < nbody; b++) nchild[parent[b]]++;
+    bool later_child[gmr::FK_MAX_BODIES] = {false};
+    for (int b = 1; b < nbody; b++) if (parent[b] != b - 1) later_child[parent[b]] = true;
     int ns = 0;
-    for (int b = 0; b < nbody; b++) t.save_slot[b] = (short)(nchild[b] >= 2 ? ns++ : -1);
+    for (int b = 0; b < nbody; b++) t.save_slot[b] = (short)(later_child[b] ? ns++ : -1);
     t.nslot = ns > 0 ? ns : 1;
     t.load_slot[0] = -1;
     for (int b = 1; b < nbody; b++) t.load_slot[b] = (short)(parent[b] == b - 1 ? -1 : t.save_slot[parent[b]]);

@@ -136,12 +136,12 @@ __global__ __launch_bounds__(FK_BLOCK) void fk_batch_kernel(const FkTree* __rest
     } else if (on) {
       float* op = body_pos + f * nb * 3;
       op[0] = px; op[1] = py; op[2] = pz;
-      if (body_rot) *reinterpret_cast<float4*>(body_rot + f * nb * 4) = make_float4(rot.x, rot.y, rot.z, rot.w);
+      if (body_rot) { float* orr = body_rot + f * nb * 4; orr[0] = rot.x; orr[1] = rot.y; orr[2] = rot.z; orr[3] = rot.w; }   // (this variant runs when a destination is not 16-B aligned)
       zmin = pz;
     }
   }
   FkBodyRec nxt = tree->rec[nb > 1 ? 1 : 0];
-  float ang_nxt = STAGED ? (outb + tid * row)[3] : 0.0f;     // parked joint angle of body 1 (garbage if it has no joint: unused)
+  float ang_nxt = STAGED ? (outb + tid * row)[nb > 1 ? 3 : 0] : 0.0f;     // parked joint angle of body 1 (garbage if it has no joint: unused)
   for (int j = 1; j < nb; j++) {
     // wave-uniform tree data: ONE 64-byte scalar load per body, issued one body ahead; so is the parked joint angle
     const FkBodyRec cur = nxt;
@@ -182,7 +182,7 @@ __global__ __launch_bounds__(FK_BLOCK) void fk_batch_kernel(const FkTree* __rest
     } else if (on) {
       float* op = body_pos + (f * nb + j) * 3;
       op[0] = px; op[1] = py; op[2] = pz;
-      if (body_rot) *reinterpret_cast<float4*>(body_rot + (f * nb + j) * 4) = make_float4(rot.x, rot.y, rot.z, rot.w);
+      if (body_rot) { float* orr = body_rot + (f * nb + j) * 4; orr[0] = rot.x; orr[1] = rot.y; orr[2] = rot.z; orr[3] = rot.w; }
       zmin = fminf(zmin, pz);
     }
   }

@@ -35,7 +35,7 @@ struct FkTree {
   short dof_body[FK_MAX_BODIES];               // body whose joint dof d drives
   short depth[FK_MAX_BODIES];
   short load_slot[FK_MAX_BODIES];              // LDS slot holding the parent transform, or -1: parent == previous body
-  short save_slot[FK_MAX_BODIES];              // LDS slot this body's transform is parked in (>= 2 children), or -1
+  short save_slot[FK_MAX_BODIES];              // LDS slot this body's transform is parked in (a child comes later than right behind it), or -1
   short parent[FK_MAX_BODIES];                 // parent body (0 for body 0): staged outputs are re-read as parent transforms
   short chain[FK_MAX_BODIES * FK_MAX_DEPTH];   // [nbody][maxd] packed with stride maxd
   float local_t[FK_MAX_BODIES * 3];
@@ -193,6 +193,19 @@ inline const char* fk_build_split(FkTree& t, const int32_t* parent, int maxw) {
         const int when = 1 + nA < m ? 1 + nA : m;
         barrier_at[w] = (at >= 0 && at < when) ? at : when;
       }
+    }
+  }
+  // More records than wrec holds (a long trunk that every wavefront walks again, 4 x 22 + 42 bodies): such a tree merely
+  // does not split.
+  {
+    int total = 0;
+    for (int w = 0; w < t.nwave; w++) total += nlist[w];
+    if (total > 2 * FK_MAX_BODIES) {
+      t.nwave = 1;
+      nlist[0] = nbody;
+      for (int b = 0; b < nbody; b++) { lists[0][b] = b; shared_slot[b] = -1; extra_dst[b] = 0; }
+      for (int w = 0; w < FK_MAX_WAVES; w++) barrier_at[w] = -1;
+      nshared = 0; share_owner = -1;
     }
   }
   bool owned[FK_MAX_BODIES] = {false};
