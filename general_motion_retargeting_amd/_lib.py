@@ -194,6 +194,11 @@ _SIGS = {
     "gmr_motion_tracker_log_prob": (C.c_int, [C.c_void_p] * 5),
     "gmr_motion_tracker_loss_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "gmr_motion_tracker_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "gmr_motion_tracker_set_optimizer": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p] + [C.c_double] * 5),
+    "gmr_motion_tracker_optimizer_step_dev": (C.c_int, [C.c_void_p] * 5),
+    "gmr_motion_tracker_optimizer_step": (C.c_int, [C.c_void_p] * 4),
+    "gmr_motion_tracker_optimizer_state": (C.c_int, [C.c_void_p] * 4),
+    "gmr_motion_tracker_optimizer_load_state": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "gmr_comm_create": (C.c_int, [C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),
     "gmr_comm_destroy": (C.c_int, [C.c_void_p]),
     "gmr_comm_rank": (C.c_int, [C.c_void_p]),
@@ -980,6 +985,11 @@ LOSS_IN = (("loc", _F, ("M", "A")), ("logstd", _F, ("A",)), ("actions", _F, ("M"
 LOSS_OUT = (("grad_loc", _F, ("M", "A")), ("grad_logstd", _F, ("A",)), ("grad_values", _F, ("M",)), ("log_prob", _F, ("M",)),
             ("terms", "float64", (len(LOSS_TERMS),)))
 LOSS_IN_FIELDS, LOSS_OUT_FIELDS = _arrays(LOSS_IN), _arrays(LOSS_OUT)
+
+
+# gmr_motion_tracker_set_optimizer / _optimizer_step[_dev] / _optimizer_state / _optimizer_load_state (include/gmr_hip.h, "tracker optimiser")
+OPT_CHUNK, OPT_MAX_TENSORS = 1024, 32
+OPT_INFO = ("total_norm", "coef", "learning_rate", "step")
 
 
 class LossIn(C.Structure):

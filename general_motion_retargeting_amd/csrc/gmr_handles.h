@@ -7,7 +7,8 @@
 // the two arrays behind them, gmr_tracker_commands.hip its command and disturbance tables and the arrays of the velocity commands,
 // gmr_tracker_episode.hip its reset-state and reward tables, the reset counters and the arrays of the episode statistics,
 // gmr_tracker_rollout.hip its rollout configuration and the partial sums of an advantages call, gmr_tracker_loss.hip its loss configuration,
-// the partial sums of a loss call and the learning rate.
+// the partial sums of a loss call and the learning rate, gmr_tracker_optim.hip its optimiser configuration, the Adam state, the chunk table
+// and the scalars of a step.
 #pragma once
 #include <stdint.h>
 
@@ -269,6 +270,27 @@ struct LossTables {
   double* part = nullptr;                   // [A + 6][ceil(M / GMR_LOSS_ROWS)] the partial sums of one call
   double* lr = nullptr;                     // [1] the learning rate
 };
+// one chunk of the optimiser's passes: GMR_OPT_CHUNK consecutive elements of one tensor, fewer at the tensor's end
+struct OptimChunk {
+  int64_t first;                            // the first element, inside its tensor
+  int64_t state;                            // the same element inside exp_avg / exp_avg_sq (floats from the block's start)
+  int32_t tensor, count;
+};
+// the optimiser of a tracker: the configuration as given and device pointers into the optimiser block
+struct OptimTables {
+  int32_t K = 0;                            // tensors; 0: the optimiser was never set
+  int32_t follow = 0;                       // the rate follows the loss block
+  int64_t chunks = 0, total = 0;            // chunks and elements of all tensors
+  int64_t size[GMR_OPT_MAX_TENSORS] = {};   // elements per tensor
+  int64_t off[GMR_OPT_MAX_TENSORS] = {};    // where a tensor's state starts in exp_avg / exp_avg_sq, in floats: on 256 bytes
+  int64_t state_floats = 0;                 // the length of exp_avg and of exp_avg_sq with the padding
+  double beta1 = 0.0, beta2 = 0.0, eps = 0.0, max_norm = 0.0;      // as given
+  const OptimChunk* table = nullptr;        // [chunks]
+  float *exp_avg = nullptr, *exp_avg_sq = nullptr;      // [state_floats]
+  double* part = nullptr;                   // [chunks] the partial sums of one step
+  double* state = nullptr;                  // [4] the rate of the next step, the step count, beta1^t, beta2^t
+  float* scal = nullptr;                    // [4] coef, bc2s, ns of the step in flight
+};
 }  // namespace gmr
 
 struct gmr_motion_tracker {
@@ -314,6 +336,8 @@ struct gmr_motion_tracker {
   gmr::DeviceBlock rollout_block; // the partial sums of an advantages call: one allocation, made by gmr_motion_tracker_set_rollout
   gmr::LossTables loss;          // loss.on = 0 until gmr_motion_tracker_set_loss configures it
   gmr::DeviceBlock loss_block;   // the partial sums of a loss call and the learning rate: one allocation, made by gmr_motion_tracker_set_loss
+  gmr::OptimTables optim;        // optim.K = 0 until gmr_motion_tracker_set_optimizer configures it
+  gmr::DeviceBlock optim_block;  // the Adam state, the chunk table, the partial sums and the scalars of a step: one allocation, made by gmr_motion_tracker_set_optimizer
   std::vector<double> clip_w;    // the clip weights as given at creation (empty: uniform)
   std::mutex mu;                 // the tables, and the whole of every synchronous entry point
 };

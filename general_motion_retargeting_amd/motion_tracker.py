@@ -20,7 +20,10 @@ with sensor noise, the regularisation penalties, the state-based termination and
 ``csrc/gmr_tracker_feet.hip``): the bilinear terrain height the reference interpolates on the host, the feet pose and edge contacts, the gait
 clock, the contact-force termination, ``collision`` and the seven ``feet_*`` terms, in one launch.  :meth:`MotionTracker.commands` and
 :meth:`MotionTracker.disturb` take what was left of the step (``csrc/gmr_tracker_commands.hip``): the velocity commands
-with their resampling and curriculum, the command-tracking terms, and the kicks and pushes.
+with their resampling and curriculum, the command-tracking terms, and the kicks and pushes.  On the learner's side
+:meth:`MotionTracker.record` / :meth:`MotionTracker.advantages` (6u), :meth:`MotionTracker.loss` (6v) and
+:meth:`MotionTracker.optimizer_step` (6x, ``csrc/gmr_tracker_optim.hip``: the clip of the gradient norm and the Adam step in three
+launches) leave the networks and their backward pass as the only part of a training iteration that is not a call of this class.
 
 No GPU framework is imported here: :meth:`MotionTracker.step` takes and returns NumPy arrays, :meth:`MotionTracker.step_dev` reads
 and writes device memory the caller names -- ``_lib.DeviceBuffer``, a raw address, or anything with ``data_ptr()``.
@@ -176,6 +179,7 @@ class MotionTracker:
     _rewards = None          # the checked configuration once set_rewards has laid the reward columns out
     _rollout = None          # the checked configuration once set_rollout has configured the rollout
     _loss = None             # the checked configuration, with its rows and columns, once set_loss has configured the loss head
+    _optim = None            # the checked configuration (sizes, rate or None: follow, betas, eps, max_norm) once set_optimizer has run
     _disturb = None          # (kick_every, push_every, push_duration) once set_disturbances has configured kicks and pushes
 
     def _init_state(self, library, num_envs, nrobot_dof=None) -> None:
@@ -2012,6 +2016,146 @@ class MotionTracker:
         table, _ = self._loss_in("loss_dev", c, inputs, update_lr, device=True)
         _lib.check(_lib.lib().gmr_motion_tracker_loss_dev(self.handle, C.byref(table), C.byref(res), 1 if update_lr else 0, _lib._s(stream)))
 
+    # ---- the clip of the gradient norm and the Adam step --------------------------------------------------------
+    def _optimizer_setup(self, sizes, learning_rate, betas, eps, max_norm):
+        """the checks of :meth:`set_optimizer`, all of them before the library is loaded -> a dict of the checked values"""
+        what = "set_optimizer"
+        try:
+            sizes = tuple(int(n) for n in sizes)
+        except TypeError:
+            raise ValueError(f"{what}: sizes is a list of element counts, one per tensor") from None
+        if not 1 <= len(sizes) <= _lib.OPT_MAX_TENSORS:
+            raise ValueError(f"{what}: K = {len(sizes)} tensors, 1 .. {_lib.OPT_MAX_TENSORS} are taken")
+        for k, n in enumerate(sizes):
+            if not 1 <= n <= 1 << 40:
+                raise ValueError(f"{what}: sizes[{k}] = {n}: at least 1 element is needed")
+        if len(tuple(betas)) != 2:
+            raise ValueError(f"{what}: betas = {betas}: two numbers are needed")
+        b1, b2 = (float(b) for b in betas)
+        for k, b in (("beta1", b1), ("beta2", b2)):
+            if not 0.0 <= b < 1.0:
+                raise ValueError(f"{what}: {k} = {b}: a number in [0, 1) is needed")
+        eps, max_norm = float(eps), float(max_norm)
+        for k, v in (("eps", eps), ("max_norm", max_norm)):
+            if not np.isfinite(v) or v <= 0.0:
+                raise ValueError(f"{what}: {k} = {v}: a finite number above 0 is needed")
+        if learning_rate is None:
+            self._need_loss(f"{what}: learning_rate=None follows the loss block's rate")
+        else:
+            learning_rate = float(learning_rate)
+            if not np.isfinite(learning_rate) or learning_rate <= 0.0:
+                raise ValueError(f"{what}: learning_rate = {learning_rate}: a finite number above 0, or None, is needed")
+        return {"sizes": sizes, "learning_rate": learning_rate, "betas": (b1, b2), "eps": eps, "max_norm": max_norm}
+
+    def set_optimizer(self, sizes, *, learning_rate: Optional[float] = None, betas=(0.9, 0.999), eps: float = 1e-8, max_norm: float = 1.0) -> None:
+        """Configures the optimiser of runner.py:33 with the clip of :164: ``torch.optim.Adam`` at torch's defaults over ``K = len(sizes)``
+        tensors of ``sizes[k]`` float32 elements (at most 32 tensors), the total norm of the gradients clipped to ``max_norm``.  ``exp_avg``
+        and ``exp_avg_sq`` live in the tracker, zero, at step 0.  ``learning_rate=None`` FOLLOWS the loss block (needs :meth:`set_loss`
+        first): the optimiser keeps a rate of its own, which starts as the loss block's; a step uses it and then takes the loss block's
+        current rate for the next step.  With ``loss_dev(update_lr=True)`` enqueued before the step in every mini-epoch this is the
+        reference's order: the step of mini-epoch n runs at the rate the rule left at the end of mini-epoch n - 1 (runner.py:165 before
+        :175-180).  A number fixes the rate; :meth:`set_loss` is not needed then.  Synchronous."""
+        c = self._optimizer_setup(sizes, learning_rate, betas, eps, max_norm)
+        n = np.array(c["sizes"], np.int64)
+        lr = float("nan") if c["learning_rate"] is None else c["learning_rate"]
+        _lib.check(_lib.lib().gmr_motion_tracker_set_optimizer(self.handle, len(n), _lib._ptr(n), lr, *c["betas"], c["eps"], c["max_norm"]))
+        self._optim = c
+
+    def _need_optimizer(self, what: str):
+        c = self._optim
+        if c is None:
+            raise ValueError(f"{what}: the optimiser is not set on this tracker, call set_optimizer() first")
+        if c["learning_rate"] is None:
+            self._need_loss(f"{what}: the optimiser follows the loss block's rate")
+        return c
+
+    @staticmethod
+    def _optimizer_lists(what: str, c, **lists):
+        K = len(c["sizes"])
+        out = []
+        for name, x in lists.items():
+            x = list(x)
+            if len(x) != K:
+                raise ValueError(f"{what}: {name} names {len(x)} tensors, the optimiser was set for K = {K}")
+            out.append(x)
+        return out
+
+    def optimizer_step_dev(self, params, grads, info=None, stream=None) -> None:
+        """``clip_grad_norm_`` and ``optimizer.step()`` (runner.py:164-165) on device memory, asynchronous on ``stream``: the norm pass, the
+        fold and the update pass -- at most THREE launches, no host synchronisation, no copy.  ``params`` and ``grads`` are lists of ``K``
+        tensors in the order of :meth:`set_optimizer` (``f32[sizes[k]]``; each a ``_lib.DeviceBuffer``, a raw address or an object with
+        ``data_ptr()``: a torch loop hands ``[p.data for p in model.parameters()]`` and ``[p.grad for ...]``); ``None`` in ``grads`` skips
+        the tensor, as ``p.grad is None`` does.  The gradients are only read: the clipped gradient is never stored.  ``info`` (``f64[4]`` on
+        the device, optional) gets total_norm, coef, the rate used and the step count."""
+        c = self._need_optimizer("optimizer_step_dev")
+        params, grads = self._optimizer_lists("optimizer_step_dev", c, params=params, grads=grads)
+        K = len(params)
+        tp, tg = (C.c_void_p * K)(), (C.c_void_p * K)()
+        for k, n in enumerate(c["sizes"]):
+            p = _dev_ptr(params[k], f"params[{k}]", "float32", n)
+            if p is None or not p.value:
+                raise ValueError(f"optimizer_step_dev: params[{k}] is needed (a tensor is skipped through grads[{k}] = None)")
+            g = _dev_ptr(grads[k], f"grads[{k}]", "float32", n)
+            tp[k], tg[k] = p.value, None if g is None else g.value
+        d_info = _dev_ptr(info, "info", "float64", len(_lib.OPT_INFO))
+        _lib.check(_lib.lib().gmr_motion_tracker_optimizer_step_dev(self.handle, tp, tg, d_info, _lib._s(stream)))
+
+    def optimizer_step(self, params, grads):
+        """:meth:`optimizer_step_dev` on host arrays -> ``(the new parameters, a list of K arrays in the shapes given; info f64[4])``.  The
+        arrays handed in are not written."""
+        c = self._need_optimizer("optimizer_step")
+        params, grads = self._optimizer_lists("optimizer_step", c, params=params, grads=grads)
+        K = len(params)
+        new, keep = [], []
+        tp, tg = (C.c_void_p * K)(), (C.c_void_p * K)()
+        for k, n in enumerate(c["sizes"]):
+            if params[k] is None:
+                raise ValueError(f"optimizer_step: params[{k}] is needed (a tensor is skipped through grads[{k}] = None)")
+            p = np.array(params[k], dtype=np.float32, order="C")                  # (a copy: the step writes it)
+            g = None if grads[k] is None else np.ascontiguousarray(grads[k], dtype=np.float32)
+            for name, a in (("params", p), ("grads", g)):
+                if a is not None and a.size != n:
+                    raise ValueError(f"optimizer_step: {name}[{k}]: {a.size} elements, {n} needed")
+            new.append(p)
+            keep.append(g)
+            tp[k], tg[k] = p.ctypes.data, None if g is None else g.ctypes.data
+        info = np.empty(len(_lib.OPT_INFO), np.float64)
+        _lib.check(_lib.lib().gmr_motion_tracker_optimizer_step(self.handle, tp, tg, _lib._ptr(info)))
+        return new, info
+
+    def optimizer_state(self) -> Optional[Dict[str, object]]:
+        """``{"step": int, "exp_avg": [K arrays], "exp_avg_sq": [K arrays]}``, flat ``f32[sizes[k]]`` each: what the ``state`` of
+        ``torch.optim.Adam.state_dict()`` holds per parameter (INTEGRATION.md has the mapping); ``None`` when the optimiser was never set.
+        Synchronises."""
+        c = self._optim
+        if c is None:
+            return None
+        total = sum(c["sizes"])
+        step, m, v = C.c_int64(0), np.empty(total, np.float32), np.empty(total, np.float32)
+        _lib.check(_lib.lib().gmr_motion_tracker_optimizer_state(self.handle, C.byref(step), _lib._ptr(m), _lib._ptr(v)))
+        cut = np.cumsum(c["sizes"])[:-1]
+        return {"step": int(step.value), "exp_avg": np.split(m, cut), "exp_avg_sq": np.split(v, cut)}
+
+    def load_optimizer_state(self, state) -> None:
+        """Continues from a state :meth:`optimizer_state` returned (or one mapped from a reference checkpoint, runner.py:95): ``step >= 0``
+        and ``K`` arrays each of ``exp_avg`` and ``exp_avg_sq``, of any shape with ``sizes[k]`` elements.  In follow mode the next step
+        runs at the loss block's current rate.  Synchronous."""
+        c = self._need_optimizer("load_optimizer_state")
+        unknown = sorted(set(state) - {"step", "exp_avg", "exp_avg_sq"})
+        if unknown or len(state) != 3:
+            raise ValueError(f"load_optimizer_state: the state holds step, exp_avg and exp_avg_sq (got {sorted(state)})")
+        step = int(state["step"])
+        if step != state["step"] or not 0 <= step <= 1 << 40:
+            raise ValueError(f"load_optimizer_state: step = {state['step']}: a whole number, at least 0, is needed")
+        flat = []
+        for name, x in zip(("exp_avg", "exp_avg_sq"), self._optimizer_lists("load_optimizer_state", c, exp_avg=state["exp_avg"], exp_avg_sq=state["exp_avg_sq"])):
+            x = [np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in x]
+            for k, (a, n) in enumerate(zip(x, c["sizes"])):
+                if a.size != n:
+                    raise ValueError(f"load_optimizer_state: {name}[{k}]: {a.size} elements, {n} needed")
+            flat.append(np.concatenate(x))
+        _lib.check(_lib.lib().gmr_motion_tracker_optimizer_load_state(self.handle, step, _lib._ptr(flat[0]), _lib._ptr(flat[1])))
+
     # ---- the step ---------------------------------------------------------------------------------------------------------
     def _counts(self):
         return _lib.widths(_lib.TRACKER_OUT, R=self.nrobot_dof), _lib.widths(_lib.TRACKER_SIM, R=self.nrobot_dof)
@@ -2307,6 +2451,7 @@ class MotionTracker:
             _lib.lib().gmr_motion_tracker_destroy(h)
             self.handle = None
             self._proprio = None          # the state arrays went with the handle
+            self._optim = None            # and so did exp_avg and exp_avg_sq
 
     def __del__(self):
         try:

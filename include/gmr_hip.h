@@ -1484,6 +1484,58 @@ int gmr_motion_tracker_loss_dev(gmr_motion_tracker_t* t, const gmr_loss_in_t* in
                                 void* stream);                                                      /* asynchronous */
 int gmr_motion_tracker_loss(gmr_motion_tracker_t* t, const gmr_loss_in_t* in, const gmr_loss_out_t* out, int update_lr);
 
+/* ---- N16: tracker optimiser (the clip of the gradient norm and the Adam step of a motion tracker) ---- */
+/* What booster_gym/utils/runner.py does with the gradients of a mini-epoch: clip_grad_norm_(model.parameters(), 1.0) and optimizer.step()
+ * (runner.py:164-165) of the torch.optim.Adam of runner.py:33 -- torch's defaults: no weight decay, no amsgrad, not maximising --, at the
+ * learning rate the rule of runner.py:175-180 left in the param groups.  The statement of record is tests/optim_mirror.py; this is the
+ * same in words.  K tensors of fixed sizes n_k, float32; one rounding per operation.
+ * CLIP: ss_k = the sum over tensor k of (double)g * (double)g (the products are exact), float64 in ONE association that is a function of
+ * the sizes alone: the elements go in chunks of GMR_OPT_CHUNK, a chunk never spans two tensors (the last chunk of a tensor is short);
+ * within a chunk the balanced tree x[i] = x[i] + x[i + s] for s = 1, 2, 4, .. over the element index (i a multiple of 2 s), an absent
+ * element counting +0; the chunks are added from +0 in rising order, tensor after tensor.  No floating-point atomics.
+ * total_norm = sqrt(total) in double; coef = (float)min(1, max_norm / (total_norm + 1e-6)); the clipped gradient is gc = g * coef.
+ * torch adds float32 norms of the tensors instead: the difference is measured by the fixture, not reproduced.
+ * ADAM, per element, in the operator order of torch's single-tensor path (torch/optim/adam.py: lerp_, mul_ / addcmul_,
+ * sqrt / bias_correction2_sqrt + eps, addcdiv_), t the step count after this step:
+ *   m = m + w1 * (gc - m)                        w1 = (float)(1 - beta1)
+ *   v = v * b2;  v = v + (c2 * gc) * gc          b2 = (float)beta2, c2 = (float)(1 - beta2)
+ *   den = sqrtf(v) / bc2s + e                    bc2s = (float)sqrt(1 - beta2^t), e = (float)eps
+ *   p = p + (ns * m) / den                       ns = (float)(-(lr / (1 - beta1^t)))
+ * The scalars are formed in double and rounded once; beta^t is the product of t factors beta from 1, in double (kept on the device from
+ * step to step, so that no pow of any library decides a bit).
+ * A tensor whose gradient pointer is NULL is skipped in the norm and in the update, like p.grad is None: its parameters and its state
+ * stay bit for bit.  THE GRADIENTS ARE READ-ONLY: the clipped gradient is never stored -- clip_grad_norm_ scales in place, and nothing
+ * in runner.py reads the gradients after the step.  Inputs are taken as finite; a non-finite gradient makes the norm and with it every
+ * parameter non-finite, as in the reference.
+ * LEARNING RATE: the optimiser keeps its own double on the device.  A step uses it; then, in FOLLOW mode (learning_rate NaN at
+ * gmr_motion_tracker_set_optimizer), the fold of that step copies the loss block's current rate (N15) into it, for the next step.  THE
+ * CONTRACT is the order of INTEGRATION.md: in every mini-epoch gmr_motion_tracker_loss_dev with update_lr is enqueued BEFORE the step, so
+ * the step of mini-epoch n runs at the rate the rule left at the end of mini-epoch n - 1, which is the reference's order
+ * (runner.py:165 before :175-180).  With a finite learning_rate the rate is fixed and the loss block is not looked at.
+ * AT MOST THREE launches per step -- the norm pass (a workgroup per chunk, one double each), the fold (one workgroup: the total, the step
+ * count, coef and the Adam scalars, info, the rate for the next step), the update pass (a workgroup per chunk) --, all on the caller's
+ * stream; no call waits for the host.  The K parameter and K gradient addresses travel by value in the kernel arguments: no copy is
+ * enqueued for them.  The tracker stays SINGLE-STREAM. */
+#define GMR_OPT_CHUNK 1024
+#define GMR_OPT_MAX_TENSORS 32
+/* The optimiser of runner.py:33: K tensors of sizes[k] >= 1 elements, K in 1 .. GMR_OPT_MAX_TENSORS; learning_rate finite and above 0,
+ * or NaN: follow the loss block, which needs gmr_motion_tracker_set_loss first; beta1, beta2 in [0, 1), eps and max_norm finite and
+ * above 0.  Allocates exp_avg and exp_avg_sq (every tensor on 256 bytes of one block each), zeroes them, sets the step count to 0 and
+ * builds the chunk table on the device; synchronises the device. */
+int gmr_motion_tracker_set_optimizer(gmr_motion_tracker_t* t, int K, const int64_t* sizes, double learning_rate, double beta1, double beta2,
+                                     double eps, double max_norm);
+/* clip_grad_norm_ and optimizer.step (runner.py:164-165): params and grads are HOST arrays of K device addresses (a NULL gradient: the
+ * tensor is skipped); info f64[4] on the device, or NULL: total_norm, coef, the rate used, the step count.  At most THREE launches. */
+int gmr_motion_tracker_optimizer_step_dev(gmr_motion_tracker_t* t, float* const* d_params, const float* const* d_grads, double* d_info,
+                                          void* stream);                                            /* asynchronous */
+int gmr_motion_tracker_optimizer_step(gmr_motion_tracker_t* t, float* const* params, const float* const* grads, double* info);
+/* The state of the Adam of runner.py:33 as its state_dict holds it (runner.py:95, :207-214): the step count and exp_avg, exp_avg_sq as
+ * flat host arrays of sum(sizes) floats in tensor order; synchronises the device. */
+int gmr_motion_tracker_optimizer_state(gmr_motion_tracker_t* t, int64_t* step, float* exp_avg, float* exp_avg_sq);
+/* Continues a checkpoint (runner.py:95): step >= 0 and the two flat arrays; in follow mode the rate of the next step is the loss block's
+ * current one; synchronises the device. */
+int gmr_motion_tracker_optimizer_load_state(gmr_motion_tracker_t* t, int64_t step, const float* exp_avg, const float* exp_avg_sq);
+
 /* ---- multi-GPU: one rank per GPU, ONE broadcast, no per-step collective ------------ */
 /* The reference parallelises over files with mp.Pool on one CPU (scripts/smplx_to_robot_dataset.py:241-242); here
  * streams shard over the ranks of one node and the only data that crosses ranks is the packed robot model + task set.
