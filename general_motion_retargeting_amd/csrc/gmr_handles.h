@@ -8,7 +8,9 @@
 // gmr_tracker_episode.hip its reset-state and reward tables, the reset counters and the arrays of the episode statistics,
 // gmr_tracker_rollout.hip its rollout configuration and the partial sums of an advantages call, gmr_tracker_loss.hip its loss configuration,
 // the partial sums of a loss call and the learning rate, gmr_tracker_optim.hip its optimiser configuration, the Adam state, the chunk table
-// and the scalars of a step.
+// and the scalars of a step.  What those translation units share beyond the structs lives beside them: gmr_tracker_host.h (host: the
+// checks of a noise spec and of a list of environments, grid sizes, the ignored-id count, the allocation and the read-back of a block's
+// state; also the noise spec itself, ProprioNoise) and gmr_tracker_dev.h (device: draws, noise, heading, small vectors, group reductions).
 #pragma once
 #include <stdint.h>
 
@@ -19,6 +21,7 @@
 #include "gmr_fk_tree.h"
 #include "gmr_internal.h"
 #include "gmr_link_plan.h"
+#include "gmr_tracker_host.h"
 #include "gmr_workspace.h"
 
 struct gmr_fk {
@@ -118,11 +121,7 @@ constexpr int CONTROL_MAX_DECIMATION = 64;
 constexpr int PROPRIO_TERMS = 14;         // lin_vel_z .. base_height, the order of include/gmr_hip.h N10
 constexpr int PROPRIO_MAX_EXTRA = 16;     // pass-through columns of the observation row
 constexpr int PROPRIO_NOISE_BLOCKS = 6;   // gravity, ang_vel, dof_pos, dof_vel, lin_vel, height
-// one noise spec as the kernel applies it: n = a + m * (z or u), then x + n or x * n
-struct ProprioNoise {
-  int32_t dist = 0, op = 0;                 // GMR_NOISE_NONE / _GAUSSIAN / _UNIFORM, GMR_NOISE_ADDITIVE / _SCALING
-  float a = 0.0f, m = 0.0f;                 // gaussian: (float)mu, (float)sigma; uniform: (float)lower, (float)(upper - lower), the span formed in double
-};
+// (one noise spec as the kernels apply it, ProprioNoise: gmr_tracker_host.h)
 // the proprioception configuration of a tracker: validated on the host, travels as a kernel argument like TrackerTables
 struct ProprioTables {
   int32_t R = 0;                            // the robot dofs it was set for; 0: proprio was never set
@@ -343,11 +342,6 @@ struct gmr_motion_tracker {
 };
 
 namespace gmr {
-// the ids outside [0, N) counted so far (synchronous): an entry point that reports them reads it before its launch and after its wait
-inline int tracker_ignored(const gmr_motion_tracker* t, uint32_t* value) {
-  GMR_HIP_TRY(hipMemcpy(value, t->S.ignored, 4, hipMemcpyDeviceToHost));
-  return GMR_OK;
-}
 // the simulator state and the outputs of a step (n environments, r robot dofs) as a synchronous step or link step stages them:
 // h holds the caller's host pointers, d gets the device pointers
 inline void stage_tracker_sim(HostStage& st, gmr_tracker_sim_t& d, const gmr_tracker_sim_t& h, size_t n, size_t r) {

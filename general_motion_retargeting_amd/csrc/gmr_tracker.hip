@@ -222,8 +222,6 @@ static int tracker_tables(const gmr_motion_lib* lib, int R, const int32_t* dof_m
   return GMR_OK;
 }
 
-static dim3 one_lane_each(int n) { return dim3((unsigned)((n + 255) / 256)); }
-
 // what the two step entry points share once the tables are in hand
 static int tracker_step_launch(gmr_motion_tracker* t, const TrackerState& S, const TrackerTables& T, const gmr_tracker_sim_t* sim,
                                const gmr_tracker_out_t* out, hipStream_t stream) {
@@ -232,9 +230,8 @@ static int tracker_step_launch(gmr_motion_tracker* t, const TrackerState& S, con
                            : TrackerSim{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   const TrackerOut O{out->ref_root_pos, out->ref_root_rot, out->ref_root_vel, out->ref_root_ang_vel, out->ref_dof_pos, out->ref_dof_vel,
                      out->err, out->term, out->total, out->status, out->finished};
-  const int per_block = 256 / MOTION_GROUP;
-  hipLaunchKernelGGL(tracker_step_kernel, dim3((unsigned)((t->N + per_block - 1) / per_block)), dim3(256), 0, stream, t->lib->A, S, T, t->N,
-                     t->loop, t->dtf, t->key[0], t->key[1], X, O);
+  hipLaunchKernelGGL(tracker_step_kernel, dim3(row_blocks(t->N, MOTION_GROUP)), dim3(256), 0, stream, t->lib->A, S, T, t->N, t->loop, t->dtf,
+                     t->key[0], t->key[1], X, O);
   GMR_HIP_TRY(hipGetLastError());
   return GMR_OK;
 }
@@ -300,7 +297,7 @@ int gmr_motion_tracker_create(const gmr_motion_lib_t* lib, int N, double dt, int
     t->S = gmr::TrackerState{(int32_t*)(d + o_clip), (float*)(d + o_time), (float*)(d + o_len), (uint32_t*)(d + o_draws), (uint32_t*)(d + o_ign),
                              clip_weights ? (const double*)(d + o_cdf) : nullptr};
     // every environment on clip 0 at time 0; the length of clip 0 is the library's to say
-    hipLaunchKernelGGL(gmr::tracker_assign_kernel, gmr::one_lane_each(N), dim3(256), 0, nullptr, lib->A, t->S, N, N, nullptr, nullptr, nullptr);
+    hipLaunchKernelGGL(gmr::tracker_assign_kernel, dim3(gmr::lane_blocks(N)), dim3(256), 0, nullptr, lib->A, t->S, N, N, nullptr, nullptr, nullptr);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -344,11 +341,10 @@ int gmr_motion_tracker_set_terms(gmr_motion_tracker_t* t, const float* scale, co
 int gmr_motion_tracker_assign_dev(gmr_motion_tracker_t* t, int n, const int32_t* d_env_ids, const int32_t* d_clip, const float* d_time,
                                   void* stream) {
   if (!t) return gmr_fail(GMR_ERR_ARG, "null motion tracker");
-  if (n < 0 || n > (1 << 26)) return gmr_fail(GMR_ERR_ARG, "n = %d out of range", n);
-  if (!d_env_ids && n != t->N) return gmr_fail(GMR_ERR_ARG, "without env_ids every environment is assigned: n = %d, N = %d", n, t->N);
-  if (n == 0) return GMR_OK;
+  const int rc = gmr::subset_check(t->N, n, d_env_ids, "every environment is assigned");
+  if (rc != GMR_OK || n == 0) return rc;
   if (!d_clip || !d_time) return gmr_fail(GMR_ERR_ARG, "null clip / time");
-  hipLaunchKernelGGL(gmr::tracker_assign_kernel, gmr::one_lane_each(n), dim3(256), 0, (hipStream_t)stream, t->lib->A, t->S, t->N, n, d_env_ids,
+  hipLaunchKernelGGL(gmr::tracker_assign_kernel, dim3(gmr::lane_blocks(n)), dim3(256), 0, (hipStream_t)stream, t->lib->A, t->S, t->N, n, d_env_ids,
                      d_clip, d_time);
   GMR_HIP_TRY(hipGetLastError());
   return GMR_OK;
@@ -357,10 +353,11 @@ int gmr_motion_tracker_assign_dev(gmr_motion_tracker_t* t, int n, const int32_t*
 int gmr_motion_tracker_reset_dev(gmr_motion_tracker_t* t, int n, const int32_t* d_env_ids, int resample, float lo, float hi, void* stream) {
   if (!t) return gmr_fail(GMR_ERR_ARG, "null motion tracker");
   if (!d_env_ids) n = t->N;
-  if (n < 0 || n > (1 << 26)) return gmr_fail(GMR_ERR_ARG, "n = %d out of range", n);
+  const int rc = gmr::subset_check(t->N, n, d_env_ids, nullptr);      // (without a list every environment is reset, whatever n says)
+  if (rc != GMR_OK) return rc;
   if (!std::isfinite(lo) || !std::isfinite(hi)) return gmr_fail(GMR_ERR_ARG, "time_offset_range (%g, %g) is not finite", (double)lo, (double)hi);
   if (n == 0) return GMR_OK;
-  hipLaunchKernelGGL(gmr::tracker_reset_kernel, gmr::one_lane_each(n), dim3(256), 0, (hipStream_t)stream, t->lib->A, t->S, t->N, n, d_env_ids,
+  hipLaunchKernelGGL(gmr::tracker_reset_kernel, dim3(gmr::lane_blocks(n)), dim3(256), 0, (hipStream_t)stream, t->lib->A, t->S, t->N, n, d_env_ids,
                      resample ? 1 : 0, lo, hi, t->key[0], t->key[1]);
   GMR_HIP_TRY(hipGetLastError());
   return GMR_OK;
@@ -381,9 +378,8 @@ int gmr_motion_tracker_step_dev(gmr_motion_tracker_t* t, const gmr_tracker_sim_t
 int gmr_motion_tracker_assign(gmr_motion_tracker_t* t, int n, const int32_t* env_ids, const int32_t* clip, const float* time, int* ignored) {
   if (!t) return gmr_fail(GMR_ERR_ARG, "null motion tracker");
   if (ignored) *ignored = 0;
-  if (n < 0 || n > (1 << 26)) return gmr_fail(GMR_ERR_ARG, "n = %d out of range", n);
-  if (!env_ids && n != t->N) return gmr_fail(GMR_ERR_ARG, "without env_ids every environment is assigned: n = %d, N = %d", n, t->N);
-  if (n == 0) return GMR_OK;
+  int rc = gmr::subset_check(t->N, n, env_ids, "every environment is assigned");
+  if (rc != GMR_OK || n == 0) return rc;
   if (!clip || !time) return gmr_fail(GMR_ERR_ARG, "null clip / time");
   std::lock_guard<std::mutex> g(t->mu);
   const size_t nb = (size_t)n * 4;
@@ -392,34 +388,28 @@ int gmr_motion_tracker_assign(gmr_motion_tracker_t* t, int n, const int32_t* env
   const float* d_time;
   st.in(d_ids, env_ids, nb); st.in(d_clip, clip, nb); st.in(d_time, time, nb);
   GMR_STAGE_TRY(st, upload);
-  uint32_t before = 0, after = 0;
-  int rc = gmr::tracker_ignored(t, &before);
-  if (rc == GMR_OK) rc = gmr_motion_tracker_assign_dev(t, n, d_ids, d_clip, d_time, nullptr);
+  gmr::IgnoredDelta ig(t->S.ignored, ignored);
+  if ((rc = ig.begin()) == GMR_OK) rc = gmr_motion_tracker_assign_dev(t, n, d_ids, d_clip, d_time, nullptr);
   if (rc != GMR_OK) return rc;
   GMR_STAGE_TRY(st, download);
-  if ((rc = gmr::tracker_ignored(t, &after)) != GMR_OK) return rc;
-  if (ignored) *ignored = (int)(after - before);
-  return GMR_OK;
+  return ig.end();
 }
 
 int gmr_motion_tracker_reset(gmr_motion_tracker_t* t, int n, const int32_t* env_ids, int resample, float lo, float hi, int* ignored) {
   if (!t) return gmr_fail(GMR_ERR_ARG, "null motion tracker");
   if (ignored) *ignored = 0;
-  if (n < 0 || n > (1 << 26)) return gmr_fail(GMR_ERR_ARG, "n = %d out of range", n);
-  if (env_ids && n == 0) return GMR_OK;
+  int rc = gmr::subset_check(t->N, n, env_ids, nullptr);      // (the rule of reset_dev)
+  if (rc != GMR_OK || (env_ids && n == 0)) return rc;
   std::lock_guard<std::mutex> g(t->mu);
   gmr::HostStage st;
   const int32_t* d_ids;
   st.in(d_ids, env_ids, (size_t)n * 4);
   GMR_STAGE_TRY(st, upload);
-  uint32_t before = 0, after = 0;
-  int rc = gmr::tracker_ignored(t, &before);
-  if (rc == GMR_OK) rc = gmr_motion_tracker_reset_dev(t, n, d_ids, resample, lo, hi, nullptr);
+  gmr::IgnoredDelta ig(t->S.ignored, ignored);
+  if ((rc = ig.begin()) == GMR_OK) rc = gmr_motion_tracker_reset_dev(t, n, d_ids, resample, lo, hi, nullptr);
   if (rc != GMR_OK) return rc;
   GMR_STAGE_TRY(st, download);
-  if ((rc = gmr::tracker_ignored(t, &after)) != GMR_OK) return rc;
-  if (ignored) *ignored = (int)(after - before);
-  return GMR_OK;
+  return ig.end();
 }
 
 int gmr_motion_tracker_step(gmr_motion_tracker_t* t, const gmr_tracker_sim_t* sim, const gmr_tracker_out_t* out) {
@@ -442,14 +432,8 @@ int gmr_motion_tracker_step(gmr_motion_tracker_t* t, const gmr_tracker_sim_t* si
 int gmr_motion_tracker_state(gmr_motion_tracker_t* t, int32_t* clip, float* time, float* length, uint32_t* draws, uint32_t* ignored) {
   if (!t) return gmr_fail(GMR_ERR_ARG, "null motion tracker");
   std::lock_guard<std::mutex> g(t->mu);
-  GMR_HIP_TRY(hipDeviceSynchronize());
   const size_t nb = (size_t)t->N * 4;
-  if (clip) GMR_HIP_TRY(hipMemcpy(clip, t->S.clip, nb, hipMemcpyDeviceToHost));
-  if (time) GMR_HIP_TRY(hipMemcpy(time, t->S.time, nb, hipMemcpyDeviceToHost));
-  if (length) GMR_HIP_TRY(hipMemcpy(length, t->S.length, nb, hipMemcpyDeviceToHost));
-  if (draws) GMR_HIP_TRY(hipMemcpy(draws, t->S.draws, nb, hipMemcpyDeviceToHost));
-  if (ignored) return gmr::tracker_ignored(t, ignored);
-  return GMR_OK;
+  return gmr::read_back({{clip, t->S.clip, nb}, {time, t->S.time, nb}, {length, t->S.length, nb}, {draws, t->S.draws, nb}, {ignored, t->S.ignored, 4}});
 }
 
 }  // extern "C"

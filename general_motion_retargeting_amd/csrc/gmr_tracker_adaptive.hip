@@ -189,7 +189,7 @@ __global__ __launch_bounds__(1024) void tracker_adapt_cdf_kernel(const AdaptiveP
 }
 
 static int adapt_launch(const AdaptivePlan& P, const AdaptiveArrays& R, const AdaptiveBins& Bn, hipStream_t stream) {
-  hipLaunchKernelGGL(tracker_adapt_ema_kernel, dim3((unsigned)((P.Bt + 255) / 256)), dim3(256), 0, stream, P, R);
+  hipLaunchKernelGGL(tracker_adapt_ema_kernel, dim3(lane_blocks(P.Bt)), dim3(256), 0, stream, P, R);
   hipLaunchKernelGGL(tracker_adapt_score_kernel, dim3((unsigned)((P.Bt + ADAPT_TILE - 1) / ADAPT_TILE)), dim3(256), 0, stream, P, R, Bn);
   hipLaunchKernelGGL(tracker_adapt_cdf_kernel, dim3(1), dim3(1024), 0, stream, P, R);
   GMR_HIP_TRY(hipGetLastError());
@@ -199,14 +199,14 @@ static int adapt_launch(const AdaptivePlan& P, const AdaptiveArrays& R, const Ad
 // every check of a masked reset, and its launch
 static int reset_done_launch(gmr_motion_tracker* t, const TrackerState& S, uint32_t* fail_now, int n, const int32_t* d_env_ids, const int32_t* d_done,
                              const int32_t* d_failed, int resample, float lo, float hi, hipStream_t stream) {
-  if (n < 0 || n > (1 << 26)) return gmr_fail(GMR_ERR_ARG, "n = %d out of range", n);
-  if (!d_env_ids && n != t->N) return gmr_fail(GMR_ERR_ARG, "without env_ids the masks cover every environment: n = %d, N = %d", n, t->N);
+  const int rc = subset_check(t->N, n, d_env_ids, "the masks cover every environment");
+  if (rc != GMR_OK) return rc;
   if (!std::isfinite(lo) || !std::isfinite(hi)) return gmr_fail(GMR_ERR_ARG, "time_offset_range (%g, %g) is not finite", (double)lo, (double)hi);
   if (S.bins && (!resample || lo != 0.0f || hi != 0.0f))
     return gmr_fail(GMR_ERR_ARG, "an adaptive tracker draws clip and start from its bins: resample = 1 and time_offset_range (0, 0) "
                                  "(got %d, (%g, %g)); gmr_motion_tracker_reset_dev serves a range", resample, (double)lo, (double)hi);
   if (n == 0) return GMR_OK;
-  hipLaunchKernelGGL(tracker_reset_done_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, t->lib->A, S, fail_now, t->N, n, d_env_ids,
+  hipLaunchKernelGGL(tracker_reset_done_kernel, dim3(lane_blocks(n)), dim3(256), 0, stream, t->lib->A, S, fail_now, t->N, n, d_env_ids,
                      d_done, d_failed, t->loop, resample ? 1 : 0, lo, hi, t->key[0], t->key[1]);
   GMR_HIP_TRY(hipGetLastError());
   return GMR_OK;
@@ -368,35 +368,28 @@ int gmr_motion_tracker_reset_done(gmr_motion_tracker_t* t, int n, const int32_t*
                                   float lo, float hi, int* ignored) {
   if (!t) return gmr_fail(GMR_ERR_ARG, "null motion tracker");
   if (ignored) *ignored = 0;
-  if (n < 0 || n > (1 << 26)) return gmr_fail(GMR_ERR_ARG, "n = %d out of range", n);
+  int rc = gmr::subset_check(t->N, n, env_ids, nullptr);      // (the launch checks the rest)
+  if (rc != GMR_OK) return rc;
   std::lock_guard<std::mutex> g(t->mu);
   const size_t nb = (size_t)n * 4;
   gmr::HostStage st;
   const int32_t *d_ids, *d_done, *d_failed;
   st.in(d_ids, env_ids, nb); st.in(d_done, done, nb); st.in(d_failed, failed, nb);
   GMR_STAGE_TRY(st, upload);
-  uint32_t before = 0, after = 0;
-  int rc = gmr::tracker_ignored(t, &before);
-  if (rc == GMR_OK) rc = gmr::reset_done_launch(t, t->S, t->bins.fail_now, n, d_ids, d_done, d_failed, resample, lo, hi, nullptr);
+  gmr::IgnoredDelta ig(t->S.ignored, ignored);
+  if ((rc = ig.begin()) == GMR_OK) rc = gmr::reset_done_launch(t, t->S, t->bins.fail_now, n, d_ids, d_done, d_failed, resample, lo, hi, nullptr);
   if (rc != GMR_OK) return rc;
   GMR_STAGE_TRY(st, download);
-  if ((rc = gmr::tracker_ignored(t, &after)) != GMR_OK) return rc;
-  if (ignored) *ignored = (int)(after - before);
-  return GMR_OK;
+  return ig.end();
 }
 
 int gmr_motion_tracker_adaptive_state(gmr_motion_tracker_t* t, int32_t* bin_start, uint32_t* fail_now, double* ema, double* prob, double* cdf) {
   if (!t) return gmr_fail(GMR_ERR_ARG, "null motion tracker");
   std::lock_guard<std::mutex> g(t->mu);
   if (t->adaptive.Bt == 0) return gmr_fail(GMR_ERR_ARG, "adaptive sampling is not configured (gmr_motion_tracker_set_adaptive)");
-  GMR_HIP_TRY(hipDeviceSynchronize());
   const size_t nb = (size_t)t->adaptive.Bt;
-  if (bin_start) GMR_HIP_TRY(hipMemcpy(bin_start, t->bin_tab.start, ((size_t)t->lib->A.C + 1) * 4, hipMemcpyDeviceToHost));
-  if (fail_now) GMR_HIP_TRY(hipMemcpy(fail_now, t->bins.fail_now, nb * 4, hipMemcpyDeviceToHost));
-  if (ema) GMR_HIP_TRY(hipMemcpy(ema, t->bins.ema, nb * 8, hipMemcpyDeviceToHost));
-  if (prob) GMR_HIP_TRY(hipMemcpy(prob, t->bins.prob, nb * 8, hipMemcpyDeviceToHost));
-  if (cdf) GMR_HIP_TRY(hipMemcpy(cdf, t->bins.cdf, nb * 8, hipMemcpyDeviceToHost));
-  return GMR_OK;
+  return gmr::read_back({{bin_start, t->bin_tab.start, ((size_t)t->lib->A.C + 1) * 4}, {fail_now, t->bins.fail_now, nb * 4}, {ema, t->bins.ema, nb * 8},
+                         {prob, t->bins.prob, nb * 8}, {cdf, t->bins.cdf, nb * 8}});
 }
 
 }  // extern "C"

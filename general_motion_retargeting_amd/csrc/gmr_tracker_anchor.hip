@@ -106,8 +106,6 @@ __global__ __launch_bounds__(256) void tracker_anchor_root_kernel(const MotionAr
   if (flags & GMR_ANCHOR_Z) S.anchor_pos[(size_t)e * 3 + 2] = sz - rz;
 }
 
-static dim3 anchor_grid(int n) { return dim3((unsigned)((n + 255) / 256)); }
-
 // the two arrays, filled with the identity (the caller holds the mutex); nothing happens when they are there already
 static int anchors_on(gmr_motion_tracker* t) {
   if (t->S.anchor_pos) return GMR_OK;
@@ -138,14 +136,11 @@ static int anchor_yaw_allowed(const gmr_motion_tracker* t) {
 static int anchor_set_launch(gmr_motion_tracker* t, const TrackerState& S, int n, const int32_t* d_ids, const float* d_pos, const float* d_yaw,
                              int yaw_is_zw, hipStream_t stream) {
   if (!S.anchor_pos) return gmr_fail(GMR_ERR_ARG, "anchors are not enabled on this tracker (gmr_motion_tracker_enable_anchors)");
-  if (n < 0 || n > (1 << 26)) return gmr_fail(GMR_ERR_ARG, "n = %d out of range", n);
-  if (!d_ids && n != t->N) return gmr_fail(GMR_ERR_ARG, "without env_ids every environment is set: n = %d, N = %d", n, t->N);
-  if (d_yaw) {
-    const int rc = anchor_yaw_allowed(t);
-    if (rc != GMR_OK) return rc;
-  }
+  int rc = subset_check(t->N, n, d_ids, "every environment is set");
+  if (rc == GMR_OK && d_yaw) rc = anchor_yaw_allowed(t);
+  if (rc != GMR_OK) return rc;
   if (n == 0 || (!d_pos && !d_yaw)) return GMR_OK;
-  hipLaunchKernelGGL(tracker_anchor_set_kernel, anchor_grid(n), dim3(256), 0, stream, S, t->N, n, d_ids, d_pos, d_yaw, yaw_is_zw);
+  hipLaunchKernelGGL(tracker_anchor_set_kernel, dim3(lane_blocks(n)), dim3(256), 0, stream, S, t->N, n, d_ids, d_pos, d_yaw, yaw_is_zw);
   GMR_HIP_TRY(hipGetLastError());
   return GMR_OK;
 }
@@ -154,15 +149,12 @@ static int anchor_root_launch(gmr_motion_tracker* t, const TrackerState& S, int 
                               const float* d_root_pos, const float* d_root_quat, int flags, hipStream_t stream) {
   if (!S.anchor_pos) return gmr_fail(GMR_ERR_ARG, "anchors are not enabled on this tracker (gmr_motion_tracker_enable_anchors)");
   if (flags & ~(GMR_ANCHOR_YAW | GMR_ANCHOR_Z)) return gmr_fail(GMR_ERR_ARG, "unknown anchor flag bits 0x%x", flags);
-  if (n < 0 || n > (1 << 26)) return gmr_fail(GMR_ERR_ARG, "n = %d out of range", n);
-  if (!d_ids && n != t->N) return gmr_fail(GMR_ERR_ARG, "without env_ids the mask and the roots cover every environment: n = %d, N = %d", n, t->N);
-  if (flags & GMR_ANCHOR_YAW) {
-    const int rc = anchor_yaw_allowed(t);
-    if (rc != GMR_OK) return rc;
-  }
+  int rc = subset_check(t->N, n, d_ids, "the mask and the roots cover every environment");
+  if (rc == GMR_OK && (flags & GMR_ANCHOR_YAW)) rc = anchor_yaw_allowed(t);
+  if (rc != GMR_OK) return rc;
   if (n == 0) return GMR_OK;
   if (!d_root_pos || !d_root_quat) return gmr_fail(GMR_ERR_ARG, "null root_pos / root_quat");
-  hipLaunchKernelGGL(tracker_anchor_root_kernel, anchor_grid(n), dim3(256), 0, stream, t->lib->A, S, t->N, n, d_ids, d_mask, d_root_pos, d_root_quat,
+  hipLaunchKernelGGL(tracker_anchor_root_kernel, dim3(lane_blocks(n)), dim3(256), 0, stream, t->lib->A, S, t->N, n, d_ids, d_mask, d_root_pos, d_root_quat,
                      t->loop, flags);
   GMR_HIP_TRY(hipGetLastError());
   return GMR_OK;
@@ -200,20 +192,16 @@ int gmr_motion_tracker_set_anchor_dev(gmr_motion_tracker_t* t, int n, const int3
 int gmr_motion_tracker_set_anchor(gmr_motion_tracker_t* t, int n, const int32_t* env_ids, const float* pos, const float* yaw, int* ignored) {
   if (!t) return gmr_fail(GMR_ERR_ARG, "null motion tracker");
   if (ignored) *ignored = 0;
-  if (n < 0 || n > (1 << 26)) return gmr_fail(GMR_ERR_ARG, "n = %d out of range", n);
-  if (!env_ids && n != t->N) return gmr_fail(GMR_ERR_ARG, "without env_ids every environment is set: n = %d, N = %d", n, t->N);
+  int rc = gmr::subset_check(t->N, n, env_ids, "every environment is set");
+  if (rc != GMR_OK) return rc;
   for (size_t i = 0; i < (size_t)n; i++) {
     if (pos && !(std::isfinite(pos[i * 3]) && std::isfinite(pos[i * 3 + 1]) && std::isfinite(pos[i * 3 + 2])))
       return gmr_fail(GMR_ERR_ARG, "pos[%zu] is not finite", i);
     if (yaw && !std::isfinite(yaw[i])) return gmr_fail(GMR_ERR_ARG, "yaw[%zu] is not finite", i);
   }
-  if (yaw) {
-    const int rc = gmr::anchor_yaw_allowed(t);
-    if (rc != GMR_OK) return rc;
-  }
+  if (yaw && (rc = gmr::anchor_yaw_allowed(t)) != GMR_OK) return rc;
   std::lock_guard<std::mutex> g(t->mu);
-  int rc = gmr::anchors_on(t);
-  if (rc != GMR_OK) return rc;
+  if ((rc = gmr::anchors_on(t)) != GMR_OK) return rc;
   if (n == 0 || (!pos && !yaw)) return GMR_OK;
   std::vector<float> zw;
   if (yaw) {
@@ -226,14 +214,12 @@ int gmr_motion_tracker_set_anchor(gmr_motion_tracker_t* t, int n, const int32_t*
   const float *d_pos, *d_yaw;
   st.in(d_ids, env_ids, nn * 4); st.in(d_pos, pos, nn * 12); st.in(d_yaw, yaw ? zw.data() : nullptr, nn * 8);
   GMR_STAGE_TRY(st, upload);
-  uint32_t before = 0, after = 0;
-  if ((rc = gmr::tracker_ignored(t, &before)) != GMR_OK) return rc;
+  gmr::IgnoredDelta ig(t->S.ignored, ignored);
+  if ((rc = ig.begin()) != GMR_OK) return rc;
   rc = gmr::anchor_set_launch(t, t->S, n, d_ids, d_pos, d_yaw, 1, nullptr);
   if (rc != GMR_OK) return rc;
   GMR_STAGE_TRY(st, download);
-  if ((rc = gmr::tracker_ignored(t, &after)) != GMR_OK) return rc;
-  if (ignored) *ignored = (int)(after - before);
-  return GMR_OK;
+  return ig.end();
 }
 
 int gmr_motion_tracker_anchor_to_root_dev(gmr_motion_tracker_t* t, int n, const int32_t* d_env_ids, const int32_t* d_mask,
@@ -252,16 +238,12 @@ int gmr_motion_tracker_anchor_to_root(gmr_motion_tracker_t* t, int n, const int3
   if (!t) return gmr_fail(GMR_ERR_ARG, "null motion tracker");
   if (ignored) *ignored = 0;
   if (flags & ~(GMR_ANCHOR_YAW | GMR_ANCHOR_Z)) return gmr_fail(GMR_ERR_ARG, "unknown anchor flag bits 0x%x", flags);
-  if (n < 0 || n > (1 << 26)) return gmr_fail(GMR_ERR_ARG, "n = %d out of range", n);
-  if (!env_ids && n != t->N) return gmr_fail(GMR_ERR_ARG, "without env_ids the mask and the roots cover every environment: n = %d, N = %d", n, t->N);
-  if (n > 0 && (!root_pos || !root_quat)) return gmr_fail(GMR_ERR_ARG, "null root_pos / root_quat");
-  if (flags & GMR_ANCHOR_YAW) {
-    const int rc = gmr::anchor_yaw_allowed(t);
-    if (rc != GMR_OK) return rc;
-  }
-  std::lock_guard<std::mutex> g(t->mu);
-  int rc = gmr::anchors_on(t);
+  int rc = gmr::subset_check(t->N, n, env_ids, "the mask and the roots cover every environment");
   if (rc != GMR_OK) return rc;
+  if (n > 0 && (!root_pos || !root_quat)) return gmr_fail(GMR_ERR_ARG, "null root_pos / root_quat");
+  if ((flags & GMR_ANCHOR_YAW) && (rc = gmr::anchor_yaw_allowed(t)) != GMR_OK) return rc;
+  std::lock_guard<std::mutex> g(t->mu);
+  if ((rc = gmr::anchors_on(t)) != GMR_OK) return rc;
   if (n == 0) return GMR_OK;
   const size_t nn = (size_t)n;
   gmr::HostStage st;
@@ -269,25 +251,20 @@ int gmr_motion_tracker_anchor_to_root(gmr_motion_tracker_t* t, int n, const int3
   const float *d_pos, *d_quat;
   st.in(d_ids, env_ids, nn * 4); st.in(d_mask, mask, nn * 4); st.in(d_pos, root_pos, nn * 12); st.in(d_quat, root_quat, nn * 16);
   GMR_STAGE_TRY(st, upload);
-  uint32_t before = 0, after = 0;
-  if ((rc = gmr::tracker_ignored(t, &before)) != GMR_OK) return rc;
+  gmr::IgnoredDelta ig(t->S.ignored, ignored);
+  if ((rc = ig.begin()) != GMR_OK) return rc;
   rc = gmr::anchor_root_launch(t, t->S, n, d_ids, d_mask, d_pos, d_quat, flags, nullptr);
   if (rc != GMR_OK) return rc;
   GMR_STAGE_TRY(st, download);
-  if ((rc = gmr::tracker_ignored(t, &after)) != GMR_OK) return rc;
-  if (ignored) *ignored = (int)(after - before);
-  return GMR_OK;
+  return ig.end();
 }
 
 int gmr_motion_tracker_anchor_state(gmr_motion_tracker_t* t, float* pos, float* yaw_zw) {
   if (!t) return gmr_fail(GMR_ERR_ARG, "null motion tracker");
   std::lock_guard<std::mutex> g(t->mu);
   if (!t->S.anchor_pos) return gmr_fail(GMR_ERR_ARG, "anchors are not enabled on this tracker (gmr_motion_tracker_enable_anchors)");
-  GMR_HIP_TRY(hipDeviceSynchronize());
   const size_t n = (size_t)t->N;
-  if (pos) GMR_HIP_TRY(hipMemcpy(pos, t->S.anchor_pos, n * 12, hipMemcpyDeviceToHost));
-  if (yaw_zw) GMR_HIP_TRY(hipMemcpy(yaw_zw, t->S.anchor_yaw, n * 8, hipMemcpyDeviceToHost));
-  return GMR_OK;
+  return gmr::read_back({{pos, t->S.anchor_pos, n * 12}, {yaw_zw, t->S.anchor_yaw, n * 8}});
 }
 
 }  // extern "C"

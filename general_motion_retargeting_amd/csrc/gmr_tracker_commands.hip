@@ -25,6 +25,7 @@
 #include "gmr_handles.h"
 #include "gmr_internal.h"
 #include "gmr_philox.h"
+#include "gmr_tracker_dev.h"
 #include "gmr_workspace.h"
 
 // one rounding per operation: tests/commands_mirror.py states every line in float32 NumPy
@@ -113,7 +114,7 @@ __global__ __launch_bounds__(256) void tracker_commands_kernel(const CommandTabl
     // ---- 6: the resample (:362-389, :415-435) ----
     if (now == rt) {
       const uint32_t n = St.draws[e], key[2] = {key0, key1};
-      const uint32_t ca[4] = {(uint32_t)e, n, 0u, 2u}, cb[4] = {(uint32_t)e, n, 1u, 2u};
+      const uint32_t ca[4] = {(uint32_t)e, n, 0u, DRAW_COMMAND}, cb[4] = {(uint32_t)e, n, 1u, DRAW_COMMAND};
       uint32_t w[4], v[4];
       philox4x32(ca, key, w);
       philox4x32(cb, key, v);
@@ -196,24 +197,7 @@ __global__ __launch_bounds__(256) void tracker_commands_grid_kernel(const Comman
   if (k == nch - 1) St.cum[G] = b + run;
 }
 
-// apply_randomization (utils/utils.py:9-25) of element i of environment e at common_step; called for a block with a spec only.  The
-// recipe of gmr_tracker_proprio.hip in the counter domain 3.
-__device__ __forceinline__ float disturbed(float x, const ProprioNoise& S, uint32_t e, uint32_t step, uint32_t i, uint32_t key0, uint32_t key1) {
-  const uint32_t ctr[4] = {e, step, i >> 1, 3u}, key[2] = {key0, key1};
-  uint32_t w[4];
-  philox4x32(ctr, key, w);
-  const uint32_t wa = (i & 1u) ? w[2] : w[0], wb = (i & 1u) ? w[3] : w[1];
-  float r;
-  if (S.dist == GMR_NOISE_GAUSSIAN) {
-    const float u1 = philox_unit_open(wa), u2 = philox_unit(wb);
-    r = __fsqrt_rn(-2.0f * logf(u1)) * cosf(6.2831855f * u2);
-  } else {
-    r = philox_unit(wa);
-  }
-  const float n = S.a + S.m * r;
-  return S.op == GMR_NOISE_SCALING ? x * n : x + n;
-}
-
+// (the noise of element i of environment e at common_step: tracker_noise of gmr_tracker_dev.h in the domain of the kicks and pushes)
 __global__ __launch_bounds__(256) void tracker_disturb_kernel(const DisturbTables Dt, const DisturbIo io, int N, uint32_t step, int act,
                                                               uint32_t key0, uint32_t key1) {
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -225,7 +209,7 @@ __global__ __launch_bounds__(256) void tracker_disturb_kernel(const DisturbTable
     const ProprioNoise& S = Dt.spec[i < 3 ? 0 : 1];
     if (S.dist == GMR_NOISE_NONE) return;
     float* p = io.root + e * 13 + 7 + i;
-    *p = disturbed(*p, S, (uint32_t)e, step, (uint32_t)i, key0, key1);
+    *p = tracker_noise(*p, S, (uint32_t)e, step, (uint32_t)i, DRAW_DISTURB, key0, key1);
     return;
   }
   if (!(act & (GMR_DISTURB_PUSH_START | GMR_DISTURB_PUSH_STOP))) return;
@@ -233,7 +217,7 @@ __global__ __launch_bounds__(256) void tracker_disturb_kernel(const DisturbTable
   const int k = i - (torque ? 9 : 6);
   const ProprioNoise& S = Dt.spec[torque ? 3 : 2];
   float v = 0.0f;                                    // the push (:509-521): the randomisation of zero, or zero
-  if ((act & GMR_DISTURB_PUSH_START) && S.dist != GMR_NOISE_NONE) v = disturbed(0.0f, S, (uint32_t)e, step, (uint32_t)i, key0, key1);
+  if ((act & GMR_DISTURB_PUSH_START) && S.dist != GMR_NOISE_NONE) v = tracker_noise(0.0f, S, (uint32_t)e, step, (uint32_t)i, DRAW_DISTURB, key0, key1);
   float* dst = torque ? io.torque : io.force;
   if (dst) dst[e * (torque ? io.torque_stride : io.force_stride) + k] = v;
   if (io.obs) io.obs[e * 6 + (i - 6)] = v * (torque ? Dt.s_torque : Dt.s_force);      // :598-599
@@ -259,7 +243,7 @@ static int commands_launch(gmr_motion_tracker* t, const CommandView& V, const gm
   if (rc != GMR_OK) return rc;
   const CmdIn X{in->episode_steps, in->done, in->lin_vel, in->ang_vel};
   const CmdOut O{out->term, out->total, out->commands, out->gait_frequency, out->flags, out->cmd_obs, out->cmd_obs_stride};
-  const dim3 grid((unsigned)((t->N + 255) / 256)), block(256);
+  const dim3 grid(lane_blocks(t->N)), block(256);
   if (!V.tab.curriculum) {
     hipLaunchKernelGGL(tracker_commands_kernel<3>, grid, block, 0, stream, V.tab, V.st, X, O, t->N, t->key[0], t->key[1]);
   } else {
@@ -292,26 +276,8 @@ static int disturb_check(const DisturbTables& Dt, const gmr_disturb_io_t* io, in
 // the launch of a step that acts (act != 0, checked)
 static int disturb_launch(gmr_motion_tracker* t, const DisturbTables& Dt, uint32_t step, int act, const gmr_disturb_io_t* io, hipStream_t stream) {
   const DisturbIo D{io->root_states, io->push_force, io->push_torque, io->push_obs, io->push_force_stride, io->push_torque_stride};
-  const int64_t lanes = (int64_t)t->N * 16;
-  hipLaunchKernelGGL(tracker_disturb_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, stream, Dt, D, t->N, step, act, t->key[0], t->key[1]);
+  hipLaunchKernelGGL(tracker_disturb_kernel, dim3(lane_blocks((int64_t)t->N * 16)), dim3(256), 0, stream, Dt, D, t->N, step, act, t->key[0], t->key[1]);
   GMR_HIP_TRY(hipGetLastError());
-  return GMR_OK;
-}
-
-static bool fits(double x) { return std::isfinite(x) && std::isfinite((float)x); }
-
-static int noise_spec(const gmr_proprio_noise_t& s, const char* name, ProprioNoise* out) {
-  *out = ProprioNoise{};
-  if (s.distribution < GMR_NOISE_NONE || s.distribution > GMR_NOISE_UNIFORM) return gmr_fail(GMR_ERR_ARG, "%s: distribution = %d", name, s.distribution);
-  if (s.distribution == GMR_NOISE_NONE) return GMR_OK;
-  if (s.operation != GMR_NOISE_ADDITIVE && s.operation != GMR_NOISE_SCALING) return gmr_fail(GMR_ERR_ARG, "%s: operation = %d", name, s.operation);
-  if (!fits(s.a) || !fits(s.b)) return gmr_fail(GMR_ERR_ARG, "%s: range (%g, %g) is not finite", name, s.a, s.b);
-  if (s.distribution == GMR_NOISE_GAUSSIAN && s.b < 0.0) return gmr_fail(GMR_ERR_ARG, "%s: a gaussian's deviation %g is negative", name, s.b);
-  out->dist = s.distribution;
-  out->op = s.operation;
-  out->a = (float)s.a;
-  out->m = s.distribution == GMR_NOISE_GAUSSIAN ? (float)s.b : (float)(s.b - s.a);
-  if (!std::isfinite(out->m)) return gmr_fail(GMR_ERR_ARG, "%s: range (%g, %g) is too wide", name, s.a, s.b);
   return GMR_OK;
 }
 
@@ -384,10 +350,9 @@ int gmr_motion_tracker_set_commands(gmr_motion_tracker_t* t, const gmr_commands_
   gmr::Carve cv;
   const size_t o_cmd = cv.take(n * 12), o_gait = cv.take(n * 4), o_rt = cv.take(n * 4), o_draws = cv.take(n * 4), o_carry = cv.take(n * 4);
   const size_t o_level = cv.take(Ct.curriculum ? n * 8 : 0), o_prob = cv.take(G * 4), o_hits = cv.take(G * 4), o_cum = cv.take(Ct.curriculum ? (G + 1) * 8 : 0);
-  GMR_HIP_TRY(hipDeviceSynchronize());               // nothing in flight reads the arrays a larger grid replaces
-  GMR_HIP_TRY(t->command_block.reserve(cv.total() + 256));
+  const int rc = gmr::fresh_block(t->command_block, cv);
+  if (rc != GMR_OK) return rc;
   char* d = t->command_block.data();
-  GMR_HIP_TRY(hipMemset(d, 0, cv.total()));
   gmr::CommandState st;
   st.commands = (float*)(d + o_cmd); st.gait_frequency = (float*)(d + o_gait); st.resample_time = (int32_t*)(d + o_rt);
   st.draws = (uint32_t*)(d + o_draws); st.carry = (int32_t*)(d + o_carry);
@@ -395,8 +360,8 @@ int gmr_motion_tracker_set_commands(gmr_motion_tracker_t* t, const gmr_commands_
     st.level = (int32_t*)(d + o_level); st.prob = (float*)(d + o_prob); st.hits = (uint32_t*)(d + o_hits); st.cum = (double*)(d + o_cum);
     const float one = 1.0f;                          // :245-251: the centre cell
     GMR_HIP_TRY(hipMemcpy(st.prob + ((size_t)Ct.L * (2 * Ct.A + 1) + Ct.A), &one, 4, hipMemcpyHostToDevice));
+    GMR_HIP_TRY(hipDeviceSynchronize());
   }
-  GMR_HIP_TRY(hipDeviceSynchronize());
   t->commands = Ct;
   t->command_state = st;
   return GMR_OK;
@@ -445,15 +410,11 @@ int gmr_motion_tracker_command_state(gmr_motion_tracker_t* t, float* commands, f
   if (!Ct.on) return gmr_fail(GMR_ERR_ARG, "commands are not set on this tracker (gmr_motion_tracker_set_commands)");
   if (!Ct.curriculum && (env_level || curriculum_prob || hits || cum))
     return gmr_fail(GMR_ERR_ARG, "env_level / curriculum_prob / hits / cum exist with a curriculum only");
-  GMR_HIP_TRY(hipDeviceSynchronize());
   const gmr::CommandState& st = t->command_state;
   const size_t n = (size_t)t->N, G = (size_t)Ct.G;
-  void* hs[8] = {commands, gait_frequency, cmd_resample_time, cmd_draws, env_level, curriculum_prob, hits, cum};
-  const void* ds[8] = {st.commands, st.gait_frequency, st.resample_time, st.draws, st.level, st.prob, st.hits, st.cum};
-  const size_t ns[8] = {n * 12, n * 4, n * 4, n * 4, n * 8, G * 4, G * 4, (G + 1) * 8};
-  for (int k = 0; k < 8; k++)
-    if (hs[k]) GMR_HIP_TRY(hipMemcpy(hs[k], ds[k], ns[k], hipMemcpyDeviceToHost));
-  return GMR_OK;
+  return gmr::read_back({{commands, st.commands, n * 12}, {gait_frequency, st.gait_frequency, n * 4}, {cmd_resample_time, st.resample_time, n * 4},
+                         {cmd_draws, st.draws, n * 4}, {env_level, st.level, n * 8}, {curriculum_prob, st.prob, G * 4}, {hits, st.hits, G * 4},
+                         {cum, st.cum, (G + 1) * 8}});
 }
 
 int gmr_motion_tracker_set_disturbances(gmr_motion_tracker_t* t, const gmr_disturb_config_t* cfg) {

@@ -98,12 +98,8 @@ __global__ __launch_bounds__(256) void tracker_hold_kernel(const TrackerState S,
   const int i = (blockIdx.x * 256 + threadIdx.x) / MOTION_GROUP;
   const int l = threadIdx.x & (MOTION_GROUP - 1);
   if (i >= n) return;
-  if (mask && mask[i] == 0) return;
   const int e = ids ? ids[i] : i;
-  if (e < 0 || e >= N) {
-    if (l == 0) atomicAdd(S.ignored, 1u);
-    return;
-  }
+  if (tracker_row_skip(S, mask, i, l, e, N)) return;
   for (int j = l; j < R; j += MOTION_GROUP) {
     held[(size_t)e * R + j] = dof_pos[(size_t)i * R + j];
     acc[(size_t)e * R + j] = 0.0f;
@@ -249,24 +245,27 @@ static int targets_launch(gmr_motion_tracker* t, const ControlView& V, const flo
   if (rc != GMR_OK) return rc;
   if (d_clipped && !d_actions) return gmr_fail(GMR_ERR_ARG, "actions_clipped needs actions");
   if (!d_targets && !d_clipped && !d_status) return GMR_OK;
-  const int per_block = 256 / MOTION_GROUP;
-  hipLaunchKernelGGL(tracker_targets_kernel, dim3((unsigned)((t->N + per_block - 1) / per_block)), dim3(256), 0, stream, t->lib->A, V.S, V.tab,
-                     V.ctl, t->N, t->loop, t->dtf, d_actions, d_steps, d_targets, d_clipped, d_status);
+  hipLaunchKernelGGL(tracker_targets_kernel, dim3(row_blocks(t->N, MOTION_GROUP)), dim3(256), 0, stream, t->lib->A, V.S, V.tab, V.ctl, t->N, t->loop,
+                     t->dtf, d_actions, d_steps, d_targets, d_clipped, d_status);
   GMR_HIP_TRY(hipGetLastError());
+  return GMR_OK;
+}
+
+// the checks of a hold call that need no device
+static int hold_check(const gmr_motion_tracker* t, const ControlTables& Ct, int n, const void* ids, const void* dof_pos) {
+  int rc = control_set(t, Ct);
+  if (rc != GMR_OK) return rc;
+  if ((rc = subset_check(t->N, n, ids, "the mask and dof_pos cover every environment")) != GMR_OK) return rc;
+  if (n > 0 && !dof_pos) return gmr_fail(GMR_ERR_ARG, "null dof_pos");
   return GMR_OK;
 }
 
 static int hold_launch(gmr_motion_tracker* t, const ControlView& V, int n, const int32_t* d_ids, const int32_t* d_mask, const float* d_dof_pos,
                        hipStream_t stream) {
-  const int rc = control_set(t, V.ctl);
-  if (rc != GMR_OK) return rc;
-  if (n < 0 || n > (1 << 26)) return gmr_fail(GMR_ERR_ARG, "n = %d out of range", n);
-  if (!d_ids && n != t->N) return gmr_fail(GMR_ERR_ARG, "without env_ids the mask and dof_pos cover every environment: n = %d, N = %d", n, t->N);
-  if (n == 0) return GMR_OK;
-  if (!d_dof_pos) return gmr_fail(GMR_ERR_ARG, "null dof_pos");
-  const int per_block = 256 / MOTION_GROUP;
-  hipLaunchKernelGGL(tracker_hold_kernel, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(256), 0, stream, V.S, t->N, V.ctl.R, n, d_ids,
-                     d_mask, d_dof_pos, V.held, V.acc);
+  const int rc = hold_check(t, V.ctl, n, d_ids, d_dof_pos);
+  if (rc != GMR_OK || n == 0) return rc;
+  hipLaunchKernelGGL(tracker_hold_kernel, dim3(row_blocks(n, MOTION_GROUP)), dim3(256), 0, stream, V.S, t->N, V.ctl.R, n, d_ids, d_mask, d_dof_pos,
+                     V.held, V.acc);
   GMR_HIP_TRY(hipGetLastError());
   return GMR_OK;
 }
@@ -283,8 +282,6 @@ static int torques_check(const gmr_motion_tracker* t, const ControlTables& Ct, i
   return GMR_OK;
 }
 
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 static int torques_launch(gmr_motion_tracker* t, const ControlView& V, int substep, const float* d_targets, const float* d_q, const float* d_qd,
                           const gmr_tracker_actuator_t* act, const int32_t* d_delay, float* d_tau, float* d_mean, hipStream_t stream) {
   const int rc = torques_check(t, V.ctl, substep, d_targets, d_q, d_qd, act, d_tau);
@@ -296,10 +293,9 @@ static int torques_launch(gmr_motion_tracker* t, const ControlView& V, int subst
              aligned16(V.acc);
   if (act->per_env) vec = vec && aligned16(act->stiffness) && aligned16(act->damping) && aligned16(act->friction);
   if (vec) {
-    const size_t lanes = total / 4 + 1;
-    hipLaunchKernelGGL(tracker_torques_kernel<true>, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, stream, T, total);
+    hipLaunchKernelGGL(tracker_torques_kernel<true>, dim3(lane_blocks(total / 4 + 1)), dim3(256), 0, stream, T, total);
   } else {
-    hipLaunchKernelGGL(tracker_torques_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, T, total);
+    hipLaunchKernelGGL(tracker_torques_kernel<false>, dim3(lane_blocks(total)), dim3(256), 0, stream, T, total);
   }
   GMR_HIP_TRY(hipGetLastError());
   return GMR_OK;
@@ -330,11 +326,9 @@ int gmr_motion_tracker_set_control(gmr_motion_tracker_t* t, const float* default
   const size_t nr = (size_t)t->N * (size_t)R * 4;
   gmr::Carve cv;
   const size_t o_held = cv.take(nr), o_acc = cv.take(nr);
-  GMR_HIP_TRY(hipDeviceSynchronize());               // nothing in flight reads the arrays a larger R replaces
-  GMR_HIP_TRY(t->control_block.reserve(cv.total() + 256));
+  const int rc = gmr::fresh_block(t->control_block, cv);
+  if (rc != GMR_OK) return rc;
   char* d = t->control_block.data();
-  GMR_HIP_TRY(hipMemset(d, 0, cv.total()));
-  GMR_HIP_TRY(hipDeviceSynchronize());
   gmr::ControlTables Ct;
   Ct.R = R; Ct.M = decimation;
   Ct.action_scale = action_scale; Ct.clip = clip_actions;
@@ -396,26 +390,20 @@ int gmr_motion_tracker_hold(gmr_motion_tracker_t* t, int n, const int32_t* env_i
   if (ignored) *ignored = 0;
   std::lock_guard<std::mutex> g(t->mu);
   const gmr::ControlView V = gmr::control_view(t);
-  int rc = gmr::control_set(t, V.ctl);
-  if (rc != GMR_OK) return rc;
-  if (n < 0 || n > (1 << 26)) return gmr_fail(GMR_ERR_ARG, "n = %d out of range", n);
-  if (!env_ids && n != t->N) return gmr_fail(GMR_ERR_ARG, "without env_ids the mask and dof_pos cover every environment: n = %d, N = %d", n, t->N);
-  if (n == 0) return GMR_OK;
-  if (!dof_pos) return gmr_fail(GMR_ERR_ARG, "null dof_pos");
+  int rc = gmr::hold_check(t, V.ctl, n, env_ids, dof_pos);
+  if (rc != GMR_OK || n == 0) return rc;
   const size_t nn = (size_t)n, nr = nn * (size_t)V.ctl.R * 4;
   gmr::HostStage st;
   const int32_t *d_ids, *d_mask;
   const float* d_pos;
   st.in(d_ids, env_ids, nn * 4); st.in(d_mask, mask, nn * 4); st.in(d_pos, dof_pos, nr);
   GMR_STAGE_TRY(st, upload);
-  uint32_t before = 0, after = 0;
-  if ((rc = gmr::tracker_ignored(t, &before)) != GMR_OK) return rc;
+  gmr::IgnoredDelta ig(V.S.ignored, ignored);
+  if ((rc = ig.begin()) != GMR_OK) return rc;
   rc = gmr::hold_launch(t, V, n, d_ids, d_mask, d_pos, nullptr);
   if (rc != GMR_OK) return rc;
   GMR_STAGE_TRY(st, download);
-  if ((rc = gmr::tracker_ignored(t, &after)) != GMR_OK) return rc;
-  if (ignored) *ignored = (int)(after - before);
-  return GMR_OK;
+  return ig.end();
 }
 
 int gmr_motion_tracker_torques_dev(gmr_motion_tracker_t* t, int substep, const float* d_dof_targets, const float* d_dof_pos,
@@ -462,11 +450,8 @@ int gmr_motion_tracker_control_state(gmr_motion_tracker_t* t, float* held, float
   std::lock_guard<std::mutex> g(t->mu);
   const int rc = gmr::control_set(t, t->control);
   if (rc != GMR_OK) return rc;
-  GMR_HIP_TRY(hipDeviceSynchronize());
   const size_t nr = (size_t)t->N * (size_t)t->control.R * 4;
-  if (held) GMR_HIP_TRY(hipMemcpy(held, t->held, nr, hipMemcpyDeviceToHost));
-  if (torque_acc) GMR_HIP_TRY(hipMemcpy(torque_acc, t->torque_acc, nr, hipMemcpyDeviceToHost));
-  return GMR_OK;
+  return gmr::read_back({{held, t->held, nr}, {torque_acc, t->torque_acc, nr}});
 }
 
 }  // extern "C"

@@ -1,12 +1,19 @@
-// gmr_tracker_dev.h -- what the kernels of the motion tracker share on the device: tracker_step_kernel (gmr_tracker.hip),
-// tracker_links_kernel (gmr_tracker_links.hip) and the masked reset (gmr_tracker_adaptive.hip).  One definition of the pointer tables,
-// the clip length, the Philox draws (by clip weight, and from the bins of adaptive sampling), the redraw of a finished clip and the
-// 16-lane sum, so that a link step leaves the same clocks, draws and term bits as a plain step.  Device code only.
+// gmr_tracker_dev.h -- what the kernels of the motion tracker (gmr_tracker*.hip) share on the device.  One definition each of
+//   * the pointer tables of a step, the clip length, the Philox draws (by clip weight, and from the bins of adaptive sampling) and the
+//     redraw of a finished clip, so that a link step leaves the same clocks, draws and term bits as a plain step;
+//   * the counter domains of the tracker's draws, and the noise of a spec (tracker_words, tracker_noise): sensor noise, kicks and
+//     pushes, reset states;
+//   * the environment of a lane (tracker_env) and the test of a 16-lane row (tracker_row_skip) of a list of environments;
+//   * the reductions over the 16 lanes of an environment (group_sum, group_or, group_count);
+//   * the heading frame (yaw_of, unyaw, unyaw_zw, unyaw_q) and the anchors;
+//   * three floats, their selection by lane and the reference's two quaternion rotations (V3, pick, rotate_inverse, rotate_forward).
+// Device code only; the host's counterpart is gmr_tracker_host.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
+#include "gmr_fk_walk.h"      // f4
 #include "gmr_handles.h"
 #include "gmr_motion_sample.h"
 #include "gmr_philox.h"
@@ -24,6 +31,10 @@ struct TrackerOut {
   int32_t *status, *finished;
 };
 
+// Word 3 of a Philox counter keeps the draws of the blocks apart: the clip and start draws of resets and finished clips, the sensor noise
+// (DESIGN.md section 6q), the command resample (6s), the kicks and pushes (6s), the reset states (6t).
+constexpr uint32_t DRAW_RESET = 0u, DRAW_SENSOR = 1u, DRAW_COMMAND = 2u, DRAW_DISTURB = 3u, DRAW_RESET_STATE = 4u;
+
 // (float)(T / fps) of clip c; 0 for a clip id outside [0, C)
 __device__ __forceinline__ float clip_length(const MotionArrays& A, int c) {
   if (c < 0 || c >= A.C) return 0.0f;
@@ -34,7 +45,7 @@ __device__ __forceinline__ float clip_length(const MotionArrays& A, int c) {
 // from word 0; the return value is u of word 1.
 __device__ __forceinline__ float tracker_draw(const MotionArrays& A, const TrackerState& S, uint32_t key0, uint32_t key1, int e,
                                               bool want_clip, int* clip) {
-  const uint32_t ctr[4] = {(uint32_t)e, S.draws[e], 0u, 0u}, key[2] = {key0, key1};
+  const uint32_t ctr[4] = {(uint32_t)e, S.draws[e], 0u, DRAW_RESET}, key[2] = {key0, key1};
   uint32_t w[4];
   philox4x32(ctr, key, w);
   S.draws[e] = ctr[1] + 1u;
@@ -58,7 +69,7 @@ __device__ __forceinline__ float tracker_draw(const MotionArrays& A, const Track
 // One draw for environment e from the bins of adaptive sampling: the counter and key of tracker_draw,
 // word 0 picks the bin -- the largest b with cdf[b] <= word0 2^-32 --, word 1 the start inside it.  Returns the start time.
 __device__ __forceinline__ float tracker_draw_bin(const MotionArrays& A, const TrackerState& S, uint32_t key0, uint32_t key1, int e, int* clip) {
-  const uint32_t ctr[4] = {(uint32_t)e, S.draws[e], 0u, 0u}, key[2] = {key0, key1};
+  const uint32_t ctr[4] = {(uint32_t)e, S.draws[e], 0u, DRAW_RESET}, key[2] = {key0, key1};
   uint32_t w[4];
   philox4x32(ctr, key, w);
   S.draws[e] = ctr[1] + 1u;
@@ -94,14 +105,89 @@ __device__ __forceinline__ int tracker_env(const TrackerState& S, const int32_t*
   return -1;
 }
 
-// the sum over the 16 lanes of an environment, in every one of them
+// The same test for a kernel that gives entry i of a list a row of 16 lanes (l: the lane inside the row, e = ids ? ids[i] : i): true when
+// the row has nothing to do, because the mask leaves the entry out or e lies outside [0, N) -- counted once, by lane 0.  (The id stays
+// with the kernel and the result is a flag: the shapes that hand e back through the helper cost the three kernels registers.)
+__device__ __forceinline__ bool tracker_row_skip(const TrackerState& S, const int32_t* mask, int i, int l, int e, int N) {
+  if (mask && mask[i] == 0) return true;
+  if (e >= 0 && e < N) return false;
+  if (l == 0) atomicAdd(S.ignored, 1u);
+  return true;
+}
+
+// the sum over the 16 lanes of an environment, in every one of them; any and the counts go through the same butterfly as integers
 __device__ __forceinline__ float group_sum(float x) {
 #pragma unroll
   for (int m = 1; m < MOTION_GROUP; m <<= 1) x = x + __shfl_xor(x, m, MOTION_GROUP);
   return x;
 }
+__device__ __forceinline__ int group_or(int x) {
+#pragma unroll
+  for (int m = 1; m < MOTION_GROUP; m <<= 1) x |= __shfl_xor(x, m, MOTION_GROUP);
+  return x;
+}
+__device__ __forceinline__ int group_count(int x) {
+#pragma unroll
+  for (int m = 1; m < MOTION_GROUP; m <<= 1) x += __shfl_xor(x, m, MOTION_GROUP);
+  return x;
+}
 
-// ---- tracker anchors (include/gmr_hip.h N8, DESIGN.md section 6o; the statement of record is tests/anchor_mirror.py) ----------------
+// ---- the noise of a spec (apply_randomization, utils/utils.py:9-25; the statements of record are the mirrors of the three blocks) --------
+
+// the two words of element i of environment e at its count n: philox4x32((e, n, i >> 1, domain), key), words (0, 1) for an even i,
+// (2, 3) for an odd one.  Returns the first, *wb is the second.
+__device__ __forceinline__ uint32_t tracker_words(uint32_t e, uint32_t n, uint32_t i, uint32_t domain, uint32_t key0, uint32_t key1, uint32_t* wb) {
+  const uint32_t ctr[4] = {e, n, i >> 1, domain}, key[2] = {key0, key1};
+  uint32_t w[4];
+  philox4x32(ctr, key, w);
+  *wb = (i & 1u) ? w[3] : w[1];
+  return (i & 1u) ? w[2] : w[0];
+}
+
+// x with the noise of element i; called for a block with a spec only (S.dist != GMR_NOISE_NONE)
+__device__ __forceinline__ float tracker_noise(float x, const ProprioNoise& S, uint32_t e, uint32_t n, uint32_t i, uint32_t domain, uint32_t key0,
+                                               uint32_t key1) {
+  uint32_t wb;
+  const uint32_t wa = tracker_words(e, n, i, domain, key0, key1, &wb);
+  float r;
+  if (S.dist == GMR_NOISE_GAUSSIAN) {
+    const float u1 = philox_unit_open(wa), u2 = philox_unit(wb);
+    r = __fsqrt_rn(-2.0f * logf(u1)) * cosf(6.2831855f * u2);
+  } else {
+    r = philox_unit(wa);
+  }
+  const float nz = S.a + S.m * r;
+  return S.op == GMR_NOISE_SCALING ? x * nz : x + nz;
+}
+
+// ---- three floats -----------------------------------------------------------------------------------------------------------------------
+struct V3 {
+  float x, y, z;
+};
+__device__ __forceinline__ float pick(const V3& v, int k) { return k == 0 ? v.x : (k == 1 ? v.y : v.z); }
+
+// quat_rotate_inverse of the reference (torch_utils.py:78-87) in its own grouping; the quaternion as given
+__device__ __forceinline__ V3 rotate_inverse(float qx, float qy, float qz, float qw, const V3& v) {
+  const float s = 2.0f * (qw * qw) - 1.0f;
+  const float d = (qx * v.x + qy * v.y) + qz * v.z;
+  V3 r;
+  r.x = v.x * s - (qy * v.z - qz * v.y) * qw * 2.0f + qx * d * 2.0f;
+  r.y = v.y * s - (qz * v.x - qx * v.z) * qw * 2.0f + qy * d * 2.0f;
+  r.z = v.z * s - (qx * v.y - qy * v.x) * qw * 2.0f + qz * d * 2.0f;
+  return r;
+}
+// quat_rotate of the reference (torch_utils.py:66-75) in its own grouping, a + b + c; the quaternion as given
+__device__ __forceinline__ V3 rotate_forward(float qx, float qy, float qz, float qw, const V3& v) {
+  const float s = 2.0f * (qw * qw) - 1.0f;
+  const float d = (qx * v.x + qy * v.y) + qz * v.z;
+  V3 r;
+  r.x = (v.x * s + (qy * v.z - qz * v.y) * qw * 2.0f) + qx * d * 2.0f;
+  r.y = (v.y * s + (qz * v.x - qx * v.z) * qw * 2.0f) + qy * d * 2.0f;
+  r.z = (v.z * s + (qx * v.y - qy * v.x) * qw * 2.0f) + qz * d * 2.0f;
+  return r;
+}
+
+// ---- the heading frame of the links and the preview (DESIGN.md sections 6l, 6m) -----------------------------------------------------------
 
 // the yaw of a rotation as the unit quaternion (0, 0, z, w): normalize(0, 0, q.z, q.w), the identity when both are zero
 __device__ __forceinline__ void yaw_of(float qz, float qw, float& z, float& w) {
@@ -112,6 +198,19 @@ __device__ __forceinline__ void yaw_of(float qz, float qw, float& z, float& w) {
     z = __fdiv_rn(qz, n); w = __fdiv_rn(qw, n);
   }
 }
+
+// Rz(-psi) (x, y) with c = cos psi, s = sin psi; for the yaw (z, w): c = w w - z z, s = 2 z w
+__device__ __forceinline__ void unyaw(float c, float s, float& x, float& y) {
+  const float nx = c * x + s * y, ny = c * y - s * x;
+  x = nx; y = ny;
+}
+__device__ __forceinline__ void unyaw_zw(float z, float w, float& x, float& y) { unyaw(w * w - z * z, 2.0f * z * w, x, y); }
+// conj(0, 0, z, w) * q
+__device__ __forceinline__ f4 unyaw_q(float z, float w, f4 q) {
+  return f4{w * q.x + z * q.y, w * q.y - z * q.x, w * q.z - z * q.w, w * q.w + z * q.z};
+}
+
+// ---- tracker anchors (include/gmr_hip.h N8, DESIGN.md section 6o; the statement of record is tests/anchor_mirror.py) ----------------
 
 // yaw_of with a correctly rounded square root (sqrtf; __fsqrt_rn above is the hardware's, good to one ulp): what anchor_to_root
 // uses, so that tests/anchor_mirror.py reproduces the anchor's bits in NumPy.  The heading frame keeps yaw_of and with it its bits.

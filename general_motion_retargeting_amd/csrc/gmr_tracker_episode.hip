@@ -27,6 +27,7 @@
 #include "gmr_handles.h"
 #include "gmr_internal.h"
 #include "gmr_philox.h"
+#include "gmr_tracker_dev.h"
 #include "gmr_workspace.h"
 
 // one rounding per operation: tests/episode_mirror.py states every line in float32 NumPy
@@ -50,30 +51,8 @@ struct ResetChain {
 
 constexpr int RESET_GROUP = 16;             // lanes per list entry
 
-// the two words of element i of environment e at its reset count n: philox4x32((e, n, i >> 1, 4), key), words (0, 1) for an even i, (2, 3)
-// for an odd one.  Word 3 = 4 keeps these draws apart from the resets (0), the sensor noise (1), the commands (2) and the kicks (3).
-__device__ __forceinline__ uint32_t reset_words(uint32_t e, uint32_t n, uint32_t i, uint32_t key0, uint32_t key1, uint32_t* wb) {
-  const uint32_t ctr[4] = {e, n, i >> 1, 4u}, key[2] = {key0, key1};
-  uint32_t w[4];
-  philox4x32(ctr, key, w);
-  *wb = (i & 1u) ? w[3] : w[1];
-  return (i & 1u) ? w[2] : w[0];
-}
-
-// apply_randomization (utils/utils.py:9-25) of element i; called for a block with a spec only.  The recipe of gmr_tracker_proprio.hip.
-__device__ __forceinline__ float randomised(float x, const ProprioNoise& S, uint32_t e, uint32_t n, uint32_t i, uint32_t key0, uint32_t key1) {
-  uint32_t wb;
-  const uint32_t wa = reset_words(e, n, i, key0, key1, &wb);
-  float r;
-  if (S.dist == GMR_NOISE_GAUSSIAN) {
-    const float u1 = philox_unit_open(wa), u2 = philox_unit(wb);
-    r = __fsqrt_rn(-2.0f * logf(u1)) * cosf(6.2831855f * u2);
-  } else {
-    r = philox_unit(wa);
-  }
-  const float nz = S.a + S.m * r;
-  return S.op == GMR_NOISE_SCALING ? x * nz : x + nz;
-}
+// (the draws of element i of environment e at its reset count: tracker_words and tracker_noise of gmr_tracker_dev.h in the domain of the
+// reset states)
 
 // Entry i of the list (environment i without one), t1.py:319-340, :311, :316 in the reference's order
 __global__ __launch_bounds__(256) void tracker_reset_states_kernel(const ResetTables Rt, const TerrainTables T, const TrackerState S, uint32_t* draws,
@@ -83,6 +62,7 @@ __global__ __launch_bounds__(256) void tracker_reset_states_kernel(const ResetTa
   const int i = (blockIdx.x * 256 + threadIdx.x) / RESET_GROUP;
   const int l = threadIdx.x & (RESET_GROUP - 1);
   if (i >= n) return;
+  // (the test of tracker_row_skip, gmr_tracker_dev.h, written out: through the helper this kernel measured 1 % slower at N = 2^20)
   if (mask && mask[i] == 0) return;
   const int e = ids ? ids[i] : i;
   if (e < 0 || e >= N) {
@@ -94,7 +74,7 @@ __global__ __launch_bounds__(256) void tracker_reset_states_kernel(const ResetTa
   // ---- 1: the dofs (:319-320) ----
   for (int j = l; j < R; j += RESET_GROUP) {
     float q = io.init_dof_pos ? io.init_dof_pos[(size_t)i * R + j] : Rt.default_pos[j];
-    if (Rt.spec[0].dist != GMR_NOISE_NONE) q = randomised(q, Rt.spec[0], ue, nd, (uint32_t)j, key0, key1);
+    if (Rt.spec[0].dist != GMR_NOISE_NONE) q = tracker_noise(q, Rt.spec[0], ue, nd, (uint32_t)j, DRAW_RESET_STATE, key0, key1);
     io.dof_pos[(size_t)e * R + j] = q;
     io.dof_vel[(size_t)e * R + j] = io.init_dof_vel ? io.init_dof_vel[(size_t)i * R + j] : 0.0f;
     if (ch.held) {                                               // what hold does (:309)
@@ -112,8 +92,8 @@ __global__ __launch_bounds__(256) void tracker_reset_states_kernel(const ResetTa
     r[1] = r[1] + Rt.origins[(size_t)e * 2 + 1];
   }
   if (Rt.spec[1].dist != GMR_NOISE_NONE) {
-    r[0] = randomised(r[0], Rt.spec[1], ue, nd, (uint32_t)R, key0, key1);
-    r[1] = randomised(r[1], Rt.spec[1], ue, nd, (uint32_t)R + 1u, key0, key1);
+    r[0] = tracker_noise(r[0], Rt.spec[1], ue, nd, (uint32_t)R, DRAW_RESET_STATE, key0, key1);
+    r[1] = tracker_noise(r[1], Rt.spec[1], ue, nd, (uint32_t)R + 1u, DRAW_RESET_STATE, key0, key1);
   }
   // ---- 3: the terrain under the drawn point (:331) ----
   if (Rt.use_terrain) {
@@ -123,22 +103,22 @@ __global__ __launch_bounds__(256) void tracker_reset_states_kernel(const ResetTa
   // ---- 4: the yaw (:332-336) ----
   if (Rt.yaw) {
     uint32_t wb;
-    const float u = philox_unit(reset_words(ue, nd, (uint32_t)R + 2u, key0, key1, &wb));
+    const float u = philox_unit(tracker_words(ue, nd, (uint32_t)R + 2u, DRAW_RESET_STATE, key0, key1, &wb));
     const float half = 0.5f * (Rt.yaw_lo + Rt.yaw_span * u);
     r[3] = 0.0f; r[4] = 0.0f; r[5] = sinf(half); r[6] = cosf(half);
   }
   // ---- 5: the planar velocity: the randomisation of zero (:337-340), of the given row's where one is given ----
   if (!io.init_root) { r[7] = 0.0f; r[8] = 0.0f; }
   if (Rt.spec[2].dist != GMR_NOISE_NONE) {
-    r[7] = randomised(r[7], Rt.spec[2], ue, nd, (uint32_t)R + 3u, key0, key1);
-    r[8] = randomised(r[8], Rt.spec[2], ue, nd, (uint32_t)R + 4u, key0, key1);
+    r[7] = tracker_noise(r[7], Rt.spec[2], ue, nd, (uint32_t)R + 3u, DRAW_RESET_STATE, key0, key1);
+    r[8] = tracker_noise(r[8], Rt.spec[2], ue, nd, (uint32_t)R + 4u, DRAW_RESET_STATE, key0, key1);
   }
 #pragma unroll
   for (int k = 0; k < 13; k++) io.root[(size_t)e * 13 + k] = r[k];
   // ---- 6, 7, 8: the delay (:316), the step count (:311), the reset counter ----
   if (Rt.decimation > 0 && io.delay) {
     uint32_t wb;
-    io.delay[e] = philox_below(reset_words(ue, nd, (uint32_t)R + 5u, key0, key1, &wb), Rt.decimation);
+    io.delay[e] = philox_below(tracker_words(ue, nd, (uint32_t)R + 5u, DRAW_RESET_STATE, key0, key1, &wb), Rt.decimation);
   }
   if (io.steps) io.steps[e] = 0;
   draws[e] = nd + 1u;
@@ -177,8 +157,8 @@ static int reset_states_check(const gmr_motion_tracker* t, const ResetView& V, i
   if (V.tab.R != V.R)
     return gmr_fail(GMR_ERR_ARG, "reset states were set for R = %d robot dofs, the dof map now has %d: call gmr_motion_tracker_set_reset_states again",
                     V.tab.R, V.R);
-  if (n < 0 || n > (1 << 26)) return gmr_fail(GMR_ERR_ARG, "n = %d out of range", n);
-  if (!ids && n != t->N) return gmr_fail(GMR_ERR_ARG, "without env_ids the mask and the init rows cover every environment: n = %d, N = %d", n, t->N);
+  const int rc = subset_check(t->N, n, ids, "the mask and the init rows cover every environment");
+  if (rc != GMR_OK) return rc;
   if (chain != 0 && chain != 1) return gmr_fail(GMR_ERR_ARG, "chain = %d, must be 0 or 1", chain);
   if (!io) return gmr_fail(GMR_ERR_ARG, "null io table");
   if (!io->root_states || !io->dof_pos || !io->dof_vel) return gmr_fail(GMR_ERR_ARG, "null root_states / dof_pos / dof_vel");
@@ -192,28 +172,9 @@ static int reset_states_launch(gmr_motion_tracker* t, const ResetView& V, int n,
   if (n == 0) return GMR_OK;
   const ResetIo X{io->root_states, io->dof_pos, io->dof_vel, io->delay_steps, io->episode_steps, io->init_root_states, io->init_dof_pos, io->init_dof_vel};
   const ResetChain none{nullptr, nullptr, nullptr, nullptr, nullptr};
-  const int per_block = 256 / RESET_GROUP;
-  hipLaunchKernelGGL(tracker_reset_states_kernel, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(256), 0, stream, V.tab, V.terrain, V.S, V.draws,
-                     X, chain ? V.chain : none, t->N, n, d_ids, d_mask, t->key[0], t->key[1]);
+  hipLaunchKernelGGL(tracker_reset_states_kernel, dim3(row_blocks(n, RESET_GROUP)), dim3(256), 0, stream, V.tab, V.terrain, V.S, V.draws, X,
+                     chain ? V.chain : none, t->N, n, d_ids, d_mask, t->key[0], t->key[1]);
   GMR_HIP_TRY(hipGetLastError());
-  return GMR_OK;
-}
-
-static bool fits(double x) { return std::isfinite(x) && std::isfinite((float)x); }
-
-// (the checks of gmr_tracker_commands.hip's noise_spec)
-static int reset_spec(const gmr_proprio_noise_t& s, const char* name, ProprioNoise* out) {
-  *out = ProprioNoise{};
-  if (s.distribution < GMR_NOISE_NONE || s.distribution > GMR_NOISE_UNIFORM) return gmr_fail(GMR_ERR_ARG, "%s: distribution = %d", name, s.distribution);
-  if (s.distribution == GMR_NOISE_NONE) return GMR_OK;
-  if (s.operation != GMR_NOISE_ADDITIVE && s.operation != GMR_NOISE_SCALING) return gmr_fail(GMR_ERR_ARG, "%s: operation = %d", name, s.operation);
-  if (!fits(s.a) || !fits(s.b)) return gmr_fail(GMR_ERR_ARG, "%s: range (%g, %g) is not finite", name, s.a, s.b);
-  if (s.distribution == GMR_NOISE_GAUSSIAN && s.b < 0.0) return gmr_fail(GMR_ERR_ARG, "%s: a gaussian's deviation %g is negative", name, s.b);
-  out->dist = s.distribution;
-  out->op = s.operation;
-  out->a = (float)s.a;
-  out->m = s.distribution == GMR_NOISE_GAUSSIAN ? (float)s.b : (float)(s.b - s.a);
-  if (!std::isfinite(out->m)) return gmr_fail(GMR_ERR_ARG, "%s: range (%g, %g) is too wide", name, s.a, s.b);
   return GMR_OK;
 }
 
@@ -458,7 +419,7 @@ int gmr_motion_tracker_set_reset_states(gmr_motion_tracker_t* t, const gmr_reset
   const gmr_proprio_noise_t* specs[gmr::RESET_SPECS] = {&cfg->init_dof_pos, &cfg->init_base_pos_xy, &cfg->init_base_lin_vel_xy};
   static const char* const names[gmr::RESET_SPECS] = {"init_dof_pos", "init_base_pos_xy", "init_base_lin_vel_xy"};
   for (int k = 0; k < gmr::RESET_SPECS; k++) {
-    const int rc = gmr::reset_spec(*specs[k], names[k], &Rt.spec[k]);
+    const int rc = gmr::noise_spec(*specs[k], names[k], &Rt.spec[k]);
     if (rc != GMR_OK) return rc;
   }
   if (cfg->yaw != 0 && cfg->yaw != 1) return gmr_fail(GMR_ERR_ARG, "yaw = %d, must be 0 or 1", cfg->yaw);
@@ -540,8 +501,8 @@ int gmr_motion_tracker_reset_states(gmr_motion_tracker_t* t, int n, const int32_
   st.in(d.init_root_states, io->init_root_states, nn * 52); st.in(d.init_dof_pos, io->init_dof_pos, nn * R * 4);
   st.in(d.init_dof_vel, io->init_dof_vel, nn * R * 4);
   GMR_STAGE_TRY(st, upload);
-  uint32_t before = 0, after = 0;
-  if ((rc = gmr::tracker_ignored(t, &before)) != GMR_OK) return rc;
+  gmr::IgnoredDelta ig(V.S.ignored, ignored);
+  if ((rc = ig.begin()) != GMR_OK) return rc;
   rc = gmr::reset_states_launch(t, V, n, d_ids, d_mask, &d, chain, nullptr);
   if (rc != GMR_OK) return rc;
   GMR_STAGE_TRY(st, download);
@@ -550,18 +511,14 @@ int gmr_motion_tracker_reset_states(gmr_motion_tracker_t* t, int n, const int32_
   GMR_HIP_TRY(hipMemcpy(io->dof_vel, d.dof_vel, N * R * 4, hipMemcpyDeviceToHost));
   if (io->delay_steps) GMR_HIP_TRY(hipMemcpy(io->delay_steps, d.delay_steps, N * 4, hipMemcpyDeviceToHost));
   if (io->episode_steps) GMR_HIP_TRY(hipMemcpy(io->episode_steps, d.episode_steps, N * 4, hipMemcpyDeviceToHost));
-  if ((rc = gmr::tracker_ignored(t, &after)) != GMR_OK) return rc;
-  if (ignored) *ignored = (int)(after - before);
-  return GMR_OK;
+  return ig.end();
 }
 
 int gmr_motion_tracker_reset_state(gmr_motion_tracker_t* t, uint32_t* reset_draws) {
   if (!t) return gmr_fail(GMR_ERR_ARG, "null motion tracker");
   std::lock_guard<std::mutex> g(t->mu);
   if (t->resets.R == 0) return gmr_fail(GMR_ERR_ARG, "reset states are not set on this tracker (gmr_motion_tracker_set_reset_states)");
-  GMR_HIP_TRY(hipDeviceSynchronize());
-  if (reset_draws) GMR_HIP_TRY(hipMemcpy(reset_draws, t->reset_draws, (size_t)t->N * 4, hipMemcpyDeviceToHost));
-  return GMR_OK;
+  return gmr::read_back({{reset_draws, t->reset_draws, (size_t)t->N * 4}});
 }
 
 int gmr_motion_tracker_set_rewards(gmr_motion_tracker_t* t, const gmr_reward_config_t* cfg) {
@@ -600,19 +557,18 @@ int gmr_motion_tracker_set_rewards(gmr_motion_tracker_t* t, const gmr_reward_con
   Rt.pos[0] = cfg->only_positive[0]; Rt.pos[1] = cfg->only_positive[1];
   Rt.gw[0] = cfg->group_weight[0]; Rt.gw[1] = cfg->group_weight[1];
   gmr::RewardState st;
-  GMR_HIP_TRY(hipDeviceSynchronize());               // nothing in flight reads the arrays a wider row replaces
+  if (!Rt.stats) GMR_HIP_TRY(hipDeviceSynchronize());      // nothing in flight reads the arrays this call drops (fresh_block waits too)
   if (Rt.stats) {
     const size_t n = (size_t)t->N, K = (size_t)C + 1, nwg = (n + gmr::REWARD_ENVS - 1) / gmr::REWARD_ENVS;
     gmr::Carve cv;
     const size_t o_steps = cv.take(n * 4), o_sum = cv.take(n * K * 4), o_fsum = cv.take(K * 8), o_fsteps = cv.take(8), o_count = cv.take(4);
     const size_t o_started = cv.take(4), o_part = cv.take(nwg * K * 8), o_any = cv.take(nwg * 4);
-    GMR_HIP_TRY(t->reward_block.reserve(cv.total() + 256));
+    const int rc = gmr::fresh_block(t->reward_block, cv);
+    if (rc != GMR_OK) return rc;
     char* d = t->reward_block.data();
-    GMR_HIP_TRY(hipMemset(d, 0, cv.total()));
     st.ep_steps = (int32_t*)(d + o_steps); st.ep_sum = (float*)(d + o_sum); st.fin_sum = (double*)(d + o_fsum);
     st.fin_steps = (unsigned long long*)(d + o_fsteps); st.fin_count = (uint32_t*)(d + o_count); st.started = (uint32_t*)(d + o_started);
     st.part = (double*)(d + o_part); st.wg_any = (uint32_t*)(d + o_any);
-    GMR_HIP_TRY(hipDeviceSynchronize());
   }
   t->rewards = Rt;
   t->reward_state = st;
@@ -697,11 +653,8 @@ int gmr_motion_tracker_reward_state(gmr_motion_tracker_t* t, int32_t* ep_steps, 
   std::lock_guard<std::mutex> g(t->mu);
   const int rc = gmr::stats_check(t->rewards);
   if (rc != GMR_OK) return rc;
-  GMR_HIP_TRY(hipDeviceSynchronize());
   const size_t n = (size_t)t->N, K = (size_t)t->rewards.C + 1;
-  if (ep_steps) GMR_HIP_TRY(hipMemcpy(ep_steps, t->reward_state.ep_steps, n * 4, hipMemcpyDeviceToHost));
-  if (ep_sum) GMR_HIP_TRY(hipMemcpy(ep_sum, t->reward_state.ep_sum, n * K * 4, hipMemcpyDeviceToHost));
-  return GMR_OK;
+  return gmr::read_back({{ep_steps, t->reward_state.ep_steps, n * 4}, {ep_sum, t->reward_state.ep_sum, n * K * 4}});
 }
 
 }  // extern "C"

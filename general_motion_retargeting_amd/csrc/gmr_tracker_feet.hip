@@ -45,10 +45,7 @@ struct FeetOut {
   int32_t *feet_contact, *done;
 };
 
-struct P3 {
-  float x, y, z;
-};
-__device__ __forceinline__ float pick3(const P3& v, int k) { return k == 0 ? v.x : (k == 1 ? v.y : v.z); }
+// (V3, pick, rotate_forward, group_or, group_count: gmr_tracker_dev.h)
 
 __global__ __launch_bounds__(256) void tracker_terrain_heights_kernel(const TerrainTables T, long long M, const float* __restrict__ points,
                                                                       long long stride, float* __restrict__ heights, int32_t* outside) {
@@ -76,28 +73,6 @@ __device__ __forceinline__ float euler_yaw(float x, float y, float z, float w) {
   return remainder_pos(atan2f(2.0f * (w * z + x * y), ((w * w + x * x) - y * y) - z * z), TWO_PI_F);
 }
 
-// quat_rotate of the reference (torch_utils.py:66-75) in its own grouping, a + b + c; the quaternion as given
-__device__ __forceinline__ P3 rotate_forward(float qx, float qy, float qz, float qw, const P3& v) {
-  const float s = 2.0f * (qw * qw) - 1.0f;
-  const float d = (qx * v.x + qy * v.y) + qz * v.z;
-  P3 r;
-  r.x = (v.x * s + (qy * v.z - qz * v.y) * qw * 2.0f) + qx * d * 2.0f;
-  r.y = (v.y * s + (qz * v.x - qx * v.z) * qw * 2.0f) + qy * d * 2.0f;
-  r.z = (v.z * s + (qx * v.y - qy * v.x) * qw * 2.0f) + qz * d * 2.0f;
-  return r;
-}
-
-__device__ __forceinline__ int group_or(int x) {
-#pragma unroll
-  for (int m = 1; m < MOTION_GROUP; m <<= 1) x |= __shfl_xor(x, m, MOTION_GROUP);
-  return x;
-}
-__device__ __forceinline__ int group_count(int x) {
-#pragma unroll
-  for (int m = 1; m < MOTION_GROUP; m <<= 1) x += __shfl_xor(x, m, MOTION_GROUP);
-  return x;
-}
-
 __global__ __launch_bounds__(256) void tracker_feet_kernel(const FeetTables Ft, const TerrainTables T, const FeetState St, const FeetIn X,
                                                            const FeetOut O, int N, float dtf) {
   __shared__ float s_edge[FEET_MAX_EDGES * 3];
@@ -120,7 +95,7 @@ __global__ __launch_bounds__(256) void tracker_feet_kernel(const FeetTables Ft, 
   const float* p1 = bp + Ft.feet_body[1] * X.body_stride[0];
   const float* q0 = br + Ft.feet_body[0] * X.body_stride[1];
   const float* q1 = br + Ft.feet_body[1] * X.body_stride[1];
-  const P3 f0{p0[0], p0[1], p0[2]}, f1{p1[0], p1[1], p1[2]};
+  const V3 f0{p0[0], p0[1], p0[2]}, f1{p1[0], p1[1], p1[2]};
   const float ax = q0[0], ay = q0[1], az = q0[2], aw = q0[3];
   const float bx = q1[0], by = q1[1], bz = q1[2], bw = q1[3];
   const float roll0 = wrap_pi(euler_roll(ax, ay, az, aw)), roll1 = wrap_pi(euler_roll(bx, by, bz, bw));
@@ -130,9 +105,9 @@ __global__ __launch_bounds__(256) void tracker_feet_kernel(const FeetTables Ft, 
   int hit = 0;
   if (l < 2 * E) {
     const int f = l >= E ? 1 : 0, k = l - f * E;
-    const P3 v{s_edge[3 * k], s_edge[3 * k + 1], s_edge[3 * k + 2]};
-    const P3 r = f ? rotate_forward(bx, by, bz, bw, v) : rotate_forward(ax, ay, az, aw, v);
-    const P3 c = f ? f1 : f0;
+    const V3 v{s_edge[3 * k], s_edge[3 * k + 1], s_edge[3 * k + 2]};
+    const V3 r = f ? rotate_forward(bx, by, bz, bw, v) : rotate_forward(ax, ay, az, aw, v);
+    const V3 c = f ? f1 : f0;
     const float ex = c.x + r.x, ey = c.y + r.y, ez = c.z + r.z;                                           // :543
     bool out;
     const float h = terrain_height(T, ex, ey, &out);
@@ -204,7 +179,7 @@ __global__ __launch_bounds__(256) void tracker_feet_kernel(const FeetTables Ft, 
 
   // ---- the outputs ----
   if (l < 6) {
-    const float v = l < 3 ? pick3(f0, l) : pick3(f1, l - 3);
+    const float v = l < 3 ? pick(f0, l) : pick(f1, l - 3);
     if (O.feet_pos) O.feet_pos[(size_t)e * 6 + l] = v;
   }
   if (l < 2) {
@@ -220,7 +195,7 @@ __global__ __launch_bounds__(256) void tracker_feet_kernel(const FeetTables Ft, 
   // ---- the roll-over (:495, :478).  Every lane of the group has read the old values and the group is part of ONE wavefront, so the
   // stores below follow the loads in program order; the wait makes sure the loads have also returned (vmcnt(0)), as in 6q. ----
   __builtin_amdgcn_s_waitcnt(0x0F70);
-  if (l < 6) St.last_feet_pos[(size_t)e * 6 + l] = l < 3 ? pick3(f0, l) : pick3(f1, l - 3);
+  if (l < 6) St.last_feet_pos[(size_t)e * 6 + l] = l < 3 ? pick(f0, l) : pick(f1, l - 3);
   if (l == 0) St.gait_process[e] = gp;
 }
 
@@ -262,9 +237,7 @@ static int feet_launch(gmr_motion_tracker* t, const FeetView& V, const gmr_track
   X.body_pos = bodies->body_pos; X.body_rot = bodies->body_rot;
   X.forces = in->contact_forces; X.root = in->root_states; X.gait_frequency = in->gait_frequency; X.steps = in->episode_steps;
   const FeetOut O{out->feet_pos, out->feet_roll, out->feet_yaw, out->ground, out->gait, out->term, out->total, out->feet_contact, out->done};
-  const int per_block = 256 / MOTION_GROUP;
-  hipLaunchKernelGGL(tracker_feet_kernel, dim3((unsigned)((t->N + per_block - 1) / per_block)), dim3(256), 0, stream, V.tab, V.terrain, V.st, X, O,
-                     t->N, t->dtf);
+  hipLaunchKernelGGL(tracker_feet_kernel, dim3(row_blocks(t->N, MOTION_GROUP)), dim3(256), 0, stream, V.tab, V.terrain, V.st, X, O, t->N, t->dtf);
   GMR_HIP_TRY(hipGetLastError());
   return GMR_OK;
 }
@@ -281,7 +254,7 @@ static int heights_launch(const TerrainTables& T, long long M, const float* d_po
   const int rc = heights_check(M, d_points, stride, d_heights);
   if (rc != GMR_OK) return rc;
   if (M == 0) return GMR_OK;
-  hipLaunchKernelGGL(tracker_terrain_heights_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, stream, T, M, d_points, stride, d_heights,
+  hipLaunchKernelGGL(tracker_terrain_heights_kernel, dim3(lane_blocks(M)), dim3(256), 0, stream, T, M, d_points, stride, d_heights,
                      d_outside);
   GMR_HIP_TRY(hipGetLastError());
   return GMR_OK;
@@ -397,11 +370,9 @@ int gmr_motion_tracker_set_feet(gmr_motion_tracker_t* t, const gmr_feet_config_t
   const size_t n = (size_t)t->N;
   gmr::Carve cv;
   const size_t o_last = cv.take(n * 24), o_gait = cv.take(n * 4);
-  GMR_HIP_TRY(hipDeviceSynchronize());
-  GMR_HIP_TRY(t->feet_block.reserve(cv.total() + 256));
+  const int rc = gmr::fresh_block(t->feet_block, cv);
+  if (rc != GMR_OK) return rc;
   char* d = t->feet_block.data();
-  GMR_HIP_TRY(hipMemset(d, 0, cv.total()));
-  GMR_HIP_TRY(hipDeviceSynchronize());
   t->feet = Ft;
   t->feet_state = gmr::FeetState{(float*)(d + o_last), (float*)(d + o_gait)};
   return GMR_OK;
@@ -450,11 +421,8 @@ int gmr_motion_tracker_feet_state(gmr_motion_tracker_t* t, float* last_feet_pos,
   std::lock_guard<std::mutex> g(t->mu);
   const int rc = gmr::feet_set(t->feet);
   if (rc != GMR_OK) return rc;
-  GMR_HIP_TRY(hipDeviceSynchronize());
   const size_t n = (size_t)t->N;
-  if (last_feet_pos) GMR_HIP_TRY(hipMemcpy(last_feet_pos, t->feet_state.last_feet_pos, n * 24, hipMemcpyDeviceToHost));
-  if (gait_process) GMR_HIP_TRY(hipMemcpy(gait_process, t->feet_state.gait_process, n * 4, hipMemcpyDeviceToHost));
-  return GMR_OK;
+  return gmr::read_back({{last_feet_pos, t->feet_state.last_feet_pos, n * 24}, {gait_process, t->feet_state.gait_process, n * 4}});
 }
 
 }  // extern "C"

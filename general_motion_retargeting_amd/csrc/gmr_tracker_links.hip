@@ -53,17 +53,7 @@ struct LinkOut {
   int32_t* fail;
 };
 
-// (yaw_of: gmr_tracker_dev.h)
-// Rz(-psi) (x, y) for the yaw (z, w): cos psi = w w - z z, sin psi = 2 z w
-__device__ __forceinline__ void unyaw(float z, float w, float& x, float& y) {
-  const float c = w * w - z * z, s = 2.0f * z * w;
-  const float nx = c * x + s * y, ny = c * y - s * x;
-  x = nx; y = ny;
-}
-// conj(0, 0, z, w) * q
-__device__ __forceinline__ f4 unyaw_q(float z, float w, f4 q) {
-  return f4{w * q.x + z * q.y, w * q.y - z * q.x, w * q.z - z * q.w, w * q.w + z * q.z};
-}
+// (the heading frame, yaw_of, unyaw_zw and unyaw_q: gmr_tracker_dev.h)
 
 // LDS of one workgroup in floats: rows [64][rs], root [13][64], slots [nslot][13][64], partials [W][5][64], total6 [64], ok [64]
 __host__ __device__ inline size_t links_lds_floats(int ndof, int nslot, int nwave) {
@@ -305,10 +295,10 @@ __global__ __launch_bounds__(64 * FK_MAX_WAVES) void tracker_links_kernel(const 
       f4 q = crot;
       if (heading) {
         px = px - rpx; py = py - rpy; pz = pz - rpz;
-        unyaw(ryz, ryw, px, py);
+        unyaw_zw(ryz, ryw, px, py);
         q = unyaw_q(ryz, ryw, q);
-        unyaw(ryz, ryw, vx, vy);
-        unyaw(ryz, ryw, ox, oy);
+        unyaw_zw(ryz, ryw, vx, vy);
+        unyaw_zw(ryz, ryw, ox, oy);
       }
       if (move) {      // the finished world row, after the walk and before it is written and differenced
         const Anchor An = anchor_load(S, (size_t)e);
@@ -331,7 +321,7 @@ __global__ __launch_bounds__(64 * FK_MAX_WAVES) void tracker_links_kernel(const 
       if (Y.body_pos) {
         const float* s = Y.body_pos + e * Y.env_stride[0] + sb * Y.body_stride[0];
         float x = s[0], y = s[1], z = s[2];
-        if (heading) { x = x - sbx; y = y - sby; z = z - sbz; unyaw(syz, syw, x, y); }
+        if (heading) { x = x - sbx; y = y - sby; z = z - sbz; unyaw_zw(syz, syw, x, y); }
         const float dx = x - px, dy = y - py, dz = z - pz;
         const float d2 = dx * dx + dy * dy + dz * dz;
         a_pos = a_pos + wb * d2;
@@ -349,14 +339,14 @@ __global__ __launch_bounds__(64 * FK_MAX_WAVES) void tracker_links_kernel(const 
       if (Y.body_vel) {
         const float* s = Y.body_vel + e * Y.env_stride[2] + sb * Y.body_stride[2];
         float x = s[0], y = s[1];
-        if (heading) unyaw(syz, syw, x, y);
+        if (heading) unyaw_zw(syz, syw, x, y);
         const float dx = x - vx, dy = y - vy, dz = s[2] - vz;
         a_vel = a_vel + wb * (dx * dx + dy * dy + dz * dz);
       }
       if (Y.body_ang_vel) {
         const float* s = Y.body_ang_vel + e * Y.env_stride[3] + sb * Y.body_stride[3];
         float x = s[0], y = s[1];
-        if (heading) unyaw(syz, syw, x, y);
+        if (heading) unyaw_zw(syz, syw, x, y);
         const float dx = x - ox, dy = y - oy, dz = s[2] - oz;
         a_ang = a_ang + wb * (dx * dx + dy * dy + dz * dz);
       }

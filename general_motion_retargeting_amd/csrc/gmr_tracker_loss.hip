@@ -339,8 +339,6 @@ __global__ __launch_bounds__(1024) void tracker_loss_fold_kernel(const FoldArgs 
   }
 }
 
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 template <int MODE>
 static void loss_kernel_launch(bool vec, const LossArgs& X, hipStream_t stream) {
   if (vec) hipLaunchKernelGGL((tracker_loss_kernel<true, MODE>), dim3((unsigned)X.G), dim3(LTHREADS), 0, stream, X);
@@ -453,10 +451,9 @@ int gmr_motion_tracker_set_loss(gmr_motion_tracker_t* t, double bound_coef, doub
   const size_t groups = (size_t)((L.M + gmr::LROWS - 1) / gmr::LROWS);
   gmr::Carve cv;
   const size_t o_part = cv.take(groups * (size_t)(L.A + gmr::ROWK) * 8), o_lr = cv.take(8);
-  GMR_HIP_TRY(hipDeviceSynchronize());               // nothing in flight reads the scratch a larger block replaces
-  GMR_HIP_TRY(t->loss_block.reserve(cv.total() + 256));
+  const int rc = gmr::fresh_block(t->loss_block, cv);
+  if (rc != GMR_OK) return rc;
   char* d = t->loss_block.data();
-  GMR_HIP_TRY(hipMemset(d, 0, cv.total()));
   GMR_HIP_TRY(hipMemcpy(d + o_lr, &learning_rate, 8, hipMemcpyHostToDevice));
   GMR_HIP_TRY(hipDeviceSynchronize());
   L.part = (double*)(d + o_part);

@@ -180,8 +180,6 @@ __global__ __launch_bounds__(OTHREADS) void tracker_optim_update_kernel(const Up
   else update_chunk<false>(p, g, m, v, f0, cnt, X);
 }
 
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 static int optim_check(const OptimTables& T, const LossTables& L, float* const* params, const float* const* grads) {
   if (T.K == 0) return gmr_fail(GMR_ERR_ARG, "the optimiser is not set on this tracker (gmr_motion_tracker_set_optimizer)");
   if (T.follow && !L.on) return gmr_fail(GMR_ERR_ARG, "the optimiser follows the loss block's learning rate and the loss is not set (gmr_motion_tracker_set_loss)");
@@ -265,10 +263,9 @@ int gmr_motion_tracker_set_optimizer(gmr_motion_tracker_t* t, int K, const int64
   gmr::Carve cv;
   const size_t o_table = cv.take(table.size() * sizeof(gmr::OptimChunk)), o_m = cv.take((size_t)T.state_floats * 4), o_v = cv.take((size_t)T.state_floats * 4);
   const size_t o_part = cv.take((size_t)T.chunks * 8), o_state = cv.take(32), o_scal = cv.take(16);
-  GMR_HIP_TRY(hipDeviceSynchronize());               // nothing in flight reads the state a larger block replaces
-  GMR_HIP_TRY(t->optim_block.reserve(cv.total() + 256));
+  const int rc = gmr::fresh_block(t->optim_block, cv);
+  if (rc != GMR_OK) return rc;
   char* d = t->optim_block.data();
-  GMR_HIP_TRY(hipMemset(d, 0, cv.total()));
   GMR_HIP_TRY(hipMemcpy(d + o_table, table.data(), table.size() * sizeof(gmr::OptimChunk), hipMemcpyHostToDevice));
   const double state[4] = {follow ? 0.0 : learning_rate, 0.0, 1.0, 1.0};
   GMR_HIP_TRY(hipMemcpy(d + o_state, state, 32, hipMemcpyHostToDevice));

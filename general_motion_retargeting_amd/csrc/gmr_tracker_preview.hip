@@ -50,21 +50,7 @@ __host__ __device__ inline int preview_width(int blocks, int R, int nsel) {
 __device__ __forceinline__ float row_get(float x, int j) { return __shfl(x, j, MOTION_GROUP); }
 __device__ __forceinline__ float pick3(int l, float a, float b, float c) { return l == 0 ? a : (l == 1 ? b : c); }
 
-// The heading frame of the tracker links (gmr_tracker_links.hip), the same definitions:
-// the yaw of a rotation as the unit quaternion (0, 0, z, w): normalize(0, 0, q.z, q.w), the identity when both are zero
-__device__ __forceinline__ void preview_yaw_of(float qz, float qw, float& z, float& w) {
-  const float n2 = qz * qz + qw * qw;
-  z = 0.0f; w = 1.0f;
-  if (n2 != 0.0f) {                // (a NaN goes through the division and stays one)
-    const float n = __fsqrt_rn(n2);
-    z = __fdiv_rn(qz, n); w = __fdiv_rn(qw, n);
-  }
-}
-// Rz(-psi) (x, y) with c = cos psi = w w - z z, s = sin psi = 2 z w
-__device__ __forceinline__ void preview_unyaw(float c, float s, float& x, float& y) {
-  const float nx = c * x + s * y, ny = c * y - s * x;
-  x = nx; y = ny;
-}
+// (the heading frame of the tracker links, yaw_of and unyaw: gmr_tracker_dev.h)
 
 __global__ __launch_bounds__(256) void tracker_preview_kernel(const MotionArrays A, const TrackerState S, const TrackerTables Tb,
                                                               const PreviewPlan P, int N, int loop, const float* __restrict__ base_pos,
@@ -159,7 +145,7 @@ __global__ __launch_bounds__(256) void tracker_preview_kernel(const MotionArrays
             if (l == 2 || l == 3) aq = base_quat[(size_t)e * 4 + l];
           }
           pax = row_get(ac, 0); pay = row_get(ac, 1); paz = row_get(ac, 2);
-          preview_yaw_of(row_get(aq, 2), row_get(aq, 3), yz, yw);
+          yaw_of(row_get(aq, 2), row_get(aq, 3), yz, yw);
           cy = yw * yw - yz * yz; sy = 2.0f * yz * yw;
         }
         int o = 0;
@@ -173,7 +159,7 @@ __global__ __launch_bounds__(256) void tracker_preview_kernel(const MotionArrays
           if (anchored) {
             float dx = px - pax, dy = py - pay;
             const float dz = pz - paz;
-            preview_unyaw(cy, sy, dx, dy);
+            unyaw(cy, sy, dx, dy);
             x = pick3(l, dx, dy, dz);
           }
           if (l < 3) row[o + l] = x;
@@ -202,7 +188,7 @@ __global__ __launch_bounds__(256) void tracker_preview_kernel(const MotionArrays
           if (anchored) {
             float vx = row_get(vc, 0), vy = row_get(vc, 1);
             const float vz = row_get(vc, 2);
-            preview_unyaw(cy, sy, vx, vy);
+            unyaw(cy, sy, vx, vy);
             x = pick3(l, vx, vy, vz);
           }
           if (l < 3) row[o + l] = x;
@@ -213,7 +199,7 @@ __global__ __launch_bounds__(256) void tracker_preview_kernel(const MotionArrays
           if (anchored) {
             float wx = row_get(wc, 0), wy = row_get(wc, 1);
             const float wz = row_get(wc, 2);
-            preview_unyaw(cy, sy, wx, wy);
+            unyaw(cy, sy, wx, wy);
             x = pick3(l, wx, wy, wz);
           }
           if (l < 3) row[o + l] = x;
@@ -250,7 +236,7 @@ __global__ __launch_bounds__(256) void tracker_preview_kernel(const MotionArrays
               const float wx = lx + qw * tx + (qy * tz - qz * ty), wy = ly + qw * ty + (qz * tx - qx * tz),
                           wz = lz + qw * tz + (qx * ty - qy * tx);
               lx = (px + wx) - pax; ly = (py + wy) - pay; lz = (pz + wz) - paz;
-              preview_unyaw(cy, sy, lx, ly);
+              unyaw(cy, sy, lx, ly);
             }
             float* d = row + o + b * 3;
             d[0] = lx; d[1] = ly; d[2] = lz;

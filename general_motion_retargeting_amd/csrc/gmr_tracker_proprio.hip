@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include <cmath>
+#include <cstdio>
 #include <mutex>
 
 #include "../../include/gmr_hip.h"
@@ -42,38 +43,7 @@ struct ProprioOut {
   int32_t* done;
 };
 
-struct V3 {
-  float x, y, z;
-};
-__device__ __forceinline__ float pick(const V3& v, int k) { return k == 0 ? v.x : (k == 1 ? v.y : v.z); }
-
-// quat_rotate_inverse of the reference (torch_utils.py:78-87) in its own grouping; the quaternion as given
-__device__ __forceinline__ V3 rotate_inverse(float qx, float qy, float qz, float qw, const V3& v) {
-  const float s = 2.0f * (qw * qw) - 1.0f;
-  const float d = (qx * v.x + qy * v.y) + qz * v.z;
-  V3 r;
-  r.x = v.x * s - (qy * v.z - qz * v.y) * qw * 2.0f + qx * d * 2.0f;
-  r.y = v.y * s - (qz * v.x - qx * v.z) * qw * 2.0f + qy * d * 2.0f;
-  r.z = v.z * s - (qx * v.y - qy * v.x) * qw * 2.0f + qz * d * 2.0f;
-  return r;
-}
-
-// apply_randomization (utils/utils.py:9-25) of element i of environment e; called for a block with a spec only
-__device__ __forceinline__ float noisy(float x, const ProprioNoise& S, uint32_t e, uint32_t tick, uint32_t i, uint32_t key0, uint32_t key1) {
-  const uint32_t ctr[4] = {e, tick, i >> 1, 1u}, key[2] = {key0, key1};
-  uint32_t w[4];
-  philox4x32(ctr, key, w);
-  const uint32_t wa = (i & 1u) ? w[2] : w[0], wb = (i & 1u) ? w[3] : w[1];
-  float r;
-  if (S.dist == GMR_NOISE_GAUSSIAN) {
-    const float u1 = philox_unit_open(wa), u2 = philox_unit(wb);
-    r = __fsqrt_rn(-2.0f * logf(u1)) * cosf(6.2831855f * u2);
-  } else {
-    r = philox_unit(wa);
-  }
-  const float n = S.a + S.m * r;
-  return S.op == GMR_NOISE_SCALING ? x * n : x + n;
-}
+// (V3, pick, rotate_inverse and the sensor noise, tracker_noise at the environment's noise tick: gmr_tracker_dev.h)
 
 __global__ __launch_bounds__(256) void tracker_proprio_kernel(const ProprioTables Pt, const ProprioState St, const ProprioIn X, const ProprioOut O,
                                                               int N, float dtf, uint32_t key0, uint32_t key1, int noise) {
@@ -185,7 +155,7 @@ __global__ __launch_bounds__(256) void tracker_proprio_kernel(const ProprioTable
       else if (i < c_a) { x = X.qd[(size_t)e * R + (i - c_qd)]; blk = 3; sc = Pt.s_qd; }
       else { x = X.act ? X.act[(size_t)e * R + (i - c_a)] : 0.0f; }
       if (blk >= 0) {
-        if (draw && Pt.noise[blk].dist != GMR_NOISE_NONE) x = noisy(x, Pt.noise[blk], (uint32_t)e, tick, (uint32_t)i, key0, key1);
+        if (draw && Pt.noise[blk].dist != GMR_NOISE_NONE) x = tracker_noise(x, Pt.noise[blk], (uint32_t)e, tick, (uint32_t)i, DRAW_SENSOR, key0, key1);
         x = x * sc;
       }
       row[i] = x;
@@ -195,7 +165,7 @@ __global__ __launch_bounds__(256) void tracker_proprio_kernel(const ProprioTable
   if (O.priv && l < 4) {
     const int blk = l < 3 ? 4 : 5;
     float x = l < 3 ? pick(blv, l) : h;
-    if (draw && Pt.noise[blk].dist != GMR_NOISE_NONE) x = noisy(x, Pt.noise[blk], (uint32_t)e, tick, (uint32_t)(W + l), key0, key1);
+    if (draw && Pt.noise[blk].dist != GMR_NOISE_NONE) x = tracker_noise(x, Pt.noise[blk], (uint32_t)e, tick, (uint32_t)(W + l), DRAW_SENSOR, key0, key1);
     if (l < 3) x = x * Pt.s_v;
     O.priv[(size_t)e * 4 + l] = x;
   }
@@ -236,12 +206,8 @@ __global__ __launch_bounds__(256) void tracker_proprio_reset_kernel(const Tracke
   const int i = (blockIdx.x * 256 + threadIdx.x) / MOTION_GROUP;
   const int l = threadIdx.x & (MOTION_GROUP - 1);
   if (i >= n) return;
-  if (mask && mask[i] == 0) return;
   const int e = ids ? ids[i] : i;
-  if (e < 0 || e >= N) {
-    if (l == 0) atomicAdd(S.ignored, 1u);
-    return;
-  }
+  if (tracker_row_skip(S, mask, i, l, e, N)) return;
   if (l < 3) {
     St.filtered_lin_vel[(size_t)e * 3 + l] = 0.0f;
     St.filtered_ang_vel[(size_t)e * 3 + l] = 0.0f;
@@ -284,18 +250,16 @@ static int proprio_launch(gmr_motion_tracker* t, const ProprioView& V, const gmr
   const ProprioIn X{in->root_states, in->dof_pos, in->dof_vel, in->actions, in->mean_torques, in->extra, in->ground, in->episode_steps};
   const ProprioOut O{out->base_lin_vel, out->base_ang_vel, out->projected_gravity, out->filtered_lin_vel, out->filtered_ang_vel,
                      out->obs, out->priv, out->term, out->total, out->done};
-  const int per_block = 256 / MOTION_GROUP;
-  hipLaunchKernelGGL(tracker_proprio_kernel, dim3((unsigned)((t->N + per_block - 1) / per_block)), dim3(256), 0, stream, V.tab, V.st, X, O, t->N,
-                     t->dtf, t->key[0], t->key[1], noise);
+  hipLaunchKernelGGL(tracker_proprio_kernel, dim3(row_blocks(t->N, MOTION_GROUP)), dim3(256), 0, stream, V.tab, V.st, X, O, t->N, t->dtf, t->key[0],
+                     t->key[1], noise);
   GMR_HIP_TRY(hipGetLastError());
   return GMR_OK;
 }
 
 static int proprio_reset_check(const gmr_motion_tracker* t, const ProprioTables& Pt, int n, const void* ids, const void* root) {
-  const int rc = proprio_set(t, Pt);
+  int rc = proprio_set(t, Pt);
   if (rc != GMR_OK) return rc;
-  if (n < 0 || n > (1 << 26)) return gmr_fail(GMR_ERR_ARG, "n = %d out of range", n);
-  if (!ids && n != t->N) return gmr_fail(GMR_ERR_ARG, "without env_ids the mask and root_states cover every environment: n = %d, N = %d", n, t->N);
+  if ((rc = subset_check(t->N, n, ids, "the mask and root_states cover every environment")) != GMR_OK) return rc;
   if (n > 0 && !root) return gmr_fail(GMR_ERR_ARG, "null root_states");
   return GMR_OK;
 }
@@ -305,14 +269,10 @@ static int proprio_reset_launch(gmr_motion_tracker* t, const ProprioView& V, int
   const int rc = proprio_reset_check(t, V.tab, n, d_ids, d_root);
   if (rc != GMR_OK) return rc;
   if (n == 0) return GMR_OK;
-  const int per_block = 256 / MOTION_GROUP;
-  hipLaunchKernelGGL(tracker_proprio_reset_kernel, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(256), 0, stream, V.S, V.st, t->N, n,
-                     d_ids, d_mask, d_root);
+  hipLaunchKernelGGL(tracker_proprio_reset_kernel, dim3(row_blocks(n, MOTION_GROUP)), dim3(256), 0, stream, V.S, V.st, t->N, n, d_ids, d_mask, d_root);
   GMR_HIP_TRY(hipGetLastError());
   return GMR_OK;
 }
-
-static bool finite_d(double x) { return std::isfinite(x); }
 
 }  // namespace gmr
 
@@ -321,7 +281,6 @@ static bool finite_d(double x) { return std::isfinite(x); }
 extern "C" {
 
 int gmr_motion_tracker_set_proprio(gmr_motion_tracker_t* t, const gmr_proprio_config_t* cfg) {
-  using gmr::finite_d;
   if (!t) return gmr_fail(GMR_ERR_ARG, "null motion tracker");
   if (!cfg) return gmr_fail(GMR_ERR_ARG, "null configuration");
   if (!cfg->default_dof_pos || !cfg->dof_pos_limits || !cfg->dof_vel_limits || !cfg->torque_limits || !cfg->scales)
@@ -329,7 +288,8 @@ int gmr_motion_tracker_set_proprio(gmr_motion_tracker_t* t, const gmr_proprio_co
   if (cfg->extra_cols < 0 || cfg->extra_cols > GMR_PROPRIO_MAX_EXTRA)
     return gmr_fail(GMR_ERR_ARG, "extra_cols = %d outside [0, %d]", cfg->extra_cols, GMR_PROPRIO_MAX_EXTRA);
   if (cfg->max_episode_steps < 0) return gmr_fail(GMR_ERR_ARG, "max_episode_steps = %d is negative", cfg->max_episode_steps);
-  if (!finite_d(cfg->filter_weight) || !finite_d(cfg->soft_dof_pos_limit) || !finite_d(cfg->soft_dof_vel_limit) || !finite_d(cfg->soft_torque_limit))
+  if (!std::isfinite(cfg->filter_weight) || !std::isfinite(cfg->soft_dof_pos_limit) || !std::isfinite(cfg->soft_dof_vel_limit) ||
+      !std::isfinite(cfg->soft_torque_limit))
     return gmr_fail(GMR_ERR_ARG, "filter_weight and the three soft factors must be finite");
   const float sc[8] = {cfg->scale_gravity, cfg->scale_lin_vel, cfg->scale_ang_vel, cfg->scale_dof_pos, cfg->scale_dof_vel, cfg->base_height_target,
                        cfg->terminate_vel, cfg->terminate_height};
@@ -337,19 +297,11 @@ int gmr_motion_tracker_set_proprio(gmr_motion_tracker_t* t, const gmr_proprio_co
     if (!std::isfinite(sc[k])) return gmr_fail(GMR_ERR_ARG, "the normalisation scales, base_height_target and the termination thresholds must be finite");
   gmr::ProprioTables Pt;
   for (int k = 0; k < GMR_PROPRIO_NOISE_BLOCKS; k++) {
-    const gmr_proprio_noise_t& s = cfg->noise[k];
-    if (s.distribution < GMR_NOISE_NONE || s.distribution > GMR_NOISE_UNIFORM) return gmr_fail(GMR_ERR_ARG, "noise[%d]: distribution = %d", k, s.distribution);
-    if (s.distribution == GMR_NOISE_NONE) continue;
-    if (s.operation != GMR_NOISE_ADDITIVE && s.operation != GMR_NOISE_SCALING) return gmr_fail(GMR_ERR_ARG, "noise[%d]: operation = %d", k, s.operation);
-    if (!finite_d(s.a) || !finite_d(s.b) || !std::isfinite((float)s.a) || !std::isfinite((float)s.b))
-      return gmr_fail(GMR_ERR_ARG, "noise[%d]: range (%g, %g) is not finite", k, s.a, s.b);
-    if (s.distribution == GMR_NOISE_GAUSSIAN && s.b < 0.0) return gmr_fail(GMR_ERR_ARG, "noise[%d]: a gaussian's deviation %g is negative", k, s.b);
-    Pt.noise[k].dist = s.distribution;
-    Pt.noise[k].op = s.operation;
-    Pt.noise[k].a = (float)s.a;
-    Pt.noise[k].m = s.distribution == GMR_NOISE_GAUSSIAN ? (float)s.b : (float)(s.b - s.a);
-    if (!std::isfinite(Pt.noise[k].m)) return gmr_fail(GMR_ERR_ARG, "noise[%d]: range (%g, %g) is too wide", k, s.a, s.b);
-    Pt.any_noise = 1;
+    char name[16];
+    snprintf(name, sizeof name, "noise[%d]", k);
+    const int rc = gmr::noise_spec(cfg->noise[k], name, &Pt.noise[k]);
+    if (rc != GMR_OK) return rc;
+    if (Pt.noise[k].dist != GMR_NOISE_NONE) Pt.any_noise = 1;
   }
   for (int k = 0; k < GMR_PROPRIO_TERMS; k++) {
     if (!std::isfinite(cfg->scales[k])) return gmr_fail(GMR_ERR_ARG, "scales[%d] is not finite", k);
@@ -384,11 +336,9 @@ int gmr_motion_tracker_set_proprio(gmr_motion_tracker_t* t, const gmr_proprio_co
   const size_t n = (size_t)t->N, nr = n * (size_t)R * 4;
   gmr::Carve cv;
   const size_t o_flv = cv.take(n * 12), o_fav = cv.take(n * 12), o_lrv = cv.take(n * 24), o_la = cv.take(nr), o_ldv = cv.take(nr), o_tick = cv.take(n * 4);
-  GMR_HIP_TRY(hipDeviceSynchronize());               // nothing in flight reads the arrays a larger R replaces
-  GMR_HIP_TRY(t->proprio_block.reserve(cv.total() + 256));
+  const int rc = gmr::fresh_block(t->proprio_block, cv);
+  if (rc != GMR_OK) return rc;
   char* d = t->proprio_block.data();
-  GMR_HIP_TRY(hipMemset(d, 0, cv.total()));
-  GMR_HIP_TRY(hipDeviceSynchronize());
   t->proprio = Pt;
   t->proprio_state = gmr::ProprioState{(float*)(d + o_flv), (float*)(d + o_fav), (float*)(d + o_lrv), (float*)(d + o_la), (float*)(d + o_ldv),
                                        (uint32_t*)(d + o_tick)};
@@ -455,14 +405,12 @@ int gmr_motion_tracker_proprio_reset(gmr_motion_tracker_t* t, int n, const int32
   const float* d_root;
   st.in(d_ids, env_ids, nn * 4); st.in(d_mask, mask, nn * 4); st.in(d_root, root_states, nn * 52);
   GMR_STAGE_TRY(st, upload);
-  uint32_t before = 0, after = 0;
-  if ((rc = gmr::tracker_ignored(t, &before)) != GMR_OK) return rc;
+  gmr::IgnoredDelta ig(V.S.ignored, ignored);
+  if ((rc = ig.begin()) != GMR_OK) return rc;
   rc = gmr::proprio_reset_launch(t, V, n, d_ids, d_mask, d_root, nullptr);
   if (rc != GMR_OK) return rc;
   GMR_STAGE_TRY(st, download);
-  if ((rc = gmr::tracker_ignored(t, &after)) != GMR_OK) return rc;
-  if (ignored) *ignored = (int)(after - before);
-  return GMR_OK;
+  return ig.end();
 }
 
 int gmr_motion_tracker_proprio_state(gmr_motion_tracker_t* t, float* filtered_lin_vel, float* filtered_ang_vel, float* last_root_vel,
@@ -471,15 +419,11 @@ int gmr_motion_tracker_proprio_state(gmr_motion_tracker_t* t, float* filtered_li
   std::lock_guard<std::mutex> g(t->mu);
   const int rc = gmr::proprio_set(t, t->proprio);
   if (rc != GMR_OK) return rc;
-  GMR_HIP_TRY(hipDeviceSynchronize());
   const gmr::ProprioState& st = t->proprio_state;
   const size_t n = (size_t)t->N, nr = n * (size_t)t->proprio.R * 4;
-  void* hs[6] = {filtered_lin_vel, filtered_ang_vel, last_root_vel, last_actions, last_dof_vel, noise_tick};
-  const void* ds[6] = {st.filtered_lin_vel, st.filtered_ang_vel, st.last_root_vel, st.last_actions, st.last_dof_vel, st.noise_tick};
-  const size_t ns[6] = {n * 12, n * 12, n * 24, nr, nr, n * 4};
-  for (int k = 0; k < 6; k++)
-    if (hs[k]) GMR_HIP_TRY(hipMemcpy(hs[k], ds[k], ns[k], hipMemcpyDeviceToHost));
-  return GMR_OK;
+  return gmr::read_back({{filtered_lin_vel, st.filtered_lin_vel, n * 12}, {filtered_ang_vel, st.filtered_ang_vel, n * 12},
+                         {last_root_vel, st.last_root_vel, n * 24}, {last_actions, st.last_actions, nr}, {last_dof_vel, st.last_dof_vel, nr},
+                         {noise_tick, st.noise_tick, n * 4}});
 }
 
 }  // extern "C"

@@ -111,7 +111,7 @@ static int record_launch(const RolloutTables& R, int N, const RecordSlots& S, co
   X.N = N;
   if (reward || done || time_outs) total += N;
   if (total == 0) return GMR_OK;
-  hipLaunchKernelGGL(tracker_rollout_record_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, X);
+  hipLaunchKernelGGL(tracker_rollout_record_kernel, dim3(lane_blocks(total)), dim3(256), 0, stream, X);
   GMR_HIP_TRY(hipGetLastError());
   return GMR_OK;
 }
@@ -321,11 +321,9 @@ int gmr_motion_tracker_set_rollout(gmr_motion_tracker_t* t, int horizon, int obs
   const size_t groups = ((size_t)t->N + gmr::ENVS - 1) / gmr::ENVS;
   gmr::Carve cv;
   const size_t o_part = cv.take(groups * 16), o_sums = cv.take(32);
-  GMR_HIP_TRY(hipDeviceSynchronize());               // nothing in flight reads the scratch a larger block replaces
-  GMR_HIP_TRY(t->rollout_block.reserve(cv.total() + 256));
+  const int rc = gmr::fresh_block(t->rollout_block, cv);
+  if (rc != GMR_OK) return rc;
   char* d = t->rollout_block.data();
-  GMR_HIP_TRY(hipMemset(d, 0, cv.total()));
-  GMR_HIP_TRY(hipDeviceSynchronize());
   R.part = (double*)(d + o_part);
   R.sums = (double*)(d + o_sums);
   t->rollout = R;

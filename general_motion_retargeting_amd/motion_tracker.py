@@ -729,32 +729,11 @@ class MotionTracker:
         for k, v in {**norm, **scalars}.items():
             if not np.isfinite(v):
                 raise ValueError(f"{k} = {v} must be finite")
-        specs = []
         noise = {} if noise is None else dict(noise)
         unknown = sorted(set(noise) - set(PROPRIO_NOISE_BLOCKS))
         if unknown:
             raise KeyError(f"noise: unknown blocks {unknown} (known: {list(PROPRIO_NOISE_BLOCKS)})")
-        for k in PROPRIO_NOISE_BLOCKS:
-            spec = noise.get(k)
-            if spec is None or spec.get("distribution", "none") == "none":
-                specs.append((0, 0, 0.0, 0.0))
-                continue
-            dist, op = spec.get("distribution"), spec.get("operation")
-            if dist not in NOISE_DISTRIBUTIONS:
-                raise ValueError(f"noise[{k!r}]: distribution is one of {sorted(NOISE_DISTRIBUTIONS)}, got {dist!r}")
-            if op not in NOISE_OPERATIONS:
-                raise ValueError(f"noise[{k!r}]: operation is one of {sorted(NOISE_OPERATIONS)}, got {op!r}")
-            rng = spec.get("range")
-            if rng is None or len(rng) != 2:
-                raise ValueError(f"noise[{k!r}]: range is a pair, got {rng!r}")
-            a, b = float(rng[0]), float(rng[1])
-            with np.errstate(over="ignore"):
-                fits = all(np.isfinite(np.float32(x)) for x in (a, b, b - a))
-            if not fits:
-                raise ValueError(f"noise[{k!r}]: range {(a, b)} is not finite in float32")
-            if dist == "gaussian" and b < 0:
-                raise ValueError(f"noise[{k!r}]: a gaussian's deviation {b} is negative")
-            specs.append((NOISE_DISTRIBUTIONS[dist], NOISE_OPERATIONS[op], a, b))
+        specs = [self._noise_spec(f"noise[{k!r}]", noise.get(k)) for k in PROPRIO_NOISE_BLOCKS]
         if scales is None:
             sc = np.zeros(len(PROPRIO_TERMS), np.float32)
         else:
@@ -1314,27 +1293,7 @@ class MotionTracker:
     def _disturb_setup(kick_lin_vel, kick_ang_vel, push_force, push_torque, kick_every, push_every, push_duration, scale_push_force,
                        scale_push_torque):
         """the checks of :meth:`set_disturbances`, all of them before the library is loaded -> a dict of the checked values"""
-        specs = []
-        for k, spec in zip(DISTURB_SPECS, (kick_lin_vel, kick_ang_vel, push_force, push_torque)):
-            if spec is None or spec.get("distribution", "none") == "none":
-                specs.append((0, 0, 0.0, 0.0))
-                continue
-            dist, op = spec.get("distribution"), spec.get("operation")
-            if dist not in NOISE_DISTRIBUTIONS:
-                raise ValueError(f"{k}: distribution is one of {sorted(NOISE_DISTRIBUTIONS)}, got {dist!r}")
-            if op not in NOISE_OPERATIONS:
-                raise ValueError(f"{k}: operation is one of {sorted(NOISE_OPERATIONS)}, got {op!r}")
-            rng = spec.get("range")
-            if rng is None or len(rng) != 2:
-                raise ValueError(f"{k}: range is a pair, got {rng!r}")
-            a, b = float(rng[0]), float(rng[1])
-            with np.errstate(over="ignore"):
-                fits = all(np.isfinite(np.float32(x)) for x in (a, b, b - a))
-            if not fits:
-                raise ValueError(f"{k}: range {(a, b)} is not finite in float32")
-            if dist == "gaussian" and b < 0:
-                raise ValueError(f"{k}: a gaussian's deviation {b} is negative")
-            specs.append((NOISE_DISTRIBUTIONS[dist], NOISE_OPERATIONS[op], a, b))
+        specs = [MotionTracker._noise_spec(k, s) for k, s in zip(DISTURB_SPECS, (kick_lin_vel, kick_ang_vel, push_force, push_torque))]
         for k, v, least in (("kick_every", kick_every, 1), ("push_every", push_every, 1), ("push_duration", push_duration, 0)):
             if int(v) != v or not least <= v < 2 ** 31:
                 raise ValueError(f"{k} = {v}: a whole number of steps, at least {least}, is needed (the caller's ceil(seconds / dt))")
