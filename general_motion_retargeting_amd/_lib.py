@@ -199,6 +199,12 @@ _SIGS = {
     "gmr_motion_tracker_optimizer_step": (C.c_int, [C.c_void_p] * 4),
     "gmr_motion_tracker_optimizer_state": (C.c_int, [C.c_void_p] * 4),
     "gmr_motion_tracker_optimizer_load_state": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "gmr_motion_tracker_set_policy": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "gmr_motion_tracker_act_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p]),
+    "gmr_motion_tracker_act": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int]),
+    "gmr_motion_tracker_values_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 5),
+    "gmr_motion_tracker_values": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 4),
+    "gmr_motion_tracker_policy_state": (C.c_int, [C.c_void_p] * 3),
     "gmr_comm_create": (C.c_int, [C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),
     "gmr_comm_destroy": (C.c_int, [C.c_void_p]),
     "gmr_comm_rank": (C.c_int, [C.c_void_p]),
@@ -990,6 +996,13 @@ LOSS_IN_FIELDS, LOSS_OUT_FIELDS = _arrays(LOSS_IN), _arrays(LOSS_OUT)
 # gmr_motion_tracker_set_optimizer / _optimizer_step[_dev] / _optimizer_state / _optimizer_load_state (include/gmr_hip.h, "tracker optimiser")
 OPT_CHUNK, OPT_MAX_TENSORS = 1024, 32
 OPT_INFO = ("total_norm", "coef", "learning_rate", "step")
+
+# gmr_motion_tracker_set_policy / _act[_dev] / _values[_dev] / _policy_state (include/gmr_hip.h, "tracker policy"): the arrays of a call
+# per network, the parameters and the hidden activations aside (lists, their shapes follow from set_policy)
+POLICY_TILE, POLICY_MAX_HIDDEN, POLICY_WIDTH_STEP, POLICY_MAX_WIDTH, POLICY_MAX_IN, POLICY_MAX_TENSORS = 32, 4, 32, 256, 512, 21
+POLICY_ACT = (("obs", _F, ("M", "O")), ("loc", _F, ("M", "A")), ("actions", _F, ("M", "A")))
+POLICY_VALUES = (("obs", _F, ("M", "O")), ("priv", _F, ("M", "P")), ("values", _F, ("M",)))
+POLICY_SHAPE = 16                        # the i32 words of gmr_motion_tracker_policy_state
 
 
 class LossIn(C.Structure):

@@ -8,7 +8,8 @@
 // gmr_tracker_episode.hip its reset-state and reward tables, the reset counters and the arrays of the episode statistics,
 // gmr_tracker_rollout.hip its rollout configuration and the partial sums of an advantages call, gmr_tracker_loss.hip its loss configuration,
 // the partial sums of a loss call and the learning rate, gmr_tracker_optim.hip its optimiser configuration, the Adam state, the chunk table
-// and the scalars of a step.  What those translation units share beyond the structs lives beside them: gmr_tracker_host.h (host: the
+// and the scalars of a step, gmr_tracker_policy.hip the shapes of its two networks and the counts of the sampled actions.  What those
+// translation units share beyond the structs lives beside them: gmr_tracker_host.h (host: the
 // checks of a noise spec and of a list of environments, grid sizes, the ignored-id count, the allocation and the read-back of a block's
 // state; also the noise spec itself, ProprioNoise) and gmr_tracker_dev.h (device: draws, noise, heading, small vectors, group reductions).
 #pragma once
@@ -22,6 +23,7 @@
 #include "gmr_internal.h"
 #include "gmr_link_plan.h"
 #include "gmr_tracker_host.h"
+#include "gmr_tracker_policy_plan.h"
 #include "gmr_workspace.h"
 
 struct gmr_fk {
@@ -290,6 +292,13 @@ struct OptimTables {
   double* state = nullptr;                  // [4] the rate of the next step, the step count, beta1^t, beta2^t
   float* scal = nullptr;                    // [4] coef, bc2s, ns of the step in flight
 };
+// the two networks of a tracker: their shapes as given and the device pointer into the policy block
+struct PolicyTables {
+  int32_t on = 0;                           // 0: the policy was never set
+  int32_t obs_cols = 0, priv_cols = 0, act_cols = 0;
+  PolicyShape actor, critic;
+  uint32_t* counts = nullptr;               // [N] the actions sampled for the environment so far
+};
 }  // namespace gmr
 
 struct gmr_motion_tracker {
@@ -337,6 +346,8 @@ struct gmr_motion_tracker {
   gmr::DeviceBlock loss_block;   // the partial sums of a loss call and the learning rate: one allocation, made by gmr_motion_tracker_set_loss
   gmr::OptimTables optim;        // optim.K = 0 until gmr_motion_tracker_set_optimizer configures it
   gmr::DeviceBlock optim_block;  // the Adam state, the chunk table, the partial sums and the scalars of a step: one allocation, made by gmr_motion_tracker_set_optimizer
+  gmr::PolicyTables policy;      // policy.on = 0 until gmr_motion_tracker_set_policy configures it
+  gmr::DeviceBlock policy_block; // the per-environment counts of the sampled actions: one allocation, made by gmr_motion_tracker_set_policy
   std::vector<double> clip_w;    // the clip weights as given at creation (empty: uniform)
   std::mutex mu;                 // the tables, and the whole of every synchronous entry point
 };

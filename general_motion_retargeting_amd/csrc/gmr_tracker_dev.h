@@ -32,8 +32,8 @@ struct TrackerOut {
 };
 
 // Word 3 of a Philox counter keeps the draws of the blocks apart: the clip and start draws of resets and finished clips, the sensor noise
-// (DESIGN.md section 6q), the command resample (6s), the kicks and pushes (6s), the reset states (6t).
-constexpr uint32_t DRAW_RESET = 0u, DRAW_SENSOR = 1u, DRAW_COMMAND = 2u, DRAW_DISTURB = 3u, DRAW_RESET_STATE = 4u;
+// (DESIGN.md section 6q), the command resample (6s), the kicks and pushes (6s), the reset states (6t), the sampled actions (6z).
+constexpr uint32_t DRAW_RESET = 0u, DRAW_SENSOR = 1u, DRAW_COMMAND = 2u, DRAW_DISTURB = 3u, DRAW_RESET_STATE = 4u, DRAW_ACTION = 5u;
 
 // (float)(T / fps) of clip c; 0 for a clip id outside [0, C)
 __device__ __forceinline__ float clip_length(const MotionArrays& A, int c) {

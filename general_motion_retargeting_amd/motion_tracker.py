@@ -24,6 +24,8 @@ with their resampling and curriculum, the command-tracking terms, and the kicks 
 :meth:`MotionTracker.record` / :meth:`MotionTracker.advantages` (6u), :meth:`MotionTracker.loss` (6v) and
 :meth:`MotionTracker.optimizer_step` (6x, ``csrc/gmr_tracker_optim.hip``: the clip of the gradient norm and the Adam step in three
 launches) leave the networks and their backward pass as the only part of a training iteration that is not a call of this class.
+:meth:`MotionTracker.act` and :meth:`MotionTracker.values` (6z, ``csrc/gmr_tracker_policy.hip``) are the forward pass of those networks
+without autograd -- the ELU MLPs of the reference's ``model.py`` on the FP32 matrix instructions, one launch each, with the sampled action.
 
 No GPU framework is imported here: :meth:`MotionTracker.step` takes and returns NumPy arrays, :meth:`MotionTracker.step_dev` reads
 and writes device memory the caller names -- ``_lib.DeviceBuffer``, a raw address, or anything with ``data_ptr()``.
@@ -180,6 +182,7 @@ class MotionTracker:
     _rollout = None          # the checked configuration once set_rollout has configured the rollout
     _loss = None             # the checked configuration, with its rows and columns, once set_loss has configured the loss head
     _optim = None            # the checked configuration (sizes, rate or None: follow, betas, eps, max_norm) once set_optimizer has run
+    _policy = None           # the checked shapes of the two networks and the sizes of their parameter list once set_policy has run
     _disturb = None          # (kick_every, push_every, push_duration) once set_disturbances has configured kicks and pushes
 
     def _init_state(self, library, num_envs, nrobot_dof=None) -> None:
@@ -2115,6 +2118,194 @@ class MotionTracker:
             flat.append(np.concatenate(x))
         _lib.check(_lib.lib().gmr_motion_tracker_optimizer_load_state(self.handle, step, _lib._ptr(flat[0]), _lib._ptr(flat[1])))
 
+    # ---- the forward pass of the actor and the critic -----------------------------------------------------------
+    @staticmethod
+    def _policy_hidden_widths(what: str, net: str, hidden):
+        try:
+            hidden = tuple(int(h) for h in hidden)
+        except TypeError:
+            raise ValueError(f"{what}: {net}_hidden is a list of widths") from None
+        if not 1 <= len(hidden) <= _lib.POLICY_MAX_HIDDEN:
+            raise ValueError(f"{what}: {net}_hidden names {len(hidden)} hidden layers, 1 .. {_lib.POLICY_MAX_HIDDEN} are taken")
+        for l, h in enumerate(hidden):
+            if not _lib.POLICY_WIDTH_STEP <= h <= _lib.POLICY_MAX_WIDTH or h % _lib.POLICY_WIDTH_STEP:
+                raise ValueError(f"{what}: {net}_hidden[{l}] = {h}: a multiple of {_lib.POLICY_WIDTH_STEP} in {_lib.POLICY_WIDTH_STEP} .. "
+                                 f"{_lib.POLICY_MAX_WIDTH} is needed")
+        return hidden
+
+    def _policy_setup(self, obs_cols, priv_cols, act_cols, actor_hidden, critic_hidden):
+        """the checks of :meth:`set_policy`, all of them before the library is loaded -> a dict of the checked shapes, with ``sizes``, the
+        element counts of the parameter list, and ``first``, where each network's ``(W, b)`` pairs start in it"""
+        what = "set_policy"
+        O, P, A = int(obs_cols), int(priv_cols), int(act_cols)
+        if O < 1 or P < 0 or O + P > _lib.POLICY_MAX_IN:
+            raise ValueError(f"{what}: obs_cols = {O} and priv_cols = {P}: an input width of 1 .. {_lib.POLICY_MAX_IN} is needed (obs_cols at least 1)")
+        if not 1 <= A <= _lib.LOSS_MAX_ACT:
+            raise ValueError(f"{what}: act_cols = {A}, 1 .. {_lib.LOSS_MAX_ACT} are taken")
+        ah, ch = self._policy_hidden_widths(what, "actor", actor_hidden), self._policy_hidden_widths(what, "critic", critic_hidden)
+        widths = {"critic": (O + P,) + ch + (1,), "actor": (O,) + ah + (A,)}
+        sizes, first = [A], {}
+        for net in ("critic", "actor"):
+            first[net] = len(sizes)
+            w = widths[net]
+            for l in range(len(w) - 1):
+                sizes += [w[l + 1] * w[l], w[l + 1]]
+        return {"obs_cols": O, "priv_cols": P, "act_cols": A, "actor_hidden": ah, "critic_hidden": ch, "widths": widths, "sizes": tuple(sizes), "first": first}
+
+    def set_policy(self, obs_cols: int, priv_cols: int, act_cols: int, actor_hidden=(256, 128, 128), critic_hidden=(256, 256, 128)) -> None:
+        """Configures the two networks of the reference's ``ActorCritic(act_cols, obs_cols, priv_cols)`` (booster_gym/utils/model.py:9-27,
+        the defaults are its widths): ELU MLPs of 1 .. 4 hidden layers, every width a multiple of 32 up to 256, the critic on ``obs`` and
+        ``priv`` side by side (at most 512 columns together), at most 32 actions.  The parameters stay the caller's: every call takes the
+        list ``[logstd, critic W, b, .., actor W, b, ..]`` -- ``list(model.parameters())``, the list :meth:`optimizer_step_dev` takes.  The
+        tracker keeps one count of sampled actions per environment, zero after this call.  Synchronous."""
+        c = self._policy_setup(obs_cols, priv_cols, act_cols, actor_hidden, critic_hidden)
+        ah, ch = np.array(c["actor_hidden"], np.int32), np.array(c["critic_hidden"], np.int32)
+        _lib.check(_lib.lib().gmr_motion_tracker_set_policy(self.handle, c["obs_cols"], c["priv_cols"], c["act_cols"], len(ah), _lib._ptr(ah), len(ch), _lib._ptr(ch)))
+        self._policy = c
+
+    def _need_policy(self, what: str):
+        c = self._policy
+        if c is None:
+            raise ValueError(f"{what}: the policy is not set on this tracker, call set_policy() first")
+        return c
+
+    def _policy_rows(self, what: str, rows, sample: bool) -> int:
+        M = self.num_envs if rows is None else int(rows)
+        if M < 1:
+            raise ValueError(f"{what}: rows = {rows}: at least 1 is needed")
+        if sample and M != self.num_envs:
+            raise ValueError(f"{what}: sample=True draws for the environments, row e is environment e: rows = {M}, num_envs = {self.num_envs}")
+        return M
+
+    @staticmethod
+    def _policy_params(what: str, c, params, device: bool):
+        """the parameter list as a table of K addresses -> (table, arrays to keep alive)"""
+        try:
+            params = list(params)
+        except TypeError:
+            raise ValueError(f"{what}: params is the list of the model's parameters") from None
+        K = len(c["sizes"])
+        if len(params) != K:
+            raise ValueError(f"{what}: params names {len(params)} tensors, the policy was set for K = {K}")
+        table, keep = (C.c_void_p * K)(), []
+        for k, n in enumerate(c["sizes"]):
+            if params[k] is None:
+                raise ValueError(f"{what}: params[{k}] is needed")
+            if device:
+                table[k] = _dev_ptr(params[k], f"params[{k}]", "float32", n).value
+                continue
+            a = np.ascontiguousarray(params[k], dtype=np.float32)
+            if a.size != n:
+                raise ValueError(f"{what}: params[{k}]: {a.size} elements, {n} needed")
+            keep.append(a)
+            table[k] = a.ctypes.data
+        return table, keep
+
+    @staticmethod
+    def _policy_hidden(what: str, c, net: str, hidden, M: int, device: bool):
+        """the optional hidden activations of a network -> (table of L addresses or None, {layer: host array})"""
+        widths = c["widths"][net][1:-1]
+        if hidden is None:
+            return None, {}
+        if device:
+            hidden = list(hidden)
+            if len(hidden) != len(widths):
+                raise ValueError(f"{what}: hidden names {len(hidden)} layers, the {net} has {len(widths)} hidden layers (None leaves one out)")
+            table = (C.c_void_p * len(widths))()
+            for l, h in enumerate(widths):
+                p = _dev_ptr(hidden[l], f"hidden[{l}]", "float32", M * h)
+                table[l] = None if p is None else p.value
+            return table, {}
+        out = {l: np.empty((M, h), np.float32) for l, h in enumerate(widths)}
+        return (C.c_void_p * len(widths))(*(a.ctypes.data for a in out.values())), out
+
+    def act_dev(self, params, obs, loc, actions=None, hidden=None, sample: bool = True, rows: Optional[int] = None, stream=None) -> None:
+        """``model.act(obs)`` (model.py:29-32) on device memory, asynchronous on ``stream``: ONE launch, no host synchronisation.  ``obs
+        f32[rows*obs_cols]`` -> ``loc f32[rows*act_cols]`` and, with ``sample``, ``actions = loc + exp(logstd) * r`` with the tracker's own
+        Gaussian draw -- ``model.act(obs).sample()`` of runner.py:109-111; sampling needs ``rows == num_envs`` (the default) and advances every
+        environment's count.  ``sample=False`` is ``model.act(obs).loc`` for any ``rows``: the old-policy pass over the whole buffer, and
+        ``Runner.play``.  ``hidden`` is a list with one array ``f32[rows*h_l]`` or ``None`` per hidden layer, for the activations after each
+        ELU.  ``params`` is the list of :meth:`set_policy`, read in place: an :meth:`optimizer_step_dev` before this call is seen by it.
+        Every array is a ``_lib.DeviceBuffer``, a raw address or an object with ``data_ptr()``."""
+        c = self._need_policy("act_dev")
+        M = self._policy_rows("act_dev", rows, sample)
+        A = c["act_cols"]
+        table, _ = self._policy_params("act_dev", c, params, device=True)
+        hid, _ = self._policy_hidden("act_dev", c, "actor", hidden, M, device=True)
+        d_obs, d_loc = _dev_ptr(obs, "obs", "float32", M * c["obs_cols"]), _dev_ptr(loc, "loc", "float32", M * A)
+        d_act = _dev_ptr(actions, "actions", "float32", M * A)
+        if d_obs is None or d_loc is None or (sample and d_act is None):
+            raise ValueError("act_dev: obs and loc are needed" + (", and actions with sample=True" if sample else ""))
+        _lib.check(_lib.lib().gmr_motion_tracker_act_dev(self.handle, table, M, d_obs, d_loc, d_act if sample else None, hid, 1 if sample else 0, _lib._s(stream)))
+
+    def act(self, params, obs, sample: bool = True, hidden: bool = False) -> Dict[str, object]:
+        """:meth:`act_dev` on host arrays: ``obs [rows, obs_cols]`` -> ``{"loc": [rows, act_cols]}``, with ``sample`` also ``"actions"``, with
+        ``hidden`` also ``"hidden"``, the list of every hidden layer's activations."""
+        c = self._need_policy("act")
+        obs = np.ascontiguousarray(obs, dtype=np.float32)
+        if obs.ndim != 2 or obs.shape[1] != c["obs_cols"]:
+            raise ValueError(f"act: obs: shape {obs.shape}, (rows, {c['obs_cols']}) needed")
+        M = self._policy_rows("act", obs.shape[0], sample)
+        table, keep = self._policy_params("act", c, params, device=False)
+        hid, hout = self._policy_hidden("act", c, "actor", True if hidden else None, M, device=False)
+        out = {"loc": np.empty((M, c["act_cols"]), np.float32)}
+        if sample:
+            out["actions"] = np.empty((M, c["act_cols"]), np.float32)
+        _lib.check(_lib.lib().gmr_motion_tracker_act(self.handle, table, M, _lib._ptr(obs), _lib._ptr(out["loc"]), _lib._ptr(out.get("actions")), hid,
+                                                     1 if sample else 0))
+        if hidden:
+            out["hidden"] = list(hout.values())
+        return out
+
+    def values_dev(self, params, obs, priv, values, hidden=None, rows: Optional[int] = None, stream=None) -> None:
+        """``model.est_value(obs, privileged_obs)`` (model.py:34-36) on device memory, asynchronous on ``stream``: ONE launch, the two
+        inputs concatenated inside it.  ``obs f32[rows*obs_cols]``, ``priv f32[rows*priv_cols]`` (``None`` when ``priv_cols`` is 0) ->
+        ``values f32[rows]``; ``rows`` defaults to ``num_envs``, the ``last_values`` pass of runner.py:133.  ``hidden`` and ``params`` as in
+        :meth:`act_dev`."""
+        c = self._need_policy("values_dev")
+        M = self._policy_rows("values_dev", rows, False)
+        table, _ = self._policy_params("values_dev", c, params, device=True)
+        hid, _ = self._policy_hidden("values_dev", c, "critic", hidden, M, device=True)
+        d_obs, d_val = _dev_ptr(obs, "obs", "float32", M * c["obs_cols"]), _dev_ptr(values, "values", "float32", M)
+        d_priv = _dev_ptr(priv, "priv", "float32", M * c["priv_cols"])
+        if d_obs is None or d_val is None or (c["priv_cols"] and d_priv is None):
+            raise ValueError("values_dev: obs and values are needed" + (", and priv" if c["priv_cols"] else ""))
+        _lib.check(_lib.lib().gmr_motion_tracker_values_dev(self.handle, table, M, d_obs, d_priv if c["priv_cols"] else None, d_val, hid, _lib._s(stream)))
+
+    def values(self, params, obs, priv=None, hidden: bool = False) -> Dict[str, object]:
+        """:meth:`values_dev` on host arrays: ``obs [rows, obs_cols]``, ``priv [rows, priv_cols]`` -> ``{"values": [rows]}``, with ``hidden``
+        also ``"hidden"``."""
+        c = self._need_policy("values")
+        obs = np.ascontiguousarray(obs, dtype=np.float32)
+        if obs.ndim != 2 or obs.shape[1] != c["obs_cols"]:
+            raise ValueError(f"values: obs: shape {obs.shape}, (rows, {c['obs_cols']}) needed")
+        M = self._policy_rows("values", obs.shape[0], False)
+        P = c["priv_cols"]
+        if P:
+            priv = np.ascontiguousarray(priv, dtype=np.float32) if priv is not None else None
+            if priv is None or priv.shape != (M, P):
+                raise ValueError(f"values: priv: shape {None if priv is None else priv.shape}, {(M, P)} needed")
+        else:
+            priv = None
+        table, keep = self._policy_params("values", c, params, device=False)
+        hid, hout = self._policy_hidden("values", c, "critic", True if hidden else None, M, device=False)
+        out = {"values": np.empty(M, np.float32)}
+        _lib.check(_lib.lib().gmr_motion_tracker_values(self.handle, table, M, _lib._ptr(obs), _lib._ptr(priv), _lib._ptr(out["values"]), hid))
+        if hidden:
+            out["hidden"] = list(hout.values())
+        return out
+
+    def policy_state(self) -> Optional[Dict[str, object]]:
+        """The shapes :meth:`set_policy` was given, as the library holds them, ``tile``, the rows a workgroup owns, and ``counts u32[N]``,
+        the actions sampled for every environment so far; ``None`` when the policy was never set.  Synchronises."""
+        if self._policy is None:
+            return None
+        shape, counts = np.zeros(_lib.POLICY_SHAPE, np.int32), np.empty(self.num_envs, np.uint32)
+        _lib.check(_lib.lib().gmr_motion_tracker_policy_state(self.handle, _lib._ptr(shape), _lib._ptr(counts)))
+        s = [int(x) for x in shape]
+        return {"obs_cols": s[0], "priv_cols": s[1], "act_cols": s[2], "actor_hidden": tuple(s[4:4 + s[3]]), "critic_hidden": tuple(s[9:9 + s[8]]),
+                "tile": s[13], "counts": counts}
+
     # ---- the step ---------------------------------------------------------------------------------------------------------
     def _counts(self):
         return _lib.widths(_lib.TRACKER_OUT, R=self.nrobot_dof), _lib.widths(_lib.TRACKER_SIM, R=self.nrobot_dof)
@@ -2411,6 +2602,7 @@ class MotionTracker:
             self.handle = None
             self._proprio = None          # the state arrays went with the handle
             self._optim = None            # and so did exp_avg and exp_avg_sq
+            self._policy = None           # and the counts of the sampled actions
 
     def __del__(self):
         try:

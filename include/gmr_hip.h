@@ -1536,6 +1536,62 @@ int gmr_motion_tracker_optimizer_state(gmr_motion_tracker_t* t, int64_t* step, f
  * current one; synchronises the device. */
 int gmr_motion_tracker_optimizer_load_state(gmr_motion_tracker_t* t, int64_t step, const float* exp_avg, const float* exp_avg_sq);
 
+/* ---- N17: tracker policy (the forward pass of the actor and of the critic of a motion tracker) ---- */
+/* What booster_gym/utils/model.py computes without autograd: model.act(obs).loc and .sample() (model.py:29-32, runner.py:109-111 and :123-124,
+ * the whole of Runner.play, :225-226), and model.est_value(obs, privileged_obs) (model.py:34-36, runner.py:133).  The statement of record is
+ * tests/policy_mirror.py; this is the same in words.
+ * A NETWORK is an MLP in -> h_1 -> .. -> h_L -> out, 1 <= L <= GMR_POLICY_MAX_HIDDEN: y = x W^T + b with W [out][in] row-major float32,
+ * the layout of torch.nn.Linear; ELU (alpha 1) after every hidden layer, none after the last.  Per output element, in float32:
+ *   z = b_j + sum_k x_k W_jk,   elu(z) = z > 0 ? z : expm1f(z).
+ * THE SUM is a chain of fused multiply-adds from +0, one rounding per term, the bias added last; its order over k is a function of the
+ * layer's shape alone: a hidden layer takes the k in blocks of eight, within a block 0, 4, 1, 5, 2, 6, 3, 7 (the two halves of a
+ * wavefront hold four consecutive k each and the matrix instruction takes one of either per step); the last layer takes them in rising
+ * order.  No floating-point atomics.  A row's result depends on nothing but that row: not on rows, not on the tile the row falls in,
+ * not on the optional outputs asked for, not on the alignment of a tensor.
+ * CAPACITIES: hidden widths are multiples of GMR_POLICY_WIDTH_STEP in GMR_POLICY_WIDTH_STEP .. GMR_POLICY_MAX_WIDTH; obs_cols >= 1,
+ * priv_cols >= 0, obs_cols + priv_cols <= GMR_POLICY_MAX_IN; act_cols in 1 .. GMR_LOSS_MAX_ACT; the critic's output width is 1.
+ * Anything else is GMR_ERR_ARG.
+ * THE PARAMETERS travel by address in the kernel arguments with every call, as the optimiser's do (N16): params is a HOST array of
+ * device addresses in the order of model.parameters() -- logstd [act_cols], the critic's (W, b) pairs, the actor's (W, b) pairs: the
+ * very list gmr_motion_tracker_optimizer_step_dev takes.  Nothing is copied or cached: a step of the optimiser between two calls is
+ * seen by the next one.  Any 4-byte-aligned address is taken; a weight tensor on 16 bytes whose rows are a multiple of 16 bytes is read
+ * 16 bytes at a time, with the same bits.
+ * THE ACTOR reads obs [rows][obs_cols] and writes loc [rows][act_cols].  With sample != 0 it also writes
+ *   actions[e][i] = loc[e][i] + exp(logstd[i]) * r(e, i),
+ * r the Gaussian draw of the tracker's noise (N10): Box-Muller on the two Philox words of element i of environment e at its count,
+ * counter domain 5 (the sampled actions), keyed by the tracker's seed.  The policy block keeps one uint32 count per environment;
+ * sampling needs rows == N (row e is environment e) and advances every count by one.  Without sample, actions is not written, no
+ * count is touched and any rows >= 1 is taken.
+ * THE CRITIC reads its input from TWO arrays, obs [rows][obs_cols] and priv [rows][priv_cols] (model.py:35, concatenated in LDS; priv
+ * may be NULL when priv_cols is 0), and writes values [rows].
+ * hidden, when given, is a HOST array of L addresses, each NULL or [rows][h_l]: the activations after the ELU of hidden layer l.
+ * ONE launch per call: a workgroup owns GMR_POLICY_TILE rows, whose activations stay in LDS from the first layer to the last; rows
+ * beyond `rows` in the last tile are neither read nor written.  Everything is enqueued on the caller's stream; no call waits for the
+ * host.  NO OVERLAP: no output may overlap another one, an input or a parameter; nothing checks it.  The tracker stays SINGLE-STREAM. */
+#define GMR_POLICY_TILE 32
+#define GMR_POLICY_MAX_HIDDEN 4
+#define GMR_POLICY_WIDTH_STEP 32
+#define GMR_POLICY_MAX_WIDTH 256
+#define GMR_POLICY_MAX_IN 512
+#define GMR_POLICY_MAX_TENSORS 21
+/* The two networks of model.py:9-27: n_*_hidden widths each.  Allocates the counts, zero; a second call replaces the block and zeroes
+ * the counts again; synchronises the device. */
+int gmr_motion_tracker_set_policy(gmr_motion_tracker_t* t, int obs_cols, int priv_cols, int act_cols, int n_actor_hidden, const int* actor_hidden,
+                                  int n_critic_hidden, const int* critic_hidden);
+/* model.act(obs) (model.py:29-32): loc, and with sample the action of runner.py:111.  ONE launch. */
+int gmr_motion_tracker_act_dev(gmr_motion_tracker_t* t, const float* const* d_params, int64_t rows, const float* d_obs, float* d_loc, float* d_actions,
+                               float* const* d_hidden, int sample, void* stream);                   /* asynchronous */
+int gmr_motion_tracker_act(gmr_motion_tracker_t* t, const float* const* params, int64_t rows, const float* obs, float* loc, float* actions,
+                           float* const* hidden, int sample);
+/* model.est_value(obs, privileged_obs) (model.py:34-36).  ONE launch. */
+int gmr_motion_tracker_values_dev(gmr_motion_tracker_t* t, const float* const* d_params, int64_t rows, const float* d_obs, const float* d_priv,
+                                  float* d_values, float* const* d_hidden, void* stream);           /* asynchronous */
+int gmr_motion_tracker_values(gmr_motion_tracker_t* t, const float* const* params, int64_t rows, const float* obs, const float* priv, float* values,
+                              float* const* hidden);
+/* The shapes of model.py:9-27 as given -- shape i32[16]: obs_cols, priv_cols, act_cols, the actor's L and four widths (0 beyond L),
+ * the critic's L and four widths, GMR_POLICY_TILE, 0, 0 -- and counts u32[N] (or NULL); synchronises the device. */
+int gmr_motion_tracker_policy_state(gmr_motion_tracker_t* t, int32_t* shape, uint32_t* counts);
+
 /* ---- multi-GPU: one rank per GPU, ONE broadcast, no per-step collective ------------ */
 /* The reference parallelises over files with mp.Pool on one CPU (scripts/smplx_to_robot_dataset.py:241-242); here
  * streams shard over the ranks of one node and the only data that crosses ranks is the packed robot model + task set.
