@@ -205,6 +205,12 @@ _SIGS = {
     "gmr_motion_tracker_values_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 5),
     "gmr_motion_tracker_values": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 4),
     "gmr_motion_tracker_policy_state": (C.c_int, [C.c_void_p] * 3),
+    "gmr_motion_tracker_set_backward": (C.c_int, [C.c_void_p, C.c_int64]),
+    "gmr_motion_tracker_act_backward_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 5),
+    "gmr_motion_tracker_act_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 4),
+    "gmr_motion_tracker_values_backward_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 6),
+    "gmr_motion_tracker_values_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 5),
+    "gmr_motion_tracker_backward_state": (C.c_int, [C.c_void_p] * 2),
     "gmr_comm_create": (C.c_int, [C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),
     "gmr_comm_destroy": (C.c_int, [C.c_void_p]),
     "gmr_comm_rank": (C.c_int, [C.c_void_p]),
@@ -1003,6 +1009,10 @@ POLICY_TILE, POLICY_MAX_HIDDEN, POLICY_WIDTH_STEP, POLICY_MAX_WIDTH, POLICY_MAX_
 POLICY_ACT = (("obs", _F, ("M", "O")), ("loc", _F, ("M", "A")), ("actions", _F, ("M", "A")))
 POLICY_VALUES = (("obs", _F, ("M", "O")), ("priv", _F, ("M", "P")), ("values", _F, ("M",)))
 POLICY_SHAPE = 16                        # the i32 words of gmr_motion_tracker_policy_state
+
+# gmr_motion_tracker_set_backward / _act_backward[_dev] / _values_backward[_dev] / _backward_state (include/gmr_hip.h, "tracker policy backward")
+POLICY_BWD_CHUNK, POLICY_BWD_MAX_ROWS = 256, 131072
+POLICY_BWD_STATE = ("chunk", "chunks", "workspace_bytes", "max_rows", "actor_tiles", "critic_tiles")      # the i64 words of _backward_state
 
 
 class LossIn(C.Structure):

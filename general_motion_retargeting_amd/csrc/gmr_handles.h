@@ -24,6 +24,7 @@
 #include "gmr_link_plan.h"
 #include "gmr_tracker_host.h"
 #include "gmr_tracker_policy_plan.h"
+#include "gmr_tracker_policy_bwd_plan.h"
 #include "gmr_workspace.h"
 
 struct gmr_fk {
@@ -299,6 +300,15 @@ struct PolicyTables {
   PolicyShape actor, critic;
   uint32_t* counts = nullptr;               // [N] the actions sampled for the environment so far
 };
+// the backward pass through them: the plan, the shapes it was made for and the device pointers into its block
+struct PolicyBwdTables {
+  int32_t on = 0;                           // 0: set_backward never ran
+  PolicyBwdPlan plan;
+  PolicyShape actor, critic;                // as the policy stood at set_backward: a set_policy with other shapes invalidates the plan
+  int32_t obs_cols = 0, priv_cols = 0;
+  float* part = nullptr;                    // [chunks][elems of the larger network]
+  const PolicyBwdTile *tab_actor = nullptr, *tab_critic = nullptr;
+};
 }  // namespace gmr
 
 struct gmr_motion_tracker {
@@ -348,6 +358,8 @@ struct gmr_motion_tracker {
   gmr::DeviceBlock optim_block;  // the Adam state, the chunk table, the partial sums and the scalars of a step: one allocation, made by gmr_motion_tracker_set_optimizer
   gmr::PolicyTables policy;      // policy.on = 0 until gmr_motion_tracker_set_policy configures it
   gmr::DeviceBlock policy_block; // the per-environment counts of the sampled actions: one allocation, made by gmr_motion_tracker_set_policy
+  gmr::PolicyBwdTables bwd;      // bwd.on = 0 until gmr_motion_tracker_set_backward configures it
+  gmr::DeviceBlock bwd_block;    // the partial sums of dW and db per row chunk and the tile tables: one allocation, made by gmr_motion_tracker_set_backward
   std::vector<double> clip_w;    // the clip weights as given at creation (empty: uniform)
   std::mutex mu;                 // the tables, and the whole of every synchronous entry point
 };

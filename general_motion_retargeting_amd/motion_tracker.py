@@ -183,6 +183,7 @@ class MotionTracker:
     _loss = None             # the checked configuration, with its rows and columns, once set_loss has configured the loss head
     _optim = None            # the checked configuration (sizes, rate or None: follow, betas, eps, max_norm) once set_optimizer has run
     _policy = None           # the checked shapes of the two networks and the sizes of their parameter list once set_policy has run
+    _backward = None         # max_rows and the policy configuration it was planned for once set_backward has run
     _disturb = None          # (kick_every, push_every, push_duration) once set_disturbances has configured kicks and pushes
 
     def _init_state(self, library, num_envs, nrobot_dof=None) -> None:
@@ -2306,6 +2307,171 @@ class MotionTracker:
         return {"obs_cols": s[0], "priv_cols": s[1], "act_cols": s[2], "actor_hidden": tuple(s[4:4 + s[3]]), "critic_hidden": tuple(s[9:9 + s[8]]),
                 "tile": s[13], "counts": counts}
 
+    # ---- the backward pass through the actor and the critic ----------------------------------------------------
+    def _backward_setup(self, max_rows):
+        """the checks of :meth:`set_backward`, all of them before the library is loaded"""
+        c = self._need_policy("set_backward")
+        M = int(max_rows)
+        if M != max_rows or not 1 <= M <= _lib.POLICY_BWD_MAX_ROWS:
+            raise ValueError(f"set_backward: max_rows = {max_rows}: a whole number in 1 .. {_lib.POLICY_BWD_MAX_ROWS} is needed")
+        return {"max_rows": M, "policy": c}
+
+    def set_backward(self, max_rows: int) -> Dict[str, int]:
+        """Prepares ``loss.backward()`` through the two networks of :meth:`set_policy` for any ``rows`` in ``1 .. max_rows`` (at most
+        131 072): one workspace for the partial sums of every weight and bias gradient of the larger network per chunk of 256 rows, and
+        the tile tables of the weight-gradient launch.  Needs :meth:`set_policy` first, and again after a new ``set_policy``.  Returns
+        :meth:`backward_state`.  Synchronous."""
+        c = self._backward_setup(max_rows)
+        _lib.check(_lib.lib().gmr_motion_tracker_set_backward(self.handle, c["max_rows"]))
+        self._backward = c
+        return self.backward_state()
+
+    def _need_backward(self, what: str):
+        p = self._need_policy(what)
+        c = self._backward
+        if c is None:
+            raise ValueError(f"{what}: the backward pass is not set on this tracker, call set_backward() first")
+        if c["policy"] is not p:
+            raise ValueError(f"{what}: the policy was set again after the backward pass, call set_backward() again")
+        return c, p
+
+    def _backward_rows(self, what: str, c, rows) -> int:
+        M = self.num_envs if rows is None else int(rows)
+        if not 1 <= M <= c["max_rows"]:
+            raise ValueError(f"{what}: rows = {M}: 1 .. max_rows = {c['max_rows']} are taken")
+        return M
+
+    @staticmethod
+    def _backward_grads(what: str, p, net: str, grads):
+        """the gradient list as a table of K addresses: the network's own entries are needed, the others are not looked at"""
+        try:
+            grads = list(grads)
+        except TypeError:
+            raise ValueError(f"{what}: grads is the list of the gradients, in the order of params") from None
+        K = len(p["sizes"])
+        if len(grads) != K:
+            raise ValueError(f"{what}: grads names {len(grads)} tensors, the policy was set for K = {K}")
+        table = (C.c_void_p * K)()
+        first = p["first"][net]
+        for k in range(first, first + 2 * (len(p["widths"][net]) - 1)):
+            g = _dev_ptr(grads[k], f"grads[{k}]", "float32", p["sizes"][k])
+            if g is None or not g.value:
+                raise ValueError(f"{what}: grads[{k}] is needed: the {net}'s gradients are written in full")
+            table[k] = g.value
+        return table
+
+    @staticmethod
+    def _backward_layers(what: str, p, net: str, name: str, arrays, M: int):
+        """``hidden`` or ``delta``: one device array per hidden layer, all of them needed"""
+        widths = p["widths"][net][1:-1]
+        try:
+            arrays = list(arrays)
+        except TypeError:
+            raise ValueError(f"{what}: {name} is a list with one array per hidden layer") from None
+        if len(arrays) != len(widths):
+            raise ValueError(f"{what}: {name} names {len(arrays)} layers, the {net} has {len(widths)} hidden layers")
+        table = (C.c_void_p * len(widths))()
+        for l, h in enumerate(widths):
+            a = _dev_ptr(arrays[l], f"{name}[{l}]", "float32", M * h)
+            if a is None or not a.value:
+                raise ValueError(f"{what}: {name}[{l}] is needed: the backward pass takes every layer")
+            table[l] = a.value
+        return table
+
+    def act_backward_dev(self, params, grads, obs, hidden, grad_loc, delta, rows: Optional[int] = None, stream=None) -> None:
+        """The actor's share of ``loss.backward()`` (runner.py:163) on device memory, asynchronous on ``stream``: THREE launches, no host
+        synchronisation.  From ``grad_loc f32[rows*act_cols]`` (:meth:`loss_dev`), the ``hidden`` list :meth:`act_dev` wrote and ``obs``,
+        ``grads[k]`` of every weight and bias of the actor is OVERWRITTEN (no ``zero_grad``); ``grads[0]`` and the critic's entries are
+        not looked at.  ``params`` and ``grads`` are lists in the order of :meth:`set_policy`; ``delta`` is a list of caller-owned arrays
+        ``f32[rows*h_l]``, one per hidden layer, which receive the gradient at each layer's pre-activation.  Any ``rows`` in
+        ``1 .. max_rows`` (default ``num_envs``)."""
+        what = "act_backward_dev"
+        c, p = self._need_backward(what)
+        M = self._backward_rows(what, c, rows)
+        table, _ = self._policy_params(what, p, params, device=True)
+        tg = self._backward_grads(what, p, "actor", grads)
+        th, td = self._backward_layers(what, p, "actor", "hidden", hidden, M), self._backward_layers(what, p, "actor", "delta", delta, M)
+        d_obs, d_g = _dev_ptr(obs, "obs", "float32", M * p["obs_cols"]), _dev_ptr(grad_loc, "grad_loc", "float32", M * p["act_cols"])
+        if d_obs is None or d_g is None:
+            raise ValueError(f"{what}: obs and grad_loc are needed")
+        _lib.check(_lib.lib().gmr_motion_tracker_act_backward_dev(self.handle, table, tg, M, d_obs, th, d_g, td, _lib._s(stream)))
+
+    def values_backward_dev(self, params, grads, obs, priv, hidden, grad_values, delta, rows: Optional[int] = None, stream=None) -> None:
+        """The critic's share, as :meth:`act_backward_dev`: from ``grad_values f32[rows]``, the ``hidden`` list of :meth:`values_dev`,
+        ``obs`` and ``priv`` (side by side, ``None`` when ``priv_cols`` is 0) to ``grads[k]`` of the critic's weights and biases."""
+        what = "values_backward_dev"
+        c, p = self._need_backward(what)
+        M = self._backward_rows(what, c, rows)
+        table, _ = self._policy_params(what, p, params, device=True)
+        tg = self._backward_grads(what, p, "critic", grads)
+        th, td = self._backward_layers(what, p, "critic", "hidden", hidden, M), self._backward_layers(what, p, "critic", "delta", delta, M)
+        d_obs, d_g = _dev_ptr(obs, "obs", "float32", M * p["obs_cols"]), _dev_ptr(grad_values, "grad_values", "float32", M)
+        d_priv = _dev_ptr(priv, "priv", "float32", M * p["priv_cols"])
+        if d_obs is None or d_g is None or (p["priv_cols"] and d_priv is None):
+            raise ValueError(f"{what}: obs and grad_values are needed" + (", and priv" if p["priv_cols"] else ""))
+        _lib.check(_lib.lib().gmr_motion_tracker_values_backward_dev(self.handle, table, tg, M, d_obs, d_priv if p["priv_cols"] else None, th, d_g, td,
+                                                                   _lib._s(stream)))
+
+    def _backward_host(self, what: str, net: str, params, obs, priv, hidden, g_out):
+        """the NumPy twin of either call -> ``{"grads": {k: array in the tensor's shape}, "delta": [one array per hidden layer]}``"""
+        c, p = self._need_backward(what)
+        obs = np.ascontiguousarray(obs, dtype=np.float32)
+        if obs.ndim != 2 or obs.shape[1] != p["obs_cols"]:
+            raise ValueError(f"{what}: obs: shape {obs.shape}, (rows, {p['obs_cols']}) needed")
+        M = self._backward_rows(what, c, obs.shape[0])
+        P = p["priv_cols"] if net == "critic" else 0
+        if P:
+            priv = np.ascontiguousarray(priv, dtype=np.float32) if priv is not None else None
+            if priv is None or priv.shape != (M, P):
+                raise ValueError(f"{what}: priv: shape {None if priv is None else priv.shape}, {(M, P)} needed")
+        else:
+            priv = None
+        w = p["widths"][net]
+        g_out = np.ascontiguousarray(g_out, dtype=np.float32)
+        if g_out.size != M * w[-1]:
+            raise ValueError(f"{what}: the output gradient: {g_out.size} elements, {M * w[-1]} needed")
+        try:
+            hidden = [np.ascontiguousarray(h, dtype=np.float32) for h in hidden]
+        except TypeError:
+            raise ValueError(f"{what}: hidden is the list of the forward pass") from None
+        if len(hidden) != len(w) - 2:
+            raise ValueError(f"{what}: hidden names {len(hidden)} layers, the {net} has {len(w) - 2} hidden layers")
+        for l, h in enumerate(hidden):
+            if h.shape != (M, w[l + 1]):
+                raise ValueError(f"{what}: hidden[{l}]: shape {h.shape}, {(M, w[l + 1])} needed")
+        table, keep = self._policy_params(what, p, params, device=False)
+        K, first = len(p["sizes"]), p["first"][net]
+        grads, tg = {}, (C.c_void_p * K)()
+        for l in range(len(w) - 1):
+            grads[first + 2 * l] = np.empty((w[l + 1], w[l]), np.float32)
+            grads[first + 2 * l + 1] = np.empty(w[l + 1], np.float32)
+        for k, a in grads.items():
+            tg[k] = a.ctypes.data
+        delta = [np.empty((M, h), np.float32) for h in w[1:-1]]
+        th, td = (C.c_void_p * len(delta))(*(h.ctypes.data for h in hidden)), (C.c_void_p * len(delta))(*(d.ctypes.data for d in delta))
+        if net == "actor":
+            _lib.check(_lib.lib().gmr_motion_tracker_act_backward(self.handle, table, tg, M, _lib._ptr(obs), th, _lib._ptr(g_out), td))
+        else:
+            _lib.check(_lib.lib().gmr_motion_tracker_values_backward(self.handle, table, tg, M, _lib._ptr(obs), _lib._ptr(priv), th, _lib._ptr(g_out), td))
+        return {"grads": grads, "delta": delta}
+
+    def act_backward(self, params, obs, hidden, grad_loc) -> Dict[str, object]:
+        """:meth:`act_backward_dev` on host arrays -> ``{"grads": {k: the gradient of params[k]} for the actor's tensors, "delta": [..]}``"""
+        return self._backward_host("act_backward", "actor", params, obs, None, hidden, grad_loc)
+
+    def values_backward(self, params, obs, priv, hidden, grad_values) -> Dict[str, object]:
+        """:meth:`values_backward_dev` on host arrays, as :meth:`act_backward`, for the critic's tensors"""
+        return self._backward_host("values_backward", "critic", params, obs, priv, hidden, grad_values)
+
+    def backward_state(self) -> Optional[Dict[str, int]]:
+        """``chunk``, the rows of one partial sum, ``chunks`` for ``max_rows``, ``workspace_bytes``, ``max_rows`` and the entries of the
+        two tile tables, as the library holds them; ``None`` when :meth:`set_backward` never ran."""
+        if self._backward is None:
+            return None
+        state = np.zeros(len(_lib.POLICY_BWD_STATE), np.int64)
+        _lib.check(_lib.lib().gmr_motion_tracker_backward_state(self.handle, _lib._ptr(state)))
+        return {k: int(v) for k, v in zip(_lib.POLICY_BWD_STATE, state)}
+
     # ---- the step ---------------------------------------------------------------------------------------------------------
     def _counts(self):
         return _lib.widths(_lib.TRACKER_OUT, R=self.nrobot_dof), _lib.widths(_lib.TRACKER_SIM, R=self.nrobot_dof)
@@ -2603,6 +2769,7 @@ class MotionTracker:
             self._proprio = None          # the state arrays went with the handle
             self._optim = None            # and so did exp_avg and exp_avg_sq
             self._policy = None           # and the counts of the sampled actions
+            self._backward = None         # and the workspace of the backward pass
 
     def __del__(self):
         try:

@@ -1592,6 +1592,52 @@ int gmr_motion_tracker_values(gmr_motion_tracker_t* t, const float* const* param
  * the critic's L and four widths, GMR_POLICY_TILE, 0, 0 -- and counts u32[N] (or NULL); synchronises the device. */
 int gmr_motion_tracker_policy_state(gmr_motion_tracker_t* t, int32_t* shape, uint32_t* counts);
 
+/* ---- N18: tracker policy backward (loss.backward() through the actor and the critic of a motion tracker) ---- */
+/* What torch.autograd computes behind runner.py:163 through the two ELU MLPs of booster_gym/utils/model.py:9-27, from the gradients at
+ * the networks' outputs (grad_loc [rows][act_cols] and grad_values [rows] of N15) to one gradient per weight and bias, in the layout of
+ * the parameter list of N17.  The statement of record is tests/policy_bwd_mirror.py; this is the same in words, in the notation of N17:
+ * layer l = 0 .. L maps width[l] -> width[l + 1], hidden[l] is the activation after layer l's ELU, a_0 the input row (the critic's: obs
+ * and priv side by side, never concatenated in memory), a_l = hidden[l - 1].  Given g_L = grad_loc or grad_values, in float32:
+ *   for l = L .. 1:   dA[m][i] = sum_j g_l[m][j] W_l[j][i],    g_{l-1}[m][i] = dA[m][i] * d(hidden[l-1][m][i]),   d(y) = y > 0 ? 1 : y + 1
+ *   for every l:      dW_l[j][i] = sum_m g_l[m][j] a_l[m][i],  db_l[j] = sum_m g_l[m][j];      dA_0 is not formed.
+ * d IS ELU'S DERIVATIVE FROM ITS OUTPUT: the forward stores y = expm1f(z), and exp(z) = y + 1 up to one rounding (torch takes exp of the
+ * saved input).
+ * THE SUM OVER j (the sweep) is a chain of fused multiply-adds from +0, one rounding per term: the last layer's A or one outputs in rising
+ * order, a hidden layer's in blocks of eight, within a block 0, 4, 1, 5, 2, 6, 3, 7, as N17's.  A delta row depends on that row alone.
+ * THE SUMS OVER ROWS: rows are cut into chunks of GMR_POLICY_BWD_CHUNK; inside a chunk the sum is ONE float32 chain of fused multiply-adds
+ * from +0 over the rows in rising order (db: the chain of fma(g, 1, .)); across chunks the partial sums are added in double, in rising
+ * chunk order, and rounded to float32 once.  The association is a function of rows and of the shape alone.  No floating-point atomics.
+ * grads is a HOST array of device addresses in the order of params.  The entries of the network's own tensors are OVERWRITTEN, not
+ * accumulated into (no zero_grad); grads[0] (logstd, whose gradient N15 writes) and the other network's entries are not looked at.
+ * hidden is the forward's list, needed in full; delta is a HOST array of L addresses [rows][width[l + 1]], needed in full: it receives
+ * g_0 .. g_{L-1} and is read back by the weight-gradient launch.  Rows at and beyond `rows` of any array are neither read nor written.
+ * THREE launches per call on the caller's stream -- the sweep (a workgroup per GMR_POLICY_TILE rows, g_l in LDS, v_mfma_f32_32x32x2_f32),
+ * the weight gradients (a wavefront per 64 x 64 block of one dW and one chunk, through the tile table) and the fold --, no wait for the
+ * host.  NO OVERLAP between an output and anything else; the tracker stays SINGLE-STREAM: both calls share one workspace. */
+#ifndef GMR_POLICY_BWD_CHUNK               /* (a diagnostic build of csrc/gmr_tracker_policy_bwd.hip alone may set another: tools/tracker_backward_probe.py) */
+#define GMR_POLICY_BWD_CHUNK 256
+#endif
+/* 131072 rows are 512 chunks; the widest networks (512 inputs, four layers of 256, 32 outputs) have 512*256 + 3*256*256 + 32*256 + 4*256
+ * + 32 = 336 928 weights and biases, so the workspace stays at 512 * 336 928 * 4 = 690 028 544 bytes, below 1 GB */
+#define GMR_POLICY_BWD_MAX_ROWS 131072
+/* Needs set_policy first; allocates the workspace for any rows in 1 .. max_rows and builds the tile tables; a set_policy with other
+ * shapes afterwards makes every backward call GMR_ERR_ARG until set_backward runs again; synchronises the device. */
+int gmr_motion_tracker_set_backward(gmr_motion_tracker_t* t, int64_t max_rows);
+/* the actor: grads[actor's pairs] from grad_loc */
+int gmr_motion_tracker_act_backward_dev(gmr_motion_tracker_t* t, const float* const* d_params, float* const* d_grads, int64_t rows, const float* d_obs,
+                                        const float* const* d_hidden, const float* d_grad_loc, float* const* d_delta, void* stream);   /* asynchronous */
+int gmr_motion_tracker_act_backward(gmr_motion_tracker_t* t, const float* const* params, float* const* grads, int64_t rows, const float* obs,
+                                    const float* const* hidden, const float* grad_loc, float* const* delta);
+/* the critic: grads[critic's pairs] from grad_values */
+int gmr_motion_tracker_values_backward_dev(gmr_motion_tracker_t* t, const float* const* d_params, float* const* d_grads, int64_t rows, const float* d_obs,
+                                           const float* d_priv, const float* const* d_hidden, const float* d_grad_values, float* const* d_delta,
+                                           void* stream);                                                                                /* asynchronous */
+int gmr_motion_tracker_values_backward(gmr_motion_tracker_t* t, const float* const* params, float* const* grads, int64_t rows, const float* obs,
+                                       const float* priv, const float* const* hidden, const float* grad_values, float* const* delta);
+/* state i64[6]: GMR_POLICY_BWD_CHUNK, the chunks of max_rows, the bytes of the workspace block, max_rows, the tiles of the actor's table,
+ * of the critic's. */
+int gmr_motion_tracker_backward_state(gmr_motion_tracker_t* t, int64_t* state);
+
 /* ---- multi-GPU: one rank per GPU, ONE broadcast, no per-step collective ------------ */
 /* The reference parallelises over files with mp.Pool on one CPU (scripts/smplx_to_robot_dataset.py:241-242); here
  * streams shard over the ranks of one node and the only data that crosses ranks is the packed robot model + task set.
