@@ -135,7 +135,8 @@ __global__ __launch_bounds__(256) void motion_fill_kernel(const MotionArrays A, 
 // frames x 128 B = 1.3 MB).  A group of G lanes (G = the power of two >= the column count, at most 64) takes one row at a
 // time, lane = column, so a wavefront reads 64 / G consecutive rows in one instruction; columns beyond 64 take another sweep.
 // Sums are FP64: partial sums per lane, then over the groups of a wavefront by __shfl_xor, then over the four wavefronts in
-// LDS.  stats f32 [C][4][3 + ndof]: mean, std (unbiased; NaN for one frame as torch.std gives), min, max.
+// LDS.  stats f32 [C][4][3 + ndof]: mean, std (unbiased; NaN for one frame as torch.std gives), min, max; all four rows NaN
+// for an empty clip.
 __global__ __launch_bounds__(256) void motion_stats_kernel(const MotionArrays A) {
   __shared__ double s_a[4][64], s_mn[4][64], s_mx[4][64];
   const int c = blockIdx.x;
@@ -147,6 +148,12 @@ __global__ __launch_bounds__(256) void motion_stats_kernel(const MotionArrays A)
   const int g = lane / G, l = lane - g * G;            // group inside the wavefront, column inside the sweep
   const int ngroup = 4 * (64 / G), mygroup = wave * (64 / G) + g;
   float* out = A.stats + (size_t)c * MOTION_STAT_ROWS * ncol;
+  if (T == 0) {
+    // an empty clip has no statistics: NaN in all four rows (the sums below would leave mean 0 / 0, std sqrt(0 / -1) = -0.0,
+    // min +inf, max -inf -- a std that reads as a constant clip).  T is the block's own: the branch is uniform.
+    for (int e = threadIdx.x; e < MOTION_STAT_ROWS * ncol; e += 256) out[e] = NAN;
+    return;
+  }
   for (int col0 = 0; col0 < ncol; col0 += 64) {
     const int col = col0 + l;
     const bool on = col < ncol;

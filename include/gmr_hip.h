@@ -400,7 +400,9 @@ int gmr_bvh_frames(gmr_bvh_t* h, int nclip, int B, const double* rows, const int
  *   stored      float32 root_pos [B][3], root_rot [B][4] xyzw, dof_pos [B][ndof], local_body_pos [B][nbody][3] (optional)
  *   derivatives root_vel, dof_vel: (x[i] - x[i - 1]) / (float)dt inside the clip, [0] = [1]; root_ang_vel [B][3]:
  *               rotvec(r_i r_{i-1}^-1) / dt in float64 from the float32 quaternions, [0] = [1]; all zero for T == 1
- *   stats       float32 [C][4][3 + ndof]: mean, unbiased std (NaN for T == 1), min, max of (root_pos | dof_pos) per column
+ *   stats       float32 [C][4][3 + ndof]: mean, unbiased std (NaN for T == 1), min, max of (root_pos | dof_pos) per column;
+ *               a NaN in a column makes that column's four values NaN; an empty clip (T == 0, which create accepts and a
+ *               query refuses) has no statistics: all four rows are NaN, never a std of zero
  * GMR_MOTION_ANGVEL_REFERENCE reproduces the reference's arithmetic, which reorders the quaternion to wxyz and then hands it
  * to a scalar-LAST constructor (:131-135) -- the log of another rotation; the default is the physical world-frame angular
  * velocity.  A library is immutable once its fill has completed, so sample calls on different streams may be in flight

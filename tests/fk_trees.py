@@ -138,7 +138,15 @@ FAMILIES = ("single", "small2", "small3", "small5", "small7", "chain24", "star",
 # ---------------------------------------------------------------------------------------------------------------------------
 def make_tree(family, seed):
     rng = np.random.default_rng([FAMILIES.index(family), seed])
-    par = np.array(_topology(family, rng), dtype=np.int32)
+    return tree_from_parents(_topology(family, rng), family, seed, rng)
+
+
+def tree_from_parents(parent, family, seed, rng=None, name=None):
+    """the hinges, dof order, local rotations, axes and translations of ``make_tree`` on a given parent list.  ``rng``: the
+    generator that drew the topology (``make_tree`` goes on with it); without one the tree draws from its own"""
+    if rng is None:
+        rng = np.random.default_rng([FAMILIES.index(family), seed, len(parent)])
+    par = np.array(parent, dtype=np.int32)
     nb = len(par)
     assert 1 <= nb <= MAX_BODIES and depth_of(par).max() + 1 <= MAX_DEPTH and all(par[b] < b for b in range(nb))
     # hinges: all bodies, most bodies, or half of them; dofs in body order or permuted
@@ -162,7 +170,7 @@ def make_tree(family, seed):
     # translations with exact zeros
     t = rng.normal(0.0, 0.1, size=(nb, 3))
     t[rng.random((nb, 3)) < 0.3] = 0.0
-    return {"name": f"{family}-{seed}", "family": family, "parent": par, "local_translation": t.astype(F), "local_rotation": q.astype(F),
+    return {"name": name or f"{family}-{seed}", "family": family, "parent": par, "local_translation": t.astype(F), "local_rotation": q.astype(F),
             "dof_idx": dof_idx, "dof_dim": hinge.astype(np.int32), "axis": axis}
 
 
@@ -183,6 +191,26 @@ GPU_LIST = (("single", 0), ("small2", 0), ("small3", 0), ("small5", 1), ("small7
 
 def gpu_trees():
     return [make_tree(f, s) for f, s in GPU_LIST]
+
+
+def small_family_trees():
+    """a comb with a trunk of 8 (17 bodies) and a binary tree of 15 bodies: the two families whose listed trees all park more
+    parents than the per-body state kernel (csrc/gmr_body_state.hip) has LDS for, at a size it takes"""
+    return [tree_from_parents(_comb(8), "comb", 0, name="comb8-0"), tree_from_parents(_binary(15), "binary", 0, name="binary15-0")]
+
+
+def body_state_lds(tree):
+    """(ndof, parked parents, bytes of LDS per workgroup) of ``gmr_motion_body_state`` on a tree, as csrc/gmr_body_state.hip lays
+    it out: 64 rows of dof_pos | dof_vel (odd stride), 13 floats x 64 per parked parent (a parent with a child that does not
+    follow it immediately, at least one slot, as gmr_fk_create counts them), staging rows of 3, 4, 3, 3 floats x 4 bodies + 1 and
+    four query scalars"""
+    par = tree["parent"]
+    ndof = int((tree["dof_dim"] > 0).sum())
+    nslot = max(1, len({int(par[b]) for b in range(1, len(par)) if par[b] != b - 1}))
+    return ndof, nslot, 4 * (64 * ((2 * ndof) | 1) + nslot * 13 * 64 + 64 * (3 * 13 + 17) + 4 * 64)
+
+
+BODY_STATE_LDS_LIMIT = 64 * 1024
 
 
 def checker_line(tree):

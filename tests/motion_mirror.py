@@ -50,8 +50,11 @@ def derivatives(root_pos, root_rot, dof_pos, fps, ang_vel="world"):
 
 
 def stats(root_pos, dof_pos):
-    """[4][3 + ndof] float32: mean, unbiased std, min, max, accumulated in float64."""
+    """[4][3 + ndof] float32: mean, unbiased std, min, max, accumulated in float64.  An empty clip has no statistics: NaN in all
+    four rows."""
     x = np.concatenate([root_pos, dof_pos], axis=1).astype(np.float64)
+    if len(x) == 0:
+        return np.full((4, x.shape[1]), np.nan, dtype=F)
     with np.errstate(invalid="ignore", divide="ignore"):
         std = x.std(axis=0, ddof=1) if len(x) > 1 else np.full(x.shape[1], np.nan)
     return np.stack([x.mean(axis=0), std, x.min(axis=0), x.max(axis=0)]).astype(F)
@@ -84,6 +87,7 @@ class Library:
         c = np.where(ok, clip, 0)
         T = self.seg[c + 1] - self.seg[c]
         ok &= T >= 1
+        c, T = np.where(ok, c, 0), np.where(ok, T, 1)       # (a refused query, an empty clip among them, reads row 0 and is masked)
         fps = self.fps[c]
         dt, dur = 1.0 / fps, T / fps
         tm = np.where(ok, time, 0.0)

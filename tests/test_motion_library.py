@@ -12,6 +12,7 @@ from conftest import get_setup
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import motion_mirror as mm  # noqa: E402
+from test_motion_edges_host import ANGVEL_C  # noqa: E402
 from test_motion_library_host import FIELDS, check_against_golden, close, constant_rate_clip, golden, golden_motions  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -78,8 +79,19 @@ def assert_library_equals_mirror(lib, mirror):
         assert got.shape == want.shape and np.array_equal(_bits(got), _bits(want)), k
     if mirror.local_body_pos is not None:
         assert np.array_equal(_bits(lib.array("local_body_pos")), _bits(mirror.local_body_pos))
-    close(lib.array("root_ang_vel"), mirror.root_ang_vel, rel=1e-6, abs_=1e-5)
-    close(lib.array("stats"), mirror.stats, rel=1e-6, abs_=1e-7)
+    # root_ang_vel and the stats' mean and std are FP64 evaluations rounded once, here and in the mirror: one float32 spacing apart at
+    # the most (tests/test_motion_edges.py holds both to mpmath), or, for a component of root_ang_vel near zero, the FP64 floor of
+    # both evaluations (ANGVEL_C 2^-52 / dt each, dt >= 1 / 120 here).  min and max are data: bit for bit.
+    def spacing_apart(a, b, floor=0.0):
+        a, b = a.astype(np.float64), b.astype(np.float64)
+        assert np.array_equal(np.isnan(a), np.isnan(b))
+        tol = np.maximum(np.spacing(np.maximum(np.abs(a), np.abs(b)).astype(F)).astype(np.float64), floor)
+        return bool((np.abs(a - b)[~np.isnan(a)] <= tol[~np.isnan(a)]).all())
+
+    assert spacing_apart(lib.array("root_ang_vel"), mirror.root_ang_vel, 2 * ANGVEL_C * 2.0 ** -52 * 120.0)
+    stats = lib.array("stats")
+    assert spacing_apart(stats[:, :2], mirror.stats[:, :2])
+    assert np.array_equal(_bits(stats[:, 2:]), _bits(mirror.stats[:, 2:]))
 
 
 # ---- 1. fill -----------------------------------------------------------------------------------------------------------------
