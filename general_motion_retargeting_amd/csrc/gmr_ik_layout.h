@@ -80,17 +80,21 @@ constexpr IkOffsets ik_offsets(int nvp, int nw) {
   // (4 x 10 x 10 + 4 x 10) in the same dead region, behind the 4 x 16 x 19 doubles.
   {
     const int rows_scr = 4 * 16 * 19;
-    const int need = nw == 4 ? ik_max(nvp * (nvp + 1), 4 * 18 * 19) : ik_max(nvp * (nvp + 1), rows_scr + 440);
+    // (the Schur parts start on a 16-byte boundary: one padding double where L.e + rows_scr is odd, counted in `need`)
+    const int pad = (L.e + rows_scr) & 1;
+    const int need = nw == 4 ? ik_max(nvp * (nvp + 1), 4 * 18 * 19) : ik_max(nvp * (nvp + 1), rows_scr + pad + 440);
     const int have = o - L.e;
     if (have < need) o += need - have;
     L.Kt = L.e;
-    if (nw != 4) { L.tr_spart = L.Kt + rows_scr; L.tr_rpart = L.tr_spart + 400; }
+    if (nw != 4) { L.tr_spart = L.Kt + rows_scr + pad; L.tr_rpart = L.tr_spart + 400; }
   }
   if (o & 1) o++;
   L.H = o; o += nvp * L.ldh + 2;
   L.c = o; o += nvp; L.x = o; o += nvp; L.lo = o; o += nvp; L.hi = o; o += nvp; L.scal = o; o += 2;
   // (tr_gpart: the four limbs' shares of the multipliers of fixed trunk variables, gmr_ik_tree.h step 6)
-  if (nw == 4) { L.tr_spart = o; o += 4 * 10 * 10; L.tr_rpart = o; o += 4 * 10; L.tr_gpart = o; o += 4 * 10; }
+  // They start on a 16-byte boundary (one padding double where the count so far is odd): a trunk lane reads its row of each
+  // Schur part (80 B, the parts 800 B apart) as 16-byte pieces.  400 and 40 are even: rpart and gpart are aligned with it.
+  if (nw == 4) { if (o & 1) o++; L.tr_spart = o; o += 4 * 10 * 10; L.tr_rpart = o; o += 4 * 10; L.tr_gpart = o; o += 4 * 10; }
   if (o & 1) o++;                                  // every region starts 16-byte aligned
   L.n_double = o;
   int i = 0;

@@ -31,6 +31,24 @@ namespace gmr {
 constexpr int TR_MAX_NL = 8;                     // capacity: limb rows per wavefront (LDS tables)
 constexpr int TR_MAX_NT = 10;                    // capacity: trunk rows
 
+// The exchange buffers of a round (Spart, rpart, gpart) start on 16-byte boundaries (gmr_ik_layout.h) and a row of Spart
+// is 80 B: two neighbouring columns are one 16-byte piece.  GMR_NO_ALIGNED_SCHUR restores the 8-byte accesses (A/B builds).
+struct __attribute__((aligned(16))) TrPair { double x, y; };
+#ifdef GMR_NO_ALIGNED_SCHUR
+constexpr bool TR_PAIRS = false;
+#else
+constexpr bool TR_PAIRS = true;
+#endif
+// The masks of a round as lane masks: an entry of the local matrix is kept where the lane's row is free (one lane mask per
+// round) and the column is free (a wave-uniform bit of the round's ballot), and the 1.0 on the diagonal of a fixed or padding
+// row is not written into the row: the pivot's diagonal broadcast takes it from the column's bit (solve_qp_tree, TR_DIAG).
+// GMR_NO_LANE_MASKS restores the per-entry identity (A/B builds).
+#ifdef GMR_NO_LANE_MASKS
+constexpr bool TR_LMASK = false;
+#else
+constexpr bool TR_LMASK = true;
+#endif
+
 // Bound sets of the QP, identical in every wavefront (wave-uniform registers, carried from solve to
 // solve for the warm start): bit d of `lower` / `upper` = dof d sits on its lower / upper bound.
 struct TreeState { unsigned long long lower, upper; };
@@ -120,12 +138,15 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
 #else
   constexpr bool FILLED = FOLD && TR_NL == 7 && TR_NT == 9;
 #endif
+  // the diagonal a pivot sees: column k of a fixed or padding row k is the identity (colmask: wave-uniform, ROWS: per row)
+#define TR_DIAG(d, k) ((TR_LMASK && ((colmask >> (k)) & 1u)) ? 1.0 : (d))
 #define TR_SYNC() do { if (ROWS) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); else __syncthreads(); } while (0)
   const int n = L.nv, ldh = L.o.ldh;
   const double* H = sm + L.o.H;
   double* xs = sm + L.o.x;
   const double* los = sm + L.o.lo;
   const double* his = sm + L.o.hi;
+  static_assert(!TR_PAIRS || (LT::o.tr_spart % 2 == 0 && TR_MAX_NT % 2 == 0), "rows of the Schur parts start on 16-byte boundaries");
   double* Spart = sm + L.o.tr_spart;                           // [4][TR_NT][TR_NT]
   double* rpart = sm + L.o.tr_rpart;                           // [4][TR_NT]
   double* gpart = sm + L.o.tr_gpart;                           // [4][TR_NT] (4-wavefront form only)
@@ -174,7 +195,9 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
       // every free row keeps all its free limb columns: D_l as full symmetric rows (limb rows), B_l (trunk rows)
       const bool keep = row && !self_fixed && !cfixed;
       double v = keep ? h[m] : 0.0;
-      if (is_limb && m == a && (self_fixed || cfixed)) v = 1.0;   // fixed / padding limb row: identity
+      // fixed / padding limb row: identity.  TR_LMASK: its diagonal stays zero here; it is read only by the pivot's diagonal
+      // broadcast (TR_DIAG) -- l is zero for rows <= pivot, ltl takes the columns beyond the diagonal only
+      if (!TR_LMASK && is_limb && m == a && (self_fixed || cfixed)) v = 1.0;
       r[m] = v;
     }
     // limb row a also keeps its trunk columns, B_l^T: column a of Y_l grows there.  (A trunk row's trunk columns start
@@ -222,7 +245,7 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
     // that the Newton steps overlap the remaining (independent) column updates of this pivot.
     double mydinv = 1.0;
     bool bad = false;
-    double dp = TR_BCAST(r[0], 0);
+    double dp = TR_DIAG(TR_BCAST(r[0], 0), 0);
     double dinv = fast_rsqrt(dp);
     tr_static_for<0, TR_NL>([&](auto P) __attribute__((always_inline)) {
       constexpr int p = decltype(P)::value;
@@ -241,6 +264,7 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
           r[p + 1] = fma(-l, TR_BCAST(l, p + 1), r[p + 1]);
           dp = TR_BCAST(r[p + 1], p + 1);
         }
+        dp = TR_DIAG(dp, p + 1);
         dinv_next = fast_rsqrt(dp);
       }
       const double yp = TR_BCAST(b, p) * dinv;               // row p keeps its unscaled b (l = 0 there): scaled after the loop
@@ -277,8 +301,12 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
     {
     TR_ROW()
     if (is_trunk) {
+      double* srow = Spart + (wave * TR_MAX_NT + t) * TR_MAX_NT;
 #pragma unroll
-      for (int u = 0; u < TR_NT; u++) Spart[(wave * TR_MAX_NT + t) * TR_MAX_NT + u] = r[TR_NL + u];
+      for (int u = 0; u < TR_NT; u++) {
+        if (TR_PAIRS && u + 1 < TR_NT && !(u & 1)) *reinterpret_cast<TrPair*>(srow + u) = TrPair{r[TR_NL + u], r[TR_NL + u + 1]};
+        else if (!(TR_PAIRS && (u & 1))) srow[u] = r[TR_NL + u];
+      }
       rpart[wave * TR_MAX_NT + t] = b;
     }
     if (lane == 0 && bad) atomicOr(&vcur[3], 1ull);
@@ -301,10 +329,24 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
         const int tt = is_trunk ? t : 0;
         double hv[TR_NT], sp[TR_NT];
 #pragma unroll
-        for (int u = 0; u < TR_NT; u++) {
-          hv[u] = h[TR_NL + u];
-          const double* q0 = Spart + tt * TR_MAX_NT + u;
-          sp[u] = (q0[0] + q0[TR_MAX_NT * TR_MAX_NT]) + (q0[2 * TR_MAX_NT * TR_MAX_NT] + q0[3 * TR_MAX_NT * TR_MAX_NT]);
+        for (int u = 0; u < TR_NT; u++) hv[u] = h[TR_NL + u];
+        if constexpr (TR_PAIRS) {
+          // the row of each part as 16-byte pieces from one address (TR_NT odd: the last piece's second half is the
+          // row's unused column TR_NT < TR_MAX_NT, read and dropped)
+          constexpr int PART = TR_MAX_NT * TR_MAX_NT / 2;
+          const TrPair* q0 = reinterpret_cast<const TrPair*>(Spart + tt * TR_MAX_NT);
+#pragma unroll
+          for (int j = 0; j < (TR_NT + 1) / 2; j++) {
+            const TrPair p0 = q0[j], p1 = q0[PART + j], p2 = q0[2 * PART + j], p3 = q0[3 * PART + j];
+            sp[2 * j] = (p0.x + p1.x) + (p2.x + p3.x);
+            if (2 * j + 1 < TR_NT) sp[2 * j + 1] = (p0.y + p1.y) + (p2.y + p3.y);
+          }
+        } else {
+#pragma unroll
+          for (int u = 0; u < TR_NT; u++) {
+            const double* q0 = Spart + tt * TR_MAX_NT + u;
+            sp[u] = (q0[0] + q0[TR_MAX_NT * TR_MAX_NT]) + (q0[2 * TR_MAX_NT * TR_MAX_NT] + q0[3 * TR_MAX_NT * TR_MAX_NT]);
+          }
         }
         const double rp = (rpart[tt] + rpart[TR_MAX_NT + tt]) + (rpart[2 * TR_MAX_NT + tt] + rpart[3 * TR_MAX_NT + tt]);
         const bool live = is_trunk && row && !self_fixed;
@@ -312,13 +354,13 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
         for (int u = 0; u < TR_NT; u++) {
           const bool cfixed = (colmask >> (TR_NL + u)) & 1u;               // wave-uniform
           double v = (live && !cfixed) ? hv[u] + sp[u] : 0.0;       // full symmetric rows, as in (1)
-          if (is_trunk && u == t && !(live && !cfixed)) v = 1.0;
+          if (!TR_LMASK && is_trunk && u == t && !(live && !cfixed)) v = 1.0;   // (TR_LMASK: TR_DIAG, as in (1))
           s[u] = v;
         }
         bt = is_trunk ? (live ? rhs0 + rp : rhs0) : 0.0;
       }
       double tdinv = 1.0;
-      double dq = TR_BCAST(s[0], TR_NL);
+      double dq = TR_DIAG(TR_BCAST(s[0], TR_NL), TR_NL);
       double dinv = fast_rsqrt(dq);
       tr_static_for<0, TR_NT>([&](auto Q) __attribute__((always_inline)) {
         constexpr int q = decltype(Q)::value;
@@ -337,6 +379,7 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
             s[q + 1] = fma(-l, TR_BCAST(l, TR_NL + q + 1), s[q + 1]);
             dq = TR_BCAST(s[q + 1], TR_NL + q + 1);
           }
+          dq = TR_DIAG(dq, TR_NL + q + 1);
           dinv_next = fast_rsqrt(dq);
         }
         const double yq = TR_BCAST(bt, TR_NL + q) * dinv;
@@ -532,6 +575,7 @@ __device__ __forceinline__ int solve_qp_tree(const LT& L, double* sm, uint32_t* 
   return GMR_STATUS_QP_MAXITER;
 #undef TR_BCAST
 #undef TR_SYNC
+#undef TR_DIAG
 #undef TR_ROW
 }
 
