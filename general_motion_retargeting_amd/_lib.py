@@ -55,6 +55,11 @@ _SIGS = {
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gmr_retarget_streams": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gmr_retarget_streams_scaled_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p]),
+    "gmr_retarget_streams_scaled": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gmr_retarget_group_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "gmr_retarget_group": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "gmr_retarget_group_window_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
@@ -415,7 +420,21 @@ class Job(C.Structure):
     """``gmr_job_t``: one (solver, batch) of a group launch."""
     _fields_ = [("solver", C.c_void_p), ("S", C.c_int32), ("T", C.c_int32), ("q0", C.c_void_p), ("human", C.c_void_p),
                 ("len", C.c_void_p), ("q_out", C.c_void_p), ("nsolve", C.c_void_p), ("status", C.c_void_p),
-                ("tgt_out", C.c_void_p), ("err_out", C.c_void_p)]
+                ("tgt_out", C.c_void_p), ("err_out", C.c_void_p), ("scale", C.c_void_p)]
+
+
+def check_scales(scales, S: int, nhuman: int, what: str = "scales"):
+    """``scales`` as the contiguous ``f64[S, nhuman]`` table of per-stream human scale rows (None stays None); checked the way
+    ``lens`` is, before any device call."""
+    if scales is None:
+        return None
+    a = np.asarray(scales)
+    if not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.integer)):
+        raise TypeError(f"{what}: numbers needed, got {a.dtype}")
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.shape != (S, nhuman):
+        raise ValueError(f"{what} must be [{S},{nhuman}], got {a.shape}")
+    return a
 
 
 class PostSrc(C.Structure):
@@ -448,7 +467,8 @@ def group_outputs(jobs, pinned: bool = True):
 def retarget_group(jobs, flags: int = 0, slices: int = 0, out_pinned: bool = False, outs=None):
     """Several (solver, batch) jobs as ONE scheduling domain through host buffers (``gmr_retarget_group``): the mixed-robot
     batch of BASELINE.json configs[3].  ``jobs`` = list of dicts ``{"solver": Solver, "human": f64[S,T,nhuman,7], optional
-    "q0": f64[S,nq] (default the solver's qpos0), "lens": i32[S]}``.  Returns one ``(q_out, nsolve, status)`` per job.
+    "q0": f64[S,nq] (default the solver's qpos0), "lens": i32[S], "scales": f64[S,nhuman] (a human scale table per stream in
+    place of the solver's: :meth:`Solver.retarget_streams`)}``.  Returns one ``(q_out, nsolve, status)`` per job.
     Inputs in pinned memory (:func:`pinned_empty`) and pinned outputs (``outs=`` from :func:`group_outputs`, reused across
     calls; or ``out_pinned=True``: allocated per call, which is slow) make the copies asynchronous, so that they overlap the
     kernels slice by slice."""
@@ -474,6 +494,7 @@ def retarget_group(jobs, flags: int = 0, slices: int = 0, out_pinned: bool = Fal
             lens = np.ascontiguousarray(lens, dtype=np.int32)
             if lens.shape != (S,):
                 raise ValueError(f"job {i}: lens must be [S]")
+        scales = check_scales(j.get("scales"), S, sol.nhuman, f"job {i}: scales")
         if given is not None:
             q_out, nsolve, status = given[i]
             if q_out.shape != (S, T, sol.nq) or nsolve.shape != (S, T, 2) or status.shape != (S,) or q_out.dtype != np.float64 \
@@ -483,22 +504,26 @@ def retarget_group(jobs, flags: int = 0, slices: int = 0, out_pinned: bool = Fal
             q_out = empty((S, T, sol.nq), np.float64)
             nsolve = empty((S, T, 2), np.int32)
             status = np.zeros(S, dtype=np.int32)
-        keep.append((human, q0, lens))
+        keep.append((human, q0, lens, scales))
         outs.append((q_out, nsolve, status))
         arr[i] = Job(sol.handle.value, S, T, _addr(q0), _addr(human), _addr(lens), _addr(q_out), _addr(nsolve), _addr(status),
-                     None, None)
+                     None, None, _addr(scales))
     check(lib().gmr_retarget_group(C.cast(arr, C.c_void_p), len(jobs), int(flags), int(slices)))
     return outs
 
 
 def retarget_group_dev(jobs, flags: int = 0, stream=None, window=None):
     """``gmr_retarget_group_dev``: ``jobs`` = list of ``(solver, S, T, d_q0, d_human, d_len, d_q_out, d_nsolve, d_status)``
-    with device pointers (DeviceBuffer or raw); asynchronous on ``stream``.  ``window=(t_begin, t_end)``: only those frames of
+    with device pointers (DeviceBuffer or raw), optionally followed by a tenth element ``d_scale`` (f64 [S][nhuman] per-stream human
+    scale tables, unchecked: the values are the caller's responsibility); asynchronous on ``stream``.  ``window=(t_begin, t_end)``: only those frames of
     every stream (``gmr_retarget_group_window_dev``; consecutive windows on one stream, starting at 0)."""
     arr = (Job * max(len(jobs), 1))()
-    for i, (sol, S, T, d_q0, d_h, d_len, d_qo, d_ns, d_st) in enumerate(jobs):
+    for i, job in enumerate(jobs):
+        if len(job) not in (9, 10):
+            raise ValueError(f"job {i}: 9 or 10 elements needed, got {len(job)}")
+        sol, S, T, d_q0, d_h, d_len, d_qo, d_ns, d_st = job[:9]
         arr[i] = Job(sol.handle.value, int(S), int(T), _addr(d_q0), _addr(d_h), _addr(d_len), _addr(d_qo), _addr(d_ns),
-                     _addr(d_st), None, None)
+                     _addr(d_st), None, None, _addr(job[9]) if len(job) == 10 else None)
     if window is None:
         check(lib().gmr_retarget_group_dev(C.cast(arr, C.c_void_p), len(jobs), int(flags), _s(stream)))
     else:
@@ -575,10 +600,11 @@ class Solver:
         return int(lib().gmr_retarget_lds_bytes(self.handle))
 
     def retarget_streams(self, q0, human, lens=None, flags: int = 0, want_targets: bool = False,
-                         want_errors: bool = False):
+                         want_errors: bool = False, scales=None):
         """Host arrays in/out: q0[S,nq], human[S,T,nhuman,7] -> q_out[S,T,nq], nsolve[S,T,2], status[S]
         (+ targets[S,T,nhuman,7] = the kernel's preprocessed frames and/or errors[S,T,2] = error1/error2 at the
-        configuration every frame ends with, when asked for)."""
+        configuration every frame ends with, when asked for).  ``scales`` f64[S,nhuman]: a human scale table per stream
+        (``ik_config.scale_rows``) in place of the solver's own, so that subjects of different heights share one launch."""
         human = np.ascontiguousarray(human, dtype=np.float64)
         if human.ndim != 4 or human.shape[2] != self.nhuman or human.shape[3] != 7:
             raise ValueError(f"human must be [S,T,{self.nhuman},7], got {human.shape}")
@@ -590,23 +616,30 @@ class Solver:
             lens = np.ascontiguousarray(lens, dtype=np.int32)
             if lens.shape != (S,):
                 raise ValueError("lens must be [S]")
+        scales = check_scales(scales, S, self.nhuman)
         q_out = np.zeros((S, T, self.nq), dtype=np.float64)
         nsolve = np.zeros((S, T, 2), dtype=np.int32)
         status = np.zeros(S, dtype=np.int32)
         targets = np.zeros((S, T, self.nhuman, 7), dtype=np.float64) if want_targets else None
         errors = np.zeros((S, T, 2), dtype=np.float64) if want_errors else None
-        check(lib().gmr_retarget_streams(self.handle, S, T, _ptr(q0), _ptr(human), _ptr(lens), int(flags),
-                                         _ptr(q_out), _ptr(nsolve), _ptr(status), _ptr(targets), _ptr(errors)))
+        check(lib().gmr_retarget_streams_scaled(self.handle, S, T, _ptr(q0), _ptr(human), _ptr(lens), _ptr(scales), int(flags),
+                                                _ptr(q_out), _ptr(nsolve), _ptr(status), _ptr(targets), _ptr(errors)))
         if want_targets or want_errors:
             return q_out, nsolve, status, targets, errors
         return q_out, nsolve, status
 
     def retarget_streams_dev(self, S, T, d_q0, d_human, d_len, flags, d_q_out, d_nsolve, d_status, stream=None,
-                             d_tgt_out=None, d_err_out=None):
-        """Device pointers (DeviceBuffer or raw c_void_p); asynchronous on `stream`."""
-        check(lib().gmr_retarget_streams_dev(self.handle, int(S), int(T), _d(d_q0), _d(d_human), _d(d_len), int(flags),
-                                             _d(d_q_out), _d(d_nsolve), _d(d_status), _d(d_tgt_out), _d(d_err_out),
-                                             _s(stream)))
+                             d_tgt_out=None, d_err_out=None, d_scale=None):
+        """Device pointers (DeviceBuffer or raw c_void_p); asynchronous on `stream`.  ``d_scale``: f64 [S][nhuman] per-stream
+        human scale tables (unchecked: the values are the caller's responsibility)."""
+        if d_scale is None:
+            check(lib().gmr_retarget_streams_dev(self.handle, int(S), int(T), _d(d_q0), _d(d_human), _d(d_len), int(flags),
+                                                 _d(d_q_out), _d(d_nsolve), _d(d_status), _d(d_tgt_out), _d(d_err_out),
+                                                 _s(stream)))
+            return
+        check(lib().gmr_retarget_streams_scaled_dev(self.handle, int(S), int(T), _d(d_q0), _d(d_human), _d(d_len), _d(d_scale),
+                                                    int(flags), _d(d_q_out), _d(d_nsolve), _d(d_status), _d(d_tgt_out),
+                                                    _d(d_err_out), _s(stream)))
 
     def close(self):
         if self.handle:

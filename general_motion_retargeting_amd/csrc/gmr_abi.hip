@@ -26,17 +26,18 @@ static_assert(offsetof(gmr_model_t, timestep) % 8 == 0, "double block of gmr_mod
 static_assert(offsetof(gmr_taskset_t, damping) % 8 == 0, "double block of gmr_taskset_t misaligned");
 
 extern "C" hipError_t gmr_launch_ik_streams(const uint4*, const gmr::IkLayout*, const gmr::IkParams*, int, int,
-                                            const double*, const double*, const int32_t*, int, double*, int32_t*,
-                                            int32_t*, double*, double*, hipStream_t, unsigned long long*);
+                                            const double*, const double*, const int32_t*, const double*, int, double*,
+                                            int32_t*, int32_t*, double*, double*, hipStream_t, unsigned long long*);
 extern "C" hipError_t gmr_ik_set_max_smem(int nvp, int nw, int tree_small, int bytes);
 extern "C" hipError_t gmr_launch_ik_wide(const char*, const gmr::WideLayout*, const gmr::IkParams*, int, int, const double*,
-                                         const double*, const int32_t*, int, double*, int32_t*, int32_t*, double*, double*,
-                                         hipStream_t, unsigned long long*, void*);
+                                         const double*, const int32_t*, const double*, int, double*, int32_t*, int32_t*, double*,
+                                         double*, hipStream_t, unsigned long long*, void*);
 struct gmr_wide_job_desc {       // (gmr_ik_wide.hip)
   const char* d_image; const gmr::WideLayout* L; const gmr::IkParams* P;
   int S, T;
   const double* d_q0; const double* d_human; const int32_t* d_len;
   double* d_q_out; int32_t* d_nsolve; int32_t* d_status; double* d_tgt_out; double* d_err_out;
+  const double* d_scale;
 };
 extern "C" hipError_t gmr_launch_ik_wide_group(const gmr_wide_job_desc*, int, int, hipStream_t, unsigned long long*, void*);
 extern "C" hipError_t gmr_launch_ik_wide_window(const gmr_wide_job_desc*, int, int, hipStream_t, unsigned long long*, void*, int, int);
@@ -312,6 +313,13 @@ int gmr_retarget_lds_bytes(const gmr_solver_t* s) { return !s ? 0 : s->layout4.t
 int gmr_retarget_streams_dev(gmr_solver_t* s, int S, int T, const double* d_q0, const double* d_human,
                              const int32_t* d_len, int flags, double* d_q_out, int32_t* d_nsolve,
                              int32_t* d_status, double* d_tgt_out, double* d_err_out, void* stream) {
+  return gmr_retarget_streams_scaled_dev(s, S, T, d_q0, d_human, d_len, nullptr, flags, d_q_out, d_nsolve, d_status, d_tgt_out,
+                                         d_err_out, stream);
+}
+
+int gmr_retarget_streams_scaled_dev(gmr_solver_t* s, int S, int T, const double* d_q0, const double* d_human,
+                                    const int32_t* d_len, const double* d_scale, int flags, double* d_q_out, int32_t* d_nsolve,
+                                    int32_t* d_status, double* d_tgt_out, double* d_err_out, void* stream) {
   if (!s) return fail(GMR_ERR_ARG, "null solver");
   if (S < 0 || T < 0) return fail(GMR_ERR_ARG, "negative S/T");
   if (S == 0 || T == 0) return GMR_OK;
@@ -320,11 +328,11 @@ int gmr_retarget_streams_dev(gmr_solver_t* s, int S, int T, const double* d_q0, 
   // latency); many streams: 1 wave per stream (more streams resident, more frames per second)
   const bool wide = s->layout4.tree_ok && (s->force_waves ? s->force_waves == 4 : S <= GMR_HELPER_MAX_STREAMS);
   if (!wide && s->wide.ok)     // throughput shape: two resident wavefronts per SIMD (gmr_ik_wide.hip)
-    GMR_HIP_TRY(gmr_launch_ik_wide(s->wide_image.data(), &s->wide, &s->params, S, T, d_q0, d_human, d_len, flags, d_q_out, d_nsolve,
-                               d_status, d_tgt_out, d_err_out, (hipStream_t)stream, nullptr, s->wide_pool));
+    GMR_HIP_TRY(gmr_launch_ik_wide(s->wide_image.data(), &s->wide, &s->params, S, T, d_q0, d_human, d_len, d_scale, flags, d_q_out,
+                               d_nsolve, d_status, d_tgt_out, d_err_out, (hipStream_t)stream, nullptr, s->wide_pool));
   else
     GMR_HIP_TRY(gmr_launch_ik_streams((const uint4*)(wide ? s->image4 : s->image).data(), wide ? &s->layout4 : &s->layout, &s->params, S, T,
-                                  d_q0, d_human, d_len, flags, d_q_out, d_nsolve, d_status, d_tgt_out, d_err_out,
+                                  d_q0, d_human, d_len, d_scale, flags, d_q_out, d_nsolve, d_status, d_tgt_out, d_err_out,
                                   (hipStream_t)stream, nullptr));
   return GMR_OK;
 }
@@ -367,11 +375,11 @@ int gmr_retarget_group_dev(const gmr_job_t* jobs, int njobs, int flags, void* st
     if (njobs > 1 && job_takes_wide_shape(s, total)) {
       if (nw == 0) pool = s->wide_pool;
       wd[nw++] = gmr_wide_job_desc{s->wide_image.data(), &s->wide, &s->params, J.S, J.T, J.q0, J.human, J.len, J.q_out, J.nsolve, J.status,
-                                   J.tgt_out, J.err_out};
+                                   J.tgt_out, J.err_out, J.scale};
       if (nw == 8) { int rc = flush(); if (rc) return rc; }
     } else {
-      int rc = gmr_retarget_streams_dev(s, J.S, J.T, J.q0, J.human, J.len, flags, J.q_out, J.nsolve, J.status, J.tgt_out,
-                                        J.err_out, stream);
+      int rc = gmr_retarget_streams_scaled_dev(s, J.S, J.T, J.q0, J.human, J.len, J.scale, flags, J.q_out, J.nsolve, J.status,
+                                               J.tgt_out, J.err_out, stream);
       if (rc) return rc;
     }
   }
@@ -411,11 +419,25 @@ int gmr_retarget_group_window_dev(const gmr_job_t* jobs, int njobs, int flags, i
     gmr_solver* s = J.solver;
     if (nw == 0) pool = s->wide_pool;
     wd[nw++] = gmr_wide_job_desc{s->wide_image.data(), &s->wide, &s->params, J.S, J.T, J.q0, J.human, J.len, J.q_out, J.nsolve, J.status,
-                                 J.tgt_out, J.err_out};
+                                 J.tgt_out, J.err_out, J.scale};
   }
   if (nw == 0) return GMR_OK;
   hipError_t e = gmr_launch_ik_wide_window(wd, nw, flags, (hipStream_t)stream, nullptr, pool, t_begin, t_end);
   if (e != hipSuccess) return fail(GMR_ERR_HIP, "window launch: %s", hipGetErrorString(e));
+  return GMR_OK;
+}
+
+// a host-side scale table: every entry finite and positive (the device entry points cannot look)
+static int check_scale(const double* scale, int S, int nhuman, int job) {
+  if (!scale) return GMR_OK;
+  for (int s = 0; s < S; s++)
+    for (int b = 0; b < nhuman; b++) {
+      const double v = scale[(size_t)s * nhuman + b];
+      if (!(v > 0.0) || !std::isfinite(v)) {
+        if (job < 0) return fail(GMR_ERR_ARG, "scale of stream %d, body %d is %g: must be finite and positive", s, b, v);
+        return fail(GMR_ERR_ARG, "job %d: scale of stream %d, body %d is %g: must be finite and positive", job, s, b, v);
+      }
+    }
   return GMR_OK;
 }
 
@@ -427,13 +449,14 @@ int gmr_retarget_group_window_dev(const gmr_job_t* jobs, int njobs, int flags, i
 // one launch -- the per-stream state travels from window to window in device memory.
 // The arrays of S streams of job J in a workspace of the host-buffer entry points, in the order the zero-fill relies on:
 // [qo, end) is what the kernel writes (q_out, nsolve, status, then tgt_out and err_out when the caller wants them).
-struct JobOff { size_t q0, h, len, qo, ns, st, tg, er, end; };
+struct JobOff { size_t q0, h, len, sc, qo, ns, st, tg, er, end; };
 static JobOff carve_job(gmr::Carve& c, const gmr_job_t& J, size_t S) {
   const size_t nq = J.solver->model.nq, nh = J.solver->ts.nhuman, T = (size_t)J.T;
   JobOff o;
   o.q0 = c.take(S * nq * 8);
   o.h = c.take(S * T * nh * 56);
   o.len = c.take(S * 4);
+  o.sc = c.take(J.scale ? S * nh * 8 : 0);
   o.qo = c.take(S * T * nq * 8);
   o.ns = c.take(S * T * 8);
   o.st = c.take(S * 4);
@@ -446,6 +469,7 @@ static JobOff carve_job(gmr::Carve& c, const gmr_job_t& J, size_t S) {
 static gmr_job_t job_at(const gmr_job_t& J, char* d, const JobOff& o) {
   gmr_job_t D = J;
   D.q0 = (const double*)(d + o.q0); D.human = (const double*)(d + o.h); D.len = J.len ? (const int32_t*)(d + o.len) : nullptr;
+  D.scale = J.scale ? (const double*)(d + o.sc) : nullptr;
   D.q_out = (double*)(d + o.qo); D.nsolve = (int32_t*)(d + o.ns); D.status = (int32_t*)(d + o.st);
   D.tgt_out = J.tgt_out ? (double*)(d + o.tg) : nullptr; D.err_out = J.err_out ? (double*)(d + o.er) : nullptr;
   return D;
@@ -488,7 +512,8 @@ static int retarget_group_windows(const gmr_job_t* jobs, int njobs, int flags, g
     const JobOff& o = off[j];
     const size_t nq = J.solver->model.nq, S = (size_t)J.S;
     if ((e = hipMemcpyAsync(d + o.q0, J.q0, S * nq * 8, hipMemcpyHostToDevice, s_in)) != hipSuccess ||
-        (J.len && (e = hipMemcpyAsync(d + o.len, J.len, S * 4, hipMemcpyHostToDevice, s_in)) != hipSuccess))
+        (J.len && (e = hipMemcpyAsync(d + o.len, J.len, S * 4, hipMemcpyHostToDevice, s_in)) != hipSuccess) ||
+        (J.scale && (e = hipMemcpyAsync(d + o.sc, J.scale, S * J.solver->ts.nhuman * 8, hipMemcpyHostToDevice, s_in)) != hipSuccess))
       rc = fail(GMR_ERR_HIP, "H2D copy: %s", hipGetErrorString(e));
     // rows the kernel does not write come back as zeros
     if (rc == GMR_OK && (J.len || J.tgt_out || J.err_out) && (e = hipMemsetAsync(d + o.qo, 0, o.end - o.qo, s_k)) != hipSuccess)
@@ -554,6 +579,7 @@ int gmr_retarget_group(const gmr_job_t* jobs, int njobs, int flags, int slices) 
     if (J.S < 0 || J.T < 0) return fail(GMR_ERR_ARG, "job %d: negative S/T", j);
     if (J.S == 0 || J.T == 0) continue;
     if (!J.q0 || !J.human || !J.q_out || !J.nsolve || !J.status) return fail(GMR_ERR_ARG, "job %d: null host buffer", j);
+    if (int rc = check_scale(J.scale, J.S, J.solver->ts.nhuman, j)) return rc;
     if (!owner) owner = J.solver;
     total += J.S;
     in_bytes += (size_t)J.S * J.T * J.solver->ts.nhuman * 56;
@@ -607,7 +633,8 @@ int gmr_retarget_group(const gmr_job_t* jobs, int njobs, int flags, int slices) 
       const size_t nq = J.solver->model.nq, nh = J.solver->ts.nhuman, S = (size_t)D.S, T = (size_t)J.T, s0 = (size_t)off[j].s0;
       if ((e = hipMemcpyAsync(d + o.q0, J.q0 + s0 * nq, S * nq * 8, hipMemcpyHostToDevice, st)) != hipSuccess ||
           (e = hipMemcpyAsync(d + o.h, J.human + s0 * T * nh * 7, S * T * nh * 56, hipMemcpyHostToDevice, st)) != hipSuccess ||
-          (J.len && (e = hipMemcpyAsync(d + o.len, J.len + s0, S * 4, hipMemcpyHostToDevice, st)) != hipSuccess))
+          (J.len && (e = hipMemcpyAsync(d + o.len, J.len + s0, S * 4, hipMemcpyHostToDevice, st)) != hipSuccess) ||
+          (J.scale && (e = hipMemcpyAsync(d + o.sc, J.scale + s0 * nh, S * nh * 8, hipMemcpyHostToDevice, st)) != hipSuccess))
         rc = fail(GMR_ERR_HIP, "H2D copy: %s", hipGetErrorString(e));
       // rows the kernel does not write come back as zeros (see gmr_hip.h)
       if (rc == GMR_OK && (J.len || J.tgt_out || J.err_out) && (e = hipMemsetAsync(d + o.qo, 0, o.end - o.qo, st)) != hipSuccess)
@@ -640,26 +667,33 @@ int gmr_retarget_streams_prof(gmr_solver_t* s, int S, int T, const double* d_q0,
                               double* d_q_out, int32_t* d_nsolve, int32_t* d_status, unsigned long long* d_prof) {
   const bool wide = s->layout4.tree_ok && (s->force_waves ? s->force_waves == 4 : S <= GMR_HELPER_MAX_STREAMS);
   if (!wide && s->wide.ok)
-    GMR_HIP_TRY(gmr_launch_ik_wide(s->wide_image.data(), &s->wide, &s->params, S, T, d_q0, d_human, nullptr, flags, d_q_out, d_nsolve,
+    GMR_HIP_TRY(gmr_launch_ik_wide(s->wide_image.data(), &s->wide, &s->params, S, T, d_q0, d_human, nullptr, nullptr, flags, d_q_out, d_nsolve,
                                d_status, nullptr, nullptr, nullptr, d_prof, nullptr));
   else
     GMR_HIP_TRY(gmr_launch_ik_streams((const uint4*)(wide ? s->image4 : s->image).data(), wide ? &s->layout4 : &s->layout, &s->params, S, T,
-                                  d_q0, d_human, nullptr, flags, d_q_out, d_nsolve, d_status, nullptr, nullptr, nullptr, d_prof));
+                                  d_q0, d_human, nullptr, nullptr, flags, d_q_out, d_nsolve, d_status, nullptr, nullptr, nullptr, d_prof));
   return GMR_OK;
 }
 #endif
 
 int gmr_retarget_streams(gmr_solver_t* s, int S, int T, const double* q0, const double* human, const int32_t* len,
                          int flags, double* q_out, int32_t* nsolve, int32_t* status, double* tgt_out, double* err_out) {
+  return gmr_retarget_streams_scaled(s, S, T, q0, human, len, nullptr, flags, q_out, nsolve, status, tgt_out, err_out);
+}
+
+int gmr_retarget_streams_scaled(gmr_solver_t* s, int S, int T, const double* q0, const double* human, const int32_t* len,
+                                const double* scale, int flags, double* q_out, int32_t* nsolve, int32_t* status, double* tgt_out,
+                                double* err_out) {
   if (!s) return fail(GMR_ERR_ARG, "null solver");
   if (S < 0 || T < 0) return fail(GMR_ERR_ARG, "negative S/T");
   if (S == 0 || T == 0) return GMR_OK;
   if (!q0 || !human || !q_out || !nsolve || !status) return fail(GMR_ERR_ARG, "null host buffer");
-  const gmr_job_t job{s, S, T, q0, human, len, q_out, nsolve, status, tgt_out, err_out};
+  const gmr_job_t job{s, S, T, q0, human, len, q_out, nsolve, status, tgt_out, err_out, scale};
   const size_t nq = s->model.nq, nh = s->ts.nhuman;
+  if (int rc = check_scale(scale, S, (int)nh, -1)) return rc;
   const size_t b_q0 = (size_t)S * nq * 8, b_h = (size_t)S * T * nh * 7 * 8, b_qo = (size_t)S * T * nq * 8;
   const size_t b_ns = (size_t)S * T * 2 * 4, b_st = (size_t)S * 4, b_len = (size_t)S * 4;
-  const size_t b_tg = tgt_out ? b_h : 0, b_er = err_out ? (size_t)S * T * 2 * 8 : 0;
+  const size_t b_tg = tgt_out ? b_h : 0, b_er = err_out ? (size_t)S * T * 2 * 8 : 0, b_sc = (size_t)S * nh * 8;
   // large batches: sliced, copies overlapped with the kernels (gmr_retarget_group)
   if (b_h >= ((size_t)32 << 20)) return gmr_retarget_group(&job, 1, flags, 0);
   gmr::Carve layout;
@@ -670,7 +704,7 @@ int gmr_retarget_streams(gmr_solver_t* s, int S, int T, const double* q0, const 
   char* d = s->ws.data();
   int rc = GMR_OK;
   hipError_t e;
-  // buffers are laid out [q0 | human | len | q_out | nsolve | status | tgt_out | err_out]; small calls (the per-frame
+  // buffers are laid out [q0 | human | len | scale | q_out | nsolve | status | tgt_out | err_out]; small calls (the per-frame
   // API) go through pinned staging so that a call is 1 H2D + 1 launch + 1 D2H + 1 sync
   const size_t in_bytes = o.qo, out_bytes = o.end - o.qo;
   const bool small = o.end <= gmr_solver::kPinBytes;
@@ -679,11 +713,13 @@ int gmr_retarget_streams(gmr_solver_t* s, int S, int T, const double* q0, const 
     memcpy(s->pin + o.q0, q0, b_q0);
     memcpy(s->pin + o.h, human, b_h);
     if (len) memcpy(s->pin + o.len, len, b_len);
+    if (scale) memcpy(s->pin + o.sc, scale, b_sc);
     if ((e = hipMemcpyAsync(d, s->pin, in_bytes, hipMemcpyHostToDevice, nullptr)) != hipSuccess)
       rc = fail(GMR_ERR_HIP, "H2D copy: %s", hipGetErrorString(e));
   } else if ((e = hipMemcpyAsync(d + o.q0, q0, b_q0, hipMemcpyHostToDevice, nullptr)) != hipSuccess ||
              (e = hipMemcpyAsync(d + o.h, human, b_h, hipMemcpyHostToDevice, nullptr)) != hipSuccess ||
-             (len && (e = hipMemcpyAsync(d + o.len, len, b_len, hipMemcpyHostToDevice, nullptr)) != hipSuccess)) {
+             (len && (e = hipMemcpyAsync(d + o.len, len, b_len, hipMemcpyHostToDevice, nullptr)) != hipSuccess) ||
+             (scale && (e = hipMemcpyAsync(d + o.sc, scale, b_sc, hipMemcpyHostToDevice, nullptr)) != hipSuccess)) {
     rc = fail(GMR_ERR_HIP, "H2D copy: %s", hipGetErrorString(e));
   }
   // frames at or beyond len[s] are not touched by the kernel, nor are the tgt_out / err_out rows of the frames after a
@@ -693,7 +729,8 @@ int gmr_retarget_streams(gmr_solver_t* s, int S, int T, const double* q0, const 
     rc = fail(GMR_ERR_HIP, "memset: %s", hipGetErrorString(e));
   const gmr_job_t D = job_at(job, d, o);
   if (rc == GMR_OK)
-    rc = gmr_retarget_streams_dev(s, S, T, D.q0, D.human, D.len, flags, D.q_out, D.nsolve, D.status, D.tgt_out, D.err_out, nullptr);
+    rc = gmr_retarget_streams_scaled_dev(s, S, T, D.q0, D.human, D.len, D.scale, flags, D.q_out, D.nsolve, D.status, D.tgt_out,
+                                         D.err_out, nullptr);
   if (rc == GMR_OK && small) {
     if ((e = hipMemcpyAsync(s->pin + o.qo, d + o.qo, out_bytes, hipMemcpyDeviceToHost, nullptr)) != hipSuccess ||
         (e = hipStreamSynchronize(nullptr)) != hipSuccess)

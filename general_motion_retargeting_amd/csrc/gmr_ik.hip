@@ -1030,6 +1030,9 @@ __device__ __forceinline__ void preprocess_wave(const LT& L, double* sm, const s
 // ---------------------------------------------------------------------------------------------
 // QP: which box-QP solver the instance carries (one per instance: the dense solver's 2 x NVP row registers would
 // otherwise set the register allocation of robots that never run it)
+// `scale` (f64 [S][nhum] or null: per-stream human scale tables) is the LAST argument on purpose: in the middle of the list,
+// beside `len`, it moved the kernarg offsets of everything behind it and cost the four-wavefront instances 4 to 8 more
+// spilled SGPRs and the headline 0.5 % frames/s; at the end every instance keeps the registers it had.
 template <int NVP, int NW, int QP>
 __global__ __launch_bounds__(64 * NW, GMR_IK_MIN_WAVES) void ik_streams_kernel(const uint4* __restrict__ image, IkLay<NVP, NW> L, IkParams P,
                                                              int S, int T, const double* __restrict__ q0,
@@ -1040,7 +1043,8 @@ __global__ __launch_bounds__(64 * NW, GMR_IK_MIN_WAVES) void ik_streams_kernel(c
                                                              int32_t* __restrict__ status,
                                                              double* __restrict__ tgt_out,
                                                              double* __restrict__ err_out,
-                                                             unsigned long long* __restrict__ prof_out) {
+                                                             unsigned long long* __restrict__ prof_out,
+                                                             const double* __restrict__ scale) {
   extern __shared__ __align__(16) double smem[];
   const int wave = threadIdx.x >> 6;
   const int lane = threadIdx.x & 63;
@@ -1082,6 +1086,8 @@ __global__ __launch_bounds__(64 * NW, GMR_IK_MIN_WAVES) void ik_streams_kernel(c
   const int max_iter = P.max_iter, human_root = P.human_root;
   const int use0 = P.use0, use1 = P.use1;
 
+  // this stream's own human scale table in place of the image's (only preprocess_wave reads it: the helpers never do)
+  if (scale && lane < nhum) (sm + L.o.scale)[lane] = scale[(size_t)s * nhum + lane];
   for (int i = lane; i < nq; i += 64) (sm + L.o.q)[i] = q0[(size_t)s * nq + i];
   WSYNC();
   hinge_sincos(L, sm, lane);
@@ -1247,15 +1253,15 @@ __global__ __launch_bounds__(64 * NW, GMR_IK_MIN_WAVES) void ik_streams_kernel(c
 template <int NVP, int NW, int QP>
 static hipError_t launch_nvp(const uint4* d_image, const gmr::IkLayout* L, const gmr::IkParams* P, int S, int T,
                              const double* d_q0, const double* d_human,
-                             const int32_t* d_len, int flags, double* d_q_out, int32_t* d_nsolve, int32_t* d_status,
-                             double* d_tgt_out, double* d_err_out, hipStream_t stream, unsigned long long* d_prof) {
+                             const int32_t* d_len, const double* d_scale, int flags, double* d_q_out, int32_t* d_nsolve,
+                             int32_t* d_status, double* d_tgt_out, double* d_err_out, hipStream_t stream, unsigned long long* d_prof) {
   hipLaunchKernelGGL((gmr::ik_streams_kernel<NVP, NW, QP>), dim3(S), dim3(64 * NW), L->smem_bytes, stream, d_image,
                      gmr::IkLay<NVP, NW>(static_cast<const gmr::IkDims&>(*L)), *P, S, T, d_q0, d_human, d_len, flags, d_q_out, d_nsolve, d_status,
-                     d_tgt_out, d_err_out, d_prof);
+                     d_tgt_out, d_err_out, d_prof, d_scale);
   return hipGetLastError();
 }
 
-#define GMR_ARGS d_image, L, P, S, T, d_q0, d_human, d_len, flags, d_q_out, d_nsolve, d_status, d_tgt_out, d_err_out, stream, d_prof
+#define GMR_ARGS d_image, L, P, S, T, d_q0, d_human, d_len, d_scale, flags, d_q_out, d_nsolve, d_status, d_tgt_out, d_err_out, stream, d_prof
 #define GMR_DISPATCH(NVP_)                                                                             \
   case NVP_:                                                                                           \
     if (L->nw == 1) return L->tree_small ? launch_nvp<NVP_, 1, gmr::QP_TREE_SMALL>(GMR_ARGS)           \
@@ -1265,8 +1271,8 @@ static hipError_t launch_nvp(const uint4* d_image, const gmr::IkLayout* L, const
 
 extern "C" hipError_t gmr_launch_ik_streams(const uint4* d_image, const gmr::IkLayout* L, const gmr::IkParams* P,
                                             int S, int T, const double* d_q0, const double* d_human,
-                                            const int32_t* d_len, int flags, double* d_q_out, int32_t* d_nsolve,
-                                            int32_t* d_status, double* d_tgt_out, double* d_err_out,
+                                            const int32_t* d_len, const double* d_scale, int flags, double* d_q_out,
+                                            int32_t* d_nsolve, int32_t* d_status, double* d_tgt_out, double* d_err_out,
                                             hipStream_t stream, unsigned long long* d_prof) {
   if (S <= 0 || T <= 0) return hipSuccess;
   switch (L->nvp) {

@@ -722,10 +722,11 @@ __device__ __forceinline__ void integrate_wide(DimsRef D, double* sm, double dt,
   PROF_END(pr, PH_INTEG);
 }
 
-// target preprocessing (motion_retarget.py:203-270); lane = human body
+// target preprocessing (motion_retarget.py:203-270); lane = human body.  `scl`: the stream's own scale row (nhum doubles
+// in device memory, read per frame: two loads that the L2 serves), or null = the image's table
 template <class DimsRef>
-__device__ __forceinline__ void preprocess_wide(DimsRef D, double* sm, const char* __restrict__ img, int human_root,
-                                                double ground_offset, int flags, int lane, Prof& pr) {
+__device__ __forceinline__ void preprocess_wide(DimsRef D, double* sm, const char* __restrict__ img, const double* __restrict__ scl,
+                                                int human_root, double ground_offset, int flags, int lane, Prof& pr) {
   PROF_BEGIN(pr);
   lane = fresh_lane(lane);     // (lane predicates of this phase are computed here and die with it: gmr_device_math.h)
   const double* raw = sm + LD.raw;
@@ -738,11 +739,11 @@ __device__ __forceinline__ void preprocess_wide(DimsRef D, double* sm, const cha
     const double* cst = img_at<double>(img, IM.pre) + 8 * lane;
     const double* in = raw + 7 * lane;
     const double* rp = raw + 7 * human_root;
-    const double sr = (img_at<double>(img, IM.pre) + 8 * human_root)[0];
+    const double sr = scl ? scl[human_root] : (img_at<double>(img, IM.pre) + 8 * human_root)[0];
     d3 srp = {sr * rp[0], sr * rp[1], sr * rp[2]};
     if (lane == human_root) p = srp;
     else {
-      const double s = cst[0];
+      const double s = scl ? scl[lane] : cst[0];
       p = d3{(in[0] - rp[0]) * s + srp.x, (in[1] - rp[1]) * s + srp.y, (in[2] - rp[2]) * s + srp.z};
     }
     d4 q = qnormalize(d4{in[3], in[4], in[5], in[6]});
@@ -804,6 +805,7 @@ struct WideJob {
   int32_t* status;
   double* tgt_out;
   double* err_out;
+  const double* scale;           // [S][nhum] per-stream human scale tables, or null = the image's table
   WideDims D;
   int max_iter, human_root, use0, use1, S, T, first;
 };
@@ -878,11 +880,13 @@ __device__ __forceinline__ bool queue_pop(const WideQueue& Q, const unsigned nch
   return true;
 }
 
-// Plain launch: ONE job, its fields are individual kernel arguments.  That matters: with ~100 SGPRs for ~350
+// Plain launch: ONE job without per-stream scale tables, its fields are individual kernel arguments.  That matters: with ~100 SGPRs for ~350
 // wave-uniform values the compiler re-loads a kernel ARGUMENT where it is used (s_load from the kernarg segment: no VALU
 // slot), while a value it cannot re-load is parked in a VGPR lane and comes back through v_readlane.  Passing the job as
 // one by-value struct (or reading it through a pointer to the kernarg segment) loses that property: measured, +500
-// v_readlane instructions in the code object and -4 % frames/s.
+// v_readlane instructions in the code object and -4 % frames/s.  For the same reason this instance has no scale
+// argument: GMR_SCALE is a literal null here and the branch in preprocess_wide folds away; a job that carries scale
+// rows runs the group instance, alone if need be.
 __global__ __launch_bounds__(64, GMR_WIDE_MIN_WAVES) void ik_wide_kernel(
     const char* __restrict__ img, WideDims D, int max_iter, int human_root, int use0, int use1, int S, int T,
     const double* __restrict__ q0, const double* __restrict__ human, const int32_t* __restrict__ len, int flags,
@@ -927,7 +931,9 @@ __global__ __launch_bounds__(64, GMR_WIDE_MIN_WAVES) void ik_wide_kernel(
 #define GMR_DIMS_T const WideDims&
 #define GMR_T_END T
 #define GMR_WINDOWED false
+#define GMR_SCALE static_cast<const double*>(nullptr)
 #include "gmr_ik_wide_item.inc"
+#undef GMR_SCALE
 #undef GMR_WINDOWED
 #undef GMR_T_END
 #undef GMR_DIMS_T
@@ -981,6 +987,7 @@ __global__ __launch_bounds__(64, GMR_WIDE_MIN_WAVES) void ik_wide_group_kernel(c
   int32_t* __restrict__ status = cj->status;
   double* __restrict__ tgt_out = cj->tgt_out;
   double* __restrict__ err_out = cj->err_out;
+  const double* __restrict__ scale = cj->scale;
   const int s = gs - cj->first;
   const int nq = D.nq, nhum = D.nhum;
   const double* prm = img_at<double>(img, IM.prm);
@@ -988,7 +995,9 @@ __global__ __launch_bounds__(64, GMR_WIDE_MIN_WAVES) void ik_wide_group_kernel(c
 #define GMR_DIMS_T const WideDims __attribute__((address_space(4)))&
 #define GMR_T_END Q.t_end
 #define GMR_WINDOWED (Q.windowed != 0)
+#define GMR_SCALE scale
 #include "gmr_ik_wide_item.inc"
+#undef GMR_SCALE
 #undef GMR_WINDOWED
 #undef GMR_T_END
 #undef GMR_DIMS_T
@@ -1060,10 +1069,12 @@ struct gmr_wide_job_desc {
   int S, T;
   const double* d_q0; const double* d_human; const int32_t* d_len;
   double* d_q_out; int32_t* d_nsolve; int32_t* d_status; double* d_tgt_out; double* d_err_out;
+  const double* d_scale;         // [S][nhum] or null
 };
 
 // Launch njobs >= 1 jobs as ONE scheduling domain on `stream`: a single job runs the plain instance (its fields are
-// kernel arguments), several jobs the group instance (job table in the workspace).  Queued dispatch engages when the
+// kernel arguments), several jobs -- or one that carries per-stream scale tables -- the group instance (job table in the
+// workspace).  Queued dispatch engages when the
 // streams of ALL jobs together outnumber the resident wavefronts.
 // t_begin / t_end: with t_end > 0 the launch covers the frames [t_begin, t_end) of every stream only and runs the group
 // instance; the per-stream state (QP bound sets, next frame, status) stays in the pool's workspace of `stream` for the next
@@ -1085,7 +1096,7 @@ extern "C" hipError_t gmr_launch_ik_wide_window(const gmr_wide_job_desc* jd, int
   memset(&tab, 0, sizeof tab);
   long long total = 0, nring = 0;
   int chunk = 0, maxT = 0, n = 0;
-  bool chunk_auto = false;
+  bool chunk_auto = false, scaled = false;
   if (p) { std::lock_guard<std::mutex> g(p->mu); chunk = p->chunk; chunk_auto = p->chunk_auto; }
   for (int j = 0; j < njobs; j++) {
     if (jd[j].S <= 0 || jd[j].T <= 0) continue;
@@ -1094,6 +1105,8 @@ extern "C" hipError_t gmr_launch_ik_wide_window(const gmr_wide_job_desc* jd, int
     J.nsolve = jd[j].d_nsolve; J.status = jd[j].d_status; J.tgt_out = jd[j].d_tgt_out; J.err_out = jd[j].d_err_out;
     J.D = static_cast<const gmr::WideDims&>(*jd[j].L);
     J.max_iter = jd[j].P->max_iter; J.human_root = jd[j].P->human_root; J.use0 = jd[j].P->use0; J.use1 = jd[j].P->use1;
+    J.scale = jd[j].d_scale;
+    scaled = scaled || J.scale;
     J.S = jd[j].S; J.T = jd[j].T; J.first = (int)total;
     total += jd[j].S;
     maxT = std::max(maxT, jd[j].T);
@@ -1103,7 +1116,7 @@ extern "C" hipError_t gmr_launch_ik_wide_window(const gmr_wide_job_desc* jd, int
   tab.njobs = n; tab.total = (int)total;
   const bool windowed = t_end > 0;
   if (windowed && (t_begin < 0 || t_begin >= t_end)) return hipErrorInvalidValue;
-  const bool multi = n > 1 || windowed;              // (windows are a feature of the group instance)
+  const bool multi = n > 1 || windowed || scaled;    // (windows and scale rows are features of the group instance)
   const int span = windowed ? std::min(maxT, t_end) - t_begin : maxT;      // frames per stream in this launch, at most
   // the ring has one entry per chunk: very long jobs get longer chunks rather than a ring beyond 64 MB (more than 2^24
   // streams cannot be helped by longer chunks: the loop ends at chunk >= T and the launch below is a direct one)
@@ -1184,11 +1197,13 @@ extern "C" hipError_t gmr_launch_ik_wide_window(const gmr_wide_job_desc* jd, int
 }
 
 extern "C" hipError_t gmr_launch_ik_wide(const char* d_image, const gmr::WideLayout* L, const gmr::IkParams* P, int S, int T,
-                                         const double* d_q0, const double* d_human, const int32_t* d_len, int flags,
-                                         double* d_q_out, int32_t* d_nsolve, int32_t* d_status, double* d_tgt_out,
-                                         double* d_err_out, hipStream_t stream, unsigned long long* d_prof, void* pool) {
+                                         const double* d_q0, const double* d_human, const int32_t* d_len,
+                                         const double* d_scale, int flags, double* d_q_out, int32_t* d_nsolve, int32_t* d_status,
+                                         double* d_tgt_out, double* d_err_out, hipStream_t stream, unsigned long long* d_prof,
+                                         void* pool) {
   if (S <= 0 || T <= 0) return hipSuccess;
-  const gmr_wide_job_desc jd{d_image, L, P, S, T, d_q0, d_human, d_len, d_q_out, d_nsolve, d_status, d_tgt_out, d_err_out};
+  if (d_scale && d_prof) return hipErrorInvalidValue;        // (the phase counters are the plain instance's)
+  const gmr_wide_job_desc jd{d_image, L, P, S, T, d_q0, d_human, d_len, d_q_out, d_nsolve, d_status, d_tgt_out, d_err_out, d_scale};
   return gmr_launch_ik_wide_group(&jd, 1, flags, stream, d_prof, pool);
 }
 

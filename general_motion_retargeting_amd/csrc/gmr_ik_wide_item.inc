@@ -7,8 +7,9 @@
 //
 // Names the including scope provides: img, D (type GMR_DIMS_T), max_iter, human_root, use0, use1, T, q0, human, len,
 // flags, q_out, nsolve, status, tgt_out, err_out, Q, queued, s, gs, t0, stat, bounds, nq, prm, fstride, sm, lane, pr; and the
-// macros GMR_T_END (frames at or beyond it are left to a later launch: T in the plain kernel) and GMR_WINDOWED (the launch is one
-// window of a stream's frames: its state is kept in Q.state for the next window; false in the plain kernel).
+// macros GMR_T_END (frames at or beyond it are left to a later launch: T in the plain kernel), GMR_WINDOWED (the launch is one
+// window of a stream's frames: its state is kept in Q.state for the next window; false in the plain kernel) and GMR_SCALE (the
+// job's per-stream human scale tables, f64 [S][nhum], or null = the image's table; a literal null in the plain kernel).
   // state that must start defined: the violation sets of the QP (double-buffered, cleared round by round)
   if (lane < 8) reinterpret_cast<unsigned long long*>(sm + LD.vset)[lane] = 0ull;
   {
@@ -24,6 +25,7 @@
   const int Tw = min(Ts, GMR_T_END);                 // this launch's share of the stream
   const int t1 = queued ? min(t0 + Q.chunk, Tw) : Tw;
   const double* hs = human + (size_t)s * T * fstride;
+  const double* scl = GMR_SCALE ? GMR_SCALE + (size_t)s * D.nhum : nullptr;
   double r0 = 0.0, r1 = 0.0;
   if (t0 < t1) {
     const double* nx = hs + (size_t)t0 * fstride;
@@ -42,7 +44,7 @@
     int ns0 = 0, ns1 = 0;
     const size_t f = (size_t)s * T + t;
     if (stat == GMR_STATUS_OK) {
-      preprocess_wide<GMR_DIMS_T>(D, sm, img, human_root, prm[4], flags, lane, pr);
+      preprocess_wide<GMR_DIMS_T>(D, sm, img, scl, human_root, prm[4], flags, lane, pr);
       if (tgt_out)     // the poses handed to task.set_target (motion_retarget.py:117-136) = scaled_human_data
         for (int i = lane; i < (int)fstride; i += 64) tgt_out[f * fstride + i] = (sm + LD.tgt)[i];
       double last_E = -1.0;                          // the stage's last residual norm (at the current configuration)

@@ -111,6 +111,16 @@ def smplx_path() -> str:
     return post_path()
 
 
+def heights_path() -> str:
+    """``"merged"`` or ``"groups"``: how a batch of clips of several human heights reaches the IK kernels.  Merged (the default):
+    ONE solver built from the unscaled config and ONE job, the heights travel as per-stream scale rows
+    (``ik_config.scale_rows``).  ``GMR_DATASET_HEIGHTS=groups`` keeps one solver and one job per height, for A/B; the bytes
+    are the same."""
+    if os.environ.get("GMR_DATASET_HEIGHTS", "merged").strip().lower() == "groups":
+        return "groups"
+    return "merged"
+
+
 class PinnedPool:
     """Page-locked output blocks for batches whose results are handed out as views.  A block is taken for one batch; it
     comes back when the LAST array viewing it has died (a finalizer on the buffer the arrays are views of), so a dict kept
@@ -225,7 +235,8 @@ class DevicePost:
         (:class:`chunking.ChunkRunner` in place of the one IK launch: NOT parity, ``chunk_reports`` says how far off); the
         post-processing reads the stitched clip-major output unchanged.
         ``jobs`` = ``[{"solver", "human": f64[S,T,nhuman,7] (page-locked for an asynchronous copy), "lens": i32[S],
-        "q0": f64[nq]}]``, all for the robot of ``km``.  A job of raw BVH clips carries, instead of ``"human"``, ``"T"`` and
+        "q0": f64[nq], optional "scales": f64[S,nhuman] (a human scale table per clip in place of the solver's; not with a
+        chunk spec that takes effect: the slots of a chunk job are not streams)}]``, all for the robot of ``km``.  A job of raw BVH clips carries, instead of ``"human"``, ``"T"`` and
         ``"bvh"`` = ``[{"handle": _lib.BvhHandle, "rows": f64[B,ncol] (page-locked), "offsets": f64[n,J,3], "clips": [index in
         lens, ...], "lens": [...]}]`` (one entry per topology) and optionally ``"packed"`` = ``[(index, f64[n,nhuman,7])]``: the
         raw rows are uploaded ragged and ``gmr_bvh_frames_dev`` writes ``human`` on the device, on the same stream, in front
@@ -324,10 +335,17 @@ class DevicePost:
             lens[:] = dlens[i]
             d_q0, d_len = self._d(f"q0_{i}", q0.nbytes), self._d(f"len_{i}", lens.nbytes)
             d_q, d_ns = self._d(f"q_out_{i}", S * T * sol.nq * 8), self._d(f"nsolve_{i}", S * T * 8)
+            d_sc = None
+            if j.get("scales") is not None:
+                rows = _lib.check_scales(j["scales"], S, sol.nhuman, f"job {i}: scales")
+                sc = self.pinned(f"scale_{i}", (S, sol.nhuman), np.float64)
+                sc[:] = rows if perms[i] is None else rows[perms[i]]
+                d_sc = self._d(f"scale_{i}", sc.nbytes)
+                copies.append((d_sc.ptr, sc))
             for dst, src in copies + [(d_q0.ptr, q0), (d_len.ptr, lens)]:
                 h2d(dst, src)
             d_status.append(C.c_void_p(base + o_st + 4 * clip))
-            launch.append((sol, S, T, d_q0, d_h, d_len, d_q, d_ns, d_status[-1]))
+            launch.append((sol, S, T, d_q0, d_h, d_len, d_q, d_ns, d_status[-1]) + (() if d_sc is None else (d_sc,)))
             sources.append((S, T, d_q, d_len))
             clip += S
         for _, _, _, d_in, _, stage in sx_calls:
@@ -344,6 +362,8 @@ class DevicePost:
         specs = [chunking.resolve_any(chunk, l, total_frames) for l in dlens]
         self.chunk_reports = [None] * len(jobs)
         if any(sp is not None for sp in specs):
+            if any(len(job) > 9 for job in launch):
+                raise ValueError("per-clip scales do not go with a chunk spec that takes effect: run the heights as groups")
             if self._chunker is None:
                 self._chunker = chunking.ChunkRunner()
             reports = self._chunker.run(launch, dlens, specs, ik_flags, st)
@@ -410,17 +430,26 @@ class ClipRetargeter:
     chunk_report: Optional[List[Dict]] = None
     _library_mode: Optional[str] = None       # hand the batch to a motion library: off
     library = None
+    _per_clip = False            # one height per clip, travelling as scale rows: off
+    _heights: Optional[np.ndarray] = None
 
-    def __init__(self, src_human: str, tgt_robot: str, actual_human_height: Optional[float] = None, height_adjust: bool = True,
+    def __init__(self, src_human: str, tgt_robot: str, actual_human_height=None, height_adjust: bool = True,
                  root_origin_offset: bool = True, offset_to_ground: bool = False, chunk=None, library=False):
-        """``library`` (``False`` | ``True`` | ``"world"`` | ``"reference"``): every batch also leaves a
+        """``actual_human_height``: one height for every clip (a number or None: the solver is built for it, as ever), or a
+        sequence with one height per clip of a call (``add(clip, height=)`` in the staged protocol): the solver is built from
+        the unscaled config and every clip carries its height as a scale row of the ONE job, the bits of a retargeter built
+        for that height.  Per-clip heights do not go with a ``chunk`` spec that takes effect (the slots of a chunk job are
+        not streams; :func:`retarget_clips` then runs the heights as groups).
+        ``library`` (``False`` | ``True`` | ``"world"`` | ``"reference"``): every batch also leaves a
         ``motion_library.MotionLibrary`` of its clips in ``self.library`` -- on the device post-processing path filled from the
         block the post-processing wrote, without a second upload (``True`` = ``"world"``).  The motion dicts do not change.
         ``chunk``: ``None`` (default: one stream per clip, as ever), a ``chunking.ChunkSpec`` or ``"auto"``: clips longer than the
         spec's ``frames`` are cut into chunks that run as independent streams (NOT parity with the sequential run; DESIGN.md
         section 6g).  ``chunk_report`` then holds, per clip of the last batch, K, ``seam_max``, seams repaired / left bad, passes
         and ``warm_solves``; ``chunk_summary`` the totals over all batches."""
-        self.gmr = GeneralMotionRetargeting(src_human, tgt_robot, actual_human_height=actual_human_height)
+        self._per_clip = actual_human_height is not None and np.ndim(actual_human_height) > 0
+        self._heights = np.asarray(actual_human_height, dtype=np.float64).reshape(-1) if self._per_clip else None
+        self.gmr = GeneralMotionRetargeting(src_human, tgt_robot, actual_human_height=None if self._per_clip else actual_human_height)
         self.height_adjust, self.root_origin_offset, self.offset_to_ground = height_adjust, root_origin_offset, offset_to_ground
         self.chunk = chunk
         self._library_mode = None if not library else ("world" if library is True else str(library))
@@ -459,6 +488,7 @@ class ClipRetargeter:
         self._cap = max(1, min(int(max_clips), int(frames_budget) // self._T))
         self._human = None                                # the padded batch: locked when the first packed clip arrives
         self._lens = np.zeros(self._cap, dtype=np.int32)
+        self._hts = np.full(self._cap, np.nan)            # per-clip heights (NaN = none: the unscaled table)
         self._n = 0
         # a batch of raw BVH clips (device path): per topology the rows of its clips, concatenated in page-locked memory
         self._raw_mode = self._seen_raw
@@ -497,14 +527,20 @@ class ClipRetargeter:
         self._raw_mode = self._seen_raw = True
         return True
 
-    def add(self, clip) -> bool:
+    def add(self, clip, height: Optional[float] = None) -> bool:
         """Copy one clip into the batch; False when it does not fit (batch full, or the clip is longer than the batch's
-        rows): the caller finishes this batch and begins another.  A raw BVH clip (``lafan1.BvhRaw``) joins a batch whose
+        rows): the caller finishes this batch and begins another.  ``height``: this clip's ``actual_human_height`` (only a
+        retargeter built with per-clip heights takes one).  A raw BVH clip (``lafan1.BvhRaw``) joins a batch whose
         frames are computed on the device (:func:`bvh_path`): only its rows are copied.  On the host path, for a file the
         device path does not take, or in a batch that already holds packed clips, its frames are computed here."""
         import time
         from .utils import lafan1
         t0 = time.perf_counter()
+        if height is not None:
+            if not self._per_clip:
+                raise ValueError("this retargeter was built for one height: build it with a sequence of heights")
+            if self._n < self._cap:
+                self._hts[self._n] = height               # (kept only if the clip is: a refused clip leaves _n where it is)
         if isinstance(clip, lafan1.BvhRaw):
             if self._bvh_device and lafan1.device_takes(clip) and (self._raw_mode or self._n == 0):
                 ok = self._add_raw(clip)
@@ -526,6 +562,13 @@ class ClipRetargeter:
         self.timing["pack"] = self.timing.get("pack", 0.0) + time.perf_counter() - t0
         return True
 
+    def _scales(self, S: int):
+        """the scale rows of the batch's clips (None for a retargeter of one height)"""
+        if not self._per_clip:
+            return None
+        from .ik_config import scale_rows
+        return scale_rows(self.gmr._ik_config, self._hts[:S])
+
     def finish(self, fps: Sequence[float]) -> List[Dict]:
         import time
         from . import _lib
@@ -535,6 +578,11 @@ class ClipRetargeter:
         t1 = time.perf_counter()
         sol = gmr.hip_solver
         lens = self._lens[:S].copy()
+        scales = self._scales(S)
+        if scales is not None:
+            from . import chunking
+            if chunking.resolve_any(self.chunk, lens) is not None:
+                raise ValueError("per-clip heights do not go with a chunk spec that takes effect: run the heights as groups")
         if post_path() == "device":
             return self._finish_device(fps, lens)
         q0 = self._buf("q0", (S, sol.nq), np.float64)
@@ -547,7 +595,7 @@ class ClipRetargeter:
             chunking.summarize(self.chunk_report, self.chunk_summary)
         else:
             outs = [(self._buf("q_out", (S, T, sol.nq), np.float64), self._buf("nsolve", (S, T, 2), np.int32), np.zeros(S, np.int32))]
-            (qpos, _, status), = _lib.retarget_group([{"solver": sol, "human": self._human[:S], "q0": q0, "lens": lens}],
+            (qpos, _, status), = _lib.retarget_group([{"solver": sol, "human": self._human[:S], "q0": q0, "lens": lens, "scales": scales}],
                                                      gmr._flags(self.offset_to_ground), 0, outs=outs)
         t2 = time.perf_counter()
         self._n = 0
@@ -581,6 +629,7 @@ class ClipRetargeter:
                             "lens": g["lens"]} for g in self._raw.values()]}
         else:
             job = {"solver": gmr.hip_solver, "human": self._human[:S], "lens": lens, "q0": gmr.model.qpos0}
+        job["scales"] = self._scales(S)
         self._n = 0
         rp, rr, dp, lbp, spans, (status,) = self._dev_post.run([job], self._km, gmr._flags(self.offset_to_ground), self.height_adjust,
                                                                self.root_origin_offset, 0.0, self.timing, chunk=self.chunk,
@@ -604,14 +653,16 @@ class ClipRetargeter:
         packed = [c if isinstance(c, (np.ndarray, BvhRaw)) else self.gmr.pack_frames(c) for c in clips]
         if not packed:
             return []
+        if self._per_clip and len(self._heights) != len(packed):
+            raise ValueError(f"{len(self._heights)} heights for {len(packed)} clips")
         self.begin(max(len(p) for p in packed), len(packed), 1 << 62)
-        for p in packed:
-            assert self.add(p)
+        for k, p in enumerate(packed):
+            assert self.add(p, float(self._heights[k]) if self._per_clip else None)
         return self.finish(fps)
 
 
 def retarget_clips(src_human: str, tgt_robot: str, clips: Sequence, fps: Sequence[float],
-                   actual_human_height: Optional[float] = None, height_adjust: bool = True,
+                   actual_human_height=None, height_adjust: bool = True,
                    root_origin_offset: bool = True, offset_to_ground: bool = False, chunk=None, report: Optional[List] = None,
                    library=False):
     """Retarget many clips of one (source, robot, height) in ONE IK launch.  ``library`` (``True`` | ``"world"`` | ``"reference"``;
@@ -622,13 +673,40 @@ def retarget_clips(src_human: str, tgt_robot: str, clips: Sequence, fps: Sequenc
     ``clips[i]`` is a list of ``human_data`` dicts or an array ``[T_i, nhuman, 7]`` (ragged lengths
     are fine: streams are padded and the kernel stops each stream at its own length).
     Returns one motion dict per clip, identical to processing the clips one by one.
+
+    ``actual_human_height``: a number (or None) for all clips, or one height per clip: still ONE solver and ONE IK launch, the
+    heights travel as per-stream scale rows, and the motions are the bytes of one call per height.  Scale rows are not
+    gathered into chunk jobs: with a ``chunk`` spec that takes effect the heights run as groups, one call per height as before
+    (and no ``library``).
     """
+    if actual_human_height is not None and np.ndim(actual_human_height) > 0:
+        heights = [float(h) for h in np.asarray(actual_human_height, dtype=np.float64).reshape(-1)]
+        if len(heights) != len(clips):
+            raise ValueError(f"{len(heights)} heights for {len(clips)} clips")
+        if heights_groups_needed(chunk, [len(c) for c in clips]):
+            if library:
+                raise ValueError("a motion library takes one job: chunked clips of several heights run as height groups")
+            out: List = [None] * len(clips)
+            for h in dict.fromkeys(heights):
+                idxs = [i for i, x in enumerate(heights) if x == h]
+                for i, md in zip(idxs, retarget_clips(src_human, tgt_robot, [clips[i] for i in idxs], [fps[i] for i in idxs], h, height_adjust,
+                                                      root_origin_offset, offset_to_ground, chunk=chunk, report=report)):
+                    out[i] = md
+            return out
     rt = ClipRetargeter(src_human, tgt_robot, actual_human_height, height_adjust, root_origin_offset, offset_to_ground, chunk=chunk,
                         library=library)
     out = rt(clips, fps)
     if report is not None and rt.chunk_report is not None:
         report.extend(rt.chunk_report)
     return (out, rt.library) if library else out
+
+
+def heights_groups_needed(chunk, lens) -> bool:
+    """Whether a batch of these clip lengths whose heights would travel as scale rows has to run as one job per height
+    instead: a chunk spec takes effect on it (some clip is longer than the spec's ``frames``).  The slots of a chunk job are
+    not streams, and their scale rows are not gathered (DESIGN.md section 6g names that as the follow-up)."""
+    from . import chunking
+    return chunking.resolve_any(chunk, np.asarray(lens, dtype=np.int64)) is not None
 
 
 def retarget_mixed(groups: Sequence[Dict], offset_to_ground: bool = False, slices: int = 0, pinned_outputs: bool = False):
@@ -639,15 +717,19 @@ def retarget_mixed(groups: Sequence[Dict], offset_to_ground: bool = False, slice
     overlap the kernels.  Bit-identical to retargeting every group by itself.
 
     ``groups[i]`` = ``{"src_human", "tgt_robot", "human": f64[S,T,nhuman,7], optional "lens",
-    "actual_human_height"}``; arrays allocated with ``_lib.pinned_empty`` are copied asynchronously.
+    "actual_human_height"}``, the height a number for the group or one per stream (``f64[S]``: the group's solver is built
+    from the unscaled config and the heights travel as scale rows); arrays allocated with ``_lib.pinned_empty`` are copied asynchronously.
     Returns a list of ``(qpos[S,T,nq], nsolve[S,T,2], status[S])``.
     """
     from . import _lib
     jobs, keep = [], []
     for g in groups:
-        gmr = GeneralMotionRetargeting(g["src_human"], g["tgt_robot"], actual_human_height=g.get("actual_human_height"))
+        h = g.get("actual_human_height")
+        per_stream = h is not None and np.ndim(h) > 0
+        gmr = GeneralMotionRetargeting(g["src_human"], g["tgt_robot"], actual_human_height=None if per_stream else h)
         keep.append(gmr)
-        jobs.append({"solver": gmr.hip_solver, "human": g["human"], "lens": g.get("lens")})
+        jobs.append({"solver": gmr.hip_solver, "human": g["human"], "lens": g.get("lens"),
+                     "scales": gmr.stream_scales(len(g["human"]), heights=h) if per_stream else None})
     flags = _lib.FLAG_OFFSET_TO_GROUND if offset_to_ground else 0
     return _lib.retarget_group(jobs, flags, slices, out_pinned=pinned_outputs)   # (rows beyond a stream's length: zeros)
 
@@ -1098,25 +1180,43 @@ def _load_smplx_raw(f):
 
 def retarget_smplx_loaded(raws: Sequence[Dict], smplx_body_model_path: str, tgt_robot: str, tgt_fps: int = 30,
                           height_adjust: bool = True, root_origin_offset: bool = True,
-                          timing: Optional[Dict[str, float]] = None, chunk=None, report: Optional[List] = None) -> List[Optional[Dict]]:
+                          timing: Optional[Dict[str, float]] = None, chunk=None, report: Optional[List] = None,
+                          library=False):
     """``process_file`` (smplx_to_robot_dataset.py:39-146) for many already-read files: joints-only body model and fps
-    alignment on the device, the clips grouped by human height (a file's height comes from its betas, :36-39) into ONE group
-    launch, two FK launches for the post-processing of all clips together.  On the device path (:func:`smplx_path`, and every
+    alignment on the device, ONE solver (built from the unscaled config, kept from batch to batch) and ONE IK job for the
+    whole batch -- a file's height comes from its betas (:36-39) and travels as that clip's scale row
+    (``ik_config.scale_rows``), so a motion library of the batch is not limited by the count of heights -- and two FK launches
+    for the post-processing of all clips together.  ``GMR_DATASET_HEIGHTS=groups`` (:func:`heights_path`) keeps one solver and
+    one job per height in one group launch; the bytes are the same.  Scale rows are not gathered into chunk jobs: with a
+    ``chunk`` spec that takes effect the batch runs as height groups whatever the switch says.  On the device path (:func:`smplx_path`, and every
     body model of the batch one that ``utils.smpl.smplx_device_takes``) the files' arrays go up as they are and ONE
     ``gmr_smplx_batch_frames_dev`` call writes the packed frames of all clips where the IK kernels read them; otherwise one
-    ``gmr_smplx_frames`` call per clip and a padded upload -- the same bits.  ``timing`` accumulates the seconds of the stages."""
+    ``gmr_smplx_frames`` call per clip and a padded upload -- the same bits.  ``timing`` accumulates the seconds of the stages.
+    ``library`` (``True`` | ``"world"`` | ``"reference"``; default off): returns ``(motions, motion_library.MotionLibrary)`` as
+    :func:`retarget_clips` does, the clips in the order of ``raws``; the batch must then be one job (the merged path)."""
     import time
     from . import _lib
     from .utils import smpl
     t0 = time.perf_counter()
+    from . import chunking
+    from .ik_config import scale_rows
     packed, fps_of, height, bms = {}, {}, {}, {}
-    gmr_of: Dict[float, GeneralMotionRetargeting] = {}
     for i, d in enumerate(raws):
         bms[i] = smpl.body_model_for(smplx_body_model_path, str(d["gender"]))
         betas = np.asarray(d["betas"])
-        h = height[i] = float(1.66 + 0.1 * (betas[0] if betas.ndim == 1 else betas[0, 0]))
-        if h not in gmr_of:
-            gmr_of[h] = GeneralMotionRetargeting("smplx", tgt_robot, actual_human_height=h)
+        height[i] = float(1.66 + 0.1 * (betas[0] if betas.ndim == 1 else betas[0, 0]))
+    # merged: the frame counts decide below whether a chunk spec takes effect; they need no solver (AMASS files say them)
+    merged = heights_path() == "merged" and bool(raws)
+    if merged and chunk is not None:
+        merged = not heights_groups_needed(chunk, [smpl.smplx_frame_count(d, tgt_fps) for d in raws])
+    gmr_of: Dict[Optional[float], GeneralMotionRetargeting] = {}
+    if merged:
+        gmr_of[None] = _smplx_base_retargeter(tgt_robot)
+    else:
+        for h in height.values():
+            if h not in gmr_of:
+                gmr_of[h] = GeneralMotionRetargeting("smplx", tgt_robot, actual_human_height=h)
+    group_of = {i: (None if merged else height[i]) for i in height}
     device = post_path() == "device" and bool(raws)
     any_g = next(iter(gmr_of.values()), None)
     raw = device and smplx_path() == "device" and all(smpl.smplx_device_takes(bm, any_g) for bm in {id(b): b for b in bms.values()}.values())
@@ -1125,17 +1225,18 @@ def retarget_smplx_loaded(raws: Sequence[Dict], smplx_body_model_path: str, tgt_
             packed[i] = smpl.smplx_raw_clip(d, bms[i], tgt_fps)
             fps_of[i] = packed[i]["aligned_fps"]
         else:
-            packed[i], fps_of[i] = smpl.smplx_frames_packed_fused(gmr_of[height[i]], d, bms[i], tgt_fps=tgt_fps)      # body model + alignment, one call
+            packed[i], fps_of[i] = smpl.smplx_frames_packed_fused(gmr_of[group_of[i]], d, bms[i], tgt_fps=tgt_fps)      # body model + alignment, one call
     t1 = time.perf_counter()
     dp = _smplx_device_post(any_g.xml_file) if device else None
     jobs, members = [], []
     for n, (h, g) in enumerate(gmr_of.items()):
-        idxs = [i for i in range(len(raws)) if height[i] == h]
+        idxs = [i for i in range(len(raws)) if group_of[i] == h]
         lens = np.array([packed[i]["nout"] if raw else packed[i].shape[0] for i in idxs], dtype=np.int32)
         T = max(int(lens.max()), 1)
         members.append((idxs, lens))
+        scales = scale_rows(g._ik_config, [height[i] for i in idxs]) if merged else None
         if raw:
-            jobs.append({"solver": g.hip_solver, "T": T, "lens": lens, "q0": g.model.qpos0,
+            jobs.append({"solver": g.hip_solver, "T": T, "lens": lens, "q0": g.model.qpos0, "scales": scales,
                          "smplx": {"handle": smpl.smplx_batch_handle(bms[idxs[0]], g), "clips": [packed[i] for i in idxs]}})
             continue
         shape = (len(idxs), T, len(g.human_body_names), 7)
@@ -1145,16 +1246,25 @@ def retarget_smplx_loaded(raws: Sequence[Dict], smplx_body_model_path: str, tgt_
         human[..., 4:] = 0.0
         for k, i in enumerate(idxs):
             human[k, : lens[k]] = packed[i]
-        jobs.append({"solver": g.hip_solver, "human": human, "lens": lens, "q0": g.model.qpos0})
+        jobs.append({"solver": g.hip_solver, "human": human, "lens": lens, "q0": g.model.qpos0, "scales": scales})
     if timing is not None:
         timing["prepare"] = timing.get("prepare", 0.0) + t1 - t0
         timing["pack"] = timing.get("pack", 0.0) + time.perf_counter() - t1
+        # counts, not seconds: batches, their IK jobs, and the batches wide enough (more than 300 streams in all) for the
+        # throughput shape of the IK kernel; the others run the latency shape job by job
+        for k, v in (("n_batches", 1), ("n_ik_jobs", len(jobs)), ("n_batches_throughput_shape", int(len(raws) > 300))):
+            timing[k] = timing.get(k, 0) + v
+    lib_mode = None if not library else ("world" if library is True else str(library))
     if not raws:
-        return []
+        return ([], None) if library else []
     fps = [fps_of[i] for i in range(len(raws))]
+    if lib_mode is not None and len(jobs) != 1:
+        raise ValueError("a motion library takes the clips in the order they were handed over: one job (the merged heights path)")
     if device:
         km, post = dp
-        rp, rr, dof, lbp, spans, status = post.run(jobs, km, 0, height_adjust, root_origin_offset, timing=timing, chunk=chunk)
+        rp, rr, dof, lbp, spans, status = post.run(jobs, km, 0, height_adjust, root_origin_offset, timing=timing, chunk=chunk,
+                                                   library=None if lib_mode is None else
+                                                   {"fps": [[fps[i] for i in idxs] for idxs, _ in members], "ang_vel": lib_mode})
         if report is not None:
             report.extend(r for rs in post.chunk_reports if rs is not None for r in rs)
         t2 = time.perf_counter()
@@ -1166,10 +1276,10 @@ def retarget_smplx_loaded(raws: Sequence[Dict], smplx_body_model_path: str, tgt_
                 out[i] = motion_dict(fps[i], rp[a:b], rr[a:b], dof[a:b], lbp[a:b], km.body_names)
         if timing is not None:
             timing["dicts"] = timing.get("dicts", 0.0) + time.perf_counter() - t2
-        return out
-    from . import chunking
+        return (out, post.library) if library else out
     total_frames = int(sum(int(l.sum()) for _, l in members))
     specs = [chunking.resolve_any(chunk, l, total_frames) for _, l in members]
+    assert not (merged and any(sp is not None for sp in specs))
     plain = [n for n, sp in enumerate(specs) if sp is None]
     results: List = [None] * len(jobs)
     for n, r in zip(plain, _lib.retarget_group([{k: v for k, v in jobs[n].items() if k != "q0"} for n in plain]) if plain else []):
@@ -1187,10 +1297,25 @@ def retarget_smplx_loaded(raws: Sequence[Dict], smplx_body_model_path: str, tgt_
         for k, i in enumerate(idxs):
             qpos[i] = q[k, : lens[k]]
     km = KinematicsModel(any_g.xml_file)
-    return postprocess_clips(qpos, km, fps, height_adjust, root_origin_offset)
+    out = postprocess_clips(qpos, km, fps, height_adjust, root_origin_offset)
+    if lib_mode is not None:
+        from .motion_library import MotionLibrary
+        lib_ = MotionLibrary.from_motions(out, lib_mode)
+        lib_._kinematics = km
+        return out, lib_
+    return out
 
 
 _SMPLX_DEVICE_POST: Dict[str, tuple] = {}
+_SMPLX_BASE: Dict[str, GeneralMotionRetargeting] = {}
+
+
+def _smplx_base_retargeter(tgt_robot: str) -> GeneralMotionRetargeting:
+    """The retargeter of a robot built from the UNSCALED config, kept for the batches of a run: every height is a scale row
+    of its one solver, so a batch builds nothing."""
+    if tgt_robot not in _SMPLX_BASE:
+        _SMPLX_BASE[tgt_robot] = GeneralMotionRetargeting("smplx", tgt_robot)
+    return _SMPLX_BASE[tgt_robot]
 
 
 def _smplx_device_post(xml_file: str):

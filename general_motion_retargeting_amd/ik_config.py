@@ -154,6 +154,23 @@ def build_task_tables(ik_config: dict, actual_human_height: Optional[float] = No
     )
 
 
+def scale_row(ik_config: dict, actual_human_height: Optional[float] = None) -> np.ndarray:
+    """The packed human scale table ``f64[nhuman]`` of one height from the UNSCALED config: the expression of
+    :func:`build_task_tables` (``v * ratio``) in ``human_names`` order, i.e. bit for bit what ``pack_taskset`` puts into
+    the task set of a solver built for that height.  A row of the ``scales`` of ``retarget_streams``."""
+    return scale_rows(ik_config, [actual_human_height])[0]
+
+
+def scale_rows(ik_config: dict, heights) -> np.ndarray:
+    """:func:`scale_row` for ``heights[S]`` (None or NaN = no height: ratio 1) -> ``f64[S, nhuman]``."""
+    h = np.array([np.nan if x is None else x for x in np.asarray(heights, dtype=object).reshape(-1)], dtype=np.float64)
+    if h.size and not np.all(np.isnan(h) | (np.isfinite(h) & (h > 0))):
+        raise ValueError("heights must be finite and positive")
+    ratio = np.where(np.isnan(h), 1.0, h / np.float64(ik_config["human_height_assumption"]))
+    table = np.array(list(ik_config["human_scale_table"].values()), dtype=np.float64)
+    return np.ascontiguousarray(table[None, :] * ratio[:, None])
+
+
 # --------------------------------------------------------------------------- #
 # packing
 # --------------------------------------------------------------------------- #

@@ -22,7 +22,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from .ik_config import TaskTables, build_task_tables, pack_model, pack_taskset
+from .ik_config import TaskTables, build_task_tables, pack_model, pack_taskset, scale_rows
 from .models import load_ik_config, load_robot
 from .params import IK_CONFIG_DICT, ROBOT_XML_DICT
 
@@ -86,6 +86,7 @@ class GeneralMotionRetargeting:
         if verbose:
             print("Use IK config: ", ik_config_path)
 
+        self._ik_config = ik_config       # unscaled: the scale rows of retarget_streams(heights=) come from it
         self._tables: TaskTables = build_task_tables(ik_config, actual_human_height, damping)
         tt = self._tables
         # same public attributes as the reference (:47-59)
@@ -278,15 +279,35 @@ class GeneralMotionRetargeting:
         self.last_num_solves = ns.copy()
         return q
 
+    def stream_scales(self, S: int, heights=None, scales=None) -> Optional[np.ndarray]:
+        """The per-stream human scale tables ``f64[S, nhuman]`` of ``heights[S]`` (``actual_human_height`` per stream: the
+        table of an object built for that height, whatever height THIS object was built for) or of ``scales`` itself; at
+        most one of the two, None for neither.  Raises before anything reaches the device."""
+        if heights is not None and scales is not None:
+            raise ValueError("give heights or scales, not both")
+        if heights is not None:
+            heights = np.asarray(heights, dtype=np.float64)
+            if heights.shape != (S,):
+                raise ValueError(f"heights must be [{S}], got {heights.shape}")
+            return scale_rows(self._ik_config, heights)
+        return _lib.check_scales(scales, S, len(self._human_names))
+
     def retarget_streams(self, human: np.ndarray, q0: Optional[np.ndarray] = None, lens=None,
-                         offset_to_ground=False):
+                         offset_to_ground=False, heights=None, scales=None, want_targets: bool = False,
+                         want_errors: bool = False):
         """Many independent streams ``human[S, T, nhuman, 7]`` (each from ``q0[s]``, default
         ``qpos0`` = a fresh object per clip as the dataset scripts do).  Does not touch this object's
-        configuration.  Returns ``(qpos[S, T, nq], nsolve[S, T, 2], status[S])``."""
+        configuration.  Returns ``(qpos[S, T, nq], nsolve[S, T, 2], status[S])``, with ``want_targets`` /
+        ``want_errors`` also ``targets[S, T, nhuman, 7]`` (every frame's ``scaled_human_data``) and ``errors[S, T, 2]``
+        (``error1()`` / ``error2()``).  ``heights[S]`` (one ``actual_human_height`` per stream) or ``scales[S, nhuman]``
+        (one human scale table per stream: per-subject limb scaling) let subjects of different sizes share this object and
+        the launch; stream ``s`` then gets the bits of an object built for ``heights[s]``."""
         S = human.shape[0]
+        scales = self.stream_scales(S, heights, scales)
         if q0 is None:
             q0 = np.broadcast_to(self.model.qpos0, (S, self.model.nq)).copy()
-        return self.hip_solver.retarget_streams(q0, human, lens=lens, flags=self._flags(offset_to_ground))
+        return self.hip_solver.retarget_streams(q0, human, lens=lens, flags=self._flags(offset_to_ground), scales=scales,
+                                                want_targets=want_targets, want_errors=want_errors)
 
     # ---- errors (reference :188-200): evaluated by the kernel ------------------------------
     def _error(self, stage: int) -> float:

@@ -190,6 +190,12 @@ def _frame_plan(smplx_data, num_frames: int, tgt_fps) -> Tuple[bool, int, float]
     return False, num_frames, tgt_fps
 
 
+def smplx_frame_count(smplx_data, tgt_fps=30) -> int:
+    """Frames a loaded AMASS file retargets to (``nout`` of :func:`_frame_plan`): host arithmetic on the file's own counts."""
+    N = int(np.asarray(smplx_data["root_orient"]).reshape(-1, 3).shape[0])
+    return int(_frame_plan(smplx_data, N, tgt_fps)[1]) if N else 0
+
+
 def _poses(body_model, smplx_output):
     J = len(body_model.parents)
     full = _np(smplx_output.full_pose, np.float32)

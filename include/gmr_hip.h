@@ -121,6 +121,25 @@ int gmr_retarget_streams_dev(gmr_solver_t* solver, int S, int T, const double* d
 int gmr_retarget_streams(gmr_solver_t* solver, int S, int T, const double* q0, const double* human,
                          const int32_t* len, int flags, double* q_out, int32_t* nsolve, int32_t* status,
                          double* tgt_out, double* err_out);
+/* The same pair with a human scale table PER STREAM, so that subjects of different heights (or limb proportions)
+ * share one solver and one launch:
+ *
+ *   scale   f64 [S][nhuman] or NULL  row s replaces, for stream s, the scale entries of the solver's task set
+ *                                    (gmr_taskset_t's human scale table, packed human-body order, the entry of the
+ *                                    human root included); NULL = the solver's own table, i.e. the pair above
+ *
+ * The reference folds `human_scale_table * actual_human_height / human_height_assumption` into the object
+ * (motion_retarget.py:13-114), one object per height; here that product is the caller's row.  A stream with row r gives
+ * the bits of a solver whose table is r.  The host entry point rejects a non-finite or non-positive entry with
+ * GMR_ERR_ARG, naming the stream and the body; the device entry point cannot look: the values are the caller's
+ * responsibility.  In the 1-wavefront shape a launch with scale rows runs the group instance of the throughput kernel. */
+int gmr_retarget_streams_scaled_dev(gmr_solver_t* solver, int S, int T, const double* d_q0, const double* d_human,
+                                    const int32_t* d_len, const double* d_scale, int flags, double* d_q_out,
+                                    int32_t* d_nsolve, int32_t* d_status, double* d_tgt_out, double* d_err_out,
+                                    void* stream);
+int gmr_retarget_streams_scaled(gmr_solver_t* solver, int S, int T, const double* q0, const double* human,
+                                const int32_t* len, const double* scale, int flags, double* q_out, int32_t* nsolve,
+                                int32_t* status, double* tgt_out, double* err_out);
 /* ---- several (robot, task set) jobs as ONE scheduling domain -------------------------------------------------------
  * BASELINE.json configs[3] ("all 6 robots mixed-DoF batch"; SURVEY.md section 8d: "per-robot kernels or one kernel
  * with per-stream model index"): the reference would run one mp.Pool worker per file whatever its robot
@@ -140,6 +159,8 @@ typedef struct gmr_job {
   int32_t* status;         /* [S]                                                                                    */
   double* tgt_out;         /* [S][T][nhuman][7] or NULL                                                              */
   double* err_out;         /* [S][T][2] or NULL                                                                      */
+  const double* scale;     /* [S][nhuman] or NULL  per-stream human scale tables (gmr_retarget_streams_scaled); the   */
+                           /* host entry point checks them, slices copy their rows, every window reads the same rows */
 } gmr_job_t;
 /* device pointers, asynchronous on `stream` */
 int gmr_retarget_group_dev(const gmr_job_t* jobs, int njobs, int flags, void* stream);

@@ -3,7 +3,10 @@
 ``python -m general_motion_retargeting_amd.dataset --source smplx`` with the batch path on the device and with
 ``GMR_DATASET_SMPLX=host`` (one gmr_smplx_frames call per clip), alternating, and the written files compared byte for byte.
 
-    python tools/smplx_dataset_probe.py [nclips] [--reps N] [--out FILE]
+    python tools/smplx_dataset_probe.py [nclips] [--reps N] [--out FILE] [--ab smplx|heights]
+
+``--ab heights`` alternates the default (one solver and one IK job per batch, the files' heights as per-stream scale rows) with
+``GMR_DATASET_HEIGHTS=groups`` (one solver and job per height) instead.
 
 The tree: two genders (two synthetic body models written like tests/test_smplx_frames.py::_synthetic_model builds one), a few
 hundred distinct betas, 120 / 60 / 30 fps, 80 .. 2 000 frames per file.
@@ -64,10 +67,12 @@ def make_tree(src, nclips, subjects=300, seed=0):
 
 def run_cli(src, tgt, models, path):
     env = dict(os.environ, PYTHONPATH=ROOT)
-    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "GMR_DATASET_SMPLX"):
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "GMR_DATASET_SMPLX", "GMR_DATASET_HEIGHTS"):
         env.pop(k, None)
     if path == "host":
         env["GMR_DATASET_SMPLX"] = "host"
+    if path == "groups":
+        env["GMR_DATASET_HEIGHTS"] = "groups"
     t0 = time.perf_counter()
     r = subprocess.run([sys.executable, "-m", "general_motion_retargeting_amd.dataset", "--source", "smplx", "--src_folder", src,
                         "--tgt_folder", tgt, "--smplx_folder", models, "--hard_motions", "--robot", "unitree_g1", "--quiet"],
@@ -95,6 +100,7 @@ def main():
     nclips = int(args[0]) if args and args[0].isdigit() else 1200
     reps = int(args[args.index("--reps") + 1]) if "--reps" in args else 2
     out_file = args[args.index("--out") + 1] if "--out" in args else None
+    paths = {"smplx": ("device", "host"), "heights": ("merged", "groups")}[args[args.index("--ab") + 1] if "--ab" in args else "smplx"]
     base = os.environ.get("GMR_DS_PROBE_DIR", "/tmp/gmr_smplx_ds_probe")
     shutil.rmtree(base, ignore_errors=True)
     src, models = os.path.join(base, "src"), os.path.join(base, "models")
@@ -104,14 +110,14 @@ def main():
     out = {"clips": nclips, "output_frames": frames, "tree_seconds": time.perf_counter() - t0, "runs": []}
     digests = {}
     for rep in range(reps):
-        for path in ("device", "host"):            # alternating: other work shares the host
+        for path in paths:                         # alternating: other work shares the host
             tgt = os.path.join(base, f"{path}_{rep}")
             run = run_cli(src, tgt, models, path)
             run["files_written"], run["sha256_of_tree"] = tree_digest(tgt)
             digests.setdefault(path, set()).add(run["sha256_of_tree"])
             out["runs"].append(run)
             shutil.rmtree(tgt, ignore_errors=True)
-    out["both_paths_wrote_the_same_bytes"] = len(digests["device"] | digests["host"]) == 1
+    out["both_paths_wrote_the_same_bytes"] = len(digests[paths[0]] | digests[paths[1]]) == 1
     shutil.rmtree(base, ignore_errors=True)
     print(json.dumps(out))
     if out_file:
