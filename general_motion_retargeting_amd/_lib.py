@@ -7,6 +7,7 @@ import importlib.util
 import math
 import os
 import sys
+from typing import NamedTuple
 
 import numpy as np
 
@@ -512,18 +513,37 @@ def retarget_group(jobs, flags: int = 0, slices: int = 0, out_pinned: bool = Fal
     return outs
 
 
+class DevJob(NamedTuple):
+    """One job of :func:`retarget_group_dev`: the fields of ``gmr_job_t`` a device caller fills, device pointers
+    (DeviceBuffer or raw).  ``scale``: f64 [S][nhuman] per-stream human scale tables, or None for the solver's own."""
+    solver: object
+    S: int
+    T: int
+    q0: object
+    human: object
+    len: object
+    q_out: object
+    nsolve: object
+    status: object
+    scale: object = None
+
+
+def dev_job(job, i: int = 0) -> DevJob:
+    """``job`` (a :class:`DevJob` or any sequence of its first 9 or all 10 fields) as a :class:`DevJob`"""
+    if len(job) not in (9, 10):
+        raise ValueError(f"job {i}: 9 or 10 elements needed, got {len(job)}")
+    return job if isinstance(job, DevJob) else DevJob(*job)
+
+
 def retarget_group_dev(jobs, flags: int = 0, stream=None, window=None):
-    """``gmr_retarget_group_dev``: ``jobs`` = list of ``(solver, S, T, d_q0, d_human, d_len, d_q_out, d_nsolve, d_status)``
-    with device pointers (DeviceBuffer or raw), optionally followed by a tenth element ``d_scale`` (f64 [S][nhuman] per-stream human
-    scale tables, unchecked: the values are the caller's responsibility); asynchronous on ``stream``.  ``window=(t_begin, t_end)``: only those frames of
+    """``gmr_retarget_group_dev``: ``jobs`` = list of :class:`DevJob` (or plain sequences of its first 9 or all 10 fields; the
+    scale tables are unchecked: the values are the caller's responsibility); asynchronous on ``stream``.  ``window=(t_begin, t_end)``: only those frames of
     every stream (``gmr_retarget_group_window_dev``; consecutive windows on one stream, starting at 0)."""
     arr = (Job * max(len(jobs), 1))()
     for i, job in enumerate(jobs):
-        if len(job) not in (9, 10):
-            raise ValueError(f"job {i}: 9 or 10 elements needed, got {len(job)}")
-        sol, S, T, d_q0, d_h, d_len, d_qo, d_ns, d_st = job[:9]
-        arr[i] = Job(sol.handle.value, int(S), int(T), _addr(d_q0), _addr(d_h), _addr(d_len), _addr(d_qo), _addr(d_ns),
-                     _addr(d_st), None, None, _addr(job[9]) if len(job) == 10 else None)
+        j = dev_job(job, i)
+        arr[i] = Job(j.solver.handle.value, int(j.S), int(j.T), _addr(j.q0), _addr(j.human), _addr(j.len), _addr(j.q_out),
+                     _addr(j.nsolve), _addr(j.status), None, None, _addr(j.scale))
     if window is None:
         check(lib().gmr_retarget_group_dev(C.cast(arr, C.c_void_p), len(jobs), int(flags), _s(stream)))
     else:

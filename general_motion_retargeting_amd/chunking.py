@@ -205,8 +205,8 @@ class ChunkRunner:
 
     def run(self, launch: Sequence[tuple], lens: Sequence[np.ndarray], specs: Sequence[Optional[ChunkSpec]], flags: int, stream,
             timed: bool = False) -> List[Optional[List[Dict]]]:
-        """``launch[i]`` = ``(solver, S, T, d_q0, d_human, d_len, d_q_out, d_nsolve, d_status)`` as :func:`_lib.retarget_group_dev`
-        takes them (clip-major device buffers), ``lens[i]`` the host copy of its clip lengths, ``specs[i]`` its
+        """``launch[i]`` = a :class:`_lib.DevJob` (or the plain tuple of its fields) as :func:`_lib.retarget_group_dev` takes
+        them (clip-major device buffers), ``lens[i]`` the host copy of its clip lengths, ``specs[i]`` its
         :class:`ChunkSpec` or ``None`` (that job is launched as it is, in the group of pass 0).  Everything goes to ``stream``;
         returns one list of per-clip reports per job (``None`` for a job without a spec).  ``timed``: record device events
         around the four steps of every pass (``pass_ms``)."""
@@ -220,14 +220,15 @@ class ChunkRunner:
         h2d = lambda dst, src: _lib.check(L.gmr_memcpy_h2d(dst.ptr, _lib._ptr(src), src.nbytes, st))     # noqa: E731
         d2h = lambda dst, src, n: _lib.check(L.gmr_memcpy_d2h(_lib._ptr(dst), src.ptr, n, st))            # noqa: E731
         mark = lambda i: ev[i].record(stream) if ev else None                                              # noqa: E731
+        launch = [_lib.dev_job(job, i) for i, job in enumerate(launch)]
         jobs = []
-        for i, (ln, spec) in enumerate(zip(launch, specs)):
+        for i, (job, spec) in enumerate(zip(launch, specs)):
             if spec is None:
                 continue
-            sol, S, T = ln[0], int(ln[1]), max(int(ln[2]), 1)
+            sol, S, T = job.solver, int(job.S), max(int(job.T), 1)
             p = plan(np.asarray(lens[i], dtype=np.int32), spec.frames, spec.warmup)
             n, Tc, nq, nh = p.nchunk, p.Tc, sol.nq, sol.nhuman
-            j = {"i": i, "spec": spec, "plan": p, "S": S, "T": T, "n": n, "sol": sol}
+            j = {"i": i, "src": job, "spec": spec, "plan": p, "S": S, "T": T, "n": n, "sol": sol}
             for name, nbytes in (("chunk", n * 16), ("first", (S + 1) * 4), ("human_c", n * Tc * nh * 56), ("len_c", n * 4),
                                  ("q0_c", n * nq * 8), ("q_out_c", n * Tc * nq * 8), ("nsolve_c", n * Tc * 8), ("status_c", n * 4),
                                  ("chunk_status", n * 4), ("q_seam", n * nq * 8), ("resid", n * 24), ("bad", n * 4), ("nbad", 4),
@@ -241,33 +242,30 @@ class ChunkRunner:
             jobs.append(j)
 
         def dims(j):
-            return j["S"], j["T"], j["sol"].nq, j["n"], j["plan"].Tc
+            return j["S"], j["T"], j["sol"].nq, j["n"], j["plan"].Tc, j["src"]
 
         def one_pass(active, mode, extra=()):
             mark(0)
             for j in active:
-                S, T, nq, n, Tc = dims(j)
+                S, T, nq, n, Tc, src = dims(j)
                 lst, nl = (j["bad"].ptr, int(j["h_nbad"][0])) if mode == REPAIR else (None, 0)
                 j["slots"] = nl if mode == REPAIR else n
-                ln = launch[j["i"]]
-                _lib.check(L.gmr_chunk_gather_dev(S, T, j["sol"].nhuman, nq, n, Tc, j["chunk"].ptr, lst, nl, mode, _lib._d(ln[4]), _lib._d(ln[3]),
-                                                  _lib._d(ln[6]), j["human_c"].ptr, j["len_c"].ptr, j["q0_c"].ptr, j["q_seam"].ptr, st))
+                _lib.check(L.gmr_chunk_gather_dev(S, T, j["sol"].nhuman, nq, n, Tc, j["chunk"].ptr, lst, nl, mode, _lib._d(src.human), _lib._d(src.q0),
+                                                  _lib._d(src.q_out), j["human_c"].ptr, j["len_c"].ptr, j["q0_c"].ptr, j["q_seam"].ptr, st))
             mark(1)
-            _lib.retarget_group_dev([(j["sol"], j["slots"], j["plan"].Tc, j["q0_c"], j["human_c"], j["len_c"], j["q_out_c"], j["nsolve_c"],
-                                      j["status_c"]) for j in active] + list(extra), flags, stream)
+            _lib.retarget_group_dev([_lib.DevJob(j["sol"], j["slots"], j["plan"].Tc, j["q0_c"], j["human_c"], j["len_c"], j["q_out_c"],
+                                                 j["nsolve_c"], j["status_c"]) for j in active] + list(extra), flags, stream)
             mark(2)
             for j in active:
-                S, T, nq, n, Tc = dims(j)
+                S, T, nq, n, Tc, src = dims(j)
                 lst, nl = (j["bad"].ptr, j["slots"]) if mode == REPAIR else (None, 0)
-                ln = launch[j["i"]]
                 _lib.check(L.gmr_chunk_stitch_dev(S, T, nq, n, Tc, j["chunk"].ptr, j["first"].ptr, lst, nl, mode, j["q_out_c"].ptr,
-                                                  j["nsolve_c"].ptr, j["status_c"].ptr, _lib._d(ln[6]), _lib._d(ln[7]), j["chunk_status"].ptr,
-                                                  _lib._d(ln[8]), j["q_seam"].ptr, j["warm"].ptr, st))
+                                                  j["nsolve_c"].ptr, j["status_c"].ptr, _lib._d(src.q_out), _lib._d(src.nsolve), j["chunk_status"].ptr,
+                                                  _lib._d(src.status), j["q_seam"].ptr, j["warm"].ptr, st))
             mark(3)
             for j in active:
-                S, T, nq, n, Tc = dims(j)
-                ln = launch[j["i"]]
-                _lib.check(L.gmr_chunk_seams_dev(S, T, nq, n, Tc, j["chunk"].ptr, j["first"].ptr, _lib._d(ln[6]), j["q_seam"].ptr,
+                S, T, nq, n, Tc, src = dims(j)
+                _lib.check(L.gmr_chunk_seams_dev(S, T, nq, n, Tc, j["chunk"].ptr, j["first"].ptr, _lib._d(src.q_out), j["q_seam"].ptr,
                                                  j["chunk_status"].ptr, float(j["spec"].tol), j["resid"].ptr, j["bad"].ptr, j["nbad"].ptr,
                                                  j["seam_max"].ptr, st))
             mark(4)
@@ -320,7 +318,7 @@ def retarget_chunked_host(solver, human: np.ndarray, q0: np.ndarray, lens, flags
     d_q, d_ns, d_st = _lib.DeviceBuffer(max(S * T * solver.nq * 8, 8)), _lib.DeviceBuffer(max(S * T * 8, 8)), _lib.DeviceBuffer(max(S * 4, 8))
     for b in (d_q, d_ns, d_st):
         _lib.check(_lib.lib().gmr_memset(b.ptr, 0, b.nbytes, st.ptr))
-    reports, = runner.run([(solver, S, T, d_q0, d_h, d_len, d_q, d_ns, d_st)], [lens], [spec], flags, st, timed)
+    reports, = runner.run([_lib.DevJob(solver, S, T, d_q0, d_h, d_len, d_q, d_ns, d_st)], [lens], [spec], flags, st, timed)
     q_out = d_q.to_host((S, T, solver.nq), np.float64, st)
     nsolve = d_ns.to_host((S, T, 2), np.int32, st)
     status = d_st.to_host((S,), np.int32, st)

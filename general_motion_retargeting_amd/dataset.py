@@ -10,14 +10,18 @@ The SMPL-X script has both adjustments on, the BVH script both off (``bvh_to_rob
 """
 from __future__ import annotations
 
+import ctypes as C
+import dataclasses
+import functools
 import os
 import threading
+import time
 import weakref
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
-from . import _lib
+from . import _lib, chunking
 from .data_loader import motion_dict
 from .kinematics_model import KinematicsModel
 from .motion_retarget import GeneralMotionRetargeting
@@ -84,7 +88,6 @@ def postprocess_clips(qpos_list: Sequence[np.ndarray], km: KinematicsModel, fps:
 # ----------------------------------------------------------------------------------------------
 def post_path() -> str:
     """``"device"`` or ``"host"``: which post-processing the drivers take (environment switch ``GMR_DATASET_POST``)."""
-    from . import _lib
     if os.environ.get("GMR_DATASET_POST", "device").strip().lower() == "host":
         return "host"
     try:
@@ -144,7 +147,6 @@ class PinnedPool:
                 self._free.remove(owner)
         if owner is None:
             if self._alloc is None:
-                from . import _lib
                 self._alloc = _lib._PinnedOwner
             owner = self._alloc(need + need // 4)
             self.blocks_allocated += 1
@@ -161,6 +163,70 @@ class PinnedPool:
     def free_blocks(self) -> int:
         with self._lock:
             return len(self._free)
+
+
+@dataclasses.dataclass
+class BlockPlan:
+    """The output block of one :meth:`DevicePost.run` (:func:`plan_block`): which rows every clip gets, which post-processing
+    calls write them, and where the five arrays lie in the block's bytes."""
+    perms: List[Optional[np.ndarray]]     # per job: device position -> clip of the job (None: the job's own order)
+    dlens: List[np.ndarray]               # per job: the clip lengths in device order
+    spans: List[List[tuple]]              # per job: (first row, end row) of every clip, in device order
+    calls: List[tuple]                    # per post-processing call: (first job, first row, seg_start i32[clips of the call + 1])
+    rows: int
+    nclip: int
+    arrays: Dict[str, tuple]              # name -> (byte offset, bytes per row, dtype, shape)
+    total: int
+
+    def to_job_order(self, i: int, x):
+        """``x`` (one entry per clip of job i, in device order) in the job's own clip order"""
+        if self.perms[i] is None:
+            return x
+        inv = np.argsort(self.perms[i])
+        return x[inv] if isinstance(x, np.ndarray) else [x[k] for k in inv.tolist()]
+
+    def at(self, base: int, name: str, row: int = 0) -> C.c_void_p:
+        """the address of ``row`` of array ``name`` in a block that starts at ``base``"""
+        off, stride = self.arrays[name][:2]
+        return C.c_void_p(base + off + row * stride)
+
+    def views(self, buf):
+        """``(root_pos, root_rot, dof_pos, local_body_pos, status)`` of a host copy of the block: four views and a copy"""
+        v = [np.frombuffer(buf, dtype=dt, count=int(np.prod(shape)), offset=off).reshape(shape) for off, _, dt, shape in self.arrays.values()]
+        return v[0], v[1], v[2], v[3], v[4].copy()
+
+
+def plan_block(lens_per_job: Sequence, perms: Sequence, ndof: int, nb: int) -> BlockPlan:
+    """The sources of one post-processing call are at most 8 jobs: more jobs -> more calls, each over its own dense range of
+    rows that starts at a multiple of 4 (so that its ``local_body_pos`` starts 16-byte aligned).  ``perms[i]`` orders the clips
+    of job i on the device (raw BVH jobs: the clips of one topology are consecutive streams), ``None`` leaves them."""
+    dlens = [np.asarray(l, dtype=np.int64) if p is None else np.asarray(l, dtype=np.int64)[p] for l, p in zip(lens_per_job, perms)]
+    calls, spans, row = [], [], 0
+    for c0 in range(0, len(dlens), 8):
+        seg = [0]
+        for lens in dlens[c0:c0 + 8]:
+            starts = row + seg[-1] + np.concatenate([[0], np.cumsum(lens)])
+            spans.append([(int(a), int(b)) for a, b in zip(starts[:-1], starts[1:])])
+            seg.extend((seg[-1] + np.cumsum(lens)).tolist())
+        calls.append((c0, row, np.asarray(seg, dtype=np.int32)))
+        row = (row + seg[-1] + 3) // 4 * 4
+    rows, nclip = max(row, 1), sum(len(l) for l in dlens)
+    arrays, total = {}, 0
+    for name, dt, shape in (("root_pos", np.float64, (rows, 3)), ("root_rot", np.float64, (rows, 4)), ("dof_pos", np.float64, (rows, ndof)),
+                            ("local_body_pos", np.float32, (rows, nb, 3)), ("status", np.int32, (nclip,))):
+        stride = int(np.prod(shape[1:])) * np.dtype(dt).itemsize
+        arrays[name] = (total, stride, dt, shape)
+        total += _lib.align256(shape[0] * stride)
+    return BlockPlan(list(perms), dlens, spans, calls, rows, nclip, arrays, total)
+
+
+def _bvh_perm(job: Dict) -> Optional[np.ndarray]:
+    """a raw BVH job's clips in the order they take on the device: topology by topology, then the packed ones"""
+    if "bvh" not in job:
+        return None
+    perm = np.array([i for g in job["bvh"] for i in g["clips"]] + [i for i, _ in job.get("packed", ())], dtype=np.int64)
+    assert sorted(perm.tolist()) == list(range(len(job["lens"])))
+    return perm
 
 
 class DevicePost:
@@ -187,7 +253,7 @@ class DevicePost:
     def _stage_smplx(self, jobs: Sequence[Dict]):
         """The raw SMPL-X clips of all jobs that carry ``"smplx"``, per handle: one page-locked block (poses, translations, the
         two tables, flags, rest joints and the per-clip destination addresses inside the jobs' ``human_{i}`` device buffers)
-        that goes up in ONE copy.  Returns ``([(handle, nclip, B, device block, offsets, staging)], {job index: human buffer})``."""
+        that goes up in ONE copy.  Returns ``({job index: human buffer}, H2D copies, frame calls)`` like the other two stages."""
         groups: Dict[int, tuple] = {}
         d_human: Dict[int, object] = {}
         for i, j in enumerate(jobs):
@@ -198,7 +264,7 @@ class DevicePost:
             assert len(sx["clips"]) == S and sx["handle"].rows == sol.nhuman and sx["handle"].batch_takes
             d_human[i] = self._d(f"human_{i}", S * T * sol.nhuman * 56)
             groups.setdefault(id(sx["handle"]), (sx["handle"], []))[1].extend((i, k, T, e) for k, e in enumerate(sx["clips"]))
-        calls = []
+        copies, calls = [], []
         for gi, (h, members) in enumerate(groups.values()):
             n, frame_bytes = len(members), h.rows * 56
             B = sum(e["N"] for _, _, _, e in members)
@@ -222,8 +288,10 @@ class DevicePost:
                 v["seg"][m + 1] = a
                 v["nout"][m], v["align"][m], v["jrest"][m] = e["nout"], e["align"], e["j_rest"]
                 v["tab"][m] = d_human[i].ptr.value + k * T * frame_bytes
-            calls.append((h, n, B, self._d(f"smplx_in_{gi}", total), offs, stage))
-        return calls, d_human
+            d_in = self._d(f"smplx_in_{gi}", total)
+            copies.append((d_in.ptr, stage))
+            calls.append(functools.partial(h.batch_frames_dev, n, B, *(C.c_void_p(d_in.ptr.value + offs[k]) for k, _, _ in fields)))
+        return d_human, copies, calls
 
     def run(self, jobs: Sequence[Dict], km: KinematicsModel, ik_flags: int = 0, height_adjust: bool = True,
             root_origin_offset: bool = True, ground_offset: float = 0.0, timing: Optional[Dict[str, float]] = None, chunk=None,
@@ -246,176 +314,222 @@ class DevicePost:
         call per handle writes every job's ``human`` through a table of per-clip addresses.  Returns ``(root_pos, root_rot, dof_pos, local_body_pos, spans, status)``:
         the four arrays are views of one pool block, ``spans[j][k] = (a, b)`` are the rows of clip k of job j, ``status[j]``
         the IK status words of job j."""
-        import ctypes as C
-        from . import _lib
-        L = _lib.lib()
         if self._stream is None:
             self._stream = _lib.Stream()
             self._events = [_lib.Event() for _ in range(6)]
         st, ev = self._stream, self._events
         fk = km.hip_handle
-        nb, ndof, nq = fk.nbody, fk.ndof, fk.ndof + 7
-        # the sources of one post-processing call are at most 8 jobs: more jobs -> more calls, each over its own dense range
-        # of rows that starts at a multiple of 4 (so that its local_body_pos starts 16-byte aligned)
-        # raw BVH jobs: the clips of one topology are consecutive streams of the batch (one gmr_bvh_frames_dev call each)
-        perms, dlens = [], []
-        for j in jobs:
-            lens = np.asarray(j["lens"], dtype=np.int64)
-            perm = None
-            if "bvh" in j:
-                perm = np.array([i for g in j["bvh"] for i in g["clips"]] + [i for i, _ in j.get("packed", ())], dtype=np.int64)
-                assert sorted(perm.tolist()) == list(range(len(lens)))
-                lens = lens[perm]
-            perms.append(perm)
-            dlens.append(lens)
-        chunks, spans, row = [], [], 0
-        for c0 in range(0, len(jobs), 8):
-            seg = [0]
-            for lens in dlens[c0:c0 + 8]:
-                starts = row + seg[-1] + np.concatenate([[0], np.cumsum(lens)])
-                spans.append([(int(a), int(b)) for a, b in zip(starts[:-1], starts[1:])])
-                seg.extend((seg[-1] + np.cumsum(lens)).tolist())
-            chunks.append((c0, row, np.asarray(seg, dtype=np.int32)))
-            row = (row + seg[-1] + 3) // 4 * 4
-        Bp, nclip = max(row, 1), sum(len(j["lens"]) for j in jobs)
-        o_rp = 0
-        o_rr = o_rp + _lib.align256(Bp * 24)
-        o_dp = o_rr + _lib.align256(Bp * 32)
-        o_lb = o_dp + _lib.align256(Bp * ndof * 8)
-        o_st = o_lb + _lib.align256(Bp * nb * 12)
-        total = o_st + _lib.align256(nclip * 4)
-        d_out = self._d("out", total)
+        block = plan_block([j["lens"] for j in jobs], [_bvh_perm(j) for j in jobs], fk.ndof, fk.nbody)
+        d_out = self._d("out", block.total)
         base = d_out.ptr.value
-        sx_calls, sx_human = self._stage_smplx(jobs)
+        sx_human, sx_copies, sx_calls = self._stage_smplx(jobs)
         ev[0].record(st)
-        launch, sources, d_status, clip, bvh_calls = [], [], [], 0, []
-        h2d = lambda dst, src: _lib.check(L.gmr_memcpy_h2d(dst, src.ctypes.data_as(C.c_void_p), src.nbytes, st.ptr))   # noqa: E731
+        launch, bvh_calls, clip = [], [], 0
         for i, j in enumerate(jobs):
-            sol = j["solver"]
             if "bvh" in j:
-                S, T, copies = len(dlens[i]), max(int(j["T"]), 1), []
-                frame_bytes = sol.nhuman * 7 * 8
-                d_h = self._d(f"human_{i}", S * T * frame_bytes)       # (rows at or beyond a clip's length stay stale: never read)
-                pos = 0
-                for gi, g in enumerate(j["bvh"]):
-                    rows, n = g["rows"], len(g["clips"])
-                    assert rows.dtype == np.float64 and rows.flags.c_contiguous and rows.shape[1] == g["handle"].ncol
-                    seg = self.pinned(f"bvhseg_{i}_{gi}", (n + 1,), np.int32)
-                    seg[0] = 0
-                    seg[1:] = np.cumsum(g["lens"])
-                    assert int(seg[-1]) == rows.shape[0] and len(g["lens"]) == n
-                    off = self.pinned(f"bvhoff_{i}_{gi}", (n, g["handle"].J, 3), np.float64)
-                    off[:] = g["offsets"]
-                    d_rows, d_seg, d_off = (self._d(f"bvh{k}_{i}_{gi}", a.nbytes) for k, a in (("rows", rows), ("seg", seg), ("off", off)))
-                    copies += [(d_rows.ptr, rows), (d_seg.ptr, seg), (d_off.ptr, off)]
-                    bvh_calls.append((g["handle"], n, rows.shape[0], d_rows, d_seg, d_off, T, C.c_void_p(d_h.ptr.value + pos * T * frame_bytes)))
-                    pos += n
-                packed = j.get("packed", ())
-                if packed:      # clips the device path does not take, computed on the host: straight into their padded rows
-                    stage = self.pinned(f"bvhpacked_{i}", (sum(len(p) for _, p in packed), sol.nhuman, 7), np.float64)
-                    a = 0
-                    for _, p in packed:
-                        stage[a:a + len(p)] = p
-                        if len(p):
-                            copies.append((C.c_void_p(d_h.ptr.value + pos * T * frame_bytes), stage[a:a + len(p)]))
-                        a += len(p)
-                        pos += 1
+                d_h, copies, calls = self._stage_bvh(i, j, block.dlens[i])
             elif "smplx" in j:
-                S, T, copies = len(dlens[i]), max(int(j["T"]), 1), []
-                d_h = sx_human[i]                                      # (frames at or beyond a clip's nout stay stale: never read)
+                d_h, copies, calls = sx_human[i], [], []          # (frames at or beyond a clip's nout stay stale: never read)
             else:
-                human = j["human"]
-                S, T = human.shape[:2]
-                assert human.dtype == np.float64 and human.flags.c_contiguous and human.shape[2:] == (sol.nhuman, 7)
-                d_h = self._d(f"human_{i}", human.nbytes)
-                copies = [(d_h.ptr, human)]
-            q0 = self.pinned(f"q0_{i}", (S, sol.nq), np.float64)
-            q0[:] = j["q0"]
-            lens = self.pinned(f"len_{i}", (S,), np.int32)
-            lens[:] = dlens[i]
-            d_q0, d_len = self._d(f"q0_{i}", q0.nbytes), self._d(f"len_{i}", lens.nbytes)
-            d_q, d_ns = self._d(f"q_out_{i}", S * T * sol.nq * 8), self._d(f"nsolve_{i}", S * T * 8)
-            d_sc = None
-            if j.get("scales") is not None:
-                rows = _lib.check_scales(j["scales"], S, sol.nhuman, f"job {i}: scales")
-                sc = self.pinned(f"scale_{i}", (S, sol.nhuman), np.float64)
-                sc[:] = rows if perms[i] is None else rows[perms[i]]
-                d_sc = self._d(f"scale_{i}", sc.nbytes)
-                copies.append((d_sc.ptr, sc))
-            for dst, src in copies + [(d_q0.ptr, q0), (d_len.ptr, lens)]:
-                h2d(dst, src)
-            d_status.append(C.c_void_p(base + o_st + 4 * clip))
-            launch.append((sol, S, T, d_q0, d_h, d_len, d_q, d_ns, d_status[-1]) + (() if d_sc is None else (d_sc,)))
-            sources.append((S, T, d_q, d_len))
-            clip += S
-        for _, _, _, d_in, _, stage in sx_calls:
-            h2d(d_in.ptr, stage)
+                d_h, copies, calls = self._stage_packed(i, j)
+            job, more = self._stage_job(i, j, d_h, block, block.at(base, "status", clip))
+            for dst, src in copies + more:
+                self._h2d(dst, src)
+            launch.append(job)
+            bvh_calls += calls
+            clip += job.S
+        for dst, src in sx_copies:
+            self._h2d(dst, src)
         ev[1].record(st)
-        for h, n, B, d_rows, d_seg, d_off, T, d_dst in bvh_calls:
-            h.frames_dev(n, B, d_rows, d_seg, d_off, T, d_dst, st)
-        for h, n, B, d_in, offs, _ in sx_calls:
-            at = lambda k: C.c_void_p(d_in.ptr.value + offs[k])          # noqa: E731
-            h.batch_frames_dev(n, B, at("ro"), at("pb"), at("tr"), at("seg"), at("nout"), at("align"), at("jrest"), at("tab"), st)
+        for call in bvh_calls + sx_calls:
+            call(st)
         ev[5].record(st)
-        from . import chunking
-        total_frames = int(sum(int(l.sum()) for l in dlens))
-        specs = [chunking.resolve_any(chunk, l, total_frames) for l in dlens]
-        self.chunk_reports = [None] * len(jobs)
-        if any(sp is not None for sp in specs):
-            if any(len(job) > 9 for job in launch):
-                raise ValueError("per-clip scales do not go with a chunk spec that takes effect: run the heights as groups")
-            if self._chunker is None:
-                self._chunker = chunking.ChunkRunner()
-            reports = self._chunker.run(launch, dlens, specs, ik_flags, st)
-            for i, r in enumerate(reports):        # back to the job's own clip order
-                self.chunk_reports[i] = r if (r is None or perms[i] is None) else [r[k] for k in np.argsort(perms[i]).tolist()]
-        else:
-            _lib.retarget_group_dev(launch, ik_flags, st)
+        self.chunk_reports = self._ik(launch, block, chunk, ik_flags)
         ev[2].record(st)
-        for n, (c0, r0, seg) in enumerate(chunks):
-            hseg = self.pinned(f"seg_{n}", seg.shape, np.int32)
-            hseg[:] = seg
-            d_seg = self._d(f"seg_{n}", seg.nbytes)
-            _lib.check(L.gmr_memcpy_h2d(d_seg.ptr, hseg.ctypes.data_as(C.c_void_p), seg.nbytes, st.ptr))
-            fk.postprocess_clips_dev(sources[c0:c0 + 8], d_seg, len(seg) - 1, int(seg[-1]), C.c_void_p(base + o_rp + r0 * 24),
-                                     C.c_void_p(base + o_rr + r0 * 32), C.c_void_p(base + o_dp + r0 * ndof * 8),
-                                     C.c_void_p(base + o_lb + r0 * nb * 12), None, height_adjust, root_origin_offset, ground_offset, st)
+        self._post(block, base, launch, fk, height_adjust, root_origin_offset, ground_offset)
         ev[3].record(st)
-        self.library = None
-        if library is not None:
-            # the block is clip-contiguous from row 0 when one post-processing call covered it, in the jobs' own clip order
-            if len(chunks) != 1 or any(p is not None and not np.array_equal(p, np.arange(len(p))) for p in perms):
-                raise ValueError("a motion library takes the clips of at most 8 jobs in the order they were handed over")
-            from .motion_library import MotionLibrary
-            names = km.body_names
-            self.library = MotionLibrary.from_device(
-                chunks[0][2], np.concatenate([np.asarray(f, dtype=np.float64).reshape(-1) for f in library["fps"]]), ndof, nb,
-                C.c_void_p(base + o_rp), C.c_void_p(base + o_rr), C.c_void_p(base + o_dp), C.c_void_p(base + o_lb),
-                ang_vel=library.get("ang_vel", "world"), stream=st, link_body_lists=[names] * nclip)
-            self.library._kinematics = km         # the robot of these clips: body_state() needs no kinematics argument
-        buf = self.pool.take(total)
-        # (the address, not ctypes.cast: a cast leaves the buffer referring to itself, and only the cycle collector would
-        #  hand the block back)
-        _lib.check(L.gmr_memcpy_d2h(C.c_void_p(C.addressof(buf)), d_out.ptr, total, st.ptr))
+        self.library = self._library(block, base, km, library)
+        buf = self._read_back(block, d_out)
         ev[4].record(st)
         st.sync()
         if timing is not None:
             for k, a, b in (("h2d", 0, 1), ("frames", 1, 5), ("ik", 5, 2), ("post", 2, 3), ("d2h", 3, 4)):
                 if k != "frames" or bvh_calls or sx_calls:
                     timing[k] = timing.get(k, 0.0) + ev[a].elapsed_ms(ev[b]) * 1e-3
-        view = lambda off, dtype, shape: np.frombuffer(buf, dtype=dtype, count=int(np.prod(shape)), offset=off).reshape(shape)   # noqa: E731
-        status_all = view(o_st, np.int32, (nclip,)).copy()
-        status, clip = [], 0
-        for i, j in enumerate(jobs):
-            stt = status_all[clip:clip + len(j["lens"])]
-            clip += len(j["lens"])
-            if perms[i] is not None:          # back to the job's own clip order
-                inv = np.empty_like(perms[i])
-                inv[perms[i]] = np.arange(len(inv))
-                stt, spans[i] = stt[inv], [spans[i][p] for p in inv.tolist()]
-            status.append(stt)
-        return (view(o_rp, np.float64, (Bp, 3)), view(o_rr, np.float64, (Bp, 4)), view(o_dp, np.float64, (Bp, ndof)),
-                view(o_lb, np.float32, (Bp, nb, 3)), spans, status)
+        rp, rr, dp, lbp, status = block.views(buf)
+        first = np.cumsum([0] + [len(l) for l in block.dlens])
+        return (rp, rr, dp, lbp, [block.to_job_order(i, sp) for i, sp in enumerate(block.spans)],
+                [block.to_job_order(i, status[a:b]) for i, (a, b) in enumerate(zip(first[:-1], first[1:]))])
+
+    def _h2d(self, dst, src: np.ndarray) -> None:
+        _lib.check(_lib.lib().gmr_memcpy_h2d(dst, src.ctypes.data_as(C.c_void_p), src.nbytes, self._stream.ptr))
+
+    def _stage_packed(self, i: int, j: Dict):
+        """job i with its frames packed on the host: one copy of the padded batch"""
+        human, sol = j["human"], j["solver"]
+        assert human.dtype == np.float64 and human.flags.c_contiguous and human.shape[2:] == (sol.nhuman, 7)
+        d_h = self._d(f"human_{i}", human.nbytes)
+        return d_h, [(d_h.ptr, human)], []
+
+    def _stage_bvh(self, i: int, j: Dict, dlens: np.ndarray):
+        """job i of raw BVH clips: per topology the ragged rows, their segment starts and joint offsets go up and one
+        ``gmr_bvh_frames_dev`` call writes the clips' padded frames; clips packed on the host go straight into theirs"""
+        sol, S, T, copies, calls = j["solver"], len(dlens), max(int(j["T"]), 1), [], []
+        frame_bytes = sol.nhuman * 7 * 8
+        d_h = self._d(f"human_{i}", S * T * frame_bytes)       # (rows at or beyond a clip's length stay stale: never read)
+        pos = 0
+        for gi, g in enumerate(j["bvh"]):
+            rows, n = g["rows"], len(g["clips"])
+            assert rows.dtype == np.float64 and rows.flags.c_contiguous and rows.shape[1] == g["handle"].ncol
+            seg = self.pinned(f"bvhseg_{i}_{gi}", (n + 1,), np.int32)
+            seg[0] = 0
+            seg[1:] = np.cumsum(g["lens"])
+            assert int(seg[-1]) == rows.shape[0] and len(g["lens"]) == n
+            off = self.pinned(f"bvhoff_{i}_{gi}", (n, g["handle"].J, 3), np.float64)
+            off[:] = g["offsets"]
+            d_rows, d_seg, d_off = (self._d(f"bvh{k}_{i}_{gi}", a.nbytes) for k, a in (("rows", rows), ("seg", seg), ("off", off)))
+            copies += [(d_rows.ptr, rows), (d_seg.ptr, seg), (d_off.ptr, off)]
+            calls.append(functools.partial(g["handle"].frames_dev, n, rows.shape[0], d_rows, d_seg, d_off, T,
+                                           C.c_void_p(d_h.ptr.value + pos * T * frame_bytes)))
+            pos += n
+        packed = j.get("packed", ())
+        if packed:      # clips the device path does not take, computed on the host
+            stage = self.pinned(f"bvhpacked_{i}", (sum(len(p) for _, p in packed), sol.nhuman, 7), np.float64)
+            a = 0
+            for _, p in packed:
+                stage[a:a + len(p)] = p
+                if len(p):
+                    copies.append((C.c_void_p(d_h.ptr.value + pos * T * frame_bytes), stage[a:a + len(p)]))
+                a += len(p)
+                pos += 1
+        return d_h, copies, calls
+
+    def _stage_job(self, i: int, j: Dict, d_h, block: BlockPlan, d_status):
+        """what every kind of job needs besides its frames: start poses, clip lengths (device order), the IK outputs and the
+        scale rows it may carry.  Returns ``(DevJob, H2D copies)``."""
+        sol, dlens = j["solver"], block.dlens[i]
+        S, T = j["human"].shape[:2] if "human" in j else (len(dlens), max(int(j["T"]), 1))
+        q0 = self.pinned(f"q0_{i}", (S, sol.nq), np.float64)
+        q0[:] = j["q0"]
+        lens = self.pinned(f"len_{i}", (S,), np.int32)
+        lens[:] = dlens
+        d_q0, d_len = self._d(f"q0_{i}", q0.nbytes), self._d(f"len_{i}", lens.nbytes)
+        d_q, d_ns = self._d(f"q_out_{i}", S * T * sol.nq * 8), self._d(f"nsolve_{i}", S * T * 8)
+        copies, d_sc = [], None
+        if j.get("scales") is not None:
+            rows = _lib.check_scales(j["scales"], S, sol.nhuman, f"job {i}: scales")
+            sc = self.pinned(f"scale_{i}", (S, sol.nhuman), np.float64)
+            sc[:] = rows if block.perms[i] is None else rows[block.perms[i]]
+            d_sc = self._d(f"scale_{i}", sc.nbytes)
+            copies.append((d_sc.ptr, sc))
+        return _lib.DevJob(sol, S, T, d_q0, d_h, d_len, d_q, d_ns, d_status, d_sc), copies + [(d_q0.ptr, q0), (d_len.ptr, lens)]
+
+    def _ik(self, launch: List, block: BlockPlan, chunk, ik_flags: int) -> List:
+        """the IK launch of all jobs, chunked where the spec takes effect; returns the chunk reports per job, in job order"""
+        total_frames = int(sum(int(l.sum()) for l in block.dlens))
+        specs = [chunking.resolve_any(chunk, l, total_frames) for l in block.dlens]
+        if all(sp is None for sp in specs):
+            _lib.retarget_group_dev(launch, ik_flags, self._stream)
+            return [None] * len(launch)
+        if any(job.scale is not None for job in launch):
+            raise ValueError("per-clip scales do not go with a chunk spec that takes effect: run the heights as groups")
+        if self._chunker is None:
+            self._chunker = chunking.ChunkRunner()
+        reports = self._chunker.run(launch, block.dlens, specs, ik_flags, self._stream)
+        return [r if r is None else block.to_job_order(i, r) for i, r in enumerate(reports)]
+
+    def _post(self, block: BlockPlan, base: int, launch: List, fk, height_adjust: bool, root_origin_offset: bool, ground_offset: float):
+        sources = [(job.S, job.T, job.q_out, job.len) for job in launch]
+        for n, (c0, r0, seg) in enumerate(block.calls):
+            hseg = self.pinned(f"seg_{n}", seg.shape, np.int32)
+            hseg[:] = seg
+            d_seg = self._d(f"seg_{n}", seg.nbytes)
+            self._h2d(d_seg.ptr, hseg)
+            fk.postprocess_clips_dev(sources[c0:c0 + 8], d_seg, len(seg) - 1, int(seg[-1]), block.at(base, "root_pos", r0),
+                                     block.at(base, "root_rot", r0), block.at(base, "dof_pos", r0), block.at(base, "local_body_pos", r0),
+                                     None, height_adjust, root_origin_offset, ground_offset, self._stream)
+
+    def _library(self, block: BlockPlan, base: int, km: KinematicsModel, library: Optional[Dict]):
+        if library is None:
+            return None
+        # the block is clip-contiguous from row 0 when one post-processing call covered it, in the jobs' own clip order
+        if len(block.calls) != 1 or any(p is not None and not np.array_equal(p, np.arange(len(p))) for p in block.perms):
+            raise ValueError("a motion library takes the clips of at most 8 jobs in the order they were handed over")
+        from .motion_library import MotionLibrary
+        fk = km.hip_handle
+        lib_ = MotionLibrary.from_device(
+            block.calls[0][2], np.concatenate([np.asarray(f, dtype=np.float64).reshape(-1) for f in library["fps"]]), fk.ndof, fk.nbody,
+            block.at(base, "root_pos"), block.at(base, "root_rot"), block.at(base, "dof_pos"), block.at(base, "local_body_pos"),
+            ang_vel=library.get("ang_vel", "world"), stream=self._stream, link_body_lists=[km.body_names] * block.nclip)
+        lib_._kinematics = km         # the robot of these clips: body_state() needs no kinematics argument
+        return lib_
+
+    def _read_back(self, block: BlockPlan, d_out):
+        """the whole block into a pool block, asynchronously; returns the buffer the views are taken of"""
+        buf = self.pool.take(block.total)
+        # (the address, not ctypes.cast: a cast leaves the buffer referring to itself, and only the cycle collector would
+        #  hand the block back)
+        _lib.check(_lib.lib().gmr_memcpy_d2h(C.c_void_p(C.addressof(buf)), d_out.ptr, block.total, self._stream.ptr))
+        return buf
+
+
+def _run_batch(jobs: Sequence[Dict], km: KinematicsModel, ik_flags: int, height_adjust: bool, root_origin_offset: bool, chunk,
+               library: Optional[str], timing: Optional[Dict[str, float]], post: Optional[DevicePost], outs=None):
+    """The tail of every driver: IK, status check, post-processing, motion dicts, motion library.  ``jobs`` as
+    :meth:`DevicePost.run` takes them, each with ``"idxs"`` (its clips' indices in the caller's order) and ``"fps"`` (per
+    clip); with a ``post`` everything runs on the device, without one through ``_lib.retarget_group`` (or the chunked host
+    entry) and :func:`postprocess_clips` (``"human"`` jobs only; ``outs()`` -> the page-locked outputs of the plain launch).
+    ``library``: ``None`` | ``"world"`` | ``"reference"``.  Returns ``(motions in the caller's order, library, chunk reports per job)``."""
+    from .motion_library import MotionLibrary
+    t0 = time.perf_counter()
+    fps = {i: f for j in jobs for i, f in zip(j["idxs"], j["fps"])}
+    out: List[Optional[Dict]] = [None] * len(fps)
+
+    def check(j, status):
+        if (status != 0).any():
+            raise RuntimeError(f"IK failed for clips {[j['idxs'][k] for k in np.nonzero(status)[0]]}")
+
+    def add(key: str, seconds: float):
+        if timing is not None:
+            timing[key] = timing.get(key, 0.0) + seconds
+
+    if post is not None:
+        rp, rr, dp, lbp, spans, status = post.run(jobs, km, ik_flags, height_adjust, root_origin_offset, 0.0, timing, chunk=chunk,
+                                                  library=None if library is None else
+                                                  {"fps": [list(j["fps"]) for j in jobs], "ang_vel": library})
+        t1 = time.perf_counter()
+        for j, sp, stt in zip(jobs, spans, status):
+            check(j, stt)
+            for i, (a, b) in zip(j["idxs"], sp):
+                out[i] = motion_dict(fps[i], rp[a:b], rr[a:b], dp[a:b], lbp[a:b], km.body_names)
+        add("dicts", time.perf_counter() - t1)
+        return out, post.library, post.chunk_reports
+    total_frames = int(sum(int(np.sum(j["lens"])) for j in jobs))
+    specs = [chunking.resolve_any(chunk, j["lens"], total_frames) for j in jobs]
+    results, reports = [None] * len(jobs), [None] * len(jobs)
+    plain = [n for n, sp in enumerate(specs) if sp is None]
+    if plain:
+        group = [{**jobs[n], "q0": np.broadcast_to(jobs[n]["q0"], (len(jobs[n]["lens"]), jobs[n]["solver"].nq))} for n in plain]
+        for n, r in zip(plain, _lib.retarget_group(group, ik_flags, 0, outs=outs() if outs is not None and len(plain) == len(jobs) else None)):
+            results[n] = r
+    for n, (j, sp) in enumerate(zip(jobs, specs)):
+        if sp is not None:
+            assert j.get("scales") is None          # (the slots of a chunk job are not streams)
+            *results[n], reports[n] = chunking.retarget_chunked_host(j["solver"], j["human"], j["q0"], j["lens"], ik_flags, sp)
+    t1 = time.perf_counter()
+    qpos: List[Optional[np.ndarray]] = [None] * len(out)
+    for j, (q, _, status) in zip(jobs, results):
+        check(j, status)
+        for k, i in enumerate(j["idxs"]):
+            qpos[i] = q[k, : j["lens"][k]]
+    out = postprocess_clips(qpos, km, [fps[i] for i in range(len(out))], height_adjust, root_origin_offset)
+    add("ik", t1 - t0)
+    add("post", time.perf_counter() - t1)
+    lib_ = None
+    if library is not None:      # (host post-processing: the arrays are on the host, so they go up once)
+        lib_ = MotionLibrary.from_motions(out, library)
+        lib_._kinematics = km
+    return out, lib_, reports
 
 
 class ClipRetargeter:
@@ -533,7 +647,6 @@ class ClipRetargeter:
         retargeter built with per-clip heights takes one).  A raw BVH clip (``lafan1.BvhRaw``) joins a batch whose
         frames are computed on the device (:func:`bvh_path`): only its rows are copied.  On the host path, for a file the
         device path does not take, or in a batch that already holds packed clips, its frames are computed here."""
-        import time
         from .utils import lafan1
         t0 = time.perf_counter()
         if height is not None:
@@ -570,82 +683,45 @@ class ClipRetargeter:
         return scale_rows(self.gmr._ik_config, self._hts[:S])
 
     def finish(self, fps: Sequence[float]) -> List[Dict]:
-        import time
-        from . import _lib
-        S, T, gmr = self._n, self._T, self.gmr
+        S = self._n
         if S == 0:
             return []
-        t1 = time.perf_counter()
-        sol = gmr.hip_solver
         lens = self._lens[:S].copy()
-        scales = self._scales(S)
-        if scales is not None:
-            from . import chunking
-            if chunking.resolve_any(self.chunk, lens) is not None:
-                raise ValueError("per-clip heights do not go with a chunk spec that takes effect: run the heights as groups")
-        if post_path() == "device":
-            return self._finish_device(fps, lens)
-        q0 = self._buf("q0", (S, sol.nq), np.float64)
-        q0[:] = gmr.model.qpos0
-        from . import chunking
-        spec = chunking.resolve_any(self.chunk, lens)
-        self.chunk_report = None
-        if spec is not None:
-            qpos, _, status, self.chunk_report = chunking.retarget_chunked_host(sol, self._human[:S], q0, lens, gmr._flags(self.offset_to_ground), spec)
-            chunking.summarize(self.chunk_report, self.chunk_summary)
-        else:
-            outs = [(self._buf("q_out", (S, T, sol.nq), np.float64), self._buf("nsolve", (S, T, 2), np.int32), np.zeros(S, np.int32))]
-            (qpos, _, status), = _lib.retarget_group([{"solver": sol, "human": self._human[:S], "q0": q0, "lens": lens, "scales": scales}],
-                                                     gmr._flags(self.offset_to_ground), 0, outs=outs)
-        t2 = time.perf_counter()
-        self._n = 0
-        if (status != 0).any():
-            raise RuntimeError(f"IK failed for clips {np.nonzero(status)[0].tolist()}")
-        if self._km is None:
-            self._km = KinematicsModel(gmr.xml_file)
-        out = postprocess_clips([qpos[i, : lens[i]] for i in range(S)], self._km, fps, self.height_adjust, self.root_origin_offset)
-        t3 = time.perf_counter()
-        for k, v in (("ik", t2 - t1), ("post", t3 - t2)):
-            self.timing[k] = self.timing.get(k, 0.0) + v
-        if self._library_mode is not None:      # (host post-processing: the arrays are on the host, so they go up once)
-            from .motion_library import MotionLibrary
-            self.library = MotionLibrary.from_motions(out, self._library_mode)
-            self.library._kinematics = self._km
-        return out
+        if self._per_clip and chunking.resolve_any(self.chunk, lens) is not None:
+            raise ValueError("per-clip heights do not go with a chunk spec that takes effect: run the heights as groups")
+        return self._finish_device(fps, lens) if post_path() == "device" else self._finish(fps, lens, None)
 
     def _finish_device(self, fps: Sequence[float], lens: np.ndarray) -> List[Dict]:
         """:meth:`finish` with the post-processing on the device: ``q_out`` and ``nsolve`` never cross the bus.  ``timing`` gets
         ``h2d`` / ``ik`` / ``post`` / ``d2h`` from device events of the one stream everything runs on (none of them overlaps
         another) and ``dicts``, the host time to wrap the views."""
-        import time
-        S, gmr = self._n, self.gmr
-        if self._km is None:
-            self._km = KinematicsModel(gmr.xml_file)
         if self._dev_post is None:
             self._dev_post = DevicePost()
+        return self._finish(fps, lens, self._dev_post)
+
+    def _finish(self, fps: Sequence[float], lens: np.ndarray, post: Optional[DevicePost]) -> List[Dict]:
+        """the batch as ONE job of :func:`_run_batch`, on the device with a ``post``"""
+        S, T, gmr = self._n, self._T, self.gmr
+        sol = gmr.hip_solver
+        if self._km is None:
+            self._km = KinematicsModel(gmr.xml_file)
+        job = {"solver": sol, "lens": lens, "q0": gmr.model.qpos0, "scales": self._scales(S), "idxs": list(range(S)), "fps": list(fps)[:S]}
         if self._raw_mode:
-            job = {"solver": gmr.hip_solver, "lens": lens, "q0": gmr.model.qpos0, "T": self._T, "packed": self._packed,
-                   "bvh": [{"handle": g["handle"], "rows": g["buf"][: g["used"]], "offsets": np.stack(g["offsets"]), "clips": g["clips"],
-                            "lens": g["lens"]} for g in self._raw.values()]}
+            job.update(T=T, packed=self._packed,
+                       bvh=[{"handle": g["handle"], "rows": g["buf"][: g["used"]], "offsets": np.stack(g["offsets"]), "clips": g["clips"],
+                             "lens": g["lens"]} for g in self._raw.values()])
         else:
-            job = {"solver": gmr.hip_solver, "human": self._human[:S], "lens": lens, "q0": gmr.model.qpos0}
-        job["scales"] = self._scales(S)
+            job["human"] = self._human[:S]
+        outs = None
+        if post is None:        # the start poses and the outputs of the plain launch stay in this object's page-locked memory
+            job["q0"] = self._buf("q0", (S, sol.nq), np.float64)
+            job["q0"][:] = gmr.model.qpos0
+            outs = lambda: [(self._buf("q_out", (S, T, sol.nq), np.float64), self._buf("nsolve", (S, T, 2), np.int32), np.zeros(S, np.int32))]   # noqa: E731
         self._n = 0
-        rp, rr, dp, lbp, spans, (status,) = self._dev_post.run([job], self._km, gmr._flags(self.offset_to_ground), self.height_adjust,
-                                                               self.root_origin_offset, 0.0, self.timing, chunk=self.chunk,
-                                                               library=None if self._library_mode is None else
-                                                               {"fps": [list(fps)[:S]], "ang_vel": self._library_mode})
-        self.library = self._dev_post.library
-        self.chunk_report = self._dev_post.chunk_reports[0]
+        out, self.library, (self.chunk_report,) = _run_batch([job], self._km, gmr._flags(self.offset_to_ground), self.height_adjust,
+                                                             self.root_origin_offset, self.chunk, self._library_mode, self.timing, post, outs)
         if self.chunk_report is not None:
-            from . import chunking
             chunking.summarize(self.chunk_report, self.chunk_summary)
-        if (status != 0).any():
-            raise RuntimeError(f"IK failed for clips {np.nonzero(status)[0].tolist()}")
-        t0 = time.perf_counter()
-        names = self._km.body_names
-        out = [motion_dict(fps[i], rp[a:b], rr[a:b], dp[a:b], lbp[a:b], names) for i, (a, b) in enumerate(spans[0])]
-        self.timing["dicts"] = self.timing.get("dicts", 0.0) + time.perf_counter() - t0
         return out
 
     def __call__(self, clips: Sequence, fps: Sequence[float]) -> List[Dict]:
@@ -705,7 +781,6 @@ def heights_groups_needed(chunk, lens) -> bool:
     """Whether a batch of these clip lengths whose heights would travel as scale rows has to run as one job per height
     instead: a chunk spec takes effect on it (some clip is longer than the spec's ``frames``).  The slots of a chunk job are
     not streams, and their scale rows are not gathered (DESIGN.md section 6g names that as the follow-up)."""
-    from . import chunking
     return chunking.resolve_any(chunk, np.asarray(lens, dtype=np.int64)) is not None
 
 
@@ -721,7 +796,6 @@ def retarget_mixed(groups: Sequence[Dict], offset_to_ground: bool = False, slice
     from the unscaled config and the heights travel as scale rows); arrays allocated with ``_lib.pinned_empty`` are copied asynchronously.
     Returns a list of ``(qpos[S,T,nq], nsolve[S,T,2], status[S])``.
     """
-    from . import _lib
     jobs, keep = [], []
     for g in groups:
         h = g.get("actual_human_height")
@@ -1194,11 +1268,8 @@ def retarget_smplx_loaded(raws: Sequence[Dict], smplx_body_model_path: str, tgt_
     ``gmr_smplx_frames`` call per clip and a padded upload -- the same bits.  ``timing`` accumulates the seconds of the stages.
     ``library`` (``True`` | ``"world"`` | ``"reference"``; default off): returns ``(motions, motion_library.MotionLibrary)`` as
     :func:`retarget_clips` does, the clips in the order of ``raws``; the batch must then be one job (the merged path)."""
-    import time
-    from . import _lib
     from .utils import smpl
     t0 = time.perf_counter()
-    from . import chunking
     from .ik_config import scale_rows
     packed, fps_of, height, bms = {}, {}, {}, {}
     for i, d in enumerate(raws):
@@ -1228,16 +1299,16 @@ def retarget_smplx_loaded(raws: Sequence[Dict], smplx_body_model_path: str, tgt_
             packed[i], fps_of[i] = smpl.smplx_frames_packed_fused(gmr_of[group_of[i]], d, bms[i], tgt_fps=tgt_fps)      # body model + alignment, one call
     t1 = time.perf_counter()
     dp = _smplx_device_post(any_g.xml_file) if device else None
-    jobs, members = [], []
+    jobs = []
     for n, (h, g) in enumerate(gmr_of.items()):
         idxs = [i for i in range(len(raws)) if group_of[i] == h]
         lens = np.array([packed[i]["nout"] if raw else packed[i].shape[0] for i in idxs], dtype=np.int32)
         T = max(int(lens.max()), 1)
-        members.append((idxs, lens))
-        scales = scale_rows(g._ik_config, [height[i] for i in idxs]) if merged else None
+        job = {"solver": g.hip_solver, "lens": lens, "q0": g.model.qpos0, "idxs": idxs, "fps": [fps_of[i] for i in idxs],
+               "scales": scale_rows(g._ik_config, [height[i] for i in idxs]) if merged else None}
+        jobs.append(job)
         if raw:
-            jobs.append({"solver": g.hip_solver, "T": T, "lens": lens, "q0": g.model.qpos0, "scales": scales,
-                         "smplx": {"handle": smpl.smplx_batch_handle(bms[idxs[0]], g), "clips": [packed[i] for i in idxs]}})
+            job.update(T=T, smplx= {"handle": smpl.smplx_batch_handle(bms[idxs[0]], g), "clips": [packed[i] for i in idxs]})
             continue
         shape = (len(idxs), T, len(g.human_body_names), 7)
         human = dp[1].pinned(f"human_{n}", shape, np.float64) if device else np.empty(shape)
@@ -1246,7 +1317,7 @@ def retarget_smplx_loaded(raws: Sequence[Dict], smplx_body_model_path: str, tgt_
         human[..., 4:] = 0.0
         for k, i in enumerate(idxs):
             human[k, : lens[k]] = packed[i]
-        jobs.append({"solver": g.hip_solver, "human": human, "lens": lens, "q0": g.model.qpos0, "scales": scales})
+        job["human"] = human
     if timing is not None:
         timing["prepare"] = timing.get("prepare", 0.0) + t1 - t0
         timing["pack"] = timing.get("pack", 0.0) + time.perf_counter() - t1
@@ -1257,53 +1328,13 @@ def retarget_smplx_loaded(raws: Sequence[Dict], smplx_body_model_path: str, tgt_
     lib_mode = None if not library else ("world" if library is True else str(library))
     if not raws:
         return ([], None) if library else []
-    fps = [fps_of[i] for i in range(len(raws))]
     if lib_mode is not None and len(jobs) != 1:
         raise ValueError("a motion library takes the clips in the order they were handed over: one job (the merged heights path)")
-    if device:
-        km, post = dp
-        rp, rr, dof, lbp, spans, status = post.run(jobs, km, 0, height_adjust, root_origin_offset, timing=timing, chunk=chunk,
-                                                   library=None if lib_mode is None else
-                                                   {"fps": [[fps[i] for i in idxs] for idxs, _ in members], "ang_vel": lib_mode})
-        if report is not None:
-            report.extend(r for rs in post.chunk_reports if rs is not None for r in rs)
-        t2 = time.perf_counter()
-        out: List[Optional[Dict]] = [None] * len(raws)
-        for (idxs, _), sp, stt in zip(members, spans, status):
-            if (stt != 0).any():
-                raise RuntimeError(f"IK failed for clips {[idxs[k] for k in np.nonzero(stt)[0]]}")
-            for i, (a, b) in zip(idxs, sp):
-                out[i] = motion_dict(fps[i], rp[a:b], rr[a:b], dof[a:b], lbp[a:b], km.body_names)
-        if timing is not None:
-            timing["dicts"] = timing.get("dicts", 0.0) + time.perf_counter() - t2
-        return (out, post.library) if library else out
-    total_frames = int(sum(int(l.sum()) for _, l in members))
-    specs = [chunking.resolve_any(chunk, l, total_frames) for _, l in members]
-    assert not (merged and any(sp is not None for sp in specs))
-    plain = [n for n, sp in enumerate(specs) if sp is None]
-    results: List = [None] * len(jobs)
-    for n, r in zip(plain, _lib.retarget_group([{k: v for k, v in jobs[n].items() if k != "q0"} for n in plain]) if plain else []):
-        results[n] = r
-    for n, sp in enumerate(specs):
-        if sp is not None:
-            q, ns, stt, rep = chunking.retarget_chunked_host(jobs[n]["solver"], jobs[n]["human"], jobs[n]["q0"], jobs[n]["lens"], 0, sp)
-            results[n] = (q, ns, stt)
-            if report is not None:
-                report.extend(rep)
-    qpos: List[Optional[np.ndarray]] = [None] * len(raws)
-    for (idxs, lens), (q, _, status) in zip(members, results):
-        if (status != 0).any():
-            raise RuntimeError(f"IK failed for clips {[idxs[k] for k in np.nonzero(status)[0]]}")
-        for k, i in enumerate(idxs):
-            qpos[i] = q[k, : lens[k]]
-    km = KinematicsModel(any_g.xml_file)
-    out = postprocess_clips(qpos, km, fps, height_adjust, root_origin_offset)
-    if lib_mode is not None:
-        from .motion_library import MotionLibrary
-        lib_ = MotionLibrary.from_motions(out, lib_mode)
-        lib_._kinematics = km
-        return out, lib_
-    return out
+    km, post = dp if device else (KinematicsModel(any_g.xml_file), None)
+    out, lib_, reports = _run_batch(jobs, km, 0, height_adjust, root_origin_offset, chunk, lib_mode, timing, post)
+    if report is not None:
+        report.extend(r for rs in reports if rs is not None for r in rs)
+    return (out, lib_) if library else out
 
 
 _SMPLX_DEVICE_POST: Dict[str, tuple] = {}
@@ -1348,7 +1379,6 @@ def run_smplx_dataset(src_folder: str, tgt_folder: str, robot: str, smplx_folder
     chunk_summary: Dict = {}
     if retarget is None:
         def retarget(raws, files):
-            from . import chunking
             rep: List = []
             out = retarget_smplx_loaded(raws, smplx_folder, robot, timing=timing, chunk=chunk, report=rep)
             if rep:
@@ -1418,7 +1448,6 @@ def main(argv=None) -> int:
     ap.add_argument("--frames_budget", type=int, default=1 << 19, help="padded frames (clips x longest clip) of one IK launch")
     ap.add_argument("--gpus", type=int, default=1, help="ranks = GPUs of this node; the files are LPT-sharded over them")
     ap.add_argument("--quiet", action="store_true")
-    from . import chunking
     chunking.add_cli_arguments(ap)
     a = ap.parse_args(argv)
     chunk = chunking.spec_from_args(a)

@@ -301,7 +301,7 @@ def smplx_batch_handle(body_model, retargeter) -> "_lib.SmplxHandle":
 
 
 def smplx_raw_clip(smplx_data, body_model, tgt_fps=30) -> Dict:
-    """One loaded AMASS file as an entry of a raw SMPL-X job (``DevicePost.run``, ``SmplxHandle.batch_frames``): the
+    """One loaded AMASS file as an entry of a raw SMPL-X job (``DevicePost._stage_smplx``, ``SmplxHandle.batch_frames``): the
     ``float32`` arrays the reference hands to the body model (utils/smpl.py:27-31), C-contiguous, with ``N``, ``nout``,
     ``align`` and ``aligned_fps`` as :func:`_frame_counts` gives them, the subject's rest joints and height.  Nothing is
     computed per frame.  Raises what the per-clip path raises for a clip it rejects (no frame at all; fps alignment of a

@@ -260,6 +260,28 @@ def test_retarget_smplx_files_device_path_equals_host_path(hip, tmp_path, monkey
             assert _pkl(a, dataset.SMPLX_KEYS) == _pkl(b, dataset.SMPLX_KEYS)
 
 
+def test_nine_jobs_in_one_run_equal_their_clips_as_one_job(hip, g1):
+    """More jobs than one post-processing call takes (8): the second call starts at a row that is a multiple of 4, and every
+    clip gets what it gets as a stream of ONE job (the streams of a group launch do not depend on each other)."""
+    from general_motion_retargeting_amd import GeneralMotionRetargeting, dataset, synth
+    nine = [[3, 2], [1], [2], [1, 1], [3], [2], [1], [2, 1], [2]]
+    spans9 = [[(0, 3), (3, 5)], [(5, 6)], [(6, 8)], [(8, 9), (9, 10)], [(10, 13)], [(13, 15)], [(15, 16)], [(16, 18), (18, 19)], [(20, 22)]]
+    gmr, km = GeneralMotionRetargeting("smplx", "unitree_g1"), _km("unitree_g1")
+    human, _ = synth.make_streams(g1.model, g1.tt, 12, 3, seed=47)
+    human = np.ascontiguousarray(human, dtype=np.float64)
+    job = lambda a, lens: {"solver": gmr.hip_solver, "human": human[a:a + len(lens)], "lens": np.array(lens, np.int32), "q0": gmr.model.qpos0}   # noqa: E731
+    first = np.cumsum([0] + [len(l) for l in nine])
+    post = dataset.DevicePost()
+    many = post.run([job(int(a), l) for a, l in zip(first, nine)], km)
+    one = post.run([job(0, [n for l in nine for n in l])], km)
+    assert many[4] == spans9 and [len(s) for s in many[5]] == [len(l) for l in nine] and many[0].shape[0] == 24
+    assert one[4] == [[(a, a + n) for a, n in zip(np.cumsum([0, 3, 2, 1, 2, 1, 1, 3, 2, 1, 2, 1]).tolist(), [n for l in nine for n in l])]]
+    assert np.array_equal(np.concatenate(many[5]), one[5][0]) and one[5][0].dtype == np.int32 and len(one[5][0]) == 12
+    for (a, b), (c, d) in zip([s for sp in many[4] for s in sp], one[4][0]):
+        for x, y in zip(many[:4], one[:4]):
+            assert x.dtype == y.dtype and np.array_equal(_bits(x[a:b]), _bits(y[c:d])), (a, b, c, d)
+
+
 def test_dicts_of_an_earlier_batch_survive_later_batches(hip, g1, monkeypatch):
     from general_motion_retargeting_amd import dataset, synth
     monkeypatch.delenv("GMR_DATASET_POST", raising=False)

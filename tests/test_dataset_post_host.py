@@ -121,3 +121,51 @@ def test_finish_takes_the_host_path_when_told_to(monkeypatch):
     assert rt.add(np.zeros((4, 3, 7)))
     rt.finish([30])
     assert calls == ["group", "host", "device"]
+
+
+NINE_JOBS = [[3, 2], [1], [2], [1, 1], [3], [2], [1], [2, 1], [2]]      # clip lengths per job: more jobs than one post-processing call takes
+
+
+def test_block_plan_of_nine_jobs_on_literal_values():
+    """a post-processing call takes at most 8 jobs, and every further call starts at a row that is a multiple of 4"""
+    ndof, nb = 5, 7
+    p = dataset.plan_block(NINE_JOBS, [None] * 9, ndof, nb)
+    assert len(p.calls) == 2
+    (c0, r0, seg0), (c1, r1, seg1) = p.calls
+    assert (c0, r0) == (0, 0) and seg0.dtype == np.int32 and seg0.tolist() == [0, 3, 5, 6, 8, 9, 10, 13, 15, 16, 18, 19]
+    assert (c1, r1) == (8, 20) and seg1.dtype == np.int32 and seg1.tolist() == [0, 2]
+    assert p.spans[0] == [(0, 3), (3, 5)] and p.spans[7] == [(16, 18), (18, 19)] and p.spans[8] == [(20, 22)]
+    assert [len(s) for s in p.spans] == [len(l) for l in NINE_JOBS]
+    assert p.rows == 24 and p.nclip == 12
+    end = 0
+    for name, row_bytes, n in (("root_pos", 24, 24), ("root_rot", 32, 24), ("dof_pos", ndof * 8, 24), ("local_body_pos", nb * 12, 24),
+                               ("status", 4, 12)):
+        off, stride = p.arrays[name][:2]
+        assert off % 256 == 0 and off >= end and stride == row_bytes, name
+        assert p.at(0x10000, name, 3).value == 0x10000 + off + 3 * row_bytes
+        end = off + n * row_bytes
+    assert list(p.arrays) == ["root_pos", "root_rot", "dof_pos", "local_body_pos", "status"]
+    assert p.total == p.arrays["status"][0] + _lib.align256(48) == p.arrays["status"][0] + 256
+    # the views of a host copy of the block lie where at() says the device wrote
+    buf = (C.c_char * p.total)()
+    rp, rr, dp, lb, status = p.views(buf)
+    assert (rp.shape, rr.shape, dp.shape, lb.shape, status.shape) == ((24, 3), (24, 4), (24, ndof), (24, nb, 3), (12,))
+    assert (rp.dtype, rr.dtype, dp.dtype, lb.dtype, status.dtype) == (np.float64, np.float64, np.float64, np.float32, np.int32)
+    base = C.addressof(buf)
+    for name, v in (("root_pos", rp), ("root_rot", rr), ("dof_pos", dp), ("local_body_pos", lb)):
+        assert v[21:].ctypes.data == p.at(base, name, 21).value, name
+    C.memset(p.at(base, "status", 11), 0x01, 4)
+    assert p.views(buf)[4].tolist() == [0] * 11 + [0x01010101] and status.tolist() == [0] * 12        # (the status words are a copy)
+
+
+def test_block_plan_without_frames_and_with_a_permutation():
+    for lens in ([], [[]], [[0, 0], [0]]):
+        p = dataset.plan_block(lens, [None] * len(lens), 5, 7)
+        assert p.rows == 1 and p.nclip == sum(len(l) for l in lens) and p.total == 4 * 256 + _lib.align256(4 * p.nclip)
+    # a raw BVH job: device position k holds clip perm[k] of the job
+    p = dataset.plan_block([[5, 1, 3], [4]], [np.array([2, 0, 1]), None], 5, 7)
+    assert p.dlens[0].tolist() == [3, 5, 1] and p.spans[0] == [(0, 3), (3, 8), (8, 9)] and p.spans[1] == [(9, 13)]
+    assert p.to_job_order(0, p.spans[0]) == [(3, 8), (8, 9), (0, 3)]                # the spans of clips 0, 1, 2
+    assert [b - a for a, b in p.to_job_order(0, p.spans[0])] == [5, 1, 3]
+    assert p.to_job_order(0, np.array([30, 50, 10])).tolist() == [50, 10, 30] and p.to_job_order(1, p.spans[1]) is p.spans[1]
+    assert p.spans[0] == [(0, 3), (3, 8), (8, 9)]                                    # (left in device order)

@@ -81,6 +81,35 @@ def test_scales_are_checked_before_any_device_call(monkeypatch):
     assert ok.dtype == np.float64 and ok.flags.c_contiguous and _lib.check_scales(None, 3, 14) is None
 
 
+def test_dev_job_names_the_nine_or_ten_elements(monkeypatch):
+    """a plain 9- or 10-sequence and a DevJob are the same job; any other length is refused before a device call"""
+    assert _lib.DevJob._fields == ("solver", "S", "T", "q0", "human", "len", "q_out", "nsolve", "status", "scale")
+    nine = ("sol", 3, 2, "q0", "human", "len", "q_out", "nsolve", "status")
+    a, b = _lib.dev_job(nine), _lib.dev_job(list(nine) + ["scale"])
+    assert a[:9] == b[:9] == nine and a.scale is None and b.scale == "scale" and (b.len, b.q_out, b.nsolve) == ("len", "q_out", "nsolve")
+    assert _lib.dev_job(b) is b and _lib.DevJob(*nine) == a and len(a) == 10
+
+    seen = []
+
+    class _Records:
+        def gmr_retarget_group_dev(self, arr, n, flags, stream):
+            jobs = C.cast(arr, C.POINTER(_lib.Job))
+            seen.append([(jobs[i].S, jobs[i].T, jobs[i].q0, jobs[i].status, jobs[i].scale) for i in range(n)])
+            return 0
+
+    monkeypatch.setattr(_lib, "lib", lambda: _Records())
+    sol = _fake_solver()
+    sol.handle = C.c_void_p(0x42)
+    q0, status, scale = C.c_void_p(0x1000), C.c_void_p(0x2000), C.c_void_p(0x3000)
+    _lib.retarget_group_dev([(sol, 3, 2, q0, None, None, None, None, status), (sol, 3, 2, q0, None, None, None, None, status, scale),
+                             _lib.DevJob(sol, 3, 2, q0, None, None, None, None, status, scale)])
+    assert seen == [[(3, 2, 0x1000, 0x2000, None), (3, 2, 0x1000, 0x2000, 0x3000), (3, 2, 0x1000, 0x2000, 0x3000)]]
+    monkeypatch.setattr(_lib, "lib", lambda: _NoDevice())
+    for n in (8, 11):
+        with pytest.raises(ValueError, match="9 or 10"):
+            _lib.retarget_group_dev([(sol, 3, 2) + (None,) * (n - 3)])
+
+
 def test_heights_and_scales_exclude_each_other(monkeypatch):
     from general_motion_retargeting_amd import GeneralMotionRetargeting
     monkeypatch.setattr(_lib, "lib", lambda: _NoDevice())
