@@ -16,9 +16,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libgmrhip.so")
 OBJ = os.path.join(os.path.dirname(HERE), "build", "obj")
-SOURCES = ["gmr_ik.hip", "gmr_ik_wide.hip", "gmr_fk.hip", "gmr_post.hip", "gmr_smplx.hip", "gmr_bvh.hip", "gmr_chunk.hip", "gmr_motion.hip", "gmr_body_state.hip", "gmr_tracker.hip", "gmr_tracker_links.hip", "gmr_tracker_preview.hip", "gmr_tracker_adaptive.hip", "gmr_tracker_anchor.hip", "gmr_tracker_control.hip", "gmr_tracker_proprio.hip", "gmr_tracker_feet.hip", "gmr_tracker_commands.hip", "gmr_tracker_episode.hip", "gmr_tracker_rollout.hip", "gmr_tracker_loss.hip", "gmr_tracker_optim.hip", "gmr_tracker_policy.hip", "gmr_tracker_policy_bwd.hip", "gmr_comm.hip", "gmr_abi.hip"]
+SOURCES = ["gmr_ik.hip", "gmr_ik_wide.hip", "gmr_fk.hip", "gmr_post.hip", "gmr_smplx.hip", "gmr_bvh.hip", "gmr_chunk.hip", "gmr_motion.hip", "gmr_body_state.hip", "gmr_tracker.hip", "gmr_tracker_links.hip", "gmr_tracker_preview.hip", "gmr_tracker_adaptive.hip", "gmr_tracker_anchor.hip", "gmr_tracker_control.hip", "gmr_tracker_proprio.hip", "gmr_tracker_feet.hip", "gmr_tracker_commands.hip", "gmr_tracker_episode.hip", "gmr_tracker_rollout.hip", "gmr_tracker_loss.hip", "gmr_tracker_optim.hip", "gmr_tracker_policy.hip", "gmr_tracker_policy_bwd.hip", "gmr_comm.hip", "gmr_ik_host.hip", "gmr_abi.hip"]
 HEADERS = ["gmr_ik_wide_item.inc", "gmr_device_math.h", "gmr_ik_layout.h", "gmr_ik_wide_layout.h", "gmr_ik_prof.h", "gmr_ik_tree.h",
-           "gmr_fk_tree.h", "gmr_fk_walk.h", "gmr_motion_sample.h", "gmr_philox.h", "gmr_tracker_dev.h", "gmr_tracker_host.h", "gmr_tracker_policy_plan.h", "gmr_tracker_policy_bwd_plan.h", "gmr_terrain.h", "gmr_link_plan.h", "gmr_handles.h", "gmr_post.h", "gmr_internal.h", "gmr_workspace.h", "../../include/gmr_hip.h", "../../include/gmr_types.h"]
+           "gmr_fk_tree.h", "gmr_fk_walk.h", "gmr_fk_handle.h", "gmr_launch.h", "gmr_ik_stage.h", "gmr_motion_sample.h", "gmr_philox.h", "gmr_tracker_dev.h", "gmr_tracker_host.h", "gmr_tracker_policy_plan.h", "gmr_tracker_policy_bwd_plan.h", "gmr_terrain.h", "gmr_link_plan.h", "gmr_handles.h", "gmr_post.h", "gmr_internal.h", "gmr_workspace.h", "../../include/gmr_hip.h", "../../include/gmr_types.h"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC"]
 # The throughput kernel must stay within 256 registers (two wavefronts per SIMD; since round 3: 168, three).  Machine-LICM hoists every FP64
 # literal and lane predicate of the (fully inlined) frame loop into registers that live for the whole kernel; they
@@ -145,7 +145,7 @@ def build_variant(name: str, defines=(), verbose: bool = False) -> str:
 def build_ik_variant(name: str, defines=(), sources=("gmr_ik.hip",), force: bool = False) -> str:
     """libgmrhip_<name>.so with extra -D flags on `sources` ONLY, linked with the default objects of every other source:
     a switch of the latency kernel (-DGMR_QP_CARRIED_START) costs one compilation, not twenty-two.  A profile build
-    (-DGMR_IK_PROFILE) names gmr_abi.hip as well: its entry point lives there.  Cached on the mtimes of sources and headers."""
+    (-DGMR_IK_PROFILE) names gmr_ik_host.hip as well: its entry point lives there.  Cached on the mtimes of sources and headers."""
     out = os.path.join(HERE, f"libgmrhip_{name}.so")
     deps = [os.path.join(CSRC, s) for s in SOURCES + HEADERS] + [os.path.abspath(__file__)]
     if not force and os.path.exists(out) and all(os.path.getmtime(d) <= os.path.getmtime(out) for d in deps):

@@ -22,9 +22,14 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <new>
+
 #include "../../include/gmr_hip.h"
 #include "gmr_fk_tree.h"
 #include "gmr_fk_walk.h"      // f4, qmul_xyzw, qrot_xyzw, fk_body: the per-body step
+#include "gmr_fk_handle.h"    // struct gmr_fk
+#include "gmr_internal.h"
+#include "gmr_launch.h"       // the prototypes of the launchers below
 
 // float32 arithmetic here mirrors torch eager ops (one rounding per operation): no FMA contraction,
 // which also makes both template variants produce the same bits
@@ -513,3 +518,111 @@ extern "C" hipError_t gmr_launch_fk_qpos(const gmr::FkTree* d_tree, const gmr::F
   if (world) return fk_launch(d_tree, h_tree, B, gmr::FkSrcQpos<true>{d_row_q}, d_body_pos, nullptr, nullptr, nullptr, stream);
   return fk_launch(d_tree, h_tree, B, gmr::FkSrcQpos<false>{d_row_q}, d_body_pos, nullptr, nullptr, nullptr, stream);
 }
+
+// ---- the C-ABI of the post-hoc FK (include/gmr_hip.h) -------------------------------------------------------------------------
+#define fail gmr_fail
+extern "C" {
+
+// checks, build (gmr_fk_tree.h: fk_build_tree, which the CPU tests drive too), upload
+int gmr_fk_create(int nbody, const int32_t* parent, const float* local_t, const float* local_r,
+                  const int32_t* dof_idx, const double* axis, int ndof, gmr_fk_t** out) {
+  if (!out || !parent || !local_t || !local_r || !dof_idx || !axis) return fail(GMR_ERR_ARG, "null argument");
+  if (nbody < 1 || nbody > gmr::FK_MAX_BODIES) return fail(GMR_ERR_ARG, "nbody out of range");
+  if (ndof < 0) return fail(GMR_ERR_ARG, "ndof negative");
+  // (every dof drives one body: FkTree::dof_body has FK_MAX_BODIES entries)
+  if (ndof > gmr::FK_MAX_BODIES) return fail(GMR_ERR_ARG, "ndof = %d out of range [0, %d]", ndof, gmr::FK_MAX_BODIES);
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(GMR_ERR_NO_DEVICE, "no HIP device visible");
+  gmr_fk* k = new (std::nothrow) gmr_fk;
+  if (!k) return fail(GMR_ERR_ARG, "out of host memory");
+  if (const char* why = gmr::fk_build_tree(k->tree, nbody, parent, local_t, local_r, dof_idx, axis, ndof)) {
+    delete k;
+    return fail(GMR_ERR_ARG, "%s", why);
+  }
+  hipError_t e;
+  if ((e = k->d_tree.reserve(sizeof(gmr::FkTree))) != hipSuccess ||
+      (e = hipMemcpy(k->d_tree.data(), &k->tree, sizeof(gmr::FkTree), hipMemcpyHostToDevice)) != hipSuccess) {
+    delete k;
+    return fail(GMR_ERR_HIP, "gmr_fk_create: %s", hipGetErrorString(e));
+  }
+  *out = k;
+  return GMR_OK;
+}
+
+int gmr_fk_destroy(gmr_fk_t* k) {
+  delete k;                                // (freeing its blocks waits for the device: nothing of the handle is in flight afterwards)
+  return GMR_OK;
+}
+
+int gmr_fk_batch_dev(gmr_fk_t* k, int B, const float* d_root_pos, const float* d_root_rot, const float* d_dof,
+                     float* d_body_pos, float* d_body_rot, float* d_min_z, void* stream) {
+  if (!k) return fail(GMR_ERR_ARG, "null fk handle");
+  if (B < 0) return fail(GMR_ERR_ARG, "negative B");
+  if (B == 0) return GMR_OK;
+  if (!d_root_pos || !d_root_rot || !d_body_pos || (k->tree.ndof > 0 && !d_dof)) return fail(GMR_ERR_ARG, "null device buffer");
+  // grows only; not graph-capturable on the first call of a size.  Earlier launches on any stream may still read the old
+  // block: freeing it waits for the device.
+  if (d_min_z) GMR_HIP_TRY(k->min_part.reserve((size_t)gmr_fk_blocks(B) * sizeof(float)));
+  GMR_HIP_TRY(gmr_launch_fk_batch(k->dev(), &k->tree, B, d_root_pos, d_root_rot, d_dof, d_body_pos,
+                              d_body_rot, (float*)k->min_part.data(), d_min_z, (hipStream_t)stream));
+  return GMR_OK;
+}
+
+int gmr_fk_segment_min_z_dev(gmr_fk_t* k, const float* d_body_pos, const int32_t* d_seg_start, int nseg, float* d_seg_min,
+                             void* stream) {
+  if (!k) return fail(GMR_ERR_ARG, "null fk handle");
+  if (nseg < 0) return fail(GMR_ERR_ARG, "negative nseg");
+  if (nseg == 0) return GMR_OK;
+  if (!d_body_pos || !d_seg_start || !d_seg_min) return fail(GMR_ERR_ARG, "null device buffer");
+  GMR_HIP_TRY(gmr_launch_fk_segment_min(d_body_pos, k->tree.nbody, d_seg_start, nseg, d_seg_min, (hipStream_t)stream));
+  return GMR_OK;
+}
+
+int gmr_fk_batch(gmr_fk_t* k, int B, const float* root_pos, const float* root_rot, const float* dof, float* body_pos,
+                 float* body_rot, float* min_z) {
+  if (!k) return fail(GMR_ERR_ARG, "null fk handle");
+  if (B < 0) return fail(GMR_ERR_ARG, "negative B");
+  if (B == 0) return GMR_OK;
+  if (!root_pos || !root_rot || !body_pos) return fail(GMR_ERR_ARG, "null host buffer");
+  const size_t n = (size_t)B, nb = k->tree.nbody, nd = k->tree.ndof;
+  gmr::HostStage st;
+  const float *d_rp, *d_rr, *d_dof;
+  float *d_bp, *d_br, *d_mz;
+  st.in(d_rp, root_pos, n * 12); st.in(d_rr, root_rot, n * 16); st.in(d_dof, dof, n * nd * 4);
+  st.out(d_bp, body_pos, n * nb * 12); st.out(d_br, body_rot, n * nb * 16); st.out(d_mz, min_z, 4);
+  GMR_STAGE_TRY(st, upload);
+  if (int rc = gmr_fk_batch_dev(k, B, d_rp, d_rr, d_dof, d_bp, d_br, d_mz, nullptr)) return rc;
+  GMR_STAGE_TRY(st, download);
+  return GMR_OK;
+}
+
+// Many clips in one launch: frames of clip g are rows [seg_start[g], seg_start[g + 1]) of the inputs.
+int gmr_fk_batch_segments(gmr_fk_t* k, int B, const float* root_pos, const float* root_rot, const float* dof, int nseg,
+                          const int32_t* seg_start, float* body_pos, float* seg_min_z) {
+  if (!k) return fail(GMR_ERR_ARG, "null fk handle");
+  if (B < 0 || nseg < 0) return fail(GMR_ERR_ARG, "negative B / nseg");
+  if (B == 0) { for (int g = 0; g < nseg && seg_min_z; g++) seg_min_z[g] = INFINITY; return GMR_OK; }
+  if (!root_pos || !root_rot || (k->tree.ndof > 0 && !dof)) return fail(GMR_ERR_ARG, "null host buffer");
+  if (nseg > 0 && (!seg_start || !seg_min_z)) return fail(GMR_ERR_ARG, "null segment buffers");
+  for (int g = 0; g < nseg; g++)
+    if (seg_start[g] < 0 || seg_start[g] > seg_start[g + 1] || seg_start[g + 1] > B) return fail(GMR_ERR_ARG, "seg_start must ascend within [0, B]");
+  const size_t n = (size_t)B, nb = k->tree.nbody, nd = k->tree.ndof;
+  gmr::HostStage st;
+  const float *d_rp, *d_rr, *d_dof;
+  const int32_t* d_ss;
+  float *d_bp, *d_sm;
+  st.in(d_rp, root_pos, n * 12); st.in(d_rr, root_rot, n * 16); st.in(d_dof, dof, n * nd * 4);
+  st.in(d_ss, nseg ? seg_start : nullptr, (size_t)(nseg + 1) * 4);
+  if (body_pos) st.out(d_bp, body_pos, n * nb * 12);
+  else st.scratch(d_bp, n * nb * 12);      // the segment minima are taken from it all the same
+  st.out(d_sm, nseg ? seg_min_z : nullptr, (size_t)nseg * 4);
+  GMR_STAGE_TRY(st, upload);
+  int rc = gmr_fk_batch_dev(k, B, d_rp, d_rr, d_dof, d_bp, nullptr, nullptr, nullptr);
+  if (rc == GMR_OK && nseg) rc = gmr_fk_segment_min_z_dev(k, d_bp, d_ss, nseg, d_sm, nullptr);
+  if (rc != GMR_OK) return rc;
+  GMR_STAGE_TRY(st, download);
+  return GMR_OK;
+}
+
+
+}  // extern "C"

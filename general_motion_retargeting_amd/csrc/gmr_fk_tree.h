@@ -1,5 +1,6 @@
 // gmr_fk_tree.h -- device-side tree of the float32 post-hoc FK (reference KinematicsModel arrays).
 #pragma once
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -284,6 +285,83 @@ inline const char* fk_build_split(FkTree& t, const int32_t* parent, int maxw) {
   }
   if (!park_ok) t.nwave = 1;
   for (int b = 0; b < nbody; b++) if (!owned[b]) return "a body is not covered";
+  return nullptr;
+}
+
+// The whole tree from the arrays of gmr_fk_create (host side; 1 <= nbody <= FK_MAX_BODIES, 0 <= ndof <= FK_MAX_BODIES, no null
+// array -- the caller's checks): depths and chains, the LDS parking slots, one record per body with the flags of its exact
+// zeros and ones, and the split walk.  Returns nullptr or why the tree is refused (a thread-local text).
+inline const char* fk_build_tree(FkTree& t, int nbody, const int32_t* parent, const float* local_t, const float* local_r,
+                                 const int32_t* dof_idx, const double* axis, int ndof) {
+  static thread_local char why[64];
+  auto refuse = [&](const char* fmt, int b) { snprintf(why, sizeof why, fmt, b); return (const char*)why; };
+  memset(&t, 0, sizeof t);
+  t.nbody = nbody; t.ndof = ndof;
+  int depth[FK_MAX_BODIES];
+  int maxd = 1;
+  if (parent[0] != -1) return "body 0 must be the root";
+  depth[0] = 0;
+  for (int b = 1; b < nbody; b++) {
+    if (parent[b] < 0 || parent[b] >= b) return refuse("parent[%d] invalid", b);
+    depth[b] = depth[parent[b]] + 1;
+    if (depth[b] + 1 > maxd) maxd = depth[b] + 1;
+  }
+  if (maxd > FK_MAX_DEPTH) return "tree too deep";
+  t.maxd = maxd;
+  // LDS slots: a body with a child that does not follow it immediately is parked; that child reloads its parent from the
+  // slot.  In depth-first body order (what the reference's parser yields) these are the bodies with >= 2 children; any other
+  // order with parent[b] < b is accepted too, and there an only child may come later than right behind its parent.
+  {
+    bool later_child[FK_MAX_BODIES] = {false};
+    for (int b = 1; b < nbody; b++) if (parent[b] != b - 1) later_child[parent[b]] = true;
+    int ns = 0;
+    for (int b = 0; b < nbody; b++) t.save_slot[b] = (short)(later_child[b] ? ns++ : -1);
+    t.nslot = ns > 0 ? ns : 1;
+    t.load_slot[0] = -1;
+    for (int b = 1; b < nbody; b++) t.load_slot[b] = (short)(parent[b] == b - 1 ? -1 : t.save_slot[parent[b]]);
+    for (int b = 0; b < nbody; b++) t.parent[b] = (short)(b == 0 ? 0 : parent[b]);
+  }
+  for (int b = 0; b < nbody; b++) {
+    if (dof_idx[b] >= ndof) return refuse("dof_idx[%d] out of range", b);
+    t.dof_idx[b] = dof_idx[b];
+    if (dof_idx[b] >= 0) t.dof_body[dof_idx[b]] = (short)b;
+    t.depth[b] = (short)depth[b];
+    int c = b;
+    for (int d = depth[b]; d >= 0; d--) { t.chain[b * maxd + d] = (short)c; c = parent[c]; }
+    // normalize(axis) = axis / max(|axis|, 1e-9) in float64 (torch_utils.py:57-59), once
+    double an = sqrt(axis[3 * b] * axis[3 * b] + axis[3 * b + 1] * axis[3 * b + 1] + axis[3 * b + 2] * axis[3 * b + 2]);
+    if (an < 1e-9) an = 1e-9;
+    for (int a = 0; a < 3; a++) { t.local_t[3 * b + a] = local_t[3 * b + a]; t.axis[3 * b + a] = axis[3 * b + a] / an; }
+    for (int a = 0; a < 4; a++) t.local_r[4 * b + a] = local_r[4 * b + a];
+  }
+  for (int b = 0; b < nbody; b++) {
+    FkBodyRec& r = t.rec[b];
+    for (int a = 0; a < 3; a++) { r.t[a] = t.local_t[3 * b + a]; r.axis[a] = t.axis[3 * b + a]; }
+    for (int a = 0; a < 4; a++) r.r[a] = t.local_r[4 * b + a];
+    r.dof_idx = t.dof_idx[b];
+    r.next_park = 0;
+    r.meta = (t.dof_idx[b] >= 0 ? 1u : 0u) | ((uint32_t)(t.load_slot[b] + 1) << 8) | ((uint32_t)(t.save_slot[b] + 1) << 16) |
+             ((uint32_t)t.parent[b] << 24);
+    // exact zeros and ones the walk does not multiply by (fk_body): a unit local rotation, a hinge axis +-e_k, zero
+    // components of the local translation
+    if (!getenv("GMR_FK_NO_SPECIAL")) {
+      for (int a = 0; a < 3; a++) if (r.t[a] == 0.0f) r.next_park |= 1u << (16 + a);
+      if (r.r[0] == 0.0f && r.r[1] == 0.0f && r.r[2] == 0.0f && r.r[3] == 1.0f) r.meta |= 2u;
+      for (int a = 0; a < 3 && t.dof_idx[b] >= 0; a++)
+        if (fabs(r.axis[a]) == 1.0 && r.axis[(a + 1) % 3] == 0.0 && r.axis[(a + 2) % 3] == 0.0) {
+          r.meta |= (uint32_t)(a + 1) << 2;
+          r.axis[0] = r.axis[a];                // the one component the walk reads for such a hinge
+          break;
+        }
+    }
+  }
+  // the split walk: per-wavefront body lists with their own records
+  const char* waves = getenv("GMR_FK_WAVES");
+  const int maxw = !waves ? FK_MAX_WAVES : atoi(waves) < 1 ? 1 : atoi(waves) > FK_MAX_WAVES ? FK_MAX_WAVES : atoi(waves);
+  if (const char* split = fk_build_split(t, parent, maxw)) {
+    snprintf(why, sizeof why, "split walk: %s", split);
+    return why;
+  }
   return nullptr;
 }
 

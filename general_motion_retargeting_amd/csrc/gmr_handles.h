@@ -1,5 +1,5 @@
 // gmr_handles.h -- the handles of the C-ABI that more than one translation unit of libgmrhip.so looks into (not part of the
-// C-ABI): the FK tree (created in gmr_abi.hip) and the motion library (gmr_motion.hip), both read by gmr_body_state.hip, and
+// C-ABI): the FK tree (gmr_fk_handle.h: created in gmr_fk.hip) and the motion library (gmr_motion.hip), both read by gmr_body_state.hip, and
 // the motion tracker (gmr_tracker.hip), which is bound to a library and, with links attached (gmr_tracker_links.hip), to an FK tree;
 // gmr_tracker_preview.hip reads its state and tables, gmr_tracker_adaptive.hip owns its bins (adaptive sampling, masked resets),
 // gmr_tracker_anchor.hip its anchors, gmr_tracker_control.hip its control tables and the two arrays of the actuator model,
@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/gmr_hip.h"
+#include "gmr_fk_handle.h"    // struct gmr_fk
 #include "gmr_fk_tree.h"
 #include "gmr_internal.h"
 #include "gmr_link_plan.h"
@@ -26,14 +27,6 @@
 #include "gmr_tracker_policy_plan.h"
 #include "gmr_tracker_policy_bwd_plan.h"
 #include "gmr_workspace.h"
-
-struct gmr_fk {
-  gmr::FkTree tree;
-  gmr::DeviceBlock d_tree;       // the tree as the kernels read it
-  const gmr::FkTree* dev() const { return (const gmr::FkTree*)d_tree.data(); }
-  gmr::DeviceBlock min_part;     // gmr_fk_batch_dev: one float per block of the min_z reduction
-  gmr::StreamWorkspace post_ws;  // gmr_postprocess_clips_dev
-};
 
 namespace gmr {
 // the arrays of a motion library as its kernels see them (device pointers into the library's one block)

@@ -47,6 +47,7 @@
 #include "gmr_device_math.h"
 #include "gmr_ik_layout.h"
 #include "gmr_ik_prof.h"
+#include "gmr_launch.h"
 
 namespace gmr {
 
@@ -1177,7 +1178,7 @@ __global__ __launch_bounds__(64 * NW, GMR_IK_MIN_WAVES) void ik_streams_kernel(c
           constexpr bool DENSE = NW == 1 && QP != QP_TREE_SMALL;
           if (first) { if (DENSE) qp_start.restore(stage, qp_state); else tree_start.restore(stage, tree_state); }
           int rc;
-          if (NW > 1) {   // the 4-wavefront shape is only launched for robots that decompose (gmr_abi.hip)
+          if (NW > 1) {   // the 4-wavefront shape is only launched for robots that decompose (gmr_ik_host.hip)
             // helpers joined after barrier B3
             rc = QP == QP_TREE_SMALL ? solve_qp_tree<7, 9, false, true>(L, sm, sw, si, 0, lane, tree_state, pr, rows_s)
                                      : solve_qp_tree<8, 10, false, false>(L, sm, sw, si, 0, lane, tree_state, pr, rows_l);
@@ -1245,7 +1246,7 @@ __global__ __launch_bounds__(64 * NW, GMR_IK_MIN_WAVES) void ik_streams_kernel(c
 
 }  // namespace gmr
 
-// host-side launchers used by gmr_abi.hip.  NW = 1: one wave per stream (throughput shape, many
+// host-side launchers used by gmr_ik_host.hip.  NW = 1: one wave per stream (throughput shape, many
 // streams); NW = 4: one main wave + 3 helpers per stream (latency shape: fewer streams than the chip
 // has SIMDs, the helpers share the two wide assembly phases).  The solver of an instance follows from the
 // robot's decomposition: NW = 1 runs the tree solver in DPP rows (<7, 9> fits a row) or the dense one,

@@ -16,7 +16,7 @@
 // (bit = the lane that owns the variable), so that no dof tables are consulted inside a pivoting round.
 //
 // Used for every robot that decomposes into <= 4 limbs of <= 7 dofs and a trunk of <= 9 (all shipped robots) when a
-// launch has more streams than the latency shape pays off for (gmr_abi.hip).
+// launch has more streams than the latency shape pays off for (gmr_ik_host.hip).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -25,6 +25,7 @@
 #include "gmr_device_math.h"
 #include "gmr_ik_prof.h"
 #include "gmr_ik_wide_layout.h"
+#include "gmr_launch.h"      // gmr_wide_job_desc and the prototypes of the launchers below
 
 #ifndef GMR_WIDE_NO_SCHUR_MFMA
 #define GMR_WIDE_SCHUR_MFMA 1
@@ -1008,7 +1009,7 @@ __global__ __launch_bounds__(64, GMR_WIDE_MIN_WAVES) void ik_wide_group_kernel(c
 }  // namespace gmr
 
 // ---------------------------------------------------------------------------------------------
-// host side: the launcher used by gmr_abi.hip and the queue workspaces of a solver
+// host side: the launcher used by gmr_ik_host.hip and the queue workspaces of a solver
 // ---------------------------------------------------------------------------------------------
 #include <map>
 #include <mutex>
@@ -1062,15 +1063,6 @@ extern "C" void gmr_ik_wide_pool_destroy(void* pool) {
   for (auto& kv : p->ws) if (kv.second.base) (void)hipFree(kv.second.base);
   delete p;
 }
-
-// one job of a launch as gmr_abi.hip hands it over (device pointers)
-struct gmr_wide_job_desc {
-  const char* d_image; const gmr::WideLayout* L; const gmr::IkParams* P;
-  int S, T;
-  const double* d_q0; const double* d_human; const int32_t* d_len;
-  double* d_q_out; int32_t* d_nsolve; int32_t* d_status; double* d_tgt_out; double* d_err_out;
-  const double* d_scale;         // [S][nhum] or null
-};
 
 // Launch njobs >= 1 jobs as ONE scheduling domain on `stream`: a single job runs the plain instance (its fields are
 // kernel arguments), several jobs -- or one that carries per-stream scale tables -- the group instance (job table in the

@@ -1,4 +1,4 @@
-// gmr_post.h -- the table of IK outputs a post-processing call reads (gmr_post.hip), shared with the C-ABI (gmr_abi.hip).
+// gmr_post.h -- the table of IK outputs a post-processing call reads (gmr_post.hip), shared with its entry point at the end of that file.
 #pragma once
 #include <stdint.h>
 

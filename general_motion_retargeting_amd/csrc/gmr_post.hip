@@ -15,8 +15,12 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "../../include/gmr_hip.h"
+#include "gmr_fk_handle.h"    // struct gmr_fk: the tree and the scratch of a call
+#include "gmr_internal.h"
+#include "gmr_launch.h"       // the prototypes of the launchers below and of the FK launchers
 #include "gmr_post.h"
 
 // float64 arithmetic here mirrors NumPy's (one rounding per operation)
@@ -105,3 +109,63 @@ extern "C" hipError_t gmr_launch_post_gather(const double* const* d_row_q, const
                      d_row_clip, d_seg_clamped, d_lowest, B, nq, flags, ground_offset, d_root_pos, d_root_rot, d_dof_pos);
   return hipGetLastError();
 }
+
+// ---- the C-ABI: the dataset drivers' post-processing on the device ---------------------------------------------------------
+#define fail gmr_fail
+extern "C" {
+
+int gmr_postprocess_clips_dev(gmr_fk_t* k, const gmr_post_src_t* src, int nsrc, int nq, const int32_t* d_seg_start, int C, int B,
+                              int flags, double ground_offset, double* d_root_pos, double* d_root_rot, double* d_dof_pos,
+                              float* d_local_body_pos, float* d_lowest, void* stream) {
+  if (!k) return fail(GMR_ERR_ARG, "null fk handle");
+  if (nsrc < 0 || nsrc > gmr::POST_MAX_SRC || (nsrc > 0 && !src)) return fail(GMR_ERR_ARG, "bad source list (at most %d sources)", gmr::POST_MAX_SRC);
+  if (nq != 7 + k->tree.ndof) return fail(GMR_ERR_ARG, "nq = %d, but this tree has %d dofs (nq = %d)", nq, k->tree.ndof, 7 + k->tree.ndof);
+  if (C < 0 || B < 0) return fail(GMR_ERR_ARG, "negative C / B");
+  if (flags & ~(GMR_POST_HEIGHT_ADJUST | GMR_POST_ROOT_ORIGIN_OFFSET)) return fail(GMR_ERR_ARG, "unknown flag bits 0x%x", flags);
+  gmr::PostSources ps;
+  memset(&ps, 0, sizeof ps);
+  ps.nsrc = nsrc;
+  long long clips = 0, rows = 0;
+  for (int i = 0; i < nsrc; i++) {
+    if (src[i].S < 0 || src[i].T < 0) return fail(GMR_ERR_ARG, "source %d: negative S/T", i);
+    if (src[i].S > 0 && (src[i].T < 1 || !src[i].q_out)) return fail(GMR_ERR_ARG, "source %d: S = %d streams need T >= 1 and q_out", i, src[i].S);
+    ps.clip0[i] = (int32_t)clips;
+    ps.T[i] = src[i].T;
+    ps.q_out[i] = src[i].q_out;
+    ps.len[i] = src[i].len;
+    clips += src[i].S;
+    rows += (long long)src[i].S * src[i].T;
+    if (clips > INT32_MAX) return fail(GMR_ERR_ARG, "too many clips");
+  }
+  for (int i = nsrc; i <= gmr::POST_MAX_SRC; i++) ps.clip0[i] = (int32_t)clips;
+  if (clips != C) return fail(GMR_ERR_ARG, "C = %d, but the sources hold %lld clips", C, clips);
+  if (B > rows) return fail(GMR_ERR_ARG, "B = %d rows, but the sources hold only %lld", B, rows);
+  if (C == 0) return GMR_OK;
+  if (!d_seg_start) return fail(GMR_ERR_ARG, "null seg_start");
+  if (B > 0 && (!d_root_pos || !d_root_rot || !d_local_body_pos || (k->tree.ndof > 0 && !d_dof_pos))) return fail(GMR_ERR_ARG, "null output buffer");
+  const bool height = flags & GMR_POST_HEIGHT_ADJUST;
+  if (B == 0 && !(height && d_lowest)) return GMR_OK;
+  // scratch: row_q [B] pointers, row_clip [B], seg_clamped [C + 1], lowest [C] (when the caller does not want it), and the
+  // world pass's body_pos [B][nbody][3]
+  gmr::Carve c;
+  const size_t o_rq = c.take((size_t)B * 8), o_rc = c.take((size_t)B * 4), o_sc = c.take((size_t)(C + 1) * 4), o_lo = c.take((size_t)C * 4),
+               o_bp = c.take(height ? (size_t)B * k->tree.nbody * 12 : 0);
+  hipStream_t st = (hipStream_t)stream;
+  const auto ws = k->post_ws.acquire(st, c.total());           // (held until the last launch below is enqueued)
+  GMR_NAMED_HIP_TRY("gmr_postprocess_clips_dev: scratch", ws.error());
+  char* d = ws.base();
+  const double** row_q = (const double**)(d + o_rq);
+  int32_t* row_clip = (int32_t*)(d + o_rc);
+  int32_t* seg_clamped = (int32_t*)(d + o_sc);
+  float* lowest = d_lowest ? d_lowest : (float*)(d + o_lo);
+  GMR_HIP_TRY(gmr_launch_post_row_map(&ps, d_seg_start, C, B, nq, row_q, row_clip, seg_clamped, st));
+  if (height) {
+    GMR_HIP_TRY(gmr_launch_fk_qpos(k->dev(), &k->tree, B, row_q, 1, (float*)(d + o_bp), st));
+    GMR_HIP_TRY(gmr_launch_fk_segment_min((const float*)(d + o_bp), k->tree.nbody, seg_clamped, C, lowest, st));
+  }
+  GMR_HIP_TRY(gmr_launch_fk_qpos(k->dev(), &k->tree, B, row_q, 0, d_local_body_pos, st));
+  GMR_HIP_TRY(gmr_launch_post_gather(row_q, row_clip, seg_clamped, lowest, B, nq, flags, ground_offset, d_root_pos, d_root_rot, d_dof_pos, st));
+  return GMR_OK;
+}
+
+}  // extern "C"

@@ -123,6 +123,7 @@ class StreamWorkspaceT {
 // the variables into it and copies the inputs; the entry point launches; download() waits for the device and copies the outputs back.
 //   null host pointer          null device pointer, no copy
 //   non-null, 0 bytes          a valid device pointer, no copy either way
+//   scratch                    a field without a host array: a valid device pointer, no copy either way
 //   in_shared                  arrays that may interleave in one tensor: when the hull of those present is no longer than the sum of
 //                              their extents it is copied once and each device pointer keeps its array's offset inside it
 // The variables must stay where they are until upload() has returned.  On an error, failed() names the operation; after a failed
@@ -137,6 +138,8 @@ class HostStageT {
   template <class T> void in_shared(T*& d, const void* h, size_t bytes) { d = nullptr; add(&d, h, bytes, kShared); }
   // copy_back = false: the kernels get the memory, the host array stays as it is
   template <class T> void out(T*& d, void* h, size_t bytes, bool copy_back = true) { d = nullptr; add(&d, h, bytes, copy_back ? kOut : kScratch); }
+  // a field no host array stands behind: what one launch of the call leaves for the next
+  template <class T> void scratch(T*& d, size_t bytes) { d = nullptr; add(&d, nullptr, bytes, kDevice); }
 
   error_t upload() {
     if (n_ == 0) return B::success;          // nothing to stage: no allocation
@@ -187,7 +190,7 @@ class HostStageT {
   const char* failed() const { return what_; }      // the operation that upload() or download() reported an error from
 
  private:
-  enum Kind { kIn, kShared, kOut, kScratch };
+  enum Kind { kIn, kShared, kOut, kScratch, kDevice };
   struct Array {
     void* var;       // the caller's pointer variable
     void* host;
@@ -195,7 +198,7 @@ class HostStageT {
     Kind kind;
   };
   void add(void* var, const void* h, size_t bytes, Kind kind) {
-    if (!h) return;
+    if (!h && kind != kDevice) return;
     if (n_ == kMaxArrays) abort();
     arrays_[n_++] = Array{var, const_cast<void*>(h), bytes, 0, kind};
   }

@@ -9,7 +9,8 @@
 //     copy; fields at multiples of 256 that do not overlap; download is synchronise, then the copies of the outputs that are
 //     neither skipped nor empty; the bytes a "kernel" (a host loop over the device pointers) wrote come back; arrays that
 //     interleave in one tensor travel as one copy of their hull, arrays apart as one copy each; a failed allocation copies
-//     nothing and writes no host output; the block is freed exactly once.  The fake's memory is malloc'd and its copies are
+//     nothing and writes no host output; a scratch field (no host array) has bytes of its own and is copied neither way;
+//     the block is freed exactly once.  The fake's memory is malloc'd and its copies are
 //     memcpy, so real bytes make the round trip.
 // Prints "ok"; exit code 0 = all good.
 #include <algorithm>
@@ -209,6 +210,34 @@ static int check_stage() {
     Stage st;
     CHECK(st.upload() == 0 && st.download() == 0 && Fake::count('a') == 0, "a call without arrays allocates nothing");
   }
+
+  // a field without a host array: what the first "launch" of a call leaves for its second
+  Fake::log.clear();
+  {
+    std::vector<unsigned char> in(70), res(70, 0);
+    for (size_t i = 0; i < in.size(); i++) in[i] = (unsigned char)(i * 3 + 2);
+    Stage st;
+    const unsigned char* d_in;
+    unsigned char *d_mid, *d_none, *d_res;
+    st.in(d_in, in.data(), in.size());
+    st.scratch(d_mid, 300);
+    st.scratch(d_none, 0);
+    st.out(d_res, res.data(), res.size());
+    CHECK(st.upload() == 0, "upload");
+    CHECK(Fake::log.size() == 2 && Fake::log[0].what == 'a' && Fake::log[1] == (Op{'u', (void*)d_in, in.size()}), "one allocation and the one input's copy: nothing is copied into a scratch field (%zu ops)", Fake::log.size());
+    const unsigned char* base = (const unsigned char*)Fake::log[0].p;
+    const size_t at_in = (size_t)(d_in - base), at_mid = (size_t)(d_mid - base), at_none = (size_t)(d_none - base), at_res = (size_t)(d_res - base);
+    CHECK(d_mid && at_mid % 256 == 0 && at_mid >= at_in + in.size() && at_none >= at_mid + 300 && at_res >= at_mid + 300 && at_res + res.size() <= Fake::log[0].bytes,
+          "the scratch field has 300 bytes of its own (in %zu, scratch %zu, out %zu)", at_in, at_mid, at_res);
+    CHECK(d_none != nullptr, "a scratch field of 0 bytes gets an address");
+    for (size_t i = 0; i < 300; i++) d_mid[i] = (unsigned char)(d_in[i % in.size()] + 1);      // launch 1
+    for (size_t i = 0; i < res.size(); i++) d_res[i] = (unsigned char)(d_mid[i] ^ d_mid[i + 230]);      // launch 2
+    Fake::log.clear();
+    CHECK(st.download() == 0, "download");
+    CHECK(Fake::log.size() == 2 && Fake::log[0] == (Op{'S', nullptr, 0}) && Fake::log[1] == (Op{'d', d_res, res.size()}), "download copies the output alone (%zu ops)", Fake::log.size());
+    for (size_t i = 0; i < res.size(); i++) CHECK(res[i] == (unsigned char)((in[i] + 1) ^ (in[(i + 230) % in.size()] + 1)), "res[%zu]", i);
+  }
+  CHECK(Fake::live.empty() && Fake::double_frees == 0, "the block is freed exactly once");
 
   // arrays that interleave in one tensor: [n][7] (pos 3, quat 4) and [n][13] (pos 3, quat 4, vel 3, ang vel 3, the vel left out)
   const size_t n = 5;

@@ -2,7 +2,8 @@
 layout + image) checked on the CPU for every (source, robot) pair: tests/cpp/layout_check.cpp is plain
 C++ (g++), includes the product header csrc/gmr_ik_layout.h and reads the packed structs from a file.
 tests/cpp/workspace_check.cpp does the same for csrc/gmr_workspace.h, how the host side owns device memory
-and stages the arrays of a synchronous call."""
+and stages the arrays of a synchronous call; tests/cpp/ik_stage_check.cpp for csrc/gmr_ik_stage.h, the arrays of an IK job and
+the copies that move them; tests/cpp/fk_tree_check.cpp for the tree builder of csrc/gmr_fk_tree.h."""
 import os
 import subprocess
 
@@ -121,6 +122,35 @@ def test_device_workspace_code_is_clean_under_sanitizers(tmp_path):
         pytest.skip("sanitizer runtime not available: " + cc.stderr[-200:])
     out = subprocess.run([exe], capture_output=True, text=True)
     assert out.returncode == 0 and out.stdout.strip() == "ok" and "runtime error" not in out.stderr and "ERROR" not in out.stderr, (out.stdout, out.stderr[-2000:])
+
+
+def _run_check(tmp_path, name, sanitize):
+    """tests/cpp/<name>.cpp as a stand-alone program, plain or under AddressSanitizer + UBSan: it prints "ok" """
+    exe = str(tmp_path / (name + ("_asan" if sanitize else "")))
+    extra = ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] if sanitize else []
+    cc = subprocess.run(["g++", "-O1", "-std=c++17", "-Wall"] + extra + ["-o", exe, os.path.join(ROOT, "tests", "cpp", name + ".cpp")],
+                        capture_output=True, text=True)
+    if sanitize and cc.returncode != 0:
+        pytest.skip("sanitizer runtime not available: " + cc.stderr[-200:])
+    assert cc.returncode == 0 and "warning" not in cc.stderr, cc.stderr[-2000:]
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and out.stdout.strip() == "ok" and "runtime error" not in out.stderr and "ERROR" not in out.stderr, (out.stdout, out.stderr[-2000:])
+
+
+@pytest.mark.parametrize("sanitize", [False, True])
+def test_ik_job_arrays_offsets_copies_and_cuts(tmp_path, sanitize):
+    """csrc/gmr_ik_stage.h on literal values: the bytes and offsets of the nine arrays of a job with every optional array
+    present and absent, the copy descriptors of slices and windows applied with memcpy around a host-loop kernel (every
+    output byte arrives exactly once, equal to an unsliced pass, no descriptor outside its array or its field), and the
+    integer rules that cut a batch and choose a launch shape.  These offsets become device copies."""
+    _run_check(tmp_path, "ik_stage_check", sanitize)
+
+
+@pytest.mark.parametrize("sanitize", [False, True])
+def test_fk_tree_builder_on_a_five_body_tree(tmp_path, sanitize):
+    """csrc/gmr_fk_tree.h: fk_build_tree, the host arithmetic of gmr_fk_create: depths, chains, parking slots, records and
+    their special-case flags, and its refusals by their text."""
+    _run_check(tmp_path, "fk_tree_check", sanitize)
 
 
 def test_layout_code_is_clean_under_sanitizers(tmp_path):

@@ -70,9 +70,9 @@ def variant_libs():
     from the default objects).  Cached on disk."""
     from general_motion_retargeting_amd import build
     return {"carried": build.build_ik_variant("carried", ["-DGMR_QP_CARRIED_START"]),
-            "prof": build.build_ik_variant("prof", ["-DGMR_IK_PROFILE"], sources=("gmr_ik.hip", "gmr_abi.hip")),
+            "prof": build.build_ik_variant("prof", ["-DGMR_IK_PROFILE"], sources=("gmr_ik.hip", "gmr_ik_host.hip")),
             "prof_carried": build.build_ik_variant("prof_carried", ["-DGMR_IK_PROFILE", "-DGMR_QP_CARRIED_START"],
-                                                   sources=("gmr_ik.hip", "gmr_abi.hip"))}
+                                                   sources=("gmr_ik.hip", "gmr_ik_host.hip"))}
 
 
 def test_kernel_compiles_with_and_without_the_switch(variant_libs):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Launch-shape crossover: frames/s of the IK kernel with 1 and 4 wavefronts per stream over the number
-of streams per launch (sets GMR_HELPER_MAX_STREAMS in gmr_abi.hip)."""
+of streams per launch (sets IK_HELPER_MAX_STREAMS in csrc/gmr_ik_stage.h)."""
 import json
 import os
 import sys
