@@ -51,6 +51,8 @@ _SIGS = {
     "gmr_solver_dims": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "gmr_solver_set_waves": (C.c_int, [C.c_void_p, C.c_int]),
     "gmr_solver_set_dispatch": (C.c_int, [C.c_void_p, C.c_int]),
+    "gmr_solver_set_velocity_limits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "gmr_solver_velocity_limits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "gmr_retarget_lds_bytes": (C.c_int, [C.c_void_p]),
     "gmr_retarget_streams_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -614,6 +616,25 @@ class Solver:
     def set_dispatch(self, frames_per_item: int) -> None:
         """Many-stream launches: > 0 = device-side FIFO of (stream, frames_per_item frames) items, 0 = one workgroup per stream."""
         check(lib().gmr_solver_set_dispatch(self.handle, int(frames_per_item)))
+
+    def set_velocity_limit(self, vmax) -> None:
+        """Per-hinge velocity limits ``vmax`` f64[nhinge] in rad/s (``inf`` = none for that hinge; ``None`` = none at all) for
+        every launch from this solver issued afterwards: each solve keeps ``|dq_h| <= vmax_h * timestep`` (mink's
+        ``VelocityLimit``).  A bound per SOLVE -- a frame runs up to 22 of them -- not on the velocity between frames."""
+        if vmax is None:
+            check(lib().gmr_solver_set_velocity_limits(self.handle, None, 0))
+            return
+        vmax = np.ascontiguousarray(vmax, dtype=np.float64)
+        if vmax.ndim != 1:
+            raise ValueError(f"velocity limits must be [{self.nv - 6}], got {vmax.shape}")
+        check(lib().gmr_solver_set_velocity_limits(self.handle, _ptr(vmax), int(vmax.shape[0])))
+
+    @property
+    def velocity_limit(self) -> np.ndarray:
+        """f64[nhinge], rad/s; ``inf`` where a hinge has none."""
+        out = np.empty(self.nv - 6, dtype=np.float64)
+        check(lib().gmr_solver_velocity_limits(self.handle, _ptr(out), int(out.shape[0])))
+        return out
 
     @property
     def lds_bytes(self) -> int:

@@ -513,10 +513,12 @@ __device__ __forceinline__ void pairs_from_jbody(const LT& L, double* sm, int st
     *reinterpret_cast<double*>(reinterpret_cast<char*>(sm + L.o.H) + zero_off[vlane - 64]) = 0.0;
 }
 
-// (c) lane = dof: gather c; bounds of the limited hinges (mink ConfigurationLimit)
-template <class LT>
+// (c) lane = dof: gather c; bounds of the limited hinges (mink ConfigurationLimit); VLIM: clamped into this dof's velocity
+// bound [-vdt, vdt] (mink VelocityLimit; vdt = +inf leaves both bits as they are).  Instances without VLIM carry no
+// trace of it: they are the kernels of a solver that has no finite limit (ik_streams_kernel).
+template <bool VLIM, class LT>
 __device__ __forceinline__ void cvec_phase(const LT& L, double* sm, int stage, const StageTabs& tb,
-                                           const short* limited, double limit_gain, int lane) {
+                                           const short* limited, double limit_gain, double vdt, int lane) {
   lane = fresh_lane(lane);
   const int nv = L.nv;
   const char* cpart = reinterpret_cast<const char*>(sm + L.o.cpart);
@@ -534,6 +536,10 @@ __device__ __forceinline__ void cvec_phase(const LT& L, double* sm, int stage, c
       double th = (sm + L.o.q)[7 + lane - 6];
       hi = limit_gain * ((sm + L.o.range_hi)[lane - 6] - th);
       lo = -limit_gain * (th - (sm + L.o.range_lo)[lane - 6]);
+    }
+    if (VLIM) {
+      lo = fmin(fmax(lo, -vdt), vdt);
+      hi = fmin(fmax(hi, -vdt), vdt);
     }
     (sm + L.o.lo)[lane] = lo;
     (sm + L.o.hi)[lane] = hi;
@@ -647,10 +653,10 @@ __device__ __forceinline__ void hacc_phase_g(const LT& L, double* sm, int stage,
 // the whole assembly as seen from the MAIN wave.  NW == 1: all four phases by this wave.  NW > 1:
 // the Jacobian columns are shared by all NW waves, then the helpers assemble H (64*(NW-1) virtual
 // lanes) while this wave gathers c and the bounds; three workgroup barriers per assembly.
-template <int NW, class LT>
+template <int NW, bool VLIM, class LT>
 __device__ __forceinline__ void build_qp_main(const LT& L, double* sm, int stage, const StageTabs& tb,
                                               const short* hinge_body, const short* limited, int* ctl, int& epoch,
-                                              double damping, double lm_damping, double limit_gain, int lane,
+                                              double damping, double lm_damping, double limit_gain, double vdt, int lane,
                                               int pk_main, bool first, Prof& pr) {   // pk_main: task of this lane's pair in this table
   double mu = jlog_phase<NW>(L, sm, stage, lm_damping, lane, pr);
   const double diag = damping + mu;
@@ -660,7 +666,7 @@ __device__ __forceinline__ void build_qp_main(const LT& L, double* sm, int stage
     WSYNC();
     PROF_END(pr, PH_PAIRS);
     PROF_BEGIN(pr);
-    cvec_phase(L, sm, stage, tb, limited, limit_gain, lane);
+    cvec_phase<VLIM>(L, sm, stage, tb, limited, limit_gain, vdt, lane);
     PROF_END(pr, PH_CVEC);
     PROF_BEGIN(pr);
     hacc_phase_g(L, sm, stage, tb.items, diag, lane);
@@ -676,7 +682,7 @@ __device__ __forceinline__ void build_qp_main(const LT& L, double* sm, int stage
     __syncthreads();                      // B2: all Jacobian columns written
     PROF_END(pr, PH_PAIRS);
     PROF_BEGIN(pr);
-    cvec_phase(L, sm, stage, tb, limited, limit_gain, lane);
+    cvec_phase<VLIM>(L, sm, stage, tb, limited, limit_gain, vdt, lane);
     PROF_END(pr, PH_CVEC);
     PROF_BEGIN(pr);
     __syncthreads();                      // B3: H complete (helpers)
@@ -1034,7 +1040,10 @@ __device__ __forceinline__ void preprocess_wave(const LT& L, double* sm, const s
 // `scale` (f64 [S][nhum] or null: per-stream human scale tables) is the LAST argument on purpose: in the middle of the list,
 // beside `len`, it moved the kernarg offsets of everything behind it and cost the four-wavefront instances 4 to 8 more
 // spilled SGPRs and the headline 0.5 % frames/s; at the end every instance keeps the registers it had.
-template <int NVP, int NW, int QP>
+// VLIM: the solver has a finite velocity limit (gmr_solver_set_velocity_limits).  It is a template argument, not a test in
+// the kernel: the clamp always on cost the headline 0.40 %, skipped by unlimited lanes 0.19 % (8 more spilled SGPRs), six
+// alternated runs each; the instances without it are the parent's code.
+template <int NVP, int NW, int QP, bool VLIM>
 __global__ __launch_bounds__(64 * NW, GMR_IK_MIN_WAVES) void ik_streams_kernel(const uint4* __restrict__ image, IkLay<NVP, NW> L, IkParams P,
                                                              int S, int T, const double* __restrict__ q0,
                                                              const double* __restrict__ human,
@@ -1086,6 +1095,9 @@ __global__ __launch_bounds__(64 * NW, GMR_IK_MIN_WAVES) void ik_streams_kernel(c
   const double* prm = sm + L.o.params;   // damping, lm_damping, tol, limit_gain, ground_offset, dt: read where used
   const int max_iter = P.max_iter, human_root = P.human_root;
   const int use0 = P.use0, use1 = P.use1;
+  // this lane's velocity bound of one solve (lane = dof), from the global image behind its LDS part: one register pair
+  // of the main wavefront for the whole launch, no LDS and no pointer kept (gmr_ik_layout.h: IK_VDT_N)
+  const double vdt = VLIM && lane < nv ? reinterpret_cast<const double*>(reinterpret_cast<const char*>(image) + L.smem_bytes)[lane] : INFINITY;
 
   // this stream's own human scale table in place of the image's (only preprocess_wave reads it: the helpers never do)
   if (scale && lane < nhum) (sm + L.o.scale)[lane] = scale[(size_t)s * nhum + lane];
@@ -1173,7 +1185,7 @@ __global__ __launch_bounds__(64 * NW, GMR_IK_MIN_WAVES) void ik_streams_kernel(c
         int nsol = 0, num_iter = 0;
         for (;;) {
           const bool first = nsol == 0;
-          build_qp_main<NW>(L, sm, stage, tb, hinge_body, limited, ctl, epoch, prm[0], prm[1], prm[3], lane, pk_main[stage], first, pr);
+          build_qp_main<NW, VLIM>(L, sm, stage, tb, hinge_body, limited, ctl, epoch, prm[0], prm[1], prm[3], vdt, lane, pk_main[stage], first, pr);
           PROF_COUNT(pr, PH_NSOLVE);
           constexpr bool DENSE = NW == 1 && QP != QP_TREE_SMALL;
           if (first) { if (DENSE) qp_start.restore(stage, qp_state); else tree_start.restore(stage, tree_state); }
@@ -1251,30 +1263,33 @@ __global__ __launch_bounds__(64 * NW, GMR_IK_MIN_WAVES) void ik_streams_kernel(c
 // has SIMDs, the helpers share the two wide assembly phases).  The solver of an instance follows from the
 // robot's decomposition: NW = 1 runs the tree solver in DPP rows (<7, 9> fits a row) or the dense one,
 // NW = 4 (only launched for robots that decompose) the <7, 9> or the <8, 10> tree instance.
-template <int NVP, int NW, int QP>
+template <int NVP, int NW, int QP, bool VLIM>
 static hipError_t launch_nvp(const uint4* d_image, const gmr::IkLayout* L, const gmr::IkParams* P, int S, int T,
                              const double* d_q0, const double* d_human,
                              const int32_t* d_len, const double* d_scale, int flags, double* d_q_out, int32_t* d_nsolve,
                              int32_t* d_status, double* d_tgt_out, double* d_err_out, hipStream_t stream, unsigned long long* d_prof) {
-  hipLaunchKernelGGL((gmr::ik_streams_kernel<NVP, NW, QP>), dim3(S), dim3(64 * NW), L->smem_bytes, stream, d_image,
+  hipLaunchKernelGGL((gmr::ik_streams_kernel<NVP, NW, QP, VLIM>), dim3(S), dim3(64 * NW), L->smem_bytes, stream, d_image,
                      gmr::IkLay<NVP, NW>(static_cast<const gmr::IkDims&>(*L)), *P, S, T, d_q0, d_human, d_len, flags, d_q_out, d_nsolve, d_status,
                      d_tgt_out, d_err_out, d_prof, d_scale);
   return hipGetLastError();
 }
 
 #define GMR_ARGS d_image, L, P, S, T, d_q0, d_human, d_len, d_scale, flags, d_q_out, d_nsolve, d_status, d_tgt_out, d_err_out, stream, d_prof
+#define GMR_DISPATCH_V(NVP_, V_)                                                                       \
+    if (L->nw == 1) return L->tree_small ? launch_nvp<NVP_, 1, gmr::QP_TREE_SMALL, V_>(GMR_ARGS)       \
+                                         : launch_nvp<NVP_, 1, gmr::QP_DENSE, V_>(GMR_ARGS);           \
+    return L->tree_small ? launch_nvp<NVP_, 4, gmr::QP_TREE_SMALL, V_>(GMR_ARGS)                       \
+                         : launch_nvp<NVP_, 4, gmr::QP_TREE, V_>(GMR_ARGS);
 #define GMR_DISPATCH(NVP_)                                                                             \
   case NVP_:                                                                                           \
-    if (L->nw == 1) return L->tree_small ? launch_nvp<NVP_, 1, gmr::QP_TREE_SMALL>(GMR_ARGS)           \
-                                         : launch_nvp<NVP_, 1, gmr::QP_DENSE>(GMR_ARGS);               \
-    return L->tree_small ? launch_nvp<NVP_, 4, gmr::QP_TREE_SMALL>(GMR_ARGS)                           \
-                         : launch_nvp<NVP_, 4, gmr::QP_TREE>(GMR_ARGS);
+    if (vlim) { GMR_DISPATCH_V(NVP_, true) }                                                           \
+    GMR_DISPATCH_V(NVP_, false)
 
 extern "C" hipError_t gmr_launch_ik_streams(const uint4* d_image, const gmr::IkLayout* L, const gmr::IkParams* P,
                                             int S, int T, const double* d_q0, const double* d_human,
                                             const int32_t* d_len, const double* d_scale, int flags, double* d_q_out,
                                             int32_t* d_nsolve, int32_t* d_status, double* d_tgt_out, double* d_err_out,
-                                            hipStream_t stream, unsigned long long* d_prof) {
+                                            hipStream_t stream, unsigned long long* d_prof, int vlim) {
   if (S <= 0 || T <= 0) return hipSuccess;
   switch (L->nvp) {
     GMR_DISPATCH(28)
@@ -1285,24 +1300,26 @@ extern "C" hipError_t gmr_launch_ik_streams(const uint4* d_image, const gmr::IkL
   }
 }
 
-template <int NVP>
+template <int NVP, bool VLIM>
 static const void* kernel_of(int nw, int tree_small) {
-  if (nw == 1) return tree_small ? reinterpret_cast<const void*>(gmr::ik_streams_kernel<NVP, 1, gmr::QP_TREE_SMALL>)
-                                 : reinterpret_cast<const void*>(gmr::ik_streams_kernel<NVP, 1, gmr::QP_DENSE>);
-  return tree_small ? reinterpret_cast<const void*>(gmr::ik_streams_kernel<NVP, 4, gmr::QP_TREE_SMALL>)
-                    : reinterpret_cast<const void*>(gmr::ik_streams_kernel<NVP, 4, gmr::QP_TREE>);
+  if (nw == 1) return tree_small ? reinterpret_cast<const void*>(gmr::ik_streams_kernel<NVP, 1, gmr::QP_TREE_SMALL, VLIM>)
+                                 : reinterpret_cast<const void*>(gmr::ik_streams_kernel<NVP, 1, gmr::QP_DENSE, VLIM>);
+  return tree_small ? reinterpret_cast<const void*>(gmr::ik_streams_kernel<NVP, 4, gmr::QP_TREE_SMALL, VLIM>)
+                    : reinterpret_cast<const void*>(gmr::ik_streams_kernel<NVP, 4, gmr::QP_TREE, VLIM>);
 }
 
-// opt the instance that (nvp, nw, tree_small) selects into `bytes` of dynamic LDS on the CURRENT device
+// opt the two instances that (nvp, nw, tree_small) selects, without and with velocity limits, into `bytes` of dynamic LDS on
+// the CURRENT device
 extern "C" hipError_t gmr_ik_set_max_smem(int nvp, int nw, int tree_small, int bytes) {
-  const void* f = nullptr;
+  const void* f[2] = {nullptr, nullptr};
   switch (nvp) {
-    case 28: f = kernel_of<28>(nw, tree_small); break;
-    case 32: f = kernel_of<32>(nw, tree_small); break;
-    case 36: f = kernel_of<36>(nw, tree_small); break;
-    case 48: f = kernel_of<48>(nw, tree_small); break;
+    case 28: f[0] = kernel_of<28, false>(nw, tree_small); f[1] = kernel_of<28, true>(nw, tree_small); break;
+    case 32: f[0] = kernel_of<32, false>(nw, tree_small); f[1] = kernel_of<32, true>(nw, tree_small); break;
+    case 36: f[0] = kernel_of<36, false>(nw, tree_small); f[1] = kernel_of<36, true>(nw, tree_small); break;
+    case 48: f[0] = kernel_of<48, false>(nw, tree_small); f[1] = kernel_of<48, true>(nw, tree_small); break;
     default: return hipErrorInvalidValue;
   }
-  return hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  const hipError_t e = hipFuncSetAttribute(f[0], hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  return e != hipSuccess ? e : hipFuncSetAttribute(f[1], hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
 #endif  // GMR_IK_WALKS_ONLY

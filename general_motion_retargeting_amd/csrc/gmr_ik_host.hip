@@ -29,6 +29,8 @@ struct gmr_solver {
   gmr::IkLayout layout4;         // main wave + 3 helpers per stream (few streams: latency shape)
   gmr::DeviceBlock image4;
   int force_waves = 0;           // 0 = choose by stream count, 1 or 4 = forced (gmr_solver_set_waves)
+  double vmax[GMR_MAX_HINGES];   // velocity limit of every hinge, rad/s; +inf = none (gmr_solver_set_velocity_limits)
+  int vlim = 0;                  // some hinge has a finite one: the latency kernel's instances that clamp (gmr_ik.hip: VLIM)
   gmr::IkParams params;
   gmr::DeviceBlock image;        // host-built LDS image of the constants (gmr_ik_layout.h)
   gmr::WideLayout wide;          // throughput shape (gmr_ik_wide.hip): ok = 0 when the robot does not fit it
@@ -104,6 +106,7 @@ int gmr_solver_create(const gmr_model_t* model, const gmr_taskset_t* taskset, gm
   if (!s) return fail(GMR_ERR_ARG, "out of host memory");
   s->model = *model;
   s->ts = *taskset;
+  std::fill(s->vmax, s->vmax + GMR_MAX_HINGES, (double)INFINITY);
   if (gmr::ik_padded_nv(s->model.nv) < 0) { delete s; return fail(GMR_ERR_ARG, "nv = %d > 48 is not supported", s->model.nv); }
   s->params = gmr::make_ik_params(s->model, s->ts);
   hipError_t e = hipSuccess;
@@ -177,6 +180,37 @@ int gmr_solver_set_dispatch(gmr_solver_t* s, int frames_per_item) {
   return GMR_OK;
 }
 
+// The velocity bounds are one table of vmax * timestep per dof in each of the solver's device images (gmr_ik_layout.h:
+// IK_VDT_N, gmr_ik_wide_layout.h: WideImg::vdt), written in place: the images keep their addresses, so a job table that
+// names them needs no rebuilding.  Launches issued before this call finish on the old table.
+int gmr_solver_set_velocity_limits(gmr_solver_t* s, const double* vmax, int n) {
+  if (!s) return fail(GMR_ERR_ARG, "null solver");
+  const int nh = s->model.nhinge;
+  if (vmax ? n != nh : (n != 0 && n != nh)) return fail(GMR_ERR_ARG, "velocity limits: n = %d, the robot has %d hinges", n, nh);
+  for (int h = 0; vmax && h < nh; h++)
+    if (!(vmax[h] > 0.0)) return fail(GMR_ERR_ARG, "velocity limit of hinge %d is %g: must be positive (+inf = none)", h, vmax[h]);
+  double next[GMR_MAX_HINGES];
+  for (int h = 0; h < GMR_MAX_HINGES; h++) next[h] = vmax && h < nh ? vmax[h] : (double)INFINITY;
+  double vdt[64];
+  gmr::ik_fill_vdt(s->model, next, vdt, 64);
+  GMR_NAMED_HIP_TRY("velocity limits", hipDeviceSynchronize());
+  if (s->image.data()) GMR_NAMED_HIP_TRY("velocity limits", hipMemcpy(s->image.data() + s->layout.smem_bytes, vdt, gmr::IK_VDT_N * 8, hipMemcpyHostToDevice));
+  if (s->layout4.tree_ok && s->image4.data())
+    GMR_NAMED_HIP_TRY("velocity limits", hipMemcpy(s->image4.data() + s->layout4.smem_bytes, vdt, gmr::IK_VDT_N * 8, hipMemcpyHostToDevice));
+  if (s->wide.ok) GMR_NAMED_HIP_TRY("velocity limits", hipMemcpy(s->wide_image.data() + gmr::wide_img().vdt, vdt, 64 * 8, hipMemcpyHostToDevice));
+  memcpy(s->vmax, next, sizeof next);
+  s->vlim = 0;
+  for (int h = 0; h < nh; h++) s->vlim |= std::isfinite(next[h]) ? 1 : 0;
+  return GMR_OK;
+}
+
+int gmr_solver_velocity_limits(const gmr_solver_t* s, double* vmax_out, int n) {
+  if (!s) return fail(GMR_ERR_ARG, "null solver");
+  if (!vmax_out || n != s->model.nhinge) return fail(GMR_ERR_ARG, "velocity limits: n = %d, the robot has %d hinges", n, s->model.nhinge);
+  memcpy(vmax_out, s->vmax, (size_t)n * sizeof(double));
+  return GMR_OK;
+}
+
 int gmr_retarget_lds_bytes(const gmr_solver_t* s) { return !s ? 0 : s->layout4.tree_ok ? s->layout4.smem_bytes : s->layout.smem_bytes; }
 
 
@@ -242,7 +276,7 @@ static int launch_job(const gmr_job_t& J, int flags, hipStream_t stream, unsigne
   else
     GMR_HIP_TRY(gmr_launch_ik_streams((const uint4*)(helpers ? s->image4 : s->image).data(), helpers ? &s->layout4 : &s->layout, &s->params,
                                       J.S, J.T, J.q0, J.human, J.len, J.scale, flags, J.q_out, J.nsolve, J.status, J.tgt_out, J.err_out,
-                                      stream, d_prof));
+                                      stream, d_prof, s->vlim));
   return GMR_OK;
 }
 

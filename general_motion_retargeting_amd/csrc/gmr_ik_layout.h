@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <vector>
 
@@ -13,6 +14,10 @@ namespace gmr {
 
 constexpr int IK_MAX_ZERO = 64;  // H cells of entries whose halves are added (gmr_ik_layout.h: make_ik_schedule)
 constexpr int IK_MAX_HOPS = 5;  // pointer-jumping rounds of the FK: 2^5 = 32 > GMR_MAX_DEPTH
+// The velocity bound of one solve, |dq_i| <= vdt_i = vmax_i * timestep (mink VelocityLimit; +inf = none, and always for
+// the six dofs of the free joint): f64 [IK_VDT_N], index = dof.  It lives in the GLOBAL image only, right behind the
+// part that is copied to LDS (byte offset = smem_bytes), so that no LDS layout grows by it.
+constexpr int IK_VDT_N = 48;    // >= the largest padded nv; 384 B: the sections behind it stay 16-byte aligned
 
 // rows of the dense register-resident factorisation are padded to one of these sizes = the SIZE CLASS of a
 // robot.  Every LDS offset is a compile-time constant of the class (and of the launch shape), so that the
@@ -414,7 +419,7 @@ inline IkLayout make_ik_layout(const gmr_model_t& m, const gmr_taskset_t& ts, co
     L.g_items[s] = -1;
   }
   L.smem_bytes = L.o.n_double * 8 + L.o.n_short * 2 + w * 4;
-  L.image_bytes = L.smem_bytes;                    // a multiple of 16
+  L.image_bytes = L.smem_bytes + IK_VDT_N * 8;     // a multiple of 16; the velocity bounds follow the LDS part
   if (nw == 1)
     for (int s = 0; s < 2; s++) { L.g_items[s] = L.image_bytes / 4; L.image_bytes += (L.nitem[s] * 8 + 15) / 16 * 16; }
   return L;
@@ -450,6 +455,14 @@ inline IkParams make_ik_params(const gmr_model_t& m, const gmr_taskset_t& ts) {
 // Host-built image of one stream's LDS: the constant regions filled, the state regions zero.  The
 // kernel prologue is then one coalesced global -> LDS copy instead of dozens of scattered loads
 // (matters for the per-frame entry point, where the prologue is paid on every call).
+// the velocity-bound table of a model: vdt[6 + h] = vmax[h] * timestep (vmax null: none), +inf everywhere else
+inline void ik_fill_vdt(const gmr_model_t& m, const double* vmax, double* vdt, int n) {
+  for (int d = 0; d < n; d++) {
+    const int h = d - 6;
+    vdt[d] = (vmax && h >= 0 && h < m.nhinge) ? vmax[h] * m.timestep : HUGE_VAL;
+  }
+}
+
 inline std::vector<char> make_ik_image(const gmr_model_t& m, const gmr_taskset_t& ts, const IkSchedule& sch,
                                        const IkLayout& L) {
   std::vector<char> img((size_t)L.image_bytes, 0);
@@ -487,6 +500,7 @@ inline std::vector<char> make_ik_image(const gmr_model_t& m, const gmr_taskset_t
     const double prm[6] = {ts.damping, ts.lm_damping, ts.tol, ts.limit_gain, ts.ground_offset, m.timestep};
     for (int i = 0; i < 6; i++) sm[L.o.params + i] = prm[i];
   }
+  ik_fill_vdt(m, nullptr, reinterpret_cast<double*>(img.data() + L.smem_bytes), IK_VDT_N);   // none: the setter writes the device copy
   for (int i = 0; i < L.nhum; i++) {
     sm[L.o.scale + i] = ts.scale[i];
     for (int a = 0; a < 3; a++) sm[L.o.pos_off + 3 * i + a] = ts.pos_off[i][a];

@@ -253,7 +253,8 @@ __device__ __forceinline__ void pairs_wide(double* sm, const char* __restrict__ 
   if (lane == 6) cpart[WD_P] = 0.0;          // and the share absent (task, dof) pairs gather
 }
 
-// (c) lane = dof: gather c; bounds of the limited hinges (mink ConfigurationLimit)
+// (c) lane = dof: gather c; bounds of the limited hinges (mink ConfigurationLimit), clamped into this dof's velocity
+// bound [-vdt, vdt] (mink VelocityLimit; vdt = +inf leaves both bits as they are)
 template <class DimsRef>
 __device__ __forceinline__ void cvec_wide(DimsRef D, double* sm, const char* __restrict__ img, int stage,
                                           double limit_gain, int lane) {
@@ -266,6 +267,7 @@ __device__ __forceinline__ void cvec_wide(DimsRef D, double* sm, const char* __r
     for (int g = 0; g < WD_K / 2; g++) w[g] = ci[64 * g];
     const double2 lim = img_at<double2>(img, IM.lim)[lane];
     const uint32_t limited = img_at<uint32_t>(img, IM.limi)[lane];
+    const double vdt = img_at<double>(img, IM.vdt)[lane];
     double cc = 0.0;
 #pragma unroll
     for (int k = 0; k < WD_K; k++) {
@@ -279,8 +281,8 @@ __device__ __forceinline__ void cvec_wide(DimsRef D, double* sm, const char* __r
       hi = limit_gain * (lim.y - th);
       lo = -limit_gain * (th - lim.x);
     }
-    (sm + LD.lo)[lane] = lo;
-    (sm + LD.hi)[lane] = hi;
+    (sm + LD.lo)[lane] = fmin(fmax(lo, -vdt), vdt);
+    (sm + LD.hi)[lane] = fmin(fmax(hi, -vdt), vdt);
   }
 }
 

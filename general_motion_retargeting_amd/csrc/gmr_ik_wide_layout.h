@@ -117,6 +117,7 @@ struct WideImg {
   int cidx[2];    // u16 [WD_K][64]     byte offset of the c share of (task k, dof = lane) in cpart (absent: slot WD_P), as u32 [WD_K/2][64]
   int lim;        // f64 [64][2] range lo, hi ; then u32 [64] limited                             lane = dof
   int limi;
+  int vdt;        // f64 [64]  velocity bound of one solve, vmax * dt (+inf: none; the free joint's six always)  lane = dof
   int tree;       // i32 [64] dof of solver lane (16 l + row) or -1
   int prm;        // f64 [8]  damping, lm_damping, tol, limit_gain, ground_offset, dt (scalar loads where used)
   int items[2];   // u64 [ntrip][64]   (runtime size: last)
@@ -138,6 +139,7 @@ constexpr WideImg wide_img() {
   }
   I.lim = o; o += wd_up16(64 * 2 * 8);
   I.limi = o; o += wd_up16(64 * 4);
+  I.vdt = o; o += wd_up16(64 * 8);
   I.tree = o; o += wd_up16(64 * 4);
   I.prm = o; o += 64;
   I.fixed_bytes = o;
@@ -452,6 +454,7 @@ inline WideLayout make_wide_layout(const gmr_model_t& m, const gmr_taskset_t& ts
     F(I.lim)[2 * d + 1] = lim ? m.range_hi[h] : 0.0;
     U(I.limi)[d] = lim ? 1u : 0u;
   }
+  ik_fill_vdt(m, nullptr, F(I.vdt), 64);       // none: gmr_solver_set_velocity_limits writes the device copy
   {
     const double prm[6] = {ts.damping, ts.lm_damping, ts.tol, ts.limit_gain, ts.ground_offset, m.timestep};
     for (int i = 0; i < 6; i++) F(I.prm)[i] = prm[i];

@@ -27,7 +27,7 @@ extern "C" {
 hipError_t gmr_launch_ik_streams(const uint4* d_image, const gmr::IkLayout* L, const gmr::IkParams* P, int S, int T, const double* d_q0,
                                  const double* d_human, const int32_t* d_len, const double* d_scale, int flags, double* d_q_out,
                                  int32_t* d_nsolve, int32_t* d_status, double* d_tgt_out, double* d_err_out, hipStream_t stream,
-                                 unsigned long long* d_prof);
+                                 unsigned long long* d_prof, int vlim);    // vlim: the image's velocity bounds are not all +inf
 hipError_t gmr_ik_set_max_smem(int nvp, int nw, int tree_small, int bytes);
 // gmr_ik_wide.hip
 hipError_t gmr_launch_ik_wide(const char* d_image, const gmr::WideLayout* L, const gmr::IkParams* P, int S, int T, const double* d_q0,

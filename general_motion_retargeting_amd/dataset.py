@@ -548,8 +548,12 @@ class ClipRetargeter:
     _heights: Optional[np.ndarray] = None
 
     def __init__(self, src_human: str, tgt_robot: str, actual_human_height=None, height_adjust: bool = True,
-                 root_origin_offset: bool = True, offset_to_ground: bool = False, chunk=None, library=False):
-        """``actual_human_height``: one height for every clip (a number or None: the solver is built for it, as ever), or a
+                 root_origin_offset: bool = True, offset_to_ground: bool = False, chunk=None, library=False,
+                 velocity_limit=None):
+        """``velocity_limit`` (default None: off): per-joint velocity limits of every solve, a scalar in rad/s, an array
+        ``[nhinge]`` or a dict ``{joint name: rad/s}`` (``GeneralMotionRetargeting.set_velocity_limit``: a bound per solve, not
+        on the velocity between frames).
+        ``actual_human_height``: one height for every clip (a number or None: the solver is built for it, as ever), or a
         sequence with one height per clip of a call (``add(clip, height=)`` in the staged protocol): the solver is built from
         the unscaled config and every clip carries its height as a scale row of the ONE job, the bits of a retargeter built
         for that height.  Per-clip heights do not go with a ``chunk`` spec that takes effect (the slots of a chunk job are
@@ -563,7 +567,8 @@ class ClipRetargeter:
         and ``warm_solves``; ``chunk_summary`` the totals over all batches."""
         self._per_clip = actual_human_height is not None and np.ndim(actual_human_height) > 0
         self._heights = np.asarray(actual_human_height, dtype=np.float64).reshape(-1) if self._per_clip else None
-        self.gmr = GeneralMotionRetargeting(src_human, tgt_robot, actual_human_height=None if self._per_clip else actual_human_height)
+        self.gmr = GeneralMotionRetargeting(src_human, tgt_robot, actual_human_height=None if self._per_clip else actual_human_height,
+                                            velocity_limit=velocity_limit)
         self.height_adjust, self.root_origin_offset, self.offset_to_ground = height_adjust, root_origin_offset, offset_to_ground
         self.chunk = chunk
         self._library_mode = None if not library else ("world" if library is True else str(library))
@@ -740,8 +745,8 @@ class ClipRetargeter:
 def retarget_clips(src_human: str, tgt_robot: str, clips: Sequence, fps: Sequence[float],
                    actual_human_height=None, height_adjust: bool = True,
                    root_origin_offset: bool = True, offset_to_ground: bool = False, chunk=None, report: Optional[List] = None,
-                   library=False):
-    """Retarget many clips of one (source, robot, height) in ONE IK launch.  ``library`` (``True`` | ``"world"`` | ``"reference"``;
+                   library=False, velocity_limit=None):
+    """Retarget many clips of one (source, robot, height) in ONE IK launch.  ``velocity_limit``: see :class:`ClipRetargeter`.  ``library`` (``True`` | ``"world"`` | ``"reference"``;
     default off): returns ``(motions, motion_library.MotionLibrary)``, the library filled on the device from the post-processed
     batch; ``motions`` are the same bytes as without it.  ``chunk`` (``chunking.ChunkSpec`` or ``"auto"``; default
     off) cuts long clips into independently running chunks -- NOT parity; the per-clip chunk reports are appended to ``report``.
@@ -766,11 +771,12 @@ def retarget_clips(src_human: str, tgt_robot: str, clips: Sequence, fps: Sequenc
             for h in dict.fromkeys(heights):
                 idxs = [i for i, x in enumerate(heights) if x == h]
                 for i, md in zip(idxs, retarget_clips(src_human, tgt_robot, [clips[i] for i in idxs], [fps[i] for i in idxs], h, height_adjust,
-                                                      root_origin_offset, offset_to_ground, chunk=chunk, report=report)):
+                                                      root_origin_offset, offset_to_ground, chunk=chunk, report=report,
+                                                      velocity_limit=velocity_limit)):
                     out[i] = md
             return out
     rt = ClipRetargeter(src_human, tgt_robot, actual_human_height, height_adjust, root_origin_offset, offset_to_ground, chunk=chunk,
-                        library=library)
+                        library=library, velocity_limit=velocity_limit)
     out = rt(clips, fps)
     if report is not None and rt.chunk_report is not None:
         report.extend(rt.chunk_report)
@@ -792,7 +798,8 @@ def retarget_mixed(groups: Sequence[Dict], offset_to_ground: bool = False, slice
     overlap the kernels.  Bit-identical to retargeting every group by itself.
 
     ``groups[i]`` = ``{"src_human", "tgt_robot", "human": f64[S,T,nhuman,7], optional "lens",
-    "actual_human_height"}``, the height a number for the group or one per stream (``f64[S]``: the group's solver is built
+    "actual_human_height", "velocity_limit"}`` (the limit as in ``GeneralMotionRetargeting``: it is the group's own, each job
+    launches with its solver's table), the height a number for the group or one per stream (``f64[S]``: the group's solver is built
     from the unscaled config and the heights travel as scale rows); arrays allocated with ``_lib.pinned_empty`` are copied asynchronously.
     Returns a list of ``(qpos[S,T,nq], nsolve[S,T,2], status[S])``.
     """
@@ -800,7 +807,8 @@ def retarget_mixed(groups: Sequence[Dict], offset_to_ground: bool = False, slice
     for g in groups:
         h = g.get("actual_human_height")
         per_stream = h is not None and np.ndim(h) > 0
-        gmr = GeneralMotionRetargeting(g["src_human"], g["tgt_robot"], actual_human_height=None if per_stream else h)
+        gmr = GeneralMotionRetargeting(g["src_human"], g["tgt_robot"], actual_human_height=None if per_stream else h,
+                                       velocity_limit=g.get("velocity_limit"))
         keep.append(gmr)
         jobs.append({"solver": gmr.hip_solver, "human": g["human"], "lens": g.get("lens"),
                      "scales": gmr.stream_scales(len(g["human"]), heights=h) if per_stream else None})
@@ -809,7 +817,7 @@ def retarget_mixed(groups: Sequence[Dict], offset_to_ground: bool = False, slice
 
 
 def retarget_bvh_files(bvh_files: Sequence[str], tgt_robot: str, fps: float = 30.0, height_adjust: bool = False,
-                       root_origin_offset: bool = False, chunk=None, report: Optional[List] = None) -> List[Dict]:
+                       root_origin_offset: bool = False, chunk=None, report: Optional[List] = None, velocity_limit=None) -> List[Dict]:
     """``scripts/bvh_to_robot_dataset.py:60-152`` for a list of files: every BVH clip becomes one
     stream of ONE launch (LAFAN1: 77 ragged clips).  Both adjustments default to off like that script
     (``HEIGHT_ADJUST = False``, :128); the loader's hard-coded height 1.75 is used (lafan1.py:39).
@@ -822,12 +830,14 @@ def retarget_bvh_files(bvh_files: Sequence[str], tgt_robot: str, fps: float = 30
     else:
         clips = [load_lafan1_packed(f, gmr.human_body_names)[0] for f in bvh_files]
     return retarget_clips("bvh", tgt_robot, clips, [fps] * len(clips), actual_human_height=1.75,
-                          height_adjust=height_adjust, root_origin_offset=root_origin_offset, chunk=chunk, report=report)
+                          height_adjust=height_adjust, root_origin_offset=root_origin_offset, chunk=chunk, report=report,
+                          velocity_limit=velocity_limit)
 
 
 def retarget_smplx_files(smplx_files: Sequence[str], smplx_body_model_path: str, tgt_robot: str, tgt_fps: int = 30,
                          height_adjust: bool = True, root_origin_offset: bool = True,
-                         skip_errors: bool = True, chunk=None, report: Optional[List] = None) -> List[Optional[Dict]]:
+                         skip_errors: bool = True, chunk=None, report: Optional[List] = None,
+                         velocity_limit=None) -> List[Optional[Dict]]:
     """``scripts/smplx_to_robot_dataset.py:39-146`` (``process_file``) for a list of AMASS-style SMPL-X
     files, everything after the file read on the device: joints-only body model + fps alignment
     (utils/smpl.py) -> packed frames -> IK (one group launch for all heights) -> FK post-processing.
@@ -844,7 +854,7 @@ def retarget_smplx_files(smplx_files: Sequence[str], smplx_body_model_path: str,
             print(f"Error loading {f}: {e}")
     out: List[Optional[Dict]] = [None] * len(smplx_files)
     for i, md in zip(ok, retarget_smplx_loaded(raws, smplx_body_model_path, tgt_robot, tgt_fps, height_adjust, root_origin_offset,
-                                               chunk=chunk, report=report)):
+                                               chunk=chunk, report=report, velocity_limit=velocity_limit)):
         out[i] = md
     return out
 
@@ -1183,8 +1193,8 @@ def _load_bvh_clip(args):
 
 def run_bvh_dataset(src_folder: str, tgt_folder: str, robot: str, override: bool = False, batch_files: int = 0,
                     retarget=None, verbose: bool = True, frames_budget: int = 1 << 19, loader_workers: int = -1,
-                    rank: int = 0, world: int = 1, load=None, stats: Optional[Dict] = None, chunk=None) -> int:
-    """``bvh_to_robot_dataset.py`` (:60-157) on the pipeline above.  ``chunk``: see :class:`ClipRetargeter` (``stats["chunk"]`` gets the totals).  ``batch_files`` > 0 additionally caps the clips of a
+                    rank: int = 0, world: int = 1, load=None, stats: Optional[Dict] = None, chunk=None, velocity_limit=None) -> int:
+    """``bvh_to_robot_dataset.py`` (:60-157) on the pipeline above.  ``velocity_limit``: see :class:`ClipRetargeter`.  ``chunk``: see :class:`ClipRetargeter` (``stats["chunk"]`` gets the totals).  ``batch_files`` > 0 additionally caps the clips of a
     launch (0: only the frames budget does).  ``retarget(clips, files)`` and ``load(file)`` are injectable (tests)."""
     # the partition is computed on ALL source files (a rank that starts later must not see another partition because
     # some targets exist by then); skip-if-exists is applied to the rank's own shard
@@ -1197,7 +1207,8 @@ def run_bvh_dataset(src_folder: str, tgt_folder: str, robot: str, override: bool
     names = gmr.human_body_names if gmr is not None else None
     rt = None
     if retarget is None:
-        rt = ClipRetargeter("bvh", robot, 1.75, height_adjust=False, root_origin_offset=False, chunk=chunk)    # HEIGHT_ADJUST = False, :128
+        rt = ClipRetargeter("bvh", robot, 1.75, height_adjust=False, root_origin_offset=False, chunk=chunk,    # HEIGHT_ADJUST = False, :128
+                            velocity_limit=velocity_limit)
         retarget = _Staged(rt, 30)
     raw = rt is not None and bvh_path() == "device"        # the loaders only parse; gmr_bvh_frames_dev computes the frames
     try:
@@ -1255,7 +1266,7 @@ def _load_smplx_raw(f):
 def retarget_smplx_loaded(raws: Sequence[Dict], smplx_body_model_path: str, tgt_robot: str, tgt_fps: int = 30,
                           height_adjust: bool = True, root_origin_offset: bool = True,
                           timing: Optional[Dict[str, float]] = None, chunk=None, report: Optional[List] = None,
-                          library=False):
+                          library=False, velocity_limit=None):
     """``process_file`` (smplx_to_robot_dataset.py:39-146) for many already-read files: joints-only body model and fps
     alignment on the device, ONE solver (built from the unscaled config, kept from batch to batch) and ONE IK job for the
     whole batch -- a file's height comes from its betas (:36-39) and travels as that clip's scale row
@@ -1283,10 +1294,11 @@ def retarget_smplx_loaded(raws: Sequence[Dict], smplx_body_model_path: str, tgt_
     gmr_of: Dict[Optional[float], GeneralMotionRetargeting] = {}
     if merged:
         gmr_of[None] = _smplx_base_retargeter(tgt_robot)
+        gmr_of[None].set_velocity_limit(velocity_limit)      # (the kept retargeter serves every batch: this batch's limit, or none)
     else:
         for h in height.values():
             if h not in gmr_of:
-                gmr_of[h] = GeneralMotionRetargeting("smplx", tgt_robot, actual_human_height=h)
+                gmr_of[h] = GeneralMotionRetargeting("smplx", tgt_robot, actual_human_height=h, velocity_limit=velocity_limit)
     group_of = {i: (None if merged else height[i]) for i in height}
     device = post_path() == "device" and bool(raws)
     any_g = next(iter(gmr_of.values()), None)
@@ -1361,7 +1373,7 @@ def _smplx_device_post(xml_file: str):
 def run_smplx_dataset(src_folder: str, tgt_folder: str, robot: str, smplx_folder: str, override: bool = False,
                       hard_motion_files: Sequence[str] = (), batch_files: int = 0, retarget=None, verbose: bool = True,
                       frames_budget: int = 1 << 19, loader_workers: int = -1, rank: int = 0, world: int = 1, load=None,
-                      stats: Optional[Dict] = None, chunk=None) -> int:
+                      stats: Optional[Dict] = None, chunk=None, velocity_limit=None) -> int:
     """``smplx_to_robot_dataset.py:main`` (:171-242) on the pipeline above.  ``retarget(raws, files)`` defaults to
     :func:`retarget_smplx_loaded`, ``load(file)`` to the npz reader (tests inject stand-ins).  Returns the number of pkl
     files this rank wrote."""
@@ -1380,7 +1392,7 @@ def run_smplx_dataset(src_folder: str, tgt_folder: str, robot: str, smplx_folder
     if retarget is None:
         def retarget(raws, files):
             rep: List = []
-            out = retarget_smplx_loaded(raws, smplx_folder, robot, timing=timing, chunk=chunk, report=rep)
+            out = retarget_smplx_loaded(raws, smplx_folder, robot, timing=timing, chunk=chunk, report=rep, velocity_limit=velocity_limit)
             if rep:
                 chunking.summarize(rep, chunk_summary)
             return out
@@ -1448,6 +1460,9 @@ def main(argv=None) -> int:
     ap.add_argument("--frames_budget", type=int, default=1 << 19, help="padded frames (clips x longest clip) of one IK launch")
     ap.add_argument("--gpus", type=int, default=1, help="ranks = GPUs of this node; the files are LPT-sharded over them")
     ap.add_argument("--quiet", action="store_true")
+    ap.add_argument("--velocity_limit", type=float, default=None, metavar="RAD_PER_S",
+                    help="per-joint velocity limit of every IK solve on every motor joint (upstream's use_velocity_limit: 9.42 = 3 pi); "
+                         "a bound per solve, not on the velocity between frames (default: none)")
     chunking.add_cli_arguments(ap)
     a = ap.parse_args(argv)
     chunk = chunking.spec_from_args(a)
@@ -1474,7 +1489,8 @@ def main(argv=None) -> int:
     stats: Dict = {}
     if a.source == "bvh":
         n = run_bvh_dataset(a.src_folder, a.tgt_folder, a.robot, a.override, a.batch_files, verbose=not a.quiet,
-                            frames_budget=a.frames_budget, loader_workers=a.num_cpus, rank=rank, world=world, stats=stats, chunk=chunk)
+                            frames_budget=a.frames_budget, loader_workers=a.num_cpus, rank=rank, world=world, stats=stats, chunk=chunk,
+                            velocity_limit=a.velocity_limit)
     else:
         from .params import ASSET_ROOT
         if ASSET_ROOT is None and (a.smplx_folder is None or a.hard_motions is None):
@@ -1485,7 +1501,7 @@ def main(argv=None) -> int:
                                                                     str(assets / "hard_motions" / "1.txt")]
         n = run_smplx_dataset(a.src_folder, a.tgt_folder, a.robot, smplx_folder, a.override, hard, a.batch_files,
                               verbose=not a.quiet, frames_budget=a.frames_budget, loader_workers=a.num_cpus, rank=rank,
-                              world=world, stats=stats, chunk=chunk)
+                              world=world, stats=stats, chunk=chunk, velocity_limit=a.velocity_limit)
     dt = time.perf_counter() - t0
     if chunk is not None:        # one line per rank: the mode is not parity, so what it did to the seams is always said
         print(json.dumps({"chunk_summary": {"rank": rank, **stats.get("chunk", {"clips_split": 0})}}))

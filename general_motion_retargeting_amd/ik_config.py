@@ -294,3 +294,36 @@ def pack_taskset(model: RobotModel, tt: TaskTables) -> np.ndarray:
                 p += 1
         r["npair"][s] = p
     return t
+
+
+# ---- per-joint velocity limits (mink.VelocityLimit) -------------------------------------------------------------------------
+DEFAULT_VELOCITY_LIMIT = 3.0 * np.pi      # rad/s on every motor joint: upstream's use_velocity_limit=True
+
+
+def velocity_limit_table(model: RobotModel, use_velocity_limit: bool = False, velocity_limit=None) -> Optional[np.ndarray]:
+    """The per-hinge table ``f64[nhinge]`` (rad/s, ``inf`` = none) of the two constructor arguments, or None for no limit.
+
+    ``velocity_limit`` may be a scalar (every hinge), an array ``[nhinge]`` in ``model.joint_names`` order or a dict
+    ``{joint name: rad/s}`` (joints not named get ``inf``); ``use_velocity_limit=True`` alone means 3 pi on every hinge.
+    Every value must be > 0 and not NaN; an unknown joint name is a KeyError."""
+    nh = len(model.joint_names)
+    if velocity_limit is None:
+        return np.full(nh, DEFAULT_VELOCITY_LIMIT) if use_velocity_limit else None
+    if isinstance(velocity_limit, dict):
+        table = np.full(nh, np.inf)
+        for name, v in velocity_limit.items():
+            if name not in model.joint_names:
+                raise KeyError(f"velocity_limit: the robot has no hinge joint {name!r}")
+            table[model.joint_names.index(name)] = float(v)
+    else:
+        v = np.asarray(velocity_limit, dtype=np.float64)
+        if v.ndim == 0:
+            table = np.full(nh, float(v))
+        elif v.shape == (nh,):
+            table = v.copy()
+        else:
+            raise ValueError(f"velocity_limit must be a scalar, a dict or an array [{nh}], got shape {v.shape}")
+    if not (table > 0.0).all():        # (NaN compares false)
+        bad = int(np.flatnonzero(~(table > 0.0))[0])
+        raise ValueError(f"velocity_limit of {model.joint_names[bad]!r} is {table[bad]}: must be > 0 (inf = none)")
+    return table

@@ -22,7 +22,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from .ik_config import TaskTables, build_task_tables, pack_model, pack_taskset, scale_rows
+from .ik_config import TaskTables, build_task_tables, pack_model, pack_taskset, scale_rows, velocity_limit_table
 from .models import load_ik_config, load_robot
 from .params import IK_CONFIG_DICT, ROBOT_XML_DICT
 
@@ -75,7 +75,12 @@ class GeneralMotionRetargeting:
         solver: str = "daqp",
         damping: float = 5e-1,
         verbose: bool = False,
+        use_velocity_limit: bool = False,
+        velocity_limit=None,
     ) -> None:
+        """``use_velocity_limit`` / ``velocity_limit``: per-joint velocity limits in the QP of every solve (upstream's
+        ``use_velocity_limit=True`` = ``mink.VelocityLimit`` at 3 pi rad/s on every motor joint); see
+        :meth:`set_velocity_limit`.  Off by default."""
         self.xml_file = str(ROBOT_XML_DICT[tgt_robot])
         if verbose:
             print("Use robot model: ", self.xml_file)
@@ -110,6 +115,8 @@ class GeneralMotionRetargeting:
         self._model_blob = pack_model(self.model)
         self._taskset_blob = pack_taskset(self.model, tt)
         self._solver: Optional[_lib.Solver] = None
+        self.use_velocity_limit = bool(use_velocity_limit) or velocity_limit is not None
+        self._velocity_limit = velocity_limit_table(self.model, use_velocity_limit, velocity_limit)
         self.setup_retarget_configuration()
 
     # ------------------------------------------------------------------ #
@@ -121,7 +128,30 @@ class GeneralMotionRetargeting:
     def hip_solver(self) -> _lib.Solver:
         if self._solver is None:
             self._solver = _lib.Solver(self._model_blob, self._taskset_blob)   # raises without GPU/library
+            if self._velocity_limit is not None:
+                self._solver.set_velocity_limit(self._velocity_limit)
         return self._solver
+
+    def set_velocity_limit(self, velocity_limit=None, use_velocity_limit: bool = False) -> None:
+        """Per-joint velocity limits for every later call of this object (all entry points: they launch from its solver).
+        ``velocity_limit``: a scalar in rad/s for every hinge, an array ``[nhinge]`` in ``model.joint_names`` order, or a
+        dict ``{joint name: rad/s}`` (joints not named: none); ``use_velocity_limit=True`` alone: 3 pi on every hinge;
+        neither: no limit.  Every solve then keeps ``|dq_h| <= vmax_h * model.timestep`` next to the joint ranges, as
+        ``mink.VelocityLimit`` does.  NOTE: that bounds ONE ``solve_ik`` call, as in mink; a frame runs up to 22 solves
+        (two stages of ``max_iter + 1``), so a joint may move up to 22 times that far between two frames -- this is not a
+        limit on the joint velocity of the retargeted clip.  The floating base is never bounded."""
+        table = velocity_limit_table(self.model, use_velocity_limit, velocity_limit)
+        same = (table is None and self._velocity_limit is None) or \
+            (table is not None and self._velocity_limit is not None and np.array_equal(table, self._velocity_limit))
+        self._velocity_limit = table
+        self.use_velocity_limit = table is not None
+        if self._solver is not None and not same:
+            self._solver.set_velocity_limit(table)
+
+    @property
+    def velocity_limit(self) -> Optional[np.ndarray]:
+        """The table in force: ``f64[nhinge]`` rad/s (``inf`` = none for that hinge) or None."""
+        return None if self._velocity_limit is None else self._velocity_limit.copy()
 
     @property
     def human_body_names(self) -> List[str]:

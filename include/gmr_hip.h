@@ -90,6 +90,19 @@ int gmr_solver_set_waves(gmr_solver_t* solver, int waves_per_stream);
  * 0 = one workgroup per stream for all of its frames.  Results are bit-identical either way.  The reference's analogue
  * is the chunking of `mp.Pool.map` over files (scripts/smplx_to_robot_dataset.py:241-242). */
 int gmr_solver_set_dispatch(gmr_solver_t* solver, int frames_per_item);
+/* Per-joint velocity limits in the QP box: mink.VelocityLimit, what GeneralMotionRetargeting(use_velocity_limit=True)
+ * appends to the limits of every solve_ik call upstream.  vmax f64 [nhinge], rad/s, in hinge order; +inf = no limit for
+ * that hinge; NULL (n = 0 or nhinge) = none at all, the state of a new solver.  Every solve then keeps
+ *     |dq_h| <= vdt_h = vmax_h * timestep
+ * on top of the joint-range box: lo = min(max(lo_cfg, -vdt_h), vdt_h), hi likewise, so that a joint that starts outside
+ * its range by more than vdt_h walks back at full rate (mink raises there).  This bounds ONE solve, as in mink -- a frame
+ * runs up to 2 * (max_iter + 1) solves, so it is NOT a bound on the joint velocity between frames.  The six dofs of the
+ * free joint are never bounded.  A property of the handle: every launch from this solver issued after the call returns
+ * uses it (streams, scaled streams, group jobs -- each job its own solver's table --, windows, queued or direct
+ * dispatch); launches issued before finish on the old table.  n != nhinge, a NaN or a value <= 0 is GMR_ERR_ARG.
+ * With no finite limit the kernels compute the bits they compute without this call. */
+int gmr_solver_set_velocity_limits(gmr_solver_t* solver, const double* vmax, int n);
+int gmr_solver_velocity_limits(const gmr_solver_t* solver, double* vmax_out, int n);
 
 /* ---- H2-H7: the retargeting loop ---------------------------------------------------------- */
 /* Replaces the caller loop `for frame in frames: qpos = retargeter.retarget(frame)`
