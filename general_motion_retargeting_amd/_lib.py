@@ -19,6 +19,7 @@ _lib = None
 
 FLAG_OFFSET_TO_GROUND = 1
 FLAG_EVAL_ONLY = 2
+FLAG_FRAME_LIMIT_FIRST = 4    # q0 is the pose of the frame before frame 0: the frame velocity limit bounds frame 0 too
 POST_HEIGHT_ADJUST, POST_ROOT_ORIGIN_OFFSET = 1, 2
 STATUS_OK, STATUS_QP_FAILED, STATUS_QP_MAXITER = 0, -1, -2
 
@@ -53,6 +54,8 @@ _SIGS = {
     "gmr_solver_set_dispatch": (C.c_int, [C.c_void_p, C.c_int]),
     "gmr_solver_set_velocity_limits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "gmr_solver_velocity_limits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "gmr_solver_set_frame_velocity_limits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_double]),
+    "gmr_solver_frame_velocity_limits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_double)]),
     "gmr_retarget_lds_bytes": (C.c_int, [C.c_void_p]),
     "gmr_retarget_streams_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -635,6 +638,26 @@ class Solver:
         out = np.empty(self.nv - 6, dtype=np.float64)
         check(lib().gmr_solver_velocity_limits(self.handle, _ptr(out), int(out.shape[0])))
         return out
+
+    def set_frame_velocity_limit(self, vmax, frame_dt: float = 0.0) -> None:
+        """Per-hinge FRAME velocity limits ``vmax`` f64[nhinge] in rad/s (``inf`` = none for that hinge; ``None`` = none at
+        all) at ``frame_dt`` seconds between frames, for every launch from this solver issued afterwards: the result keeps
+        ``|theta_h(t) - theta_h(t - 1)| <= vmax_h * frame_dt`` (gmr_solver_set_frame_velocity_limits).  Frame 0 of a stream is
+        free unless the launch carries ``FLAG_FRAME_LIMIT_FIRST``."""
+        if vmax is None:
+            check(lib().gmr_solver_set_frame_velocity_limits(self.handle, None, 0, C.c_double(0.0)))
+            return
+        vmax = np.ascontiguousarray(vmax, dtype=np.float64)
+        if vmax.ndim != 1:
+            raise ValueError(f"frame velocity limits must be [{self.nv - 6}], got {vmax.shape}")
+        check(lib().gmr_solver_set_frame_velocity_limits(self.handle, _ptr(vmax), int(vmax.shape[0]), C.c_double(float(frame_dt))))
+
+    def frame_velocity_limit(self):
+        """``(vmax f64[nhinge] rad/s, frame_dt)``: ``inf`` where a hinge has none, ``frame_dt`` 0 while none has."""
+        out = np.empty(self.nv - 6, dtype=np.float64)
+        dt = C.c_double(0.0)
+        check(lib().gmr_solver_frame_velocity_limits(self.handle, _ptr(out), int(out.shape[0]), C.byref(dt)))
+        return out, float(dt.value)
 
     @property
     def lds_bytes(self) -> int:

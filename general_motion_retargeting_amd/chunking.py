@@ -186,6 +186,13 @@ def summarize(reports: Sequence[Dict], into: Optional[Dict] = None) -> Dict:
     return s
 
 
+# Every chunk starts from qpos0 behind a warm-up and a bad seam is repaired by re-running the chunk from its predecessor's last
+# frame: neither the warm-up's first frame nor a seam before its repair carries |theta(t) - theta(t - 1)| <= w, and a repair
+# that does may no longer reach the frames the unbounded pass found.  No half version: the two do not go together.
+FRAME_LIMIT_REFUSAL = ("chunked retargeting does not carry the frame velocity limit across chunk seams: "
+                       "drop chunk= or clear the limit (set_frame_velocity_limit(None))")
+
+
 class ChunkRunner:
     """The pass loop on one HIP stream.  Device buffers are grow-only and reused from batch to batch::
 
@@ -226,6 +233,8 @@ class ChunkRunner:
             if spec is None:
                 continue
             sol, S, T = job.solver, int(job.S), max(int(job.T), 1)
+            if np.isfinite(sol.frame_velocity_limit()[0]).any():
+                raise ValueError(FRAME_LIMIT_REFUSAL)
             p = plan(np.asarray(lens[i], dtype=np.int32), spec.frames, spec.warmup)
             n, Tc, nq, nh = p.nchunk, p.Tc, sol.nq, sol.nhuman
             j = {"i": i, "src": job, "spec": spec, "plan": p, "S": S, "T": T, "n": n, "sol": sol}

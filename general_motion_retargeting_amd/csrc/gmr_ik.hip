@@ -513,12 +513,18 @@ __device__ __forceinline__ void pairs_from_jbody(const LT& L, double* sm, int st
     *reinterpret_cast<double*>(reinterpret_cast<char*>(sm + L.o.H) + zero_off[vlane - 64]) = 0.0;
 }
 
+// the frame window of the main wavefront's lane = dof in the VLIM instances: its width (once per launch), the angle the frame
+// started from and whether this frame is bounded (once per frame, the same for every lane)
+struct FrameWindow { double fw, th0; bool on; };
+
 // (c) lane = dof: gather c; bounds of the limited hinges (mink ConfigurationLimit); VLIM: clamped into this dof's velocity
 // bound [-vdt, vdt] (mink VelocityLimit; vdt = +inf leaves both bits as they are).  Instances without VLIM carry no
-// trace of it: they are the kernels of a solver that has no finite limit (ik_streams_kernel).
+// trace of it: they are the kernels of a solver that has no finite limit (ik_streams_kernel).  VLIM and fwd.on (wave-uniform:
+// this frame is bounded): clamped last into the frame window [th0 - fw, th0 + fw] - theta around this dof's angle th0 at the
+// start of the frame (gmr_solver_set_frame_velocity_limits; fw = +inf leaves both bits as they are).
 template <bool VLIM, class LT>
 __device__ __forceinline__ void cvec_phase(const LT& L, double* sm, int stage, const StageTabs& tb,
-                                           const short* limited, double limit_gain, double vdt, int lane) {
+                                           const short* limited, double limit_gain, double vdt, const FrameWindow& fwd, int lane) {
   lane = fresh_lane(lane);
   const int nv = L.nv;
   const char* cpart = reinterpret_cast<const char*>(sm + L.o.cpart);
@@ -540,6 +546,12 @@ __device__ __forceinline__ void cvec_phase(const LT& L, double* sm, int stage, c
     if (VLIM) {
       lo = fmin(fmax(lo, -vdt), vdt);
       hi = fmin(fmax(hi, -vdt), vdt);
+      if (fwd.on) {
+        const double th = lane >= 6 ? (sm + L.o.q)[7 + lane - 6] : 0.0;     // (the free joint's fw is +inf, its th0 zero)
+        const double lf = (fwd.th0 - fwd.fw) - th, hf = (fwd.th0 + fwd.fw) - th;
+        lo = fmin(fmax(lo, lf), hf);
+        hi = fmin(fmax(hi, lf), hf);
+      }
     }
     (sm + L.o.lo)[lane] = lo;
     (sm + L.o.hi)[lane] = hi;
@@ -656,7 +668,7 @@ __device__ __forceinline__ void hacc_phase_g(const LT& L, double* sm, int stage,
 template <int NW, bool VLIM, class LT>
 __device__ __forceinline__ void build_qp_main(const LT& L, double* sm, int stage, const StageTabs& tb,
                                               const short* hinge_body, const short* limited, int* ctl, int& epoch,
-                                              double damping, double lm_damping, double limit_gain, double vdt, int lane,
+                                              double damping, double lm_damping, double limit_gain, double vdt, const FrameWindow& fwd, int lane,
                                               int pk_main, bool first, Prof& pr) {   // pk_main: task of this lane's pair in this table
   double mu = jlog_phase<NW>(L, sm, stage, lm_damping, lane, pr);
   const double diag = damping + mu;
@@ -666,7 +678,7 @@ __device__ __forceinline__ void build_qp_main(const LT& L, double* sm, int stage
     WSYNC();
     PROF_END(pr, PH_PAIRS);
     PROF_BEGIN(pr);
-    cvec_phase<VLIM>(L, sm, stage, tb, limited, limit_gain, vdt, lane);
+    cvec_phase<VLIM>(L, sm, stage, tb, limited, limit_gain, vdt, fwd, lane);
     PROF_END(pr, PH_CVEC);
     PROF_BEGIN(pr);
     hacc_phase_g(L, sm, stage, tb.items, diag, lane);
@@ -682,7 +694,7 @@ __device__ __forceinline__ void build_qp_main(const LT& L, double* sm, int stage
     __syncthreads();                      // B2: all Jacobian columns written
     PROF_END(pr, PH_PAIRS);
     PROF_BEGIN(pr);
-    cvec_phase<VLIM>(L, sm, stage, tb, limited, limit_gain, vdt, lane);
+    cvec_phase<VLIM>(L, sm, stage, tb, limited, limit_gain, vdt, fwd, lane);
     PROF_END(pr, PH_CVEC);
     PROF_BEGIN(pr);
     __syncthreads();                      // B3: H complete (helpers)
@@ -1040,7 +1052,8 @@ __device__ __forceinline__ void preprocess_wave(const LT& L, double* sm, const s
 // `scale` (f64 [S][nhum] or null: per-stream human scale tables) is the LAST argument on purpose: in the middle of the list,
 // beside `len`, it moved the kernarg offsets of everything behind it and cost the four-wavefront instances 4 to 8 more
 // spilled SGPRs and the headline 0.5 % frames/s; at the end every instance keeps the registers it had.
-// VLIM: the solver has a finite velocity limit (gmr_solver_set_velocity_limits).  It is a template argument, not a test in
+// VLIM: the solver has a finite velocity limit (gmr_solver_set_velocity_limits) or a finite frame window
+// (gmr_solver_set_frame_velocity_limits).  It is a template argument, not a test in
 // the kernel: the clamp always on cost the headline 0.40 %, skipped by unlimited lanes 0.19 % (8 more spilled SGPRs), six
 // alternated runs each; the instances without it are the parent's code.
 template <int NVP, int NW, int QP, bool VLIM>
@@ -1098,6 +1111,9 @@ __global__ __launch_bounds__(64 * NW, GMR_IK_MIN_WAVES) void ik_streams_kernel(c
   // this lane's velocity bound of one solve (lane = dof), from the global image behind its LDS part: one register pair
   // of the main wavefront for the whole launch, no LDS and no pointer kept (gmr_ik_layout.h: IK_VDT_N)
   const double vdt = VLIM && lane < nv ? reinterpret_cast<const double*>(reinterpret_cast<const char*>(image) + L.smem_bytes)[lane] : INFINITY;
+  // and its frame window, from the table behind that one; th0 and on are set frame by frame
+  FrameWindow fwd = {VLIM && lane < nv ? reinterpret_cast<const double*>(reinterpret_cast<const char*>(image) + L.smem_bytes)[IK_VDT_N + lane] : INFINITY,
+                     0.0, false};
 
   // this stream's own human scale table in place of the image's (only preprocess_wave reads it: the helpers never do)
   if (scale && lane < nhum) (sm + L.o.scale)[lane] = scale[(size_t)s * nhum + lane];
@@ -1151,6 +1167,10 @@ __global__ __launch_bounds__(64 * NW, GMR_IK_MIN_WAVES) void ik_streams_kernel(c
       if (lane + 64 < (int)fstride) r1 = nx[lane + 64];
     }
     WSYNC();
+    if (VLIM) {        // q still holds what the frame starts from: the previous frame's result, or q0 (bounded only on the caller's word)
+      fwd.on = t > 0 || (flags & GMR_FLAG_FRAME_LIMIT_FIRST);
+      fwd.th0 = lane >= 6 && lane < nv ? (sm + L.o.q)[7 + lane - 6] : 0.0;
+    }
     int ns0 = 0, ns1 = 0;
     const size_t f = (size_t)s * T + t;
     if (stat == GMR_STATUS_OK) {
@@ -1185,7 +1205,7 @@ __global__ __launch_bounds__(64 * NW, GMR_IK_MIN_WAVES) void ik_streams_kernel(c
         int nsol = 0, num_iter = 0;
         for (;;) {
           const bool first = nsol == 0;
-          build_qp_main<NW, VLIM>(L, sm, stage, tb, hinge_body, limited, ctl, epoch, prm[0], prm[1], prm[3], vdt, lane, pk_main[stage], first, pr);
+          build_qp_main<NW, VLIM>(L, sm, stage, tb, hinge_body, limited, ctl, epoch, prm[0], prm[1], prm[3], vdt, fwd, lane, pk_main[stage], first, pr);
           PROF_COUNT(pr, PH_NSOLVE);
           constexpr bool DENSE = NW == 1 && QP != QP_TREE_SMALL;
           if (first) { if (DENSE) qp_start.restore(stage, qp_state); else tree_start.restore(stage, tree_state); }

@@ -31,6 +31,9 @@ struct gmr_solver {
   int force_waves = 0;           // 0 = choose by stream count, 1 or 4 = forced (gmr_solver_set_waves)
   double vmax[GMR_MAX_HINGES];   // velocity limit of every hinge, rad/s; +inf = none (gmr_solver_set_velocity_limits)
   int vlim = 0;                  // some hinge has a finite one: the latency kernel's instances that clamp (gmr_ik.hip: VLIM)
+  double fvmax[GMR_MAX_HINGES];  // frame velocity limit of every hinge, rad/s; +inf = none (gmr_solver_set_frame_velocity_limits)
+  double frame_dt = 0.0;         // seconds between two frames of a stream; 0 while no hinge has a finite frame limit
+  int flim = 0;                  // some hinge has a finite one: the VLIM instances again, and the throughput kernel's with GMR_FWIN
   gmr::IkParams params;
   gmr::DeviceBlock image;        // host-built LDS image of the constants (gmr_ik_layout.h)
   gmr::WideLayout wide;          // throughput shape (gmr_ik_wide.hip): ok = 0 when the robot does not fit it
@@ -107,6 +110,7 @@ int gmr_solver_create(const gmr_model_t* model, const gmr_taskset_t* taskset, gm
   s->model = *model;
   s->ts = *taskset;
   std::fill(s->vmax, s->vmax + GMR_MAX_HINGES, (double)INFINITY);
+  std::fill(s->fvmax, s->fvmax + GMR_MAX_HINGES, (double)INFINITY);
   if (gmr::ik_padded_nv(s->model.nv) < 0) { delete s; return fail(GMR_ERR_ARG, "nv = %d > 48 is not supported", s->model.nv); }
   s->params = gmr::make_ik_params(s->model, s->ts);
   hipError_t e = hipSuccess;
@@ -211,6 +215,43 @@ int gmr_solver_velocity_limits(const gmr_solver_t* s, double* vmax_out, int n) {
   return GMR_OK;
 }
 
+// The frame windows are a second table per dof, vmax_frame * frame_dt, right behind the velocity bounds in the latency images
+// and in WideImg::fw of the throughput image.  Written in place under the contract of gmr_solver_set_velocity_limits above.
+int gmr_solver_set_frame_velocity_limits(gmr_solver_t* s, const double* vmax, int n, double frame_dt) {
+  if (!s) return fail(GMR_ERR_ARG, "null solver");
+  const int nh = s->model.nhinge;
+  if (vmax ? n != nh : (n != 0 && n != nh)) return fail(GMR_ERR_ARG, "frame velocity limits: n = %d, the robot has %d hinges", n, nh);
+  int finite = 0;
+  for (int h = 0; vmax && h < nh; h++) {
+    if (!(vmax[h] > 0.0)) return fail(GMR_ERR_ARG, "frame velocity limit of hinge %d is %g: must be positive (+inf = none)", h, vmax[h]);
+    finite |= std::isfinite(vmax[h]) ? 1 : 0;
+  }
+  if (finite && !(std::isfinite(frame_dt) && frame_dt > 0.0))
+    return fail(GMR_ERR_ARG, "frame_dt is %g: must be finite and positive while a frame velocity limit is", frame_dt);
+  double next[GMR_MAX_HINGES];
+  for (int h = 0; h < GMR_MAX_HINGES; h++) next[h] = vmax && h < nh ? vmax[h] : (double)INFINITY;
+  double fw[64];
+  gmr::ik_fill_frame_window(s->model, next, frame_dt, fw, 64);
+  GMR_NAMED_HIP_TRY("frame velocity limits", hipDeviceSynchronize());
+  if (s->image.data())
+    GMR_NAMED_HIP_TRY("frame velocity limits", hipMemcpy(s->image.data() + s->layout.smem_bytes + gmr::IK_VDT_N * 8, fw, gmr::IK_VDT_N * 8, hipMemcpyHostToDevice));
+  if (s->layout4.tree_ok && s->image4.data())
+    GMR_NAMED_HIP_TRY("frame velocity limits", hipMemcpy(s->image4.data() + s->layout4.smem_bytes + gmr::IK_VDT_N * 8, fw, gmr::IK_VDT_N * 8, hipMemcpyHostToDevice));
+  if (s->wide.ok) GMR_NAMED_HIP_TRY("frame velocity limits", hipMemcpy(s->wide_image.data() + gmr::wide_img().fw, fw, 64 * 8, hipMemcpyHostToDevice));
+  memcpy(s->fvmax, next, sizeof next);
+  s->frame_dt = finite ? frame_dt : 0.0;
+  s->flim = finite;
+  return GMR_OK;
+}
+
+int gmr_solver_frame_velocity_limits(const gmr_solver_t* s, double* vmax_out, int n, double* frame_dt_out) {
+  if (!s) return fail(GMR_ERR_ARG, "null solver");
+  if (!vmax_out || n != s->model.nhinge) return fail(GMR_ERR_ARG, "frame velocity limits: n = %d, the robot has %d hinges", n, s->model.nhinge);
+  memcpy(vmax_out, s->fvmax, (size_t)n * sizeof(double));
+  if (frame_dt_out) *frame_dt_out = s->frame_dt;
+  return GMR_OK;
+}
+
 int gmr_retarget_lds_bytes(const gmr_solver_t* s) { return !s ? 0 : s->layout4.tree_ok ? s->layout4.smem_bytes : s->layout.smem_bytes; }
 
 
@@ -264,7 +305,7 @@ static bool job_takes_wide_shape(const gmr_solver* s, long long streams) {
 static gmr_wide_job_desc wide_desc(const gmr_job_t& J) {
   gmr_solver* s = J.solver;
   return gmr_wide_job_desc{s->wide_image.data(), &s->wide, &s->params, J.S, J.T, J.q0, J.human, J.len, J.q_out, J.nsolve, J.status,
-                           J.tgt_out, J.err_out, J.scale};
+                           J.tgt_out, J.err_out, J.scale, s->flim};
 }
 // a checked job with work, by itself (d_prof: diagnostic builds)
 static int launch_job(const gmr_job_t& J, int flags, hipStream_t stream, unsigned long long* d_prof = nullptr) {
@@ -272,11 +313,11 @@ static int launch_job(const gmr_job_t& J, int flags, hipStream_t stream, unsigne
   const bool helpers = gmr::ik_helpers_shape(s->layout4.tree_ok, s->force_waves, J.S);
   if (job_takes_wide_shape(s, J.S))
     GMR_HIP_TRY(gmr_launch_ik_wide(s->wide_image.data(), &s->wide, &s->params, J.S, J.T, J.q0, J.human, J.len, J.scale, flags, J.q_out,
-                                   J.nsolve, J.status, J.tgt_out, J.err_out, stream, d_prof, d_prof ? nullptr : s->wide_pool));
+                                   J.nsolve, J.status, J.tgt_out, J.err_out, stream, d_prof, d_prof ? nullptr : s->wide_pool, s->flim));
   else
     GMR_HIP_TRY(gmr_launch_ik_streams((const uint4*)(helpers ? s->image4 : s->image).data(), helpers ? &s->layout4 : &s->layout, &s->params,
                                       J.S, J.T, J.q0, J.human, J.len, J.scale, flags, J.q_out, J.nsolve, J.status, J.tgt_out, J.err_out,
-                                      stream, d_prof, s->vlim));
+                                      stream, d_prof, s->vlim | s->flim));
   return GMR_OK;
 }
 

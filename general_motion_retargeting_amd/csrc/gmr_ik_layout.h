@@ -18,6 +18,9 @@ constexpr int IK_MAX_HOPS = 5;  // pointer-jumping rounds of the FK: 2^5 = 32 > 
 // the six dofs of the free joint): f64 [IK_VDT_N], index = dof.  It lives in the GLOBAL image only, right behind the
 // part that is copied to LDS (byte offset = smem_bytes), so that no LDS layout grows by it.
 constexpr int IK_VDT_N = 48;    // >= the largest padded nv; 384 B: the sections behind it stay 16-byte aligned
+// The frame window, |theta_i(t) - theta_i(t - 1)| <= fw_i = vmax_frame_i * frame_dt (gmr_solver_set_frame_velocity_limits;
+// +inf = none, and always for the free joint): f64 [IK_VDT_N], index = dof, right behind the table above (byte offset =
+// smem_bytes + IK_VDT_N * 8).  Global image only, like it.
 
 // rows of the dense register-resident factorisation are padded to one of these sizes = the SIZE CLASS of a
 // robot.  Every LDS offset is a compile-time constant of the class (and of the launch shape), so that the
@@ -419,7 +422,7 @@ inline IkLayout make_ik_layout(const gmr_model_t& m, const gmr_taskset_t& ts, co
     L.g_items[s] = -1;
   }
   L.smem_bytes = L.o.n_double * 8 + L.o.n_short * 2 + w * 4;
-  L.image_bytes = L.smem_bytes + IK_VDT_N * 8;     // a multiple of 16; the velocity bounds follow the LDS part
+  L.image_bytes = L.smem_bytes + 2 * IK_VDT_N * 8; // a multiple of 16; the velocity bounds and the frame windows follow the LDS part
   if (nw == 1)
     for (int s = 0; s < 2; s++) { L.g_items[s] = L.image_bytes / 4; L.image_bytes += (L.nitem[s] * 8 + 15) / 16 * 16; }
   return L;
@@ -463,6 +466,15 @@ inline void ik_fill_vdt(const gmr_model_t& m, const double* vmax, double* vdt, i
   }
 }
 
+// the frame-window table of a model: fw[6 + h] = vmax[h] * frame_dt where vmax[h] is finite, +inf everywhere else (an
+// infinite vmax never meets frame_dt: no limit at all leaves frame_dt unset)
+inline void ik_fill_frame_window(const gmr_model_t& m, const double* vmax, double frame_dt, double* fw, int n) {
+  for (int d = 0; d < n; d++) {
+    const int h = d - 6;
+    fw[d] = (vmax && h >= 0 && h < m.nhinge && std::isfinite(vmax[h])) ? vmax[h] * frame_dt : HUGE_VAL;
+  }
+}
+
 inline std::vector<char> make_ik_image(const gmr_model_t& m, const gmr_taskset_t& ts, const IkSchedule& sch,
                                        const IkLayout& L) {
   std::vector<char> img((size_t)L.image_bytes, 0);
@@ -500,7 +512,7 @@ inline std::vector<char> make_ik_image(const gmr_model_t& m, const gmr_taskset_t
     const double prm[6] = {ts.damping, ts.lm_damping, ts.tol, ts.limit_gain, ts.ground_offset, m.timestep};
     for (int i = 0; i < 6; i++) sm[L.o.params + i] = prm[i];
   }
-  ik_fill_vdt(m, nullptr, reinterpret_cast<double*>(img.data() + L.smem_bytes), IK_VDT_N);   // none: the setter writes the device copy
+  ik_fill_vdt(m, nullptr, reinterpret_cast<double*>(img.data() + L.smem_bytes), 2 * IK_VDT_N);   // none, both tables: the setters write the device copy
   for (int i = 0; i < L.nhum; i++) {
     sm[L.o.scale + i] = ts.scale[i];
     for (int a = 0; a < 3; a++) sm[L.o.pos_off + 3 * i + a] = ts.pos_off[i][a];

@@ -254,10 +254,12 @@ __device__ __forceinline__ void pairs_wide(double* sm, const char* __restrict__ 
 }
 
 // (c) lane = dof: gather c; bounds of the limited hinges (mink ConfigurationLimit), clamped into this dof's velocity
-// bound [-vdt, vdt] (mink VelocityLimit; vdt = +inf leaves both bits as they are)
+// bound [-vdt, vdt] (mink VelocityLimit; vdt = +inf leaves both bits as they are).  fwin (wave-uniform, and a literal false in
+// the instances without GMR_FWIN: this frame is bounded): clamped last into [th0 - fw, th0 + fw] - theta, the window around this
+// dof's angle th0 at the start of the frame (gmr_solver_set_frame_velocity_limits; fw = +inf leaves both bits as they are)
 template <class DimsRef>
 __device__ __forceinline__ void cvec_wide(DimsRef D, double* sm, const char* __restrict__ img, int stage,
-                                          double limit_gain, int lane) {
+                                          double limit_gain, bool fwin, double th0, int lane) {
   lane = fresh_lane(lane);     // (lane predicates of this phase are computed here and die with it: gmr_device_math.h)
   const double* cpart = sm + LD.cpart;
   if (lane < D.nv) {
@@ -281,8 +283,17 @@ __device__ __forceinline__ void cvec_wide(DimsRef D, double* sm, const char* __r
       hi = limit_gain * (lim.y - th);
       lo = -limit_gain * (th - lim.x);
     }
-    (sm + LD.lo)[lane] = fmin(fmax(lo, -vdt), vdt);
-    (sm + LD.hi)[lane] = fmin(fmax(hi, -vdt), vdt);
+    lo = fmin(fmax(lo, -vdt), vdt);
+    hi = fmin(fmax(hi, -vdt), vdt);
+    if (fwin) {
+      const double fw = img_at<double>(img, IM.fw)[lane];
+      const double th = lane >= 6 ? (sm + LD.q)[7 + lane - 6] : 0.0;     // (the free joint's fw is +inf, its th0 zero)
+      const double lf = (th0 - fw) - th, hf = (th0 + fw) - th;
+      lo = fmin(fmax(lo, lf), hf);
+      hi = fmin(fmax(hi, lf), hf);
+    }
+    (sm + LD.lo)[lane] = lo;
+    (sm + LD.hi)[lane] = hi;
   }
 }
 
@@ -883,129 +894,20 @@ __device__ __forceinline__ bool queue_pop(const WideQueue& Q, const unsigned nch
   return true;
 }
 
-// Plain launch: ONE job without per-stream scale tables, its fields are individual kernel arguments.  That matters: with ~100 SGPRs for ~350
-// wave-uniform values the compiler re-loads a kernel ARGUMENT where it is used (s_load from the kernarg segment: no VALU
-// slot), while a value it cannot re-load is parked in a VGPR lane and comes back through v_readlane.  Passing the job as
-// one by-value struct (or reading it through a pointer to the kernarg segment) loses that property: measured, +500
-// v_readlane instructions in the code object and -4 % frames/s.  For the same reason this instance has no scale
-// argument: GMR_SCALE is a literal null here and the branch in preprocess_wide folds away; a job that carries scale
-// rows runs the group instance, alone if need be.
-__global__ __launch_bounds__(64, GMR_WIDE_MIN_WAVES) void ik_wide_kernel(
-    const char* __restrict__ img, WideDims D, int max_iter, int human_root, int use0, int use1, int S, int T,
-    const double* __restrict__ q0, const double* __restrict__ human, const int32_t* __restrict__ len, int flags,
-    double* q_out, int32_t* __restrict__ nsolve, int32_t* __restrict__ status, double* __restrict__ tgt_out,
-    double* __restrict__ err_out, WideQueue Q, unsigned long long* __restrict__ prof_out) {
-  extern __shared__ __align__(16) double sm[];
-  const int lane = threadIdx.x;
-  const bool queued = Q.ring != nullptr;
-  if (!queued && (int)blockIdx.x >= S) return;
-  Prof pr;
-#ifdef GMR_IK_PROFILE
-  for (int i = 0; i < PH_COUNT; i++) pr.acc[i] = 0;
-  const unsigned long long k_t0 = __builtin_amdgcn_s_memtime(), k_r0 = __builtin_amdgcn_s_memrealtime();
-#endif
-  const int nq = D.nq, nhum = D.nhum;
-  const double* prm = img_at<double>(img, IM.prm);   // damping, lm_damping, tol, limit_gain, ground_offset, dt
-  const unsigned nchunk = queued ? Q.hdr[2] : 0u;
-  const size_t fstride = (size_t)nhum * 7;
-  for (;;) {
-  int s = blockIdx.x, t0 = 0, stat = GMR_STATUS_OK;
-  RowState bounds = {0ull, 0ull};
-  if (queued) {
-    unsigned ticket = 0;
-    if (lane == 0) ticket = __hip_atomic_fetch_add(&Q.hdr[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    ticket = __builtin_amdgcn_readfirstlane(ticket);
-    if (ticket >= nchunk) break;
-    unsigned v = 0;
-    for (;;) {
-      if (lane == 0) v = __hip_atomic_load(&Q.ring[ticket], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      v = __builtin_amdgcn_readfirstlane(v);
-      if (v) break;
-      __builtin_amdgcn_s_sleep(64);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   // the producer's q_out row and state are visible from here
-    s = (int)v - 1;
-    const WideStreamState st = Q.state[s];
-    bounds.lower = uniform64(st.lower); bounds.upper = uniform64(st.upper);
-    t0 = __builtin_amdgcn_readfirstlane(st.t_next);
-    stat = __builtin_amdgcn_readfirstlane(st.stat);
-  }
-  const int gs = s;
-#define GMR_DIMS_T const WideDims&
-#define GMR_T_END T
-#define GMR_WINDOWED false
-#define GMR_SCALE static_cast<const double*>(nullptr)
-#include "gmr_ik_wide_item.inc"
-#undef GMR_SCALE
-#undef GMR_WINDOWED
-#undef GMR_T_END
-#undef GMR_DIMS_T
-  }
-#ifdef GMR_IK_PROFILE
-  pr.acc[PH_TICKS] = __builtin_amdgcn_s_memtime() - k_t0;
-  pr.acc[PH_REALTIME] = __builtin_amdgcn_s_memrealtime() - k_r0;
-  if (lane == 0 && prof_out && !queued)
-    for (int i = 0; i < PH_COUNT; i++) prof_out[(size_t)blockIdx.x * PH_COUNT + i] = pr.acc[i];
-#else
-  (void)prof_out;
-#endif
-}
-
-// Group launch: the job of an item comes from the table in device memory, by scalar loads through a constant-memory
-// pointer (wave-uniform, like kernel arguments, but not re-loadable for free: this instance keeps a few more values in
-// registers than the plain one).
-__global__ __launch_bounds__(64, GMR_WIDE_MIN_WAVES) void ik_wide_group_kernel(const WideJob* __restrict__ jobs, int njobs,
-                                                                               int total, int flags, WideQueue Q) {
-  extern __shared__ __align__(16) double sm[];
-  const int lane = threadIdx.x;
-  const bool queued = Q.ring != nullptr;
-  if (!queued && (int)blockIdx.x >= total) return;
-  Prof pr;
-#ifdef GMR_IK_PROFILE
-  for (int i = 0; i < PH_COUNT; i++) pr.acc[i] = 0;
-#endif
-  const unsigned nchunk = queued ? Q.hdr[2] : 0u;
-  for (;;) {
-  int gs = blockIdx.x, t0 = 0, stat = GMR_STATUS_OK;
-  RowState bounds = {0ull, 0ull};
-  if (queued) {
-    if (!queue_pop(Q, nchunk, lane, gs, t0, stat, bounds)) break;
-  } else if (Q.windowed && Q.t_begin > 0) {           // a later window of a direct launch: continue from the parked state
-    const WideStreamState st = Q.state[gs];
-    bounds.lower = uniform64(st.lower); bounds.upper = uniform64(st.upper);
-    t0 = __builtin_amdgcn_readfirstlane(st.t_next);
-    stat = __builtin_amdgcn_readfirstlane(st.stat);
-  }
-  typedef const WideJob __attribute__((address_space(4))) CJob;
-  const int j = __builtin_amdgcn_readfirstlane(job_of(jobs, njobs, gs, lane));
-  CJob* cj = reinterpret_cast<CJob*>(reinterpret_cast<uintptr_t>(jobs + j));
-  const WideDims __attribute__((address_space(4)))& D = cj->D;
-  const char* __restrict__ img = cj->img;
-  const int max_iter = cj->max_iter, human_root = cj->human_root, use0 = cj->use0, use1 = cj->use1, T = cj->T;
-  const double* __restrict__ q0 = cj->q0;
-  const double* __restrict__ human = cj->human;
-  const int32_t* __restrict__ len = cj->len;
-  double* q_out = cj->q_out;
-  int32_t* __restrict__ nsolve = cj->nsolve;
-  int32_t* __restrict__ status = cj->status;
-  double* __restrict__ tgt_out = cj->tgt_out;
-  double* __restrict__ err_out = cj->err_out;
-  const double* __restrict__ scale = cj->scale;
-  const int s = gs - cj->first;
-  const int nq = D.nq, nhum = D.nhum;
-  const double* prm = img_at<double>(img, IM.prm);
-  const size_t fstride = (size_t)nhum * 7;
-#define GMR_DIMS_T const WideDims __attribute__((address_space(4)))&
-#define GMR_T_END Q.t_end
-#define GMR_WINDOWED (Q.windowed != 0)
-#define GMR_SCALE scale
-#include "gmr_ik_wide_item.inc"
-#undef GMR_SCALE
-#undef GMR_WINDOWED
-#undef GMR_T_END
-#undef GMR_DIMS_T
-  }
-}
+#define GMR_FWIN false
+#define GMR_WIDE_KERNEL ik_wide_kernel
+#define GMR_WIDE_GROUP_KERNEL ik_wide_group_kernel
+#include "gmr_ik_wide_kernels.inc"
+#undef GMR_WIDE_GROUP_KERNEL
+#undef GMR_WIDE_KERNEL
+#undef GMR_FWIN
+#define GMR_FWIN true
+#define GMR_WIDE_KERNEL ik_wide_fw_kernel
+#define GMR_WIDE_GROUP_KERNEL ik_wide_group_fw_kernel
+#include "gmr_ik_wide_kernels.inc"
+#undef GMR_WIDE_GROUP_KERNEL
+#undef GMR_WIDE_KERNEL
+#undef GMR_FWIN
 
 }  // namespace wide
 }  // namespace gmr
@@ -1090,7 +992,7 @@ extern "C" hipError_t gmr_launch_ik_wide_window(const gmr_wide_job_desc* jd, int
   memset(&tab, 0, sizeof tab);
   long long total = 0, nring = 0;
   int chunk = 0, maxT = 0, n = 0;
-  bool chunk_auto = false, scaled = false;
+  bool chunk_auto = false, scaled = false, fwin = false;
   if (p) { std::lock_guard<std::mutex> g(p->mu); chunk = p->chunk; chunk_auto = p->chunk_auto; }
   for (int j = 0; j < njobs; j++) {
     if (jd[j].S <= 0 || jd[j].T <= 0) continue;
@@ -1101,6 +1003,7 @@ extern "C" hipError_t gmr_launch_ik_wide_window(const gmr_wide_job_desc* jd, int
     J.max_iter = jd[j].P->max_iter; J.human_root = jd[j].P->human_root; J.use0 = jd[j].P->use0; J.use1 = jd[j].P->use1;
     J.scale = jd[j].d_scale;
     scaled = scaled || J.scale;
+    fwin = fwin || jd[j].fwin;      // one job with a frame window: the instances that apply it (a job without one is not changed by them: its window is +inf)
     J.S = jd[j].S; J.T = jd[j].T; J.first = (int)total;
     total += jd[j].S;
     maxT = std::max(maxT, jd[j].T);
@@ -1180,10 +1083,11 @@ extern "C" hipError_t gmr_launch_ik_wide_window(const gmr_wide_job_desc* jd, int
     if (e != hipSuccess) return e;
   }
   if (multi) {
-    hipLaunchKernelGGL(ik_wide_group_kernel, dim3(grid), dim3(64), wide_lds_launch_bytes(), stream, d_jobs, n, (int)total, flags, Q);
+    hipLaunchKernelGGL(fwin ? ik_wide_group_fw_kernel : ik_wide_group_kernel, dim3(grid), dim3(64), wide_lds_launch_bytes(), stream, d_jobs, n,
+                       (int)total, flags, Q);
   } else {
     const WideJob& J = tab.job[0];
-    hipLaunchKernelGGL(ik_wide_kernel, dim3(grid), dim3(64), wide_lds_launch_bytes(), stream, J.img, J.D, J.max_iter, J.human_root,
+    hipLaunchKernelGGL(fwin ? ik_wide_fw_kernel : ik_wide_kernel, dim3(grid), dim3(64), wide_lds_launch_bytes(), stream, J.img, J.D, J.max_iter, J.human_root,
                        J.use0, J.use1, J.S, J.T, J.q0, J.human, J.len, flags, J.q_out, J.nsolve, J.status, J.tgt_out, J.err_out, Q,
                        d_prof);
   }
@@ -1194,10 +1098,10 @@ extern "C" hipError_t gmr_launch_ik_wide(const char* d_image, const gmr::WideLay
                                          const double* d_q0, const double* d_human, const int32_t* d_len,
                                          const double* d_scale, int flags, double* d_q_out, int32_t* d_nsolve, int32_t* d_status,
                                          double* d_tgt_out, double* d_err_out, hipStream_t stream, unsigned long long* d_prof,
-                                         void* pool) {
+                                         void* pool, int fwin) {
   if (S <= 0 || T <= 0) return hipSuccess;
   if (d_scale && d_prof) return hipErrorInvalidValue;        // (the phase counters are the plain instance's)
-  const gmr_wide_job_desc jd{d_image, L, P, S, T, d_q0, d_human, d_len, d_q_out, d_nsolve, d_status, d_tgt_out, d_err_out, d_scale};
+  const gmr_wide_job_desc jd{d_image, L, P, S, T, d_q0, d_human, d_len, d_q_out, d_nsolve, d_status, d_tgt_out, d_err_out, d_scale, fwin};
   return gmr_launch_ik_wide_group(&jd, 1, flags, stream, d_prof, pool);
 }
 

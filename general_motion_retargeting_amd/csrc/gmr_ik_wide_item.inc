@@ -9,7 +9,8 @@
 // flags, q_out, nsolve, status, tgt_out, err_out, Q, queued, s, gs, t0, stat, bounds, nq, prm, fstride, sm, lane, pr; and the
 // macros GMR_T_END (frames at or beyond it are left to a later launch: T in the plain kernel), GMR_WINDOWED (the launch is one
 // window of a stream's frames: its state is kept in Q.state for the next window; false in the plain kernel) and GMR_SCALE (the
-// job's per-stream human scale tables, f64 [S][nhum], or null = the image's table; a literal null in the plain kernel).
+// job's per-stream human scale tables, f64 [S][nhum], or null = the image's table; a literal null in the plain kernel); and
+// GMR_FWIN, a literal: the instance applies the frame window (gmr_ik_wide_kernels.inc).
   // state that must start defined: the violation sets of the QP (double-buffered, cleared round by round)
   if (lane < 8) reinterpret_cast<unsigned long long*>(sm + LD.vset)[lane] = 0ull;
   {
@@ -41,6 +42,12 @@
       if (lane + 64 < (int)fstride) r1 = nx[lane + 64];
     }
     wsync();
+    // The frame window (gmr_solver_set_frame_velocity_limits): every solve of this frame keeps the hinges within fw of the
+    // angle the frame starts from -- LDS q holds it here: the previous frame's result, q0, or the q_out row an earlier item
+    // or window wrote.  Only in the instances with GMR_FWIN (gmr_ik_wide_kernels.inc); whether the frame is bounded is decided
+    // where the window is applied (cvec_wide), from values the wavefront can re-load, so that this register pair is all the
+    // window keeps alive across the frame.  Frame 0 of a stream is bounded only on the caller's word.
+    const double th0 = (GMR_FWIN && lane >= 6 && lane < D.nv) ? (sm + LD.q)[7 + lane - 6] : 0.0;
     int ns0 = 0, ns1 = 0;
     const size_t f = (size_t)s * T + t;
     if (stat == GMR_STATUS_OK) {
@@ -64,7 +71,7 @@
           wsync();
           PROF_END(pr, PH_PAIRS);
           PROF_BEGIN(pr);
-          cvec_wide<GMR_DIMS_T>(D, sm, img, stage, prm[3], lane);
+          cvec_wide<GMR_DIMS_T>(D, sm, img, stage, prm[3], GMR_FWIN && (t > 0 || (flags & GMR_FLAG_FRAME_LIMIT_FIRST)), th0, lane);
           PROF_END(pr, PH_CVEC);
           PROF_BEGIN(pr);
           hacc_wide(sm, img, D.items[stage], D.ntrip[stage], diag, lane);

@@ -120,6 +120,7 @@ struct WideImg {
   int vdt;        // f64 [64]  velocity bound of one solve, vmax * dt (+inf: none; the free joint's six always)  lane = dof
   int tree;       // i32 [64] dof of solver lane (16 l + row) or -1
   int prm;        // f64 [8]  damping, lm_damping, tol, limit_gain, ground_offset, dt (scalar loads where used)
+  int fw;         // f64 [64]  frame window, vmax_frame * frame_dt (+inf: none; the free joint's six always)          lane = dof
   int items[2];   // u64 [ntrip][64]   (runtime size: last)
   int fixed_bytes;
 };
@@ -142,6 +143,7 @@ constexpr WideImg wide_img() {
   I.vdt = o; o += wd_up16(64 * 8);
   I.tree = o; o += wd_up16(64 * 4);
   I.prm = o; o += 64;
+  I.fw = o; o += wd_up16(64 * 8);      // (last of the fixed part: every section in front of it keeps its offset)
   I.fixed_bytes = o;
   return I;
 }
@@ -455,6 +457,7 @@ inline WideLayout make_wide_layout(const gmr_model_t& m, const gmr_taskset_t& ts
     U(I.limi)[d] = lim ? 1u : 0u;
   }
   ik_fill_vdt(m, nullptr, F(I.vdt), 64);       // none: gmr_solver_set_velocity_limits writes the device copy
+  ik_fill_vdt(m, nullptr, F(I.fw), 64);        // none: gmr_solver_set_frame_velocity_limits writes the device copy
   {
     const double prm[6] = {ts.damping, ts.lm_damping, ts.tol, ts.limit_gain, ts.ground_offset, m.timestep};
     for (int i = 0; i < 6; i++) F(I.prm)[i] = prm[i];

@@ -20,6 +20,7 @@ struct gmr_wide_job_desc {
   const double* d_q0; const double* d_human; const int32_t* d_len;
   double* d_q_out; int32_t* d_nsolve; int32_t* d_status; double* d_tgt_out; double* d_err_out;
   const double* d_scale;         // [S][nhum] or null
+  int fwin;                      // the image's frame windows are not all +inf
 };
 
 extern "C" {
@@ -33,7 +34,7 @@ hipError_t gmr_ik_set_max_smem(int nvp, int nw, int tree_small, int bytes);
 hipError_t gmr_launch_ik_wide(const char* d_image, const gmr::WideLayout* L, const gmr::IkParams* P, int S, int T, const double* d_q0,
                               const double* d_human, const int32_t* d_len, const double* d_scale, int flags, double* d_q_out,
                               int32_t* d_nsolve, int32_t* d_status, double* d_tgt_out, double* d_err_out, hipStream_t stream,
-                              unsigned long long* d_prof, void* pool);
+                              unsigned long long* d_prof, void* pool, int fwin);    // fwin: as in gmr_wide_job_desc
 hipError_t gmr_launch_ik_wide_group(const gmr_wide_job_desc* jd, int njobs, int flags, hipStream_t stream, unsigned long long* d_prof,
                                     void* pool);
 hipError_t gmr_launch_ik_wide_window(const gmr_wide_job_desc* jd, int njobs, int flags, hipStream_t stream, unsigned long long* d_prof,

@@ -546,13 +546,18 @@ class ClipRetargeter:
     library = None
     _per_clip = False            # one height per clip, travelling as scale rows: off
     _heights: Optional[np.ndarray] = None
+    _frame_limit = None          # velocity limits between frames: off
 
     def __init__(self, src_human: str, tgt_robot: str, actual_human_height=None, height_adjust: bool = True,
                  root_origin_offset: bool = True, offset_to_ground: bool = False, chunk=None, library=False,
-                 velocity_limit=None):
+                 velocity_limit=None, frame_velocity_limit=None):
         """``velocity_limit`` (default None: off): per-joint velocity limits of every solve, a scalar in rad/s, an array
         ``[nhinge]`` or a dict ``{joint name: rad/s}`` (``GeneralMotionRetargeting.set_velocity_limit``: a bound per solve, not
         on the velocity between frames).
+        ``frame_velocity_limit`` (default None: off): per-joint velocity limits BETWEEN FRAMES, in the same three forms
+        (``GeneralMotionRetargeting.set_frame_velocity_limit``); the frames are ``1 / fps`` apart, the fps of the batch, so a
+        batch whose clips disagree on fps raises ``ValueError`` while it is on; every clip starts free (from ``qpos0``).  It
+        does not go with ``chunk`` (``ValueError``).
         ``actual_human_height``: one height for every clip (a number or None: the solver is built for it, as ever), or a
         sequence with one height per clip of a call (``add(clip, height=)`` in the staged protocol): the solver is built from
         the unscaled config and every clip carries its height as a scale row of the ONE job, the bits of a retargeter built
@@ -569,6 +574,8 @@ class ClipRetargeter:
         self._heights = np.asarray(actual_human_height, dtype=np.float64).reshape(-1) if self._per_clip else None
         self.gmr = GeneralMotionRetargeting(src_human, tgt_robot, actual_human_height=None if self._per_clip else actual_human_height,
                                             velocity_limit=velocity_limit)
+        self._frame_limit = frame_velocity_limit
+        _refuse_chunk_under_frame_limit(self.gmr, frame_velocity_limit, chunk)      # (and the limit is parsed once, here)
         self.height_adjust, self.root_origin_offset, self.offset_to_ground = height_adjust, root_origin_offset, offset_to_ground
         self.chunk = chunk
         self._library_mode = None if not library else ("world" if library is True else str(library))
@@ -694,6 +701,8 @@ class ClipRetargeter:
         lens = self._lens[:S].copy()
         if self._per_clip and chunking.resolve_any(self.chunk, lens) is not None:
             raise ValueError("per-clip heights do not go with a chunk spec that takes effect: run the heights as groups")
+        if self._frame_limit is not None:           # (this object's own retargeter: without a limit it never had one)
+            _set_batch_frame_limit([self.gmr], self._frame_limit, list(fps)[:S])
         return self._finish_device(fps, lens) if post_path() == "device" else self._finish(fps, lens, None)
 
     def _finish_device(self, fps: Sequence[float], lens: np.ndarray) -> List[Dict]:
@@ -742,11 +751,33 @@ class ClipRetargeter:
         return self.finish(fps)
 
 
+def _refuse_chunk_under_frame_limit(gmr: GeneralMotionRetargeting, frame_velocity_limit, chunk) -> None:
+    """``chunk=`` and a finite frame velocity limit do not go together (chunking.FRAME_LIMIT_REFUSAL); parses the limit."""
+    table, _ = gmr._frame_limit_table(frame_velocity_limit, 1.0)
+    if chunk is not None and table is not None and np.isfinite(table).any():
+        raise ValueError(chunking.FRAME_LIMIT_REFUSAL)
+
+
+def _set_batch_frame_limit(gmrs, frame_velocity_limit, fps) -> None:
+    """The frame velocity limit of one batch on the retargeters that serve it (None: cleared -- a kept retargeter serves every
+    batch).  One ``frame_dt = 1 / fps`` per solver, so the clips of a batch under a limit must agree on their fps."""
+    f = None
+    if frame_velocity_limit is not None:
+        distinct = sorted({float(x) for x in fps})
+        if len(distinct) > 1:
+            raise ValueError(f"frame_velocity_limit: the clips of a batch must share one fps (frame_dt = 1 / fps), got {distinct}")
+        f = distinct[0] if distinct else None
+        if f is None:
+            return
+    for g in gmrs:
+        g.set_frame_velocity_limit(frame_velocity_limit, f)
+
+
 def retarget_clips(src_human: str, tgt_robot: str, clips: Sequence, fps: Sequence[float],
                    actual_human_height=None, height_adjust: bool = True,
                    root_origin_offset: bool = True, offset_to_ground: bool = False, chunk=None, report: Optional[List] = None,
-                   library=False, velocity_limit=None):
-    """Retarget many clips of one (source, robot, height) in ONE IK launch.  ``velocity_limit``: see :class:`ClipRetargeter`.  ``library`` (``True`` | ``"world"`` | ``"reference"``;
+                   library=False, velocity_limit=None, frame_velocity_limit=None):
+    """Retarget many clips of one (source, robot, height) in ONE IK launch.  ``velocity_limit``, ``frame_velocity_limit``: see :class:`ClipRetargeter`.  ``library`` (``True`` | ``"world"`` | ``"reference"``;
     default off): returns ``(motions, motion_library.MotionLibrary)``, the library filled on the device from the post-processed
     batch; ``motions`` are the same bytes as without it.  ``chunk`` (``chunking.ChunkSpec`` or ``"auto"``; default
     off) cuts long clips into independently running chunks -- NOT parity; the per-clip chunk reports are appended to ``report``.
@@ -772,11 +803,11 @@ def retarget_clips(src_human: str, tgt_robot: str, clips: Sequence, fps: Sequenc
                 idxs = [i for i, x in enumerate(heights) if x == h]
                 for i, md in zip(idxs, retarget_clips(src_human, tgt_robot, [clips[i] for i in idxs], [fps[i] for i in idxs], h, height_adjust,
                                                       root_origin_offset, offset_to_ground, chunk=chunk, report=report,
-                                                      velocity_limit=velocity_limit)):
+                                                      velocity_limit=velocity_limit, frame_velocity_limit=frame_velocity_limit)):
                     out[i] = md
             return out
     rt = ClipRetargeter(src_human, tgt_robot, actual_human_height, height_adjust, root_origin_offset, offset_to_ground, chunk=chunk,
-                        library=library, velocity_limit=velocity_limit)
+                        library=library, velocity_limit=velocity_limit, frame_velocity_limit=frame_velocity_limit)
     out = rt(clips, fps)
     if report is not None and rt.chunk_report is not None:
         report.extend(rt.chunk_report)
@@ -798,8 +829,8 @@ def retarget_mixed(groups: Sequence[Dict], offset_to_ground: bool = False, slice
     overlap the kernels.  Bit-identical to retargeting every group by itself.
 
     ``groups[i]`` = ``{"src_human", "tgt_robot", "human": f64[S,T,nhuman,7], optional "lens",
-    "actual_human_height", "velocity_limit"}`` (the limit as in ``GeneralMotionRetargeting``: it is the group's own, each job
-    launches with its solver's table), the height a number for the group or one per stream (``f64[S]``: the group's solver is built
+    "actual_human_height", "velocity_limit", "frame_velocity_limit", "fps"}`` (the limits as in ``GeneralMotionRetargeting``: they
+    are the group's own, each job launches with its solver's tables; a frame limit needs the group's ``fps``), the height a number for the group or one per stream (``f64[S]``: the group's solver is built
     from the unscaled config and the heights travel as scale rows); arrays allocated with ``_lib.pinned_empty`` are copied asynchronously.
     Returns a list of ``(qpos[S,T,nq], nsolve[S,T,2], status[S])``.
     """
@@ -808,7 +839,8 @@ def retarget_mixed(groups: Sequence[Dict], offset_to_ground: bool = False, slice
         h = g.get("actual_human_height")
         per_stream = h is not None and np.ndim(h) > 0
         gmr = GeneralMotionRetargeting(g["src_human"], g["tgt_robot"], actual_human_height=None if per_stream else h,
-                                       velocity_limit=g.get("velocity_limit"))
+                                       velocity_limit=g.get("velocity_limit"),
+                                       frame_velocity_limit=g.get("frame_velocity_limit"), fps=g.get("fps"))
         keep.append(gmr)
         jobs.append({"solver": gmr.hip_solver, "human": g["human"], "lens": g.get("lens"),
                      "scales": gmr.stream_scales(len(g["human"]), heights=h) if per_stream else None})
@@ -817,7 +849,8 @@ def retarget_mixed(groups: Sequence[Dict], offset_to_ground: bool = False, slice
 
 
 def retarget_bvh_files(bvh_files: Sequence[str], tgt_robot: str, fps: float = 30.0, height_adjust: bool = False,
-                       root_origin_offset: bool = False, chunk=None, report: Optional[List] = None, velocity_limit=None) -> List[Dict]:
+                       root_origin_offset: bool = False, chunk=None, report: Optional[List] = None, velocity_limit=None,
+                       frame_velocity_limit=None) -> List[Dict]:
     """``scripts/bvh_to_robot_dataset.py:60-152`` for a list of files: every BVH clip becomes one
     stream of ONE launch (LAFAN1: 77 ragged clips).  Both adjustments default to off like that script
     (``HEIGHT_ADJUST = False``, :128); the loader's hard-coded height 1.75 is used (lafan1.py:39).
@@ -831,13 +864,13 @@ def retarget_bvh_files(bvh_files: Sequence[str], tgt_robot: str, fps: float = 30
         clips = [load_lafan1_packed(f, gmr.human_body_names)[0] for f in bvh_files]
     return retarget_clips("bvh", tgt_robot, clips, [fps] * len(clips), actual_human_height=1.75,
                           height_adjust=height_adjust, root_origin_offset=root_origin_offset, chunk=chunk, report=report,
-                          velocity_limit=velocity_limit)
+                          velocity_limit=velocity_limit, frame_velocity_limit=frame_velocity_limit)
 
 
 def retarget_smplx_files(smplx_files: Sequence[str], smplx_body_model_path: str, tgt_robot: str, tgt_fps: int = 30,
                          height_adjust: bool = True, root_origin_offset: bool = True,
                          skip_errors: bool = True, chunk=None, report: Optional[List] = None,
-                         velocity_limit=None) -> List[Optional[Dict]]:
+                         velocity_limit=None, frame_velocity_limit=None) -> List[Optional[Dict]]:
     """``scripts/smplx_to_robot_dataset.py:39-146`` (``process_file``) for a list of AMASS-style SMPL-X
     files, everything after the file read on the device: joints-only body model + fps alignment
     (utils/smpl.py) -> packed frames -> IK (one group launch for all heights) -> FK post-processing.
@@ -854,7 +887,8 @@ def retarget_smplx_files(smplx_files: Sequence[str], smplx_body_model_path: str,
             print(f"Error loading {f}: {e}")
     out: List[Optional[Dict]] = [None] * len(smplx_files)
     for i, md in zip(ok, retarget_smplx_loaded(raws, smplx_body_model_path, tgt_robot, tgt_fps, height_adjust, root_origin_offset,
-                                               chunk=chunk, report=report, velocity_limit=velocity_limit)):
+                                               chunk=chunk, report=report, velocity_limit=velocity_limit,
+                                               frame_velocity_limit=frame_velocity_limit)):
         out[i] = md
     return out
 
@@ -1193,8 +1227,9 @@ def _load_bvh_clip(args):
 
 def run_bvh_dataset(src_folder: str, tgt_folder: str, robot: str, override: bool = False, batch_files: int = 0,
                     retarget=None, verbose: bool = True, frames_budget: int = 1 << 19, loader_workers: int = -1,
-                    rank: int = 0, world: int = 1, load=None, stats: Optional[Dict] = None, chunk=None, velocity_limit=None) -> int:
-    """``bvh_to_robot_dataset.py`` (:60-157) on the pipeline above.  ``velocity_limit``: see :class:`ClipRetargeter`.  ``chunk``: see :class:`ClipRetargeter` (``stats["chunk"]`` gets the totals).  ``batch_files`` > 0 additionally caps the clips of a
+                    rank: int = 0, world: int = 1, load=None, stats: Optional[Dict] = None, chunk=None, velocity_limit=None,
+                    frame_velocity_limit=None) -> int:
+    """``bvh_to_robot_dataset.py`` (:60-157) on the pipeline above.  ``velocity_limit``, ``frame_velocity_limit`` (at the 30 fps of the clips): see :class:`ClipRetargeter`.  ``chunk``: see :class:`ClipRetargeter` (``stats["chunk"]`` gets the totals).  ``batch_files`` > 0 additionally caps the clips of a
     launch (0: only the frames budget does).  ``retarget(clips, files)`` and ``load(file)`` are injectable (tests)."""
     # the partition is computed on ALL source files (a rank that starts later must not see another partition because
     # some targets exist by then); skip-if-exists is applied to the rank's own shard
@@ -1208,7 +1243,7 @@ def run_bvh_dataset(src_folder: str, tgt_folder: str, robot: str, override: bool
     rt = None
     if retarget is None:
         rt = ClipRetargeter("bvh", robot, 1.75, height_adjust=False, root_origin_offset=False, chunk=chunk,    # HEIGHT_ADJUST = False, :128
-                            velocity_limit=velocity_limit)
+                            velocity_limit=velocity_limit, frame_velocity_limit=frame_velocity_limit)
         retarget = _Staged(rt, 30)
     raw = rt is not None and bvh_path() == "device"        # the loaders only parse; gmr_bvh_frames_dev computes the frames
     try:
@@ -1266,7 +1301,7 @@ def _load_smplx_raw(f):
 def retarget_smplx_loaded(raws: Sequence[Dict], smplx_body_model_path: str, tgt_robot: str, tgt_fps: int = 30,
                           height_adjust: bool = True, root_origin_offset: bool = True,
                           timing: Optional[Dict[str, float]] = None, chunk=None, report: Optional[List] = None,
-                          library=False, velocity_limit=None):
+                          library=False, velocity_limit=None, frame_velocity_limit=None):
     """``process_file`` (smplx_to_robot_dataset.py:39-146) for many already-read files: joints-only body model and fps
     alignment on the device, ONE solver (built from the unscaled config, kept from batch to batch) and ONE IK job for the
     whole batch -- a file's height comes from its betas (:36-39) and travels as that clip's scale row
@@ -1278,7 +1313,9 @@ def retarget_smplx_loaded(raws: Sequence[Dict], smplx_body_model_path: str, tgt_
     ``gmr_smplx_batch_frames_dev`` call writes the packed frames of all clips where the IK kernels read them; otherwise one
     ``gmr_smplx_frames`` call per clip and a padded upload -- the same bits.  ``timing`` accumulates the seconds of the stages.
     ``library`` (``True`` | ``"world"`` | ``"reference"``; default off): returns ``(motions, motion_library.MotionLibrary)`` as
-    :func:`retarget_clips` does, the clips in the order of ``raws``; the batch must then be one job (the merged path)."""
+    :func:`retarget_clips` does, the clips in the order of ``raws``; the batch must then be one job (the merged path).
+    ``frame_velocity_limit``: see :class:`ClipRetargeter`; ``frame_dt`` is ``1 / `` the aligned fps of the batch (``tgt_fps``,
+    unless the files are slower), and files whose aligned fps differ raise ``ValueError``."""
     from .utils import smpl
     t0 = time.perf_counter()
     from .ik_config import scale_rows
@@ -1300,6 +1337,8 @@ def retarget_smplx_loaded(raws: Sequence[Dict], smplx_body_model_path: str, tgt_
             if h not in gmr_of:
                 gmr_of[h] = GeneralMotionRetargeting("smplx", tgt_robot, actual_human_height=h, velocity_limit=velocity_limit)
     group_of = {i: (None if merged else height[i]) for i in height}
+    if gmr_of:
+        _refuse_chunk_under_frame_limit(next(iter(gmr_of.values())), frame_velocity_limit, chunk)
     device = post_path() == "device" and bool(raws)
     any_g = next(iter(gmr_of.values()), None)
     raw = device and smplx_path() == "device" and all(smpl.smplx_device_takes(bm, any_g) for bm in {id(b): b for b in bms.values()}.values())
@@ -1309,6 +1348,7 @@ def retarget_smplx_loaded(raws: Sequence[Dict], smplx_body_model_path: str, tgt_
             fps_of[i] = packed[i]["aligned_fps"]
         else:
             packed[i], fps_of[i] = smpl.smplx_frames_packed_fused(gmr_of[group_of[i]], d, bms[i], tgt_fps=tgt_fps)      # body model + alignment, one call
+    _set_batch_frame_limit(gmr_of.values(), frame_velocity_limit, fps_of.values())     # (the kept retargeter: this batch's limit, or none)
     t1 = time.perf_counter()
     dp = _smplx_device_post(any_g.xml_file) if device else None
     jobs = []
@@ -1373,7 +1413,7 @@ def _smplx_device_post(xml_file: str):
 def run_smplx_dataset(src_folder: str, tgt_folder: str, robot: str, smplx_folder: str, override: bool = False,
                       hard_motion_files: Sequence[str] = (), batch_files: int = 0, retarget=None, verbose: bool = True,
                       frames_budget: int = 1 << 19, loader_workers: int = -1, rank: int = 0, world: int = 1, load=None,
-                      stats: Optional[Dict] = None, chunk=None, velocity_limit=None) -> int:
+                      stats: Optional[Dict] = None, chunk=None, velocity_limit=None, frame_velocity_limit=None) -> int:
     """``smplx_to_robot_dataset.py:main`` (:171-242) on the pipeline above.  ``retarget(raws, files)`` defaults to
     :func:`retarget_smplx_loaded`, ``load(file)`` to the npz reader (tests inject stand-ins).  Returns the number of pkl
     files this rank wrote."""
@@ -1392,7 +1432,8 @@ def run_smplx_dataset(src_folder: str, tgt_folder: str, robot: str, smplx_folder
     if retarget is None:
         def retarget(raws, files):
             rep: List = []
-            out = retarget_smplx_loaded(raws, smplx_folder, robot, timing=timing, chunk=chunk, report=rep, velocity_limit=velocity_limit)
+            out = retarget_smplx_loaded(raws, smplx_folder, robot, timing=timing, chunk=chunk, report=rep, velocity_limit=velocity_limit,
+                                        frame_velocity_limit=frame_velocity_limit)
             if rep:
                 chunking.summarize(rep, chunk_summary)
             return out
@@ -1463,6 +1504,9 @@ def main(argv=None) -> int:
     ap.add_argument("--velocity_limit", type=float, default=None, metavar="RAD_PER_S",
                     help="per-joint velocity limit of every IK solve on every motor joint (upstream's use_velocity_limit: 9.42 = 3 pi); "
                          "a bound per solve, not on the velocity between frames (default: none)")
+    ap.add_argument("--frame_velocity_limit", type=float, default=None, metavar="RAD_PER_S",
+                    help="per-joint velocity limit between consecutive frames of every retargeted clip, on every motor joint, at the "
+                         "fps of the clips; not with --chunk_frames (default: none)")
     chunking.add_cli_arguments(ap)
     a = ap.parse_args(argv)
     chunk = chunking.spec_from_args(a)
@@ -1490,7 +1534,7 @@ def main(argv=None) -> int:
     if a.source == "bvh":
         n = run_bvh_dataset(a.src_folder, a.tgt_folder, a.robot, a.override, a.batch_files, verbose=not a.quiet,
                             frames_budget=a.frames_budget, loader_workers=a.num_cpus, rank=rank, world=world, stats=stats, chunk=chunk,
-                            velocity_limit=a.velocity_limit)
+                            velocity_limit=a.velocity_limit, frame_velocity_limit=a.frame_velocity_limit)
     else:
         from .params import ASSET_ROOT
         if ASSET_ROOT is None and (a.smplx_folder is None or a.hard_motions is None):
@@ -1501,7 +1545,8 @@ def main(argv=None) -> int:
                                                                     str(assets / "hard_motions" / "1.txt")]
         n = run_smplx_dataset(a.src_folder, a.tgt_folder, a.robot, smplx_folder, a.override, hard, a.batch_files,
                               verbose=not a.quiet, frames_budget=a.frames_budget, loader_workers=a.num_cpus, rank=rank,
-                              world=world, stats=stats, chunk=chunk, velocity_limit=a.velocity_limit)
+                              world=world, stats=stats, chunk=chunk, velocity_limit=a.velocity_limit,
+                              frame_velocity_limit=a.frame_velocity_limit)
     dt = time.perf_counter() - t0
     if chunk is not None:        # one line per rank: the mode is not parity, so what it did to the seams is always said
         print(json.dumps({"chunk_summary": {"rank": rank, **stats.get("chunk", {"clips_split": 0})}}))

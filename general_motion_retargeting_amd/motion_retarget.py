@@ -77,10 +77,14 @@ class GeneralMotionRetargeting:
         verbose: bool = False,
         use_velocity_limit: bool = False,
         velocity_limit=None,
+        frame_velocity_limit=None,
+        fps: Optional[float] = None,
     ) -> None:
         """``use_velocity_limit`` / ``velocity_limit``: per-joint velocity limits in the QP of every solve (upstream's
         ``use_velocity_limit=True`` = ``mink.VelocityLimit`` at 3 pi rad/s on every motor joint); see
-        :meth:`set_velocity_limit`.  Off by default."""
+        :meth:`set_velocity_limit`.  Off by default.
+        ``frame_velocity_limit`` / ``fps``: per-joint velocity limits of the retargeted motion itself, between consecutive
+        frames ``1 / fps`` apart; see :meth:`set_frame_velocity_limit`.  Off by default."""
         self.xml_file = str(ROBOT_XML_DICT[tgt_robot])
         if verbose:
             print("Use robot model: ", self.xml_file)
@@ -117,12 +121,14 @@ class GeneralMotionRetargeting:
         self._solver: Optional[_lib.Solver] = None
         self.use_velocity_limit = bool(use_velocity_limit) or velocity_limit is not None
         self._velocity_limit = velocity_limit_table(self.model, use_velocity_limit, velocity_limit)
+        self._frame_velocity_limit, self._frame_fps = self._frame_limit_table(frame_velocity_limit, fps)
         self.setup_retarget_configuration()
 
     # ------------------------------------------------------------------ #
     def setup_retarget_configuration(self):
         """Fresh configuration at ``qpos0`` (reference :74-75); tasks live in the packed task set."""
         self.configuration = _Configuration(self.model, self.model.qpos0.copy())
+        self._frames_done = 0         # frames retargeted into the configuration: from the second call on it IS the previous frame
 
     @property
     def hip_solver(self) -> _lib.Solver:
@@ -130,6 +136,8 @@ class GeneralMotionRetargeting:
             self._solver = _lib.Solver(self._model_blob, self._taskset_blob)   # raises without GPU/library
             if self._velocity_limit is not None:
                 self._solver.set_velocity_limit(self._velocity_limit)
+            if self._frame_velocity_limit is not None:
+                self._solver.set_frame_velocity_limit(self._frame_velocity_limit, 1.0 / self._frame_fps)
         return self._solver
 
     def set_velocity_limit(self, velocity_limit=None, use_velocity_limit: bool = False) -> None:
@@ -139,7 +147,8 @@ class GeneralMotionRetargeting:
         neither: no limit.  Every solve then keeps ``|dq_h| <= vmax_h * model.timestep`` next to the joint ranges, as
         ``mink.VelocityLimit`` does.  NOTE: that bounds ONE ``solve_ik`` call, as in mink; a frame runs up to 22 solves
         (two stages of ``max_iter + 1``), so a joint may move up to 22 times that far between two frames -- this is not a
-        limit on the joint velocity of the retargeted clip.  The floating base is never bounded."""
+        limit on the joint velocity of the retargeted clip (that is :meth:`set_frame_velocity_limit`).  The floating base is
+        never bounded."""
         table = velocity_limit_table(self.model, use_velocity_limit, velocity_limit)
         same = (table is None and self._velocity_limit is None) or \
             (table is not None and self._velocity_limit is not None and np.array_equal(table, self._velocity_limit))
@@ -152,6 +161,42 @@ class GeneralMotionRetargeting:
     def velocity_limit(self) -> Optional[np.ndarray]:
         """The table in force: ``f64[nhinge]`` rad/s (``inf`` = none for that hinge) or None."""
         return None if self._velocity_limit is None else self._velocity_limit.copy()
+
+    def _frame_limit_table(self, limit, fps):
+        """(table f64[nhinge] or None, fps or None) of the two arguments; raises before anything reaches the device."""
+        table = velocity_limit_table(self.model, False, limit)
+        if table is None:
+            return None, None
+        if fps is None or not (np.isfinite(float(fps)) and float(fps) > 0.0):
+            raise ValueError(f"frame_velocity_limit needs fps > 0 (the frames are 1 / fps apart), got fps = {fps!r}")
+        return table, float(fps)
+
+    def set_frame_velocity_limit(self, limit=None, fps: Optional[float] = None) -> None:
+        """Per-joint velocity limits of the retargeted MOTION, for every later call of this object: every frame keeps
+        ``|theta_h(t) - theta_h(t - 1)| <= limit_h / fps`` for every hinge, next to the joint ranges and the per-solve limit of
+        :meth:`set_velocity_limit`, inside the QP of every solve -- the other joints compensate for one that saturates, and a
+        joint that starts outside its range walks back by ``limit_h / fps`` per frame.  ``limit``: a scalar in rad/s for
+        every hinge, an array ``[nhinge]`` in ``model.joint_names`` order, or a dict ``{joint name: rad/s}`` (joints not
+        named: none); ``None``: no limit.  ``fps`` is required with a limit.  The first frame after construction or
+        :meth:`setup_retarget_configuration` is free (the configuration is ``qpos0`` then, not a pose of the motion); every
+        later frame of :meth:`retarget`, :meth:`retarget_packed` and :meth:`retarget_clip` is bounded around the frame
+        before it, so a per-frame loop equals one ``retarget_clip`` call.  The floating base is never bounded.  Does not go
+        with ``chunk=`` (chunks start from ``qpos0`` and seams are repaired by re-running: a seam would not carry the bound)."""
+        table, fps = self._frame_limit_table(limit, fps)
+        old = self._frame_velocity_limit
+        same = fps == self._frame_fps and ((table is None and old is None) or
+                                           (table is not None and old is not None and np.array_equal(table, old)))
+        self._frame_velocity_limit, self._frame_fps = table, fps
+        if self._solver is not None and not same:
+            self._solver.set_frame_velocity_limit(table, 0.0 if table is None else 1.0 / fps)
+
+    @property
+    def frame_velocity_limit(self) -> Optional[np.ndarray]:
+        """The frame table in force: ``f64[nhinge]`` rad/s (``inf`` = none for that hinge) or None."""
+        return None if self._frame_velocity_limit is None else self._frame_velocity_limit.copy()
+
+    def _frame_limit_on(self) -> bool:
+        return self._frame_velocity_limit is not None and bool(np.isfinite(self._frame_velocity_limit).any())
 
     @property
     def human_body_names(self) -> List[str]:
@@ -251,12 +296,14 @@ class GeneralMotionRetargeting:
         """One launch over ``human[T, nhuman, 7]`` continuing from the current configuration; keeps the last
         frame's targets and residual norms so that scaled_human_data / error1() / error2() refer to it."""
         q_out, nsolve, status, tg, er = self.hip_solver.retarget_streams(
-            self.configuration.data.qpos[None], human[None], flags=self._flags(offset_to_ground),
+            self.configuration.data.qpos[None], human[None],
+            flags=self._flags(offset_to_ground) | (_lib.FLAG_FRAME_LIMIT_FIRST if self._frames_done else 0),
             want_targets=True, want_errors=True)
         if status[0] != 0:
             raise RuntimeError(f"IK failed (status {int(status[0])}): QP not solvable / non-finite input")
         self._set_frame(human[-1], offset_to_ground, key_order)
         self.configuration.data.qpos = q_out[0, -1].copy()
+        self._frames_done += human.shape[0]
         self._targets, self._errors, self._errors_q = tg[0, -1], er[0, -1], q_out[0, -1].copy()
         return q_out[0], nsolve[0]
 
@@ -283,7 +330,8 @@ class GeneralMotionRetargeting:
         configuration exactly like calling :meth:`retarget` per frame.  ``frames`` is a sequence of
         ``human_data`` dicts or an array ``[T, nhuman, 7]``.  Returns ``qpos f64[T, nq]``.
         ``chunk`` (a ``chunking.ChunkSpec`` or ``"auto"``; default off): a clip longer than the spec's ``frames`` runs as
-        independent chunks with warm-up -- NOT parity with the per-frame loop; ``self.chunk_report`` says how far off."""
+        independent chunks with warm-up -- NOT parity with the per-frame loop; ``self.chunk_report`` says how far off.
+        ``chunk`` is refused (``ValueError``) while a finite frame velocity limit is set."""
         key_order = None
         if isinstance(frames, np.ndarray):
             human = np.ascontiguousarray(frames, dtype=np.float64)
@@ -293,6 +341,8 @@ class GeneralMotionRetargeting:
         if human.shape[0] == 0:
             return np.zeros((0, self.model.nq))
         from . import chunking
+        if chunk is not None and self._frame_limit_on():
+            raise ValueError(chunking.FRAME_LIMIT_REFUSAL)
         spec = chunking.resolve_any(chunk, [human.shape[0]])
         self.chunk_report = None
         if spec is not None:
@@ -302,6 +352,7 @@ class GeneralMotionRetargeting:
                 raise RuntimeError(f"IK failed (status {int(status[0])}): QP not solvable / non-finite input")
             self._set_frame(human[-1], offset_to_ground, key_order)
             self.configuration.data.qpos = q[0, -1].copy()
+            self._frames_done += human.shape[0]
             self._targets, self._errors, self._errors_q = None, None, None      # (evaluated on demand: tgt_out / err_out are not chunked)
             self.last_num_solves = ns[0].copy()
             return q[0]
@@ -324,19 +375,22 @@ class GeneralMotionRetargeting:
 
     def retarget_streams(self, human: np.ndarray, q0: Optional[np.ndarray] = None, lens=None,
                          offset_to_ground=False, heights=None, scales=None, want_targets: bool = False,
-                         want_errors: bool = False):
+                         want_errors: bool = False, q0_is_previous_frame: bool = False):
         """Many independent streams ``human[S, T, nhuman, 7]`` (each from ``q0[s]``, default
         ``qpos0`` = a fresh object per clip as the dataset scripts do).  Does not touch this object's
         configuration.  Returns ``(qpos[S, T, nq], nsolve[S, T, 2], status[S])``, with ``want_targets`` /
         ``want_errors`` also ``targets[S, T, nhuman, 7]`` (every frame's ``scaled_human_data``) and ``errors[S, T, 2]``
         (``error1()`` / ``error2()``).  ``heights[S]`` (one ``actual_human_height`` per stream) or ``scales[S, nhuman]``
         (one human scale table per stream: per-subject limb scaling) let subjects of different sizes share this object and
-        the launch; stream ``s`` then gets the bits of an object built for ``heights[s]``."""
+        the launch; stream ``s`` then gets the bits of an object built for ``heights[s]``.
+        ``q0_is_previous_frame`` (callers that resume streams): ``q0[s]`` is the pose of the frame before ``human[s, 0]``, so
+        the frame velocity limit (:meth:`set_frame_velocity_limit`) bounds frame 0 around it; by default frame 0 is free."""
         S = human.shape[0]
         scales = self.stream_scales(S, heights, scales)
         if q0 is None:
             q0 = np.broadcast_to(self.model.qpos0, (S, self.model.nq)).copy()
-        return self.hip_solver.retarget_streams(q0, human, lens=lens, flags=self._flags(offset_to_ground), scales=scales,
+        flags = self._flags(offset_to_ground) | (_lib.FLAG_FRAME_LIMIT_FIRST if q0_is_previous_frame else 0)
+        return self.hip_solver.retarget_streams(q0, human, lens=lens, flags=flags, scales=scales,
                                                 want_targets=want_targets, want_errors=want_errors)
 
     # ---- errors (reference :188-200): evaluated by the kernel ------------------------------

@@ -40,6 +40,9 @@ extern "C" {
 #define GMR_FLAG_OFFSET_TO_GROUND 1 /* retarget(human_data, offset_to_ground=True), motion_retarget.py:139 */
 #define GMR_FLAG_EVAL_ONLY 2        /* update_targets() without solve: preprocess + residual norms only, q_out = q in
                                        (motion_retarget.py:117-136 followed by error1()/error2(), :188-200)          */
+#define GMR_FLAG_FRAME_LIMIT_FIRST 4 /* q0 is the pose of the frame BEFORE frame 0: the frame velocity limit
+                                       (gmr_solver_set_frame_velocity_limits) bounds frame 0 around q0 as well; without it
+                                       frame 0 of a stream is free.  No effect without such a limit or with EVAL_ONLY      */
 
 /* per-stream status written by the IK kernel */
 #define GMR_STATUS_OK 0
@@ -96,13 +99,35 @@ int gmr_solver_set_dispatch(gmr_solver_t* solver, int frames_per_item);
  *     |dq_h| <= vdt_h = vmax_h * timestep
  * on top of the joint-range box: lo = min(max(lo_cfg, -vdt_h), vdt_h), hi likewise, so that a joint that starts outside
  * its range by more than vdt_h walks back at full rate (mink raises there).  This bounds ONE solve, as in mink -- a frame
- * runs up to 2 * (max_iter + 1) solves, so it is NOT a bound on the joint velocity between frames.  The six dofs of the
+ * runs up to 2 * (max_iter + 1) solves, so it is NOT a bound on the joint velocity between frames: that one is
+ * gmr_solver_set_frame_velocity_limits below.  The six dofs of the
  * free joint are never bounded.  A property of the handle: every launch from this solver issued after the call returns
  * uses it (streams, scaled streams, group jobs -- each job its own solver's table --, windows, queued or direct
  * dispatch); launches issued before finish on the old table.  n != nhinge, a NaN or a value <= 0 is GMR_ERR_ARG.
  * With no finite limit the kernels compute the bits they compute without this call. */
 int gmr_solver_set_velocity_limits(gmr_solver_t* solver, const double* vmax, int n);
 int gmr_solver_velocity_limits(const gmr_solver_t* solver, double* vmax_out, int n);
+/* Per-FRAME joint velocity limits: the retargeted clip itself keeps |theta_h(t) - theta_h(t - 1)| <= w_h = vmax[h] * frame_dt
+ * for every hinge (what a PD controller or hardware that plays the clip needs).  vmax f64 [nhinge] rad/s in hinge order,
+ * +inf = none for that hinge, NULL (n = 0 or nhinge) = none at all, the state of a new solver; frame_dt in seconds, one per
+ * handle; w_h is computed once, here, in double.  With theta0_h the hinge's angle when the frame starts (the previous
+ * frame's result; q0 for frame 0) every solve of the frame, at its current iterate theta_h, takes the box of the limits
+ * above (joint range, then the per-solve bound) and clamps it last into the window:
+ *     lf = (theta0_h - w_h) - theta_h,  hf = (theta0_h + w_h) - theta_h,
+ *     lo = min(max(lo, lf), hf),        hi = min(max(hi, lf), hf)
+ * -- the clamp form, so the box is never empty, and the window is the bound that always holds: a hinge outside its range
+ * walks back by w_h per frame.  A hinge without a range is bounded by the window alone; the free joint never is.
+ * Frame 0 of a stream is free unless the launch carries GMR_FLAG_FRAME_LIMIT_FIRST; frames t >= 1 are bounded around frame
+ * t - 1 by their index in the stream, so later windows of gmr_retarget_group_window_dev and later queue items continue
+ * under the bound with no flag.  Same contract as gmr_solver_set_velocity_limits: written in place into the images the
+ * solver owns (job tables stay valid), earlier launches finish on the old table, every launch path reads it.  n != nhinge,
+ * a NaN, a value <= 0, or a frame_dt that is not finite and positive while some vmax is finite: GMR_ERR_ARG, and nothing
+ * reaches the device.  With no finite entry the kernels compute the bits they compute without this call.
+ * NOT for chunked retargeting (chunking.py: gmr_chunk_*): every chunk starts from qpos0 and seams are repaired by
+ * re-running, so a seam would not carry the bound; the Python layer refuses chunk= while a finite frame limit is set.
+ * The getter returns the table and, where frame_dt_out is not NULL, frame_dt (0 while no entry is finite). */
+int gmr_solver_set_frame_velocity_limits(gmr_solver_t* solver, const double* vmax, int n, double frame_dt);
+int gmr_solver_frame_velocity_limits(const gmr_solver_t* solver, double* vmax_out, int n, double* frame_dt_out);
 
 /* ---- H2-H7: the retargeting loop ---------------------------------------------------------- */
 /* Replaces the caller loop `for frame in frames: qpos = retargeter.retarget(frame)`
