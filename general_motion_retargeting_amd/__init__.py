@@ -6,7 +6,7 @@ out of scope: SURVEY.md section 2).  Importing this package needs neither a GPU 
 library; every numerical entry point does, and raises if either is missing.
 """
 from .params import IK_CONFIG_ROOT, ASSET_ROOT, ROBOT_XML_DICT, IK_CONFIG_DICT, ROBOT_BASE_DICT, VIEWER_CAM_DISTANCE_DICT
-from .motion_retarget import GeneralMotionRetargeting, TargetNotSet
+from .motion_retarget import GeneralMotionRetargeting, TargetNotSet, body_weights_from_missing
 from .data_loader import load_robot_motion, save_robot_motion
 from .kinematics_model import KinematicsModel
 from .motion_library import MotionLibrary, MotionLoader
@@ -21,4 +21,4 @@ class RobotMotionViewer:  # pragma: no cover - out of scope (GUI), kept so impor
 
 __all__ = ["IK_CONFIG_ROOT", "ASSET_ROOT", "ROBOT_XML_DICT", "IK_CONFIG_DICT", "ROBOT_BASE_DICT",
            "VIEWER_CAM_DISTANCE_DICT", "GeneralMotionRetargeting", "TargetNotSet", "KinematicsModel",
-           "RobotMotionViewer", "load_robot_motion", "save_robot_motion", "MotionLibrary", "MotionLoader", "MotionTracker"]
+           "RobotMotionViewer", "body_weights_from_missing", "load_robot_motion", "save_robot_motion", "MotionLibrary", "MotionLoader", "MotionTracker"]

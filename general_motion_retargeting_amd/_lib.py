@@ -69,6 +69,14 @@ _SIGS = {
     "gmr_retarget_group_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "gmr_retarget_group": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "gmr_retarget_group_window_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "gmr_retarget_streams_weighted_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p]),
+    "gmr_retarget_streams_weighted": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gmr_retarget_group_weighted_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "gmr_retarget_group_weighted_window_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "gmr_retarget_group_weighted": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]),
     "gmr_host_alloc": (C.c_int, [C.POINTER(C.c_void_p), C.c_size_t]),
     "gmr_host_free": (C.c_int, [C.c_void_p]),
     "gmr_host_register": (C.c_int, [C.c_void_p, C.c_size_t]),
@@ -443,6 +451,35 @@ def check_scales(scales, S: int, nhuman: int, what: str = "scales"):
     return a
 
 
+def check_weights(weights, S: int, T: int, nhuman: int, what: str = "weights", lens=None):
+    """``weights`` as the contiguous ``f64[S, T, nhuman]`` array of per-frame body weights (None stays None): shape and values
+    -- finite, not negative -- are checked here, before any device call.  ``lens`` (``i32[S]`` or None): only the frames a stream
+    has are looked at; rows at or beyond ``lens[s]`` are padding that is never read, like the ``human`` rows there."""
+    if weights is None:
+        return None
+    a = np.asarray(weights)
+    if not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.integer) or a.dtype == np.bool_):
+        raise TypeError(f"{what}: numbers needed, got {a.dtype}")
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.shape != (S, T, nhuman):
+        raise ValueError(f"{what} must be [{S},{T},{nhuman}], got {a.shape}")
+    bad = ~(np.isfinite(a) & (a >= 0.0))
+    if lens is not None:
+        bad &= (np.arange(T)[None, :] < np.asarray(lens).reshape(S, 1))[..., None]
+    if bad.any():
+        s, t, b = (int(x) for x in np.argwhere(bad)[0])
+        raise ValueError(f"{what}: stream {s}, frame {t}, body {b} is {a[s, t, b]}: must be finite and not negative")
+    return a
+
+
+def _weight_list(ws):
+    """the parallel ``const double* const* weight`` of a job list: None when no job has weights"""
+    if all(w is None for w in ws):
+        return None, None
+    arr = (C.c_void_p * len(ws))(*[_addr(w) for w in ws])
+    return arr, C.cast(arr, C.c_void_p)
+
+
 class PostSrc(C.Structure):
     """``gmr_post_src_t``: one IK job's output as a source of :meth:`FkHandle.postprocess_clips_dev`."""
     _fields_ = [("S", C.c_int32), ("T", C.c_int32), ("q_out", C.c_void_p), ("len", C.c_void_p)]
@@ -474,12 +511,13 @@ def retarget_group(jobs, flags: int = 0, slices: int = 0, out_pinned: bool = Fal
     """Several (solver, batch) jobs as ONE scheduling domain through host buffers (``gmr_retarget_group``): the mixed-robot
     batch of BASELINE.json configs[3].  ``jobs`` = list of dicts ``{"solver": Solver, "human": f64[S,T,nhuman,7], optional
     "q0": f64[S,nq] (default the solver's qpos0), "lens": i32[S], "scales": f64[S,nhuman] (a human scale table per stream in
-    place of the solver's: :meth:`Solver.retarget_streams`)}``.  Returns one ``(q_out, nsolve, status)`` per job.
+    place of the solver's: :meth:`Solver.retarget_streams`), "weights": f64[S,T,nhuman] (per-frame body weights, 0 = the body is
+    missing in that frame; ``gmr_retarget_group_weighted``)}``.  Returns one ``(q_out, nsolve, status)`` per job.
     Inputs in pinned memory (:func:`pinned_empty`) and pinned outputs (``outs=`` from :func:`group_outputs`, reused across
     calls; or ``out_pinned=True``: allocated per call, which is slow) make the copies asynchronous, so that they overlap the
     kernels slice by slice."""
     arr = (Job * max(len(jobs), 1))()
-    keep, given, outs = [], outs, []
+    keep, given, outs, wts = [], outs, [], []
     empty = pinned_empty if out_pinned else (lambda shape, dtype: np.empty(shape, dtype))
     for i, j in enumerate(jobs):
         sol = j["solver"]
@@ -501,6 +539,7 @@ def retarget_group(jobs, flags: int = 0, slices: int = 0, out_pinned: bool = Fal
             if lens.shape != (S,):
                 raise ValueError(f"job {i}: lens must be [S]")
         scales = check_scales(j.get("scales"), S, sol.nhuman, f"job {i}: scales")
+        wts.append(check_weights(j.get("weights"), S, T, sol.nhuman, f"job {i}: weights", lens))
         if given is not None:
             q_out, nsolve, status = given[i]
             if q_out.shape != (S, T, sol.nq) or nsolve.shape != (S, T, 2) or status.shape != (S,) or q_out.dtype != np.float64 \
@@ -514,7 +553,11 @@ def retarget_group(jobs, flags: int = 0, slices: int = 0, out_pinned: bool = Fal
         outs.append((q_out, nsolve, status))
         arr[i] = Job(sol.handle.value, S, T, _addr(q0), _addr(human), _addr(lens), _addr(q_out), _addr(nsolve), _addr(status),
                      None, None, _addr(scales))
-    check(lib().gmr_retarget_group(C.cast(arr, C.c_void_p), len(jobs), int(flags), int(slices)))
+    wkeep, wlist = _weight_list(wts)
+    if wlist is None:
+        check(lib().gmr_retarget_group(C.cast(arr, C.c_void_p), len(jobs), int(flags), int(slices)))
+    else:
+        check(lib().gmr_retarget_group_weighted(C.cast(arr, C.c_void_p), len(jobs), wlist, int(flags), int(slices)))
     return outs
 
 
@@ -540,16 +583,26 @@ def dev_job(job, i: int = 0) -> DevJob:
     return job if isinstance(job, DevJob) else DevJob(*job)
 
 
-def retarget_group_dev(jobs, flags: int = 0, stream=None, window=None):
+def retarget_group_dev(jobs, flags: int = 0, stream=None, window=None, weights=None):
     """``gmr_retarget_group_dev``: ``jobs`` = list of :class:`DevJob` (or plain sequences of its first 9 or all 10 fields; the
     scale tables are unchecked: the values are the caller's responsibility); asynchronous on ``stream``.  ``window=(t_begin, t_end)``: only those frames of
-    every stream (``gmr_retarget_group_window_dev``; consecutive windows on one stream, starting at 0)."""
+    every stream (``gmr_retarget_group_window_dev``; consecutive windows on one stream, starting at 0).  ``weights``: one entry
+    per job, None or the job's per-frame body weights f64 [S][T][nhuman] on the device (unchecked, like the scale tables;
+    ``gmr_retarget_group_weighted_dev`` / ``_window_dev``)."""
+    if weights is not None and len(weights) != len(jobs):
+        raise ValueError(f"weights: one entry per job needed, got {len(weights)} for {len(jobs)} jobs")
+    wkeep, wlist = _weight_list(weights) if weights is not None else (None, None)
     arr = (Job * max(len(jobs), 1))()
     for i, job in enumerate(jobs):
         j = dev_job(job, i)
         arr[i] = Job(j.solver.handle.value, int(j.S), int(j.T), _addr(j.q0), _addr(j.human), _addr(j.len), _addr(j.q_out),
                      _addr(j.nsolve), _addr(j.status), None, None, _addr(j.scale))
-    if window is None:
+    if wlist is not None and window is None:
+        check(lib().gmr_retarget_group_weighted_dev(C.cast(arr, C.c_void_p), len(jobs), wlist, int(flags), _s(stream)))
+    elif wlist is not None:
+        check(lib().gmr_retarget_group_weighted_window_dev(C.cast(arr, C.c_void_p), len(jobs), wlist, int(flags), int(window[0]),
+                                                           int(window[1]), _s(stream)))
+    elif window is None:
         check(lib().gmr_retarget_group_dev(C.cast(arr, C.c_void_p), len(jobs), int(flags), _s(stream)))
     else:
         check(lib().gmr_retarget_group_window_dev(C.cast(arr, C.c_void_p), len(jobs), int(flags), int(window[0]), int(window[1]),
@@ -664,11 +717,13 @@ class Solver:
         return int(lib().gmr_retarget_lds_bytes(self.handle))
 
     def retarget_streams(self, q0, human, lens=None, flags: int = 0, want_targets: bool = False,
-                         want_errors: bool = False, scales=None):
+                         want_errors: bool = False, scales=None, weights=None):
         """Host arrays in/out: q0[S,nq], human[S,T,nhuman,7] -> q_out[S,T,nq], nsolve[S,T,2], status[S]
         (+ targets[S,T,nhuman,7] = the kernel's preprocessed frames and/or errors[S,T,2] = error1/error2 at the
         configuration every frame ends with, when asked for).  ``scales`` f64[S,nhuman]: a human scale table per stream
-        (``ik_config.scale_rows``) in place of the solver's own, so that subjects of different heights share one launch."""
+        (``ik_config.scale_rows``) in place of the solver's own, so that subjects of different heights share one launch.
+        ``weights`` f64[S,T,nhuman]: a multiplier per (stream, frame, human body) on the cost of every task bound to that body;
+        0 = the body is missing in that frame and its ``human`` row may hold anything (``gmr_retarget_streams_weighted``)."""
         human = np.ascontiguousarray(human, dtype=np.float64)
         if human.ndim != 4 or human.shape[2] != self.nhuman or human.shape[3] != 7:
             raise ValueError(f"human must be [S,T,{self.nhuman},7], got {human.shape}")
@@ -681,21 +736,32 @@ class Solver:
             if lens.shape != (S,):
                 raise ValueError("lens must be [S]")
         scales = check_scales(scales, S, self.nhuman)
+        weights = check_weights(weights, S, T, self.nhuman, lens=lens)
         q_out = np.zeros((S, T, self.nq), dtype=np.float64)
         nsolve = np.zeros((S, T, 2), dtype=np.int32)
         status = np.zeros(S, dtype=np.int32)
         targets = np.zeros((S, T, self.nhuman, 7), dtype=np.float64) if want_targets else None
         errors = np.zeros((S, T, 2), dtype=np.float64) if want_errors else None
-        check(lib().gmr_retarget_streams_scaled(self.handle, S, T, _ptr(q0), _ptr(human), _ptr(lens), _ptr(scales), int(flags),
-                                                _ptr(q_out), _ptr(nsolve), _ptr(status), _ptr(targets), _ptr(errors)))
+        if weights is None:
+            check(lib().gmr_retarget_streams_scaled(self.handle, S, T, _ptr(q0), _ptr(human), _ptr(lens), _ptr(scales), int(flags),
+                                                    _ptr(q_out), _ptr(nsolve), _ptr(status), _ptr(targets), _ptr(errors)))
+        else:
+            check(lib().gmr_retarget_streams_weighted(self.handle, S, T, _ptr(q0), _ptr(human), _ptr(lens), _ptr(scales), _ptr(weights),
+                                                      int(flags), _ptr(q_out), _ptr(nsolve), _ptr(status), _ptr(targets), _ptr(errors)))
         if want_targets or want_errors:
             return q_out, nsolve, status, targets, errors
         return q_out, nsolve, status
 
     def retarget_streams_dev(self, S, T, d_q0, d_human, d_len, flags, d_q_out, d_nsolve, d_status, stream=None,
-                             d_tgt_out=None, d_err_out=None, d_scale=None):
+                             d_tgt_out=None, d_err_out=None, d_scale=None, d_weight=None):
         """Device pointers (DeviceBuffer or raw c_void_p); asynchronous on `stream`.  ``d_scale``: f64 [S][nhuman] per-stream
-        human scale tables (unchecked: the values are the caller's responsibility)."""
+        human scale tables, ``d_weight``: f64 [S][T][nhuman] per-frame body weights (both unchecked: the values are the caller's
+        responsibility)."""
+        if d_weight is not None:
+            check(lib().gmr_retarget_streams_weighted_dev(self.handle, int(S), int(T), _d(d_q0), _d(d_human), _d(d_len), _d(d_scale),
+                                                          _d(d_weight), int(flags), _d(d_q_out), _d(d_nsolve), _d(d_status),
+                                                          _d(d_tgt_out), _d(d_err_out), _s(stream)))
+            return
         if d_scale is None:
             check(lib().gmr_retarget_streams_dev(self.handle, int(S), int(T), _d(d_q0), _d(d_human), _d(d_len), int(flags),
                                                  _d(d_q_out), _d(d_nsolve), _d(d_status), _d(d_tgt_out), _d(d_err_out),

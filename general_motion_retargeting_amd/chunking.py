@@ -193,6 +193,11 @@ FRAME_LIMIT_REFUSAL = ("chunked retargeting does not carry the frame velocity li
                        "drop chunk= or clear the limit (set_frame_velocity_limit(None))")
 
 
+# A chunk's warm-up frames and a repaired seam re-run frames of the clip under a chunk-local frame index, and the chunk entry
+# points take no weight array: the weights would have to be gathered and re-indexed with the frames.  No half version.
+BODY_WEIGHTS_REFUSAL = ("chunked retargeting does not take per-frame body weights: drop chunk= or the weights")
+
+
 class ChunkRunner:
     """The pass loop on one HIP stream.  Device buffers are grow-only and reused from batch to batch::
 

@@ -187,10 +187,12 @@ __device__ __forceinline__ void fk_wave(const LT& L, double* sm, const FkLane& F
 // ---------------------------------------------------------------------------------------------
 // residuals of the stage's tasks (mink FrameTask.compute_error) and their unweighted norm
 // (motion_retarget.py:188-200).  lane k < K.  Returns E in every lane.
+// WGT (the instances of launches with per-frame body weights, ik_streams_kernel): a task whose body is missing in this frame
+// -- both of its weights in table `stage` are zero, as the frame's rewrite left them -- stays out of the norm.
 // ---------------------------------------------------------------------------------------------
-template <int NW, class LT>
+template <int NW, bool WGT = false, class LT>
 __device__ __forceinline__ double errors_wave(const LT& L, double* sm, const short* task_body,
-                                              const short* task_human, int K, int lane, Prof& pr) {
+                                              const short* task_human, int K, int lane, Prof& pr, int stage = 0) {
   lane = fresh_lane(lane);
   PROF_BEGIN(pr);
   double ss = 0.0;
@@ -202,8 +204,10 @@ __device__ __forceinline__ double errors_wave(const LT& L, double* sm, const sho
     se3_log_rel5(d3{x[0], x[1], x[2]}, d4{x[3], x[4], x[5], x[6]}, d3{tg[0], tg[1], tg[2]},
                  d4{tg[3], tg[4], tg[5], tg[6]}, e, aux);
     double* eo = sm + L.o.e + 6 * lane;
+    bool keep = true;
+    if (WGT) keep = (sm + L.o.wpos[stage])[lane] != 0.0 || (sm + L.o.wrot[stage])[lane] != 0.0;
 #pragma unroll
-    for (int r = 0; r < 6; r++) { eo[r] = e[r]; ss += e[r] * e[r]; }
+    for (int r = 0; r < 6; r++) { eo[r] = e[r]; if (!WGT || keep) ss += e[r] * e[r]; }
     double* ao = sm + L.o.eaux + 5 * lane;     // a, sin|w|, cos|w|, |w|, 1/|w|: reused by the Jl^-1 phase
 #pragma unroll
     for (int r = 0; r < 5; r++) ao[r] = aux[r];
@@ -282,9 +286,10 @@ __device__ __forceinline__ RotHalf rot_half_wave(const LT& L, double* sm, const 
   return R;
 }
 
-// after the barrier behind helper 1's walk: e[0..2] and the residual norm E (in every lane)
-template <class LT>
-__device__ __forceinline__ double pos_half_wave(const LT& L, double* sm, const RotHalf& R, int tq, int th, int K, int lane, Prof& pr) {
+// after the barrier behind helper 1's walk: e[0..2] and the residual norm E (in every lane); WGT: as in errors_wave
+template <bool WGT = false, class LT>
+__device__ __forceinline__ double pos_half_wave(const LT& L, double* sm, const RotHalf& R, int tq, int th, int K, int lane, Prof& pr,
+                                                int stage = 0) {
   lane = fresh_lane(lane);
   PROF_BEGIN(pr);
   double ss = 0.0;
@@ -294,10 +299,12 @@ __device__ __forceinline__ double pos_half_wave(const LT& L, double* sm, const R
     double v[3];
     se3_log_rel5_pos(d3{x[0], x[1], x[2]}, R.qb, d3{tg[0], tg[1], tg[2]}, R.w, R.a, v);
     double* eo = sm + L.o.e + 6 * lane;
+    bool keep = true;
+    if (WGT) keep = (sm + L.o.wpos[stage])[lane] != 0.0 || (sm + L.o.wrot[stage])[lane] != 0.0;
 #pragma unroll
-    for (int r = 0; r < 3; r++) { eo[r] = v[r]; ss += v[r] * v[r]; }
+    for (int r = 0; r < 3; r++) { eo[r] = v[r]; if (!WGT || keep) ss += v[r] * v[r]; }
 #pragma unroll
-    for (int r = 0; r < 3; r++) ss += R.w[r] * R.w[r];
+    for (int r = 0; r < 3; r++) if (!WGT || keep) ss += R.w[r] * R.w[r];
   }
   ss = row0_sum(ss);
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
@@ -1002,10 +1009,13 @@ __device__ __forceinline__ void integrate_wave(const LT& L, double* sm, double d
 
 // ---------------------------------------------------------------------------------------------
 // target preprocessing (motion_retarget.py:203-270).  lane b < nhuman.
+// WGT: mw is this lane's body's multiplier of the frame.  A body with mw == 0 that is not the human root is missing: whatever
+// its raw row holds stays in this lane -- out of the lowest-foot search, and its target is the identity pose, which nothing reads
+// into a result (its tasks weigh zero and stay out of the residual norm).  The root's row is always read: every body moves with it.
 // ---------------------------------------------------------------------------------------------
-template <int NW, class LT>
+template <int NW, bool WGT = false, class LT>
 __device__ __forceinline__ void preprocess_wave(const LT& L, double* sm, const short* is_foot, int human_root,
-                                                double ground_offset, int flags, int lane, Prof& pr) {
+                                                double ground_offset, int flags, int lane, Prof& pr, double mw = 1.0) {
   lane = fresh_lane(lane);
   PROF_BEGIN(pr);
   const double* raw = sm + L.o.raw;
@@ -1014,6 +1024,7 @@ __device__ __forceinline__ void preprocess_wave(const LT& L, double* sm, const s
   d3 p = {0, 0, 0};
   d4 uq = {1, 0, 0, 0};
   const bool on = lane < L.nhum;
+  const bool missing = WGT && on && mw == 0.0 && lane != human_root;
   if (on) {
     const double* in = raw + 7 * lane;
     const double* rp = raw + 7 * human_root;
@@ -1030,12 +1041,13 @@ __device__ __forceinline__ void preprocess_wave(const LT& L, double* sm, const s
     d4 q = qnormalize(d4{in[3], in[4], in[5], in[6]});
     uq = qnormalize(qmul(q, qnormalize(d4{qo[0], qo[1], qo[2], qo[3]})));
     p = p + qrot(uq, d3{po[0], po[1], po[2]});
-    if (is_foot[lane] && p.x == p.x) z = p.z;
+    if (is_foot[lane] && p.x == p.x && (!WGT || !missing)) z = p.z;
   }
   if (flags & GMR_FLAG_OFFSET_TO_GROUND) {
     double lowest = row0_min(z);      // human bodies live in lanes 0..nhum-1, nhum <= 16
     p.z = p.z - lowest + ground_offset;
   }
+  if (WGT && missing) { p = d3{0, 0, 0}; uq = d4{1, 0, 0, 0}; }
   if (on) {
     double* o = tgt + 7 * lane;
     o[0] = p.x; o[1] = p.y; o[2] = p.z; o[3] = uq.w; o[4] = uq.x; o[5] = uq.y; o[6] = uq.z;
@@ -1056,7 +1068,12 @@ __device__ __forceinline__ void preprocess_wave(const LT& L, double* sm, const s
 // (gmr_solver_set_frame_velocity_limits).  It is a template argument, not a test in
 // the kernel: the clamp always on cost the headline 0.40 %, skipped by unlimited lanes 0.19 % (8 more spilled SGPRs), six
 // alternated runs each; the instances without it are the parent's code.
-template <int NVP, int NW, int QP, bool VLIM>
+// WGT: the launch carries per-frame body weights (`weight`, f64 [S][T][nhum], the last argument for the reason `scale` was:
+// gmr_retarget_streams_weighted).  At the top of a frame the main wavefront rewrites the task weight rows of both tables in LDS
+// as configured weight (re-read from the global image) times the multiplier of the task's human body; every reader of the rows
+// sits behind a later barrier.  Again a template argument: only <.., VLIM = true, WGT = true> exists besides the two above -- a
+// weighted launch of a solver without limits runs against its +inf tables, which leave the box's bits alone.
+template <int NVP, int NW, int QP, bool VLIM, bool WGT>
 __global__ __launch_bounds__(64 * NW, GMR_IK_MIN_WAVES) void ik_streams_kernel(const uint4* __restrict__ image, IkLay<NVP, NW> L, IkParams P,
                                                              int S, int T, const double* __restrict__ q0,
                                                              const double* __restrict__ human,
@@ -1067,7 +1084,8 @@ __global__ __launch_bounds__(64 * NW, GMR_IK_MIN_WAVES) void ik_streams_kernel(c
                                                              double* __restrict__ tgt_out,
                                                              double* __restrict__ err_out,
                                                              unsigned long long* __restrict__ prof_out,
-                                                             const double* __restrict__ scale) {
+                                                             const double* __restrict__ scale,
+                                                             const double* __restrict__ weight) {
   extern __shared__ __align__(16) double smem[];
   const int wave = threadIdx.x >> 6;
   const int lane = threadIdx.x & 63;
@@ -1153,18 +1171,35 @@ __global__ __launch_bounds__(64 * NW, GMR_IK_MIN_WAVES) void ik_streams_kernel(c
   int epoch = 0;
   // first frame's raw targets
   double r0 = 0.0, r1 = 0.0;
+  // WGT: lane b < nhum holds the multiplier of human body b, fetched with the frame (lanes beyond, or no array: 1)
+  const double* ws = WGT && weight ? weight + (size_t)s * T * nhum : nullptr;
+  double wn = 1.0;
   if (Ts > 0) {
     if (lane < (int)fstride) r0 = hs[lane];
     if (lane + 64 < (int)fstride) r1 = hs[lane + 64];
+    if (WGT && ws && lane < nhum) wn = ws[lane];
   }
   for (int t = 0; t < Ts; t++) {
     if (lane < (int)fstride) (sm + L.o.raw)[lane] = r0;
     if (lane + 64 < (int)fstride) (sm + L.o.raw)[lane + 64] = r1;
+    const double mw = wn;
     // prefetch the next frame (nhuman*7 <= 128 doubles)
     if (t + 1 < Ts) {
       const double* nx = hs + (size_t)(t + 1) * fstride;
       if (lane < (int)fstride) r0 = nx[lane];
       if (lane + 64 < (int)fstride) r1 = nx[lane + 64];
+      if (WGT && ws && lane < nhum) wn = ws[(size_t)(t + 1) * nhum + lane];
+    }
+    if (WGT) {         // this frame's task weights: one IEEE product each, formed from the solver's own (the helpers wait at a barrier)
+#pragma unroll
+      for (int st = 0; st < 2; st++) {
+        const bool on = lane < L.K[st];
+        const double mk = bpermute_d(on ? 4 * (si + L.o.i_task_human[st])[lane] : 0, mw);     // the multiplier of this task's body
+        if (on) {
+          (sm + L.o.wpos[st])[lane] = reinterpret_cast<const double*>(image)[L.o.wpos[st] + lane] * mk;
+          (sm + L.o.wrot[st])[lane] = reinterpret_cast<const double*>(image)[L.o.wrot[st] + lane] * mk;
+        }
+      }
     }
     WSYNC();
     if (VLIM) {        // q still holds what the frame starts from: the previous frame's result, or q0 (bounded only on the caller's word)
@@ -1174,9 +1209,17 @@ __global__ __launch_bounds__(64 * NW, GMR_IK_MIN_WAVES) void ik_streams_kernel(c
     int ns0 = 0, ns1 = 0;
     const size_t f = (size_t)s * T + t;
     if (stat == GMR_STATUS_OK) {
-      preprocess_wave<NW>(L, sm, is_foot, human_root, prm[4], flags, lane, pr);
-      if (tgt_out)     // the poses handed to task.set_target (motion_retarget.py:117-136) = scaled_human_data
-        for (int i = lane; i < (int)fstride; i += 64) tgt_out[f * fstride + i] = (sm + L.o.tgt)[i];
+      if (!WGT) {
+        preprocess_wave<NW>(L, sm, is_foot, human_root, prm[4], flags, lane, pr);
+        if (tgt_out)     // the poses handed to task.set_target (motion_retarget.py:117-136) = scaled_human_data
+          for (int i = lane; i < (int)fstride; i += 64) tgt_out[f * fstride + i] = (sm + L.o.tgt)[i];
+      } else {
+        preprocess_wave<NW, true>(L, sm, is_foot, human_root, prm[4], flags, lane, pr, mw);
+        if (tgt_out && lane < nhum) {      // a body lane stores its own row: seven NaNs for a missing body, as for an absent one
+          const bool missing = mw == 0.0 && lane != human_root;
+          for (int r = 0; r < 7; r++) tgt_out[f * fstride + 7 * lane + r] = missing ? (double)NAN : (sm + L.o.tgt)[7 * lane + r];
+        }
+      }
       double last_E = -1.0;                          // the stage's last residual norm (at the current configuration)
       for (int stage = 0; stage < 2; stage++) {
         if (!(stage == 0 ? use0 : use1) || (flags & GMR_FLAG_EVAL_ONLY)) continue;
@@ -1201,7 +1244,7 @@ __global__ __launch_bounds__(64 * NW, GMR_IK_MIN_WAVES) void ik_streams_kernel(c
         // (same task list in both tables: the first stage's last evaluation is this stage's first, and its residuals
         //  and log-map terms are still in LDS for the Jl^-1 phase)
         double curr = (stage == 1 && (use1 & 2) && last_E >= 0.0) ? last_E
-                                                                 : errors_wave<NW>(L, sm, tb.task_body, tb.task_human, K, lane, pr);
+                                                                 : errors_wave<NW, WGT>(L, sm, tb.task_body, tb.task_human, K, lane, pr, stage);
         int nsol = 0, num_iter = 0;
         for (;;) {
           const bool first = nsol == 0;
@@ -1231,11 +1274,11 @@ __global__ __launch_bounds__(64 * NW, GMR_IK_MIN_WAVES) void ik_streams_kernel(c
             PROF_BEGIN(pr);
             __syncthreads();                    // K2: xa is final; the helpers go on to the body Jacobians
             PROF_END(pr, PH_K2);
-            next = pos_half_wave(L, sm, rh, tq_main[stage], th_main[stage], K, lane, pr);
+            next = pos_half_wave<WGT>(L, sm, rh, tq_main[stage], th_main[stage], K, lane, pr, stage);
           } else {
             integrate_wave<NW>(L, sm, prm[5], lane, pr);
             fk_wave<NW>(L, sm, fkc, lane, pr);
-            next = errors_wave<NW>(L, sm, tb.task_body, tb.task_human, K, lane, pr);
+            next = errors_wave<NW, WGT>(L, sm, tb.task_body, tb.task_human, K, lane, pr, stage);
           }
           last_E = next;
           nsol++;
@@ -1253,7 +1296,7 @@ __global__ __launch_bounds__(64 * NW, GMR_IK_MIN_WAVES) void ik_streams_kernel(c
       for (int stage = 0; stage < 2; stage++) {
         double E = 0.0;
         if (stage == 0 ? use0 : use1)
-          E = errors_wave<NW>(L, sm, si + L.o.i_task_body[stage], si + L.o.i_task_human[stage], L.K[stage], lane, pr);
+          E = errors_wave<NW, WGT>(L, sm, si + L.o.i_task_body[stage], si + L.o.i_task_human[stage], L.K[stage], lane, pr, stage);
         if (lane == 0) err_out[2 * f + stage] = E;
       }
     }
@@ -1283,33 +1326,35 @@ __global__ __launch_bounds__(64 * NW, GMR_IK_MIN_WAVES) void ik_streams_kernel(c
 // has SIMDs, the helpers share the two wide assembly phases).  The solver of an instance follows from the
 // robot's decomposition: NW = 1 runs the tree solver in DPP rows (<7, 9> fits a row) or the dense one,
 // NW = 4 (only launched for robots that decompose) the <7, 9> or the <8, 10> tree instance.
-template <int NVP, int NW, int QP, bool VLIM>
+template <int NVP, int NW, int QP, bool VLIM, bool WGT>
 static hipError_t launch_nvp(const uint4* d_image, const gmr::IkLayout* L, const gmr::IkParams* P, int S, int T,
                              const double* d_q0, const double* d_human,
                              const int32_t* d_len, const double* d_scale, int flags, double* d_q_out, int32_t* d_nsolve,
-                             int32_t* d_status, double* d_tgt_out, double* d_err_out, hipStream_t stream, unsigned long long* d_prof) {
-  hipLaunchKernelGGL((gmr::ik_streams_kernel<NVP, NW, QP, VLIM>), dim3(S), dim3(64 * NW), L->smem_bytes, stream, d_image,
+                             int32_t* d_status, double* d_tgt_out, double* d_err_out, hipStream_t stream, unsigned long long* d_prof,
+                             const double* d_weight) {
+  hipLaunchKernelGGL((gmr::ik_streams_kernel<NVP, NW, QP, VLIM, WGT>), dim3(S), dim3(64 * NW), L->smem_bytes, stream, d_image,
                      gmr::IkLay<NVP, NW>(static_cast<const gmr::IkDims&>(*L)), *P, S, T, d_q0, d_human, d_len, flags, d_q_out, d_nsolve, d_status,
-                     d_tgt_out, d_err_out, d_prof, d_scale);
+                     d_tgt_out, d_err_out, d_prof, d_scale, d_weight);
   return hipGetLastError();
 }
 
-#define GMR_ARGS d_image, L, P, S, T, d_q0, d_human, d_len, d_scale, flags, d_q_out, d_nsolve, d_status, d_tgt_out, d_err_out, stream, d_prof
-#define GMR_DISPATCH_V(NVP_, V_)                                                                       \
-    if (L->nw == 1) return L->tree_small ? launch_nvp<NVP_, 1, gmr::QP_TREE_SMALL, V_>(GMR_ARGS)       \
-                                         : launch_nvp<NVP_, 1, gmr::QP_DENSE, V_>(GMR_ARGS);           \
-    return L->tree_small ? launch_nvp<NVP_, 4, gmr::QP_TREE_SMALL, V_>(GMR_ARGS)                       \
-                         : launch_nvp<NVP_, 4, gmr::QP_TREE, V_>(GMR_ARGS);
+#define GMR_ARGS d_image, L, P, S, T, d_q0, d_human, d_len, d_scale, flags, d_q_out, d_nsolve, d_status, d_tgt_out, d_err_out, stream, d_prof, d_weight
+#define GMR_DISPATCH_V(NVP_, V_, W_)                                                                   \
+    if (L->nw == 1) return L->tree_small ? launch_nvp<NVP_, 1, gmr::QP_TREE_SMALL, V_, W_>(GMR_ARGS)   \
+                                         : launch_nvp<NVP_, 1, gmr::QP_DENSE, V_, W_>(GMR_ARGS);       \
+    return L->tree_small ? launch_nvp<NVP_, 4, gmr::QP_TREE_SMALL, V_, W_>(GMR_ARGS)                   \
+                         : launch_nvp<NVP_, 4, gmr::QP_TREE, V_, W_>(GMR_ARGS);
 #define GMR_DISPATCH(NVP_)                                                                             \
   case NVP_:                                                                                           \
-    if (vlim) { GMR_DISPATCH_V(NVP_, true) }                                                           \
-    GMR_DISPATCH_V(NVP_, false)
+    if (d_weight) { GMR_DISPATCH_V(NVP_, true, true) }      /* (the limits' tables are +inf where none is set) */ \
+    if (vlim) { GMR_DISPATCH_V(NVP_, true, false) }                                                    \
+    GMR_DISPATCH_V(NVP_, false, false)
 
 extern "C" hipError_t gmr_launch_ik_streams(const uint4* d_image, const gmr::IkLayout* L, const gmr::IkParams* P,
                                             int S, int T, const double* d_q0, const double* d_human,
                                             const int32_t* d_len, const double* d_scale, int flags, double* d_q_out,
                                             int32_t* d_nsolve, int32_t* d_status, double* d_tgt_out, double* d_err_out,
-                                            hipStream_t stream, unsigned long long* d_prof, int vlim) {
+                                            hipStream_t stream, unsigned long long* d_prof, int vlim, const double* d_weight) {
   if (S <= 0 || T <= 0) return hipSuccess;
   switch (L->nvp) {
     GMR_DISPATCH(28)
@@ -1320,26 +1365,29 @@ extern "C" hipError_t gmr_launch_ik_streams(const uint4* d_image, const gmr::IkL
   }
 }
 
-template <int NVP, bool VLIM>
+template <int NVP, bool VLIM, bool WGT = false>
 static const void* kernel_of(int nw, int tree_small) {
-  if (nw == 1) return tree_small ? reinterpret_cast<const void*>(gmr::ik_streams_kernel<NVP, 1, gmr::QP_TREE_SMALL, VLIM>)
-                                 : reinterpret_cast<const void*>(gmr::ik_streams_kernel<NVP, 1, gmr::QP_DENSE, VLIM>);
-  return tree_small ? reinterpret_cast<const void*>(gmr::ik_streams_kernel<NVP, 4, gmr::QP_TREE_SMALL, VLIM>)
-                    : reinterpret_cast<const void*>(gmr::ik_streams_kernel<NVP, 4, gmr::QP_TREE, VLIM>);
+  if (nw == 1) return tree_small ? reinterpret_cast<const void*>(gmr::ik_streams_kernel<NVP, 1, gmr::QP_TREE_SMALL, VLIM, WGT>)
+                                 : reinterpret_cast<const void*>(gmr::ik_streams_kernel<NVP, 1, gmr::QP_DENSE, VLIM, WGT>);
+  return tree_small ? reinterpret_cast<const void*>(gmr::ik_streams_kernel<NVP, 4, gmr::QP_TREE_SMALL, VLIM, WGT>)
+                    : reinterpret_cast<const void*>(gmr::ik_streams_kernel<NVP, 4, gmr::QP_TREE, VLIM, WGT>);
 }
 
-// opt the two instances that (nvp, nw, tree_small) selects, without and with velocity limits, into `bytes` of dynamic LDS on
-// the CURRENT device
+// opt the three instances that (nvp, nw, tree_small) selects -- without limits, with velocity limits, with body weights -- into
+// `bytes` of dynamic LDS on the CURRENT device
+#define GMR_SMEM_CASE(NVP_) \
+    case NVP_: f[0] = kernel_of<NVP_, false>(nw, tree_small); f[1] = kernel_of<NVP_, true>(nw, tree_small); f[2] = kernel_of<NVP_, true, true>(nw, tree_small); break;
 extern "C" hipError_t gmr_ik_set_max_smem(int nvp, int nw, int tree_small, int bytes) {
-  const void* f[2] = {nullptr, nullptr};
+  const void* f[3] = {nullptr, nullptr, nullptr};
   switch (nvp) {
-    case 28: f[0] = kernel_of<28, false>(nw, tree_small); f[1] = kernel_of<28, true>(nw, tree_small); break;
-    case 32: f[0] = kernel_of<32, false>(nw, tree_small); f[1] = kernel_of<32, true>(nw, tree_small); break;
-    case 36: f[0] = kernel_of<36, false>(nw, tree_small); f[1] = kernel_of<36, true>(nw, tree_small); break;
-    case 48: f[0] = kernel_of<48, false>(nw, tree_small); f[1] = kernel_of<48, true>(nw, tree_small); break;
+    GMR_SMEM_CASE(28)
+    GMR_SMEM_CASE(32)
+    GMR_SMEM_CASE(36)
+    GMR_SMEM_CASE(48)
     default: return hipErrorInvalidValue;
   }
-  const hipError_t e = hipFuncSetAttribute(f[0], hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  return e != hipSuccess ? e : hipFuncSetAttribute(f[1], hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  for (int i = 0; i < 3; i++)
+    if (const hipError_t e = hipFuncSetAttribute(f[i], hipFuncAttributeMaxDynamicSharedMemorySize, bytes)) return e;
+  return hipSuccess;
 }
 #endif  // GMR_IK_WALKS_ONLY

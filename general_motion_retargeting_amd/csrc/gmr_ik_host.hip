@@ -15,6 +15,7 @@
 #include "../../include/gmr_hip.h"
 #include "gmr_ik_layout.h"
 #include "gmr_ik_stage.h"
+#include "gmr_ik_weight_stage.h"
 #include "gmr_ik_wide_layout.h"
 #include "gmr_internal.h"
 #include "gmr_launch.h"
@@ -260,8 +261,9 @@ static bool has_work(const gmr_job_t& J) { return J.S > 0 && J.T > 0; }
 
 // What every entry point asks of a job, in this order: a solver, S and T not negative -- a job without streams or frames is
 // not looked at further -- every mandatory buffer, and, for host buffers (the device entry points cannot look), every entry of
-// a scale table finite and positive.  j >= 0 puts "job j: " in front of the message.
-static int check_job(const gmr_job_t& J, bool host, int j) {
+// a scale table finite and positive and every body weight finite and not negative.  j >= 0 puts "job j: " in front of the message.
+// `weight`: the job's per-frame body weights [S][T][nhuman] or null; they travel beside the job (gmr_ik_weight_stage.h).
+static int check_job(const gmr_job_t& J, const double* weight, bool host, int j) {
   char pre[24] = "";
   if (j >= 0) snprintf(pre, sizeof pre, "job %d: ", j);
   if (!J.solver) return fail(GMR_ERR_ARG, "%snull solver", pre);
@@ -273,25 +275,35 @@ static int check_job(const gmr_job_t& J, bool host, int j) {
   for (size_t i = 0; host && J.scale && i < (size_t)J.S * nh; i++)
     if (!(J.scale[i] > 0.0) || !std::isfinite(J.scale[i]))
       return fail(GMR_ERR_ARG, "%sscale of stream %d, body %d is %g: must be finite and positive", pre, (int)(i / nh), (int)(i % nh), J.scale[i]);
+  // (only the frames a stream has: rows at or beyond len[s] are padding that no kernel reads, like the human rows there)
+  for (int s = 0; host && weight && s < J.S; s++) {
+    const size_t Ts = (size_t)(J.len ? std::min(std::max(J.len[s], 0), J.T) : J.T);
+    const double* w = weight + (size_t)s * J.T * nh;
+    for (size_t i = 0; i < Ts * nh; i++)
+      if (!(w[i] >= 0.0) || !std::isfinite(w[i]))
+        return fail(GMR_ERR_ARG, "%sweight of stream %d, frame %d, body %d is %g: must be finite and not negative", pre, s, (int)(i / nh),
+                    (int)(i % nh), w[i]);
+  }
   return GMR_OK;
 }
 
 // a list of jobs: the first bad one reports; what the jobs with work add up to
 struct Batch {
   long long total = 0;           // streams
-  size_t in_bytes = 0;           // of the human frames
+  size_t in_bytes = 0;           // of the per-frame inputs: the human frames and the body weights a job carries
   int njobs = 0, maxT = 0;
   gmr_solver* owner = nullptr;   // the first of their solvers: its pipeline streams, workspaces and queue pool serve the batch
 };
-static int check_jobs(const gmr_job_t* jobs, int njobs, bool host, Batch* b) {
+static const double* weight_of(const double* const* weight, int j) { return weight ? weight[j] : nullptr; }
+static int check_jobs(const gmr_job_t* jobs, int njobs, const double* const* weight, bool host, Batch* b) {
   if (njobs < 0 || (njobs > 0 && !jobs)) return fail(GMR_ERR_ARG, "bad job list");
   for (int j = 0; j < njobs; j++) {
     const gmr_job_t& J = jobs[j];
-    if (int rc = check_job(J, host, j)) return rc;
+    if (int rc = check_job(J, weight_of(weight, j), host, j)) return rc;
     if (!has_work(J)) continue;
     if (!b->owner) b->owner = J.solver;
     b->total += J.S;
-    b->in_bytes += (size_t)J.S * J.T * gmr::kIkFields[gmr::IK_HUMAN].per_nhuman * J.solver->ts.nhuman;
+    b->in_bytes += (size_t)J.S * J.T * (gmr::kIkFields[gmr::IK_HUMAN].per_nhuman + (weight_of(weight, j) ? 8 : 0)) * J.solver->ts.nhuman;
     b->njobs++;
     b->maxT = std::max(b->maxT, (int)J.T);
   }
@@ -302,50 +314,61 @@ static int check_jobs(const gmr_job_t* jobs, int njobs, bool host, Batch* b) {
 static bool job_takes_wide_shape(const gmr_solver* s, long long streams) {
   return gmr::ik_throughput_shape(s->layout4.tree_ok, s->force_waves, streams, s->wide.ok);
 }
-static gmr_wide_job_desc wide_desc(const gmr_job_t& J) {
+static gmr_wide_job_desc wide_desc(const gmr_job_t& J, const double* d_weight) {
   gmr_solver* s = J.solver;
   return gmr_wide_job_desc{s->wide_image.data(), &s->wide, &s->params, J.S, J.T, J.q0, J.human, J.len, J.q_out, J.nsolve, J.status,
-                           J.tgt_out, J.err_out, J.scale, s->flim};
+                           J.tgt_out, J.err_out, J.scale, s->flim, d_weight};
 }
-// a checked job with work, by itself (d_prof: diagnostic builds)
-static int launch_job(const gmr_job_t& J, int flags, hipStream_t stream, unsigned long long* d_prof = nullptr) {
+// a checked job with work, by itself (d_weight: its body weights on the device or null; d_prof: diagnostic builds)
+static int launch_job(const gmr_job_t& J, const double* d_weight, int flags, hipStream_t stream, unsigned long long* d_prof = nullptr) {
   gmr_solver* s = J.solver;
   const bool helpers = gmr::ik_helpers_shape(s->layout4.tree_ok, s->force_waves, J.S);
   if (job_takes_wide_shape(s, J.S))
     GMR_HIP_TRY(gmr_launch_ik_wide(s->wide_image.data(), &s->wide, &s->params, J.S, J.T, J.q0, J.human, J.len, J.scale, flags, J.q_out,
-                                   J.nsolve, J.status, J.tgt_out, J.err_out, stream, d_prof, d_prof ? nullptr : s->wide_pool, s->flim));
+                                   J.nsolve, J.status, J.tgt_out, J.err_out, stream, d_prof, d_prof ? nullptr : s->wide_pool, s->flim, d_weight));
   else
     GMR_HIP_TRY(gmr_launch_ik_streams((const uint4*)(helpers ? s->image4 : s->image).data(), helpers ? &s->layout4 : &s->layout, &s->params,
                                       J.S, J.T, J.q0, J.human, J.len, J.scale, flags, J.q_out, J.nsolve, J.status, J.tgt_out, J.err_out,
-                                      stream, d_prof, s->vlim | s->flim));
+                                      stream, d_prof, s->vlim | s->flim, d_weight));
   return GMR_OK;
 }
 
 int gmr_retarget_streams_dev(gmr_solver_t* s, int S, int T, const double* d_q0, const double* d_human, const int32_t* d_len, int flags,
                              double* d_q_out, int32_t* d_nsolve, int32_t* d_status, double* d_tgt_out, double* d_err_out, void* stream) {
-  return gmr_retarget_streams_scaled_dev(s, S, T, d_q0, d_human, d_len, nullptr, flags, d_q_out, d_nsolve, d_status, d_tgt_out, d_err_out, stream);
+  return gmr_retarget_streams_weighted_dev(s, S, T, d_q0, d_human, d_len, nullptr, nullptr, flags, d_q_out, d_nsolve, d_status, d_tgt_out, d_err_out, stream);
 }
 
 int gmr_retarget_streams_scaled_dev(gmr_solver_t* s, int S, int T, const double* d_q0, const double* d_human, const int32_t* d_len,
                                     const double* d_scale, int flags, double* d_q_out, int32_t* d_nsolve, int32_t* d_status,
                                     double* d_tgt_out, double* d_err_out, void* stream) {
+  return gmr_retarget_streams_weighted_dev(s, S, T, d_q0, d_human, d_len, d_scale, nullptr, flags, d_q_out, d_nsolve, d_status, d_tgt_out, d_err_out, stream);
+}
+
+int gmr_retarget_streams_weighted_dev(gmr_solver_t* s, int S, int T, const double* d_q0, const double* d_human, const int32_t* d_len,
+                                      const double* d_scale, const double* d_weight, int flags, double* d_q_out, int32_t* d_nsolve,
+                                      int32_t* d_status, double* d_tgt_out, double* d_err_out, void* stream) {
   const gmr_job_t job{s, S, T, d_q0, d_human, d_len, d_q_out, d_nsolve, d_status, d_tgt_out, d_err_out, d_scale};
-  if (int rc = check_job(job, false, -1)) return rc;
-  return has_work(job) ? launch_job(job, flags, (hipStream_t)stream) : GMR_OK;
+  if (int rc = check_job(job, d_weight, false, -1)) return rc;
+  return has_work(job) ? launch_job(job, d_weight, flags, (hipStream_t)stream) : GMR_OK;
 }
 
 #ifdef GMR_IK_PROFILE
 // diagnostic builds only (tools/phase_profile.py): per-stream phase cycle counters
 int gmr_retarget_streams_prof(gmr_solver_t* s, int S, int T, const double* d_q0, const double* d_human, int flags,
                               double* d_q_out, int32_t* d_nsolve, int32_t* d_status, unsigned long long* d_prof) {
-  return launch_job(gmr_job_t{s, S, T, d_q0, d_human, nullptr, d_q_out, d_nsolve, d_status, nullptr, nullptr, nullptr}, flags, nullptr, d_prof);
+  return launch_job(gmr_job_t{s, S, T, d_q0, d_human, nullptr, d_q_out, d_nsolve, d_status, nullptr, nullptr, nullptr}, nullptr, flags, nullptr, d_prof);
 }
 #endif
 
 // ---- group launches: several (robot, task set) jobs as one scheduling domain ---------------------------------------
 int gmr_retarget_group_dev(const gmr_job_t* jobs, int njobs, int flags, void* stream) {
+  return gmr_retarget_group_weighted_dev(jobs, njobs, nullptr, flags, stream);
+}
+
+// weight: null, or njobs entries, each null or the job's body weights [S][T][nhuman] on the device
+int gmr_retarget_group_weighted_dev(const gmr_job_t* jobs, int njobs, const double* const* weight, int flags, void* stream) {
   Batch b;
-  if (int rc = check_jobs(jobs, njobs, false, &b)) return rc;
+  if (int rc = check_jobs(jobs, njobs, weight, false, &b)) return rc;
   // The throughput kernel is one instance for every robot of its size class: all jobs that take that shape at this
   // width (the width of the GROUP decides, not a job's own) go out as launches of up to 8 jobs; the others -- robots
   // that do not decompose, solvers forced to the latency shape, groups too small for the throughput shape -- one by one.
@@ -364,9 +387,9 @@ int gmr_retarget_group_dev(const gmr_job_t* jobs, int njobs, int flags, void* st
     if (!has_work(J)) continue;
     if (njobs > 1 && job_takes_wide_shape(J.solver, b.total)) {
       if (nw == 0) pool = J.solver->wide_pool;
-      wd[nw++] = wide_desc(J);
+      wd[nw++] = wide_desc(J, weight_of(weight, j));
       if (nw == 8) { int rc = flush(); if (rc) return rc; }
-    } else if (int rc = launch_job(J, flags, (hipStream_t)stream)) {
+    } else if (int rc = launch_job(J, weight_of(weight, j), flags, (hipStream_t)stream)) {
       return rc;
     }
   }
@@ -385,15 +408,20 @@ static bool group_is_windowable(const gmr_job_t* jobs, int njobs, const Batch& b
 }
 
 int gmr_retarget_group_window_dev(const gmr_job_t* jobs, int njobs, int flags, int t_begin, int t_end, void* stream) {
+  return gmr_retarget_group_weighted_window_dev(jobs, njobs, nullptr, flags, t_begin, t_end, stream);
+}
+
+int gmr_retarget_group_weighted_window_dev(const gmr_job_t* jobs, int njobs, const double* const* weight, int flags, int t_begin,
+                                           int t_end, void* stream) {
   const bool list_ok = njobs >= 0 && (njobs == 0 || jobs);       // (a bad list reports first, from check_jobs)
   if (list_ok && (t_begin < 0 || t_end <= t_begin)) return fail(GMR_ERR_ARG, "bad window [%d, %d)", t_begin, t_end);
   Batch b;
-  if (int rc = check_jobs(jobs, njobs, false, &b)) return rc;
+  if (int rc = check_jobs(jobs, njobs, weight, false, &b)) return rc;
   if (!group_is_windowable(jobs, njobs, b)) return fail(GMR_ERR_ARG, "this batch does not take the throughput shape as a whole: launch it unwindowed");
   gmr_wide_job_desc wd[8];
   int nw = 0;
   for (int j = 0; j < njobs; j++)
-    if (has_work(jobs[j])) wd[nw++] = wide_desc(jobs[j]);
+    if (has_work(jobs[j])) wd[nw++] = wide_desc(jobs[j], weight_of(weight, j));
   hipError_t e = gmr_launch_ik_wide_window(wd, nw, flags, (hipStream_t)stream, nullptr, b.owner->wide_pool, t_begin, t_end);
   if (e != hipSuccess) return fail(GMR_ERR_HIP, "window launch: %s", hipGetErrorString(e));
   return GMR_OK;
@@ -402,6 +430,20 @@ int gmr_retarget_group_window_dev(const gmr_job_t* jobs, int njobs, int flags, i
 // ---- host buffers -------------------------------------------------------------------------------------------------------------
 static gmr::IkJobOff carve_job(gmr::Carve& c, const gmr_job_t& J, size_t S) {
   return gmr::ik_carve_job(c, J, (size_t)J.solver->model.nq, (size_t)J.solver->ts.nhuman, S);
+}
+// S streams of a job's body weights, in front of the job's own arrays (gmr_ik_weight_stage.h)
+static gmr::IkWeightOff carve_weight(gmr::Carve& c, const gmr_job_t& J, const double* weight, size_t S) {
+  return gmr::ik_carve_weight(c, weight, (size_t)J.solver->ts.nhuman, S, (size_t)J.T);
+}
+// n (0 or 1) copies of the host array `weight` into the device block d, on `st`
+static int issue_weight(const gmr::IkCopy* c, int n, const double* weight, char* d, hipStream_t st, const char* what) {
+  for (int i = 0; i < n; i++) {
+    const char* h = reinterpret_cast<const char*>(weight) + c[i].host;
+    const hipError_t e = c[i].rows == 1 ? hipMemcpyAsync(d + c[i].dev, h, c[i].width, hipMemcpyHostToDevice, st)
+                                        : hipMemcpy2DAsync(d + c[i].dev, c[i].pitch, h, c[i].pitch, c[i].width, c[i].rows, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return fail(GMR_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+  }
+  return GMR_OK;
 }
 // the copies c[0 .. n) between the host arrays of J and the device block d, on `st`; a failure reports as "<what>: ..."
 static int issue(const gmr::IkCopy* c, int n, const gmr_job_t& J, char* d, hipStream_t st, const char* what) {
@@ -429,12 +471,17 @@ static int zero_outputs(const gmr_job_t& J, char* d, const gmr::IkJobOff& o, hip
 // window w - 1 likewise.  (Cutting such a batch by streams loses: launches narrower than the resident width are bound by
 // their longest stream.)  Three HIP streams, one device workspace holding the whole batch; results are bit-identical to
 // one launch -- the per-stream state travels from window to window in device memory.
-static int retarget_group_windows(const gmr_job_t* jobs, int njobs, int flags, const Batch& b, int W) {
+static int retarget_group_windows(const gmr_job_t* jobs, int njobs, const double* const* weight, int flags, const Batch& b, int W) {
   gmr_solver* owner = b.owner;
   std::vector<gmr::IkJobOff> off((size_t)njobs);
+  std::vector<gmr::IkWeightOff> woff((size_t)njobs);
+  std::vector<const double*> dw((size_t)njobs, nullptr);      // the jobs' weights on the device
   gmr::Carve need;
   for (int j = 0; j < njobs; j++)
-    if (has_work(jobs[j])) off[j] = carve_job(need, jobs[j], (size_t)jobs[j].S);
+    if (has_work(jobs[j])) {
+      woff[j] = carve_weight(need, jobs[j], weight_of(weight, j), (size_t)jobs[j].S);
+      off[j] = carve_job(need, jobs[j], (size_t)jobs[j].S);
+    }
   for (int i = 0; i < 3; i++)
     if (!owner->pipe_stream[i]) GMR_HIP_TRY(hipStreamCreateWithFlags(&owner->pipe_stream[i], hipStreamNonBlocking));
   hipStream_t s_in = owner->pipe_stream[0], s_k = owner->pipe_stream[1], s_out = owner->pipe_stream[2];
@@ -445,7 +492,7 @@ static int retarget_group_windows(const gmr_job_t* jobs, int njobs, int flags, c
   const int wl = gmr::ik_window_frames(b.maxT, W);
   std::vector<gmr_job_t> dj(jobs, jobs + njobs);
   std::vector<hipEvent_t> ev;
-  gmr::IkCopy c[gmr::IK_NFIELD];
+  gmr::IkCopy c[gmr::IK_NFIELD], cw;
   int rc = GMR_OK;
   hipError_t e = hipSuccess;
   // an event recorded on `from` that `to` waits for
@@ -459,20 +506,23 @@ static int retarget_group_windows(const gmr_job_t* jobs, int njobs, int flags, c
   // the inputs or the outputs of every job that has frames at tb, in job order: the frames [tb, te), or (te = 0) the per-stream arrays
   auto move = [&](bool out, int tb, int te, hipStream_t st, const char* what) {
     for (int j = 0; j < njobs && rc == GMR_OK; j++)
-      if (has_work(jobs[j]) && tb < jobs[j].T)
+      if (has_work(jobs[j]) && tb < jobs[j].T) {
         rc = issue(c, te ? gmr::ik_window_copies(off[j], out, tb, te, c) : gmr::ik_slice_copies(off[j], out, 0, c, gmr::IK_PER_STREAM), jobs[j], d, st, what);
+        if (rc == GMR_OK && !out && te) rc = issue_weight(&cw, gmr::ik_weight_window_copy(woff[j], tb, te, &cw), weight_of(weight, j), d, st, what);
+      }
   };
   move(false, 0, 0, s_in, "H2D copy");                // q0, len, scale: once, before the first window
   for (int j = 0; j < njobs && rc == GMR_OK; j++) {
     if (!has_work(jobs[j])) continue;
     dj[j] = gmr::ik_job_at(jobs[j], d, off[j]);
+    dw[j] = gmr::ik_weight_at(d, woff[j]);
     rc = zero_outputs(jobs[j], d, off[j], s_k);
   }
   for (int tb = 0; tb < b.maxT && rc == GMR_OK; tb += wl) {
     const int te = std::min(tb + wl, b.maxT);
     move(false, tb, te, s_in, "H2D window copy");
     if (rc == GMR_OK && (e = order(s_in, s_k)) != hipSuccess) rc = fail(GMR_ERR_HIP, "window events: %s", hipGetErrorString(e));
-    if (rc == GMR_OK) rc = gmr_retarget_group_window_dev(dj.data(), njobs, flags, tb, te, s_k);
+    if (rc == GMR_OK) rc = gmr_retarget_group_weighted_window_dev(dj.data(), njobs, dw.data(), flags, tb, te, s_k);
     if (rc == GMR_OK && (e = order(s_k, s_out)) != hipSuccess) rc = fail(GMR_ERR_HIP, "window events: %s", hipGetErrorString(e));
     move(true, tb, te, s_out, "D2H window copy");
   }
@@ -490,14 +540,20 @@ static int retarget_group_windows(const gmr_job_t* jobs, int njobs, int flags, c
 // run those one after the other.  Pinned host memory (gmr_host_alloc / gmr_host_register) makes the copies truly
 // asynchronous; pageable memory works, staged by the runtime.
 int gmr_retarget_group(const gmr_job_t* jobs, int njobs, int flags, int slices) {
+  return gmr_retarget_group_weighted(jobs, njobs, nullptr, flags, slices);
+}
+
+// weight: null, or njobs entries, each null or the job's body weights [S][T][nhuman] in host memory: checked here, cut with the
+// slices and the windows like the human frames
+int gmr_retarget_group_weighted(const gmr_job_t* jobs, int njobs, const double* const* weight, int flags, int slices) {
   Batch b;
-  if (int rc = check_jobs(jobs, njobs, true, &b)) return rc;
+  if (int rc = check_jobs(jobs, njobs, weight, true, &b)) return rc;
   gmr_solver* owner = b.owner;
   if (!owner) return GMR_OK;
   const int n = gmr::ik_slice_count(slices, b.total, b.in_bytes);
   // (slices < 0: |slices| windows, the caller's choice)
   if (gmr::ik_cut_in_time(slices, n, b.maxT, b.in_bytes) && group_is_windowable(jobs, njobs, b) && !getenv("GMR_NO_WINDOWS"))
-    return retarget_group_windows(jobs, njobs, flags, b, slices < 0 ? -slices : (int)std::min<size_t>(8, b.in_bytes >> 26));
+    return retarget_group_windows(jobs, njobs, weight, flags, b, slices < 0 ? -slices : (int)std::min<size_t>(8, b.in_bytes >> 26));
   int rc = GMR_OK;
   hipError_t e = hipSuccess;
   const int nslot = std::min(n, (int)gmr_solver::kPipe);
@@ -506,7 +562,9 @@ int gmr_retarget_group(const gmr_job_t* jobs, int njobs, int flags, int slices) 
   std::vector<gmr_job_t> dj((size_t)njobs);
   std::vector<gmr::IkJobOff> off((size_t)njobs);
   std::vector<int> s0((size_t)njobs);
-  gmr::IkCopy c[gmr::IK_NFIELD];
+  std::vector<gmr::IkWeightOff> woff((size_t)njobs);
+  std::vector<const double*> dw((size_t)njobs, nullptr);
+  gmr::IkCopy c[gmr::IK_NFIELD], cw;
   for (int k = 0; k < n && rc == GMR_OK; k++) {
     const int slot = k % gmr_solver::kPipe;
     hipStream_t st = owner->pipe_stream[slot];
@@ -515,6 +573,7 @@ int gmr_retarget_group(const gmr_job_t* jobs, int njobs, int flags, int slices) 
     for (int j = 0; j < njobs; j++) {
       int S = 0;
       if (has_work(jobs[j])) gmr::ik_slice_range(jobs[j].S, k, n, &s0[j], &S);
+      woff[j] = carve_weight(need, jobs[j], weight_of(weight, j), (size_t)S);
       off[j] = carve_job(need, jobs[j], (size_t)S);
     }
     if (need.total() > owner->pipe_ws[slot].size()) GMR_HIP_TRY(hipStreamSynchronize(st));
@@ -524,12 +583,15 @@ int gmr_retarget_group(const gmr_job_t* jobs, int njobs, int flags, int slices) 
       gmr_job_t& D = dj[j];
       D = jobs[j];
       D.S = (int32_t)off[j].S;
+      dw[j] = nullptr;
       if (D.S == 0) continue;
       rc = issue(c, gmr::ik_slice_copies(off[j], false, (size_t)s0[j], c), jobs[j], d, st, "H2D copy");
+      if (rc == GMR_OK) rc = issue_weight(&cw, gmr::ik_weight_slice_copy(woff[j], (size_t)s0[j], &cw), weight_of(weight, j), d, st, "H2D copy");
+      dw[j] = gmr::ik_weight_at(d, woff[j]);
       if (rc == GMR_OK) rc = zero_outputs(jobs[j], d, off[j], st);
       D = gmr::ik_job_at(D, d, off[j]);
     }
-    if (rc == GMR_OK) rc = gmr_retarget_group_dev(dj.data(), njobs, flags, st);
+    if (rc == GMR_OK) rc = gmr_retarget_group_weighted_dev(dj.data(), njobs, dw.data(), flags, st);
     for (int j = 0; j < njobs && rc == GMR_OK; j++)
       if (off[j].S) rc = issue(c, gmr::ik_slice_copies(off[j], true, (size_t)s0[j], c), jobs[j], d, st, "D2H copy");
   }
@@ -549,12 +611,20 @@ int gmr_retarget_streams(gmr_solver_t* s, int S, int T, const double* q0, const 
 int gmr_retarget_streams_scaled(gmr_solver_t* s, int S, int T, const double* q0, const double* human, const int32_t* len,
                                 const double* scale, int flags, double* q_out, int32_t* nsolve, int32_t* status, double* tgt_out,
                                 double* err_out) {
+  return gmr_retarget_streams_weighted(s, S, T, q0, human, len, scale, nullptr, flags, q_out, nsolve, status, tgt_out, err_out);
+}
+
+// (the body weights lie in front of the job's arrays: with none the layout is the one it was, and [0, out_begin) is all input)
+int gmr_retarget_streams_weighted(gmr_solver_t* s, int S, int T, const double* q0, const double* human, const int32_t* len,
+                                  const double* scale, const double* weight, int flags, double* q_out, int32_t* nsolve, int32_t* status,
+                                  double* tgt_out, double* err_out) {
   const gmr_job_t job{s, S, T, q0, human, len, q_out, nsolve, status, tgt_out, err_out, scale};
-  if (int rc = check_job(job, true, -1)) return rc;
+  if (int rc = check_job(job, weight, true, -1)) return rc;
   if (!has_work(job)) return GMR_OK;
   gmr::Carve layout;
+  const gmr::IkWeightOff wo = carve_weight(layout, job, weight, (size_t)S);
   const gmr::IkJobOff o = carve_job(layout, job, (size_t)S);
-  if (o.S * o.stride(gmr::IK_HUMAN) >= ((size_t)32 << 20)) return gmr_retarget_group(&job, 1, flags, 0);
+  if (o.S * o.stride(gmr::IK_HUMAN) + wo.S * wo.stride() >= ((size_t)32 << 20)) return gmr_retarget_group_weighted(&job, 1, &weight, flags, 0);
   // grow-only workspace kept on the handle: a per-frame caller (retarget() once per frame) pays no
   // hipMalloc/hipFree per call.  Like the reference object, a handle is not re-entrant on this path.
   GMR_HIP_TRY(s->ws.reserve(o.end, 0, 1u << 20));
@@ -562,13 +632,17 @@ int gmr_retarget_streams_scaled(gmr_solver_t* s, int S, int T, const double* q0,
   const size_t ob = o.out_begin();
   const bool small = o.end <= gmr_solver::kPinBytes;
   if (small && !s->pin) GMR_HIP_TRY(hipHostMalloc((void**)&s->pin, gmr_solver::kPinBytes, hipHostMallocDefault));
-  gmr::IkCopy ci[gmr::IK_NFIELD], co[gmr::IK_NFIELD];
-  const int ni = gmr::ik_slice_copies(o, false, 0, ci), no = gmr::ik_slice_copies(o, true, 0, co);
+  gmr::IkCopy ci[gmr::IK_NFIELD], co[gmr::IK_NFIELD], cw;
+  const int ni = gmr::ik_slice_copies(o, false, 0, ci), no = gmr::ik_slice_copies(o, true, 0, co), nw = gmr::ik_weight_slice_copy(wo, 0, &cw);
   for (int i = 0; small && i < ni; i++) memcpy(s->pin + ci[i].dev, gmr::ik_ptr(job, ci[i].field) + ci[i].host, ci[i].width);
+  if (small && nw) memcpy(s->pin + cw.dev, reinterpret_cast<const char*>(weight) + cw.host, cw.width);
   if (small) GMR_NAMED_HIP_TRY("H2D copy", hipMemcpyAsync(d, s->pin, ob, hipMemcpyHostToDevice, nullptr));
-  else if (int rc = issue(ci, ni, job, d, nullptr, "H2D copy")) return rc;
+  else {
+    if (int rc = issue(ci, ni, job, d, nullptr, "H2D copy")) return rc;
+    if (int rc = issue_weight(&cw, nw, weight, d, nullptr, "H2D copy")) return rc;
+  }
   if (int rc = zero_outputs(job, d, o, nullptr)) return rc;
-  if (int rc = launch_job(gmr::ik_job_at(job, d, o), flags, nullptr)) return rc;
+  if (int rc = launch_job(gmr::ik_job_at(job, d, o), gmr::ik_weight_at(d, wo), flags, nullptr)) return rc;
   if (small) GMR_NAMED_HIP_TRY("kernel / D2H copy", hipMemcpyAsync(s->pin + ob, d + ob, o.end - ob, hipMemcpyDeviceToHost, nullptr));
   else if (int rc = issue(co, no, job, d, nullptr, "kernel / D2H copy")) return rc;
   GMR_NAMED_HIP_TRY("kernel / D2H copy", hipStreamSynchronize(nullptr));

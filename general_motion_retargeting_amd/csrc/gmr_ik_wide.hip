@@ -115,8 +115,10 @@ __device__ __forceinline__ void fk_wide(DimsRef D, double* sm, const char* __res
   PROF_END(pr, PH_FK);
 }
 
-// residuals of the stage's tasks and their unweighted norm (motion_retarget.py:188-200); lane = task
-__device__ __forceinline__ double errors_wide(double* sm, uint32_t taskw, int K, int lane, Prof& pr) {
+// residuals of the stage's tasks and their unweighted norm (motion_retarget.py:188-200); lane = task.  WGT (the instance with
+// body weights): keep is false in the lane of a task whose body is missing in this frame -- out of the norm
+template <bool WGT = false>
+__device__ __forceinline__ double errors_wide(double* sm, uint32_t taskw, int K, int lane, Prof& pr, bool keep = true) {
   PROF_BEGIN(pr);
   lane = fresh_lane(lane);     // (lane predicates of this phase are computed here and die with it: gmr_device_math.h)
   double ss = 0.0;
@@ -129,7 +131,7 @@ __device__ __forceinline__ double errors_wide(double* sm, uint32_t taskw, int K,
                  d4{tg[3], tg[4], tg[5], tg[6]}, e, aux);
     double* eo = sm + LD.e + 6 * lane;
 #pragma unroll
-    for (int r = 0; r < 6; r++) { eo[r] = e[r]; ss += e[r] * e[r]; }
+    for (int r = 0; r < 6; r++) { eo[r] = e[r]; if (!WGT || keep) ss += e[r] * e[r]; }
     double* ao = sm + LD.eaux + 5 * lane;       // a, sin|w|, cos|w|, |w|, 1/|w|: reused by the Jl^-1 phase
 #pragma unroll
     for (int r = 0; r < 5; r++) ao[r] = aux[r];
@@ -144,15 +146,18 @@ __device__ __forceinline__ double errors_wide(double* sm, uint32_t taskw, int K,
 // form); returns the LM term mu.  (Round 2 measured this form here as "the same frames/s, 13 more registers, 8 of them in
 // scratch"; since the lane predicates are no longer parked -- 229 registers -- it fits, and the phase issues a third of the
 // instructions: 14 of 64 lanes were doing all of it.  GMR_WIDE_JLOG_ROWS restores the one-lane-per-task form.)
+// WGT (the instance with body weights): the frame's weights are the image's times mk, the multiplier of the task's human body
+// in the task's lane -- one IEEE product each, staged into `wts` where every later reader finds them.
+template <bool WGT = false>
 __device__ __forceinline__ double jlog_wide(double* sm, const char* __restrict__ img, int stage, int K, double lm_damping,
-                                            int lane, Prof& pr) {
+                                            int lane, Prof& pr, double mk = 1.0) {
   PROF_BEGIN(pr);
   lane = fresh_lane(lane);     // (lane predicates of this phase are computed here and die with it: gmr_device_math.h)
   double mu = 0.0;
 #ifdef GMR_WIDE_JLOG_ROWS
   if (lane < K) {
     const double* w = img_at<double>(img, IM.task[stage]) + 2 * lane;
-    const double wp = w[0], wr = w[1];
+    const double wp = WGT ? w[0] * mk : w[0], wr = WGT ? w[1] * mk : w[1];
     const double* e = sm + LD.e + 6 * lane;
     double ee[6];
 #pragma unroll
@@ -188,7 +193,7 @@ __device__ __forceinline__ double jlog_wide(double* sm, const char* __restrict__
     for (int i = 0; i < 3; i++) { M[3 * i] = -Ac[i]; M[9 + 3 * i] = -Bc[i]; }
     if (j == 0) {
       const double* w = img_at<double>(img, IM.task[stage]) + 2 * k;
-      const double wp = w[0], wr = w[1];
+      const double wp = WGT ? w[0] * mk : w[0], wr = WGT ? w[1] * mk : w[1];      // (j == 0: lane = k, the task's own lane)
       double* wt = sm + LD.wts + 2 * k;
       wt[0] = wp; wt[1] = wr;
 #pragma unroll
@@ -737,10 +742,13 @@ __device__ __forceinline__ void integrate_wide(DimsRef D, double* sm, double dt,
 }
 
 // target preprocessing (motion_retarget.py:203-270); lane = human body.  `scl`: the stream's own scale row (nhum doubles
-// in device memory, read per frame: two loads that the L2 serves), or null = the image's table
-template <class DimsRef>
+// in device memory, read per frame: two loads that the L2 serves), or null = the image's table.  WGT (the instance with body
+// weights) and `missing`: this lane's body has multiplier 0 in this frame and is not the human root -- whatever its raw row
+// holds stays in this lane: out of the lowest-foot search, the identity pose as its target, which no result depends on
+template <class DimsRef, bool WGT = false>
 __device__ __forceinline__ void preprocess_wide(DimsRef D, double* sm, const char* __restrict__ img, const double* __restrict__ scl,
-                                                int human_root, double ground_offset, int flags, int lane, Prof& pr) {
+                                                int human_root, double ground_offset, int flags, int lane, Prof& pr,
+                                                bool missing = false) {
   PROF_BEGIN(pr);
   lane = fresh_lane(lane);     // (lane predicates of this phase are computed here and die with it: gmr_device_math.h)
   const double* raw = sm + LD.raw;
@@ -763,12 +771,13 @@ __device__ __forceinline__ void preprocess_wide(DimsRef D, double* sm, const cha
     d4 q = qnormalize(d4{in[3], in[4], in[5], in[6]});
     uq = qnormalize(qmul(q, qnormalize(d4{cst[4], cst[5], cst[6], cst[7]})));
     p = p + qrot(uq, d3{cst[1], cst[2], cst[3]});
-    if (img_at<uint32_t>(img, IM.prei)[lane] && p.x == p.x) z = p.z;
+    if (img_at<uint32_t>(img, IM.prei)[lane] && p.x == p.x && (!WGT || !missing)) z = p.z;
   }
   if (flags & GMR_FLAG_OFFSET_TO_GROUND) {
     double lowest = row0_min(z);
     p.z = p.z - lowest + ground_offset;
   }
+  if (WGT && missing) { p = d3{0, 0, 0}; uq = d4{1, 0, 0, 0}; }
   if (on) {
     double* o = tgt + 7 * lane;
     o[0] = p.x; o[1] = p.y; o[2] = p.z; o[3] = uq.w; o[4] = uq.x; o[5] = uq.y; o[6] = uq.z;
@@ -822,6 +831,7 @@ struct WideJob {
   const double* scale;           // [S][nhum] per-stream human scale tables, or null = the image's table
   WideDims D;
   int max_iter, human_root, use0, use1, S, T, first;
+  const double* weight;          // [S][T][nhum] per-frame body weights, or null (LAST: the fields above keep their offsets)
 };
 static_assert(sizeof(WideJob) <= 256 && sizeof(WideJob) % 4 == 0, "a job is read as one dword per lane");
 constexpr int WD_MAX_JOBS = 8;
@@ -894,6 +904,12 @@ __device__ __forceinline__ bool queue_pop(const WideQueue& Q, const unsigned nch
   return true;
 }
 
+// the multiplier of the task in this lane (taskw: its word of the task table) from the frame's row, 1 without a row
+__device__ __forceinline__ double task_mult(const double* __restrict__ wrow, uint32_t taskw, int K, int lane) {
+  return wrow && lane < K ? wrow[taskw >> 8] : 1.0;
+}
+
+#define GMR_WGT 0
 #define GMR_FWIN false
 #define GMR_WIDE_KERNEL ik_wide_kernel
 #define GMR_WIDE_GROUP_KERNEL ik_wide_group_kernel
@@ -907,6 +923,16 @@ __device__ __forceinline__ bool queue_pop(const WideQueue& Q, const unsigned nch
 #include "gmr_ik_wide_kernels.inc"
 #undef GMR_WIDE_GROUP_KERNEL
 #undef GMR_WIDE_KERNEL
+#undef GMR_WGT
+// per-frame body weights (gmr_retarget_streams_weighted): the group kernel alone -- like scale rows the array is a field of the
+// job table --, and with the frame window, whose +inf table leaves the bits of a solver without one alone
+#define GMR_WGT 1
+#define GMR_WEIGHT weight
+#define GMR_WIDE_GROUP_KERNEL ik_wide_group_w_kernel
+#include "gmr_ik_wide_kernels.inc"
+#undef GMR_WIDE_GROUP_KERNEL
+#undef GMR_WEIGHT
+#undef GMR_WGT
 #undef GMR_FWIN
 
 }  // namespace wide
@@ -992,7 +1018,7 @@ extern "C" hipError_t gmr_launch_ik_wide_window(const gmr_wide_job_desc* jd, int
   memset(&tab, 0, sizeof tab);
   long long total = 0, nring = 0;
   int chunk = 0, maxT = 0, n = 0;
-  bool chunk_auto = false, scaled = false, fwin = false;
+  bool chunk_auto = false, scaled = false, fwin = false, weighted = false;
   if (p) { std::lock_guard<std::mutex> g(p->mu); chunk = p->chunk; chunk_auto = p->chunk_auto; }
   for (int j = 0; j < njobs; j++) {
     if (jd[j].S <= 0 || jd[j].T <= 0) continue;
@@ -1003,6 +1029,8 @@ extern "C" hipError_t gmr_launch_ik_wide_window(const gmr_wide_job_desc* jd, int
     J.max_iter = jd[j].P->max_iter; J.human_root = jd[j].P->human_root; J.use0 = jd[j].P->use0; J.use1 = jd[j].P->use1;
     J.scale = jd[j].d_scale;
     scaled = scaled || J.scale;
+    J.weight = jd[j].d_weight;
+    weighted = weighted || J.weight;   // one job with body weights: the instance that applies them (a job without is not changed by it: its multipliers are 1)
     fwin = fwin || jd[j].fwin;      // one job with a frame window: the instances that apply it (a job without one is not changed by them: its window is +inf)
     J.S = jd[j].S; J.T = jd[j].T; J.first = (int)total;
     total += jd[j].S;
@@ -1013,7 +1041,7 @@ extern "C" hipError_t gmr_launch_ik_wide_window(const gmr_wide_job_desc* jd, int
   tab.njobs = n; tab.total = (int)total;
   const bool windowed = t_end > 0;
   if (windowed && (t_begin < 0 || t_begin >= t_end)) return hipErrorInvalidValue;
-  const bool multi = n > 1 || windowed || scaled;    // (windows and scale rows are features of the group instance)
+  const bool multi = n > 1 || windowed || scaled || weighted;    // (windows, scale rows and body weights are features of the group instance)
   const int span = windowed ? std::min(maxT, t_end) - t_begin : maxT;      // frames per stream in this launch, at most
   // the ring has one entry per chunk: very long jobs get longer chunks rather than a ring beyond 64 MB (more than 2^24
   // streams cannot be helped by longer chunks: the loop ends at chunk >= T and the launch below is a direct one)
@@ -1083,7 +1111,7 @@ extern "C" hipError_t gmr_launch_ik_wide_window(const gmr_wide_job_desc* jd, int
     if (e != hipSuccess) return e;
   }
   if (multi) {
-    hipLaunchKernelGGL(fwin ? ik_wide_group_fw_kernel : ik_wide_group_kernel, dim3(grid), dim3(64), wide_lds_launch_bytes(), stream, d_jobs, n,
+    hipLaunchKernelGGL(weighted ? ik_wide_group_w_kernel : fwin ? ik_wide_group_fw_kernel : ik_wide_group_kernel, dim3(grid), dim3(64), wide_lds_launch_bytes(), stream, d_jobs, n,
                        (int)total, flags, Q);
   } else {
     const WideJob& J = tab.job[0];
@@ -1098,10 +1126,10 @@ extern "C" hipError_t gmr_launch_ik_wide(const char* d_image, const gmr::WideLay
                                          const double* d_q0, const double* d_human, const int32_t* d_len,
                                          const double* d_scale, int flags, double* d_q_out, int32_t* d_nsolve, int32_t* d_status,
                                          double* d_tgt_out, double* d_err_out, hipStream_t stream, unsigned long long* d_prof,
-                                         void* pool, int fwin) {
+                                         void* pool, int fwin, const double* d_weight) {
   if (S <= 0 || T <= 0) return hipSuccess;
-  if (d_scale && d_prof) return hipErrorInvalidValue;        // (the phase counters are the plain instance's)
-  const gmr_wide_job_desc jd{d_image, L, P, S, T, d_q0, d_human, d_len, d_q_out, d_nsolve, d_status, d_tgt_out, d_err_out, d_scale, fwin};
+  if ((d_scale || d_weight) && d_prof) return hipErrorInvalidValue;        // (the phase counters are the plain instance's)
+  const gmr_wide_job_desc jd{d_image, L, P, S, T, d_q0, d_human, d_len, d_q_out, d_nsolve, d_status, d_tgt_out, d_err_out, d_scale, fwin, d_weight};
   return gmr_launch_ik_wide_group(&jd, 1, flags, stream, d_prof, pool);
 }
 

@@ -10,7 +10,12 @@
 // macros GMR_T_END (frames at or beyond it are left to a later launch: T in the plain kernel), GMR_WINDOWED (the launch is one
 // window of a stream's frames: its state is kept in Q.state for the next window; false in the plain kernel) and GMR_SCALE (the
 // job's per-stream human scale tables, f64 [S][nhum], or null = the image's table; a literal null in the plain kernel); and
-// GMR_FWIN, a literal: the instance applies the frame window (gmr_ik_wide_kernels.inc).
+// GMR_FWIN, a literal: the instance applies the frame window (gmr_ik_wide_kernels.inc); and GMR_WGT, 0 or 1: the instance
+// applies GMR_WEIGHT, the job's per-frame body weights (f64 [S][T][nhum], or null = every multiplier is 1; only
+// ik_wide_group_w_kernel).  What the weights add stands behind #if GMR_WGT, so that the other instances compile the text they
+// compiled without the feature.  The frame's row is indexed by t in the stream and read where it is used -- by the body lanes before
+// the preprocessing, by the task lanes once per stage (L1 hits: the same 128 bytes) --, so queue items and later windows carry no
+// state for it and no LDS holds it.
   // state that must start defined: the violation sets of the QP (double-buffered, cleared round by round)
   if (lane < 8) reinterpret_cast<unsigned long long*>(sm + LD.vset)[lane] = 0ull;
   {
@@ -27,6 +32,9 @@
   const int t1 = queued ? min(t0 + Q.chunk, Tw) : Tw;
   const double* hs = human + (size_t)s * T * fstride;
   const double* scl = GMR_SCALE ? GMR_SCALE + (size_t)s * D.nhum : nullptr;
+#if GMR_WGT
+  const double* wstream = GMR_WEIGHT ? GMR_WEIGHT + (size_t)s * T * D.nhum : nullptr;
+#endif
   double r0 = 0.0, r1 = 0.0;
   if (t0 < t1) {
     const double* nx = hs + (size_t)t0 * fstride;
@@ -50,10 +58,26 @@
     const double th0 = (GMR_FWIN && lane >= 6 && lane < D.nv) ? (sm + LD.q)[7 + lane - 6] : 0.0;
     int ns0 = 0, ns1 = 0;
     const size_t f = (size_t)s * T + t;
+#if GMR_WGT
+    const double* wrow = wstream ? wstream + (size_t)t * D.nhum : nullptr;      // this frame's multipliers, by human body
+#endif
     if (stat == GMR_STATUS_OK) {
+#if GMR_WGT
+      // a body whose multiplier is 0 is missing in this frame (the human root's row is always read: every body moves with it)
+      const bool missing = wrow && lane < D.nhum && lane != human_root && wrow[lane] == 0.0;
+      preprocess_wide<GMR_DIMS_T, true>(D, sm, img, scl, human_root, prm[4], flags, lane, pr, missing);
+      if (tgt_out) {   // the poses handed to task.set_target (motion_retarget.py:117-136) = scaled_human_data
+        if (!wrow) {
+          for (int i = lane; i < (int)fstride; i += 64) tgt_out[f * fstride + i] = (sm + LD.tgt)[i];
+        } else if (lane < D.nhum) {      // a body lane stores its own row: seven NaNs for a missing body, as for an absent one
+          for (int r = 0; r < 7; r++) tgt_out[f * fstride + 7 * lane + r] = missing ? (double)NAN : (sm + LD.tgt)[7 * lane + r];
+        }
+      }
+#else
       preprocess_wide<GMR_DIMS_T>(D, sm, img, scl, human_root, prm[4], flags, lane, pr);
       if (tgt_out)     // the poses handed to task.set_target (motion_retarget.py:117-136) = scaled_human_data
         for (int i = lane; i < (int)fstride; i += 64) tgt_out[f * fstride + i] = (sm + LD.tgt)[i];
+#endif
       double last_E = -1.0;                          // the stage's last residual norm (at the current configuration)
       for (int stage = 0; stage < 2; stage++) {
         if (!(stage == 0 ? use0 : use1) || (flags & GMR_FLAG_EVAL_ONLY)) continue;
@@ -61,10 +85,20 @@
         const uint32_t taskw = lane < K ? img_at<uint32_t>(img, IM.taski[stage])[lane] : 0u;
         // (same task list in both tables -- bit 1 of use1, gmr_ik_layout.h: the first stage's last evaluation is this
         //  stage's first, and its residuals and log-map terms are still in LDS for the Jl^-1 phase)
+#if GMR_WGT
+        const double mk = task_mult(wrow, taskw, K, lane);      // the multiplier of this lane's task (1 for a job without weights)
+        const bool keep = mk != 0.0;
+        double curr = (stage == 1 && (use1 & 2) && last_E >= 0.0) ? last_E : errors_wide<true>(sm, taskw, K, lane, pr, keep);
+#else
         double curr = (stage == 1 && (use1 & 2) && last_E >= 0.0) ? last_E : errors_wide(sm, taskw, K, lane, pr);
+#endif
         int nsol = 0, num_iter = 0;
         for (;;) {
+#if GMR_WGT
+          const double mu = jlog_wide<true>(sm, img, stage, K, prm[1], lane, pr, mk);
+#else
           const double mu = jlog_wide(sm, img, stage, K, prm[1], lane, pr);
+#endif
           const double diag = prm[0] + mu;
           PROF_BEGIN(pr);
           pairs_wide(sm, img, stage, D.P[stage], lane);
@@ -83,7 +117,11 @@
           if (rc != GMR_STATUS_OK) { stat = rc; break; }
           integrate_wide<GMR_DIMS_T>(D, sm, prm[5], lane, pr);
           fk_wide<GMR_DIMS_T>(D, sm, img, lane, pr);
+#if GMR_WGT
+          const double next = errors_wide<true>(sm, taskw, K, lane, pr, keep);
+#else
           const double next = errors_wide(sm, taskw, K, lane, pr);
+#endif
           last_E = next;
           nsol++;
           if (nsol > 1) num_iter++;
@@ -100,7 +138,12 @@
         double E = 0.0;
         if (stage == 0 ? use0 : use1) {
           const int K = D.K[stage];
+#if GMR_WGT
+          const uint32_t taskw = lane < K ? img_at<uint32_t>(img, IM.taski[stage])[lane] : 0u;
+          E = errors_wide<true>(sm, taskw, K, lane, pr, task_mult(wrow, taskw, K, lane) != 0.0);
+#else
           E = errors_wide(sm, lane < K ? img_at<uint32_t>(img, IM.taski[stage])[lane] : 0u, K, lane, pr);
+#endif
         }
         if (lane == 0) err_out[2 * f + stage] = E;
       }

@@ -1,10 +1,13 @@
-// gmr_ik_wide_kernels.inc -- the two kernels of the throughput shape, included TWICE by gmr_ik_wide.hip: once as ik_wide_kernel /
-// ik_wide_group_kernel with GMR_FWIN false, the kernels of launches none of whose solvers has a finite frame window
-// (gmr_solver_set_frame_velocity_limits), and once as ik_wide_fw_kernel / ik_wide_group_fw_kernel with GMR_FWIN true, which
-// clamp the QP box into the frame window.  Two instances, not a test in one: with the window behind a wave-uniform test in the
-// only instance, the register pair of theta0 and 9 more spilled SGPRs cost the 1M-frame batch 0.85 % with no limit set, the
-// same sign in five alternated runs out of five (DESIGN.md 6zd); with GMR_FWIN false the window folds away and the instance
-// is the code it was without the feature.  Textual, like gmr_ik_wide_item.inc and for its reason.
+// gmr_ik_wide_kernels.inc -- the two kernels of the throughput shape, included THREE times by gmr_ik_wide.hip:
+//   1. as ik_wide_kernel / ik_wide_group_kernel with GMR_FWIN false and GMR_WGT 0: the kernels of launches none of whose solvers
+//      has a finite frame window (gmr_solver_set_frame_velocity_limits) and none of whose jobs carries body weights;
+//   2. as ik_wide_fw_kernel / ik_wide_group_fw_kernel with GMR_FWIN true and GMR_WGT 0, which clamp the QP box into the frame window;
+//   3. as ik_wide_group_w_kernel with GMR_FWIN true and GMR_WGT 1, the group kernel alone (GMR_WIDE_KERNEL is not defined, so the
+//      plain kernel is left out): per-frame body weights from the job table (gmr_retarget_streams_weighted).
+// Instances, not a test in one kernel: with the window behind a wave-uniform test in the only instance, the register pair of
+// theta0 and 9 more spilled SGPRs cost the 1M-frame batch 0.85 % with no limit set, the same sign in five alternated runs out of
+// five (DESIGN.md 6zd); with GMR_FWIN false and GMR_WGT 0 both features fold away and the instance is the code it was without
+// them.  Textual, like gmr_ik_wide_item.inc and for its reason.
 // Plain launch: ONE job without per-stream scale tables, its fields are individual kernel arguments.  That matters: with ~100 SGPRs for ~350
 // wave-uniform values the compiler re-loads a kernel ARGUMENT where it is used (s_load from the kernarg segment: no VALU
 // slot), while a value it cannot re-load is parked in a VGPR lane and comes back through v_readlane.  Passing the job as
@@ -12,6 +15,7 @@
 // v_readlane instructions in the code object and -4 % frames/s.  For the same reason this instance has no scale
 // argument: GMR_SCALE is a literal null here and the branch in preprocess_wide folds away; a job that carries scale
 // rows runs the group instance, alone if need be.
+#ifdef GMR_WIDE_KERNEL
 __global__ __launch_bounds__(64, GMR_WIDE_MIN_WAVES) void GMR_WIDE_KERNEL(
     const char* __restrict__ img, WideDims D, int max_iter, int human_root, int use0, int use1, int S, int T,
     const double* __restrict__ q0, const double* __restrict__ human, const int32_t* __restrict__ len, int flags,
@@ -72,6 +76,7 @@ __global__ __launch_bounds__(64, GMR_WIDE_MIN_WAVES) void GMR_WIDE_KERNEL(
   (void)prof_out;
 #endif
 }
+#endif  // GMR_WIDE_KERNEL
 
 // Group launch: the job of an item comes from the table in device memory, by scalar loads through a constant-memory
 // pointer (wave-uniform, like kernel arguments, but not re-loadable for free: this instance keeps a few more values in
@@ -113,6 +118,9 @@ __global__ __launch_bounds__(64, GMR_WIDE_MIN_WAVES) void GMR_WIDE_GROUP_KERNEL(
   double* __restrict__ tgt_out = cj->tgt_out;
   double* __restrict__ err_out = cj->err_out;
   const double* __restrict__ scale = cj->scale;
+#if GMR_WGT
+  const double* __restrict__ weight = cj->weight;
+#endif
   const int s = gs - cj->first;
   const int nq = D.nq, nhum = D.nhum;
   const double* prm = img_at<double>(img, IM.prm);

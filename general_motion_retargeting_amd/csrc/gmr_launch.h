@@ -21,6 +21,7 @@ struct gmr_wide_job_desc {
   double* d_q_out; int32_t* d_nsolve; int32_t* d_status; double* d_tgt_out; double* d_err_out;
   const double* d_scale;         // [S][nhum] or null
   int fwin;                      // the image's frame windows are not all +inf
+  const double* d_weight;        // [S][T][nhum] per-frame body weights, or null
 };
 
 extern "C" {
@@ -28,13 +29,14 @@ extern "C" {
 hipError_t gmr_launch_ik_streams(const uint4* d_image, const gmr::IkLayout* L, const gmr::IkParams* P, int S, int T, const double* d_q0,
                                  const double* d_human, const int32_t* d_len, const double* d_scale, int flags, double* d_q_out,
                                  int32_t* d_nsolve, int32_t* d_status, double* d_tgt_out, double* d_err_out, hipStream_t stream,
-                                 unsigned long long* d_prof, int vlim);    // vlim: the image's velocity bounds are not all +inf
+                                 unsigned long long* d_prof, int vlim,     // vlim: the image's velocity bounds are not all +inf
+                                 const double* d_weight);                  // [S][T][nhum] per-frame body weights, or null
 hipError_t gmr_ik_set_max_smem(int nvp, int nw, int tree_small, int bytes);
 // gmr_ik_wide.hip
 hipError_t gmr_launch_ik_wide(const char* d_image, const gmr::WideLayout* L, const gmr::IkParams* P, int S, int T, const double* d_q0,
                               const double* d_human, const int32_t* d_len, const double* d_scale, int flags, double* d_q_out,
                               int32_t* d_nsolve, int32_t* d_status, double* d_tgt_out, double* d_err_out, hipStream_t stream,
-                              unsigned long long* d_prof, void* pool, int fwin);    // fwin: as in gmr_wide_job_desc
+                              unsigned long long* d_prof, void* pool, int fwin, const double* d_weight);    // fwin, d_weight: as in gmr_wide_job_desc
 hipError_t gmr_launch_ik_wide_group(const gmr_wide_job_desc* jd, int njobs, int flags, hipStream_t stream, unsigned long long* d_prof,
                                     void* pool);
 hipError_t gmr_launch_ik_wide_window(const gmr_wide_job_desc* jd, int njobs, int flags, hipStream_t stream, unsigned long long* d_prof,

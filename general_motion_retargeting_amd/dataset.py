@@ -304,7 +304,8 @@ class DevicePost:
         post-processing reads the stitched clip-major output unchanged.
         ``jobs`` = ``[{"solver", "human": f64[S,T,nhuman,7] (page-locked for an asynchronous copy), "lens": i32[S],
         "q0": f64[nq], optional "scales": f64[S,nhuman] (a human scale table per clip in place of the solver's; not with a
-        chunk spec that takes effect: the slots of a chunk job are not streams)}]``, all for the robot of ``km``.  A job of raw BVH clips carries, instead of ``"human"``, ``"T"`` and
+        chunk spec that takes effect: the slots of a chunk job are not streams), optional "weights": f64[S,T,nhuman] (per-frame
+        body weights, 0 = the body is missing in that frame; not with a chunk spec that takes effect either)}]``, all for the robot of ``km``.  A job of raw BVH clips carries, instead of ``"human"``, ``"T"`` and
         ``"bvh"`` = ``[{"handle": _lib.BvhHandle, "rows": f64[B,ncol] (page-locked), "offsets": f64[n,J,3], "clips": [index in
         lens, ...], "lens": [...]}]`` (one entry per topology) and optionally ``"packed"`` = ``[(index, f64[n,nhuman,7])]``: the
         raw rows are uploaded ragged and ``gmr_bvh_frames_dev`` writes ``human`` on the device, on the same stream, in front
@@ -324,7 +325,7 @@ class DevicePost:
         base = d_out.ptr.value
         sx_human, sx_copies, sx_calls = self._stage_smplx(jobs)
         ev[0].record(st)
-        launch, bvh_calls, clip = [], [], 0
+        launch, bvh_calls, clip, d_weights = [], [], 0, []
         for i, j in enumerate(jobs):
             if "bvh" in j:
                 d_h, copies, calls = self._stage_bvh(i, j, block.dlens[i])
@@ -332,10 +333,11 @@ class DevicePost:
                 d_h, copies, calls = sx_human[i], [], []          # (frames at or beyond a clip's nout stay stale: never read)
             else:
                 d_h, copies, calls = self._stage_packed(i, j)
-            job, more = self._stage_job(i, j, d_h, block, block.at(base, "status", clip))
+            job, more, d_w = self._stage_job(i, j, d_h, block, block.at(base, "status", clip))
             for dst, src in copies + more:
                 self._h2d(dst, src)
             launch.append(job)
+            d_weights.append(d_w)
             bvh_calls += calls
             clip += job.S
         for dst, src in sx_copies:
@@ -344,7 +346,7 @@ class DevicePost:
         for call in bvh_calls + sx_calls:
             call(st)
         ev[5].record(st)
-        self.chunk_reports = self._ik(launch, block, chunk, ik_flags)
+        self.chunk_reports = self._ik(launch, block, chunk, ik_flags, d_weights)
         ev[2].record(st)
         self._post(block, base, launch, fk, height_adjust, root_origin_offset, ground_offset)
         ev[3].record(st)
@@ -406,7 +408,7 @@ class DevicePost:
 
     def _stage_job(self, i: int, j: Dict, d_h, block: BlockPlan, d_status):
         """what every kind of job needs besides its frames: start poses, clip lengths (device order), the IK outputs and the
-        scale rows it may carry.  Returns ``(DevJob, H2D copies)``."""
+        scale rows and body weights it may carry.  Returns ``(DevJob, H2D copies, the weights on the device or None)``."""
         sol, dlens = j["solver"], block.dlens[i]
         S, T = j["human"].shape[:2] if "human" in j else (len(dlens), max(int(j["T"]), 1))
         q0 = self.pinned(f"q0_{i}", (S, sol.nq), np.float64)
@@ -422,15 +424,26 @@ class DevicePost:
             sc[:] = rows if block.perms[i] is None else rows[block.perms[i]]
             d_sc = self._d(f"scale_{i}", sc.nbytes)
             copies.append((d_sc.ptr, sc))
-        return _lib.DevJob(sol, S, T, d_q0, d_h, d_len, d_q, d_ns, d_status, d_sc), copies + [(d_q0.ptr, q0), (d_len.ptr, lens)]
+        d_w = None
+        if j.get("weights") is not None:
+            rows = _lib.check_weights(j["weights"], S, T, sol.nhuman, f"job {i}: weights", j["lens"])
+            w = self.pinned(f"weight_{i}", (S, T, sol.nhuman), np.float64)
+            w[:] = rows if block.perms[i] is None else rows[block.perms[i]]
+            d_w = self._d(f"weight_{i}", w.nbytes)
+            copies.append((d_w.ptr, w))
+        return _lib.DevJob(sol, S, T, d_q0, d_h, d_len, d_q, d_ns, d_status, d_sc), copies + [(d_q0.ptr, q0), (d_len.ptr, lens)], d_w
 
-    def _ik(self, launch: List, block: BlockPlan, chunk, ik_flags: int) -> List:
-        """the IK launch of all jobs, chunked where the spec takes effect; returns the chunk reports per job, in job order"""
+    def _ik(self, launch: List, block: BlockPlan, chunk, ik_flags: int, d_weights: Optional[List] = None) -> List:
+        """the IK launch of all jobs (``d_weights``: per job its body weights on the device, or None), chunked where the spec
+        takes effect; returns the chunk reports per job, in job order"""
         total_frames = int(sum(int(l.sum()) for l in block.dlens))
         specs = [chunking.resolve_any(chunk, l, total_frames) for l in block.dlens]
+        weighted = d_weights is not None and any(w is not None for w in d_weights)
         if all(sp is None for sp in specs):
-            _lib.retarget_group_dev(launch, ik_flags, self._stream)
+            _lib.retarget_group_dev(launch, ik_flags, self._stream, weights=d_weights if weighted else None)
             return [None] * len(launch)
+        if weighted:
+            raise ValueError(chunking.BODY_WEIGHTS_REFUSAL)
         if any(job.scale is not None for job in launch):
             raise ValueError("per-clip scales do not go with a chunk spec that takes effect: run the heights as groups")
         if self._chunker is None:
@@ -515,6 +528,8 @@ def _run_batch(jobs: Sequence[Dict], km: KinematicsModel, ik_flags: int, height_
     for n, (j, sp) in enumerate(zip(jobs, specs)):
         if sp is not None:
             assert j.get("scales") is None          # (the slots of a chunk job are not streams)
+            if j.get("weights") is not None:
+                raise ValueError(chunking.BODY_WEIGHTS_REFUSAL)
             *results[n], reports[n] = chunking.retarget_chunked_host(j["solver"], j["human"], j["q0"], j["lens"], ik_flags, sp)
     t1 = time.perf_counter()
     qpos: List[Optional[np.ndarray]] = [None] * len(out)
@@ -615,6 +630,7 @@ class ClipRetargeter:
         self._human = None                                # the padded batch: locked when the first packed clip arrives
         self._lens = np.zeros(self._cap, dtype=np.int32)
         self._hts = np.full(self._cap, np.nan)            # per-clip heights (NaN = none: the unscaled table)
+        self._wts = None                                  # per-frame body weights of the batch: locked when the first clip that has some arrives
         self._n = 0
         # a batch of raw BVH clips (device path): per topology the rows of its clips, concatenated in page-locked memory
         self._raw_mode = self._seen_raw
@@ -653,10 +669,12 @@ class ClipRetargeter:
         self._raw_mode = self._seen_raw = True
         return True
 
-    def add(self, clip, height: Optional[float] = None) -> bool:
+    def add(self, clip, height: Optional[float] = None, body_weights=None) -> bool:
         """Copy one clip into the batch; False when it does not fit (batch full, or the clip is longer than the batch's
         rows): the caller finishes this batch and begins another.  ``height``: this clip's ``actual_human_height`` (only a
-        retargeter built with per-clip heights takes one).  A raw BVH clip (``lafan1.BvhRaw``) joins a batch whose
+        retargeter built with per-clip heights takes one).  ``body_weights`` (``[T_i, nhuman]`` or one dict ``{body: m}`` per
+        frame): this clip's per-frame body weights, packed into the batch beside its frames (clips without: ones); 0 = the body
+        is missing in that frame.  Not for raw BVH clips (the device-side reader produces no dropouts) and not with ``chunk``.  A raw BVH clip (``lafan1.BvhRaw``) joins a batch whose
         frames are computed on the device (:func:`bvh_path`): only its rows are copied.  On the host path, for a file the
         device path does not take, or in a batch that already holds packed clips, its frames are computed here."""
         from .utils import lafan1
@@ -666,15 +684,27 @@ class ClipRetargeter:
                 raise ValueError("this retargeter was built for one height: build it with a sequence of heights")
             if self._n < self._cap:
                 self._hts[self._n] = height               # (kept only if the clip is: a refused clip leaves _n where it is)
+        w = None
+        if body_weights is not None:
+            if self.chunk is not None:
+                raise ValueError(chunking.BODY_WEIGHTS_REFUSAL)
+            if isinstance(clip, lafan1.BvhRaw) or self._raw_mode:
+                raise ValueError("body weights go with packed clips, not with raw BVH clips")
+            w = self.gmr.clip_body_weights(body_weights, len(clip))
         if isinstance(clip, lafan1.BvhRaw):
             if self._bvh_device and lafan1.device_takes(clip) and (self._raw_mode or self._n == 0):
                 ok = self._add_raw(clip)
                 self.timing["pack"] = self.timing.get("pack", 0.0) + time.perf_counter() - t0
                 return ok
             clip = lafan1.packed_from_raw(clip, self.gmr.human_body_names)
-        p = clip if isinstance(clip, np.ndarray) else self.gmr.pack_frames(clip)
+        p = clip if isinstance(clip, np.ndarray) else self.gmr.pack_frames(clip, w)
         if self._n >= self._cap or p.shape[0] > self._T:
             return False
+        if w is not None:
+            if self._wts is None:
+                self._wts = self._buf("weights", (self._cap, self._T, self.gmr.hip_solver.nhuman), np.float64)
+                self._wts[:] = 1.0
+            self._wts[self._n, : w.shape[0]] = w
         if self._raw_mode and self._bvh_device:
             self._packed.append((self._n, np.asarray(p, dtype=np.float64)))      # uploaded into its padded rows by DevicePost
         else:
@@ -726,6 +756,8 @@ class ClipRetargeter:
                              "lens": g["lens"]} for g in self._raw.values()])
         else:
             job["human"] = self._human[:S]
+        if self._wts is not None:
+            job["weights"] = self._wts[:S]
         outs = None
         if post is None:        # the start poses and the outputs of the plain launch stay in this object's page-locked memory
             job["q0"] = self._buf("q0", (S, sol.nq), np.float64)
@@ -738,16 +770,23 @@ class ClipRetargeter:
             chunking.summarize(self.chunk_report, self.chunk_summary)
         return out
 
-    def __call__(self, clips: Sequence, fps: Sequence[float]) -> List[Dict]:
+    def __call__(self, clips: Sequence, fps: Sequence[float], body_weights: Optional[Sequence] = None) -> List[Dict]:
+        """``body_weights``: None, or one entry per clip, each None or that clip's ``[T_i, nhuman]`` (see :meth:`add`)."""
         from .utils.lafan1 import BvhRaw
-        packed = [c if isinstance(c, (np.ndarray, BvhRaw)) else self.gmr.pack_frames(c) for c in clips]
+        if body_weights is not None and len(body_weights) != len(clips):
+            raise ValueError(f"{len(body_weights)} body_weights for {len(clips)} clips")
+        if body_weights is not None and self.chunk is not None and any(w is not None for w in body_weights):
+            raise ValueError(chunking.BODY_WEIGHTS_REFUSAL)
+        bw = [None] * len(clips) if body_weights is None else [None if w is None else self.gmr.clip_body_weights(w, len(c))
+                                                               for w, c in zip(body_weights, clips)]
+        packed = [c if isinstance(c, (np.ndarray, BvhRaw)) else self.gmr.pack_frames(c, w) for c, w in zip(clips, bw)]
         if not packed:
             return []
         if self._per_clip and len(self._heights) != len(packed):
             raise ValueError(f"{len(self._heights)} heights for {len(packed)} clips")
         self.begin(max(len(p) for p in packed), len(packed), 1 << 62)
         for k, p in enumerate(packed):
-            assert self.add(p, float(self._heights[k]) if self._per_clip else None)
+            assert self.add(p, float(self._heights[k]) if self._per_clip else None, bw[k])
         return self.finish(fps)
 
 
@@ -776,8 +815,10 @@ def _set_batch_frame_limit(gmrs, frame_velocity_limit, fps) -> None:
 def retarget_clips(src_human: str, tgt_robot: str, clips: Sequence, fps: Sequence[float],
                    actual_human_height=None, height_adjust: bool = True,
                    root_origin_offset: bool = True, offset_to_ground: bool = False, chunk=None, report: Optional[List] = None,
-                   library=False, velocity_limit=None, frame_velocity_limit=None):
-    """Retarget many clips of one (source, robot, height) in ONE IK launch.  ``velocity_limit``, ``frame_velocity_limit``: see :class:`ClipRetargeter`.  ``library`` (``True`` | ``"world"`` | ``"reference"``;
+                   library=False, velocity_limit=None, frame_velocity_limit=None, body_weights=None):
+    """Retarget many clips of one (source, robot, height) in ONE IK launch.  ``body_weights``: None, or one entry per clip, each
+    None or ``[T_i, nhuman]`` per-frame body weights (0 = the body is missing in that frame: :meth:`GeneralMotionRetargeting.retarget_streams`),
+    packed into the batch beside the frames; refused (``ValueError``) together with ``chunk``.  ``velocity_limit``, ``frame_velocity_limit``: see :class:`ClipRetargeter`.  ``library`` (``True`` | ``"world"`` | ``"reference"``;
     default off): returns ``(motions, motion_library.MotionLibrary)``, the library filled on the device from the post-processed
     batch; ``motions`` are the same bytes as without it.  ``chunk`` (``chunking.ChunkSpec`` or ``"auto"``; default
     off) cuts long clips into independently running chunks -- NOT parity; the per-clip chunk reports are appended to ``report``.
@@ -791,6 +832,8 @@ def retarget_clips(src_human: str, tgt_robot: str, clips: Sequence, fps: Sequenc
     gathered into chunk jobs: with a ``chunk`` spec that takes effect the heights run as groups, one call per height as before
     (and no ``library``).
     """
+    if body_weights is not None and chunk is not None:
+        raise ValueError(chunking.BODY_WEIGHTS_REFUSAL)
     if actual_human_height is not None and np.ndim(actual_human_height) > 0:
         heights = [float(h) for h in np.asarray(actual_human_height, dtype=np.float64).reshape(-1)]
         if len(heights) != len(clips):
@@ -808,7 +851,7 @@ def retarget_clips(src_human: str, tgt_robot: str, clips: Sequence, fps: Sequenc
             return out
     rt = ClipRetargeter(src_human, tgt_robot, actual_human_height, height_adjust, root_origin_offset, offset_to_ground, chunk=chunk,
                         library=library, velocity_limit=velocity_limit, frame_velocity_limit=frame_velocity_limit)
-    out = rt(clips, fps)
+    out = rt(clips, fps) if body_weights is None else rt(clips, fps, body_weights)
     if report is not None and rt.chunk_report is not None:
         report.extend(rt.chunk_report)
     return (out, rt.library) if library else out
@@ -828,7 +871,8 @@ def retarget_mixed(groups: Sequence[Dict], offset_to_ground: bool = False, slice
     (robot, stream, chunk) items (``gmr_retarget_group``) -- and the host buffers are cut into slices whose copies
     overlap the kernels.  Bit-identical to retargeting every group by itself.
 
-    ``groups[i]`` = ``{"src_human", "tgt_robot", "human": f64[S,T,nhuman,7], optional "lens",
+    ``groups[i]`` = ``{"src_human", "tgt_robot", "human": f64[S,T,nhuman,7], optional "lens", "weights" (f64[S,T,nhuman]
+    per-frame body weights of the group's streams),
     "actual_human_height", "velocity_limit", "frame_velocity_limit", "fps"}`` (the limits as in ``GeneralMotionRetargeting``: they
     are the group's own, each job launches with its solver's tables; a frame limit needs the group's ``fps``), the height a number for the group or one per stream (``f64[S]``: the group's solver is built
     from the unscaled config and the heights travel as scale rows); arrays allocated with ``_lib.pinned_empty`` are copied asynchronously.
@@ -843,7 +887,7 @@ def retarget_mixed(groups: Sequence[Dict], offset_to_ground: bool = False, slice
                                        frame_velocity_limit=g.get("frame_velocity_limit"), fps=g.get("fps"))
         keep.append(gmr)
         jobs.append({"solver": gmr.hip_solver, "human": g["human"], "lens": g.get("lens"),
-                     "scales": gmr.stream_scales(len(g["human"]), heights=h) if per_stream else None})
+                     "scales": gmr.stream_scales(len(g["human"]), heights=h) if per_stream else None, "weights": g.get("weights")})
     flags = _lib.FLAG_OFFSET_TO_GROUND if offset_to_ground else 0
     return _lib.retarget_group(jobs, flags, slices, out_pinned=pinned_outputs)   # (rows beyond a stream's length: zeros)
 

@@ -64,6 +64,16 @@ def _quat_rotate(q, v):
     return _quat_mul(_quat_mul(q, qv), q * np.array([1.0, -1.0, -1.0, -1.0]))[1:]
 
 
+def body_weights_from_missing(human) -> np.ndarray:
+    """Body weights ``f64[..., nhuman]`` of packed frames ``human[..., nhuman, 7]``: 1 where all seven entries of a body's row
+    are finite, 0 (the body is missing in that frame) where one is not -- what ``retarget_streams(weights=)`` takes for a
+    capture with dropouts."""
+    human = np.asarray(human, dtype=np.float64)
+    if human.ndim < 2 or human.shape[-1] != 7:
+        raise ValueError(f"packed frames [..., nhuman, 7] needed, got {human.shape}")
+    return np.isfinite(human).all(axis=-1).astype(np.float64)
+
+
 class GeneralMotionRetargeting:
     """General Motion Retargeting (GMR), MI355X-native backend."""
 
@@ -206,7 +216,24 @@ class GeneralMotionRetargeting:
     # ------------------------------------------------------------------ #
     # packing of the reference's dict format (App. D) into the C-ABI layout
     # ------------------------------------------------------------------ #
-    def _check_names(self, human_data: Dict) -> None:
+    def body_weight_row(self, body_weights) -> Optional[np.ndarray]:
+        """``{body: m}`` (names not given: 1) or an array ``[nhuman]`` as the packed row ``f64[nhuman]`` of one frame's body
+        weights; None stays None.  Raises for a name that is no body of the packed layout and for a value that is not finite and
+        not negative, before anything reaches the device."""
+        if body_weights is None:
+            return None
+        if isinstance(body_weights, dict):
+            row = np.ones(len(self._human_names))
+            for n, m in body_weights.items():
+                if n not in self._human_names:
+                    raise KeyError(n)
+                row[self._human_names.index(n)] = float(m)
+        else:
+            row = np.asarray(body_weights, dtype=np.float64)
+        return _lib.check_weights(row[None, None], 1, 1, len(self._human_names), "body_weights")[0, 0]
+
+    def _check_names(self, human_data: Dict, weights: Optional[np.ndarray] = None) -> None:
+        """``weights`` (a packed row): a task body with weight 0 may be absent from the frame; the human root may not."""
         tt = self._tables
         if tt.human_root_name not in human_data:
             raise KeyError(tt.human_root_name)
@@ -221,12 +248,15 @@ class GeneralMotionRetargeting:
             if len(set(hs)) != len(hs):
                 raise TargetNotSet("two robot frames are mapped to one human body: a task has no target")
             for n in hs:
-                if n not in human_data or n not in tt.scale_table:
+                if n not in tt.scale_table:
+                    raise KeyError(n)
+                if n not in human_data and not (weights is not None and weights[self._human_names.index(n)] == 0.0):
                     raise KeyError(n)
 
-    def pack_frame(self, human_data: Dict) -> np.ndarray:
-        """dict{name: (pos, quat_wxyz)} -> f64[nhuman, 7]; bodies absent from the dict become NaN rows."""
-        self._check_names(human_data)
+    def pack_frame(self, human_data: Dict, weights: Optional[np.ndarray] = None) -> np.ndarray:
+        """dict{name: (pos, quat_wxyz)} -> f64[nhuman, 7]; bodies absent from the dict become NaN rows.  ``weights`` (the
+        frame's packed body weights): a task body whose weight is 0 may be absent."""
+        self._check_names(human_data, weights)
         out = np.full((len(self._human_names), 7), np.nan)
         for i, n in enumerate(self._human_names):
             if n in human_data:
@@ -234,20 +264,22 @@ class GeneralMotionRetargeting:
                 out[i, 3:] = human_data[n][1]
         return out
 
-    def pack_frames(self, frames: Sequence[Dict]) -> np.ndarray:
-        return np.stack([self.pack_frame(self.to_numpy(f)) for f in frames]) if len(frames) else \
-            np.zeros((0, len(self._human_names), 7))
+    def pack_frames(self, frames: Sequence[Dict], weights: Optional[np.ndarray] = None) -> np.ndarray:
+        return np.stack([self.pack_frame(self.to_numpy(f), None if weights is None else weights[i]) for i, f in enumerate(frames)]) \
+            if len(frames) else np.zeros((0, len(self._human_names), 7))
 
     # ------------------------------------------------------------------ #
     # reference API
     # ------------------------------------------------------------------ #
-    def update_targets(self, human_data, offset_to_ground=False):
+    def update_targets(self, human_data, offset_to_ground=False, body_weights=None):
         human_data = self.to_numpy(human_data)
-        self._set_frame(self.pack_frame(human_data), offset_to_ground, list(human_data.keys()))
+        w = self.body_weight_row(body_weights)
+        self._set_frame(self.pack_frame(human_data, w), offset_to_ground, list(human_data.keys()), w)
 
-    def _set_frame(self, frame, offset_to_ground, key_order=None):
-        """New targets (a packed frame): everything derived from the previous ones is stale."""
+    def _set_frame(self, frame, offset_to_ground, key_order=None, weights=None):
+        """New targets (a packed frame and, or None, its packed body weights): everything derived from the previous ones is stale."""
         self._raw_frame = frame
+        self._raw_weights = weights
         self._ground_flag = bool(offset_to_ground)
         self._key_order = key_order
         self._targets = None          # f64[nhuman, 7]: the kernel's preprocessed frame (tgt_out)
@@ -267,7 +299,7 @@ class GeneralMotionRetargeting:
         q = self.configuration.data.qpos
         _, _, status, tg, er = self.hip_solver.retarget_streams(
             q[None], self._raw_frame[None, None], flags=self._flags(self._ground_flag) | _lib.FLAG_EVAL_ONLY,
-            want_targets=True, want_errors=True)
+            want_targets=True, want_errors=True, weights=None if self._raw_weights is None else self._raw_weights[None, None])
         if status[0] != 0:
             raise RuntimeError(f"evaluation failed (status {int(status[0])})")
         self._targets, self._errors, self._errors_q = tg[0, 0], er[0, 0], q.copy()
@@ -283,7 +315,9 @@ class GeneralMotionRetargeting:
             if self._targets is None:
                 self._evaluate()
             names = self._human_names
-            rows = {n: self._targets[i] for i, n in enumerate(names) if not np.isnan(self._raw_frame[i, 0])}
+            w = self._raw_weights          # a body missing in this frame (weight 0, not the root) is dropped like an absent one
+            rows = {n: self._targets[i] for i, n in enumerate(names) if not np.isnan(self._raw_frame[i, 0])
+                    and not (w is not None and w[i] == 0.0 and n != self.human_root_name)}
             order = [self.human_root_name] + [n for n in (self._key_order or names) if n != self.human_root_name]
             self._scaled_cache = {n: [rows[n][:3].copy(), rows[n][3:].copy()] for n in order if n in rows}
         return self._scaled_cache
@@ -292,57 +326,79 @@ class GeneralMotionRetargeting:
     def scaled_human_data(self, value):
         self._scaled_cache = value
 
-    def _run(self, human, offset_to_ground, key_order=None):
-        """One launch over ``human[T, nhuman, 7]`` continuing from the current configuration; keeps the last
-        frame's targets and residual norms so that scaled_human_data / error1() / error2() refer to it."""
+    def _run(self, human, offset_to_ground, key_order=None, weights=None):
+        """One launch over ``human[T, nhuman, 7]`` (``weights[T, nhuman]``: its body weights, or None) continuing from the
+        current configuration; keeps the last frame's targets and residual norms so that scaled_human_data / error1() /
+        error2() refer to it."""
         q_out, nsolve, status, tg, er = self.hip_solver.retarget_streams(
             self.configuration.data.qpos[None], human[None],
             flags=self._flags(offset_to_ground) | (_lib.FLAG_FRAME_LIMIT_FIRST if self._frames_done else 0),
-            want_targets=True, want_errors=True)
+            want_targets=True, want_errors=True, weights=None if weights is None else weights[None])
         if status[0] != 0:
             raise RuntimeError(f"IK failed (status {int(status[0])}): QP not solvable / non-finite input")
-        self._set_frame(human[-1], offset_to_ground, key_order)
+        self._set_frame(human[-1], offset_to_ground, key_order, None if weights is None else weights[-1])
         self.configuration.data.qpos = q_out[0, -1].copy()
         self._frames_done += human.shape[0]
         self._targets, self._errors, self._errors_q = tg[0, -1], er[0, -1], q_out[0, -1].copy()
         return q_out[0], nsolve[0]
 
-    def retarget(self, human_data, offset_to_ground=False):
-        """One frame (reference :139-185): warm-started from the previous call, returns qpos f64[nq]."""
+    def retarget(self, human_data, offset_to_ground=False, body_weights=None):
+        """One frame (reference :139-185): warm-started from the previous call, returns qpos f64[nq].  ``body_weights``
+        ``{body: m}``: a multiplier on the cost of every task bound to that human body in this frame (names not given: 1);
+        ``m == 0``: the body is missing -- it may be absent from ``human_data`` or hold anything (the human root is always
+        needed), and ``scaled_human_data`` drops it."""
         human_data = self.to_numpy(human_data)
-        frame = self.pack_frame(human_data)
-        q, ns = self._run(frame[None], offset_to_ground, list(human_data.keys()))
+        w = self.body_weight_row(body_weights)
+        frame = self.pack_frame(human_data, w)
+        q, ns = self._run(frame[None], offset_to_ground, list(human_data.keys()), None if w is None else w[None])
         self.last_num_solves = ns[0].copy()
         return q[0].copy()
 
-    def retarget_packed(self, frame: np.ndarray, offset_to_ground=False) -> np.ndarray:
+    def retarget_packed(self, frame: np.ndarray, offset_to_ground=False, weights=None) -> np.ndarray:
         """:meth:`retarget` for a frame that is already packed (``f64[nhuman, 7]``, rows in
-        ``human_body_names`` order, NaN rows = absent bodies): the streaming path (utils/optitrack.py)."""
+        ``human_body_names`` order, NaN rows = absent bodies): the streaming path (utils/optitrack.py).  ``weights``
+        ``f64[nhuman]``: the frame's body weights in the same order (0 = the body is missing, its row may hold anything)."""
         frame = np.ascontiguousarray(frame, dtype=np.float64)
         if frame.shape != (len(self._human_names), 7):
             raise ValueError(f"packed frame must be [{len(self._human_names)}, 7], got {frame.shape}")
-        q, ns = self._run(frame[None], offset_to_ground)
+        w = self.body_weight_row(weights)
+        q, ns = self._run(frame[None], offset_to_ground, None, None if w is None else w[None])
         self.last_num_solves = ns[0].copy()
         return q[0].copy()
 
-    def retarget_clip(self, frames, offset_to_ground=False, chunk=None) -> np.ndarray:
+    def clip_body_weights(self, body_weights, T: int) -> Optional[np.ndarray]:
+        """A clip's body weights -- a sequence of T dicts ``{body: m}`` or an array ``[T, nhuman]`` -- as ``f64[T, nhuman]``;
+        None stays None.  Checked before anything reaches the device."""
+        if body_weights is None:
+            return None
+        if not isinstance(body_weights, np.ndarray) and len(body_weights) and isinstance(body_weights[0], dict):
+            if len(body_weights) != T:
+                raise ValueError(f"body_weights: one dict per frame needed, got {len(body_weights)} for {T} frames")
+            return np.stack([self.body_weight_row(w) for w in body_weights])
+        return _lib.check_weights(np.asarray(body_weights)[None], 1, T, len(self._human_names), "body_weights")[0]
+
+    def retarget_clip(self, frames, offset_to_ground=False, chunk=None, body_weights=None) -> np.ndarray:
         """All frames of one clip in ONE launch (time loop on device); continues from the current
         configuration exactly like calling :meth:`retarget` per frame.  ``frames`` is a sequence of
         ``human_data`` dicts or an array ``[T, nhuman, 7]``.  Returns ``qpos f64[T, nq]``.
         ``chunk`` (a ``chunking.ChunkSpec`` or ``"auto"``; default off): a clip longer than the spec's ``frames`` runs as
         independent chunks with warm-up -- NOT parity with the per-frame loop; ``self.chunk_report`` says how far off.
-        ``chunk`` is refused (``ValueError``) while a finite frame velocity limit is set."""
+        ``chunk`` is refused (``ValueError``) while a finite frame velocity limit is set, and together with ``body_weights``.
+        ``body_weights``: a list of T dicts ``{body: m}`` or an array ``[T, nhuman]`` (see :meth:`retarget`)."""
         key_order = None
+        weights = self.clip_body_weights(body_weights, len(frames))
         if isinstance(frames, np.ndarray):
             human = np.ascontiguousarray(frames, dtype=np.float64)
         else:
-            human = self.pack_frames(frames)
+            human = self.pack_frames(frames, weights)
             key_order = list(frames[-1].keys()) if len(frames) else None
         if human.shape[0] == 0:
             return np.zeros((0, self.model.nq))
         from . import chunking
         if chunk is not None and self._frame_limit_on():
             raise ValueError(chunking.FRAME_LIMIT_REFUSAL)
+        if chunk is not None and weights is not None:
+            raise ValueError(chunking.BODY_WEIGHTS_REFUSAL)
         spec = chunking.resolve_any(chunk, [human.shape[0]])
         self.chunk_report = None
         if spec is not None:
@@ -356,7 +412,7 @@ class GeneralMotionRetargeting:
             self._targets, self._errors, self._errors_q = None, None, None      # (evaluated on demand: tgt_out / err_out are not chunked)
             self.last_num_solves = ns[0].copy()
             return q[0]
-        q, ns = self._run(human, offset_to_ground, key_order)
+        q, ns = self._run(human, offset_to_ground, key_order, weights)
         self.last_num_solves = ns.copy()
         return q
 
@@ -375,7 +431,7 @@ class GeneralMotionRetargeting:
 
     def retarget_streams(self, human: np.ndarray, q0: Optional[np.ndarray] = None, lens=None,
                          offset_to_ground=False, heights=None, scales=None, want_targets: bool = False,
-                         want_errors: bool = False, q0_is_previous_frame: bool = False):
+                         want_errors: bool = False, q0_is_previous_frame: bool = False, weights=None):
         """Many independent streams ``human[S, T, nhuman, 7]`` (each from ``q0[s]``, default
         ``qpos0`` = a fresh object per clip as the dataset scripts do).  Does not touch this object's
         configuration.  Returns ``(qpos[S, T, nq], nsolve[S, T, 2], status[S])``, with ``want_targets`` /
@@ -384,14 +440,17 @@ class GeneralMotionRetargeting:
         (one human scale table per stream: per-subject limb scaling) let subjects of different sizes share this object and
         the launch; stream ``s`` then gets the bits of an object built for ``heights[s]``.
         ``q0_is_previous_frame`` (callers that resume streams): ``q0[s]`` is the pose of the frame before ``human[s, 0]``, so
-        the frame velocity limit (:meth:`set_frame_velocity_limit`) bounds frame 0 around it; by default frame 0 is free."""
+        the frame velocity limit (:meth:`set_frame_velocity_limit`) bounds frame 0 around it; by default frame 0 is free.
+        ``weights[S, T, nhuman]``: a multiplier per (stream, frame, human body) on the cost of every task bound to that body;
+        0 = the body is missing in that frame, its ``human`` row may hold anything (NaN included) and its ``targets`` row comes
+        back as NaN (:func:`body_weights_from_missing` builds such an array from the NaN rows of ``human``)."""
         S = human.shape[0]
         scales = self.stream_scales(S, heights, scales)
         if q0 is None:
             q0 = np.broadcast_to(self.model.qpos0, (S, self.model.nq)).copy()
         flags = self._flags(offset_to_ground) | (_lib.FLAG_FRAME_LIMIT_FIRST if q0_is_previous_frame else 0)
         return self.hip_solver.retarget_streams(q0, human, lens=lens, flags=flags, scales=scales,
-                                                want_targets=want_targets, want_errors=want_errors)
+                                                want_targets=want_targets, want_errors=want_errors, weights=weights)
 
     # ---- errors (reference :188-200): evaluated by the kernel ------------------------------
     def _error(self, stage: int) -> float:

@@ -72,11 +72,18 @@ class RigidBodyPacker:
             if tt.use_stage[s]:
                 need.update(tt.stages[s].human_names)
         self._required = np.array(sorted(row_of[n] for n in need if n in row_of), dtype=np.int64)
+        self._root = row_of[tt.human_root_name]
         missing_in_map = [n for n in need if n not in set(id_map.values())]
         if missing_in_map:
             raise KeyError(f"id map has no id for the bodies the IK config needs: {missing_in_map}")
 
-    def pack(self, ids: Sequence[int], pos: np.ndarray, rot_xyzw: np.ndarray) -> np.ndarray:
+    def pack(self, ids: Sequence[int], pos: np.ndarray, rot_xyzw: np.ndarray, missing: str = "raise"):
+        """``missing="raise"``: the packed frame; a frame that lacks a body the IK config needs raises ``KeyError``.
+        ``missing="drop"``: ``(frame, weights)`` with ``weights f64[nhuman]`` 0 for the needed bodies the frame lacks and 1
+        elsewhere -- what ``retarget_packed(frame, weights=)`` takes, so that an occluded body costs its tasks for that frame
+        instead of ending the stream.  A frame without the human root raises either way: every body is placed relative to it."""
+        if missing not in ("raise", "drop"):
+            raise ValueError(f'missing must be "raise" or "drop", got {missing!r}')
         ids = np.asarray(ids, dtype=np.int64)
         pos = np.asarray(pos, dtype=np.float64).reshape(-1, 3)
         rot = np.asarray(rot_xyzw, dtype=np.float64).reshape(-1, 4)
@@ -87,22 +94,34 @@ class RigidBodyPacker:
         out[rows[sel], :3] = pos[sel]
         out[rows[sel], 3] = rot[sel, 3]
         out[rows[sel], 4:] = rot[sel, :3]
-        if np.isnan(out[self._required, 0]).any():
-            lacking = [self.names[r] for r in self._required if np.isnan(out[r, 0])]
-            raise KeyError(lacking[0])                            # what retarget(dict) raises (:129,:135)
-        return out
+        lacking = [r for r in self._required if np.isnan(out[r, 0])]
+        if lacking and (missing == "raise" or self._root in lacking):
+            raise KeyError(self.names[self._root if self._root in lacking else lacking[0]])     # what retarget(dict) raises (:129,:135)
+        if missing == "raise":
+            return out
+        weights = np.ones(len(self.names))
+        weights[lacking] = 0.0
+        return out, weights
 
 
 class StreamingRetargeter:
     """The loop of ``scripts/optitrack_to_robot.py:37-46`` without the dict: one packed frame per call,
     warm-started on the device-side state of ``retargeter`` exactly like ``retarget``."""
 
-    def __init__(self, retargeter, id_map: Optional[Dict[int, str]] = None):
+    def __init__(self, retargeter, id_map: Optional[Dict[int, str]] = None, missing: str = "raise"):
+        """``missing``: what a frame that lacks a needed body does (:meth:`RigidBodyPacker.pack`): ``"raise"``, or ``"drop"``
+        = retarget the frame with that body's tasks weighted 0."""
+        if missing not in ("raise", "drop"):
+            raise ValueError(f'missing must be "raise" or "drop", got {missing!r}')
         self.retargeter = retargeter
         self.packer = RigidBodyPacker(retargeter, id_map)
+        self.missing = missing
         self.frame_number = -1
 
     def step(self, ids, pos, rot_xyzw, frame_number: Optional[int] = None, offset_to_ground: bool = False):
-        frame = self.packer.pack(ids, pos, rot_xyzw)
+        packed = self.packer.pack(ids, pos, rot_xyzw, self.missing)
+        frame, weights = packed if self.missing == "drop" else (packed, None)
         self.frame_number = self.frame_number + 1 if frame_number is None else int(frame_number)
-        return self.retargeter.retarget_packed(frame, offset_to_ground)
+        if weights is None or weights.all():
+            return self.retargeter.retarget_packed(frame, offset_to_ground)
+        return self.retargeter.retarget_packed(frame, offset_to_ground, weights)

@@ -215,6 +215,47 @@ int gmr_retarget_group_window_dev(const gmr_job_t* jobs, int njobs, int flags, i
  * |slices| windows explicitly.  Use pinned host memory (below) for the
  * copies to be asynchronous.  gmr_retarget_streams takes this path by itself for inputs of 32 MB and more. */
 int gmr_retarget_group(const gmr_job_t* jobs, int njobs, int flags, int slices);
+/* Per-frame BODY WEIGHTS on the cost side of the QP: one multiplier per (stream, frame, human body), so that a caller can say
+ * "the left wrist is occluded in frames 212-230" (weight 0) or "trust the feet more while they are in contact" (weight > 1)
+ * without editing the clip or building a second solver.
+ *
+ *   weight  f64 [S][T][nhuman] or NULL  m = weight[s][t][b], in the packed human-body order of `human`; NULL = the entry
+ *                                       points above, bit for bit
+ *
+ * Present tasks: every task k of either table whose human body is b uses w_pos[k] * m and w_rot[k] * m in that frame --
+ * one IEEE double product each, formed once per frame from the solver's own weights -- wherever the weights occur: the
+ * weighted Jacobian columns, c, and the LM term mu = lm_damping |W e|^2.  The structural pair lists of the task set depend
+ * on the configured weights only.  A body with m > 0 enters the (unweighted) residual norm of the stop rule and of err_out
+ * as it does without weights.
+ * Missing tasks, m == 0: the body is missing in that frame.  Its tasks add exact zeros to H, c and mu, and their residuals
+ * are LEFT OUT of the residual norm that the stop rule (curr - next > tol) and err_out use.  The `human` row of a missing
+ * body that is not the human root is never read into a result: it may hold NaN, zeros or garbage; it is kept out of the
+ * lowest-foot search of GMR_FLAG_OFFSET_TO_GROUND (a frame whose feet are ALL missing behaves like a frame whose feet are
+ * all NaN: out of scope); its target is the identity pose, which no output depends on; its tgt_out row is seven NaNs, the
+ * row of an absent body.  The human root's row is always read -- every other body is moved relative to it --, so a weight
+ * of 0 there removes the root's task only, and a non-finite root row fails the stream as it does without weights.
+ * A frame with every body missing is a plain damped solve: one solve per stage, q stays where it is inside its ranges.
+ * GMR_FLAG_EVAL_ONLY applies the weights to err_out and tgt_out in the same way.
+ * The host entry points reject an entry that is NaN, infinite or negative with GMR_ERR_ARG, naming stream, frame and body,
+ * before anything reaches the device (only the frames t < len[s] are looked at: rows beyond a stream's length are padding
+ * that is never read, like the human rows there); the device entry points cannot look: the values are the caller's responsibility.
+ * gmr_job_t is closed, so group launches take the arrays BESIDE the job list: `weight` is NULL or has njobs entries, each
+ * NULL or that job's array; a job without weights is not changed by a neighbour that has them.  Slices copy the rows of
+ * their streams, windows the rows of their frames (the row of frame t is found by t: no state travels between windows).
+ * The latency shape runs its instances with the velocity-limit box (+inf tables where the solver has none: the same bits),
+ * the throughput shape the group instance, alone if need be.
+ * NOT for chunked retargeting (chunking.py): the Python layer refuses chunk= together with weights. */
+int gmr_retarget_streams_weighted_dev(gmr_solver_t* solver, int S, int T, const double* d_q0, const double* d_human,
+                                      const int32_t* d_len, const double* d_scale, const double* d_weight, int flags,
+                                      double* d_q_out, int32_t* d_nsolve, int32_t* d_status, double* d_tgt_out,
+                                      double* d_err_out, void* stream);
+int gmr_retarget_streams_weighted(gmr_solver_t* solver, int S, int T, const double* q0, const double* human,
+                                  const int32_t* len, const double* scale, const double* weight, int flags, double* q_out,
+                                  int32_t* nsolve, int32_t* status, double* tgt_out, double* err_out);
+int gmr_retarget_group_weighted_dev(const gmr_job_t* jobs, int njobs, const double* const* weight, int flags, void* stream);
+int gmr_retarget_group_weighted_window_dev(const gmr_job_t* jobs, int njobs, const double* const* weight, int flags,
+                                           int t_begin, int t_end, void* stream);
+int gmr_retarget_group_weighted(const gmr_job_t* jobs, int njobs, const double* const* weight, int flags, int slices);
 /* pinned (page-locked) host memory for the host-pointer entry points; gmr_host_register pins a caller's own buffer */
 int gmr_host_alloc(void** ptr, size_t bytes);
 int gmr_host_free(void* ptr);
