@@ -18,7 +18,7 @@ LIB = os.path.join(HERE, "libgmrhip.so")
 OBJ = os.path.join(os.path.dirname(HERE), "build", "obj")
 SOURCES = ["gmr_ik.hip", "gmr_ik_wide.hip", "gmr_fk.hip", "gmr_post.hip", "gmr_smplx.hip", "gmr_bvh.hip", "gmr_chunk.hip", "gmr_motion.hip", "gmr_body_state.hip", "gmr_tracker.hip", "gmr_tracker_links.hip", "gmr_tracker_preview.hip", "gmr_tracker_adaptive.hip", "gmr_tracker_anchor.hip", "gmr_tracker_control.hip", "gmr_tracker_proprio.hip", "gmr_tracker_feet.hip", "gmr_tracker_commands.hip", "gmr_tracker_episode.hip", "gmr_tracker_rollout.hip", "gmr_tracker_loss.hip", "gmr_tracker_optim.hip", "gmr_tracker_policy.hip", "gmr_tracker_policy_bwd.hip", "gmr_comm.hip", "gmr_ik_host.hip", "gmr_abi.hip"]
 HEADERS = ["gmr_ik_wide_item.inc", "gmr_ik_wide_kernels.inc", "gmr_device_math.h", "gmr_ik_layout.h", "gmr_ik_weight_stage.h", "gmr_ik_wide_layout.h", "gmr_ik_prof.h", "gmr_ik_tree.h",
-           "gmr_fk_tree.h", "gmr_fk_walk.h", "gmr_fk_handle.h", "gmr_launch.h", "gmr_ik_stage.h", "gmr_motion_sample.h", "gmr_philox.h", "gmr_tracker_dev.h", "gmr_tracker_host.h", "gmr_tracker_policy_plan.h", "gmr_tracker_policy_bwd_plan.h", "gmr_terrain.h", "gmr_link_plan.h", "gmr_handles.h", "gmr_post.h", "gmr_internal.h", "gmr_workspace.h", "../../include/gmr_hip.h", "../../include/gmr_types.h"]
+           "gmr_fk_tree.h", "gmr_fk_walk.h", "gmr_fk_handle.h", "gmr_launch.h", "gmr_ik_stage.h", "gmr_motion_sample.h", "gmr_philox.h", "gmr_tracker_dev.h", "gmr_tracker_host.h", "gmr_tracker_policy_plan.h", "gmr_tracker_policy_bwd_plan.h", "gmr_terrain.h", "gmr_link_plan.h", "gmr_smplx_prog.h", "gmr_bvh_prog.h", "gmr_handles.h", "gmr_post.h", "gmr_internal.h", "gmr_workspace.h", "../../include/gmr_hip.h", "../../include/gmr_types.h"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC"]
 # The throughput kernel must stay within 256 registers (two wavefronts per SIMD; since round 3: 168, three).  Machine-LICM hoists every FP64
 # literal and lane predicate of the (fully inlined) frame loop into registers that live for the whole kernel; they

@@ -34,27 +34,12 @@
 // float64 arithmetic here mirrors NumPy's (one rounding per operation)
 #pragma clang fp contract(off)
 
-#define BVH_MAX_JOINTS 256
-#define BVH_MAX_STEPS 64        // joints walked: one bit each in a frame's flip mask
-#define BVH_MAX_ROWS 64
-#define BVH_BLOCK 64            // frames kernel: one wavefront, lane = frame
+#include "gmr_bvh_prog.h"          // BvhProg, bvh_make_prog, the LDS size (host-only, checked by tests/cpp/ingest_prog_check.cpp)
+
 #define BVH_SCAN_BLOCK 256
 #define BVH_SCAN_ROWS 252       // four wavefronts x 63 rows (lane 0 of each is the row below its 63)
 
 namespace gmr {
-
-struct BvhProg {
-  int n;                              // joints walked: the ancestor closure of the selection, in joint order (parents first)
-  int J, ncol, nrow, nslot;
-  int ax[3];                          // axis (0, 1, 2 = x, y, z) of the three Euler channels, in channel order
-  short joint[BVH_MAX_STEPS];         // joint index of step k
-  short rcol[BVH_MAX_STEPS];          // column of its first rotation channel
-  short pcol[BVH_MAX_STEPS];          // column of its first translation channel, or -1: the clip's offset of the joint
-  signed char load[BVH_MAX_STEPS];    // parent transform: -2 none (root), -1 the previous step's, >= 0 an LDS slot
-  signed char save[BVH_MAX_STEPS];    // slot this step's transform is parked in, or -1
-  unsigned char ent0[BVH_MAX_STEPS + 1];   // outputs of step k: ent[ent0[k] .. ent0[k + 1])
-  short ent[2 * BVH_MAX_ROWS];        // row * 2 + (0: position, 1: orientation)
-};
 
 struct bq { double w, x, y, z; };
 struct bv { double x, y, z; };
@@ -282,72 +267,20 @@ int gmr_bvh_create(int J, const int32_t* parents, int channels, const char* orde
   for (int j = 1; j < J; j++)
     if (parents[j] < 0 || parents[j] >= j) return gmr_fail(GMR_ERR_ARG, "gmr_bvh_create: parents must precede children, joint 0 is the only root (joint %d)", j);
   if (nsel < 1 || nsel > BVH_MAX_ROWS || !sel_pos || !sel_rot) return gmr_fail(GMR_ERR_ARG, "gmr_bvh_create: 1 <= nsel <= %d", BVH_MAX_ROWS);
-  std::vector<char> keep(J, 0);
-  for (int r = 0; r < nsel; r++) {
+  for (int r = 0; r < nsel; r++)
     if (sel_pos[r] < 0 || sel_pos[r] >= J || sel_rot[r] < 0 || sel_rot[r] >= J)
       return gmr_fail(GMR_ERR_ARG, "gmr_bvh_create: row %d selects joint %d / %d of %d", r, sel_pos[r], sel_rot[r], J);
-    for (int a = sel_pos[r]; a >= 0 && !keep[a]; a = parents[a]) keep[a] = 1;
-    for (int a = sel_rot[r]; a >= 0 && !keep[a]; a = parents[a]) keep[a] = 1;
-  }
   gmr_bvh* h = new (std::nothrow) gmr_bvh;
   if (!h) return gmr_fail(GMR_ERR_ARG, "out of memory");
   gmr::BvhProg& P = h->prog;
-  memset(&P, 0, sizeof P);
-  P.J = J;
-  P.ncol = channels == 3 ? 3 + 3 * J : 6 * J;
-  P.nrow = nsel;
-  for (int i = 0; i < 3; i++) P.ax[i] = ax[i];
-  std::vector<int> step_of(J, -1);
-  int n = 0;
-  for (int j = 0; j < J; j++) {
-    if (!keep[j]) continue;
-    if (n == BVH_MAX_STEPS) { delete h; return gmr_fail(GMR_ERR_ARG, "gmr_bvh_create: the selection needs more than %d joints", BVH_MAX_STEPS); }
-    step_of[j] = n;
-    P.joint[n] = (short)j;
-    P.rcol[n] = (short)(channels == 3 ? 3 + 3 * j : 6 * j + 3);
-    P.pcol[n] = (short)(channels == 3 ? (j == 0 ? 0 : -1) : 6 * j);
-    n++;
+  const gmr::BvhProgStatus ps = gmr::bvh_make_prog(J, parents, channels, ax, nsel, sel_pos, sel_rot, &P, &h->lds_bytes);
+  if (ps == gmr::BVH_PROG_STEPS) { delete h; return gmr_fail(GMR_ERR_ARG, "gmr_bvh_create: the selection needs more than %d joints", BVH_MAX_STEPS); }
+  if (ps == gmr::BVH_PROG_LDS) {
+    const int nslot = P.nslot;
+    delete h;
+    return gmr_fail(GMR_ERR_ARG, "gmr_bvh_create: %d rows and %d parked joints do not fit the LDS", nsel, nslot);
   }
-  P.n = n;
-  // parent transforms: in registers when the parent is the previous step, else parked in an LDS slot that is free again
-  // after the last child that reads it
-  std::vector<int> last_use(n, -1), slot(n, -1);
-  for (int k = 1; k < n; k++) {
-    const int pk = step_of[parents[P.joint[k]]];
-    if (pk != k - 1) last_use[pk] = k;
-  }
-  std::vector<int> busy_until;      // per slot
-  for (int k = 0; k < n; k++) {
-    P.save[k] = -1;
-    if (k == 0) {
-      P.load[k] = -2;
-    } else {
-      const int pk = step_of[parents[P.joint[k]]];
-      P.load[k] = (signed char)(pk == k - 1 ? -1 : slot[pk]);
-    }
-    if (last_use[k] >= 0) {
-      int sidx = -1;
-      for (size_t i = 0; i < busy_until.size(); i++)
-        if (busy_until[i] < k) { sidx = (int)i; break; }
-      if (sidx < 0) { sidx = (int)busy_until.size(); busy_until.push_back(0); }
-      busy_until[sidx] = last_use[k];
-      slot[k] = sidx;
-      P.save[k] = (signed char)sidx;
-    }
-  }
-  P.nslot = (int)busy_until.size();
-  int ne = 0;
-  for (int k = 0; k < n; k++) {
-    P.ent0[k] = (unsigned char)ne;
-    for (int r = 0; r < nsel; r++) {
-      if (sel_pos[r] == P.joint[k]) P.ent[ne++] = (short)(r * 2);
-      if (sel_rot[r] == P.joint[k]) P.ent[ne++] = (short)(r * 2 + 1);
-    }
-  }
-  P.ent0[n] = (unsigned char)ne;
-  h->lds_bytes = ((size_t)BVH_BLOCK * nsel * 7 + (size_t)P.nslot * 7 * BVH_BLOCK) * sizeof(double);
-  if (h->lds_bytes > 160 * 1024 - 1024) { delete h; return gmr_fail(GMR_ERR_ARG, "gmr_bvh_create: %d rows and %d parked joints do not fit the LDS", nsel, P.nslot); }
-  if (h->lds_bytes > 48 * 1024) {
+  if (h->lds_bytes > gmr::BVH_LDS_DEFAULT) {
     hipError_t e = hipFuncSetAttribute((const void*)gmr::bvh_frames_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes);
     if (e != hipSuccess) { delete h; return gmr_fail(GMR_ERR_HIP, "gmr_bvh_create: %s", hipGetErrorString(e)); }
   }

@@ -27,25 +27,9 @@
 #include "gmr_internal.h"
 #include "gmr_workspace.h"
 
-#define SX_MAX_JOINTS 64
-#define SX_BLOCK 64
+#include "gmr_smplx_prog.h"        // SmplxProg, make_prog, the LDS sizes (host-only, checked by tests/cpp/ingest_prog_check.cpp)
 
 namespace gmr {
-
-struct SmplxProg {
-  int n;                         // joints visited (DFS order)
-  int J;                         // joints per pose row
-  int nrow;                      // rows written per frame
-  int max_depth;                 // stack levels
-  short joint[SX_MAX_JOINTS];    // joint index of step k
-  short depth[SX_MAX_JOINTS];    // its depth (root = 0)
-  short row[SX_MAX_JOINTS];      // output row or -1
-  short parent[SX_MAX_JOINTS];   // parent JOINT index of step k (joints kernel: rest offsets)
-  // joints kernel: the parent's transform is the previous step's (still in registers: load = -1) or parked in an LDS slot;
-  // only joints with two or more visited children are parked (save >= 0).  SMPL-X: 3 slots instead of 11 stack levels
-  short load[SX_MAX_JOINTS], save[SX_MAX_JOINTS];
-  int nslot;
-};
 
 struct q4 { double x, y, z, w; };   // xyzw like SciPy
 
@@ -374,9 +358,6 @@ __global__ __launch_bounds__(SX_BLOCK) void smplx_joints_kernel(SmplxProg P, int
 // the search ends after log2(nclip) steps whatever they hold, the clip's range is clamped into [0, B], and a lane outside its
 // clip's clamped range returns, so every load stays inside the B-frame inputs and the scratch.  A store goes to frame o <
 // min(nout[c], N_c) of clip_out[c].
-#define SX_BODY_JOINTS 22            // root_orient + pose_body: joints 0 .. 21
-#define SX_BODY_POSE 63              // floats per pose_body row
-
 // np.linspace(0, N - 1, Nout)[o] (utils/smpl.py:127): arange(Nout) * ((N - 1) / (Nout - 1)), the last one set to N - 1
 __host__ __device__ inline double sx_target_time(int o, int N, int Nout) {
   if (Nout <= 1) return 0.0;
@@ -594,50 +575,6 @@ __global__ __launch_bounds__(SX_BLOCK) void smplx_batch_align_kernel(SmplxProg P
   }
 }
 
-// DFS program over the joints in `keep` (all when empty); rows from `row_of` (-1 = not written)
-static bool make_prog(int J, const int32_t* parents, const std::vector<char>& keep, const std::vector<int>& row_of,
-                      int nrow, SmplxProg* P) {
-  memset(P, 0, sizeof *P);
-  P->J = J;
-  P->nrow = nrow;
-  std::vector<std::vector<int>> kids(J);
-  int root = -1;
-  for (int j = 0; j < J; j++) {
-    if (parents[j] < 0) { if (root >= 0) return false; root = j; }
-    else kids[parents[j]].push_back(j);
-  }
-  if (root < 0) return false;
-  std::vector<std::pair<int, int>> st;     // (joint, depth)
-  st.push_back({root, 0});
-  int n = 0, md = 0;
-  while (!st.empty()) {
-    auto [j, d] = st.back();
-    st.pop_back();
-    if (!keep[j]) continue;
-    P->joint[n] = (short)j; P->depth[n] = (short)d; P->row[n] = (short)row_of[j];
-    P->parent[n] = (short)(parents[j] < 0 ? 0 : parents[j]);
-    n++;
-    md = std::max(md, d + 1);
-    for (int c = (int)kids[j].size() - 1; c >= 0; c--) st.push_back({kids[j][c], d + 1});
-  }
-  P->n = n;
-  P->max_depth = md;
-  // parking slots of the joints kernel: slot of a joint = the number of parked ancestors above it
-  std::vector<int> nkept(J, 0), parked_above(J, 0), slot_of(J, -1);
-  for (int k = 0; k < n; k++) if (k > 0) nkept[P->parent[k]]++;
-  int ns = 0;
-  for (int k = 0; k < n; k++) {
-    const int j = P->joint[k], p = P->parent[k];
-    parked_above[j] = k == 0 ? 0 : parked_above[p] + (nkept[p] >= 2 ? 1 : 0);
-    P->save[k] = -1;
-    if (nkept[j] >= 2) { slot_of[j] = parked_above[j]; P->save[k] = (short)slot_of[j]; ns = std::max(ns, slot_of[j] + 1); }
-    P->load[k] = (short)((k == 0 || P->joint[k - 1] == p) ? -1 : slot_of[p]);
-    if (k > 0 && P->joint[k - 1] != p && slot_of[p] < 0) return false;      // (cannot happen in DFS preorder)
-  }
-  P->nslot = std::max(ns, 1);
-  return true;
-}
-
 }  // namespace gmr
 
 struct gmr_smplx {
@@ -668,49 +605,30 @@ int gmr_smplx_create(int J, const int32_t* parents, int nsel, const int32_t* sel
   if (!h) return gmr_fail(GMR_ERR_ARG, "out of memory");
   h->J = J;
   h->nsel = nsel;
-  std::vector<char> keep(J, 1);
-  std::vector<int> row(J);
-  for (int j = 0; j < J; j++) row[j] = j;
-  bool ok = gmr::make_prog(J, parents, keep, row, J, &h->all);
-  if (ok && nsel > 0) {
-    std::fill(keep.begin(), keep.end(), 0);
-    std::fill(row.begin(), row.end(), -1);
-    for (int r = 0; r < nsel && ok; r++) {
-      int j = sel[r];
-      if (j < 0 || j >= J || row[j] >= 0) { ok = false; break; }
-      row[j] = r;
-      for (int a = j; a >= 0; a = parents[a]) keep[a] = 1;
-    }
-    ok = ok && gmr::make_prog(J, parents, keep, row, nsel, &h->sel);
-  } else if (ok) {
-    h->sel = h->all;
-  }
+  const bool ok = gmr::smplx_make_progs(J, parents, nsel, sel, &h->all, &h->sel);
   if (!ok) { delete h; return gmr_fail(GMR_ERR_ARG, "gmr_smplx_create: bad tree or duplicate / out-of-range selection"); }
-  const int lds_align = h->all.max_depth * 4 * SX_BLOCK * 8, lds_joints = std::max(h->all.nslot - 1, 1) * 12 * SX_BLOCK * 8;
-  if (lds_joints > 160 * 1024 - 1024) { delete h; return gmr_fail(GMR_ERR_ARG, "gmr_smplx_create: tree too deep (%d levels)", h->all.max_depth); }
+  const gmr::SmplxLds lds = gmr::smplx_lds(h->all, h->sel, nsel);
+  const int lds_align = lds.align, lds_joints = lds.joints;
+  if (lds_joints > gmr::SX_LDS_LIMIT) { delete h; return gmr_fail(GMR_ERR_ARG, "gmr_smplx_create: tree too deep (%d levels)", h->all.max_depth); }
   hipError_t e = hipSuccess;
-  if (lds_align > 48 * 1024) {
+  if (lds_align > gmr::SX_LDS_DEFAULT) {
     e = hipFuncSetAttribute((const void*)gmr::smplx_align_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_align);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gmr::smplx_align_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_align);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gmr::smplx_align_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_align);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gmr::smplx_align_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_align);
   }
-  if (e == hipSuccess && lds_joints > 48 * 1024)
+  if (e == hipSuccess && lds_joints > gmr::SX_LDS_DEFAULT)
     {
     e = hipFuncSetAttribute((const void*)gmr::smplx_joints_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_joints);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gmr::smplx_joints_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_joints);
   }
-  // the batch entry points read root_orient + pose_body, the poses of joints 0 .. 21
-  h->batch_ok = nsel > 0;
-  for (int k = 0; k < h->sel.n; k++)
-    if (h->sel.joint[k] >= SX_BODY_JOINTS) h->batch_ok = false;
-  h->batch_nslot_lds = std::max(h->sel.nslot - 1, 1);
-  h->batch_lds_joints = h->batch_nslot_lds * 12 * SX_BLOCK * 8 + SX_BLOCK * SX_BODY_POSE * (int)sizeof(float);
-  h->batch_lds_align = h->sel.max_depth * 4 * SX_BLOCK * 8;
-  if (h->batch_lds_joints > 160 * 1024 - 1024) h->batch_ok = false;
-  if (e == hipSuccess && h->batch_ok && h->batch_lds_joints > 48 * 1024)
+  h->batch_ok = lds.batch_ok;
+  h->batch_nslot_lds = lds.batch_nslot;
+  h->batch_lds_joints = lds.batch_joints;
+  h->batch_lds_align = lds.batch_align;
+  if (e == hipSuccess && h->batch_ok && h->batch_lds_joints > gmr::SX_LDS_DEFAULT)
     e = hipFuncSetAttribute((const void*)gmr::smplx_batch_joints_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, h->batch_lds_joints);
-  if (e == hipSuccess && h->batch_ok && h->batch_lds_align > 48 * 1024)
+  if (e == hipSuccess && h->batch_ok && h->batch_lds_align > gmr::SX_LDS_DEFAULT)
     e = hipFuncSetAttribute((const void*)gmr::smplx_batch_align_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, h->batch_lds_align);
   if (e == hipSuccess) e = h->jrest.reserve((size_t)J * 3 * sizeof(double));
   if (e != hipSuccess) { delete h; return gmr_fail(GMR_ERR_HIP, "gmr_smplx_create: %s", hipGetErrorString(e)); }

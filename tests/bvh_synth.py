@@ -16,12 +16,13 @@ def all_names(raw):
     return list(raw.names) + ["LeftFootMod", "RightFootMod"]
 
 
-def make_raw(T, seed=0, channels=3, order="zyx", toggles=(), base=None, offset_scale=1.0):
+def make_raw(T, seed=0, channels=3, order="zyx", toggles=(), base=None, offset_scale=1.0, pos_scale=20.0):
     """A clip of T frames on the golden topology: smooth Euler angles that wrap through +-180 degrees (every wrap of a
     rotation channel flips the sign of the joint's quaternion) plus, at the frames in ``toggles``, a 360 degree step of
-    every joint's first rotation channel (a flip of every joint at exactly that frame)."""
+    every joint's first rotation channel (a flip of every joint at exactly that frame).  ``base``: another skeleton
+    (:func:`skeleton_raw`); ``pos_scale``: the spread of the translation channels in centimetres."""
     from general_motion_retargeting_amd.utils import lafan1
-    base = base or golden_raw()
+    base = golden_raw() if base is None else base        # (an empty clip is falsy)
     rng = np.random.default_rng(seed)
     J = len(base.parents)
     t = np.arange(T, dtype=np.float64)[:, None, None]
@@ -33,7 +34,7 @@ def make_raw(T, seed=0, channels=3, order="zyx", toggles=(), base=None, offset_s
         if 0 <= f < T:
             step[f:] = 360.0 - step[f:]
     eul[:, :, 0] += step[:, None]
-    pos = rng.normal(size=(T, J, 3)) * 20.0
+    pos = rng.normal(size=(T, J, 3)) * pos_scale
     if channels == 3:
         rows = np.concatenate([pos[:, 0], eul.reshape(T, J * 3)], axis=1)
     else:
@@ -45,6 +46,28 @@ def make_raw(T, seed=0, channels=3, order="zyx", toggles=(), base=None, offset_s
 def host_packed(raw, body_names):
     from general_motion_retargeting_amd.utils import lafan1
     return lafan1.packed_from_raw(raw, body_names)
+
+
+def skeleton_raw(parents, seed=0, offset_sd=10.0):
+    """An empty clip on any topology (joints ``j000`` ...), rest offsets N(0, offset_sd) centimetres: the ``base`` of
+    :func:`make_raw` for skeletons that have no feet to name."""
+    from general_motion_retargeting_amd.utils import lafan1
+    J = len(parents)
+    rng = np.random.default_rng([seed, J])
+    return lafan1.BvhRaw([f"j{j:03d}" for j in range(J)], np.asarray(parents, dtype=np.int32), rng.normal(0.0, offset_sd, size=(J, 3)), 3, "zyx",
+                         1.0 / 30.0, np.zeros((0, 3 + 3 * J)))
+
+
+def host_packed_sel(raw, sel_pos, sel_rot):
+    """:func:`host_packed` for rows given as (position joint, orientation joint) pairs -- what ``gmr_bvh_create`` takes --: the
+    functions ``lafan1.packed_from_raw`` goes through (``bvh_from_raw``, ``quat_fk``, its Y-up cm -> Z-up m step) without the two
+    ``FootMod`` rows, which need joints called LeftFoot, LeftToe, RightFoot and RightToe."""
+    from general_motion_retargeting_amd.utils import lafan1
+    data = lafan1.bvh_from_raw(raw)
+    grot, gpos = lafan1.quat_fk(data.quats, data.pos, data.parents)
+    orient = lafan1._quat_mul(np.broadcast_to(lafan1._ROT_QUAT, grot.shape), grot)
+    position = gpos @ lafan1._ROT.T / 100
+    return np.concatenate([position[:, list(sel_pos)], orient[:, list(sel_rot)]], axis=-1)
 
 
 def write_bvh(path, names, parents, offsets, rows, frametime=1.0 / 30.0):
